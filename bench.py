@@ -245,13 +245,15 @@ class Leg:
         self.name, self.train, self.bf16, self.split = name, train, bf16, split  # split: the opt-in split-fp32 inference mode (model.split_mlp)
 
 
-def run_leg(leg, model, inputs, K, steps, warmup, dist, dev, bucket, time_allreduce=True, warmup_seconds=0.0, profile=True):
+def run_leg(leg, model, inputs, K, steps, warmup, dist, dev, bucket, time_allreduce=True, warmup_seconds=0.0, profile=True, outputs=None):
     """W untimed + K timed steps of one configuration, bracketed by barrier + synchronize; returns (elapsed s [max over
     ranks], per-kernel HIP-event profile of the library, all-reduce ms per step or None).  time_allreduce=False: no event pair around the
     collective (two markers per step on the stream are not free at a 0.5 ms step).  warmup_seconds: keep warming up (untimed) for that
     long -- the small-batch legs follow 4096-ray fp32 legs in the same process, and a few sub-millisecond steps are not enough for the
     clocks to settle at the lighter load's own level.  profile=False: the library records no HIP events around its kernels (two markers per
-    kernel are 3-4 % of a sub-millisecond step; the 4096-ray legs, which the roofline needs live events for, do not notice them)."""
+    kernel are 3-4 % of a sub-millisecond step; the 4096-ray legs, which the roofline needs live events for, do not notice them).
+    outputs: a dict to fill with what the LAST timed step returned to its caller (host float32 copies, taken after the timed region):
+    forward C_coarse / C_fine; train step C_coarse / C_fine / loss and one grad_<parameter name> per network tensor."""
     import torch
 
     from nerf_tiny_amd import _abi
@@ -269,11 +271,12 @@ def run_leg(leg, model, inputs, K, steps, warmup, dist, dev, bucket, time_allred
                 for p in model.network.parameters():
                     p.grad = None
             if FUSED_TRAIN_STEP:  # nerf.py:470-473 (forward, ray_loss, backward) as ONE library call: what NeRFRunner.trainer makes
-                model.train_step(row, col, pb, K, C_true)
+                res = model.train_step(row, col, pb, K, C_true)
             else:                 # --autograd-step: the reference's three calls through torch.autograd (same kernels)
                 Cc, Cf = model(row, col, pb, K)
                 loss = model.ray_loss(Cc, Cf, C_true)
                 loss.backward()
+                res = (Cc, Cf, loss)
             if bucket is not None and dist is not None:  # data-parallel trainer: ONE flat 2.27 MiB SUM all-reduce over RCCL/xGMI
                 if timed and time_allreduce:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -284,9 +287,9 @@ def run_leg(leg, model, inputs, K, steps, warmup, dist, dev, bucket, time_allred
                     ar_events.append((e0, e1))
             elif bucket is not None:
                 bucket.consume()  # no collective in this run: the gradients count as used
-        else:
-            with torch.no_grad():
-                model(row, col, pb, K)
+            return res
+        with torch.no_grad():
+            return model(row, col, pb, K)
 
     def fence():
         torch.cuda.synchronize()
@@ -314,10 +317,14 @@ def run_leg(leg, model, inputs, K, steps, warmup, dist, dev, bucket, time_allred
             _abi.profile_begin(steps * 40 + 40)
         t0 = time.perf_counter()
         for _ in range(steps):
-            step(True)
+            last = step(True)
         fence()
         elapsed = time.perf_counter() - t0
         prof = _abi.profile_end() if profile else {}
+        if outputs is not None:  # before any later call can reuse the gradient bucket
+            outputs.update((n, t.detach().float().cpu().numpy()) for n, t in zip(("C_coarse", "C_fine", "loss"), last))
+            if leg.train:
+                outputs.update(("grad_" + n, p.grad.detach().float().cpu().numpy()) for n, p in model.named_parameters())
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -593,6 +600,7 @@ def parity_block(model, dev):
 # the result line: compact (<= LINE_LIMIT bytes) for the driver; the full record goes to bench_extra.json beside this script
 # --------------------------------------------------------------------------------------------------------------------
 LINE_LIMIT = 4096
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes in all
 SIDE_FILE = "bench_extra.json"
 
 
@@ -732,12 +740,18 @@ def main():
     ap.add_argument("--side-file", default=None, help="where the full record goes (default: bench_extra.json beside this script); the stdout line "
                                                       "is the compact <= 4 KB form of it")
     ap.add_argument("--dry", action="store_true", help="CPU rehearsal of the launcher + process group over gloo (no kernels; tests only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last timed step returned (rank 0) as DIR/<name>.npy, float32: "
+                         "C_coarse, C_fine [4096, 3]; train: also loss and grad_<parameter> (2.4 MB).  Inputs and weights are seeded: "
+                         "two runs with the same arguments see the same inputs")
     args = ap.parse_args()
 
     global FUSED_TRAIN_STEP
     FUSED_TRAIN_STEP = not args.autograd_step
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         # parent of an N-rank job: nothing below this line runs here, in particular no torch.cuda / HIP call
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -814,7 +828,15 @@ def main():
     if args.split and args.mlp == "bf16":
         raise SystemExit("--split is the split-fp32 mode (inference: model.split_mlp, train step: model.split_train): not with --mlp bf16")
     head = Leg("headline", args.mode == "train", args.mlp == "bf16", args.split)
-    elapsed, prof, ar_ms = run_leg(head, model, inputs, K, args.steps, args.warmup, dist, dev, bucket)
+    dumped = {} if args.dump_outputs else None
+    elapsed, prof, ar_ms = run_leg(head, model, inputs, K, args.steps, args.warmup, dist, dev, bucket, outputs=dumped)
+    if dumped is not None and rank == 0:
+        import numpy as np
+
+        assert sum(a.nbytes for a in dumped.values()) <= DUMP_LIMIT, "bench.py: --dump-outputs would write more than 64 MB"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     rep = leg_report(head, elapsed, prof, ar_ms, args.steps, args.warmup, world, b_local, strong)
     extra = {}
     # (name, train, bf16, timed steps, warm-up steps): every leg is timed over >= 0.1 s

@@ -38,6 +38,13 @@ def test_mismatched_world_size_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
 
 
+def test_zero_timed_steps_are_refused():
+    """ms_per_step is elapsed / --steps: a run with no timed step has no such number"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry"], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode != 0 and "--steps" in (r.stderr + r.stdout)
+
+
 def test_train_traffic_lookup_matches_the_shipped_kernel_names():
     """bench.py reads the weight-gradient phase's HBM bytes from the committed PMC summary by kernel name: a renamed kernel
     (or a summary collected before the rename) would silently turn `roofline.traffic` into null."""

@@ -111,6 +111,31 @@ def test_bench_default_line_carries_the_per_rank_proxy(tmp_path):
 
 
 @pytest.mark.timeout(900)
+@pytest.mark.parametrize("mode", ["forward", "train"])
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path, mode):
+    """--dump-outputs DIR: the headline leg's last timed step as float32 .npy files (forward: C_coarse / C_fine; train step: also loss and
+    one grad_<parameter> per network tensor), at most 64 MB in all.  The inputs are seeded, so a second run with the same arguments writes
+    the same arrays bit for bit; --steps is the number of timed steps of the line."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        d = str(tmp_path / f"dump{i}")
+        line, _ = _bench(["--mode", mode, "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--dump-outputs", d], _env(), tmp_path)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = runs
+    grads = [k for k in a if k.startswith("grad_network.")]
+    assert set(a) == {"C_coarse", "C_fine"} | ({"loss", *grads} if mode == "train" else set())
+    assert len(grads) == (24 if mode == "train" else 0)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["C_coarse"].shape == a["C_fine"].shape == (4096, 3)
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+
+
+@pytest.mark.timeout(900)
 def test_bench_two_ranks_rehearsed_on_one_gpu(tmp_path):
     """The driver's N > 1 command (`python bench.py --gpus 2 ...`: this process launches the ranks itself) has never met a multi-GPU node.
     Rehearsed here with BOTH ranks on the one GPU of the box and gloo in RCCL's place (BENCH_DIST_BACKEND=gloo): the launcher, per-rank
