@@ -72,13 +72,6 @@ bool pair_bf16(int B) {
   static const int forced = [] { const char* e = getenv("NERF_PAIR_BF16"); return e ? atoi(e) : -1; }();
   return forced >= 0 ? forced != 0 : B <= PAIR_BF16_MAX_RAYS;
 }
-// large batches: the small-block products of the bf16 weight-gradient phase in one launch (see nerf_hip_backward_overlap).
-// NERF_DW_BF16_SMALLGROUP=0 / 1 / 2 selects the variant (A/B measurements); default below
-constexpr int DW_BF16_SMALL_GROUP_DEFAULT = 2;  // measured (weight-gradient phase): 2,048 rays 0.767 -> 0.707 ms, 4,096 rays 1.375 -> 1.36; variant 1: +-0
-int dw_bf16_small_group() {
-  static const int v = [] { const char* e = getenv("NERF_DW_BF16_SMALLGROUP"); return e ? atoi(e) : DW_BF16_SMALL_GROUP_DEFAULT; }();
-  return v;
-}
 // bf16 training: the per-ray stages as epilogues / prologues of the field launches up to this many rays (one round of fine-pass workgroups:
 // the stage runs on a quarter of a workgroup's waves).  NERF_FUSE_RAYS=0 / 1 overrides the choice (A/B measurements only)
 constexpr int FUSE_RAYS_BF16_MAX_RAYS = 512;
@@ -97,8 +90,7 @@ bool dw_bf16_multi(int wb_tot) {
 // head, + the thin colour head -- in launch order, with their slab offsets; pointers are filled in by nerf_hip_backward (null
 // here: only sizes matter for the layout).
 constexpr int DW_EARLY_ITEMS = 9;  // layers 1..7, layer 4's skip columns, layer 0 = every tensor of point_layer[0..7]
-long long build_dw_batch(DwBatch& b, const float* G, const float* save, const float* dz4, size_t MS, float* const* dw, float* mbuf,
-                         bool grouped = true) {
+long long build_dw_batch(DwBatch& b, const float* G, const float* save, const float* dz4, size_t MS, float* const* dw, float* mbuf) {
   memset(&b, 0, sizeof(b));
   auto add = [&](const float* g, int nout, const float* x, int nin, int nin_real, float* dW, int ldw, int col0, float* db) -> DwItem& {
     DwItem& it = b.item[b.n++];
@@ -121,7 +113,7 @@ long long build_dw_batch(DwBatch& b, const float* G, const float* save, const fl
   th.thin = 1; th.db2 = D(B_SIGMA);
   // The seven 256 x 256 products share one launch with DW_GROUP_WGS workgroups each (dw_f32.hip: k_dw4_group); every other product
   // gets ALL DW_WGS workgroups in a launch of its own.
-  b.grouped = grouped ? 7 : 0;
+  b.grouped = 7;
   long long off = 0;
   for (int i = 0; i < b.n; ++i) {
     b.item[i].nwg = i < b.grouped ? DW_GROUP_WGS : DW_WGS;
@@ -729,10 +721,10 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
     // LARGE batches, the products with SMALL blocks (layer 0: 20 KiB per wave block, the folded dir_info product 28, the colour head 10): alone
     // in a launch each is paced by the ring's per-block latency (3.4 / 4.3 / 3.8 TB/s against the 5.8 of the 256 x 256 products:
     // profiles/r03_train_bf16_pmc.json); sharing ONE launch (k_dw_bf16_multi, workgroups dealt out by cost) their streams overlap.
-    // Variant 1: six | layer 4 | {layer 0, folded, colour}; 2: six | {layer 4, layer 0, folded, colour}; 0: a launch each (round 3).
+    // The six 256 x 256 products, then {layer 4, layer 0, folded, colour} in one launch; measured (weight-gradient phase) against a launch
+    // each: 2,048 rays 0.767 -> 0.707 ms, 4,096 rays 1.375 -> 1.36 (layer 4 in a launch of its own: +-0).
     // Without an early event only (the overlap needs layer 0 in front of the event and the other two behind it).
-    const int small_group = ev ? 0 : dw_bf16_small_group();
-    if (small_group) {
+    if (!ev) {
       static const int layers[6] = {1, 2, 3, 5, 6, 7};
       const unsigned char* Gs[6];
       const unsigned char* Xs[6];
@@ -741,32 +733,20 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
       for (int k = 0; k < 6; ++k)
         red(slabs + (size_t)k * ns * 256 * 257, ns, 256, 256, 0, 256, 0, WIDTH, dwp[2 * layers[k]], WIDTH, 0, dwp[2 * layers[k] + 1]);
       slabs += (size_t)6 * ns * 256 * 257;
-      DwBfProd pr[4];
-      memset(pr, 0, sizeof(pr));
-      int n = 0, i_l4 = -1;
-      if (small_group == 1) {
-        HIP_TRY(launch_dw_bf16_gemm(Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, wb_tot, slabs, &ns, st, sp));
-        red(slabs, ns, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
-        slabs += (size_t)ns * 256 * 321;
-      } else {
-        i_l4 = n;
-        pr[n++] = DwBfProd{Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, nullptr, 0};
-      }
-      const int i_l0 = n;
-      pr[n++] = DwBfProd{Gt(BG_L0), 16, X(BS_GP), 4, nullptr, 0, nullptr, nullptr, 0};
-      const int i_d = n;
-      pr[n++] = DwBfProd{Gt(BG_D), 8, X(BS_GD), 2, X(BS_H0 + 7), 16, Gt(BG_Z), nullptr, 0};
-      const int i_c = n;
-      pr[n++] = DwBfProd{Gt(BG_Z), 2, X(BS_C), 8, nullptr, 0, nullptr, nullptr, 0};
+      DwBfProd pr[4] = {
+          DwBfProd{Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, nullptr, 0},       // 0: layer 4, X = [h3 | gamma_p]
+          DwBfProd{Gt(BG_L0), 16, X(BS_GP), 4, nullptr, 0, nullptr, nullptr, 0},                  // 1: layer 0 (X = gamma_p)
+          DwBfProd{Gt(BG_D), 8, X(BS_GD), 2, X(BS_H0 + 7), 16, Gt(BG_Z), nullptr, 0},             // 2: folded dir_info product + sigma head
+          DwBfProd{Gt(BG_Z), 2, X(BS_C), 8, nullptr, 0, nullptr, nullptr, 0}};                    // 3: colour head
       float* end = slabs;
-      HIP_TRY(launch_dw_bf16_multi(pr, n, wb_tot, slabs, slab_limit, &end, st, sp));
-      if (i_l4 >= 0) red(pr[i_l4].slabs, pr[i_l4].nslab, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
-      red(pr[i_l0].slabs, pr[i_l0].nslab, 256, 64, 0, 256, 0, POINT_DIM, dwp[0], POINT_DIM, 0, dwp[1]);
-      red(pr[i_d].slabs, pr[i_d].nslab, 160, 288, 0, HALF, 0, DIR_DIM, dwp[W_DIR], WIDTH + DIR_DIM, 0, dwp[B_DIR]);
-      red(pr[i_d].slabs, pr[i_d].nslab, 160, 288, 0, HALF, 32, WIDTH, mbuf, WIDTH, 0, nullptr);
-      red(pr[i_d].slabs, pr[i_d].nslab, 160, 288, HALF + 3, 1, 32, WIDTH, dwp[W_SIGMA], WIDTH, 0, nullptr);
-      red(pr[i_c].slabs, pr[i_c].nslab, 32, 128, 0, 3, 0, HALF, dwp[W_COLOR], HALF, 0, dwp[B_COLOR]);
-      red(pr[i_c].slabs, pr[i_c].nslab, 32, 128, 3, 1, 0, 0, nullptr, 0, 0, dwp[B_SIGMA]);
+      HIP_TRY(launch_dw_bf16_multi(pr, 4, wb_tot, slabs, slab_limit, &end, st, sp));
+      red(pr[0].slabs, pr[0].nslab, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
+      red(pr[1].slabs, pr[1].nslab, 256, 64, 0, 256, 0, POINT_DIM, dwp[0], POINT_DIM, 0, dwp[1]);
+      red(pr[2].slabs, pr[2].nslab, 160, 288, 0, HALF, 0, DIR_DIM, dwp[W_DIR], WIDTH + DIR_DIM, 0, dwp[B_DIR]);
+      red(pr[2].slabs, pr[2].nslab, 160, 288, 0, HALF, 32, WIDTH, mbuf, WIDTH, 0, nullptr);
+      red(pr[2].slabs, pr[2].nslab, 160, 288, HALF + 3, 1, 32, WIDTH, dwp[W_SIGMA], WIDTH, 0, nullptr);
+      red(pr[3].slabs, pr[3].nslab, 32, 128, 0, 3, 0, HALF, dwp[W_COLOR], HALF, 0, dwp[B_COLOR]);
+      red(pr[3].slabs, pr[3].nslab, 32, 128, 3, 1, 0, 0, nullptr, 0, 0, dwp[B_SIGMA]);
       HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
       FoldGradArgs fg;
       fg.M = mbuf; fg.db_dir = dwp[B_DIR]; fg.w_dir = w.p[W_DIR]; fg.w_pi = w.p[W_PI]; fg.b_pi = w.p[B_PI];
@@ -831,7 +811,7 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   } else {
     ProfScope ps(NERF_HIP_K_BWD_DW, st, &pc);
     DwBatch batch;
-    build_dw_batch(batch, G, save, at<float>(ws, L.dz), MS, dw, at<float>(ws, L.mbuf), Mtot <= DW_GROUP_MAX_ROWS);
+    build_dw_batch(batch, G, save, at<float>(ws, L.dz), MS, dw, at<float>(ws, L.mbuf));
     float* slabs = at<float>(ws, L.slabs);
     batch.slabs = slabs;
 #ifdef NERF_STAMPS

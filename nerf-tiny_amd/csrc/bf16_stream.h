@@ -18,10 +18,7 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3)))* lptr_t;
 
-#ifndef NERF_BF_NS  // (timing experiments only: ring depth of the forward stream)
-#define NERF_BF_NS 8
-#endif
-constexpr int BF_NS = NERF_BF_NS;  // LDS ring slots of the forward kernel (a stream description names its own: S::NS)
+constexpr int BF_NS = 8;        // LDS ring slots of the forward kernel (a stream description names its own: S::NS)
 constexpr int BF_SYNC_POS = 8;  // fragment position inside a chunk at which the next chunk is published
 constexpr int BF_D = 6;         // fragment reads in flight per wave (<= BF_CHUNK - BF_SYNC_POS); a stream names its own: S::D
 constexpr int BF_EPI_POS = 2;   // k-step of the next tile at which a finished accumulator is consumed
@@ -97,9 +94,6 @@ struct BfCtx {
 // Inline asm on purpose: hipcc treats a builtin LDS-DMA as a pending write to the whole LDS array and drains the load
 // queue (vmcnt(0)) in front of unrelated ds_reads; hidden from it, the loads are ordered by bf_sync's counted waits alone.
 __device__ __forceinline__ void glds16(const unsigned char* gsrc, unsigned lds_dst) {
-#ifdef NERF_TIMING_NO_DMA  // (timing experiments only)
-  return;
-#endif
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
@@ -111,13 +105,7 @@ __device__ __forceinline__ void glds16(const unsigned char* gsrc, unsigned lds_d
 // gigabytes per step) with the non-temporal hint: measured 3 % on the whole bf16 train step against plain stores (forward-with-saves
 // 0.93 -> 0.87 ms, chains 0.96 -> 0.91, and the weight-gradient kernels that follow 1.45 -> 1.38: less dirty data parked in L2).
 __device__ __forceinline__ void store_piece(unsigned char* dst, const u32x4& v) {
-#if defined(NERF_SAVE_STORE_SC1)    // (timing experiment: write-through, line dropped from L2)
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-#elif defined(NERF_SAVE_STORE_PLAIN)  // (timing experiment)
-  *reinterpret_cast<u32x4*>(dst) = v;
-#else
   __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
-#endif
 }
 
 // this wave's two 1-KiB pieces of chunk c -> ring slot c % S::NS  (S::RING_OFF = LDS offset of the ring)
@@ -151,12 +139,8 @@ __device__ __forceinline__ constexpr int bf_wait_count(int c) {
 // executed by every wave at fragment position BF_SYNC_POS of chunk c
 template <class S, int chunk>
 __device__ __forceinline__ void bf_sync(const BfCtx& c) {
-#ifndef NERF_TIMING_NO_WAIT                   // (timing experiments only)
   wait_vmcnt<bf_wait_count<S>(chunk)>();     // my pieces of chunk + 1 are in LDS ...
-#endif
-#ifndef NERF_TIMING_NO_BARRIER               // (timing experiments only: results are wrong without it)
   __builtin_amdgcn_s_barrier();              // ... and so are everybody's; everybody is past chunk - 1
-#endif
   asm volatile("" ::: "memory");             // no LDS read may be moved above the barrier by the compiler
   if (chunk + S::NS - 1 < S::NCHUNK) bf_dma_chunk<S>(c, chunk + S::NS - 1);  // into the slot of chunk - 1
 }
@@ -230,9 +214,7 @@ __device__ __forceinline__ void bf_segment(const BfCtx& c, u32x4 (&fr)[S::D], f3
     constexpr int cur = (P0 + f) & 1, oth = (P0 + f + 1) & 1;
     if constexpr (idx % BF_CHUNK == BF_SYNC_POS) bf_sync<S, idx / BF_CHUNK>(c);
     const u32x4 a = fr[idx % S::D];
-#ifndef NERF_TIMING_NO_FRAG  // (timing experiments only)
     if constexpr (idx + S::D < S::NFRAG) fr[idx % S::D] = bf_frag<S>(c, idx + S::D);
-#endif
     if constexpr (ks < KSA)
       acc[cur] = bf_mfma(a, inA[ks], acc[cur]);
     else

@@ -17,8 +17,6 @@
 // The kernel is HBM-bound by construction (1 KiB of operands per 128 kFLOP): it is paced by the ring, not by the MFMAs.
 #include "bf16_stream.h"
 
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace nerf {
@@ -122,26 +120,13 @@ __device__ __forceinline__ void dw_bf16_body(const DwBfArgs& a, unsigned char* l
       const long long gd = mid ? a.gdelta : 0, xd = mid ? a.xdelta : 0;
       const unsigned char* src;
       int ks, dst;
-      // (timing experiments only, results wrong: NERF_TIMING_DW_HALF_G / _X read every second piece twice -> half the distinct bytes of
-      // that operand reach HBM, the instruction stream and the LDS image stay as they are: the upper bound of what a design that moves
-      // half the bytes -- alternate-layer recompute for X, zero-compaction for both -- could gain in this phase)
-#ifdef NERF_TIMING_DW_HALF_G
-#define DWB_GSRC(k) ((k) >> 1)
-#else
-#define DWB_GSRC(k) (k)
-#endif
-#ifdef NERF_TIMING_DW_HALF_X
-#define DWB_XSRC(k) ((k) >> 1)
-#else
-#define DWB_XSRC(k) (k)
-#endif
       if (pc < gks) {
         ks = pc; dst = ks;
-        src = gG + gd + ((size_t)wb * gks + DWB_GSRC(ks)) * BF_FRAG_BYTES;
+        src = gG + gd + ((size_t)wb * gks + ks) * BF_FRAG_BYTES;
       } else if (pc < gks + XKS) {
         const int x = pc - gks;
         ks = x; dst = 16 + x;  // parity of the slot piece = parity of x (x1_ks is even)
-        src = (x < x1 ? gX1 + ((size_t)wb * x1 + DWB_XSRC(x)) * BF_FRAG_BYTES : a.X2 + ((size_t)wb * (XKS - x1) + DWB_XSRC(x - x1)) * BF_FRAG_BYTES) + xd;
+        src = (x < x1 ? gX1 + ((size_t)wb * x1 + x) * BF_FRAG_BYTES : a.X2 + ((size_t)wb * (XKS - x1) + (x - x1)) * BF_FRAG_BYTES) + xd;
       } else {
         ks = pc - gks - XKS; dst = 16 + XKS + ks;
         src = a.Z + gd + ((size_t)wb * 2 + ks) * BF_FRAG_BYTES;
@@ -416,18 +401,12 @@ hipError_t launch_dw_bf16_multi(DwBfProd* p, int n, int wb_tot, float* slab_base
   m.n = n;
   // cost of a product per wave block = its KiB, weighted by how far below the big products' rate its shape streams (small blocks are paced
   // by the ring's per-block latency: profiles/r03_train_bf16_pmc.json -- 256 x 256 products 5.8 TB/s, layer 4 5.4, the folded product 4.3,
-  // colour head 3.8, layer 0 3.4); NERF_DW_BF16_COST=0: plain bytes (A/B measurements only)
-  static const bool by_cost = [] { const char* e = getenv("NERF_DW_BF16_COST"); return !(e && atoi(e) == 0); }();
-  // NERF_DW_BF16_COSTS="l0,col,fold,l4" (per cent; tuning sweeps only) replaces the shape factors below
-  static const struct Costs { int l0, col, fold, l4; } costs = [] {
-    Costs c{170, 150, 135, 107};
-    if (const char* e = getenv("NERF_DW_BF16_COSTS")) sscanf(e, "%d,%d,%d,%d", &c.l0, &c.col, &c.fold, &c.l4);
-    return c;
-  }();
+  // colour head 3.8, layer 0 3.4); the factors in per cent
+  constexpr struct { int l0, col, fold, l4; } costs = {170, 150, 135, 107};
   int pieces[DwBfMulti::MAXP], total = 0;
   for (int i = 0; i < n; ++i) {
     const int kib = p[i].g_ks + p[i].x1_ks + p[i].x2_ks + (p[i].Z ? 2 : 0), xks = p[i].x1_ks + p[i].x2_ks;
-    const int pct = !by_cost ? 100 : xks == 4 ? costs.l0 : xks == 8 ? costs.col : (xks == 18 && p[i].Z) ? costs.fold : xks == 20 ? costs.l4 : 100;
+    const int pct = xks == 4 ? costs.l0 : xks == 8 ? costs.col : (xks == 18 && p[i].Z) ? costs.fold : xks == 20 ? costs.l4 : 100;
     pieces[i] = kib * pct;
     total += pieces[i];
   }

@@ -19,10 +19,7 @@
 
 namespace nerf {
 
-#ifndef NERF_BB_NS  // (timing experiments only: ring depth of the chain's stream)
-#define NERF_BB_NS 5
-#endif
-constexpr int BB_NS = NERF_BB_NS;
+constexpr int BB_NS = 5;  // LDS ring slots of the chain's stream
 constexpr int BB_MASK_BYTES = 8 * BM_LAYERS * 1024;  // per workgroup: wave w, layer l at (w * 9 + l) * 1024
 constexpr int BB_LDS_BYTES = BB_MASK_BYTES + BB_NS * BF_CHUNK * BF_FRAG_BYTES;
 
@@ -76,11 +73,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwd
   const int m = blockIdx.x * (32 * WAVES) + c.wv * 32 + j;
   const bool valid = m < a.M;
   const int mc = valid ? m : a.M - 1;
-#ifdef NERF_TIMING_SAVE_ALIAS  // (timing experiments only: masks read from / gradients written to the same few KiB)
-  const int wb = c.wv;
-#else
   const int wb = a.wb0 + blockIdx.x * WAVES + c.wv;
-#endif
 
   // ---- SMALL batches (kernels.h BwdFuse): the per-ray backward stage that would be the launch in FRONT of this one runs here first, on the
   // workgroup's own rays (32 WAVES samples = 1 or 2 fine rays, 2 or 4 coarse rays); its outputs (d rgb, d sigma, d t of the samples) go to
@@ -138,9 +131,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwd
   // `lane16` = this lane's byte offset inside a piece; the epilogues pass one produced at THEIR program point (lane_id_here): an
   // address register kept from the prologue lives across the whole stream -- the allocator parked five of them in scratch
   auto grad_piece = [&](int tensor, int ks, const u32x4& v, unsigned lane16) {
-#ifdef NERF_TIMING_G_HALF  // (timing experiments only, results wrong: half the distinct gradient bytes reach HBM)
-    ks >>= 1;
-#endif
     store_piece(a.bG + ((size_t)a.wb_tot * bg_cum(tensor) + (size_t)wb * bg_ks(tensor) + ks) * BF_FRAG_BYTES + lane16, v);
   };
   grad_piece(BG_Z, 0, zin[0], lane * 16);

@@ -11,12 +11,8 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 // kernels, 8 GB per step) with the non-temporal hint: measured 1.1 % on the fp32 train step (19.37 -> 19.16 ms; the fine chain
 // 4.50 -> 4.36 ms) against plain stores -- as for the bf16 saves (bf16_stream.h), less dirty data parked in L2.
 __device__ __forceinline__ void store_row4(float* dst, const float4& v) {
-#ifdef NERF_F32_PLAIN_SAVES  // (timing experiment)
-  *reinterpret_cast<float4*>(dst) = v;
-#else
   const f32x4v q = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(q, reinterpret_cast<f32x4v*>(dst));
-#endif
 }
 
 // Weight-fragment loads of the register-streaming kernels (field_fwd_reg.hip, field_bwd_reg.hip) as BUFFER loads: address = resource

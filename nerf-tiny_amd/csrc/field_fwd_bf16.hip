@@ -104,11 +104,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
       if (pi < 30) {
         const int cc = pi / 10, l = pi - 10 * cc;
         const float x = (cc == 0) ? p[0] : ((cc == 1) ? p[1] : p[2]);
-#ifdef NERF_TIMING_NO_SINCOS  // (timing experiments only)
-        sv = x; cv = x * 0.5f;
-#else
         sincos_phase(x * __uint_as_float(kFreqPointBits[l]), sv, cv);
-#endif
       }
       gp[ks][q] = pack2(sv, cv);
     }
@@ -121,37 +117,18 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
       if (pi < 12) {
         const int cc = pi / 4, l = pi - 4 * cc;
         const float x = (cc == 0) ? dw[0] : ((cc == 1) ? dw[1] : dw[2]);
-#ifdef NERF_TIMING_NO_SINCOS
-        sv = x; cv = x * 0.5f;
-#else
         sincos_phase(x * __uint_as_float(kFreqDirBits[l]), sv, cv);
-#endif
       }
       gd[ks][q] = pack2(sv, cv);
     }
 
   // ---- training: this wave's block of the fragment-layout save buffers (bf16_common.h); every lane stores, also
   // lanes beyond the pass (they hold a copy of the last sample): the counted waits rely on the stores being issued
-#ifdef NERF_TIMING_SAVE_ALIAS  // (timing experiments only: every save lands in the same few KiB -> the stores issue, HBM sees none)
-  const int wb = c.wv;
-#else
   const int wb = a.wb0 + blockIdx.x * WAVES + c.wv;
-#endif
   unsigned mw[4];  // (every word is assigned by its even tile before the odd one ORs into it; words 2, 3 of a 4-tile layer are written as 0)
   // `lane16` = this lane's byte offset inside a piece.  The layers' epilogues pass a value produced AT their program point (mbcnt): left
   // alone the compiler forms every layer's 64-bit store address in the prologue and parks them -- and the lane pointer -- in scratch
-  // (timing experiments only, results wrong -- DESIGN.md section 9: NERF_TIMING_SAVE_HALF writes every second piece of a saved tensor over its
-  // neighbour, i.e. half the distinct bytes reach HBM -- what zero-compaction could at most take out of this kernel; NERF_TIMING_SAVE_SKIPALT
-  // sends h1, h3, h5, h7 to one aliased KiB per wave -- what alternate-layer recompute in the weight-gradient kernels would not write)
   auto save_piece = [&](int tensor, int ks, const u32x4& v, unsigned lane16) {
-#if defined(NERF_TIMING_SAVE_HALF)
-    ks >>= 1;
-#elif defined(NERF_TIMING_SAVE_SKIPALT)
-    if (tensor == BS_H0 + 1 || tensor == BS_H0 + 3 || tensor == BS_H0 + 5 || tensor == BS_H0 + 7) {
-      store_piece(a.bsave + (size_t)c.wv * BF_FRAG_BYTES + lane16, v);
-      return;
-    }
-#endif
     store_piece(a.bsave + ((size_t)a.wb_tot * bs_cum(tensor) + (size_t)wb * bs_ks(tensor) + ks) * BF_FRAG_BYTES + lane16, v);
   };
   if (SAVE) {
@@ -177,13 +154,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
   // epilogue of a ReLU layer: tile f -> packed k-steps 2f, 2f+1 of the next layer's input; training: + save + alive mask
   auto relu_to = [&](u32x4* out, int tensor = -1, int mlayer = -1, int ntiles = 8) {
     return [&, out, tensor, mlayer, ntiles](int f, const f32x16& A) {
-#ifdef NERF_TIMING_NO_EPI  // (timing experiments only: no conversion, half the values dropped)
-      if (f >= 0) {
-        for (int mh = 0; mh < 2; ++mh)
-          for (int q = 0; q < 4; ++q) out[2 * f + mh][q] = __float_as_uint(A[8 * mh + 2 * q]) & 0x3f803f80u;
-        return;
-      }
-#endif
 #pragma unroll
       for (int mh = 0; mh < 2; ++mh)
 #pragma unroll

@@ -38,8 +38,6 @@ struct BxStream {
   static constexpr int PROLOGUE_STORES = 0;
   __device__ static constexpr int stores_before(int) { return 0; }
 };
-// The two-column form (NH = 4): ONE wave per SIMD holds 64 samples (four 16-sample groups, 512 registers), 4 waves = the same 256
-// samples per workgroup and per pass over the weight image, but every fragment read from LDS feeds FOUR MFMAs instead of two.
 struct BxStream4 : BxStream {
   static constexpr int PW = 4;  // 16 pieces of a chunk over 4 waves
 };
@@ -48,6 +46,7 @@ struct BxStream4 : BxStream {
 template <int WAVES> struct BxStreamOf { using type = BxStream; };
 template <> struct BxStreamOf<4> { using type = BxStream4; };
 
+// NH = 16-sample groups per wave: 2 is shipped; 4, the two-column form, was measured and not adopted
 template <int NH> struct AccN { f32x4 c[NH]; };  // one 16-feature tile for the wave's NH 16-sample groups
 
 __device__ __forceinline__ f32x4 bx_mfma(const u32x4& a, const u32x4& b, const f32x4& c) {
@@ -543,9 +542,6 @@ hipError_t launch_pack_weights_bf16x(const Weights24& w, const float* fold, unsi
   return hipGetLastError();
 }
 
-#ifndef NERF_BX_GROUPS  // 16-sample groups per wave: 2 = two waves per SIMD, 4 = the two-column form (make variant DEFS=-DNERF_BX_GROUPS=..)
-#define NERF_BX_GROUPS 2
-#endif
 template <int NH, int WAVES>
 static hipError_t bx_launch(const FieldArgs& a, hipStream_t st) {
   static std::atomic<unsigned long long> opted{0};
@@ -557,12 +553,8 @@ static hipError_t bx_launch(const FieldArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_field_fwd_bf16x(const FieldArgs& a, hipStream_t st) {
-  constexpr int NH = NERF_BX_GROUPS;
-  if constexpr (NH == 4) return bx_launch<4, 4>(a, st);
-#ifndef NERF_BX_NO_SMALL
   // a pass of at most 256 x 128 samples: 4-wave workgroups, so that every CU gets one
   if ((a.M + 127) / 128 <= BX_SMALL_MAX_WGS) return bx_launch<2, 4>(a, st);
-#endif
   return bx_launch<2, 8>(a, st);
 }
 

@@ -112,17 +112,6 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
           acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(cur.w[f], s), b, acc[f], 0, 0, 0);
       }
     }
-#ifdef NERF_FWD_SAVE_SPREAD  // (variant build only -- `make variant NAME=spread DEFS=-DNERF_FWD_SAVE_SPREAD`: the activation's stores one per 8 MFMAs instead of
-                             // one burst.  Measured round 5: +10 % on this kernel -- 865 instead of 131 s_nops of hazard padding per tile)
-    if (SAVE && NFT == 8 && (kb & 3) == 2 && (kb >> 2) + 1 < KT) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);   // 8 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 24, 0);  // the VALU work of a quarter of the tile
-        __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);   // 1 vector-memory store
-      }
-    }
-#endif
   }
   if (KB & 1) st0 = st1;  // (all segments have an even number of k-blocks: the next k-block 0 already sits in st0)
 }
@@ -205,11 +194,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
 
   // training: where this lane's rows / mask words go (rows of the coarse pass first, then the fine pass)
   const size_t MS = (size_t)a.MSrows * WIDTH;
-#ifdef NERF_TIMING_SAVE_ALIAS  // (timing experiments only: every save lands in the dump rows -> the stores issue, HBM sees none)
-  const long long rrow = a.Mtot + j;
-#else
   const long long rrow = valid ? (long long)(a.row0 + m) : a.Mtot + j;  // lanes past the end: dump row
-#endif
   float* const srow = SAVE ? a.save + (size_t)rrow * WIDTH + 4 * h : nullptr;
   uint16_t* const mrow = SAVE ? a.masks + ((size_t)(a.tile0 + (m0 >> 6)) * 4 + ((m0 >> 5) & 1)) * 256 + h * 32 + j : nullptr;
   const size_t MKS = (size_t)a.tiles_tot * 4 * 256;

@@ -378,7 +378,7 @@ def _variant(tmp_path, name, env_extra, B=96):
 
     from conftest import ROOT
 
-    env = {k: v for k, v in os.environ.items() if k not in ("NERF_PREP_BF16", "NERF_DW_BF16_MULTI", "NERF_PAIR_BF16", "NERF_BF16_4WAVE", "NERF_DW_BF16_SMALLGROUP", "NERF_FUSE_RAYS")}
+    env = {k: v for k, v in os.environ.items() if k not in ("NERF_PREP_BF16", "NERF_DW_BF16_MULTI", "NERF_PAIR_BF16", "NERF_BF16_4WAVE", "NERF_FUSE_RAYS")}
     env.update(env_extra)
     out = str(tmp_path / (name + ".pt"))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tools", "bf16_variant_dump.py"), out, str(B)], capture_output=True, text=True,
