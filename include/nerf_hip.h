@@ -42,8 +42,9 @@
 extern "C" {
 #endif
 
-#define NERF_HIP_ABI_VERSION 6 /* 2: NERF_HIP_BF16_MLP, nerf_hip_field_bf16; 3: nerf_hip_backward_overlap, NERF_HIP_SPLIT_MLP;
-                                  4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED */
+#define NERF_HIP_ABI_VERSION 7 /* 2: NERF_HIP_BF16_MLP, nerf_hip_field_bf16; 3: nerf_hip_backward_overlap, NERF_HIP_SPLIT_MLP;
+                                  4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED;
+                                  7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid */
 
 enum {
   NERF_HIP_OK = 0,
@@ -222,6 +223,31 @@ int nerf_hip_adam_step(float* const* params24, const float* const* grads24, floa
  * pix_val [B,3] and poses_bound [B,17] f32 -- the tuple nerf.py:458 iterates over, already on the device. */
 int nerf_hip_gather_rays(const int64_t* index, const float* pixels, const float* poses17, int B, int H, int W,
                          int64_t* row, int64_t* col, int64_t* pic, float* pix_val, float* poses_bound, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The trained field at explicit points: density grids (occupancy, marching cubes, empty-space culling) and colour probes.
+ * Same register-resident exact-fp32 kernel as the forward's field passes, fed with points instead of ray samples: results are
+ * bit-identical to the forward's at the same point and direction.  The model's flags do not apply (no bf16 / split-fp32 variant).
+ * Enqueue-only; each call packs its own weight image into `ws` (a query workspace, never a forward's).  Accurate for |p_c| <= 320:
+ * the encoding's phase reduction holds its error below 1e-10 rad up to 2^20 rad, and the largest point frequency is 1024 pi.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) for the two calls below: packed weight image, fold and, with_rgb != 0, the direction
+ * vectors of one chunk of points.  Independent of M and of the grid size. */
+int nerf_hip_query_ws_bytes(int with_rgb, size_t* bytes);
+
+/* Network + Encoder (nerf.py:101-124, 135-167) at explicit points: sigma[M] from points[M,3] (world frame).
+ * dirs[M,3] (unit, world frame, NOT renormalised, as Encoder consumes them) and rgb[M,3] are both NULL (sigma only, 7,744 of the
+ * 8,256 MFMAs of a sample) or both set (colour too; ws sized with with_rgb = 1).  M == 0 succeeds and launches nothing;
+ * M < 0 is refused. */
+int nerf_hip_query(const float* const* weights24, const float* points, const float* dirs, int M,
+                   float* rgb, float* sigma, void* ws, size_t ws_bytes, void* stream);
+
+/* sigma at the lattice points lo + (i, j, k) * step (HOST lo3 / step3; each coordinate lo_c + (float)i_c * step_c with the
+ * product and the sum rounded separately), written C-order [nx][ny][nz] (z fastest).  Every dimension >= 1 and
+ * nx * ny * nz < 2^31.  No points buffer is formed: a 512^3 grid needs only its 512 MiB of sigma. */
+int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz,
+                          float* sigma, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NERF_HIP_LIB", os.path.join(_HERE, "libnerf_hip.so"))  # override: diagnostic builds only
 
-NERF_HIP_ABI_VERSION = 6
+NERF_HIP_ABI_VERSION = 7
 SAVE_FOR_BACKWARD = 1 << 0
 FORCE_TILE_KERNEL = 1 << 1
 BF16_MLP = 1 << 2
@@ -44,6 +44,9 @@ _PROTOS = {
     "nerf_hip_coarse_composite": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "nerf_hip_coarse_composite_backward": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "nerf_hip_merge_composite": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p]),
+    "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),
+    "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -80,6 +83,13 @@ def check(rc: int) -> None:
 def ws_bytes(B: int, Nc: int, Nf: int, flags: int) -> int:
     n = C.c_size_t(0)
     check(lib().nerf_hip_ws_bytes(B, Nc, Nf, flags, C.byref(n)))
+    return int(n.value)
+
+
+def query_ws_bytes(with_rgb: bool) -> int:
+    """Workspace bytes of nerf_hip_query / nerf_hip_density_grid (independent of the number of points)."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_query_ws_bytes(1 if with_rgb else 0, C.byref(n)))
     return int(n.value)
 
 

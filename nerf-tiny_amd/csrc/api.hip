@@ -1092,3 +1092,113 @@ int nerf_hip_merge_composite(const float* t_c, const float* t_f, const float* si
 }
 
 }  // extern "C"
+
+namespace {
+
+// Workspace of the point queries: the packed weight image, the fold, and (colour queries) the dvec rows of ONE chunk of QUERY_CHUNK points.
+// Nothing in it depends on the number of points or the grid size.
+struct QueryLayout {
+  size_t packed, fold, dvec, total;
+};
+QueryLayout query_layout(bool rgb) {
+  QueryLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  L.packed = take((size_t)PACKED_ALL_F4 * 16);  // (the extent the register kernels' buffer resource declares: reg_buf)
+  L.fold = take((size_t)FOLD_FLOATS * 4);
+  L.dvec = rgb ? take((size_t)QUERY_CHUNK * HALF * 4) : 0;
+  L.total = o;
+  return L;
+}
+
+int check_query_ws(const QueryLayout& L, const void* ws, size_t ws_bytes) {
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L.total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+  return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_query_ws_bytes(int with_rgb, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  *bytes = query_layout(with_rgb != 0).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_query(const float* const* weights24, const float* points, const float* dirs, int M, float* rgb, float* sigma, void* ws,
+                   size_t ws_bytes, void* stream) {
+  if (M < 0) return fail(NERF_HIP_ERR_ARG, "M=%d < 0", M);
+  if ((dirs == nullptr) != (rgb == nullptr)) return fail(NERF_HIP_ERR_ARG, "dirs and rgb must both be null (sigma only) or both be set");
+  const bool with_rgb = dirs != nullptr;
+  if (M == 0) return NERF_HIP_OK;
+  if (int rc = check_weights(weights24)) return rc;
+  if (!points || !sigma) return fail(NERF_HIP_ERR_ARG, "null argument");
+  const QueryLayout L = query_layout(with_rgb);
+  if (int rc = check_query_ws(L, ws, ws_bytes)) return rc;
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Weights24 w = as_w24(weights24);
+  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.wp = at<float4>(ws, L.packed);
+  fa.w = w;
+  QuerySrc q;
+  memset(&q, 0, sizeof(q));
+  if (!with_rgb) {
+    fa.sigma = sigma;
+    fa.M = M;
+    q.points = points;
+    HIP_TRY(launch_query_reg(fa, q, false, st));
+    return NERF_HIP_OK;
+  }
+  // colour: chunk by chunk through the workspace's dvec rows (stream order: a chunk's rows are consumed before the next chunk writes them)
+  fa.dvec = at<float>(ws, L.dvec);
+  for (int off = 0; off < M; off += QUERY_CHUNK) {
+    const int n = (M - off < QUERY_CHUNK) ? M - off : QUERY_CHUNK;
+    HIP_TRY(launch_dirs_dvec(dirs + (size_t)off * 3, n, w.p[W_DIR], w.p[B_DIR], at<float>(ws, L.fold), at<float>(ws, L.dvec), st));
+    fa.rgb = rgb + (size_t)off * 3;
+    fa.sigma = sigma + off;
+    fa.M = n;
+    q.points = points + (size_t)off * 3;
+    HIP_TRY(launch_query_reg(fa, q, true, st));
+    if (M - off <= QUERY_CHUNK) break;  // (off + QUERY_CHUNK could pass INT_MAX)
+  }
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, float* sigma,
+                          void* ws, size_t ws_bytes, void* stream) {
+  if (nx < 1 || ny < 1 || nz < 1) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: every dimension must be positive", nx, ny, nz);
+  // the kernels index points with 32-bit integers, as the forward does its samples
+  if ((long long)nx * ny * nz >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: a grid must stay below 2^31 points", nx, ny, nz);
+  if (int rc = check_weights(weights24)) return rc;
+  if (!lo3 || !step3 || !sigma) return fail(NERF_HIP_ERR_ARG, "null argument");
+  const QueryLayout L = query_layout(false);
+  if (int rc = check_query_ws(L, ws, ws_bytes)) return rc;
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Weights24 w = as_w24(weights24);
+  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.wp = at<float4>(ws, L.packed);
+  fa.w = w;
+  fa.sigma = sigma;
+  fa.M = nx * ny * nz;
+  QuerySrc q;
+  memset(&q, 0, sizeof(q));
+  for (int c = 0; c < 3; ++c) {
+    q.lo[c] = lo3[c];
+    q.step[c] = step3[c];
+  }
+  q.ny = ny;
+  q.nz = nz;
+  HIP_TRY(launch_query_reg(fa, q, false, st));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"

@@ -13,7 +13,8 @@
 //     k-block = 32 MFMAs = 2048 cycles ahead, also across layer boundaries);
 //   * biases enter as one extra MFMA per tile (A = bias, B = 1 on lane half 0); the sigma and colour heads are
 //     VALU dot products over the registers the wave already holds.
-// One wave per SIMD (about 400 VGPRs).  Used when nothing has to be saved for backward.
+// One wave per SIMD (about 400 VGPRs).  Used when nothing has to be saved for backward, and for the point queries (k_field_fwd_reg's
+// SRC / RGB template arguments below).
 #include "field_common.h"
 
 namespace nerf {
@@ -136,8 +137,16 @@ __device__ __forceinline__ void bias_load(const float* __restrict__ bias, int la
 #define RSTAMP(slot) do { } while (0)
 #endif
 
-template <bool SAVE, bool DEBUG>
-__global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
+// Where a wave's 32 samples come from.  SRC_RAYS: a ray record and a depth per sample (sample_point; the forward passes, q unused).
+// SRC_POINTS / SRC_LATTICE: the point queries (nerf_hip_query / nerf_hip_density_grid) -- sample m IS point m (no ray record, one
+// dvec row per point): p = q.points[m], or the lattice point q.lo + (i, j, k) * q.step of m = (i * ny + j) * nz + k.
+// RGB = false: sigma only -- the folded point_info / dir_info layer (512 of the 8,256 MFMAs per tile) and the colour head are skipped.
+// The query forms are template arguments of THIS kernel rather than a shared inline body: moving the body into a function changes the
+// register allocation of the forward instantiations, and these must stay instruction for instruction what they were.
+enum { SRC_RAYS = 0, SRC_POINTS = 1, SRC_LATTICE = 2 };
+
+template <bool SAVE, bool DEBUG, int SRC = SRC_RAYS, bool RGB = true>
+__global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, const QuerySrc q) {
 #ifdef NERF_STAMPS
   unsigned long long tsum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = __builtin_readcyclecounter();
@@ -147,8 +156,8 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
   const int m = m0 + j;
   const bool valid = m < a.M;
   const int mc = valid ? m : a.M - 1;
-  const int ray = mc / a.N;
-  const float* rf = a.rayf + (size_t)ray * RAYF;
+  const int ray = (SRC == SRC_RAYS) ? mc / a.N : mc;  // (the row of dvec)
+  const float* rf = (SRC == SRC_RAYS) ? a.rayf + (size_t)ray * RAYF : nullptr;
   const float4* wp = a.wp;
   const RegBuf rb = reg_buf(a.wp, threadIdx.x);  // (64-thread workgroups: threadIdx.x is the lane)
 
@@ -159,7 +168,18 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
   // ---- sample point and its encoding, straight into B-operand registers:
   // gp[t][4g + s] = gamma_p[k], k = 32t + 8g + 4h + s  (4 consecutive k = two (sin, cos) pairs)
   float p[3];
-  sample_point(rf, a.t[mc], p);
+  if constexpr (SRC == SRC_RAYS) {
+    sample_point(rf, a.t[mc], p);
+  } else if constexpr (SRC == SRC_POINTS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = q.points[(size_t)mc * 3 + c];
+  } else {  // C order, z fastest; product and sum rounded separately (-ffp-contract=off): p is lo + (float)i * step bit for bit
+    const int iz = mc % q.nz, ixy = mc / q.nz;
+    const int iy = ixy % q.ny, ix = ixy / q.ny;
+    p[0] = q.lo[0] + (float)ix * q.step[0];
+    p[1] = q.lo[1] + (float)iy * q.step[1];
+    p[2] = q.lo[2] + (float)iz * q.step[2];
+  }
   if (DEBUG && a.pts_dbg && valid && h == 0) {
     a.pts_dbg[(size_t)m * 3 + 0] = p[0];
     a.pts_dbg[(size_t)m * 3 + 1] = p[1];
@@ -232,7 +252,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
   bias_load<8>(a.w.p[13], lane, bv);
   reg_layer<32, 8, 32, 8, true, true, SAVE>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_relu(5), rb);
   bias_load<8>(a.w.p[15], lane, bv);
-  reg_layer<32, 8, 32, 4, true, true, SAVE>(sL5 + 2 * L256, seg_off4(SEG_FOLD), lane, A, B, st0, bv, sv_relu(6), rb);
+  reg_layer<32, 8, 32, 4, true, true, SAVE>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_relu(6), rb);
   RSTAMP(4);  // layers 5..7 (3,096 MFMAs)
   // ---- sigma head on h7 = relu(B) (VALU): sigma = |w_sigma . h7 + b|  (nerf.py:94, 115)
   {
@@ -268,6 +288,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
     }
   }
   RSTAMP(5);  // sigma head
+  if constexpr (!RGB) return;
   // ---- point_info (256 -> 256, no activation) and dir_info's feature columns as ONE 128 x 256 layer on h7 (common.h SEG_FOLD):
   // c = relu(W_fold h7 + dvec), dvec (per ray) = b_dir + W_dir[:, :24] gamma_d + W_dir[:, 24:] b_pi = the accumulator start
   {
@@ -325,11 +346,23 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a) {
 hipError_t launch_field_fwd_reg(const FieldArgs& a, bool save, hipStream_t st) {
   const int tiles = (a.M + RM - 1) / RM;
   if (save)
-    hipLaunchKernelGGL((k_field_fwd_reg<true, false>), dim3(tiles), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_field_fwd_reg<true, false>), dim3(tiles), dim3(64), 0, st, a, QuerySrc{});
   else if (a.pts_dbg || a.gp_dbg)
-    hipLaunchKernelGGL((k_field_fwd_reg<false, true>), dim3(tiles), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_field_fwd_reg<false, true>), dim3(tiles), dim3(64), 0, st, a, QuerySrc{});
   else
-    hipLaunchKernelGGL((k_field_fwd_reg<false, false>), dim3(tiles), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false>), dim3(tiles), dim3(64), 0, st, a, QuerySrc{});
+  return hipGetLastError();
+}
+
+hipError_t launch_query_reg(const FieldArgs& a, const QuerySrc& q, bool rgb, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  const unsigned tiles = (unsigned)(((long long)a.M + RM - 1) / RM);
+  if (q.points == nullptr)
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_LATTICE, false>), dim3(tiles), dim3(64), 0, st, a, q);
+  else if (rgb)
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, true>), dim3(tiles), dim3(64), 0, st, a, q);
+  else
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, false>), dim3(tiles), dim3(64), 0, st, a, q);
   return hipGetLastError();
 }
 

@@ -55,6 +55,17 @@ struct FieldArgs {
   unsigned long long* stamps;  // diagnostic build (-DNERF_STAMPS) only: [8] cycle sums per phase
 };
 
+// Point queries (nerf_hip_query / nerf_hip_density_grid; k_field_fwd_reg's SRC_POINTS / SRC_LATTICE forms): sample m of the launch is
+// point m.  The FieldArgs of such a launch use wp, w, dvec ([M][128], one row per point; colour queries only), rgb, sigma and M.
+struct QuerySrc {
+  const float* points;     // [M][3] world points, or null: the lattice below
+  float lo[3], step[3];    // lattice point (i, j, k) = lo + (i, j, k) * step, each coordinate one product and one sum
+  int ny, nz;              // lattice: m = (i * ny + j) * nz + k (C order, z fastest)
+};
+// Colour queries run in chunks of this many points: the dvec rows of one chunk live in the workspace (independent of M), and a chunk is
+// 8 waves for every SIMD of the chip (256 CUs x 4 SIMDs x 32 points x 8) at the kernel's one wave per SIMD.
+constexpr int QUERY_CHUNK = 256 * 4 * 32 * 8;
+
 // saved by the forward: h0..h7, c, gamma_p (feat = point_info's output is not saved: with point_info folded into dir_info no weight
 // gradient needs it, see common.h SEG_FOLD)
 constexpr int S_H0 = 0, S_C = 8, S_GP = 9, NSAVE = 10;
@@ -127,6 +138,9 @@ hipError_t launch_pack_weights(const Weights24& w, float* fold, float4* out, int
 hipError_t launch_fold_weights(const Weights24& w, float* fold, hipStream_t st);  // fold: FOLD_FLOATS (b_fold, then W_fold): bf16-MLP variant
 hipError_t launch_field_fwd(const FieldArgs& a, bool save, hipStream_t st);
 hipError_t launch_field_fwd_reg(const FieldArgs& a, bool save, hipStream_t st);
+hipError_t launch_query_reg(const FieldArgs& a, const QuerySrc& q, bool rgb, hipStream_t st);  // rgb: colour and sigma (q.points, a.dvec set), else sigma
+// dir_info start vectors of n points from their directions: dvec[i][128] as k_rays forms them from a ray's world direction (ray_ops.hip)
+hipError_t launch_dirs_dvec(const float* dirs, int n, const float* w_dir, const float* b_dir, const float* b_fold, float* dvec, hipStream_t st);
 hipError_t launch_field_fwd_bf16(const FieldArgs& a, bool save, hipStream_t st, const FwdFuse* fuse = nullptr);
 // the bf16 packers read the fp32 fold (launch_fold_weights, same stream, before them)
 hipError_t launch_pack_weights_bf16(const Weights24& w, const float* fold, unsigned char* img, hipStream_t st);

@@ -91,6 +91,26 @@ __device__ __forceinline__ void ray_record(const RaysArgs& a, const int ray, flo
 // coarse depth i of a ray (nerf.py:288: numpy.linspace(near, far, Nc) in fp32 -- separate multiply and add, the end point exact)
 __device__ __forceinline__ float coarse_depth(float near, float far, float step, int i, int Nc) { return (i == Nc - 1) ? far : ((float)i * step + near); }
 
+// The start vector of the folded dir_info layer for one world direction dw[3] (a ray's, or a queried point's), by 128 consecutive threads
+// (tid = 0..127, thread o writes out[o]): out[o] = (b_dir[o] + W_dir[o][:24] . gamma_d(dw)) (+ b_fold[o]).  gamma_d goes through LDS
+// (gd: DIR_DIM floats per group); ends in a __syncthreads(): every thread of the block must call this.
+__device__ __forceinline__ void dvec_block(const float* dw, const float* w_dir, const float* b_dir, const float* b_fold, const int tid,
+                                           float* gd, float* out) {
+  if (tid < 12) {
+    const int c = tid >> 2, l = tid & 3;
+    const float ph = dw[c] * __uint_as_float(kFreqDirBits[l]);
+    gd[c * 8 + 2 * l] = sinf(ph);
+    gd[c * 8 + 2 * l + 1] = cosf(ph);
+  }
+  __syncthreads();
+  const float* wr = w_dir + (size_t)tid * (WIDTH + DIR_DIM);
+  float s = b_dir[tid];
+#pragma unroll
+  for (int k = 0; k < DIR_DIM; ++k) s = __builtin_fmaf(wr[k], gd[k], s);
+  if (b_fold) s += b_fold[tid];  // point_info's bias through dir_info's feature columns (common.h SEG_FOLD)
+  out[tid] = s;
+}
+
 // one ray by 128 consecutive threads (tid = 0..127 inside the group); the dvec part ends in a __syncthreads(): with a.dvec every thread
 // of the block must call this
 __device__ __forceinline__ void ray_block(const RaysArgs& a, const int ray, const int tid, float* gd /* LDS, DIR_DIM floats per group */) {
@@ -112,21 +132,7 @@ __device__ __forceinline__ void ray_block(const RaysArgs& a, const int ray, cons
   if (a.t_c) {
     for (int i = tid; i < a.Nc; i += 128) a.t_c[(size_t)ray * a.Nc + i] = coarse_depth(near, far, step, i, a.Nc);
   }
-  if (a.dvec) {
-    if (tid < 12) {
-      const int c = tid >> 2, l = tid & 3;
-      const float ph = rec[RF_DWRD + c] * __uint_as_float(kFreqDirBits[l]);
-      gd[c * 8 + 2 * l] = sinf(ph);
-      gd[c * 8 + 2 * l + 1] = cosf(ph);
-    }
-    __syncthreads();
-    const float* wr = a.w_dir + (size_t)tid * (WIDTH + DIR_DIM);
-    float s = a.b_dir[tid];
-#pragma unroll
-    for (int k = 0; k < DIR_DIM; ++k) s = __builtin_fmaf(wr[k], gd[k], s);
-    if (a.b_fold) s += a.b_fold[tid];  // point_info's bias through dir_info's feature columns (common.h SEG_FOLD)
-    a.dvec[(size_t)ray * HALF + tid] = s;
-  }
+  if (a.dvec) dvec_block(rec + RF_DWRD, a.w_dir, a.b_dir, a.b_fold, tid, gd, a.dvec + (size_t)ray * HALF);
 }
 
 }  // namespace nerf

@@ -1,5 +1,6 @@
 // ray_ops.hip -- the per-ray (HBM/latency-bound) stages of the hot path for MI355X (gfx950):
 //   k_rays              pixel -> camera/world direction, coarse depths, per-ray direction-branch vector
+//   k_dirs_dvec         the direction-branch vector of queried points (nerf_hip_query)
 //   k_coarse            sigma -> weights (inclusive transmittance), C_coarse, inverse-CDF resampling
 //   k_merge             merge coarse+fine, five independent channel sorts, composite -> C_fine
 //   k_ray_loss          sum-of-squares loss and its gradient
@@ -22,6 +23,14 @@ namespace nerf {
 __global__ __launch_bounds__(128) void k_rays(const RaysArgs a) {
   __shared__ float gd[DIR_DIM];
   ray_block(a, blockIdx.x, threadIdx.x, gd);
+}
+
+// k_dirs_dvec: the same start vectors for the colour point queries (nerf_hip_query), one per point from dirs[n][3] as given (not
+// renormalised).  grid = n blocks of 128 threads.
+__global__ __launch_bounds__(128) void k_dirs_dvec(const float* dirs, const float* w_dir, const float* b_dir, const float* b_fold, float* dvec) {
+  __shared__ float gd[DIR_DIM];
+  const size_t i = blockIdx.x;
+  dvec_block(dirs + i * 3, w_dir, b_dir, b_fold, threadIdx.x, gd, dvec + i * HALF);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -82,6 +91,11 @@ __global__ __launch_bounds__(1024) void k_ray_loss(const float* Cc, const float*
 // ---------------------------------------------------------------------------------------------
 hipError_t launch_rays(const RaysArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_rays, dim3(a.B), dim3(128), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_dirs_dvec(const float* dirs, int n, const float* w_dir, const float* b_dir, const float* b_fold, float* dvec, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dirs_dvec, dim3(n), dim3(128), 0, st, dirs, w_dir, b_dir, b_fold, dvec);
   return hipGetLastError();
 }
 hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st) {

@@ -22,9 +22,8 @@ from configparser import ConfigParser
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
-if __name__ == "__main__":
-    import nerf_tiny_amd as P
 
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="NeRF argument parser.")
     ap.add_argument("--conf", type=str, default="lego")
     ap.add_argument("--conf-dir", type=str, default=os.path.join(HERE, "conf"))
@@ -37,7 +36,18 @@ if __name__ == "__main__":
                                                                "two-part operands): 2x the exact fp32 step, opt-in (also ini key SPLIT_TRAIN = True)")
     ap.add_argument("--split-mlp", action="store_true", help="render (validation, display) on the split-fp32 inference kernels: same 1e-4 bar, "
                                                              "3x the rate; training is unaffected (also ini key SPLIT_MLP = True)")
-    args = ap.parse_args()
+    ap.add_argument("--density-grid", type=int, default=None, metavar="RES",
+                    help="after display(): write sigma on a RES^3 lattice over --grid-bbox to <RESULTS_PATH><time>_<iter>_sigma<RES>.npz "
+                         "(rank 0 only).  With CONTINUE = True and --total-iter at the checkpoint's iteration this exports without training")
+    ap.add_argument("--grid-bbox", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="box of --density-grid: its lowest and highest lattice corner (default -1.5 .. 1.5 on every axis)")
+    return ap
+
+
+if __name__ == "__main__":
+    import nerf_tiny_amd as P
+
+    args = build_parser().parse_args()
     conf = ConfigParser()
     conf.read(os.path.join(args.conf_dir, args.conf + ".ini"))
     c = lambda k, d=None: conf.get(args.conf, k, fallback=d)
@@ -59,3 +69,5 @@ if __name__ == "__main__":
     run = P.NeRFRunner(**kw)
     run.trainer("train")
     run.display()
+    if args.density_grid is not None:
+        run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)

@@ -193,6 +193,7 @@ class NeRFModel(nn.Module):
         self._last_ws = None
         self._frozen = False
         self._packed = set()
+        self._qws = {}           # with_rgb -> workspace of the point queries (query / density_grid): independent of the point count
 
     # ----- plumbing -------------------------------------------------------------------------
     def _workspace(self, B, flags):
@@ -245,6 +246,7 @@ class NeRFModel(nn.Module):
         d["_frozen"] = False
         d["_ws_capacity"] = False
         d["grad_bucket"] = None
+        d["_qws"] = {}
         return d
 
     def __setstate__(self, d):  # checkpoints written by an earlier build lack the newer plumbing attributes
@@ -256,6 +258,7 @@ class NeRFModel(nn.Module):
         self.__dict__["_ws"], self.__dict__["_ws_generation"] = {}, {}
         self.__dict__["_last_ws"], self.__dict__["_packed"], self.__dict__["_frozen"] = None, set(), False
         self.__dict__["_ws_capacity"] = False
+        self.__dict__["_qws"] = {}
 
     def _params(self):
         ps = list(self.network.parameters())
@@ -382,6 +385,53 @@ class NeRFModel(nn.Module):
                                     "weight image of that call was poisoned, its results are NaN")
         return hit
 
+    # ----- the field at explicit points (not in the reference: what a trained model is queried for besides rendering) ---------------------
+    def _query_workspace(self, with_rgb: bool, dev):
+        ws = self._qws.get(with_rgb)
+        if ws is None or ws.device != dev:
+            ws = torch.empty(_abi.query_ws_bytes(with_rgb), dtype=torch.uint8, device=dev)
+            self._qws[with_rgb] = ws
+        return ws
+
+    @torch.no_grad()
+    def query(self, points, dirs=None):
+        """The field (Network + Encoder, nerf.py:101-124, 135-167) at explicit points: points [M, 3] world coordinates, any M (0 too);
+        dirs [M, 3] unit world directions as Encoder consumes them (not renormalised) or None.  Returns (rgb [M, 3] or None, sigma [M]),
+        fp32 on the model's device, not requiring grad; the weights are only read.  ALWAYS exact fp32 -- ``bf16_mlp`` / ``split_mlp``
+        do not apply -- and bit-identical to what a forward computes for a sample at the same point seen along the same direction.
+        Without dirs only sigma is computed (the colour branch is skipped).  Accurate for |p| <= 320 per coordinate
+        (include/nerf_hip.h)."""
+        from . import ops
+
+        ps = self._params()
+        dev = ps[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("NeRFModel runs only on a ROCm device (MI355X): model.to('cuda'); there is no CPU path")
+        pts = torch.as_tensor(points).to(dev, torch.float32).reshape(-1, 3)
+        d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3) if dirs is not None else None
+        return ops.query(ps, pts, d, ws=self._query_workspace(d is not None, dev))
+
+    @torch.no_grad()
+    def density_grid(self, lo, hi, res):
+        """sigma on a regular lattice spanning the box [lo, hi] (three floats each): res = n or (nx, ny, nz), every n >= 1 and
+        nx * ny * nz < 2^31.  Point (i, j, k) is lo + (i, j, k) * step with step = (hi - lo) / (n - 1) computed in fp32 on the host
+        (0 where n == 1), each coordinate one fp32 product and one fp32 sum -- so the LAST point is lo + (n - 1) * step, which can
+        differ from hi in the last bits.  Returns sigma [nx, ny, nz] (C order, z fastest) on the model's device, exact fp32 whatever
+        ``bf16_mlp`` / ``split_mlp`` say, and no points buffer is formed: a 512^3 grid needs its 512 MiB of sigma and nothing else."""
+        import numpy as np
+
+        from . import ops
+
+        ps = self._params()
+        dev = ps[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("NeRFModel runs only on a ROCm device (MI355X): model.to('cuda'); there is no CPU path")
+        shape = grid_shape(res)
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        step = grid_step(lo32, hi32, shape)
+        return ops.density_grid(ps, lo32.tolist(), step.tolist(), shape, ws=self._query_workspace(False, dev))
+
     @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):
         """Inference over a LONG list of rays (a frame, a test set) -- rays [lo, hi) of it -- with the reference's batch semantics and few
@@ -424,6 +474,23 @@ class NeRFModel(nn.Module):
         if getattr(self, "bf16_mlp", False):
             self.read_status()  # a frame is not handed out on a poisoned weight image (raises on STATUS_PREP_TIMEOUT; one sync per frame)
         return C_c, C_f
+
+
+def grid_shape(res) -> tuple:
+    """res = n or (nx, ny, nz) -> (nx, ny, nz) as ints."""
+    shape = (int(res),) * 3 if isinstance(res, (int,)) or (hasattr(res, "ndim") and res.ndim == 0) else tuple(int(n) for n in res)
+    if len(shape) != 3:
+        raise ValueError(f"res {res!r}: an int or three ints")
+    return shape
+
+
+def grid_step(lo32, hi32, shape):
+    """The lattice step of NeRFModel.density_grid in fp32: (hi - lo) / (n - 1), 0 where n == 1."""
+    import numpy as np
+
+    n1 = np.asarray([max(n - 1, 1) for n in shape], dtype=np.float32)
+    step = (np.asarray(hi32, dtype=np.float32) - np.asarray(lo32, dtype=np.float32)) / n1
+    return np.where(np.asarray(shape) > 1, step, np.float32(0.0)).astype(np.float32)
 
 
 def fuse_plan(near_far0, n: int, batch: int, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):

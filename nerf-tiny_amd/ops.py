@@ -58,6 +58,37 @@ def field_bf16(params, row, col, poses_bound_f32, K_inv, t):
     return rgb, sigma
 
 
+def query(params, points, dirs=None, ws=None):
+    """The field at explicit points (nerf_hip_query, exact fp32): points[M,3] (and unit world dirs[M,3]) on the device ->
+    (rgb[M,3] or None, sigma[M]).  ws: a uint8 device buffer of >= _abi.query_ws_bytes(dirs is not None) bytes (allocated here if None)."""
+    M, dev = points.shape[0], points.device
+    with_rgb = dirs is not None
+    points = points.to(torch.float32).contiguous()
+    dirs = dirs.to(dev, torch.float32).contiguous() if with_rgb else None
+    if with_rgb and dirs.shape != points.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and points {tuple(points.shape)} differ")
+    sigma = torch.empty(M, device=dev)
+    rgb = torch.empty(M, 3, device=dev) if with_rgb else None
+    if ws is None:
+        ws = torch.empty(_abi.query_ws_bytes(with_rgb), dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_query(_abi.ptr_array(params), points.data_ptr(), dirs.data_ptr() if with_rgb else None, M,
+                                         rgb.data_ptr() if with_rgb else None, sigma.data_ptr(), ws.data_ptr(), ws.numel(), _stream(points)))
+    return rgb, sigma
+
+
+def density_grid(params, lo, step, shape, ws=None):
+    """sigma at lo + (i, j, k) * step (nerf_hip_density_grid, exact fp32): lo / step three host floats, shape (nx, ny, nz) ->
+    sigma[nx, ny, nz] on the parameters' device.  ws as in query() (sigma only)."""
+    nx, ny, nz = (int(n) for n in shape)
+    dev = params[0].device
+    sigma = torch.empty(max(nx, 0), max(ny, 0), max(nz, 0), device=dev)
+    if ws is None:
+        ws = torch.empty(_abi.query_ws_bytes(False), dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_density_grid(_abi.ptr_array(params), _abi.f32_array(lo), _abi.f32_array(step), nx, ny, nz,
+                                                sigma.data_ptr(), ws.data_ptr(), ws.numel(), _stream(sigma)))
+    return sigma
+
+
 def coarse_composite(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
     """-> w_c[B,Nc], C_coarse[B,3], t_f[B,Nf], status(int)"""
     B, Nc = t_c.shape

@@ -365,6 +365,30 @@ class NeRFRunner:
         self.last_iter = it - 1
         return self.last_iter
 
+    def density_grid(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, save=True):
+        """sigma of the current model on a res^3 (or res = (nx, ny, nz)) lattice spanning the box [lo, hi] (NeRFModel.density_grid: exact
+        fp32, lattice point (i, j, k) = lo + (i, j, k) * step, step = (hi - lo) / (n - 1)).  save: writes
+        ``<results_path><start_time>_<last_iter>_sigma<res>.npz`` with ``sigma`` (float32 [nx, ny, nz]), ``lo``, ``hi``, ``step`` and ``iter``
+        -- the input of a marching-cubes mesh extraction.  Under a launcher only rank 0 computes and writes the grid; the
+        other ranks return None.  Returns sigma as a numpy array."""
+        import numpy as np
+
+        from .nerf import grid_shape, grid_step
+
+        if self.rank != 0:
+            return None
+        shape = grid_shape(res)
+        lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+        self.model.eval()
+        sigma = self.model.density_grid(lo32, hi32, shape).cpu().numpy()
+        if save:
+            tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_sigma" + tag + ".npz"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            np.savez(path, sigma=sigma, lo=lo32, hi=hi32, step=grid_step(lo32, hi32, shape), iter=np.int64(self.last_iter))
+        return sigma
+
     # nerf.py:503-530
     def display(self, save=True):
         rays = self.disp_rays
