@@ -44,7 +44,8 @@ extern "C" {
 
 #define NERF_HIP_ABI_VERSION 7 /* 2: NERF_HIP_BF16_MLP, nerf_hip_field_bf16; 3: nerf_hip_backward_overlap, NERF_HIP_SPLIT_MLP;
                                   4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED;
-                                  7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid */
+                                  7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
+                                     nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit */
 
 enum {
   NERF_HIP_OK = 0,
@@ -248,6 +249,36 @@ int nerf_hip_query(const float* const* weights24, const float* points, const flo
  * nx * ny * nz < 2^31.  No points buffer is formed: a 512^3 grid needs only its 512 MiB of sigma. */
 int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz,
                           float* sigma, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Marching cubes over a density grid: an indexed triangle mesh of the isosurface sigma == level.
+ * sigma is C-order fp32 [nx][ny][nz] (z fastest, as nerf_hip_density_grid writes it); lattice point (i, j, k) sits at
+ * lo + (i, j, k) * step (each coordinate one fp32 product and one fp32 sum).  Inside means sigma > level; NaN is outside.
+ * - A vertex on every lattice edge (to the +x, +y or +z neighbour) whose ends differ in insideness, at p_a + t * (p_b - p_a) with
+ *   t = (level - s_a) / (s_b - s_a) (0.5 where that is not finite), ordered by the edge's lower endpoint's linear index
+ *   (i * ny + j) * nz + k, then by axis x < y < z.  Its normal is -g / |g| ((0, 0, 0) where |g| is 0 or not finite), g the sigma
+ *   gradient (central differences, one-sided at the grid's faces) interpolated with the same t.
+ * - Faces (three int32 vertex indices) from the classic table (csrc/mc_tables.h), ordered by cell linear index (C order over the
+ *   (nx-1)(ny-1)(nz-1) cells), then by the table's order; counter-clockwise seen from outside (cross(v1 - v0, v2 - v0) points toward
+ *   decreasing sigma).
+ * - Any dimension < 2: no cells, the empty mesh.  Every dimension >= 1, nx * ny * nz < 2^31, level finite; emit also needs every
+ *   step > 0 (and finite) along a dimension of more than one point.
+ * Enqueue-only: neither call synchronises with the host.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of a mesh over an nx x ny x nz grid: 4 bytes per lattice point and 24 per 4096 points. */
+int nerf_hip_mesh_ws_bytes(int nx, int ny, int nz, size_t* bytes);
+
+/* Counts the mesh: writes counts[0] = V and counts[1] = F (DEVICE int64[2]) and leaves the vertex offsets in ws for the emit. */
+int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, int64_t* counts,
+                        void* stream);
+
+/* Writes verts[V][3], normals[V][3] (fp32) and faces[F][3] (int32).  Must follow a nerf_hip_mesh_count on the same workspace, grid and
+ * level (stream order).  max_v / max_f are the caller's capacities in rows: the kernels clamp every store to them, so a wrong capacity
+ * or a mismatched count/emit pair gives wrong or partial output, never a write outside the buffers.  Face indices are int32: a mesh
+ * with V >= 2^31 cannot be indexed (the caller refuses it after the count).  lo3 / step3 are HOST arrays. */
+int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
+                       size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

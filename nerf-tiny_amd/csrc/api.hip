@@ -1202,3 +1202,121 @@ int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const
 }
 
 }  // extern "C"
+
+namespace {
+
+// Workspace of the mesh calls: per lattice point its in-block vertex offset and owned-edge mask, then per workgroup of MESH_PTS points
+// its vertex / face totals and their 64-bit exclusive scans.
+struct MeshLayout {
+  size_t offs, tv, tf, bv, bf, total;
+  int nb;
+};
+MeshLayout mesh_layout(int nx, int ny, int nz) {
+  MeshLayout L;
+  const long long n = (long long)nx * ny * nz;
+  L.nb = mesh_blocks(n);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  L.offs = take((size_t)n * 4);
+  L.tv = take((size_t)L.nb * 4);
+  L.tf = take((size_t)L.nb * 4);
+  L.bv = take((size_t)(L.nb + 1) * 8);
+  L.bf = take((size_t)(L.nb + 1) * 8);
+  L.total = o;
+  return L;
+}
+
+int check_mesh_grid(int nx, int ny, int nz) {
+  if (nx < 1 || ny < 1 || nz < 1) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: every dimension must be positive", nx, ny, nz);
+  // the kernels index lattice points with 32-bit integers, as the density grid does
+  if ((long long)nx * ny * nz >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: a grid must stay below 2^31 points", nx, ny, nz);
+  return NERF_HIP_OK;
+}
+
+int check_mesh_call(const float* sigma, int nx, int ny, int nz, float level, const void* ws, size_t ws_bytes, MeshLayout* L) {
+  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
+  if (!isfinite(level)) return fail(NERF_HIP_ERR_ARG, "level %g is not finite", (double)level);
+  if (!sigma) return fail(NERF_HIP_ERR_ARG, "sigma is null");
+  *L = mesh_layout(nx, ny, nz);
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
+  return NERF_HIP_OK;
+}
+
+MeshArgs mesh_args(const float* sigma, int nx, int ny, int nz, float level, const void* ws, const MeshLayout& L) {
+  MeshArgs a;
+  memset(&a, 0, sizeof(a));
+  void* w = const_cast<void*>(ws);
+  a.sigma = sigma;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.level = level;
+  a.offs = at<unsigned>(w, L.offs);
+  a.tv = at<int>(w, L.tv);
+  a.tf = at<int>(w, L.tf);
+  a.bv = at<long long>(w, L.bv);
+  a.bf = at<long long>(w, L.bf);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_ws_bytes(int nx, int ny, int nz, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
+  *bytes = mesh_layout(nx, ny, nz).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+  MeshLayout L;
+  if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
+  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
+  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (nx < 2 || ny < 2 || nz < 2) {  // no cells: the empty mesh
+    HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
+    return NERF_HIP_OK;
+  }
+  MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_mesh_count(a, st));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
+                       size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream) {
+  MeshLayout L;
+  if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
+  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
+  const int dims[3] = {nx, ny, nz};
+  for (int c = 0; c < 3; ++c) {
+    // a step <= 0 would mirror the lattice and silently flip the winding
+    if (dims[c] > 1 && !(step3[c] > 0.0f && isfinite(step3[c])))
+      return fail(NERF_HIP_ERR_ARG, "step[%d] = %g: must be positive and finite along a dimension of more than one point", c, (double)step3[c]);
+  }
+  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (max_v > 0 && (!verts || !normals)) return fail(NERF_HIP_ERR_ARG, "verts / normals is null");
+  if (max_f > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (int rc = check_device()) return rc;
+  if (nx < 2 || ny < 2 || nz < 2 || (max_v == 0 && max_f == 0)) return NERF_HIP_OK;  // nothing to write
+  MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.step[c] = step3[c];
+  }
+  a.verts = verts;
+  a.normals = normals;
+  a.faces = faces;
+  a.max_v = max_v;
+  a.max_f = max_f;
+  HIP_TRY(launch_mesh_emit(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"

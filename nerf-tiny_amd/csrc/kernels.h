@@ -377,4 +377,27 @@ struct GatherArgs {
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_gather_rays(const GatherArgs& a, hipStream_t st);
 
+// ---- marching cubes over a density grid (mesh.hip; nerf_hip_mesh_count / nerf_hip_mesh_emit) ----
+constexpr int MESH_WG = 256;                   // threads per workgroup
+constexpr int MESH_ROUNDS = 16;                // rounds of MESH_WG consecutive lattice points per workgroup
+constexpr int MESH_PTS = MESH_WG * MESH_ROUNDS;  // lattice points per workgroup (the scan's block)
+
+struct MeshArgs {
+  const float* sigma;      // [nx][ny][nz], z fastest
+  int nx, ny, nz;          // every dimension >= 2, nx * ny * nz < 2^31
+  float level;
+  float lo[3], step[3];    // emit only
+  unsigned* offs;          // [N]: (in-block exclusive vertex offset << 3) | owned-edge mask, written only where the mask is non-zero
+  int *tv, *tf;            // [nb] per-block vertex / face totals
+  long long *bv, *bf;      // [nb + 1] exclusive scans of tv / tf; [nb] = the totals
+  long long* counts;       // [2] = V, F (count only)
+  float *verts, *normals;  // [max_v][3] (emit only)
+  int* faces;              // [max_f][3]
+  long long max_v, max_f;
+};
+
+inline int mesh_blocks(long long n_points) { return (int)((n_points + MESH_PTS - 1) / MESH_PTS); }
+hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st);  // count + in-block vertex scan, then the scan of the block totals
+hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st);
+
 }  // namespace nerf

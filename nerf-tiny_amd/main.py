@@ -40,7 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after display(): write sigma on a RES^3 lattice over --grid-bbox to <RESULTS_PATH><time>_<iter>_sigma<RES>.npz "
                          "(rank 0 only).  With CONTINUE = True and --total-iter at the checkpoint's iteration this exports without training")
     ap.add_argument("--grid-bbox", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
-                    help="box of --density-grid: its lowest and highest lattice corner (default -1.5 .. 1.5 on every axis)")
+                    help="box of --density-grid and --mesh: its lowest and highest lattice corner (default -1.5 .. 1.5 on every axis)")
+    ap.add_argument("--mesh", type=int, default=None, metavar="RES",
+                    help="after display(): extract the isosurface sigma == --mesh-level on a RES^3 lattice over --grid-bbox (marching cubes on "
+                         "the device, vertex colours) to <RESULTS_PATH><time>_<iter>_mesh<RES>.ply (rank 0 only)")
+    ap.add_argument("--mesh-level", type=float, default=50.0, metavar="SIGMA", help="density threshold of --mesh (default 50.0)")
     return ap
 
 
@@ -71,3 +75,5 @@ if __name__ == "__main__":
     run.display()
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
+    if args.mesh is not None:
+        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)

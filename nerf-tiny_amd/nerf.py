@@ -433,6 +433,26 @@ class NeRFModel(nn.Module):
         return ops.density_grid(ps, lo32.tolist(), step.tolist(), shape, ws=self._query_workspace(False, dev))
 
     @torch.no_grad()
+    def extract_mesh(self, lo, hi, res, level, color=True):
+        """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
+        grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
+        its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
+        device, exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say.  The grid's 4 bytes per point are held only during the call, with
+        a mesh workspace of 4 bytes per point more."""
+        import numpy as np
+
+        from . import mesh
+
+        shape = grid_shape(res)
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        sigma = self.density_grid(lo32, hi32, shape)
+        verts, faces, normals = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
+        del sigma
+        rgb = self.query(verts, -normals)[0] if color else None
+        return mesh.Mesh(verts, faces, normals, rgb)
+
+    @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):
         """Inference over a LONG list of rays (a frame, a test set) -- rays [lo, hi) of it -- with the reference's batch semantics and few
         kernel calls: the list is the sequence of batches [g*batch_ray, (g+1)*batch_ray) the reference's display loop feeds to `forward`

@@ -89,6 +89,35 @@ def density_grid(params, lo, step, shape, ws=None):
     return sigma
 
 
+def marching_cubes(sigma, lo, step, level, ws=None):
+    """Isosurface sigma == level of a device grid sigma[nx, ny, nz] (nerf_hip_mesh_count + nerf_hip_mesh_emit): lo / step three host
+    floats (lattice point (i, j, k) at lo + (i, j, k) * step) -> (verts[V, 3] fp32, faces[F, 3] int32, normals[V, 3] fp32) on sigma's
+    device.  One count call, one 16-byte read of the counts (this synchronises with the stream), then the emit into buffers sized from
+    them.  ws: a uint8 device buffer of >= _abi.mesh_ws_bytes(nx, ny, nz) bytes (allocated here if None)."""
+    if sigma.dim() != 3:
+        raise ValueError(f"sigma {tuple(sigma.shape)}: a [nx, ny, nz] grid")
+    nx, ny, nz = (int(n) for n in sigma.shape)
+    dev = sigma.device
+    sigma = sigma.to(torch.float32).contiguous()
+    if ws is None:
+        ws = torch.empty(_abi.mesh_ws_bytes(nx, ny, nz), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    L, st = _abi.lib(), _stream(sigma)
+    _abi.check(L.nerf_hip_mesh_count(sigma.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), ws.numel(), counts.data_ptr(), st))
+    V, F = (int(n) for n in counts.cpu())
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise ValueError(f"the mesh has {V} vertices and {F} faces: int32 face indices hold fewer than 2^31 of either "
+                         "(raise the level or lower the resolution)")
+    verts = torch.empty(V, 3, device=dev)
+    normals = torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    if V == 0:
+        return verts, faces, normals
+    _abi.check(L.nerf_hip_mesh_emit(sigma.data_ptr(), nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step), float(level), ws.data_ptr(),
+                                    ws.numel(), verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, F, st))
+    return verts, faces, normals
+
+
 def coarse_composite(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
     """-> w_c[B,Nc], C_coarse[B,3], t_f[B,Nf], status(int)"""
     B, Nc = t_c.shape

@@ -389,6 +389,32 @@ class NeRFRunner:
             np.savez(path, sigma=sigma, lo=lo32, hi=hi32, step=grid_step(lo32, hi32, shape), iter=np.int64(self.last_iter))
         return sigma
 
+    def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True):
+        """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
+        (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
+        normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
+        normals and, with color, uchar colours).  Under a launcher only rank 0 computes and writes the mesh; the other ranks return
+        None.  Returns mesh.Mesh of numpy arrays (rgb None without color)."""
+        import numpy as np
+
+        from .mesh import Mesh, write_ply
+        from .nerf import grid_shape
+
+        if self.rank != 0:
+            return None
+        shape = grid_shape(res)
+        lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
+        self.model.eval()
+        m = self.model.extract_mesh(lo32, hi32, shape, level, color=color)
+        out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
+        if save:
+            tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + ".ply"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            write_ply(path, out.verts, out.faces, out.normals, out.rgb)
+        return out
+
     # nerf.py:503-530
     def display(self, save=True):
         rays = self.disp_rays
