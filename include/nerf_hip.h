@@ -45,7 +45,7 @@ extern "C" {
 #define NERF_HIP_ABI_VERSION 7 /* 2: NERF_HIP_BF16_MLP, nerf_hip_field_bf16; 3: nerf_hip_backward_overlap, NERF_HIP_SPLIT_MLP;
                                   4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED;
                                   7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
-                                     nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit */
+                                     nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps */
 
 enum {
   NERF_HIP_OK = 0,
@@ -132,6 +132,24 @@ int nerf_hip_forward(const float* const* weights24, const int64_t* row, const in
                      const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
                      int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine,
                      void* ws, size_t ws_bytes, int flags, void* stream);
+
+/*
+ * nerf_hip_forward plus each ray's expected depth and accumulated opacity (INFERENCE only).
+ *   maps            [B,4] f32 out, device: (D_c, A_c, D_f, A_f) per ray, where
+ *                     D_c = sum_i w_c,i t_c,i   A_c = sum_i w_c,i   over the Nc coarse samples, with the weights of C_coarse;
+ *                     D_f = sum_i w_i t_s,i     A_f = sum_i w_i     over the Nc + Nf merged, sorted samples, with the weights of C_fine.
+ *                   t_s is the SORTED depth channel: without NERF_HIP_CORRECTED the five channels are sorted independently (as the
+ *                   reference does), so D_f is what compositing t like a colour channel gives; with NERF_HIP_CORRECTED (one joint sort)
+ *                   it is the physical expected depth.  Sums in fp32 per lane, then a wave reduction: deterministic, no atomics.
+ *                   Disparity is not formed: a caller derives it from D and A.
+ * Every other argument, the workspace (size and layout: nerf_hip_ws_bytes, NERF_HIP_WEIGHTS_UNCHANGED reuse) and C_coarse / C_fine / the
+ * status word are exactly nerf_hip_forward's, bit for bit, in every inference mode.  NERF_HIP_SAVE_FOR_BACKWARD or a null maps ->
+ * NERF_HIP_ERR_ARG before any device work.  (Small bf16-MLP batches run the separate launches instead of the one-launch ray-pair kernel.)
+ */
+int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, const int64_t* col,
+                          const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
+                          int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
+                          void* ws, size_t ws_bytes, int flags, void* stream);
 
 /*
  * Backward of nerf_hip_forward (autograd through nerf.py:286-323, called at nerf.py:473).

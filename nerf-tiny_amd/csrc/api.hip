@@ -308,9 +308,10 @@ struct TrainLoss {
   float *dC_c, *dC_f, *terms, *loss;
   bool fused;
 };
+// maps: nerf_hip_forward_maps's [B][4] output (inference calls only; its caller has checked the flags), else null
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl);
+                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr);
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
                   const TrainLoss* tl);
@@ -325,13 +326,22 @@ int nerf_hip_forward(const float* const* weights24, const int64_t* row, const in
                       nullptr);
 }
 
+int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
+                          const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
+                          float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream) {
+  if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_maps is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
+  if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
+  return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
+                      nullptr, maps);
+}
+
 }  // extern "C"
 
 namespace {
 
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl) {
+                 int flags, void* stream, TrainLoss* tl, float* maps) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
@@ -356,7 +366,8 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   // SMALL bf16-MLP inference batches at the shipped sample counts: ONE launch renders every ray pair end to end, ray records included
   // (field_fwd_bf16x.hip: k_render_pair_bf16x); with the weight image reused (rendering loops) it is the only launch of the call
   const bool corrected = (flags & NERF_HIP_CORRECTED) != 0;  // joint depth sort (forward); the fused small-batch forms keep the reference's sorts only
-  const bool pair = bf16x && Nc == 64 && Nf == 128 && pair_bf16(B) && !corrected;
+  // (a maps call takes the separate launches: the pair kernel forms no depth / opacity; same pixels, test_pair_kernel_equals_separate_launches)
+  const bool pair = bf16x && Nc == 64 && Nf == 128 && pair_bf16(B) && !corrected && !maps;
   if (!(flags & NERF_HIP_WEIGHTS_UNCHANGED) && !one_prep) {
     ProfScope ps(NERF_HIP_K_PACK, st, &pc);
     if (bf16 || split) HIP_TRY(launch_fold_weights(w, at<float>(ws, L.fold), st));  // fp32 W_fold, b_fold for the bf16 / split packers (bf16_common.h)
@@ -465,7 +476,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     ff.mode = 0;
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_COARSE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(launch_coarse(ca, st)); }
+    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(launch_coarse(ca, st, maps)); }
   }
 
   // fine pass (nerf.py:299), same network (quirk Q10)
@@ -493,7 +504,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(launch_merge(ma, st)); }
+    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(launch_merge(ma, st, maps)); }
   }
   return NERF_HIP_OK;
 }

@@ -177,9 +177,10 @@ hipError_t launch_rays(const RaysArgs& a, hipStream_t st);
 constexpr int PREP_READY_WORDS = 256;
 hipError_t launch_prep_bf16(const Weights24& w, float* fold, unsigned char* img_fwd, int fwd_form, unsigned char* img_bwd,
                             unsigned* ready, unsigned token, unsigned* sticky, const RaysArgs& rays, hipStream_t st);
-hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st);
+// maps != null (nerf_hip_forward_maps, inference): k_coarse_maps / k_merge_maps, which also store each ray's (D_c, A_c) / (D_f, A_f) to maps [B][4]
+hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps = nullptr);
 size_t merge_lds_bytes(int P);
-hipError_t launch_merge(const MergeArgs& a, hipStream_t st);
+hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps = nullptr);
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st);
 
 }  // namespace nerf

@@ -3,6 +3,7 @@
 //   k_dirs_dvec         the direction-branch vector of queried points (nerf_hip_query)
 //   k_coarse            sigma -> weights (inclusive transmittance), C_coarse, inverse-CDF resampling
 //   k_merge             merge coarse+fine, five independent channel sorts, composite -> C_fine
+//   k_coarse_maps / k_merge_maps   the same, plus each ray's expected depth and opacity (nerf_hip_forward_maps)
 //   k_ray_loss          sum-of-squares loss and its gradient
 // One 64-lane wave owns one ray: the transmittance cumsum / CDF are wave scans (fp64 accumulator like
 // ATen's CPU cumsum, rounded to fp32 per element), searchsorted is a per-lane binary search in LDS and
@@ -47,6 +48,16 @@ __global__ __launch_bounds__(256) void k_coarse(const CoarseArgs a) {
   coarse_ray_stage(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); });
 }
 
+// k_coarse_maps: k_coarse that also stores each live ray's coarse depth and opacity to maps [B][4] columns 0, 1 (nerf_hip_forward_maps).  The
+// pointer is a kernel argument of its own, not a CoarseArgs field: CoarseArgs rides inside FwdFuse, the bf16 training kernels' argument.
+__global__ __launch_bounds__(256) void k_coarse_maps(const CoarseArgs a, float* maps) {
+  __shared__ float s_w[4][MAXN];
+  __shared__ float s_cdf[4][MAXN];
+  __shared__ float s_t[4][MAXN];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  coarse_ray_stage<true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps);
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_merge: nerf.py:302-321.  cat -> sort(dim=1) of a [B,N,5] bundle = five INDEPENDENT ascending channel
 // sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine.
@@ -60,6 +71,16 @@ __global__ __launch_bounds__(64) void k_merge(const MergeArgs a) {
   float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
   uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
   merge_ray_stage<WITH_IDX>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); });
+}
+
+// k_merge_maps: k_merge that also stores each ray's fine depth and opacity to maps [B][4] columns 2, 3 (nerf_hip_forward_maps; pointer passed
+// as for k_coarse_maps).  Both sort paths (registers at P = 256, LDS otherwise) end in the same merge_ray_composite.
+template <bool WITH_IDX>
+__global__ __launch_bounds__(64) void k_merge_maps(const MergeArgs a, float* maps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
+  uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
+  merge_ray_stage<WITH_IDX, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -98,13 +119,22 @@ hipError_t launch_dirs_dvec(const float* dirs, int n, const float* w_dir, const 
   hipLaunchKernelGGL(k_dirs_dvec, dim3(n), dim3(128), 0, st, dirs, w_dir, b_dir, b_fold, dvec);
   return hipGetLastError();
 }
-hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_coarse, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps) {
+  if (maps) hipLaunchKernelGGL(k_coarse_maps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps);
+  else hipLaunchKernelGGL(k_coarse, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 size_t merge_lds_bytes(int P) { return (size_t)5 * P * (sizeof(float) + sizeof(uint16_t)); }
-hipError_t launch_merge(const MergeArgs& a, hipStream_t st) {
+template <bool WITH_IDX>
+hipError_t launch_merge_maps(const MergeArgs& a, float* maps, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_maps<WITH_IDX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  hipLaunchKernelGGL(k_merge_maps<WITH_IDX>, dim3(a.B), dim3(64), lds, st, a, maps);
+  return hipGetLastError();
+}
+hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps) {
   const size_t lds = merge_lds_bytes(a.P);
+  if (maps) return (a.perm || a.joint) ? launch_merge_maps<true>(a, maps, lds, st) : launch_merge_maps<false>(a, maps, lds, st);
   if (a.perm || a.joint) {  // (the joint-sort mode needs the depth channel's permutation, stored or not)
     if (lds > 48 * 1024)
       if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;

@@ -48,11 +48,16 @@ __device__ __forceinline__ float ray0_spacing(float n0, float f0, int Nc) {
 // get_density (nerf.py:263-272) with delta = (far - near) / Nc (quirk Q5), color_cum (nerf.py:274-281): the ray's Nc coarse samples at
 // sigma[i], rgb[3 i + ch], t_c[i] (global or LDS) -> w, cdf, tc (LDS, this wave's), optionally w_c (global) and C_coarse[3]; lo / hi =
 // min / max of the cdf (nerf.py:240-241).  The caller orders the LDS writes before coarse_ray_resample's reads.
+// MAPS (nerf_hip_forward_maps): also the ray's coarse depth and opacity D_c = sum_i w_i t_c,i, A_c = sum_i w_i -- fp32 per lane, then wave_sum,
+// as the colour sums -- stored by lane 0 to maps_out[0..1] (null: nothing stored).  Without MAPS the code is the colour-only one.
+template <bool MAPS = false>
 __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const float* rgb, const float* t_c, float near, float far, int Nc, int lane,
-                                                   float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out) {
+                                                   float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out,
+                                                   float* maps_out = nullptr) {
   const float delta_c = (far - near) / (float)Nc;
   double carry = 0.0, carry2 = 0.0;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+  float dsum = 0.f, asum = 0.f;  // (MAPS only)
   float lo = INFINITY, hi = -INFINITY;
   for (int base = 0; base < Nc; base += 64) {
     const int i = base + lane;
@@ -75,6 +80,10 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
       c0 += wi * rgb[gi * 3 + 0];
       c1 += wi * rgb[gi * 3 + 1];
       c2 += wi * rgb[gi * 3 + 2];
+      if constexpr (MAPS) {
+        dsum += wi * t_c[gi];
+        asum += wi;
+      }
       lo = fminf(lo, cd);
       hi = fmaxf(hi, cd);
     }
@@ -88,6 +97,14 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
     C_out[0] = c0;
     C_out[1] = c1;
     C_out[2] = c2;
+  }
+  if constexpr (MAPS) {
+    dsum = wave_sum(dsum);
+    asum = wave_sum(asum);
+    if (lane == 0 && maps_out) {
+      maps_out[0] = dsum;
+      maps_out[1] = asum;
+    }
   }
 }
 
@@ -283,17 +300,20 @@ __device__ __forceinline__ void merge_channel_job(const MergeArgs& a, const int 
   *reinterpret_cast<uint2*>(idx + 4 * lane) = pk;
 }
 
-template <bool WITH_IDX>
+template <bool WITH_IDX, bool MAPS = false>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
-                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret = nullptr);
+                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret = nullptr,
+                                                    float* maps_out = nullptr);
 
 // nerf.py:302-321 behind the load: val [5][P] (channel 0 = t, 1..3 = rgb, 4 = sigma; slots >= N padded with NaN) and, WITH_IDX, idx [5][P]
 // = the original slot, in LDS -> five independent ascending channel sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`,
-// weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).
+// weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).  MAPS: also the fine depth and
+// opacity to maps_out[0..1] (merge_ray_composite).
 struct MergeNoFix { __device__ __forceinline__ void operator()() const {} };
-template <bool WITH_IDX, class Sync, class PostSort = MergeNoFix>
+template <bool WITH_IDX, bool MAPS = false, class Sync, class PostSort = MergeNoFix>
 __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* idx, int P, int N, float last, int lane, float* w_out, float* bundle_out,
-                                                         uint16_t* perm_out, float* C_out, Sync&& sync, PostSort&& post_sort = MergeNoFix{}) {
+                                                         uint16_t* perm_out, float* C_out, Sync&& sync, PostSort&& post_sort = MergeNoFix{},
+                                                         float* maps_out = nullptr) {
   if (P == 256) {  // the usual size (64 + 128 samples): the whole network in registers
     sort256_regs<WITH_IDX>(val, idx, lane, sync);
   } else
@@ -327,15 +347,19 @@ __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* i
     }
   }
   post_sort();  // (the joint-sort mode re-fills channels 1..4 by the depth channel's permutation here)
-  merge_ray_composite<WITH_IDX>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out);
+  merge_ray_composite<WITH_IDX, MAPS>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out);
 }
 
 // the composite over the SORTED channels val [5][P] (and idx): delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine[3]
-template <bool WITH_IDX>
+// MAPS (nerf_hip_forward_maps): also D_f = sum_i w_i t_s,i over the sorted depth channel t_s (in the reference's mode the channels are sorted
+// independently, quirk Q1: D_f is t composited like a colour channel; in the joint-sort mode the physical expected depth) and A_f = sum_i w_i,
+// fp32 per lane then wave_sum as the colour sums, stored by lane 0 to maps_out[0..1] (null: nothing stored)
+template <bool WITH_IDX, bool MAPS>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
-                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret) {
+                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, float* maps_out) {
   double carry = 0.0;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+  float dsum = 0.f, asum = 0.f;  // (MAPS only)
   for (int base = 0; base < N; base += 64) {
     const int i = base + lane;
     const bool v = i < N;
@@ -350,6 +374,10 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
     if (v) {
       const float r = val[P + i], g = val[2 * P + i], b = val[3 * P + i];
       c0 += wi * r; c1 += wi * g; c2 += wi * b;
+      if constexpr (MAPS) {
+        dsum += wi * ti;
+        asum += wi;
+      }
       if (w_out) w_out[i] = wi;
       if (bundle_out) {
         float* o = bundle_out + (size_t)i * 5;
@@ -374,14 +402,24 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
     c_ret[1] = c1;
     c_ret[2] = c2;
   }
+  if constexpr (MAPS) {
+    dsum = wave_sum(dsum);
+    asum = wave_sum(asum);
+    if (lane == 0 && maps_out) {
+      maps_out[0] = dsum;
+      maps_out[1] = asum;
+    }
+  }
 }
 
 // ---- the per-ray stages as their kernels run them (arguments, liveness, stores), for ONE ray by one wave: k_coarse / k_merge (ray_ops.hip)
 // and the small-batch epilogues of the bf16 training forward kernels (field_fwd_bf16.hip) are these functions ----
 
-// k_coarse for ray `ray_raw` (rays behind the batch: computed on a copy of the last ray, nothing stored); w / cdf / tc: Nc floats of LDS each
-template <class Sync>
-__device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int ray_raw, const int lane, float* w, float* cdf, float* tc, Sync&& sync) {
+// k_coarse for ray `ray_raw` (rays behind the batch: computed on a copy of the last ray, nothing stored); w / cdf / tc: Nc floats of LDS each.
+// MAPS (k_coarse_maps): maps [B][4] also gets the ray's (D_c, A_c) in its columns 0, 1
+template <bool MAPS = false, class Sync>
+__device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int ray_raw, const int lane, float* w, float* cdf, float* tc, Sync&& sync,
+                                                 float* maps = nullptr) {
   const bool live = ray_raw < a.B;
   const int ray = live ? ray_raw : a.B - 1;
   float near, far;
@@ -401,17 +439,20 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
   }
   const size_t g0 = (size_t)ray * a.Nc;
   float lo, hi;
-  coarse_ray_weights(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
-                     (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi);
+  coarse_ray_weights<MAPS>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
+                           (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi,
+                           (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr);
   sync();
   const bool bad = coarse_ray_resample(w, cdf, tc, lo, hi, delta0, a.Nc, a.Nf, lane, live ? a.t_f + (size_t)ray * a.Nf : nullptr);
   if (live && bad && a.status) atomicOr(a.status, 1u);
   if (live && bad && a.sticky) atomicOr(a.sticky, 1u);
 }
 
-// k_merge for ray `ray` (< B): load the ray's coarse + fine samples into val [5][P] (idx [5][P]: original slots), sort, composite
-template <bool WITH_IDX, class Sync>
-__device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ray, const int lane, float* val, uint16_t* idx, Sync&& sync) {
+// k_merge for ray `ray` (< B): load the ray's coarse + fine samples into val [5][P] (idx [5][P]: original slots), sort, composite.
+// MAPS (k_merge_maps): maps [B][4] also gets the ray's (D_f, A_f) in its columns 2, 3
+template <bool WITH_IDX, bool MAPS = false, class Sync>
+__device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ray, const int lane, float* val, uint16_t* idx, Sync&& sync,
+                                                float* maps = nullptr) {
   const int P = a.P, N = a.Nc + a.Nf;
   // load: channel 0 = t, 1..3 = rgb, 4 = sigma
   for (int i = lane; i < P; i += 64) {
@@ -450,8 +491,9 @@ __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ra
       }
     }
   };
-  merge_ray_sort_composite<WITH_IDX>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
-                                     (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix);
+  merge_ray_sort_composite<WITH_IDX, MAPS>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
+                                           (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix,
+                                           (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr);
 }
 
 // ---- ray_loss (nerf.py:325-331) in two pieces, bit-compatible with k_ray_loss (ray_ops.hip) ----

@@ -82,29 +82,42 @@ def _call_flags(model, need_grad: bool) -> int:
             | (_abi.SPLIT_MLP if split and not bf16 else 0))
 
 
-class _RenderFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, need_grad, row, col, pb, K9, ray0, *params):
-        B = row.shape[0]
-        Nc, Nf = model.num_coarse, model.num_fine
-        flags = _call_flags(model, need_grad)
-        ws = model._workspace(B, flags)  # (inside NeRFModel.render: the frame's one workspace, sized for its longest call)
-        # rendering loops (`with model.frozen_weights():`): the packed weight image a previous call of the SAME frozen section
-        # left in this workspace is reused.  Outside such a section the image is rebuilt on every call (12 us): a version
-        # stamp cannot see writes through `.data`, dist.broadcast or raw pointers.
-        reuse = model._frozen and not need_grad and (ws.data_ptr(), flags) in model._packed
-        call_flags = flags | (_abi.WEIGHTS_UNCHANGED if reuse else 0)
-        dev = row.device
-        C_c = torch.empty(B, 3, dtype=torch.float32, device=dev)
-        C_f = torch.empty(B, 3, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        wptr = _abi.ptr_array(params)
+def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None):
+    """One nerf_hip_forward call on the model's workspace -> (C_coarse, C_fine, ws, flags).  maps ([B, 4] fp32, inference calls only):
+    nerf_hip_forward_maps instead, which also fills maps with each ray's (D_c, A_c, D_f, A_f) and leaves the colours' bits as they are."""
+    B = row.shape[0]
+    Nc, Nf = model.num_coarse, model.num_fine
+    flags = _call_flags(model, need_grad)
+    ws = model._workspace(B, flags)  # (inside NeRFModel.render: the frame's one workspace, sized for its longest call)
+    # rendering loops (`with model.frozen_weights():`): the packed weight image a previous call of the SAME frozen section
+    # left in this workspace is reused.  Outside such a section the image is rebuilt on every call (12 us): a version
+    # stamp cannot see writes through `.data`, dist.broadcast or raw pointers.
+    reuse = model._frozen and not need_grad and (ws.data_ptr(), flags) in model._packed
+    call_flags = flags | (_abi.WEIGHTS_UNCHANGED if reuse else 0)
+    dev = row.device
+    C_c = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    C_f = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    wptr = _abi.ptr_array(params)
+    if maps is None:
         _abi.check(_abi.lib().nerf_hip_forward(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9,
                                                ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
                                                ws.data_ptr(), ws.numel(), call_flags, stream))
-        if model._frozen and not need_grad:
-            model._packed.add((ws.data_ptr(), flags))
-        model._last_ws = ws
+    else:
+        _abi.check(_abi.lib().nerf_hip_forward_maps(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9,
+                                                    ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(),
+                                                    ws.data_ptr(), ws.numel(), call_flags, stream))
+    if model._frozen and not need_grad:
+        model._packed.add((ws.data_ptr(), flags))
+    model._last_ws = ws
+    return C_c, C_f, ws, flags
+
+
+class _RenderFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, need_grad, row, col, pb, K9, ray0, *params):
+        C_c, C_f, ws, flags = _forward_call(model, need_grad, row, col, pb, K9, ray0, params)
+        B = row.shape[0]
         if need_grad:
             gen = model._ws_generation.get(flags, 0) + 1
             model._ws_generation[flags] = gen
@@ -283,18 +296,24 @@ class NeRFModel(nn.Module):
             raise ValueError(f"batch of {row.shape[0]} rays, model built for batch_ray={self.batch_ray} (nerf.py:172-176)")
         return self._launch(ps, row, column, poses_bound, K_inv)
 
-    def _launch(self, ps, row, column, poses_bound, K_inv):
+    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False):
+        """maps=True (inference only, no graph): nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4])."""
         dev = ps[0].device
         K9 = _abi.f32_array(K_inv.detach().to("cpu", torch.float32).reshape(-1).tolist())
         pb = poses_bound.to(torch.float).to(dev).contiguous()  # cast first like nerf.py:338
         row_d = row.to(dev, torch.int64).contiguous()
         col_d = column.to(dev, torch.int64).contiguous()
         ray0 = _abi.f32_array(self.ray0_near_far) if self.ray0_near_far is not None else None
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
-        C_c, C_f = _RenderFn.apply(self, need_grad, row_d, col_d, pb, K9, ray0, *ps)
+        if maps:
+            M = torch.empty(row_d.shape[0], 4, dtype=torch.float32, device=dev)
+            with torch.no_grad():
+                C_c, C_f, _, _ = _forward_call(self, False, row_d, col_d, pb, K9, ray0, ps, maps=M)
+        else:
+            need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
+            C_c, C_f = _RenderFn.apply(self, need_grad, row_d, col_d, pb, K9, ray0, *ps)
         if self.check_resample and self.resample_fault():
             raise ResampleIndexError("resample index outside [0, Nf-1] (the reference exit(0)s here, nerf.py:251-253)")
-        return C_c, C_f
+        return (C_c, C_f, M) if maps else (C_c, C_f)
 
     def train_step(self, row, column, poses_bound, K_inv, C_true):
         """The device work of one iteration of the reference's loop (nerf.py:470-473: ``model(...)``, ``ray_loss``, ``loss.backward()``) in ONE
@@ -453,21 +472,24 @@ class NeRFModel(nn.Module):
         return mesh.Mesh(verts, faces, normals, rgb)
 
     @torch.no_grad()
-    def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):
+    def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False):
         """Inference over a LONG list of rays (a frame, a test set) -- rays [lo, hi) of it -- with the reference's batch semantics and few
         kernel calls: the list is the sequence of batches [g*batch_ray, (g+1)*batch_ray) the reference's display loop feeds to `forward`
         (nerf.py:503-520), every ray gets exactly the bits a per-batch `forward` gives it (`fuse_plan`: consecutive batches whose ray 0
         has the same near / far share a launch of up to `fuse_rays` rays), and a 400-ray batch size no longer means 400-ray launches
         (0.71 of the fp32 roof, a fifth of the chip for the bf16 kernels).  The tail batch is rendered too (the reference drops it,
-        nerf.py:442), with its own ray 0.  The weights must not change during the call.  Returns (C_coarse, C_fine) [hi - lo, 3]."""
+        nerf.py:442), with its own ray 0.  The weights must not change during the call.  Returns (C_coarse, C_fine) [hi - lo, 3].
+        maps=True: every call is a nerf_hip_forward_maps call (same colour bits) and the return is (C_coarse, C_fine, maps) with maps
+        [hi - lo, 4] = each ray's (D_c, A_c, D_f, A_f): expected depth and accumulated opacity of the coarse and the fine composite."""
         ps = self._params()
         dev = ps[0].device
         n, Bm = row.shape[0], self.batch_ray
         hi = n if hi is None else hi
         C_c = torch.empty(max(hi - lo, 0), 3, dtype=torch.float32, device=dev)
         C_f = torch.empty_like(C_c)
+        M = torch.empty(max(hi - lo, 0), 4, dtype=torch.float32, device=dev) if maps else None
         if hi <= lo:
-            return C_c, C_f
+            return (C_c, C_f, M) if maps else (C_c, C_f)
         starts = torch.arange(0, n, Bm)
         nf0 = poses_bound[starts.to(poses_bound.device)][:, 15:17].to(torch.float32).cpu().tolist()  # ONE host copy per call
         plan = fuse_plan(nf0, n, Bm, lo, hi, fuse_rays)
@@ -486,14 +508,16 @@ class NeRFModel(nn.Module):
                         # over explicitly, so the real ray's bits do not change
                         k = MIN_CALL_RAYS - (e - s)
                         r_, c_, p_ = (torch.cat((x, x[-1:].expand(k, *x.shape[1:]))) for x in (r_, c_, p_))
-                    c, f = self._launch(ps, r_, c_, p_, K_inv)
-                    C_c[s - lo:e - lo] = c[: e - s]
-                    C_f[s - lo:e - lo] = f[: e - s]
+                    out = self._launch(ps, r_, c_, p_, K_inv, maps=maps)
+                    C_c[s - lo:e - lo] = out[0][: e - s]
+                    C_f[s - lo:e - lo] = out[1][: e - s]
+                    if maps:
+                        M[s - lo:e - lo] = out[2][: e - s]
         finally:
             self.ray0_near_far, self._ws_capacity = prev_ray0, prev_cap
         if getattr(self, "bf16_mlp", False):
             self.read_status()  # a frame is not handed out on a poisoned weight image (raises on STATUS_PREP_TIMEOUT; one sync per frame)
-        return C_c, C_f
+        return (C_c, C_f, M) if maps else (C_c, C_f)
 
 
 def grid_shape(res) -> tuple:

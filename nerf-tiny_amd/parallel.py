@@ -242,7 +242,7 @@ def batch_shard_bounds(n: int, batch: int, rank: int, world: int) -> tuple[int, 
 
 
 def render_rows_sharded(model, row, col, poses_bound, K_inv, rank: int, world: int, out: torch.Tensor | None = None,
-                        align_to_batches: bool = True, fuse_rays: int = 16384):
+                        align_to_batches: bool = True, fuse_rays: int = 16384, maps: bool = False):
     """Inference over a long list of rays (e.g. one frame): this rank renders a contiguous range [lo, hi) in batches of
     model.batch_ray.  No collective.  Returns (lo, hi, C_fine[hi-lo, 3]).
 
@@ -250,21 +250,27 @@ def render_rows_sharded(model, row, col, poses_bound, K_inv, rank: int, world: i
     ray 0 OF EACH BATCH (nerf.py:233, quirk Q6).  To return the same pixels for any sharding, every kernel call here covers
     rays of reference batches that agree in their ray 0's (near, far) and is handed that pair (`nerf.fuse_plan`; `fuse_rays` = the
     longest call, `model.batch_ray` = one call per batch as up to round 2); with `align_to_batches` (default) shards start
-    on the batch grid.  The reference silently drops the tail batch (nerf.py:442); here it is rendered, with its own ray 0."""
+    on the batch grid.  The reference silently drops the tail batch (nerf.py:442); here it is rendered, with its own ray 0.
+    maps=True: returns (lo, hi, C_fine, maps[hi-lo, 4]) with NeRFModel.render's per-ray (D_c, A_c, D_f, A_f) (`out` gets C_fine only)."""
     n, Bm = row.shape[0], model.batch_ray
     lo, hi = batch_shard_bounds(n, Bm, rank, world) if align_to_batches else shard_bounds(n, rank, world)
     # NeRFModel.render: the batches of this range that share their ray 0's (near, far) share kernel calls (same bits per ray)
-    C = model.render(row, col, poses_bound, K_inv, lo, hi, fuse_rays=fuse_rays)[1] if hi > lo else torch.empty(0, 3)
+    if hi > lo:
+        r = model.render(row, col, poses_bound, K_inv, lo, hi, fuse_rays=fuse_rays, maps=maps)
+        C, M = r[1], (r[2] if maps else None)
+    else:
+        C, M = torch.empty(0, 3), torch.empty(0, 4)
     if out is not None and hi > lo:
         out[lo:hi] = C
-    return lo, hi, C
+    return (lo, hi, C, M) if maps else (lo, hi, C)
 
 
 def gather_rows(C_local: torch.Tensor, n_total: int, rank: int, world: int, group=None, bounds=None, batch: int | None = None) -> torch.Tensor:
     """Assemble the full [n_total, 3] picture on every rank (outside the timed data path).  The shards must be the ones the rows
     were rendered with: `batch` = model.batch_ray for the output of `render_rows_sharded` with its default `align_to_batches`
     (shards on the reference's batch grid, `batch_shard_bounds`); `bounds` = an explicit list of every rank's (lo, hi); neither =
-    plain `shard_bounds`.  A local shard of another length than this rank's entry is an error, never silently misplaced."""
+    plain `shard_bounds`.  A local shard of another length than this rank's entry is an error, never silently misplaced.
+    Rows of another width (the [rows, 4] maps of `render_rows_sharded(..., maps=True)`) are gathered the same way: [n_total, width]."""
     if bounds is not None and batch is not None:
         raise ValueError("gather_rows: give `bounds` or `batch`, not both")
     if bounds is not None:
@@ -280,7 +286,7 @@ def gather_rows(C_local: torch.Tensor, n_total: int, rank: int, world: int, grou
     if world == 1:
         return C_local
     mx = max(h - l for l, h in sizes)
-    pad = torch.zeros(mx, 3, dtype=C_local.dtype, device=C_local.device)
+    pad = torch.zeros(mx, *C_local.shape[1:], dtype=C_local.dtype, device=C_local.device)
     pad[: C_local.shape[0]] = C_local
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)

@@ -416,9 +416,17 @@ class NeRFRunner:
         return out
 
     # nerf.py:503-530
-    def display(self, save=True):
+    def display(self, save=True, maps=False):
+        """Renders every display frame (white where the reference's loop leaves a pixel out) and returns them, [pic, H, W, 3] numpy.
+        maps=True: also the fine expected depth and accumulated opacity of every rendered pixel (NeRFModel.render(maps=True): D_f, A_f;
+        NaN depth and 0 opacity where the frame stays white), returned as (frames, depth, acc) with depth / acc [pic, H, W] fp32; with save,
+        rank 0 also writes ``<results_path><start_time>_<last_iter>_maps.npz`` (``depth``, ``acc``, and every frame's ``near`` / ``far``)
+        and ``<i>_depth.png`` (depth normalised by the frame's near / far) and ``<i>_acc.png`` previews beside the frames."""
         rays = self.disp_rays
         result = torch.full((rays.pic_num, self.height, self.width, 3), 1.0, device=self.device)
+        if maps:
+            depth = torch.full((rays.pic_num, self.height, self.width), float("nan"), device=self.device)
+            acc = torch.zeros((rays.pic_num, self.height, self.width), device=self.device)
         self.model.eval()
         # the reference's loop (batches of batch_ray rays in pixel order, the tail < batch stays white) through NeRFModel.render: batches
         # whose ray 0 has the same near / far share kernel calls -- same bits per pixel, launches of up to 16,384 rays instead of 400
@@ -435,11 +443,16 @@ class NeRFRunner:
                     if self.distributed:
                         # cfg5: the chunk's reference batches dealt out over the ranks (shards on the batch grid, every call handed its
                         # batches' ray 0: same pixels for any world size), NO collective in the data path; the picture is assembled after
-                        _, _, C_loc = par.render_rows_sharded(self.model, row, col, poses_bound, self.K_inv, self.rank, self.world)
-                        C_fine = par.gather_rows(C_loc.to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray)
+                        r = par.render_rows_sharded(self.model, row, col, poses_bound, self.K_inv, self.rank, self.world, maps=maps)
+                        C_fine = par.gather_rows(r[2].to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray)
+                        M = par.gather_rows(r[3].to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray) if maps else None
                     else:
-                        _, C_fine = self.model.render(row, col, poses_bound, self.K_inv)
+                        r = self.model.render(row, col, poses_bound, self.K_inv, maps=maps)
+                        C_fine, M = r[1], (r[2] if maps else None)
                     result[pic, row, col] = C_fine
+                    if maps:
+                        depth[pic, row, col] = M[:, 2]
+                        acc[pic, row, col] = M[:, 3]
         finally:
             self.model.batch_ray = prev_batch
         result = result.cpu().numpy()
@@ -461,4 +474,22 @@ class NeRFRunner:
                                  (result * 255.0).astype(np.uint8), fps=30)
             except Exception:
                 pass  # imageio is optional (absent offline)
-        return result
+        if not maps:
+            return result
+        depth, acc = depth.cpu().numpy(), acc.cpu().numpy()
+        if save and self.rank == 0:
+            import numpy as np
+
+            nf = rays.poses[:, 15:17].cpu().numpy()  # every frame's near / far as the kernels see them
+            np.savez(self.results_path + self.start_time + "_" + str(self.last_iter) + "_maps.npz", depth=depth, acc=acc,
+                     near=nf[:, 0].copy(), far=nf[:, 1].copy())
+            try:
+                import matplotlib.pyplot as plt
+
+                for i in range(rays.pic_num):
+                    d = (depth[i] - nf[i, 0]) / (nf[i, 1] - nf[i, 0])
+                    plt.imsave(save_dir + str(i) + "_depth.png", np.nan_to_num(d, nan=1.0).clip(0, 1), cmap="gray", vmin=0.0, vmax=1.0)
+                    plt.imsave(save_dir + str(i) + "_acc.png", acc[i].clip(0, 1), cmap="gray", vmin=0.0, vmax=1.0)
+            except Exception as e:  # pragma: no cover
+                print("display: could not write map previews:", e)
+        return result, depth, acc

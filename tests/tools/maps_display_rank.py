@@ -1,0 +1,42 @@
+"""One rank of a tile-sharded NeRFRunner.display(maps=True), started by tests/test_gpu_maps.py in a FRESH child process: under
+``python -m torch.distributed.run ... maps_display_rank.py OUT_DIR`` with NERF_DIST_BACKEND=gloo (every rank on the box's one GPU), or
+plainly (``python maps_display_rank.py OUT_DIR``: the single-process runner the ranks are compared with).  No training: the frames, depth
+and opacity of the initial weights (rank 0's, broadcast).  Rank 0 writes OUT_DIR/result.pt = {frame, depth, acc, world}.
+"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    out = sys.argv[1]
+    if os.environ.get("NERF_DIST_BACKEND") == "gloo":
+        os.environ["LOCAL_RANK"] = "0"  # every rank of the rehearsal on the box's one GPU
+
+    import torch
+
+    import nerf_tiny_amd as P
+
+    torch.manual_seed(0)
+    scene = P.data.synthetic_scene(n_pic=3, H=24, W=24, seed=4)
+    kw = dict(gpu=0, img_dir="", results_path=os.path.join(out, "res") + "/", ckpt_path=os.path.join(out, "ck") + "/", low_res=1, total_iter=1,
+              batch_ray=100, learning=1e-3, lr_gamma=0.1, lr_milestone=[10, 200], n_coarse=32, n_fine=64, data_type="sync", step=1,
+              decay_end=10000, sched="EXP", datasets={"train": scene, "val": scene, "test": scene}, log_every=1, on_resample_fault="warn")
+    run = P.NeRFRunner(continue_=False, **kw)
+    frame, depth, acc = run.display(save=True, maps=True)
+    if run.rank == 0:
+        os.makedirs(out, exist_ok=True)
+        torch.save({"frame": torch.from_numpy(frame), "depth": torch.from_numpy(depth), "acc": torch.from_numpy(acc), "world": run.world},
+                   os.path.join(out, "result.pt"))
+    if run.distributed:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    print("MAPS-DISPLAY-OK")
+
+
+if __name__ == "__main__":
+    main()
