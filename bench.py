@@ -3,9 +3,11 @@
 
 A "step" = one full forward of the hot path (ray generation, 64 coarse + 128 fine samples per ray,
 encode, 8x256 MLP per sample, resample, merge/sort, composite) over one batch of 4096 synthetic rays of
-a 400x400 lego-like view, fp32, inputs already resident in HBM.  That is the headline `value`.  The same run
-also times the other three configurations of the path (fp32 train step, bf16-MLP forward and train step: BASELINE.json
-cfg3) for a fraction of a second each and reports them under `extra`, each with its own roofline block.
+a 400x400 lego-like view, fp32, inputs already resident in HBM.  That is the headline `value`.  A plain run does only what
+that figure needs: set-up, W warm-up and K timed steps, the --dump-outputs arrays if asked for, the result line.  With --full
+the same run also times the other configurations of the path (fp32 train step, bf16-MLP forward and train step: BASELINE.json
+cfg3; the split-fp32 forms) for a fraction of a second each, reports them under `extra`, each with its own roofline block, and
+adds everything marked --full below.
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W
   * N > 1 and no RANK in the environment: this process only LAUNCHES -- before torch.cuda or the HIP library is touched it
@@ -15,15 +17,16 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     batches -- image-space ray batches are independent units, so the data path has no collective: scaling = "weak".
     The train legs add the one real exchange of the path, a SUM all-reduce of the 593,924 fp32 gradients (2.27 MiB) in one
     flat bucket the backward kernels write straight into; its measured time is reported (`allreduce_ms`).
-    The same line also carries the STRONG-scaling form of the legs (`extra.strong_*`: one 4096-ray batch split 4096/N, the global
+    --full: the line also carries the STRONG-scaling form of the legs (`extra.strong_*`: one 4096-ray batch split 4096/N, the global
     ray 0's spacing forwarded to every shard, each with its `allreduce_ms`) -- north_star's ">= 6x strong scaling to 8 GPUs".
-  * N = 1: `per_rank_proxy` times what one rank of that 8-GPU job does with its share (512 rays; and the reference's default batch of
-    400 rays, conf/lego.ini:7) + a single-rank RCCL all-reduce, and reports `implied_strong_scaling_8 = t(4096) / (t(512) + allreduce)`.
-  * `parity`: the timed configuration rendered once on the golden cfg2 fixture against the REFERENCE's own outputs (max-rel, PSNR).
+  * N = 1, --full: `per_rank_proxy` times what one rank of that 8-GPU job does with its share (512 rays; and the reference's default batch
+    of 400 rays, conf/lego.ini:7) + a single-rank RCCL all-reduce, and reports `implied_strong_scaling_8 = t(4096) / (t(512) + allreduce)`.
+  * --full: `parity`, the timed configuration rendered once on the golden cfg2 fixture against the REFERENCE's own outputs (max-rel, PSNR);
+    at N = 1 also `frame_render` (one 400 x 400 frame) and `cpu_baseline` (the oracle on this host's cores).
   * `n_gpus` in the line is `dist.get_world_size()`, not the flag.
-Rank 0 prints ONE JSON line of at most 4 KB (compact_line: the contract's keys, `roofline`, `cpu_baseline`, `parity`, a few scalars of the other
-legs); the full record -- `extra`, `roofline_phases`, `per_rank_proxy`, `frame_render`, every note -- goes to bench_extra.json beside this
-script (--side-file) and, prefixed "bench_extra: ", to stderr.
+Rank 0 prints ONE JSON line of at most 4 KB (compact_line: the contract's keys, `roofline` and, with --full, `cpu_baseline`, `parity`, a few
+scalars of the other legs); the full record -- `extra`, `roofline_phases`, `per_rank_proxy`, `frame_render`, every note -- goes to
+bench_extra.json beside this script (--side-file) and, prefixed "bench_extra: ", to stderr.
 """
 import argparse
 import json
@@ -735,8 +738,12 @@ def main():
                     help="train legs: forward, ray_loss, backward as three calls through torch.autograd (the reference's call surface) instead of "
                          "NeRFModel.train_step, the one library call NeRFRunner.trainer makes (same kernels, same results)")
     ap.add_argument("--overlap", action="store_true", help="N > 1 train legs: overlap the early part of the all-reduce with the last weight-gradient products")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="only the leg named by --mode/--mlp (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: the other legs (and at N > 1 their strong-scaling form), at N = 1 the per-rank proxy, "
+                         "a 400 x 400 frame and the CPU baseline, and the parity check against the reference's outputs.  Without it the "
+                         "run times the headline leg alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other legs, proxy, frame and parity (profiling runs)")
     ap.add_argument("--side-file", default=None, help="where the full record goes (default: bench_extra.json beside this script); the stdout line "
                                                       "is the compact <= 4 KB form of it")
     ap.add_argument("--dry", action="store_true", help="CPU rehearsal of the launcher + process group over gloo (no kernels; tests only)")
@@ -838,6 +845,8 @@ def main():
         for name, a in dumped.items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     rep = leg_report(head, elapsed, prof, ar_ms, args.steps, args.warmup, world, b_local, strong)
+    # everything below that runs more kernels, or the CPU oracle, is --full's: a plain run ends with the headline leg
+    more = args.full and not args.no_extra
     extra = {}
     # (name, train, bf16, timed steps, warm-up steps): every leg is timed over >= 0.1 s
     legs = (("forward_f32", False, False, 20, 3), ("train_f32", True, False, 8, 2), ("forward_bf16", False, True, 160, 8), ("train_bf16", True, True, 40, 4),
@@ -866,7 +875,7 @@ def main():
             r["step_hbm"]["frac"] = round(r["step_hbm"]["frac"] * scale, 4)
         return r
 
-    if not args.no_extra:
+    if more:
         for name, train, bf16, k, w in legs:
             split = name.endswith("_split")
             if (train, bf16, split) == (head.train, head.bf16, head.split):
@@ -876,7 +885,7 @@ def main():
     # ---- N > 1: the STRONG-scaling form of the same legs in the same line (north_star: ">= 6x strong scaling to 8 GPUs"): ONE 4096-ray
     # batch (the same on every rank) split into contiguous slices of 4096 / N rays, the global ray 0's spacing forwarded, one flat SUM
     # all-reduce per train step where the reference has loss.backward(); optimizer.step() (nerf.py:473-474)
-    if dist is not None and not strong and not args.no_extra and B % world == 0:  # (also in the single-rank RCCL rehearsal: same code path)
+    if dist is not None and not strong and more and B % world == 0:  # (also in the single-rank RCCL rehearsal: same code path)
         g_full = synth_inputs(seed=1000)
         g_full = (g_full[0], g_full[1], g_full[2], g_full[4])
         bs = B // world
@@ -889,7 +898,7 @@ def main():
     # ---- N = 1: what ONE rank of an 8-GPU strong-scaling job does with its share, measured here: 512 rays (4096 / 8) and the reference's
     # own default batch of 400 rays (conf/lego.ini:7), the first rays of the same batch (global ray 0 = local ray 0)
     proxy = None
-    if world == 1 and dist is None and not strong and not args.no_extra:
+    if world == 1 and dist is None and not strong and more:
         proxy = {}
         t_full = {name: (rep["ms_per_step"] if (train, bf16, name.endswith("_split")) == (head.train, head.bf16, head.split) else extra[name]["ms_per_step"])
                   for name, train, bf16, _, _ in legs}
@@ -978,7 +987,7 @@ def main():
     # ---- parity of the timed configuration, in the line: the reference's OWN outputs for cfg2 (tests/golden/cfg2_lego_rand4096.npz: inputs,
     # weight seed and the C_coarse / C_fine the reference returned in the build container) against this library's render of the same
     parity = None
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and more:
         try:
             parity = parity_block(model, dev)
         except Exception as ex:
@@ -1013,7 +1022,7 @@ def main():
             out["parity"] = parity
         if extra:
             out["extra"] = extra
-        if world == 1 and not args.no_extra:
+        if world == 1 and more:
             try:
                 out["frame_render"] = frame_render_block(dev)
             except Exception as ex:
@@ -1022,7 +1031,7 @@ def main():
             out["per_rank_proxy"] = proxy
             out["implied_strong_scaling_8"] = proxy["implied_strong_scaling_8"]  # upper bound: see per_rank_proxy.note
             out["implied_strong_scaling_8_with_ring_estimate"] = proxy["implied_strong_scaling_8_with_ring_estimate"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline()
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = round(rep["value"] / cb["value"], 1)

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/final
 mkdir -p $OUT
 cd $ROOT
-python3 bench.py --steps 50 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (default line: forward fp32 + extra legs + cpu baseline) done"
+python3 bench.py --steps 50 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (full record: forward fp32 + extra legs + cpu baseline) done"
 python3 bench.py --mode train --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $OUT/bench_train.json 2> $OUT/bench_train.err && echo "bench train done"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o fwd -- python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $OUT/fwd_under_rocprof.json 2> $OUT/fwd_rocprof.err && echo "rocprof fwd done"

@@ -8,7 +8,7 @@ TAG=${1:-r03}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT $ROOT/gpurun_out/pmc
 cd $ROOT
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (default line) done"
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (full record) done"
 cd /tmp && export TMPDIR=/tmp
 for leg in "fwd_f32:--mode forward --mlp f32 --steps 20 --warmup 3" "train_f32:--mode train --mlp f32 --steps 6 --warmup 2" "fwd_bf16:--mode forward --mlp bf16 --steps 40 --warmup 5" "train_bf16:--mode train --mlp bf16 --steps 10 --warmup 3" "split_fwd:--mode forward --split --steps 30 --warmup 4"; do
   name=${leg%%:*}; args=${leg#*:}

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT $ROOT/gpurun_out/pmc
 cd $ROOT
 echo "[collect] bench default line"
-python3 bench.py --side-file $OUT/bench_extra.json > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (default line) done: $(wc -c < $OUT/bench_default.json) bytes"
+python3 bench.py --full --side-file $OUT/bench_extra.json > $OUT/bench_default.json 2> $OUT/bench_default.err && echo "bench (full record) done: $(wc -c < $OUT/bench_default.json) bytes"
 cd /tmp && export TMPDIR=/tmp
 for leg in "fwd_f32:--mode forward --mlp f32 --steps 20 --warmup 3" "train_f32:--mode train --mlp f32 --steps 6 --warmup 2" "fwd_bf16:--mode forward --mlp bf16 --steps 40 --warmup 5" "train_bf16:--mode train --mlp bf16 --steps 10 --warmup 3" "split_fwd:--mode forward --split --steps 30 --warmup 4" "train_split:--mode train --split --steps 10 --warmup 3"; do
   name=${leg%%:*}; args=${leg#*:}

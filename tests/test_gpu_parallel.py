@@ -56,7 +56,7 @@ def test_bench_train_leg_with_rccl_allreduce(tmp_path):
     all-reduce measured, and (side file) every extra leg present with its own roofline block."""
     env = _env()
     env["BENCH_FORCE_DIST"] = "1"
-    line, out = _bench(["--mode", "train", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env, tmp_path)
+    line, out = _bench(["--mode", "train", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env, tmp_path)
     assert out["n_gpus"] == 1 and out["config"]["mode"] == "train"
     assert line["allreduce_ms"] == out["allreduce_ms"] and line["parity"]["pass"] is True
     assert line["strong_train_bf16_rays_per_s"] == out["extra"]["strong_train_bf16"]["value"]
@@ -83,11 +83,11 @@ def test_bench_train_leg_with_rccl_allreduce(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_bench_default_line_carries_the_per_rank_proxy(tmp_path):
-    """The driver's command (`python bench.py`, N = 1; fewer steps here): one compact JSON line with roofline + parity; the side file holds
+    """The full run (`python bench.py --full`, N = 1; fewer steps here): one compact JSON line with roofline + parity; the side file holds
     the per-rank proxy of the 8-GPU strong-scaling step -- a rank's 512-ray share and the reference's 400-ray batch, the train legs also as the
     MEASURED data-parallel step (train_step + the flat SUM all-reduce behind it on a single-rank RCCL group) that `implied_strong_scaling_8` is
     computed from."""
-    line, out = _bench(["--steps", "5", "--warmup", "2", "--no-cpu-baseline"], _env(), tmp_path)
+    line, out = _bench(["--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"], _env(), tmp_path)
     assert out["n_gpus"] == 1 and out["dtype"] == "f32" and 0.0 < out["roofline"]["frac"] <= 1.0 and out["parity"]["pass"] is True
     assert line["parity"]["pass"] is True and line["implied_strong_scaling_8_min"] == min(out["implied_strong_scaling_8"].values())
     assert line["train_f32_rays_per_s"] == out["extra"]["train_f32"]["value"] and line["train_bf16_rays_per_s"] == out["extra"]["train_bf16"]["value"]
@@ -108,6 +108,20 @@ def test_bench_default_line_carries_the_per_rank_proxy(tmp_path):
     assert imp["forward_bf16"] == round(px["4096"]["forward_bf16"]["ms_per_step"] / px["512"]["forward_bf16"]["ms_per_step"], 2)
     for name, leg in px["4096"].items():  # the same step with and without the library's kernel events: within a few per cent
         assert 0.9 * leg["ms_per_step_with_kernel_events"] < leg["ms_per_step"] < 1.05 * leg["ms_per_step_with_kernel_events"], (name, leg)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("mode", ["forward", "train"])
+def test_bench_plain_run_times_the_headline_leg_alone(tmp_path, mode):
+    """The driver's command without --full: the headline leg with its own roofline (and, for the train step, its phases) from the HIP events
+    of its timed steps, and nothing else -- no other legs, no per-rank proxy, no frame, no parity, no CPU baseline."""
+    line, full = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--mode", mode], _env(), tmp_path)
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["mode"] == mode and line["dtype"] == "f32" and 0.0 < line["roofline"]["frac"] <= 1.0
+    assert (set(full.get("roofline_phases", {})) == {"forward_with_saves", "dx_chain", "dw"}) == (mode == "train")
+    for k in ("extra", "per_rank_proxy", "implied_strong_scaling_8", "frame_render", "parity", "cpu_baseline"):
+        assert k not in full, k
+    assert not any(k.endswith("_rays_per_s") for k in line) and "cpu_baseline" not in line and "parity" not in line
 
 
 @pytest.mark.timeout(900)
@@ -143,7 +157,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(tmp_path):
     all-reduce, the MAX reduction of the times, rank 0's compact line with its strong_* scalars -- the code path, not a measurement."""
     env = _env()
     env["BENCH_DIST_BACKEND"] = "gloo"
-    line, full = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env, tmp_path)
+    line, full = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], env, tmp_path)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and "rehearsal" in line
     assert line["config"]["rays_per_step_per_gpu"] == 4096 and line["value"] > 0
     for k in ("train_f32_rays_per_s", "train_bf16_rays_per_s", "strong_train_f32_rays_per_s", "strong_train_bf16_rays_per_s",
