@@ -45,7 +45,8 @@ extern "C" {
 #define NERF_HIP_ABI_VERSION 7 /* 2: NERF_HIP_BF16_MLP, nerf_hip_field_bf16; 3: nerf_hip_backward_overlap, NERF_HIP_SPLIT_MLP;
                                   4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED;
                                   7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
-                                     nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps */
+                                     nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps;
+                                     nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad */
 
 enum {
   NERF_HIP_OK = 0,
@@ -267,6 +268,31 @@ int nerf_hip_query(const float* const* weights24, const float* points, const flo
  * nx * ny * nz < 2^31.  No points buffer is formed: a 512^3 grid needs only its 512 MiB of sigma. */
 int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz,
                           float* sigma, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Point gradients of the field: the query above plus the exact-fp32 chain back to the points, for analytic
+ * surface normals and autograd through a field query.  Gradient with respect to the points only; the weights are constants here.
+ * Gradient convention (the train step's): the encoding's phase is phi = fp32(x_c * f_l), sin and cos are evaluated at that rounded
+ * phase, and d(sin phi, cos phi)/d x_c is taken as f_l * (cos phi, -sin phi) -- the rounding of the product is not differentiated.
+ * d|s|/ds = sign(s) with sign(0) = 0 at the sigma head, d relu = [pre > 0], as the train step has them.
+ * Two kernels per chunk of 131,072 points (4 rounds of one wave per SIMD): the query forward with a compact save (ReLU masks of the 8
+ * hidden layers, the sigma pre-activation, gamma_p and, with colour, the dir_info output c: 516 / 1,028 bytes per point) and the dX
+ * chain of the train step reading it.  Workspace: 72.8 MB sigma only, 207.0 MB with colour, independent of M.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of nerf_hip_query_grad: packed weight image with the transposed segments, fold, one chunk's
+ * save and (with_rgb != 0) its direction vectors.  Independent of M. */
+int nerf_hip_query_grad_ws_bytes(int with_rgb, size_t* bytes);
+
+/* sigma[M] (and rgb[M,3]) exactly as nerf_hip_query computes them at the same points, bit for bit, and the vector-Jacobian product
+ * dpoints[m] = dsigma[m] * d sigma_m / d p_m + sum_c drgb[m][c] * d rgb_m[c] / d p_m  (STORED, [M,3]).
+ * dsigma [M] or NULL (= every entry 1: dpoints is then the gradient of sigma).  dirs and rgb are both NULL (sigma only) or both set
+ * (ws sized with with_rgb = 1); drgb [M,3] only with dirs, and may be NULL there (no colour term: the sigma-only chain runs).
+ * Refused before any device work: M < 0, drgb without dirs, dirs without rgb or rgb without dirs, and with M > 0 a NULL points / sigma /
+ * dpoints or a workspace that is NULL, too small or not 256-byte aligned.  M == 0 succeeds and launches nothing.  Enqueue-only. */
+int nerf_hip_query_grad(const float* const* weights24, const float* points, const float* dirs, int M,
+                        const float* dsigma, const float* drgb, float* rgb, float* sigma, float* dpoints,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Marching cubes over a density grid: an indexed triangle mesh of the isosurface sigma == level.

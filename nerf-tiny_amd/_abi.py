@@ -49,6 +49,8 @@ _PROTOS = {
     "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
+    "nerf_hip_query_grad_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "nerf_hip_query_grad": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_mesh_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_mesh_count": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_float, _p, C.c_size_t, _p, _p]),
     "nerf_hip_mesh_emit": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_float, _p, C.c_size_t, _p, _p, _p, C.c_int64,
@@ -96,6 +98,13 @@ def query_ws_bytes(with_rgb: bool) -> int:
     """Workspace bytes of nerf_hip_query / nerf_hip_density_grid (independent of the number of points)."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_query_ws_bytes(1 if with_rgb else 0, C.byref(n)))
+    return int(n.value)
+
+
+def query_grad_ws_bytes(with_rgb: bool) -> int:
+    """Workspace bytes of nerf_hip_query_grad (independent of the number of points)."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_query_grad_ws_bytes(1 if with_rgb else 0, C.byref(n)))
     return int(n.value)
 
 

@@ -1216,6 +1216,100 @@ int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const
 
 namespace {
 
+// Workspace of the gradient queries: the packed weight image WITH the transposed segments (the chain reads them), the fold, and for ONE
+// chunk of QGRAD_CHUNK points the compact save (kernels.h QGRAD_*) and, colour queries, the dvec rows.  Independent of M.
+struct QGradLayout {
+  size_t packed, fold, dvec, save, masks, spre, total;
+};
+QGradLayout qgrad_layout(bool rgb) {
+  QGradLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  const size_t rows = (size_t)QGRAD_CHUNK + DUMP_ROWS;
+  L.packed = take((size_t)PACKED_ALL_F4 * 16);
+  L.fold = take((size_t)FOLD_FLOATS * 4);
+  L.dvec = rgb ? take((size_t)QGRAD_CHUNK * HALF * 4) : 0;
+  L.save = take(rows * (QGRAD_GP + (rgb ? QGRAD_C : 0)) * 4);
+  L.masks = take((size_t)8 * (QGRAD_CHUNK / 64) * 4 * 256 * 2);
+  L.spre = take(rows * 4);
+  L.total = o;
+  return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_query_grad_ws_bytes(int with_rgb, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  *bytes = qgrad_layout(with_rgb != 0).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_query_grad(const float* const* weights24, const float* points, const float* dirs, int M, const float* dsigma, const float* drgb,
+                        float* rgb, float* sigma, float* dpoints, void* ws, size_t ws_bytes, void* stream) {
+  if (M < 0) return fail(NERF_HIP_ERR_ARG, "M=%d < 0", M);
+  if (drgb && !dirs) return fail(NERF_HIP_ERR_ARG, "drgb needs dirs: without them no colour is computed");
+  if ((dirs == nullptr) != (rgb == nullptr)) return fail(NERF_HIP_ERR_ARG, "dirs and rgb must both be null (sigma only) or both be set");
+  const bool with_rgb = dirs != nullptr;
+  if (M == 0) return NERF_HIP_OK;  // (empty buffers may have null pointers, as for nerf_hip_query)
+  if (!points || !sigma || !dpoints) return fail(NERF_HIP_ERR_ARG, "null argument (points, sigma and dpoints are required)");
+  if (int rc = check_weights(weights24)) return rc;
+  const QGradLayout L = qgrad_layout(with_rgb);
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L.total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Weights24 w = as_w24(weights24);
+  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG, st));
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.wp = at<float4>(ws, L.packed);
+  fa.w = w;
+  fa.dvec = with_rgb ? at<float>(ws, L.dvec) : nullptr;
+  fa.save = at<float>(ws, L.save);
+  fa.masks = at<uint16_t>(ws, L.masks);
+  fa.spre = at<float>(ws, L.spre);
+  fa.tiles_tot = QGRAD_CHUNK / 64;
+  fa.MSrows = (long long)QGRAD_CHUNK + DUMP_ROWS;
+  FieldBwdArgs fb;
+  memset(&fb, 0, sizeof(fb));  // G = null: the chain writes no gradient rows
+  fb.wp = fa.wp;
+  fb.w = w;
+  fb.save = fa.save;
+  fb.masks = fa.masks;
+  fb.spre = fa.spre;
+  fb.tiles_tot = fa.tiles_tot;
+  fb.MSrows = fa.MSrows;
+  QuerySrc q;
+  memset(&q, 0, sizeof(q));
+  // chunk by chunk through the workspace (stream order: the chain has read a chunk's save before the next forward overwrites it)
+  for (int off = 0; off < M; off += QGRAD_CHUNK) {
+    const int n = (M - off < QGRAD_CHUNK) ? M - off : QGRAD_CHUNK;
+    if (with_rgb) HIP_TRY(launch_dirs_dvec(dirs + (size_t)off * 3, n, w.p[W_DIR], w.p[B_DIR], at<float>(ws, L.fold), at<float>(ws, L.dvec), st));
+    fa.rgb = with_rgb ? rgb + (size_t)off * 3 : nullptr;
+    fa.sigma = sigma + off;
+    fa.M = n;
+    fa.Mtot = n;
+    q.points = points + (size_t)off * 3;
+    HIP_TRY(launch_query_grad_fwd(fa, q, with_rgb, st));
+    fb.rgb = fa.rgb;
+    fb.drgb = drgb ? drgb + (size_t)off * 3 : nullptr;
+    fb.dsig = dsigma ? dsigma + off : nullptr;
+    fb.dt = dpoints + (size_t)off * 3;
+    fb.M = n;
+    fb.Mtot = n;
+    HIP_TRY(launch_query_grad_bwd(fb, drgb != nullptr, st));  // no drgb: the colour branch adds nothing, the sigma-only chain runs
+    if (M - off <= QGRAD_CHUNK) break;  // (off + QGRAD_CHUNK could pass INT_MAX)
+  }
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Workspace of the mesh calls: per lattice point its in-block vertex offset and owned-edge mask, then per workgroup of MESH_PTS points
 // its vertex / face totals and their 64-bit exclusive scans.
 struct MeshLayout {

@@ -6,6 +6,12 @@
 // Every layer's pre-activation gradient is streamed to the row-major G buffers by its CONSUMER, one 16-byte group per
 // lane and k-block tile, interleaved with the MFMA stream (the weight-gradient GEMMs read G afterwards).
 // FINE additionally carries d loss/d gamma_p (skip layer + layer 0) -> d loss/d point -> d loss/d t_fine (quirk Q9).
+// QUERY (nerf_hip_query_grad; FINE only): the same chain back to the points of a gradient query, from the compact save of
+// k_field_fwd_reg<..., GSAVE = true> (kernels.h QGRAD_*): upstream dsigma (null = ones) and, RGB, drgb; no G / dz / dspre rows; the
+// epilogue STORES dpoints[m][3] instead of projecting onto the ray direction.  RGB = false skips the colour head and the folded
+// point_info / dir_info layer: dh7 = w_sigma (x) dsigma_pre.  The query launch passes G = null and the layers take it as their row
+// pointer, so reg_layer_bwd's RUNTIME null test skips the stores: with a compile-time null the whole chain became one scheduling region
+// and spilled 80 bytes per lane.
 #include "field_common.h"
 
 namespace nerf {
@@ -170,8 +176,9 @@ __device__ __forceinline__ void reg_layer_bwd_thin(const int seg, const int next
 #define BSTAMP(slot) do { } while (0)
 #endif
 
-template <bool FINE>
+template <bool FINE, bool QUERY = false, bool RGB = true>
 __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
+  static_assert(FINE || !QUERY, "the query form carries the chain back to the points");
 #ifdef NERF_STAMPS
   unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = __builtin_readcyclecounter();
@@ -195,8 +202,13 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   WStageB<8> st0;
+  if constexpr (RGB) {
 #pragma unroll
-  for (int f = 0; f < 8; ++f) st0.w[f] = reg_ldw(rb, seg_off4(SEG_T_FOLD) + (f * 16) * 64);
+    for (int f = 0; f < 8; ++f) st0.w[f] = reg_ldw(rb, seg_off4(SEG_T_FOLD) + (f * 16) * 64);
+  } else {
+#pragma unroll
+    for (int f = 0; f < 8; ++f) st0.w[f] = reg_ldw(rb, seg_off4(SEG_T_L7) + (f * 32) * 64);
+  }
   auto mlayer = [&](int layer) { return mrow + (size_t)layer * MKS; };
   unsigned mfirst = mask_word(mlayer(7), 0);  // first masked layer of the chain; every later word is fetched a tile ahead
 
@@ -206,31 +218,36 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
   f32x16 D0[4];
   float ds;  // d loss / d sigma_pre of this lane's sample
   {
-    const float* crow = srow + S_C * MS;
+    const float* crow = QUERY ? a.save + (size_t)a.MSrows * QGRAD_GP + (size_t)rrow * QGRAD_C + 4 * h : srow + S_C * MS;
     float4 cv[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) cv[t][g] = *reinterpret_cast<const float4*>(crow + 32 * t + 8 * g);
     float dz[3];
+    if constexpr (RGB) {
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float o = a.rgb[(size_t)mc * 3 + ch];
-      const float up = a.drgb[(size_t)mc * 3 + ch];
-      dz[ch] = valid ? up * ((1.0f - o) * o) : 0.f;
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) cv[t][g] = *reinterpret_cast<const float4*>(crow + 32 * t + 8 * g);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float o = a.rgb[(size_t)mc * 3 + ch];
+        const float up = a.drgb[(size_t)mc * 3 + ch];
+        dz[ch] = valid ? up * ((1.0f - o) * o) : 0.f;
+      }
     }
     // sigma head upstream: sigma = |pre|, d|x|/dx with sign(0) = 0 like torch.  (dz_r, dz_g, dz_b, dsigma_pre) is the A operand
     // of the thin-heads weight-gradient product (dw_f32.hip)
     const float sp = a.spre[a.row0 + mc];
     const float sgn = sp > 0.f ? 1.0f : (sp < 0.f ? -1.0f : 0.f);
-    ds = valid ? a.dsig[mc] * sgn : 0.f;
-    if (valid && h == 0) {
+    if constexpr (QUERY)
+      ds = valid ? (a.dsig != nullptr ? a.dsig[mc] : 1.0f) * sgn : 0.f;
+    else
+      ds = valid ? a.dsig[mc] * sgn : 0.f;
+    if (!QUERY && valid && h == 0) {
       *reinterpret_cast<float4*>(a.dz + (size_t)(a.row0 + m) * 4) = make_float4(dz[0], dz[1], dz[2], ds);
       a.dspre[a.row0 + m] = ds;
     }
     const float* wc = a.w.p[W_COLOR] + 4 * h;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < (RGB ? 4 : 0); ++t) {
       float4 q0[4], q1[4], q2[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -263,20 +280,21 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
 #pragma unroll
     for (int f = 0; f < 8; ++f) B[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws[f * 32 + j], dsb, zero, 0, 0, 0);
   }
-  reg_layer_bwd<16, 8, 32, 8, false, false>(seg_off4(SEG_T_FOLD), seg_off4(SEG_T_L7), lane, D0, B, st0, nullptr, nullptr, mfirst,
-                                            grow + G_D * MS, rb);
+  if constexpr (RGB)
+    reg_layer_bwd<16, 8, 32, 8, false, false>(seg_off4(SEG_T_FOLD), seg_off4(SEG_T_L7), lane, D0, B, st0, nullptr, nullptr, mfirst,
+                                              QUERY ? a.G : grow + G_D * MS, rb);
   BSTAMP(1);  // dir_info + point_info folded, sigma head (520 MFMAs)
   BSTAMP(2);
   // ---- layers 7, 6, 5: input = raw d h_l masked by h_l > 0 (= dpre_l, stored), output = raw d h_{l-1}
   constexpr int sT7 = seg_off4(SEG_T_L7);
-  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7, sT7 + L256, lane, B, A, st0, mlayer(7), mlayer(6), mfirst, grow + 7 * MS, rb);
-  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7 + L256, sT7 + 2 * L256, lane, A, B, st0, mlayer(6), mlayer(5), mfirst, grow + 6 * MS, rb);
-  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7 + 2 * L256, seg_off4(SEG_T_L4A), lane, B, A, st0, mlayer(5), mlayer(4), mfirst, grow + 5 * MS, rb);
+  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7, sT7 + L256, lane, B, A, st0, mlayer(7), mlayer(6), mfirst, QUERY ? a.G : grow + 7 * MS, rb);
+  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7 + L256, sT7 + 2 * L256, lane, A, B, st0, mlayer(6), mlayer(5), mfirst, QUERY ? a.G : grow + 6 * MS, rb);
+  reg_layer_bwd<32, 8, 32, 8, true, true>(sT7 + 2 * L256, seg_off4(SEG_T_L4A), lane, B, A, st0, mlayer(5), mlayer(4), mfirst, QUERY ? a.G : grow + 5 * MS, rb);
   BSTAMP(3);  // layers 7..5 (3,072 MFMAs)
   // ---- layer 4 (input cat(h3, gamma_p)): d h3, and for the fine pass d gamma_p through the skip connection
   f32x16 accg[2];
   if (FINE) {
-    reg_layer_bwd<32, 8, 32, 2, true, true>(seg_off4(SEG_T_L4A), seg_off4(SEG_T_L4B), lane, A, B, st0, mlayer(4), mlayer(4), mfirst, grow + 4 * MS, rb);
+    reg_layer_bwd<32, 8, 32, 2, true, true>(seg_off4(SEG_T_L4A), seg_off4(SEG_T_L4B), lane, A, B, st0, mlayer(4), mlayer(4), mfirst, QUERY ? a.G : grow + 4 * MS, rb);
     reg_layer_bwd_thin<32, 32, 8, true, false, true>(seg_off4(SEG_T_L4B), seg_off4(SEG_T_L3), lane, A, accg, st0, mlayer(4), mlayer(3), mfirst, nullptr, rb);
   } else {
     reg_layer_bwd<32, 8, 32, 8, true, true>(seg_off4(SEG_T_L4A), seg_off4(SEG_T_L3), lane, A, B, st0, mlayer(4), mlayer(3), mfirst, grow + 4 * MS, rb);
@@ -284,19 +302,20 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
   BSTAMP(4);  // layer 4 (1,024 / 1,280 MFMAs)
   // ---- layers 3, 2, 1
   constexpr int sT3 = seg_off4(SEG_T_L3);
-  reg_layer_bwd<32, 8, 32, 8, true, true>(sT3, sT3 + L256, lane, B, A, st0, mlayer(3), mlayer(2), mfirst, grow + 3 * MS, rb);
-  reg_layer_bwd<32, 8, 32, 8, true, true>(sT3 + L256, sT3 + 2 * L256, lane, A, B, st0, mlayer(2), mlayer(1), mfirst, grow + 2 * MS, rb);
+  reg_layer_bwd<32, 8, 32, 8, true, true>(sT3, sT3 + L256, lane, B, A, st0, mlayer(3), mlayer(2), mfirst, QUERY ? a.G : grow + 3 * MS, rb);
+  reg_layer_bwd<32, 8, 32, 8, true, true>(sT3 + L256, sT3 + 2 * L256, lane, A, B, st0, mlayer(2), mlayer(1), mfirst, QUERY ? a.G : grow + 2 * MS, rb);
   unsigned mb0[8];  // coarse pass: the eight mask words of layer 0 for the epilogue, requested a whole layer ahead
   if (!FINE) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) mb0[t] = mask_word(mlayer(0), t);
   }
   reg_layer_bwd<32, 8, 32, 2, true, true, true, FINE>(sT3 + 2 * L256, FINE ? seg_off4(SEG_T_L0) : -1, lane, B, A, st0, mlayer(1),
-                                                      mlayer(0), mfirst, grow + 1 * MS, rb);
+                                                      mlayer(0), mfirst, QUERY ? a.G : grow + 1 * MS, rb);
   BSTAMP(5);  // layers 3..1 (3,072 MFMAs)
   // ---- dpre_0 = d h0 masked; fine: d gamma_p += W_0^T dpre_0
   if (FINE) {
-    reg_layer_bwd_thin<32, 32, 2, false, true, false>(seg_off4(SEG_T_L0), -1, lane, A, accg, st0, mlayer(0), nullptr, mfirst, grow, rb);
+    reg_layer_bwd_thin<32, 32, 2, false, !QUERY, false>(seg_off4(SEG_T_L0), -1, lane, A, accg, st0, mlayer(0), nullptr, mfirst,
+                                                        QUERY ? nullptr : grow, rb);
     // gamma -> point -> depth.  accg[t][4g + 2e], [.. + 1] = d loss / d (sin, cos) of pair pi = 4(4t+g) + 2h + e.
     // d gamma / d x needs (cos, -sin) of the same phases: they ARE the saved layer-0 input (tensor S_GP: this lane's eight
     // 16-byte groups hold exactly its pairs), so they are loaded, not recomputed -- 8 loads instead of ~15 sincos with their
@@ -309,8 +328,8 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
     const bool valid_e = m_e < a.M;
     const int mc_e = valid_e ? m_e : a.M - 1;
     const long long rrow_e = valid_e ? (long long)(a.row0 + m_e) : a.Mtot + j_e;
-    const float* rf = a.rayf + (size_t)(mc_e / a.N) * RAYF;
-    const float* gprow = a.save + (size_t)rrow_e * WIDTH + 4 * h_e + S_GP * ((size_t)a.MSrows * WIDTH);
+    const float* rf = QUERY ? nullptr : a.rayf + (size_t)(mc_e / a.N) * RAYF;
+    const float* gprow = QUERY ? a.save + (size_t)rrow_e * QGRAD_GP + 4 * h_e : a.save + (size_t)rrow_e * WIDTH + 4 * h_e + S_GP * ((size_t)a.MSrows * WIDTH);
     float4 gq[8];
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) gq[g8] = *reinterpret_cast<const float4*>(gprow + 8 * g8);
@@ -331,7 +350,11 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
       }
 #pragma unroll
     for (int c = 0; c < 3; ++c) dp[c] += __shfl_xor(dp[c], 32);
-    if (valid_e && h_e == 0) {
+    if (QUERY && valid_e && h_e == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) a.dt[(size_t)m_e * 3 + c] = dp[c];
+    }
+    if (!QUERY && valid_e && h_e == 0) {
       const float dtp = __builtin_fmaf(rf[RF_DWRD + 2], dp[2], __builtin_fmaf(rf[RF_DWRD + 1], dp[1], rf[RF_DWRD] * dp[0]));
       a.dt[m_e] += dtp;
     }
@@ -355,6 +378,16 @@ __global__ __launch_bounds__(64, 1) void k_field_bwd_reg(const FieldBwdArgs a) {
     atomicAdd(a.stamps + (FINE ? 30 : 31), 1ull);
   }
 #endif
+}
+
+hipError_t launch_query_grad_bwd(const FieldBwdArgs& a, bool rgb, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  const unsigned tiles = (unsigned)(((long long)a.M + RMB - 1) / RMB);
+  if (rgb)
+    hipLaunchKernelGGL((k_field_bwd_reg<true, true, true>), dim3(tiles), dim3(64), 0, st, a);
+  else
+    hipLaunchKernelGGL((k_field_bwd_reg<true, true, false>), dim3(tiles), dim3(64), 0, st, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_field_bwd_reg(const FieldBwdArgs& a, bool fine, hipStream_t st) {

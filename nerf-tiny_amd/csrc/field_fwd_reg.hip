@@ -14,7 +14,7 @@
 //   * biases enter as one extra MFMA per tile (A = bias, B = 1 on lane half 0); the sigma and colour heads are
 //     VALU dot products over the registers the wave already holds.
 // One wave per SIMD (about 400 VGPRs).  Used when nothing has to be saved for backward, and for the point queries (k_field_fwd_reg's
-// SRC / RGB template arguments below).
+// SRC / RGB template arguments below) -- with GSAVE, the forward of a gradient query (nerf_hip_query_grad).
 #include "field_common.h"
 
 namespace nerf {
@@ -48,15 +48,17 @@ __device__ __forceinline__ float f4c(const float4& v, int c) { return c == 0 ? v
 // the compiler from sinking the requests towards their uses.  st0 holds k-block 0 on entry and the next segment's
 // k-block 0 on exit.  bv (8 bias rows of this lane) != nullptr: one extra MFMA per tile starts the accumulator
 // at the bias (A = bias on every lane, B = 1 on lane half 0, C = 0).
-// Training (SAVE): the CONSUMER layer writes its activated input tiles to the row-major save buffer (lane (j, h) owns
+// Training (SAVE = 1): the CONSUMER layer writes its activated input tiles to the row-major save buffer (lane (j, h) owns
 // the 16-byte groups 32t + 8g + 4h of row j) and, for ReLU inputs, the u16 mask words in the tile kernels' layout.
+// Gradient queries (SAVE = 2, the compact save): a ReLU-input layer writes only its mask words, the layer-0 input (gamma_p) only its rows
+// -- the activation rows feed weight gradients alone, and a point gradient needs none.
 struct SaveIn {
   float* rows;      // &save[tensor][this lane's row][4h]   (null = nothing to save); lanes past the end of the pass own a dump
                     // row behind the tensor (kernels.h: MSrows), so no store carries a predicate
   uint16_t* mask;   // &masks[layer][tile64][st][h*32 + j] (null = no masks); entry (f, wv) at + (f*2)*256 + wv*64
 };
 
-template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, bool SAVE = false>
+template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, int SAVE = 0>
 __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* float4 offsets into the packed image; < 0: none */, int lane,
                                           const f32x16* prev, f32x16* acc, WStage<8>& st0, const float* bv,
                                           const SaveIn sv, const RegBuf& rb) {
@@ -71,21 +73,21 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
   f32x16 tin[2];
   auto activate = [&](int t) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tin[t & 1][r] = RELU_IN ? (SAVE ? fmaxf(prev[t][r], 0.f) : relu1(prev[t][r])) : prev[t][r];  // (the training variant's register allocation falls apart with the integer form)
+    for (int r = 0; r < 16; ++r) tin[t & 1][r] = RELU_IN ? (SAVE == 1 ? fmaxf(prev[t][r], 0.f) : relu1(prev[t][r])) : prev[t][r];  // (the training variant's register allocation falls apart with the integer form)
     // pin the activated tile to this program point; without it the compiler hoists every tile's ReLU to the top of the
     // layer and spills ~370 registers
 #pragma unroll
     for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(tin[t & 1][r]));
-    if (SAVE) {  // compile-time: a SAVE layer always has rows, a SAVE && RELU_IN layer always has masks (no null tests in the stream)
+    if (SAVE == 1 || (SAVE == 2 && !RELU_IN)) {  // compile-time: such a layer always has rows, a SAVE && RELU_IN layer always has masks
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         store_row4(sv.rows + 32 * t + 8 * g, make_float4(tin[t & 1][4 * g], tin[t & 1][4 * g + 1], tin[t & 1][4 * g + 2], tin[t & 1][4 * g + 3]));
-      if (RELU_IN) {
-        unsigned bits = 0;
+    }
+    if (SAVE != 0 && RELU_IN) {
+      unsigned bits = 0;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) bits |= (prev[t][r] > 0.f) ? (1u << r) : 0u;
-        sv.mask[((t & 1) * 2) * 256 + (t >> 1) * 64] = (uint16_t)bits;  // feature tile t = (wave t>>1, f = t&1)
-      }
+      for (int r = 0; r < 16; ++r) bits |= (prev[t][r] > 0.f) ? (1u << r) : 0u;
+      sv.mask[((t & 1) * 2) * 256 + (t >> 1) * 64] = (uint16_t)bits;  // feature tile t = (wave t>>1, f = t&1)
     }
   };
   activate(0);
@@ -143,9 +145,11 @@ __device__ __forceinline__ void bias_load(const float* __restrict__ bias, int la
 // RGB = false: sigma only -- the folded point_info / dir_info layer (512 of the 8,256 MFMAs per tile) and the colour head are skipped.
 // The query forms are template arguments of THIS kernel rather than a shared inline body: moving the body into a function changes the
 // register allocation of the forward instantiations, and these must stay instruction for instruction what they were.
+// GSAVE (gradient queries, SRC_POINTS only; nerf_hip_query_grad): the compact save that k_field_bwd_reg's query form reads -- the ReLU
+// masks of h0..h7, spre, gamma_p rows and (RGB) the c rows, laid out as kernels.h QGRAD_* describes; no activation rows.
 enum { SRC_RAYS = 0, SRC_POINTS = 1, SRC_LATTICE = 2 };
 
-template <bool SAVE, bool DEBUG, int SRC = SRC_RAYS, bool RGB = true>
+template <bool SAVE, bool DEBUG, int SRC = SRC_RAYS, bool RGB = true, bool GSAVE = false>
 __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, const QuerySrc q) {
 #ifdef NERF_STAMPS
   unsigned long long tsum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -216,10 +220,15 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   const size_t MS = (size_t)a.MSrows * WIDTH;
   const long long rrow = valid ? (long long)(a.row0 + m) : a.Mtot + j;  // lanes past the end: dump row
   float* const srow = SAVE ? a.save + (size_t)rrow * WIDTH + 4 * h : nullptr;
-  uint16_t* const mrow = SAVE ? a.masks + ((size_t)(a.tile0 + (m0 >> 6)) * 4 + ((m0 >> 5) & 1)) * 256 + h * 32 + j : nullptr;
+  uint16_t* const mrow = (SAVE || GSAVE) ? a.masks + ((size_t)(a.tile0 + (m0 >> 6)) * 4 + ((m0 >> 5) & 1)) * 256 + h * 32 + j : nullptr;
   const size_t MKS = (size_t)a.tiles_tot * 4 * 256;
   auto sv_rows = [&](int tensor) { return SaveIn{SAVE ? srow + (size_t)tensor * MS : nullptr, nullptr}; };
   auto sv_relu = [&](int layer) { return SaveIn{SAVE ? srow + (size_t)layer * MS : nullptr, SAVE ? mrow + (size_t)layer * MKS : nullptr}; };
+  // gradient queries: gamma_p rows of QGRAD_GP floats, then (RGB) c rows of QGRAD_C floats, MSrows rows each
+  float* const gprow = GSAVE ? a.save + (size_t)rrow * QGRAD_GP + 4 * h : nullptr;
+  float* const crow = GSAVE ? a.save + (size_t)a.MSrows * QGRAD_GP + (size_t)rrow * QGRAD_C + 4 * h : nullptr;
+  constexpr int SV = SAVE ? 1 : (GSAVE ? 2 : 0);
+  auto sv_in = [&](int layer) { return GSAVE ? SaveIn{nullptr, mrow + (size_t)layer * MKS} : sv_relu(layer); };
 
   RSTAMP(0);  // prologue: ray / depth loads, sample point, positional encoding
   // two accumulator sets ping-pong: a layer reads the previous layer's raw accumulators (ReLU applied lazily)
@@ -231,28 +240,28 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
 
   // ---- layer 0: gamma_p 60(64) -> 256
   bias_load<8>(a.w.p[B_L0], lane, bv);
-  reg_layer<8, 8, 32, 8, true, false, SAVE>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bv, sv_rows(S_GP), rb);
+  reg_layer<8, 8, 32, 8, true, false, SV>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bv, GSAVE ? SaveIn{gprow, nullptr} : sv_rows(S_GP), rb);
   RSTAMP(1);  // layer 0 (264 MFMAs)
   // ---- layers 1..3 (the segment after L3 is L4A: same shape)
   bias_load<8>(a.w.p[3], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SAVE>(sL1, sL1 + L256, lane, A, B, st0, bv, sv_relu(0), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV>(sL1, sL1 + L256, lane, A, B, st0, bv, sv_in(0), rb);
   bias_load<8>(a.w.p[5], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SAVE>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bv, sv_relu(1), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bv, sv_in(1), rb);
   bias_load<8>(a.w.p[7], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SAVE>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bv, sv_relu(2), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bv, sv_in(2), rb);
   RSTAMP(2);  // layers 1..3 (3,096 MFMAs)
   // ---- layer 4: cat(h3, gamma_p), hidden first (nerf.py:109)
   bias_load<8>(a.w.p[9], lane, bv);
-  reg_layer<32, 8, 8, 8, true, true, SAVE>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bv, sv_relu(3), rb);
+  reg_layer<32, 8, 8, 8, true, true, SV>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bv, sv_in(3), rb);
   reg_layer<8, 8, 32, 8, false, false>(seg_off4(SEG_L4B), sL5, lane, gp, A, st0, nullptr, SaveIn{nullptr, nullptr}, rb);
   RSTAMP(3);  // layer 4 (1,288 MFMAs)
   // ---- layers 5..7 (the segment after L7 is the folded point_info / dir_info layer: 4 tiles)
   bias_load<8>(a.w.p[11], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SAVE>(sL5, sL5 + L256, lane, A, B, st0, bv, sv_relu(4), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV>(sL5, sL5 + L256, lane, A, B, st0, bv, sv_in(4), rb);
   bias_load<8>(a.w.p[13], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SAVE>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_relu(5), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_in(5), rb);
   bias_load<8>(a.w.p[15], lane, bv);
-  reg_layer<32, 8, 32, 4, true, true, SAVE>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_relu(6), rb);
+  reg_layer<32, 8, 32, 4, true, true, SV>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_in(6), rb);
   RSTAMP(4);  // layers 5..7 (3,096 MFMAs)
   // ---- sigma head on h7 = relu(B) (VALU): sigma = |w_sigma . h7 + b|  (nerf.py:94, 115)
   {
@@ -270,6 +279,12 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
         for (int g = 0; g < 4; ++g) wq[(t + 1) & 1][g] = *reinterpret_cast<const float4*>(ws + 32 * (t + 1) + 8 * g);
       }
       if (SAVE) __builtin_amdgcn_sched_barrier(0);
+      if (GSAVE) {  // the mask of h7, here in both forms (the fold layer, which stores it in training, does not run without colour)
+        unsigned bits = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bits |= (B[t][r] > 0.f) ? (1u << r) : 0u;
+        mrow[7 * MKS + ((t & 1) * 2) * 256 + (t >> 1) * 64] = (uint16_t)bits;
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 q = wq[t & 1][g];
@@ -284,7 +299,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
     if (valid && h == 0) {
       const float pre = s + a.w.p[B_SIGMA][0];
       a.sigma[m] = fabsf(pre);
-      if (SAVE) a.spre[a.row0 + m] = pre;
+      if (SAVE || GSAVE) a.spre[a.row0 + m] = pre;
     }
   }
   RSTAMP(5);  // sigma head
@@ -304,7 +319,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
         A[f][4 * g + 3] = q.w;
       }
   }
-  reg_layer<32, 4, 32, 4, false, true, SAVE>(seg_off4(SEG_FOLD), -1, lane, B, A, st0, nullptr, sv_relu(7), rb);
+  reg_layer<32, 4, 32, 4, false, true, SAVE>(seg_off4(SEG_FOLD), -1, lane, B, A, st0, nullptr, GSAVE ? SaveIn{nullptr, nullptr} : sv_relu(7), rb);
   RSTAMP(6);  // point_info + dir_info folded (512 MFMAs)
   // ---- colour head (VALU): rgb = sigmoid(W_c relu(.) + b)  (nerf.py:99, 119)
   {
@@ -320,6 +335,7 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
         const float c0 = relu1(A[t][4 * g + 0]), c1 = relu1(A[t][4 * g + 1]);
         const float c2 = relu1(A[t][4 * g + 2]), c3 = relu1(A[t][4 * g + 3]);
         if (SAVE) store_row4(srow + S_C * MS + 32 * t + 8 * g, make_float4(c0, c1, c2, c3));
+        if (GSAVE) store_row4(crow + 32 * t + 8 * g, make_float4(c0, c1, c2, c3));
         z0 = __builtin_fmaf(c3, q0.w, __builtin_fmaf(c2, q0.z, __builtin_fmaf(c1, q0.y, __builtin_fmaf(c0, q0.x, z0))));
         z1 = __builtin_fmaf(c3, q1.w, __builtin_fmaf(c2, q1.z, __builtin_fmaf(c1, q1.y, __builtin_fmaf(c0, q1.x, z1))));
         z2 = __builtin_fmaf(c3, q2.w, __builtin_fmaf(c2, q2.z, __builtin_fmaf(c1, q2.y, __builtin_fmaf(c0, q2.x, z2))));
@@ -351,6 +367,16 @@ hipError_t launch_field_fwd_reg(const FieldArgs& a, bool save, hipStream_t st) {
     hipLaunchKernelGGL((k_field_fwd_reg<false, true>), dim3(tiles), dim3(64), 0, st, a, QuerySrc{});
   else
     hipLaunchKernelGGL((k_field_fwd_reg<false, false>), dim3(tiles), dim3(64), 0, st, a, QuerySrc{});
+  return hipGetLastError();
+}
+
+hipError_t launch_query_grad_fwd(const FieldArgs& a, const QuerySrc& q, bool rgb, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  const unsigned tiles = (unsigned)(((long long)a.M + RM - 1) / RM);
+  if (rgb)
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, true, true>), dim3(tiles), dim3(64), 0, st, a, q);
+  else
+    hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, false, true>), dim3(tiles), dim3(64), 0, st, a, q);
   return hipGetLastError();
 }
 

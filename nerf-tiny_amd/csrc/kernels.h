@@ -65,6 +65,14 @@ struct QuerySrc {
 // Colour queries run in chunks of this many points: the dvec rows of one chunk live in the workspace (independent of M), and a chunk is
 // 8 waves for every SIMD of the chip (256 CUs x 4 SIMDs x 32 points x 8) at the kernel's one wave per SIMD.
 constexpr int QUERY_CHUNK = 256 * 4 * 32 * 8;
+// Gradient queries (nerf_hip_query_grad): the compact save-carrying forward (k_field_fwd_reg<..., SRC_POINTS, RGB, GSAVE = true>) and the
+// query form of the dX chain (k_field_bwd_reg<true, true, RGB>) run chunk by chunk, 4 rounds of one wave per SIMD (256 CUs x 4 SIMDs x
+// 32 points x 4).  The FieldArgs / FieldBwdArgs of such a launch use, besides the query fields: save = [MSrows][QGRAD_GP] gamma_p rows,
+// then (RGB) [MSrows][QGRAD_C] c rows; masks = [8][tiles_tot][4][256] ReLU masks of h0..h7 (the training layout); spre [MSrows];
+// row0 = tile0 = 0, Mtot = the chunk's points, MSrows = QGRAD_CHUNK + DUMP_ROWS.  The chain's upstream is dsig ([M], null = ones) and,
+// RGB, drgb [M][3] with the forward's rgb; its output dt is dpoints [M][3] (stored, not added).  G is null: no G / dz / dspre row is written.
+constexpr int QGRAD_CHUNK = 256 * 4 * 32 * 4;
+constexpr int QGRAD_GP = 64, QGRAD_C = 128;  // floats per saved gamma_p row (60 used) / c row
 
 // saved by the forward: h0..h7, c, gamma_p (feat = point_info's output is not saved: with point_info folded into dir_info no weight
 // gradient needs it, see common.h SEG_FOLD)
@@ -139,6 +147,7 @@ hipError_t launch_fold_weights(const Weights24& w, float* fold, hipStream_t st);
 hipError_t launch_field_fwd(const FieldArgs& a, bool save, hipStream_t st);
 hipError_t launch_field_fwd_reg(const FieldArgs& a, bool save, hipStream_t st);
 hipError_t launch_query_reg(const FieldArgs& a, const QuerySrc& q, bool rgb, hipStream_t st);  // rgb: colour and sigma (q.points, a.dvec set), else sigma
+hipError_t launch_query_grad_fwd(const FieldArgs& a, const QuerySrc& q, bool rgb, hipStream_t st);  // launch_query_reg + the compact save (QGRAD_*)
 // dir_info start vectors of n points from their directions: dvec[i][128] as k_rays forms them from a ray's world direction (ray_ops.hip)
 hipError_t launch_dirs_dvec(const float* dirs, int n, const float* w_dir, const float* b_dir, const float* b_fold, float* dvec, hipStream_t st);
 hipError_t launch_field_fwd_bf16(const FieldArgs& a, bool save, hipStream_t st, const FwdFuse* fuse = nullptr);
@@ -311,6 +320,7 @@ struct SmallGradArgs {
 hipError_t launch_field_bwd(const FieldBwdArgs& a, bool fine, hipStream_t st);
 hipError_t launch_field_bwd_split(const FieldBwdArgs& a, bool fine, hipStream_t st);  // split-fp32 training chain (field_bwd_split.hip)
 hipError_t launch_field_bwd_reg(const FieldBwdArgs& a, bool fine, hipStream_t st);
+hipError_t launch_query_grad_bwd(const FieldBwdArgs& a, bool rgb, hipStream_t st);  // the query form of the chain: a.dt = dpoints [M][3] (QGRAD_*)
 hipError_t launch_field_bwd_bf16(const FieldBwdArgs& a, bool fine, hipStream_t st, const BwdFuse* fuse = nullptr);
 hipError_t launch_pack_weights_bf16_bwd(const Weights24& w, const float* fold, unsigned char* img, hipStream_t st);
 size_t dw_bf16_slab_floats();

@@ -45,6 +45,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after display(): extract the isosurface sigma == --mesh-level on a RES^3 lattice over --grid-bbox (marching cubes on "
                          "the device, vertex colours) to <RESULTS_PATH><time>_<iter>_mesh<RES>.ply (rank 0 only)")
     ap.add_argument("--mesh-level", type=float, default=50.0, metavar="SIGMA", help="density threshold of --mesh (default 50.0)")
+    ap.add_argument("--mesh-normals", choices=["grid", "field"], default="grid",
+                    help="vertex normals of --mesh: grid = central differences of the lattice (default), field = the field's analytic "
+                         "gradient at each vertex (not limited by the grid spacing)")
     ap.add_argument("--maps", action="store_true",
                     help="display() also renders every frame's expected depth and opacity: <RESULTS_PATH><time>_<iter>_maps.npz (depth, acc, "
                          "near, far) and <i>_depth.png / <i>_acc.png previews beside the frames (rank 0 writes)")
@@ -79,4 +82,4 @@ if __name__ == "__main__":
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:
-        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
+        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals)

@@ -165,6 +165,39 @@ class _RenderFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, *grads)
 
 
+def field_normals(g):
+    """Outward unit normals -g / |g| of sigma gradients g [V, 3] (fp32, |g| = sqrt(g0^2 + g1^2 + g2^2) rounded per operation), (0, 0, 0)
+    where |g| is 0 or not finite: the marching-cubes kernel's rule (include/nerf_hip.h)."""
+    length = torch.sqrt(g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1] + g[:, 2] * g[:, 2])[:, None]
+    ok = torch.isfinite(length) & (length > 0)
+    return torch.where(ok, -g / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(g))
+
+
+class _FieldQuery(torch.autograd.Function):
+    """NeRFModel.field: forward = nerf_hip_query, backward = nerf_hip_query_grad with the upstream gradients (a recompute; the weights
+    are constants).  Outputs (rgb, sigma) with dirs, sigma alone without."""
+
+    @staticmethod
+    def forward(ctx, points, model, dirs):
+        ctx.model = model
+        ctx.save_for_backward(*(t for t in (points, dirs) if t is not None))
+        rgb, sigma = model.query(points, dirs)
+        return sigma if dirs is None else (rgb, sigma)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        points, dirs = saved[0], (saved[1] if len(saved) > 1 else None)
+        if dirs is None:
+            g_rgb, g_sigma = None, grads[0]
+        else:
+            g_rgb, g_sigma = grads
+        if g_sigma is None:
+            g_sigma = torch.zeros(points.shape[0], dtype=torch.float32, device=points.device)
+        dp = ctx.model.query_grad(points, dirs, dsigma=g_sigma, drgb=g_rgb)[2]
+        return dp, None, None
+
+
 class NeRFModel(nn.Module):
     """Drop-in for the reference's ``NeRFModel`` (nerf.py:169-348)."""
 
@@ -430,6 +463,55 @@ class NeRFModel(nn.Module):
         d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3) if dirs is not None else None
         return ops.query(ps, pts, d, ws=self._query_workspace(d is not None, dev))
 
+    def _query_grad_workspace(self, with_rgb: bool, dev):
+        key = ("grad", with_rgb)
+        ws = self._qws.get(key)
+        if ws is None or ws.device != dev:
+            ws = torch.empty(_abi.query_grad_ws_bytes(with_rgb), dtype=torch.uint8, device=dev)
+            self._qws[key] = ws
+        return ws
+
+    def _device_params(self):
+        ps = self._params()
+        if ps[0].device.type != "cuda":
+            raise RuntimeError("NeRFModel runs only on a ROCm device (MI355X): model.to('cuda'); there is no CPU path")
+        return ps
+
+    @torch.no_grad()
+    def query_grad(self, points, dirs=None, dsigma=None, drgb=None):
+        """query() and the vector-Jacobian product of the field with respect to the points: points [M, 3], dirs [M, 3] or None as in
+        query(); upstream dsigma [M] (None = ones, which gives the gradient of sigma) and, only with dirs, drgb [M, 3] (None = no colour
+        term).  Returns (rgb [M, 3] or None, sigma [M], dpoints [M, 3]) with dpoints[m] = dsigma[m] d sigma_m / d p_m + drgb[m] . d rgb_m
+        / d p_m.  rgb and sigma are query()'s bits.  Exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say; gradients with respect to
+        points only (not dirs, not the weights).  The gradient convention is the train step's (include/nerf_hip.h): the encoding's
+        phase fp32(x * f) is differentiated as if it were exact, and d|s|/ds = sign(s) with sign(0) = 0."""
+        from . import ops
+
+        ps = self._device_params()
+        dev = ps[0].device
+        pts = torch.as_tensor(points).to(dev, torch.float32).reshape(-1, 3)
+        d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3) if dirs is not None else None
+        ds = torch.as_tensor(dsigma).to(dev, torch.float32).reshape(-1) if dsigma is not None else None
+        dc = torch.as_tensor(drgb).to(dev, torch.float32).reshape(-1, 3) if drgb is not None else None
+        return ops.query_grad(ps, pts, d, ds, dc, ws=self._query_grad_workspace(d is not None, dev))
+
+    def field(self, points, dirs=None):
+        """query() as a differentiable function of the points: returns (rgb [M, 3] or None, sigma [M]) with query()'s values, and a
+        backward that runs nerf_hip_query_grad with the upstream gradients (recomputing the forward: nothing per point is kept between
+        the two).  The gradient flows to ``points`` only: the weights are constants of this function (they get no .grad from it, and
+        must not change between forward and backward), and ``dirs`` must not require grad -- no gradient with respect to directions is
+        computed, so that raises instead of silently giving none.  For surface normals, eikonal or surface-projection losses and probes."""
+        if dirs is not None and torch.is_tensor(dirs) and dirs.requires_grad:
+            raise ValueError("model.field gives gradients with respect to points only: dirs must not require grad (detach them)")
+        ps = self._device_params()
+        dev = ps[0].device
+        pts = torch.as_tensor(points).to(dev, torch.float32).reshape(-1, 3)
+        d = torch.as_tensor(dirs).to(dev, torch.float32).reshape(-1, 3).detach() if dirs is not None else None
+        if d is None:
+            return None, _FieldQuery.apply(pts, self, None)
+        rgb, sigma = _FieldQuery.apply(pts, self, d)
+        return rgb, sigma
+
     @torch.no_grad()
     def density_grid(self, lo, hi, res):
         """sigma on a regular lattice spanning the box [lo, hi] (three floats each): res = n or (nx, ny, nz), every n >= 1 and
@@ -452,24 +534,31 @@ class NeRFModel(nn.Module):
         return ops.density_grid(ps, lo32.tolist(), step.tolist(), shape, ws=self._query_workspace(False, dev))
 
     @torch.no_grad()
-    def extract_mesh(self, lo, hi, res, level, color=True):
+    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid"):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
         device, exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say.  The grid's 4 bytes per point are held only during the call, with
-        a mesh workspace of 4 bytes per point more."""
+        a mesh workspace of 4 bytes per point more.
+        normals="grid": the marching-cubes normals (central differences of the grid, interpolated to the vertex).  normals="field": -g / |g|
+        of the field's analytic gradient g at each vertex (query_grad; (0, 0, 0) where |g| is 0 or not finite) -- not limited by the grid
+        spacing; the colours are then seen along these normals."""
         import numpy as np
 
         from . import mesh
 
+        if normals not in ("grid", "field"):
+            raise ValueError(f"normals={normals!r}: 'grid' or 'field'")
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
         sigma = self.density_grid(lo32, hi32, shape)
-        verts, faces, normals = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
+        verts, faces, nrm = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
         del sigma
-        rgb = self.query(verts, -normals)[0] if color else None
-        return mesh.Mesh(verts, faces, normals, rgb)
+        if normals == "field":
+            nrm = field_normals(self.query_grad(verts)[2])
+        rgb = self.query(verts, -nrm)[0] if color else None
+        return mesh.Mesh(verts, faces, nrm, rgb)
 
     @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False):

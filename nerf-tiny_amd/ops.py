@@ -76,6 +76,38 @@ def query(params, points, dirs=None, ws=None):
     return rgb, sigma
 
 
+def query_grad(params, points, dirs=None, dsigma=None, drgb=None, ws=None):
+    """The field and its vector-Jacobian product with respect to the points (nerf_hip_query_grad, exact fp32): points[M,3] (and unit
+    world dirs[M,3]) on the device; upstream dsigma[M] (None = ones: the gradient of sigma) and, only with dirs, drgb[M,3] (None = no
+    colour term) -> (rgb[M,3] or None, sigma[M], dpoints[M,3]).  rgb and sigma are query()'s bits.  ws: a uint8 device buffer of
+    >= _abi.query_grad_ws_bytes(dirs is not None) bytes (allocated here if None)."""
+    M, dev = points.shape[0], points.device
+    with_rgb = dirs is not None
+    if drgb is not None and not with_rgb:
+        raise ValueError("drgb needs dirs: without them no colour is computed")
+    points = points.to(torch.float32).contiguous()
+    dirs = dirs.to(dev, torch.float32).contiguous() if with_rgb else None
+    if with_rgb and dirs.shape != points.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and points {tuple(points.shape)} differ")
+    if dsigma is not None:
+        dsigma = dsigma.to(dev, torch.float32).reshape(-1).contiguous()
+        if dsigma.shape[0] != M:
+            raise ValueError(f"dsigma has {dsigma.shape[0]} entries for {M} points")
+    if drgb is not None:
+        drgb = drgb.to(dev, torch.float32).contiguous()
+        if drgb.shape != points.shape:
+            raise ValueError(f"drgb {tuple(drgb.shape)} and points {tuple(points.shape)} differ")
+    sigma = torch.empty(M, device=dev)
+    rgb = torch.empty(M, 3, device=dev) if with_rgb else None
+    dpoints = torch.empty(M, 3, device=dev)
+    if ws is None:
+        ws = torch.empty(_abi.query_grad_ws_bytes(with_rgb), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _abi.check(_abi.lib().nerf_hip_query_grad(_abi.ptr_array(params), points.data_ptr(), ptr(dirs), M, ptr(dsigma), ptr(drgb), ptr(rgb),
+                                              sigma.data_ptr(), dpoints.data_ptr(), ws.data_ptr(), ws.numel(), _stream(points)))
+    return rgb, sigma, dpoints
+
+
 def density_grid(params, lo, step, shape, ws=None):
     """sigma at lo + (i, j, k) * step (nerf_hip_density_grid, exact fp32): lo / step three host floats, shape (nx, ny, nz) ->
     sigma[nx, ny, nz] on the parameters' device.  ws as in query() (sigma only)."""
