@@ -46,7 +46,8 @@ extern "C" {
                                   4: nerf_hip_read_status_sticky; 5: nerf_hip_train_step; 6: NERF_HIP_CORRECTED;
                                   7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
                                      nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps;
-                                     nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad */
+                                     nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad; nerf_hip_metrics_ws_bytes,
+                                     nerf_hip_image_metrics */
 
 enum {
   NERF_HIP_OK = 0,
@@ -293,6 +294,32 @@ int nerf_hip_query_grad_ws_bytes(int with_rgb, size_t* bytes);
 int nerf_hip_query_grad(const float* const* weights24, const float* points, const float* dirs, int M,
                         const float* dsigma, const float* drgb, float* rgb, float* sigma, float* dpoints,
                         void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Image metrics of rendered frames: per view the MSE and the SSIM of pred against gt, both
+ * [n][H][W][3] fp32, row-major (the layout of NeRFRunner.display()), device-resident.  Data range 1, no clipping.
+ *   MSE_v  = sum over the H * W * 3 values of (pred - gt)^2 / (H * W * 3);  PSNR = -10 log10(MSE) is the caller's (+inf at 0).
+ *   SSIM_v (Wang et al. 2004 as mip-NeRF's compute_ssim reports it), per channel c of x = pred, y = gt:
+ *     g[k] = exp(-((k - 5) / 1.5)^2 / 2) / sum_j exp(-((j - 5) / 1.5)^2 / 2),  k = 0..10  (sigma 1.5, sum 1)
+ *     f(z)[i][j] = sum_a g[a] sum_b g[b] z[i + a][j + b]  (horizontal pass first, then vertical; VALID: 0 <= i < H - 10,
+ *                  0 <= j < W - 10, no padding)
+ *     mu_x = f(x), mu_y = f(y), s_xx = max(f(x^2) - mu_x^2, 0), s_yy = max(f(y^2) - mu_y^2, 0),
+ *     s_xy = sign(t) min(sqrt(s_xx s_yy), |t|) with t = f(xy) - mu_x mu_y,   C1 = 0.01^2, C2 = 0.03^2
+ *     map = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2))
+ *   SSIM_v = the mean of map over the 3 channels and the (H - 10) x (W - 10) valid pixels.
+ * Every product, filter tap and sum runs in fp64.  No atomics: the per-tile partial sums go to `ws` and a fixed-order pass reduces
+ * them, so repeated calls are bit-identical whatever `ws` held.  NaN / inf in a view's inputs reaches that view's results (the clamps
+ * let NaN through).  One workgroup per (view, tile of 16 x 32 outputs) and one per view.  Enqueue-only.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of nerf_hip_image_metrics for n views of H x W: 16 bytes per (view, tile). */
+int nerf_hip_metrics_ws_bytes(int n, int H, int W, size_t* bytes);
+
+/* mse[n], ssim[n] (fp64, device) as defined above.  Refused before any device work: n < 0, H < 11 or W < 11 (the window),
+ * H * W * 3 >= 2^31, and with n > 0 a NULL pred / gt / mse / ssim, or a workspace that is NULL, not 256-byte aligned or smaller
+ * than nerf_hip_metrics_ws_bytes(n, H, W).  n == 0 succeeds and launches nothing. */
+int nerf_hip_image_metrics(const float* pred, const float* gt, int n, int H, int W, double* mse, double* ssim,
+                           void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Marching cubes over a density grid: an indexed triangle mesh of the isosurface sigma == level.

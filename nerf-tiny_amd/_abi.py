@@ -51,6 +51,8 @@ _PROTOS = {
     "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
     "nerf_hip_query_grad_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query_grad": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p, C.c_size_t, _p]),
+    "nerf_hip_metrics_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "nerf_hip_image_metrics": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_mesh_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_mesh_count": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_float, _p, C.c_size_t, _p, _p]),
     "nerf_hip_mesh_emit": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_float, _p, C.c_size_t, _p, _p, _p, C.c_int64,
@@ -113,6 +115,13 @@ def mesh_ws_bytes(nx: int, ny: int, nz: int) -> int:
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_ws_bytes(int(nx), int(ny), int(nz), C.byref(n)))
     return int(n.value)
+
+
+def metrics_ws_bytes(n: int, H: int, W: int) -> int:
+    """Workspace bytes of nerf_hip_image_metrics for n views of H x W."""
+    k = C.c_size_t(0)
+    check(lib().nerf_hip_metrics_ws_bytes(int(n), int(H), int(W), C.byref(k)))
+    return int(k.value)
 
 
 KERNEL_NAMES = ("pack_weights", "rays", "field_fwd_coarse", "coarse_composite", "field_fwd_fine", "merge_composite",

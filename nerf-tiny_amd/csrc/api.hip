@@ -1425,3 +1425,69 @@ int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* 
 }
 
 }  // extern "C"
+
+namespace {
+
+// Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
+int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
+  if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);
+  if (H < MT_WIN || W < MT_WIN) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: SSIM's %d x %d window needs H, W >= %d", H, W, MT_WIN, MT_WIN, MT_WIN);
+  const long long per_view = (long long)H * W * 3;
+  // (with n < 2^31 the whole input then stays below 2^62 values)
+  if (per_view >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: the element count H * W * 3 of a view must stay below 2^31", H, W);
+  *tiles_x = metrics_tiles_x(W);
+  *tiles = *tiles_x * metrics_tiles_y(H);
+  return NERF_HIP_OK;
+}
+
+void metrics_window(double g[MT_WIN]) {  // exp(-((k - 5) / 1.5)^2 / 2), normalised to sum 1 (summed in k order)
+  double s = 0.0;
+  for (int k = 0; k < MT_WIN; ++k) {
+    const double u = (k - MT_WIN / 2) / 1.5;
+    g[k] = exp(-0.5 * (u * u));
+    s += g[k];
+  }
+  for (int k = 0; k < MT_WIN; ++k) g[k] /= s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_metrics_ws_bytes(int n, int H, int W, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  int tiles_x = 0, tiles = 0;
+  if (int rc = check_metrics_shape(n, H, W, &tiles_x, &tiles)) return rc;
+  *bytes = al((size_t)n * tiles * 2 * sizeof(double));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_image_metrics(const float* pred, const float* gt, int n, int H, int W, double* mse, double* ssim, void* ws, size_t ws_bytes,
+                           void* stream) {
+  int tiles_x = 0, tiles = 0;
+  if (int rc = check_metrics_shape(n, H, W, &tiles_x, &tiles)) return rc;
+  if (n == 0) return NERF_HIP_OK;  // (empty buffers may have null pointers)
+  if (!pred || !gt || !mse || !ssim) return fail(NERF_HIP_ERR_ARG, "null argument (pred, gt, mse and ssim are required)");
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  const size_t need = al((size_t)n * tiles * 2 * sizeof(double));
+  if (ws_bytes < need) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
+  if (int rc = check_device()) return rc;
+  MetricsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.gt = gt;
+  a.n = n;
+  a.H = H;
+  a.W = W;
+  a.tiles_x = tiles_x;
+  a.tiles = tiles;
+  a.part = static_cast<double*>(ws);
+  a.mse = mse;
+  a.ssim = ssim;
+  metrics_window(a.g);
+  HIP_TRY(launch_image_metrics(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"

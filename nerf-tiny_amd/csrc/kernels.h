@@ -411,4 +411,23 @@ inline int mesh_blocks(long long n_points) { return (int)((n_points + MESH_PTS -
 hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st);  // count + in-block vertex scan, then the scan of the block totals
 hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st);
 
+// ---- image metrics (metrics.hip): per-view MSE and SSIM of pred vs gt [n][H][W][3] fp32, fp64 arithmetic
+constexpr int MT_WIN = 11;                   // SSIM's Gaussian window (taps); valid filtering drops MT_WIN - 1 rows / columns
+constexpr int MT_X = 32, MT_Y = 16;          // valid SSIM outputs per workgroup (columns x rows)
+constexpr int MT_WG = 256;
+
+inline int metrics_tiles_x(int W) { return (W - MT_WIN + MT_X) / MT_X; }  // ceil((W - 10) / MT_X)
+inline int metrics_tiles_y(int H) { return (H - MT_WIN + MT_Y) / MT_Y; }
+
+struct MetricsArgs {
+  const float *pred, *gt;  // [n][H][W][3]
+  int n, H, W;             // H, W >= MT_WIN, H * W * 3 < 2^31
+  int tiles_x, tiles;      // workgroups per view: tiles_x * tiles_y
+  double* part;            // [n * tiles][2]: (sum of squared errors over the tile's own pixels, sum of the tile's SSIM map)
+  double *mse, *ssim;      // [n]
+  double g[MT_WIN];        // the normalised window
+};
+
+hipError_t launch_image_metrics(const MetricsArgs& a, hipStream_t st);  // per-tile partial sums, then a fixed-order pass per view
+
 }  // namespace nerf

@@ -51,6 +51,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--maps", action="store_true",
                     help="display() also renders every frame's expected depth and opacity: <RESULTS_PATH><time>_<iter>_maps.npz (depth, acc, "
                          "near, far) and <i>_depth.png / <i>_acc.png previews beside the frames (rank 0 writes)")
+    ap.add_argument("--eval", action="store_true",
+                    help="after display(): PSNR / SSIM / MSE of the display split (the \"test\" dataset) against its ground truth, printed and "
+                         "written to <RESULTS_PATH><time>_<iter>_eval.json (rank 0)")
+    ap.add_argument("--eval-every", type=int, default=None, metavar="N",
+                    help="during training, every N iterations: PSNR / SSIM of the val split, logged and printed (training is unchanged)")
+    ap.add_argument("--eval-views", type=int, nargs="+", default=None, metavar="I",
+                    help="view indices of --eval and --eval-every (default: every view)")
     return ap
 
 
@@ -74,11 +81,18 @@ if __name__ == "__main__":
     kw["split_train"] = args.split_train or ast.literal_eval(c("SPLIT_TRAIN", "False"))
     if args.on_resample_fault or c("ON_RESAMPLE_FAULT"):
         kw["on_resample_fault"] = args.on_resample_fault or c("ON_RESAMPLE_FAULT")
+    if args.eval_every is not None:
+        kw["eval_every"], kw["eval_views"] = args.eval_every, args.eval_views
     # data-parallel: started as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 .../main.py ...`
     # every rank runs this file; NeRFRunner reads RANK / WORLD_SIZE / LOCAL_RANK from the environment before its first GPU call
     run = P.NeRFRunner(**kw)
     run.trainer("train")
     run.display(maps=args.maps)
+    if args.eval:
+        r = run.evaluate("disp", views=args.eval_views, save=True)
+        if r is not None:
+            print(f"[EVAL] {r['iter']} disp [PSNR] {r['psnr']:.3f} dB [SSIM] {r['ssim']:.4f} [MSE] {r['mse']:.3e} [{len(r['views'])} views, "
+                  f"{r['seconds']:.2f} s]")
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:

@@ -150,6 +150,27 @@ def marching_cubes(sigma, lo, step, level, ws=None):
     return verts, faces, normals
 
 
+def image_metrics(pred, gt, ws=None):
+    """Per-view MSE and SSIM (nerf_hip_image_metrics, fp64 arithmetic; definition in include/nerf_hip.h): pred, gt [n, H, W, 3] device
+    tensors of the same shape and device (cast to contiguous fp32 here) -> (mse[n], ssim[n]) fp64 on that device.  ws: a uint8 device
+    buffer of >= _abi.metrics_ws_bytes(n, H, W) bytes (allocated here if None)."""
+    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)}: two [n, H, W, 3] tensors of the same shape")
+    if pred.device != gt.device or pred.device.type != "cuda":
+        raise ValueError(f"pred on {pred.device}, gt on {gt.device}: both on one ROCm device (there is no CPU path)")
+    n, H, W, _ = (int(d) for d in pred.shape)
+    dev = pred.device
+    pred = pred.to(torch.float32).contiguous()
+    gt = gt.to(torch.float32).contiguous()
+    mse = torch.empty(n, dtype=torch.float64, device=dev)
+    ssim = torch.empty(n, dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = torch.empty(max(_abi.metrics_ws_bytes(n, H, W), 1), dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_image_metrics(pred.data_ptr(), gt.data_ptr(), n, H, W, mse.data_ptr(), ssim.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), _stream(pred)))
+    return mse, ssim
+
+
 def coarse_composite(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
     """-> w_c[B,Nc], C_coarse[B,3], t_f[B,Nf], status(int)"""
     B, Nc = t_c.shape

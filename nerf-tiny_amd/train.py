@@ -5,7 +5,9 @@ and updates a preview image every iteration, nerf.py:478-483).
 """
 from __future__ import annotations
 
+import contextlib
 import glob
+import numbers
 import os
 import time
 
@@ -111,6 +113,25 @@ def _writer():
         return _NullWriter()
 
 
+def _view_list(views) -> list:
+    """views: an index or an iterable of indices -> a non-empty list of ints."""
+    if isinstance(views, numbers.Integral):
+        views = [views]
+    try:
+        views = list(views)
+    except TypeError:
+        raise ValueError(f"views={views!r}: an index or a list of indices") from None
+    if not views or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in views):
+        raise ValueError(f"views={views!r}: a non-empty list of integer indices (None selects every view)")
+    return [int(v) for v in views]
+
+
+def _check_views(views, pic_num: int, mode: str) -> None:
+    bad = [v for v in views if not 0 <= v < pic_num]
+    if bad:
+        raise ValueError(f"views {bad}: the {mode!r} split has views 0 .. {pic_num - 1}")
+
+
 class NeRFRunner:
     """The reference's runner surface: same 17 constructor arguments (nerf.py:354-372), ``trainer(mode)`` (nerf.py:445)
     and ``display()`` (nerf.py:503).  ``mode`` defaults to "train" so the reference's ``main.py:55`` call works.
@@ -124,7 +145,9 @@ class NeRFRunner:
     itself clamps the index and goes on.  Default "raise": the reference stops there too), ``distributed`` (None: data-parallel iff a
     launcher started more than one rank; True: also with one rank -- rehearsals; False: never), ``overlap_allreduce`` (None: the
     NERF_DP_OVERLAP environment variable, default off; True: reduce the early 83 % of the gradient bucket on a side stream beside the last
-    weight-gradient products).
+    weight-gradient products), ``eval_every`` (None: off; N: every N iterations the held-out ``val`` split is evaluated -- ``evaluate("val",
+    eval_views, save=False)``, every rank taking part -- its PSNR / SSIM logged as ``psnr/val`` / ``ssim/val`` and printed by rank 0; training
+    is bit-identical to a run without it), ``eval_views`` (the view indices of those evaluations; None: all).
 
     **Data-parallel training (BASELINE.json cfg3) and tile-sharded rendering (cfg5)**: under ``python -m torch.distributed.run
     --nproc-per-node N .../main.py`` every rank builds this runner on ``cuda:LOCAL_RANK`` (RANK / WORLD_SIZE / LOCAL_RANK are read from
@@ -139,9 +162,15 @@ class NeRFRunner:
     def __init__(self, gpu=0, img_dir="../nerf_synthetic/lego/", results_path="./results/", ckpt_path="./checkpoint/", low_res=1,
                  total_iter=100000, batch_ray=400, learning=1e-3, lr_gamma=0.1, lr_milestone=(10, 200), n_coarse=64, n_fine=128,
                  data_type="sync", step=100, decay_end=200000, sched="EXP", continue_=False, *, datasets=None, log_every=None,
-                 seed=624, bf16_mlp=False, split_mlp=False, split_train=False, on_resample_fault="raise", distributed=None, overlap_allreduce=None):
+                 seed=624, bf16_mlp=False, split_mlp=False, split_train=False, on_resample_fault="raise", distributed=None, overlap_allreduce=None,
+                 eval_every=None, eval_views=None):
         from . import nerf as _nerf
         from . import parallel as par
+
+        if eval_every is not None and (isinstance(eval_every, bool) or not isinstance(eval_every, int) or eval_every < 1):
+            raise ValueError(f"eval_every={eval_every!r}: None or a positive number of iterations")
+        self.eval_every = eval_every
+        self.eval_views = _view_list(eval_views) if eval_views is not None else None
 
         # ---- the launcher's environment first: nothing above this line has touched the GPU
         self.env = par.DistEnv.from_env()
@@ -227,6 +256,9 @@ class NeRFRunner:
         self.disp_rays = DeviceRays(self.disp_dataset, self.device, seed + 2)
         self.height, self.width, self.focal = self.train_dataset.height, self.train_dataset.width, self.train_dataset.focal
         self.num_pic = self.train_dataset.pic_num
+        if self.eval_views is not None and self.eval_every is not None:
+            _check_views(self.eval_views, self.val_rays.pic_num, "val")
+        self._eval_ws = {}  # the model's inference workspaces while it is evaluated (_evaluation)
         # inverse intrinsics, transposed (nerf.py:433)
         self.K_inv = torch.tensor([[1.0, 0.0, -0.5 * self.width], [0.0, -1.0, 0.5 * self.height], [0.0, 0.0, -self.focal]]).to(torch.float).transpose(0, 1)
 
@@ -294,6 +326,7 @@ class NeRFRunner:
         rays = {"train": self.train_rays, "val": self.val_rays, "disp": self.disp_rays}[mode]
         it = self.last_iter + 1
         t0, n0 = time.perf_counter(), it
+        t_eval = 0.0  # seconds spent in evaluations (eval_every), left out of the printed rate
         self.model.train()
         skip = 0
         if self._resume_sampler is not None and self._resume_sampler[0] == mode:
@@ -336,7 +369,7 @@ class NeRFRunner:
                     lv, fault, any_err = self._global_loss_and_fault(loss, fault, err is not None)
                     if any_err:
                         raise err if err is not None else _abi.NerfHipError(f"iteration <= {it}: another rank reported a library error at this logging point")
-                    dt = time.perf_counter() - t0
+                    dt = time.perf_counter() - t0 - t_eval
                     self.writer.add_scalar("loss/" + mode, lv, it)
                     self.writer.add_scalar("lr/" + mode, self.optimizer.param_groups[0]["lr"], it)
                     self.writer.flush()
@@ -357,6 +390,15 @@ class NeRFRunner:
                                                      "NeRFRunner(on_resample_fault='warn') trains on")
                 if (it + 1) % self.step == 0 and self.rank == 0:
                     self._save_checkpoint(it, rays, mode, epoch_gen_state, bi + 1)
+                if self.eval_every is not None and (it + 1) % self.eval_every == 0:
+                    # every rank renders its share of the views; nothing the loop reads changes (_evaluation)
+                    r = self._evaluate("val", self.eval_views, False, it)
+                    if r is not None:
+                        t_eval += r["seconds"]
+                        self.writer.add_scalar("psnr/val", r["psnr"], it)
+                        self.writer.add_scalar("ssim/val", r["ssim"], it)
+                        self.writer.flush()
+                        print(f"[EVAL] {it} [PSNR] {r['psnr']:.3f} dB [SSIM] {r['ssim']:.4f} [{len(r['views'])} val views, {r['seconds']:.2f} s]")
                 it += 1
                 if it >= self.total_iter:
                     break
@@ -364,6 +406,96 @@ class NeRFRunner:
                 break
         self.last_iter = it - 1
         return self.last_iter
+
+    # ----- held-out evaluation (not in the reference, which only writes the frames: nerf.py:503-530) -----
+    def _split_rays(self, mode: str):
+        splits = {"train": self.train_rays, "val": self.val_rays, "disp": self.disp_rays}
+        if mode not in splits:
+            raise ValueError(f"mode={mode!r}: 'train', 'val' or 'disp'")
+        return splits[mode]
+
+    @contextlib.contextmanager
+    def _evaluation(self):
+        """Rendering for an evaluation without touching what the training loop reads: the model's inference calls run on workspaces of
+        their own (so a ray that meets the resample condition leaves no bit in the sticky status words ``resample_fault_since`` reads at
+        the logging points), on the reference's batch grid, and the model's train / eval mode comes back as it was (it is pickled into
+        the checkpoints)."""
+        m = self.model
+        saved = (m._ws, m._last_ws, m.batch_ray, m.training)
+        m._ws, m.batch_ray = self._eval_ws, self.batch_ray
+        m.eval()
+        try:
+            yield m
+        finally:
+            self._eval_ws = m._ws
+            m._ws, m._last_ws, m.batch_ray = saved[:3]
+            m.train(saved[3])
+
+    def render_view(self, i: int, mode: str = "disp"):
+        """View i of a split ("train", "val" or "disp") rendered as its own ray list: its pixels in row-major order through
+        NeRFModel.render on the ``batch_ray`` grid, every pixel including the tail batch, with the model's inference flags.  Where the
+        split's views share near / far these are display()'s bits wherever display() renders the pixel.  Under a launcher every rank
+        must call it: the view's reference batches are dealt out as in display() (render_rows_sharded + gather_rows) and every rank gets
+        the whole frame.  Returns (frame, gt), [H, W, 3] fp32 device tensors."""
+        from . import parallel as par
+
+        rays = self._split_rays(mode)
+        (i,) = _view_list(i)
+        _check_views([i], rays.pic_num, mode)
+        H, W = rays.height, rays.width
+        n = H * W
+        row, col, pix, poses_bound, _ = rays.gather(torch.arange(i * n, (i + 1) * n, device=self.device))
+        with torch.no_grad(), self._evaluation() as m:
+            if self.distributed:
+                r = par.render_rows_sharded(m, row, col, poses_bound, self.K_inv, self.rank, self.world)
+                C = par.gather_rows(r[2].to(self.device), n, self.rank, self.world, self.group, batch=self.batch_ray)
+            else:
+                C = m.render(row, col, poses_bound, self.K_inv)[1]
+        return C.reshape(H, W, 3), pix.reshape(H, W, 3)
+
+    def evaluate(self, mode="disp", views=None, save=True):
+        """Held-out metrics of the current model on a split ("disp": the "test" dataset display() renders, "val", "train"): every selected
+        view (``views``: indices, None = all) is rendered by render_view() and scored against its ground truth by ``nerf_hip_image_metrics``
+        (metrics.py: MSE, PSNR = -10 log10 MSE with data range 1, SSIM with an 11-tap Gaussian window, valid filtering).  Under a launcher
+        every rank must call it; the metrics are computed on rank 0 and the other ranks return None.  Returns {"iter", "mode", "views",
+        "psnr", "ssim", "mse", "per_view": [{"view", "psnr", "ssim", "mse"}], "seconds"}, the means over views (PSNR averaged per view, as
+        papers report it); with save, rank 0 writes it to ``<results_path><start_time>_<last_iter>_eval.json``."""
+        return self._evaluate(mode, views, save, self.last_iter)
+
+    def _evaluate(self, mode, views, save, it):
+        import json
+
+        import numpy as np
+
+        from . import ops
+        from .metrics import psnr_from_mse
+
+        rays = self._split_rays(mode)
+        views = list(range(rays.pic_num)) if views is None else _view_list(views)
+        _check_views(views, rays.pic_num, mode)
+        t0 = time.perf_counter()
+        mses, ssims = [], []
+        for i in views:
+            frame, gt = self.render_view(i, mode)
+            if self.rank == 0:
+                mse, ssim = ops.image_metrics(frame[None], gt[None])
+                mses.append(mse)
+                ssims.append(ssim)
+        if self.rank != 0:
+            return None
+        mse, ssim = torch.cat(mses).cpu().numpy(), torch.cat(ssims).cpu().numpy()  # (the one host sync)
+        psnr = psnr_from_mse(mse)
+        out = {"iter": int(it), "mode": mode, "views": views, "psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim)),
+               "mse": float(np.mean(mse)),
+               "per_view": [{"view": v, "psnr": float(p), "ssim": float(s), "mse": float(e)} for v, p, s, e in zip(views, psnr, ssim, mse)],
+               "seconds": time.perf_counter() - t0}
+        if save:
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_eval.json"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(out, f, indent=1)
+        return out
 
     def density_grid(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, save=True):
         """sigma of the current model on a res^3 (or res = (nx, ny, nz)) lattice spanning the box [lo, hi] (NeRFModel.density_grid: exact
