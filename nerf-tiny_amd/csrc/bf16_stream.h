@@ -43,12 +43,13 @@ __device__ __forceinline__ unsigned pack2_relu(float a, float b) {
   s = __builtin_elementwise_max(s, z);  // bf16 as int16: negative values (sign bit) -> 0, positive order preserved
   return __builtin_bit_cast(unsigned, s);
 }
-// bit (15 - r) = accumulator register r is >= +0 ("alive": its ReLU passes the gradient); one v_alignbit per register
+// bit (15 - r) = accumulator register r is > 0 ("alive": its ReLU passes the gradient, as torch's ReLU backward and the other paths
+// have it -- a pre-activation of exactly +0 is dead); per register a clamp of the bit pattern to {0, 1} (-0 and negatives: 0) and a shift-or
 __device__ __forceinline__ unsigned alive_bits(const f32x16& A) {
   unsigned bits = 0;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(A[r]), 31);
-  return ~bits & 0xffffu;
+  for (int r = 0; r < 16; ++r) bits = (bits << 1) | (unsigned)min(max(__float_as_int(A[r]), 0), 1);
+  return bits;
 }
 
 // The lane id, produced AT this program point: what the epilogues of the stream kernels form their addresses from.  The zero the count starts

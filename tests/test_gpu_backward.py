@@ -31,30 +31,14 @@ import pytest
 import torch
 
 from conftest import golden_inputs, l2_rel, load_golden
+import ws_operands
 
 pytestmark = pytest.mark.gpu
 GTOL = 1e-4          # well-conditioned gradients
 NOISE_BAND = 2e-2    # full gradient with the reference's discrete decisions replayed (reference fp32-vs-fp64: ~1e-2)
 
 
-def _relu_mask_image(hidden, tiles):
-    """ReLU masks in the field kernels' accumulator layout: [8][tiles][4][256] int16, bit r of entry
-    (f*2+st, tid = wv*64 + h*32 + j) <-> feature wv*64 + f*32 + 8(r>>2) + 4h + (r&3) of sample st*32 + j."""
-    f, st, wv, h, j, r = torch.meshgrid(torch.arange(2), torch.arange(2), torch.arange(4), torch.arange(2), torch.arange(32),
-                                        torch.arange(16), indexing="ij")
-    feat = wv * 64 + f * 32 + 8 * (r >> 2) + 4 * h + (r & 3)
-    samp = st * 32 + j
-    out = []
-    for H in hidden:  # [M, 256]
-        M = H.shape[0]
-        Hp = torch.zeros(tiles * 64, 256, dtype=torch.bool)
-        Hp[:M] = H > 0
-        Hp = Hp.view(tiles, 64, 256)
-        bits = Hp[:, samp, feat].to(torch.int32)  # [tiles, f, st, wv, h, j, r]
-        word = (bits << torch.arange(16, dtype=torch.int32)).sum(-1)
-        word = word - 65536 * (word >= 32768).to(torch.int32)
-        out.append(word.reshape(tiles, 4, 256).to(torch.int16))
-    return torch.stack(out)  # [8, tiles, 4, 256]
+_relu_mask_image = ws_operands.relu_mask_image  # (moved to tests/ws_operands.py; the old name stays importable here)
 
 
 def _views(pkg, m, B, Nc, Nf):

@@ -1,5 +1,6 @@
 """The operands of the weight-gradient products, read back from a train step's workspace, and a float64 reference of the 24
-gradients the kernels form from them (tests/test_gpu_weight_gradients.py).
+gradients the kernels form from them (tests/test_gpu_weight_gradients.py); the operands of every forward layer and every layer of
+the dX chain, and float64 references of each layer from its own saved operands (tests/test_gpu_layers.py).
 
 After a backward the workspace still holds exactly what the products read: ``save`` / ``G`` / ``dz`` (fp32 train step), the
 fragment-layout ``bsave`` / ``bG`` (bf16 MLP) and also their mid parts ``bsave2`` / ``bG2`` (split-fp32 train step).  Evaluating
@@ -100,11 +101,6 @@ def read_operands(ws, B, Nc, Nf, flags):
     return {k: (v,) for k, v in p.items()}
 
 
-def rows(ops, a, b):
-    """The operands of rows [a, b) only."""
-    return {k: tuple(t[a:b] for t in v) for k, v in ops.items()}
-
-
 def _prod(G, X):
     """(sum_s G[s]^T X[s], the same on absolute values) in float64.  Split operands: hi.hi + hi.mid + mid.hi -- the three products
     dw_bf16.hip forms (the mid.mid term is not part of the kernels' arithmetic); otherwise the one product."""
@@ -156,3 +152,242 @@ def dw_reference(ops, weights):
 def dw_statistic(got, ref, mag):
     """||got - ref|| / ||mag||: does not grow where the sum cancels (bias gradients, the scalar sigma bias)."""
     return float((got.double().reshape(ref.shape) - ref).norm() / mag.norm().clamp_min(1e-300))
+
+
+# ---- the forward and the dX chain: readers -------------------------------------------------------------------------------------
+TM = 64                  # csrc/common.h:16  samples per tile of the fp32 field kernels (the fp32 mask image)
+BM_LAYERS = 9            # csrc/bf16_common.h:68  bmask layers: h0..h7, c
+NOT_ROWS = {"fold", "b_fold"}  # per-call operands (no rows): rows() passes them through
+
+
+def relu_mask_image(hidden, tiles):
+    """ReLU masks in the fp32 field kernels' accumulator layout: [8][tiles][4][256] int16, bit r of entry
+    (f*2+st, tid = wv*64 + h*32 + j) <-> feature wv*64 + f*32 + 8(r>>2) + 4h + (r&3) of sample st*32 + j."""
+    f, st, wv, h, j, r = torch.meshgrid(torch.arange(2), torch.arange(2), torch.arange(4), torch.arange(2), torch.arange(32),
+                                        torch.arange(16), indexing="ij")
+    feat = wv * 64 + f * 32 + 8 * (r >> 2) + 4 * h + (r & 3)
+    samp = st * 32 + j
+    out = []
+    for H in hidden:  # [M, 256]
+        M = H.shape[0]
+        Hp = torch.zeros(tiles * 64, 256, dtype=torch.bool)
+        Hp[:M] = H > 0
+        Hp = Hp.view(tiles, 64, 256)
+        bits = Hp[:, samp, feat].to(torch.int32)  # [tiles, f, st, wv, h, j, r]
+        word = (bits << torch.arange(16, dtype=torch.int32)).sum(-1)
+        word = word - 65536 * (word >= 32768).to(torch.int32)
+        out.append(word.reshape(tiles, 4, 256).to(torch.int16))
+    return torch.stack(out)  # [8, tiles, 4, 256]
+
+
+def decode_relu_masks(img):
+    """The inverse of relu_mask_image: [L][tiles][4][256] int16 -> [L, tiles * 64 samples, 256 features] bool, on img's device."""
+    L, tiles = img.shape[:2]
+    r = torch.arange(16, device=img.device, dtype=torch.int32)
+    bits = (img.to(torch.int32).view(L, tiles, 2, 2, 4, 2, 32, 1) >> r) & 1  # L, tile, f, st, wv, h, j, r
+    bits = bits.view(L, tiles, 2, 2, 4, 2, 32, 4, 4)                          # r = 4 rq + rr
+    # sample st*32 + j, feature wv*64 + f*32 + 8 rq + 4h + rr
+    return bits.permute(0, 1, 3, 6, 4, 2, 7, 5, 8).reshape(L, tiles * 64, WIDTH).bool()
+
+
+def decode_bmask(words, wb_tot):
+    """bf16 / split `bmask`: u16 [9 layers: h0..h7, c][wb_tot][64 lanes][8 tiles], bit 15 - r = accumulator register r of tile f; lane
+    h * 32 + j holds sample wb * 32 + j, register r = feature 32 f + 8 (r >> 2) + 4 h + (r & 3) (csrc/bf16_common.h:67, the map of
+    decode).  -> [9, wb_tot * 32, 256] bool (the c layer's features 128..255 are the zero words of tiles 4..7)."""
+    r = torch.arange(16, device=words.device, dtype=torch.int32)
+    bits = (words.to(torch.int32).view(BM_LAYERS, wb_tot, 2, WAVE_ROWS, 8, 1) >> (15 - r)) & 1  # l, wb, h, j, f, r
+    bits = bits.view(BM_LAYERS, wb_tot, 2, WAVE_ROWS, 8, 4, 4)                                 # r = 4 rq + rr
+    return bits.permute(0, 1, 3, 4, 5, 2, 6).reshape(BM_LAYERS, wb_tot * WAVE_ROWS, WIDTH).bool()
+
+
+def read_layer_operands(ws, B, Nc, Nf, flags):
+    """read_operands plus what the forward and the chain read and write besides the products' operands:
+      m0..m7, mc  ReLU masks of h0..h7 and c (bool; fp32: c's mask is c > 0, as field_bwd_reg.hip forms it from the saved c)
+      spre  sigma pre-activation   sig, rgb  per-sample outputs   drgb, dsig  their upstream gradients
+      start  fp32: dir_info's per-ray start vector (dvec) of every row
+      fold, b_fold  bf16 / split: the fp32 W_fold [128][256] and b_fold [128] of the workspace (no rows)
+    Every per-row entry is a tuple of parts like read_operands' (one part except the split's layer inputs and gradients)."""
+    from nerf_tiny_amd import _abi
+
+    ops = read_operands(ws, B, Nc, Nf, flags)
+    dev = ws.device
+    view = lambda name, shape, dt=None: _abi.ws_view(ws, B, Nc, Nf, flags, name, shape, dt)
+    cat = lambda a, b: torch.cat((a, b))
+    ops["spre"] = (view("spre", (B * (Nc + Nf),)),)
+    ops["sig"] = (cat(view("sig_c", (B * Nc,)), view("sig_f", (B * Nf,))),)
+    ops["rgb"] = (cat(view("rgb_c", (B * Nc, 3)), view("rgb_f", (B * Nf, 3))),)
+    ops["drgb"] = (cat(view("drgb_c", (B * Nc, 3)), view("drgb_f", (B * Nf, 3))),)
+    ops["dsig"] = (cat(view("dsig_c", (B * Nc,)), view("dsig_f", (B * Nf,))),)
+    if flags & (_abi.BF16_MLP | _abi.SPLIT_MLP):
+        _, wb_tot, ranges = pass_rows(B, Nc, Nf)
+        m = decode_bmask(view("bmask", (BM_LAYERS * wb_tot * 64 * 8,), torch.int16), wb_tot)
+        for l in range(8):
+            ops[f"m{l}"] = (_real(m[l], ranges),)
+        ops["mc"] = (_real(m[8], ranges)[:, :HALF],)
+        fold = view("fold", (HALF + HALF * WIDTH,))
+        ops["b_fold"], ops["fold"] = (fold[:HALF],), (fold[HALF:].view(HALF, WIDTH),)
+        return ops
+    tiles_c, tiles_f = -(-B * Nc // TM), -(-B * Nf // TM)
+    m = decode_relu_masks(view("masks", (8, tiles_c + tiles_f, 4, 256), torch.int16))
+    for l in range(8):
+        ops[f"m{l}"] = (cat(m[l, :B * Nc], m[l, tiles_c * TM:tiles_c * TM + B * Nf]),)
+    ops["mc"] = (ops["c"][0] > 0,)
+    ray = torch.cat((torch.arange(B * Nc, device=dev) // Nc, torch.arange(B * Nf, device=dev) // Nf))
+    ops["start"] = (view("dvec", (B, HALF))[ray],)
+    return ops
+
+
+def rows(ops, a, b):
+    """The operands of rows [a, b) only."""
+    return {k: v if k in NOT_ROWS else tuple(t[a:b] for t in v) for k, v in ops.items()}
+
+
+# ---- bf16 rounding, exactly ----------------------------------------------------------------------------------------------------
+BF16_EMIN = -133  # exponent of the smallest bf16 subnormal
+
+
+def pow2(q):
+    """2^q as float64, exactly, for integer tensors q in [-1022, 1023] (torch.ldexp forms 2^q with pow, which need not be exact on the
+    device)."""
+    return ((q.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def _bf16_exponent(x):
+    """Exponent q of the bf16 unit in the last place at |x| (8 significant bits; subnormals share 2^-133)."""
+    _, e = torch.frexp(x)
+    return torch.clamp(e.to(torch.int64) - 8, min=BF16_EMIN)
+
+
+def rne_bf16(x):
+    """float64 -> the nearest bf16 value, ties to even (torch.round rounds half to even), as float64.  Exact: no detour through fp32
+    (.to(torch.bfloat16) of a float64 may round twice), and the scalings are exact powers of two.  Beyond the bf16 range nothing is checked: the operands here are far inside."""
+    q = _bf16_exponent(x)
+    return torch.round(x * pow2(-q)) * pow2(q)
+
+
+def trunc_bf16(x):
+    """float64 -> bf16 by truncation toward zero (the teeth of the RNE interval test)."""
+    q = _bf16_exponent(x)
+    return torch.trunc(x * pow2(-q)) * pow2(q)
+
+
+def ulp_bf16(x):
+    """The bf16 spacing at |x| (upward from |x|)."""
+    return pow2(_bf16_exponent(x))
+
+
+def split_bf16(w):
+    """fp32 values (as float64) -> (hi, mid) = (RNE(w), RNE(w - hi)): the split-fp32 parts (w - hi is exact in fp32)."""
+    hi = rne_bf16(w)
+    return hi, rne_bf16(w - hi)
+
+
+# ---- the forward and the dX chain: float64 references --------------------------------------------------------------------------
+SPLIT_TERMS = ((0, 0), (0, 1), (1, 0))  # (operand part, weight part): hi.hi + hi.mid + mid.hi (mid.mid is not in the kernels' arithmetic)
+
+
+def _mv(X, Wp, Wmag=None, terms=SPLIT_TERMS, transpose=True):
+    """sum over terms of X[i] W[j]^T (transpose=False: X[i] W[j]) in float64, and the same on absolute values (Wmag: the magnitude
+    matrix of a weight whose value is not a plain product -- the fp32 fold)."""
+    terms = [(0, 0)] if len(X) == 1 else terms
+    v = m = 0
+    for i, j in terms:
+        x, w = X[i].double(), Wp[j]
+        wm = Wmag if Wmag is not None else w.abs()
+        if transpose:
+            w, wm = w.T, wm.T
+        v = v + x @ w
+        m = m + x.abs() @ wm
+    return v, m
+
+
+def reference_weights(ops, weights, mode):
+    """The weight operands the kernels multiplied by, float64, as tuples of parts, and the float64 biases.
+      fp32   the parameters; W_fold = W_dir[:, 24:] W_pi in float64 (the fp32 packer folds straight into `packed`), magnitude
+             |W_dir[:, 24:]| |W_pi|; the start of dir_info = the workspace's dvec (no W_dir[:, :24] term)
+      bf16   RNE-bf16 of the parameters and of the device's fp32 W_fold (oracle.mlp_bf16 is the spec); the start = b_dir + b_fold
+             plus W_dir[:, :24] gamma_d
+      split  (hi, mid) of the same fp32 values"""
+    parts = (lambda w: (w.double(),)) if mode == "fp32" else (lambda w: (rne_bf16(w.double()),)) if mode == "bf16" else \
+        (lambda w: split_bf16(w.double()))
+    out = {"W": [parts(weights[2 * l]) for l in range(8)], "b": [weights[2 * l + 1].double() for l in range(8)],
+           "w_sigma": parts(weights[W_SIGMA]), "b_sigma": weights[B_SIGMA].double(),
+           "W_color": parts(weights[W_COLOR]), "b_color": weights[B_COLOR].double()}
+    Wd = weights[W_DIR].double()
+    if mode == "fp32":
+        Wpi = weights[W_PI].double()
+        out["W_fold"], out["W_fold_mag"] = (Wd[:, DIR_DIM:] @ Wpi,), Wd[:, DIR_DIM:].abs() @ Wpi.abs()
+    else:
+        out["W_fold"], out["W_fold_mag"] = parts(ops["fold"][0]), None
+        out["W_dir_gd"] = parts(weights[W_DIR][:, :DIR_DIM])
+        out["b_dir"] = weights[B_DIR].double() + ops["b_fold"][0].double()
+    return out
+
+
+def iter_layer_reference(ops, weights, mode, terms=SPLIT_TERMS):
+    """Each forward layer in float64 from the device's own saved input of that layer: yields (name, (value, magnitude, pre-activation)).
+      h0..h7  relu(W_l x + b_l), x = gamma_p, h_{l-1}, or cat(h3, gamma_p) (hidden first) for layer 4
+      spre    w_sigma . h7 + b_sigma          sigma  |spre|
+      c       relu(W_fold h7 + start)         rgb    sigmoid(W_c c + b_c)  (magnitude and pre-activation: of W_c c + b_c)
+    mode: "fp32", "bf16" or "split" (reference_weights).  Magnitude = the same formula on absolute values, |W| |x| + |b|."""
+    R = reference_weights(ops, weights, mode)
+    cat = lambda a, b: tuple(torch.cat((x, y), 1) for x, y in zip(a, b))
+    for l in range(8):
+        X = ops["gp"] if l == 0 else cat(ops["h3"], ops["gp"]) if l == 4 else ops[f"h{l - 1}"]
+        v, m = _mv(X, R["W"][l], terms=terms)
+        v, m = v + R["b"][l], m + R["b"][l].abs()
+        yield f"h{l}", (v.clamp_min(0), m, v)
+        del v, m
+    v, m = _mv(ops["h7"], R["w_sigma"], terms=terms)
+    v, m = v[:, 0] + R["b_sigma"], m[:, 0] + R["b_sigma"].abs()
+    yield "spre", (v, m, v)
+    yield "sigma", (v.abs(), m, v)
+    v, m = _mv(ops["h7"], R["W_fold"], R["W_fold_mag"], terms=terms)
+    if mode == "fp32":
+        s = ops["start"][0].double()
+        v, m = v + s, m + s.abs()
+    else:
+        vd, md = _mv(ops["gd"], R["W_dir_gd"], terms=terms)
+        v, m = v + vd + R["b_dir"], m + md + R["b_dir"].abs()
+    yield "c", (v.clamp_min(0), m, v)
+    v, m = _mv(ops["c"], R["W_color"], terms=terms)
+    v, m = v + R["b_color"], m + R["b_color"].abs()
+    yield "rgb", (torch.sigmoid(v), m, v)
+
+
+def layer_reference(ops, weights, mode):
+    """{name: (value, magnitude, pre-activation)} of iter_layer_reference (all at once: small batches and CPU checks)."""
+    return dict(iter_layer_reference(ops, weights, mode))
+
+
+def upstream_reference(ops):
+    """The chain's first step, in the kernels' fp32 arithmetic (field_bwd_reg.hip:233, -ffp-contract=off): dz = drgb * ((1 - o) * o),
+    o the saved per-sample rgb, and dspre = dsig * sign(spre), sign(0) = 0.  fp32 tensors."""
+    o, up = ops["rgb"][0], ops["drgb"][0]
+    return up * ((1 - o) * o), ops["dsig"][0] * torch.sign(ops["spre"][0])
+
+
+def iter_chain_reference(ops, weights, mode, terms=SPLIT_TERMS):
+    """Each layer of the dX chain in float64 from the device's own next-layer operand: yields (name, (value, magnitude)).
+      gdir  [c > 0] (W_c^T dz)          g7  mask7 (W_fold^T gdir + w_sigma dspre)
+      g_l   mask_l (W_{l+1}^T g_{l+1}), the first 256 columns of W4 for g3
+    The masks are the device's (checked against the forward's pre-activations separately)."""
+    R = reference_weights(ops, weights, mode)
+    v, m = _mv(ops["dz"], R["W_color"], terms=terms, transpose=False)
+    mk = ops["mc"][0]
+    yield "gdir", (v * mk, m * mk)
+    v, m = _mv(ops["gdir"], R["W_fold"], R["W_fold_mag"], terms=terms, transpose=False)
+    vs, ms = _mv(ops["dspre"], R["w_sigma"], terms=terms, transpose=False)
+    mk = ops["m7"][0]
+    yield "g7", ((v + vs) * mk, (m + ms) * mk)
+    for l in range(6, -1, -1):
+        W = tuple(w[:, :WIDTH] for w in R["W"][l + 1])
+        v, m = _mv(ops[f"g{l + 1}"], W, terms=terms, transpose=False)
+        mk = ops[f"m{l}"][0]
+        yield f"g{l}", (v * mk, m * mk)
+        del v, m
+
+
+def chain_reference(ops, weights, mode):
+    """{name: (value, magnitude)} of iter_chain_reference."""
+    return dict(iter_chain_reference(ops, weights, mode))
