@@ -47,7 +47,7 @@ extern "C" {
                                   7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
                                      nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps;
                                      nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad; nerf_hip_metrics_ws_bytes,
-                                     nerf_hip_image_metrics */
+                                     nerf_hip_image_metrics; nerf_hip_forward_maps_train, nerf_hip_backward_maps */
 
 enum {
   NERF_HIP_OK = 0,
@@ -154,6 +154,18 @@ int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, con
                           void* ws, size_t ws_bytes, int flags, void* stream);
 
 /*
+ * nerf_hip_forward_maps for TRAINING (the maps are differentiable through nerf_hip_backward_maps).  The arguments of
+ * nerf_hip_forward_maps; NERF_HIP_SAVE_FOR_BACKWARD is required (without it, or with a null maps: NERF_HIP_ERR_ARG before any device
+ * work).  Every training mode (exact fp32, NERF_HIP_FORCE_TILE_KERNEL, split-fp32, bf16 MLP, NERF_HIP_CORRECTED); C_coarse, C_fine, the
+ * status word and the workspace's saves are those of nerf_hip_forward with the same flags.  The per-ray stages always run as separate
+ * launches: at the small bf16-MLP sizes where nerf_hip_forward fuses them into the field launches, this call does not.
+ */
+int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* row, const int64_t* col,
+                                const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
+                                int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
+                                void* ws, size_t ws_bytes, int flags, void* stream);
+
+/*
  * Backward of nerf_hip_forward (autograd through nerf.py:286-323, called at nerf.py:473).
  * Needs the workspace of a forward run with NERF_HIP_SAVE_FOR_BACKWARD and the same sizes/inputs.
  *   dC_coarse, dC_fine [B,3] f32   upstream gradients
@@ -177,6 +189,24 @@ int nerf_hip_backward_overlap(const float* const* weights24, const float* dC_coa
                               const float* ray0_near_far, int B, int Nc, int Nf, float last_delta,
                               float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream,
                               void* early_event);
+
+/*
+ * nerf_hip_backward_overlap with the upstream gradient of the maps as well.
+ *   dmaps   [B,4] f32, device, not NULL: g = (gD_c, gA_c, gD_f, gA_f) per ray, the gradient of the loss with respect to
+ *           (D_c, A_c, D_f, A_f) of nerf_hip_forward_maps.  Its terms, added behind the colour terms as separate additions:
+ *             d w_c,i += gD_c t_c,i + gA_c        (every coarse sample i; t_c carries no gradient)
+ *             d w_k   += gD_f t_s,k + gA_f        (sorted position k of the merged samples)
+ *             d t_s,k += gD_f w_k                 (through the t channel's own permutation to d t_fine; a coarse origin drops it;
+ *                                                  NERF_HIP_CORRECTED detaches t_fine and drops it with the rest)
+ *           With dmaps = 0 every gradient equals nerf_hip_backward's bit for bit.
+ * Valid after either training forward (nerf_hip_forward or nerf_hip_forward_maps_train with NERF_HIP_SAVE_FOR_BACKWARD) on the
+ * workspace.  The per-ray stages always run as separate launches (never fused into the bf16-MLP chain launches).  Null dmaps ->
+ * NERF_HIP_ERR_ARG before any device work.
+ */
+int nerf_hip_backward_maps(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
+                           const float* ray0_near_far, int B, int Nc, int Nf, float last_delta,
+                           float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream,
+                           void* early_event);
 
 /*
  * One train step's device work in ONE call: nerf_hip_forward (with NERF_HIP_SAVE_FOR_BACKWARD), nerf_hip_ray_loss and

@@ -308,13 +308,16 @@ struct TrainLoss {
   float *dC_c, *dC_f, *terms, *loss;
   bool fused;
 };
-// maps: nerf_hip_forward_maps's [B][4] output (inference calls only; its caller has checked the flags), else null
+// maps: the [B][4] output of nerf_hip_forward_maps (inference) / nerf_hip_forward_maps_train (training; its caller has checked the flags),
+// else null.  A maps call always takes the separate k_coarse / k_merge launches (never the pair kernel, never the FwdFuse epilogues)
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
                  int flags, void* stream, TrainLoss* tl, float* maps = nullptr);
+// dmaps: nerf_hip_backward_maps's [B][4] upstream of the maps (its caller has checked it), else null.  A dmaps call always takes the
+// separate k_merge_bwd_maps / k_coarse_bwd_maps launches (never the BwdFuse prologues)
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl);
+                  const TrainLoss* tl, const float* dmaps = nullptr);
 }  // namespace
 
 extern "C" {
@@ -330,6 +333,16 @@ int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, con
                           const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
                           float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream) {
   if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_maps is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
+  if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
+  return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
+                      nullptr, maps);
+}
+
+int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
+                                const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
+                                float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream) {
+  if (!(flags & NERF_HIP_SAVE_FOR_BACKWARD))
+    return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_maps_train is training only (NERF_HIP_SAVE_FOR_BACKWARD not set)");
   if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
                       nullptr, maps);
@@ -454,7 +467,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     return NERF_HIP_OK;
   }
   // SMALL bf16 TRAINING batches at the shipped sample counts: k_coarse / k_merge ride as epilogues of the field launches (kernels.h FwdFuse)
-  const bool fuse_rays = bf16 && save && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected;
+  const bool fuse_rays = bf16 && save && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !maps;
   FwdFuse ff;
   memset(&ff, 0, sizeof(ff));
   const bool tile_kernel = (flags & NERF_HIP_FORCE_TILE_KERNEL) != 0;
@@ -566,13 +579,21 @@ int nerf_hip_backward_overlap(const float* const* weights24, const float* dC_coa
                        nullptr);
 }
 
+int nerf_hip_backward_maps(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
+                           const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* const* dweights24, void* ws,
+                           size_t ws_bytes, int flags, void* stream, void* early_event) {
+  if (!dmaps) return fail(NERF_HIP_ERR_ARG, "dmaps is null");
+  return backward_impl(weights24, dC_coarse, dC_fine, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes, flags, stream, early_event,
+                       nullptr, dmaps);
+}
+
 }  // extern "C"
 
 namespace {
 
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl) {
+                  const TrainLoss* tl, const float* dmaps) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (int rc = check_weights(const_cast<const float* const*>(dweights24))) return rc;
@@ -606,10 +627,12 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   mb.drgb_f = at<float>(ws, L.drgb_f); mb.dsig_f = at<float>(ws, L.dsig_f); mb.dt_f = at<float>(ws, L.dt_f);
   // SMALL bf16 batches: the per-ray backward stages ride as prologues of the chain launches (kernels.h BwdFuse)
   const bool corrected = (flags & NERF_HIP_CORRECTED) != 0;
-  const bool fuse_rays = bf16 && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected;  // (must agree with the forward's choice)
+  // (the workspace holds the same saves after a fused and after a separate forward: either backward form may follow either forward)
+  const bool fuse_rays = bf16 && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !dmaps;
   BwdFuse bz;
   memset(&bz, 0, sizeof(bz));
-  if (!fuse_rays) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd(mb, st)); }
+  if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd_maps(mb, dmaps, st)); }
+  else if (!fuse_rays) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd(mb, st)); }
 
   // 2. fine-pass field backward (dX chain incl. d loss / d t_fine)
   FieldBwdArgs fb;
@@ -656,6 +679,7 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   if (ray0_near_far) { cb.ray0_override = 1; cb.near0 = ray0_near_far[0]; cb.far0 = ray0_near_far[1]; }
   cb.drgb_c = at<float>(ws, L.drgb_c); cb.dsig_c = at<float>(ws, L.dsig_c);
   if (fuse_rays) { bz.mode = 2; bz.c = cb; }
+  else if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd_maps(cb, dmaps, st)); }
   else { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd(cb, st)); }
 
   // 4. coarse-pass field backward

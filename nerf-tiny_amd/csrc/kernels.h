@@ -186,7 +186,7 @@ hipError_t launch_rays(const RaysArgs& a, hipStream_t st);
 constexpr int PREP_READY_WORDS = 256;
 hipError_t launch_prep_bf16(const Weights24& w, float* fold, unsigned char* img_fwd, int fwd_form, unsigned char* img_bwd,
                             unsigned* ready, unsigned token, unsigned* sticky, const RaysArgs& rays, hipStream_t st);
-// maps != null (nerf_hip_forward_maps, inference): k_coarse_maps / k_merge_maps, which also store each ray's (D_c, A_c) / (D_f, A_f) to maps [B][4]
+// maps != null (nerf_hip_forward_maps, nerf_hip_forward_maps_train): k_coarse_maps / k_merge_maps, which also store each ray's (D_c, A_c) / (D_f, A_f) to maps [B][4]
 hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps = nullptr);
 size_t merge_lds_bytes(int P);
 hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps = nullptr);
@@ -362,6 +362,9 @@ hipError_t launch_small_grads(const SmallGradArgs& a, float* scratch, hipStream_
 size_t merge_bwd_lds_bytes(int N);
 hipError_t launch_merge_bwd(const MergeBwdArgs& a, hipStream_t st);
 hipError_t launch_coarse_bwd(const CoarseBwdArgs& a, hipStream_t st);
+// nerf_hip_backward_maps: k_merge_bwd_maps / k_coarse_bwd_maps, which also take each ray's upstream (gD_c, gA_c, gD_f, gA_f) from dmaps [B][4]
+hipError_t launch_merge_bwd_maps(const MergeBwdArgs& a, const float* dmaps, hipStream_t st);
+hipError_t launch_coarse_bwd_maps(const CoarseBwdArgs& a, const float* dmaps, hipStream_t st);
 
 struct AdamArgs {
   float* param[24];

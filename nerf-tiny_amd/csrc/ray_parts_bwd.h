@@ -24,18 +24,29 @@ __device__ __forceinline__ double wave_suffix_scan_d(double v, int lane) {
   return v;
 }
 
-// backward of the merged composite + channel sorts for ONE ray by one wave (nerf.py:302-321); sm_f: 4 * (Nc + Nf) floats of LDS of this wave;
-// `sync` orders this wave's LDS writes before its reads (a one-wave workgroup passes __syncthreads, a wave of a bigger workgroup a wave fence)
-template <class Sync>
-__device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int ray, const int lane, float* sm_f, Sync&& sync) {
+// backward of the merged composite + channel sorts for ONE ray by one wave (nerf.py:302-321); sm_f: 4 * (Nc + Nf) floats of LDS of this wave
+// (MAPS: 5 * (Nc + Nf)); `sync` orders this wave's LDS writes before its reads (a one-wave workgroup passes __syncthreads, a wave of a bigger
+// workgroup a wave fence).
+// MAPS (nerf_hip_backward_maps): dmaps [B][4] holds each ray's upstream (gD_c, gA_c, gD_f, gA_f); the fine maps add
+// gD_f t_s,k + gA_f to dw_k (pass 1) and gD_f w_k to d t_s,k (pass 3, un-sorted through perm[0] as the delta terms), each as a separate
+// addition behind the colour-only expression.  Without MAPS the code is the colour-only one.
+template <bool MAPS = false, class Sync>
+__device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int ray, const int lane, float* sm_f, Sync&& sync,
+                                              const float* dmaps = nullptr) {
   const int N = a.Nc + a.Nf;
   float* s_te = sm_f;          // T_k * exp(-s_k)
   float* s_dww = sm_f + N;     // dw_k * w_k
   float* s_dw = sm_f + 2 * N;  // dw_k
   float* s_dd = sm_f + 3 * N;  // d delta_k
+  float* s_w = sm_f + 4 * N;   // w_k (MAPS only)
   const float* bun = a.bundle + (size_t)ray * N * 5;
   const float dC0 = a.dC_f[(size_t)ray * 3], dC1 = a.dC_f[(size_t)ray * 3 + 1], dC2 = a.dC_f[(size_t)ray * 3 + 2];
   const uint16_t* pm = a.perm + (size_t)ray * 5 * N;
+  float gD = 0.f, gA = 0.f;  // (MAPS only)
+  if constexpr (MAPS) {
+    gD = dmaps[(size_t)ray * 4 + 2];
+    gA = dmaps[(size_t)ray * 4 + 3];
+  }
 
   // pass 1 (forward): recompute T, w exactly as k_merge did; d rgb_sorted scattered immediately
   double carry = 0.0;
@@ -53,7 +64,11 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
     const float wi = T * (1.0f - e);
     if (v) {
       const float r = bun[(size_t)i * 5 + 1], g = bun[(size_t)i * 5 + 2], b = bun[(size_t)i * 5 + 3];
-      const float dw = __builtin_fmaf(b, dC2, __builtin_fmaf(g, dC1, r * dC0));
+      float dw = __builtin_fmaf(b, dC2, __builtin_fmaf(g, dC1, r * dC0));
+      if constexpr (MAPS) {
+        dw += gD * ti + gA;
+        s_w[i] = wi;
+      }
       s_te[i] = T * e;
       s_dw[i] = dw;
       s_dww[i] = dw * wi;
@@ -95,15 +110,19 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
     float g = 0.f;
     if (i > 0) g += s_dd[i - 1];
     if (i + 1 < N) g -= s_dd[i];
+    if constexpr (MAPS) g += gD * s_w[i];
     const int src = pm[i];
     if (src >= a.Nc) a.dt_f[(size_t)ray * a.Nf + (src - a.Nc)] = g;  // t_coarse carries no gradient
   }
 }
 
 
-// backward of resampling + coarse composite for ONE ray by one wave (nerf.py:225-281); w: 5 * Nc floats, ks: Nf u16 of LDS of this wave
-template <class Sync>
-__device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int ray, const bool live, const int lane, float* w, uint16_t* ks, Sync&& sync) {
+// backward of resampling + coarse composite for ONE ray by one wave (nerf.py:225-281); w: 5 * Nc floats, ks: Nf u16 of LDS of this wave.
+// MAPS (nerf_hip_backward_maps): the coarse maps add gD_c t_c,i + gA_c (dmaps [B][4] columns 0, 1) to dw_i as a separate addition
+// behind the colour-only sum; t_c carries no gradient.  Without MAPS the code is the colour-only one.
+template <bool MAPS = false, class Sync>
+__device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int ray, const bool live, const int lane, float* w, uint16_t* ks, Sync&& sync,
+                                               const float* dmaps = nullptr) {
   const int Nc = a.Nc, Nf = a.Nf;
   float near, far;
   if (a.rayf) {
@@ -202,7 +221,12 @@ __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int
   }
   sync();
   const float dC0 = a.dC_c[(size_t)ray * 3], dC1 = a.dC_c[(size_t)ray * 3 + 1], dC2 = a.dC_c[(size_t)ray * 3 + 2];
-  // dw_i = suffix_sum(dcdf)_i + dwn_{i-1} + rgb_i . dC_c ; then composite backward
+  float gD = 0.f, gA = 0.f;  // (MAPS only)
+  if constexpr (MAPS) {
+    gD = dmaps[(size_t)ray * 4];
+    gA = dmaps[(size_t)ray * 4 + 1];
+  }
+  // dw_i = suffix_sum(dcdf)_i + dwn_{i-1} + rgb_i . dC_c (+ gD_c t_c,i + gA_c) ; then composite backward
   double rc = 0.0, rc2 = 0.0;
   const int nchunks = (Nc + 63) / 64;
   for (int ch = nchunks - 1; ch >= 0; --ch) {
@@ -215,6 +239,7 @@ __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int
     if (v) {
       dw = (float)sufc + (i > 0 ? ys[i - 1] : 0.f);
       dw += __builtin_fmaf(a.rgb[gi * 3 + 2], dC2, __builtin_fmaf(a.rgb[gi * 3 + 1], dC1, a.rgb[gi * 3] * dC0));
+      if constexpr (MAPS) dw += gD * a.t_c[gi] + gA;
     }
     const double suf = wave_suffix_scan_d(v ? (double)(dw * w[i]) : 0.0, lane) + rc2;
     rc2 = __shfl(suf, 0);

@@ -66,7 +66,9 @@ def data_preprocess(root_dir: str, type: str, mode: str) -> None:
 
 class NeRFDataset(torch.utils.data.Dataset):
     """Per-pixel dataset with the reference's constructor, attributes and ``__getitem__`` tuple (loader.py:61-133):
-    ``(row, column, pix_val[3], poses_bound[17], pic)``.  ``low_res`` is stored and not applied, like the reference."""
+    ``(row, column, pix_val[3], poses_bound[17], pic)``.  ``low_res`` is stored and not applied, like the reference.
+    ``all_alpha`` (not in the reference): ``[num_pix]`` fp32, each pixel's PNG alpha / 255 for ``type="sync"`` (the RGB is composited on
+    white exactly as before), None for LLFF."""
 
     def __init__(self, root_dir, low_res=8, transform=None, type="sync", mode="train"):
         from PIL import Image
@@ -86,15 +88,18 @@ class NeRFDataset(torch.utils.data.Dataset):
         self.pic_size = self.height * self.width
         self.num_pix = self.pic_size * self.pic_num
         imgs = torch.zeros(self.pic_num, self.height, self.width, 3)
+        alpha = torch.zeros(self.pic_num, self.height, self.width) if type == "sync" else None
         for i, path in enumerate(self.file_list):
             with Image.open(path) as im:
                 im.load()
                 if type == "sync":  # RGBA on white (loader.py:67-71)
+                    alpha[i] = torch.tensor(np.array(im.split()[3]) / 255.0)
                     bg = Image.new("RGB", im.size, (255, 255, 255))
                     bg.paste(im, mask=im.split()[3])
                     im = bg
                 imgs[i] = torch.tensor(np.array(im) / 255.0)
         self.all_pix = imgs.flatten(0, 2)
+        self.all_alpha = alpha.flatten() if alpha is not None else None
 
     def __len__(self):
         return self.num_pix
@@ -106,15 +111,19 @@ class NeRFDataset(torch.utils.data.Dataset):
 
 
 class ArrayDataset(torch.utils.data.Dataset):
-    """Same tuple as NeRFDataset from in-memory arrays (synthetic scenes, tests)."""
+    """Same tuple as NeRFDataset from in-memory arrays (synthetic scenes, tests).  alpha: optional [N, H, W] per-pixel opacity
+    (``all_alpha``, as NeRFDataset's)."""
 
-    def __init__(self, images: torch.Tensor, poses_bounds: np.ndarray):
+    def __init__(self, images: torch.Tensor, poses_bounds: np.ndarray, alpha: torch.Tensor | None = None):
         self.pic_num, self.height, self.width, _ = images.shape
         self.poses_bounds = np.asarray(poses_bounds, dtype=np.float64)
         self.focal = self.poses_bounds[0][14]
         self.pic_size = self.height * self.width
         self.num_pix = self.pic_size * self.pic_num
         self.all_pix = images.to(torch.float32).flatten(0, 2)
+        if alpha is not None and tuple(alpha.shape) != tuple(images.shape[:3]):
+            raise ValueError(f"alpha of shape {tuple(alpha.shape)} for images of shape {tuple(images.shape)}: [N, H, W] expected")
+        self.all_alpha = alpha.to(torch.float32).flatten() if alpha is not None else None
 
     def __len__(self):
         return self.num_pix
@@ -149,13 +158,14 @@ def synthetic_scene(n_pic=8, H=64, W=64, seed=0):
 def analytic_sphere_scene(n_pic=24, H=64, W=64, seed=5, device="cuda:0"):
     """A multi-view-CONSISTENT synthetic scene: a unit sphere at the origin (position-coloured, Lambert-shaded) in front of
     a white background, seen by the ring of cameras of ``synthetic_scene``.  The rays come from ``nerf_hip_rays``, i.e. the
-    reference's camera convention incl. quirk Q2.  Returns an ArrayDataset."""
+    reference's camera convention incl. quirk Q2.  Returns an ArrayDataset whose alpha is 1 where the ray hits the sphere, 0 elsewhere."""
     from . import ops
 
     base = synthetic_scene(n_pic=n_pic, H=H, W=W, seed=seed)
     poses = base.poses_bounds
     K_inv = torch.tensor([[1.0, 0.0, -0.5 * W], [0.0, -1.0, 0.5 * H], [0.0, 0.0, -base.focal]]).float().t()
     imgs = torch.ones(n_pic, H, W, 3)
+    alpha = torch.zeros(n_pic, H, W)
     rr, cc = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
     row, col = rr.reshape(-1).to(device), cc.reshape(-1).to(device)
     light = torch.tensor([0.5, 0.3, 0.8]).double()
@@ -171,13 +181,15 @@ def analytic_sphere_scene(n_pic=24, H=64, W=64, seed=5, device="cuda:0"):
         p = o + t[:, None] * d
         colour = (0.5 + 0.5 * p) * (p * light).sum(1).clamp_min(0.15)[:, None]
         imgs[i] = torch.where((disc > 0)[:, None], colour, torch.ones_like(colour)).float().reshape(H, W, 3)
-    return ArrayDataset(imgs, poses)
+        alpha[i] = (disc > 0).float().reshape(H, W)
+    return ArrayDataset(imgs, poses, alpha)
 
 
 class DeviceRays:
     """GPU-resident ray sampler (row f1).  ``for row, col, pix_val, poses_bound, pic in rays.epoch(B)`` yields what the
     reference's ``DataLoader(shuffle=True, drop_last=True)`` yields (nerf.py:424, 458) -- but as device tensors produced
-    by one gather kernel, with the shuffle done by ``torch.randperm`` on the device."""
+    by one gather kernel, with the shuffle done by ``torch.randperm`` on the device.  ``alpha``: the dataset's per-pixel opacity
+    (``all_alpha``) on the device, or None; ``with_alpha=True`` yields it beside a batch (the default tuples are the reference's)."""
 
     def __init__(self, dataset, device, seed: int | None = None):
         self.device = torch.device(device)
@@ -185,12 +197,14 @@ class DeviceRays:
         self.pic_num, self.num_pix = dataset.pic_num, dataset.num_pix
         self.pixels = dataset.all_pix.to(self.device, torch.float32).contiguous()
         self.poses = torch.as_tensor(np.asarray(dataset.poses_bounds)).to(torch.float32).to(self.device).contiguous()  # cast like nerf.py:338
+        a = getattr(dataset, "all_alpha", None)
+        self.alpha = a.to(self.device, torch.float32).contiguous() if a is not None else None
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
             self.gen.manual_seed(seed)
 
-    def gather(self, index: torch.Tensor):
-        """index [B] i64 (device) -> (row, col, pix_val, poses_bound, pic)"""
+    def gather(self, index: torch.Tensor, with_alpha: bool = False):
+        """index [B] i64 (device) -> (row, col, pix_val, poses_bound, pic); with_alpha: (row, col, pix_val, poses_bound, pic, alpha [B])"""
         B = index.shape[0]
         dev = self.device
         row = torch.empty(B, dtype=torch.int64, device=dev)
@@ -202,6 +216,10 @@ class DeviceRays:
         _abi.check(_abi.lib().nerf_hip_gather_rays(index.data_ptr(), self.pixels.data_ptr(), self.poses.data_ptr(), B, self.height,
                                                    self.width, row.data_ptr(), col.data_ptr(), pic.data_ptr(), pix.data_ptr(),
                                                    pb.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        if with_alpha:
+            if self.alpha is None:
+                raise ValueError("this dataset has no alpha (LLFF): nothing to yield beside the batch")
+            return row, col, pix, pb, pic, self.alpha[index]
         return row, col, pix, pb, pic
 
     def epoch_order(self, shuffle: bool = True) -> torch.Tensor:
@@ -211,17 +229,19 @@ class DeviceRays:
             return torch.randperm(self.num_pix, device=self.device, generator=self.gen)
         return torch.arange(self.num_pix, device=self.device)
 
-    def epoch(self, batch_ray: int, shuffle: bool = True, first_batch: int = 0):
-        """`first_batch`: skip that many batches of the epoch's order (a resumed run continues the interrupted epoch)."""
+    def epoch(self, batch_ray: int, shuffle: bool = True, first_batch: int = 0, with_alpha: bool = False):
+        """`first_batch`: skip that many batches of the epoch's order (a resumed run continues the interrupted epoch); `with_alpha`: every
+        batch with the alpha of its pixels behind `pic` (gather)."""
         order = self.epoch_order(shuffle)
         for s in range(first_batch * batch_ray, self.num_pix - batch_ray + 1, batch_ray):  # drop_last=True
-            yield self.gather(order[s:s + batch_ray])
+            yield self.gather(order[s:s + batch_ray], with_alpha=True) if with_alpha else self.gather(order[s:s + batch_ray])
 
-    def epoch_sharded(self, batch_ray: int, rank: int, world: int, shuffle: bool = True, first_batch: int = 0):
+    def epoch_sharded(self, batch_ray: int, rank: int, world: int, shuffle: bool = True, first_batch: int = 0, with_alpha: bool = False):
         """One epoch of a data-parallel trainer: every rank draws the SAME order (same seed) and gathers only its contiguous slice
         [lo, hi) of every global `batch_ray` batch (parallel.shard_bounds).  Yields (row, col, pix_val, poses_bound, pic, ray0) where
         ray0 = (near, far) of the GLOBAL batch's ray 0 as host floats -- the one cross-ray term of the path (quirk Q6, nerf.py:233); the
-        pictures of all first rays come to the host in ONE copy per epoch, so the loop itself has no host sync."""
+        pictures of all first rays come to the host in ONE copy per epoch, so the loop itself has no host sync.  `with_alpha`: the slice's
+        alpha behind `pic` (before ray0)."""
         from .parallel import shard_bounds
 
         order = self.epoch_order(shuffle)
@@ -234,7 +254,8 @@ class DeviceRays:
         for b, s in enumerate(starts):
             if b < first_batch:  # (a resumed run continues the interrupted epoch)
                 continue
-            yield (*self.gather(order[s + lo:s + hi]), (float(nf[b, 0]), float(nf[b, 1])))
+            sl = order[s + lo:s + hi]
+            yield (*(self.gather(sl, with_alpha=True) if with_alpha else self.gather(sl)), (float(nf[b, 0]), float(nf[b, 1])))
 
     def __len__(self):
         return self.num_pix

@@ -48,6 +48,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-normals", choices=["grid", "field"], default="grid",
                     help="vertex normals of --mesh: grid = central differences of the lattice (default), field = the field's analytic "
                          "gradient at each vertex (not limited by the grid spacing)")
+    ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
+                    help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--maps", action="store_true",
                     help="display() also renders every frame's expected depth and opacity: <RESULTS_PATH><time>_<iter>_maps.npz (depth, acc, "
                          "near, far) and <i>_depth.png / <i>_acc.png previews beside the frames (rank 0 writes)")
@@ -81,6 +83,7 @@ if __name__ == "__main__":
     kw["split_train"] = args.split_train or ast.literal_eval(c("SPLIT_TRAIN", "False"))
     if args.on_resample_fault or c("ON_RESAMPLE_FAULT"):
         kw["on_resample_fault"] = args.on_resample_fault or c("ON_RESAMPLE_FAULT")
+    kw["mask_weight"] = args.mask_weight if args.mask_weight is not None else float(c("MASK_WEIGHT", 0.0))
     if args.eval_every is not None:
         kw["eval_every"], kw["eval_views"] = args.eval_every, args.eval_views
     # data-parallel: started as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 .../main.py ...`

@@ -83,8 +83,9 @@ def _call_flags(model, need_grad: bool) -> int:
 
 
 def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None):
-    """One nerf_hip_forward call on the model's workspace -> (C_coarse, C_fine, ws, flags).  maps ([B, 4] fp32, inference calls only):
-    nerf_hip_forward_maps instead, which also fills maps with each ray's (D_c, A_c, D_f, A_f) and leaves the colours' bits as they are."""
+    """One nerf_hip_forward call on the model's workspace -> (C_coarse, C_fine, ws, flags).  maps ([B, 4] fp32): nerf_hip_forward_maps
+    (inference) / nerf_hip_forward_maps_train (need_grad) instead, which also fill maps with each ray's (D_c, A_c, D_f, A_f) and leave the
+    colours' bits as they are."""
     B = row.shape[0]
     Nc, Nf = model.num_coarse, model.num_fine
     flags = _call_flags(model, need_grad)
@@ -104,65 +105,104 @@ def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None):
                                                ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
                                                ws.data_ptr(), ws.numel(), call_flags, stream))
     else:
-        _abi.check(_abi.lib().nerf_hip_forward_maps(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9,
-                                                    ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(),
-                                                    ws.data_ptr(), ws.numel(), call_flags, stream))
+        fn = _abi.lib().nerf_hip_forward_maps_train if need_grad else _abi.lib().nerf_hip_forward_maps
+        _abi.check(fn(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
+                      maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags, stream))
     if model._frozen and not need_grad:
         model._packed.add((ws.data_ptr(), flags))
     model._last_ws = ws
     return C_c, C_f, ws, flags
 
 
+def _record(ctx, model, flags, ws, B, params, ray0):
+    """A training forward on the workspace slot of `flags`: what its backward needs, and the slot's generation (a later training forward on
+    the same slot makes this graph's backward raise instead of reading the other call's saves)."""
+    gen = model._ws_generation.get(flags, 0) + 1
+    model._ws_generation[flags] = gen
+    ctx.generation = gen
+    ctx.model, ctx.ws, ctx.flags, ctx.B = model, ws, flags, B
+    ctx.params, ctx.ray0 = params, ray0
+    ctx.bucket = model.grad_bucket  # bound when the graph is recorded: toggling model.grad_bucket later does not change this step
+
+
+def _backward_call(ctx, call):
+    """The shared part of a backward through the library: workspace-generation guard, gradient targets (fresh tensors or the views of
+    model.grad_bucket), then `call(ptr_array(params), ptr_array(grads), stream, early_event)`.  Returns the gradients for autograd (None in
+    bucket mode, where p.grad IS the bucket view)."""
+    model = ctx.model
+    if ctx.generation != model._ws_generation.get(ctx.flags):
+        raise RuntimeError("the workspace of this forward was reused by a later training forward; call backward first")
+    params = ctx.params
+    bucket = ctx.bucket
+    if bucket is not None:
+        # data-parallel trainer: the kernels write straight into views of the flat all-reduce buffer (parallel.GradBucket).
+        # Overwrite semantics: ONE backward per step.  torch.autograd.grad, parameter hooks, gradient accumulation and a second
+        # loss through the same model are not supported in bucket mode (they would see None / overwritten gradients).
+        if len(bucket.params) != len(params) or any(a is not b for a, b in zip(bucket.params, params)):
+            raise RuntimeError("model.grad_bucket was built for other parameters")
+        if bucket.pending:
+            raise RuntimeError("a second backward would overwrite the gradients of the previous one in model.grad_bucket before "
+                               "they were used: bucket.allreduce_sum(), train.FusedAdam.step() / .zero_grad() release it; after any other "
+                               "optimizer's step call bucket.consume()")
+        bucket.pending = True
+        grads = bucket.views
+    else:
+        grads = [torch.empty_like(p) for p in params]
+    stream = torch.cuda.current_stream(params[0].device).cuda_stream
+    # a bucket with overlap enabled gets the event at which point_layer[0..7]'s gradients are final (parallel.GradBucket)
+    early = bucket.early_event_handle if bucket is not None else 0
+    call(_abi.ptr_array(params), _abi.ptr_array(grads), stream, early or None)
+    if bucket is not None:
+        # p.grad IS the bucket view (overwritten every step, like the C ABI's dweights24): nothing for autograd to accumulate
+        for p, v in zip(params, grads):
+            if p.grad is None or p.grad.data_ptr() != v.data_ptr():
+                p.grad = v
+        return [None] * len(params)
+    return grads
+
+
 class _RenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, need_grad, row, col, pb, K9, ray0, *params):
         C_c, C_f, ws, flags = _forward_call(model, need_grad, row, col, pb, K9, ray0, params)
-        B = row.shape[0]
         if need_grad:
-            gen = model._ws_generation.get(flags, 0) + 1
-            model._ws_generation[flags] = gen
-            ctx.generation = gen
-            ctx.model, ctx.ws, ctx.flags, ctx.B = model, ws, flags, B
-            ctx.params, ctx.ray0 = params, ray0
-            ctx.bucket = model.grad_bucket  # bound when the graph is recorded: toggling model.grad_bucket later does not change this step
+            _record(ctx, model, flags, ws, row.shape[0], params, ray0)
         return C_c, C_f
 
     @staticmethod
     def backward(ctx, dC_c, dC_f):
-        model = ctx.model
-        if ctx.generation != model._ws_generation.get(ctx.flags):
-            raise RuntimeError("the workspace of this forward was reused by a later training forward; call backward first")
-        params = ctx.params
-        bucket = ctx.bucket
-        if bucket is not None:
-            # data-parallel trainer: the kernels write straight into views of the flat all-reduce buffer (parallel.GradBucket).
-            # Overwrite semantics: ONE backward per step.  torch.autograd.grad, parameter hooks, gradient accumulation and a second
-            # loss through the same model are not supported in bucket mode (they would see None / overwritten gradients).
-            if len(bucket.params) != len(params) or any(a is not b for a, b in zip(bucket.params, params)):
-                raise RuntimeError("model.grad_bucket was built for other parameters")
-            if bucket.pending:
-                raise RuntimeError("a second backward would overwrite the gradients of the previous one in model.grad_bucket before "
-                                   "they were used: bucket.allreduce_sum(), train.FusedAdam.step() / .zero_grad() release it; after any other "
-                                   "optimizer's step call bucket.consume()")
-            bucket.pending = True
-            grads = bucket.views
-        else:
-            grads = [torch.empty_like(p) for p in params]
         dC_c = dC_c.contiguous().float()
         dC_f = dC_f.contiguous().float()
-        stream = torch.cuda.current_stream(dC_c.device).cuda_stream
-        # a bucket with overlap enabled gets the event at which point_layer[0..7]'s gradients are final (parallel.GradBucket)
-        early = bucket.early_event_handle if bucket is not None else 0
-        _abi.check(_abi.lib().nerf_hip_backward_overlap(_abi.ptr_array(params), dC_c.data_ptr(), dC_f.data_ptr(), ctx.ray0, ctx.B,
-                                                        model.num_coarse, model.num_fine, LAST_DELTA, _abi.ptr_array(grads),
-                                                        ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early or None))
-        if bucket is not None:
-            # p.grad IS the bucket view (overwritten every step, like the C ABI's dweights24): nothing for autograd to accumulate
-            for p, v in zip(params, grads):
-                if p.grad is None or p.grad.data_ptr() != v.data_ptr():
-                    p.grad = v
-            return (None,) * (7 + len(params))
+        model = ctx.model
+        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_overlap(
+            wp, dC_c.data_ptr(), dC_f.data_ptr(), ctx.ray0, ctx.B, model.num_coarse, model.num_fine, LAST_DELTA, gp, ctx.ws.data_ptr(),
+            ctx.ws.numel(), ctx.flags, stream, early)))
         return (None, None, None, None, None, None, None, *grads)
+
+
+class _RenderMapsFn(torch.autograd.Function):
+    """A training forward with maps (nerf_hip_forward_maps_train) -> (C_coarse, C_fine, maps [B, 4]); its backward is ONE
+    nerf_hip_backward_maps call.  An upstream gradient autograd hands over as None counts as zero."""
+
+    @staticmethod
+    def forward(ctx, model, row, col, pb, K9, ray0, *params):
+        ctx.set_materialize_grads(False)
+        M = torch.empty(row.shape[0], 4, dtype=torch.float32, device=row.device)
+        C_c, C_f, ws, flags = _forward_call(model, True, row, col, pb, K9, ray0, params, maps=M)
+        _record(ctx, model, flags, ws, row.shape[0], params, ray0)
+        return C_c, C_f, M
+
+    @staticmethod
+    def backward(ctx, dC_c, dC_f, dM):
+        B = ctx.B
+        dev = ctx.params[0].device
+        up = [torch.zeros(B, n, dtype=torch.float32, device=dev) if g is None else g.contiguous().float()
+              for g, n in ((dC_c, 3), (dC_f, 3), (dM, 4))]
+        model = ctx.model
+        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_maps(
+            wp, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(), ctx.ray0, B, model.num_coarse, model.num_fine, LAST_DELTA, gp,
+            ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early)))
+        return (None, None, None, None, None, None, *grads)
 
 
 def field_normals(g):
@@ -318,31 +358,44 @@ class NeRFModel(nn.Module):
         """nerf.py:325-331: sum (not mean) of squared errors of both colours."""
         return _RayLossFn.apply(C_coarse, C_fine, C_true)
 
-    def forward(self, row, column, poses_bound, K_inv):
+    def mask_loss(self, maps, alpha):
+        """Not in the reference: the alpha-mask loss of object captures, sum_b (A_c,b - alpha_b)^2 + (A_f,b - alpha_b)^2 over the opacity
+        columns of forward(maps=True)'s maps [B, 4] and the batch's alpha [B] -- a sum, like ray_loss.  Plain torch ops on B elements."""
+        a = alpha.reshape(-1).to(maps.device, torch.float32)
+        return torch.sum(torch.square(maps[:, 1] - a)) + torch.sum(torch.square(maps[:, 3] - a))
+
+    def forward(self, row, column, poses_bound, K_inv, maps=False):
         """nerf.py:333-348.  row/column [B] i64, poses_bound [B,17] (any float dtype), K_inv [3,3];
-        CPU or device tensors.  Returns (C_coarse, C_fine) [B,3] fp32 on the model's device."""
+        CPU or device tensors.  Returns (C_coarse, C_fine) [B,3] fp32 on the model's device.
+        maps=True (not in the reference): returns (C_coarse, C_fine, maps) with maps [B, 4] = each ray's (D_c, A_c, D_f, A_f), expected depth
+        and accumulated opacity of the coarse and the fine composite (include/nerf_hip.h).  With grad enabled and a parameter that requires
+        grad the call records a graph and all three outputs are differentiable with respect to the weights (a mask or depth loss:
+        DESIGN.md section 3l); otherwise it is the inference maps call.  The colours' bits are those of maps=False either way."""
         ps = self._params()
         dev = ps[0].device
         if dev.type != "cuda":
             raise RuntimeError("NeRFModel runs only on a ROCm device (MI355X): model.to('cuda'); there is no CPU path")
         if row.shape[0] != self.batch_ray:
             raise ValueError(f"batch of {row.shape[0]} rays, model built for batch_ray={self.batch_ray} (nerf.py:172-176)")
-        return self._launch(ps, row, column, poses_bound, K_inv)
+        return self._launch(ps, row, column, poses_bound, K_inv, maps=maps, train_maps=maps)
 
-    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False):
-        """maps=True (inference only, no graph): nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4])."""
+    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False, train_maps=False):
+        """maps=True: nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4]) -- with no graph unless `train_maps` is set and grad is
+        enabled for a parameter (then nerf_hip_forward_maps_train under _RenderMapsFn)."""
         dev = ps[0].device
         K9 = _abi.f32_array(K_inv.detach().to("cpu", torch.float32).reshape(-1).tolist())
         pb = poses_bound.to(torch.float).to(dev).contiguous()  # cast first like nerf.py:338
         row_d = row.to(dev, torch.int64).contiguous()
         col_d = column.to(dev, torch.int64).contiguous()
         ray0 = _abi.f32_array(self.ray0_near_far) if self.ray0_near_far is not None else None
-        if maps:
+        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
+        if maps and train_maps and need_grad:
+            C_c, C_f, M = _RenderMapsFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)
+        elif maps:
             M = torch.empty(row_d.shape[0], 4, dtype=torch.float32, device=dev)
             with torch.no_grad():
                 C_c, C_f, _, _ = _forward_call(self, False, row_d, col_d, pb, K9, ray0, ps, maps=M)
         else:
-            need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
             C_c, C_f = _RenderFn.apply(self, need_grad, row_d, col_d, pb, K9, ray0, *ps)
         if self.check_resample and self.resample_fault():
             raise ResampleIndexError("resample index outside [0, Nf-1] (the reference exit(0)s here, nerf.py:251-253)")

@@ -134,12 +134,14 @@ def consume_buckets_of(params) -> int:
     return n
 
 
-def train_step_local(model, bucket: GradBucket, row, col, poses_bound, K_inv, C_true, ray0, world: int, group=None):
+def train_step_local(model, bucket: GradBucket, row, col, poses_bound, K_inv, C_true, ray0, world: int, group=None, alpha=None,
+                     mask_weight: float = 0.0):
     """One data-parallel train step on tensors that ARE this rank's slice of the global batch (`NeRFRunner`: the device sampler gathers
     only the slice; `ray0` = (near, far) of the GLOBAL batch's ray 0, host floats -- quirk Q6).  `model.batch_ray` must equal the slice
     size.  Forward + loss + backward with the gradients written straight into `bucket`, then ONE flat SUM all-reduce (in two overlapped
     parts with `bucket.enable_overlap()`), placed where the reference has ``loss.backward(); optimizer.step()`` (nerf.py:473-474).
-    Returns this rank's (C_coarse, C_fine, local loss); every rank then holds the full-batch gradient in p.grad (views of `bucket.flat`)."""
+    Returns this rank's (C_coarse, C_fine, local loss); every rank then holds the full-batch gradient in p.grad (views of `bucket.flat`).
+    mask_weight > 0: the step is train.mask_train_step with the slice's `alpha` (ray_loss + mask_weight * mask_loss through autograd)."""
     prev_ray0, prev_bucket = model.ray0_near_far, model.grad_bucket
     # `model.check_resample` (mimic nerf.py:251-253: raise where the reference exit(0)s) is a RANK-LOCAL raise; taken before the
     # collective it would leave the other ranks blocked in all_reduce.  The check is therefore made AFTER the all-reduce, its
@@ -150,7 +152,11 @@ def train_step_local(model, bucket: GradBucket, row, col, poses_bound, K_inv, C_
     try:
         if check:
             model.check_resample = False
-        if hasattr(model, "train_step"):  # forward + loss + backward in ONE library call (same kernels, same bits)
+        if mask_weight > 0:
+            from .train import mask_train_step
+
+            C_c, C_f, loss = mask_train_step(model, row, col, poses_bound, K_inv, C_true, alpha, mask_weight)
+        elif hasattr(model, "train_step"):  # forward + loss + backward in ONE library call (same kernels, same bits)
             C_c, C_f, loss = model.train_step(row, col, poses_bound, K_inv, C_true)
         else:
             C_c, C_f = model(row, col, poses_bound, K_inv)

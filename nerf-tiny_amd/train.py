@@ -104,6 +104,16 @@ class _NullWriter:
         pass
 
 
+def mask_train_step(model, row, col, poses_bound, K_inv, C_true, alpha, weight):
+    """One train step with the alpha-mask loss (not in the reference): ``forward(maps=True)``, ``loss = ray_loss + weight * mask_loss`` (both
+    sums over the batch), ``loss.backward()`` -- the gradients land where the autograd path puts them (``p.grad``, or the views of
+    ``model.grad_bucket``).  Returns ``(C_coarse, C_fine, loss)`` detached, as ``NeRFModel.train_step`` does."""
+    C_c, C_f, M = model(row, col, poses_bound, K_inv, maps=True)
+    loss = model.ray_loss(C_c, C_f, C_true) + weight * model.mask_loss(M, alpha)
+    loss.backward()
+    return C_c.detach(), C_f.detach(), loss.detach()
+
+
 def _writer():
     try:
         from torch.utils.tensorboard import SummaryWriter  # absent offline
@@ -163,7 +173,7 @@ class NeRFRunner:
                  total_iter=100000, batch_ray=400, learning=1e-3, lr_gamma=0.1, lr_milestone=(10, 200), n_coarse=64, n_fine=128,
                  data_type="sync", step=100, decay_end=200000, sched="EXP", continue_=False, *, datasets=None, log_every=None,
                  seed=624, bf16_mlp=False, split_mlp=False, split_train=False, on_resample_fault="raise", distributed=None, overlap_allreduce=None,
-                 eval_every=None, eval_views=None):
+                 eval_every=None, eval_views=None, mask_weight=0.0):
         from . import nerf as _nerf
         from . import parallel as par
 
@@ -171,6 +181,12 @@ class NeRFRunner:
             raise ValueError(f"eval_every={eval_every!r}: None or a positive number of iterations")
         self.eval_every = eval_every
         self.eval_views = _view_list(eval_views) if eval_views is not None else None
+        mask_weight = float(mask_weight)
+        if not mask_weight >= 0.0 or mask_weight == float("inf"):
+            raise ValueError(f"mask_weight={mask_weight!r}: a finite weight >= 0")
+        self.mask_weight = mask_weight
+        if mask_weight > 0 and datasets is None and data_type == "llff":  # (refused before anything touches the GPU or a process group)
+            raise ValueError(f"MASK_WEIGHT = {mask_weight} needs the per-pixel alpha of the training images; LLFF captures carry none")
 
         # ---- the launcher's environment first: nothing above this line has touched the GPU
         self.env = par.DistEnv.from_env()
@@ -250,6 +266,9 @@ class NeRFRunner:
             return NeRFDataset(root_dir=img_dir, low_res=low_res, transform=None, type=data_type, mode=mode)
 
         self.train_dataset, self.val_dataset, self.disp_dataset = ds("train"), ds("val"), ds("test")
+        if self.mask_weight > 0 and getattr(self.train_dataset, "all_alpha", None) is None:
+            raise ValueError(f"MASK_WEIGHT = {self.mask_weight} needs the per-pixel alpha of the training images; this dataset has none "
+                             f"(data_type={data_type!r}: LLFF captures carry no alpha)")
         # the SAME seeds on every rank: the ranks draw identical permutations and take disjoint slices of every batch
         self.train_rays = DeviceRays(self.train_dataset, self.device, seed)
         self.val_rays = DeviceRays(self.val_dataset, self.device, seed + 1)
@@ -336,8 +355,9 @@ class NeRFRunner:
         self._resume_sampler = None
         while it < self.total_iter:
             epoch_gen_state = rays.gen.get_state()  # (a host copy of the generator's 16 bytes of Philox state: no device sync)
-            batches = (rays.epoch_sharded(self.batch_ray, self.rank, self.world, first_batch=skip) if self.distributed
-                       else rays.epoch(self.batch_ray, first_batch=skip))
+            masked = self.mask_weight > 0  # the alpha of every batch's pixels rides behind `pic`
+            batches = (rays.epoch_sharded(self.batch_ray, self.rank, self.world, first_batch=skip, with_alpha=masked) if self.distributed
+                       else rays.epoch(self.batch_ray, first_batch=skip, with_alpha=masked))
             bi = skip - 1
             skip = 0
             for batch in batches:
@@ -346,8 +366,16 @@ class NeRFRunner:
                 # (no zero_grad: the backward kernels OVERWRITE the bucket's views, which ARE p.grad; FusedAdam.step releases the bucket)
                 if self.distributed:
                     # this rank's slice of the batch: forward + loss + backward into the flat bucket, ONE SUM all-reduce (nerf.py:473-474)
-                    _, _, loss = par.train_step_local(self.model, self.bucket, row, col, poses_bound, self.K_inv, pix_val, batch[5],
-                                                      self.world, self.group)
+                    _, _, loss = par.train_step_local(self.model, self.bucket, row, col, poses_bound, self.K_inv, pix_val, batch[-1],
+                                                      self.world, self.group, alpha=batch[5] if masked else None,
+                                                      mask_weight=self.mask_weight)
+                elif masked:
+                    # ray_loss + MASK_WEIGHT * mask_loss through autograd (forward(maps=True), nerf_hip_backward_maps) into the bucket
+                    self.model.grad_bucket = self.bucket
+                    try:
+                        _, _, loss = mask_train_step(self.model, row, col, poses_bound, self.K_inv, pix_val, batch[5], self.mask_weight)
+                    finally:
+                        self.model.grad_bucket = None
                 else:
                     # nerf.py:470-473 (forward, ray_loss, backward) as ONE library call: same kernels, no interpreter between them
                     self.model.grad_bucket = self.bucket
