@@ -1,6 +1,7 @@
 // field_fwd_reg.hip -- inference forward of the field query with REGISTER-RESIDENT activations (MI355X / gfx950).
 //
-// Same arithmetic as k_field_fwd (field_fwd.hip) and the same packed weight image, but no LDS and no barriers:
+// Same arithmetic as k_field_fwd (field_fwd.hip) and the same packed weight image, but no activations in LDS and no barriers
+// (the forms that save no activation rows send their lazy ReLU through 8 KiB of wave-private LDS: ReluLds below):
 //   * one 64-lane wave owns 32 samples and computes ALL 256 features of every layer for them:
 //     D[feature][sample] = W . act  with v_mfma_f32_32x32x2_f32, 8 feature tiles x 16 accumulator VGPRs;
 //   * in the 32x32 accumulator layout lane (j, h) holds features 32t + 8g + 4h + r of sample j.  The MFMA sums over
@@ -16,10 +17,20 @@
 // One wave per SIMD (about 400 VGPRs).  Used when nothing has to be saved for backward, and for the point queries (k_field_fwd_reg's
 // SRC / RGB template arguments below) -- with GSAVE, the forward of a gradient query (nerf_hip_query_grad).
 #include "field_common.h"
+#include <type_traits>
 
 namespace nerf {
 
 constexpr int RM = 32;  // samples per wave
+
+// f(integral_constant<int, I>) for I = I0 .. I1 - 1
+template <int I0, int I1, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I0 < I1) {
+    f(std::integral_constant<int, I0>{});
+    static_for<I0 + 1, I1>(f);
+  }
+}
 
 template <int NFT>
 struct WStage {
@@ -38,6 +49,46 @@ __device__ __forceinline__ void stage_load(const float4* __restrict__ seg_lane, 
 __device__ __forceinline__ float relu1(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
 __device__ __forceinline__ float f4c(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
+
+// The lazy ReLU of the instantiations that save no activation rows, through LDS instead of the VALU: next to fp32 MFMAs a
+// v_accvgpr_read + v_max_i32 pair per value is matrix time lost, a DS instruction behind an MFMA is not (scripts/micro/mfma_f32_bank.hip,
+// profiles/fwd_f32_relu_paths_micro.txt: ONE DS instruction per MFMA costs nothing, bursts of them do).  A tile of 16 accumulator
+// registers makes the round trip in 24 DS instructions, group g of 4 registers in 6: ds_write_b128 straight from the accumulator
+// registers, 4 x ds_max_i32 with 0 (integer max = relu1, -0 -> +0 included), ds_read_b128 into the B-operand registers.  The DS
+// instructions of a wave execute in order, so the three need no barrier in a 64-thread workgroup, and the compiler counts lgkmcnt.
+// Layout: 2 slots (tile t in slot t & 1) x 4 groups x 64 lanes x 16 bytes = 8 KiB.  The b128 forms are conflict-free with lanes 16 bytes
+// apart; a b32 instruction serves 32 lanes per pass from 32 banks, so the c-th ds_max of lane l takes dword (c + l / 8) & 3 of the
+// lane's 16 bytes: lanes 8 apart hit different banks, all 32 lanes of a pass distinct ones.
+typedef int lds_i32 __attribute__((address_space(3), may_alias));
+typedef int i32x4v __attribute__((ext_vector_type(4), may_alias));
+typedef __attribute__((address_space(3))) i32x4v lds_i32x4;
+constexpr int RELU_LDS_DWORDS = 2 * 4 * 64 * 4;
+struct ReluLds {
+  lds_i32* w;     // this lane's 16 bytes of slot 0, group 0
+  lds_i32* m[4];  // the dword of them that this lane's c-th ds_max takes
+};
+__device__ __forceinline__ ReluLds relu_lds(lds_i32* base, int lane) {
+  ReluLds L;
+  L.w = base + 4 * lane;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) L.m[c] = base + 4 * lane + ((c + (lane >> 3)) & 3);
+  return L;
+}
+// DS instruction i (0..23) of the round trip of accumulator tile src through slot `slot`; the reads (i = 6g + 5) land in dst[4g .. 4g+3]
+template <typename DST>
+__device__ __forceinline__ void relu_lds_op(const ReluLds& L, const f32x16& src, DST& dst, int dst0, int slot, int i) {
+  const int g = i / 6, j = i - 6 * g, off = (slot * 4 + g) * 256;
+  if (j == 0) {
+    const i32x4v v = {__float_as_int(src[4 * g]), __float_as_int(src[4 * g + 1]), __float_as_int(src[4 * g + 2]), __float_as_int(src[4 * g + 3])};
+    *reinterpret_cast<lds_i32x4*>(L.w + off) = v;
+  } else if (j < 5) {
+    __hip_atomic_fetch_max(L.m[j - 1] + off, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else {
+    const i32x4v v = *reinterpret_cast<lds_i32x4*>(L.w + off);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dst[dst0 + c] = __int_as_float(v[c]);
+  }
+}
 
 // acc[f] (+)= sum_k W[f-tile][k] * act(prev)[k]   over KB k-blocks of 8.
 // prev = KB/4 register tiles in accumulator layout; RELU_IN: they are the previous layer's raw accumulators and the
@@ -58,11 +109,18 @@ struct SaveIn {
   uint16_t* mask;   // &masks[layer][tile64][st][h*32 + j] (null = no masks); entry (f, wv) at + (f*2)*256 + wv*64
 };
 
-template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, int SAVE = 0>
+// LDS_RELU (never with SAVE = 1): a ReLU-input layer takes its input tiles through the LDS round trip above, ONE DS instruction behind
+// each MFMA: tile t >= 1 behind the MFMAs of the second half of tile t - 1 (NFT = 8; from its second k-block on with NFT = 4), where the
+// VALU form stood.  Tile 0 has no such lead -- it is complete 7 MFMAs before the producing layer ends -- so the PRODUCER (NEXT_RELU) sends
+// group 0 of its accumulator tile 0 behind its last MFMAs and hands the registers over in `head`; the consumer sends groups 1..3
+// behind its bias MFMAs and its first k-block, each group well ahead of the k-block that reads it.
+template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, int SAVE = 0, bool LDS_RELU = false, bool NEXT_RELU = false>
 __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* float4 offsets into the packed image; < 0: none */, int lane,
                                           const f32x16* prev, f32x16* acc, WStage<8>& st0, const float* bv,
-                                          const SaveIn sv, const RegBuf& rb) {
+                                          const SaveIn sv, const RegBuf& rb, const ReluLds& rl, f32x4v& head) {
+  static_assert(!(LDS_RELU || NEXT_RELU) || SAVE != 1, "the saving forward keeps the VALU ReLU");
   constexpr int KT = KB / 4;
+  constexpr bool LR = LDS_RELU && RELU_IN;
   WStage<8> st1;
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (bv != nullptr) {  // accumulators start at the bias (same rounding order as ATen's addmm and as k_field_fwd)
@@ -71,7 +129,31 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
     for (int f = 0; f < NFT; ++f) acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[f], one_h0, zero, 0, 0, 0);
   }
   f32x16 tin[2];
+  if constexpr (LR) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) tin[0][c] = head[c];
+    if (bv != nullptr) {  // one behind each bias MFMA
+#pragma unroll
+      for (int i = 6; i < 14; ++i) relu_lds_op(rl, prev[0], tin[0], 4 * (i / 6), 0, i);
+#pragma unroll
+      for (int i = 6; i < 14; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
+      }
+    }
+  }
+  [[maybe_unused]] const int lr0 = (bv != nullptr) ? 14 : 6;  // first DS instruction of tile 0 that goes behind the MFMAs of k-block 0
+  auto mask_word = [&](int t) {  // gradient queries: the mask word comes from the raw accumulators, as in the VALU form
+    unsigned bits = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bits |= (prev[t][r] > 0.f) ? (1u << r) : 0u;
+    sv.mask[((t & 1) * 2) * 256 + (t >> 1) * 64] = (uint16_t)bits;
+  };
   auto activate = [&](int t) {
+    if constexpr (LR) {
+      if (SAVE != 0) mask_word(t);
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) tin[t & 1][r] = RELU_IN ? (SAVE == 1 ? fmaxf(prev[t][r], 0.f) : relu1(prev[t][r])) : prev[t][r];  // (the training variant's register allocation falls apart with the integer form)
     // pin the activated tile to this program point; without it the compiler hoists every tile's ReLU to the top of the
@@ -91,6 +173,7 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
     }
   };
   activate(0);
+  if constexpr (!(LR || NEXT_RELU)) {  // the VALU form, as it always was (the saving forward's register allocation hangs on this very text)
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
     WStage<8>& ld = (kb & 1) ? st0 : st1;
@@ -115,6 +198,62 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
           acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(cur.w[f], s), b, acc[f], 0, 0, 0);
       }
     }
+  }
+  } else {
+  // The same stream with the DS instructions of the round trips behind its MFMAs.  The k-block is a compile-time constant here
+  // (static_for): as a loop counter it leaves the DS schedule to the unroller, whose size limit the undecided body then exceeds.
+  // DS instruction numbers that follow MFMA (k4, s, f) of tile kt: i0 of input tile 0, i1 of input tile kt + 1, i2 of output tile 0.
+  auto ds0 = [&](int kt, int k4, int s, int f) { const int i = lr0 + (k4 * 4 + s) * NFT + f; return (LR && kt == 0 && i < 24) ? i : -1; };
+  auto ds1 = [&](int kt, int k4, int s, int f) { const int i = (k4 * 4 + s) * NFT + f - (NFT == 8 ? 64 : 16); return (LR && kt + 1 < KT && i >= 0 && i < 24) ? i : -1; };
+  auto ds2 = [&](int kt, int k4, int s, int f) { return (NEXT_RELU && kt == KT - 1 && k4 == 3 && s == 3 && f < 6) ? f : -1; };
+  static_for<0, KB>([&](auto kbc) __attribute__((always_inline)) {
+    constexpr int kb = decltype(kbc)::value, kt = kb >> 2, k4 = kb & 3;
+    WStage<8>& ld = (kb & 1) ? st0 : st1;
+    const WStage<8>& cur = (kb & 1) ? st1 : st0;
+    if (kb + 1 < KB) {
+#pragma unroll
+      for (int f = 0; f < NFT; ++f) ld.w[f] = reg_ldw(rb, seg + (f * KB + kb + 1) * 64);
+    } else if (next_seg >= 0) {
+#pragma unroll
+      for (int f = 0; f < NNFT; ++f) ld.w[f] = reg_ldw(rb, next_seg + (f * NKB) * 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (k4 == 2 && kt + 1 < KT) activate(kt + 1);  // (gradient queries: the mask word of the next input tile)
+    bool any = false;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const float b = tin[kt & 1][4 * k4 + s];
+#pragma unroll
+      for (int f = 0; f < NFT; ++f) {
+        if (ZERO_INIT && bv == nullptr && kb == 0 && s == 0)
+          acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(cur.w[f], s), b, zero, 0, 0, 0);
+        else
+          acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(cur.w[f], s), b, acc[f], 0, 0, 0);
+        const int i0 = ds0(kt, k4, s, f), i1 = ds1(kt, k4, s, f), i2 = ds2(kt, k4, s, f);
+        if constexpr (LR) {
+          if (i0 >= 0) relu_lds_op(rl, prev[0], tin[0], 4 * (i0 / 6), 0, i0);
+          if (i1 >= 0) relu_lds_op(rl, prev[kt + 1], tin[(kt + 1) & 1], 4 * (i1 / 6), (kt + 1) & 1, i1);
+        }
+        if constexpr (NEXT_RELU) {
+          if (i2 >= 0) relu_lds_op(rl, acc[0], head, 0, 0, i2);
+        }
+        any |= i0 >= 0 || i1 >= 0 || i2 >= 0;
+      }
+    }
+    // the order above is the order wanted: left alone the scheduler gathers each tile's DS instructions into bursts, and a burst holds
+    // the wave's (in-order) issue until the LDS queue has drained -- the MFMAs behind it wait
+    if (any) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int f = 0; f < NFT; ++f) {
+          const int n = (ds0(kt, k4, s, f) >= 0) + (ds1(kt, k4, s, f) >= 0) + (ds2(kt, k4, s, f) >= 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (n == 1) __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
+          if (n == 2) __builtin_amdgcn_sched_group_barrier(0x080, 2, 0);
+        }
+    }
+  });
   }
   if (KB & 1) st0 = st1;  // (all segments have an even number of k-blocks: the next k-block 0 already sits in st0)
 }
@@ -230,6 +369,14 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   constexpr int SV = SAVE ? 1 : (GSAVE ? 2 : 0);
   auto sv_in = [&](int layer) { return GSAVE ? SaveIn{nullptr, mrow + (size_t)layer * MKS} : sv_relu(layer); };
 
+  // the inference forms take the lazy ReLU through LDS (reg_layer); the saving forward allocates none
+  constexpr bool LR = !SAVE;
+  ReluLds rl{};
+  if constexpr (LR) {
+    __shared__ int relu_slots[RELU_LDS_DWORDS];
+    rl = relu_lds((lds_i32*)relu_slots, lane);
+  }
+  f32x4v head = {0.f, 0.f, 0.f, 0.f};  // group 0 of the next layer's input tile 0, activated (LR only)
   RSTAMP(0);  // prologue: ray / depth loads, sample point, positional encoding
   // two accumulator sets ping-pong: a layer reads the previous layer's raw accumulators (ReLU applied lazily)
   f32x16 A[8], B[8];
@@ -240,28 +387,28 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
 
   // ---- layer 0: gamma_p 60(64) -> 256
   bias_load<8>(a.w.p[B_L0], lane, bv);
-  reg_layer<8, 8, 32, 8, true, false, SV>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bv, GSAVE ? SaveIn{gprow, nullptr} : sv_rows(S_GP), rb);
+  reg_layer<8, 8, 32, 8, true, false, SV, LR, LR>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bv, GSAVE ? SaveIn{gprow, nullptr} : sv_rows(S_GP), rb, rl, head);
   RSTAMP(1);  // layer 0 (264 MFMAs)
   // ---- layers 1..3 (the segment after L3 is L4A: same shape)
   bias_load<8>(a.w.p[3], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV>(sL1, sL1 + L256, lane, A, B, st0, bv, sv_in(0), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1, sL1 + L256, lane, A, B, st0, bv, sv_in(0), rb, rl, head);
   bias_load<8>(a.w.p[5], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bv, sv_in(1), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bv, sv_in(1), rb, rl, head);
   bias_load<8>(a.w.p[7], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bv, sv_in(2), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bv, sv_in(2), rb, rl, head);
   RSTAMP(2);  // layers 1..3 (3,096 MFMAs)
   // ---- layer 4: cat(h3, gamma_p), hidden first (nerf.py:109)
   bias_load<8>(a.w.p[9], lane, bv);
-  reg_layer<32, 8, 8, 8, true, true, SV>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bv, sv_in(3), rb);
-  reg_layer<8, 8, 32, 8, false, false>(seg_off4(SEG_L4B), sL5, lane, gp, A, st0, nullptr, SaveIn{nullptr, nullptr}, rb);
+  reg_layer<32, 8, 8, 8, true, true, SV, LR, false>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bv, sv_in(3), rb, rl, head);
+  reg_layer<8, 8, 32, 8, false, false, 0, LR, LR>(seg_off4(SEG_L4B), sL5, lane, gp, A, st0, nullptr, SaveIn{nullptr, nullptr}, rb, rl, head);
   RSTAMP(3);  // layer 4 (1,288 MFMAs)
   // ---- layers 5..7 (the segment after L7 is the folded point_info / dir_info layer: 4 tiles)
   bias_load<8>(a.w.p[11], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV>(sL5, sL5 + L256, lane, A, B, st0, bv, sv_in(4), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL5, sL5 + L256, lane, A, B, st0, bv, sv_in(4), rb, rl, head);
   bias_load<8>(a.w.p[13], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_in(5), rb);
+  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_in(5), rb, rl, head);
   bias_load<8>(a.w.p[15], lane, bv);
-  reg_layer<32, 8, 32, 4, true, true, SV>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_in(6), rb);
+  reg_layer<32, 8, 32, 4, true, true, SV, LR, false>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_in(6), rb, rl, head);
   RSTAMP(4);  // layers 5..7 (3,096 MFMAs)
   // ---- sigma head on h7 = relu(B) (VALU): sigma = |w_sigma . h7 + b|  (nerf.py:94, 115)
   {
@@ -319,7 +466,9 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
         A[f][4 * g + 3] = q.w;
       }
   }
-  reg_layer<32, 4, 32, 4, false, true, SAVE>(seg_off4(SEG_FOLD), -1, lane, B, A, st0, nullptr, GSAVE ? SaveIn{nullptr, nullptr} : sv_relu(7), rb);
+  // (the VALU ReLU in every form: the sigma head above has just activated all of h7 for its own use and the compiler shares those
+  // registers with this layer, so its input costs nothing more; sent through LDS as well, this layer measured 750 cycles per tile slower)
+  reg_layer<32, 4, 32, 4, false, true, SAVE, false, false>(seg_off4(SEG_FOLD), -1, lane, B, A, st0, nullptr, GSAVE ? SaveIn{nullptr, nullptr} : sv_relu(7), rb, rl, head);
   RSTAMP(6);  // point_info + dir_info folded (512 MFMAs)
   // ---- colour head (VALU): rgb = sigmoid(W_c relu(.) + b)  (nerf.py:99, 119)
   {
