@@ -60,8 +60,10 @@ constexpr int PACKED_ALL_F4 = seg_off4(NSEG);
 
 // positional-encoding frequencies f_l = fp32(2^e_l)*fp32(pi), e = linspace(0,L,L) (nerf.py:141-146, quirk Q3);
 // bit patterns as produced by torch 2.10 (tests/golden/make_golden.py prints them; tests/test_oracle_golden.py pins them).
-__device__ __constant__ const uint32_t kFreqPointBits[10] = {0x40490fdbu, 0x40d928aeu, 0x416a8b6cu, 0x41fd527bu, 0x4288cd33u,
-                                                             0x4313c0fau, 0x439f953cu, 0x442c5befu, 0x44ba2881u, 0x45490fdbu};
+#define NERF_FREQ_POINT_BITS 0x40490fdbu, 0x40d928aeu, 0x416a8b6cu, 0x41fd527bu, 0x4288cd33u, 0x4313c0fau, 0x439f953cu, 0x442c5befu, 0x44ba2881u, 0x45490fdbu
+__device__ __constant__ const uint32_t kFreqPointBits[10] = {NERF_FREQ_POINT_BITS};
+// the same ten values for use in constant expressions (an index known at compile time becomes a literal operand: no table, no load)
+constexpr uint32_t kFreqPointLit[10] = {NERF_FREQ_POINT_BITS};
 __device__ __constant__ const uint32_t kFreqDirBits[4] = {0x40490fdbu, 0x40fd527au, 0x419f953cu, 0x42490fdbu};
 
 // weights24 indices

@@ -9,11 +9,12 @@
 //     accumulator registers of layer L are used, as they stand, as the B operand of layer L+1
 //     (k-step (t, 4g + r): half h supplies k = 32t + 8g + 4h + r), and the A fragment that goes with it is the
 //     4 consecutive weights W[i][32t + 8g + 4h .. +3] -- exactly the float4 the packed image already stores;
-//   * nothing is shared between waves, so nothing synchronises: a wave streams 8,256 MFMAs per tile with a
+//   * nothing is shared between waves, so nothing synchronises: a wave streams 8,192 MFMAs per tile (the saving forward 8,256) with a
 //     2-stage register pipeline of A fragments (8 x 16-byte loads per k-block, L2/L1 resident, requested one
 //     k-block = 32 MFMAs = 2048 cycles ahead, also across layer boundaries);
-//   * biases enter as one extra MFMA per tile (A = bias, B = 1 on lane half 0); the sigma and colour heads are
-//     VALU dot products over the registers the wave already holds.
+//   * biases are the start value of the accumulators: 16-byte loads straight into the accumulator registers, requested behind MFMAs
+//     of the layer in front (reg_layer's NEXT_BIAS; the saving forward: one extra MFMA per tile, A = bias, B = 1 on lane half 0);
+//     the sigma and colour heads are VALU dot products over the registers the wave already holds.
 // One wave per SIMD (about 400 VGPRs).  Used when nothing has to be saved for backward, and for the point queries (k_field_fwd_reg's
 // SRC / RGB template arguments below) -- with GSAVE, the forward of a gradient query (nerf_hip_query_grad).
 #include "field_common.h"
@@ -63,6 +64,10 @@ typedef int lds_i32 __attribute__((address_space(3), may_alias));
 typedef int i32x4v __attribute__((ext_vector_type(4), may_alias));
 typedef __attribute__((address_space(3))) i32x4v lds_i32x4;
 constexpr int RELU_LDS_DWORDS = 2 * 4 * 64 * 4;
+// behind the slots (inference forms with colour): W_color as it lies in memory, [3][128] floats, then b_color[3] at dword 3 * HALF.  The colour
+// head runs behind the last MFMA with nothing to hide a global load behind; its operands are requested in the prologue, parked here, and
+// come back as ds_read_b128 (every lane of a half reads the same 16 bytes: a broadcast, no bank conflict).
+constexpr int COL_LDS_DWORDS = 3 * HALF + 4;
 struct ReluLds {
   lds_i32* w;     // this lane's 16 bytes of slot 0, group 0
   lds_i32* m[4];  // the dword of them that this lane's c-th ds_max takes
@@ -73,6 +78,10 @@ __device__ __forceinline__ ReluLds relu_lds(lds_i32* base, int lane) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) L.m[c] = base + 4 * lane + ((c + (lane >> 3)) & 3);
   return L;
+}
+__device__ __forceinline__ float4 lds_ld4(const lds_i32* p) {  // ds_read_b128
+  const i32x4v v = *reinterpret_cast<const lds_i32x4*>(p);
+  return make_float4(__int_as_float(v[0]), __int_as_float(v[1]), __int_as_float(v[2]), __int_as_float(v[3]));
 }
 // DS instruction i (0..23) of the round trip of accumulator tile src through slot `slot`; the reads (i = 6g + 5) land in dst[4g .. 4g+3]
 template <typename DST>
@@ -113,12 +122,35 @@ struct SaveIn {
 // each MFMA: tile t >= 1 behind the MFMAs of the second half of tile t - 1 (NFT = 8; from its second k-block on with NFT = 4), where the
 // VALU form stood.  Tile 0 has no such lead -- it is complete 7 MFMAs before the producing layer ends -- so the PRODUCER (NEXT_RELU) sends
 // group 0 of its accumulator tile 0 behind its last MFMAs and hands the registers over in `head`; the consumer sends groups 1..3
-// behind its bias MFMAs and its first k-block, each group well ahead of the k-block that reads it.
-template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, int SAVE = 0, bool LDS_RELU = false, bool NEXT_RELU = false>
+// behind the first 18 MFMAs of its first k-block (behind its bias MFMAs first, where it has them), each group well ahead of the
+// k-block that reads it.
+//
+// NEXT_BIAS (never with SAVE = 1): the bias of the layer BEHIND this one enters as the start value of that layer's accumulators -- 16-byte
+// loads that land in the accumulator registers, with no MFMA and no VALU, as the folded layer's dvec always did -- instead of one
+// MFMA per tile (A = bias, B = 1, C = 0: 64 MFMA issue slots per layer that computed nothing).  This layer requests them, ONE load behind
+// an MFMA: nb = that layer's bias + 4h (register 4g + r of tile t holds feature 32t + 8g + 4h + r), nacc = its accumulator tiles.  With
+// NEXT_BIAS = 1 those are THIS layer's input tiles (the two sets ping-pong), and tile t may be overwritten once its last reader has gone:
+// tile 0 in k-block 1, tile t >= 1 in k-block 4(t - 1) + 3, one k-block behind the ds_write / mask word that reads it last.  NEXT_BIAS = 2
+// (layer 0, whose input is gamma_p): the tiles are free, tile t goes in k-block t.  The consuming layer then runs with bv = nullptr and
+// ZERO_INIT = false.  (0 + b * 1 = b for every b but -0, which the MFMA form turned into +0; every such pre-activation goes through the
+// integer ReLU, which gives +0 for both, and the mask words read `> 0`.)
+__device__ __forceinline__ void bias_group(const float* b4h, int t, int g, f32x16& acc) {
+  const float4 q = *reinterpret_cast<const float4*>(b4h + 32 * t + 8 * g);
+  acc[4 * g + 0] = q.x;
+  acc[4 * g + 1] = q.y;
+  acc[4 * g + 2] = q.z;
+  acc[4 * g + 3] = q.w;
+}
+
+template <int KB, int NFT, int NKB, int NNFT, bool ZERO_INIT, bool RELU_IN, int SAVE = 0, bool LDS_RELU = false, bool NEXT_RELU = false, int NEXT_BIAS = 0>
 __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* float4 offsets into the packed image; < 0: none */, int lane,
                                           const f32x16* prev, f32x16* acc, WStage<8>& st0, const float* bv,
-                                          const SaveIn sv, const RegBuf& rb, const ReluLds& rl, f32x4v& head) {
-  static_assert(!(LDS_RELU || NEXT_RELU) || SAVE != 1, "the saving forward keeps the VALU ReLU");
+                                          const SaveIn sv, const RegBuf& rb, const ReluLds& rl, f32x4v& head,
+                                          const float* nb = nullptr, f32x16* nacc = nullptr) {
+  static_assert(!(LDS_RELU || NEXT_RELU || NEXT_BIAS) || SAVE != 1, "the saving forward keeps the VALU ReLU and the bias MFMAs");
+  static_assert(NEXT_BIAS == 0 || ((LDS_RELU && RELU_IN) || NEXT_RELU), "the bias loads live in the stream with compile-time k-blocks");
+  static_assert(NEXT_BIAS != 1 || (KB == 32 && RELU_IN), "NEXT_BIAS = 1 overwrites the 8 input tiles of a 256-wide ReLU layer");
+  static_assert(NEXT_BIAS != 2 || KB == 8, "NEXT_BIAS = 2: one tile per k-block of layer 0");
   constexpr int KT = KB / 4;
   constexpr bool LR = LDS_RELU && RELU_IN;
   WStage<8> st1;
@@ -206,6 +238,12 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
   auto ds0 = [&](int kt, int k4, int s, int f) { const int i = lr0 + (k4 * 4 + s) * NFT + f; return (LR && kt == 0 && i < 24) ? i : -1; };
   auto ds1 = [&](int kt, int k4, int s, int f) { const int i = (k4 * 4 + s) * NFT + f - (NFT == 8 ? 64 : 16); return (LR && kt + 1 < KT && i >= 0 && i < 24) ? i : -1; };
   auto ds2 = [&](int kt, int k4, int s, int f) { return (NEXT_RELU && kt == KT - 1 && k4 == 3 && s == 3 && f < 6) ? f : -1; };
+  // the tile of the next layer's accumulators whose bias group f is requested behind MFMA (s = 0, f < 4) of k-block kb; -1: none
+  auto nbt = [&](int kb, int s, int f) {
+    if (NEXT_BIAS == 0 || s != 0 || f >= 4) return -1;
+    if (NEXT_BIAS == 2) return kb;
+    return kb == 1 ? 0 : (((kb & 3) == 3 && (kb >> 2) + 1 < KT) ? (kb >> 2) + 1 : -1);
+  };
   static_for<0, KB>([&](auto kbc) __attribute__((always_inline)) {
     constexpr int kb = decltype(kbc)::value, kt = kb >> 2, k4 = kb & 3;
     WStage<8>& ld = (kb & 1) ? st0 : st1;
@@ -237,6 +275,11 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
         if constexpr (NEXT_RELU) {
           if (i2 >= 0) relu_lds_op(rl, acc[0], head, 0, 0, i2);
         }
+        if constexpr (NEXT_BIAS != 0) {
+          const int tb = nbt(kb, s, f);
+          if (tb >= 0) bias_group(nb, tb, f, nacc[tb]);
+          any |= tb >= 0;
+        }
         any |= i0 >= 0 || i1 >= 0 || i2 >= 0;
       }
     }
@@ -251,6 +294,7 @@ __device__ __forceinline__ void reg_layer(const int seg, const int next_seg /* f
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           if (n == 1) __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
           if (n == 2) __builtin_amdgcn_sched_group_barrier(0x080, 2, 0);
+          if (nbt(kb, s, f) >= 0) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         }
     }
   });
@@ -307,6 +351,17 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   // first fragments of layer 0 are requested before anything else
   WStage<8> st0;
   stage_load<8, 8>(wp + seg_off4(SEG_L0) + lane, 0, st0);
+  // the inference forms take the lazy ReLU through LDS (reg_layer) and keep the colour head's operands there; the saving forward allocates none
+  constexpr bool LR = !SAVE;
+  constexpr bool COL_LDS = LR && RGB;
+  [[maybe_unused]] float4 cw0, cw1;  // W_color: 96 float4, lane l brings l and (l < 32) 64 + l; b_color: lanes 0..2
+  [[maybe_unused]] float cb;
+  if constexpr (COL_LDS) {
+    const float4* wc4 = reinterpret_cast<const float4*>(a.w.p[W_COLOR]);
+    cw0 = wc4[lane];
+    cw1 = wc4[64 + j];
+    cb = a.w.p[B_COLOR][lane < 3 ? lane : 2];
+  }
 
   // ---- sample point and its encoding, straight into B-operand registers:
   // gp[t][4g + s] = gamma_p[k], k = 32t + 8g + 4h + s  (4 consecutive k = two (sin, cos) pairs)
@@ -328,23 +383,30 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
     a.pts_dbg[(size_t)m * 3 + 1] = p[1];
     a.pts_dbg[(size_t)m * 3 + 2] = p[2];
   }
+  // The pair index 4 g8 + 2 h + e depends on the lane half, so with the frequency table indexed by it every pair paid a dependent
+  // global load (s_getpc + global_load_dword + s_waitcnt vmcnt(0): 16 exposed round trips per tile, each also waiting for the layer-0
+  // fragments above) inside an exec-mask region of its own.  For fixed (g8, e) both candidates are compile-time values: frequency and
+  // coordinate are selected on h from literals / registers, the zero padding (pairs 30, 31 = lane half 1 of g8 = 7) is a select too.
+  // No memory, no branch: the encode is one block of VALU work in front of layer 0's first k-step, waiting for nothing but the sample point.
   f32x16 gp[2];
-#pragma unroll
-  for (int g8 = 0; g8 < 8; ++g8) {
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int pi = 4 * g8 + 2 * h + e;  // (sin, cos) pair index: k = 2 pi
-      float sv = 0.f, cv = 0.f;
-      if (pi < 30) {
-        const int c = pi / 10, l = pi - 10 * c;
-        const float x = (c == 0) ? p[0] : ((c == 1) ? p[1] : p[2]);
-        const float ph = x * __uint_as_float(kFreqPointBits[l]);
-        sincos_phase(ph, sv, cv);
-      }
-      gp[g8 >> 2][4 * (g8 & 3) + 2 * e] = sv;
-      gp[g8 >> 2][4 * (g8 & 3) + 2 * e + 1] = cv;
+  static_for<0, 16>([&](auto ic) __attribute__((always_inline)) {
+    constexpr int g8 = decltype(ic)::value >> 1, e = decltype(ic)::value & 1;
+    constexpr int pa = 4 * g8 + e, pb = pa + 2;  // (sin, cos) pair index on lane half 0 / 1: k = 2 pi
+    constexpr bool pad = pb >= 30;               // (lane half 1 computes half 0's pair and drops it)
+    constexpr int ca = pa / 10, la = pa - 10 * ca, cb = pad ? ca : pb / 10, lb = pad ? la : pb - 10 * cb;
+    static_assert(pa < 30, "lane half 0 never pads");
+    constexpr uint32_t fa = kFreqPointLit[la], fb = kFreqPointLit[lb];
+    const float x = (ca == cb) ? p[ca] : (h ? p[cb] : p[ca]);
+    const float f = (la == lb) ? __uint_as_float(fa) : (h ? __uint_as_float(fb) : __uint_as_float(fa));
+    float sv, cv;
+    sincos_phase(x * f, sv, cv);
+    if (pad) {
+      sv = h ? 0.f : sv;
+      cv = h ? 0.f : cv;
     }
-  }
+    gp[g8 >> 2][4 * (g8 & 3) + 2 * e] = sv;
+    gp[g8 >> 2][4 * (g8 & 3) + 2 * e + 1] = cv;
+  });
   if (DEBUG && a.gp_dbg && valid) {
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8)
@@ -369,12 +431,19 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   constexpr int SV = SAVE ? 1 : (GSAVE ? 2 : 0);
   auto sv_in = [&](int layer) { return GSAVE ? SaveIn{nullptr, mrow + (size_t)layer * MKS} : sv_relu(layer); };
 
-  // the inference forms take the lazy ReLU through LDS (reg_layer); the saving forward allocates none
-  constexpr bool LR = !SAVE;
   ReluLds rl{};
+  [[maybe_unused]] lds_i32* col = nullptr;
   if constexpr (LR) {
-    __shared__ int relu_slots[RELU_LDS_DWORDS];
+    __shared__ int relu_slots[RELU_LDS_DWORDS + (COL_LDS ? COL_LDS_DWORDS : 0)];
     rl = relu_lds((lds_i32*)relu_slots, lane);
+    if constexpr (COL_LDS) {  // (a one-wave workgroup: its DS instructions execute in order, the reads at the end need no barrier)
+      col = (lds_i32*)relu_slots + RELU_LDS_DWORDS;
+      const i32x4v v0 = {__float_as_int(cw0.x), __float_as_int(cw0.y), __float_as_int(cw0.z), __float_as_int(cw0.w)};
+      const i32x4v v1 = {__float_as_int(cw1.x), __float_as_int(cw1.y), __float_as_int(cw1.z), __float_as_int(cw1.w)};
+      *reinterpret_cast<lds_i32x4*>(col + 4 * lane) = v0;
+      *reinterpret_cast<lds_i32x4*>(col + 4 * (64 + j)) = v1;  // (both halves write the same 16 bytes)
+      col[3 * HALF + (lane < 3 ? lane : 2)] = __float_as_int(cb);
+    }
   }
   f32x4v head = {0.f, 0.f, 0.f, 0.f};  // group 0 of the next layer's input tile 0, activated (LR only)
   RSTAMP(0);  // prologue: ray / depth loads, sample point, positional encoding
@@ -384,32 +453,40 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   constexpr int sL1 = seg_off4(SEG_L1);
   constexpr int sL5 = seg_off4(SEG_L5);
   float bv[8];
+  // The inference forms start every layer's accumulators at its bias with loads (reg_layer's NEXT_BIAS: requested by the layer in front,
+  // layer 0's own right here); the saving forward keeps one bias MFMA per tile.  bl(i): the bias rows of weights24[i] for this lane half
+  constexpr bool BL = LR;
+  constexpr int NB1 = BL ? 1 : 0;
+  auto bl = [&](int i) { return BL ? a.w.p[i] + 4 * h : nullptr; };
+  auto bias_mfma = [&](int i) -> const float* {
+    if constexpr (BL) return nullptr;
+    bias_load<8>(a.w.p[i], lane, bv);
+    return bv;
+  };
+  if constexpr (BL) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) bias_group(bl(B_L0), t, g, A[t]);
+  }
 
   // ---- layer 0: gamma_p 60(64) -> 256
-  bias_load<8>(a.w.p[B_L0], lane, bv);
-  reg_layer<8, 8, 32, 8, true, false, SV, LR, LR>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bv, GSAVE ? SaveIn{gprow, nullptr} : sv_rows(S_GP), rb, rl, head);
-  RSTAMP(1);  // layer 0 (264 MFMAs)
+  reg_layer<8, 8, 32, 8, !BL, false, SV, LR, LR, BL ? 2 : 0>(seg_off4(SEG_L0), sL1, lane, gp, A, st0, bias_mfma(B_L0), GSAVE ? SaveIn{gprow, nullptr} : sv_rows(S_GP), rb, rl, head, bl(3), B);
+  RSTAMP(1);  // layer 0 (256 MFMAs; the saving forward: 264)
   // ---- layers 1..3 (the segment after L3 is L4A: same shape)
-  bias_load<8>(a.w.p[3], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1, sL1 + L256, lane, A, B, st0, bv, sv_in(0), rb, rl, head);
-  bias_load<8>(a.w.p[5], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bv, sv_in(1), rb, rl, head);
-  bias_load<8>(a.w.p[7], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bv, sv_in(2), rb, rl, head);
-  RSTAMP(2);  // layers 1..3 (3,096 MFMAs)
-  // ---- layer 4: cat(h3, gamma_p), hidden first (nerf.py:109)
-  bias_load<8>(a.w.p[9], lane, bv);
-  reg_layer<32, 8, 8, 8, true, true, SV, LR, false>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bv, sv_in(3), rb, rl, head);
+  reg_layer<32, 8, 32, 8, !BL, true, SV, LR, LR, NB1>(sL1, sL1 + L256, lane, A, B, st0, bias_mfma(3), sv_in(0), rb, rl, head, bl(5), A);
+  reg_layer<32, 8, 32, 8, !BL, true, SV, LR, LR, NB1>(sL1 + L256, sL1 + 2 * L256, lane, B, A, st0, bias_mfma(5), sv_in(1), rb, rl, head, bl(7), B);
+  reg_layer<32, 8, 32, 8, !BL, true, SV, LR, LR, NB1>(sL1 + 2 * L256, seg_off4(SEG_L4A), lane, A, B, st0, bias_mfma(7), sv_in(2), rb, rl, head, bl(9), A);
+  RSTAMP(2);  // layers 1..3 (3,072 MFMAs; the saving forward: 3,096)
+  // ---- layer 4: cat(h3, gamma_p), hidden first (nerf.py:109); its first part requests layer 5's bias
+  reg_layer<32, 8, 8, 8, !BL, true, SV, LR, false, NB1>(seg_off4(SEG_L4A), seg_off4(SEG_L4B), lane, B, A, st0, bias_mfma(9), sv_in(3), rb, rl, head, bl(11), B);
   reg_layer<8, 8, 32, 8, false, false, 0, LR, LR>(seg_off4(SEG_L4B), sL5, lane, gp, A, st0, nullptr, SaveIn{nullptr, nullptr}, rb, rl, head);
-  RSTAMP(3);  // layer 4 (1,288 MFMAs)
+  RSTAMP(3);  // layer 4 (1,280 MFMAs; the saving forward: 1,288)
   // ---- layers 5..7 (the segment after L7 is the folded point_info / dir_info layer: 4 tiles)
-  bias_load<8>(a.w.p[11], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL5, sL5 + L256, lane, A, B, st0, bv, sv_in(4), rb, rl, head);
-  bias_load<8>(a.w.p[13], lane, bv);
-  reg_layer<32, 8, 32, 8, true, true, SV, LR, LR>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bv, sv_in(5), rb, rl, head);
-  bias_load<8>(a.w.p[15], lane, bv);
-  reg_layer<32, 8, 32, 4, true, true, SV, LR, false>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bv, sv_in(6), rb, rl, head);
-  RSTAMP(4);  // layers 5..7 (3,096 MFMAs)
+  reg_layer<32, 8, 32, 8, !BL, true, SV, LR, LR, NB1>(sL5, sL5 + L256, lane, A, B, st0, bias_mfma(11), sv_in(4), rb, rl, head, bl(13), A);
+  reg_layer<32, 8, 32, 8, !BL, true, SV, LR, LR, NB1>(sL5 + L256, sL5 + 2 * L256, lane, B, A, st0, bias_mfma(13), sv_in(5), rb, rl, head, bl(15), B);
+  reg_layer<32, 8, 32, 4, !BL, true, SV, LR, false>(sL5 + 2 * L256, RGB ? seg_off4(SEG_FOLD) : -1, lane, A, B, st0, bias_mfma(15), sv_in(6), rb, rl, head);
+  RSTAMP(4);  // layers 5..7 (3,072 MFMAs; the saving forward: 3,096)
   // ---- sigma head on h7 = relu(B) (VALU): sigma = |w_sigma . h7 + b|  (nerf.py:94, 115)
   {
     const float* ws = a.w.p[W_SIGMA] + 4 * h;
@@ -478,9 +555,16 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        const float4 q0 = *reinterpret_cast<const float4*>(wc + 32 * t + 8 * g);
-        const float4 q1 = *reinterpret_cast<const float4*>(wc + HALF + 32 * t + 8 * g);
-        const float4 q2 = *reinterpret_cast<const float4*>(wc + 2 * HALF + 32 * t + 8 * g);
+        float4 q0, q1, q2;
+        if constexpr (COL_LDS) {
+          q0 = lds_ld4(col + 4 * h + 32 * t + 8 * g);
+          q1 = lds_ld4(col + 4 * h + HALF + 32 * t + 8 * g);
+          q2 = lds_ld4(col + 4 * h + 2 * HALF + 32 * t + 8 * g);
+        } else {
+          q0 = *reinterpret_cast<const float4*>(wc + 32 * t + 8 * g);
+          q1 = *reinterpret_cast<const float4*>(wc + HALF + 32 * t + 8 * g);
+          q2 = *reinterpret_cast<const float4*>(wc + 2 * HALF + 32 * t + 8 * g);
+        }
         const float c0 = relu1(A[t][4 * g + 0]), c1 = relu1(A[t][4 * g + 1]);
         const float c2 = relu1(A[t][4 * g + 2]), c3 = relu1(A[t][4 * g + 3]);
         if (SAVE) store_row4(srow + S_C * MS + 32 * t + 8 * g, make_float4(c0, c1, c2, c3));
@@ -492,8 +576,16 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
     z0 += __shfl_xor(z0, 32);
     z1 += __shfl_xor(z1, 32);
     z2 += __shfl_xor(z2, 32);
+    float bc[3];
+    if constexpr (COL_LDS) {  // every lane, one address: no load inside the branch
+      const float4 b = lds_ld4(col + 3 * HALF);
+      bc[0] = b.x, bc[1] = b.y, bc[2] = b.z;
+    }
     if (valid && h == 0) {
-      const float* bc = a.w.p[B_COLOR];
+      if constexpr (!COL_LDS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bc[c] = a.w.p[B_COLOR][c];
+      }
       a.rgb[(size_t)m * 3 + 0] = 1.0f / (1.0f + expf(-(z0 + bc[0])));
       a.rgb[(size_t)m * 3 + 1] = 1.0f / (1.0f + expf(-(z1 + bc[1])));
       a.rgb[(size_t)m * 3 + 2] = 1.0f / (1.0f + expf(-(z2 + bc[2])));

@@ -27,7 +27,9 @@ if tile:
     ideal = [0, 4608 * 64, 0, 0, 0, 0]
 else:
     names = ["prologue (loads, point, encode)", "layer 0", "layers 1-3", "layer 4", "layers 5-7", "sigma head", "point_info + dir_info (folded)", "colour head + stores"]
-    ideal = [0, 264 * 64, 3096 * 64, 1288 * 64, 3096 * 64, 0, 512 * 64, 0]
+    # 64 cycles per v_mfma_f32_32x32x2_f32.  The inference forward starts its accumulators at the bias with loads: 8,192 MFMAs
+    # per tile.  A library from before that change (one bias MFMA per accumulator tile) ran 264 / 3,096 / 1,288 / 3,096 in layers 0 / 1-3 / 4 / 5-7.
+    ideal = [0, 256 * 64, 3072 * 64, 1280 * 64, 3072 * 64, 0, 512 * 64, 0]
 n = v[7] if tile else v[31]; tot = sum(v[:len(names)])  # (the LDS-tile kernel keeps its count at word 7)
 if n == 0:
     raise SystemExit("no stamps recorded: run with NERF_HIP_LIB=nerf-tiny_amd/libnerf_hip_stamps.so (make -C nerf-tiny_amd/csrc stamps)")
