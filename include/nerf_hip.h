@@ -47,7 +47,8 @@ extern "C" {
                                   7: nerf_hip_query_ws_bytes, nerf_hip_query, nerf_hip_density_grid; later additions under 7:
                                      nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps;
                                      nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad; nerf_hip_metrics_ws_bytes,
-                                     nerf_hip_image_metrics; nerf_hip_forward_maps_train, nerf_hip_backward_maps */
+                                     nerf_hip_image_metrics; nerf_hip_forward_maps_train, nerf_hip_backward_maps;
+                                     nerf_hip_band_ws_bytes, nerf_hip_band_begin, nerf_hip_band_grow */
 
 enum {
   NERF_HIP_OK = 0,
@@ -380,6 +381,47 @@ int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level,
  * with V >= 2^31 cannot be indexed (the caller refuses it after the count).  lo3 / step3 are HOST arrays. */
 int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
                        size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Narrow-band density grid: the dense grid of nerf_hip_density_grid with the field evaluated only in a band
+ * of blocks around the level set; everywhere else the array holds a fill value of the right class.  For marching cubes at the same
+ * level: a surface crosses O(n^2) of the n^3 cells.  Lattice, point positions and the inside rule (sigma > level, NaN outside) are
+ * nerf_hip_density_grid's and the mesh calls'; every evaluated value is nerf_hip_density_grid's, bit for bit.
+ *   Blocks: per axis a, nb_a = ceil(n_a / block); block b owns the points [b * block, min((b + 1) * block, n_a)) and has its corner
+ *   planes at the point indices min(b * block, n_a - 1) and min((b + 1) * block, n_a - 1).  A cell or a block is MIXED when its 8
+ *   corners are not all of one class.
+ *   begin: (1) the field at the corner lattice, each point once, stored at its own position; (2) seeds S = the blocks whose 8 corner
+ *   samples are mixed, active set A = empty; (3) every lattice point takes the value of its block's lowest point; then the first list.
+ *   grow (one round): the field at every point owned by the listed blocks; S = the blocks of A with an in-grid 26-neighbour outside A
+ *   that own a corner point of a mixed cell of the array as it now stands; then the next list.
+ *   The list: new = (S grown by one block in the 26-neighbourhood, clipped to the grid) minus A, in ascending block order
+ *   (bx * nb_y + by) * nb_z + bz; A |= new; counts[0] = the list's length, counts[1] = the lattice points those blocks own.
+ * The caller reads counts after begin and after every grow (one 16-byte read; this is the only synchronisation), and calls grow with
+ * n_blocks = counts[0] until that is 0.  At that point every mixed cell of sigma has its 8 corners and their +-1 neighbours exact (this
+ * needs block >= 2), so marching cubes over it gives the dense grid's mesh restricted to the cells the band reached -- vertices, faces
+ * and normals bit for bit the dense mesh whenever every connected piece of the surface is mixed in some block's corner samples or is
+ * connected to a piece that is.
+ * WHAT IT CANNOT SEE: a piece of the surface that fits between the corner samples -- an island smaller than a block, a whole object
+ * inside one block -- is never found and is missing from the mesh, silently.  Lower `block` where that matters; the dense calls stay.
+ * Exact fp32 (the point queries' kernel in two more index forms).  Enqueue-only.  Refused before any device work: a dimension < 1,
+ * nx * ny * nz >= 2^31, block < 2, more than 2^25 blocks, a level that is not finite, a NULL sigma / lo3 / step3 / counts / weights, a
+ * workspace that is NULL, not 256-byte aligned or too small, counts not 8-byte aligned, n_blocks < 0 or above the number of blocks.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of the two calls below: nerf_hip_query_ws_bytes(0) plus 10 bytes per block and 16 per 256
+ * blocks.  Nothing per lattice point. */
+int nerf_hip_band_ws_bytes(int nx, int ny, int nz, int block, size_t* bytes);
+
+/* Packs the weights, then steps (1)-(3) and the first list.  sigma [nx][ny][nz] (device) is written everywhere; counts is DEVICE
+ * int64[2]; lo3 / step3 are HOST arrays as for nerf_hip_density_grid. */
+int nerf_hip_band_begin(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block,
+                        float level, float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+
+/* One round on the same arguments, workspace and weights as the begin before it (stream order; the packed image is reused): evaluates
+ * the n_blocks listed blocks -- n_blocks as read from counts[0]; the kernel also bounds itself by the device's count, so a wrong value
+ * leaves blocks unevaluated, never a write outside sigma -- then re-derives S and leaves the next list and its counts. */
+int nerf_hip_band_grow(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block,
+                       float level, int64_t n_blocks, float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

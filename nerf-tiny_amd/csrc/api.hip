@@ -1452,6 +1452,173 @@ int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* 
 
 namespace {
 
+// Workspace of the narrow-band grid: the point queries' packed weight image and fold, then per block of r^3 lattice points 10 bytes
+// (the sets A and S, the new-block offsets, the list) and per BAND_WG blocks 16 more.  Nothing per lattice point.
+struct BandLayout {
+  size_t packed, fold, active, seed, offs, list, tn, tp, bn, total;
+  int r, nb[3], nblk, nwg;
+};
+constexpr int BAND_MAX_BLOCKS = 1 << 25;  // (one wave per block in k_band_reseed: the launch stays below 2^32 threads)
+
+int band_layout(int nx, int ny, int nz, int block, BandLayout* L) {
+  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
+  if (block < 2) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least 2 points along every axis", block);
+  const int nmax = nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz);
+  L->r = block < nmax ? block : (nmax > 2 ? nmax : 2);  // (any block >= the grid is one block per axis)
+  const int n[3] = {nx, ny, nz};
+  long long nblk = 1;
+  for (int c = 0; c < 3; ++c) {
+    L->nb[c] = (n[c] + L->r - 1) / L->r;
+    nblk *= L->nb[c];
+  }
+  if (nblk > BAND_MAX_BLOCKS)
+    return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d in blocks of %d: %lld blocks, at most %d (raise block)", nx, ny, nz, block, nblk, BAND_MAX_BLOCKS);
+  L->nblk = (int)nblk;
+  L->nwg = (L->nblk + BAND_WG - 1) / BAND_WG;
+  const QueryLayout Q = query_layout(false);
+  size_t o = Q.total;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  L->packed = Q.packed;
+  L->fold = Q.fold;
+  L->active = take((size_t)L->nblk);
+  L->seed = take((size_t)L->nblk);
+  L->offs = take((size_t)L->nblk * 4);
+  L->list = take((size_t)L->nblk * 4);
+  L->tn = take((size_t)L->nwg * 4);
+  L->tp = take((size_t)L->nwg * 8);
+  L->bn = take((size_t)L->nwg * 4);
+  L->total = o;
+  return NERF_HIP_OK;
+}
+
+// the checks of both band calls, in the mesh calls' order: grid, block, level, pointers, workspace, counts
+int check_band_call(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
+                    const float* sigma, const void* ws, size_t ws_bytes, const int64_t* counts, BandLayout* L) {
+  if (int rc = band_layout(nx, ny, nz, block, L)) return rc;
+  if (!isfinite(level)) return fail(NERF_HIP_ERR_ARG, "level %g is not finite", (double)level);
+  if (!sigma) return fail(NERF_HIP_ERR_ARG, "sigma is null");
+  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
+  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
+  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
+  return check_weights(weights24);
+}
+
+BandArgs band_args(float* sigma, int nx, int ny, int nz, float level, void* ws, const BandLayout& L, int64_t* counts) {
+  BandArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.r = L.r;
+  a.nbx = L.nb[0];
+  a.nby = L.nb[1];
+  a.nbz = L.nb[2];
+  a.nblk = L.nblk;
+  a.nwg = L.nwg;
+  a.level = level;
+  a.active = at<unsigned char>(ws, L.active);
+  a.seed = at<unsigned char>(ws, L.seed);
+  a.offs = at<unsigned>(ws, L.offs);
+  a.list = at<int>(ws, L.list);
+  a.tn = at<int>(ws, L.tn);
+  a.tp = at<long long>(ws, L.tp);
+  a.bn = at<int>(ws, L.bn);
+  a.counts = reinterpret_cast<long long*>(counts);
+  return a;
+}
+
+void band_field_args(const Weights24& w, const float* lo3, const float* step3, int nx, int ny, int nz, float* sigma, void* ws,
+                     const BandLayout& L, FieldArgs* fa, QuerySrc* q) {
+  memset(fa, 0, sizeof(*fa));
+  fa->wp = at<float4>(ws, L.packed);
+  fa->w = w;
+  fa->sigma = sigma;
+  memset(q, 0, sizeof(*q));
+  for (int c = 0; c < 3; ++c) {
+    q->lo[c] = lo3[c];
+    q->step[c] = step3[c];
+  }
+  q->nx = nx;
+  q->ny = ny;
+  q->nz = nz;
+  q->r = L.r;
+  q->nby = L.nb[1];
+  q->nbz = L.nb[2];
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_band_ws_bytes(int nx, int ny, int nz, int block, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  BandLayout L;
+  if (int rc = band_layout(nx, ny, nz, block, &L)) return rc;
+  *bytes = L.total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_band_begin(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
+                        float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+  BandLayout L;
+  if (int rc = check_band_call(weights24, lo3, step3, nx, ny, nz, block, level, sigma, ws, ws_bytes, counts, &L)) return rc;
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Weights24 w = as_w24(weights24);
+  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
+  FieldArgs fa;
+  QuerySrc q;
+  band_field_args(w, lo3, step3, nx, ny, nz, sigma, ws, L, &fa, &q);
+  const int n[3] = {nx, ny, nz};
+  for (int c = 0; c < 3; ++c) q.ext[c] = (n[c] - 1 + L.r - 1) / L.r + 1;  // the unique planes min(u r, n - 1)
+  fa.M = q.ext[0] * q.ext[1] * q.ext[2];  // (<= nx ny nz)
+  HIP_TRY(launch_band_corners(fa, q, st));
+  const BandArgs a = band_args(sigma, nx, ny, nz, level, ws, L, counts);
+  HIP_TRY(launch_band_begin(a, st));
+  HIP_TRY(launch_band_next(a, st));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_band_grow(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
+                       int64_t n_blocks, float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+  BandLayout L;
+  if (int rc = check_band_call(weights24, lo3, step3, nx, ny, nz, block, level, sigma, ws, ws_bytes, counts, &L)) return rc;
+  if (n_blocks < 0 || n_blocks > L.nblk) return fail(NERF_HIP_ERR_ARG, "n_blocks=%lld: the grid has %d blocks", (long long)n_blocks, L.nblk);
+  if (int rc = check_device()) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const BandArgs a = band_args(sigma, nx, ny, nz, level, ws, L, counts);
+  FieldArgs fa;
+  QuerySrc q;
+  band_field_args(as_w24(weights24), lo3, step3, nx, ny, nz, sigma, ws, L, &fa, &q);
+  const int n[3] = {nx, ny, nz};
+  long long vol = 1;
+  for (int c = 0; c < 3; ++c) {
+    q.ext[c] = n[c] < L.r ? n[c] : L.r;
+    vol *= q.ext[c];  // (<= nx ny nz)
+  }
+  q.list = a.list;
+  q.nlist = a.counts;
+  // the listed blocks, in launches of fewer than 2^31 samples (the counts are read by these launches and rewritten only after them)
+  const long long per = ((1ll << 31) - 64) / vol;
+  for (long long e0 = 0; e0 < n_blocks; e0 += per) {
+    const long long ne = n_blocks - e0 < per ? n_blocks - e0 : per;
+    q.e0 = (int)e0;
+    fa.M = (int)(ne * vol);
+    HIP_TRY(launch_band_blocks(fa, q, st));
+  }
+  HIP_TRY(launch_band_reseed(a, st));
+  HIP_TRY(launch_band_next(a, st));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
 int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
   if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);

@@ -330,7 +330,11 @@ __device__ __forceinline__ void bias_load(const float* __restrict__ bias, int la
 // register allocation of the forward instantiations, and these must stay instruction for instruction what they were.
 // GSAVE (gradient queries, SRC_POINTS only; nerf_hip_query_grad): the compact save that k_field_bwd_reg's query form reads -- the ReLU
 // masks of h0..h7, spre, gamma_p rows and (RGB) the c rows, laid out as kernels.h QGRAD_* describes; no activation rows.
-enum { SRC_RAYS = 0, SRC_POINTS = 1, SRC_LATTICE = 2 };
+// SRC_CORNERS / SRC_BLOCKS (sigma only; the narrow-band grid, nerf_hip_band_begin / nerf_hip_band_grow): sample m maps by integer
+// arithmetic to a lattice index (kernels.h QuerySrc) -- the strided, clamped corner lattice, or a listed block's local point -- and from
+// there to p exactly as SRC_LATTICE does; sigma goes to the dense grid at the point's own linear index, so the bits are density_grid's.
+// Points of a ragged last block past the grid are computed on the clamped index and not stored.
+enum { SRC_RAYS = 0, SRC_POINTS = 1, SRC_LATTICE = 2, SRC_CORNERS = 3, SRC_BLOCKS = 4 };
 
 template <bool SAVE, bool DEBUG, int SRC = SRC_RAYS, bool RGB = true, bool GSAVE = false>
 __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, const QuerySrc q) {
@@ -366,17 +370,47 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
   // ---- sample point and its encoding, straight into B-operand registers:
   // gp[t][4g + s] = gamma_p[k], k = 32t + 8g + 4h + s  (4 consecutive k = two (sin, cos) pairs)
   float p[3];
+  [[maybe_unused]] bool band_keep = false;  // SRC_CORNERS / SRC_BLOCKS: this lane's point is stored, at band_at of the dense grid
+  [[maybe_unused]] size_t band_at = 0;
   if constexpr (SRC == SRC_RAYS) {
     sample_point(rf, a.t[mc], p);
   } else if constexpr (SRC == SRC_POINTS) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) p[c] = q.points[(size_t)mc * 3 + c];
-  } else {  // C order, z fastest; product and sum rounded separately (-ffp-contract=off): p is lo + (float)i * step bit for bit
+  } else if constexpr (SRC == SRC_LATTICE) {  // C order, z fastest; product and sum rounded separately (-ffp-contract=off): p is lo + (float)i * step bit for bit
     const int iz = mc % q.nz, ixy = mc / q.nz;
     const int iy = ixy % q.ny, ix = ixy / q.ny;
     p[0] = q.lo[0] + (float)ix * q.step[0];
     p[1] = q.lo[1] + (float)iy * q.step[1];
     p[2] = q.lo[2] + (float)iz * q.step[2];
+  } else {
+    static_assert(!RGB && !SAVE && !GSAVE && !DEBUG, "the band forms are sigma-only inference");
+    const unsigned n[3] = {(unsigned)q.nx, (unsigned)q.ny, (unsigned)q.nz};
+    unsigned idx[3];
+    band_keep = valid;
+    if constexpr (SRC == SRC_CORNERS) {
+      const unsigned uz = (unsigned)mc % (unsigned)q.ext[2], uxy = (unsigned)mc / (unsigned)q.ext[2];
+      idx[0] = uxy / (unsigned)q.ext[1] * (unsigned)q.r;
+      idx[1] = uxy % (unsigned)q.ext[1] * (unsigned)q.r;
+      idx[2] = uz * (unsigned)q.r;
+    } else {
+      const unsigned vol = (unsigned)(q.ext[0] * q.ext[1] * q.ext[2]);
+      const unsigned e = (unsigned)mc / vol, l = (unsigned)mc - e * vol;
+      band_keep = band_keep && (long long)q.e0 + e < *q.nlist;
+      const unsigned b = band_keep ? (unsigned)q.list[(size_t)q.e0 + e] : 0u;
+      const unsigned lz = l % (unsigned)q.ext[2], lxy = l / (unsigned)q.ext[2];
+      const unsigned bz = b % (unsigned)q.nbz, bxy = b / (unsigned)q.nbz;
+      idx[0] = bxy / (unsigned)q.nby * (unsigned)q.r + lxy / (unsigned)q.ext[1];
+      idx[1] = bxy % (unsigned)q.nby * (unsigned)q.r + lxy % (unsigned)q.ext[1];
+      idx[2] = bz * (unsigned)q.r + lz;
+      band_keep = band_keep && idx[0] < n[0] && idx[1] < n[1] && idx[2] < n[2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) idx[c] = idx[c] < n[c] ? idx[c] : n[c] - 1u;
+    band_at = ((size_t)idx[0] * n[1] + idx[1]) * n[2] + idx[2];
+    p[0] = q.lo[0] + (float)(int)idx[0] * q.step[0];
+    p[1] = q.lo[1] + (float)(int)idx[1] * q.step[1];
+    p[2] = q.lo[2] + (float)(int)idx[2] * q.step[2];
   }
   if (DEBUG && a.pts_dbg && valid && h == 0) {
     a.pts_dbg[(size_t)m * 3 + 0] = p[0];
@@ -520,7 +554,9 @@ __global__ __launch_bounds__(64, 1) void k_field_fwd_reg(const FieldArgs a, cons
       if (SAVE) __builtin_amdgcn_sched_barrier(0);
     }
     s += __shfl_xor(s, 32);
-    if (valid && h == 0) {
+    if constexpr (SRC == SRC_CORNERS || SRC == SRC_BLOCKS) {
+      if (band_keep && h == 0) a.sigma[band_at] = fabsf(s + a.w.p[B_SIGMA][0]);
+    } else if (valid && h == 0) {
       const float pre = s + a.w.p[B_SIGMA][0];
       a.sigma[m] = fabsf(pre);
       if (SAVE || GSAVE) a.spre[a.row0 + m] = pre;
@@ -630,6 +666,18 @@ hipError_t launch_query_reg(const FieldArgs& a, const QuerySrc& q, bool rgb, hip
     hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, true>), dim3(tiles), dim3(64), 0, st, a, q);
   else
     hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_POINTS, false>), dim3(tiles), dim3(64), 0, st, a, q);
+  return hipGetLastError();
+}
+
+hipError_t launch_band_corners(const FieldArgs& a, const QuerySrc& q, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_CORNERS, false>), dim3((unsigned)(((long long)a.M + RM - 1) / RM)), dim3(64), 0, st, a, q);
+  return hipGetLastError();
+}
+
+hipError_t launch_band_blocks(const FieldArgs& a, const QuerySrc& q, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  hipLaunchKernelGGL((k_field_fwd_reg<false, false, SRC_BLOCKS, false>), dim3((unsigned)(((long long)a.M + RM - 1) / RM)), dim3(64), 0, st, a, q);
   return hipGetLastError();
 }
 

@@ -61,6 +61,15 @@ struct QuerySrc {
   const float* points;     // [M][3] world points, or null: the lattice below
   float lo[3], step[3];    // lattice point (i, j, k) = lo + (i, j, k) * step, each coordinate one product and one sum
   int ny, nz;              // lattice: m = (i * ny + j) * nz + k (C order, z fastest)
+  // ---- narrow-band forms (SRC_CORNERS / SRC_BLOCKS, nerf_hip_band_*): the samples are points of the nx x ny x nz lattice above, cut into
+  // blocks of r^3 points, and sigma is stored at the point's own lattice index (a.sigma is the dense grid)
+  const int* list;         // SRC_BLOCKS: ascending block ids, block = (bx * nby + by) * nbz + bz; this launch starts at entry e0
+  const long long* nlist;  // SRC_BLOCKS: the list's length (device); entries past it are computed on block 0 and not stored
+  int e0;
+  int nx, r;
+  int ext[3];              // SRC_CORNERS: corner planes per axis, plane u at min(u * r, n - 1), sample m = (ux * ext[1] + uy) * ext[2] + uz
+                           // SRC_BLOCKS: points per block and axis = min(r, n), sample m = (entry * ext[0] * ext[1] * ext[2]) + local index
+  int nby, nbz;            // SRC_BLOCKS: blocks along y and z
 };
 // Colour queries run in chunks of this many points: the dvec rows of one chunk live in the workspace (independent of M), and a chunk is
 // 8 waves for every SIMD of the chip (256 CUs x 4 SIMDs x 32 points x 8) at the kernel's one wave per SIMD.
@@ -413,6 +422,31 @@ struct MeshArgs {
 inline int mesh_blocks(long long n_points) { return (int)((n_points + MESH_PTS - 1) / MESH_PTS); }
 hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st);  // count + in-block vertex scan, then the scan of the block totals
 hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st);
+
+// ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
+constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
+
+struct BandArgs {
+  float* sigma;            // [nx][ny][nz], z fastest: the dense grid
+  int nx, ny, nz;
+  int r;                   // block size, 2 <= r <= max(nx, ny, nz)
+  int nbx, nby, nbz, nblk; // blocks per axis = ceil(n / r), and their product
+  int nwg;                 // ceil(nblk / BAND_WG)
+  float level;
+  unsigned char *active, *seed;  // [nblk] the sets A and S
+  unsigned* offs;          // [nblk] (exclusive offset among the workgroup's new blocks << 1) | new
+  int* list;               // [nblk] the new blocks, ascending
+  int* tn;                 // [nwg] new blocks per workgroup
+  long long* tp;           // [nwg] lattice points they own
+  int* bn;                 // [nwg] exclusive scan of tn
+  long long* counts;       // [2] = new blocks, the points they own
+};
+
+hipError_t launch_band_corners(const FieldArgs& a, const QuerySrc& q, hipStream_t st);  // a.M = ext[0] * ext[1] * ext[2]
+hipError_t launch_band_blocks(const FieldArgs& a, const QuerySrc& q, hipStream_t st);   // a.M = entries * ext[0] * ext[1] * ext[2]
+hipError_t launch_band_begin(const BandArgs& a, hipStream_t st);   // seeds from the corner samples (A = empty), then the fill
+hipError_t launch_band_reseed(const BandArgs& a, hipStream_t st);  // S from A and the grid as it stands
+hipError_t launch_band_next(const BandArgs& a, hipStream_t st);    // new = dilate(S) - A -> list, counts; A |= new
 
 // ---- image metrics (metrics.hip): per-view MSE and SSIM of pred vs gt [n][H][W][3] fp32, fp64 arithmetic
 constexpr int MT_WIN = 11;                   // SSIM's Gaussian window (taps); valid filtering drops MT_WIN - 1 rows / columns

@@ -48,6 +48,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-normals", choices=["grid", "field"], default="grid",
                     help="vertex normals of --mesh: grid = central differences of the lattice (default), field = the field's analytic "
                          "gradient at each vertex (not limited by the grid spacing)")
+    ap.add_argument("--mesh-band", type=int, default=None, metavar="R",
+                    help="--mesh evaluates the field only in a band of R^3-point blocks around the surface (R >= 2; narrow-band grid: the "
+                         "same mesh wherever the band finds the surface, a component smaller than a block can be missed; default: dense)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--maps", action="store_true",
@@ -99,4 +102,5 @@ if __name__ == "__main__":
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:
-        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals)
+        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
+                         band=args.mesh_band)

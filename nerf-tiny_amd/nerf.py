@@ -587,7 +587,33 @@ class NeRFModel(nn.Module):
         return ops.density_grid(ps, lo32.tolist(), step.tolist(), shape, ws=self._query_workspace(False, dev))
 
     @torch.no_grad()
-    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid"):
+    def density_band(self, lo, hi, res, level, block=8):
+        """density_grid(lo, hi, res) with the field evaluated only near the level set sigma == level: a coarse pass samples the corners
+        of blocks of ``block``^3 lattice points (block >= 2), and the exact field is evaluated in a band of blocks around the corners'
+        class changes that grows until the surface no longer leaves it.  Returns (sigma [nx, ny, nz], info).  Every evaluated value is
+        density_grid's, bit for bit; every other point holds its block's lowest corner value, which has the right class.  Marching
+        cubes at ``level`` over this array therefore gives the dense mesh restricted to the cells the band reached -- the dense mesh
+        itself, bit for bit, when every connected piece of the surface shows in some block's corner samples or hangs together with
+        one that does.  WHAT IT CANNOT SEE: a piece that fits between the corner samples (an island smaller than a block, a whole
+        object inside one block) is missing, silently: lower ``block`` where that matters, or use density_grid.  info: ``rounds`` (grow
+        iterations), ``blocks_active``, ``blocks_total``, ``points_evaluated`` (the unique corner points plus the points of every block
+        as it becomes active, so corner points inside active blocks count twice) and ``points_total``.  Exact fp32 whatever
+        ``bf16_mlp`` / ``split_mlp`` say; the array is for this level only."""
+        import numpy as np
+
+        from . import ops
+
+        ps = self._device_params()
+        dev = ps[0].device
+        shape = grid_shape(res)
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        step = grid_step(lo32, hi32, shape)
+        ws = torch.empty(_abi.band_ws_bytes(*shape, int(block)), dtype=torch.uint8, device=dev)
+        return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
+
+    @torch.no_grad()
+    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -595,7 +621,10 @@ class NeRFModel(nn.Module):
         a mesh workspace of 4 bytes per point more.
         normals="grid": the marching-cubes normals (central differences of the grid, interpolated to the vertex).  normals="field": -g / |g|
         of the field's analytic gradient g at each vertex (query_grad; (0, 0, 0) where |g| is 0 or not finite) -- not limited by the grid
-        spacing; the colours are then seen along these normals."""
+        spacing; the colours are then seen along these normals.
+        band=None: the dense grid.  band=r (an int >= 2): density_band(lo, hi, res, level, block=r) in its place -- the field is evaluated
+        only in blocks of r^3 points around the surface, and the mesh is the dense one wherever the band found the surface; a component
+        smaller than a block can be missed (density_band says when).  Everything after the grid is the same."""
         import numpy as np
 
         from . import mesh
@@ -605,7 +634,7 @@ class NeRFModel(nn.Module):
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
-        sigma = self.density_grid(lo32, hi32, shape)
+        sigma = self.density_grid(lo32, hi32, shape) if band is None else self.density_band(lo32, hi32, shape, level, block=band)[0]
         verts, faces, nrm = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
         del sigma
         if normals == "field":

@@ -121,6 +121,42 @@ def density_grid(params, lo, step, shape, ws=None):
     return sigma
 
 
+def density_band(params, lo, step, shape, level, block=8, ws=None, sigma=None, counts=None):
+    """density_grid() with the field evaluated only in a band of ``block``^3-point blocks around the level set sigma == level
+    (nerf_hip_band_begin, then nerf_hip_band_grow until the surface no longer leaves the band; include/nerf_hip.h states the rounds and
+    what the band cannot see).  -> (sigma[nx, ny, nz], info): every evaluated value is density_grid's bits, the rest a fill value of
+    the right class; info = dict(rounds, blocks_active, blocks_total, points_evaluated, points_total).  One 16-byte read of the device
+    counts after the begin and after every round (each synchronises with the stream).  ws: a uint8 device buffer of
+    >= _abi.band_ws_bytes(nx, ny, nz, block) bytes; sigma / counts: caller-owned outputs (fp32 [nx, ny, nz] contiguous / int64 [2]);
+    each is allocated here if None."""
+    nx, ny, nz = (int(n) for n in shape)
+    block = int(block)
+    dev = params[0].device
+    L = _abi.lib()
+    if ws is None:
+        ws = torch.empty(_abi.band_ws_bytes(nx, ny, nz, block), dtype=torch.uint8, device=dev)
+    if sigma is None:
+        sigma = torch.empty(max(nx, 0), max(ny, 0), max(nz, 0), device=dev)
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+    st = _stream(sigma)
+    head = (_abi.ptr_array(params), _abi.f32_array(lo), _abi.f32_array(step), nx, ny, nz, block, float(level))
+    tail = (sigma.data_ptr(), ws.data_ptr(), ws.numel(), counts.data_ptr(), st)
+    _abi.check(L.nerf_hip_band_begin(*head, *tail))
+    r = min(block, max(nx, ny, nz, 2))
+    corner_planes = lambda n: (n - 1 + r - 1) // r + 1
+    info = dict(rounds=0, blocks_active=0, blocks_total=-(-nx // r) * -(-ny // r) * -(-nz // r),
+                points_evaluated=corner_planes(nx) * corner_planes(ny) * corner_planes(nz), points_total=nx * ny * nz)
+    while True:
+        n_new, n_pts = (int(n) for n in counts.cpu())
+        if n_new == 0:
+            return sigma, info
+        _abi.check(L.nerf_hip_band_grow(*head, n_new, *tail))
+        info["rounds"] += 1
+        info["blocks_active"] += n_new
+        info["points_evaluated"] += n_pts
+
+
 def marching_cubes(sigma, lo, step, level, ws=None):
     """Isosurface sigma == level of a device grid sigma[nx, ny, nz] (nerf_hip_mesh_count + nerf_hip_mesh_emit): lo / step three host
     floats (lattice point (i, j, k) at lo + (i, j, k) * step) -> (verts[V, 3] fp32, faces[F, 3] int32, normals[V, 3] fp32) on sigma's
