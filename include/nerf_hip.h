@@ -48,14 +48,17 @@ extern "C" {
                                      nerf_hip_mesh_ws_bytes, nerf_hip_mesh_count, nerf_hip_mesh_emit; nerf_hip_forward_maps;
                                      nerf_hip_query_grad_ws_bytes, nerf_hip_query_grad; nerf_hip_metrics_ws_bytes,
                                      nerf_hip_image_metrics; nerf_hip_forward_maps_train, nerf_hip_backward_maps;
-                                     nerf_hip_band_ws_bytes, nerf_hip_band_begin, nerf_hip_band_grow */
+                                     nerf_hip_band_ws_bytes, nerf_hip_band_begin, nerf_hip_band_grow; nerf_hip_mesh_cc_ws_bytes,
+                                     nerf_hip_mesh_cc_round, nerf_hip_mesh_cc_ids, nerf_hip_mesh_cc_stats, nerf_hip_mesh_cc_compact
+                                     (with NERF_HIP_ERR_CONVERGE) */
 
 enum {
   NERF_HIP_OK = 0,
   NERF_HIP_ERR_ARG = -1,       /* bad shape / null pointer / unsupported size        */
   NERF_HIP_ERR_WORKSPACE = -2, /* workspace too small for (B, Nc, Nf, flags)          */
   NERF_HIP_ERR_DEVICE = -3,    /* a HIP runtime call failed (text in last_error)      */
-  NERF_HIP_ERR_ARCH = -4       /* device is not gfx950                                */
+  NERF_HIP_ERR_ARCH = -4,      /* device is not gfx950                                */
+  NERF_HIP_ERR_CONVERGE = -5   /* nerf_hip_mesh_cc_round: no fixed point within its cap of rounds */
 };
 
 /* flags */
@@ -422,6 +425,61 @@ int nerf_hip_band_begin(const float* const* weights24, const float* lo3, const f
  * leaves blocks unevaluated, never a write outside sigma -- then re-derives S and leaves the next list and its counts. */
 int nerf_hip_band_grow(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block,
                        float level, int64_t n_blocks, float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Connected components of an indexed triangle mesh: labels, per-component counts and boxes, and the
+ * compaction that drops components -- the floaters of a density field's isosurface.  Any indexed mesh, not only marching cubes':
+ * faces[F][3] int32 over V vertices, V, F < 2^31.
+ * - Two vertices are connected when some face contains both (two triangles that share one vertex are one component); a vertex in no
+ *   face is a component of its own with 0 faces.
+ * - A face with an index outside [0, V) takes no part: it connects nothing, its face_comp is -1, no count includes it, the compaction
+ *   drops it, and its indices are never used as addresses.
+ * - Component ids are 0 .. C-1 in ascending order of the component's smallest vertex index.  vert_comp[V] is each vertex's id,
+ *   face_comp[F] the id of the face's first vertex.
+ * - n_verts[C], n_faces[C] (int32): the component's vertices and (participating) faces.  bbox_lo[C][3], bbox_hi[C][3] (fp32): per
+ *   coordinate the minimum and maximum over the component's vertices; a coordinate that is not finite is ignored, -0 counts as +0, and
+ *   a component without a finite value along a coordinate has (+inf, -inf) there.
+ * Every output is a function of the input alone: integer atomics only (min, max, add -- the boxes go through the floats'
+ * order-preserving unsigned images), nothing is placed by an atomic, identical bits from run to run.
+ *
+ * Labelling: min-label hooking in rounds that the HOST drives, as it drives nerf_hip_band_grow.  L[v] = v; a round is (hook) per
+ * face, the labels r_k = L[v_k] of its vertices, m = min r_k, atomicMin(&L[r_k], m) for every r_k != m, and a device word `changed`
+ * set when any of these lowered a label; then (compress) per vertex, L[v] = the root of v.  The caller reads `changed` (4 bytes: the
+ * only synchronisation) after each round and stops at the first round that left it 0: then L is the smallest vertex index of each
+ * component.  round = 0, 1, 2, ... in order; round >= 64 is refused with NERF_HIP_ERR_CONVERGE and enqueues nothing (a strip of 65,536
+ * vertices in random order needs 11), so a caller's loop always ends, and a labelling that did not converge has no result.
+ * Then nerf_hip_mesh_cc_ids (ids by a scan over the roots), nerf_hip_mesh_cc_stats, and nerf_hip_mesh_cc_compact as often as wanted.
+ * All calls are enqueue-only on the caller's stream and check every argument on the host before anything is enqueued: V or F outside
+ * [0, 2^31), a NULL array that the sizes need, a workspace that is NULL, not 256-byte aligned or too small, count(s) not 8-byte
+ * aligned.  Indices read from device arrays (faces, vert_comp, face_comp) are range-checked by the kernels before use and every store is
+ * clamped to the caller's capacities: wrong arguments give wrong output, never an access outside the buffers.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of the calls below: 4 bytes per vertex, and 8 per 2048 vertices or faces, whichever are more. */
+int nerf_hip_mesh_cc_ws_bytes(int64_t V, int64_t F, size_t* bytes);
+
+/* One labelling round (round 0 also initialises the labels in ws).  changed: DEVICE int32[1], cleared and then set by this round. */
+int nerf_hip_mesh_cc_round(const int32_t* faces, int64_t V, int64_t F, int round, void* ws, size_t ws_bytes, int32_t* changed,
+                           void* stream);
+
+/* After the round that changed nothing, on the same workspace: vert_comp[V], face_comp[F] (int32) and count[0] = C (DEVICE int64[1]). */
+int nerf_hip_mesh_cc_ids(const int32_t* faces, int64_t V, int64_t F, void* ws, size_t ws_bytes, int32_t* vert_comp, int32_t* face_comp,
+                         int64_t* count, void* stream);
+
+/* n_verts[max_c], n_faces[max_c] and, with bbox_lo / bbox_hi (both or neither; they need verts[V][3]), the boxes [max_c][3].  max_c is
+ * the caller's capacity in components (C, read from count): ids outside [0, max_c) are left out, rows from C on are empty (0, 0, +inf,
+ * -inf).  Needs no workspace. */
+int nerf_hip_mesh_cc_stats(const float* verts, const int32_t* vert_comp, const int32_t* face_comp, int64_t V, int64_t F, int32_t* n_verts,
+                           int32_t* n_faces, float* bbox_lo, float* bbox_hi, int64_t max_c, void* stream);
+
+/* Drops the components c with keep[c] == 0 (keep: DEVICE uint8[C]).  Kept vertices go to out_verts (and normals / rgb [V][3], each may be
+ * NULL with its output, to out_normals / out_rgb) at their rank among the kept vertices; kept faces (those that take part and whose
+ * component is kept) go to out_faces with their indices renumbered; both keep their order.  counts (DEVICE int64[2]) = V', F'.  max_v /
+ * max_f are the outputs' capacities in rows: every store is clamped to them.  The workspace's labels are overwritten. */
+int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
+                             const int32_t* vert_comp, const int32_t* face_comp, const uint8_t* keep, int64_t C, void* ws,
+                             size_t ws_bytes, float* out_verts, float* out_normals, float* out_rgb, int32_t* out_faces, int64_t max_v,
+                             int64_t max_f, int64_t* counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -63,6 +63,12 @@ _PROTOS = {
     "nerf_hip_band_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_band_begin": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, C.c_size_t, _p, _p]),
     "nerf_hip_band_grow": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64, _p, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_mesh_cc_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_cc_round": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_mesh_cc_ids": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p]),
+    "nerf_hip_mesh_cc_stats": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_int64, _p]),
+    "nerf_hip_mesh_cc_compact": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p,
+                                           C.c_int64, C.c_int64, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -127,6 +133,13 @@ def band_ws_bytes(nx: int, ny: int, nz: int, block: int) -> int:
     """Workspace bytes of nerf_hip_band_begin / nerf_hip_band_grow over an nx x ny x nz grid in blocks of ``block`` points."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_band_ws_bytes(int(nx), int(ny), int(nz), int(block), C.byref(n)))
+    return int(n.value)
+
+
+def mesh_cc_ws_bytes(V: int, F: int) -> int:
+    """Workspace bytes of the nerf_hip_mesh_cc_* calls on a mesh of V vertices and F faces."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_cc_ws_bytes(int(V), int(F), C.byref(n)))
     return int(n.value)
 
 

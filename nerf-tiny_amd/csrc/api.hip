@@ -1619,6 +1619,168 @@ int nerf_hip_band_grow(const float* const* weights24, const float* lo3, const fl
 
 namespace {
 
+// Workspace of the component calls: 4 bytes per vertex (the labels L; the compaction keeps its new vertex indices there) and 8 bytes
+// per CC_PTS vertices or faces, whichever are more (a workgroup's total and its exclusive scan).
+struct CcLayout {
+  size_t L, tot, base, total;
+};
+CcLayout cc_layout(long long V, long long F) {
+  CcLayout L;
+  const int nb = cc_blocks(V > F ? V : F);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  L.L = take((size_t)V * 4);
+  L.tot = take((size_t)nb * 4);
+  L.base = take((size_t)nb * 4);
+  L.total = o;
+  return L;
+}
+
+int check_cc_sizes(int64_t V, int64_t F) {
+  if (V < 0 || F < 0) return fail(NERF_HIP_ERR_ARG, "V=%lld F=%lld: counts must be >= 0", (long long)V, (long long)F);
+  // vertex indices are int32, and the kernels index faces with 32-bit integers as well
+  if (V >= (1ll << 31) || F >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "V=%lld F=%lld: a mesh must stay below 2^31 vertices and faces", (long long)V, (long long)F);
+  return NERF_HIP_OK;
+}
+
+int check_cc_ws(int64_t V, int64_t F, const void* ws, size_t ws_bytes, CcLayout* L) {
+  if (int rc = check_cc_sizes(V, F)) return rc;
+  *L = cc_layout(V, F);
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
+  return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_cc_ws_bytes(int64_t V, int64_t F, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_cc_sizes(V, F)) return rc;
+  *bytes = cc_layout(V, F).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_cc_round(const int32_t* faces, int64_t V, int64_t F, int round, void* ws, size_t ws_bytes, int32_t* changed, void* stream) {
+  CcLayout L;
+  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (!changed) return fail(NERF_HIP_ERR_ARG, "changed is null");
+  if (((uintptr_t)changed & 3) != 0) return fail(NERF_HIP_ERR_ARG, "changed must be 4-byte aligned");
+  if (round < 0) return fail(NERF_HIP_ERR_ARG, "round=%d < 0", round);
+  if (round >= CC_MAX_ROUNDS)
+    return fail(NERF_HIP_ERR_CONVERGE, "the component labelling did not converge in %d rounds (V=%lld F=%lld); no result", CC_MAX_ROUNDS,
+                (long long)V, (long long)F);
+  if (int rc = check_device()) return rc;
+  CcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  a.L = at<int>(ws, L.L);
+  a.changed = changed;
+  HIP_TRY(launch_cc_round(a, round == 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_cc_ids(const int32_t* faces, int64_t V, int64_t F, void* ws, size_t ws_bytes, int32_t* vert_comp, int32_t* face_comp,
+                         int64_t* count, void* stream) {
+  CcLayout L;
+  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (F > 0 && (!faces || !face_comp)) return fail(NERF_HIP_ERR_ARG, "faces / face_comp is null");
+  if (V > 0 && !vert_comp) return fail(NERF_HIP_ERR_ARG, "vert_comp is null");
+  if (!count) return fail(NERF_HIP_ERR_ARG, "count is null");
+  if (((uintptr_t)count & 7) != 0) return fail(NERF_HIP_ERR_ARG, "count must be 8-byte aligned");
+  if (int rc = check_device()) return rc;
+  CcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  a.L = at<int>(ws, L.L);
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  a.vert_comp = vert_comp;
+  a.face_comp = face_comp;
+  a.count = reinterpret_cast<long long*>(count);
+  HIP_TRY(launch_cc_ids(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_cc_stats(const float* verts, const int32_t* vert_comp, const int32_t* face_comp, int64_t V, int64_t F, int32_t* n_verts,
+                           int32_t* n_faces, float* bbox_lo, float* bbox_hi, int64_t max_c, void* stream) {
+  if (int rc = check_cc_sizes(V, F)) return rc;
+  if (max_c < 0 || max_c >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "max_c=%lld: a capacity in [0, 2^31)", (long long)max_c);
+  if (V > 0 && !vert_comp) return fail(NERF_HIP_ERR_ARG, "vert_comp is null");
+  if (F > 0 && !face_comp) return fail(NERF_HIP_ERR_ARG, "face_comp is null");
+  if (max_c > 0 && (!n_verts || !n_faces)) return fail(NERF_HIP_ERR_ARG, "n_verts / n_faces is null");
+  if ((bbox_lo == nullptr) != (bbox_hi == nullptr)) return fail(NERF_HIP_ERR_ARG, "bbox_lo and bbox_hi come together");
+  if (bbox_lo && V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "boxes need verts");
+  if (int rc = check_device()) return rc;
+  CcStatsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.vert_comp = vert_comp;
+  a.face_comp = face_comp;
+  a.verts = verts;
+  a.V = V;
+  a.F = F;
+  a.max_c = max_c;
+  a.n_verts = n_verts;
+  a.n_faces = n_faces;
+  a.lo = reinterpret_cast<unsigned*>(bbox_lo);
+  a.hi = reinterpret_cast<unsigned*>(bbox_hi);
+  HIP_TRY(launch_cc_stats(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
+                             const int32_t* vert_comp, const int32_t* face_comp, const uint8_t* keep, int64_t C, void* ws, size_t ws_bytes,
+                             float* out_verts, float* out_normals, float* out_rgb, int32_t* out_faces, int64_t max_v, int64_t max_f,
+                             int64_t* counts, void* stream) {
+  CcLayout L;
+  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (C < 0 || C > V) return fail(NERF_HIP_ERR_ARG, "C=%lld: a mesh of %lld vertices has at most as many components", (long long)C, (long long)V);
+  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (V > 0 && (!verts || !vert_comp)) return fail(NERF_HIP_ERR_ARG, "verts / vert_comp is null");
+  if (F > 0 && (!faces || !face_comp)) return fail(NERF_HIP_ERR_ARG, "faces / face_comp is null");
+  if (C > 0 && !keep) return fail(NERF_HIP_ERR_ARG, "keep is null");
+  if (max_v > 0 && (!out_verts || (normals && !out_normals) || (rgb && !out_rgb))) return fail(NERF_HIP_ERR_ARG, "an output of max_v rows is null");
+  if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
+  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
+  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
+  if (int rc = check_device()) return rc;
+  CcCompactArgs a;
+  memset(&a, 0, sizeof(a));
+  a.verts = verts;
+  a.normals = normals;
+  a.rgb = rgb;
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  a.C = (int)C;
+  a.vert_comp = vert_comp;
+  a.face_comp = face_comp;
+  a.keep = keep;
+  a.newidx = at<int>(ws, L.L);
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  a.out_verts = out_verts;
+  a.out_normals = out_normals;
+  a.out_rgb = out_rgb;
+  a.out_faces = out_faces;
+  a.max_v = max_v;
+  a.max_f = max_f;
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_cc_compact(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
 int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
   if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);

@@ -423,6 +423,51 @@ inline int mesh_blocks(long long n_points) { return (int)((n_points + MESH_PTS -
 hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st);  // count + in-block vertex scan, then the scan of the block totals
 hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st);
 
+// ---- connected components of an indexed mesh (mesh_cc.hip; nerf_hip_mesh_cc_*) ----
+constexpr int CC_WG = 256;                     // threads per workgroup
+constexpr int CC_ROUNDS = 8;                   // rounds of CC_WG consecutive items per workgroup of the scans
+constexpr int CC_PTS = CC_WG * CC_ROUNDS;      // items per workgroup (the scan's block)
+constexpr int CC_MAX_ROUNDS = 64;              // labelling rounds before the call gives up (NERF_HIP_ERR_CONVERGE)
+
+inline int cc_blocks(long long n) { return (int)((n + CC_PTS - 1) / CC_PTS); }
+
+struct CcArgs {
+  const int* faces;        // [F][3]
+  int V, F;
+  int* L;                  // [V] labels: L[x] <= x, a vertex of x's component (workspace)
+  int* changed;            // [1] round only: 1 when the round's hooks lowered a label
+  int *tot, *base;         // [cc_blocks(V)] ids only: roots per workgroup and their exclusive scan (workspace)
+  int *vert_comp, *face_comp;  // [V], [F] ids only
+  long long* count;        // [1] ids only: C
+};
+
+struct CcStatsArgs {
+  const int *vert_comp, *face_comp;  // [V], [F]
+  const float* verts;      // [V][3] or null (with lo / hi)
+  long long V, F, max_c;   // ids >= max_c (and < 0) are left out
+  int *n_verts, *n_faces;  // [max_c]
+  unsigned *lo, *hi;       // [max_c][3] or null: keys while the atomics run, decoded to floats in place by the last launch
+};
+
+struct CcCompactArgs {
+  const float *verts, *normals, *rgb;  // [V][3]; normals / rgb (with their outputs) may be null
+  const int* faces;        // [F][3]
+  int V, F, C;
+  const int *vert_comp, *face_comp;
+  const unsigned char* keep;  // [C]
+  int* newidx;             // [V] rank of a kept vertex among the kept, -1 for a dropped one (workspace, in L's place)
+  int *tot, *base;         // [cc_blocks(max(V, F))] (workspace)
+  float *out_verts, *out_normals, *out_rgb;  // [max_v][3]
+  int* out_faces;          // [max_f][3]
+  long long max_v, max_f;
+  long long* counts;       // [2] = V', F'
+};
+
+hipError_t launch_cc_round(const CcArgs& a, bool first, hipStream_t st);  // (first: L[v] = v,) changed = 0, hook, compress
+hipError_t launch_cc_ids(const CcArgs& a, hipStream_t st);                // roots -> ascending ids (scan), vert_comp, face_comp, count
+hipError_t launch_cc_stats(const CcStatsArgs& a, hipStream_t st);
+hipError_t launch_cc_compact(const CcCompactArgs& a, hipStream_t st);     // the kept vertices' scan and placement, then the kept faces'
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

@@ -1,0 +1,429 @@
+// mesh_cc.hip -- connected components of an indexed triangle mesh (nerf_hip_mesh_cc_*; the definition is in
+// include/nerf_hip.h): labels, per-component counts and boxes, and the compaction that drops components.
+//   k_cc_init        L[v] = v
+//   k_cc_hook        per face: the three labels r_k = L[v_k], m = min r_k, atomicMin(&L[r_k], m) for every r_k != m; sets `changed`
+//   k_cc_compress    per vertex: walks x = L[x] to the root, halving the path on the way, and leaves the root in L[v]
+//   k_cc_count / k_cc_scan / k_cc_place   the three-launch scan of mesh.hip over a 0/1 flag per item (roots, kept vertices, kept
+//                    faces): totals per workgroup of CC_PTS items, one workgroup's exclusive scan of them, then the placement
+//   k_cc_fill / k_cc_faces                vert_comp of the non-roots from their root's id; face_comp
+//   k_cc_stats_*     counts and boxes by integer atomics, aggregated inside the wave first
+// One round of the labelling is a hook launch and a compress launch; the host reads `changed` after each round and stops at the first
+// round that lowered nothing (ops.mesh_components), as density_band drives its rounds.
+//
+// WHY THE ROUNDS ARE SAFE ON THIS MEMORY SYSTEM (per-XCD L2s that are not coherent inside a launch, L1s that are never refreshed):
+//   (I1) L[x] <= x always, and every write to L after k_cc_init is an agent-scope atomicMin, so an entry only ever decreases.  (The
+//        path halving uses atomicMin too, not a plain store: a plain store that lost a race against another lane's lower store would
+//        RAISE the entry again, and one that landed after the owner's final store would leave the entry uncompressed.)
+//   (I2) Every value ever stored in L[x] is x's parent, an older ancestor of x, or its root: a vertex of the same component.  A stale
+//        read therefore only yields an older ancestor, never a wrong one.
+//   (I3) By (I1) every walk strictly descends and ends after at most x steps, whatever mixture of old and new values it reads.  No
+//        kernel waits for another workgroup inside a launch.
+//   (I4) A launch boundary makes every earlier write visible.  The roots are fixed during a compress launch (hooks run in the other
+//        launch), each owner's walk ends at its true root r, and atomicMin(&L[v], r) leaves L[v] == r because nothing stored there is
+//        lower: every round starts fully compressed, so the r_k that k_cc_hook reads are roots.
+//   (I5) A hook launch that lowered nothing wrote nothing, so it read one consistent image (I4): every face had three equal labels
+//        (an r_k != m that atomicMin did not lower would have been lowered by another lane of the same launch, which then sets
+//        `changed`).  Labels are equal only inside a component (I2), so the stopping test is exact.
+// Skipping r_k == m keeps a giant component from hammering one address: once it has one root, its faces issue no atomic at all.
+// Nothing is placed by atomics; the only atomics are integer min / max / add, whose results do not depend on arrival order.  Every
+// index read from memory is checked before it is used as an address, so a wrong argument gives wrong output, never a wild access.
+#include "kernels.h"
+
+namespace nerf {
+
+namespace {
+
+__device__ inline unsigned cc_lane_prefix(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+__device__ inline int cc_atomic_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ inline bool cc_face_ok(int a, int b, int c, int V) {
+  return (unsigned)a < (unsigned)V && (unsigned)b < (unsigned)V && (unsigned)c < (unsigned)V;
+}
+
+// the floats' order-preserving unsigned images (ray_parts.h sort_key: -0 keyed as +0); only finite values are keyed here
+__device__ inline unsigned cc_key(float x) {
+  unsigned b = __float_as_uint(x);
+  if (b == 0x80000000u) b = 0u;
+  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ inline float cc_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+constexpr unsigned CC_KEY_NONE_LO = 0xFFFFFFFFu, CC_KEY_NONE_HI = 0u;  // the identities of min / max: the image of no finite float
+
+}  // namespace
+
+// ---- labelling ----
+
+// grid = ceil(V / CC_WG)
+__global__ __launch_bounds__(CC_WG) void k_cc_init(int* __restrict__ L, int V) {
+  const long long v = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (v < V) L[v] = (int)v;
+}
+
+// grid = ceil(F / CC_WG), one thread per face
+__global__ __launch_bounds__(CC_WG) void k_cc_hook(const int* __restrict__ faces, int V, int F, int* L, int* changed) {
+  const long long f = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (f >= F) return;
+  const int a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
+  if (!cc_face_ok(a, b, c, V)) return;  // takes no part, and is never used as an address
+  const int ra = L[a], rb = L[b], rc = L[c];
+  if ((unsigned)ra > (unsigned)a || (unsigned)rb > (unsigned)b || (unsigned)rc > (unsigned)c) return;  // (I1) holds: never taken
+  const int m = min(ra, min(rb, rc));
+  bool lowered = false;
+  if (ra != m) lowered |= cc_atomic_min(&L[ra], m) > m;
+  if (rb != m) lowered |= cc_atomic_min(&L[rb], m) > m;
+  if (rc != m) lowered |= cc_atomic_min(&L[rc], m) > m;
+  if (lowered) *changed = 1;
+}
+
+// grid = ceil(V / CC_WG), one thread per vertex
+__global__ __launch_bounds__(CC_WG) void k_cc_compress(int* L, int V) {
+  const long long vl = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (vl >= V) return;
+  const int v = (int)vl;
+  const int p0 = L[v];
+  int x = v, p = p0;
+  while ((unsigned)p < (unsigned)x) {  // (I3): p < x until the root, where p == x
+    const int g = L[p];
+    if ((unsigned)g >= (unsigned)p) {
+      x = p;
+      break;
+    }
+    cc_atomic_min(&L[x], g);  // halve: x's grandparent becomes its parent
+    x = g;
+    p = L[x];
+  }
+  if (x != p0) cc_atomic_min(&L[v], x);
+}
+
+// ---- the scan pattern over a flag per item ----
+
+namespace {
+
+// in-workgroup exclusive prefix of a 0/1 flag in item order plus the workgroup's total; part = LDS [CC_WG / 64]
+__device__ inline int cc_wg_prefix(int flag, int* part, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  const int pre = (int)cc_lane_prefix(m);
+  if (lane == 0) part[wave] = __popcll(m);
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < CC_WG / 64; ++w) {
+    const int t = part[w];
+    before += (w < wave) ? t : 0;
+    total += t;
+  }
+  __syncthreads();
+  return before + pre;
+}
+
+}  // namespace
+
+// the flags (is item i counted?) and sinks (item i, its flag, its rank among the flagged) of the three uses
+struct RootFlag {  // v is a root
+  const int* L;
+  __device__ int operator()(long long i) const { return L[i] == (int)i; }
+};
+struct RootSink {  // roots take their ids
+  int* vert_comp;
+  __device__ void operator()(long long i, int flag, long long pos) const {
+    if (flag) vert_comp[i] = (int)pos;
+  }
+};
+
+struct VertKeep {
+  const int* vert_comp;
+  const unsigned char* keep;
+  int C;
+  __device__ int operator()(long long i) const {
+    const int c = vert_comp[i];
+    return (unsigned)c < (unsigned)C && keep[c] != 0;
+  }
+};
+struct VertSink {
+  const float *verts, *normals, *rgb;
+  float *out_verts, *out_normals, *out_rgb;
+  int* newidx;
+  long long max_v;
+  __device__ void operator()(long long i, int flag, long long pos) const {
+    newidx[i] = flag ? (int)pos : -1;
+    if (!flag || pos >= max_v) return;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      out_verts[pos * 3 + d] = verts[i * 3 + d];
+      if (normals) out_normals[pos * 3 + d] = normals[i * 3 + d];
+      if (rgb) out_rgb[pos * 3 + d] = rgb[i * 3 + d];
+    }
+  }
+};
+
+struct FaceKeep {
+  const int *faces, *face_comp;
+  const unsigned char* keep;
+  int V, C;
+  __device__ int operator()(long long i) const {
+    const int c = face_comp[i];
+    if ((unsigned)c >= (unsigned)C || keep[c] == 0) return 0;
+    return cc_face_ok(faces[i * 3 + 0], faces[i * 3 + 1], faces[i * 3 + 2], V);
+  }
+};
+struct FaceSink {
+  const int *faces, *newidx;
+  int* out_faces;
+  long long max_f;
+  __device__ void operator()(long long i, int flag, long long pos) const {
+    if (!flag || pos >= max_f) return;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out_faces[pos * 3 + d] = newidx[faces[i * 3 + d]];  // (FaceKeep checked the three indices)
+  }
+};
+
+// grid = nb = ceil(n / CC_PTS)
+template <class Flag>
+__global__ __launch_bounds__(CC_WG) void k_cc_count(const Flag flag, long long n, int* __restrict__ tot) {
+  __shared__ int part[CC_WG / 64];
+  const long long base = (long long)blockIdx.x * CC_PTS;
+  int run = 0;
+  for (int r = 0; r < CC_ROUNDS; ++r) {
+    const long long i = base + r * CC_WG + threadIdx.x;
+    int total;
+    (void)cc_wg_prefix(i < n ? flag(i) : 0, part, total);
+    run += total;
+  }
+  if (threadIdx.x == 0) tot[blockIdx.x] = run;
+}
+
+// one workgroup of 1024: thread t scans a contiguous run of the workgroup totals, the runs are joined by an LDS scan
+__global__ __launch_bounds__(1024) void k_cc_scan(const int* __restrict__ tot, int* __restrict__ base, int nb, long long* count) {
+  __shared__ long long s[1024];
+  const int per = (nb + 1023) / 1024, b0 = threadIdx.x * per;
+  long long t = 0;
+  for (int q = 0; q < per; ++q) {
+    const int b = b0 + q;
+    if (b < nb) t += tot[b];
+  }
+  s[threadIdx.x] = t;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
+    const long long x = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
+    __syncthreads();
+    s[threadIdx.x] += x;
+    __syncthreads();
+  }
+  long long e = s[threadIdx.x] - t;
+  for (int q = 0; q < per; ++q) {
+    const int b = b0 + q;
+    if (b < nb) {
+      base[b] = (int)e;  // (at most n < 2^31 items are flagged)
+      e += tot[b];
+    }
+  }
+  if (threadIdx.x == 1023) *count = s[1023];
+}
+
+// grid = nb; the flags are recomputed: no launch between the count and here writes what they read
+template <class Flag, class Sink>
+__global__ __launch_bounds__(CC_WG) void k_cc_place(const Flag flag, const Sink sink, long long n, const int* __restrict__ bases) {
+  __shared__ int part[CC_WG / 64];
+  const long long base = (long long)blockIdx.x * CC_PTS;
+  long long run = bases[blockIdx.x];
+  for (int r = 0; r < CC_ROUNDS; ++r) {
+    const long long i = base + r * CC_WG + threadIdx.x;
+    const int fl = i < n ? flag(i) : 0;
+    int total;
+    const int pre = cc_wg_prefix(fl, part, total);
+    if (i < n) sink(i, fl, run + pre);
+    run += total;
+  }
+}
+
+// grid = ceil(V / CC_WG): the non-roots take their root's id.  Reads only roots' entries of vert_comp (written by the launch before) and
+// writes only non-roots' entries.
+__global__ __launch_bounds__(CC_WG) void k_cc_fill(const int* __restrict__ L, int V, int* vert_comp) {
+  const long long v = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (v >= V) return;
+  const int r = L[v];
+  if ((unsigned)r < (unsigned)v) vert_comp[v] = vert_comp[r];
+}
+
+// grid = ceil(F / CC_WG)
+__global__ __launch_bounds__(CC_WG) void k_cc_faces(const int* __restrict__ faces, int V, int F, const int* __restrict__ vert_comp,
+                                                    int* __restrict__ face_comp) {
+  const long long f = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (f >= F) return;
+  const int a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
+  face_comp[f] = cc_face_ok(a, b, c, V) ? vert_comp[a] : -1;
+}
+
+// ---- per-component counts and boxes ----
+
+namespace {
+
+__device__ inline unsigned cc_wave_min(unsigned x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x = min(x, (unsigned)__shfl_xor((int)x, d));
+  return x;
+}
+__device__ inline unsigned cc_wave_max(unsigned x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x = max(x, (unsigned)__shfl_xor((int)x, d));
+  return x;
+}
+
+}  // namespace
+
+// grid = ceil(max_c / CC_WG)
+__global__ __launch_bounds__(CC_WG) void k_cc_stats_init(const CcStatsArgs a) {
+  const long long c = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (c >= a.max_c) return;
+  a.n_verts[c] = 0;
+  a.n_faces[c] = 0;
+  if (a.lo) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      a.lo[c * 3 + d] = CC_KEY_NONE_LO;
+      a.hi[c * 3 + d] = CC_KEY_NONE_HI;
+    }
+  }
+}
+
+// grid = ceil(n / CC_WG), whole waves.  One atomic per distinct component per wave-instruction: the wave peels off the component of its
+// first remaining lane (a wave of a cell-ordered mesh usually holds one), its lanes are counted by a ballot and, BOX, their keys reduced
+// across the wave; the leading lane issues the atomics.  BOX = false counts faces, BOX = true counts vertices and bounds them.
+template <bool BOX>
+__global__ __launch_bounds__(CC_WG) void k_cc_stats(const CcStatsArgs a) {
+  const long long i = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  const long long n = BOX ? a.V : a.F;
+  const int lane = threadIdx.x & 63;
+  int c = -1;
+  if (i < n) c = BOX ? a.vert_comp[i] : a.face_comp[i];
+  const bool act = (unsigned)c < (unsigned)a.max_c;  // behind the caller's capacity (and -1 = a face that takes no part)
+  unsigned klo[3] = {CC_KEY_NONE_LO, CC_KEY_NONE_LO, CC_KEY_NONE_LO}, khi[3] = {CC_KEY_NONE_HI, CC_KEY_NONE_HI, CC_KEY_NONE_HI};
+  if (BOX && a.lo && act) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float x = a.verts[i * 3 + d];
+      if (isfinite(x)) klo[d] = khi[d] = cc_key(x);
+    }
+  }
+  int* const cnt = BOX ? a.n_verts : a.n_faces;
+  unsigned long long todo = __ballot(act);
+  while (todo) {  // (uniform)
+    const int lead = __ffsll((long long)todo) - 1;
+    const int lc = __shfl(c, lead);
+    const bool mine = act && c == lc;
+    const unsigned long long grp = __ballot(mine);
+    const int k = __popcll(grp);
+    if (lane == lead) atomicAdd(&cnt[lc], k);
+    if (BOX && a.lo) {
+      unsigned rlo[3], rhi[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        rlo[d] = mine ? klo[d] : CC_KEY_NONE_LO;
+        rhi[d] = mine ? khi[d] : CC_KEY_NONE_HI;
+        if (k > 1) {  // (uniform)
+          rlo[d] = cc_wave_min(rlo[d]);
+          rhi[d] = cc_wave_max(rhi[d]);
+        }
+      }
+      if (lane == lead) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          if (rlo[d] != CC_KEY_NONE_LO) {
+            atomicMin(&a.lo[(long long)lc * 3 + d], rlo[d]);
+            atomicMax(&a.hi[(long long)lc * 3 + d], rhi[d]);
+          }
+        }
+      }
+    }
+    todo &= ~grp;
+  }
+}
+
+// grid = ceil(3 max_c / CC_WG): keys -> floats in place; a component without a finite coordinate keeps (+inf, -inf)
+__global__ __launch_bounds__(CC_WG) void k_cc_stats_decode(const CcStatsArgs a) {
+  const long long i = (long long)blockIdx.x * CC_WG + threadIdx.x;
+  if (i >= a.max_c * 3) return;
+  const unsigned l = a.lo[i], h = a.hi[i];
+  a.lo[i] = __float_as_uint(l == CC_KEY_NONE_LO ? INFINITY : cc_unkey(l));
+  a.hi[i] = __float_as_uint(h == CC_KEY_NONE_HI ? -INFINITY : cc_unkey(h));
+}
+
+// ---- launchers ----
+
+namespace {
+
+inline unsigned cc_grid(long long n) { return (unsigned)((n + CC_WG - 1) / CC_WG); }
+
+#define CC_LAUNCH(...)                            \
+  do {                                            \
+    hipLaunchKernelGGL(__VA_ARGS__);              \
+    const hipError_t e_ = hipGetLastError();      \
+    if (e_ != hipSuccess) return e_;              \
+  } while (0)
+
+template <class Flag, class Sink>
+hipError_t cc_scan_place(const Flag& flag, const Sink& sink, long long n, int* tot, int* base, long long* count, hipStream_t st) {
+  const int nb = cc_blocks(n);
+  CC_LAUNCH((k_cc_count<Flag>), dim3(nb), dim3(CC_WG), 0, st, flag, n, tot);
+  CC_LAUNCH(k_cc_scan, dim3(1), dim3(1024), 0, st, tot, base, nb, count);
+  CC_LAUNCH((k_cc_place<Flag, Sink>), dim3(nb), dim3(CC_WG), 0, st, flag, sink, n, base);
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_cc_round(const CcArgs& a, bool first, hipStream_t st) {
+  if (first && a.V > 0) CC_LAUNCH(k_cc_init, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V);
+  hipError_t e = hipMemsetAsync(a.changed, 0, sizeof(int), st);
+  if (e != hipSuccess) return e;
+  if (a.V == 0 || a.F == 0) return hipSuccess;  // no face can hook anything
+  CC_LAUNCH(k_cc_hook, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.L, a.changed);
+  CC_LAUNCH(k_cc_compress, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V);
+  return hipSuccess;
+}
+
+hipError_t launch_cc_ids(const CcArgs& a, hipStream_t st) {
+  if (a.V == 0) {
+    const hipError_t e = hipMemsetAsync(a.count, 0, sizeof(long long), st);
+    if (e != hipSuccess) return e;
+  } else {
+    const hipError_t e = cc_scan_place(RootFlag{a.L}, RootSink{a.vert_comp}, a.V, a.tot, a.base, a.count, st);
+    if (e != hipSuccess) return e;
+    CC_LAUNCH(k_cc_fill, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V, a.vert_comp);
+  }
+  if (a.F > 0) CC_LAUNCH(k_cc_faces, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.vert_comp, a.face_comp);
+  return hipSuccess;
+}
+
+hipError_t launch_cc_stats(const CcStatsArgs& a, hipStream_t st) {
+  if (a.max_c == 0) return hipSuccess;
+  CC_LAUNCH(k_cc_stats_init, dim3(cc_grid(a.max_c)), dim3(CC_WG), 0, st, a);
+  if (a.V > 0) CC_LAUNCH(k_cc_stats<true>, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a);
+  if (a.F > 0) CC_LAUNCH(k_cc_stats<false>, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a);
+  if (a.lo) CC_LAUNCH(k_cc_stats_decode, dim3(cc_grid(a.max_c * 3)), dim3(CC_WG), 0, st, a);
+  return hipSuccess;
+}
+
+hipError_t launch_cc_compact(const CcCompactArgs& a, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.counts, 0, 2 * sizeof(long long), st);
+  if (e != hipSuccess) return e;
+  if (a.V > 0) {
+    e = cc_scan_place(VertKeep{a.vert_comp, a.keep, a.C},
+                      VertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v}, a.V, a.tot, a.base,
+                      a.counts, st);
+    if (e != hipSuccess) return e;
+  }
+  if (a.F > 0 && a.V > 0) {  // (after the vertices' placement: the faces read newidx across workgroups)
+    e = cc_scan_place(FaceKeep{a.faces, a.face_comp, a.keep, a.V, a.C}, FaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot,
+                      a.base, a.counts + 1, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace nerf

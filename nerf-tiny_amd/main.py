@@ -51,6 +51,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-band", type=int, default=None, metavar="R",
                     help="--mesh evaluates the field only in a band of R^3-point blocks around the surface (R >= 2; narrow-band grid: the "
                          "same mesh wherever the band finds the surface, a component smaller than a block can be missed; default: dense)")
+    ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
+                    help="--mesh drops the floaters: connected components of fewer than N faces, labelled and removed on the device before "
+                         "normals and colours are queried (with --mesh-band the band may already have missed islands smaller than a block; "
+                         "this removes the rest; default: keep everything)")
+    ap.add_argument("--mesh-keep-largest", type=int, default=None, metavar="K",
+                    help="--mesh keeps only the K connected components with the most faces (ties: the lower component id; combines with "
+                         "--mesh-min-faces; default: keep everything)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--maps", action="store_true",
@@ -103,4 +110,4 @@ if __name__ == "__main__":
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:
         run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
-                         band=args.mesh_band)
+                         band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest)

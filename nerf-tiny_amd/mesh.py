@@ -1,5 +1,6 @@
 """Triangle meshes of the field's isosurfaces (not in the reference): marching cubes over a device density grid (HIP kernels,
-csrc/mesh.hip) and a binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
+csrc/mesh.hip), connected components on the device -- label, measure and drop the floaters (csrc/mesh_cc.hip,
+DESIGN.md section 3h-3) -- and a binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -29,6 +30,62 @@ def marching_cubes(sigma, level, lo=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), ws=No
     lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
     step32 = np.asarray(step, dtype=np.float32).reshape(3)
     return ops.marching_cubes(sigma, lo32.tolist(), step32.tolist(), float(np.float32(level)), ws=ws)
+
+
+class Components(NamedTuple):
+    vert_comp: object  # [V] int32 component id of each vertex; ids 0 .. C-1 ascend with the component's smallest vertex index
+    face_comp: object  # [F] int32 id of the face's first vertex; -1 for a face with an index outside [0, V)
+    n_verts: object    # [C] int32
+    n_faces: object    # [C] int32
+    bbox_lo: object    # [C, 3] fp32 minimum of the component's finite vertex coordinates (+inf where it has none), or None
+    bbox_hi: object    # [C, 3] fp32 maximum (-inf where it has none), or None
+    rounds: object = None  # labelling rounds the device took, the last one changing nothing
+
+
+def components(faces, num_verts, verts=None):
+    """Connected components of an indexed triangle mesh on the DEVICE: faces [F, 3] int32 over num_verts vertices (any indexed mesh,
+    not only marching_cubes').  Two vertices are connected when some face contains both, so two triangles that share one vertex are
+    one component; a vertex in no face is a component of its own with 0 faces; a face with an index outside [0, num_verts) takes no
+    part (face_comp -1).  Returns Components of device tensors, the boxes only with verts [V, 3]; the exact rules are in
+    include/nerf_hip.h and every output is a pure function of the input (identical bits from run to run).  A CPU tensor raises: there
+    is no CPU path."""
+    from . import ops
+
+    faces = torch.as_tensor(faces)
+    if faces.device.type != "cuda":
+        raise RuntimeError("components runs only on a ROCm device (MI355X): faces.to('cuda'); there is no CPU path")
+    return Components(*ops.mesh_components(faces, num_verts, verts))
+
+
+def select_components(comps, min_faces=1, keep_largest=None):
+    """A keep mask [C] bool over comps (a Components): n_faces >= min_faces, and with keep_largest=k also among the k components with
+    the most faces (ties go to the lower id).  Bookkeeping on the [C] arrays in torch; build a mask of your own from comps.bbox_lo /
+    bbox_hi / n_verts where these rules do not fit (e.g. keep what intersects a box)."""
+    n = torch.as_tensor(comps.n_faces)
+    keep = n >= int(min_faces)
+    if keep_largest is not None:
+        k = int(keep_largest)
+        if k < 0:
+            raise ValueError(f"keep_largest={k} < 0")
+        order = torch.sort(n, descending=True, stable=True).indices  # (stable: equal counts stay in id order)
+        top = torch.zeros_like(keep)
+        top[order[:k]] = True
+        keep = keep & top
+    return keep
+
+
+def filter_components(m, comps, keep):
+    """The Mesh m without the components whose keep[c] is False (device compaction): kept vertices -- with their normals and rgb where m
+    has them -- and kept faces stay in their order, face indices are renumbered, faces that take no part (face_comp -1) are dropped."""
+    from . import ops
+
+    keep = torch.as_tensor(keep).to(comps.n_faces.device) != 0
+    if tuple(keep.shape) != tuple(comps.n_faces.shape):
+        raise ValueError(f"keep {tuple(keep.shape)}: one entry per component, [{len(comps.n_faces)}]")
+    V1 = int(comps.n_verts[keep].sum())  # (one read; the device writes the same counts)
+    F1 = int(comps.n_faces[keep].sum())
+    v, f, n, c, _ = ops.mesh_compact(m.verts, m.faces, m.normals, m.rgb, comps.vert_comp, comps.face_comp, keep, V1, F1)
+    return Mesh(v, f, n, c)
 
 
 def _np(a):

@@ -613,7 +613,7 @@ class NeRFModel(nn.Module):
         return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
 
     @torch.no_grad()
-    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None):
+    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -624,7 +624,12 @@ class NeRFModel(nn.Module):
         spacing; the colours are then seen along these normals.
         band=None: the dense grid.  band=r (an int >= 2): density_band(lo, hi, res, level, block=r) in its place -- the field is evaluated
         only in blocks of r^3 points around the surface, and the mesh is the dense one wherever the band found the surface; a component
-        smaller than a block can be missed (density_band says when).  Everything after the grid is the same."""
+        smaller than a block can be missed (density_band says when).  Everything after the grid is the same.
+        min_faces=n / keep_largest=k (either or both; None, None: nothing of this runs): the floaters go -- right after marching cubes
+        the mesh's connected components are labelled on the device (mesh.components) and only those with at least n faces and, with k,
+        among the k with the most faces stay (mesh.select_components, mesh.filter_components).  This happens BEFORE the field normals and
+        the colours are queried, so a dropped vertex is never evaluated; the result is, bit for bit, filter_components applied to the
+        unfiltered call.  With band=: the band may already have missed islands smaller than a block; filtering removes the rest."""
         import numpy as np
 
         from . import mesh
@@ -637,6 +642,10 @@ class NeRFModel(nn.Module):
         sigma = self.density_grid(lo32, hi32, shape) if band is None else self.density_band(lo32, hi32, shape, level, block=band)[0]
         verts, faces, nrm = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
         del sigma
+        if min_faces is not None or keep_largest is not None:
+            comps = mesh.components(faces, len(verts), verts)
+            keep = mesh.select_components(comps, 1 if min_faces is None else min_faces, keep_largest)
+            verts, faces, nrm, _ = mesh.filter_components(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), comps, keep)
         if normals == "field":
             nrm = field_normals(self.query_grad(verts)[2])
         rgb = self.query(verts, -nrm)[0] if color else None

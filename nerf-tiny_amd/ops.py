@@ -186,6 +186,83 @@ def marching_cubes(sigma, lo, step, level, ws=None):
     return verts, faces, normals
 
 
+def _cc_faces(faces, num_verts):
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"faces {tuple(faces.shape)} {faces.dtype}: an int32 [F, 3] tensor")
+    V = int(num_verts)
+    if V < 0:
+        raise ValueError(f"num_verts={V} < 0")
+    return faces.contiguous(), V, int(faces.shape[0])
+
+
+def mesh_components(faces, num_verts, verts=None, ws=None):
+    """Connected components of the indexed mesh faces[F, 3] (int32, device) over num_verts vertices (nerf_hip_mesh_cc_round until a
+    round changes nothing, then nerf_hip_mesh_cc_ids and nerf_hip_mesh_cc_stats; the definition is in include/nerf_hip.h) ->
+    (vert_comp[V] int32, face_comp[F] int32, n_verts[C] int32, n_faces[C] int32, bbox_lo[C, 3], bbox_hi[C, 3] fp32 -- both None without
+    verts[V, 3] --, rounds).  One 4-byte read of the device's `changed` word per round and one 8-byte read of C (each synchronises with
+    the stream).  A labelling that does not converge within the library's cap of rounds raises NerfHipError: there is no partial
+    result.  ws: a uint8 device buffer of >= _abi.mesh_cc_ws_bytes(V, F) bytes (allocated here if None)."""
+    faces, V, F = _cc_faces(faces, num_verts)
+    dev = faces.device
+    if verts is not None:
+        if tuple(verts.shape) != (V, 3) or verts.device != dev:
+            raise ValueError(f"verts {tuple(verts.shape)} on {verts.device}: a [{V}, 3] tensor on {dev}")
+        verts = verts.to(torch.float32).contiguous()
+    if ws is None:
+        ws = torch.empty(max(_abi.mesh_cc_ws_bytes(V, F), 1), dtype=torch.uint8, device=dev)
+    L, st = _abi.lib(), _stream(faces)
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    rounds = 0
+    while True:  # (the library refuses the round past its cap: the loop ends)
+        _abi.check(L.nerf_hip_mesh_cc_round(faces.data_ptr(), V, F, rounds, ws.data_ptr(), ws.numel(), changed.data_ptr(), st))
+        rounds += 1
+        if int(changed.cpu()) == 0:
+            break
+    vert_comp = torch.empty(V, dtype=torch.int32, device=dev)
+    face_comp = torch.empty(F, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    _abi.check(L.nerf_hip_mesh_cc_ids(faces.data_ptr(), V, F, ws.data_ptr(), ws.numel(), vert_comp.data_ptr(), face_comp.data_ptr(),
+                                      count.data_ptr(), st))
+    C_ = int(count.cpu())
+    n_verts = torch.empty(C_, dtype=torch.int32, device=dev)
+    n_faces = torch.empty(C_, dtype=torch.int32, device=dev)
+    lo = hi = None
+    if verts is not None:
+        lo, hi = torch.empty(C_, 3, device=dev), torch.empty(C_, 3, device=dev)
+    _abi.check(L.nerf_hip_mesh_cc_stats(verts.data_ptr() if verts is not None else None, vert_comp.data_ptr(), face_comp.data_ptr(), V, F,
+                                        n_verts.data_ptr(), n_faces.data_ptr(), lo.data_ptr() if lo is not None else None,
+                                        hi.data_ptr() if hi is not None else None, C_, st))
+    return vert_comp, face_comp, n_verts, n_faces, lo, hi, rounds
+
+
+def mesh_compact(verts, faces, normals, rgb, vert_comp, face_comp, keep, max_v, max_f, ws=None):
+    """Drops the components c with keep[c] == 0 (nerf_hip_mesh_cc_compact): -> (verts[max_v, 3], faces[max_f, 3], normals, rgb -- None
+    where the input is None --, counts int64[2] = (V', F') on the device).  max_v / max_f: the outputs' rows (the kept components'
+    n_verts / n_faces sums); nothing is stored past them.  keep: a bool or uint8 [C] device tensor."""
+    faces, V, F = _cc_faces(faces, verts.shape[0])
+    dev = faces.device
+    f32 = lambda a: None if a is None else a.to(torch.float32).contiguous()
+    verts, normals, rgb = f32(verts), f32(normals), f32(rgb)
+    for a in (verts, normals, rgb):
+        if a is not None and (tuple(a.shape) != (V, 3) or a.device != dev):
+            raise ValueError(f"a per-vertex array {tuple(a.shape)} on {a.device}: [{V}, 3] on {dev}")
+    if tuple(vert_comp.shape) != (V,) or tuple(face_comp.shape) != (F,) or vert_comp.dtype != torch.int32 or face_comp.dtype != torch.int32:
+        raise ValueError(f"vert_comp {tuple(vert_comp.shape)} / face_comp {tuple(face_comp.shape)}: int32 [{V}] / [{F}]")
+    keep = keep.to(device=dev, dtype=torch.uint8).contiguous()
+    if ws is None:
+        ws = torch.empty(max(_abi.mesh_cc_ws_bytes(V, F), 1), dtype=torch.uint8, device=dev)
+    max_v, max_f = int(max_v), int(max_f)
+    out = lambda a: None if a is None else torch.empty(max_v, 3, device=dev)
+    ov, on, oc = out(verts), out(normals), out(rgb)
+    of = torch.empty(max_f, 3, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    ptr = lambda a: None if a is None else a.data_ptr()
+    _abi.check(_abi.lib().nerf_hip_mesh_cc_compact(ptr(verts), ptr(normals), ptr(rgb), faces.data_ptr(), V, F, vert_comp.contiguous().data_ptr(),
+                                                   face_comp.contiguous().data_ptr(), keep.data_ptr(), keep.numel(), ws.data_ptr(), ws.numel(),
+                                                   ptr(ov), ptr(on), ptr(oc), of.data_ptr(), max_v, max_f, counts.data_ptr(), _stream(faces)))
+    return ov, of, on, oc, counts
+
+
 def image_metrics(pred, gt, ws=None):
     """Per-view MSE and SSIM (nerf_hip_image_metrics, fp64 arithmetic; definition in include/nerf_hip.h): pred, gt [n, H, W, 3] device
     tensors of the same shape and device (cast to contiguous fp32 here) -> (mse[n], ssim[n]) fp64 on that device.  ws: a uint8 device

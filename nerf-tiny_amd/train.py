@@ -549,7 +549,8 @@ class NeRFRunner:
             np.savez(path, sigma=sigma, lo=lo32, hi=hi32, step=grid_step(lo32, hi32, shape), iter=np.int64(self.last_iter))
         return sigma
 
-    def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None):
+    def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
+                     keep_largest=None):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -557,7 +558,10 @@ class NeRFRunner:
         None.  Returns mesh.Mesh of numpy arrays (rgb None without color).  normals: "grid" (marching-cubes normals from the grid) or
         "field" (the field's analytic gradient at each vertex), as NeRFModel.extract_mesh.  band: None (the dense grid) or a block size
         r >= 2 -- the field is evaluated only in a band of r^3-point blocks around the surface (NeRFModel.density_band: far fewer points,
-        the same mesh wherever the band finds the surface; a component smaller than a block can be missed).  Same file name either way."""
+        the same mesh wherever the band finds the surface; a component smaller than a block can be missed).  min_faces / keep_largest: drop
+        the floaters on the device before normals and colours are queried -- keep the connected components with at least min_faces faces
+        and, with keep_largest=k, among the k with the most faces (NeRFModel.extract_mesh; both None: no filtering).  With band= the band
+        may already have missed islands smaller than a block, and filtering removes the rest.  Same file name either way."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -568,7 +572,8 @@ class NeRFRunner:
         shape = grid_shape(res)
         lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
         self.model.eval()
-        m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band)
+        m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
+                                    keep_largest=keep_largest)
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
