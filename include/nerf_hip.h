@@ -50,7 +50,8 @@ extern "C" {
                                      nerf_hip_image_metrics; nerf_hip_forward_maps_train, nerf_hip_backward_maps;
                                      nerf_hip_band_ws_bytes, nerf_hip_band_begin, nerf_hip_band_grow; nerf_hip_mesh_cc_ws_bytes,
                                      nerf_hip_mesh_cc_round, nerf_hip_mesh_cc_ids, nerf_hip_mesh_cc_stats, nerf_hip_mesh_cc_compact
-                                     (with NERF_HIP_ERR_CONVERGE) */
+                                     (with NERF_HIP_ERR_CONVERGE); nerf_hip_mesh_simplify_ws_bytes, nerf_hip_mesh_simplify_count,
+                                     nerf_hip_mesh_simplify_emit (with NERF_HIP_SIMPLIFY_TABLE_FULL) */
 
 enum {
   NERF_HIP_OK = 0,
@@ -480,6 +481,57 @@ int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const flo
                              const int32_t* vert_comp, const int32_t* face_comp, const uint8_t* keep, int64_t C, void* ws,
                              size_t ws_bytes, float* out_verts, float* out_normals, float* out_rgb, int32_t* out_faces, int64_t max_v,
                              int64_t max_f, int64_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Simplification of an indexed triangle mesh by uniform vertex clustering (Rossignac-Borrel).  Any indexed
+ * mesh: verts[V][3] fp32, optional normals[V][3] fp32, faces[F][3] int32, V, F < 2^31; and a cluster lattice lo[3], cell[3] (fp32,
+ * lo finite, each cell > 0 and finite), dims[3] (each in 1 .. 2048, product < 2^31).  Every output is a pure function of the input:
+ * identical bits from run to run, no float atomic anywhere.
+ * 1. Cell of a vertex.  Per axis u = fp32(fp32(p - lo) / cell) (two fp32 roundings, IEEE division), uc = clamp(u, 0, dims) and
+ *    i = min(floor(uc), dims - 1); the linear cell index is in C order, z fastest (the grids' order).  A vertex with a coordinate that
+ *    is not finite belongs to no cluster.  Vertices outside the lattice are pulled to its faces by the clamp (their uc as well, so
+ *    they pull their cluster's position to the face): this is not an error.
+ * 2. Clusters are the occupied cells.
+ * 3. Faces.  A face takes no part if it has an index outside [0, V) (never used as an address) or a vertex in no cluster.  A face is
+ *    degenerate if two of its vertices share a cell.  Among the remaining faces two are duplicates when their cell triples are equal up
+ *    to rotation (the same orientation), and the one with the lowest input index is kept.  The triple in REVERSED orientation is a
+ *    different face and both are kept: a thin sheet that collapsed, seen from its two sides.  Kept faces keep their input order and
+ *    their own corner order.
+ * 4. Vertices out are the clusters that at least one kept face uses, in ascending cell index.  Other clusters are dropped: an island
+ *    inside one cell leaves nothing.
+ * 5. Position of a cluster.  Per axis S = the sum over its members of rint(double(uc) * 2^20) as int64 (exact, order free; a term is
+ *    at most 2^31, so it cannot overflow), n = the member count, and the coordinate is
+ *    fp32(double(lo) + double(cell) * (double(S) / (double(n) * 2^20))), every fp64 operation rounded separately.
+ * 6. Normal of a cluster (only with normals).  Per axis T = the sum of rint(double(clamp(nrm, -2, 2)) * 2^28) as int64 over the members
+ *    whose normal has three finite components (any other member adds nothing); the component is fp32(T / sqrt((Tx Tx + Ty Ty) + Tz Tz))
+ *    in fp64, products and sums rounded separately in that order, and (0, 0, 0) where the length is 0.
+ * 7. Colours are not carried: the field is there to be asked at the new vertices.
+ * 8. counts (DEVICE int64[6]) = V', F', the number of occupied clusters, a flags word (NERF_HIP_SIMPLIFY_TABLE_FULL), the number of
+ *    degenerate faces, the number of duplicate faces dropped.
+ * Two calls in the shape of nerf_hip_mesh_count / nerf_hip_mesh_emit: count does everything up to counts, the caller reads them (the
+ * only synchronisation) and sizes the outputs, emit fills them; emit may be repeated.  Both are enqueue-only on the caller's stream and
+ * check every argument on the host before anything is enqueued (NERF_HIP_ERR_ARG: sizes, NULL arrays, a lattice outside the limits
+ * above, workspace NULL or not 256-byte aligned, counts not 8-byte aligned; NERF_HIP_ERR_WORKSPACE: workspace too small).  Indices read
+ * from device arrays are range-checked by the kernels before use and every store is clamped to max_v / max_f.
+ * Duplicates are found through an open-addressing table of face indices (a power of two of at least 2 F slots; above F = 2^30 it is
+ * capped at 2^31 slots, still more than F).  A face's probe is bounded by the table size; a probe that found no slot -- which more
+ * slots than faces rule out -- sets NERF_HIP_SIMPLIFY_TABLE_FULL in counts[3], and the result must then be discarded.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_SIMPLIFY_TABLE_FULL 1
+
+/* Bytes of workspace (256-byte aligned) of the two calls below: 4 per cell of the cluster lattice; 60 per vertex; per face 4 and 4 per
+ * slot of the face table (8 to 16 per face); and 8 per 2048 cells, vertices or faces, whichever are most. */
+int nerf_hip_mesh_simplify_ws_bytes(int64_t V, int64_t F, const int* dims3, size_t* bytes);
+
+/* Everything up to counts (DEVICE int64[6], see 8.).  lo3, cell3, dims3: HOST arrays.  normals may be NULL. */
+int nerf_hip_mesh_simplify_count(const float* verts, const float* normals, const int32_t* faces, int64_t V, int64_t F, const float* lo3,
+                                 const float* cell3, const int* dims3, void* ws, size_t ws_bytes, int64_t* counts, void* stream);
+
+/* After the count call, with the same faces, sizes, lattice and workspace: out_verts[max_v][3], out_normals[max_v][3] (NULL: none; only
+ * meaningful when the count call had normals) and out_faces[max_f][3]; max_v / max_f are the capacities in rows. */
+int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws,
+                                size_t ws_bytes, float* out_verts, float* out_normals, int32_t* out_faces, int64_t max_v, int64_t max_f,
+                                void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

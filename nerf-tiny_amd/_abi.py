@@ -20,6 +20,7 @@ SPLIT_MLP = 1 << 4
 CORRECTED = 1 << 5
 STATUS_RESAMPLE_INDEX = 1 << 0
 STATUS_PREP_TIMEOUT = 1 << 1
+SIMPLIFY_TABLE_FULL = 1 << 0
 
 _p = C.c_void_p
 _PROTOS = {
@@ -69,6 +70,9 @@ _PROTOS = {
     "nerf_hip_mesh_cc_stats": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_int64, _p]),
     "nerf_hip_mesh_cc_compact": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p,
                                            C.c_int64, C.c_int64, _p, _p]),
+    "nerf_hip_mesh_simplify_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, _p, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_simplify_count": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_mesh_simplify_emit": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, C.c_int64, C.c_int64, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -140,6 +144,17 @@ def mesh_cc_ws_bytes(V: int, F: int) -> int:
     """Workspace bytes of the nerf_hip_mesh_cc_* calls on a mesh of V vertices and F faces."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_cc_ws_bytes(int(V), int(F), C.byref(n)))
+    return int(n.value)
+
+
+def i32_array(values) -> "C.Array":
+    return (C.c_int * len(values))(*[int(v) for v in values])
+
+
+def mesh_simplify_ws_bytes(V: int, F: int, dims) -> int:
+    """Workspace bytes of nerf_hip_mesh_simplify_count / _emit on a mesh of V vertices and F faces over a cluster lattice of dims cells."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_simplify_ws_bytes(int(V), int(F), i32_array(dims), C.byref(n)))
     return int(n.value)
 
 

@@ -1781,6 +1781,145 @@ int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const flo
 
 namespace {
 
+// Workspace of the simplification calls.  Per cell of the cluster lattice 4 bytes (occupancy, then cluster ids); per vertex 60: its
+// cell / cluster (4), and per possible cluster -- there are at most V -- the member count (4), the coordinate and normal sums (24
+// each) and the referenced mark / output id (4); per face 4 (state) and the face table's 4 bytes per slot (the power of two >= 2 F:
+// 8 to 16 bytes per face); and 8 bytes per CC_PTS cells, vertices or faces, whichever are most (the scans).
+struct MsLayout {
+  size_t occ, vcl, cnt, S, T, ref, fstate, table, tot, base, scratch, total;
+  long long ncell, slots;
+};
+MsLayout ms_layout(long long V, long long F, const int* dims3) {
+  MsLayout L;
+  L.ncell = (long long)dims3[0] * dims3[1] * dims3[2];
+  L.slots = ms_table_slots(F);
+  long long most = L.ncell > V ? L.ncell : V;
+  most = most > F ? most : F;
+  const int nb = cc_blocks(most);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
+  L.occ = take((size_t)L.ncell * 4);
+  L.vcl = take((size_t)V * 4);
+  L.cnt = take((size_t)V * 4);
+  L.S = take((size_t)V * 24);
+  L.T = take((size_t)V * 24);
+  L.ref = take((size_t)V * 4);
+  L.fstate = take((size_t)F * 4);
+  L.table = take((size_t)L.slots * 4);
+  L.tot = take((size_t)nb * 4);
+  L.base = take((size_t)nb * 4);
+  L.scratch = take(8);
+  L.total = o;
+  return L;
+}
+
+int check_ms_dims(const int* dims3) {
+  if (!dims3) return fail(NERF_HIP_ERR_ARG, "dims3 is null");
+  long long n = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (dims3[c] < 1 || dims3[c] > 2048) return fail(NERF_HIP_ERR_ARG, "dims[%d]=%d: the cluster lattice has 1 .. 2048 cells per axis", c, dims3[c]);
+    n *= dims3[c];
+  }
+  if (n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "dims=(%d, %d, %d): the cluster lattice must stay below 2^31 cells", dims3[0], dims3[1], dims3[2]);
+  return NERF_HIP_OK;
+}
+
+int check_ms(int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, const void* ws, size_t ws_bytes, MsLayout* L) {
+  if (int rc = check_cc_sizes(V, F)) return rc;
+  if (int rc = check_ms_dims(dims3)) return rc;
+  if (!lo3 || !cell3) return fail(NERF_HIP_ERR_ARG, "lo3 / cell3 is null");
+  for (int c = 0; c < 3; ++c) {
+    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the cluster lattice's corner must be finite", c, (double)lo3[c]);
+    if (!(cell3[c] > 0.0f) || !isfinite(cell3[c]))
+      return fail(NERF_HIP_ERR_ARG, "cell[%d]=%g: the cluster lattice's cells must be > 0 and finite", c, (double)cell3[c]);
+  }
+  *L = ms_layout(V, F, dims3);
+  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
+  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
+  return NERF_HIP_OK;
+}
+
+MsArgs ms_args(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws, const MsLayout& L) {
+  MsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.cell[c] = cell3[c];
+    a.dims[c] = dims3[c];
+  }
+  a.ncell = L.ncell;
+  a.slots = L.slots;
+  a.occ = at<int>(ws, L.occ);
+  a.vcl = at<int>(ws, L.vcl);
+  a.cnt = at<int>(ws, L.cnt);
+  a.S = at<long long>(ws, L.S);
+  a.T = at<long long>(ws, L.T);
+  a.ref = at<int>(ws, L.ref);
+  a.fstate = at<int>(ws, L.fstate);
+  a.table = at<int>(ws, L.table);
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  a.scratch = at<long long>(ws, L.scratch);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_simplify_ws_bytes(int64_t V, int64_t F, const int* dims3, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_cc_sizes(V, F)) return rc;
+  if (int rc = check_ms_dims(dims3)) return rc;
+  *bytes = ms_layout(V, F, dims3).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_simplify_count(const float* verts, const float* normals, const int32_t* faces, int64_t V, int64_t F, const float* lo3,
+                                 const float* cell3, const int* dims3, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+  MsLayout L;
+  if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
+  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
+  if (int rc = check_device()) return rc;
+  MsArgs a = ms_args(faces, V, F, lo3, cell3, dims3, ws, L);
+  a.verts = verts;
+  a.normals = normals;
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_ms_count(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws,
+                                size_t ws_bytes, float* out_verts, float* out_normals, int32_t* out_faces, int64_t max_v, int64_t max_f,
+                                void* stream) {
+  MsLayout L;
+  if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (max_v > 0 && !out_verts) return fail(NERF_HIP_ERR_ARG, "out_verts is null");
+  if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
+  if (int rc = check_device()) return rc;
+  MsArgs a = ms_args(faces, V, F, lo3, cell3, dims3, ws, L);
+  a.out_verts = out_verts;
+  a.out_normals = out_normals;
+  a.out_faces = out_faces;
+  a.max_v = max_v;
+  a.max_f = max_f;
+  HIP_TRY(launch_ms_emit(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
 int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
   if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);

@@ -468,6 +468,45 @@ hipError_t launch_cc_ids(const CcArgs& a, hipStream_t st);                // roo
 hipError_t launch_cc_stats(const CcStatsArgs& a, hipStream_t st);
 hipError_t launch_cc_compact(const CcCompactArgs& a, hipStream_t st);     // the kept vertices' scan and placement, then the kept faces'
 
+// ---- simplification of an indexed mesh by uniform vertex clustering (mesh_simplify.hip; nerf_hip_mesh_simplify_*, DESIGN.md
+// section 3h-4).  The kernels use the component calls' workgroup shape (CC_WG, CC_PTS). ----
+constexpr long long MS_MAX_SLOTS = 1ll << 31;  // the face table's slots are indexed by int32
+
+// slots of the face table: the power of two that is at least 2 F (at least 2), capped at MS_MAX_SLOTS -- above F = 2^30 the table is
+// between F and 2 F slots, still more than the keys it can hold
+inline long long ms_table_slots(long long F) {
+  long long s = 2;
+  while (s < 2 * F && s < MS_MAX_SLOTS) s <<= 1;
+  return s;
+}
+
+struct MsArgs {
+  const float *verts, *normals;  // [V][3]; normals may be null (count only)
+  const int* faces;        // [F][3]
+  int V, F;
+  float lo[3], cell[3];    // the cluster lattice
+  int dims[3];
+  long long ncell;         // dims[0] * dims[1] * dims[2] < 2^31
+  long long slots;         // ms_table_slots(F)
+  // workspace
+  int* occ;                // [ncell] 1 where a vertex lies in the cell; after the scan the cell's cluster id + 1 (0: empty)
+  int* vcl;                // [V] the vertex's cell, then (k_ms_accum) its cluster id; -1 for a vertex in no cluster
+  int* cnt;                // [V] members of a cluster (clusters are at most V)
+  long long *S, *T;        // [V][3] fixed-point sums of the members' lattice coordinates / normals
+  int* ref;                // [V] 1 where a kept face uses the cluster; after the scan its output vertex id + 1 (0: dropped)
+  int* fstate;             // [F] the face's table slot or -1 (k_ms_faces), then 1 for a kept face and 0 for any other (k_ms_mark)
+  int* table;              // [slots] face indices, -1 for an empty slot
+  int *tot, *base;         // [cc_blocks(max(ncell, V, F))]
+  long long* scratch;      // [1] emit's throw-away total
+  long long* counts;       // [6] = V', F', occupied clusters, flags, degenerate faces, duplicate faces (count only)
+  float *out_verts, *out_normals;  // [max_v][3] (emit only; out_normals may be null)
+  int* out_faces;          // [max_f][3]
+  long long max_v, max_f;
+};
+
+hipError_t launch_ms_count(const MsArgs& a, hipStream_t st);  // everything up to counts
+hipError_t launch_ms_emit(const MsArgs& a, hipStream_t st);   // positions / normals of the referenced clusters, the kept faces
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

@@ -51,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-band", type=int, default=None, metavar="R",
                     help="--mesh evaluates the field only in a band of R^3-point blocks around the surface (R >= 2; narrow-band grid: the "
                          "same mesh wherever the band finds the surface, a component smaller than a block can be missed; default: dense)")
+    ap.add_argument("--mesh-simplify", type=int, default=None, metavar="K",
+                    help="--mesh simplifies the mesh on the device by vertex clustering in cells of K lattice steps (K >= 2; roughly 1 / K^2 "
+                         "of the faces), after the floaters are dropped and before normals and colours are queried (default: no simplification)")
     ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
                     help="--mesh drops the floaters: connected components of fewer than N faces, labelled and removed on the device before "
                          "normals and colours are queried (with --mesh-band the band may already have missed islands smaller than a block; "
@@ -110,4 +113,5 @@ if __name__ == "__main__":
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:
         run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
-                         band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest)
+                         band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
+                         simplify=args.mesh_simplify)

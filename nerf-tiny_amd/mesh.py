@@ -1,6 +1,7 @@
 """Triangle meshes of the field's isosurfaces (not in the reference): marching cubes over a device density grid (HIP kernels,
 csrc/mesh.hip), connected components on the device -- label, measure and drop the floaters (csrc/mesh_cc.hip,
-DESIGN.md section 3h-3) -- and a binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
+DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the device (csrc/mesh_simplify.hip)
+and a binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -86,6 +87,59 @@ def filter_components(m, comps, keep):
     F1 = int(comps.n_faces[keep].sum())
     v, f, n, c, _ = ops.mesh_compact(m.verts, m.faces, m.normals, m.rgb, comps.vert_comp, comps.face_comp, keep, V1, F1)
     return Mesh(v, f, n, c)
+
+
+SIMPLIFY_MAX_DIM = 2048  # cells per axis of a cluster lattice (include/nerf_hip.h)
+
+
+def simplify_lattice(verts, cell, lo=None):
+    """The default cluster lattice of simplify(): (lo [3] fp32, cell [3] fp32, dims [3] int) as numpy arrays.  Over the vertices whose
+    three coordinates are finite, lo = the per-axis minimum (unless lo is given) and, with hi the per-axis maximum,
+    dims = clamp(floor(fp32(fp32(hi - lo) / cell)) + 1, 1, 2048) -- the cell rule of include/nerf_hip.h applied to hi, so every finite
+    vertex lies in the cell of its own coordinates unless an axis needs more than 2048 cells (the clamp then pulls the rest into the
+    last one).  A mesh without a finite vertex gets lo = 0 (unless given) and dims = 1."""
+    cell32 = np.broadcast_to(np.asarray(cell, dtype=np.float32), (3,)).copy()
+    v = torch.as_tensor(verts).to(torch.float32).reshape(-1, 3)
+    ok = torch.isfinite(v).all(1, keepdim=True)
+    if not bool(ok.any()):
+        return (np.zeros(3, np.float32) if lo is None else np.asarray(lo, np.float32).reshape(3)), cell32, np.ones(3, np.int64)
+    inf = torch.full_like(v, float("inf"))
+    if lo is None:
+        lo = torch.where(ok, v, inf).amin(0).cpu().numpy()
+    lo = np.asarray(lo, np.float32).reshape(3)
+    hi = torch.where(ok, v, -inf).amax(0).cpu().numpy()
+    with np.errstate(all="ignore"):
+        u = ((hi - lo).astype(np.float32) / cell32).astype(np.float32)
+        dims = np.clip(np.floor(u.astype(np.float64)) + 1, 1, SIMPLIFY_MAX_DIM)
+    return lo, cell32, np.where(np.isnan(dims), 1, dims).astype(np.int64)
+
+
+def simplify(m, cell, lo=None, dims=None):
+    """The Mesh m simplified on the DEVICE by uniform vertex clustering (Rossignac-Borrel): the vertices in one cell of a regular
+    lattice merge into one vertex at their mean, faces that lose a corner this way or repeat an earlier face go.  Any indexed mesh.
+    cell: the cell size, a float or three (> 0); lo: the lattice's corner (three floats), dims: its cells per axis (three ints in
+    1 .. 2048, product < 2^31) -- by default simplify_lattice(m.verts, cell, lo), which covers the finite vertices; vertices outside a
+    given lattice are pulled to its faces.  Returns (Mesh, info): verts, faces, normals (the members' normals summed and normalised;
+    None when m has none) and rgb=None -- colours are not carried, query the field at the new vertices --; info = dict(verts_in,
+    faces_in, verts_out, faces_out, clusters, degenerate_faces, duplicate_faces, lo, cell, dims).  A face whose three corners fall into
+    the same three cells in the OPPOSITE orientation of an earlier one is kept: a collapsed thin sheet seen from both sides.  The
+    exact rules are in include/nerf_hip.h; every output is a pure function of the input (identical bits from run to run).  A CPU
+    tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = torch.as_tensor(m.verts), torch.as_tensor(m.faces)
+    if verts.device.type != "cuda":
+        raise RuntimeError("simplify runs only on a ROCm device (MI355X): move the mesh to 'cuda'; there is no CPU path")
+    cell32 = np.broadcast_to(np.asarray(cell, dtype=np.float32), (3,)).copy()
+    if lo is None or dims is None:
+        dlo, _, ddims = simplify_lattice(verts, cell32, lo)
+        lo = dlo
+        dims = ddims if dims is None else dims
+    lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+    dims3 = [int(d) for d in np.asarray(dims).reshape(3)]
+    v, f, n, info = ops.mesh_simplify(verts, faces, m.normals, lo32.tolist(), cell32.tolist(), dims3)
+    info.update(lo=lo32, cell=cell32, dims=tuple(dims3))
+    return Mesh(v, f, n, None), info
 
 
 def _np(a):

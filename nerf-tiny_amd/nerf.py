@@ -613,7 +613,7 @@ class NeRFModel(nn.Module):
         return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
 
     @torch.no_grad()
-    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None):
+    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -629,13 +629,21 @@ class NeRFModel(nn.Module):
         the mesh's connected components are labelled on the device (mesh.components) and only those with at least n faces and, with k,
         among the k with the most faces stay (mesh.select_components, mesh.filter_components).  This happens BEFORE the field normals and
         the colours are queried, so a dropped vertex is never evaluated; the result is, bit for bit, filter_components applied to the
-        unfiltered call.  With band=: the band may already have missed islands smaller than a block; filtering removes the rest."""
+        unfiltered call.  With band=: the band may already have missed islands smaller than a block; filtering removes the rest.
+        simplify=None: nothing more.  simplify=k (an int >= 2): the mesh is simplified on the device by vertex clustering in cells of k
+        lattice steps (mesh.simplify with lo = the grid's lo, cell = fp32(k * step) -- 1 along an axis of one lattice point -- and
+        dims = max(1, ceil((n - 1) / k)) per axis): a mesh of roughly 1 / k^2 of the faces.  It runs after marching cubes and after the
+        component filter (min_faces still counts the original faces) and BEFORE the field normals and the colours, which are then
+        queried at the new vertices only; with normals="grid" the normals are the clusters' summed and normalised grid normals.  The
+        result is, bit for bit, mesh.simplify of the unsimplified call's mesh with normals and colours made at its vertices."""
         import numpy as np
 
         from . import mesh
 
         if normals not in ("grid", "field"):
             raise ValueError(f"normals={normals!r}: 'grid' or 'field'")
+        if simplify is not None and (int(simplify) != simplify or int(simplify) < 2):
+            raise ValueError(f"simplify={simplify!r}: None or an int >= 2 (cells of that many lattice steps)")
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
@@ -646,6 +654,9 @@ class NeRFModel(nn.Module):
             comps = mesh.components(faces, len(verts), verts)
             keep = mesh.select_components(comps, 1 if min_faces is None else min_faces, keep_largest)
             verts, faces, nrm, _ = mesh.filter_components(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), comps, keep)
+        if simplify is not None:
+            cell, dims = simplify_lattice_of_grid(grid_step(lo32, hi32, shape), shape, int(simplify))
+            (verts, faces, nrm, _), _ = mesh.simplify(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), cell, lo32, dims)
         if normals == "field":
             nrm = field_normals(self.query_grad(verts)[2])
         rgb = self.query(verts, -nrm)[0] if color else None
@@ -715,6 +726,17 @@ def grid_step(lo32, hi32, shape):
     n1 = np.asarray([max(n - 1, 1) for n in shape], dtype=np.float32)
     step = (np.asarray(hi32, dtype=np.float32) - np.asarray(lo32, dtype=np.float32)) / n1
     return np.where(np.asarray(shape) > 1, step, np.float32(0.0)).astype(np.float32)
+
+
+def simplify_lattice_of_grid(step, shape, k: int):
+    """The cluster lattice of extract_mesh(simplify=k) over a density grid of ``shape`` points and fp32 ``step``: cells of k lattice
+    steps -> (cell [3] fp32 = fp32(k * step), 1 along an axis of one point, dims [3] = max(1, ceil((n - 1) / k)))."""
+    import numpy as np
+
+    step = np.asarray(step, dtype=np.float32).reshape(3)
+    cell = np.where(np.asarray(shape) > 1, (np.float32(k) * step).astype(np.float32), np.float32(1.0)).astype(np.float32)
+    dims = [max(1, -(-(int(n) - 1) // int(k))) for n in shape]
+    return cell, dims
 
 
 def fuse_plan(near_far0, n: int, batch: int, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):

@@ -263,6 +263,44 @@ def mesh_compact(verts, faces, normals, rgb, vert_comp, face_comp, keep, max_v, 
     return ov, of, on, oc, counts
 
 
+def mesh_simplify(verts, faces, normals, lo, cell, dims, ws=None, counts=None):
+    """Uniform vertex clustering of the indexed mesh (verts[V, 3] fp32, faces[F, 3] int32, normals[V, 3] fp32 or None; device) over the
+    cluster lattice lo / cell (three host floats each) / dims (three host ints): nerf_hip_mesh_simplify_count, one 48-byte read of the
+    device counts (this synchronises with the stream), then nerf_hip_mesh_simplify_emit into buffers sized from them; the definition
+    is in include/nerf_hip.h.  -> (verts[V', 3], faces[F', 3] int32, normals[V', 3] or None, info) with info = dict(verts_in, faces_in,
+    verts_out, faces_out, clusters, degenerate_faces, duplicate_faces).  A face table that reports itself full raises NerfHipError:
+    there is no partial result.  ws: a uint8 device buffer of >= _abi.mesh_simplify_ws_bytes(V, F, dims) bytes; counts: an int64 [6]
+    device tensor; each is allocated here if None."""
+    faces, V, F = _cc_faces(faces, verts.shape[0])
+    dev = faces.device
+    f32 = lambda a: None if a is None else a.to(torch.float32).contiguous()
+    verts, normals = f32(verts), f32(normals)
+    for a in (verts, normals):
+        if a is not None and (tuple(a.shape) != (V, 3) or a.device != dev):
+            raise ValueError(f"a per-vertex array {tuple(a.shape)} on {a.device}: [{V}, 3] on {dev}")
+    lo3, cell3, dims3 = _abi.f32_array(lo), _abi.f32_array(cell), _abi.i32_array(dims)
+    if len(lo3) != 3 or len(cell3) != 3 or len(dims3) != 3:
+        raise ValueError("lo, cell and dims have three entries each")
+    if ws is None:
+        ws = torch.empty(max(_abi.mesh_simplify_ws_bytes(V, F, dims), 1), dtype=torch.uint8, device=dev)
+    if counts is None:
+        counts = torch.empty(6, dtype=torch.int64, device=dev)
+    L, st = _abi.lib(), _stream(faces)
+    ptr = lambda a: None if a is None else a.data_ptr()
+    _abi.check(L.nerf_hip_mesh_simplify_count(ptr(verts), ptr(normals), faces.data_ptr(), V, F, lo3, cell3, dims3, ws.data_ptr(), ws.numel(),
+                                              counts.data_ptr(), st))
+    V1, F1, clusters, flags, n_deg, n_dup = (int(n) for n in counts.cpu())
+    if flags & _abi.SIMPLIFY_TABLE_FULL:
+        raise _abi.NerfHipError(f"mesh_simplify: the face table reported itself full (V={V} F={F}); no result")
+    ov = torch.empty(V1, 3, device=dev)
+    on = torch.empty(V1, 3, device=dev) if normals is not None else None
+    of = torch.empty(F1, 3, dtype=torch.int32, device=dev)
+    _abi.check(L.nerf_hip_mesh_simplify_emit(faces.data_ptr(), V, F, lo3, cell3, dims3, ws.data_ptr(), ws.numel(), ptr(ov), ptr(on),
+                                             of.data_ptr(), V1, F1, st))
+    info = dict(verts_in=V, faces_in=F, verts_out=V1, faces_out=F1, clusters=clusters, degenerate_faces=n_deg, duplicate_faces=n_dup)
+    return ov, of, on, info
+
+
 def image_metrics(pred, gt, ws=None):
     """Per-view MSE and SSIM (nerf_hip_image_metrics, fp64 arithmetic; definition in include/nerf_hip.h): pred, gt [n, H, W, 3] device
     tensors of the same shape and device (cast to contiguous fp32 here) -> (mse[n], ssim[n]) fp64 on that device.  ws: a uint8 device
