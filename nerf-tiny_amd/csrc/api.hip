@@ -1,41 +1,20 @@
-// api.hip -- the extern "C" surface of libnerf_hip.so (include/nerf_hip.h).  Host code only: argument
-// checks, workspace carve-up and kernel sequencing on the caller's stream.  No allocation, no host sync
-// (except nerf_hip_read_status).
-#include "../../include/nerf_hip.h"
-
-#include <stdarg.h>
-#include <stdio.h>
+// api.hip -- the render, training and profiling part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h; the queries,
+// grids, meshes and metrics are in api_geometry.hip).  Host code only: argument checks, workspace carve-up and kernel sequencing on
+// the caller's stream.  No allocation, no host sync (except nerf_hip_read_status).
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <atomic>
 #include <mutex>
 
+#include "api_common.h"
 #include "bf16_common.h"
-#include "kernels.h"
 
 using namespace nerf;
 
+thread_local char nerf::g_err[512] = "";
+
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(NERF_HIP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int next_pow2(int n) {
   int p = 2;
@@ -133,96 +112,68 @@ WsLayout layout(int B, int Nc, int Nf, int flags) {
   WsLayout L;
   memset(&L, 0, sizeof(L));
   const size_t b = (size_t)B, N = (size_t)Nc + Nf;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L.status = take(256);
-  L.dbg = take(DBG_WORDS * 8);  // diagnostic builds (-DNERF_STAMPS) write cycle stamps here; untouched otherwise
-  L.packed = take((size_t)PACKED_ALL_F4 * 16);
-  if (flags & NERF_HIP_BF16_MLP) L.packed_bf = take(BF_IMAGE_BYTES);
-  if ((flags & NERF_HIP_SPLIT_MLP) && !(flags & NERF_HIP_BF16_MLP)) L.packed_sp = take(split_image_bytes());
-  L.fold = take((FOLD_FLOATS + PREP_READY_WORDS) * 4);  // + the "fold row o is out" words of the one-launch preparation (prep_bf16.hip)
-  L.rayf = take(b * RAYF * 4);
-  L.dvec = take(b * HALF * 4);
-  L.t_c = take(b * Nc * 4);
-  L.sig_c = take(b * Nc * 4);
-  L.rgb_c = take(b * Nc * 12);
-  L.w_c = take(b * Nc * 4);
-  L.t_f = take(b * Nf * 4);
-  L.sig_f = take(b * Nf * 4);
-  L.rgb_f = take(b * Nf * 12);
+  Carve c;
+  L.status = c.take(256);
+  L.dbg = c.take(DBG_WORDS * 8);  // diagnostic builds (-DNERF_STAMPS) write cycle stamps here; untouched otherwise
+  L.packed = c.take((size_t)PACKED_ALL_F4 * 16);
+  if (flags & NERF_HIP_BF16_MLP) L.packed_bf = c.take(BF_IMAGE_BYTES);
+  if ((flags & NERF_HIP_SPLIT_MLP) && !(flags & NERF_HIP_BF16_MLP)) L.packed_sp = c.take(split_image_bytes());
+  L.fold = c.take((FOLD_FLOATS + PREP_READY_WORDS) * 4);  // + the "fold row o is out" words of the one-launch preparation (prep_bf16.hip)
+  L.rayf = c.take(b * RAYF * 4);
+  L.dvec = c.take(b * HALF * 4);
+  L.t_c = c.take(b * Nc * 4);
+  L.sig_c = c.take(b * Nc * 4);
+  L.rgb_c = c.take(b * Nc * 12);
+  L.w_c = c.take(b * Nc * 4);
+  L.t_f = c.take(b * Nf * 4);
+  L.sig_f = c.take(b * Nf * 4);
+  L.rgb_f = c.take(b * Nf * 12);
   if (flags & NERF_HIP_SAVE_FOR_BACKWARD) {
-    L.perm = take(b * 5 * N * 2);
-    L.w_m = take(b * N * 4);
-    L.bundle = take(b * N * 5 * 4);
+    L.perm = c.take(b * 5 * N * 2);
+    L.w_m = c.take(b * N * 4);
+    L.bundle = c.take(b * N * 5 * 4);
     const size_t Mtot = b * N;
     const size_t tiles = (b * Nc + TM - 1) / TM + (b * Nf + TM - 1) / TM;
-    L.spre = take(Mtot * 4);
+    L.spre = c.take(Mtot * 4);
     if (flags & NERF_HIP_BF16_MLP) {
       const size_t wb = wave_blocks(B, Nc) + wave_blocks(B, Nf);
-      L.packed_bf_bwd = take(BB_IMAGE_BYTES);
-      L.bsave = take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
-      L.bmask = take(wb * BM_LAYERS * 1024);
-      L.bG = take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
-      L.bslabs = take(dw_bf16_slab_floats() * 4);
-      L.mbuf = take((size_t)HALF * WIDTH * 4);
+      L.packed_bf_bwd = c.take(BB_IMAGE_BYTES);
+      L.bsave = c.take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
+      L.bmask = c.take(wb * BM_LAYERS * 1024);
+      L.bG = c.take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
+      L.bslabs = c.take(dw_bf16_slab_floats() * 4);
+      L.mbuf = c.take((size_t)HALF * WIDTH * 4);
     } else if (flags & NERF_HIP_SPLIT_MLP) {
       // split-fp32 training: the bf16 variant's fragment-layout buffers twice (hi parts, mid parts)
       const size_t wb = wave_blocks(B, Nc) + wave_blocks(B, Nf);
-      L.packed_sp_bwd = take(split_bwd_image_bytes());
-      L.bsave = take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
-      L.bsave2 = take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
-      L.bmask = take(wb * BM_LAYERS * 1024);
-      L.bG = take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
-      L.bG2 = take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
-      L.bslabs = take(dw_bf16_slab_floats() * 4);
-      L.mbuf = take((size_t)HALF * WIDTH * 4);
+      L.packed_sp_bwd = c.take(split_bwd_image_bytes());
+      L.bsave = c.take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
+      L.bsave2 = c.take(wb * BS_TOTAL_KS * BF_FRAG_BYTES);
+      L.bmask = c.take(wb * BM_LAYERS * 1024);
+      L.bG = c.take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
+      L.bG2 = c.take(wb * BG_TOTAL_KS * BF_FRAG_BYTES);
+      L.bslabs = c.take(dw_bf16_slab_floats() * 4);
+      L.mbuf = c.take((size_t)HALF * WIDTH * 4);
     } else {
-      L.save = take((size_t)NSAVE * (Mtot + DUMP_ROWS) * WIDTH * 4);  // + dump rows (kernels.h: MSrows)
-      L.masks = take((size_t)8 * tiles * 4 * 256 * 2);
-      L.G = take((size_t)NGRAD * (Mtot + DUMP_ROWS) * WIDTH * 4);
-      L.dz = take(Mtot * 16);
-      L.dspre = take(Mtot * 4);
-      L.slabs = take(dw_batch_slab_floats() * 4);  // every product of the step keeps its own slabs: ONE reduce launch at the end
-      L.sbuf = take(2 * b * HALF * 4);
-      L.gdbuf = take(b * DIR_DIM * 4);
-      L.mbuf = take((size_t)HALF * WIDTH * 4);
+      L.save = c.take((size_t)NSAVE * (Mtot + DUMP_ROWS) * WIDTH * 4);  // + dump rows (kernels.h: MSrows)
+      L.masks = c.take((size_t)8 * tiles * 4 * 256 * 2);
+      L.G = c.take((size_t)NGRAD * (Mtot + DUMP_ROWS) * WIDTH * 4);
+      L.dz = c.take(Mtot * 16);
+      L.dspre = c.take(Mtot * 4);
+      L.slabs = c.take(dw_batch_slab_floats() * 4);  // every product of the step keeps its own slabs: ONE reduce launch at the end
+      L.sbuf = c.take(2 * b * HALF * 4);
+      L.gdbuf = c.take(b * DIR_DIM * 4);
+      L.mbuf = c.take((size_t)HALF * WIDTH * 4);
     }
-    L.drgb_c = take(b * Nc * 12);
-    L.dsig_c = take(b * Nc * 4);
-    L.drgb_f = take(b * Nf * 12);
-    L.dsig_f = take(b * Nf * 4);
-    L.dt_f = take(b * Nf * 4);
-    L.dC = take(b * 9 * 4);  // nerf_hip_train_step: d loss / d C_coarse, d loss / d C_fine, the loss's summands ([B][3] each)
+    L.drgb_c = c.take(b * Nc * 12);
+    L.dsig_c = c.take(b * Nc * 4);
+    L.drgb_f = c.take(b * Nf * 12);
+    L.dsig_f = c.take(b * Nf * 4);
+    L.dt_f = c.take(b * Nf * 4);
+    L.dC = c.take(b * 9 * 4);  // nerf_hip_train_step: d loss / d C_coarse, d loss / d C_fine, the loss's summands ([B][3] each)
   }
-  L.total = o;
+  L.total = c.o;
   return L;
-}
-
-int check_device() {
-  static thread_local int checked_dev = -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev == checked_dev) return NERF_HIP_OK;
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, dev));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(NERF_HIP_ERR_ARCH, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
-  checked_dev = dev;
-  return NERF_HIP_OK;
-}
-
-int check_weights(const float* const* w) {
-  if (!w) return fail(NERF_HIP_ERR_ARG, "weights24 is null");
-  for (int i = 0; i < 24; ++i) {
-    if (!w[i]) return fail(NERF_HIP_ERR_ARG, "weights24[%d] is null", i);
-    if (((uintptr_t)w[i] & 15) != 0) return fail(NERF_HIP_ERR_ARG, "weights24[%d] is not 16-byte aligned", i);
-  }
-  return NERF_HIP_OK;
-}
-
-Weights24 as_w24(const float* const* w) {
-  Weights24 r;
-  for (int i = 0; i < 24; ++i) r.p[i] = w[i];
-  return r;
 }
 
 // ---- optional per-kernel HIP-event timing (bench.py's roofline leg); off by default ----
@@ -277,11 +228,6 @@ struct ProfScope {
     if (chain) chain->last = stop;  // (null when this phase was not recorded: the next one records its own start)
   }
 };
-
-template <class T>
-T* at(void* ws, size_t off) {
-  return reinterpret_cast<T*>(static_cast<unsigned char*>(ws) + off);
-}
 
 }  // namespace
 
@@ -358,9 +304,8 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
   const WsLayout L = layout(B, Nc, Nf, flags);
-  if (ws_bytes < L.total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
   if (int rc = check_device()) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool save = (flags & NERF_HIP_SAVE_FOR_BACKWARD) != 0;
@@ -1123,862 +1068,6 @@ int nerf_hip_merge_composite(const float* t_c, const float* t_f, const float* si
   ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
   ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine;
   HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the point queries: the packed weight image, the fold, and (colour queries) the dvec rows of ONE chunk of QUERY_CHUNK points.
-// Nothing in it depends on the number of points or the grid size.
-struct QueryLayout {
-  size_t packed, fold, dvec, total;
-};
-QueryLayout query_layout(bool rgb) {
-  QueryLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L.packed = take((size_t)PACKED_ALL_F4 * 16);  // (the extent the register kernels' buffer resource declares: reg_buf)
-  L.fold = take((size_t)FOLD_FLOATS * 4);
-  L.dvec = rgb ? take((size_t)QUERY_CHUNK * HALF * 4) : 0;
-  L.total = o;
-  return L;
-}
-
-int check_query_ws(const QueryLayout& L, const void* ws, size_t ws_bytes) {
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L.total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-  return NERF_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_query_ws_bytes(int with_rgb, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  *bytes = query_layout(with_rgb != 0).total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_query(const float* const* weights24, const float* points, const float* dirs, int M, float* rgb, float* sigma, void* ws,
-                   size_t ws_bytes, void* stream) {
-  if (M < 0) return fail(NERF_HIP_ERR_ARG, "M=%d < 0", M);
-  if ((dirs == nullptr) != (rgb == nullptr)) return fail(NERF_HIP_ERR_ARG, "dirs and rgb must both be null (sigma only) or both be set");
-  const bool with_rgb = dirs != nullptr;
-  if (M == 0) return NERF_HIP_OK;
-  if (int rc = check_weights(weights24)) return rc;
-  if (!points || !sigma) return fail(NERF_HIP_ERR_ARG, "null argument");
-  const QueryLayout L = query_layout(with_rgb);
-  if (int rc = check_query_ws(L, ws, ws_bytes)) return rc;
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Weights24 w = as_w24(weights24);
-  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
-  FieldArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.wp = at<float4>(ws, L.packed);
-  fa.w = w;
-  QuerySrc q;
-  memset(&q, 0, sizeof(q));
-  if (!with_rgb) {
-    fa.sigma = sigma;
-    fa.M = M;
-    q.points = points;
-    HIP_TRY(launch_query_reg(fa, q, false, st));
-    return NERF_HIP_OK;
-  }
-  // colour: chunk by chunk through the workspace's dvec rows (stream order: a chunk's rows are consumed before the next chunk writes them)
-  fa.dvec = at<float>(ws, L.dvec);
-  for (int off = 0; off < M; off += QUERY_CHUNK) {
-    const int n = (M - off < QUERY_CHUNK) ? M - off : QUERY_CHUNK;
-    HIP_TRY(launch_dirs_dvec(dirs + (size_t)off * 3, n, w.p[W_DIR], w.p[B_DIR], at<float>(ws, L.fold), at<float>(ws, L.dvec), st));
-    fa.rgb = rgb + (size_t)off * 3;
-    fa.sigma = sigma + off;
-    fa.M = n;
-    q.points = points + (size_t)off * 3;
-    HIP_TRY(launch_query_reg(fa, q, true, st));
-    if (M - off <= QUERY_CHUNK) break;  // (off + QUERY_CHUNK could pass INT_MAX)
-  }
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_density_grid(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, float* sigma,
-                          void* ws, size_t ws_bytes, void* stream) {
-  if (nx < 1 || ny < 1 || nz < 1) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: every dimension must be positive", nx, ny, nz);
-  // the kernels index points with 32-bit integers, as the forward does its samples
-  if ((long long)nx * ny * nz >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: a grid must stay below 2^31 points", nx, ny, nz);
-  if (int rc = check_weights(weights24)) return rc;
-  if (!lo3 || !step3 || !sigma) return fail(NERF_HIP_ERR_ARG, "null argument");
-  const QueryLayout L = query_layout(false);
-  if (int rc = check_query_ws(L, ws, ws_bytes)) return rc;
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Weights24 w = as_w24(weights24);
-  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
-  FieldArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.wp = at<float4>(ws, L.packed);
-  fa.w = w;
-  fa.sigma = sigma;
-  fa.M = nx * ny * nz;
-  QuerySrc q;
-  memset(&q, 0, sizeof(q));
-  for (int c = 0; c < 3; ++c) {
-    q.lo[c] = lo3[c];
-    q.step[c] = step3[c];
-  }
-  q.ny = ny;
-  q.nz = nz;
-  HIP_TRY(launch_query_reg(fa, q, false, st));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the gradient queries: the packed weight image WITH the transposed segments (the chain reads them), the fold, and for ONE
-// chunk of QGRAD_CHUNK points the compact save (kernels.h QGRAD_*) and, colour queries, the dvec rows.  Independent of M.
-struct QGradLayout {
-  size_t packed, fold, dvec, save, masks, spre, total;
-};
-QGradLayout qgrad_layout(bool rgb) {
-  QGradLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  const size_t rows = (size_t)QGRAD_CHUNK + DUMP_ROWS;
-  L.packed = take((size_t)PACKED_ALL_F4 * 16);
-  L.fold = take((size_t)FOLD_FLOATS * 4);
-  L.dvec = rgb ? take((size_t)QGRAD_CHUNK * HALF * 4) : 0;
-  L.save = take(rows * (QGRAD_GP + (rgb ? QGRAD_C : 0)) * 4);
-  L.masks = take((size_t)8 * (QGRAD_CHUNK / 64) * 4 * 256 * 2);
-  L.spre = take(rows * 4);
-  L.total = o;
-  return L;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_query_grad_ws_bytes(int with_rgb, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  *bytes = qgrad_layout(with_rgb != 0).total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_query_grad(const float* const* weights24, const float* points, const float* dirs, int M, const float* dsigma, const float* drgb,
-                        float* rgb, float* sigma, float* dpoints, void* ws, size_t ws_bytes, void* stream) {
-  if (M < 0) return fail(NERF_HIP_ERR_ARG, "M=%d < 0", M);
-  if (drgb && !dirs) return fail(NERF_HIP_ERR_ARG, "drgb needs dirs: without them no colour is computed");
-  if ((dirs == nullptr) != (rgb == nullptr)) return fail(NERF_HIP_ERR_ARG, "dirs and rgb must both be null (sigma only) or both be set");
-  const bool with_rgb = dirs != nullptr;
-  if (M == 0) return NERF_HIP_OK;  // (empty buffers may have null pointers, as for nerf_hip_query)
-  if (!points || !sigma || !dpoints) return fail(NERF_HIP_ERR_ARG, "null argument (points, sigma and dpoints are required)");
-  if (int rc = check_weights(weights24)) return rc;
-  const QGradLayout L = qgrad_layout(with_rgb);
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L.total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L.total);
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Weights24 w = as_w24(weights24);
-  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG, st));
-  FieldArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.wp = at<float4>(ws, L.packed);
-  fa.w = w;
-  fa.dvec = with_rgb ? at<float>(ws, L.dvec) : nullptr;
-  fa.save = at<float>(ws, L.save);
-  fa.masks = at<uint16_t>(ws, L.masks);
-  fa.spre = at<float>(ws, L.spre);
-  fa.tiles_tot = QGRAD_CHUNK / 64;
-  fa.MSrows = (long long)QGRAD_CHUNK + DUMP_ROWS;
-  FieldBwdArgs fb;
-  memset(&fb, 0, sizeof(fb));  // G = null: the chain writes no gradient rows
-  fb.wp = fa.wp;
-  fb.w = w;
-  fb.save = fa.save;
-  fb.masks = fa.masks;
-  fb.spre = fa.spre;
-  fb.tiles_tot = fa.tiles_tot;
-  fb.MSrows = fa.MSrows;
-  QuerySrc q;
-  memset(&q, 0, sizeof(q));
-  // chunk by chunk through the workspace (stream order: the chain has read a chunk's save before the next forward overwrites it)
-  for (int off = 0; off < M; off += QGRAD_CHUNK) {
-    const int n = (M - off < QGRAD_CHUNK) ? M - off : QGRAD_CHUNK;
-    if (with_rgb) HIP_TRY(launch_dirs_dvec(dirs + (size_t)off * 3, n, w.p[W_DIR], w.p[B_DIR], at<float>(ws, L.fold), at<float>(ws, L.dvec), st));
-    fa.rgb = with_rgb ? rgb + (size_t)off * 3 : nullptr;
-    fa.sigma = sigma + off;
-    fa.M = n;
-    fa.Mtot = n;
-    q.points = points + (size_t)off * 3;
-    HIP_TRY(launch_query_grad_fwd(fa, q, with_rgb, st));
-    fb.rgb = fa.rgb;
-    fb.drgb = drgb ? drgb + (size_t)off * 3 : nullptr;
-    fb.dsig = dsigma ? dsigma + off : nullptr;
-    fb.dt = dpoints + (size_t)off * 3;
-    fb.M = n;
-    fb.Mtot = n;
-    HIP_TRY(launch_query_grad_bwd(fb, drgb != nullptr, st));  // no drgb: the colour branch adds nothing, the sigma-only chain runs
-    if (M - off <= QGRAD_CHUNK) break;  // (off + QGRAD_CHUNK could pass INT_MAX)
-  }
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the mesh calls: per lattice point its in-block vertex offset and owned-edge mask, then per workgroup of MESH_PTS points
-// its vertex / face totals and their 64-bit exclusive scans.
-struct MeshLayout {
-  size_t offs, tv, tf, bv, bf, total;
-  int nb;
-};
-MeshLayout mesh_layout(int nx, int ny, int nz) {
-  MeshLayout L;
-  const long long n = (long long)nx * ny * nz;
-  L.nb = mesh_blocks(n);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L.offs = take((size_t)n * 4);
-  L.tv = take((size_t)L.nb * 4);
-  L.tf = take((size_t)L.nb * 4);
-  L.bv = take((size_t)(L.nb + 1) * 8);
-  L.bf = take((size_t)(L.nb + 1) * 8);
-  L.total = o;
-  return L;
-}
-
-int check_mesh_grid(int nx, int ny, int nz) {
-  if (nx < 1 || ny < 1 || nz < 1) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: every dimension must be positive", nx, ny, nz);
-  // the kernels index lattice points with 32-bit integers, as the density grid does
-  if ((long long)nx * ny * nz >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d: a grid must stay below 2^31 points", nx, ny, nz);
-  return NERF_HIP_OK;
-}
-
-int check_mesh_call(const float* sigma, int nx, int ny, int nz, float level, const void* ws, size_t ws_bytes, MeshLayout* L) {
-  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
-  if (!isfinite(level)) return fail(NERF_HIP_ERR_ARG, "level %g is not finite", (double)level);
-  if (!sigma) return fail(NERF_HIP_ERR_ARG, "sigma is null");
-  *L = mesh_layout(nx, ny, nz);
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
-  return NERF_HIP_OK;
-}
-
-MeshArgs mesh_args(const float* sigma, int nx, int ny, int nz, float level, const void* ws, const MeshLayout& L) {
-  MeshArgs a;
-  memset(&a, 0, sizeof(a));
-  void* w = const_cast<void*>(ws);
-  a.sigma = sigma;
-  a.nx = nx;
-  a.ny = ny;
-  a.nz = nz;
-  a.level = level;
-  a.offs = at<unsigned>(w, L.offs);
-  a.tv = at<int>(w, L.tv);
-  a.tf = at<int>(w, L.tf);
-  a.bv = at<long long>(w, L.bv);
-  a.bf = at<long long>(w, L.bf);
-  return a;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_mesh_ws_bytes(int nx, int ny, int nz, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
-  *bytes = mesh_layout(nx, ny, nz).total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
-  MeshLayout L;
-  if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
-  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
-  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nx < 2 || ny < 2 || nz < 2) {  // no cells: the empty mesh
-    HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), st));
-    return NERF_HIP_OK;
-  }
-  MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
-  a.counts = reinterpret_cast<long long*>(counts);
-  HIP_TRY(launch_mesh_count(a, st));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
-                       size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream) {
-  MeshLayout L;
-  if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
-  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
-  const int dims[3] = {nx, ny, nz};
-  for (int c = 0; c < 3; ++c) {
-    // a step <= 0 would mirror the lattice and silently flip the winding
-    if (dims[c] > 1 && !(step3[c] > 0.0f && isfinite(step3[c])))
-      return fail(NERF_HIP_ERR_ARG, "step[%d] = %g: must be positive and finite along a dimension of more than one point", c, (double)step3[c]);
-  }
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
-  if (max_v > 0 && (!verts || !normals)) return fail(NERF_HIP_ERR_ARG, "verts / normals is null");
-  if (max_f > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
-  if (int rc = check_device()) return rc;
-  if (nx < 2 || ny < 2 || nz < 2 || (max_v == 0 && max_f == 0)) return NERF_HIP_OK;  // nothing to write
-  MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
-  for (int c = 0; c < 3; ++c) {
-    a.lo[c] = lo3[c];
-    a.step[c] = step3[c];
-  }
-  a.verts = verts;
-  a.normals = normals;
-  a.faces = faces;
-  a.max_v = max_v;
-  a.max_f = max_f;
-  HIP_TRY(launch_mesh_emit(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the narrow-band grid: the point queries' packed weight image and fold, then per block of r^3 lattice points 10 bytes
-// (the sets A and S, the new-block offsets, the list) and per BAND_WG blocks 16 more.  Nothing per lattice point.
-struct BandLayout {
-  size_t packed, fold, active, seed, offs, list, tn, tp, bn, total;
-  int r, nb[3], nblk, nwg;
-};
-constexpr int BAND_MAX_BLOCKS = 1 << 25;  // (one wave per block in k_band_reseed: the launch stays below 2^32 threads)
-
-int band_layout(int nx, int ny, int nz, int block, BandLayout* L) {
-  if (int rc = check_mesh_grid(nx, ny, nz)) return rc;
-  if (block < 2) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least 2 points along every axis", block);
-  const int nmax = nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz);
-  L->r = block < nmax ? block : (nmax > 2 ? nmax : 2);  // (any block >= the grid is one block per axis)
-  const int n[3] = {nx, ny, nz};
-  long long nblk = 1;
-  for (int c = 0; c < 3; ++c) {
-    L->nb[c] = (n[c] + L->r - 1) / L->r;
-    nblk *= L->nb[c];
-  }
-  if (nblk > BAND_MAX_BLOCKS)
-    return fail(NERF_HIP_ERR_ARG, "grid %d x %d x %d in blocks of %d: %lld blocks, at most %d (raise block)", nx, ny, nz, block, nblk, BAND_MAX_BLOCKS);
-  L->nblk = (int)nblk;
-  L->nwg = (L->nblk + BAND_WG - 1) / BAND_WG;
-  const QueryLayout Q = query_layout(false);
-  size_t o = Q.total;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L->packed = Q.packed;
-  L->fold = Q.fold;
-  L->active = take((size_t)L->nblk);
-  L->seed = take((size_t)L->nblk);
-  L->offs = take((size_t)L->nblk * 4);
-  L->list = take((size_t)L->nblk * 4);
-  L->tn = take((size_t)L->nwg * 4);
-  L->tp = take((size_t)L->nwg * 8);
-  L->bn = take((size_t)L->nwg * 4);
-  L->total = o;
-  return NERF_HIP_OK;
-}
-
-// the checks of both band calls, in the mesh calls' order: grid, block, level, pointers, workspace, counts
-int check_band_call(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
-                    const float* sigma, const void* ws, size_t ws_bytes, const int64_t* counts, BandLayout* L) {
-  if (int rc = band_layout(nx, ny, nz, block, L)) return rc;
-  if (!isfinite(level)) return fail(NERF_HIP_ERR_ARG, "level %g is not finite", (double)level);
-  if (!sigma) return fail(NERF_HIP_ERR_ARG, "sigma is null");
-  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
-  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
-  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
-  return check_weights(weights24);
-}
-
-BandArgs band_args(float* sigma, int nx, int ny, int nz, float level, void* ws, const BandLayout& L, int64_t* counts) {
-  BandArgs a;
-  memset(&a, 0, sizeof(a));
-  a.sigma = sigma;
-  a.nx = nx;
-  a.ny = ny;
-  a.nz = nz;
-  a.r = L.r;
-  a.nbx = L.nb[0];
-  a.nby = L.nb[1];
-  a.nbz = L.nb[2];
-  a.nblk = L.nblk;
-  a.nwg = L.nwg;
-  a.level = level;
-  a.active = at<unsigned char>(ws, L.active);
-  a.seed = at<unsigned char>(ws, L.seed);
-  a.offs = at<unsigned>(ws, L.offs);
-  a.list = at<int>(ws, L.list);
-  a.tn = at<int>(ws, L.tn);
-  a.tp = at<long long>(ws, L.tp);
-  a.bn = at<int>(ws, L.bn);
-  a.counts = reinterpret_cast<long long*>(counts);
-  return a;
-}
-
-void band_field_args(const Weights24& w, const float* lo3, const float* step3, int nx, int ny, int nz, float* sigma, void* ws,
-                     const BandLayout& L, FieldArgs* fa, QuerySrc* q) {
-  memset(fa, 0, sizeof(*fa));
-  fa->wp = at<float4>(ws, L.packed);
-  fa->w = w;
-  fa->sigma = sigma;
-  memset(q, 0, sizeof(*q));
-  for (int c = 0; c < 3; ++c) {
-    q->lo[c] = lo3[c];
-    q->step[c] = step3[c];
-  }
-  q->nx = nx;
-  q->ny = ny;
-  q->nz = nz;
-  q->r = L.r;
-  q->nby = L.nb[1];
-  q->nbz = L.nb[2];
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_band_ws_bytes(int nx, int ny, int nz, int block, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  BandLayout L;
-  if (int rc = band_layout(nx, ny, nz, block, &L)) return rc;
-  *bytes = L.total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_band_begin(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
-                        float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
-  BandLayout L;
-  if (int rc = check_band_call(weights24, lo3, step3, nx, ny, nz, block, level, sigma, ws, ws_bytes, counts, &L)) return rc;
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Weights24 w = as_w24(weights24);
-  HIP_TRY(launch_pack_weights(w, at<float>(ws, L.fold), at<float4>(ws, L.packed), NSEG_FWD, st));
-  FieldArgs fa;
-  QuerySrc q;
-  band_field_args(w, lo3, step3, nx, ny, nz, sigma, ws, L, &fa, &q);
-  const int n[3] = {nx, ny, nz};
-  for (int c = 0; c < 3; ++c) q.ext[c] = (n[c] - 1 + L.r - 1) / L.r + 1;  // the unique planes min(u r, n - 1)
-  fa.M = q.ext[0] * q.ext[1] * q.ext[2];  // (<= nx ny nz)
-  HIP_TRY(launch_band_corners(fa, q, st));
-  const BandArgs a = band_args(sigma, nx, ny, nz, level, ws, L, counts);
-  HIP_TRY(launch_band_begin(a, st));
-  HIP_TRY(launch_band_next(a, st));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_band_grow(const float* const* weights24, const float* lo3, const float* step3, int nx, int ny, int nz, int block, float level,
-                       int64_t n_blocks, float* sigma, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
-  BandLayout L;
-  if (int rc = check_band_call(weights24, lo3, step3, nx, ny, nz, block, level, sigma, ws, ws_bytes, counts, &L)) return rc;
-  if (n_blocks < 0 || n_blocks > L.nblk) return fail(NERF_HIP_ERR_ARG, "n_blocks=%lld: the grid has %d blocks", (long long)n_blocks, L.nblk);
-  if (int rc = check_device()) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const BandArgs a = band_args(sigma, nx, ny, nz, level, ws, L, counts);
-  FieldArgs fa;
-  QuerySrc q;
-  band_field_args(as_w24(weights24), lo3, step3, nx, ny, nz, sigma, ws, L, &fa, &q);
-  const int n[3] = {nx, ny, nz};
-  long long vol = 1;
-  for (int c = 0; c < 3; ++c) {
-    q.ext[c] = n[c] < L.r ? n[c] : L.r;
-    vol *= q.ext[c];  // (<= nx ny nz)
-  }
-  q.list = a.list;
-  q.nlist = a.counts;
-  // the listed blocks, in launches of fewer than 2^31 samples (the counts are read by these launches and rewritten only after them)
-  const long long per = ((1ll << 31) - 64) / vol;
-  for (long long e0 = 0; e0 < n_blocks; e0 += per) {
-    const long long ne = n_blocks - e0 < per ? n_blocks - e0 : per;
-    q.e0 = (int)e0;
-    fa.M = (int)(ne * vol);
-    HIP_TRY(launch_band_blocks(fa, q, st));
-  }
-  HIP_TRY(launch_band_reseed(a, st));
-  HIP_TRY(launch_band_next(a, st));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the component calls: 4 bytes per vertex (the labels L; the compaction keeps its new vertex indices there) and 8 bytes
-// per CC_PTS vertices or faces, whichever are more (a workgroup's total and its exclusive scan).
-struct CcLayout {
-  size_t L, tot, base, total;
-};
-CcLayout cc_layout(long long V, long long F) {
-  CcLayout L;
-  const int nb = cc_blocks(V > F ? V : F);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L.L = take((size_t)V * 4);
-  L.tot = take((size_t)nb * 4);
-  L.base = take((size_t)nb * 4);
-  L.total = o;
-  return L;
-}
-
-int check_cc_sizes(int64_t V, int64_t F) {
-  if (V < 0 || F < 0) return fail(NERF_HIP_ERR_ARG, "V=%lld F=%lld: counts must be >= 0", (long long)V, (long long)F);
-  // vertex indices are int32, and the kernels index faces with 32-bit integers as well
-  if (V >= (1ll << 31) || F >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "V=%lld F=%lld: a mesh must stay below 2^31 vertices and faces", (long long)V, (long long)F);
-  return NERF_HIP_OK;
-}
-
-int check_cc_ws(int64_t V, int64_t F, const void* ws, size_t ws_bytes, CcLayout* L) {
-  if (int rc = check_cc_sizes(V, F)) return rc;
-  *L = cc_layout(V, F);
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
-  return NERF_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_mesh_cc_ws_bytes(int64_t V, int64_t F, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  if (int rc = check_cc_sizes(V, F)) return rc;
-  *bytes = cc_layout(V, F).total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_cc_round(const int32_t* faces, int64_t V, int64_t F, int round, void* ws, size_t ws_bytes, int32_t* changed, void* stream) {
-  CcLayout L;
-  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
-  if (!changed) return fail(NERF_HIP_ERR_ARG, "changed is null");
-  if (((uintptr_t)changed & 3) != 0) return fail(NERF_HIP_ERR_ARG, "changed must be 4-byte aligned");
-  if (round < 0) return fail(NERF_HIP_ERR_ARG, "round=%d < 0", round);
-  if (round >= CC_MAX_ROUNDS)
-    return fail(NERF_HIP_ERR_CONVERGE, "the component labelling did not converge in %d rounds (V=%lld F=%lld); no result", CC_MAX_ROUNDS,
-                (long long)V, (long long)F);
-  if (int rc = check_device()) return rc;
-  CcArgs a;
-  memset(&a, 0, sizeof(a));
-  a.faces = faces;
-  a.V = (int)V;
-  a.F = (int)F;
-  a.L = at<int>(ws, L.L);
-  a.changed = changed;
-  HIP_TRY(launch_cc_round(a, round == 0, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_cc_ids(const int32_t* faces, int64_t V, int64_t F, void* ws, size_t ws_bytes, int32_t* vert_comp, int32_t* face_comp,
-                         int64_t* count, void* stream) {
-  CcLayout L;
-  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
-  if (F > 0 && (!faces || !face_comp)) return fail(NERF_HIP_ERR_ARG, "faces / face_comp is null");
-  if (V > 0 && !vert_comp) return fail(NERF_HIP_ERR_ARG, "vert_comp is null");
-  if (!count) return fail(NERF_HIP_ERR_ARG, "count is null");
-  if (((uintptr_t)count & 7) != 0) return fail(NERF_HIP_ERR_ARG, "count must be 8-byte aligned");
-  if (int rc = check_device()) return rc;
-  CcArgs a;
-  memset(&a, 0, sizeof(a));
-  a.faces = faces;
-  a.V = (int)V;
-  a.F = (int)F;
-  a.L = at<int>(ws, L.L);
-  a.tot = at<int>(ws, L.tot);
-  a.base = at<int>(ws, L.base);
-  a.vert_comp = vert_comp;
-  a.face_comp = face_comp;
-  a.count = reinterpret_cast<long long*>(count);
-  HIP_TRY(launch_cc_ids(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_cc_stats(const float* verts, const int32_t* vert_comp, const int32_t* face_comp, int64_t V, int64_t F, int32_t* n_verts,
-                           int32_t* n_faces, float* bbox_lo, float* bbox_hi, int64_t max_c, void* stream) {
-  if (int rc = check_cc_sizes(V, F)) return rc;
-  if (max_c < 0 || max_c >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "max_c=%lld: a capacity in [0, 2^31)", (long long)max_c);
-  if (V > 0 && !vert_comp) return fail(NERF_HIP_ERR_ARG, "vert_comp is null");
-  if (F > 0 && !face_comp) return fail(NERF_HIP_ERR_ARG, "face_comp is null");
-  if (max_c > 0 && (!n_verts || !n_faces)) return fail(NERF_HIP_ERR_ARG, "n_verts / n_faces is null");
-  if ((bbox_lo == nullptr) != (bbox_hi == nullptr)) return fail(NERF_HIP_ERR_ARG, "bbox_lo and bbox_hi come together");
-  if (bbox_lo && V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "boxes need verts");
-  if (int rc = check_device()) return rc;
-  CcStatsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.vert_comp = vert_comp;
-  a.face_comp = face_comp;
-  a.verts = verts;
-  a.V = V;
-  a.F = F;
-  a.max_c = max_c;
-  a.n_verts = n_verts;
-  a.n_faces = n_faces;
-  a.lo = reinterpret_cast<unsigned*>(bbox_lo);
-  a.hi = reinterpret_cast<unsigned*>(bbox_hi);
-  HIP_TRY(launch_cc_stats(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
-                             const int32_t* vert_comp, const int32_t* face_comp, const uint8_t* keep, int64_t C, void* ws, size_t ws_bytes,
-                             float* out_verts, float* out_normals, float* out_rgb, int32_t* out_faces, int64_t max_v, int64_t max_f,
-                             int64_t* counts, void* stream) {
-  CcLayout L;
-  if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
-  if (C < 0 || C > V) return fail(NERF_HIP_ERR_ARG, "C=%lld: a mesh of %lld vertices has at most as many components", (long long)C, (long long)V);
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
-  if (V > 0 && (!verts || !vert_comp)) return fail(NERF_HIP_ERR_ARG, "verts / vert_comp is null");
-  if (F > 0 && (!faces || !face_comp)) return fail(NERF_HIP_ERR_ARG, "faces / face_comp is null");
-  if (C > 0 && !keep) return fail(NERF_HIP_ERR_ARG, "keep is null");
-  if (max_v > 0 && (!out_verts || (normals && !out_normals) || (rgb && !out_rgb))) return fail(NERF_HIP_ERR_ARG, "an output of max_v rows is null");
-  if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
-  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
-  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
-  if (int rc = check_device()) return rc;
-  CcCompactArgs a;
-  memset(&a, 0, sizeof(a));
-  a.verts = verts;
-  a.normals = normals;
-  a.rgb = rgb;
-  a.faces = faces;
-  a.V = (int)V;
-  a.F = (int)F;
-  a.C = (int)C;
-  a.vert_comp = vert_comp;
-  a.face_comp = face_comp;
-  a.keep = keep;
-  a.newidx = at<int>(ws, L.L);
-  a.tot = at<int>(ws, L.tot);
-  a.base = at<int>(ws, L.base);
-  a.out_verts = out_verts;
-  a.out_normals = out_normals;
-  a.out_rgb = out_rgb;
-  a.out_faces = out_faces;
-  a.max_v = max_v;
-  a.max_f = max_f;
-  a.counts = reinterpret_cast<long long*>(counts);
-  HIP_TRY(launch_cc_compact(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Workspace of the simplification calls.  Per cell of the cluster lattice 4 bytes (occupancy, then cluster ids); per vertex 60: its
-// cell / cluster (4), and per possible cluster -- there are at most V -- the member count (4), the coordinate and normal sums (24
-// each) and the referenced mark / output id (4); per face 4 (state) and the face table's 4 bytes per slot (the power of two >= 2 F:
-// 8 to 16 bytes per face); and 8 bytes per CC_PTS cells, vertices or faces, whichever are most (the scans).
-struct MsLayout {
-  size_t occ, vcl, cnt, S, T, ref, fstate, table, tot, base, scratch, total;
-  long long ncell, slots;
-};
-MsLayout ms_layout(long long V, long long F, const int* dims3) {
-  MsLayout L;
-  L.ncell = (long long)dims3[0] * dims3[1] * dims3[2];
-  L.slots = ms_table_slots(F);
-  long long most = L.ncell > V ? L.ncell : V;
-  most = most > F ? most : F;
-  const int nb = cc_blocks(most);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += al(bytes); return r; };
-  L.occ = take((size_t)L.ncell * 4);
-  L.vcl = take((size_t)V * 4);
-  L.cnt = take((size_t)V * 4);
-  L.S = take((size_t)V * 24);
-  L.T = take((size_t)V * 24);
-  L.ref = take((size_t)V * 4);
-  L.fstate = take((size_t)F * 4);
-  L.table = take((size_t)L.slots * 4);
-  L.tot = take((size_t)nb * 4);
-  L.base = take((size_t)nb * 4);
-  L.scratch = take(8);
-  L.total = o;
-  return L;
-}
-
-int check_ms_dims(const int* dims3) {
-  if (!dims3) return fail(NERF_HIP_ERR_ARG, "dims3 is null");
-  long long n = 1;
-  for (int c = 0; c < 3; ++c) {
-    if (dims3[c] < 1 || dims3[c] > 2048) return fail(NERF_HIP_ERR_ARG, "dims[%d]=%d: the cluster lattice has 1 .. 2048 cells per axis", c, dims3[c]);
-    n *= dims3[c];
-  }
-  if (n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "dims=(%d, %d, %d): the cluster lattice must stay below 2^31 cells", dims3[0], dims3[1], dims3[2]);
-  return NERF_HIP_OK;
-}
-
-int check_ms(int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, const void* ws, size_t ws_bytes, MsLayout* L) {
-  if (int rc = check_cc_sizes(V, F)) return rc;
-  if (int rc = check_ms_dims(dims3)) return rc;
-  if (!lo3 || !cell3) return fail(NERF_HIP_ERR_ARG, "lo3 / cell3 is null");
-  for (int c = 0; c < 3; ++c) {
-    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the cluster lattice's corner must be finite", c, (double)lo3[c]);
-    if (!(cell3[c] > 0.0f) || !isfinite(cell3[c]))
-      return fail(NERF_HIP_ERR_ARG, "cell[%d]=%g: the cluster lattice's cells must be > 0 and finite", c, (double)cell3[c]);
-  }
-  *L = ms_layout(V, F, dims3);
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  if (ws_bytes < L->total) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, L->total);
-  return NERF_HIP_OK;
-}
-
-MsArgs ms_args(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws, const MsLayout& L) {
-  MsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.faces = faces;
-  a.V = (int)V;
-  a.F = (int)F;
-  for (int c = 0; c < 3; ++c) {
-    a.lo[c] = lo3[c];
-    a.cell[c] = cell3[c];
-    a.dims[c] = dims3[c];
-  }
-  a.ncell = L.ncell;
-  a.slots = L.slots;
-  a.occ = at<int>(ws, L.occ);
-  a.vcl = at<int>(ws, L.vcl);
-  a.cnt = at<int>(ws, L.cnt);
-  a.S = at<long long>(ws, L.S);
-  a.T = at<long long>(ws, L.T);
-  a.ref = at<int>(ws, L.ref);
-  a.fstate = at<int>(ws, L.fstate);
-  a.table = at<int>(ws, L.table);
-  a.tot = at<int>(ws, L.tot);
-  a.base = at<int>(ws, L.base);
-  a.scratch = at<long long>(ws, L.scratch);
-  return a;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_mesh_simplify_ws_bytes(int64_t V, int64_t F, const int* dims3, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  if (int rc = check_cc_sizes(V, F)) return rc;
-  if (int rc = check_ms_dims(dims3)) return rc;
-  *bytes = ms_layout(V, F, dims3).total;
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_simplify_count(const float* verts, const float* normals, const int32_t* faces, int64_t V, int64_t F, const float* lo3,
-                                 const float* cell3, const int* dims3, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
-  MsLayout L;
-  if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
-  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
-  if (!counts) return fail(NERF_HIP_ERR_ARG, "counts is null");
-  if (((uintptr_t)counts & 7) != 0) return fail(NERF_HIP_ERR_ARG, "counts must be 8-byte aligned");
-  if (int rc = check_device()) return rc;
-  MsArgs a = ms_args(faces, V, F, lo3, cell3, dims3, ws, L);
-  a.verts = verts;
-  a.normals = normals;
-  a.counts = reinterpret_cast<long long*>(counts);
-  HIP_TRY(launch_ms_count(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws,
-                                size_t ws_bytes, float* out_verts, float* out_normals, int32_t* out_faces, int64_t max_v, int64_t max_f,
-                                void* stream) {
-  MsLayout L;
-  if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
-  if (max_v > 0 && !out_verts) return fail(NERF_HIP_ERR_ARG, "out_verts is null");
-  if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
-  if (int rc = check_device()) return rc;
-  MsArgs a = ms_args(faces, V, F, lo3, cell3, dims3, ws, L);
-  a.out_verts = out_verts;
-  a.out_normals = out_normals;
-  a.out_faces = out_faces;
-  a.max_v = max_v;
-  a.max_f = max_f;
-  HIP_TRY(launch_ms_emit(a, static_cast<hipStream_t>(stream)));
-  return NERF_HIP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
-int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
-  if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);
-  if (H < MT_WIN || W < MT_WIN) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: SSIM's %d x %d window needs H, W >= %d", H, W, MT_WIN, MT_WIN, MT_WIN);
-  const long long per_view = (long long)H * W * 3;
-  // (with n < 2^31 the whole input then stays below 2^62 values)
-  if (per_view >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: the element count H * W * 3 of a view must stay below 2^31", H, W);
-  *tiles_x = metrics_tiles_x(W);
-  *tiles = *tiles_x * metrics_tiles_y(H);
-  return NERF_HIP_OK;
-}
-
-void metrics_window(double g[MT_WIN]) {  // exp(-((k - 5) / 1.5)^2 / 2), normalised to sum 1 (summed in k order)
-  double s = 0.0;
-  for (int k = 0; k < MT_WIN; ++k) {
-    const double u = (k - MT_WIN / 2) / 1.5;
-    g[k] = exp(-0.5 * (u * u));
-    s += g[k];
-  }
-  for (int k = 0; k < MT_WIN; ++k) g[k] /= s;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nerf_hip_metrics_ws_bytes(int n, int H, int W, size_t* bytes) {
-  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
-  int tiles_x = 0, tiles = 0;
-  if (int rc = check_metrics_shape(n, H, W, &tiles_x, &tiles)) return rc;
-  *bytes = al((size_t)n * tiles * 2 * sizeof(double));
-  return NERF_HIP_OK;
-}
-
-int nerf_hip_image_metrics(const float* pred, const float* gt, int n, int H, int W, double* mse, double* ssim, void* ws, size_t ws_bytes,
-                           void* stream) {
-  int tiles_x = 0, tiles = 0;
-  if (int rc = check_metrics_shape(n, H, W, &tiles_x, &tiles)) return rc;
-  if (n == 0) return NERF_HIP_OK;  // (empty buffers may have null pointers)
-  if (!pred || !gt || !mse || !ssim) return fail(NERF_HIP_ERR_ARG, "null argument (pred, gt, mse and ssim are required)");
-  if (!ws) return fail(NERF_HIP_ERR_ARG, "workspace is null");
-  if (((uintptr_t)ws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "workspace must be 256-byte aligned");
-  const size_t need = al((size_t)n * tiles * 2 * sizeof(double));
-  if (ws_bytes < need) return fail(NERF_HIP_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
-  if (int rc = check_device()) return rc;
-  MetricsArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pred = pred;
-  a.gt = gt;
-  a.n = n;
-  a.H = H;
-  a.W = W;
-  a.tiles_x = tiles_x;
-  a.tiles = tiles;
-  a.part = static_cast<double*>(ws);
-  a.mse = mse;
-  a.ssim = ssim;
-  metrics_window(a.g);
-  HIP_TRY(launch_image_metrics(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

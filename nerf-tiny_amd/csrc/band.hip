@@ -3,12 +3,13 @@
 //   k_band_seed      per block: seed[b] = its 8 corner samples are not all of one class; active[b] = 0
 //   k_band_fill      per lattice point: the value of its block's lowest point (which is a corner sample)
 //   k_band_new       per block: new = not active and a seed in its 27-neighbourhood; in-workgroup exclusive offsets, workgroup totals
-//   k_band_scan      one workgroup: exclusive scan of the workgroup totals; counts = {new blocks, the points they own}
+//   k_band_scan      one workgroup: exclusive scan of the workgroup totals (scan.h scan_totals: the new blocks with bases, the points
+//                    as a totals-only channel); counts = {new blocks, the points they own}
 //   k_band_list      list[base + offset] = b for the new blocks (ascending block order), active[b] = 1
 //   k_band_reseed    one wave per block: seed[b] = active, an in-grid 26-neighbour is not, and b owns a corner of a mixed cell
 // The list's order is fixed by the scans -- no atomic places anything -- and no kernel reads, across workgroups, what the same launch
 // writes: new / list / reseed are separate launches (DESIGN.md section 3h gives the reason).  Inside means sigma > level, NaN outside.
-#include "kernels.h"
+#include "scan.h"
 
 namespace nerf {
 
@@ -96,63 +97,28 @@ __global__ __launch_bounds__(BAND_WG) void k_band_new(const BandArgs a) {
     if (flag) pts = (long long)owned_along(q.x, a.r, a.nx) * owned_along(q.y, a.r, a.ny) * owned_along(q.z, a.r, a.nz);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int pre = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) pts += __shfl_xor(pts, d);
-  if (lane == 0) {
-    part[wave] = __popcll(m);
-    ppart[wave] = pts;
-  }
-  __syncthreads();
-  int before = 0, total = 0;
+  if (lane == 0) ppart[wave] = pts;  // (published by wg_prefix's first barrier)
+  int total;
+  const int pre = wg_prefix<BAND_WG, 1>(flag, part, total);
   long long ptot = 0;
 #pragma unroll
-  for (int w = 0; w < BAND_WG / 64; ++w) {
-    before += (w < wave) ? part[w] : 0;
-    total += part[w];
-    ptot += ppart[w];
-  }
-  if (bl < a.nblk) a.offs[b] = ((unsigned)(before + pre) << 1) | (unsigned)flag;
+  for (int w = 0; w < BAND_WG / 64; ++w) ptot += ppart[w];
+  if (bl < a.nblk) a.offs[b] = ((unsigned)pre << 1) | (unsigned)flag;
   if (threadIdx.x == 0) {
     a.tn[blockIdx.x] = total;
     a.tp[blockIdx.x] = ptot;
   }
 }
 
-// one workgroup of 1024: thread t scans a contiguous run of the workgroup totals, the runs are joined by an LDS scan
+// one workgroup of 1024
 __global__ __launch_bounds__(1024) void k_band_scan(const BandArgs a) {
-  __shared__ long long sn[1024], sp[1024];
-  const int nwg = a.nwg, per = (nwg + 1023) / 1024, w0 = threadIdx.x * per;
-  long long n = 0, p = 0;
-  for (int q = 0; q < per; ++q) {
-    const int w = w0 + q;
-    if (w < nwg) {
-      n += a.tn[w];
-      p += a.tp[w];
-    }
-  }
-  sn[threadIdx.x] = n;
-  sp[threadIdx.x] = p;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-    const long long xn = threadIdx.x >= d ? sn[threadIdx.x - d] : 0, xp = threadIdx.x >= d ? sp[threadIdx.x - d] : 0;
-    __syncthreads();
-    sn[threadIdx.x] += xn;
-    sp[threadIdx.x] += xp;
-    __syncthreads();
-  }
-  long long en = sn[threadIdx.x] - n;
-  for (int q = 0; q < per; ++q) {
-    const int w = w0 + q;
-    if (w < nwg) {
-      a.bn[w] = (int)en;
-      en += a.tn[w];
-    }
-  }
+  long long n[2];  // new blocks, the points they own (no bases: the total only)
+  scan_totals(a.nwg, n, Totals<int, int>{a.tn, a.bn}, Totals<long long, long long>{a.tp, nullptr});
   if (threadIdx.x == 1023) {
-    a.counts[0] = sn[1023];
-    a.counts[1] = sp[1023];
+    a.counts[0] = n[0];
+    a.counts[1] = n[1];
   }
 }
 
@@ -213,27 +179,21 @@ __global__ __launch_bounds__(64) void k_band_reseed(const BandArgs a) {
 
 hipError_t launch_band_begin(const BandArgs& a, hipStream_t st) {
   const long long N = (long long)a.nx * a.ny * a.nz;
-  hipLaunchKernelGGL(k_band_seed, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_band_fill, dim3((unsigned)((N + BAND_WG - 1) / BAND_WG)), dim3(BAND_WG), 0, st, a);
-  return hipGetLastError();
+  LAUNCH(k_band_seed, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
+  LAUNCH(k_band_fill, dim3(grid(N, BAND_WG)), dim3(BAND_WG), 0, st, a);
+  return hipSuccess;
 }
 
 hipError_t launch_band_reseed(const BandArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_band_reseed, dim3(a.nblk), dim3(64), 0, st, a);
-  return hipGetLastError();
+  LAUNCH(k_band_reseed, dim3(a.nblk), dim3(64), 0, st, a);
+  return hipSuccess;
 }
 
 hipError_t launch_band_next(const BandArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_band_new, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_band_scan, dim3(1), dim3(1024), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_band_list, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
-  return hipGetLastError();
+  LAUNCH(k_band_new, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
+  LAUNCH(k_band_scan, dim3(1), dim3(1024), 0, st, a);
+  LAUNCH(k_band_list, dim3(a.nwg), dim3(BAND_WG), 0, st, a);
+  return hipSuccess;
 }
 
 }  // namespace nerf

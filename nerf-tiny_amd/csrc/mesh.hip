@@ -1,14 +1,15 @@
 // mesh.hip -- marching cubes over a density grid (nerf_hip_mesh_count / nerf_hip_mesh_emit):
 //   k_mesh_count   per lattice point: the 0-3 vertices it owns (edges to its +x / +y / +z neighbour whose ends differ in insideness)
 //                  and the triangle count of the cell whose lowest corner it is; in-block exclusive vertex offsets, block totals
-//   k_mesh_scan    one workgroup: 64-bit exclusive scans of the block totals, and the totals V, F
+//   k_mesh_scan    one workgroup: 64-bit exclusive scans of the block totals (scan.h scan_totals over two channels), and the totals V, F
 //   k_mesh_emit    vertices + normals of the owned edges at their offsets, faces at the block's face base + an in-block scan of the
 //                  recomputed triangle counts; vertex ids of neighbouring owners from the stored offsets
 // A workgroup takes MESH_PTS consecutive lattice points in MESH_ROUNDS rounds of MESH_WG (reads along z are coalesced).  The output
 // order is fixed by the scans -- no atomics place anything -- and every store is clamped to the caller's capacities.  The scan is
-// three kernels, never a single-pass look-back: no flag crosses workgroups (or XCDs) inside a launch.
+// three kernels, never a single-pass look-back: no flag crosses workgroups (or XCDs) inside a launch.  The in-workgroup prefixes
+// (wg_prefix<MESH_WG, 2> over the vertex counts, <MESH_WG, 3> over the triangle counts) and the scan of the totals are scan.h's.
 // Built with -ffp-contract=off: every product and sum below is rounded on its own, as tests/mc_reference.py restates them.
-#include "kernels.h"
+#include "scan.h"
 
 #define MC_TABLE_QUALIFIER static constexpr
 #include "mc_tables.h"
@@ -86,36 +87,6 @@ __device__ inline int cube_row(const float* __restrict__ s, const Point& q, int 
   return c;
 }
 
-__device__ inline unsigned lane_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// Exclusive prefix of a small per-lane count (bits 0 .. nbits-1) across the workgroup's four waves, in lattice order, plus the
-// workgroup's total.  Uses part[0..3] of LDS; ends with a barrier so part can be reused.
-template <int NBITS>
-__device__ inline int wg_prefix(int v, int* part, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int b = 0; b < NBITS; ++b) {
-    const unsigned long long m = __ballot((v >> b) & 1);
-    pre += (int)lane_prefix(m) << b;
-    tot += __popcll(m) << b;
-  }
-  if (lane == 0) part[wave] = tot;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < MESH_WG / 64; ++w) {
-    const int t = part[w];
-    before += (w < wave) ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + pre;
-}
-
 __device__ inline float lattice(float lo, int i, float step) { return lo + (float)i * step; }
 
 // d sigma / d x_a at lattice point p (index ia of na >= 2 along a): central inside, one-sided at the grid's faces
@@ -146,8 +117,8 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_count(const MeshArgs a) {
       nf = (c > 0 && c < 255) ? c_mc_ntri.n[c] : 0;
     }
     int tot_v, tot_f;
-    const int pre_v = wg_prefix<2>(__popc(mask), part, tot_v);
-    (void)wg_prefix<3>(nf, part, tot_f);
+    const int pre_v = wg_prefix<MESH_WG, 2>(__popc(mask), part, tot_v);
+    (void)wg_prefix<MESH_WG, 3>(nf, part, tot_f);
     if (mask) a.offs[q.p] = ((unsigned)(run_v + pre_v) << 3) | mask;  // read back only for owners of vertices
     run_v += tot_v;
     run_f += tot_f;
@@ -158,43 +129,15 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_count(const MeshArgs a) {
   }
 }
 
-// one workgroup of 1024: thread t scans a contiguous run of the block totals, the runs are joined by an LDS scan
+// one workgroup of 1024
 __global__ __launch_bounds__(1024) void k_mesh_scan(const MeshArgs a, int nb) {
-  __shared__ long long sv[1024], sf[1024];
-  const int per = (nb + 1023) / 1024, b0 = threadIdx.x * per;
-  long long v = 0, f = 0;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) {
-      v += a.tv[b];
-      f += a.tf[b];
-    }
-  }
-  sv[threadIdx.x] = v;
-  sf[threadIdx.x] = f;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-    const long long xv = threadIdx.x >= d ? sv[threadIdx.x - d] : 0, xf = threadIdx.x >= d ? sf[threadIdx.x - d] : 0;
-    __syncthreads();
-    sv[threadIdx.x] += xv;
-    sf[threadIdx.x] += xf;
-    __syncthreads();
-  }
-  long long ev = sv[threadIdx.x] - v, ef = sf[threadIdx.x] - f;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) {
-      a.bv[b] = ev;
-      a.bf[b] = ef;
-      ev += a.tv[b];
-      ef += a.tf[b];
-    }
-  }
+  long long n[2];  // V, F
+  scan_totals(nb, n, Totals<int, long long>{a.tv, a.bv}, Totals<int, long long>{a.tf, a.bf});
   if (threadIdx.x == 1023) {
-    a.bv[nb] = sv[1023];
-    a.bf[nb] = sf[1023];
-    a.counts[0] = sv[1023];
-    a.counts[1] = sf[1023];
+    a.bv[nb] = n[0];
+    a.bf[nb] = n[1];
+    a.counts[0] = n[0];
+    a.counts[1] = n[1];
   }
 }
 
@@ -260,7 +203,7 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
       nf = (c > 0 && c < 255) ? c_mc_ntri.n[c] : 0;
     }
     int tot_f;
-    const int pre_f = wg_prefix<3>(nf, part, tot_f);
+    const int pre_f = wg_prefix<MESH_WG, 3>(nf, part, tot_f);
     if (nf) {
       long long f = fb + run_f + pre_f;
       for (int t = 0; t < nf; ++t, ++f) {
@@ -286,16 +229,14 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
 
 hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st) {
   const int nb = mesh_blocks((long long)a.nx * a.ny * a.nz);
-  hipLaunchKernelGGL(k_mesh_count, dim3(nb), dim3(MESH_WG), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(1024), 0, st, a, nb);
-  return hipGetLastError();
+  LAUNCH(k_mesh_count, dim3(nb), dim3(MESH_WG), 0, st, a);
+  LAUNCH(k_mesh_scan, dim3(1), dim3(1024), 0, st, a, nb);
+  return hipSuccess;
 }
 
 hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_mesh_emit, dim3(mesh_blocks((long long)a.nx * a.ny * a.nz)), dim3(MESH_WG), 0, st, a);
-  return hipGetLastError();
+  LAUNCH(k_mesh_emit, dim3(mesh_blocks((long long)a.nx * a.ny * a.nz)), dim3(MESH_WG), 0, st, a);
+  return hipSuccess;
 }
 
 }  // namespace nerf

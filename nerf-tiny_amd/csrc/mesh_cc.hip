@@ -3,8 +3,8 @@
 //   k_cc_init        L[v] = v
 //   k_cc_hook        per face: the three labels r_k = L[v_k], m = min r_k, atomicMin(&L[r_k], m) for every r_k != m; sets `changed`
 //   k_cc_compress    per vertex: walks x = L[x] to the root, halving the path on the way, and leaves the root in L[v]
-//   k_cc_count / k_cc_scan / k_cc_place   the three-launch scan of mesh.hip over a 0/1 flag per item (roots, kept vertices, kept
-//                    faces): totals per workgroup of CC_PTS items, one workgroup's exclusive scan of them, then the placement
+//   scan.h's k_flag_count / k_flag_scan / k_flag_place   the three-launch compaction over a 0/1 flag per item, instantiated here for
+//                    the roots (-> ascending component ids), the kept vertices and the kept faces
 //   k_cc_fill / k_cc_faces                vert_comp of the non-roots from their root's id; face_comp
 //   k_cc_stats_*     counts and boxes by integer atomics, aggregated inside the wave first
 // One round of the labelling is a hook launch and a compress launch; the host reads `changed` after each round and stops at the first
@@ -27,17 +27,11 @@
 // Skipping r_k == m keeps a giant component from hammering one address: once it has one root, its faces issue no atomic at all.
 // Nothing is placed by atomics; the only atomics are integer min / max / add, whose results do not depend on arrival order.  Every
 // index read from memory is checked before it is used as an address, so a wrong argument gives wrong output, never a wild access.
-#include "kernels.h"
+#include "scan.h"
 
 namespace nerf {
 
 namespace {
-
-__device__ inline unsigned cc_lane_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-__device__ inline int cc_atomic_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ inline bool cc_face_ok(int a, int b, int c, int V) {
   return (unsigned)a < (unsigned)V && (unsigned)b < (unsigned)V && (unsigned)c < (unsigned)V;
@@ -72,9 +66,9 @@ __global__ __launch_bounds__(CC_WG) void k_cc_hook(const int* __restrict__ faces
   if ((unsigned)ra > (unsigned)a || (unsigned)rb > (unsigned)b || (unsigned)rc > (unsigned)c) return;  // (I1) holds: never taken
   const int m = min(ra, min(rb, rc));
   bool lowered = false;
-  if (ra != m) lowered |= cc_atomic_min(&L[ra], m) > m;
-  if (rb != m) lowered |= cc_atomic_min(&L[rb], m) > m;
-  if (rc != m) lowered |= cc_atomic_min(&L[rc], m) > m;
+  if (ra != m) lowered |= agent_atomic_min(&L[ra], m) > m;
+  if (rb != m) lowered |= agent_atomic_min(&L[rb], m) > m;
+  if (rc != m) lowered |= agent_atomic_min(&L[rc], m) > m;
   if (lowered) *changed = 1;
 }
 
@@ -91,39 +85,17 @@ __global__ __launch_bounds__(CC_WG) void k_cc_compress(int* L, int V) {
       x = p;
       break;
     }
-    cc_atomic_min(&L[x], g);  // halve: x's grandparent becomes its parent
+    agent_atomic_min(&L[x], g);  // halve: x's grandparent becomes its parent
     x = g;
     p = L[x];
   }
-  if (x != p0) cc_atomic_min(&L[v], x);
+  if (x != p0) agent_atomic_min(&L[v], x);
 }
 
-// ---- the scan pattern over a flag per item ----
+// ---- the flags and sinks of scan.h's compaction ----
 
-namespace {
-
-// in-workgroup exclusive prefix of a 0/1 flag in item order plus the workgroup's total; part = LDS [CC_WG / 64]
-__device__ inline int cc_wg_prefix(int flag, int* part, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int pre = (int)cc_lane_prefix(m);
-  if (lane == 0) part[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CC_WG / 64; ++w) {
-    const int t = part[w];
-    before += (w < wave) ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + pre;
-}
-
-}  // namespace
-
-// the flags (is item i counted?) and sinks (item i, its flag, its rank among the flagged) of the three uses
+// the flags (is item i counted?) and sinks (item i, its flag, its rank among the flagged) of the three uses.  k_flag_place recomputes
+// the flags: no launch between the count and the placement writes what they read
 struct RootFlag {  // v is a root
   const int* L;
   __device__ int operator()(long long i) const { return L[i] == (int)i; }
@@ -181,65 +153,6 @@ struct FaceSink {
     for (int d = 0; d < 3; ++d) out_faces[pos * 3 + d] = newidx[faces[i * 3 + d]];  // (FaceKeep checked the three indices)
   }
 };
-
-// grid = nb = ceil(n / CC_PTS)
-template <class Flag>
-__global__ __launch_bounds__(CC_WG) void k_cc_count(const Flag flag, long long n, int* __restrict__ tot) {
-  __shared__ int part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  int run = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long i = base + r * CC_WG + threadIdx.x;
-    int total;
-    (void)cc_wg_prefix(i < n ? flag(i) : 0, part, total);
-    run += total;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = run;
-}
-
-// one workgroup of 1024: thread t scans a contiguous run of the workgroup totals, the runs are joined by an LDS scan
-__global__ __launch_bounds__(1024) void k_cc_scan(const int* __restrict__ tot, int* __restrict__ base, int nb, long long* count) {
-  __shared__ long long s[1024];
-  const int per = (nb + 1023) / 1024, b0 = threadIdx.x * per;
-  long long t = 0;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) t += tot[b];
-  }
-  s[threadIdx.x] = t;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-    const long long x = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-    __syncthreads();
-    s[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long e = s[threadIdx.x] - t;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) {
-      base[b] = (int)e;  // (at most n < 2^31 items are flagged)
-      e += tot[b];
-    }
-  }
-  if (threadIdx.x == 1023) *count = s[1023];
-}
-
-// grid = nb; the flags are recomputed: no launch between the count and here writes what they read
-template <class Flag, class Sink>
-__global__ __launch_bounds__(CC_WG) void k_cc_place(const Flag flag, const Sink sink, long long n, const int* __restrict__ bases) {
-  __shared__ int part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = bases[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long i = base + r * CC_WG + threadIdx.x;
-    const int fl = i < n ? flag(i) : 0;
-    int total;
-    const int pre = cc_wg_prefix(fl, part, total);
-    if (i < n) sink(i, fl, run + pre);
-    run += total;
-  }
-}
 
 // grid = ceil(V / CC_WG): the non-roots take their root's id.  Reads only roots' entries of vert_comp (written by the launch before) and
 // writes only non-roots' entries.
@@ -355,74 +268,44 @@ __global__ __launch_bounds__(CC_WG) void k_cc_stats_decode(const CcStatsArgs a) 
 
 // ---- launchers ----
 
-namespace {
-
-inline unsigned cc_grid(long long n) { return (unsigned)((n + CC_WG - 1) / CC_WG); }
-
-#define CC_LAUNCH(...)                            \
-  do {                                            \
-    hipLaunchKernelGGL(__VA_ARGS__);              \
-    const hipError_t e_ = hipGetLastError();      \
-    if (e_ != hipSuccess) return e_;              \
-  } while (0)
-
-template <class Flag, class Sink>
-hipError_t cc_scan_place(const Flag& flag, const Sink& sink, long long n, int* tot, int* base, long long* count, hipStream_t st) {
-  const int nb = cc_blocks(n);
-  CC_LAUNCH((k_cc_count<Flag>), dim3(nb), dim3(CC_WG), 0, st, flag, n, tot);
-  CC_LAUNCH(k_cc_scan, dim3(1), dim3(1024), 0, st, tot, base, nb, count);
-  CC_LAUNCH((k_cc_place<Flag, Sink>), dim3(nb), dim3(CC_WG), 0, st, flag, sink, n, base);
-  return hipSuccess;
-}
-
-}  // namespace
-
 hipError_t launch_cc_round(const CcArgs& a, bool first, hipStream_t st) {
-  if (first && a.V > 0) CC_LAUNCH(k_cc_init, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V);
-  hipError_t e = hipMemsetAsync(a.changed, 0, sizeof(int), st);
-  if (e != hipSuccess) return e;
+  if (first && a.V > 0) LAUNCH(k_cc_init, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a.L, a.V);
+  TRY(hipMemsetAsync(a.changed, 0, sizeof(int), st));
   if (a.V == 0 || a.F == 0) return hipSuccess;  // no face can hook anything
-  CC_LAUNCH(k_cc_hook, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.L, a.changed);
-  CC_LAUNCH(k_cc_compress, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V);
+  LAUNCH(k_cc_hook, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.L, a.changed);
+  LAUNCH(k_cc_compress, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a.L, a.V);
   return hipSuccess;
 }
 
 hipError_t launch_cc_ids(const CcArgs& a, hipStream_t st) {
   if (a.V == 0) {
-    const hipError_t e = hipMemsetAsync(a.count, 0, sizeof(long long), st);
-    if (e != hipSuccess) return e;
+    TRY(hipMemsetAsync(a.count, 0, sizeof(long long), st));
   } else {
-    const hipError_t e = cc_scan_place(RootFlag{a.L}, RootSink{a.vert_comp}, a.V, a.tot, a.base, a.count, st);
-    if (e != hipSuccess) return e;
-    CC_LAUNCH(k_cc_fill, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a.L, a.V, a.vert_comp);
+    TRY(scan_place(RootFlag{a.L}, RootSink{a.vert_comp}, a.V, a.tot, a.base, a.count, st));
+    LAUNCH(k_cc_fill, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a.L, a.V, a.vert_comp);
   }
-  if (a.F > 0) CC_LAUNCH(k_cc_faces, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.vert_comp, a.face_comp);
+  if (a.F > 0) LAUNCH(k_cc_faces, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a.faces, a.V, a.F, a.vert_comp, a.face_comp);
   return hipSuccess;
 }
 
 hipError_t launch_cc_stats(const CcStatsArgs& a, hipStream_t st) {
   if (a.max_c == 0) return hipSuccess;
-  CC_LAUNCH(k_cc_stats_init, dim3(cc_grid(a.max_c)), dim3(CC_WG), 0, st, a);
-  if (a.V > 0) CC_LAUNCH(k_cc_stats<true>, dim3(cc_grid(a.V)), dim3(CC_WG), 0, st, a);
-  if (a.F > 0) CC_LAUNCH(k_cc_stats<false>, dim3(cc_grid(a.F)), dim3(CC_WG), 0, st, a);
-  if (a.lo) CC_LAUNCH(k_cc_stats_decode, dim3(cc_grid(a.max_c * 3)), dim3(CC_WG), 0, st, a);
+  LAUNCH(k_cc_stats_init, dim3(grid(a.max_c, CC_WG)), dim3(CC_WG), 0, st, a);
+  if (a.V > 0) LAUNCH(k_cc_stats<true>, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a);
+  if (a.F > 0) LAUNCH(k_cc_stats<false>, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
+  if (a.lo) LAUNCH(k_cc_stats_decode, dim3(grid(a.max_c * 3, CC_WG)), dim3(CC_WG), 0, st, a);
   return hipSuccess;
 }
 
 hipError_t launch_cc_compact(const CcCompactArgs& a, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(a.counts, 0, 2 * sizeof(long long), st);
-  if (e != hipSuccess) return e;
-  if (a.V > 0) {
-    e = cc_scan_place(VertKeep{a.vert_comp, a.keep, a.C},
-                      VertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v}, a.V, a.tot, a.base,
-                      a.counts, st);
-    if (e != hipSuccess) return e;
-  }
-  if (a.F > 0 && a.V > 0) {  // (after the vertices' placement: the faces read newidx across workgroups)
-    e = cc_scan_place(FaceKeep{a.faces, a.face_comp, a.keep, a.V, a.C}, FaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot,
-                      a.base, a.counts + 1, st);
-    if (e != hipSuccess) return e;
-  }
+  TRY(hipMemsetAsync(a.counts, 0, 2 * sizeof(long long), st));
+  if (a.V > 0)
+    TRY(scan_place(VertKeep{a.vert_comp, a.keep, a.C},
+                   VertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v}, a.V, a.tot, a.base,
+                   a.counts, st));
+  if (a.F > 0 && a.V > 0)  // (after the vertices' placement: the faces read newidx across workgroups)
+    TRY(scan_place(FaceKeep{a.faces, a.face_comp, a.keep, a.V, a.C}, FaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot,
+                   a.base, a.counts + 1, st));
   return hipSuccess;
 }
 

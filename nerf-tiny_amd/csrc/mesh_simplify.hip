@@ -1,8 +1,8 @@
 // mesh_simplify.hip -- simplification of an indexed triangle mesh by uniform vertex clustering (nerf_hip_mesh_simplify_*; DESIGN.md
 // section 3h-4; the definition is in include/nerf_hip.h).
 //   k_ms_keys        per vertex: its cell of the cluster lattice into vcl[v] (-1: a coordinate is not finite), occ[cell] = 1
-//   k_ms_count / k_ms_scan / k_ms_place   mesh_cc.hip's three-launch scan over a 0/1 flag per item, instantiated here for the occupied
-//                    cells (-> ascending cluster ids), the referenced clusters (-> output vertex ids) and the kept faces
+//   scan.h's k_flag_count / k_flag_scan / k_flag_place   the three-launch compaction over a 0/1 flag per item, instantiated here for
+//                    the occupied cells (-> ascending cluster ids), the referenced clusters (-> output vertex ids) and the kept faces
 //   k_ms_accum       per vertex: vcl[v] = its cluster id; member counts and fixed-point coordinate / normal sums by integer atomics,
 //                    aggregated inside the wave first
 //   k_ms_faces       per face: take part / degenerate; the canonical cluster triple goes into the face table
@@ -25,7 +25,7 @@
 // Which slot a key lands in depends on the interleaving; nothing that leaves this file does.  All sums are integer atomics (order
 // free), nothing is placed by an atomic, and the plain stores that race (occ[c] = 1, ref[c] = 1) all store the same value.  Every
 // index read from memory is checked before it is used as an address and every output store is clamped to max_v / max_f.
-#include "kernels.h"
+#include "scan.h"
 
 namespace nerf {
 
@@ -35,15 +35,10 @@ constexpr double MS_POS_ONE = 1048576.0;    // 2^20: fixed point of the lattice 
 constexpr double MS_NRM_ONE = 268435456.0;  // 2^28: fixed point of the normals' components (clamped to [-2, 2]: at most 2^29)
 constexpr long long MS_FLAG_TABLE_FULL = 1;
 
-__device__ inline unsigned ms_lane_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
 __device__ inline int ms_atomic_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline long long ms_atomic_add(long long* p, long long v) {
   return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ inline int ms_atomic_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // -> the slot's value before: -1 when f was stored
 __device__ inline int ms_atomic_claim(int* p, int f) {
   int expected = -1;
@@ -101,28 +96,10 @@ __device__ inline unsigned ms_hash(const int (&k)[3]) {
   return h;
 }
 
-// in-workgroup exclusive prefix of a 0/1 flag in item order plus the workgroup's total; part = LDS [CC_WG / 64]
-__device__ inline int ms_wg_prefix(int flag, int* part, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int pre = (int)ms_lane_prefix(m);
-  if (lane == 0) part[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CC_WG / 64; ++w) {
-    const int t = part[w];
-    before += (w < wave) ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + pre;
-}
-
 }  // namespace
 
-// ---- the scan pattern over a flag per item (mesh_cc.hip's, instantiated for this file's flags and sinks) ----
+// ---- the flags and sinks of scan.h's compaction.  k_flag_place recomputes the flags: a sink changes its own item only, and never
+// whether it is flagged ----
 
 // a non-zero word is flagged; the sink leaves rank + 1 in its place (0 stays 0), so the flags read the same before and after
 struct MsWordFlag {
@@ -159,65 +136,6 @@ struct MsFaceSink {  // the kept faces' corners: vertex -> cluster -> output ver
     }
   }
 };
-
-// grid = nb = ceil(n / CC_PTS)
-template <class Flag>
-__global__ __launch_bounds__(CC_WG) void k_ms_count(const Flag flag, long long n, int* __restrict__ tot) {
-  __shared__ int part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  int run = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long i = base + r * CC_WG + threadIdx.x;
-    int total;
-    (void)ms_wg_prefix(i < n ? flag(i) : 0, part, total);
-    run += total;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = run;
-}
-
-// one workgroup of 1024: thread t scans a contiguous run of the workgroup totals, the runs are joined by an LDS scan
-__global__ __launch_bounds__(1024) void k_ms_scan(const int* __restrict__ tot, int* __restrict__ base, int nb, long long* count) {
-  __shared__ long long s[1024];
-  const int per = (nb + 1023) / 1024, b0 = threadIdx.x * per;
-  long long t = 0;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) t += tot[b];
-  }
-  s[threadIdx.x] = t;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-    const long long x = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-    __syncthreads();
-    s[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long e = s[threadIdx.x] - t;
-  for (int q = 0; q < per; ++q) {
-    const int b = b0 + q;
-    if (b < nb) {
-      base[b] = (int)e;  // (at most n < 2^31 items are flagged)
-      e += tot[b];
-    }
-  }
-  if (threadIdx.x == 1023) *count = s[1023];
-}
-
-// grid = nb; the flags are recomputed: a sink changes its own item only, and never whether it is flagged
-template <class Flag, class Sink>
-__global__ __launch_bounds__(CC_WG) void k_ms_place(const Flag flag, const Sink sink, long long n, const int* __restrict__ bases) {
-  __shared__ int part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = bases[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long i = base + r * CC_WG + threadIdx.x;
-    const int fl = i < n ? flag(i) : 0;
-    int total;
-    const int pre = ms_wg_prefix(fl, part, total);
-    if (i < n) sink(i, fl, run + pre);
-    run += total;
-  }
-}
 
 // ---- vertices -> cells -> clusters ----
 
@@ -312,7 +230,7 @@ __global__ __launch_bounds__(CC_WG) void k_ms_faces(const MsArgs a) {
       }
       int kg[3];
       if ((unsigned)g < (unsigned)a.F && ms_triple(a, g, kg) == 2 && kg[0] == k[0] && kg[1] == k[1] && kg[2] == k[2]) {
-        if (f < g) ms_atomic_min(&a.table[s], f);  // (the slot only decreases: nothing to do for f > g)
+        if (f < g) agent_atomic_min(&a.table[s], f);  // (the slot only decreases: nothing to do for f > g)
         slot = (int)s;
         break;
       }
@@ -377,64 +295,34 @@ __global__ __launch_bounds__(CC_WG) void k_ms_verts(const MsArgs a) {
 
 // ---- launchers ----
 
-namespace {
-
-inline unsigned ms_grid(long long n) { return (unsigned)((n + CC_WG - 1) / CC_WG); }
-
-#define MS_LAUNCH(...)                            \
-  do {                                            \
-    hipLaunchKernelGGL(__VA_ARGS__);              \
-    const hipError_t e_ = hipGetLastError();      \
-    if (e_ != hipSuccess) return e_;              \
-  } while (0)
-#define MS_TRY(x)                                 \
-  do {                                            \
-    const hipError_t e_ = (x);                    \
-    if (e_ != hipSuccess) return e_;              \
-  } while (0)
-
-template <class Flag, class Sink>
-hipError_t ms_scan_place(const Flag& flag, const Sink& sink, long long n, int* tot, int* base, long long* count, hipStream_t st) {
-  const int nb = cc_blocks(n);
-  MS_LAUNCH((k_ms_count<Flag>), dim3(nb), dim3(CC_WG), 0, st, flag, n, tot);
-  MS_LAUNCH(k_ms_scan, dim3(1), dim3(1024), 0, st, tot, base, nb, count);
-  MS_LAUNCH((k_ms_place<Flag, Sink>), dim3(nb), dim3(CC_WG), 0, st, flag, sink, n, base);
-  return hipSuccess;
-}
-
-}  // namespace
-
 hipError_t launch_ms_count(const MsArgs& a, hipStream_t st) {
-  MS_TRY(hipMemsetAsync(a.counts, 0, 6 * sizeof(long long), st));
+  TRY(hipMemsetAsync(a.counts, 0, 6 * sizeof(long long), st));
   if (a.V == 0) return hipSuccess;  // no cluster, and no face takes part
-  MS_TRY(hipMemsetAsync(a.occ, 0, (size_t)a.ncell * sizeof(int), st));
-  MS_TRY(hipMemsetAsync(a.cnt, 0, (size_t)a.V * sizeof(int), st));
-  MS_TRY(hipMemsetAsync(a.S, 0, (size_t)a.V * 3 * sizeof(long long), st));
-  MS_TRY(hipMemsetAsync(a.T, 0, (size_t)a.V * 3 * sizeof(long long), st));
-  MS_TRY(hipMemsetAsync(a.ref, 0, (size_t)a.V * sizeof(int), st));
-  MS_LAUNCH(k_ms_keys, dim3(ms_grid(a.V)), dim3(CC_WG), 0, st, a);
-  MS_TRY(ms_scan_place(MsWordFlag{a.occ}, MsWordSink{a.occ}, a.ncell, a.tot, a.base, a.counts + 2, st));
+  TRY(hipMemsetAsync(a.occ, 0, (size_t)a.ncell * sizeof(int), st));
+  TRY(hipMemsetAsync(a.cnt, 0, (size_t)a.V * sizeof(int), st));
+  TRY(hipMemsetAsync(a.S, 0, (size_t)a.V * 3 * sizeof(long long), st));
+  TRY(hipMemsetAsync(a.T, 0, (size_t)a.V * 3 * sizeof(long long), st));
+  TRY(hipMemsetAsync(a.ref, 0, (size_t)a.V * sizeof(int), st));
+  LAUNCH(k_ms_keys, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a);
+  TRY(scan_place(MsWordFlag{a.occ}, MsWordSink{a.occ}, a.ncell, a.tot, a.base, a.counts + 2, st));
   if (a.normals)
-    MS_LAUNCH(k_ms_accum<true>, dim3(ms_grid(a.V)), dim3(CC_WG), 0, st, a);
+    LAUNCH(k_ms_accum<true>, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a);
   else
-    MS_LAUNCH(k_ms_accum<false>, dim3(ms_grid(a.V)), dim3(CC_WG), 0, st, a);
+    LAUNCH(k_ms_accum<false>, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a);
   if (a.F == 0) return hipSuccess;
-  MS_TRY(hipMemsetAsync(a.table, 0xFF, (size_t)a.slots * sizeof(int), st));
-  MS_LAUNCH(k_ms_faces, dim3(ms_grid(a.F)), dim3(CC_WG), 0, st, a);
-  MS_LAUNCH(k_ms_mark, dim3(ms_grid(a.F)), dim3(CC_WG), 0, st, a);
-  MS_TRY(ms_scan_place(MsWordFlag{a.ref}, MsWordSink{a.ref}, a.V, a.tot, a.base, a.counts + 0, st));
+  TRY(hipMemsetAsync(a.table, 0xFF, (size_t)a.slots * sizeof(int), st));
+  LAUNCH(k_ms_faces, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
+  LAUNCH(k_ms_mark, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
+  TRY(scan_place(MsWordFlag{a.ref}, MsWordSink{a.ref}, a.V, a.tot, a.base, a.counts + 0, st));
   // the kept faces are only counted here: the emit call places them
-  const int nb = cc_blocks(a.F);
-  MS_LAUNCH((k_ms_count<MsFaceKeep>), dim3(nb), dim3(CC_WG), 0, st, MsFaceKeep{a.fstate}, (long long)a.F, a.tot);
-  MS_LAUNCH(k_ms_scan, dim3(1), dim3(1024), 0, st, a.tot, a.base, nb, a.counts + 1);
-  return hipSuccess;
+  return scan_count(MsFaceKeep{a.fstate}, a.F, a.tot, a.base, a.counts + 1, st);
 }
 
 hipError_t launch_ms_emit(const MsArgs& a, hipStream_t st) {
   if (a.V == 0 || a.F == 0) return hipSuccess;  // V' = F' = 0
-  if (a.max_v > 0) MS_LAUNCH(k_ms_verts, dim3(ms_grid(a.V)), dim3(CC_WG), 0, st, a);
+  if (a.max_v > 0) LAUNCH(k_ms_verts, dim3(grid(a.V, CC_WG)), dim3(CC_WG), 0, st, a);
   if (a.max_f > 0)
-    MS_TRY(ms_scan_place(MsFaceKeep{a.fstate}, MsFaceSink{a.faces, a.vcl, a.ref, a.out_faces, a.V, a.max_f}, a.F, a.tot, a.base, a.scratch,
+    TRY(scan_place(MsFaceKeep{a.fstate}, MsFaceSink{a.faces, a.vcl, a.ref, a.out_faces, a.V, a.max_f}, a.F, a.tot, a.base, a.scratch,
                          st));
   return hipSuccess;
 }

@@ -64,6 +64,21 @@ def test_band_matches_the_restatement_and_the_dense_mesh(oracle, pkg, dev, shape
             assert torch.equal(a, b)
 
 
+def test_block_scan_with_more_totals_than_scan_threads(oracle, pkg, dev):
+    """130 x 128 x 128 in blocks of 2: 65 * 64 * 64 = 266,240 blocks, 1,040 workgroup totals -- the scan's threads take runs of two, in
+    the int channel (new blocks, with bases) and in the 64-bit one (their points, the total only)."""
+    shape, r = (130, 128, 128), 2
+    assert -(-(65 * 64 * 64) // 256) > 1024
+    m = _blob(pkg, oracle, dev, 1.5)
+    _, winfo = _check_against_restatement(m, B.BOX_LO, B.BOX_HI, shape, B.LEVEL, r)
+    assert winfo["rounds"] >= 1 and winfo["blocks_total"] == 266240 and winfo["blocks_active"] > 2048
+    dense = m.extract_mesh(B.BOX_LO, B.BOX_HI, shape, B.LEVEL)
+    band = m.extract_mesh(B.BOX_LO, B.BOX_HI, shape, B.LEVEL, band=r)
+    assert len(dense.faces) > 10000
+    for a, b in zip(band, dense):
+        assert torch.equal(a, b)
+
+
 def test_rough_field_is_the_composition(oracle, pkg, dev):
     m = pkg.NeRFModel(64, 128, 8)
     m.load_state_dict(oracle.make_weights(5, True))

@@ -205,6 +205,27 @@ def test_compaction(pkg, dev):
     assert plain.normals is None and plain.rgb is None and torch.equal(plain.verts, out.verts) and torch.equal(plain.faces, out.faces)
 
 
+# the compaction's scan at the edges of its partition: a workgroup's CC_PTS = 2048 items (one total, exactly one, two), and the first V
+# at which the scan of the totals gives a thread a run of two (more than 1024 totals).  Synthetic labels: no labelling runs.
+@pytest.mark.parametrize("V,F", [(2047, 4100), (2048, 2048), (2049, 2049), (1024 * 2048, 5000), (1024 * 2048 + 1, 4097)])
+def test_compaction_across_the_scan_partition(pkg, dev, V, F):
+    rng = np.random.default_rng(V)
+    vert_comp = (np.arange(V) % 3).astype(np.int32)
+    face_comp = rng.integers(0, 3, F).astype(np.int32)
+    faces = (3 * rng.integers(0, (V - 3) // 3 + 1, (F, 3)) + face_comp[:, None]).astype(np.int32)  # three vertices of the face's component
+    assert faces.max() < V and np.array_equal(vert_comp[faces], np.repeat(face_comp[:, None], 3, 1))
+    verts, normals, rgb = (rng.random((V, 3), dtype=np.float32) for _ in range(3))
+    keep = np.array([1, 0, 1], np.uint8)
+    rv, rf, rn, rc = R.compact(verts, faces, vert_comp, face_comp, keep, normals, rgb)
+    assert len(rv) == V - (V + 1) // 3 and 0 < len(rf) < F
+    t = lambda a: torch.from_numpy(a).to(dev)
+    ov, of, on, oc, counts = pkg.ops.mesh_compact(t(verts), t(faces), t(normals), t(rgb), t(vert_comp), t(face_comp), t(keep), len(rv), len(rf))
+    assert counts.tolist() == [len(rv), len(rf)]
+    assert np.array_equal(of.cpu().numpy(), rf)
+    for got, want in ((ov, rv), (on, rn), (oc, rc)):
+        assert np.array_equal(_bits(got.cpu().numpy()), _bits(want))
+
+
 def test_compaction_stays_inside_its_capacities(pkg, dev):
     m, ref = _blob_mesh(pkg, dev)
     c = pkg.mesh.components(m.faces, len(m.verts), m.verts)

@@ -72,6 +72,17 @@ def test_random_field(pkg, dev, name):
         assert ref["duplicate_faces"] >= 1 and ref["opposite_pairs"] >= 1
 
 
+def test_lattice_of_more_cells_than_one_scan_run(pkg, dev):
+    """129 x 128 x 128 = 2,113,536 cells are more than 1024 workgroup totals of 2048: every thread of the totals' scan takes a run of
+    two.  The corner at x = -1 puts the mesh's cells up to the lattice's last plane, so the last totals are not empty."""
+    v, f, n = M.random_mesh()
+    lo, cell, dims = (-1.0, 0.0, 0.0), (np.float32(0.125),) * 3, (129, 128, 128)
+    assert dims[0] * dims[1] * dims[2] > 1024 * 2048 and max(dims) <= 2048
+    _, info, ref = _check(pkg, dev, v, f, n, lo, cell, dims)
+    assert ref["cells"].min() < 2048 * 128 and ref["cells"].max() >= 2048 * 1030  # occupied cells in the first and in the last runs
+    assert info["faces_out"] > 1000
+
+
 def test_default_lattice(pkg, dev):
     v, f, n = M.random_mesh()
     lo, cell, dims = R.default_lattice(v, 3.0)

@@ -27,7 +27,7 @@ BAR = 1e-6    # fp32 accumulation over up to 786k rows, relative to the magnitud
 TEETH = 4.0   # one wave block dropped from or doubled in the reference moves the statistic at least this far above BAR
 
 # ---- which schedule a case selects (restated from the library) ---------------------------------------------------------------
-DW_BF16_MULTI_MAX_WB = 5120  # csrc/api.hip:82
+DW_BF16_MULTI_MAX_WB = 5120  # csrc/api.hip DW_BF16_MULTI_MAX_WB
 DW4_DEPTH = 8                # csrc/dw_f32.hip:139
 DW_WGS = 256                 # csrc/kernels.h:227: workgroups of the dir_info product (not one of the grouped seven)
 DIR_MSUBS = 2                # csrc/dw_f32.hip:314-318: nout 128, nin 256 -> 4 waves over 2 blocks
@@ -47,8 +47,8 @@ def dw_ray_duty_ok(B, Nc, Nf):
 def expected_path(arith, B, Nc, Nf, event):
     if arith == "fp32":
         return "duty" if dw_ray_duty_ok(B, Nc, Nf) else "noduty"
-    wb_tot = W.wave_blocks(B, Nc) + W.wave_blocks(B, Nf)  # csrc/api.hip:56, 583
-    small = wb_tot <= DW_BF16_MULTI_MAX_WB                  # csrc/api.hip:83-86, 674
+    wb_tot = W.wave_blocks(B, Nc) + W.wave_blocks(B, Nf)  # csrc/api.hip wave_blocks(), backward_impl()
+    small = wb_tot <= DW_BF16_MULTI_MAX_WB                  # csrc/api.hip dw_bf16_multi(), backward_impl()
     return ("b" if event else "a") if small else ("d" if event else "c")
 
 

@@ -33,7 +33,7 @@ W_SIGMA, B_SIGMA, W_PI, B_PI, W_DIR, B_DIR, W_COLOR, B_COLOR = 16, 17, 18, 19, 2
 
 
 def wave_blocks(B, N):
-    """csrc/api.hip:56: wave blocks of one pass of the bf16 kernels -- whole 256-sample workgroups."""
+    """csrc/api.hip wave_blocks(): wave blocks of one pass of the bf16 kernels -- whole 256-sample workgroups."""
     return ((B * N + 255) // 256) * 8
 
 
