@@ -51,7 +51,9 @@ extern "C" {
                                      nerf_hip_band_ws_bytes, nerf_hip_band_begin, nerf_hip_band_grow; nerf_hip_mesh_cc_ws_bytes,
                                      nerf_hip_mesh_cc_round, nerf_hip_mesh_cc_ids, nerf_hip_mesh_cc_stats, nerf_hip_mesh_cc_compact
                                      (with NERF_HIP_ERR_CONVERGE); nerf_hip_mesh_simplify_ws_bytes, nerf_hip_mesh_simplify_count,
-                                     nerf_hip_mesh_simplify_emit (with NERF_HIP_SIMPLIFY_TABLE_FULL) */
+                                     nerf_hip_mesh_simplify_emit (with NERF_HIP_SIMPLIFY_TABLE_FULL); nerf_hip_mesh_edges_ws_bytes,
+                                     nerf_hip_mesh_edges_build (with NERF_HIP_EDGES_TABLE_FULL), nerf_hip_mesh_smooth_step,
+                                     nerf_hip_mesh_vertex_normals */
 
 enum {
   NERF_HIP_OK = 0,
@@ -532,6 +534,92 @@ int nerf_hip_mesh_simplify_count(const float* verts, const float* normals, const
 int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, const float* lo3, const float* cell3, const int* dims3, void* ws,
                                 size_t ws_bytes, float* out_verts, float* out_normals, int32_t* out_faces, int64_t max_v, int64_t max_f,
                                 void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Edge topology, smoothing steps and face-derived vertex normals of an indexed triangle mesh.  Any indexed
+ * mesh: verts[V][3] fp32, faces[F][3] int32, V, F < 2^31.  Every output is a pure function of the input: identical bits from run to
+ * run, no float atomic anywhere.
+ *
+ * A. EDGES AND TOPOLOGY (nerf_hip_mesh_edges_build).  Coordinates play no role.
+ * 1. A face TAKES PART iff its three indices lie in [0, V) (others are never used as an address) and are pairwise different.
+ * 2. The EDGES are the unordered pairs {a, b} that occur as (i0, i1), (i1, i2) or (i2, i0) of a face that takes part.  count(e) = the
+ *    number of participating faces that contain e; tally(e) = (those that run it from its smaller index to its larger) - (those that
+ *    run it from its larger to its smaller).
+ * 3. A BOUNDARY edge has count == 1, a NON-MANIFOLD edge count > 2, an INCONSISTENT edge count == 2 and tally != 0 (its two faces
+ *    run it in the same direction: they are oriented against each other).
+ * 4. degree[V] int32 = the number of edges at the vertex (its distinct neighbours); vert_flags[V] int32: bit 0 = the vertex is on a
+ *    boundary edge, bit 1 = on a non-manifold edge.
+ * 5. counts (DEVICE int64[8]) = the faces that take part, E (the edges), the boundary edges, the non-manifold edges, the
+ *    inconsistent edges, the vertices with degree > 0, a flags word (NERF_HIP_EDGES_TABLE_FULL), the largest degree.  From them
+ *    euler = used vertices - E + participating faces, and a mesh is CLOSED iff it has a participating face and no boundary,
+ *    non-manifold or inconsistent edge.
+ * 6. The build call also leaves the NEIGHBOURS of every vertex (the other ends of its edges) in the workspace, for the step call; the
+ *    order in which a row lists them is not defined and nothing depends on it.
+ * The edges are found through an open-addressing table of int64 keys (a power of two of at least 4 F slots, at least 4).  A probe is
+ * bounded by the table size; a probe that found no slot -- which more slots than the 3 F possible keys rule out -- sets
+ * NERF_HIP_EDGES_TABLE_FULL in counts[6], and every result of the call must then be discarded.
+ *
+ * B. THE BOX AND THE FIXED-POINT COORDINATE (steps and normals).  A box is lo[3] (fp32, finite) and ONE scale (fp32, > 0, finite;
+ * one scalar on purpose: an anisotropic scale would turn normals).  Per axis, for a finite coordinate p:
+ *    uc = clamp((double(p) - double(lo)) / double(scale), -1, 2)      (fp64; the difference and the quotient rounded separately)
+ *    q  = rint(uc * 2^30) as int64                                     (round half to even; |q| <= 2^31)
+ * A vertex outside [lo - scale, lo + 2 scale] is pulled in by the clamp wherever it acts as a NEIGHBOUR or a CORNER: documented
+ * behaviour, as in the simplification, not an error.  The callers' default box (mesh.smooth_box in the Python package): lo = the
+ * per-axis minimum over the vertices whose three coordinates are finite; with hi their per-axis maximum and
+ * ext = the largest of fp32(hi - lo) over the axes, scale = the smallest power of two >= ext (2^127 where ext is not finite or
+ * above 2^127; 1 where ext is not > 0); a mesh without a finite vertex gets lo = 0 and scale = 1.  A caller that gives lo but no scale gets the same rule
+ * with ITS lo: ext = the largest of fp32(hi - given lo), hi still the finite vertices' maximum (and lo stays as given, scale = 1,
+ * without a finite vertex); a caller that gives scale but no lo gets lo = the minimum and that scale.
+ *
+ * C. A SMOOTHING STEP with weight w (a finite double) maps verts_in to verts_out, two buffers that do not overlap (a Jacobi step: it
+ * reads only its input).
+ * 1. A vertex MOVES iff its three coordinates are finite, it has at least one neighbour (A.6) whose three coordinates are finite,
+ *    and it is not pinned: it is pinned iff vert_flags is given and bit 0 of its entry is set.
+ * 2. For a moving vertex, per axis: S = the sum of q_j over its distinct neighbours j with three finite coordinates (int64, exact,
+ *    order free: fewer than 2^31 terms of at most 2^31), n their number,
+ *       m   = double(lo) + double(scale) * (double(S) / (double(n) * 2^30))
+ *       out = fp32(double(p) + w * (m - double(p)))
+ *    in fp64 with every product, quotient, sum and difference rounded on its own, evaluated as bracketed (no fused multiply-add).
+ * 3. Any other vertex is copied bit for bit.
+ * A Taubin iteration is a step with w = lambda > 0 followed by a step with w = mu < -lambda; plain Laplacian smoothing is the first
+ * alone.
+ *
+ * D. VERTEX NORMALS FROM FACES (nerf_hip_mesh_vertex_normals).
+ * 1. A face CONTRIBUTES iff it takes part (A.1) and its three vertices have three finite coordinates each.
+ * 2. With u_a, u_b, u_c the clamped box coordinates uc (B; fp64, NOT the rounded q) of its corners i0, i1, i2:
+ *    e1 = u_b - u_a, e2 = u_c - u_a, N = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), every difference and product
+ *    rounded on its own.  |N_k| <= 18.  The face's term is rint(N_k * 2^40) as int64 per component (below 2^45).
+ * 3. T_v = the sum of the terms of the contributing faces that have v as a corner: area-weighted, no square root per face.  T_v is
+ *    exact while it fits int64, which covers every vertex with fewer than 2^17 incident faces whatever their size (2^17 * 18 * 2^40
+ *    < 2^63) and far more in practice; past that it wraps in two's complement.
+ * 4. normal = fp32(T / sqrt((Tx Tx + Ty Ty) + Tz Tz)) in fp64, products and sums rounded separately in that order, and (0, 0, 0)
+ *    where the length is 0.  Faces are counter-clockwise seen from outside, so the normal points outward.
+ *
+ * All three calls are enqueue-only on the caller's stream and check every argument on the host before anything is enqueued
+ * (NERF_HIP_ERR_ARG: sizes, NULL arrays, lo / scale / w outside the limits above, overlapping step buffers, workspace NULL or not
+ * 256-byte aligned, counts not 8-byte aligned; NERF_HIP_ERR_WORKSPACE: workspace too small).  Indices read from device arrays are
+ * range-checked by the kernels before use and every store is clamped to max_v.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_EDGES_TABLE_FULL 1
+
+/* Bytes of workspace (256-byte aligned) shared by the three calls below: 16 per slot of the edge table (key 8, count 4, tally 4; the
+ * power of two >= 4 F slots, so 64 to 128 per face); 24 per face (the 6 F neighbour entries); 36 per vertex (row offset 8, cursor 4,
+ * the normals' sums 24); and 16 per 2048 vertices (the scan). */
+int nerf_hip_mesh_edges_ws_bytes(int64_t V, int64_t F, size_t* bytes);
+
+/* A: degree[V], vert_flags[V] (DEVICE int32), counts (DEVICE int64[8]) and, in the workspace, the neighbours. */
+int nerf_hip_mesh_edges_build(const int32_t* faces, int64_t V, int64_t F, void* ws, size_t ws_bytes, int32_t* degree, int32_t* vert_flags,
+                              int64_t* counts, void* stream);
+
+/* C: one step verts_in[V][3] -> verts_out[max_v][3] (rows from max_v on are not stored) over the neighbours a build call with the same
+ * V, F and workspace left.  lo3: a HOST array.  vert_flags: the build call's (DEVICE int32[V]) to pin the boundary, or NULL to pin
+ * nothing.  The workspace is only read. */
+int nerf_hip_mesh_smooth_step(const float* verts_in, float* verts_out, int64_t V, int64_t F, const float* lo3, float scale, double w,
+                              const int32_t* vert_flags, const void* ws, size_t ws_bytes, int64_t max_v, void* stream);
+
+/* D: normals[max_v][3].  Needs no build call and leaves a build call's neighbours intact (it uses the workspace's sums only). */
+int nerf_hip_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, void* ws,
+                                 size_t ws_bytes, float* normals, int64_t max_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -21,6 +21,7 @@ CORRECTED = 1 << 5
 STATUS_RESAMPLE_INDEX = 1 << 0
 STATUS_PREP_TIMEOUT = 1 << 1
 SIMPLIFY_TABLE_FULL = 1 << 0
+EDGES_TABLE_FULL = 1 << 0
 
 _p = C.c_void_p
 _PROTOS = {
@@ -73,6 +74,10 @@ _PROTOS = {
     "nerf_hip_mesh_simplify_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, _p, C.POINTER(C.c_size_t)]),
     "nerf_hip_mesh_simplify_count": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_size_t, _p, _p]),
     "nerf_hip_mesh_simplify_emit": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, C.c_int64, C.c_int64, _p]),
+    "nerf_hip_mesh_edges_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_edges_build": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p]),
+    "nerf_hip_mesh_smooth_step": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_double, _p, _p, C.c_size_t, C.c_int64, _p]),
+    "nerf_hip_mesh_vertex_normals": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, C.c_size_t, _p, C.c_int64, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -155,6 +160,13 @@ def mesh_simplify_ws_bytes(V: int, F: int, dims) -> int:
     """Workspace bytes of nerf_hip_mesh_simplify_count / _emit on a mesh of V vertices and F faces over a cluster lattice of dims cells."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_simplify_ws_bytes(int(V), int(F), i32_array(dims), C.byref(n)))
+    return int(n.value)
+
+
+def mesh_edges_ws_bytes(V: int, F: int) -> int:
+    """Workspace bytes of nerf_hip_mesh_edges_build / nerf_hip_mesh_smooth_step / nerf_hip_mesh_vertex_normals on V vertices and F faces."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_edges_ws_bytes(int(V), int(F), C.byref(n)))
     return int(n.value)
 
 

@@ -1,6 +1,7 @@
 // api_geometry.hip -- the geometry part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h): point and gradient queries,
-// density grids, marching cubes, the narrow band, mesh components, mesh simplification and image metrics.  Host code only, as api.hip:
-// argument checks, workspace carve-up and kernel sequencing on the caller's stream.  No allocation, no host sync.
+// density grids, marching cubes, the narrow band, mesh components, mesh simplification, mesh edges / smoothing / normals and image
+// metrics.  Host code only, as api.hip: argument checks, workspace carve-up and kernel sequencing on the caller's stream.  No
+// allocation, no host sync.
 #include <math.h>
 
 #include "api_common.h"
@@ -744,6 +745,148 @@ int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, cons
   a.max_v = max_v;
   a.max_f = max_f;
   HIP_TRY(launch_ms_emit(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Workspace of the edge calls.  Per slot of the edge table 16 bytes (the key 8, count 4, tally 4; the power of two >= 4 F slots: 64 to
+// 128 bytes per face); per face 24 more (the adjacency's 6 F entries); per vertex 36 (row offset 8, cursor 4, the normals' sums 24);
+// and 16 bytes per CC_PTS vertices (the scan).
+struct MeLayout {
+  size_t keys, cnt, tally, off, cursor, adj, tot, base, T, total;
+  long long slots;
+};
+MeLayout me_layout(long long V, long long F) {
+  MeLayout L;
+  L.slots = me_table_slots(F);
+  const int nb = cc_blocks(V);
+  Carve c;
+  L.keys = c.take((size_t)L.slots * 8);
+  L.cnt = c.take((size_t)L.slots * 4);
+  L.tally = c.take((size_t)L.slots * 4);
+  L.off = c.take(((size_t)V + 1) * 8);
+  L.cursor = c.take((size_t)V * 4);
+  L.adj = c.take((size_t)F * 6 * 4);
+  L.tot = c.take((size_t)nb * 8);
+  L.base = c.take((size_t)nb * 8);
+  L.T = c.take((size_t)V * 24);
+  L.total = c.o;
+  return L;
+}
+
+int check_me_ws(int64_t V, int64_t F, const void* ws, size_t ws_bytes, MeLayout* L) {
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  *L = me_layout(V, F);
+  return check_ws(ws, ws_bytes, L->total);
+}
+
+int check_me_box(const float* lo3, float scale) {
+  if (!lo3) return fail(NERF_HIP_ERR_ARG, "lo3 is null");
+  for (int c = 0; c < 3; ++c)
+    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the box's corner must be finite", c, (double)lo3[c]);
+  if (!(scale > 0.0f) || !isfinite(scale)) return fail(NERF_HIP_ERR_ARG, "scale=%g: the box's scale must be > 0 and finite", (double)scale);
+  return NERF_HIP_OK;
+}
+
+MeArgs me_args(int64_t V, int64_t F, const void* ws, const MeLayout& L) {
+  MeArgs a;
+  memset(&a, 0, sizeof(a));
+  void* w = const_cast<void*>(ws);
+  a.V = (int)V;
+  a.F = (int)F;
+  a.slots = L.slots;
+  a.cap = (long long)F * 6;
+  a.keys = at<long long>(w, L.keys);
+  a.cnt = at<int>(w, L.cnt);
+  a.tally = at<int>(w, L.tally);
+  a.off = at<long long>(w, L.off);
+  a.cursor = at<int>(w, L.cursor);
+  a.adj = at<int>(w, L.adj);
+  a.tot = at<long long>(w, L.tot);
+  a.base = at<long long>(w, L.base);
+  a.T = at<long long>(w, L.T);
+  return a;
+}
+
+void me_box(MeArgs* a, const float* lo3, float scale) {
+  for (int c = 0; c < 3; ++c) a->lo[c] = lo3[c];
+  a->scale = scale;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_edges_ws_bytes(int64_t V, int64_t F, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  *bytes = me_layout(V, F).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_edges_build(const int32_t* faces, int64_t V, int64_t F, void* ws, size_t ws_bytes, int32_t* degree, int32_t* vert_flags,
+                              int64_t* counts, void* stream) {
+  MeLayout L;
+  if (int rc = check_me_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (V > 0 && (!degree || !vert_flags)) return fail(NERF_HIP_ERR_ARG, "degree / vert_flags is null");
+  if (int rc = check_out(counts, "counts", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  MeArgs a = me_args(V, F, ws, L);
+  a.faces = faces;
+  a.degree = degree;
+  a.vflags = vert_flags;
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_me_build(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_smooth_step(const float* verts_in, float* verts_out, int64_t V, int64_t F, const float* lo3, float scale, double w,
+                              const int32_t* vert_flags, const void* ws, size_t ws_bytes, int64_t max_v, void* stream) {
+  MeLayout L;
+  if (int rc = check_me_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (int rc = check_me_box(lo3, scale)) return rc;
+  if (!isfinite(w)) return fail(NERF_HIP_ERR_ARG, "w=%g: a step's weight must be finite", w);
+  if (max_v < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld: a capacity must be >= 0", (long long)max_v);
+  const int64_t n = V < max_v ? V : max_v;
+  if (V > 0 && !verts_in) return fail(NERF_HIP_ERR_ARG, "verts_in is null");
+  if (n > 0 && !verts_out) return fail(NERF_HIP_ERR_ARG, "verts_out is null");
+  if (n > 0) {  // a Jacobi step: the output may not alias the input
+    const uintptr_t i0 = (uintptr_t)verts_in, i1 = i0 + (size_t)V * 12, o0 = (uintptr_t)verts_out, o1 = o0 + (size_t)n * 12;
+    if (i0 < o1 && o0 < i1) return fail(NERF_HIP_ERR_ARG, "verts_in and verts_out overlap: a step reads only its input");
+  }
+  if (int rc = check_device()) return rc;
+  MeArgs a = me_args(V, F, ws, L);
+  me_box(&a, lo3, scale);
+  a.verts = verts_in;
+  a.out = verts_out;
+  a.max_v = max_v;
+  a.w = w;
+  a.pin = vert_flags;
+  HIP_TRY(launch_me_step(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, void* ws,
+                                 size_t ws_bytes, float* normals, int64_t max_v, void* stream) {
+  MeLayout L;
+  if (int rc = check_me_ws(V, F, ws, ws_bytes, &L)) return rc;
+  if (int rc = check_me_box(lo3, scale)) return rc;
+  if (max_v < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld: a capacity must be >= 0", (long long)max_v);
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (V > 0 && max_v > 0 && !normals) return fail(NERF_HIP_ERR_ARG, "normals is null");
+  if (int rc = check_device()) return rc;
+  MeArgs a = me_args(V, F, ws, L);
+  me_box(&a, lo3, scale);
+  a.faces = faces;
+  a.verts = verts;
+  a.out = normals;
+  a.max_v = max_v;
+  HIP_TRY(launch_me_normals(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

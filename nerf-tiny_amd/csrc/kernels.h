@@ -507,6 +507,45 @@ struct MsArgs {
 hipError_t launch_ms_count(const MsArgs& a, hipStream_t st);  // everything up to counts
 hipError_t launch_ms_emit(const MsArgs& a, hipStream_t st);   // positions / normals of the referenced clusters, the kept faces
 
+// ---- edge topology, smoothing steps and face normals of an indexed mesh (mesh_smooth.hip; nerf_hip_mesh_edges_*,
+// nerf_hip_mesh_smooth_step, nerf_hip_mesh_vertex_normals).  The component calls' workgroup shape. ----
+
+// slots of the edge table: the power of two that is at least 4 F (at least 4) -- strictly more than the 3 F keys F faces can bring
+inline long long me_table_slots(long long F) {
+  long long s = 4;
+  while (s < 4 * F) s <<= 1;
+  return s;
+}
+
+struct MeArgs {
+  const int* faces;        // [F][3] (build, normals)
+  int V, F;
+  long long slots;         // me_table_slots(F)
+  long long cap;           // 6 F: the adjacency's entries (two per edge, at most 3 F edges)
+  // workspace
+  long long* keys;         // [slots] (min << 32) | max, -1 for an empty slot
+  int *cnt, *tally;        // [slots] faces of the edge; those that run it min -> max less those that run it max -> min
+  long long* off;          // [V + 1] row offsets into adj: the exclusive scan of the degrees
+  int* cursor;             // [V] entries of the row placed so far (fill only)
+  int* adj;                // [cap] the neighbours, row by row; the order inside a row is not defined
+  long long *tot, *base;   // [cc_blocks(V)] degree sums per workgroup and their exclusive scan
+  long long* T;            // [V][3] fixed-point sums of the incident faces' cross products (normals only)
+  // build
+  int *degree, *vflags;    // [V] outputs
+  long long* counts;       // [8] = faces that take part, E, boundary, non-manifold, inconsistent edges, used vertices, flags, largest degree
+  // step / normals
+  const float* verts;      // [V][3]
+  float* out;              // [max_v][3] the step's positions / the normals
+  long long max_v;
+  float lo[3], scale;      // the box
+  double w;                // step only
+  const int* pin;          // [V] step only: a vertex whose bit 0 is set stays (null: none is pinned)
+};
+
+hipError_t launch_me_build(const MeArgs& a, hipStream_t st);    // table, counts, degrees, flags, offsets, adjacency
+hipError_t launch_me_step(const MeArgs& a, hipStream_t st);     // one Jacobi step verts -> out
+hipError_t launch_me_normals(const MeArgs& a, hipStream_t st);  // T = 0, the faces' terms, the unit normals
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

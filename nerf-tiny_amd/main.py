@@ -54,6 +54,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-simplify", type=int, default=None, metavar="K",
                     help="--mesh simplifies the mesh on the device by vertex clustering in cells of K lattice steps (K >= 2; roughly 1 / K^2 "
                          "of the faces), after the floaters are dropped and before normals and colours are queried (default: no simplification)")
+    ap.add_argument("--mesh-smooth", type=int, default=None, metavar="N",
+                    help="--mesh smooths the vertex positions on the device by N Taubin iterations (N >= 1; boundary vertices stay), after the "
+                         "floaters are dropped and before --mesh-simplify; prints the mesh's edge topology (default: no smoothing)")
     ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
                     help="--mesh drops the floaters: connected components of fewer than N faces, labelled and removed on the device before "
                          "normals and colours are queried (with --mesh-band the band may already have missed islands smaller than a block; "
@@ -112,6 +115,11 @@ if __name__ == "__main__":
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.mesh is not None:
-        run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
-                         band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
-                         simplify=args.mesh_simplify)
+        m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
+                             band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
+                             simplify=args.mesh_simplify, smooth=args.mesh_smooth)
+        if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
+            import torch
+
+            t = P.mesh.topology(torch.from_numpy(m.faces).to(run.device), len(m.verts))
+            print(f"[MESH] {len(m.verts)} vertices, {len(m.faces)} faces; topology: {t.summary()}")

@@ -1,7 +1,8 @@
 """Triangle meshes of the field's isosurfaces (not in the reference): marching cubes over a device density grid (HIP kernels,
 csrc/mesh.hip), connected components on the device -- label, measure and drop the floaters (csrc/mesh_cc.hip,
-DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the device (csrc/mesh_simplify.hip)
-and a binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
+DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the device (csrc/mesh_simplify.hip),
+edge topology, Taubin smoothing and face-derived vertex normals on the device (csrc/mesh_smooth.hip) and a
+binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -140,6 +141,140 @@ def simplify(m, cell, lo=None, dims=None):
     v, f, n, info = ops.mesh_simplify(verts, faces, m.normals, lo32.tolist(), cell32.tolist(), dims3)
     info.update(lo=lo32, cell=cell32, dims=tuple(dims3))
     return Mesh(v, f, n, None), info
+
+
+class Topology(NamedTuple):
+    degree: object              # [V] int32 distinct neighbours of each vertex (device)
+    vert_flags: object          # [V] int32: bit 0 = on a boundary edge, bit 1 = on a non-manifold edge (device)
+    faces: int                  # faces that take part: three different indices in [0, V)
+    edges: int                  # E: the unique undirected edges of those faces
+    boundary_edges: int         # edges in one face
+    nonmanifold_edges: int      # edges in more than two faces
+    inconsistent_edges: int     # edges whose two faces run them in the same direction
+    used_verts: int             # vertices with degree > 0
+    max_degree: int
+    euler: int                  # used_verts - edges + faces
+    closed: bool                # faces > 0 and no boundary, non-manifold or inconsistent edge
+
+    def summary(self) -> str:
+        return (f"E {self.edges}, boundary {self.boundary_edges}, non-manifold {self.nonmanifold_edges}, inconsistent "
+                f"{self.inconsistent_edges}, closed {self.closed}, euler {self.euler}")
+
+
+def _topology(degree, flags, c):
+    closed = c["faces"] > 0 and c["boundary_edges"] == 0 and c["nonmanifold_edges"] == 0 and c["inconsistent_edges"] == 0
+    return Topology(degree, flags, c["faces"], c["edges"], c["boundary_edges"], c["nonmanifold_edges"], c["inconsistent_edges"],
+                    c["used_verts"], c["max_degree"], c["used_verts"] - c["edges"] + c["faces"], closed)
+
+
+def topology(faces, num_verts):
+    """The edge topology of an indexed triangle mesh on the DEVICE: faces [F, 3] int32 over num_verts vertices (any indexed mesh).  A
+    face takes part iff its three indices lie in [0, num_verts) and differ; the edges are the unordered index pairs of those faces.
+    Returns a Topology: the per-vertex degree and flags as device tensors, the counts as Python ints (one host read) and euler /
+    closed derived from them.  The exact rules are in include/nerf_hip.h; every output is a pure function of the input.  A CPU tensor
+    raises: there is no CPU path."""
+    from . import ops
+
+    faces = torch.as_tensor(faces)
+    if faces.device.type != "cuda":
+        raise RuntimeError("topology runs only on a ROCm device (MI355X): faces.to('cuda'); there is no CPU path")
+    degree, flags, counts, _ = ops.mesh_edges(faces, num_verts)
+    return _topology(degree, flags, ops.mesh_edge_counts(counts.cpu().tolist(), int(num_verts), int(faces.shape[0])))
+
+
+def pow2_at_least(ext) -> np.float32:
+    """The scale rule of the smoothing box: the smallest power of two >= ext as fp32; 2^127 where ext is not finite or lies above
+    2^127 (the box coordinates reach 2, so it still holds ext), 1 where ext is not > 0."""
+    ext = np.float32(ext)
+    if not ext > 0:
+        return np.float32(1.0)
+    if not np.isfinite(ext):
+        return np.float32(2.0 ** 127)
+    m, e = np.frexp(ext)  # ext = m * 2^e, m in [0.5, 1)
+    return ext if m == 0.5 else np.float32(np.ldexp(np.float64(1.0), min(int(e), 127)))
+
+
+def smooth_box(verts, lo=None, scale=None):
+    """The default box of smooth() / vertex_normals(): (lo [3] fp32 numpy, scale fp32).  Over the vertices whose three coordinates
+    are finite, lo = the per-axis minimum (unless given) and scale = pow2_at_least(the largest of fp32(hi - lo) over the axes) with hi
+    the per-axis maximum (unless given).  A mesh without a finite vertex gets lo = 0 and scale = 1 (unless given)."""
+    given = lo is not None and scale is not None
+    v = torch.as_tensor(verts).to(torch.float32).reshape(-1, 3)
+    ok = None if given else torch.isfinite(v).all(1, keepdim=True)
+    if given or not bool(ok.any()):
+        lo = np.zeros(3, np.float32) if lo is None else np.asarray(lo, np.float32).reshape(3)
+        return lo, np.float32(1.0 if scale is None else scale)
+    inf = torch.full_like(v, float("inf"))
+    ext = torch.stack((torch.where(ok, v, inf).amin(0), torch.where(ok, v, -inf).amax(0))).cpu().numpy()  # (one host read)
+    lo = ext[0] if lo is None else np.asarray(lo, np.float32).reshape(3)
+    if scale is None:
+        with np.errstate(all="ignore"):
+            scale = pow2_at_least((ext[1] - lo).astype(np.float32).max())
+    return lo.astype(np.float32), np.float32(scale)
+
+
+def _check_box(lo, scale):
+    if not np.isfinite(lo).all():
+        raise ValueError(f"lo={lo!r}: the box's corner must be finite")
+    if not np.isfinite(scale) or not scale > 0:
+        raise ValueError(f"scale={scale!r}: must be finite and > 0")
+
+
+def vertex_normals(verts, faces, lo=None, scale=None):
+    """Unit vertex normals computed from the faces on the DEVICE: the area-weighted sum of the incident faces' cross products, in
+    fixed point over the box lo / scale (by default smooth_box(verts)), normalised in fp64; (0, 0, 0) for a vertex without a
+    contributing face.  Faces are counter-clockwise seen from outside, so the normals point outward.  verts [V, 3] fp32, faces [F, 3]
+    int32 (any indexed mesh) -> [V, 3] fp32.  The exact rules are in include/nerf_hip.h; identical bits from run to run.  A CPU tensor
+    raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = torch.as_tensor(verts), torch.as_tensor(faces)
+    if verts.device.type != "cuda":
+        raise RuntimeError("vertex_normals runs only on a ROCm device (MI355X): move the mesh to 'cuda'; there is no CPU path")
+    lo, scale = smooth_box(verts, lo, scale)
+    _check_box(lo, scale)
+    return ops.mesh_vertex_normals(verts, faces, lo.tolist(), float(scale))
+
+
+def smooth(m, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, lo=None, scale=None, normals=True):
+    """The Mesh m with its vertex positions smoothed on the DEVICE by ``iterations`` Taubin iterations: a Jacobi step that moves every
+    vertex by lam towards the mean of its distinct neighbours, then one by mu (< -lam: it undoes the shrinkage of the first); mu=None
+    runs the lam steps alone (plain Laplacian smoothing, which shrinks).  The neighbours come from the mesh's unique edges, built once;
+    the means are exact fixed-point sums over the box lo / scale (by default smooth_box(m.verts)), so the result is a pure function of
+    the input -- identical bits from run to run.  fix_boundary: vertices on a boundary edge stay where they are (otherwise every
+    opening shrinks).  Vertices with a coordinate that is not finite, or without a finite neighbour, stay as well.  Any indexed
+    mesh.  Returns (Mesh, info): verts, the input's faces tensor, normals = vertex_normals of the result over the same box, rgb=None --
+    colours are not carried, query the field at the new vertices --; info = dict(faces, edges, boundary_edges, nonmanifold_edges,
+    inconsistent_edges, used_verts, max_degree, euler, closed, pinned, steps, lo, scale).  normals=False skips the normal pass (a
+    memset, nine int64 atomics per face and a pass over the vertices) and returns normals=None, for a caller that makes its own.
+    One host read of the counts.  The exact
+    rules are in include/nerf_hip.h.  A CPU tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = torch.as_tensor(m.verts), torch.as_tensor(m.faces)
+    if verts.device.type != "cuda":
+        raise RuntimeError("smooth runs only on a ROCm device (MI355X): move the mesh to 'cuda'; there is no CPU path")
+    if int(iterations) != iterations or int(iterations) < 0:
+        raise ValueError(f"iterations={iterations!r}: an int >= 0")
+    if not np.isfinite(lam) or (mu is not None and not np.isfinite(mu)):
+        raise ValueError(f"lam={lam!r} mu={mu!r}: finite weights (mu=None: no second step)")
+    lo, scale = smooth_box(verts, lo, scale)
+    _check_box(lo, scale)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    degree, flags, counts, ws = ops.mesh_edges(faces, V)
+    pinned = (flags & 1).sum().reshape(1) if fix_boundary else torch.zeros(1, dtype=torch.int64, device=counts.device)
+    host = torch.cat((counts, pinned)).cpu().tolist()  # (the one read)
+    topo = _topology(degree, flags, ops.mesh_edge_counts(host[:8], V, F))
+    cur = verts.to(torch.float32).contiguous()
+    weights = ([float(lam)] if mu is None else [float(lam), float(mu)]) * int(iterations)
+    if weights:
+        bufs = [torch.empty_like(cur), torch.empty_like(cur) if len(weights) > 1 else None]
+        for i, w in enumerate(weights):
+            cur = ops.mesh_smooth_step(cur, bufs[i & 1], F, lo.tolist(), float(scale), w, flags if fix_boundary else None, ws)
+    nrm = ops.mesh_vertex_normals(cur, faces, lo.tolist(), float(scale), ws=ws) if normals else None
+    info = {k: getattr(topo, k) for k in Topology._fields[2:]}
+    info.update(pinned=int(host[8]), steps=len(weights), lo=lo, scale=np.float32(scale))
+    return Mesh(cur, m.faces, nrm, None), info
 
 
 def _np(a):

@@ -613,7 +613,8 @@ class NeRFModel(nn.Module):
         return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
 
     @torch.no_grad()
-    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None):
+    def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None,
+                     smooth=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -635,7 +636,13 @@ class NeRFModel(nn.Module):
         dims = max(1, ceil((n - 1) / k)) per axis): a mesh of roughly 1 / k^2 of the faces.  It runs after marching cubes and after the
         component filter (min_faces still counts the original faces) and BEFORE the field normals and the colours, which are then
         queried at the new vertices only; with normals="grid" the normals are the clusters' summed and normalised grid normals.  The
-        result is, bit for bit, mesh.simplify of the unsimplified call's mesh with normals and colours made at its vertices."""
+        result is, bit for bit, mesh.simplify of the unsimplified call's mesh with normals and colours made at its vertices.
+        smooth=None: nothing more, and every output keeps its bits.  smooth=n (an int >= 1): n Taubin iterations on the device
+        (mesh.smooth with its default weights and pinned boundary, lo = the grid's lo and scale = mesh.pow2_at_least of the grid box's
+        largest fp32 extent) take the lattice staircase and the field's noise out of the positions.  It runs AFTER the component filter
+        and BEFORE simplify, so simplification clusters the denoised surface; with normals="grid" the normals are then mesh.smooth's
+        (area-weighted, from the faces) -- averaged per cluster by simplify --, with normals="field" they are the field's gradient at
+        the final vertices as always.  The result is, bit for bit, the later stages applied to mesh.smooth of the earlier stages' mesh."""
         import numpy as np
 
         from . import mesh
@@ -644,6 +651,8 @@ class NeRFModel(nn.Module):
             raise ValueError(f"normals={normals!r}: 'grid' or 'field'")
         if simplify is not None and (int(simplify) != simplify or int(simplify) < 2):
             raise ValueError(f"simplify={simplify!r}: None or an int >= 2 (cells of that many lattice steps)")
+        if smooth is not None and (int(smooth) != smooth or int(smooth) < 1):
+            raise ValueError(f"smooth={smooth!r}: None or an int >= 1 (Taubin iterations)")
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
@@ -654,6 +663,9 @@ class NeRFModel(nn.Module):
             comps = mesh.components(faces, len(verts), verts)
             keep = mesh.select_components(comps, 1 if min_faces is None else min_faces, keep_largest)
             verts, faces, nrm, _ = mesh.filter_components(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), comps, keep)
+        if smooth is not None:
+            (verts, faces, nrm, _), _ = mesh.smooth(mesh.Mesh(verts, faces, None, None), int(smooth), lo=lo32, scale=smooth_scale_of_grid(lo32, hi32),
+                                                    normals=normals == "grid")  # (field normals are queried below)
         if simplify is not None:
             cell, dims = simplify_lattice_of_grid(grid_step(lo32, hi32, shape), shape, int(simplify))
             (verts, faces, nrm, _), _ = mesh.simplify(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), cell, lo32, dims)
@@ -737,6 +749,15 @@ def simplify_lattice_of_grid(step, shape, k: int):
     cell = np.where(np.asarray(shape) > 1, (np.float32(k) * step).astype(np.float32), np.float32(1.0)).astype(np.float32)
     dims = [max(1, -(-(int(n) - 1) // int(k))) for n in shape]
     return cell, dims
+
+
+def smooth_scale_of_grid(lo32, hi32):
+    """The box scale of extract_mesh(smooth=n): mesh.pow2_at_least of the largest fp32 extent of the grid's box [lo, hi]."""
+    import numpy as np
+
+    from .mesh import pow2_at_least
+
+    return pow2_at_least((np.asarray(hi32, dtype=np.float32) - np.asarray(lo32, dtype=np.float32)).astype(np.float32).max())
 
 
 def fuse_plan(near_far0, n: int, batch: int, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384):

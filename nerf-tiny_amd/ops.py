@@ -301,6 +301,80 @@ def mesh_simplify(verts, faces, normals, lo, cell, dims, ws=None, counts=None):
     return ov, of, on, info
 
 
+def _box(lo, scale):
+    lo3 = _abi.f32_array(lo)
+    if len(lo3) != 3:
+        raise ValueError("lo has three entries")
+    return lo3, float(scale)
+
+
+def mesh_edges(faces, num_verts, ws=None, counts=None):
+    """The unique undirected edges of the indexed mesh faces[F, 3] (int32, device) over num_verts vertices (nerf_hip_mesh_edges_build;
+    the definition is in include/nerf_hip.h) -> (degree[V] int32, vert_flags[V] int32, counts int64[8] ON THE DEVICE, ws).  Enqueue
+    only: the caller reads counts (and raises on EDGES_TABLE_FULL in counts[6]).  The workspace then holds every vertex's neighbours
+    for mesh_smooth_step.  ws: a uint8 device buffer of >= _abi.mesh_edges_ws_bytes(V, F) bytes; counts: an int64 [8] device tensor;
+    each is allocated here if None."""
+    faces, V, F = _cc_faces(faces, num_verts)
+    dev = faces.device
+    if ws is None:
+        ws = torch.empty(_abi.mesh_edges_ws_bytes(V, F), dtype=torch.uint8, device=dev)
+    if counts is None:
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+    degree = torch.empty(V, dtype=torch.int32, device=dev)
+    flags = torch.empty(V, dtype=torch.int32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_edges_build(faces.data_ptr(), V, F, ws.data_ptr(), ws.numel(), degree.data_ptr(), flags.data_ptr(),
+                                                    counts.data_ptr(), _stream(faces)))
+    return degree, flags, counts, ws
+
+
+EDGE_COUNT_NAMES = ("faces", "edges", "boundary_edges", "nonmanifold_edges", "inconsistent_edges", "used_verts", "flags", "max_degree")
+
+
+def mesh_edge_counts(counts, V, F):
+    """The host's reading of mesh_edges' counts (eight ints, already on the host) -> a dict by EDGE_COUNT_NAMES without the flags word;
+    a table that reported itself full raises NerfHipError: there is no partial result."""
+    c = dict(zip(EDGE_COUNT_NAMES, (int(n) for n in counts)))
+    if c.pop("flags") & _abi.EDGES_TABLE_FULL:
+        raise _abi.NerfHipError(f"mesh_edges: the edge table reported itself full (V={V} F={F}); no result")
+    return c
+
+
+def mesh_smooth_step(verts_in, verts_out, num_faces, lo, scale, w, vert_flags, ws):
+    """One smoothing step with weight w (nerf_hip_mesh_smooth_step): verts_in[V, 3] -> verts_out[V, 3], two contiguous fp32 device
+    tensors that do not overlap, over the neighbours mesh_edges left in ws.  vert_flags: mesh_edges' flags to pin the boundary, or
+    None.  Enqueue only."""
+    V = int(verts_in.shape[0])
+    for a in (verts_in, verts_out):
+        if tuple(a.shape) != (V, 3) or a.dtype != torch.float32 or not a.is_contiguous() or a.device != ws.device:
+            raise ValueError(f"a position array {tuple(a.shape)} {a.dtype} on {a.device}: contiguous fp32 [{V}, 3] on {ws.device}")
+    if vert_flags is not None and (tuple(vert_flags.shape) != (V,) or vert_flags.dtype != torch.int32 or not vert_flags.is_contiguous()
+                                   or vert_flags.device != ws.device):
+        raise ValueError(f"vert_flags {tuple(vert_flags.shape)} {vert_flags.dtype} on {vert_flags.device}: contiguous int32 [{V}] on {ws.device}")
+    lo3, scale = _box(lo, scale)
+    _abi.check(_abi.lib().nerf_hip_mesh_smooth_step(verts_in.data_ptr(), verts_out.data_ptr(), V, int(num_faces), lo3, scale, float(w),
+                                                    vert_flags.data_ptr() if vert_flags is not None else None, ws.data_ptr(), ws.numel(), V,
+                                                    _stream(verts_in)))
+    return verts_out
+
+
+def mesh_vertex_normals(verts, faces, lo, scale, ws=None):
+    """Area-weighted vertex normals from the faces (nerf_hip_mesh_vertex_normals; the definition is in include/nerf_hip.h): verts[V, 3]
+    fp32, faces[F, 3] int32 (device), the box lo (three host floats) / scale -> normals[V, 3] fp32.  Enqueue only.  ws: as mesh_edges
+    (whose neighbours it leaves intact)."""
+    faces, V, F = _cc_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = verts.to(torch.float32).contiguous()
+    if tuple(verts.shape) != (V, 3) or verts.device != dev:
+        raise ValueError(f"verts {tuple(verts.shape)} on {verts.device}: [{V}, 3] on {dev}")
+    if ws is None:
+        ws = torch.empty(_abi.mesh_edges_ws_bytes(V, F), dtype=torch.uint8, device=dev)
+    lo3, scale = _box(lo, scale)
+    normals = torch.empty(V, 3, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_vertex_normals(verts.data_ptr(), faces.data_ptr(), V, F, lo3, scale, ws.data_ptr(), ws.numel(),
+                                                       normals.data_ptr(), V, _stream(faces)))
+    return normals
+
+
 def image_metrics(pred, gt, ws=None):
     """Per-view MSE and SSIM (nerf_hip_image_metrics, fp64 arithmetic; definition in include/nerf_hip.h): pred, gt [n, H, W, 3] device
     tensors of the same shape and device (cast to contiguous fp32 here) -> (mse[n], ssim[n]) fp64 on that device.  ws: a uint8 device

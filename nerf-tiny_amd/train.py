@@ -550,7 +550,7 @@ class NeRFRunner:
         return sigma
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
-                     keep_largest=None, simplify=None):
+                     keep_largest=None, simplify=None, smooth=None):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -563,7 +563,8 @@ class NeRFRunner:
         and, with keep_largest=k, among the k with the most faces (NeRFModel.extract_mesh; both None: no filtering).  With band= the band
         may already have missed islands smaller than a block, and filtering removes the rest.  simplify: None or an int k >= 2 -- the mesh
         is simplified on the device by vertex clustering in cells of k lattice steps, after the filter and before normals and colours
-        are queried (NeRFModel.extract_mesh).  Same file name either way."""
+        are queried (NeRFModel.extract_mesh).  smooth: None or an int n >= 1 -- n Taubin smoothing iterations on the device after the
+        filter and before simplify (NeRFModel.extract_mesh, mesh.smooth).  Same file name either way."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -575,7 +576,7 @@ class NeRFRunner:
         lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
         self.model.eval()
         m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
-                                    keep_largest=keep_largest, simplify=simplify)
+                                    keep_largest=keep_largest, simplify=simplify, smooth=smooth)
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
