@@ -53,7 +53,9 @@ extern "C" {
                                      (with NERF_HIP_ERR_CONVERGE); nerf_hip_mesh_simplify_ws_bytes, nerf_hip_mesh_simplify_count,
                                      nerf_hip_mesh_simplify_emit (with NERF_HIP_SIMPLIFY_TABLE_FULL); nerf_hip_mesh_edges_ws_bytes,
                                      nerf_hip_mesh_edges_build (with NERF_HIP_EDGES_TABLE_FULL), nerf_hip_mesh_smooth_step,
-                                     nerf_hip_mesh_vertex_normals */
+                                     nerf_hip_mesh_vertex_normals; nerf_hip_mesh_measure, nerf_hip_mesh_sample_ws_bytes,
+                                     nerf_hip_mesh_sample, nerf_hip_points_nearest_ws_bytes, nerf_hip_points_grid_build,
+                                     nerf_hip_points_nearest, nerf_hip_distance_stats */
 
 enum {
   NERF_HIP_OK = 0,
@@ -620,6 +622,111 @@ int nerf_hip_mesh_smooth_step(const float* verts_in, float* verts_out, int64_t V
 /* D: normals[max_v][3].  Needs no build call and leaves a build call's neighbours intact (it uses the workspace's sums only). */
 int nerf_hip_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, void* ws,
                                  size_t ws_bytes, float* normals, int64_t max_v, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Geometry evaluation: measures of a mesh, area-weighted surface samples, exact nearest points between two clouds
+ * and distance statistics.  Any indexed mesh (verts[V][3] fp32, faces[F][3] int32, V, F < 2^31), any clouds of
+ * fewer than 2^31 points.  Every output is a pure function of the input: identical bits from run to run, no float atomic anywhere;
+ * every product, quotient, sum and difference below is fp64 (unless marked fp32), rounded on its own and evaluated as bracketed.
+ *
+ * A. MEASURES (nerf_hip_mesh_measure) over a box lo[3] / scale (section B of the block above: one scale, fp32).
+ * 1. A face TAKES PART iff its three indices lie in [0, V) (others are never used as an address), are pairwise different, and its
+ *    three corners have three finite coordinates each.  u_a, u_b, u_c = the clamped box coordinates uc (fp64) of corners i0, i1, i2.
+ * 2. e1 = u_b - u_a, e2 = u_c - u_a, N = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), len = sqrt((Nx Nx + Ny Ny) + Nz Nz),
+ *    area = len * 0.5.  X = (u_by u_cz - u_bz u_cy, u_bz u_cx - u_bx u_cz, u_bx u_cy - u_by u_cx), six = (u_ax Xx + u_ay Xy) + u_az Xz:
+ *    six times the signed volume of the tetrahedron (box origin, a, b, c).  m_d = area * (((u_ad + u_bd) + u_cd) / 3.0) per axis d.
+ * 3. The face's five terms are rint(area * 2^40), rint(six * 2^40) and rint(m_d * 2^40) as int64 (round half to even).  The sixth of
+ *    the volume is left to the reader of the sums (one division instead of one rounding per face: a mesh whose box coordinates are
+ *    small integers, a unit cube in its default box, has an exact volume whatever its triangulation).
+ * 4. out (DEVICE int64[8]) = the sum of the area terms, of the six-volume terms, of the three moment terms, the number of faces that
+ *    take part, 0, 0.  In box units: area = out[0] / 2^40, volume = out[1] / (6 * 2^40) (meaningful for a closed, consistently
+ *    oriented mesh; positive for outward faces), area-weighted centroid = out[2 + d] / out[0]; in the mesh's units area * scale^2,
+ *    volume * scale^3, lo + scale * centroid.
+ * 5. THE BOUND.  With |uc| <= 2: |N_k| <= 18, area < 16, |six| <= 48, |m_d| < 32, so a term is below 2^46 and the sums are exact while
+ *    F < 2^17, whatever the mesh and the box.  Inside its default box (mesh.smooth_box: uc in [0, 1]) a face has area < 1, |six| <= 2
+ *    and |m_d| <= area, so every sum of a mesh of fewer than 2^22 faces is exact; a larger mesh keeps exact sums while its total area
+ *    stays below 2^23 box faces and the absolute sum of its six-volumes below 2^23 (6 at most for a simple closed surface): any
+ *    surface that does not fold millions of times across its box.  The 2^40 is the normals' (section 3h-6): a face of a 4096^3
+ *    lattice still has 16 bits of area.  Past the bound the sums wrap in two's complement, as section 3h-6's normal sums do.
+ *
+ * B. SURFACE SAMPLES (nerf_hip_mesh_sample): n points distributed by area, a pure function of (verts, faces, n, seed, box).
+ * 1. The WEIGHT of a face is w_f = rint(len * 2^39) as int64 with len of A.2 -- the area term of A.3, bit for bit -- and 0 for a face
+ *    that takes no part.  cum[f] = w_0 + ... + w_f (int64), W = cum[F - 1] (0 for F == 0) = out[0] of A.  info (DEVICE int64[1]) = W.
+ * 2. h(seed, i, s) for the uint32 seed, the sample i and the stream s in {0, 1, 2}, all arithmetic modulo 2^32:
+ *       fin(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *       h = fin(fin(fin(seed + 0x9E3779B9 * (s + 1)) ^ i) + seed)           r_s = (double(h) + 0.5) / 2^32   in (0, 1)
+ * 3. Sample i (stratified: one sample per stratum of W / n):  t = (int64) floor(((double(i) + r_0) / double(n)) * double(W)), at most
+ *    W - 1;  f = the first face with cum[f] > t (a face of weight 0 is never chosen);  (r_1, r_2) folded: if r_1 + r_2 > 1.0 then
+ *    r_1 = 1.0 - r_1 and r_2 = 1.0 - r_2;  per axis, on the ORIGINAL coordinates A, B, C of corners i0, i1, i2 widened to fp64:
+ *       point = fp32((A + r_1 * (B - A)) + r_2 * (C - A))
+ *    points[i] = point, face[i] = f.  Where W <= 0 (no area, or sums past A.5's bound), or the chosen face takes no part (possible
+ *    only past that bound), face[i] = -1 and points[i] = 0.  Rows from cap_n on are not stored.
+ *
+ * C. NEAREST POINTS (nerf_hip_points_grid_build, nerf_hip_points_nearest): ref[M][3], query[N][3] fp32.
+ * 1. d2(q, p) = (dx dx + dy dy) + dz dz with dx = double(q_x) - double(p_x) and so on.  dist2[j] (fp64) = the minimum of d2(query_j, p)
+ *    over the reference points p with three finite coordinates; idx[j] (int32) = the LOWEST index that attains it.  A query with a
+ *    coordinate that is not finite, and any query when no reference point is finite, gets idx = -1 and dist2 = +inf.  That is the
+ *    brute-force result, bit for bit.
+ * 2. THE GRID is an accelerator and never changes an output: lo[3] (fp32, finite), ONE cell size (fp32, > 0, finite) and dims[3]
+ *    (>= 1 each, product < 2^31), any values.  A point's cell along an axis is floor((double(p) - double(lo)) / double(cell)) clamped to
+ *    [0, dims - 1]; queries use the same function, so they may lie anywhere.  The callers' sizing rule (mesh.nearest_grid in the Python
+ *    package, from one min / max read): over the finite reference points, their number m, lo = the per-axis minimum, ext =
+ *    double(hi) - double(lo) per axis; no finite point or no ext > 0: cell = 1, dims = (1, 1, 1); otherwise with k = the axes of
+ *    ext > 0, cell = fp32((the product of those ext / m) ^ (1 / k)) kept inside [2^-126, 2^127], doubled until dims_d =
+ *    floor(ext_d / cell) + 1 (1 on an axis of zero extent) have a product <= 2 m + 8 (one cell if 2^127 is reached first):
+ *    cells <= 2 M + 8, below 2^31.
+ * 3. The build call sorts the reference points by cell (counts by integer atomics, an exclusive scan, placement through per-cell
+ *    cursor atomics) into 16-byte records (x, y, z, index) in the workspace; counts (DEVICE int64[2]) = the finite reference points,
+ *    the points of the fullest cell.  The order of the records inside a cell is not defined and nothing depends on it.
+ * 4. The query call walks, per query, the Chebyshev shells r = 0, 1, 2, ... of cells around the query's own (clamped) cell and stops
+ *    after shell r when best < g * g, g = the smallest over the faces of the block [c - r, c + r] that are not faces of the grid of
+ *    (the distance from the query to the face's plane lo + n * cell) - 2^-45 * (|q| + |lo| + n * cell); or when the block covers the
+ *    grid.  The proof that this is the brute-force result is at the top of csrc/mesh_distance.hip.  sort_queries != 0 processes the
+ *    queries in their own cell order (the same counting sort) and scatters each result to the query's slot; the results are the same.
+ *    The query call leaves the build call's records intact: one build serves any number of query calls with the same M, grid and
+ *    workspace (N may differ as long as the workspace holds nerf_hip_points_nearest_ws_bytes(M, N, dims)).
+ *
+ * D. DISTANCE STATISTICS (nerf_hip_distance_stats): dist2[N] fp64, a unit (fp64, > 0, finite, its square as well) and K <= 8
+ * thresholds tau_k (fp64, finite, >= 0; HOST array).  A distance COUNTS iff it is finite and >= 0.  out (DEVICE int64[4 + K]) =
+ *    the distances that count;  the sum of rint(min(sqrt(d2) / unit, 8) * 2^30);  the sum of rint(min(d2 / (unit * unit), 64) * 2^30);
+ *    those with sqrt(d2) / unit > 8 or d2 / (unit * unit) > 64 (CLAMPED: reported, never hidden);  per k those with d2 <= tau_k * tau_k.
+ * A term is at most 2^36: the sums are exact for N < 2^27 whatever the distances, and for every N < 2^31 when nothing is clamped
+ * and sqrt(d2) <= 2 unit.
+ *
+ * All calls are enqueue-only on the caller's stream and check every argument on the host before anything is enqueued
+ * (NERF_HIP_ERR_ARG: sizes, NULL arrays, lo / scale / cell / unit / thresholds outside the limits above, workspace NULL or not
+ * 256-byte aligned, int64 / fp64 outputs not 8-byte aligned; NERF_HIP_ERR_WORKSPACE: workspace too small).  Indices read from device
+ * arrays are range-checked by the kernels before use and every store is clamped to cap_n.
+ * ------------------------------------------------------------------------------------------- */
+
+/* A: out (DEVICE int64[8]).  lo3: a HOST array. */
+int nerf_hip_mesh_measure(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, int64_t* out,
+                          void* stream);
+
+/* Bytes of workspace (256-byte aligned) of the sampling call: 8 per face (cum) and 16 per 2048 faces (the scan). */
+int nerf_hip_mesh_sample_ws_bytes(int64_t F, size_t* bytes);
+
+/* B: points[cap_n][3] fp32, face[cap_n] int32, info (DEVICE int64[1]) = W.  n < 2^31. */
+int nerf_hip_mesh_sample(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, int64_t n,
+                         uint32_t seed, void* ws, size_t ws_bytes, float* points, int32_t* face, int64_t cap_n, int64_t* info,
+                         void* stream);
+
+/* Bytes of workspace (256-byte aligned) of the two calls below: the reference grid -- 8 per cell (count / cursor, start), 16 per
+ * reference point (its record), 8 per 2048 cells (the scan) -- then the queries' order: 8 more per cell, 16 per query, 8 for their
+ * total.  The build call needs only the first part: nerf_hip_points_nearest_ws_bytes(M, 0, dims). */
+int nerf_hip_points_nearest_ws_bytes(int64_t M, int64_t N, const int* dims3, size_t* bytes);
+
+/* C.3: the reference grid into the workspace, counts (DEVICE int64[2]).  lo3, dims3: HOST arrays. */
+int nerf_hip_points_grid_build(const float* ref, int64_t M, const float* lo3, float cell, const int* dims3, void* ws, size_t ws_bytes,
+                               int64_t* counts, void* stream);
+
+/* C.4: idx[cap_n] int32, dist2[cap_n] fp64 for query[N][3] against the grid a build call with the same M, lo3, cell, dims3 and
+ * workspace left. */
+int nerf_hip_points_nearest(const float* query, int64_t M, int64_t N, const float* lo3, float cell, const int* dims3, void* ws,
+                            size_t ws_bytes, int sort_queries, int32_t* idx, double* dist2, int64_t cap_n, void* stream);
+
+/* D: out (DEVICE int64[4 + K]).  tau: a HOST array of K doubles. */
+int nerf_hip_distance_stats(const double* dist2, int64_t N, double unit, const double* tau, int K, int64_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -78,6 +78,14 @@ _PROTOS = {
     "nerf_hip_mesh_edges_build": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p]),
     "nerf_hip_mesh_smooth_step": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_double, _p, _p, C.c_size_t, C.c_int64, _p]),
     "nerf_hip_mesh_vertex_normals": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, C.c_size_t, _p, C.c_int64, _p]),
+    "nerf_hip_mesh_measure": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, _p]),
+    "nerf_hip_mesh_sample_ws_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_sample": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, C.c_int64, C.c_uint32, _p, C.c_size_t, _p, _p, C.c_int64,
+                                       _p, _p]),
+    "nerf_hip_points_nearest_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, _p, C.POINTER(C.c_size_t)]),
+    "nerf_hip_points_grid_build": (C.c_int, [_p, C.c_int64, _p, C.c_float, _p, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_points_nearest": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_float, _p, _p, C.c_size_t, C.c_int, _p, _p, C.c_int64, _p]),
+    "nerf_hip_distance_stats": (C.c_int, [_p, C.c_int64, C.c_double, _p, C.c_int, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -167,6 +175,20 @@ def mesh_edges_ws_bytes(V: int, F: int) -> int:
     """Workspace bytes of nerf_hip_mesh_edges_build / nerf_hip_mesh_smooth_step / nerf_hip_mesh_vertex_normals on V vertices and F faces."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_edges_ws_bytes(int(V), int(F), C.byref(n)))
+    return int(n.value)
+
+
+def mesh_sample_ws_bytes(F: int) -> int:
+    """Workspace bytes of nerf_hip_mesh_sample on a mesh of F faces."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_sample_ws_bytes(int(F), C.byref(n)))
+    return int(n.value)
+
+
+def points_nearest_ws_bytes(M: int, N: int, dims) -> int:
+    """Workspace bytes of nerf_hip_points_grid_build (N = 0) / nerf_hip_points_nearest for M reference points, N queries and a grid of dims cells."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_points_nearest_ws_bytes(int(M), int(N), i32_array(dims), C.byref(n)))
     return int(n.value)
 
 

@@ -1,7 +1,7 @@
 // api_geometry.hip -- the geometry part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h): point and gradient queries,
-// density grids, marching cubes, the narrow band, mesh components, mesh simplification, mesh edges / smoothing / normals and image
-// metrics.  Host code only, as api.hip: argument checks, workspace carve-up and kernel sequencing on the caller's stream.  No
-// allocation, no host sync.
+// density grids, marching cubes, the narrow band, mesh components, mesh simplification, mesh edges / smoothing / normals, mesh
+// measures / samples / nearest points / distance statistics and image metrics.  Host code only, as api.hip: argument checks,
+// workspace carve-up and kernel sequencing on the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
 #include "api_common.h"
@@ -887,6 +887,227 @@ int nerf_hip_mesh_vertex_normals(const float* verts, const int32_t* faces, int64
   a.out = normals;
   a.max_v = max_v;
   HIP_TRY(launch_me_normals(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Workspace of the sampling call: per face 8 bytes (the inclusive prefix of the weights) and 16 per CC_PTS faces (the scan).
+struct MdSampleLayout {
+  size_t cum, tot, base, total;
+};
+MdSampleLayout md_sample_layout(long long F) {
+  MdSampleLayout L;
+  const int nb = cc_blocks(F);
+  Carve c;
+  L.cum = c.take((size_t)F * 8);
+  L.tot = c.take((size_t)nb * 8);
+  L.base = c.take((size_t)nb * 8);
+  L.total = c.o;
+  return L;
+}
+
+int check_md_mesh(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale) {
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (int rc = check_me_box(lo3, scale)) return rc;
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  return NERF_HIP_OK;
+}
+
+MdMeshArgs md_mesh_args(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale) {
+  MdMeshArgs a;
+  memset(&a, 0, sizeof(a));
+  a.verts = verts;
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  for (int c = 0; c < 3; ++c) a.lo[c] = lo3[c];
+  a.scale = scale;
+  return a;
+}
+
+// Workspace of the nearest-point calls.  The reference points' grid: per cell 8 bytes (count / cursor 4, start 4), per reference point
+// 16 (its record), and 8 per CC_PTS cells (the scan); then the queries' order: per cell 8 more, per query 16, and 8 for their total.
+struct MdGridLayout {
+  size_t cnt, start, rec, tot, base, qcnt, qstart, qrec, scratch, ref_total, total;
+  long long ncell;
+};
+MdGridLayout md_grid_layout(long long M, long long N, const int* dims3) {
+  MdGridLayout L;
+  L.ncell = (long long)dims3[0] * dims3[1] * dims3[2];
+  const int nb = cc_blocks(L.ncell);
+  Carve c;
+  L.cnt = c.take((size_t)L.ncell * 4);
+  L.start = c.take(((size_t)L.ncell + 1) * 4);
+  L.rec = c.take((size_t)M * 16);
+  L.tot = c.take((size_t)nb * 4);
+  L.base = c.take((size_t)nb * 4);
+  L.ref_total = c.o;
+  L.qcnt = c.take((size_t)L.ncell * 4);
+  L.qstart = c.take(((size_t)L.ncell + 1) * 4);
+  L.qrec = c.take((size_t)N * 16);
+  L.scratch = c.take(8);
+  L.total = c.o;
+  return L;
+}
+
+int check_md_dims(const int* dims3) {
+  if (!dims3) return fail(NERF_HIP_ERR_ARG, "dims3 is null");
+  long long n = 1;
+  for (int c = 0; c < 3; ++c) {
+    if (dims3[c] < 1) return fail(NERF_HIP_ERR_ARG, "dims[%d]=%d: the grid has at least one cell per axis", c, dims3[c]);
+    n *= dims3[c];
+    if (n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "dims=(%d, %d, %d): the grid must stay below 2^31 cells", dims3[0], dims3[1], dims3[2]);
+  }
+  return NERF_HIP_OK;
+}
+
+int check_md_grid(int64_t M, int64_t N, const float* lo3, float cell, const int* dims3) {
+  if (int rc = check_mesh_sizes(M, N)) return rc;  // (point counts below 2^31, as vertices)
+  if (int rc = check_md_dims(dims3)) return rc;
+  if (!lo3) return fail(NERF_HIP_ERR_ARG, "lo3 is null");
+  for (int c = 0; c < 3; ++c)
+    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the grid's corner must be finite", c, (double)lo3[c]);
+  if (!(cell > 0.0f) || !isfinite(cell)) return fail(NERF_HIP_ERR_ARG, "cell=%g: the grid's cell must be > 0 and finite", (double)cell);
+  return NERF_HIP_OK;
+}
+
+MdGridArgs md_grid_args(int64_t M, int64_t N, const float* lo3, float cell, const int* dims3, void* ws, const MdGridLayout& L) {
+  MdGridArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.dims[c] = dims3[c];
+  }
+  a.cell = cell;
+  a.ncell = (int)L.ncell;
+  a.M = (int)M;
+  a.N = (int)N;
+  a.cnt = at<int>(ws, L.cnt);
+  a.start = at<int>(ws, L.start);
+  a.rec = at<float4>(ws, L.rec);
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  a.qcnt = at<int>(ws, L.qcnt);
+  a.qstart = at<int>(ws, L.qstart);
+  a.qrec = at<float4>(ws, L.qrec);
+  a.scratch = at<long long>(ws, L.scratch);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_measure(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, int64_t* out,
+                          void* stream) {
+  if (int rc = check_md_mesh(verts, faces, V, F, lo3, scale)) return rc;
+  if (int rc = check_out(out, "out", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  MdMeshArgs a = md_mesh_args(verts, faces, V, F, lo3, scale);
+  a.out = reinterpret_cast<long long*>(out);
+  HIP_TRY(launch_md_measure(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_sample_ws_bytes(int64_t F, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_sizes(0, F)) return rc;
+  *bytes = md_sample_layout(F).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_sample(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale, int64_t n,
+                         uint32_t seed, void* ws, size_t ws_bytes, float* points, int32_t* face, int64_t cap_n, int64_t* info,
+                         void* stream) {
+  if (int rc = check_md_mesh(verts, faces, V, F, lo3, scale)) return rc;
+  if (n < 0 || n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "n=%lld: a sample count in [0, 2^31)", (long long)n);
+  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (n > 0 && cap_n > 0 && (!points || !face)) return fail(NERF_HIP_ERR_ARG, "points / face is null");
+  const MdSampleLayout L = md_sample_layout(F);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (int rc = check_out(info, "info", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  MdMeshArgs a = md_mesh_args(verts, faces, V, F, lo3, scale);
+  a.n = n;
+  a.cap_n = cap_n;
+  a.seed = seed;
+  a.cum = at<long long>(ws, L.cum);
+  a.tot = at<long long>(ws, L.tot);
+  a.base = at<long long>(ws, L.base);
+  a.info = reinterpret_cast<long long*>(info);
+  a.points = points;
+  a.face = face;
+  HIP_TRY(launch_md_sample(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_points_nearest_ws_bytes(int64_t M, int64_t N, const int* dims3, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_sizes(M, N)) return rc;
+  if (int rc = check_md_dims(dims3)) return rc;
+  *bytes = md_grid_layout(M, N, dims3).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_points_grid_build(const float* ref, int64_t M, const float* lo3, float cell, const int* dims3, void* ws, size_t ws_bytes,
+                               int64_t* counts, void* stream) {
+  if (int rc = check_md_grid(M, 0, lo3, cell, dims3)) return rc;
+  if (M > 0 && !ref) return fail(NERF_HIP_ERR_ARG, "ref is null");
+  const MdGridLayout L = md_grid_layout(M, 0, dims3);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (int rc = check_out(counts, "counts", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  MdGridArgs a = md_grid_args(M, 0, lo3, cell, dims3, ws, L);
+  a.ref = ref;
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_md_grid_build(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_points_nearest(const float* query, int64_t M, int64_t N, const float* lo3, float cell, const int* dims3, void* ws,
+                            size_t ws_bytes, int sort_queries, int32_t* idx, double* dist2, int64_t cap_n, void* stream) {
+  if (int rc = check_md_grid(M, N, lo3, cell, dims3)) return rc;
+  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (N > 0 && !query) return fail(NERF_HIP_ERR_ARG, "query is null");
+  if (N > 0 && cap_n > 0 && (!idx || !dist2)) return fail(NERF_HIP_ERR_ARG, "idx / dist2 is null");
+  if (dist2 && ((uintptr_t)dist2 & 7) != 0) return fail(NERF_HIP_ERR_ARG, "dist2 must be 8-byte aligned");
+  const MdGridLayout L = md_grid_layout(M, N, dims3);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (int rc = check_device()) return rc;
+  MdGridArgs a = md_grid_args(M, N, lo3, cell, dims3, ws, L);
+  a.query = query;
+  a.idx = idx;
+  a.dist2 = dist2;
+  a.cap_n = cap_n;
+  HIP_TRY(launch_md_nearest(a, sort_queries != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_distance_stats(const double* dist2, int64_t N, double unit, const double* tau, int K, int64_t* out, void* stream) {
+  if (N < 0 || N >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "N=%lld: a count in [0, 2^31)", (long long)N);
+  if (K < 0 || K > MD_MAX_TAU) return fail(NERF_HIP_ERR_ARG, "K=%d: at most %d thresholds", K, MD_MAX_TAU);
+  if (!(unit > 0.0) || !isfinite(unit) || !isfinite(unit * unit) || !(unit * unit > 0.0))
+    return fail(NERF_HIP_ERR_ARG, "unit=%g: must be > 0 and finite, its square as well", unit);
+  if (K > 0 && !tau) return fail(NERF_HIP_ERR_ARG, "tau is null");
+  if (N > 0 && (!dist2 || ((uintptr_t)dist2 & 7) != 0)) return fail(NERF_HIP_ERR_ARG, "dist2 is null or not 8-byte aligned");
+  if (int rc = check_out(out, "out", 8)) return rc;
+  MdStatsArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < K; ++k) {
+    if (!isfinite(tau[k]) || tau[k] < 0.0) return fail(NERF_HIP_ERR_ARG, "tau[%d]=%g: a threshold must be finite and >= 0", k, tau[k]);
+    a.tau2[k] = tau[k] * tau[k];
+  }
+  if (int rc = check_device()) return rc;
+  a.dist2 = dist2;
+  a.N = N;
+  a.unit = unit;
+  a.K = K;
+  a.out = reinterpret_cast<long long*>(out);
+  HIP_TRY(launch_md_stats(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

@@ -546,6 +546,65 @@ hipError_t launch_me_build(const MeArgs& a, hipStream_t st);    // table, counts
 hipError_t launch_me_step(const MeArgs& a, hipStream_t st);     // one Jacobi step verts -> out
 hipError_t launch_me_normals(const MeArgs& a, hipStream_t st);  // T = 0, the faces' terms, the unit normals
 
+// ---- geometry evaluation: measures, surface samples, exact nearest points, distance statistics (mesh_distance.hip;
+// nerf_hip_mesh_measure, nerf_hip_mesh_sample, nerf_hip_points_*, nerf_hip_distance_stats).  The component
+// calls' workgroup shape. ----
+constexpr int MD_MAX_TAU = 8;  // thresholds of one statistics call
+
+struct MdMeshArgs {
+  const float* verts;      // [V][3]
+  const int* faces;        // [F][3]
+  int V, F;
+  float lo[3], scale;      // the box (measure and the sampling weights)
+  long long* out;          // measure: [8] = area, six volumes, three centroid moments (2^-40 box units), faces that take part, 0, 0
+  // sampling
+  long long n, cap_n;      // samples, and the rows the outputs hold
+  unsigned seed;
+  long long* cum;          // [F] inclusive prefix of the weights (workspace)
+  long long *tot, *base;   // [cc_blocks(F)] weight sums per workgroup and their exclusive scan (workspace)
+  long long* info;         // [1] = W
+  float* points;           // [cap_n][3]
+  int* face;               // [cap_n]
+};
+
+hipError_t launch_md_measure(const MdMeshArgs& a, hipStream_t st);
+hipError_t launch_md_sample(const MdMeshArgs& a, hipStream_t st);
+
+struct MdGridArgs {
+  float lo[3], cell;       // the grid: corner and the one cell size
+  int dims[3];
+  int ncell;               // dims[0] * dims[1] * dims[2] < 2^31
+  const float* ref;        // [M][3]
+  const float* query;      // [N][3]
+  int M, N;
+  // workspace: the reference points' grid, then the queries' order
+  int *cnt, *start;        // [ncell] points per cell (then the placement's cursors); [ncell + 1] a cell's first record
+  float4* rec;             // [M] (x, y, z, original index), cell by cell
+  int *qcnt, *qstart;      // the same for the queries
+  float4* qrec;            // [N]
+  int *tot, *base;         // [cc_blocks(ncell)] counts per workgroup of cells and their exclusive scan
+  long long* scratch;      // [1] the queries' total (workspace)
+  long long* counts;       // build: [2] = finite reference points, the fullest cell's points
+  // query
+  int* idx;                // [cap_n]
+  double* dist2;           // [cap_n]
+  long long cap_n;
+};
+
+hipError_t launch_md_grid_build(const MdGridArgs& a, hipStream_t st);
+hipError_t launch_md_nearest(const MdGridArgs& a, bool sort_queries, hipStream_t st);
+
+struct MdStatsArgs {
+  const double* dist2;     // [N]
+  long long N;
+  double unit;
+  int K;
+  double tau2[MD_MAX_TAU]; // tau_k * tau_k
+  long long* out;          // [4 + K]
+};
+
+hipError_t launch_md_stats(const MdStatsArgs& a, hipStream_t st);
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

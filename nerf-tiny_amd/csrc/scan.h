@@ -1,5 +1,5 @@
-// scan.h -- the scan and compaction scaffolding of the geometry kernels (mesh.hip, band.hip, mesh_cc.hip, mesh_simplify.hip; DESIGN.md
-// section 3h-5).  Included by those four translation units only, never by a render or training one.
+// scan.h -- the scan and compaction scaffolding of the geometry kernels (mesh.hip, band.hip, mesh_cc.hip, mesh_simplify.hip,
+// mesh_smooth.hip, mesh_distance.hip).  Included by those six translation units only, never by a render or training one.
 //   lane_prefix / wg_prefix     exclusive prefix of a small per-lane count inside the wave / the workgroup, in item order
 //   Totals / scan_totals        channels of workgroup totals -> exclusive bases and the grand totals, by ONE workgroup of 1024
 //   k_flag_count / k_flag_scan / k_flag_place   compaction over a 0/1 flag per item in three launches: totals per workgroup of CC_PTS

@@ -64,6 +64,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-keep-largest", type=int, default=None, metavar="K",
                     help="--mesh keeps only the K connected components with the most faces (ties: the lower component id; combines with "
                          "--mesh-min-faces; default: keep everything)")
+    ap.add_argument("--mesh-compare", default=None, metavar="FILE",
+                    help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
+                         "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
+                         "to <RESULTS_PATH><time>_<iter>_mesh_eval.json (rank 0)")
+    ap.add_argument("--mesh-compare-samples", type=int, default=200_000, metavar="N",
+                    help="surface samples per mesh of --mesh-compare (default 200000)")
+    ap.add_argument("--mesh-compare-tau", type=float, nargs="+", default=(), metavar="T",
+                    help="distance thresholds of --mesh-compare's precision / recall / F-score (up to 8; default: none)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--maps", action="store_true",
@@ -117,7 +125,8 @@ if __name__ == "__main__":
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
-                             simplify=args.mesh_simplify, smooth=args.mesh_smooth)
+                             simplify=args.mesh_simplify, smooth=args.mesh_smooth, compare=args.mesh_compare,
+                             compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau))
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

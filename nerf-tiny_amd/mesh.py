@@ -1,8 +1,10 @@
 """Triangle meshes of the field's isosurfaces (not in the reference): marching cubes over a device density grid (HIP kernels,
 csrc/mesh.hip), connected components on the device -- label, measure and drop the floaters (csrc/mesh_cc.hip,
 DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the device (csrc/mesh_simplify.hip),
-edge topology, Taubin smoothing and face-derived vertex normals on the device (csrc/mesh_smooth.hip) and a
-binary PLY writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh build on these."""
+edge topology, Taubin smoothing and face-derived vertex normals on the device (csrc/mesh_smooth.hip), geometry
+evaluation on the device -- measures, area-weighted surface samples, exact nearest points, Chamfer distance and F-scores
+(csrc/mesh_distance.hip) -- and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
+build on these."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -277,6 +279,190 @@ def smooth(m, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, lo=None, scal
     return Mesh(cur, m.faces, nrm, None), info
 
 
+class Measure(NamedTuple):
+    area: float        # surface area, in the mesh's units squared
+    volume: float      # signed enclosed volume (meaningful for a closed, consistently oriented mesh; > 0 for outward faces)
+    centroid: object   # [3] fp64 area-weighted centroid of the surface (NaN without area)
+    faces: int         # faces that take part: three different indices in [0, V), finite corners
+    raw: tuple         # the device's int64 sums: area, six volumes, three moments (2^-40 box units), faces, 0, 0
+
+
+MEASURE_ONE = float(2 ** 40)
+
+
+def measure_from_raw(raw, lo, scale):
+    """The host's reading of nerf_hip_mesh_measure's eight int64s over the box lo / scale -> Measure."""
+    raw = tuple(int(x) for x in raw)
+    lo64, sc = np.asarray(lo, np.float32).reshape(3).astype(np.float64), float(np.float32(scale))
+    with np.errstate(all="ignore"):
+        cen = lo64 + sc * (np.array(raw[2:5], np.float64) / np.float64(raw[0])) if raw[0] else np.full(3, np.nan)
+    return Measure(raw[0] / MEASURE_ONE * sc * sc, raw[1] / (6.0 * MEASURE_ONE) * sc * sc * sc, cen, raw[5], raw)
+
+
+def _on_device(t, what):
+    t = torch.as_tensor(t)
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{what} runs only on a ROCm device (MI355X): move the input to 'cuda'; there is no CPU path")
+    return t
+
+
+def measure(m, lo=None, scale=None):
+    """Area, enclosed volume and area-weighted centroid of the Mesh m (any indexed mesh) on the DEVICE: per face the fp64 terms over
+    the box lo / scale (by default smooth_box(m.verts)) rounded to int64 fixed point and summed by integer atomics, so the result is a
+    pure function of the input.  Returns a Measure (one host read).  The exact rules are in include/nerf_hip.h.  A CPU tensor raises:
+    there is no CPU path."""
+    from . import ops
+
+    verts, faces = _on_device(m.verts, "measure"), torch.as_tensor(m.faces)
+    lo, scale = smooth_box(verts, lo, scale)
+    _check_box(lo, scale)
+    return measure_from_raw(ops.mesh_measure(verts, faces, lo.tolist(), float(scale)).cpu().tolist(), lo, scale)
+
+
+def sample_surface(m, n, seed=0, lo=None, scale=None):
+    """n points on the surface of the Mesh m distributed by area, on the DEVICE: stratified over the integer prefix of the faces'
+    areas, the face by binary search, folded barycentrics from a counter-based hash of (seed, sample, stream) -- a pure function of
+    (verts, faces, n, seed, box), no generator state.  seed: an int in [0, 2^32).  The box lo / scale (by default smooth_box(m.verts))
+    only fixes the weights' fixed point.  Returns (points [n, 3] fp32, face [n] int32) on the device; a mesh without area raises
+    ValueError (one host read of the total weight).  The exact rules are in include/nerf_hip.h.  A CPU tensor raises: there is no CPU
+    path."""
+    from . import ops
+
+    verts, faces = _on_device(m.verts, "sample_surface"), torch.as_tensor(m.faces)
+    if int(n) != n or int(n) < 0 or int(n) >= 2 ** 31:
+        raise ValueError(f"n={n!r}: an int in [0, 2^31)")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"seed={seed!r}: an int in [0, 2^32)")
+    lo, scale = smooth_box(verts, lo, scale)
+    _check_box(lo, scale)
+    points, face, info = ops.mesh_sample(verts, faces, int(n), int(seed), lo.tolist(), float(scale))
+    W = int(info.cpu())
+    if W <= 0:
+        raise ValueError(f"sample_surface: the mesh has no area to sample (V={int(verts.shape[0])} F={int(faces.shape[0])}, total weight {W})")
+    return points, face
+
+
+def _cloud_box(p):
+    """-> (lo [3], hi [3] fp32 numpy over the finite rows, their number): one host read"""
+    v = torch.as_tensor(p).to(torch.float32).reshape(-1, 3)
+    if v.shape[0] == 0:
+        return np.zeros(3, np.float32), np.zeros(3, np.float32), 0
+    ok = torch.isfinite(v).all(1, keepdim=True)
+    inf = torch.full_like(v, float("inf"))
+    host = torch.cat((torch.where(ok, v, inf).amin(0).double(), torch.where(ok, v, -inf).amax(0).double(), ok.sum().double().reshape(1)))
+    host = host.cpu().numpy()
+    m = int(host[6])
+    if m == 0:
+        return np.zeros(3, np.float32), np.zeros(3, np.float32), 0
+    return host[0:3].astype(np.float32), host[3:6].astype(np.float32), m
+
+
+def grid_rule(lo, hi, m):
+    """The sizing rule of nearest()'s grid (include/nerf_hip.h): (lo [3] fp32, cell fp32, dims (3 ints)) from the finite reference
+    points' box lo / hi and their number m: about one point per cell, at most 2 m + 8 cells, one cell along an axis of zero extent."""
+    lo = np.asarray(lo, np.float32).reshape(3)
+    ext = np.asarray(hi, np.float32).reshape(3).astype(np.float64) - lo.astype(np.float64)
+    pos = ext > 0
+    if m <= 0 or not pos.any():
+        return lo, np.float32(1.0), (1, 1, 1)
+    with np.errstate(all="ignore"):
+        cell = np.float32((np.prod(ext[pos]) / m) ** (1.0 / int(pos.sum())))
+    top = np.float32(2.0 ** 127)
+    if not cell >= np.float32(2.0 ** -126):
+        cell = np.float32(2.0 ** -126)
+    cell = min(cell, top)
+    while True:
+        dims = tuple(int(np.floor(e / np.float64(cell))) + 1 if e > 0 else 1 for e in ext)
+        if dims[0] * dims[1] * dims[2] <= 2 * m + 8:
+            return lo, np.float32(cell), dims
+        if cell >= top:
+            return lo, np.float32(cell), (1, 1, 1)
+        cell = np.float32(cell * np.float32(2.0))
+
+
+def nearest_grid(ref):
+    """grid_rule over the finite rows of ref [M, 3] (one host read of their minimum, maximum and number) -> (lo, cell, dims)."""
+    return grid_rule(*_cloud_box(ref))
+
+
+def nearest(ref, query, grid=None, sort_queries=False):
+    """The exact nearest reference point of every query on the DEVICE: ref [M, 3], query [N, 3] fp32 -> (idx [N] int32, dist2 [N] fp64),
+    dist2 the fp64 squared distance to the nearest ref row with three finite coordinates and idx the LOWEST index that attains it;
+    idx -1 and dist2 +inf for a query that is not finite, and for every query when no ref row is finite.  That is the brute-force
+    result bit for bit; a uniform grid over ref (grid = (lo, cell, dims), by default nearest_grid(ref)) only accelerates it, and
+    sort_queries (process the queries in cell order, scatter the results back; off by default: measured no faster, DESIGN.md
+    section 3h-7) changes the speed alone.  The exact rules are in
+    include/nerf_hip.h.  CPU tensors raise: there is no CPU path."""
+    from . import ops
+
+    ref, query = _on_device(ref, "nearest"), _on_device(query, "nearest")
+    lo, cell, dims = nearest_grid(ref) if grid is None else grid
+    lo = np.asarray(lo, np.float32).reshape(3)
+    ws, _ = ops.points_grid(ref, lo.tolist(), float(cell), dims, n_query=int(query.shape[0]))
+    return ops.points_nearest(query, int(ref.shape[0]), lo.tolist(), float(cell), dims, ws, sort_queries=sort_queries)
+
+
+DIST_ONE = float(2 ** 30)
+
+
+def stats_from_raw(raw, unit, n):
+    """The host's reading of nerf_hip_distance_stats' int64s for n distances in units of `unit` -> dict(mean, rms, count, total,
+    clamped, within [K])."""
+    raw = [int(x) for x in raw]
+    c = raw[0]
+    mean = raw[1] / (c * DIST_ONE) * unit if c else float("nan")
+    rms = float(np.sqrt(raw[2] / (c * DIST_ONE))) * unit if c else float("nan")
+    return dict(mean=mean, rms=rms, count=c, total=int(n), clamped=raw[3], within=raw[4:])
+
+
+def chamfer(a, b, thresholds=(), unit=None):
+    """Chamfer distance and F-scores between two point clouds a [Na, 3] and b [Nb, 3] on the DEVICE: nearest() both ways, then the
+    distances' statistics as exact integer sums (nerf_hip_distance_stats), so the result is a pure function of the input.  unit: the
+    fixed point's unit, by default pow2_at_least(the two clouds' joint extent) -- then no distance reaches the clamp at 8 units; a
+    non-zero ``clamped`` count in the result says the means are lower bounds.  thresholds: up to 8 distances tau.  Returns a dict:
+    a_to_b / b_to_a = dict(mean, rms, count, total, clamped, within) (count: the finite distances among total), chamfer = the mean of
+    the two means, thresholds, and per threshold precision (the share of a within tau of b), recall (of b within tau of a) and fscore
+    (their harmonic mean), clamped, unit.  a is the cloud under test, b the ground truth.  CPU tensors raise: there is no CPU path."""
+    from . import ops
+
+    a, b = _on_device(a, "chamfer"), _on_device(b, "chamfer")
+    thresholds = tuple(float(t) for t in thresholds)
+    if len(thresholds) > 8 or any(not np.isfinite(t) or t < 0 for t in thresholds):
+        raise ValueError(f"thresholds={thresholds!r}: at most 8 finite distances >= 0")
+    box_a, box_b = _cloud_box(a), _cloud_box(b)
+    if unit is None:
+        both = [bx for bx in (box_a, box_b) if bx[2] > 0]
+        ext = 1.0
+        if both:
+            with np.errstate(all="ignore"):
+                ext = (np.max([bx[1] for bx in both], axis=0) - np.min([bx[0] for bx in both], axis=0)).astype(np.float32).max()
+        unit = float(pow2_at_least(ext))
+    unit = float(unit)
+    if not np.isfinite(unit) or not unit > 0 or not np.isfinite(unit * unit) or not unit * unit > 0:
+        raise ValueError(f"unit={unit!r}: must be finite and > 0, its square as well")
+    _, d_ab = nearest(b, a, grid=grid_rule(*box_b))
+    _, d_ba = nearest(a, b, grid=grid_rule(*box_a))
+    raw = torch.cat((ops.distance_stats(d_ab, unit, thresholds), ops.distance_stats(d_ba, unit, thresholds))).cpu().tolist()  # (one read)
+    k = 4 + len(thresholds)
+    ab, ba = stats_from_raw(raw[:k], unit, d_ab.shape[0]), stats_from_raw(raw[k:], unit, d_ba.shape[0])
+    frac = lambda s: [w / s["total"] if s["total"] else float("nan") for w in s["within"]]
+    prec, rec = frac(ab), frac(ba)
+    fs = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(prec, rec)]
+    return dict(a_to_b=ab, b_to_a=ba, chamfer=0.5 * (ab["mean"] + ba["mean"]), thresholds=list(thresholds), precision=prec, recall=rec,
+                fscore=fs, clamped=ab["clamped"] + ba["clamped"], unit=unit)
+
+
+def compare(m_a, m_b, n=200_000, seed=0, thresholds=()):
+    """The geometric distance between two meshes on the DEVICE: n area-weighted samples of each (sample_surface with seeds seed and
+    seed + 1), chamfer(samples of m_a, samples of m_b, thresholds) and both meshes' measure() as measure_a / measure_b.  m_a is the
+    mesh under test (precision), m_b the ground truth (recall).  A mesh without area raises ValueError."""
+    pa, _ = sample_surface(m_a, n, seed)
+    pb, _ = sample_surface(m_b, n, (int(seed) + 1) & 0xFFFFFFFF)
+    out = chamfer(pa, pb, thresholds)
+    out.update(samples=int(n), seed=int(seed), measure_a=measure(m_a), measure_b=measure(m_b))
+    return out
+
+
 def _np(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
@@ -315,3 +501,100 @@ def write_ply(path, verts, faces, normals=None, rgb=None):
         fh.write(header.encode("ascii"))
         fh.write(vrec.tobytes())
         fh.write(frec.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """Reads a triangle mesh from a PLY 1.0 file, ASCII or binary little-endian: what write_ply writes, and any file whose ``vertex``
+    element carries scalar properties with ``x y z`` among them (others are skipped by their declared sizes) followed by a ``face``
+    element of one list property of 3 indices each.  Returns (verts [V, 3] fp32, faces [F, 3] int32, normals [V, 3] fp32 or None --
+    ``nx ny nz`` --, rgb [V, 3] uint8 or None -- uchar ``red green blue``, as stored: divide by 255 for floats) as numpy arrays.
+    Anything else raises ValueError naming the offending header line; faces that are not triangles are refused, not triangulated."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end) if end >= 0 else -1
+    if not data.startswith(b"ply") or nl < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' ... 'end_header' header)")
+    try:
+        lines = [ln.strip() for ln in data[:nl].decode("ascii").splitlines()]
+    except UnicodeDecodeError:
+        raise ValueError(f"{path}: the PLY header is not ASCII") from None
+    body = data[nl + 1:]
+    if lines[0] != "ply" or lines[-1] != "end_header":
+        raise ValueError(f"{path}: unsupported PLY header line {lines[0] if lines[0] != 'ply' else lines[-1]!r}")
+    fmt, elems = None, []  # elems: [name, count, properties]
+    for ln in lines[1:-1]:
+        tok = ln.split()
+        bad = ValueError(f"{path}: unsupported PLY header line {ln!r}")
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            if fmt is not None or len(tok) != 3 or tok[1] not in ("ascii", "binary_little_endian") or tok[2] != "1.0":
+                raise bad
+            fmt = tok[1]
+        elif tok[0] == "element":
+            if len(tok) != 3 or not tok[2].isdigit() or len(elems) >= 2 or tok[1] != ("vertex", "face")[len(elems)]:
+                raise bad
+            elems.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elems:
+                raise bad
+            if len(tok) == 3 and tok[1] in _PLY_TYPES and elems[-1][0] == "vertex":
+                elems[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+            elif (len(tok) == 5 and tok[1] == "list" and elems[-1][0] == "face" and not elems[-1][2] and tok[2] in _PLY_TYPES
+                  and tok[3] in _PLY_TYPES and _PLY_TYPES[tok[2]][0] in "iu" and _PLY_TYPES[tok[3]][0] in "iu"):
+                elems[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                raise bad
+        else:
+            raise bad
+    if fmt is None:
+        raise ValueError(f"{path}: the PLY header has no 'format' line")
+    if len(elems) != 2 or not elems[1][2]:
+        raise ValueError(f"{path}: the PLY header needs 'element vertex' and 'element face' with one list property")
+    (_, V, vprops), (_, F, (flist,)) = elems
+    names = [p[0] for p in vprops]
+    if len(set(names)) != len(names) or any(k not in names for k in "xyz"):
+        raise ValueError(f"{path}: the vertex element needs properties x, y and z, once each (it has {names})")
+    if fmt == "ascii":
+        tok = body.split()
+        need = V * len(vprops)
+        if len(tok) < need:
+            raise ValueError(f"{path}: {len(tok)} values, the {V} vertices need {need}")
+        try:
+            table = np.array([float(t) for t in tok[:need]], dtype=np.float64).reshape(V, len(vprops))
+            rest = np.array([int(t) for t in tok[need:]], dtype=np.int64)
+        except ValueError:
+            raise ValueError(f"{path}: a value of the body is not a number") from None
+        vcol = {k: table[:, i].astype(t) for i, (k, t) in enumerate(vprops)}
+        whole = min(len(rest) // 4, F)
+        rows = rest[:whole * 4].reshape(whole, 4)
+        counts, index = rows[:, 0], rows[:, 1:]
+    else:
+        vdt = np.dtype([(k, "<" + t) for k, t in vprops])
+        fdt = np.dtype([("n", "<" + flist[1]), ("i", "<" + flist[2], (3,))])
+        if len(body) < V * vdt.itemsize:
+            raise ValueError(f"{path}: {len(body)} bytes, the {V} vertices need {V * vdt.itemsize}")
+        vrec = np.frombuffer(body, dtype=vdt, count=V)
+        vcol = {k: vrec[k] for k in names}
+        fbody = body[V * vdt.itemsize:]
+        whole = min(F, len(fbody) // fdt.itemsize)
+        frec = np.frombuffer(fbody, dtype=fdt, count=whole)
+        counts, index = frec["n"].astype(np.int64), frec["i"].astype(np.int64)
+    if (counts != 3).any():  # (the first such face is where it says: every face before it had 3 indices)
+        k = int(np.argmax(counts != 3))
+        raise ValueError(f"{path}: face {k} has {int(counts[k])} indices: only triangles are supported")
+    if whole < F:
+        raise ValueError(f"{path}: the face list ends after {whole} of {F} triangles")
+    if F and (index.min() < -2 ** 31 or index.max() >= 2 ** 31):
+        raise ValueError(f"{path}: a face index does not fit int32")
+    types = dict(vprops)
+    col3 = lambda keys, dt: np.stack([vcol[k].astype(dt) for k in keys], axis=1).reshape(V, 3)
+    verts = col3("xyz", np.float32)
+    normals = col3(("nx", "ny", "nz"), np.float32) if all(k in vcol for k in ("nx", "ny", "nz")) else None
+    rgb = col3(("red", "green", "blue"), np.uint8) if all(types.get(k) == "u1" for k in ("red", "green", "blue")) else None
+    return verts, np.ascontiguousarray(index, dtype=np.int32).reshape(F, 3), normals, rgb

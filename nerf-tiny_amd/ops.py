@@ -375,6 +375,97 @@ def mesh_vertex_normals(verts, faces, lo, scale, ws=None):
     return normals
 
 
+def _md_mesh(verts, faces):
+    faces, V, F = _cc_faces(faces, verts.shape[0])
+    verts = verts.to(torch.float32).contiguous()
+    if tuple(verts.shape) != (V, 3) or verts.device != faces.device:
+        raise ValueError(f"verts {tuple(verts.shape)} on {verts.device}: [{V}, 3] on {faces.device}")
+    return verts, faces, V, F
+
+
+def mesh_measure(verts, faces, lo, scale):
+    """The measures of an indexed mesh over the box lo / scale (nerf_hip_mesh_measure; the definition is in include/nerf_hip.h) ->
+    int64[8] ON THE DEVICE: the fixed-point sums of the area, the six-volumes and the three centroid moments, the faces that take
+    part, 0, 0.  Enqueue only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    lo3, scale = _box(lo, scale)
+    out = torch.empty(8, dtype=torch.int64, device=faces.device)
+    _abi.check(_abi.lib().nerf_hip_mesh_measure(verts.data_ptr(), faces.data_ptr(), V, F, lo3, scale, out.data_ptr(), _stream(faces)))
+    return out
+
+
+def mesh_sample(verts, faces, n, seed, lo, scale, ws=None):
+    """n area-weighted surface samples of an indexed mesh (nerf_hip_mesh_sample; the definition is in include/nerf_hip.h) ->
+    (points[n, 3] fp32, face[n] int32, info int64[1] = the total weight W ON THE DEVICE).  Enqueue only: the caller reads info (W <= 0:
+    a mesh without area, every face id is -1).  ws: a uint8 device buffer of >= _abi.mesh_sample_ws_bytes(F) bytes."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    dev = faces.device
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n={n} < 0")
+    lo3, scale = _box(lo, scale)
+    if ws is None:
+        ws = torch.empty(max(_abi.mesh_sample_ws_bytes(F), 256), dtype=torch.uint8, device=dev)
+    points = torch.empty(n, 3, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    info = torch.empty(1, dtype=torch.int64, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_sample(verts.data_ptr(), faces.data_ptr(), V, F, lo3, scale, n, int(seed) & 0xFFFFFFFF, ws.data_ptr(),
+                                               ws.numel(), points.data_ptr(), face.data_ptr(), n, info.data_ptr(), _stream(faces)))
+    return points, face, info
+
+
+def _md_points(p, name):
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"{name} {tuple(p.shape)}: a [n, 3] tensor")
+    return p.to(torch.float32).contiguous()
+
+
+def points_grid(ref, lo, cell, dims, n_query=0, ws=None):
+    """Sorts the reference points ref[M, 3] (fp32, device) by cell of the grid lo (three host floats) / cell (one float) / dims (three
+    host ints) (nerf_hip_points_grid_build) -> (ws, counts int64[2] ON THE DEVICE = the finite points, the fullest cell's points).  ws
+    is sized for queries of up to n_query points: a uint8 device buffer of >= _abi.points_nearest_ws_bytes(M, n_query, dims) bytes."""
+    ref = _md_points(ref, "ref")
+    M = int(ref.shape[0])
+    lo3, dims3 = _abi.f32_array(lo), _abi.i32_array(dims)
+    if len(lo3) != 3 or len(dims3) != 3:
+        raise ValueError("lo and dims have three entries each")
+    if ws is None:
+        ws = torch.empty(_abi.points_nearest_ws_bytes(M, n_query, dims), dtype=torch.uint8, device=ref.device)
+    counts = torch.empty(2, dtype=torch.int64, device=ref.device)
+    _abi.check(_abi.lib().nerf_hip_points_grid_build(ref.data_ptr(), M, lo3, float(cell), dims3, ws.data_ptr(), ws.numel(), counts.data_ptr(),
+                                                     _stream(ref)))
+    return ws, counts
+
+
+def points_nearest(query, num_ref, lo, cell, dims, ws, sort_queries=False):
+    """The nearest reference point of every query[N, 3] (fp32, device) over the grid points_grid left in ws (nerf_hip_points_nearest; the
+    definition is in include/nerf_hip.h) -> (idx[N] int32, dist2[N] fp64).  Enqueue only."""
+    query = _md_points(query, "query")
+    N = int(query.shape[0])
+    if query.device != ws.device:
+        raise ValueError(f"query on {query.device}: the grid is on {ws.device}")
+    idx = torch.empty(N, dtype=torch.int32, device=query.device)
+    dist2 = torch.empty(N, dtype=torch.float64, device=query.device)
+    _abi.check(_abi.lib().nerf_hip_points_nearest(query.data_ptr(), int(num_ref), N, _abi.f32_array(lo), float(cell), _abi.i32_array(dims),
+                                                  ws.data_ptr(), ws.numel(), 1 if sort_queries else 0, idx.data_ptr(), dist2.data_ptr(), N,
+                                                  _stream(query)))
+    return idx, dist2
+
+
+def distance_stats(dist2, unit, thresholds=()):
+    """The statistics of squared distances dist2[N] (fp64, device) in units of `unit` (nerf_hip_distance_stats; the definition is in
+    include/nerf_hip.h) -> int64[4 + K] ON THE DEVICE: the finite count, the fixed-point sums of d / unit and d2 / unit^2, the clamped,
+    and per threshold the distances <= it.  Enqueue only."""
+    if dist2.dim() != 1 or dist2.dtype != torch.float64:
+        raise ValueError(f"dist2 {tuple(dist2.shape)} {dist2.dtype}: an fp64 [N] tensor")
+    dist2 = dist2.contiguous()
+    tau = (C.c_double * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+    out = torch.empty(4 + len(thresholds), dtype=torch.int64, device=dist2.device)
+    _abi.check(_abi.lib().nerf_hip_distance_stats(dist2.data_ptr(), int(dist2.shape[0]), float(unit), tau, len(thresholds), out.data_ptr(),
+                                                  _stream(dist2)))
+    return out
+
+
 def image_metrics(pred, gt, ws=None):
     """Per-view MSE and SSIM (nerf_hip_image_metrics, fp64 arithmetic; definition in include/nerf_hip.h): pred, gt [n, H, W, 3] device
     tensors of the same shape and device (cast to contiguous fp32 here) -> (mse[n], ssim[n]) fp64 on that device.  ws: a uint8 device

@@ -550,7 +550,7 @@ class NeRFRunner:
         return sigma
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
-                     keep_largest=None, simplify=None, smooth=None):
+                     keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=()):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -564,7 +564,12 @@ class NeRFRunner:
         may already have missed islands smaller than a block, and filtering removes the rest.  simplify: None or an int k >= 2 -- the mesh
         is simplified on the device by vertex clustering in cells of k lattice steps, after the filter and before normals and colours
         are queried (NeRFModel.extract_mesh).  smooth: None or an int n >= 1 -- n Taubin smoothing iterations on the device after the
-        filter and before simplify (NeRFModel.extract_mesh, mesh.smooth).  Same file name either way."""
+        filter and before simplify (NeRFModel.extract_mesh, mesh.smooth).  Same file name either way.  compare: None, or a
+        ground-truth mesh -- the path of a PLY file (mesh.read_ply) or a mesh.Mesh -- against which the extracted mesh is measured on the
+        device after it is written: mesh.compare(extracted, ground truth, n=compare_samples, thresholds=compare_tau) -- Chamfer
+        distance, precision / recall / F-score per threshold, both meshes' area and volume.  The result is kept as
+        ``self.last_mesh_eval``, printed on one line and, with save, written to ``<results_path><start_time>_<last_iter>_mesh_eval.json``.
+        Without compare nothing new is computed, printed or written."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -584,7 +589,43 @@ class NeRFRunner:
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
             write_ply(path, out.verts, out.faces, out.normals, out.rgb)
+        if compare is not None:
+            self.last_mesh_eval = self._compare_mesh(m, compare, compare_samples, compare_tau, save)
         return out
+
+    def _compare_mesh(self, m, truth, samples, taus, save):
+        """extract_mesh(compare=): mesh.compare of the device mesh m against truth (a PLY path or a Mesh) -> the result as plain
+        Python numbers; printed, and with save written beside the mesh."""
+        import json
+
+        import numpy as np
+
+        from . import mesh as M
+
+        name = None
+        if not isinstance(truth, M.Mesh):
+            name = os.fspath(truth)
+            tv, tf, _, _ = M.read_ply(name)
+            truth = M.Mesh(tv, tf, None, None)
+        dev = m.verts.device
+        truth = M.Mesh(torch.as_tensor(np.asarray(truth.verts, np.float32) if not torch.is_tensor(truth.verts) else truth.verts).to(dev),
+                       torch.as_tensor(np.asarray(truth.faces, np.int32) if not torch.is_tensor(truth.faces) else truth.faces).to(dev), None, None)
+        r = M.compare(M.Mesh(m.verts, m.faces, None, None), truth, n=int(samples), thresholds=tuple(taus))
+        for k in ("measure_a", "measure_b"):
+            ms = r[k]
+            r[k] = dict(area=ms.area, volume=ms.volume, centroid=[float(c) for c in ms.centroid], faces=ms.faces)
+        r.update(iter=int(self.last_iter), truth=name)
+        per_tau = " ".join(f"[F@{t:g}] {f:.4f} (P {p:.4f} R {q:.4f})" for t, f, p, q in zip(r["thresholds"], r["fscore"], r["precision"], r["recall"]))
+        print(f"[MESH-EVAL] {r['iter']} [CHAMFER] {r['chamfer']:.6g} (mesh->truth {r['a_to_b']['mean']:.6g}, truth->mesh {r['b_to_a']['mean']:.6g}) "
+              f"{per_tau + ' ' if per_tau else ''}[AREA] {r['measure_a']['area']:.6g} vs {r['measure_b']['area']:.6g} [VOLUME] "
+              f"{r['measure_a']['volume']:.6g} vs {r['measure_b']['volume']:.6g} [{r['samples']} samples, clamped {r['clamped']}]")
+        if save:
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh_eval.json"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as fh:
+                json.dump(r, fh, indent=1)
+        return r
 
     # nerf.py:503-530
     def display(self, save=True, maps=False):
