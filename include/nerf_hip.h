@@ -729,6 +729,103 @@ int nerf_hip_points_nearest(const float* query, int64_t M, int64_t N, const floa
 int nerf_hip_distance_stats(const double* dist2, int64_t N, double unit, const double* tau, int K, int64_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Rays against a mesh: closest hit and occlusion over a uniform grid of triangles, the visibility of faces from a
+ * camera and the selection of faces.  Any indexed mesh (verts[V][3] fp32, faces[F][3] int32, V, F < 2^31),
+ * fewer than 2^31 rays.  All arithmetic below is fp64 on the fp32 inputs widened exactly; every product, quotient, sum and difference
+ * is rounded on its own and evaluated as bracketed; (a x b) = (ay bz - az by, az bx - ax bz, ax by - ay bx).  There is no float atomic:
+ * every output is a pure function of the input, identical bits from run to run.  Every comparison is false on NaN.
+ *
+ * R. THE HIT RULE, a function of one ray and one face only.
+ * 1. A face TAKES PART iff its three indices lie in [0, V) (others are never used as an address) and its nine coordinates are finite
+ *    (the indices may repeat: such a face has det == 0 and is never hit).  A ray TAKES PART iff its origin o and direction d (fp32,
+ *    d not normalised: t is in units of d) are six finite numbers and d != 0.
+ * 2. With the corners A, B, C of indices i0, i1, i2 (Moeller-Trumbore):
+ *       e1 = B - A,  e2 = C - A,  p = d x e2,  det = (e1x px + e1y py) + e1z pz,  s = o - A,  q = s x e1
+ *       u = ((sx px + sy py) + sz pz) / det,   v = ((dx qx + dy qy) + dz qz) / det,   t = ((e2x qx + e2y qy) + e2z qz) / det
+ *       h_k = o_k + t * d_k per axis k,        e = 2^-20 * the largest |coordinate| of the face's nine
+ *    The ray HITS the face iff det != 0, u >= 0, v >= 0, u + v <= 1, tmin <= t <= tmax and on every axis
+ *    min(A_k, B_k, C_k) - e <= h_k <= max(A_k, B_k, C_k) + e: a hit whose computed point is not on its triangle is no hit.  (That last
+ *    condition is what lets a grid reproduce brute force exactly; it changed no answer on the test meshes.)
+ * 3. A ray's answer is the hit with the smallest t, among equal t the LOWEST face index.  skip[N] (int32, may be NULL): ray i ignores
+ *    face skip[i].  Outputs: t[N] fp64, uv[N][2] fp64 = (u, v), face[N] int32, side[N] int8 = +1 for det > 0 (the ray meets the
+ *    counter-clockwise side), -1 for det < 0.  No hit, or a ray that takes no part: t = +inf, uv = 0, face = -1, side = 0.
+ * 4. any_hit != 0: the only output is occluded[N] uint8 = (face >= 0 of the closest-hit call); the walk stops at the first hit.
+ * 5. This is NOT a watertight test: u, v of two faces that share an edge are rounded independently, so a ray through the edge can
+ *    in principle miss both.
+ *
+ * G. THE TRIANGLE GRID is an accelerator and never changes an output: lo[3] (fp32, finite), ONE cell size (fp32, > 0, finite) and
+ *    dims[3] (>= 1 each, product < 2^31), any values.  cellidx_k(x) = floor((x - double(lo_k)) / double(cell)), not clamped.  The
+ *    index box of a face that takes part is [cellidx_k(min_k - e), cellidx_k(max_k + e)] per axis with min, max and e of R.2.  A face
+ *    whose box lies in [0, dims_k - 1] on every axis is INSIDE and is entered in every cell of its box; any other goes to the OUTSIDE
+ *    list, which every ray tests in full; a face that takes no part is entered nowhere.  nerf_hip_mesh_raycast_grid_count returns
+ *    counts (DEVICE int64[3]) = the faces that take part, the entries E (the sum of the INSIDE faces' box volumes), the OUTSIDE faces;
+ *    the host reads E (it must be < 2^31) and sizes the workspace; nerf_hip_mesh_raycast_grid_fill counts the cells' entries by integer
+ *    atomics, scans them and places the entries through per-cell cursor atomics.  The order of the entries inside a cell is not defined
+ *    and nothing depends on it.  Nothing is stored past cap_entries (a cap below E leaves a grid that misses faces).  The callers'
+ *    sizing rule (mesh.raycast_grid in the Python package): C.2's rule of the block above over the finite vertices' box grown by 2^-19
+ *    of its largest |coordinate| on every side (more than e: no face with finite corners is OUTSIDE), with m = F, the cell doubled
+ *    while E > 4 F + 64.  The cast call walks the ray through the cells in intervals of t; the proof that the result is the
+ *    brute-force answer over all faces for every grid is at the top of csrc/mesh_raycast.hip.
+ *
+ * V. FACE VISIBILITY FROM A CAMERA (nerf_hip_mesh_face_rays): one shadow ray per face.  cam_o[3] (HOST fp32) is the camera's position
+ *    and Q (HOST fp64 3x3, row-major) maps a world direction to homogeneous pixel coordinates: with the ray rule of nerf_hip_rays,
+ *    p_j = (x K[j] + y K[3 + j]) + K[6 + j] and the world direction R p, Q = inverse(R K^T), formed by the caller.  Per face that takes
+ *    part: G = ((A + B) + C) / 3.0, N = e1 x e2, w = double(cam_o) - G; FACING iff (Nx wx + Ny wy) + Nz wz > 0; m = Q (-w) row by row as
+ *    (Q_i0 a + Q_i1 b) + Q_i2 c; IN VIEW iff m_2 > 0, -0.5 <= m_0 / m_2 < H - 0.5 and -0.5 <= m_1 / m_2 < W - 0.5 (x is the row: quirk
+ *    Q2).  Outputs: orig[F][3] = fp32(G), valid[F] uint8 = facing and in view, dir[F][3] = fp32(double(cam_o) - double(orig)) for a valid
+ *    face and 0 for any other; a face that takes no part gets orig = 0 as well.  The caller then casts (orig, dir) in any-hit mode
+ *    with skip = the face itself over [tmin, 1]: the face is seen from this camera iff valid and not occluded.  tmin keeps the
+ *    segment off the surface it starts on; the package's default 1e-4 of the segment is a choice, not a measurement.
+ *
+ * S. FACE SELECTION (nerf_hip_mesh_select_faces_count / _emit) with keep[F] uint8: a face is kept iff keep[f] != 0 and its three
+ *    indices lie in [0, V); a vertex is kept iff a kept face uses it.  Both keep their order, the faces are renumbered, normals and
+ *    rgb are carried where given.  The count call returns counts (DEVICE int64[2]) = V', F'; the emit call stores nothing past max_v /
+ *    max_f rows.
+ *
+ * All calls are enqueue-only on the caller's stream and check every argument on the host before anything is enqueued
+ * (NERF_HIP_ERR_ARG: sizes, NULL arrays, lo / cell / dims / cam_o / Q outside the limits above, tmin or tmax NaN, workspace NULL or not
+ * 256-byte aligned, int64 / fp64 outputs not 8-byte aligned; NERF_HIP_ERR_WORKSPACE: workspace too small).  Indices read from device
+ * arrays are range-checked by the kernels before use and every store is clamped to its capacity.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of workspace (256-byte aligned) of the fill and cast calls: 8 per cell, 4 per entry, 4 per face (the OUTSIDE list), 8 per 2048
+ * cells or faces (the scans), 16 more. */
+int nerf_hip_mesh_raycast_ws_bytes(int64_t F, int64_t cap_entries, const int* dims3, size_t* bytes);
+
+/* G: counts (DEVICE int64[3]).  lo3, dims3: HOST arrays.  Needs no workspace. */
+int nerf_hip_mesh_raycast_grid_count(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
+                                     const int* dims3, int64_t* counts, void* stream);
+
+/* G: the grid into the workspace. */
+int nerf_hip_mesh_raycast_grid_fill(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
+                                    const int* dims3, int64_t cap_entries, void* ws, size_t ws_bytes, void* stream);
+
+/* R: origins, dirs [N][3] fp32 against the grid a fill call with the same mesh, lo3, cell, dims3, cap_entries and workspace left.
+ * any_hit == 0: t[cap_n], uv[cap_n][2], face[cap_n], side[cap_n] (occluded may be NULL); otherwise occluded[cap_n] (the others may be
+ * NULL).  tmin, tmax: fp64, infinite ends allowed. */
+int nerf_hip_mesh_raycast(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell, const int* dims3,
+                          int64_t cap_entries, const void* ws, size_t ws_bytes, const float* origins, const float* dirs,
+                          const int32_t* skip, int64_t N, double tmin, double tmax, int any_hit, double* t, double* uv, int32_t* face,
+                          int8_t* side, uint8_t* occluded, int64_t cap_n, void* stream);
+
+/* V: orig[cap_f][3], dir[cap_f][3] fp32, valid[cap_f] uint8.  cam_o3: HOST fp32[3]; Q9: HOST fp64[9]. */
+int nerf_hip_mesh_face_rays(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* cam_o3, const double* Q9, int H,
+                            int W, float* orig, float* dir, uint8_t* valid, int64_t cap_f, void* stream);
+
+/* Bytes of workspace (256-byte aligned) of the two selection calls: 8 per vertex, 8 per 2048 vertices or faces, 16 more. */
+int nerf_hip_mesh_select_faces_ws_bytes(int64_t V, int64_t F, size_t* bytes);
+
+/* S: counts (DEVICE int64[2]) = V', F'. */
+int nerf_hip_mesh_select_faces_count(const int32_t* faces, int64_t V, int64_t F, const uint8_t* keep, void* ws, size_t ws_bytes,
+                                     int64_t* counts, void* stream);
+
+/* S: out_verts / out_normals / out_rgb [max_v][3] (the latter two only where normals / rgb are given), out_faces[max_f][3].  Needs no
+ * count call before it. */
+int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
+                                    const uint8_t* keep, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_rgb,
+                                    int32_t* out_faces, int64_t max_v, int64_t max_f, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path
  * table can be parity-checked on its own).
  * ------------------------------------------------------------------------------------------- */

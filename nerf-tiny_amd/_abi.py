@@ -86,6 +86,16 @@ _PROTOS = {
     "nerf_hip_points_grid_build": (C.c_int, [_p, C.c_int64, _p, C.c_float, _p, _p, C.c_size_t, _p, _p]),
     "nerf_hip_points_nearest": (C.c_int, [_p, C.c_int64, C.c_int64, _p, C.c_float, _p, _p, C.c_size_t, C.c_int, _p, _p, C.c_int64, _p]),
     "nerf_hip_distance_stats": (C.c_int, [_p, C.c_int64, C.c_double, _p, C.c_int, _p, _p]),
+    "nerf_hip_mesh_raycast_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, _p, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_raycast_grid_count": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, _p, _p]),
+    "nerf_hip_mesh_raycast_grid_fill": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, C.c_int64, _p, C.c_size_t, _p]),
+    "nerf_hip_mesh_raycast": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, C.c_float, _p, C.c_int64, _p, C.c_size_t, _p, _p, _p, C.c_int64,
+                                        C.c_double, C.c_double, C.c_int, _p, _p, _p, _p, _p, C.c_int64, _p]),
+    "nerf_hip_mesh_face_rays": (C.c_int, [_p, _p, C.c_int64, C.c_int64, _p, _p, C.c_int, C.c_int, _p, _p, _p, C.c_int64, _p]),
+    "nerf_hip_mesh_select_faces_ws_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "nerf_hip_mesh_select_faces_count": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_mesh_select_faces_emit": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, _p, _p, C.c_size_t, _p, _p, _p, _p, C.c_int64, C.c_int64,
+                                                  _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -182,6 +192,20 @@ def mesh_sample_ws_bytes(F: int) -> int:
     """Workspace bytes of nerf_hip_mesh_sample on a mesh of F faces."""
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_sample_ws_bytes(int(F), C.byref(n)))
+    return int(n.value)
+
+
+def mesh_raycast_ws_bytes(F: int, cap_entries: int, dims) -> int:
+    """Workspace bytes of nerf_hip_mesh_raycast_grid_fill / nerf_hip_mesh_raycast for F faces, cap_entries grid entries and a grid of dims cells."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_raycast_ws_bytes(int(F), int(cap_entries), i32_array(dims), C.byref(n)))
+    return int(n.value)
+
+
+def mesh_select_faces_ws_bytes(V: int, F: int) -> int:
+    """Workspace bytes of nerf_hip_mesh_select_faces_count / _emit on a mesh of V vertices and F faces."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_mesh_select_faces_ws_bytes(int(V), int(F), C.byref(n)))
     return int(n.value)
 
 

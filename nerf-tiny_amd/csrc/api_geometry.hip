@@ -1,6 +1,6 @@
 // api_geometry.hip -- the geometry part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h): point and gradient queries,
 // density grids, marching cubes, the narrow band, mesh components, mesh simplification, mesh edges / smoothing / normals, mesh
-// measures / samples / nearest points / distance statistics and image metrics.  Host code only, as api.hip: argument checks,
+// measures / samples / nearest points / distance statistics, ray casting / face visibility / face selection and image metrics.  Host code only, as api.hip: argument checks,
 // workspace carve-up and kernel sequencing on the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -1108,6 +1108,265 @@ int nerf_hip_distance_stats(const double* dist2, int64_t N, double unit, const d
   a.K = K;
   a.out = reinterpret_cast<long long*>(out);
   HIP_TRY(launch_md_stats(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Workspace of the ray-casting calls: per cell 8 bytes (count / cursor 4, start 4), per entry 4 (a face index), per face 4 (the OUTSIDE
+// list), 8 per CC_PTS cells or faces, whichever are more (the scans), and 16 for the two totals.
+struct RcLayout {
+  size_t cnt, start, entries, outside, tot, base, info, total;
+  long long ncell;
+};
+RcLayout rc_layout(long long F, long long E, const int* dims3) {
+  RcLayout L;
+  L.ncell = (long long)dims3[0] * dims3[1] * dims3[2];
+  const int nb = cc_blocks(L.ncell > F ? L.ncell : F);
+  Carve c;
+  L.cnt = c.take((size_t)L.ncell * 4);
+  L.start = c.take(((size_t)L.ncell + 1) * 4);
+  L.entries = c.take((size_t)E * 4);
+  L.outside = c.take((size_t)F * 4);
+  L.tot = c.take((size_t)nb * 4);
+  L.base = c.take((size_t)nb * 4);
+  L.info = c.take(16);
+  L.total = c.o;
+  return L;
+}
+
+int check_rc_entries(int64_t cap_entries) {
+  if (cap_entries < 0 || cap_entries >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "cap_entries=%lld: the grid's entries in [0, 2^31)", (long long)cap_entries);
+  return NERF_HIP_OK;
+}
+
+int check_rc_mesh(const float* verts, const int32_t* faces, int64_t V, int64_t F) {
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  return NERF_HIP_OK;
+}
+
+RcGridArgs rc_grid_args(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell, const int* dims3) {
+  RcGridArgs a;
+  memset(&a, 0, sizeof(a));
+  a.verts = verts;
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.dims[c] = dims3[c];
+  }
+  a.cell = cell;
+  a.ncell = dims3[0] * dims3[1] * dims3[2];
+  return a;
+}
+
+void rc_grid_ws(RcGridArgs* a, int64_t cap_entries, void* ws, const RcLayout& L) {
+  a->cap_entries = cap_entries;
+  a->cnt = at<int>(ws, L.cnt);
+  a->start = at<int>(ws, L.start);
+  a->entries = at<int>(ws, L.entries);
+  a->outside = at<int>(ws, L.outside);
+  a->tot = at<int>(ws, L.tot);
+  a->base = at<int>(ws, L.base);
+  a->info = at<long long>(ws, L.info);
+}
+
+// Workspace of the face selection: per vertex 8 bytes (the used mark, the new index), 8 per CC_PTS vertices or faces, whichever are
+// more (the scans), and 16 for emit's throw-away totals.
+struct SelLayout {
+  size_t used, newidx, tot, base, scratch, total;
+};
+SelLayout sel_layout(long long V, long long F) {
+  SelLayout L;
+  const int nb = cc_blocks(V > F ? V : F);
+  Carve c;
+  L.used = c.take((size_t)V * 4);
+  L.newidx = c.take((size_t)V * 4);
+  L.tot = c.take((size_t)nb * 4);
+  L.base = c.take((size_t)nb * 4);
+  L.scratch = c.take(16);
+  L.total = c.o;
+  return L;
+}
+
+int check_sel(const int32_t* faces, int64_t V, int64_t F, const uint8_t* keep, const void* ws, size_t ws_bytes, SelLayout* L) {
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (F > 0 && (!faces || !keep)) return fail(NERF_HIP_ERR_ARG, "faces / keep is null");
+  *L = sel_layout(V, F);
+  return check_ws(ws, ws_bytes, L->total);
+}
+
+SelArgs sel_args(const int32_t* faces, int64_t V, int64_t F, const uint8_t* keep, void* ws, const SelLayout& L) {
+  SelArgs a;
+  memset(&a, 0, sizeof(a));
+  a.faces = faces;
+  a.keep = keep;
+  a.V = (int)V;
+  a.F = (int)F;
+  a.used = at<int>(ws, L.used);
+  a.newidx = at<int>(ws, L.newidx);
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_raycast_ws_bytes(int64_t F, int64_t cap_entries, const int* dims3, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_sizes(0, F)) return rc;
+  if (int rc = check_rc_entries(cap_entries)) return rc;
+  if (int rc = check_md_dims(dims3)) return rc;
+  *bytes = rc_layout(F, cap_entries, dims3).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_raycast_grid_count(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
+                                     const int* dims3, int64_t* counts, void* stream) {
+  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
+  if (int rc = check_out(counts, "counts", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  RcGridArgs a = rc_grid_args(verts, faces, V, F, lo3, cell, dims3);
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_rc_grid_count(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_raycast_grid_fill(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
+                                    const int* dims3, int64_t cap_entries, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
+  if (int rc = check_rc_entries(cap_entries)) return rc;
+  const RcLayout L = rc_layout(F, cap_entries, dims3);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (int rc = check_device()) return rc;
+  RcGridArgs a = rc_grid_args(verts, faces, V, F, lo3, cell, dims3);
+  rc_grid_ws(&a, cap_entries, ws, L);
+  HIP_TRY(launch_rc_grid_fill(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_raycast(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell, const int* dims3,
+                          int64_t cap_entries, const void* ws, size_t ws_bytes, const float* origins, const float* dirs,
+                          const int32_t* skip, int64_t N, double tmin, double tmax, int any_hit, double* t, double* uv, int32_t* face,
+                          int8_t* side, uint8_t* occluded, int64_t cap_n, void* stream) {
+  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
+  if (int rc = check_rc_entries(cap_entries)) return rc;
+  if (N < 0 || N >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "N=%lld: a ray count in [0, 2^31)", (long long)N);
+  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (tmin != tmin || tmax != tmax) return fail(NERF_HIP_ERR_ARG, "tmin=%g tmax=%g: the window's ends may be infinite, not NaN", tmin, tmax);
+  if (N > 0 && (!origins || !dirs)) return fail(NERF_HIP_ERR_ARG, "origins / dirs is null");
+  if (N > 0 && cap_n > 0) {
+    if (any_hit) {
+      if (!occluded) return fail(NERF_HIP_ERR_ARG, "occluded is null");
+    } else {
+      if (!t || !uv || !face || !side) return fail(NERF_HIP_ERR_ARG, "t / uv / face / side is null");
+      if ((((uintptr_t)t | (uintptr_t)uv) & 7) != 0) return fail(NERF_HIP_ERR_ARG, "t and uv must be 8-byte aligned");
+    }
+  }
+  const RcLayout L = rc_layout(F, cap_entries, dims3);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (int rc = check_device()) return rc;
+  RcCastArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = rc_grid_args(verts, faces, V, F, lo3, cell, dims3);
+  rc_grid_ws(&a.g, cap_entries, const_cast<void*>(ws), L);
+  a.orig = origins;
+  a.dir = dirs;
+  a.skip = skip;
+  a.N = N;
+  a.cap_n = cap_n;
+  a.tmin = tmin;
+  a.tmax = tmax;
+  a.t = t;
+  a.uv = uv;
+  a.face = face;
+  a.side = reinterpret_cast<signed char*>(side);
+  a.occluded = occluded;
+  HIP_TRY(launch_rc_cast(a, any_hit != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_face_rays(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* cam_o3, const double* Q9, int H,
+                            int W, float* orig, float* dir, uint8_t* valid, int64_t cap_f, void* stream) {
+  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (!cam_o3 || !Q9) return fail(NERF_HIP_ERR_ARG, "cam_o3 / Q9 is null");
+  for (int c = 0; c < 3; ++c)
+    if (!isfinite(cam_o3[c])) return fail(NERF_HIP_ERR_ARG, "cam_o[%d]=%g: the camera's position must be finite", c, (double)cam_o3[c]);
+  for (int c = 0; c < 9; ++c)
+    if (!isfinite(Q9[c])) return fail(NERF_HIP_ERR_ARG, "Q[%d]=%g: the camera's matrix must be finite", c, Q9[c]);
+  if (H < 1 || W < 1) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: an image has at least one pixel", H, W);
+  if (cap_f < 0) return fail(NERF_HIP_ERR_ARG, "cap_f=%lld: a capacity must be >= 0", (long long)cap_f);
+  if (F > 0 && cap_f > 0 && (!orig || !dir || !valid)) return fail(NERF_HIP_ERR_ARG, "orig / dir / valid is null");
+  if (int rc = check_device()) return rc;
+  RcFaceRaysArgs a;
+  memset(&a, 0, sizeof(a));
+  a.verts = verts;
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  for (int c = 0; c < 3; ++c) a.cam[c] = cam_o3[c];
+  for (int c = 0; c < 9; ++c) a.Q[c] = Q9[c];
+  a.H = H;
+  a.W = W;
+  a.orig = orig;
+  a.dir = dir;
+  a.valid = valid;
+  a.cap_f = cap_f;
+  HIP_TRY(launch_rc_face_rays(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_select_faces_ws_bytes(int64_t V, int64_t F, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  *bytes = sel_layout(V, F).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_select_faces_count(const int32_t* faces, int64_t V, int64_t F, const uint8_t* keep, void* ws, size_t ws_bytes,
+                                     int64_t* counts, void* stream) {
+  SelLayout L;
+  if (int rc = check_sel(faces, V, F, keep, ws, ws_bytes, &L)) return rc;
+  if (int rc = check_out(counts, "counts", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  SelArgs a = sel_args(faces, V, F, keep, ws, L);
+  a.counts = reinterpret_cast<long long*>(counts);
+  HIP_TRY(launch_sel_count(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
+                                    const uint8_t* keep, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_rgb,
+                                    int32_t* out_faces, int64_t max_v, int64_t max_f, void* stream) {
+  SelLayout L;
+  if (int rc = check_sel(faces, V, F, keep, ws, ws_bytes, &L)) return rc;
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (max_v > 0 && (!out_verts || (normals && !out_normals) || (rgb && !out_rgb))) return fail(NERF_HIP_ERR_ARG, "an output of max_v rows is null");
+  if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
+  if (int rc = check_device()) return rc;
+  SelArgs a = sel_args(faces, V, F, keep, ws, L);
+  a.verts = verts;
+  a.normals = normals;
+  a.rgb = rgb;
+  a.counts = at<long long>(ws, L.scratch);
+  a.out_verts = out_verts;
+  a.out_normals = out_normals;
+  a.out_rgb = out_rgb;
+  a.out_faces = out_faces;
+  a.max_v = max_v;
+  a.max_f = max_f;
+  HIP_TRY(launch_sel_emit(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

@@ -605,6 +605,69 @@ struct MdStatsArgs {
 
 hipError_t launch_md_stats(const MdStatsArgs& a, hipStream_t st);
 
+// ---- ray casting against an indexed mesh, face visibility and face selection (mesh_raycast.hip; nerf_hip_mesh_raycast*,
+// nerf_hip_mesh_face_rays, nerf_hip_mesh_select_faces_*).  The component calls' workgroup shape. ----
+struct RcGridArgs {
+  const float* verts;      // [V][3]
+  const int* faces;        // [F][3]
+  int V, F;
+  float lo[3], cell;       // the grid: corner and the one cell size
+  int dims[3];
+  int ncell;               // dims[0] * dims[1] * dims[2] < 2^31
+  long long cap_entries;   // the entries the workspace holds (< 2^31)
+  // workspace
+  int *cnt, *start;        // [ncell] entries per cell (then the placement's cursors); [ncell + 1] a cell's first entry
+  int* entries;            // [cap_entries] face indices, cell by cell; the order inside a cell is not defined
+  int* outside;            // [F] the OUTSIDE faces, ascending
+  int *tot, *base;         // [cc_blocks(max(ncell, F))]
+  long long* info;         // [2] = the entries the scan counted, the OUTSIDE faces
+  long long* counts;       // count only: [3] = faces that take part, entries E, OUTSIDE faces
+};
+
+struct RcCastArgs {
+  RcGridArgs g;
+  const float *orig, *dir; // [N][3]
+  const int* skip;         // [N] or null: the face ray i ignores
+  long long N, cap_n;
+  double tmin, tmax;
+  double *t, *uv;          // [cap_n], [cap_n][2] (closest hit)
+  int* face;               // [cap_n]
+  signed char* side;       // [cap_n]
+  unsigned char* occluded; // [cap_n] (any hit)
+};
+
+struct RcFaceRaysArgs {
+  const float* verts;
+  const int* faces;
+  int V, F;
+  float cam[3];
+  double Q[9];             // row-major
+  int H, W;
+  float *orig, *dir;       // [cap_f][3]
+  unsigned char* valid;    // [cap_f]
+  long long cap_f;
+};
+
+struct SelArgs {
+  const float *verts, *normals, *rgb;  // [V][3]; normals / rgb (with their outputs) may be null (emit)
+  const int* faces;        // [F][3]
+  const unsigned char* keep;  // [F]
+  int V, F;
+  int *used, *newidx;      // [V] 1 where a kept face uses the vertex; its rank among those, -1 for any other (workspace)
+  int *tot, *base;         // [cc_blocks(max(V, F))] (workspace)
+  long long* counts;       // count: [2] = V', F'; emit: the workspace's throw-away totals
+  float *out_verts, *out_normals, *out_rgb;  // [max_v][3]
+  int* out_faces;          // [max_f][3]
+  long long max_v, max_f;
+};
+
+hipError_t launch_rc_grid_count(const RcGridArgs& a, hipStream_t st);
+hipError_t launch_rc_grid_fill(const RcGridArgs& a, hipStream_t st);
+hipError_t launch_rc_cast(const RcCastArgs& a, bool any_hit, hipStream_t st);
+hipError_t launch_rc_face_rays(const RcFaceRaysArgs& a, hipStream_t st);
+hipError_t launch_sel_count(const SelArgs& a, hipStream_t st);
+hipError_t launch_sel_emit(const SelArgs& a, hipStream_t st);
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

@@ -61,30 +61,6 @@ __device__ inline long long md_wave_sum(long long x) {
   return x;
 }
 
-// exclusive prefix of v across the workgroup in thread order, plus the workgroup's total; part[CC_WG / 64] of LDS, ends with a barrier
-template <class T>
-__device__ inline T md_wg_prefix(T v, T* part, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) part[wave] = x;
-  __syncthreads();
-  T before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CC_WG / 64; ++w) {
-    const T t = part[w];
-    before += (w < wave) ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + x - v;
-}
-
 __device__ inline bool md_finite3(const float (&p)[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
 // does face f take part?  -> its corners' coordinates in p[corner][axis]
@@ -201,7 +177,7 @@ __global__ __launch_bounds__(CC_WG) void k_md_wsum(const MdMeshArgs a) {
   for (int r = 0; r < CC_ROUNDS; ++r) {
     const long long f = base + r * CC_WG + threadIdx.x;
     long long total;
-    (void)md_wg_prefix<long long>(f < a.F ? md_weight(a, f) : 0, part, total);
+    (void)wg_prefix_sum<long long>(f < a.F ? md_weight(a, f) : 0, part, total);
     run += total;
   }
   if (threadIdx.x == 0) a.tot[blockIdx.x] = run;
@@ -216,7 +192,7 @@ __global__ __launch_bounds__(CC_WG) void k_md_cum(const MdMeshArgs a) {
     const long long f = base + r * CC_WG + threadIdx.x;
     const long long w = f < a.F ? md_weight(a, f) : 0;
     long long total;
-    const long long pre = md_wg_prefix<long long>(w, part, total);
+    const long long pre = wg_prefix_sum<long long>(w, part, total);
     if (f < a.F) a.cum[f] = run + pre + w;
     run += total;
   }
@@ -288,7 +264,7 @@ __global__ __launch_bounds__(CC_WG) void k_pn_cellsum(const int* __restrict__ cn
     const long long c = base + r * CC_WG + threadIdx.x;
     const int v = c < ncell ? md_count(cnt, c, n) : 0;
     long long total;
-    (void)md_wg_prefix<long long>(v, part, total);
+    (void)wg_prefix_sum<long long>(v, part, total);
     run += total;
     top = v > top ? v : top;
   }
@@ -312,7 +288,7 @@ __global__ __launch_bounds__(CC_WG) void k_pn_offsets(int* __restrict__ cnt, int
     const long long c = base + r * CC_WG + threadIdx.x;
     const int v = c < ncell ? md_count(cnt, c, n) : 0;
     long long total;
-    const long long pre = md_wg_prefix<long long>(v, part, total);
+    const long long pre = wg_prefix_sum<long long>(v, part, total);
     if (c < ncell) {
       start[c] = (int)(run + pre > n ? n : run + pre);
       cnt[c] = 0;

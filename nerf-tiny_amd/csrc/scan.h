@@ -1,6 +1,8 @@
 // scan.h -- the scan and compaction scaffolding of the geometry kernels (mesh.hip, band.hip, mesh_cc.hip, mesh_simplify.hip,
-// mesh_smooth.hip, mesh_distance.hip).  Included by those six translation units only, never by a render or training one.
+// mesh_smooth.hip, mesh_distance.hip, mesh_raycast.hip).  Included by those seven translation units only, never
+// by a render or training one.
 //   lane_prefix / wg_prefix     exclusive prefix of a small per-lane count inside the wave / the workgroup, in item order
+//   wg_prefix_sum               the same for a value of any size (weights, per-cell counts) across a workgroup of CC_WG
 //   Totals / scan_totals        channels of workgroup totals -> exclusive bases and the grand totals, by ONE workgroup of 1024
 //   k_flag_count / k_flag_scan / k_flag_place   compaction over a 0/1 flag per item in three launches: totals per workgroup of CC_PTS
 //                               items, the scan of the totals, then the placement (scan_count: the first two, scan_place: all three)
@@ -58,6 +60,31 @@ __device__ inline int wg_prefix(int v, int* part, int& total) {
   }
   __syncthreads();
   return before + pre;
+}
+
+// Exclusive prefix of v across a workgroup of CC_WG in thread order, plus the workgroup's total; part[CC_WG / 64] of LDS, ends with a
+// barrier.
+template <class T>
+__device__ inline T wg_prefix_sum(T v, T* part, T& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T y = __shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) part[wave] = x;
+  __syncthreads();
+  T before = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < CC_WG / 64; ++w) {
+    const T t = part[w];
+    before += (w < wave) ? t : 0;
+    total += t;
+  }
+  __syncthreads();
+  return before + x - v;
 }
 
 // One channel of the scan of workgroup totals: tot [nb] -> base [nb], base[b] = the sum of tot[0 .. b) (base null: the grand total only)

@@ -64,6 +64,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-keep-largest", type=int, default=None, metavar="K",
                     help="--mesh keeps only the K connected components with the most faces (ties: the lower component id; combines with "
                          "--mesh-min-faces; default: keep everything)")
+    ap.add_argument("--mesh-visible", nargs="?", const="train", default=None, choices=["train", "val", "test"], metavar="SPLIT",
+                    help="--mesh drops the faces that no camera of SPLIT (train, val or test; default train) sees: one shadow ray per face "
+                         "and camera on the device, after the floaters are dropped and before smoothing, simplification, normals and "
+                         "colours; prints the number of faces seen (default: keep everything)")
     ap.add_argument("--mesh-compare", default=None, metavar="FILE",
                     help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
                          "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
@@ -126,7 +130,7 @@ if __name__ == "__main__":
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
                              simplify=args.mesh_simplify, smooth=args.mesh_smooth, compare=args.mesh_compare,
-                             compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau))
+                             compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible)
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

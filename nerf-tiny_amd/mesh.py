@@ -3,7 +3,8 @@ csrc/mesh.hip), connected components on the device -- labe
 DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the device (csrc/mesh_simplify.hip),
 edge topology, Taubin smoothing and face-derived vertex normals on the device (csrc/mesh_smooth.hip), geometry
 evaluation on the device -- measures, area-weighted surface samples, exact nearest points, Chamfer distance and F-scores
-(csrc/mesh_distance.hip) -- and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
+(csrc/mesh_distance.hip) --, rays against a mesh on the device -- closest hits, occlusion, depth images, the
+faces no camera sees (csrc/mesh_raycast.hip) -- and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
 build on these."""
 from __future__ import annotations
 
@@ -461,6 +462,160 @@ def compare(m_a, m_b, n=200_000, seed=0, thresholds=()):
     out = chamfer(pa, pb, thresholds)
     out.update(samples=int(n), seed=int(seed), measure_a=measure(m_a), measure_b=measure(m_b))
     return out
+
+
+class Raycaster(NamedTuple):
+    verts: object    # [V, 3] fp32 (device): the mesh the grid was built over
+    faces: object    # [F, 3] int32
+    lo: object       # [3] fp32 numpy: the grid's corner
+    cell: object     # fp32: its one cell size
+    dims: tuple      # (3 ints): its cells per axis
+    entries: int     # E: the (face, cell) pairs of the INSIDE faces
+    taking_part: int  # faces with indices in range and finite corners
+    outside: int     # faces that reach out of the grid: every ray tests them in full
+    ws: object       # the device workspace that holds the grid
+
+
+def raycast_grid(verts, faces, count=None):
+    """The sizing rule of build_raycast()'s triangle grid -> (lo [3] fp32, cell fp32, dims (3 ints)): grid_rule over the finite vertices'
+    box, grown by 2^-19 of its largest |coordinate| on every side, with m = F (about one cell per face), the cell doubled while the
+    entries E -- the sum over the faces of the cells their boxes touch -- exceed 4 F + 64.  With this box no face with finite
+    corners is OUTSIDE (the growth covers the 2^-20 by which the hit rule widens a face's box).  count(lo, cell, dims) -> E; by default the device's count
+    call (nerf_hip_mesh_raycast_grid_count: one 24-byte read per attempt), for which CPU tensors raise."""
+    from . import ops
+
+    verts, faces = torch.as_tensor(verts), torch.as_tensor(faces)
+    if count is None:
+        _on_device(verts, "raycast_grid")
+        count = lambda lo, cell, dims: int(ops.mesh_raycast_count(verts, faces, lo.tolist(), float(cell), dims).cpu()[1])
+    blo, bhi, n = _cloud_box(verts)
+    F = int(faces.shape[0])
+    # the box grows by 2^-19 of its largest |coordinate| on every side: more than the 2^-20 by which the hit rule widens a face's box
+    pad = np.float32(2.0 ** -19) * np.float32(max(np.abs(blo).max(), np.abs(bhi).max()))
+    blo, bhi = (blo - pad).astype(np.float32), (bhi + pad).astype(np.float32)
+    lo, cell, dims = grid_rule(blo, bhi, F if n > 0 else 0)
+    ext = bhi.astype(np.float64) - blo.astype(np.float64)
+    top = np.float32(2.0 ** 127)
+    while F > 0 and n > 0 and cell < top and count(lo, cell, dims) > 4 * F + 64:
+        cell = np.float32(cell * np.float32(2.0))
+        dims = tuple(int(np.floor(e / np.float64(cell))) + 1 if e > 0 else 1 for e in ext)
+    return lo, np.float32(cell), dims
+
+
+def build_raycast(m, grid=None):
+    """A Raycaster over the Mesh m (any indexed mesh) on the DEVICE: the faces entered in the cells of a uniform grid, grid = (lo, cell,
+    dims) or by default raycast_grid(m.verts, m.faces).  The grid is an accelerator only: raycast() gives the brute-force answer over
+    all faces for every grid (include/nerf_hip.h, rule G; the proof is at the top of csrc/mesh_raycast.hip).  One host read of the
+    grid's sizes.  The mesh must not change while the Raycaster is used.  A CPU tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = _on_device(m.verts, "build_raycast"), torch.as_tensor(m.faces)
+    verts = verts.to(torch.float32).contiguous()
+    faces = faces.contiguous()
+    lo, cell, dims = raycast_grid(verts, faces) if grid is None else grid
+    lo = np.asarray(lo, np.float32).reshape(3)
+    dims = tuple(int(d) for d in dims)
+    part, E, out = (int(x) for x in ops.mesh_raycast_count(verts, faces, lo.tolist(), float(cell), dims).cpu())
+    if E >= 2 ** 31:
+        raise ValueError(f"build_raycast: the grid {dims} of cell {float(cell)!r} has {E} entries, at most 2^31 - 1 (use larger cells)")
+    ws = ops.mesh_raycast_fill(verts, faces, lo.tolist(), float(cell), dims, E)
+    return Raycaster(verts, faces, lo, np.float32(cell), dims, E, part, out, ws)
+
+
+def raycast(handle, origins, dirs, tmin=0.0, tmax=float("inf"), skip=None, any_hit=False):
+    """Casts rays against a Raycaster's mesh on the DEVICE: origins, dirs [N, 3] fp32 (dirs need not be normalised: t is in units of
+    dirs) -> (t [N] fp64, uv [N, 2] fp64, face [N] int32, side [N] int8): the closest hit with tmin <= t <= tmax, the lowest face
+    index among equal t; its barycentrics (the point is (1 - u - v) A + u B + v C); side +1 where the ray meets the counter-clockwise
+    (outer) side, -1 the other.  No hit, or a ray with a component that is not finite or dirs == 0: t = +inf, uv = 0, face = -1,
+    side = 0.  skip: int32 [N], ray i ignores face skip[i].  any_hit=True -> occluded [N] uint8 alone (= face >= 0; the walk stops
+    at the first hit).  The hit rule is Moeller-Trumbore in fp64 (include/nerf_hip.h, rule R), not a watertight test; every output
+    is a pure function of the input.  CPU tensors raise: there is no CPU path."""
+    from . import ops
+
+    origins, dirs = _on_device(origins, "raycast"), _on_device(dirs, "raycast")
+    if np.isnan(tmin) or np.isnan(tmax):
+        raise ValueError(f"tmin={tmin!r} tmax={tmax!r}: the window's ends may be infinite, not NaN")
+    h = handle
+    return ops.mesh_raycast(h.verts, h.faces, h.lo.tolist(), float(h.cell), h.dims, h.entries, h.ws, origins, dirs, tmin, tmax,
+                            None if skip is None else torch.as_tensor(skip).to(h.faces.device), any_hit)
+
+
+def camera_q(pose17, K_inv):
+    """-> (Q [3, 3] fp64 numpy, cam_o [3] fp32 numpy) of one camera: with the project's ray rule (pixel (x, y), x the row: p_j =
+    (x K[j] + y K[3 + j]) + K[6 + j] over the nine entries K of K_inv, world direction R p), Q = inverse(R K^T) maps a world direction to
+    homogeneous pixel coordinates; cam_o is the pose's translation."""
+    pb = np.asarray(torch.as_tensor(pose17).detach().cpu().numpy(), np.float32).reshape(17)
+    K = np.asarray(torch.as_tensor(K_inv).detach().cpu().numpy(), np.float32).reshape(3, 3).astype(np.float64)
+    P = pb[:15].reshape(3, 5)
+    return np.linalg.inv(P[:, :3].astype(np.float64) @ K.T), P[:, 3].copy()
+
+
+def camera_rays(poses_bound17, K_inv, H, W, device=None):
+    """The rays of every pixel of the cameras poses_bound17 [n, 17] (or [17]) through the project's own ray kernel (ops.rays) ->
+    (origins [n * H * W, 3], dirs [n * H * W, 3] fp32 on the device), pixel (row x, column y) of camera c at index (c * H + x) * W + y:
+    the origin is the pose's translation and the direction the unit d_wrd the renderer marches along, so t of raycast() is on the
+    scale of render(maps=True)'s depth."""
+    from . import ops
+
+    pb = torch.as_tensor(poses_bound17)
+    dev = torch.device(device) if device is not None else (pb.device if pb.device.type == "cuda" else torch.device("cuda"))
+    pb = pb.to(dev, torch.float32).reshape(-1, 17)
+    n, H, W = int(pb.shape[0]), int(H), int(W)
+    if n * H * W == 0:
+        return torch.empty(0, 3, device=dev), torch.empty(0, 3, device=dev)
+    row = torch.arange(H, device=dev).repeat_interleave(W).repeat(n)
+    col = torch.arange(W, device=dev).repeat(n * H)
+    per = pb.repeat_interleave(H * W, dim=0).contiguous()
+    _, d_wrd, _ = ops.rays(row, col, per, torch.as_tensor(K_inv), 2)
+    return per.view(-1, 17)[:, :15].reshape(-1, 3, 5)[:, :, 3].contiguous(), d_wrd
+
+
+def render_depth(handle, poses_bound17, K_inv, H, W):
+    """The mesh seen from the cameras poses_bound17 [n, 17]: raycast(handle, *camera_rays(...)) as images -> (t [n, H, W] fp64 -- +inf
+    where the pixel's ray meets no face --, face [n, H, W] int32, uv [n, H, W, 2] fp64): the mesh's depth along the rays whose expected
+    depth render(maps=True) gives."""
+    o, d = camera_rays(poses_bound17, K_inv, H, W, device=handle.faces.device)
+    t, uv, face, _ = raycast(handle, o, d)
+    n = o.shape[0] // max(int(H) * int(W), 1)
+    return t.view(n, H, W), face.view(n, H, W), uv.view(n, H, W, 2)
+
+
+def visibility(m, poses_bound, K_inv, H, W, tmin=1e-4):
+    """Which faces of the Mesh m does some camera see?  On the DEVICE, per camera of poses_bound [n, 17] with the H x W image of K_inv:
+    a face is VALID iff it takes part, faces the camera (its counter-clockwise side) and its centroid projects into the image; a
+    valid face is SEEN iff the segment from its centroid to the camera, over t in [tmin, 1] of the segment, meets no other face (an
+    any-hit cast with the face itself skipped).  tmin keeps the segment off the surface it starts on: the default 1e-4 of the segment
+    is a choice, not a measurement.  One shadow ray per face and camera -- the centroid stands for the face; pixel-ray visibility is
+    not built.  Returns (seen [F] bool on the device, per-camera counts of seen faces as a list of ints: one host read).  The exact
+    rules are in include/nerf_hip.h (rules V and R).  A CPU tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = _on_device(m.verts, "visibility"), torch.as_tensor(m.faces)
+    pb = torch.as_tensor(poses_bound).detach().cpu().reshape(-1, 17)
+    h = build_raycast(Mesh(verts, faces, None, None))
+    F = int(faces.shape[0])
+    own = torch.arange(F, dtype=torch.int32, device=h.faces.device)
+    seen = torch.zeros(F, dtype=torch.bool, device=h.faces.device)
+    counts = []
+    for c in range(pb.shape[0]):
+        Q, cam = camera_q(pb[c], K_inv)
+        orig, dirs, valid = ops.mesh_face_rays(h.verts, h.faces, cam.tolist(), Q.reshape(-1).tolist(), H, W)
+        vis = (valid != 0) & (raycast(h, orig, dirs, tmin, 1.0, skip=own, any_hit=True) == 0)
+        seen |= vis
+        counts.append(vis.sum())
+    counts = torch.stack(counts).cpu().tolist() if counts else []
+    return seen, counts
+
+
+def filter_faces(m, keep):
+    """The Mesh m restricted to the faces with keep[f] true (device compaction): kept faces and the vertices they use -- with their
+    normals and rgb where m has them -- stay in their order, face indices are renumbered, faces with an index outside [0, V) go.
+    One host read of the new sizes.  A CPU tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts = _on_device(m.verts, "filter_faces")
+    keep = torch.as_tensor(keep).to(verts.device) != 0
+    return Mesh(*ops.mesh_select_faces(verts, torch.as_tensor(m.faces), m.normals, m.rgb, keep))
 
 
 def _np(a):

@@ -614,7 +614,7 @@ class NeRFModel(nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None,
-                     smooth=None):
+                     smooth=None, visible=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -642,7 +642,13 @@ class NeRFModel(nn.Module):
         largest fp32 extent) take the lattice staircase and the field's noise out of the positions.  It runs AFTER the component filter
         and BEFORE simplify, so simplification clusters the denoised surface; with normals="grid" the normals are then mesh.smooth's
         (area-weighted, from the faces) -- averaged per cluster by simplify --, with normals="field" they are the field's gradient at
-        the final vertices as always.  The result is, bit for bit, the later stages applied to mesh.smooth of the earlier stages' mesh."""
+        the final vertices as always.  The result is, bit for bit, the later stages applied to mesh.smooth of the earlier stages' mesh.
+        visible=None: nothing more.  visible=(poses_bound [n, 17], K_inv, H, W): the faces that none of these cameras sees go, with the
+        vertices only they use -- interior sheets and pockets of the isosurface that hang on to the object, which the component filter
+        cannot drop (mesh.visibility with its default tmin: one shadow ray from each face's centroid to each camera, on the device;
+        then mesh.filter_faces).  It runs AFTER the component filter and BEFORE smoothing, simplification and the normal and colour
+        queries, so a hidden vertex is never evaluated.  With normals="grid" the kept vertices keep their grid normals.  The result
+        is, bit for bit, the later stages applied to mesh.filter_faces of the earlier stages' mesh."""
         import numpy as np
 
         from . import mesh
@@ -663,6 +669,11 @@ class NeRFModel(nn.Module):
             comps = mesh.components(faces, len(verts), verts)
             keep = mesh.select_components(comps, 1 if min_faces is None else min_faces, keep_largest)
             verts, faces, nrm, _ = mesh.filter_components(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), comps, keep)
+        if visible is not None:
+            poses_bound, K_inv, H, W = visible
+            m = mesh.Mesh(verts, faces, None if normals == "field" else nrm, None)
+            self.last_visibility = mesh.visibility(m, poses_bound, K_inv, H, W)
+            verts, faces, nrm, _ = mesh.filter_faces(m, self.last_visibility[0])
         if smooth is not None:
             (verts, faces, nrm, _), _ = mesh.smooth(mesh.Mesh(verts, faces, None, None), int(smooth), lo=lo32, scale=smooth_scale_of_grid(lo32, hi32),
                                                     normals=normals == "grid")  # (field normals are queried below)

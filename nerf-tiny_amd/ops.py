@@ -452,6 +452,114 @@ def points_nearest(query, num_ref, lo, cell, dims, ws, sort_queries=False):
     return idx, dist2
 
 
+def _rc_grid(lo, dims):
+    lo3, dims3 = _abi.f32_array(lo), _abi.i32_array(dims)
+    if len(lo3) != 3 or len(dims3) != 3:
+        raise ValueError("lo and dims have three entries each")
+    return lo3, dims3
+
+
+def mesh_raycast_count(verts, faces, lo, cell, dims, counts=None):
+    """The sizes of the triangle grid lo (three host floats) / cell (one float) / dims (three host ints) over an indexed mesh
+    (nerf_hip_mesh_raycast_grid_count; the definition is in include/nerf_hip.h) -> counts int64[3] ON THE DEVICE = the faces that take
+    part, the entries E, the OUTSIDE faces.  Enqueue only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    lo3, dims3 = _rc_grid(lo, dims)
+    if counts is None:
+        counts = torch.empty(3, dtype=torch.int64, device=faces.device)
+    _abi.check(_abi.lib().nerf_hip_mesh_raycast_grid_count(verts.data_ptr(), faces.data_ptr(), V, F, lo3, float(cell), dims3, counts.data_ptr(),
+                                                           _stream(faces)))
+    return counts
+
+
+def mesh_raycast_fill(verts, faces, lo, cell, dims, cap_entries, ws=None):
+    """Enters the faces in the cells of the triangle grid (nerf_hip_mesh_raycast_grid_fill) -> ws, a uint8 device buffer of >=
+    _abi.mesh_raycast_ws_bytes(F, cap_entries, dims) bytes (allocated here if None).  cap_entries: E of mesh_raycast_count.  Enqueue
+    only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    lo3, dims3 = _rc_grid(lo, dims)
+    if ws is None:
+        ws = torch.empty(_abi.mesh_raycast_ws_bytes(F, cap_entries, dims), dtype=torch.uint8, device=faces.device)
+    _abi.check(_abi.lib().nerf_hip_mesh_raycast_grid_fill(verts.data_ptr(), faces.data_ptr(), V, F, lo3, float(cell), dims3, int(cap_entries),
+                                                          ws.data_ptr(), ws.numel(), _stream(faces)))
+    return ws
+
+
+def mesh_raycast(verts, faces, lo, cell, dims, cap_entries, ws, origins, dirs, tmin=0.0, tmax=float("inf"), skip=None, any_hit=False):
+    """Casts the rays origins[N, 3] / dirs[N, 3] (fp32, device) against the mesh over the grid mesh_raycast_fill left in ws
+    (nerf_hip_mesh_raycast; the definition is in include/nerf_hip.h) -> (t[N] fp64, uv[N, 2] fp64, face[N] int32, side[N] int8), or
+    occluded[N] uint8 with any_hit.  skip: int32 [N] or None.  Enqueue only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    origins, dirs = _md_points(origins, "origins"), _md_points(dirs, "dirs")
+    N, dev = int(origins.shape[0]), faces.device
+    if tuple(dirs.shape) != (N, 3) or origins.device != dev or dirs.device != dev or ws.device != dev:
+        raise ValueError(f"origins {tuple(origins.shape)} on {origins.device}, dirs {tuple(dirs.shape)} on {dirs.device}: [N, 3] each on {dev}")
+    if skip is not None:
+        if tuple(skip.shape) != (N,) or skip.device != dev:
+            raise ValueError(f"skip {tuple(skip.shape)} on {skip.device}: [{N}] on {dev}")
+        skip = skip.to(torch.int32).contiguous()
+    lo3, dims3 = _rc_grid(lo, dims)
+    ptr = lambda a: None if a is None else a.data_ptr()
+    t = uv = face = side = occ = None
+    if any_hit:
+        occ = torch.empty(N, dtype=torch.uint8, device=dev)
+    else:
+        t = torch.empty(N, dtype=torch.float64, device=dev)
+        uv = torch.empty(N, 2, dtype=torch.float64, device=dev)
+        face = torch.empty(N, dtype=torch.int32, device=dev)
+        side = torch.empty(N, dtype=torch.int8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_raycast(verts.data_ptr(), faces.data_ptr(), V, F, lo3, float(cell), dims3, int(cap_entries), ws.data_ptr(),
+                                                ws.numel(), origins.data_ptr(), dirs.data_ptr(), ptr(skip), N, float(tmin), float(tmax),
+                                                1 if any_hit else 0, ptr(t), ptr(uv), ptr(face), ptr(side), ptr(occ), N, _stream(faces)))
+    return occ if any_hit else (t, uv, face, side)
+
+
+def mesh_face_rays(verts, faces, cam_o, Q, H, W):
+    """One shadow ray per face towards the camera at cam_o (three host floats) with Q (nine host doubles, row-major)
+    (nerf_hip_mesh_face_rays; the definition is in include/nerf_hip.h) -> (orig[F, 3], dir[F, 3] fp32, valid[F] uint8).  Enqueue only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    dev = faces.device
+    cam3 = _abi.f32_array(cam_o)
+    q9 = (C.c_double * 9)(*[float(x) for x in Q])
+    if len(cam3) != 3:
+        raise ValueError("cam_o has three entries")
+    orig = torch.empty(F, 3, device=dev)
+    dirs = torch.empty(F, 3, device=dev)
+    valid = torch.empty(F, dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_face_rays(verts.data_ptr(), faces.data_ptr(), V, F, cam3, q9, int(H), int(W), orig.data_ptr(),
+                                                  dirs.data_ptr(), valid.data_ptr(), F, _stream(faces)))
+    return orig, dirs, valid
+
+
+def mesh_select_faces(verts, faces, normals, rgb, keep, ws=None):
+    """The faces with keep[f] != 0 and the vertices they use (nerf_hip_mesh_select_faces_count, one 16-byte read of the device counts --
+    this synchronises with the stream --, then nerf_hip_mesh_select_faces_emit) -> (verts[V', 3], faces[F', 3] int32, normals, rgb --
+    None where the input is None).  keep: a bool or uint8 [F] device tensor."""
+    faces, V, F = _cc_faces(faces, verts.shape[0])
+    dev = faces.device
+    f32 = lambda a: None if a is None else a.to(torch.float32).contiguous()
+    verts, normals, rgb = f32(verts), f32(normals), f32(rgb)
+    for a in (verts, normals, rgb):
+        if a is not None and (tuple(a.shape) != (V, 3) or a.device != dev):
+            raise ValueError(f"a per-vertex array {tuple(a.shape)} on {a.device}: [{V}, 3] on {dev}")
+    if tuple(keep.shape) != (F,):
+        raise ValueError(f"keep {tuple(keep.shape)}: one entry per face, [{F}]")
+    keep = keep.to(device=dev, dtype=torch.uint8).contiguous()
+    if ws is None:
+        ws = torch.empty(_abi.mesh_select_faces_ws_bytes(V, F), dtype=torch.uint8, device=dev)
+    L, st = _abi.lib(), _stream(faces)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _abi.check(L.nerf_hip_mesh_select_faces_count(faces.data_ptr(), V, F, keep.data_ptr(), ws.data_ptr(), ws.numel(), counts.data_ptr(), st))
+    V1, F1 = (int(n) for n in counts.cpu())
+    out = lambda a: None if a is None else torch.empty(V1, 3, device=dev)
+    ov, on, oc = out(verts), out(normals), out(rgb)
+    of = torch.empty(F1, 3, dtype=torch.int32, device=dev)
+    ptr = lambda a: None if a is None else a.data_ptr()
+    _abi.check(L.nerf_hip_mesh_select_faces_emit(ptr(verts), ptr(normals), ptr(rgb), faces.data_ptr(), V, F, keep.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), ptr(ov), ptr(on), ptr(oc), of.data_ptr(), V1, F1, st))
+    return ov, of, on, oc
+
+
 def distance_stats(dist2, unit, thresholds=()):
     """The statistics of squared distances dist2[N] (fp64, device) in units of `unit` (nerf_hip_distance_stats; the definition is in
     include/nerf_hip.h) -> int64[4 + K] ON THE DEVICE: the finite count, the fixed-point sums of d / unit and d2 / unit^2, the clamped,

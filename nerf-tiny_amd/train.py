@@ -550,7 +550,7 @@ class NeRFRunner:
         return sigma
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
-                     keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=()):
+                     keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -569,7 +569,10 @@ class NeRFRunner:
         device after it is written: mesh.compare(extracted, ground truth, n=compare_samples, thresholds=compare_tau) -- Chamfer
         distance, precision / recall / F-score per threshold, both meshes' area and volume.  The result is kept as
         ``self.last_mesh_eval``, printed on one line and, with save, written to ``<results_path><start_time>_<last_iter>_mesh_eval.json``.
-        Without compare nothing new is computed, printed or written."""
+        Without compare nothing new is computed, printed or written.  visible_from: None, or "train" / "val" / "test" -- the faces that
+        no camera of that split sees go before smoothing, simplification, normals and colours (NeRFModel.extract_mesh(visible=): one
+        shadow ray per face and camera on the device); one ``[MESH]`` line says how many faces were seen.  Same file name either way;
+        without it nothing new is computed, printed or written."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -580,8 +583,18 @@ class NeRFRunner:
         shape = grid_shape(res)
         lo32, hi32 = np.asarray(lo, dtype=np.float32).reshape(3), np.asarray(hi, dtype=np.float32).reshape(3)
         self.model.eval()
+        kw = {}
+        if visible_from is not None:
+            if visible_from not in ("train", "val", "test"):
+                raise ValueError(f"visible_from={visible_from!r}: None, 'train', 'val' or 'test'")
+            rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[visible_from]
+            kw["visible"] = (rays.poses, self.K_inv, rays.height, rays.width)
         m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
-                                    keep_largest=keep_largest, simplify=simplify, smooth=smooth)
+                                    keep_largest=keep_largest, simplify=simplify, smooth=smooth, **kw)
+        if visible_from is not None:
+            seen, per_cam = self.model.last_visibility
+            print(f"[MESH] {self.last_iter} [VISIBLE] {int(seen.sum())} / {int(seen.numel())} faces seen from the {len(per_cam)} {visible_from} "
+                  f"cameras (per camera {min(per_cam, default=0)} .. {max(per_cam, default=0)})")
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
