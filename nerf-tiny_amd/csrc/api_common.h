@@ -99,4 +99,28 @@ inline int check_mesh_sizes(int64_t V, int64_t F) {
   return NERF_HIP_OK;
 }
 
+// the pointers of a mesh that has vertices / faces
+inline int check_mesh_ptrs(const float* verts, const int32_t* faces, int64_t V, int64_t F) {
+  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
+  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  return NERF_HIP_OK;
+}
+
+// the rows the caller's outputs hold
+inline int check_cap(const char* name, int64_t cap) {
+  if (cap < 0) return fail(NERF_HIP_ERR_ARG, "%s=%lld: a capacity must be >= 0", name, (long long)cap);
+  return NERF_HIP_OK;
+}
+inline int check_caps(int64_t max_v, int64_t max_f) {
+  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  return NERF_HIP_OK;
+}
+
+// three finite floats: name[c] as the caller calls them, noun = what they are
+inline int check_finite3(const float* p3, const char* name, const char* noun) {
+  for (int c = 0; c < 3; ++c)
+    if (!isfinite(p3[c])) return fail(NERF_HIP_ERR_ARG, "%s[%d]=%g: %s must be finite", name, c, (double)p3[c], noun);
+  return NERF_HIP_OK;
+}
+
 }  // namespace nerf

@@ -284,7 +284,7 @@ int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* 
     if (dims[c] > 1 && !(step3[c] > 0.0f && isfinite(step3[c])))
       return fail(NERF_HIP_ERR_ARG, "step[%d] = %g: must be positive and finite along a dimension of more than one point", c, (double)step3[c]);
   }
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (int rc = check_caps(max_v, max_f)) return rc;
   if (max_v > 0 && (!verts || !normals)) return fail(NERF_HIP_ERR_ARG, "verts / normals is null");
   if (max_f > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
   if (int rc = check_device()) return rc;
@@ -580,7 +580,7 @@ int nerf_hip_mesh_cc_compact(const float* verts, const float* normals, const flo
   CcLayout L;
   if (int rc = check_cc_ws(V, F, ws, ws_bytes, &L)) return rc;
   if (C < 0 || C > V) return fail(NERF_HIP_ERR_ARG, "C=%lld: a mesh of %lld vertices has at most as many components", (long long)C, (long long)V);
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (int rc = check_caps(max_v, max_f)) return rc;
   if (V > 0 && (!verts || !vert_comp)) return fail(NERF_HIP_ERR_ARG, "verts / vert_comp is null");
   if (F > 0 && (!faces || !face_comp)) return fail(NERF_HIP_ERR_ARG, "faces / face_comp is null");
   if (C > 0 && !keep) return fail(NERF_HIP_ERR_ARG, "keep is null");
@@ -664,11 +664,10 @@ int check_ms(int64_t V, int64_t F, const float* lo3, const float* cell3, const i
   if (int rc = check_mesh_sizes(V, F)) return rc;
   if (int rc = check_ms_dims(dims3)) return rc;
   if (!lo3 || !cell3) return fail(NERF_HIP_ERR_ARG, "lo3 / cell3 is null");
-  for (int c = 0; c < 3; ++c) {
-    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the cluster lattice's corner must be finite", c, (double)lo3[c]);
+  if (int rc = check_finite3(lo3, "lo", "the cluster lattice's corner")) return rc;
+  for (int c = 0; c < 3; ++c)
     if (!(cell3[c] > 0.0f) || !isfinite(cell3[c]))
       return fail(NERF_HIP_ERR_ARG, "cell[%d]=%g: the cluster lattice's cells must be > 0 and finite", c, (double)cell3[c]);
-  }
   *L = ms_layout(V, F, dims3);
   return check_ws(ws, ws_bytes, L->total);
 }
@@ -716,8 +715,7 @@ int nerf_hip_mesh_simplify_count(const float* verts, const float* normals, const
                                  const float* cell3, const int* dims3, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
   MsLayout L;
   if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
-  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (int rc = check_out(counts, "counts", 8)) return rc;
   if (int rc = check_device()) return rc;
   MsArgs a = ms_args(faces, V, F, lo3, cell3, dims3, ws, L);
@@ -734,7 +732,7 @@ int nerf_hip_mesh_simplify_emit(const int32_t* faces, int64_t V, int64_t F, cons
   MsLayout L;
   if (int rc = check_ms(V, F, lo3, cell3, dims3, ws, ws_bytes, &L)) return rc;
   if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (int rc = check_caps(max_v, max_f)) return rc;
   if (max_v > 0 && !out_verts) return fail(NERF_HIP_ERR_ARG, "out_verts is null");
   if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
   if (int rc = check_device()) return rc;
@@ -785,8 +783,7 @@ int check_me_ws(int64_t V, int64_t F, const void* ws, size_t ws_bytes, MeLayout*
 
 int check_me_box(const float* lo3, float scale) {
   if (!lo3) return fail(NERF_HIP_ERR_ARG, "lo3 is null");
-  for (int c = 0; c < 3; ++c)
-    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the box's corner must be finite", c, (double)lo3[c]);
+  if (int rc = check_finite3(lo3, "lo", "the box's corner")) return rc;
   if (!(scale > 0.0f) || !isfinite(scale)) return fail(NERF_HIP_ERR_ARG, "scale=%g: the box's scale must be > 0 and finite", (double)scale);
   return NERF_HIP_OK;
 }
@@ -850,7 +847,7 @@ int nerf_hip_mesh_smooth_step(const float* verts_in, float* verts_out, int64_t V
   if (int rc = check_me_ws(V, F, ws, ws_bytes, &L)) return rc;
   if (int rc = check_me_box(lo3, scale)) return rc;
   if (!isfinite(w)) return fail(NERF_HIP_ERR_ARG, "w=%g: a step's weight must be finite", w);
-  if (max_v < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld: a capacity must be >= 0", (long long)max_v);
+  if (int rc = check_cap("max_v", max_v)) return rc;
   const int64_t n = V < max_v ? V : max_v;
   if (V > 0 && !verts_in) return fail(NERF_HIP_ERR_ARG, "verts_in is null");
   if (n > 0 && !verts_out) return fail(NERF_HIP_ERR_ARG, "verts_out is null");
@@ -875,9 +872,8 @@ int nerf_hip_mesh_vertex_normals(const float* verts, const int32_t* faces, int64
   MeLayout L;
   if (int rc = check_me_ws(V, F, ws, ws_bytes, &L)) return rc;
   if (int rc = check_me_box(lo3, scale)) return rc;
-  if (max_v < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld: a capacity must be >= 0", (long long)max_v);
-  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (int rc = check_cap("max_v", max_v)) return rc;
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (V > 0 && max_v > 0 && !normals) return fail(NERF_HIP_ERR_ARG, "normals is null");
   if (int rc = check_device()) return rc;
   MeArgs a = me_args(V, F, ws, L);
@@ -912,8 +908,7 @@ MdSampleLayout md_sample_layout(long long F) {
 int check_md_mesh(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float scale) {
   if (int rc = check_mesh_sizes(V, F)) return rc;
   if (int rc = check_me_box(lo3, scale)) return rc;
-  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   return NERF_HIP_OK;
 }
 
@@ -969,8 +964,7 @@ int check_md_grid(int64_t M, int64_t N, const float* lo3, float cell, const int*
   if (int rc = check_mesh_sizes(M, N)) return rc;  // (point counts below 2^31, as vertices)
   if (int rc = check_md_dims(dims3)) return rc;
   if (!lo3) return fail(NERF_HIP_ERR_ARG, "lo3 is null");
-  for (int c = 0; c < 3; ++c)
-    if (!isfinite(lo3[c])) return fail(NERF_HIP_ERR_ARG, "lo[%d]=%g: the grid's corner must be finite", c, (double)lo3[c]);
+  if (int rc = check_finite3(lo3, "lo", "the grid's corner")) return rc;
   if (!(cell > 0.0f) || !isfinite(cell)) return fail(NERF_HIP_ERR_ARG, "cell=%g: the grid's cell must be > 0 and finite", (double)cell);
   return NERF_HIP_OK;
 }
@@ -1025,7 +1019,7 @@ int nerf_hip_mesh_sample(const float* verts, const int32_t* faces, int64_t V, in
                          void* stream) {
   if (int rc = check_md_mesh(verts, faces, V, F, lo3, scale)) return rc;
   if (n < 0 || n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "n=%lld: a sample count in [0, 2^31)", (long long)n);
-  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (int rc = check_cap("cap_n", cap_n)) return rc;
   if (n > 0 && cap_n > 0 && (!points || !face)) return fail(NERF_HIP_ERR_ARG, "points / face is null");
   const MdSampleLayout L = md_sample_layout(F);
   if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
@@ -1071,7 +1065,7 @@ int nerf_hip_points_grid_build(const float* ref, int64_t M, const float* lo3, fl
 int nerf_hip_points_nearest(const float* query, int64_t M, int64_t N, const float* lo3, float cell, const int* dims3, void* ws,
                             size_t ws_bytes, int sort_queries, int32_t* idx, double* dist2, int64_t cap_n, void* stream) {
   if (int rc = check_md_grid(M, N, lo3, cell, dims3)) return rc;
-  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (int rc = check_cap("cap_n", cap_n)) return rc;
   if (N > 0 && !query) return fail(NERF_HIP_ERR_ARG, "query is null");
   if (N > 0 && cap_n > 0 && (!idx || !dist2)) return fail(NERF_HIP_ERR_ARG, "idx / dist2 is null");
   if (dist2 && ((uintptr_t)dist2 & 7) != 0) return fail(NERF_HIP_ERR_ARG, "dist2 must be 8-byte aligned");
@@ -1139,13 +1133,6 @@ RcLayout rc_layout(long long F, long long E, const int* dims3) {
 
 int check_rc_entries(int64_t cap_entries) {
   if (cap_entries < 0 || cap_entries >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "cap_entries=%lld: the grid's entries in [0, 2^31)", (long long)cap_entries);
-  return NERF_HIP_OK;
-}
-
-int check_rc_mesh(const float* verts, const int32_t* faces, int64_t V, int64_t F) {
-  if (int rc = check_mesh_sizes(V, F)) return rc;
-  if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (F > 0 && !faces) return fail(NERF_HIP_ERR_ARG, "faces is null");
   return NERF_HIP_OK;
 }
 
@@ -1230,7 +1217,8 @@ int nerf_hip_mesh_raycast_ws_bytes(int64_t F, int64_t cap_entries, const int* di
 
 int nerf_hip_mesh_raycast_grid_count(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
                                      const int* dims3, int64_t* counts, void* stream) {
-  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
   if (int rc = check_out(counts, "counts", 8)) return rc;
   if (int rc = check_device()) return rc;
@@ -1242,7 +1230,8 @@ int nerf_hip_mesh_raycast_grid_count(const float* verts, const int32_t* faces, i
 
 int nerf_hip_mesh_raycast_grid_fill(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* lo3, float cell,
                                     const int* dims3, int64_t cap_entries, void* ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
   if (int rc = check_rc_entries(cap_entries)) return rc;
   const RcLayout L = rc_layout(F, cap_entries, dims3);
@@ -1258,11 +1247,12 @@ int nerf_hip_mesh_raycast(const float* verts, const int32_t* faces, int64_t V, i
                           int64_t cap_entries, const void* ws, size_t ws_bytes, const float* origins, const float* dirs,
                           const int32_t* skip, int64_t N, double tmin, double tmax, int any_hit, double* t, double* uv, int32_t* face,
                           int8_t* side, uint8_t* occluded, int64_t cap_n, void* stream) {
-  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (int rc = check_md_grid(0, 0, lo3, cell, dims3)) return rc;
   if (int rc = check_rc_entries(cap_entries)) return rc;
   if (N < 0 || N >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "N=%lld: a ray count in [0, 2^31)", (long long)N);
-  if (cap_n < 0) return fail(NERF_HIP_ERR_ARG, "cap_n=%lld: a capacity must be >= 0", (long long)cap_n);
+  if (int rc = check_cap("cap_n", cap_n)) return rc;
   if (tmin != tmin || tmax != tmax) return fail(NERF_HIP_ERR_ARG, "tmin=%g tmax=%g: the window's ends may be infinite, not NaN", tmin, tmax);
   if (N > 0 && (!origins || !dirs)) return fail(NERF_HIP_ERR_ARG, "origins / dirs is null");
   if (N > 0 && cap_n > 0) {
@@ -1298,14 +1288,14 @@ int nerf_hip_mesh_raycast(const float* verts, const int32_t* faces, int64_t V, i
 
 int nerf_hip_mesh_face_rays(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* cam_o3, const double* Q9, int H,
                             int W, float* orig, float* dir, uint8_t* valid, int64_t cap_f, void* stream) {
-  if (int rc = check_rc_mesh(verts, faces, V, F)) return rc;
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
   if (!cam_o3 || !Q9) return fail(NERF_HIP_ERR_ARG, "cam_o3 / Q9 is null");
-  for (int c = 0; c < 3; ++c)
-    if (!isfinite(cam_o3[c])) return fail(NERF_HIP_ERR_ARG, "cam_o[%d]=%g: the camera's position must be finite", c, (double)cam_o3[c]);
+  if (int rc = check_finite3(cam_o3, "cam_o", "the camera's position")) return rc;
   for (int c = 0; c < 9; ++c)
     if (!isfinite(Q9[c])) return fail(NERF_HIP_ERR_ARG, "Q[%d]=%g: the camera's matrix must be finite", c, Q9[c]);
   if (H < 1 || W < 1) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: an image has at least one pixel", H, W);
-  if (cap_f < 0) return fail(NERF_HIP_ERR_ARG, "cap_f=%lld: a capacity must be >= 0", (long long)cap_f);
+  if (int rc = check_cap("cap_f", cap_f)) return rc;
   if (F > 0 && cap_f > 0 && (!orig || !dir || !valid)) return fail(NERF_HIP_ERR_ARG, "orig / dir / valid is null");
   if (int rc = check_device()) return rc;
   RcFaceRaysArgs a;
@@ -1351,7 +1341,7 @@ int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, co
   SelLayout L;
   if (int rc = check_sel(faces, V, F, keep, ws, ws_bytes, &L)) return rc;
   if (V > 0 && !verts) return fail(NERF_HIP_ERR_ARG, "verts is null");
-  if (max_v < 0 || max_f < 0) return fail(NERF_HIP_ERR_ARG, "max_v=%lld max_f=%lld: capacities must be >= 0", (long long)max_v, (long long)max_f);
+  if (int rc = check_caps(max_v, max_f)) return rc;
   if (max_v > 0 && (!out_verts || (normals && !out_normals) || (rgb && !out_rgb))) return fail(NERF_HIP_ERR_ARG, "an output of max_v rows is null");
   if (max_f > 0 && !out_faces) return fail(NERF_HIP_ERR_ARG, "out_faces is null");
   if (int rc = check_device()) return rc;

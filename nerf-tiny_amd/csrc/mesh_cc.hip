@@ -33,10 +33,6 @@ namespace nerf {
 
 namespace {
 
-__device__ inline bool cc_face_ok(int a, int b, int c, int V) {
-  return (unsigned)a < (unsigned)V && (unsigned)b < (unsigned)V && (unsigned)c < (unsigned)V;
-}
-
 // the floats' order-preserving unsigned images (ray_parts.h sort_key: -0 keyed as +0); only finite values are keyed here
 __device__ inline unsigned cc_key(float x) {
   unsigned b = __float_as_uint(x);
@@ -60,8 +56,9 @@ __global__ __launch_bounds__(CC_WG) void k_cc_init(int* __restrict__ L, int V) {
 __global__ __launch_bounds__(CC_WG) void k_cc_hook(const int* __restrict__ faces, int V, int F, int* L, int* changed) {
   const long long f = (long long)blockIdx.x * CC_WG + threadIdx.x;
   if (f >= F) return;
-  const int a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-  if (!cc_face_ok(a, b, c, V)) return;  // takes no part, and is never used as an address
+  int i[3];
+  if (!face_corners<false>(faces, V, f, i)) return;  // takes no part
+  const int a = i[0], b = i[1], c = i[2];
   const int ra = L[a], rb = L[b], rc = L[c];
   if ((unsigned)ra > (unsigned)a || (unsigned)rb > (unsigned)b || (unsigned)rc > (unsigned)c) return;  // (I1) holds: never taken
   const int m = min(ra, min(rb, rc));
@@ -94,8 +91,9 @@ __global__ __launch_bounds__(CC_WG) void k_cc_compress(int* L, int V) {
 
 // ---- the flags and sinks of scan.h's compaction ----
 
-// the flags (is item i counted?) and sinks (item i, its flag, its rank among the flagged) of the three uses.  k_flag_place recomputes
-// the flags: no launch between the count and the placement writes what they read
+// the flags (is item i counted?) and sinks (item i, its flag, its rank among the flagged) of the three uses; the sinks of the kept
+// vertices and faces are mesh_parts.h's.  k_flag_place recomputes the flags: no launch between the count and the placement writes what
+// they read
 struct RootFlag {  // v is a root
   const int* L;
   __device__ int operator()(long long i) const { return L[i] == (int)i; }
@@ -116,23 +114,6 @@ struct VertKeep {
     return (unsigned)c < (unsigned)C && keep[c] != 0;
   }
 };
-struct VertSink {
-  const float *verts, *normals, *rgb;
-  float *out_verts, *out_normals, *out_rgb;
-  int* newidx;
-  long long max_v;
-  __device__ void operator()(long long i, int flag, long long pos) const {
-    newidx[i] = flag ? (int)pos : -1;
-    if (!flag || pos >= max_v) return;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      out_verts[pos * 3 + d] = verts[i * 3 + d];
-      if (normals) out_normals[pos * 3 + d] = normals[i * 3 + d];
-      if (rgb) out_rgb[pos * 3 + d] = rgb[i * 3 + d];
-    }
-  }
-};
-
 struct FaceKeep {
   const int *faces, *face_comp;
   const unsigned char* keep;
@@ -140,17 +121,8 @@ struct FaceKeep {
   __device__ int operator()(long long i) const {
     const int c = face_comp[i];
     if ((unsigned)c >= (unsigned)C || keep[c] == 0) return 0;
-    return cc_face_ok(faces[i * 3 + 0], faces[i * 3 + 1], faces[i * 3 + 2], V);
-  }
-};
-struct FaceSink {
-  const int *faces, *newidx;
-  int* out_faces;
-  long long max_f;
-  __device__ void operator()(long long i, int flag, long long pos) const {
-    if (!flag || pos >= max_f) return;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) out_faces[pos * 3 + d] = newidx[faces[i * 3 + d]];  // (FaceKeep checked the three indices)
+    int k[3];
+    return face_corners<false>(faces, V, i, k);
   }
 };
 
@@ -168,8 +140,8 @@ __global__ __launch_bounds__(CC_WG) void k_cc_faces(const int* __restrict__ face
                                                     int* __restrict__ face_comp) {
   const long long f = (long long)blockIdx.x * CC_WG + threadIdx.x;
   if (f >= F) return;
-  const int a = faces[f * 3 + 0], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-  face_comp[f] = cc_face_ok(a, b, c, V) ? vert_comp[a] : -1;
+  int i[3];
+  face_comp[f] = face_corners<false>(faces, V, f, i) ? vert_comp[i[0]] : -1;
 }
 
 // ---- per-component counts and boxes ----
@@ -301,10 +273,10 @@ hipError_t launch_cc_compact(const CcCompactArgs& a, hipStream_t st) {
   TRY(hipMemsetAsync(a.counts, 0, 2 * sizeof(long long), st));
   if (a.V > 0)
     TRY(scan_place(VertKeep{a.vert_comp, a.keep, a.C},
-                   VertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v}, a.V, a.tot, a.base,
+                   SubVertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v}, a.V, a.tot, a.base,
                    a.counts, st));
   if (a.F > 0 && a.V > 0)  // (after the vertices' placement: the faces read newidx across workgroups)
-    TRY(scan_place(FaceKeep{a.faces, a.face_comp, a.keep, a.V, a.C}, FaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot,
+    TRY(scan_place(FaceKeep{a.faces, a.face_comp, a.keep, a.V, a.C}, SubFaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot,
                    a.base, a.counts + 1, st));
   return hipSuccess;
 }

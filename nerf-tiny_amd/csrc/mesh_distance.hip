@@ -2,12 +2,10 @@
 // nearest points over a uniform grid and distance statistics (nerf_hip_mesh_measure, nerf_hip_mesh_sample, nerf_hip_points_grid_build,
 // nerf_hip_points_nearest, nerf_hip_distance_stats; the definitions are in include/nerf_hip.h).
 //   k_md_measure     per face: area, six volumes and centroid moments as int64 fixed point, summed per wave, then five integer atomics
-//   k_md_wsum        per CC_PTS faces: the sum of their integer weights
-//   scan.h's k_flag_scan   the workgroup sums -> exclusive bases, the grand total W into info
-//   k_md_cum         per face: cum[f] = the inclusive prefix of the weights
+//   scan.h's value scan over FaceWeight   per face: cum[f] = the inclusive prefix of the integer weights, the grand total W into info
 //   k_md_sample      per sample: stratum -> face by binary search in cum -> folded barycentrics -> point
 //   k_pn_count       per point: its cell's count by an integer atomic (reference points and queries alike)
-//   k_pn_cellsum / k_flag_scan / k_pn_offsets   per-cell counts -> start[cell], the exclusive scan; the counts are zeroed for the cursors
+//   scan.h's cells_to_start   per-cell counts -> start[cell], the exclusive scan; the counts are zeroed for the cursors
 //   k_pn_place       per point: its record (x, y, z, index) placed through its cell's cursor atomic
 //   k_pn_fill        per query: idx = -1, dist2 = +inf
 //   k_pn_query       per query: Chebyshev shells of cells around its own cell until the stopping rule holds
@@ -51,33 +49,8 @@ constexpr double MD_D_ONE = 1073741824.0;        // 2^30: fixed point of the dis
 constexpr double MD_MARGIN = 2.842170943040401e-14;  // 2^-45 (N2)
 constexpr double MD_INF = __builtin_huge_val();
 
-__device__ inline long long md_add(long long* p, long long v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int md_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the sum of x over the wave's 64 lanes, in every lane (integers: the order plays no role)
-__device__ inline long long md_wave_sum(long long x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
-
-__device__ inline bool md_finite3(const float (&p)[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
-// does face f take part?  -> its corners' coordinates in p[corner][axis]
-__device__ inline bool md_face(const MdMeshArgs& a, long long f, float (&p)[3][3]) {
-  const int i[3] = {a.faces[f * 3 + 0], a.faces[f * 3 + 1], a.faces[f * 3 + 2]};
-  const unsigned V = (unsigned)a.V;
-  if ((unsigned)i[0] >= V || (unsigned)i[1] >= V || (unsigned)i[2] >= V) return false;  // never used as an address
-  if (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]) return false;
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) p[c][d] = a.verts[(long long)i[c] * 3 + d];
-    ok = ok && md_finite3(p[c]);
-  }
-  return ok;
-}
+// does face f take part (three distinct corners with finite coordinates)?  -> the coordinates in p[corner][axis]
+__device__ inline bool md_face(const MdMeshArgs& a, long long f, float (&p)[3][3]) { return face_coords<true>(a.verts, a.faces, a.V, f, p); }
 
 // the clamped box coordinates of a participating face's corners (section 3h-6's uc)
 __device__ inline void md_box(const MdMeshArgs& a, const float (&p)[3][3], double (&u)[3][3]) {
@@ -162,41 +135,27 @@ __global__ __launch_bounds__(CC_WG) void k_md_measure(const MdMeshArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    const long long s = md_wave_sum(t[k]);
-    if ((threadIdx.x & 63) == 0 && s != 0) md_add(&a.out[k], s);
+    const long long s = wave_sum(t[k]);
+    if ((threadIdx.x & 63) == 0 && s != 0) agent_add(&a.out[k], s);
   }
 }
 
 // ---- B. surface samples ----
 
-// grid = cc_blocks(F)
-__global__ __launch_bounds__(CC_WG) void k_md_wsum(const MdMeshArgs a) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long f = base + r * CC_WG + threadIdx.x;
-    long long total;
-    (void)wg_prefix_sum<long long>(f < a.F ? md_weight(a, f) : 0, part, total);
-    run += total;
-  }
-  if (threadIdx.x == 0) a.tot[blockIdx.x] = run;
-}
+namespace {
 
-// grid = cc_blocks(F).  The weights are recomputed, not stored: nothing they depend on changes between the two launches.
-__global__ __launch_bounds__(CC_WG) void k_md_cum(const MdMeshArgs a) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = a.base[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long f = base + r * CC_WG + threadIdx.x;
-    const long long w = f < a.F ? md_weight(a, f) : 0;
-    long long total;
-    const long long pre = wg_prefix_sum<long long>(w, part, total);
-    if (f < a.F) a.cum[f] = run + pre + w;
-    run += total;
-  }
-}
+// the value and sink of the weights' scan.  k_value_place recomputes the weights: nothing they depend on changes between the launches
+struct FaceWeight {
+  MdMeshArgs a;
+  __device__ long long operator()(long long f) const { return md_weight(a, f); }
+};
+struct CumSink {  // the inclusive prefix
+  long long* cum;
+  __device__ void operator()(long long f, long long w, long long pre) const { cum[f] = pre + w; }
+  __device__ void end(long long) const {}
+};
+
+}  // namespace
 
 // grid = ceil(min(n, cap_n) / CC_WG), one thread per sample
 __global__ __launch_bounds__(CC_WG) void k_md_sample(const MdMeshArgs a) {
@@ -243,59 +202,9 @@ __global__ __launch_bounds__(CC_WG) void k_pn_count(const MdGridArgs a, const fl
   const long long i = (long long)blockIdx.x * CC_WG + threadIdx.x;
   if (i >= n) return;
   const float p[3] = {pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2]};
-  if (!md_finite3(p)) return;
+  if (!finite3(p)) return;
   int c[3];
-  md_add(&cnt[md_cell3(a, p, c)], 1);
-}
-
-// a count as the scan takes it: what k_pn_count left, kept inside [0, n]
-__device__ inline int md_count(const int* cnt, long long c, int n) {
-  const int v = cnt[c];
-  return v < 0 ? 0 : (v > n ? n : v);
-}
-
-// grid = cc_blocks(ncell); most (may be null): the fullest cell's count
-__global__ __launch_bounds__(CC_WG) void k_pn_cellsum(const int* __restrict__ cnt, int ncell, int n, int* __restrict__ tot, long long* most) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = 0;
-  int top = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long c = base + r * CC_WG + threadIdx.x;
-    const int v = c < ncell ? md_count(cnt, c, n) : 0;
-    long long total;
-    (void)wg_prefix_sum<long long>(v, part, total);
-    run += total;
-    top = v > top ? v : top;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = (int)(run > n ? n : run);
-  if (most) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const int o = __shfl_xor(top, d);
-      top = o > top ? o : top;
-    }
-    if ((threadIdx.x & 63) == 0 && top > 0) __hip_atomic_fetch_max(most, (long long)top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// grid = cc_blocks(ncell): start[c] = the points in the cells before c, start[ncell] = all of them; the counts become the cursors (0)
-__global__ __launch_bounds__(CC_WG) void k_pn_offsets(int* __restrict__ cnt, int ncell, int n, const int* __restrict__ bases, int* __restrict__ start) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = bases[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long c = base + r * CC_WG + threadIdx.x;
-    const int v = c < ncell ? md_count(cnt, c, n) : 0;
-    long long total;
-    const long long pre = wg_prefix_sum<long long>(v, part, total);
-    if (c < ncell) {
-      start[c] = (int)(run + pre > n ? n : run + pre);
-      cnt[c] = 0;
-    }
-    run += total;
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) start[ncell] = (int)(run > n ? n : run);
+  agent_add(&cnt[md_cell3(a, p, c)], 1);
 }
 
 // grid = ceil(n / CC_WG), one thread per point.  Which record of its cell a point gets depends on the interleaving; the cell's set of
@@ -305,11 +214,11 @@ __global__ __launch_bounds__(CC_WG) void k_pn_place(const MdGridArgs a, const fl
   const long long i = (long long)blockIdx.x * CC_WG + threadIdx.x;
   if (i >= n) return;
   const float p[3] = {pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2]};
-  if (!md_finite3(p)) return;
+  if (!finite3(p)) return;
   int c[3];
   const int cell = md_cell3(a, p, c);
   const long long b = start[cell], e = start[cell + 1];
-  const long long at = b + (long long)md_add(&cursor[cell], 1);
+  const long long at = b + (long long)agent_add(&cursor[cell], 1);
   if (b >= 0 && at >= b && at < e && e <= n) rec[at] = make_float4(p[0], p[1], p[2], __int_as_float((int)i));
 }
 
@@ -363,14 +272,14 @@ __global__ __launch_bounds__(CC_WG) void k_pn_query(const MdGridArgs a) {
     const float4 r = a.qrec[s];
     p[0] = r.x, p[1] = r.y, p[2] = r.z;
     j = __float_as_int(r.w);
-    if (j < 0 || j >= a.N || !md_finite3(p)) return;
+    if (j < 0 || j >= a.N || !finite3(p)) return;
   } else {
     p[0] = a.query[s * 3 + 0], p[1] = a.query[s * 3 + 1], p[2] = a.query[s * 3 + 2];
   }
   if (j >= a.cap_n) return;
   double best = MD_INF;
   int bi = -1;
-  if (md_finite3(p)) {
+  if (finite3(p)) {
     const double q[3] = {(double)p[0], (double)p[1], (double)p[2]};
     int c[3];
     (void)md_cell3(a, p, c);
@@ -433,8 +342,8 @@ __global__ __launch_bounds__(CC_WG) void k_md_stats(const MdStatsArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 4 + MD_MAX_TAU; ++k) {
-    const long long s = md_wave_sum(t[k]);
-    if (k < 4 + a.K && (threadIdx.x & 63) == 0 && s != 0) md_add(&a.out[k], s);
+    const long long s = wave_sum(t[k]);
+    if (k < 4 + a.K && (threadIdx.x & 63) == 0 && s != 0) agent_add(&a.out[k], s);
   }
 }
 
@@ -448,12 +357,7 @@ hipError_t launch_md_measure(const MdMeshArgs& a, hipStream_t st) {
 
 hipError_t launch_md_sample(const MdMeshArgs& a, hipStream_t st) {
   TRY(hipMemsetAsync(a.info, 0, sizeof(long long), st));
-  if (a.F > 0) {
-    const int nb = cc_blocks(a.F);
-    LAUNCH(k_md_wsum, dim3(nb), dim3(CC_WG), 0, st, a);
-    LAUNCH((k_flag_scan<long long, long long>), dim3(1), dim3(1024), 0, st, a.tot, a.base, nb, a.info);
-    LAUNCH(k_md_cum, dim3(nb), dim3(CC_WG), 0, st, a);
-  }
+  if (a.F > 0) TRY(scan_values<long long>(FaceWeight{a}, NoWatch{}, CumSink{a.cum}, a.F, NO_CAP, a.tot, a.base, a.info, st));
   const long long n = a.n < a.cap_n ? a.n : a.cap_n;
   if (n > 0) LAUNCH(k_md_sample, dim3(grid(n, CC_WG)), dim3(CC_WG), 0, st, a);
   return hipSuccess;
@@ -464,12 +368,9 @@ namespace {
 // the counting sort of pts[n] by cell: cnt (zeroed here), start, rec; *total = the finite points, *most (may be null) the fullest cell
 hipError_t md_sort(const MdGridArgs& a, const float* pts, int n, int* cnt, int* start, float4* rec, long long* total, long long* most,
                    hipStream_t st) {
-  const int nb = cc_blocks(a.ncell);
   TRY(hipMemsetAsync(cnt, 0, (size_t)a.ncell * sizeof(int), st));
   if (n > 0) LAUNCH(k_pn_count, dim3(grid(n, CC_WG)), dim3(CC_WG), 0, st, a, pts, n, cnt);
-  LAUNCH(k_pn_cellsum, dim3(nb), dim3(CC_WG), 0, st, cnt, a.ncell, n, a.tot, most);
-  LAUNCH((k_flag_scan<int, int>), dim3(1), dim3(1024), 0, st, a.tot, a.base, nb, total);
-  LAUNCH(k_pn_offsets, dim3(nb), dim3(CC_WG), 0, st, cnt, a.ncell, n, a.base, start);
+  TRY(cells_to_start(cnt, a.ncell, n, a.tot, a.base, start, total, most, st));
   if (n > 0) LAUNCH(k_pn_place, dim3(grid(n, CC_WG)), dim3(CC_WG), 0, st, a, pts, n, cnt, start, rec);
   return hipSuccess;
 }

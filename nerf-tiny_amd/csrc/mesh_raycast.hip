@@ -3,7 +3,7 @@
 // nerf_hip_mesh_select_faces_count / _emit; the definitions are in include/nerf_hip.h).
 //   k_rc_count       per face: does it take part, is it INSIDE, the cells of its box; summed per wave, then three integer atomics
 //   k_rc_cells       per INSIDE face: its box's cells counted by integer atomics (PLACE: the face entered through the cells' cursors)
-//   k_rc_cellsum / k_flag_scan / k_rc_offsets   per-cell counts -> start[cell], the exclusive scan; the counts are zeroed for the cursors
+//   scan.h's cells_to_start   per-cell counts -> start[cell], the exclusive scan; the counts are zeroed for the cursors
 //   scan.h's compaction over OutsideFlag   the OUTSIDE faces, ascending, and their number
 //   k_rc_cast        per ray: the OUTSIDE list in full, then the grid walk below
 //   k_rc_face_rays   per face: centroid, facing and in-view tests, the shadow ray towards the camera
@@ -50,28 +50,9 @@ constexpr double RC_MAX = 1.7976931348623157e308;   // DBL_MAX
 constexpr double RC_EPS = 9.5367431640625e-07;      // 2^-20: the box margin of the hit rule
 constexpr double RC_SKIP = 9.094947017729282e-13;   // 2^-40: the margin of (W4)'s guess (speed only)
 
-__device__ inline long long rc_add(long long* p, long long v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int rc_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline long long rc_wave_sum(long long x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
-
-// does face f take part?  -> its corners' coordinates in p[corner][axis]
-__device__ inline bool rc_face(const float* __restrict__ verts, const int* __restrict__ faces, int V, long long f, float (&p)[3][3]) {
-  const int i[3] = {faces[f * 3 + 0], faces[f * 3 + 1], faces[f * 3 + 2]};
-  if ((unsigned)i[0] >= (unsigned)V || (unsigned)i[1] >= (unsigned)V || (unsigned)i[2] >= (unsigned)V) return false;  // never used as an address
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      p[c][d] = verts[(long long)i[c] * 3 + d];
-      ok = ok && isfinite(p[c][d]);
-    }
-  return ok;
+// does face f take part (corners in range with finite coordinates; they need not be distinct)?  -> the coordinates in p[corner][axis]
+__device__ inline bool rc_face(const float* verts, const int* faces, int V, long long f, float (&p)[3][3]) {
+  return face_coords<false>(verts, faces, V, f, p);
 }
 
 // the face's box widened by e: mn[k] = min_k - e, mx[k] = max_k + e
@@ -167,8 +148,8 @@ __global__ __launch_bounds__(CC_WG) void k_rc_count(const RcGridArgs a) {
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const long long s = rc_wave_sum(t[k]);
-    if ((threadIdx.x & 63) == 0 && s != 0) rc_add(&a.counts[k], s);
+    const long long s = wave_sum(t[k]);
+    if ((threadIdx.x & 63) == 0 && s != 0) agent_add(&a.counts[k], s);
   }
 }
 
@@ -186,58 +167,13 @@ __global__ __launch_bounds__(CC_WG) void k_rc_cells(const RcGridArgs a) {
       for (int z = b0[2]; z <= b1[2]; ++z) {
         const long long c = ((long long)x * a.dims[1] + y) * a.dims[2] + z;  // (inside the grid: rc_box)
         if (!PLACE) {
-          rc_add(&a.cnt[c], 1);
+          agent_add(&a.cnt[c], 1);
         } else {
           const long long b = a.start[c], e = a.start[c + 1];
-          const long long at = b + (long long)rc_add(&a.cnt[c], 1);
+          const long long at = b + (long long)agent_add(&a.cnt[c], 1);
           if (b >= 0 && at >= b && at < e && e <= a.cap_entries) a.entries[at] = (int)f;
         }
       }
-}
-
-namespace {
-
-// a count as the scan takes it: what k_rc_cells left, kept inside [0, cap]
-__device__ inline long long rc_count_of(const int* cnt, long long c, long long cap) {
-  const long long v = cnt[c];
-  return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-}  // namespace
-
-// grid = cc_blocks(ncell)
-__global__ __launch_bounds__(CC_WG) void k_rc_cellsum(const int* __restrict__ cnt, int ncell, long long cap, int* __restrict__ tot) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long c = base + r * CC_WG + threadIdx.x;
-    long long total;
-    (void)wg_prefix_sum<long long>(c < ncell ? rc_count_of(cnt, c, cap) : 0, part, total);
-    run += total;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = (int)(run > cap ? cap : run);
-}
-
-// grid = cc_blocks(ncell): start[c] = the entries of the cells before c, start[ncell] = all of them, each at most cap; the counts
-// become the cursors (0)
-__global__ __launch_bounds__(CC_WG) void k_rc_offsets(int* __restrict__ cnt, int ncell, long long cap, const int* __restrict__ bases,
-                                                      int* __restrict__ start) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = bases[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long c = base + r * CC_WG + threadIdx.x;
-    const long long v = c < ncell ? rc_count_of(cnt, c, cap) : 0;
-    long long total;
-    const long long pre = wg_prefix_sum<long long>(v, part, total);
-    if (c < ncell) {
-      start[c] = (int)(run + pre > cap ? cap : run + pre);
-      cnt[c] = 0;
-    }
-    run += total;
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) start[ncell] = (int)(run > cap ? cap : run);
 }
 
 namespace {
@@ -422,40 +358,22 @@ __global__ __launch_bounds__(CC_WG) void k_rc_face_rays(const RcFaceRaysArgs a) 
 
 namespace {
 
-__device__ inline bool sel_face_kept(const SelArgs& a, long long f) {
-  if (a.keep[f] == 0) return false;
-  const unsigned V = (unsigned)a.V;
-  return (unsigned)a.faces[f * 3 + 0] < V && (unsigned)a.faces[f * 3 + 1] < V && (unsigned)a.faces[f * 3 + 2] < V;
+// -> the kept face's corners in i[3]
+__device__ inline bool sel_face_kept(const SelArgs& a, long long f, int (&i)[3]) {
+  return a.keep[f] != 0 && face_corners<false>(a.faces, a.V, f, i);
 }
 
-// the flags and sinks of the two compactions.  k_flag_place recomputes the flags: `used` is written by k_sel_mark alone, before both
+// the flags of the two compactions (the sinks are mesh_parts.h's).  k_flag_place recomputes the flags: `used` is written by k_sel_mark
+// alone, before both
 struct UsedFlag {
   const int* used;
   __device__ int operator()(long long v) const { return used[v] != 0; }
 };
-struct UsedSink {
-  SelArgs a;
-  __device__ void operator()(long long v, int flag, long long pos) const {
-    a.newidx[v] = flag ? (int)pos : -1;
-    if (!flag || pos >= a.max_v) return;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      a.out_verts[pos * 3 + d] = a.verts[v * 3 + d];
-      if (a.normals) a.out_normals[pos * 3 + d] = a.normals[v * 3 + d];
-      if (a.rgb) a.out_rgb[pos * 3 + d] = a.rgb[v * 3 + d];
-    }
-  }
-};
 struct KeepFlag {
   SelArgs a;
-  __device__ int operator()(long long f) const { return sel_face_kept(a, f); }
-};
-struct KeepSink {
-  SelArgs a;
-  __device__ void operator()(long long f, int flag, long long pos) const {
-    if (!flag || pos >= a.max_f) return;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) a.out_faces[pos * 3 + d] = a.newidx[a.faces[f * 3 + d]];  // (KeepFlag checked the three indices)
+  __device__ int operator()(long long f) const {
+    int i[3];
+    return sel_face_kept(a, f, i);
   }
 };
 
@@ -464,9 +382,10 @@ struct KeepSink {
 // grid = ceil(F / CC_WG): used[v] = 1 for the corners of the kept faces (every writer stores the same 1)
 __global__ __launch_bounds__(CC_WG) void k_sel_mark(const SelArgs a) {
   const long long f = (long long)blockIdx.x * CC_WG + threadIdx.x;
-  if (f >= a.F || !sel_face_kept(a, f)) return;
+  int i[3];
+  if (f >= a.F || !sel_face_kept(a, f, i)) return;
 #pragma unroll
-  for (int d = 0; d < 3; ++d) a.used[a.faces[f * 3 + d]] = 1;
+  for (int d = 0; d < 3; ++d) a.used[i[d]] = 1;
 }
 
 // ---- launchers ----
@@ -478,14 +397,11 @@ hipError_t launch_rc_grid_count(const RcGridArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_rc_grid_fill(const RcGridArgs& a, hipStream_t st) {
-  const int nb = cc_blocks(a.ncell);
   const bool faces = a.F > 0 && a.V > 0;
   TRY(hipMemsetAsync(a.cnt, 0, (size_t)a.ncell * sizeof(int), st));
   TRY(hipMemsetAsync(a.info, 0, 2 * sizeof(long long), st));
   if (faces) LAUNCH(k_rc_cells<false>, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
-  LAUNCH(k_rc_cellsum, dim3(nb), dim3(CC_WG), 0, st, a.cnt, a.ncell, a.cap_entries, a.tot);
-  LAUNCH((k_flag_scan<int, int>), dim3(1), dim3(1024), 0, st, a.tot, a.base, nb, a.info);
-  LAUNCH(k_rc_offsets, dim3(nb), dim3(CC_WG), 0, st, a.cnt, a.ncell, a.cap_entries, a.base, a.start);
+  TRY(cells_to_start(a.cnt, a.ncell, a.cap_entries, a.tot, a.base, a.start, a.info, nullptr, st));
   if (faces) {
     LAUNCH(k_rc_cells<true>, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
     TRY(scan_place(OutsideFlag{a}, OutsideSink{a.outside, a.F}, a.F, a.tot, a.base, a.info + 1, st));
@@ -527,9 +443,11 @@ hipError_t launch_sel_count(const SelArgs& a, hipStream_t st) {
 
 hipError_t launch_sel_emit(const SelArgs& a, hipStream_t st) {
   TRY(sel_mark(a, st));
-  if (a.V > 0) TRY(scan_place(UsedFlag{a.used}, UsedSink{a}, a.V, a.tot, a.base, a.counts, st));
+  if (a.V > 0)
+    TRY(scan_place(UsedFlag{a.used}, SubVertSink{a.verts, a.normals, a.rgb, a.out_verts, a.out_normals, a.out_rgb, a.newidx, a.max_v},
+                   a.V, a.tot, a.base, a.counts, st));
   if (a.F > 0 && a.V > 0)  // (after the vertices' placement: the faces read newidx across workgroups)
-    TRY(scan_place(KeepFlag{a}, KeepSink{a}, a.F, a.tot, a.base, a.counts + 1, st));
+    TRY(scan_place(KeepFlag{a}, SubFaceSink{a.faces, a.newidx, a.out_faces, a.max_f}, a.F, a.tot, a.base, a.counts + 1, st));
   return hipSuccess;
 }
 

@@ -35,21 +35,11 @@ constexpr double MS_POS_ONE = 1048576.0;    // 2^20: fixed point of the lattice 
 constexpr double MS_NRM_ONE = 268435456.0;  // 2^28: fixed point of the normals' components (clamped to [-2, 2]: at most 2^29)
 constexpr long long MS_FLAG_TABLE_FULL = 1;
 
-__device__ inline int ms_atomic_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline long long ms_atomic_add(long long* p, long long v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // -> the slot's value before: -1 when f was stored
 __device__ inline int ms_atomic_claim(int* p, int f) {
   int expected = -1;
   __hip_atomic_compare_exchange_strong(p, &expected, f, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return expected;
-}
-
-__device__ inline long long ms_wave_sum(long long x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
 }
 
 // the clamped lattice coordinates uc[3] of vertex v and its cell (C order, z fastest); -1 when a coordinate is not finite
@@ -193,15 +183,15 @@ __global__ __launch_bounds__(CC_WG) void k_ms_accum(const MsArgs a) {
 #pragma unroll
     for (int d = 0; d < NS; ++d) {
       r[d] = mine ? term[d] : 0;
-      if (k > 1) r[d] = ms_wave_sum(r[d]);  // (uniform)
+      if (k > 1) r[d] = wave_sum(r[d]);  // (uniform)
     }
     if (lane == lead) {
-      ms_atomic_add(&a.cnt[lc], k);
+      agent_add(&a.cnt[lc], k);
 #pragma unroll
-      for (int d = 0; d < 3; ++d) ms_atomic_add(&a.S[(long long)lc * 3 + d], r[d]);
+      for (int d = 0; d < 3; ++d) agent_add(&a.S[(long long)lc * 3 + d], r[d]);
       if (NRM) {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) ms_atomic_add(&a.T[(long long)lc * 3 + d], r[3 + d]);
+        for (int d = 0; d < 3; ++d) agent_add(&a.T[(long long)lc * 3 + d], r[3 + d]);
       }
     }
     todo &= ~grp;
@@ -241,7 +231,7 @@ __global__ __launch_bounds__(CC_WG) void k_ms_faces(const MsArgs a) {
     a.fstate[fl] = -1;
   }
   const unsigned long long deg = __ballot(code == 1);
-  if (lane == 0 && deg) ms_atomic_add(&a.counts[4], (long long)__popcll(deg));
+  if (lane == 0 && deg) agent_add(&a.counts[4], (long long)__popcll(deg));
 }
 
 // grid = ceil(F / CC_WG), whole waves
@@ -267,7 +257,7 @@ __global__ __launch_bounds__(CC_WG) void k_ms_mark(const MsArgs a) {
     a.fstate[f] = kept ? 1 : 0;
   }
   const unsigned long long m = __ballot(dup);
-  if (lane == 0 && m) ms_atomic_add(&a.counts[5], (long long)__popcll(m));
+  if (lane == 0 && m) agent_add(&a.counts[5], (long long)__popcll(m));
 }
 
 // ---- output vertices ----

@@ -3,9 +3,8 @@
 // include/nerf_hip.h).
 //   k_me_insert      per face: take part?; its three undirected edges go into the edge table, count and tally by integer atomics
 //   k_me_edges       per slot: the edge's class -> counts; degrees by integer atomics, vertex flags by fetch_or
-//   k_me_degsum      per CC_PTS vertices: the sum of their degrees; vertices in use and the largest degree -> counts
-//   scan.h's k_flag_scan   the workgroup sums -> exclusive bases, the grand total (2 E) into off[V]
-//   k_me_offsets     per vertex: off[v] = its row's start
+//   scan.h's value scan over Degree   per vertex: off[v] = its row's start, the grand total (2 E) into off[V]; its sum pass (DegWatch)
+//                    leaves the vertices in use and the largest degree in counts
 //   k_me_fill        per slot: the edge's two directed entries, each placed through its row's cursor atomic
 //   k_me_step        per vertex: one Jacobi step -- walks its row, sums the neighbours' fixed-point coordinates in int64 registers
 //   k_me_nrm_accum   per face: rint(cross product * 2^40) added to its three vertices by int64 atomics
@@ -35,10 +34,6 @@ constexpr double ME_POS_ONE = 1073741824.0;     // 2^30: fixed point of the box 
 constexpr double ME_NRM_ONE = 1099511627776.0;  // 2^40: fixed point of a face's cross product (|N_k| <= 18: a term is below 2^45)
 constexpr long long ME_FLAG_TABLE_FULL = 1;
 
-__device__ inline int me_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline long long me_add(long long* p, long long v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // -> the slot's value before: -1 when key was stored
 __device__ inline long long me_claim(long long* p, long long key) {
   long long expected = -1;
@@ -58,16 +53,11 @@ __device__ inline unsigned long long me_hash(unsigned long long k) {
 // one add per wave: the lanes whose flag is set, counted by a ballot
 __device__ inline void me_count(bool flag, long long* counter) {
   const unsigned long long m = __ballot(flag);
-  if ((threadIdx.x & 63) == 0 && m) me_add(counter, (long long)__popcll(m));
+  if ((threadIdx.x & 63) == 0 && m) agent_add(counter, (long long)__popcll(m));
 }
 
-// does face f take part?  -> its corners in i[3]
-__device__ inline bool me_face(const MeArgs& a, long long f, int (&i)[3]) {
-  i[0] = a.faces[f * 3 + 0], i[1] = a.faces[f * 3 + 1], i[2] = a.faces[f * 3 + 2];
-  const unsigned V = (unsigned)a.V;
-  if ((unsigned)i[0] >= V || (unsigned)i[1] >= V || (unsigned)i[2] >= V) return false;  // never used as an address
-  return i[0] != i[1] && i[1] != i[2] && i[0] != i[2];
-}
+// does face f take part (three distinct corners in range)?  -> its corners in i[3]
+__device__ inline bool me_face(const MeArgs& a, long long f, int (&i)[3]) { return face_corners<true>(a.faces, a.V, f, i); }
 
 // the edge of slot s: false for an empty slot (or a word that is no key of this mesh)
 __device__ inline bool me_slot_edge(const MeArgs& a, long long s, int& lo, int& hi) {
@@ -78,42 +68,33 @@ __device__ inline bool me_slot_edge(const MeArgs& a, long long s, int& lo, int& 
   return (unsigned)lo < (unsigned)a.V && (unsigned)hi < (unsigned)a.V && lo < hi;
 }
 
-__device__ inline bool me_finite3(const float (&p)[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
 // the clamped box coordinate of p along axis d
 __device__ inline double me_uc(const MeArgs& a, float p, int d) {
   const double u = ((double)p - (double)a.lo[d]) / (double)a.scale;
   return fmin(fmax(u, -1.0), 2.0);
 }
 
-// exclusive prefix of v across the workgroup in thread order, plus the workgroup's total; part[CC_WG / 64] of LDS, ends with a barrier
-__device__ inline long long me_wg_prefix(long long v, long long* part, long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long y = __shfl_up(x, d);
-    if (lane >= d) x += y;
+// the value, watch and sink of the degrees' scan.  A degree is what k_me_edges left, kept inside [0, V]; k_value_place recomputes
+// it: nothing writes the degrees after k_me_edges
+struct Degree {
+  const int* degree;
+  long long V;
+  __device__ long long operator()(long long v) const { return count_in(degree, v, V); }
+};
+struct DegWatch {  // counts[5] = the vertices of degree > 0, counts[7] = the largest degree
+  long long* counts;
+  WatchMax top;
+  __device__ void operator()(long long d) {
+    top(d);
+    me_count(d > 0, &counts[5]);
   }
-  if (lane == 63) part[wave] = x;
-  __syncthreads();
-  long long before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CC_WG / 64; ++w) {
-    const long long t = part[w];
-    before += (w < wave) ? t : 0;
-    total += t;
-  }
-  __syncthreads();
-  return before + x - v;
-}
-
-// a degree as the scan takes it: what k_me_edges left, kept inside [0, V]
-__device__ inline long long me_degree(const MeArgs& a, long long v) {
-  const int d = a.degree[v];
-  return d < 0 ? 0 : (d > a.V ? a.V : d);
-}
+  __device__ void done() { top.done(); }
+};
+struct RowSink {  // off[V] (the grand total) is k_flag_scan's
+  long long* off;
+  __device__ void operator()(long long v, long long, long long pre) const { off[v] = pre; }
+  __device__ void end(long long) const {}
+};
 
 }  // namespace
 
@@ -145,8 +126,8 @@ __global__ __launch_bounds__(CC_WG) void k_me_insert(const MeArgs a) {
       if (slot < 0) {
         full = true;
       } else {
-        me_add(&a.cnt[slot], 1);
-        me_add(&a.tally[slot], p < q ? 1 : -1);
+        agent_add(&a.cnt[slot], 1);
+        agent_add(&a.tally[slot], p < q ? 1 : -1);
       }
     }
     if (full) __hip_atomic_fetch_or(&a.counts[6], ME_FLAG_TABLE_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -163,8 +144,8 @@ __global__ __launch_bounds__(CC_WG) void k_me_edges(const MeArgs a) {
   if (edge) {
     c = a.cnt[s];
     t = a.tally[s];
-    me_add(&a.degree[lo], 1);
-    me_add(&a.degree[hi], 1);
+    agent_add(&a.degree[lo], 1);
+    agent_add(&a.degree[hi], 1);
     const int bits = (c == 1 ? 1 : 0) | (c > 2 ? 2 : 0);
     if (bits) {
       __hip_atomic_fetch_or(&a.vflags[lo], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -177,47 +158,7 @@ __global__ __launch_bounds__(CC_WG) void k_me_edges(const MeArgs a) {
   me_count(edge && c == 2 && t != 0, &a.counts[4]);
 }
 
-// ---- degrees -> row offsets ----
-
-// grid = cc_blocks(V)
-__global__ __launch_bounds__(CC_WG) void k_me_degsum(const MeArgs a) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = 0;
-  int most = 0;
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long v = base + r * CC_WG + threadIdx.x;
-    const long long d = v < a.V ? me_degree(a, v) : 0;
-    long long total;
-    (void)me_wg_prefix(d, part, total);
-    run += total;
-    most = d > most ? (int)d : most;
-    me_count(d > 0, &a.counts[5]);
-  }
-  if (threadIdx.x == 0) a.tot[blockIdx.x] = run;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const int o = __shfl_xor(most, d);
-    most = o > most ? o : most;
-  }
-  if ((threadIdx.x & 63) == 0 && most > 0)
-    __hip_atomic_fetch_max(&a.counts[7], (long long)most, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid = cc_blocks(V); off[V] (the grand total) is k_flag_scan's
-__global__ __launch_bounds__(CC_WG) void k_me_offsets(const MeArgs a) {
-  __shared__ long long part[CC_WG / 64];
-  const long long base = (long long)blockIdx.x * CC_PTS;
-  long long run = a.base[blockIdx.x];
-  for (int r = 0; r < CC_ROUNDS; ++r) {
-    const long long v = base + r * CC_WG + threadIdx.x;
-    const long long d = v < a.V ? me_degree(a, v) : 0;
-    long long total;
-    const long long pre = me_wg_prefix(d, part, total);
-    if (v < a.V) a.off[v] = run + pre;
-    run += total;
-  }
-}
+// ---- row offsets -> the adjacency ----
 
 // grid = ceil(slots / CC_WG), one thread per slot.  Which entry of its row an edge gets depends on the interleaving; the row's set of
 // entries does not.
@@ -230,7 +171,7 @@ __global__ __launch_bounds__(CC_WG) void k_me_fill(const MeArgs a) {
   for (int e = 0; e < 2; ++e) {
     const int v = end[e];
     const long long b = a.off[v], n = a.off[v + 1];
-    const long long at = b + (long long)me_add(&a.cursor[v], 1);
+    const long long at = b + (long long)agent_add(&a.cursor[v], 1);
     if (b >= 0 && at >= b && at < n && n <= a.cap) a.adj[at] = end[1 - e];
   }
 }
@@ -246,14 +187,14 @@ __global__ __launch_bounds__(CC_WG) void k_me_step(const MeArgs a) {
   const float p[3] = {__uint_as_float(bits[0]), __uint_as_float(bits[1]), __uint_as_float(bits[2])};
   long long S[3] = {0, 0, 0}, n = 0;
   const bool pinned = a.pin != nullptr && (a.pin[v] & 1) != 0;
-  if (me_finite3(p) && !pinned) {
+  if (finite3(p) && !pinned) {
     long long b = a.off[v], e = a.off[v + 1];
     if (b < 0 || e < b || e > a.cap) b = e = 0;
     for (long long r = b; r < e; ++r) {
       const int j = a.adj[r];
       if ((unsigned)j >= (unsigned)a.V) continue;
       const float pj[3] = {a.verts[(long long)j * 3 + 0], a.verts[(long long)j * 3 + 1], a.verts[(long long)j * 3 + 2]};
-      if (!me_finite3(pj)) continue;
+      if (!finite3(pj)) continue;
       ++n;
 #pragma unroll
       for (int d = 0; d < 3; ++d) S[d] += (long long)__builtin_rint(me_uc(a, pj[d], d) * ME_POS_ONE);
@@ -284,7 +225,7 @@ __global__ __launch_bounds__(CC_WG) void k_me_nrm_accum(const MeArgs a) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float p[3] = {a.verts[(long long)i[c] * 3 + 0], a.verts[(long long)i[c] * 3 + 1], a.verts[(long long)i[c] * 3 + 2]};
-    ok = ok && me_finite3(p);
+    ok = ok && finite3(p);
 #pragma unroll
     for (int d = 0; d < 3; ++d) u[c][d] = me_uc(a, p[d], d);
   }
@@ -301,7 +242,7 @@ __global__ __launch_bounds__(CC_WG) void k_me_nrm_accum(const MeArgs a) {
     const long long term = (long long)__builtin_rint(N[d] * ME_NRM_ONE);
     if (term == 0) continue;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) me_add(&a.T[(long long)i[c] * 3 + d], term);
+    for (int c = 0; c < 3; ++c) agent_add(&a.T[(long long)i[c] * 3 + d], term);
   }
 }
 
@@ -329,12 +270,10 @@ hipError_t launch_me_build(const MeArgs& a, hipStream_t st) {
   TRY(hipMemsetAsync(a.cnt, 0, (size_t)a.slots * sizeof(int), st));
   TRY(hipMemsetAsync(a.tally, 0, (size_t)a.slots * sizeof(int), st));
   TRY(hipMemsetAsync(a.cursor, 0, (size_t)a.V * sizeof(int), st));
-  const int nb = cc_blocks(a.V);
   LAUNCH(k_me_insert, dim3(grid(a.F, CC_WG)), dim3(CC_WG), 0, st, a);
   LAUNCH(k_me_edges, dim3(grid(a.slots, CC_WG)), dim3(CC_WG), 0, st, a);
-  LAUNCH(k_me_degsum, dim3(nb), dim3(CC_WG), 0, st, a);
-  LAUNCH((k_flag_scan<long long, long long>), dim3(1), dim3(1024), 0, st, a.tot, a.base, nb, a.off + a.V);
-  LAUNCH(k_me_offsets, dim3(nb), dim3(CC_WG), 0, st, a);
+  TRY(scan_values<long long>(Degree{a.degree, a.V}, DegWatch{a.counts, {&a.counts[7]}}, RowSink{a.off}, a.V, NO_CAP, a.tot, a.base,
+                             a.off + a.V, st));
   LAUNCH(k_me_fill, dim3(grid(a.slots, CC_WG)), dim3(CC_WG), 0, st, a);
   return hipSuccess;
 }

@@ -6,10 +6,12 @@
 //   Totals / scan_totals        channels of workgroup totals -> exclusive bases and the grand totals, by ONE workgroup of 1024
 //   k_flag_count / k_flag_scan / k_flag_place   compaction over a 0/1 flag per item in three launches: totals per workgroup of CC_PTS
 //                               items, the scan of the totals, then the placement (scan_count: the first two, scan_place: all three)
+//   k_value_sum / k_flag_scan / k_value_place   the same three launches over an integer value per item: every item's exclusive prefix
+//                               (scan_values); cells_to_start: per-cell counts -> start[], the middle of a counting sort by cell
 // The output order is fixed by the scans -- no atomic places anything -- and the scan is three kernels, never a single-pass look-back:
 // no flag crosses workgroups (or XCDs) inside a launch.  Everything here has internal linkage: every includer gets its own copy.
 #pragma once
-#include "kernels.h"
+#include "mesh_parts.h"
 
 #define LAUNCH(...)                               \
   do {                                            \
@@ -28,8 +30,6 @@ namespace nerf {
 namespace {
 
 inline unsigned grid(long long n, int wg) { return (unsigned)((n + wg - 1) / wg); }
-
-__device__ inline int agent_atomic_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // lanes below this one whose bit is set in the ballot m
 __device__ inline unsigned lane_prefix(unsigned long long m) {
@@ -196,6 +196,100 @@ hipError_t scan_place(const Flag& flag, const Sink& sink, long long n, int* tot,
   TRY(scan_count(flag, n, tot, base, count, st));
   LAUNCH((k_flag_place<Flag, Sink>), dim3(cc_blocks(n)), dim3(CC_WG), 0, st, flag, sink, n, base);
   return hipSuccess;
+}
+
+// ---- the scan of a value per item: Value = item i -> a non-negative integer, Watch = sees every value of the sum pass (all lanes
+// reach it in every round, with 0 past the end), Sink = (item i, its value, the sum of the values before it) and end(the sum of all).
+// The sums run in 64 bits inside a workgroup; the totals, the bases and what the sink sees are kept at or below cap (NO_CAP: none). ----
+
+constexpr long long NO_CAP = 0x7FFFFFFFFFFFFFFFll;
+
+struct NoWatch {
+  __device__ void operator()(long long) {}
+  __device__ void done() {}
+};
+// the largest value (below 2^31) into *most by an integer atomic; most may be null
+struct WatchMax {
+  long long* most;
+  int top = 0;
+  __device__ void operator()(long long v) { top = (int)v > top ? (int)v : top; }
+  __device__ void done() {
+    if (!most) return;
+    top = wave_max(top);
+    if ((threadIdx.x & 63) == 0 && top > 0) __hip_atomic_fetch_max(most, (long long)top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// grid = nb = cc_blocks(n)
+template <class T, class Value, class Watch>
+__global__ __launch_bounds__(CC_WG) void k_value_sum(const Value value, Watch watch, long long n, long long cap, T* __restrict__ tot) {
+  __shared__ long long part[CC_WG / 64];
+  const long long base = (long long)blockIdx.x * CC_PTS;
+  long long run = 0;
+  for (int r = 0; r < CC_ROUNDS; ++r) {
+    const long long i = base + r * CC_WG + threadIdx.x;
+    const long long v = i < n ? (long long)value(i) : 0;
+    long long total;
+    (void)wg_prefix_sum<long long>(v, part, total);
+    run += total;
+    watch(v);
+  }
+  if (threadIdx.x == 0) tot[blockIdx.x] = (T)(run > cap ? cap : run);
+  watch.done();
+}
+
+// grid = nb.  The values are recomputed, not stored: between the sum launch and this one nothing may change them (a sink may change
+// its own item's once it has been read).
+template <class T, class Value, class Sink>
+__global__ __launch_bounds__(CC_WG) void k_value_place(const Value value, const Sink sink, long long n, long long cap, const T* __restrict__ bases) {
+  __shared__ long long part[CC_WG / 64];
+  const long long base = (long long)blockIdx.x * CC_PTS;
+  long long run = bases[blockIdx.x];
+  for (int r = 0; r < CC_ROUNDS; ++r) {
+    const long long i = base + r * CC_WG + threadIdx.x;
+    const long long v = i < n ? (long long)value(i) : 0;
+    long long total;
+    const long long pre = wg_prefix_sum<long long>(v, part, total);
+    if (i < n) sink(i, v, run + pre > cap ? cap : run + pre);
+    run += total;
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) sink.end(run > cap ? cap : run);
+}
+
+// tot, base: [cc_blocks(n)] of T; *count = the sum of the workgroups' (capped) totals
+template <class T, class Value, class Watch, class Sink>
+hipError_t scan_values(const Value& value, const Watch& watch, const Sink& sink, long long n, long long cap, T* tot, T* base,
+                       long long* count, hipStream_t st) {
+  const int nb = cc_blocks(n);
+  LAUNCH((k_value_sum<T, Value, Watch>), dim3(nb), dim3(CC_WG), 0, st, value, watch, n, cap, tot);
+  LAUNCH((k_flag_scan<T, T>), dim3(1), dim3(1024), 0, st, tot, base, nb, count);
+  LAUNCH((k_value_place<T, Value, Sink>), dim3(nb), dim3(CC_WG), 0, st, value, sink, n, cap, base);
+  return hipSuccess;
+}
+
+// ---- the middle of a counting sort by cell: between the caller's count launch, which left cnt[c] items in cell c, and its place
+// launch, which takes cnt as the cells' cursors ----
+
+struct CellCount {
+  const int* cnt;
+  long long cap;
+  __device__ long long operator()(long long c) const { return count_in(cnt, c, cap); }
+};
+struct CellStart {  // start[c] = the items of the cells before c, start[ncell] = all of them; the counts become the cursors (0)
+  int *cnt, *start;
+  long long ncell;
+  __device__ void operator()(long long c, long long, long long pre) const {
+    start[c] = (int)pre;
+    cnt[c] = 0;
+  }
+  __device__ void end(long long all) const { start[ncell] = (int)all; }
+};
+
+// cnt [ncell] -> start [ncell + 1], every entry at most cap (< 2^31); *total = the items, *most (may be null) = the fullest cell's.
+// (T = int; a template, as k_flag_scan is, so that only the includers that call it carry its kernels)
+template <class T>
+hipError_t cells_to_start(T* cnt, int ncell, long long cap, T* tot, T* base, T* start, long long* total, long long* most, hipStream_t st) {
+  return scan_values<T>(CellCount{cnt, cap}, WatchMax{most}, CellStart{cnt, start, ncell}, ncell, cap, tot, base, total, st);
 }
 
 }  // namespace

@@ -129,6 +129,38 @@ def test_nearest_one_crowded_cell_and_outliers(pkg, dev):
     _check_nearest(pkg, dev, ref, q)
 
 
+# one workgroup of the cell scan (2048 cells) less one, exactly one, one more; 1024 * 2048 + 1: the first size at which a thread of the
+# scan of the workgroups' totals takes a run of two
+SCAN_EDGES = (2047, 2048, 2049, 1024 * 2048 + 1)
+
+
+@pytest.mark.parametrize("ncell,axis", [(2047, 0), (2048, 2), (2049, 0), (2049, 2), (1024 * 2048 + 1, 2)])
+def test_nearest_grids_at_the_scan_edges(pkg, dev, ncell, axis):
+    """Explicit grids of ncell cells in a row along one axis: the first cell, the last, and the cells on both sides of the first
+    workgroup's end hold points; the last cell is the fullest."""
+    cell = F32(1.0) / F32(ncell)
+    dims = [1, 1, 1]
+    dims[axis] = ncell
+    rng = np.random.default_rng(ncell + axis)
+    ref, q = D.cloud(300, 61 + axis).copy(), D.cloud(200, 63 + axis).copy()
+    at = [k for k in (0, 2046, 2047, 2048, ncell - 2, ncell - 1) if k < ncell] + [ncell - 1] * 6
+    ref[:len(at), axis] = ((np.array(at, np.float64) + 0.5) * np.float64(cell)).astype(F32)
+    ref[len(at), 1] = np.nan  # one row that is not finite
+    ref = ref[rng.permutation(len(ref))]
+    q[:len(at), axis] = ref[:len(at), axis][::-1]
+    fin = np.isfinite(ref).all(1)
+    k = np.clip(np.floor((ref[fin, axis].astype(np.float64) - 0.0) / np.float64(cell)), 0, ncell - 1).astype(np.int64)
+    per = np.bincount(k, minlength=ncell)
+    assert per[0] >= 1 and per[ncell - 1] == per.max() >= 7 and all(per[c] >= 1 for c in (2046, 2047, 2048) if c < ncell)
+    want_i, want_d = D.nearest(ref, q)
+    tr, tq = _t(ref, dev), _t(q, dev)
+    ws, counts = pkg.ops.points_grid(tr, (0.0, 0.0, 0.0), float(cell), dims, n_query=len(q))
+    assert counts.cpu().tolist() == [int(fin.sum()), int(per.max())]
+    for sort in (False, True):
+        idx, d2 = pkg.ops.points_nearest(tq, len(ref), (0.0, 0.0, 0.0), float(cell), dims, ws, sort_queries=sort)
+        assert np.array_equal(idx.cpu().numpy(), want_i) and np.array_equal(_bits64(d2), _bits64(want_d)), sort
+
+
 def test_nearest_rows_that_are_not_finite(pkg, dev):
     ref, q = D.cloud(3000, 20).copy(), D.cloud(1000, 21).copy()
     rng = np.random.default_rng(22)
@@ -177,6 +209,41 @@ def test_sample_surface(pkg, dev, name):
     assert np.array_equal(_bits(m.verts), _bits(v)) and np.array_equal(m.faces.cpu().numpy(), f)
     if name == "blobs":
         assert len(f) == 2052  # one over a scan block
+
+
+def _scan_edge_mesh(F):
+    """300 random vertices, F faces of three distinct random corners; one face in ten, and faces on both sides of the first workgroup's
+    end, repeat a corner and so weigh nothing"""
+    rng = np.random.default_rng(F)
+    V = 300
+    a, o1, d = rng.integers(0, V, F), rng.integers(1, V, F), rng.integers(1, V - 1, F)
+    o2 = (o1 - 1 + d) % (V - 1) + 1  # in [1, V), and never o1
+    f = np.stack((a, (a + o1) % V, (a + o2) % V), axis=1).astype(np.int32)
+    assert (f[:, 0] != f[:, 1]).all() and (f[:, 1] != f[:, 2]).all() and (f[:, 0] != f[:, 2]).all()
+    flat = rng.random(F) < 0.1
+    flat[[k for k in (0, 2045, 2047, 2049, 2050) if k < F]] = True
+    flat[[k for k in (2046, 2048) if k < F]] = False
+    f[flat, 1] = f[flat, 0]
+    return D.cloud(V, 71), f
+
+
+@pytest.mark.parametrize("F", SCAN_EDGES)
+def test_sample_surface_at_the_scan_edges(pkg, dev, F):
+    """The scan of the weights at its partition edges (the reference at F = 2^21 + 1 takes about 3 s of numpy)."""
+    v, f = _scan_edge_mesh(F)
+    # the first seed whose REFERENCE samples reach a face of the second workgroup (F = 2049 has one such face with a weight, 2048)
+    for seed in range(7, 64):
+        want_p, want_f, W = D.sample_surface(v, f, 1000, seed)
+        if F <= 2048 or want_f.max() >= 2048:
+            break
+    w = D.weights(v, f[:2051])
+    assert w[0] == 0 and w[2045] == 0 and w[2046] > 0 and (F <= 2047 or w[2047] == 0) and (F <= 2048 or w[2048] > 0)
+    assert W > 0 and (want_f >= 0).all() and (F <= 2048 or want_f.max() >= 2048)
+    m = _mesh(pkg, dev, v, f)
+    lo, scale = S.default_box(v)
+    assert int(pkg.ops.mesh_sample(m.verts, m.faces, 1000, seed, lo.tolist(), float(scale))[2].cpu()) == W  # the scan's grand total
+    p, fid = pkg.mesh.sample_surface(m, 1000, seed)
+    assert np.array_equal(fid.cpu().numpy(), want_f) and np.array_equal(_bits(p), _bits(want_p))
 
 
 def test_sample_surface_without_area(pkg, dev):

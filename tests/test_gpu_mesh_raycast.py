@@ -232,6 +232,29 @@ def test_grid_independence(pkg, dev, name):
             assert h.entries > h.taking_part - h.outside > 0
 
 
+@pytest.mark.parametrize("dims", [(23, 1, 89), (16, 8, 16), (3, 683, 1)])
+def test_grids_at_the_scan_edges(pkg, dev, dims):
+    """Grids of 2047, 2048 and 2049 cells -- one workgroup of the cell scan less one, exactly one, one more -- under the random mesh
+    stretched to fill the grid, and one triangle beside it: entries from the first cell to the last, one face OUTSIDE."""
+    assert int(np.prod(dims)) in (2047, 2048, 2049)
+    v, f = MESHES["random"]()
+    lo, hi = _box(v)
+    v = ((v - lo) / (hi - lo) * (np.asarray(dims, F32) - F32(0.04)) + F32(0.02)).astype(F32)
+    v, f = np.concatenate((v, np.array([[-3, -3, -3], [-2, -3, -3], [-3, -2, -3]], F32))), np.concatenate((f, [[len(v), len(v) + 1, len(v) + 2]])).astype(np.int32)
+    m = _mesh(pkg, dev, v, f)
+    h = pkg.mesh.build_raycast(m, (np.zeros(3, F32), 1.0, dims))
+    counts = R.grid_counts(v, f, h.lo, h.cell, h.dims)
+    assert tuple(h.dims) == dims and [h.taking_part, h.entries, h.outside] == counts and h.outside == 1 and h.entries > h.taking_part
+    part, inside, b0, b1 = R.grid_boxes(v, f, h.lo, h.cell, h.dims)
+    cell_of = lambda b: int(((b[0] * dims[1] + b[1]) * dims[2] + b[2]))
+    firsts, lasts = [cell_of(b) for b in b0[inside]], [cell_of(b) for b in b1[inside]]
+    assert min(firsts) == 0 and max(lasts) == int(np.prod(dims)) - 1  # the first and the last cell hold entries
+    o, d = R.random_rays(v, 200, 5)
+    want = R.cast(v, f, o, d)
+    assert _same(pkg.mesh.raycast(h, _t(o, dev), _t(d, dev)), want) and (want[2] >= 0).sum() > 20
+    assert np.array_equal(pkg.mesh.raycast(h, _t(o, dev), _t(d, dev), any_hit=True).cpu().numpy(), (want[2] >= 0).astype(np.uint8))
+
+
 # ---- (3) visibility and face selection ----
 
 def test_visibility_on_nested_balls(pkg, dev):
