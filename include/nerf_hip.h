@@ -55,7 +55,8 @@ extern "C" {
                                      nerf_hip_mesh_edges_build (with NERF_HIP_EDGES_TABLE_FULL), nerf_hip_mesh_smooth_step,
                                      nerf_hip_mesh_vertex_normals; nerf_hip_mesh_measure, nerf_hip_mesh_sample_ws_bytes,
                                      nerf_hip_mesh_sample, nerf_hip_points_nearest_ws_bytes, nerf_hip_points_grid_build,
-                                     nerf_hip_points_nearest, nerf_hip_distance_stats */
+                                     nerf_hip_points_nearest, nerf_hip_distance_stats; the nerf_hip_mesh_raycast* calls,
+                                     nerf_hip_mesh_face_rays, nerf_hip_mesh_select_faces_*; nerf_hip_tsdf_integrate */
 
 enum {
   NERF_HIP_OK = 0,
@@ -824,6 +825,46 @@ int nerf_hip_mesh_select_faces_count(const int32_t* faces, int64_t V, int64_t F,
 int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, const float* rgb, const int32_t* faces, int64_t V, int64_t F,
                                     const uint8_t* keep, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_rgb,
                                     int32_t* out_faces, int64_t max_v, int64_t max_f, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 addition.  TSDF fusion: depth images of known cameras integrated into a truncated signed distance volume (DESIGN.md section
+ * 3h-9).  tsdf and weight are fp32 volumes [nx][ny][nz] (C order, z fastest) on the lattice of nerf_hip_density_grid: point (i, j, k) is
+ * lo + (i, j, k) * step, each coordinate one fp32 product and one fp32 sum.  The caller owns both volumes and zeroes them before the
+ * first call; later calls continue the same fusion.  depth[n][H][W] (fp32) is the distance along the UNIT ray of pixel (row x, column
+ * y) of view c; opacity[n][H][W] (fp32) may be NULL.  cam_o (HOST fp32 [n][3]) are the cameras' positions and Q (HOST fp64 [n][9],
+ * row-major) their maps from a world direction to homogeneous pixel coordinates, Q = inverse(R K^T) as in rule V above.
+ *
+ * T. THE FUSION RULE.  All arithmetic is fp64 on the fp32 inputs widened exactly; every operation is rounded on its own and evaluated
+ *    as bracketed (rule R's convention); every comparison is false on NaN.  Per voxel p, with state (T, Wt) = (tsdf, weight) at p, and
+ *    per view c IN VIEW ORDER:
+ *       w   = double(p) - double(cam_o_c)                                  per axis
+ *       m_i = (Q_i0 wx + Q_i1 wy) + Q_i2 wz                                i = 0, 1, 2
+ *       x   = floor(m_0 / m_2 + 0.5),   y = floor(m_1 / m_2 + 0.5)         (x is the row: quirk Q2)
+ *       IN VIEW iff m_2 > 0, 0 <= x <= H - 1 and 0 <= y <= W - 1           (compared in fp64, before any conversion to an integer)
+ *       r   = sqrt((wx wx + wy wy) + wz wz)
+ *       d   = depth[c][x][y],   a = opacity[c][x][y]
+ *       FOREGROUND iff opacity is NULL or a >= min_opacity
+ *    A voxel that is not in view is not observed.  A FOREGROUND pixel observes the voxel iff d is finite, d > 0 and
+ *    sdf = d - r >= -trunc; the observation is val = min(1.0, sdf / trunc).  With NERF_HIP_TSDF_CARVE a pixel that is in view and NOT
+ *    foreground observes the voxel with val = 1.0 (the ray saw nothing: everything along it is empty); without the flag such a pixel
+ *    observes nothing.  An observation updates
+ *       T'  = fp32(((double(T) * double(Wt)) + val) / (double(Wt) + 1.0)),   Wt' = fp32(double(Wt) + 1.0)
+ *    The state is rounded to fp32 after every view, so the result does not depend on how the views are grouped into launches or calls.
+ *    T > 0 in front of the observed surface, T < 0 behind it (down to one truncation distance); Wt = the number of observations.
+ *
+ * One thread per voxel, z fastest; each launch reads and writes every voxel once and runs NERF_HIP_TSDF_VIEWS_PER_LAUNCH views, whose
+ * cameras travel in the kernel arguments.  No atomics: every output is a pure function of the input.  Enqueue-only; every argument is
+ * checked on the host before anything is enqueued (NERF_HIP_ERR_ARG): a dimension < 1, nx * ny * nz >= 2^31, n < 0, H < 1, W < 1,
+ * n * H * W >= 2^31, a NULL tsdf / weight / lo3 / step3 and, with n > 0, a NULL depth / cam_o / Q, a lo, step, cam_o or Q that is not
+ * finite, trunc not finite or not > 0, min_opacity NaN, a flag bit other than NERF_HIP_TSDF_CARVE.  n == 0 succeeds and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_TSDF_CARVE 1
+#define NERF_HIP_TSDF_VIEWS_PER_LAUNCH 32 /* 88 bytes of camera each: 2.8 KB of the 4 KB a kernel's arguments may take */
+
+int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* lo3, const float* step3,
+                            const float* depth, const float* opacity, int n, int H, int W,
+                            const float* cam_o /* HOST [n][3] */, const double* Q /* HOST [n][9] */,
+                            double trunc, float min_opacity, int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -22,6 +22,8 @@ STATUS_RESAMPLE_INDEX = 1 << 0
 STATUS_PREP_TIMEOUT = 1 << 1
 SIMPLIFY_TABLE_FULL = 1 << 0
 EDGES_TABLE_FULL = 1 << 0
+TSDF_CARVE = 1 << 0
+TSDF_VIEWS_PER_LAUNCH = 32  # NERF_HIP_TSDF_VIEWS_PER_LAUNCH: views whose cameras travel in one launch's kernel arguments
 
 _p = C.c_void_p
 _PROTOS = {
@@ -96,6 +98,8 @@ _PROTOS = {
     "nerf_hip_mesh_select_faces_count": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_size_t, _p, _p]),
     "nerf_hip_mesh_select_faces_emit": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int64, _p, _p, C.c_size_t, _p, _p, _p, _p, C.c_int64, C.c_int64,
                                                   _p]),
+    "nerf_hip_tsdf_integrate": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_double,
+                                          C.c_float, C.c_int, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -1,6 +1,6 @@
 // api_geometry.hip -- the geometry part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h): point and gradient queries,
 // density grids, marching cubes, the narrow band, mesh components, mesh simplification, mesh edges / smoothing / normals, mesh
-// measures / samples / nearest points / distance statistics, ray casting / face visibility / face selection and image metrics.  Host code only, as api.hip: argument checks,
+// measures / samples / nearest points / distance statistics, ray casting / face visibility / face selection, TSDF fusion and image metrics.  Host code only, as api.hip: argument checks,
 // workspace carve-up and kernel sequencing on the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -1357,6 +1357,61 @@ int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, co
   a.max_v = max_v;
   a.max_f = max_f;
   HIP_TRY(launch_sel_emit(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+static_assert(TSDF_VIEWS == NERF_HIP_TSDF_VIEWS_PER_LAUNCH, "the header states the kernel's views per launch");
+
+int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* lo3, const float* step3, const float* depth,
+                            const float* opacity, int n, int H, int W, const float* cam_o, const double* Q, double trunc, float min_opacity,
+                            int flags, void* stream) {
+  if (int rc = check_grid(nx, ny, nz)) return rc;
+  if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);
+  if (H < 1 || W < 1) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: an image has at least one pixel", H, W);
+  // (H * W first: three 31-bit factors would not fit 64 bits)
+  if ((long long)H * W >= (1ll << 31) || (long long)n * ((long long)H * W) >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "n=%d H=%d W=%d: the depth images must stay below 2^31 pixels", n, H, W);
+  if ((flags & ~NERF_HIP_TSDF_CARVE) != 0) return fail(NERF_HIP_ERR_ARG, "flags=0x%x: the only flag is NERF_HIP_TSDF_CARVE", flags);
+  if (!isfinite(trunc) || !(trunc > 0.0)) return fail(NERF_HIP_ERR_ARG, "trunc=%g: the truncation distance must be finite and > 0", trunc);
+  if (min_opacity != min_opacity) return fail(NERF_HIP_ERR_ARG, "min_opacity is NaN");
+  if (!tsdf || !weight || !lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "tsdf / weight / lo3 / step3 is null");
+  if (int rc = check_finite3(lo3, "lo", "the lattice's corner")) return rc;
+  if (int rc = check_finite3(step3, "step", "the lattice's step")) return rc;
+  if (n == 0) return NERF_HIP_OK;  // (empty arrays may have null pointers)
+  if (!depth || !cam_o || !Q) return fail(NERF_HIP_ERR_ARG, "depth / cam_o / Q is null");
+  for (int c = 0; c < n; ++c) {
+    if (int rc = check_finite3(cam_o + (size_t)c * 3, "cam_o", "a camera's position")) return rc;
+    for (int e = 0; e < 9; ++e)
+      if (!isfinite(Q[(size_t)c * 9 + e])) return fail(NERF_HIP_ERR_ARG, "Q[%d][%d]=%g: a camera's matrix must be finite", c, e, Q[(size_t)c * 9 + e]);
+  }
+  if (int rc = check_device()) return rc;
+  TsdfArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tsdf = tsdf;
+  a.weight = weight;
+  a.ny = ny;
+  a.nz = nz;
+  a.npts = nx * ny * nz;
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.step[c] = step3[c];
+  }
+  a.H = H;
+  a.W = W;
+  a.carve = (flags & NERF_HIP_TSDF_CARVE) != 0;
+  a.min_opacity = min_opacity;
+  a.trunc = trunc;
+  const size_t hw = (size_t)H * W;
+  // launches in view order on one stream: each reads the state the one before it wrote
+  for (int v0 = 0; v0 < n; v0 += TSDF_VIEWS) {
+    a.nviews = n - v0 < TSDF_VIEWS ? n - v0 : TSDF_VIEWS;
+    a.depth = depth + (size_t)v0 * hw;
+    a.opacity = opacity ? opacity + (size_t)v0 * hw : nullptr;
+    for (int c = 0; c < a.nviews; ++c) {
+      for (int e = 0; e < 9; ++e) a.cam[c].Q[e] = Q[(size_t)(v0 + c) * 9 + e];
+      for (int e = 0; e < 3; ++e) a.cam[c].o[e] = cam_o[(size_t)(v0 + c) * 3 + e];
+    }
+    HIP_TRY(launch_tsdf_integrate(a, static_cast<hipStream_t>(stream)));
+  }
   return NERF_HIP_OK;
 }
 

@@ -668,6 +668,34 @@ hipError_t launch_rc_face_rays(const RcFaceRaysArgs& a, hipStream_t st);
 hipError_t launch_sel_count(const SelArgs& a, hipStream_t st);
 hipError_t launch_sel_emit(const SelArgs& a, hipStream_t st);
 
+// ---- TSDF fusion of depth images (tsdf.hip; nerf_hip_tsdf_integrate; rule T of include/nerf_hip.h) ----
+constexpr int TSDF_VIEWS = 32;                 // views per launch (NERF_HIP_TSDF_VIEWS_PER_LAUNCH)
+constexpr int TSDF_WG = 256;
+
+struct TsdfCam {
+  double Q[9];             // row-major: world direction -> homogeneous pixel coordinates
+  float o[3];              // the camera's position
+  float pad;
+};
+
+struct TsdfArgs {
+  float *tsdf, *weight;    // [nx][ny][nz], z fastest
+  int ny, nz;
+  int npts;                // nx * ny * nz < 2^31
+  float lo[3], step[3];
+  const float* depth;      // [nviews][H][W]: the FIRST view of this launch onwards
+  const float* opacity;    // the same, or null
+  int nviews;              // 1 .. TSDF_VIEWS
+  int H, W;
+  int carve;
+  float min_opacity;
+  double trunc;
+  TsdfCam cam[TSDF_VIEWS]; // by value: uniform reads of the kernel arguments, no buffer to fill and keep alive
+};
+static_assert(sizeof(TsdfArgs) <= 4096, "a kernel's arguments may take 4 KB");
+
+hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st);
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

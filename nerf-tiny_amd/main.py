@@ -68,6 +68,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--mesh drops the faces that no camera of SPLIT (train, val or test; default train) sees: one shadow ray per face "
                          "and camera on the device, after the floaters are dropped and before smoothing, simplification, normals and "
                          "colours; prints the number of faces seen (default: keep everything)")
+    ap.add_argument("--mesh-tsdf", nargs="?", const="train", default=None, choices=["train", "val", "test"], metavar="SPLIT",
+                    help="--mesh extracts the zero set of a TSDF volume fused on the device from the rendered depth of SPLIT's cameras "
+                         "(train, val or test; default train) instead of the isosurface of sigma: --mesh-level and --mesh-band are ignored, "
+                         "the file is <...>_mesh<RES>_tsdf.ply (default: the isosurface)")
+    ap.add_argument("--mesh-tsdf-trunc", type=float, default=None, metavar="D",
+                    help="truncation distance of --mesh-tsdf in world units (default: 4 lattice steps)")
+    ap.add_argument("--mesh-tsdf-every", type=int, default=1, metavar="N", help="--mesh-tsdf fuses every N-th camera of the split (default 1)")
     ap.add_argument("--mesh-compare", default=None, metavar="FILE",
                     help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
                          "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
@@ -130,7 +137,8 @@ if __name__ == "__main__":
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
                              simplify=args.mesh_simplify, smooth=args.mesh_smooth, compare=args.mesh_compare,
-                             compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible)
+                             compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible,
+                             tsdf_from=args.mesh_tsdf, tsdf_trunc=args.mesh_tsdf_trunc, tsdf_every=args.mesh_tsdf_every)
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

@@ -4,7 +4,8 @@ DESIGN.md section 3h-3) --, simplification by uniform vertex clustering on the d
 edge topology, Taubin smoothing and face-derived vertex normals on the device (csrc/mesh_smooth.hip), geometry
 evaluation on the device -- measures, area-weighted surface samples, exact nearest points, Chamfer distance and F-scores
 (csrc/mesh_distance.hip) --, rays against a mesh on the device -- closest hits, occlusion, depth images, the
-faces no camera sees (csrc/mesh_raycast.hip) -- and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
+faces no camera sees (csrc/mesh_raycast.hip) --, TSDF fusion of depth images into a signed distance volume on the
+device (csrc/tsdf.hip) and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
 build on these."""
 from __future__ import annotations
 
@@ -616,6 +617,61 @@ def filter_faces(m, keep):
     verts = _on_device(m.verts, "filter_faces")
     keep = torch.as_tensor(keep).to(verts.device) != 0
     return Mesh(*ops.mesh_select_faces(verts, torch.as_tensor(m.faces), m.normals, m.rgb, keep))
+
+
+def tsdf_volume(shape, device):
+    """A zeroed TSDF state (T, Wt): two fp32 [nx, ny, nz] volumes on ``device`` -- the truncated signed distance, in units of the
+    truncation distance, and the number of observations of every lattice point -- for tsdf_integrate."""
+    from .nerf import grid_shape
+
+    shape = grid_shape(shape)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("tsdf_volume: the volumes live on a ROCm device (MI355X); there is no CPU path")
+    return torch.zeros(shape, dtype=torch.float32, device=dev), torch.zeros(shape, dtype=torch.float32, device=dev)
+
+
+def tsdf_trunc(step):
+    """The default truncation distance of a lattice of fp32 ``step`` [3]: 4 x its largest step (a choice, not a measurement)."""
+    return 4.0 * float(np.asarray(step, dtype=np.float32).reshape(3).max())
+
+
+def tsdf_integrate(T, Wt, lo, step, depth, poses_bound17, K_inv, opacity=None, trunc=None, min_opacity=0.5, carve=True):
+    """Integrates depth images into the TSDF state (T, Wt) IN PLACE on the DEVICE and returns it.  T, Wt: tsdf_volume's pair over the
+    lattice lo + (i, j, k) * step (the density grid's: pass its lo and fp32 step).  depth [n, H, W] fp32: per pixel (row x, column y) of
+    camera c the distance to the surface along the UNIT ray the renderer marches along -- render(maps=True)'s D / A, raycast()'s t over
+    camera_rays(); +inf, NaN or <= 0: the pixel saw no surface.  poses_bound17 [n, 17] and K_inv: the cameras, as everywhere (camera_q
+    forms each view's Q and position).  opacity [n, H, W] or None: a pixel with opacity < min_opacity is background; with carve it
+    then marks every lattice point along its ray as empty, without carve it says nothing.  trunc: the truncation distance in world
+    units, by default tsdf_trunc(step).  Every lattice point within trunc behind a view's surface, or in front of it, averages
+    min(1, (depth - distance to the camera) / trunc) into T and counts 1 into Wt; the exact rule is T of include/nerf_hip.h and the
+    result does not depend on how the views are split over calls.  CPU tensors raise: there is no CPU path."""
+    from . import ops
+
+    T, Wt = _on_device(T, "tsdf_integrate"), _on_device(Wt, "tsdf_integrate")
+    depth = torch.as_tensor(depth)
+    if depth.dim() != 3:
+        raise ValueError(f"depth {tuple(depth.shape)}: [n, H, W]")
+    pb = poses_bound17 if torch.is_tensor(poses_bound17) else torch.from_numpy(np.array(poses_bound17))  # (np.array: a writable copy)
+    pb = pb.detach().cpu().reshape(-1, 17)
+    if pb.shape[0] != depth.shape[0]:
+        raise ValueError(f"{pb.shape[0]} poses for {depth.shape[0]} depth images")
+    lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+    step32 = np.asarray(step, dtype=np.float32).reshape(3)
+    cams = [camera_q(pb[c], K_inv) for c in range(pb.shape[0])]
+    ops.tsdf_integrate(T, Wt, lo32.tolist(), step32.tolist(), depth, opacity, [cam.tolist() for _, cam in cams],
+                       [Q.reshape(-1).tolist() for Q, _ in cams], tsdf_trunc(step32) if trunc is None else float(trunc), min_opacity, carve)
+    return T, Wt
+
+
+def tsdf_grid(T, Wt, unseen="solid"):
+    """The array marching_cubes(..., level=0.0) takes from a TSDF state: -T where Wt > 0 (marching cubes' inside is value > level, so
+    the negation keeps inside = behind the surface and the grid normals pointing outward); where no view observed the point, +1 for
+    unseen="solid" (unseen space is inside: the mesh closes behind what the cameras saw) or -1 for unseen="empty"."""
+    if unseen not in ("solid", "empty"):
+        raise ValueError(f"unseen={unseen!r}: 'solid' or 'empty'")
+    T = torch.as_tensor(T)
+    return torch.where(torch.as_tensor(Wt) > 0, -T, torch.full_like(T, 1.0 if unseen == "solid" else -1.0))
 
 
 def _np(a):

@@ -653,18 +653,21 @@ class NeRFModel(nn.Module):
 
         from . import mesh
 
-        if normals not in ("grid", "field"):
-            raise ValueError(f"normals={normals!r}: 'grid' or 'field'")
-        if simplify is not None and (int(simplify) != simplify or int(simplify) < 2):
-            raise ValueError(f"simplify={simplify!r}: None or an int >= 2 (cells of that many lattice steps)")
-        if smooth is not None and (int(smooth) != smooth or int(smooth) < 1):
-            raise ValueError(f"smooth={smooth!r}: None or an int >= 1 (Taubin iterations)")
+        _check_mesh_stages(normals, simplify, smooth)
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
         sigma = self.density_grid(lo32, hi32, shape) if band is None else self.density_band(lo32, hi32, shape, level, block=band)[0]
         verts, faces, nrm = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
         del sigma
+        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible)
+
+    def _mesh_stages(self, verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible):
+        """Everything of extract_mesh / extract_mesh_tsdf behind marching cubes, in extract_mesh's documented order: the component
+        filter, the visibility filter, smoothing, simplification, then the field normals and the colours at the final vertices.
+        verts / faces / nrm: marching cubes' output over the lattice (lo32, hi32, shape)."""
+        from . import mesh
+
         if min_faces is not None or keep_largest is not None:
             comps = mesh.components(faces, len(verts), verts)
             keep = mesh.select_components(comps, 1 if min_faces is None else min_faces, keep_largest)
@@ -684,6 +687,87 @@ class NeRFModel(nn.Module):
             nrm = field_normals(self.query_grad(verts)[2])
         rgb = self.query(verts, -nrm)[0] if color else None
         return mesh.Mesh(verts, faces, nrm, rgb)
+
+    @torch.no_grad()
+    def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None):
+        """TSDF fusion of the model's own rendered depth: every camera of views = (poses_bound [n, 17], K_inv, H, W) is rendered with
+        render(maps=True), its expected depth image is integrated into a truncated signed distance volume over the density grid's lattice
+        of the box [lo, hi] at res (mesh.tsdf_integrate; rule T of include/nerf_hip.h), and the state (T, Wt) -- two fp32 [nx, ny, nz]
+        device volumes -- is returned: mesh.tsdf_grid turns it into the array marching cubes takes at level 0.  The surface is then where
+        the rendered views agree it is, not where sigma crosses a threshold; what the views see through is carved away.
+        Per view and pixel with the maps (D, A): the depth is D / A where A >= min_opacity and +inf elsewhere, the opacity image is A; a
+        pixel below min_opacity is background and, with carve, marks the lattice points along its ray as empty.  trunc: the truncation
+        distance in world units; None = 4 x the largest lattice step (a choice, not a measurement).
+        depth: "coarse" uses (D_c, A_c), "fine" (D_f, A_f), "auto" the fine pair under ``model.corrected`` and the coarse pair otherwise.
+        In the default mode the fine pass sorts its five channels independently (quirk Q1), so D_f pairs weights
+        with depths they do not belong to -- it is what compositing t like a colour gives --, while D_c is the physical expected depth of
+        the coarse samples; with ``corrected`` the merged samples are sorted once and D_f is physical and sharper.  It is the EXPECTED
+        depth, not the median: a ray that grazes a silhouette averages foreground and background.
+        The views are rendered one at a time (each a render() call of H * W rays: ``bf16_mlp`` / ``split_mlp`` apply as in render) and
+        integrated views_per_call at a time (default: the kernel's views per launch), so no more than views_per_call depth and opacity
+        images exist at once; the result does not depend on views_per_call."""
+        import numpy as np
+
+        from . import mesh
+
+        if depth not in ("auto", "coarse", "fine"):
+            raise ValueError(f"depth={depth!r}: 'auto', 'coarse' or 'fine'")
+        col0 = 2 if depth == "fine" or (depth == "auto" and getattr(self, "corrected", False)) else 0
+        per_call = _abi.TSDF_VIEWS_PER_LAUNCH if views_per_call is None else int(views_per_call)
+        if per_call < 1:
+            raise ValueError(f"views_per_call={views_per_call!r}: None or an int >= 1")
+        ps = self._device_params()
+        dev = ps[0].device
+        poses_bound, K_inv, H, W = views
+        H, W = int(H), int(W)
+        pb = torch.as_tensor(poses_bound).reshape(-1, 17)
+        shape = grid_shape(res)
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        step = grid_step(lo32, hi32, shape)
+        T, Wt = mesh.tsdf_volume(shape, dev)
+        n = int(pb.shape[0])
+        if n == 0:
+            return T, Wt
+        row = torch.arange(H, device=dev).repeat_interleave(W)
+        col = torch.arange(W, device=dev).repeat(H)
+        inf = torch.full((), float("inf"), device=dev)
+        D = torch.empty(min(per_call, n), H, W, device=dev)
+        A = torch.empty_like(D)
+        for v0 in range(0, n, per_call):
+            k = min(per_call, n - v0)
+            for c in range(k):
+                M = self.render(row, col, pb[v0 + c].to(dev).expand(H * W, 17), K_inv, maps=True)[2]
+                d, a = M[:, col0], M[:, col0 + 1]
+                D[c] = torch.where(a >= min_opacity, d / a, inf).view(H, W)
+                A[c] = a.view(H, W)
+            mesh.tsdf_integrate(T, Wt, lo32, step, D[:k], pb[v0:v0 + k], K_inv, opacity=A[:k], trunc=trunc, min_opacity=min_opacity, carve=carve)
+        return T, Wt
+
+    @torch.no_grad()
+    def extract_mesh_tsdf(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, unseen="solid", color=True,
+                          normals="grid", min_faces=None, keep_largest=None, simplify=None, smooth=None, visible=None, views_per_call=None):
+        """A triangle mesh of the surface the rendered views agree on: fuse_depth(views, lo, hi, res, ...) -> mesh.tsdf_grid(T, Wt, unseen)
+        -> mesh.marching_cubes at level 0 over the same lattice -> the stages of extract_mesh behind marching cubes, with the same keywords
+        and order (min_faces / keep_largest, visible, smooth, simplify, then normals and colours at the final vertices).  No density
+        threshold enters.  normals="grid": the TSDF lattice's normals (its central differences, pointing outward); "field" and the
+        colours query the field at the final vertices as in extract_mesh.  unseen="solid" (default): lattice points no view observed count
+        as inside, so the mesh closes behind what the cameras saw; with unseen="empty", or with carve=False, a second sheet appears one
+        truncation distance behind the surface, where the observed band ends (there is no masked marching cubes).  Colours are queried
+        from the field, not fused from the views.  The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt)."""
+        import numpy as np
+
+        from . import mesh
+
+        _check_mesh_stages(normals, simplify, smooth)
+        shape = grid_shape(res)
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        T, Wt = self.fuse_depth(views, lo32, hi32, shape, trunc=trunc, depth=depth, min_opacity=min_opacity, carve=carve,
+                                views_per_call=views_per_call)
+        self.last_tsdf = (T, Wt)
+        verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, unseen), 0.0, lo32, grid_step(lo32, hi32, shape))
+        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible)
 
     @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False):
@@ -732,6 +816,16 @@ class NeRFModel(nn.Module):
         if getattr(self, "bf16_mlp", False):
             self.read_status()  # a frame is not handed out on a poisoned weight image (raises on STATUS_PREP_TIMEOUT; one sync per frame)
         return (C_c, C_f, M) if maps else (C_c, C_f)
+
+
+def _check_mesh_stages(normals, simplify, smooth):
+    """The keywords extract_mesh and extract_mesh_tsdf share, checked before any device work."""
+    if normals not in ("grid", "field"):
+        raise ValueError(f"normals={normals!r}: 'grid' or 'field'")
+    if simplify is not None and (int(simplify) != simplify or int(simplify) < 2):
+        raise ValueError(f"simplify={simplify!r}: None or an int >= 2 (cells of that many lattice steps)")
+    if smooth is not None and (int(smooth) != smooth or int(smooth) < 1):
+        raise ValueError(f"smooth={smooth!r}: None or an int >= 1 (Taubin iterations)")
 
 
 def grid_shape(res) -> tuple:

@@ -560,6 +560,36 @@ def mesh_select_faces(verts, faces, normals, rgb, keep, ws=None):
     return ov, of, on, oc
 
 
+def tsdf_integrate(tsdf, weight, lo, step, depth, opacity, cam_o, Q, trunc, min_opacity=0.5, carve=True):
+    """Integrates the depth images depth[n, H, W] (fp32, device; opacity the same or None) of the cameras cam_o (n x 3 host floats) / Q
+    (n x 9 host doubles, row-major) into the volumes tsdf / weight [nx, ny, nz] IN PLACE (nerf_hip_tsdf_integrate; rule T of
+    include/nerf_hip.h): contiguous fp32 device tensors on the lattice lo + (i, j, k) * step (three host floats each).  Enqueue only."""
+    if tsdf.dim() != 3 or tsdf.shape != weight.shape:
+        raise ValueError(f"tsdf {tuple(tsdf.shape)} weight {tuple(weight.shape)}: two [nx, ny, nz] volumes")
+    for name, t in (("tsdf", tsdf), ("weight", weight)):
+        if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: a contiguous fp32 device tensor (it is updated in place)")
+    if depth.dim() != 3:
+        raise ValueError(f"depth {tuple(depth.shape)}: [n, H, W]")
+    dev = tsdf.device
+    depth = depth.to(dev, torch.float32).contiguous()
+    n, H, W = (int(x) for x in depth.shape)
+    if opacity is not None:
+        opacity = opacity.to(dev, torch.float32).contiguous()
+        if opacity.shape != depth.shape:
+            raise ValueError(f"opacity {tuple(opacity.shape)}: the depth's shape {tuple(depth.shape)}")
+    cam = [float(x) for row in cam_o for x in row]
+    q = [float(x) for row in Q for x in row]
+    if len(cam) != 3 * n or len(q) != 9 * n:
+        raise ValueError(f"cam_o / Q: three and nine entries for each of the {n} views")
+    nx, ny, nz = (int(x) for x in tsdf.shape)
+    _abi.check(_abi.lib().nerf_hip_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step),
+                                                  depth.data_ptr(), opacity.data_ptr() if opacity is not None else None, n, H, W,
+                                                  _abi.f32_array(cam), (C.c_double * len(q))(*q), float(trunc), float(min_opacity),
+                                                  _abi.TSDF_CARVE if carve else 0, _stream(tsdf)))
+    return tsdf, weight
+
+
 def distance_stats(dist2, unit, thresholds=()):
     """The statistics of squared distances dist2[N] (fp64, device) in units of `unit` (nerf_hip_distance_stats; the definition is in
     include/nerf_hip.h) -> int64[4 + K] ON THE DEVICE: the finite count, the fixed-point sums of d / unit and d2 / unit^2, the clamped,

@@ -550,7 +550,8 @@ class NeRFRunner:
         return sigma
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
-                     keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None):
+                     keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None,
+                     tsdf_from=None, tsdf_trunc=None, tsdf_every=1):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -572,11 +573,17 @@ class NeRFRunner:
         Without compare nothing new is computed, printed or written.  visible_from: None, or "train" / "val" / "test" -- the faces that
         no camera of that split sees go before smoothing, simplification, normals and colours (NeRFModel.extract_mesh(visible=): one
         shadow ray per face and camera on the device); one ``[MESH]`` line says how many faces were seen.  Same file name either way;
-        without it nothing new is computed, printed or written."""
+        without it nothing new is computed, printed or written.  tsdf_from: None, or "train" / "val" / "test" -- the mesh is not the
+        isosurface of sigma but the zero set of a TSDF volume fused from the model's rendered depth of every tsdf_every-th camera of
+        that split over the same lattice (NeRFModel.extract_mesh_tsdf: truncation distance tsdf_trunc, None = 4 lattice steps; unseen
+        space solid, background rays carve).  ``level`` and ``band`` are then ignored -- the ``[MESH] ... [TSDF]`` line says so, with
+        the views, the lattice points observed and the truncation distance -- and the file name gets ``_tsdf`` before ``.ply``.  Without
+        it nothing new is computed, printed or written."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
-        from .nerf import grid_shape
+        from .mesh import tsdf_trunc as default_trunc
+        from .nerf import grid_shape, grid_step
 
         if self.rank != 0:
             return None
@@ -589,8 +596,23 @@ class NeRFRunner:
                 raise ValueError(f"visible_from={visible_from!r}: None, 'train', 'val' or 'test'")
             rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[visible_from]
             kw["visible"] = (rays.poses, self.K_inv, rays.height, rays.width)
-        m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
-                                    keep_largest=keep_largest, simplify=simplify, smooth=smooth, **kw)
+        if tsdf_from is not None:
+            if tsdf_from not in ("train", "val", "test"):
+                raise ValueError(f"tsdf_from={tsdf_from!r}: None, 'train', 'val' or 'test'")
+            if int(tsdf_every) != tsdf_every or int(tsdf_every) < 1:
+                raise ValueError(f"tsdf_every={tsdf_every!r}: an int >= 1")
+            rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[tsdf_from]
+            poses = rays.poses[::int(tsdf_every)]
+            m = self.model.extract_mesh_tsdf((poses, self.K_inv, rays.height, rays.width), lo32, hi32, shape, trunc=tsdf_trunc, color=color,
+                                             normals=normals, min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth,
+                                             **kw)
+            Wt = self.model.last_tsdf[1]
+            trunc = default_trunc(grid_step(lo32, hi32, shape)) if tsdf_trunc is None else float(tsdf_trunc)
+            print(f"[MESH] {self.last_iter} [TSDF] {len(poses)} {tsdf_from} views fused, {int((Wt > 0).sum())} / {Wt.numel()} lattice points "
+                  f"observed, trunc {trunc:.6g} (level {level!r} ignored: the surface is the fused depth's)")
+        else:
+            m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
+                                        keep_largest=keep_largest, simplify=simplify, smooth=smooth, **kw)
         if visible_from is not None:
             seen, per_cam = self.model.last_visibility
             print(f"[MESH] {self.last_iter} [VISIBLE] {int(seen.sum())} / {int(seen.numel())} faces seen from the {len(per_cam)} {visible_from} "
@@ -598,7 +620,7 @@ class NeRFRunner:
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
-            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + ".ply"
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + ("" if tsdf_from is None else "_tsdf") + ".ply"
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
             write_ply(path, out.verts, out.faces, out.normals, out.rgb)
