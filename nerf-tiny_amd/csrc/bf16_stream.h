@@ -1,6 +1,8 @@
-// bf16_stream.h -- the machinery shared by the bf16 field kernels (forward and backward chain): a workgroup of 8 waves
-// consumes one stream of 1-KiB MFMA A fragments through an LDS ring filled by direct-to-LDS loads, each wave holding 32
-// samples x all features in registers (see field_fwd_bf16.hip for the design notes).  MI355X / gfx950 only.
+// bf16_stream.h -- the machinery shared by the bf16 and split-fp32 field kernels (forward and backward chain): a workgroup of 8 (or 4)
+// waves consumes one stream of 1-KiB MFMA A fragments through an LDS ring filled by direct-to-LDS loads, each wave holding 32
+// samples x all features in registers (see field_fwd_bf16.hip for the design notes).  Also what those kernels share around the
+// stream: the context set-up and the positional encoder into B-operand registers.
+// (The two-part segment of the split-fp32 kernels: bf16_split.h.)  MI355X / gfx950 only.
 #pragma once
 #include "bf16_common.h"
 #include "field_common.h"
@@ -30,6 +32,8 @@ inline bool bf16_four_waves_disabled() {
   static const bool off = [] { const char* e = getenv("NERF_BF16_4WAVE"); return e && atoi(e) == 0; }();
   return off;
 }
+// a SMALL pass of `wgs` 256-sample workgroups gets 4-wave workgroups (2 wgs of them), so that every CU has one
+inline bool bf16_small_pass(int wgs) { return 2 * wgs <= BF_SMALL_MAX_WGS && !bf16_four_waves_disabled(); }
 static_assert(BF_D <= BF_CHUNK - BF_SYNC_POS, "a prefetched fragment must not lie in an unpublished chunk");
 
 __device__ __forceinline__ unsigned pack2(float a, float b) {  // two fp32 -> two bf16 (RNE), a in the low half
@@ -84,12 +88,25 @@ __device__ __forceinline__ void static_for(F&& f) {
 template <class S, class = void> struct BfPW { static constexpr int v = 2; };
 template <class S> struct BfPW<S, std::void_t<decltype(S::PW)>> { static constexpr int v = S::PW; };
 
+// A stream description for a 4-wave workgroup: the 16 pieces of a chunk over 4 waves
+template <class Base> struct FourWaves : Base { static constexpr int PW = 4; };
+
 struct BfCtx {
   const unsigned char* wimg;  // global: bias block + fragment stream
   unsigned char* lds;         // bias block + ring
   unsigned lds_base;          // the same as an LDS byte address
   int lane, wv;
 };
+// what every stream kernel starts with: wimg = the packed weight image, lds = the workgroup's dynamic LDS
+__device__ __forceinline__ BfCtx bf_ctx(const unsigned char* wimg, unsigned char* lds) {
+  BfCtx c;
+  c.wimg = wimg;
+  c.lds = lds;
+  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
+  c.lane = threadIdx.x & 63;
+  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return c;
+}
 
 // One direct-to-LDS load: 64 lanes x 16 bytes from per-lane global addresses to lds_dst + lane*16 (lds_dst wave-uniform).
 // Inline asm on purpose: hipcc treats a builtin LDS-DMA as a pending write to the whole LDS array and drains the load
@@ -122,9 +139,10 @@ __device__ __forceinline__ void bf_dma_chunk(const BfCtx& c, int chunk) {
   }
 }
 
-// A stream description S provides: NFRAG, NCHUNK, NS, RING_OFF, PROLOGUE_STORES and stores_before(idx) = number of vector stores the
-// wave has issued (in program order) before the sync point at stream step idx, not counting the prologue's.  Stores share
-// the vmcnt queue with the weight loads and retire in order, so the counted wait must allow for the younger ones.
+// A stream description S provides: NFRAG, NCHUNK, NS, RING_OFF, PROLOGUE_STORES, the segment table SEGS / NSEG (bf16_common.h; the
+// 16x16x32 stream has none) and stores_before(idx) = number of vector stores the wave has issued (in program order) before the sync
+// point at fragment idx, not counting the prologue's.  Stores share the vmcnt queue with the weight loads and retire in order, so the
+// counted wait must allow for the younger ones.
 template <class S>
 __device__ __forceinline__ constexpr int bf_wait_count(int c) {
   const int last = (c + S::NS - 2 < S::NCHUNK - 1) ? c + S::NS - 2 : S::NCHUNK - 1;  // newest chunk requested so far
@@ -198,16 +216,18 @@ __device__ __forceinline__ f32x16 bf_mfma(const u32x4& a, const u32x4& b, const 
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-// One segment of the stream: NFT output tiles x (KSA + KSB) k-steps starting at fragment S0; inputs inA (k-steps
-// 0..KSA-1) then inB.  fr = ring of BF_D prefetched fragments (fr[idx % BF_D] holds fragment idx on entry to step idx).
+// Segment ROW of stream S (S::SEGS[ROW]: NFT output tiles x (KSA + KSB) k-steps starting at fragment S0); inputs inA (k-steps
+// 0..KSA-1) then inB.  fr = ring of S::D prefetched fragments (fr[idx % S::D] holds fragment idx on entry to step idx).
 // Two accumulators alternate so that nothing waits for an MFMA result: tile f runs in acc[(P0 + f) & 1]; the finished
 // accumulator of tile f-1 is consumed by epi(f-1, .) BF_EPI_POS k-steps into tile f (the last tile of the previous
 // segment by prev_epi), and right after that it is re-started at the bias of tile f+1 (or of the next segment's tile 0,
 // bias tile NEXT_BT; BT0 < 0: no biases, accumulators start at zero), an LDS read with >= 1 k-steps of MFMAs to land in.
-template <class S, int S0, int NFT, int KSA, int KSB, int BT0, int P0, int NEXT_BT, class Epi, class PrevEpi>
+template <class S, int ROW, class Epi, class PrevEpi>
 __device__ __forceinline__ void bf_segment(const BfCtx& c, u32x4 (&fr)[S::D], f32x16 (&acc)[2], const u32x4* inA, const u32x4* inB,
                                            Epi&& epi, PrevEpi&& prev_epi) {
-  constexpr int KS = KSA + KSB;
+  constexpr BfSeg G = S::SEGS[ROW];
+  constexpr int S0 = G.s0, NFT = G.nft, KSA = G.ksa, KSB = G.ksb, BT0 = G.bt0, KS = KSA + KSB;
+  constexpr int P0 = bf_seg_p0(S::SEGS, ROW), NEXT_BT = bf_seg_next_bt(S::SEGS, S::NSEG, ROW);
   static_assert(KS > BF_EPI_POS + 1, "segment too short for the deferred epilogue");
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   static_for<NFT * KS>([&](auto I) {
@@ -235,12 +255,49 @@ __device__ __forceinline__ void bf_segment(const BfCtx& c, u32x4 (&fr)[S::D], f3
   });
 }
 
-// ---- a stream's store schedule: tiles in stream order, each with the number of stores its epilogue issues -------------
-// The epilogue of the tile that ENDS at fragment index `end` (exclusive) runs in step end + BF_EPI_POS, after that step's
-// sync point; so it precedes the sync point of step idx iff end + BF_EPI_POS < idx.
+// ---- a stream's store schedule, from its segment table ---------------------------------------------------------------------------
+// Counted: the burst behind a segment's last tile -- `mul` stores per piece of its output (1; 2 = hi and mid) + `extra` (the mask
+// piece) -- which every lane issues unconditionally.  That tile's epilogue runs inside tile 0 of the NEXT segment, at its k-step
+// BF_EPI_POS, or, in a two-part stream (PARTS = 2 fragments per step: bf16_split.h spreads the epilogue over k-steps), behind part 7
+// at k-step BF_EPI_POS + 7 where that segment has as many k-steps; in both after that step's sync point.  A burst past the end of the
+// stream follows the last sync point and is not counted.  Uncounted (conditional) stores only make a wait more conservative.
 template <int NFRAG_>
 struct BfStoreTable {
-  int cum[NFRAG_ + 1];  // cum[i] = stores of all tiles with end + BF_EPI_POS < i
+  int cum[NFRAG_ + 1];  // cum[i] = counted stores issued before the sync point at fragment i
 };
+constexpr int bf_burst_kstep(int parts, int next_ks) { return BF_EPI_POS + (parts == 2 && next_ks >= BF_EPI_POS + 8 ? 7 : 0); }
+template <int NFRAG_, int PARTS>
+constexpr BfStoreTable<NFRAG_> bf_store_table(const BfSeg* segs, int nseg, int mul, int extra) {
+  constexpr int NSTEP = NFRAG_ / PARTS;
+  BfStoreTable<NFRAG_> t{};
+  int ev[NSTEP + 1] = {};  // counted stores issued in step i
+  for (int r = 0; r < nseg; ++r) {
+    if (segs[r].pieces == 0) continue;
+    const int e = bf_seg_end(segs[r]) + bf_burst_kstep(PARTS, r + 1 < nseg ? bf_seg_ks(segs[r + 1]) : 0);
+    if (e < NSTEP) ev[e] += mul * segs[r].pieces + extra;
+  }
+  int run = 0, step = 0;
+  for (int i = 0; i <= NFRAG_; ++i) {  // the steps before fragment i are 0 .. i / PARTS - 1 (sync points sit on a step's first fragment)
+    while (step < i / PARTS) run += ev[step++];
+    t.cum[i] = run;
+  }
+  return t;
+}
+
+// ---- positional encoding, for the B-operand registers of a stream's first segments -------------------------------------------------------
+// (sin, cos) of pair pi = L * coordinate + frequency of the encoding of the 3-vector v with L frequencies (freq_bits: their fp32 bit
+// patterns), fp32 exactly as in the fp32 path; zeros past 3 L (the padding of the last k-step)
+template <int L>
+__device__ __forceinline__ void encode_pair(const float (&v)[3], const uint32_t (&freq_bits)[L], int pi, float& sv, float& cv) {
+  sv = 0.f;
+  cv = 0.f;
+  if (pi < 3 * L) {
+    const int cc = pi / L, l = pi - L * cc;
+    const float x = (cc == 0) ? v[0] : ((cc == 1) ? v[1] : v[2]);
+    sincos_phase(x * __uint_as_float(freq_bits[l]), sv, cv);
+  }
+}
+__device__ __forceinline__ void encode_point_pair(const float (&p)[3], int pi, float& sv, float& cv) { encode_pair(p, kFreqPointBits, pi, sv, cv); }
+__device__ __forceinline__ void encode_dir_pair(const float (&d)[3], int pi, float& sv, float& cv) { encode_pair(d, kFreqDirBits, pi, sv, cv); }
 
 }  // namespace nerf

@@ -1,27 +1,29 @@
 // bf16_weights.h -- element (fragment, row, input) of the bf16 weight streams of bf16_common.h (32x32x16 forward image and its bias block,
-// 16x16x32 inference image, transposed backward image), shared by their packers (field_fwd_bf16.hip, field_fwd_bf16x.hip, field_bwd_bf16.hip,
-// field_fwd_split.hip) and by the one-launch preparation kernel (prep_bf16.hip).
+// 16x16x32 inference image, transposed backward image) and one lane's 16 bytes of a fragment of any of them, shared by their packers
+// (field_fwd_bf16.hip, field_fwd_bf16x.hip, field_bwd_bf16.hip, field_fwd_split.hip, field_bwd_split.hip) and by the one-launch
+// preparation kernel (prep_bf16.hip).  The tiles-by-k-steps arithmetic of the 32x32x16 images comes from the segment tables.
 #pragma once
-#include "bf16_common.h"
+#include "bf16_stream.h"
 
 namespace nerf {
 
-__device__ __forceinline__ float bf_weight(const Weights24& w, const float* __restrict__ fold, int frag, int i, int kk /* 0..15 inside the k-step */, int h) {
-  (void)h;
+__device__ __forceinline__ float bf_weight(const Weights24& w, const float* __restrict__ fold, int frag, int i, int kk /* 0..15 inside the k-step */) {
+  constexpr int KS0 = bf_seg_ks(kFwdSegs[FSEG_L0]), KSH = bf_seg_ks(kFwdSegs[FSEG_L1]), LAYER = kFwdSegs[FSEG_L1].nft * KSH;  // 4, 16, 128
+  constexpr int KS4 = bf_seg_ks(kFwdSegs[FSEG_L4]), KSD = bf_seg_ks(kFwdSegs[FSEG_DIR]), KSGD = kFwdSegs[FSEG_DIR].ksa;          // 20, 18, 2
   if (frag < BFS_L1) {  // L0
-    const int f = frag / 4, ks = frag % 4, k = 16 * ks + kk;
+    const int f = frag / KS0, ks = frag % KS0, k = 16 * ks + kk;
     return k < POINT_DIM ? w.p[0][(size_t)(32 * f + i) * POINT_DIM + k] : 0.f;
   }
   if (frag < BFS_L4) {  // L1..L3
-    const int r = frag - BFS_L1, l = 1 + r / 128, q = r % 128, f = q / 16, ks = q % 16;
+    const int r = frag - BFS_L1, l = 1 + r / LAYER, q = r % LAYER, f = q / KSH, ks = q % KSH;
     return w.p[2 * l][(size_t)(32 * f + i) * WIDTH + 16 * ks + kk];
   }
   if (frag < BFS_L5) {  // L4: [256][316] = cat(hidden, gamma_p)
-    const int q = frag - BFS_L4, f = q / 20, ks = q % 20, k = 16 * ks + kk;
+    const int q = frag - BFS_L4, f = q / KS4, ks = q % KS4, k = 16 * ks + kk;
     return (k < WIDTH + POINT_DIM) ? w.p[8][(size_t)(32 * f + i) * (WIDTH + POINT_DIM) + k] : 0.f;
   }
   if (frag < BFS_SIG) {  // L5..L7
-    const int r = frag - BFS_L5, l = 5 + r / 128, q = r % 128, f = q / 16, ks = q % 16;
+    const int r = frag - BFS_L5, l = 5 + r / LAYER, q = r % LAYER, f = q / KSH, ks = q % KSH;
     return w.p[2 * l][(size_t)(32 * f + i) * WIDTH + 16 * ks + kk];
   }
   if (frag < BFS_DIR) {  // sigma row on h7
@@ -29,9 +31,9 @@ __device__ __forceinline__ float bf_weight(const Weights24& w, const float* __re
     return i == 0 ? w.p[W_SIGMA][k] : 0.f;
   }
   if (frag < BFS_COL) {  // dir_info: gamma_d columns of W_dir (24 -> 32), then W_fold = W_dir[:, 24:] W_pi on h7
-    const int q = frag - BFS_DIR, f = q / 18, ks = q % 18, k = 16 * ks + kk;
-    if (ks < 2) return k < DIR_DIM ? w.p[W_DIR][(size_t)(32 * f + i) * (WIDTH + DIR_DIM) + k] : 0.f;
-    return fold[HALF + (size_t)(32 * f + i) * WIDTH + (k - 32)];
+    const int q = frag - BFS_DIR, f = q / KSD, ks = q % KSD, k = 16 * ks + kk;
+    if (ks < KSGD) return k < DIR_DIM ? w.p[W_DIR][(size_t)(32 * f + i) * (WIDTH + DIR_DIM) + k] : 0.f;
+    return fold[HALF + (size_t)(32 * f + i) * WIDTH + (k - 16 * KSGD)];
   }
   const int ks = frag - BFS_COL, k = 16 * ks + kk;  // colour head
   return i < 3 ? w.p[W_COLOR][(size_t)i * HALF + k] : 0.f;
@@ -94,28 +96,50 @@ __device__ __forceinline__ float bx_weight(const Weights24& w, const float* __re
 // ---- the transposed image of the backward chain (field_bwd_bf16.hip; segments: bf16_common.h BBS_*) ----
 // fragment (f, ks), lane (i, h), slot s  =  W[out = 16ks + 4h + (s&3) + 8(s>>2)][in = 32f + i]
 __device__ __forceinline__ float bb_weight(const Weights24& w, const float* __restrict__ fold, int frag, int i, int kk) {
+  constexpr int KSC = bf_seg_ks(kBwdSegs[BSEG_COLT]), KSF = bf_seg_ks(kBwdSegs[BSEG_FOLDT]), KSFA = kBwdSegs[BSEG_FOLDT].ksa;     // 4, 9, 8
+  constexpr int KSH = bf_seg_ks(kBwdSegs[BSEG_L7T]), LAYER = kBwdSegs[BSEG_L7T].nft * KSH;                                         // 16, 128
+  constexpr int KSG = bf_seg_ks(kBwdSegs[BSEG_G0T]), KSGA = kBwdSegs[BSEG_G0T].ksa;                                                // 32, 16
   if (frag < BBS_FOLDT) {  // COLT: d c = W_color^T dz
-    const int f = frag / 4, ks = frag % 4, k = 16 * ks + kk;
+    const int f = frag / KSC, ks = frag % KSC, k = 16 * ks + kk;
     return k < 3 ? w.p[W_COLOR][(size_t)k * HALF + 32 * f + i] : 0.f;
   }
   if (frag < BBS_L7T) {  // FOLDT: 8 k-steps of W_fold^T (W_fold = W_dir[:, 24:] W_pi, [128][256]), then the sigma step (input slot 3)
-    const int q = frag - BBS_FOLDT, f = q / 9, ks = q % 9, k = 16 * ks + kk;
-    if (ks < 8) return fold[HALF + (size_t)k * WIDTH + 32 * f + i];
+    const int q = frag - BBS_FOLDT, f = q / KSF, ks = q % KSF, k = 16 * ks + kk;
+    if (ks < KSFA) return fold[HALF + (size_t)k * WIDTH + 32 * f + i];
     return kk == 3 ? w.p[W_SIGMA][32 * f + i] : 0.f;
   }
   if (frag < BBS_G0T) {  // L7T .. L1T (layer 4: hidden columns of the [256][316] matrix)
-    const int r = frag - BBS_L7T, l = 7 - r / 128, q = r % 128, f = q / 16, ks = q % 16;
+    const int r = frag - BBS_L7T, l = 7 - r / LAYER, q = r % LAYER, f = q / KSH, ks = q % KSH;
     const int ld = (l == 4) ? WIDTH + POINT_DIM : WIDTH;
     return w.p[2 * l][(size_t)(16 * ks + kk) * ld + 32 * f + i];
   }
   if (frag < BBF_NFRAG) {  // d gamma_p, fine pass: tile f = 16 k-steps of W_0^T (input dpre0), then 16 k-steps of W_4[:, 256:]^T (input dpre4)
-    const int q = frag - BBS_G0T, f = q / 32, ks = q % 32, col = 32 * f + i;
+    const int q = frag - BBS_G0T, f = q / KSG, ks = q % KSG, col = 32 * f + i;
     if (col >= POINT_DIM) return 0.f;
-    if (ks < 16) return w.p[0][(size_t)(16 * ks + kk) * POINT_DIM + col];
-    return w.p[8][(size_t)(16 * (ks - 16) + kk) * (WIDTH + POINT_DIM) + WIDTH + col];
+    if (ks < KSGA) return w.p[0][(size_t)(16 * ks + kk) * POINT_DIM + col];
+    return w.p[8][(size_t)(16 * (ks - KSGA) + kk) * (WIDTH + POINT_DIM) + WIDTH + col];
   }
   return 0.f;  // padding up to whole chunks
 }
 
+// ---- one lane's 16 bytes of fragment `frag` of a weight image -------------------------------------------------------------------------
+// W = the image's element function (bf_weight, bb_weight: ROWS = 32; bx_weight: ROWS = 16).  Lane (i, s) = (lane % ROWS, lane / ROWS) holds
+// row i; its slot pair q = inputs 4 s + 2 (q & 1) + (256 / ROWS) (q >> 1) + {0, 1} of the k-step, handed to sink(q, w0, w1).
+typedef float (*WeightFn)(const Weights24&, const float* __restrict__, int, int, int);
+template <int ROWS, WeightFn W, class Sink>
+__device__ __forceinline__ void frag_lane(const Weights24& w, const float* __restrict__ fold, int frag, int lane, Sink&& sink) {
+  const int i = lane & (ROWS - 1), s = lane / ROWS;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int kk = 4 * s + 2 * (q & 1) + (256 / ROWS) * (q >> 1);
+    sink(q, W(w, fold, frag, i, kk), W(w, fold, frag, i, kk + 1));
+  }
+}
+template <int ROWS, WeightFn W>
+__device__ __forceinline__ u32x4 frag_lane_bf16(const Weights24& w, const float* __restrict__ fold, int frag, int lane) {
+  u32x4 v;
+  frag_lane<ROWS, W>(w, fold, frag, lane, [&](int q, float x0, float x1) { v[q] = pack2(x0, x1); });
+  return v;
+}
 
 }  // namespace nerf

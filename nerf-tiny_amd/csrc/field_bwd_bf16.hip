@@ -23,52 +23,26 @@ constexpr int BB_NS = 5;  // LDS ring slots of the chain's stream
 constexpr int BB_MASK_BYTES = 8 * BM_LAYERS * 1024;  // per workgroup: wave w, layer l at (w * 9 + l) * 1024
 constexpr int BB_LDS_BYTES = BB_MASK_BYTES + BB_NS * BF_CHUNK * BF_FRAG_BYTES;
 
-struct BwdTiles { int s0, nft, ks, last_stores; };  // a layer's gradient pieces go out in one burst with its last tile
-
+// counted stores (bf16_stream.h bf_store_table): a layer's gradient pieces go out in one burst with its last tile; the d gamma_p tiles store nothing
 template <bool FINE>
 struct BwdStream {
   static constexpr int NFRAG = FINE ? BBF_NFRAG : BBC_NFRAG;
   static constexpr int NCHUNK = FINE ? BBF_NCHUNK : BBC_NCHUNK;
   static constexpr int NS = BB_NS, RING_OFF = BB_MASK_BYTES, D = 4;
+  static constexpr const BfSeg* SEGS = kBwdSegs;
+  static constexpr int NSEG = FINE ? BSEG_N : BSEG_G0T;
   static constexpr bool HAS_BIAS = false;
   static constexpr int PROLOGUE_STORES = 2;  // the dz / dspre fragment and its zero partner
-  static constexpr int L3T = BBS_L3T;
-  static constexpr BfStoreTable<NFRAG> make() {
-    const BwdTiles tiles[] = {{BBS_COLT, 4, 4, 8},        {BBS_FOLDT, 8, 9, 16},      {BBS_L7T, 8, 16, 16},
-                              {BBS_L7T + 128, 8, 16, 16}, {BBS_L7T + 256, 8, 16, 16}, {BBS_L4T, 8, 16, 16},     {L3T, 8, 16, 16},
-                              {L3T + 128, 8, 16, 16},     {L3T + 256, 8, 16, 16}};  // the d gamma_p tiles store nothing
-    BfStoreTable<NFRAG> t{};
-    int ev[NFRAG + 64] = {};
-    for (const BwdTiles& g : tiles)
-      {
-        int e = g.s0 + g.nft * g.ks + BF_EPI_POS;  // epilogue of the segment's last tile
-        // (an epilogue deferred past the end of the coarse stream runs after the last sync point)
-        ev[e < NFRAG + 64 ? e : NFRAG + 63] += g.last_stores;
-      }
-    int run = 0;
-    for (int i = 0; i <= NFRAG; ++i) {
-      t.cum[i] = run;
-      run += ev[i];
-    }
-    return t;
-  }
-  static constexpr BfStoreTable<NFRAG> tab = make();
+  static constexpr BfStoreTable<NFRAG> tab = bf_store_table<NFRAG, 1>(SEGS, NSEG, 1, 0);
   __device__ static constexpr int stores_before(int idx) { return tab.cum[idx]; }
 };
-
-template <class Base> struct FourWavesB : Base { static constexpr int PW = 4; };
 
 // WAVES = 4 (128 samples per workgroup, one wave per SIMD): small passes, so that every CU gets a workgroup (field_fwd_bf16.hip)
 template <bool FINE, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwdArgs a, const BwdFuse fz) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  using S = std::conditional_t<WAVES == 4, FourWavesB<BwdStream<FINE>>, BwdStream<FINE>>;
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  using S = std::conditional_t<WAVES == 4, FourWaves<BwdStream<FINE>>, BwdStream<FINE>>;
+  const BfCtx c = bf_ctx(a.wbf, lds);
   const int lane = c.lane, j = lane & 31, h = lane >> 5;
   const int m = blockIdx.x * (32 * WAVES) + c.wv * 32 + j;
   const bool valid = m < a.M;
@@ -170,17 +144,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwd
   auto nothing = [](const f32x16&) {};
 
   // colour head: dc = W_color^T dz, through c's ReLU -> dpre_dir
-  bf_segment<S, BBS_COLT, 4, 4, 0, -1, 0, -1>(c, fr, acc, zin, nullptr, grad_to(X, BG_D, 8, 4), nothing);
+  bf_segment<S, BSEG_COLT>(c, fr, acc, zin, nullptr, grad_to(X, BG_D, 8, 4), nothing);
   // dir_info and point_info as ONE transposed layer (point_info has no activation: folded, bf16_common.h) + the sigma head:
   // dh7 = W_fold^T dpre_dir + w_sigma dspre, through h7's ReLU
-  bf_segment<S, BBS_FOLDT, 8, 8, 1, -1, 0, -1>(c, fr, acc, X, zin, grad_to(Y, BG_L0 + 7, 7), last_of(grad_to(X, BG_D, 8, 4), 3));
-  bf_segment<S, BBS_L7T, 8, 16, 0, -1, 0, -1>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 6, 6), last_of(grad_to(Y, BG_L0 + 7, 7), 7));
-  bf_segment<S, BBS_L7T + 128, 8, 16, 0, -1, 0, -1>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 5, 5), last_of(grad_to(X, BG_L0 + 6, 6), 7));
-  bf_segment<S, BBS_L7T + 256, 8, 16, 0, -1, 0, -1>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 4, 4), last_of(grad_to(Y, BG_L0 + 5, 5), 7));
-  bf_segment<S, BBS_L4T, 8, 16, 0, -1, 0, -1>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 3, 3), last_of(grad_to(X, BG_L0 + 4, 4), 7));
-  bf_segment<S, BBS_L3T, 8, 16, 0, -1, 0, -1>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 2, 2), last_of(grad_to(Y, BG_L0 + 3, 3), 7));
-  bf_segment<S, BBS_L3T + 128, 8, 16, 0, -1, 0, -1>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 1, 1), last_of(grad_to(X, BG_L0 + 2, 2), 7));
-  bf_segment<S, BBS_L3T + 256, 8, 16, 0, -1, 0, -1>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 0, 0), last_of(grad_to(Y, BG_L0 + 1, 1), 7));
+  bf_segment<S, BSEG_FOLDT>(c, fr, acc, X, zin, grad_to(Y, BG_L0 + 7, 7), last_of(grad_to(X, BG_D, 8, 4), 3));
+  bf_segment<S, BSEG_L7T>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 6, 6), last_of(grad_to(Y, BG_L0 + 7, 7), 7));
+  bf_segment<S, BSEG_L6T>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 5, 5), last_of(grad_to(X, BG_L0 + 6, 6), 7));
+  bf_segment<S, BSEG_L5T>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 4, 4), last_of(grad_to(Y, BG_L0 + 5, 5), 7));
+  bf_segment<S, BSEG_L4T>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 3, 3), last_of(grad_to(X, BG_L0 + 4, 4), 7));
+  bf_segment<S, BSEG_L3T>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 2, 2), last_of(grad_to(Y, BG_L0 + 3, 3), 7));
+  bf_segment<S, BSEG_L2T>(c, fr, acc, X, nullptr, grad_to(Y, BG_L0 + 1, 1), last_of(grad_to(X, BG_L0 + 2, 2), 7));
+  bf_segment<S, BSEG_L1T>(c, fr, acc, Y, nullptr, grad_to(X, BG_L0 + 0, 0), last_of(grad_to(Y, BG_L0 + 1, 1), 7));
   if constexpr (!FINE) {
     grad_to(X, BG_L0 + 0, 0)(7, acc[1]);  // the last tile of the stream
   } else {
@@ -196,11 +170,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwd
       for (int ks = 0; ks < 16; ++ks)
         Y[ks] = *reinterpret_cast<const u32x4*>(a.bG + ((size_t)a.wb_tot * bg_cum(BG_L0 + 4) + (size_t)wb * 16 + ks) * BF_FRAG_BYTES + lane16);
     }
-    bf_segment<S, BBS_G0T, 2, 16, 16, -1, 0, -1>(c, fr, acc, X, Y, [&](int, const f32x16& A) { dgp[0] = A; },
+    bf_segment<S, BSEG_G0T>(c, fr, acc, X, Y, [&](int, const f32x16& A) { dgp[0] = A; },
                                                  last_of(grad_to(X, BG_L0 + 0, 0), 7));
     dgp[1] = acc[1];
     // gamma -> point -> depth (t_fine is not detached, quirk Q9).  dgp[t][4g + 2e], [.. + 1] = d loss / d (sin, cos) of
     // pair pi = 16t + 4g + 2h + e
+    // (the same text closes field_bwd_split.hip, as the upstream prologue above opens it: moved into shared inline functions both
+    // compiled to different machine code in these kernels -- DESIGN.md section 7a -- so each kernel keeps its copy)
     // (the sample index is re-derived from the lane id HERE: nothing of the prologue stays alive across the stream, and the geometry
     // loads and the 16 sincos below cannot be hoisted over it)
     const int lane_e = (int)lane_id_here();
@@ -244,14 +220,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_bwd_bf16(const FieldBwd
 __global__ __launch_bounds__(256) void k_pack_weights_bf16_bwd(const Weights24 w, const float* __restrict__ fold, unsigned char* __restrict__ img) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= BBF_NCHUNK * BF_CHUNK * 64) return;
-  const int frag = gid >> 6, lane = gid & 63, i = lane & 31, h = lane >> 5;
-  u32x4 v;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-    v[q] = pack2(bb_weight(w, fold, frag, i, kk), bb_weight(w, fold, frag, i, kk + 1));
-  }
-  *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
+  const int frag = gid >> 6, lane = gid & 63;
+  *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = frag_lane_bf16<32, bb_weight>(w, fold, frag, lane);
 }
 
 hipError_t launch_pack_weights_bf16_bwd(const Weights24& w, const float* fold, unsigned char* img, hipStream_t st) {
@@ -268,7 +238,7 @@ hipError_t launch_field_bwd_bf16(const FieldBwdArgs& a, bool fine, hipStream_t s
   if (hipError_t e = ensure_dynamic_lds(opted, {reinterpret_cast<const void*>(&k_field_bwd_bf16<false, 8>), reinterpret_cast<const void*>(&k_field_bwd_bf16<true, 8>),
                                                 reinterpret_cast<const void*>(&k_field_bwd_bf16<false, 4>), reinterpret_cast<const void*>(&k_field_bwd_bf16<true, 4>)}, BB_LDS_BYTES)) return e;
   const int wgs = (a.M + BF_WG / 2 - 1) / (BF_WG / 2);
-  if (2 * wgs <= BF_SMALL_MAX_WGS && !bf16_four_waves_disabled()) {  // a small pass: 4-wave workgroups, so that every CU gets one
+  if (bf16_small_pass(wgs)) {  // 4-wave workgroups, so that every CU gets one
     if (fine)
       hipLaunchKernelGGL((k_field_bwd_bf16<true, 4>), dim3(2 * wgs), dim3(256), BB_LDS_BYTES, st, a, fz);
     else

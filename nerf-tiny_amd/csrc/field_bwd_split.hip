@@ -1,7 +1,7 @@
 // field_bwd_split.hip -- backward dX chain of the split-fp32 TRAIN step (NERF_HIP_SPLIT_MLP | NERF_HIP_SAVE_FOR_BACKWARD), MI355X / gfx950.
 // (forward: field_fwd_split.hip<SAVE>; weight gradients: the SPLIT instantiations of dw_bf16.hip)
 //
-// field_bwd_bf16.hip with every fp32 operand written as hi + mid (two bf16 parts, field_fwd_split.hip): the stream holds the TRANSPOSED
+// field_bwd_bf16.hip with every fp32 operand written as hi + mid (two bf16 parts, bf16_split.h): the stream holds the TRANSPOSED
 // weights from the colour head back to layer 0 as (hi, mid) fragment pairs, a wave owns 32 samples, and the fp32 accumulator of "d input" of
 // one layer, masked with the layer's saved ReLU bits and split into hi + mid, is the two-part B operand of the next (earlier) layer:
 //     dz -> dc -> dpre_dir -> dh7 (W_fold^T + w_sigma dspre) -> dpre7 -> ... -> dpre0 [-> d gamma_p -> dt, fine pass]
@@ -10,8 +10,7 @@
 // a.bG, mid parts to a.bG2 -- a layer's 2 x 16 pieces in one burst behind its last tile.  One wave per SIMD (the two-part operands of a
 // layer's input and output are 2 x 128 registers), 128 samples per workgroup; the wave's ReLU masks (9 x 1 KiB) come to LDS once, ahead of
 // the stream, by the same direct-to-LDS loads (LDS: 36 KiB masks + 7 x 16 KiB ring).
-#include "bf16_stream.h"
-#include "bf16_weights.h"
+#include "bf16_split.h"
 
 namespace nerf {
 
@@ -22,111 +21,24 @@ constexpr int SPB_LDS_BYTES = SPB_MASK_BYTES + SPB_NS * BF_CHUNK * BF_FRAG_BYTES
 static_assert(SPB_LDS_BYTES <= 160 * 1024, "LDS of one CU");
 static_assert((2 * BBC_NFRAG) % BF_CHUNK == 0 && (2 * BBF_NFRAG) % BF_CHUNK == 0, "whole chunks");
 
-// stores of the bursts (2 x (2 ntiles) pieces), each issued inside tile 0 of the NEXT segment: lumped at k-step BF_EPI_POS where that
-// segment has < BF_EPI_POS + 8 k-steps, behind part 7 (k-step BF_EPI_POS + 7) otherwise.  STEPS = bf16 fragment indices.
-struct SplitBwdBurst { int next_s0, next_ks, stores; };
+// counted stores (bf16_stream.h bf_store_table, two-part form): the bursts of 2 x (2 ntiles) gradient pieces
 template <bool FINE>
 struct SplitBwdStream {
-  static constexpr int NSTEP = FINE ? BBF_NFRAG : BBC_NFRAG;
-  static constexpr int NFRAG = 2 * NSTEP, NCHUNK = NFRAG / BF_CHUNK;
+  static constexpr int NFRAG = 2 * (FINE ? BBF_NFRAG : BBC_NFRAG), NCHUNK = NFRAG / BF_CHUNK;
   static constexpr int NS = SPB_NS, RING_OFF = SPB_MASK_BYTES, D = 6, PW = 4;
+  static constexpr const BfSeg* SEGS = kBwdSegs;  // STEPS of the two-part stream = fragments of the bf16 stream
+  static constexpr int NSEG = FINE ? BSEG_N : BSEG_G0T;
   static constexpr bool HAS_BIAS = false;
   static constexpr int PROLOGUE_STORES = 4;  // the dz / dspre fragment and its zero partner, hi and mid
-  struct Table { int cum[2 * BBF_NFRAG + 1]; };
-  static constexpr Table make() {
-    const SplitBwdBurst bursts[] = {{BBS_FOLDT, 9, 16},      {BBS_L7T, 16, 32},       {BBS_L7T + 128, 16, 32}, {BBS_L7T + 256, 16, 32}, {BBS_L4T, 16, 32},
-                                    {BBS_L3T, 16, 32},       {BBS_L3T + 128, 16, 32}, {BBS_L3T + 256, 16, 32}, {BBS_G0T, 32, 32}};  // (the last one: fine pass only)
-    Table t{};
-    int ev[BBF_NFRAG + 64] = {};
-    for (const SplitBwdBurst& b : bursts) {
-      const int e = b.next_s0 + BF_EPI_POS + (b.next_ks >= BF_EPI_POS + 8 ? 7 : 0);
-      if (e < NSTEP) ev[e] += b.stores;
-    }
-    int run = 0, step = 0;
-    for (int i = 0; i <= NFRAG; ++i) {
-      while (step < i / 2) run += ev[step++];
-      t.cum[i] = run;
-    }
-    return t;
-  }
-  static constexpr Table tab = make();
+  static constexpr BfStoreTable<NFRAG> tab = bf_store_table<NFRAG, 2>(SEGS, NSEG, 2, 0);
   __device__ static constexpr int stores_before(int idx) { return tab.cum[idx]; }
 };
-
-struct HiMidB { unsigned hi, mid; };
-__device__ __forceinline__ HiMidB split2b(float x0, float x1) {
-  HiMidB r;
-  r.hi = pack2(x0, x1);
-  const float h0 = __uint_as_float(r.hi << 16), h1 = __uint_as_float(r.hi & 0xffff0000u);
-  r.mid = pack2(x0 - h0, x1 - h1);
-  return r;
-}
-
-struct EpiTmpB { float x0, x1; unsigned hi; };
-
-// One segment of the two-part stream (field_fwd_split.hip's sp_segment without biases): NFT output tiles x (KSA + KSB) k-steps starting at
-// STEP S0; inputs inA then inB as hi / mid parts; the finished tile's epilogue spread one register pair per k-step where the tile is long enough.
-template <class S, int S0, int NFT, int KSA, int KSB, int P0, class Epi, class PrevEpi>
-__device__ __forceinline__ void spb_segment(const BfCtx& c, u32x4 (&fr)[S::D], f32x16 (&acc)[2], const u32x4* inA_hi, const u32x4* inA_mid,
-                                            const u32x4* inB_hi, const u32x4* inB_mid, Epi&& epi, PrevEpi&& prev_epi) {
-  constexpr int KS = KSA + KSB;
-  constexpr bool SPREAD = KS >= BF_EPI_POS + 8;
-  constexpr int LAST = SPREAD ? BF_EPI_POS + 7 : BF_EPI_POS;
-  static_assert(KS > LAST, "segment too short for the deferred epilogue");
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  EpiTmpB tmp = {0.f, 0.f, 0u};
-  static_for<NFT * KS>([&](auto I) {
-    constexpr int f = I / KS, ks = I % KS, i0 = 2 * (S0 + I), i1 = i0 + 1;
-    constexpr int cur = (P0 + f) & 1, oth = (P0 + f + 1) & 1;
-    constexpr bool EPI = SPREAD && ks >= BF_EPI_POS && ks <= LAST;
-    auto phase = [&](auto PH) {
-      if constexpr (EPI) {
-        if constexpr (f == 0)
-          prev_epi(ks - BF_EPI_POS, (int)PH, acc[oth], tmp);
-        else
-          epi(f - 1, ks - BF_EPI_POS, (int)PH, acc[oth], tmp);
-      }
-    };
-    if constexpr (i0 % BF_CHUNK == BF_SYNC_POS) bf_sync<S, i0 / BF_CHUNK>(c);
-    const u32x4 a_hi = fr[i0 % S::D];
-    if constexpr (i0 + S::D < S::NFRAG) fr[i0 % S::D] = bf_frag<S>(c, i0 + S::D);
-    const u32x4 a_mid = fr[i1 % S::D];
-    if constexpr (i1 + S::D < S::NFRAG) fr[i1 % S::D] = bf_frag<S>(c, i1 + S::D);
-    const u32x4& b_hi = ks < KSA ? inA_hi[ks < KSA ? ks : 0] : inB_hi[ks < KSA ? 0 : ks - KSA];
-    const u32x4& b_mid = ks < KSA ? inA_mid[ks < KSA ? ks : 0] : inB_mid[ks < KSA ? 0 : ks - KSA];
-    acc[cur] = bf_mfma(a_mid, b_hi, acc[cur]);
-    phase(std::integral_constant<int, 0>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    acc[cur] = bf_mfma(a_hi, b_mid, acc[cur]);
-    phase(std::integral_constant<int, 1>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    acc[cur] = bf_mfma(a_hi, b_hi, acc[cur]);
-    phase(std::integral_constant<int, 2>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!SPREAD && ks == BF_EPI_POS) {
-      static_for<8>([&](auto P) {
-        static_for<3>([&](auto PH) {
-          if constexpr (f == 0)
-            prev_epi((int)P, (int)PH, acc[oth], tmp);
-          else
-            epi(f - 1, (int)P, (int)PH, acc[oth], tmp);
-        });
-      });
-    }
-    if constexpr (ks == LAST) acc[oth] = zero;
-  });
-}
 
 template <bool FINE>
 __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   using S = SplitBwdStream<FINE>;
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BfCtx c = bf_ctx(a.wbf, lds);
   const int lane = c.lane, j = lane & 31, h = lane >> 5;
   const int m = blockIdx.x * (SPB_WG / 2) + c.wv * 32 + j;
   const bool valid = m < a.M;
@@ -146,7 +58,7 @@ __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArg
   // as a two-part B operand / gradient fragment: inputs 0..2 = dz, input 3 = dspre  (k = 4h + s: lane half 0, slots 0..3)
   u32x4 zh[4], zm[4];
   {
-    const HiMidB e0 = split2b(dz[0], dz[1]), e1 = split2b(dz[2], ds);
+    const HiMid e0 = split2(dz[0], dz[1]), e1 = split2(dz[2], ds);
     zh[0] = u32x4{h == 0 ? e0.hi : 0u, h == 0 ? e1.hi : 0u, 0u, 0u};
     zm[0] = u32x4{h == 0 ? e0.mid : 0u, h == 0 ? e1.mid : 0u, 0u, 0u};
   }
@@ -180,7 +92,7 @@ __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArg
   // epilogue, one register pair (part = (mh, q)) of d(input) tile f per call and phase: mask with the ReLU bits of `mlayer` (bit 15 - r = register r
   // alive) -> two-part packed slot q of k-step 2f + mh of the next GEMM; behind the tensor's last tile its 2 x (2 ntiles) pieces in one burst
   auto grad_to = [&](u32x4* oh, u32x4* om, int tensor, int mlayer, int ntiles = 8) {
-    return [&, oh, om, tensor, mlayer, ntiles](int f, int part, int ph, const f32x16& A, EpiTmpB& t) {
+    return [&, oh, om, tensor, mlayer, ntiles](int f, int part, int ph, const f32x16& A, EpiTmp& t) {
       const int mh = part >> 2, q = part & 3, r = 8 * mh + 2 * q;
       if (ph == 0) {
         const int bits = mk[mlayer * 512 + f];
@@ -202,25 +114,25 @@ __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArg
       }
     };
   };
-  auto last_of = [](auto epi, int f) { return [epi, f](int part, int ph, const f32x16& A, EpiTmpB& t) { epi(f, part, ph, A, t); }; };
-  auto nothing = [](int, int, const f32x16&, EpiTmpB&) {};
+  auto last_of = [](auto epi, int f) { return [epi, f](int part, int ph, const f32x16& A, EpiTmp& t) { epi(f, part, ph, A, t); }; };
+  auto nothing = [](int, int, const f32x16&, EpiTmp&) {};
 
   auto gd = grad_to(Xh, Xm, BG_D, 8, 4);  // d c through c's ReLU = dpre_dir (4 tiles)
   auto g7 = grad_to(Yh, Ym, BG_L0 + 7, 7), g6 = grad_to(Xh, Xm, BG_L0 + 6, 6), g5 = grad_to(Yh, Ym, BG_L0 + 5, 5), g4 = grad_to(Xh, Xm, BG_L0 + 4, 4);
   auto g3 = grad_to(Yh, Ym, BG_L0 + 3, 3), g2 = grad_to(Xh, Xm, BG_L0 + 2, 2), g1 = grad_to(Yh, Ym, BG_L0 + 1, 1), g0 = grad_to(Xh, Xm, BG_L0 + 0, 0);
   // colour head: dc = W_color^T dz, through c's ReLU -> dpre_dir
-  spb_segment<S, BBS_COLT, 4, 4, 0, 0>(c, fr, acc, zh, zm, nullptr, nullptr, gd, nothing);
+  sp_segment<S, BSEG_COLT>(c, fr, acc, zh, zm, nullptr, nullptr, gd, nothing);
   // dir_info and point_info as ONE transposed layer (folded) + the sigma head: dh7 = W_fold^T dpre_dir + w_sigma dspre, through h7's ReLU
-  spb_segment<S, BBS_FOLDT, 8, 8, 1, 0>(c, fr, acc, Xh, Xm, zh, zm, g7, last_of(gd, 3));
-  spb_segment<S, BBS_L7T, 8, 16, 0, 0>(c, fr, acc, Yh, Ym, nullptr, nullptr, g6, last_of(g7, 7));
-  spb_segment<S, BBS_L7T + 128, 8, 16, 0, 0>(c, fr, acc, Xh, Xm, nullptr, nullptr, g5, last_of(g6, 7));
-  spb_segment<S, BBS_L7T + 256, 8, 16, 0, 0>(c, fr, acc, Yh, Ym, nullptr, nullptr, g4, last_of(g5, 7));
-  spb_segment<S, BBS_L4T, 8, 16, 0, 0>(c, fr, acc, Xh, Xm, nullptr, nullptr, g3, last_of(g4, 7));
-  spb_segment<S, BBS_L3T, 8, 16, 0, 0>(c, fr, acc, Yh, Ym, nullptr, nullptr, g2, last_of(g3, 7));
-  spb_segment<S, BBS_L3T + 128, 8, 16, 0, 0>(c, fr, acc, Xh, Xm, nullptr, nullptr, g1, last_of(g2, 7));
-  spb_segment<S, BBS_L3T + 256, 8, 16, 0, 0>(c, fr, acc, Yh, Ym, nullptr, nullptr, g0, last_of(g1, 7));
+  sp_segment<S, BSEG_FOLDT>(c, fr, acc, Xh, Xm, zh, zm, g7, last_of(gd, 3));
+  sp_segment<S, BSEG_L7T>(c, fr, acc, Yh, Ym, nullptr, nullptr, g6, last_of(g7, 7));
+  sp_segment<S, BSEG_L6T>(c, fr, acc, Xh, Xm, nullptr, nullptr, g5, last_of(g6, 7));
+  sp_segment<S, BSEG_L5T>(c, fr, acc, Yh, Ym, nullptr, nullptr, g4, last_of(g5, 7));
+  sp_segment<S, BSEG_L4T>(c, fr, acc, Xh, Xm, nullptr, nullptr, g3, last_of(g4, 7));
+  sp_segment<S, BSEG_L3T>(c, fr, acc, Yh, Ym, nullptr, nullptr, g2, last_of(g3, 7));
+  sp_segment<S, BSEG_L2T>(c, fr, acc, Xh, Xm, nullptr, nullptr, g1, last_of(g2, 7));
+  sp_segment<S, BSEG_L1T>(c, fr, acc, Yh, Ym, nullptr, nullptr, g0, last_of(g1, 7));
   if constexpr (!FINE) {
-    EpiTmpB t = {0.f, 0.f, 0u};
+    EpiTmp t = {0.f, 0.f, 0u};
     static_for<8>([&](auto P) { static_for<3>([&](auto PH) { g0(7, (int)P, (int)PH, acc[1], t); }); });  // the last tile of the stream
   } else {
     // ---- d gamma_p (fp32) = W_0^T dpre0 + W_4[:, 256:]^T dpre4  (nerf.py:104, 109).  dpre4 is long gone from the registers: the wave reads
@@ -236,10 +148,11 @@ __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArg
         Ym[ks] = *reinterpret_cast<const u32x4*>(a.bG2 + off);
       }
     }
-    auto take0 = [&](int, int part, int ph, const f32x16& A, EpiTmpB&) { if (part == 0 && ph == 0) dgp[0] = A; };
-    spb_segment<S, BBS_G0T, 2, 16, 16, 0>(c, fr, acc, Xh, Xm, Yh, Ym, take0, last_of(g0, 7));
+    auto take0 = [&](int, int part, int ph, const f32x16& A, EpiTmp&) { if (part == 0 && ph == 0) dgp[0] = A; };
+    sp_segment<S, BSEG_G0T>(c, fr, acc, Xh, Xm, Yh, Ym, take0, last_of(g0, 7));
     dgp[1] = acc[1];
     // gamma -> point -> depth (t_fine is not detached, quirk Q9).  dgp[t][4g + 2e], [.. + 1] = d loss / d (sin, cos) of pair pi = 16t + 4g + 2h + e
+    // (field_bwd_bf16.hip's tail and prologue, kept as copies: see there)
     const int lane_e = (int)lane_id_here();
     const int h_e = lane_e >> 5;
     const int m_e = blockIdx.x * (SPB_WG / 2) + c.wv * 32 + (lane_e & 31);
@@ -281,18 +194,11 @@ __global__ __launch_bounds__(SPB_WG, 1) void k_field_bwd_split(const FieldBwdArg
 __global__ __launch_bounds__(256) void k_pack_weights_split_bwd(const Weights24 w, const float* __restrict__ fold, unsigned char* __restrict__ img) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= BBF_NFRAG * 64) return;
-  const int step = gid >> 6, lane = gid & 63, i = lane & 31, h = lane >> 5;
-  u32x4 vh, vm;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-    const HiMidB e = split2b(bb_weight(w, fold, step, i, kk), bb_weight(w, fold, step, i, kk + 1));
-    vh[q] = e.hi;
-    vm[q] = e.mid;
-  }
+  const int step = gid >> 6, lane = gid & 63;
+  const FragHiMid v = frag_lane_split<32, bb_weight>(w, fold, step, lane);
   unsigned char* dst = img + BF_BIAS_BYTES + (size_t)(2 * step) * BF_FRAG_BYTES + lane * 16;
-  *reinterpret_cast<u32x4*>(dst) = vh;
-  *reinterpret_cast<u32x4*>(dst + BF_FRAG_BYTES) = vm;
+  *reinterpret_cast<u32x4*>(dst) = v.hi;
+  *reinterpret_cast<u32x4*>(dst + BF_FRAG_BYTES) = v.mid;
 }
 
 size_t split_bwd_image_bytes() { return (size_t)BF_BIAS_BYTES + (size_t)2 * BBF_NFRAG * BF_FRAG_BYTES; }

@@ -25,27 +25,10 @@
 
 namespace nerf {
 
-// ---- store schedule of the training variant (see bf16_stream.h): stores per tile epilogue ------------------------------
+// ---- store schedule of the training variant (bf16_stream.h bf_store_table) -----------------------------------------------------------------
 // The 16 (8) pieces of a layer's output and its 8 (4) mask words (one 16-byte store per lane) go out in ONE burst with the
 // layer's last tile -- 17 KiB contiguous per wave instead of pieces spread over the layer (DRAM page locality of the writes).
-struct FwdTiles { int s0, nft, ks, stores, last_extra; };
-constexpr FwdTiles kFwdTiles[] = {
-    {BFS_L0, 8, 4, 0, 17},        {BFS_L1, 8, 16, 0, 17},       {BFS_L1 + 128, 8, 16, 0, 17}, {BFS_L1 + 256, 8, 16, 0, 17},
-    {BFS_L4, 8, 20, 0, 17},       {BFS_L5, 8, 16, 0, 17},       {BFS_L5 + 128, 8, 16, 0, 17}, {BFS_L5 + 256, 8, 16, 0, 17},
-    {BFS_SIG, 1, 16, 0, 0},       {BFS_DIR, 4, 18, 0, 9},       {BFS_COL, 1, 8, 0, 0}};
-constexpr BfStoreTable<BF_NFRAG> make_fwd_store_table() {
-  BfStoreTable<BF_NFRAG> t{};
-  int ev[BF_NFRAG + 64] = {};
-  for (const FwdTiles& g : kFwdTiles)
-    for (int f = 0; f < g.nft; ++f) ev[g.s0 + (f + 1) * g.ks + BF_EPI_POS] += g.stores + (f == g.nft - 1 ? g.last_extra : 0);
-  int run = 0;
-  for (int i = 0; i <= BF_NFRAG; ++i) {
-    t.cum[i] = run;  // events strictly before step i
-    run += ev[i];
-  }
-  return t;
-}
-constexpr BfStoreTable<BF_NFRAG> kFwdStoreTable = make_fwd_store_table();
+constexpr BfStoreTable<BF_NFRAG> kFwdStoreTable = bf_store_table<BF_NFRAG, 1>(kFwdSegs, FSEG_N, 1, 1);
 
 constexpr int BFW_LDS_BYTES = BF_LDS_BYTES + BF_WG * 32;  // bias block + ring + 32 bytes per lane of parked direction encodings = 160 KiB
 static_assert(BFW_LDS_BYTES <= 160 * 1024, "LDS of one CU");
@@ -53,25 +36,19 @@ static_assert(BFW_LDS_BYTES <= 160 * 1024, "LDS of one CU");
 template <bool SAVE>
 struct FwdStream {
   static constexpr int NFRAG = BF_NFRAG, NCHUNK = BF_NCHUNK, NS = BF_NS, RING_OFF = BF_BIAS_BYTES, D = BF_D;
+  static constexpr const BfSeg* SEGS = kFwdSegs;
+  static constexpr int NSEG = FSEG_N;
   static constexpr bool HAS_BIAS = true;
   static constexpr int PROLOGUE_STORES = SAVE ? 6 : 0;  // gamma_p (4 pieces) and gamma_d (2)
   __device__ static constexpr int stores_before(int idx) { return SAVE ? kFwdStoreTable.cum[idx] : 0; }
 };
-
-// A stream description for a 4-wave workgroup: the 16 pieces of a chunk over 4 waves (bf16_stream.h BfPW)
-template <class Base> struct FourWaves : Base { static constexpr int PW = 4; };
 
 // WAVES = 8: 256 samples per workgroup, two waves per SIMD.  WAVES = 4 (128 samples, one wave per SIMD) is what a SMALL pass gets: the
 // coarse pass of a 512-ray batch is 128 workgroups of 256 samples -- half of the CUs idle -- or 256 of 128 (as field_fwd_bf16x.hip does).
 template <bool SAVE, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArgs a, const FwdFuse fz) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BfCtx c = bf_ctx(a.wbf, lds);
   const int lane = c.lane, j = lane & 31, h = lane >> 5;
   const int m = blockIdx.x * (32 * WAVES) + c.wv * 32 + j;
   const bool valid = m < a.M;
@@ -99,26 +76,16 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int pi = 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1);
-      float sv = 0.f, cv = 0.f;
-      if (pi < 30) {
-        const int cc = pi / 10, l = pi - 10 * cc;
-        const float x = (cc == 0) ? p[0] : ((cc == 1) ? p[1] : p[2]);
-        sincos_phase(x * __uint_as_float(kFreqPointBits[l]), sv, cv);
-      }
+      float sv, cv;
+      encode_point_pair(p, 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1), sv, cv);
       gp[ks][q] = pack2(sv, cv);
     }
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int pi = 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1);
-      float sv = 0.f, cv = 0.f;
-      if (pi < 12) {
-        const int cc = pi / 4, l = pi - 4 * cc;
-        const float x = (cc == 0) ? dw[0] : ((cc == 1) ? dw[1] : dw[2]);
-        sincos_phase(x * __uint_as_float(kFreqDirBits[l]), sv, cv);
-      }
+      float sv, cv;
+      encode_dir_pair(dw, 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1), sv, cv);
       gd[ks][q] = pack2(sv, cv);
     }
 
@@ -180,18 +147,18 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
   auto nothing_f = [](int, const f32x16&) {};
 
   // ---- layers 0..7 (nerf.py:104-112)
-  bf_segment<S, BFS_L0, 8, 4, 0, BFB_L0, 0, BFB_L0 + 8>(c, fr, acc, gp, nullptr, relu_to(X, BS_H0 + 0, 0), nothing);
-  bf_segment<S, BFS_L1, 8, 16, 0, BFB_L0 + 8, 0, BFB_L0 + 16>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 1, 1), last_of(relu_to(X, BS_H0 + 0, 0), 7));
-  bf_segment<S, BFS_L1 + 128, 8, 16, 0, BFB_L0 + 16, 0, BFB_L0 + 24>(c, fr, acc, Y, nullptr, relu_to(X, BS_H0 + 2, 2), last_of(relu_to(Y, BS_H0 + 1, 1), 7));
-  bf_segment<S, BFS_L1 + 256, 8, 16, 0, BFB_L0 + 24, 0, BFB_L0 + 32>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 3, 3), last_of(relu_to(X, BS_H0 + 2, 2), 7));
-  bf_segment<S, BFS_L4, 8, 16, 4, BFB_L0 + 32, 0, BFB_L0 + 40>(c, fr, acc, Y, gp, relu_to(X, BS_H0 + 4, 4), last_of(relu_to(Y, BS_H0 + 3, 3), 7));
-  bf_segment<S, BFS_L5, 8, 16, 0, BFB_L0 + 40, 0, BFB_L0 + 48>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 5, 5), last_of(relu_to(X, BS_H0 + 4, 4), 7));
-  bf_segment<S, BFS_L5 + 128, 8, 16, 0, BFB_L0 + 48, 0, BFB_L0 + 56>(c, fr, acc, Y, nullptr, relu_to(X, BS_H0 + 6, 6), last_of(relu_to(Y, BS_H0 + 5, 5), 7));
-  bf_segment<S, BFS_L5 + 256, 8, 16, 0, BFB_L0 + 56, 0, BFB_SIGMA>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 7, 7), last_of(relu_to(X, BS_H0 + 6, 6), 7));
+  bf_segment<S, FSEG_L0>(c, fr, acc, gp, nullptr, relu_to(X, BS_H0 + 0, 0), nothing);
+  bf_segment<S, FSEG_L1>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 1, 1), last_of(relu_to(X, BS_H0 + 0, 0), 7));
+  bf_segment<S, FSEG_L2>(c, fr, acc, Y, nullptr, relu_to(X, BS_H0 + 2, 2), last_of(relu_to(Y, BS_H0 + 1, 1), 7));
+  bf_segment<S, FSEG_L3>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 3, 3), last_of(relu_to(X, BS_H0 + 2, 2), 7));
+  bf_segment<S, FSEG_L4>(c, fr, acc, Y, gp, relu_to(X, BS_H0 + 4, 4), last_of(relu_to(Y, BS_H0 + 3, 3), 7));
+  bf_segment<S, FSEG_L5>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 5, 5), last_of(relu_to(X, BS_H0 + 4, 4), 7));
+  bf_segment<S, FSEG_L6>(c, fr, acc, Y, nullptr, relu_to(X, BS_H0 + 6, 6), last_of(relu_to(Y, BS_H0 + 5, 5), 7));
+  bf_segment<S, FSEG_L7>(c, fr, acc, X, nullptr, relu_to(Y, BS_H0 + 7, 7), last_of(relu_to(X, BS_H0 + 6, 6), 7));
   // ---- sigma head (one tile, row 0) on h7: sigma = |w_sigma . h7 + b|  (nerf.py:94, 113-115)
   float spre = 0.f;
   auto sig_epi = [&](const f32x16& A) { spre = A[0]; };
-  bf_segment<S, BFS_SIG, 1, 16, 0, BFB_SIGMA, 0, BFB_DIR>(c, fr, acc, Y, nullptr, nothing_f, last_of(relu_to(Y, BS_H0 + 7, 7), 7));
+  bf_segment<S, FSEG_SIG>(c, fr, acc, Y, nullptr, nothing_f, last_of(relu_to(Y, BS_H0 + 7, 7), 7));
   // ---- point_info folded into dir_info (bf16_common.h): c = relu(W_dir[:, :24] gamma_d + W_fold h7 + b_dir + W_dir[:, 24:] b_pi)
   // (nerf.py:117-118); its first tile also retires the sigma tile
   {
@@ -200,7 +167,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
     gd[0] = back[0];
     gd[1] = back[1];
   }
-  bf_segment<S, BFS_DIR, 4, 2, 16, BFB_DIR, 1, BFB_COL>(c, fr, acc, gd, Y, relu_to(X, BS_C, 8, 4), sig_epi);
+  bf_segment<S, FSEG_DIR>(c, fr, acc, gd, Y, relu_to(X, BS_C, 8, 4), sig_epi);
   // (the sample index is re-derived from the lane id behind the stream -- mbcnt, not threadIdx: nothing to keep alive or spill)
   const int lane_e = (int)lane_id_here();
   const int m_e = blockIdx.x * (32 * WAVES) + c.wv * 32 + (lane_e & 31);
@@ -215,7 +182,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
   unsigned char* const park_w = lds + BF_LDS_BYTES + c.wv * 2048;
   if (SAVE && fz.mode != 0 && lane_e < 32) reinterpret_cast<float*>(park_w)[lane_e] = fabsf(spre);
   // ---- colour head: rows 0..2 of one tile, sigmoid (nerf.py:99, 119)
-  bf_segment<S, BFS_COL, 1, 8, 0, BFB_COL, 1, -1>(c, fr, acc, X, nullptr, nothing_f, last_of(relu_to(X, BS_C, 8, 4), 3));
+  bf_segment<S, FSEG_COL>(c, fr, acc, X, nullptr, nothing_f, last_of(relu_to(X, BS_C, 8, 4), 3));
   {
     const float r0 = 1.0f / (1.0f + expf(-acc[1][0])), r1 = 1.0f / (1.0f + expf(-acc[1][1])), r2 = 1.0f / (1.0f + expf(-acc[1][2]));
     if (out_e) {
@@ -308,14 +275,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16(const FieldArg
 __global__ __launch_bounds__(256) void k_pack_weights_bf16(const Weights24 w, const float* __restrict__ fold, unsigned char* __restrict__ img, int first_thread) {
   const int gid = first_thread + blockIdx.x * 256 + threadIdx.x;
   if (gid < BF_NFRAG * 64) {
-    const int frag = gid >> 6, lane = gid & 63, i = lane & 31, h = lane >> 5;
-    u32x4 v;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-      v[q] = pack2(bf_weight(w, fold, frag, i, kk, h), bf_weight(w, fold, frag, i, kk + 1, h));
-    }
-    *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
+    const int frag = gid >> 6, lane = gid & 63;
+    *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = frag_lane_bf16<32, bf_weight>(w, fold, frag, lane);
   } else {
     const int b = gid - BF_NFRAG * 64;
     if (b < BF_BIAS_BYTES / 4) {
@@ -344,7 +305,7 @@ hipError_t launch_field_fwd_bf16(const FieldArgs& a, bool save, hipStream_t st, 
   if (hipError_t e = ensure_dynamic_lds(opted, {reinterpret_cast<const void*>(&k_field_fwd_bf16<false, 8>), reinterpret_cast<const void*>(&k_field_fwd_bf16<true, 8>),
                                                 reinterpret_cast<const void*>(&k_field_fwd_bf16<false, 4>), reinterpret_cast<const void*>(&k_field_fwd_bf16<true, 4>)}, BFW_LDS_BYTES)) return e;
   const int wgs = (a.M + BF_WG / 2 - 1) / (BF_WG / 2);  // 256-sample workgroups: the pass's wave blocks are whole ones of these (api.hip wave_blocks)
-  if (2 * wgs <= BF_SMALL_MAX_WGS && !bf16_four_waves_disabled()) {  // a small pass: 4-wave workgroups, so that every CU gets one
+  if (bf16_small_pass(wgs)) {  // 4-wave workgroups, so that every CU gets one
     if (save)
       hipLaunchKernelGGL((k_field_fwd_bf16<true, 4>), dim3(2 * wgs), dim3(256), BFW_LDS_BYTES, st, a, fz);
     else

@@ -110,6 +110,7 @@ __device__ __forceinline__ void bx_field_pass(const BfCtx& c, unsigned char* lds
 
   // ---- encodings straight into B-operand registers: k-step s, slot pair (j, j+1) = (sin, cos) pair
   // pi = 16s + 8 (j >> 2) + 2q + ((j >> 1) & 1), i.e. features 32s + 16 (j >> 2) + 4q + (j & 3)
+  // (bf16_stream.h encode_pair written out: called from here it changed the machine code of this unit's kernels -- DESIGN.md section 7a)
   u32x4 gp[NH][8], gd[NH][8];  // only [.][0..1] / [.][0] are used (the segment interface indexes [group][k-step])
 #pragma unroll
   for (int h = 0; h < NH; ++h) {
@@ -207,12 +208,7 @@ template <int NH, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_field_fwd_bf16x(const FieldArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   using S = typename BxStreamOf<WAVES>::type;
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BfCtx c = bf_ctx(a.wbf, lds);
   const int lane = c.lane, n = lane & 15;
   const int m0 = blockIdx.x * (16 * NH * WAVES) + c.wv * (16 * NH);
 
@@ -396,12 +392,7 @@ __device__ __forceinline__ void pair_fine_pass(const PairArgs& a, const BfCtx& c
 
 __global__ __launch_bounds__(BF_WG, 1) void k_render_pair_bf16x(const PairArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BfCtx c = bf_ctx(a.wbf, lds);
   float* const res = reinterpret_cast<float*>(lds);
   const int r0 = 2 * blockIdx.x;  // this workgroup's rays r0, r0 + 1 (the second one may lie behind the batch: computed on a copy, not stored)
   // No kernel runs in front of this one in a rendering loop (the ray records are made here, the weight image is reused), so nobody has
@@ -524,14 +515,8 @@ hipError_t launch_render_pair_bf16x(const PairArgs& a, hipStream_t st) {
 __global__ __launch_bounds__(256) void k_pack_weights_bf16x(const Weights24 w, const float* __restrict__ fold, unsigned char* __restrict__ img) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= BX_NCHUNK * BF_CHUNK * 64) return;
-  const int frag = gid >> 6, lane = gid & 63, i = lane & 15, q = lane >> 4;
-  u32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {  // slots 2e, 2e + 1
-    const int kk = 16 * (e >> 1) + 4 * q + 2 * (e & 1);
-    v[e] = pack2(bx_weight(w, fold, frag, i, kk), bx_weight(w, fold, frag, i, kk + 1));
-  }
-  *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
+  const int frag = gid >> 6, lane = gid & 63;
+  *reinterpret_cast<u32x4*>(img + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = frag_lane_bf16<16, bx_weight>(w, fold, frag, lane);
 }
 
 hipError_t launch_pack_weights_bf16x(const Weights24& w, const float* fold, unsigned char* img, hipStream_t st) {

@@ -15,12 +15,11 @@
 // save buffer (bf16_common.h: 1-KiB pieces, one per wave and k-step, whole lines per store) -- with the ReLU masks of the bf16 layout and the
 // sigma pre-activation; a layer's 2 x 16 pieces + its mask words go out in one burst behind the layer's last tile.
 //
-// Machinery: bf16_stream.h (LDS ring of 1-KiB A fragments filled by direct-to-LDS loads, activations in registers, the accumulator
+// Machinery: bf16_stream.h and its two-part form bf16_split.h (LDS ring of 1-KiB A fragments filled by direct-to-LDS loads, activations in registers, the accumulator
 // of one layer = the operand of the next), in a 4-wave form: ONE wave per SIMD (the two-part activations of a layer's input and
 // output are 2 x 128 registers), 128 samples per workgroup.  The stream interleaves the two parts of every fragment of the bf16
 // layout of bf16_common.h (point_info folded into dir_info: common.h SEG_FOLD): fragment 2 s = hi, 2 s + 1 = mid of step s.
-#include "bf16_stream.h"
-#include "bf16_weights.h"
+#include "bf16_split.h"
 
 namespace nerf {
 
@@ -29,32 +28,15 @@ constexpr int SP_NCHUNK = SP_NFRAG / BF_CHUNK;
 static_assert(SP_NCHUNK * BF_CHUNK == SP_NFRAG, "whole chunks");
 constexpr int SP_WG = 256;                        // 4 waves x 32 samples
 
-// ---- store schedule of the SAVE variant (bf16_stream.h: stores share the vmcnt queue with the ring's loads and retire in order, so every
-// counted wait allows for the younger ones).  Counted: the burst behind a layer's last tile -- 2 x (2 ntiles) pieces + 1 mask piece -- which
-// every lane issues unconditionally.  The last tile's epilogue runs inside the NEXT segment's tile 0: spread over k-steps BF_EPI_POS ..
-// BF_EPI_POS + 7 where that segment has >= BF_EPI_POS + 8 k-steps (the burst follows part 7), in one lump at k-step BF_EPI_POS otherwise.
-// The conditional stores (sigma, spre, rgb) are NOT counted: an uncounted store only makes a wait more conservative.
-struct SplitBurst { int next_s0, next_ks, stores; };  // next segment's first STEP (= bf16 fragment index) and k-steps per tile; stores of the burst
-constexpr SplitBurst kSplitBursts[] = {
-    {BFS_L1, 16, 33},       {BFS_L1 + 128, 16, 33}, {BFS_L1 + 256, 16, 33}, {BFS_L4, 20, 33}, {BFS_L5, 16, 33},
-    {BFS_L5 + 128, 16, 33}, {BFS_L5 + 256, 16, 33}, {BFS_SIG, 16, 33},      {BFS_COL, 8, 17}};
-struct SplitStoreTable { int cum[2 * BF_NFRAG + 1]; };
-constexpr SplitStoreTable make_split_store_table() {
-  SplitStoreTable t{};
-  int ev[BF_NFRAG + 64] = {};  // counted stores issued in STEP i (after that step's sync point)
-  for (const SplitBurst& b : kSplitBursts) ev[b.next_s0 + BF_EPI_POS + (b.next_ks >= BF_EPI_POS + 8 ? 7 : 0)] += b.stores;
-  int run = 0, step = 0;
-  for (int i = 0; i <= 2 * BF_NFRAG; ++i) {  // fragment index i: the steps before it are 0 .. i / 2 - 1 (sync points sit on even indices)
-    while (step < i / 2) run += ev[step++];
-    t.cum[i] = run;
-  }
-  return t;
-}
-constexpr SplitStoreTable kSplitStoreTable = make_split_store_table();
+// ---- store schedule of the SAVE variant (bf16_stream.h bf_store_table, two-part form): the burst behind a layer's last tile is
+// 2 x (2 ntiles) pieces + 1 mask piece.  The conditional stores (sigma, spre, rgb) are not counted.
+constexpr BfStoreTable<SP_NFRAG> kSplitStoreTable = bf_store_table<SP_NFRAG, 2>(kFwdSegs, FSEG_N, 2, 1);
 
 template <bool SAVE>
 struct SplitStreamT {
   static constexpr int NFRAG = SP_NFRAG, NCHUNK = SP_NCHUNK, NS = BF_NS, RING_OFF = BF_BIAS_BYTES, D = 6, PW = 4;
+  static constexpr const BfSeg* SEGS = kFwdSegs;  // STEPS of the two-part stream = fragments of the bf16 stream
+  static constexpr int NSEG = FSEG_N;
   static constexpr bool HAS_BIAS = true;
   static constexpr int PROLOGUE_STORES = SAVE ? 12 : 0;  // gamma_p (4 k-steps) and gamma_d (2), hi and mid pieces each
   __device__ static constexpr int stores_before(int idx) { return SAVE ? kSplitStoreTable.cum[idx] : 0; }
@@ -62,98 +44,11 @@ struct SplitStreamT {
 using SplitStream = SplitStreamT<false>;
 static_assert(BF_SYNC_POS % 2 == 0 && SplitStream::D % 2 == 0, "a step's two fragments stay in one chunk / keep their ring parity");
 
-// two fp32 values -> their hi parts (packed bf16 pair) and mid parts
-struct HiMid { unsigned hi, mid; };
-__device__ __forceinline__ HiMid split2(float x0, float x1) {
-  HiMid r;
-  r.hi = pack2(x0, x1);
-  const float h0 = __uint_as_float(r.hi << 16), h1 = __uint_as_float(r.hi & 0xffff0000u);
-  r.mid = pack2(x0 - h0, x1 - h1);
-  return r;
-}
-
-// One segment: NFT output tiles x (KSA + KSB) k-steps starting at STEP S0 (fragments 2 S0 ..); inputs inA (k-steps 0..KSA-1) then
-// inB, each as hi / mid parts.  Per step three MFMAs, the small products first.  Accumulator hand-over as in bf_segment, except that
-// the epilogue of the finished tile is SPREAD: with one wave per SIMD nothing else fills the matrix pipe while this wave converts, so the
-// 8 register pairs of a tile (epi(f, part, acc): ~13 vector instructions each) go one per k-step behind k-steps 2 .. 9 of the next
-// tile -- about four vector instructions per MFMA, which the 32-cycle MFMA hides -- instead of ~110 in one lump.  Segments shorter than
-// ten k-steps keep the lump.
-struct EpiTmp { float x0, x1; unsigned hi; };  // state of one register pair between the three phases of its conversion
-// a ReLU'd value is >= +0: alive (its ReLU passes the gradient) <=> its bit pattern is >= 1; bit 15 - r of a tile's mask word = register r
-__device__ __forceinline__ unsigned alive_pair(float x0, float x1, int r) {
-  return ((unsigned)min(__float_as_int(x0), 1) << (15 - r)) | ((unsigned)min(__float_as_int(x1), 1) << (14 - r));
-}
-
-template <class S, int S0, int NFT, int KSA, int KSB, int BT0, int P0, int NEXT_BT, class Epi, class PrevEpi>
-__device__ __forceinline__ void sp_segment(const BfCtx& c, u32x4 (&fr)[S::D], f32x16 (&acc)[2], const u32x4* inA_hi, const u32x4* inA_mid,
-                                           const u32x4* inB_hi, const u32x4* inB_mid, Epi&& epi, PrevEpi&& prev_epi) {
-  constexpr int KS = KSA + KSB;
-  constexpr bool SPREAD = KS >= BF_EPI_POS + 8;
-  constexpr int LAST = SPREAD ? BF_EPI_POS + 7 : BF_EPI_POS;  // k-step behind which the finished accumulator is free again
-  static_assert(KS > LAST, "segment too short for the deferred epilogue");
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  EpiTmp tmp = {0.f, 0.f, 0u};
-  static_for<NFT * KS>([&](auto I) {
-    constexpr int f = I / KS, ks = I % KS, i0 = 2 * (S0 + I), i1 = i0 + 1;
-    constexpr int cur = (P0 + f) & 1, oth = (P0 + f + 1) & 1;
-    constexpr bool EPI = SPREAD && ks >= BF_EPI_POS && ks <= LAST;
-    auto phase = [&](auto PH) {  // one third of the conversion of register pair ks - BF_EPI_POS of the finished tile, behind ONE MFMA
-      if constexpr (EPI) {
-        if constexpr (f == 0)
-          prev_epi(ks - BF_EPI_POS, (int)PH, acc[oth], tmp);
-        else
-          epi(f - 1, ks - BF_EPI_POS, (int)PH, acc[oth], tmp);
-      }
-    };
-    if constexpr (i0 % BF_CHUNK == BF_SYNC_POS) bf_sync<S, i0 / BF_CHUNK>(c);
-    const u32x4 a_hi = fr[i0 % S::D];
-    if constexpr (i0 + S::D < S::NFRAG) fr[i0 % S::D] = bf_frag<S>(c, i0 + S::D);
-    const u32x4 a_mid = fr[i1 % S::D];
-    if constexpr (i1 + S::D < S::NFRAG) fr[i1 % S::D] = bf_frag<S>(c, i1 + S::D);
-    const u32x4& b_hi = ks < KSA ? inA_hi[ks < KSA ? ks : 0] : inB_hi[ks < KSA ? 0 : ks - KSA];
-    const u32x4& b_mid = ks < KSA ? inA_mid[ks < KSA ? ks : 0] : inB_mid[ks < KSA ? 0 : ks - KSA];
-    // program order = issue order for one wave per SIMD: every MFMA is followed by its share of vector work, and the fences keep
-    // the compiler from collecting that work into lumps the matrix pipe would have to wait for
-    acc[cur] = bf_mfma(a_mid, b_hi, acc[cur]);
-    phase(std::integral_constant<int, 0>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    acc[cur] = bf_mfma(a_hi, b_mid, acc[cur]);
-    phase(std::integral_constant<int, 1>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    acc[cur] = bf_mfma(a_hi, b_hi, acc[cur]);
-    phase(std::integral_constant<int, 2>{});
-    if constexpr (EPI) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!SPREAD && ks == BF_EPI_POS) {
-      static_for<8>([&](auto P) {
-        static_for<3>([&](auto PH) {
-          if constexpr (f == 0)
-            prev_epi((int)P, (int)PH, acc[oth], tmp);
-          else
-            epi(f - 1, (int)P, (int)PH, acc[oth], tmp);
-        });
-      });
-    }
-    if constexpr (ks == LAST) {
-      if constexpr (f + 1 < NFT)
-        acc[oth] = BT0 >= 0 ? bf_bias_tile(c, BT0 + f + 1) : zero;
-      else if constexpr (NEXT_BT >= 0)
-        acc[oth] = bf_bias_tile(c, NEXT_BT);
-      else
-        acc[oth] = zero;
-    }
-  });
-}
-
 template <bool SAVE>
 __global__ __launch_bounds__(SP_WG, 1) void k_field_fwd_split(const FieldArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   using S = SplitStreamT<SAVE>;
-  BfCtx c;
-  c.wimg = a.wbf;
-  c.lds = lds;
-  c.lds_base = (unsigned)(uintptr_t)(lptr_t)lds;
-  c.lane = threadIdx.x & 63;
-  c.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const BfCtx c = bf_ctx(a.wbf, lds);
   const int lane = c.lane, j = lane & 31, h = lane >> 5;
   const int m = blockIdx.x * (SP_WG / 2) + c.wv * 32 + j;
   const bool valid = m < a.M;
@@ -178,13 +73,8 @@ __global__ __launch_bounds__(SP_WG, 1) void k_field_fwd_split(const FieldArgs a)
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int pi = 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1);
-      float sv = 0.f, cv = 0.f;
-      if (pi < 30) {
-        const int cc = pi / 10, l = pi - 10 * cc;
-        const float x = (cc == 0) ? p[0] : ((cc == 1) ? p[1] : p[2]);
-        sincos_phase(x * __uint_as_float(kFreqPointBits[l]), sv, cv);
-      }
+      float sv, cv;
+      encode_point_pair(p, 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1), sv, cv);
       const HiMid e = split2(sv, cv);
       gp_hi[ks][q] = e.hi;
       gp_mid[ks][q] = e.mid;
@@ -193,13 +83,8 @@ __global__ __launch_bounds__(SP_WG, 1) void k_field_fwd_split(const FieldArgs a)
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int pi = 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1);
-      float sv = 0.f, cv = 0.f;
-      if (pi < 12) {
-        const int cc = pi / 4, l = pi - 4 * cc;
-        const float x = (cc == 0) ? dw[0] : ((cc == 1) ? dw[1] : dw[2]);
-        sincos_phase(x * __uint_as_float(kFreqDirBits[l]), sv, cv);
-      }
+      float sv, cv;
+      encode_dir_pair(dw, 8 * ks + 2 * h + (q & 1) + 4 * (q >> 1), sv, cv);
       const HiMid e = split2(sv, cv);
       gd_hi[ks][q] = e.hi;
       gd_mid[ks][q] = e.mid;
@@ -269,24 +154,24 @@ __global__ __launch_bounds__(SP_WG, 1) void k_field_fwd_split(const FieldArgs a)
   auto e0 = relu_to(Xh, Xm, BS_H0 + 0, 0), e1 = relu_to(Yh, Ym, BS_H0 + 1, 1), e2 = relu_to(Xh, Xm, BS_H0 + 2, 2), e3 = relu_to(Yh, Ym, BS_H0 + 3, 3);
   auto e4 = relu_to(Xh, Xm, BS_H0 + 4, 4), e5 = relu_to(Yh, Ym, BS_H0 + 5, 5), e6 = relu_to(Xh, Xm, BS_H0 + 6, 6), e7 = relu_to(Yh, Ym, BS_H0 + 7, 7);
   auto ec = relu_to(Xh, Xm, BS_C, 8, 4);  // c = relu(dir_info pre-activation): 4 tiles
-  sp_segment<S, BFS_L0, 8, 4, 0, BFB_L0, 0, BFB_L0 + 8>(c, fr, acc, gp_hi, gp_mid, nullptr, nullptr, e0, nothing);
-  sp_segment<S, BFS_L1, 8, 16, 0, BFB_L0 + 8, 0, BFB_L0 + 16>(c, fr, acc, Xh, Xm, nullptr, nullptr, e1, last_of(e0, 7));
-  sp_segment<S, BFS_L1 + 128, 8, 16, 0, BFB_L0 + 16, 0, BFB_L0 + 24>(c, fr, acc, Yh, Ym, nullptr, nullptr, e2, last_of(e1, 7));
-  sp_segment<S, BFS_L1 + 256, 8, 16, 0, BFB_L0 + 24, 0, BFB_L0 + 32>(c, fr, acc, Xh, Xm, nullptr, nullptr, e3, last_of(e2, 7));
-  sp_segment<S, BFS_L4, 8, 16, 4, BFB_L0 + 32, 0, BFB_L0 + 40>(c, fr, acc, Yh, Ym, gp_hi, gp_mid, e4, last_of(e3, 7));
-  sp_segment<S, BFS_L5, 8, 16, 0, BFB_L0 + 40, 0, BFB_L0 + 48>(c, fr, acc, Xh, Xm, nullptr, nullptr, e5, last_of(e4, 7));
-  sp_segment<S, BFS_L5 + 128, 8, 16, 0, BFB_L0 + 48, 0, BFB_L0 + 56>(c, fr, acc, Yh, Ym, nullptr, nullptr, e6, last_of(e5, 7));
-  sp_segment<S, BFS_L5 + 256, 8, 16, 0, BFB_L0 + 56, 0, BFB_SIGMA>(c, fr, acc, Xh, Xm, nullptr, nullptr, e7, last_of(e6, 7));
+  sp_segment<S, FSEG_L0>(c, fr, acc, gp_hi, gp_mid, nullptr, nullptr, e0, nothing);
+  sp_segment<S, FSEG_L1>(c, fr, acc, Xh, Xm, nullptr, nullptr, e1, last_of(e0, 7));
+  sp_segment<S, FSEG_L2>(c, fr, acc, Yh, Ym, nullptr, nullptr, e2, last_of(e1, 7));
+  sp_segment<S, FSEG_L3>(c, fr, acc, Xh, Xm, nullptr, nullptr, e3, last_of(e2, 7));
+  sp_segment<S, FSEG_L4>(c, fr, acc, Yh, Ym, gp_hi, gp_mid, e4, last_of(e3, 7));
+  sp_segment<S, FSEG_L5>(c, fr, acc, Xh, Xm, nullptr, nullptr, e5, last_of(e4, 7));
+  sp_segment<S, FSEG_L6>(c, fr, acc, Yh, Ym, nullptr, nullptr, e6, last_of(e5, 7));
+  sp_segment<S, FSEG_L7>(c, fr, acc, Xh, Xm, nullptr, nullptr, e7, last_of(e6, 7));
   // ---- sigma head (one tile, row 0) on h7: sigma = |w_sigma . h7 + b|  (nerf.py:94, 113-115)
   float spre = 0.f;
   auto sig_epi = [&](int part, int ph, const f32x16& A, EpiTmp&) { if (part == 0 && ph == 0) spre = A[0]; };
-  sp_segment<S, BFS_SIG, 1, 16, 0, BFB_SIGMA, 0, BFB_DIR>(c, fr, acc, Yh, Ym, nullptr, nullptr, nothing_f, last_of(e7, 7));
+  sp_segment<S, FSEG_SIG>(c, fr, acc, Yh, Ym, nullptr, nullptr, nothing_f, last_of(e7, 7));
   // ---- point_info folded into dir_info: c = relu(W_dir[:, :24] gamma_d + W_fold h7 + b_dir + W_dir[:, 24:] b_pi)  (nerf.py:117-118)
-  sp_segment<S, BFS_DIR, 4, 2, 16, BFB_DIR, 1, BFB_COL>(c, fr, acc, gd_hi, gd_mid, Yh, Ym, ec, sig_epi);
+  sp_segment<S, FSEG_DIR>(c, fr, acc, gd_hi, gd_mid, Yh, Ym, ec, sig_epi);
   if (SAVE && valid && h == 0) a.spre[a.row0 + m] = spre;
   if (valid && h == 0) a.sigma[m] = fabsf(spre);
   // ---- colour head: rows 0..2 of one tile, sigmoid (nerf.py:99, 119)
-  sp_segment<S, BFS_COL, 1, 8, 0, BFB_COL, 1, -1>(c, fr, acc, Xh, Xm, nullptr, nullptr, nothing_f, last_of(ec, 3));
+  sp_segment<S, FSEG_COL>(c, fr, acc, Xh, Xm, nullptr, nullptr, nothing_f, last_of(ec, 3));
   if (valid && h == 0) {
     a.rgb[(size_t)m * 3 + 0] = 1.0f / (1.0f + expf(-acc[1][0]));
     a.rgb[(size_t)m * 3 + 1] = 1.0f / (1.0f + expf(-acc[1][1]));
@@ -300,18 +185,11 @@ __global__ __launch_bounds__(SP_WG, 1) void k_field_fwd_split(const FieldArgs a)
 __global__ __launch_bounds__(256) void k_pack_weights_split(const Weights24 w, const float* __restrict__ fold, unsigned char* __restrict__ img) {
   const int gid = blockIdx.x * 256 + threadIdx.x;
   if (gid < BF_NFRAG * 64) {
-    const int step = gid >> 6, lane = gid & 63, i = lane & 31, h = lane >> 5;
-    u32x4 vh, vm;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-      const HiMid e = split2(bf_weight(w, fold, step, i, kk, h), bf_weight(w, fold, step, i, kk + 1, h));
-      vh[q] = e.hi;
-      vm[q] = e.mid;
-    }
+    const int step = gid >> 6, lane = gid & 63;
+    const FragHiMid v = frag_lane_split<32, bf_weight>(w, fold, step, lane);
     unsigned char* dst = img + BF_BIAS_BYTES + (size_t)(2 * step) * BF_FRAG_BYTES + lane * 16;
-    *reinterpret_cast<u32x4*>(dst) = vh;
-    *reinterpret_cast<u32x4*>(dst + BF_FRAG_BYTES) = vm;
+    *reinterpret_cast<u32x4*>(dst) = v.hi;
+    *reinterpret_cast<u32x4*>(dst + BF_FRAG_BYTES) = v.mid;
   } else {
     const int b = gid - BF_NFRAG * 64;
     if (b < BF_BIAS_BYTES / 4) {

@@ -114,30 +114,14 @@ __global__ __launch_bounds__(256) void k_prep_bf16(const PrepArgs a) {
       bool ok = true;
       if (f0 + 3 >= BFS_DIR && f0 < BFS_COL) ok = prep_wait_fold(a);
       if (frag >= BF_NFRAG) return;
-      const int i = lane & 31, h = lane >> 5;
-      u32x4 v = poison;
-      if (ok) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-          v[q] = pack2(bf_weight(a.w, a.fold, frag, i, kk, h), bf_weight(a.w, a.fold, frag, i, kk + 1, h));
-        }
-      }
+      const u32x4 v = ok ? frag_lane_bf16<32, bf_weight>(a.w, a.fold, frag, lane) : poison;
       *reinterpret_cast<u32x4*>(a.img_fwd + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
     } else {
       const int f0 = (gid - threadIdx.x) >> 6;
       bool ok = true;
       if (f0 + 3 >= BXS_DIR && f0 < BXS_COL) ok = prep_wait_fold(a);
       if (frag >= BX_NCHUNK * BF_CHUNK) return;
-      const int i = lane & 15, q = lane >> 4;
-      u32x4 v = poison;
-      if (ok) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int kk = 16 * (e >> 1) + 4 * q + 2 * (e & 1);
-          v[e] = pack2(bx_weight(a.w, a.fold, frag, i, kk), bx_weight(a.w, a.fold, frag, i, kk + 1));
-        }
-      }
+      const u32x4 v = ok ? frag_lane_bf16<16, bx_weight>(a.w, a.fold, frag, lane) : poison;
       *reinterpret_cast<u32x4*>(a.img_fwd + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
     }
     return;
@@ -148,15 +132,7 @@ __global__ __launch_bounds__(256) void k_prep_bf16(const PrepArgs a) {
     bool ok = true;
     if (f0 + 3 >= BBS_FOLDT && f0 < BBS_L7T) ok = prep_wait_fold(a);
     if (frag >= BBF_NCHUNK * BF_CHUNK) return;
-    const int i = lane & 31, h = lane >> 5;
-    u32x4 v = poison;
-    if (ok) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int kk = 4 * h + 2 * (q & 1) + 8 * (q >> 1);
-        v[q] = pack2(bb_weight(a.w, a.fold, frag, i, kk), bb_weight(a.w, a.fold, frag, i, kk + 1));
-      }
-    }
+    const u32x4 v = ok ? frag_lane_bf16<32, bb_weight>(a.w, a.fold, frag, lane) : poison;
     *reinterpret_cast<u32x4*>(a.img_bwd + BF_BIAS_BYTES + (size_t)frag * BF_FRAG_BYTES + lane * 16) = v;
     return;
   }

@@ -1,4 +1,5 @@
-"""CPU checks of the bf16 stream / buffer layout constants in csrc/bf16_common.h and bf16_weights.h: the segment starts
+"""CPU checks of the bf16 stream / buffer layout constants in csrc/bf16_common.h and bf16_weights.h: the segment starts (the rows of
+the two segment tables, from which the header derives its named offsets)
 must be the running sums of (tiles x k-steps) in the order the kernels consume them, the streams must be whole 16-fragment
 chunks (or padded up to one), and the training buffers' per-wave-block sizes must add up.  A silent edit of one constant
 would otherwise only show as wrong numbers on the GPU."""
@@ -17,31 +18,68 @@ def _consts(path):
     return out, txt
 
 
+def _seg_table(txt, table, prefix):
+    """rows (s0, nft, ksa, ksb, bt0, pieces) of a BfSeg table of bf16_common.h, keyed by the row names of its enum (without the prefix)"""
+    body = re.search(r"constexpr BfSeg %s\[\w+\] = \{(.*?)\};" % table, txt, re.S).group(1)
+    rows = [tuple(int(v) for v in m) for m in re.findall(r"\{(-?\d+), (-?\d+), (-?\d+), (-?\d+), (-?\d+), (-?\d+)\}", body)]
+    names = re.findall(r"\b%s([A-Z0-9]+)\b" % prefix, re.search(r"enum \{ (%s[^}]*) \};" % prefix, txt).group(1))
+    assert names[-1] == "N" and len(names) - 1 == len(rows)
+    return dict(zip(names[:-1], rows))
+
+
+def _derived(txt, name, table, row, field="s0"):
+    """the header computes `name` from the table row, not from a literal of its own"""
+    return re.search(r"\b%s = %s\[%s\]\.%s\b" % (name, table, row, field), txt) is not None
+
+
 def test_forward_stream_32x32x16():
-    c, _ = _consts(os.path.join(CSRC, "bf16_common.h"))
+    c, txt = _consts(os.path.join(CSRC, "bf16_common.h"))
+    t = _seg_table(txt, "kFwdSegs", "FSEG_")
     # point_info is folded into dir_info: the sigma head is a tile of its own on h7, dir_info reads gamma_d (2) + h7 (16)
-    segs = [("BFS_L0", 8 * 4), ("BFS_L1", 3 * 8 * 16), ("BFS_L4", 8 * 20), ("BFS_L5", 3 * 8 * 16), ("BFS_SIG", 1 * 16),
-            ("BFS_DIR", 4 * 18), ("BFS_COL", 1 * 8)]
-    pos = 0
-    for name, n in segs:
-        assert c[name] == pos, name
-        pos += n
-    assert c["BF_NFRAG"] == pos == 1056 and pos % c["BF_CHUNK"] == 0
+    want = [("L0", 8, 4, 0), ("L1", 8, 16, 0), ("L2", 8, 16, 0), ("L3", 8, 16, 0), ("L4", 8, 16, 4), ("L5", 8, 16, 0), ("L6", 8, 16, 0),
+            ("L7", 8, 16, 0), ("SIG", 1, 16, 0), ("DIR", 4, 2, 16), ("COL", 1, 8, 0)]
+    assert list(t) == [w[0] for w in want]
+    pos = tiles = 0
+    start = {}
+    for name, nft, ksa, ksb in want:
+        s0, r_nft, r_ksa, r_ksb, bt0, pieces = t[name]
+        assert (s0, r_nft, r_ksa, r_ksb, bt0) == (pos, nft, ksa, ksb, tiles), name  # starts and bias tiles are running sums
+        assert pieces == (2 * nft if nft > 1 else 0), name                            # a ReLU layer's output: two 1-KiB pieces per tile
+        start[name] = pos
+        pos += nft * (ksa + ksb)
+        tiles += nft
+    segs = [("BFS_L0", "L0", 0), ("BFS_L1", "L1", 32), ("BFS_L4", "L4", 416), ("BFS_L5", "L5", 576), ("BFS_SIG", "SIG", 960),
+            ("BFS_DIR", "DIR", 976), ("BFS_COL", "COL", 1048)]
+    for cname, row, at in segs:
+        assert start[row] == at and _derived(txt, cname, "kFwdSegs", "FSEG_" + row), cname
+    assert re.search(r"BF_NFRAG = bf_seg_end\(kFwdSegs\[FSEG_N - 1\]\)", txt) and pos == 1056 and pos % c["BF_CHUNK"] == 0
+    assert "static_assert(bf_segs_tile(kFwdSegs, FSEG_N, BF_NFRAG)" in txt
     # bias tiles: 8 layers x 8, sigma 1, dir 4, colour 1
-    assert (c["BFB_L0"], c["BFB_SIGMA"], c["BFB_DIR"], c["BFB_COL"], c["BF_NBIAS_TILES"]) == (0, 64, 65, 69, 70)
-    assert c["BF_NBIAS_TILES"] * 32 * 4 <= c["BF_BIAS_BYTES"]
+    assert (t["L0"][4], t["SIG"][4], t["DIR"][4], t["COL"][4], tiles) == (0, 64, 65, 69, 70)
+    for cname, row in (("BFB_L0", "L0"), ("BFB_SIGMA", "SIG"), ("BFB_DIR", "DIR"), ("BFB_COL", "COL")):
+        assert _derived(txt, cname, "kFwdSegs", "FSEG_" + row, "bt0"), cname
+    assert "BF_NBIAS_TILES = BFB_COL + kFwdSegs[FSEG_COL].nft" in txt
+    assert tiles * 32 * 4 <= c["BF_BIAS_BYTES"]
 
 
 def test_backward_stream():
-    c, _ = _consts(os.path.join(CSRC, "bf16_common.h"))
-    segs = [("BBS_COLT", 4 * 4), ("BBS_FOLDT", 8 * 9), ("BBS_L7T", 3 * 8 * 16), ("BBS_L4T", 8 * 16),
-            ("BBS_L3T", 3 * 8 * 16), ("BBS_G0T", 2 * 32)]
+    _, txt = _consts(os.path.join(CSRC, "bf16_common.h"))
+    t = _seg_table(txt, "kBwdSegs", "BSEG_")
+    want = [("COLT", 4, 4, 0, 8), ("FOLDT", 8, 8, 1, 16)] + [("L%dT" % l, 8, 16, 0, 16) for l in range(7, 0, -1)] + [("G0T", 2, 16, 16, 0)]
+    assert list(t) == [w[0] for w in want]
     pos = 0
-    for name, n in segs:
-        assert c[name] == pos, name
-        pos += n
-    assert c["BBC_NFRAG"] == c["BBS_G0T"] == 984  # the coarse pass stops in front of the d gamma_p segments
-    assert c["BBF_NFRAG"] == pos == 1048
+    start = {}
+    for name, nft, ksa, ksb, pieces in want:
+        assert t[name] == (pos, nft, ksa, ksb, -1, pieces), name  # no biases in the chain
+        start[name] = pos
+        pos += nft * (ksa + ksb)
+    segs = [("BBS_COLT", "COLT", 0), ("BBS_FOLDT", "FOLDT", 16), ("BBS_L7T", "L7T", 88), ("BBS_L4T", "L4T", 472), ("BBS_L3T", "L3T", 600),
+            ("BBS_G0T", "G0T", 984)]
+    for cname, row, at in segs:
+        assert start[row] == at and _derived(txt, cname, "kBwdSegs", "BSEG_" + row), cname
+    # the coarse pass stops in front of the d gamma_p segments
+    assert "BBC_NFRAG = BBS_G0T, BBF_NFRAG = bf_seg_end(kBwdSegs[BSEG_G0T])" in txt and start["G0T"] == 984 and pos == 1048
+    assert "bf_segs_tile(kBwdSegs, BSEG_G0T, BBC_NFRAG) && bf_segs_tile(kBwdSegs, BSEG_N, BBF_NFRAG)" in txt
 
 
 def test_forward_stream_16x16x32():
