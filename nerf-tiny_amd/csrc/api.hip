@@ -34,9 +34,6 @@ int check_sizes(int B, int Nc, int Nf) {
 // wave blocks (32 samples) of one pass of the bf16 kernels: whole 256-sample workgroups
 size_t wave_blocks(int B, int N) { return (((size_t)B * N + 255) / 256) * 8; }
 
-// bf16 weight-gradient phase: all products in one or two launches (dw_bf16.hip: k_dw_bf16_multi) up to this many wave blocks -- where the
-// per-product launches' slabs (219 MB per step whatever the batch) and launch boundaries weigh -- and a launch per product beyond.
-// NERF_DW_BF16_MULTI=0 / 1 overrides the choice (A/B measurements only).
 // NERF_PREP_BF16=0: the bf16 paths prepare with separate launches (fold, pack, rays; the backward packs its own image) as up to round 3
 // (A/B measurements only)
 bool prep_bf16_disabled() {
@@ -57,11 +54,6 @@ constexpr int FUSE_RAYS_BF16_MAX_RAYS = 512;
 bool fuse_rays_bf16(int B) {
   static const int forced = [] { const char* e = getenv("NERF_FUSE_RAYS"); return e ? atoi(e) : -1; }();
   return forced >= 0 ? forced != 0 : B <= FUSE_RAYS_BF16_MAX_RAYS;
-}
-constexpr int DW_BF16_MULTI_MAX_WB = 5120;  // 853 rays x (64 + 128); measured: 400 rays -25 %, 512 -18 %, 1024 +-0, 2048 +10 %, 4096 +30 %
-bool dw_bf16_multi(int wb_tot) {
-  static const int forced = [] { const char* e = getenv("NERF_DW_BF16_MULTI"); return e ? atoi(e) : -1; }();
-  return forced >= 0 ? forced != 0 : wb_tot <= DW_BF16_MULTI_MAX_WB;
 }
 
 
@@ -634,160 +626,15 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   { ProfScope ps(NERF_HIP_K_BWD_FIELD_COARSE, st, &pc); HIP_TRY(chain(fb, false)); }
 
   // 5. weight gradients: dW = G^T X over all B*(Nc+Nf) samples
-  // the bf16 products over a pair of fragment-layout buffers (layer inputs `bs`, pre-activation gradients `bg`) into the 24 gradient tensors `dwp`
-  // and the folded product's M (`mbuf`); `fold`: finish with k_fold_grads.  `sp` != {0, 0}: the split-fp32 train step -- `bs` / `bg` hold the hi
-  // parts, the mid parts lie sp.xdelta / sp.gdelta bytes behind, and every product is formed as hi x hi + hi x mid + mid x hi in ONE pass.
-  auto dw_bf16_phase = [&](const unsigned char* bs, const unsigned char* bg, float* const* dwp, float* mbuf, void* ev, bool fold, DwBfSplit sp) -> int {
-    float* slabs = at<float>(ws, L.bslabs);
-    const float* const slab_limit = slabs + dw_bf16_slab_floats();  // checked by launch_dw_bf16_multi before it enqueues anything
-    auto X = [&](int t) { return bs + (size_t)wb_tot * bs_cum(t) * BF_FRAG_BYTES; };
-    auto Gt = [&](int t) { return bg + (size_t)wb_tot * bg_cum(t) * BF_FRAG_BYTES; };
-    int ns = 0;
-    // every product writes its own slab region; ONE launch sums them all at the end
-    DwBfReduceBatch rb;
-    memset(&rb, 0, sizeof(rb));
-    auto red = [&](const float* sl, int nslab, int rows, int ni, int o_first, int o_count, int i_first, int i_count, float* dW, int ldw, int col0, float* db) {
-      DwBfReduceArgs& r = rb.r[rb.n++];
-      r.slabs = sl; r.nslab = nslab; r.rows = rows; r.ni = ni; r.o_first = o_first; r.o_count = o_count; r.i_first = i_first; r.i_count = i_count;
-      r.dW = dW; r.ldw = ldw; r.col0 = col0; r.db = db;
-    };
-    if (dw_bf16_multi(wb_tot)) {
-      // SMALL batch (a rank's share of a strong-scaling step, the reference's 400-ray batch): all products of the early part in ONE
-      // launch and all of the late part in another (ONE launch for everything without an early event), the workgroups dealt out in
-      // proportion to the products' bytes: a quarter of the slab traffic, three or four launch boundaries fewer, long streams
-      static const int layers[6] = {1, 2, 3, 5, 6, 7};
-      DwBfProd pr[10];
-      memset(pr, 0, sizeof(pr));
-      int n = 0;
-      pr[n++] = DwBfProd{Gt(BG_L0), 16, X(BS_GP), 4, nullptr, 0, nullptr, nullptr, 0};                                   // 0: layer 0 (X = gamma_p)
-      for (int k = 0; k < 6; ++k) pr[n++] = DwBfProd{Gt(BG_L0 + layers[k]), 16, X(BS_H0 + layers[k] - 1), 16, nullptr, 0, nullptr, nullptr, 0};  // 1..6
-      pr[n++] = DwBfProd{Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, nullptr, 0};                        // 7: layer 4, X = [h3 | gamma_p]
-      const int n_early = n;
-      pr[n++] = DwBfProd{Gt(BG_D), 8, X(BS_GD), 2, X(BS_H0 + 7), 16, Gt(BG_Z), nullptr, 0};                              // 8: folded dir_info product + sigma head
-      pr[n++] = DwBfProd{Gt(BG_Z), 2, X(BS_C), 8, nullptr, 0, nullptr, nullptr, 0};                                       // 9: colour head
-      auto early_reds = [&]() {
-        red(pr[0].slabs, pr[0].nslab, 256, 64, 0, 256, 0, POINT_DIM, dwp[0], POINT_DIM, 0, dwp[1]);
-        for (int k = 0; k < 6; ++k) red(pr[1 + k].slabs, pr[1 + k].nslab, 256, 256, 0, 256, 0, WIDTH, dwp[2 * layers[k]], WIDTH, 0, dwp[2 * layers[k] + 1]);
-        red(pr[7].slabs, pr[7].nslab, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
-      };
-      auto late_reds = [&]() {
-        red(pr[8].slabs, pr[8].nslab, 160, 288, 0, HALF, 0, DIR_DIM, dwp[W_DIR], WIDTH + DIR_DIM, 0, dwp[B_DIR]);
-        red(pr[8].slabs, pr[8].nslab, 160, 288, 0, HALF, 32, WIDTH, mbuf, WIDTH, 0, nullptr);
-        red(pr[8].slabs, pr[8].nslab, 160, 288, HALF + 3, 1, 32, WIDTH, dwp[W_SIGMA], WIDTH, 0, nullptr);
-        red(pr[9].slabs, pr[9].nslab, 32, 128, 0, 3, 0, HALF, dwp[W_COLOR], HALF, 0, dwp[B_COLOR]);
-        red(pr[9].slabs, pr[9].nslab, 32, 128, 3, 1, 0, 0, nullptr, 0, 0, dwp[B_SIGMA]);
-      };
-      float* end = slabs;
-      if (ev) {
-        HIP_TRY(launch_dw_bf16_multi(pr, n_early, wb_tot, slabs, slab_limit, &end, st, sp));
-        early_reds();
-        HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
-        HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev), st));
-        rb.n = 0;
-        HIP_TRY(launch_dw_bf16_multi(pr + n_early, n - n_early, wb_tot, end, slab_limit, &end, st, sp));
-        late_reds();
-      } else {
-        HIP_TRY(launch_dw_bf16_multi(pr, n, wb_tot, slabs, slab_limit, &end, st, sp));
-        early_reds();
-        late_reds();
-      }
-      HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
-      FoldGradArgs fg;
-      fg.M = mbuf; fg.db_dir = dwp[B_DIR]; fg.w_dir = w.p[W_DIR]; fg.w_pi = w.p[W_PI]; fg.b_pi = w.p[B_PI];
-      fg.dW_pi = dwp[W_PI]; fg.db_pi = dwp[B_PI]; fg.dW_dir = dwp[W_DIR];
-      if (fold) HIP_TRY(launch_fold_grads(fg, st));
-      return NERF_HIP_OK;
-    }
-    // LARGE batches, the products with SMALL blocks (layer 0: 20 KiB per wave block, the folded dir_info product 28, the colour head 10): alone
-    // in a launch each is paced by the ring's per-block latency (3.4 / 4.3 / 3.8 TB/s against the 5.8 of the 256 x 256 products:
-    // profiles/r03_train_bf16_pmc.json); sharing ONE launch (k_dw_bf16_multi, workgroups dealt out by cost) their streams overlap.
-    // The six 256 x 256 products, then {layer 4, layer 0, folded, colour} in one launch; measured (weight-gradient phase) against a launch
-    // each: 2,048 rays 0.767 -> 0.707 ms, 4,096 rays 1.375 -> 1.36 (layer 4 in a launch of its own: +-0).
-    // Without an early event only (the overlap needs layer 0 in front of the event and the other two behind it).
-    if (!ev) {
-      static const int layers[6] = {1, 2, 3, 5, 6, 7};
-      const unsigned char* Gs[6];
-      const unsigned char* Xs[6];
-      for (int k = 0; k < 6; ++k) { Gs[k] = Gt(BG_L0 + layers[k]); Xs[k] = X(BS_H0 + layers[k] - 1); }
-      HIP_TRY(launch_dw_bf16_group(Gs, Xs, 6, wb_tot, slabs, &ns, st, sp));
-      for (int k = 0; k < 6; ++k)
-        red(slabs + (size_t)k * ns * 256 * 257, ns, 256, 256, 0, 256, 0, WIDTH, dwp[2 * layers[k]], WIDTH, 0, dwp[2 * layers[k] + 1]);
-      slabs += (size_t)6 * ns * 256 * 257;
-      DwBfProd pr[4] = {
-          DwBfProd{Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, nullptr, 0},       // 0: layer 4, X = [h3 | gamma_p]
-          DwBfProd{Gt(BG_L0), 16, X(BS_GP), 4, nullptr, 0, nullptr, nullptr, 0},                  // 1: layer 0 (X = gamma_p)
-          DwBfProd{Gt(BG_D), 8, X(BS_GD), 2, X(BS_H0 + 7), 16, Gt(BG_Z), nullptr, 0},             // 2: folded dir_info product + sigma head
-          DwBfProd{Gt(BG_Z), 2, X(BS_C), 8, nullptr, 0, nullptr, nullptr, 0}};                    // 3: colour head
-      float* end = slabs;
-      HIP_TRY(launch_dw_bf16_multi(pr, 4, wb_tot, slabs, slab_limit, &end, st, sp));
-      red(pr[0].slabs, pr[0].nslab, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
-      red(pr[1].slabs, pr[1].nslab, 256, 64, 0, 256, 0, POINT_DIM, dwp[0], POINT_DIM, 0, dwp[1]);
-      red(pr[2].slabs, pr[2].nslab, 160, 288, 0, HALF, 0, DIR_DIM, dwp[W_DIR], WIDTH + DIR_DIM, 0, dwp[B_DIR]);
-      red(pr[2].slabs, pr[2].nslab, 160, 288, 0, HALF, 32, WIDTH, mbuf, WIDTH, 0, nullptr);
-      red(pr[2].slabs, pr[2].nslab, 160, 288, HALF + 3, 1, 32, WIDTH, dwp[W_SIGMA], WIDTH, 0, nullptr);
-      red(pr[3].slabs, pr[3].nslab, 32, 128, 0, 3, 0, HALF, dwp[W_COLOR], HALF, 0, dwp[B_COLOR]);
-      red(pr[3].slabs, pr[3].nslab, 32, 128, 3, 1, 0, 0, nullptr, 0, 0, dwp[B_SIGMA]);
-      HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
-      FoldGradArgs fg;
-      fg.M = mbuf; fg.db_dir = dwp[B_DIR]; fg.w_dir = w.p[W_DIR]; fg.w_pi = w.p[W_PI]; fg.b_pi = w.p[B_PI];
-      fg.dW_pi = dwp[W_PI]; fg.db_pi = dwp[B_PI]; fg.dW_dir = dwp[W_DIR];
-      if (fold) HIP_TRY(launch_fold_grads(fg, st));
-      return NERF_HIP_OK;
-    }
-    // layer 0: X = gamma_p
-    HIP_TRY(launch_dw_bf16_gemm(Gt(BG_L0), 16, X(BS_GP), 4, nullptr, 0, nullptr, wb_tot, slabs, &ns, st, sp));
-    red(slabs, ns, 256, 64, 0, 256, 0, POINT_DIM, dwp[0], POINT_DIM, 0, dwp[1]);
-    slabs += (size_t)ns * 256 * 65;
-    {  // layers 1, 2, 3, 5, 6, 7: six 256 x 256 products in ONE launch (42 workgroups each: a sixth of the slab traffic)
-      static const int layers[6] = {1, 2, 3, 5, 6, 7};
-      const unsigned char* Gs[6];
-      const unsigned char* Xs[6];
-      for (int k = 0; k < 6; ++k) { Gs[k] = Gt(BG_L0 + layers[k]); Xs[k] = X(BS_H0 + layers[k] - 1); }
-      HIP_TRY(launch_dw_bf16_group(Gs, Xs, 6, wb_tot, slabs, &ns, st, sp));
-      for (int k = 0; k < 6; ++k)
-        red(slabs + (size_t)k * ns * 256 * 257, ns, 256, 256, 0, 256, 0, WIDTH, dwp[2 * layers[k]], WIDTH, 0, dwp[2 * layers[k] + 1]);
-      slabs += (size_t)6 * ns * 256 * 257;
-    }
-    // layer 4: one pass over dpre4 for both column groups of the [256][316] matrix: X = [h3 | gamma_p]
-    HIP_TRY(launch_dw_bf16_gemm(Gt(BG_L0 + 4), 16, X(BS_H0 + 3), 16, X(BS_GP), 4, nullptr, wb_tot, slabs, &ns, st, sp));
-    red(slabs, ns, 256, 320, 0, 256, 0, WIDTH + POINT_DIM, dwp[8], WIDTH + POINT_DIM, 0, dwp[9]);
-    slabs += (size_t)ns * 256 * 321;
-    if (ev) {  // point_layer[0..7] are complete here: their sums go out now, the rest of the products follow the event
-      HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
-      HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev), st));
-      rb.n = 0;
-    }
-    // point_info folded into dir_info (bf16_common.h): ONE product dpre_dir^T [gamma_d | h7] -- columns 0..23 are dir_info's direction
-    // columns, columns 32.. are M = dpre_dir^T h7 (-> k_fold_grads below) -- and in the same pass over h7 the sigma head: row 3 of h7^T (dz, dspre)
-    HIP_TRY(launch_dw_bf16_gemm(Gt(BG_D), 8, X(BS_GD), 2, X(BS_H0 + 7), 16, Gt(BG_Z), wb_tot, slabs, &ns, st, sp));
-    red(slabs, ns, 160, 288, 0, HALF, 0, DIR_DIM, dwp[W_DIR], WIDTH + DIR_DIM, 0, dwp[B_DIR]);
-    red(slabs, ns, 160, 288, 0, HALF, 32, WIDTH, mbuf, WIDTH, 0, nullptr);
-    red(slabs, ns, 160, 288, HALF + 3, 1, 32, WIDTH, dwp[W_SIGMA], WIDTH, 0, nullptr);
-    slabs += (size_t)ns * 160 * 289;
-    // colour head = rows 0..2 of the (dz, dspre) tile against c; row 3 of its column sums = the sigma bias gradient
-    HIP_TRY(launch_dw_bf16_gemm(Gt(BG_Z), 2, X(BS_C), 8, nullptr, 0, nullptr, wb_tot, slabs, &ns, st, sp));
-    red(slabs, ns, 32, 128, 0, 3, 0, HALF, dwp[W_COLOR], HALF, 0, dwp[B_COLOR]);
-    red(slabs, ns, 32, 128, 3, 1, 0, 0, nullptr, 0, 0, dwp[B_SIGMA]);
-    HIP_TRY(launch_dw_bf16_reduce_batch(rb, st));
-    {
-      FoldGradArgs fg;
-      fg.M = mbuf; fg.db_dir = dwp[B_DIR]; fg.w_dir = w.p[W_DIR]; fg.w_pi = w.p[W_PI]; fg.b_pi = w.p[B_PI];
-      fg.dW_pi = dwp[W_PI]; fg.db_pi = dwp[B_PI]; fg.dW_dir = dwp[W_DIR];
-      if (fold) HIP_TRY(launch_fold_grads(fg, st));
-    }
-    return NERF_HIP_OK;
-  };
-  if (bf16) {
-    ProfScope ps(NERF_HIP_K_BWD_DW, st, &pc);
-    if (int rc = dw_bf16_phase(at<unsigned char>(ws, L.bsave), at<unsigned char>(ws, L.bG), dw, at<float>(ws, L.mbuf), early_event, true, DwBfSplit{})) return rc;
-  } else if (split) {
+  if (bf16 || split) {
+    // every product of the step over the fragment-layout buffers, their slab sums and k_fold_grads: dw_bf16.hip.
     // split-fp32 train step: G = G_hi + G_mid, X = X_hi + X_mid (bf16 parts, fragment layout): G^T X = G_hi^T X_hi + G_hi^T X_mid + G_mid^T X_hi
-    // + O(2^-16), formed block by block inside the two-part instantiations of the bf16 products (dw_bf16.hip): ONE pass over the four buffers
+    // + O(2^-16), formed block by block inside the two-part instantiations of the bf16 products: ONE pass over the four buffers
     ProfScope ps(NERF_HIP_K_BWD_DW, st, &pc);
     DwBfSplit sp;
-    sp.xdelta = (long long)L.bsave2 - (long long)L.bsave;
-    sp.gdelta = (long long)L.bG2 - (long long)L.bG;
-    if (int rc = dw_bf16_phase(at<unsigned char>(ws, L.bsave), at<unsigned char>(ws, L.bG), dw, at<float>(ws, L.mbuf), early_event, true, sp)) return rc;
+    if (split) { sp.xdelta = (long long)L.bsave2 - (long long)L.bsave; sp.gdelta = (long long)L.bG2 - (long long)L.bG; }
+    HIP_TRY(launch_dw_bf16_phase(at<unsigned char>(ws, L.bsave), at<unsigned char>(ws, L.bG), wb_tot, dw, at<float>(ws, L.mbuf), at<float>(ws, L.bslabs),
+                                 dw_bf16_slab_floats(), w, early_event, sp, st));
   } else {
     ProfScope ps(NERF_HIP_K_BWD_DW, st, &pc);
     DwBatch batch;
@@ -816,10 +663,7 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
       HIP_TRY(launch_dw(batch, Mtot, slabs, st));
       HIP_TRY(launch_dw_reduce(batch, st));
     }
-    FoldGradArgs fg;
-    fg.M = at<float>(ws, L.mbuf); fg.db_dir = dw[B_DIR]; fg.w_dir = w.p[W_DIR]; fg.w_pi = w.p[W_PI]; fg.b_pi = w.p[B_PI];
-    fg.dW_pi = dw[W_PI]; fg.db_pi = dw[B_PI]; fg.dW_dir = dw[W_DIR];
-    HIP_TRY(launch_fold_grads(fg, st));
+    HIP_TRY(launch_fold_grads(fold_grad_args(w, dw, at<float>(ws, L.mbuf)), st));
     // direction-encoding columns of dir_info (per-ray sums)
     SmallGradArgs sg;
     memset(&sg, 0, sizeof(sg));

@@ -12,11 +12,12 @@
 //     64 different banks in every transposed read (unswizzled: 4-way conflicts);
 //   * per block and wave: 2 k-steps x (1 A fragment + NIT B fragments), 2 transposed reads each, NIT (+1: bias
 //     gradient = G^T . ones) MFMAs per k-step; accumulators (NIT x 16 fp32 registers) persist over the whole share;
-//   * the per-workgroup partial sums go to a slab and are added up in workgroup order by k_dw_bf16_reduce: the result
+//   * the per-workgroup partial sums go to a slab and are added up in workgroup order by k_dw_bf16_reduce_batch: the result
 //     does not depend on timing.
 // The kernel is HBM-bound by construction (1 KiB of operands per 128 kFLOP): it is paced by the ring, not by the MFMAs.
 #include "bf16_stream.h"
 
+#include <stdlib.h>
 #include <string.h>
 
 namespace nerf {
@@ -248,42 +249,17 @@ __global__ __launch_bounds__(BF_WG, 1) void k_dw_bf16_multi(const DwBfMulti m) {
   }
 }
 
-// 64 output elements per block; the slabs are split over 4 thread groups whose partial sums are added in a fixed order
-__global__ __launch_bounds__(256) void k_dw_bf16_reduce(const DwBfReduceArgs a) {
-  __shared__ float part[4][64];
-  const int ld = a.ni + 1;
-  const int e = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int idx = blockIdx.x * 64 + e;
-  const bool in_range = idx < a.o_count * ld;
-  const int o = in_range ? idx / ld : 0, i = in_range ? idx - o * ld : 0;
-  const bool wanted = in_range && ((i < a.ni && i >= a.i_first && i < a.i_first + a.i_count && a.dW != nullptr) || (i == a.ni && a.db != nullptr));
-  float s = 0.f;
-  if (wanted) {
-    const float* p = a.slabs + (size_t)(a.o_first + o) * ld + i;
-    const size_t stride = (size_t)a.rows * ld;
-    const int per = (a.nslab + 3) / 4, k0 = grp * per, k1 = min(a.nslab, k0 + per);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int k = k0;
-    for (; k + 3 < k1; k += 4) {
-      s0 += p[(size_t)k * stride];
-      s1 += p[(size_t)(k + 1) * stride];
-      s2 += p[(size_t)(k + 2) * stride];
-      s3 += p[(size_t)(k + 3) * stride];
-    }
-    for (; k < k1; ++k) s0 += p[(size_t)k * stride];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  part[grp][e] = s;
-  __syncthreads();
-  if (grp == 0 && wanted) {
-    const float t = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
-    if (i == a.ni)
-      a.db[o] = t;
-    else
-      a.dW[(size_t)o * a.ldw + a.col0 + (i - a.i_first)] = t;
-  }
-}
+// dW[o][col0 + i - i_first] = sum over slabs of row o_first + o, column i; db[o] likewise from the last slab column
+struct DwBfReduceArgs {
+  const float* slabs;
+  int nslab, rows, ni;          // slab = [rows][ni + 1]
+  int o_first, o_count, i_first, i_count;   // slab columns [i_first, i_first + i_count) -> dW columns col0 ..
+  float* dW; int ldw, col0;
+  float* db;                    // or null
+};
+struct DwBfReduceBatch { DwBfReduceArgs r[16]; int n; };
 
+// 64 output elements per block; the slabs are split over 4 thread groups whose partial sums are added in a fixed order.
 // ONE launch for all slab sums of a step: blockIdx.y = descriptor (the thirteen per-product launches cost 90 us per step in launch
 // gaps and tiny grids -- a quarter of the weight-gradient phase of a 512-ray step)
 __global__ __launch_bounds__(256) void k_dw_bf16_reduce_batch(const DwBfReduceBatch b) {
@@ -323,21 +299,108 @@ __global__ __launch_bounds__(256) void k_dw_bf16_reduce_batch(const DwBfReduceBa
   }
 }
 
-hipError_t launch_dw_bf16_reduce_batch(const DwBfReduceBatch& b, hipStream_t st) {
-  int most = 1;
-  for (int k = 0; k < b.n; ++k) {
-    const int blocks = (b.r[k].o_count * (b.r[k].ni + 1) + 63) / 64;
-    most = blocks > most ? blocks : most;
-  }
-  hipLaunchKernelGGL(k_dw_bf16_reduce_batch, dim3(most, b.n), dim3(256), 0, st, b);
-  return hipGetLastError();
+// ---- host side: the products of a step as ONE table; launches, reduce descriptors and the slab space all come from it -------------
+// One output of a product: slab rows [o_first, o_first + o_count), columns [i_first, i_first + i_count) -> tensor `dst` [o][col0 + i] of
+// row length ldw, and the last slab column (the sums of G) -> tensor `bias`.  Tensors: 0..23 = the gradient tensors, DWB_MBUF = the
+// folded product's M, -1 = none.  (o_count = 0: no such output.)
+constexpr int DWB_MBUF = 24;
+struct DwbOut { int o_first, o_count, i_first, i_count, dst, ldw, col0, bias; };
+struct DwbProd {
+  int g, g_ks;                 // gradient tensor (BG_*) and its pieces per wave block
+  int x1, x1_ks, x2, x2_ks;    // input tensors (BS_*): the i index runs over X1's pieces, then X2's (x2 = -1: none)
+  bool z;                      // BG_Z rides along: X^T Z in 32 extra slab rows (the sigma head, on the product whose X2 is h7)
+  int pct;                     // cost of a KiB of this product in a multi launch, in per cent of a 256 x 256 product's (see DwbPhase::multi)
+  bool early;                  // its outputs are tensors of point_layer[0..7]: final before the early event
+  DwbOut out[3];
+  constexpr int nit() const { return (x1_ks + x2_ks) / 2; }
+  constexpr int kind() const { return 2 * nit() + (z ? 1 : 0); }          // DwBfMulti::kind
+  constexpr int kib() const { return g_ks + x1_ks + x2_ks + (z ? 2 : 0); }  // read per wave block
+  constexpr int o_tiles() const { return (g_ks + 1) / 2; }
+  constexpr int z_tile0() const { return z ? x1_ks / 2 : 0; }             // Z multiplies the X2 tiles
+  constexpr int rows() const { return o_tiles() * 32 + (z ? 32 : 0); }
+  constexpr int ni() const { return nit() * 32; }
+  constexpr size_t slab_floats() const { return (size_t)rows() * (ni() + 1); }  // per workgroup
+};
+constexpr DwbProd dwb_prod(int g, int x1, int x2, bool z, int pct, bool early, DwbOut o0, DwbOut o1 = {}, DwbOut o2 = {}) {
+  return DwbProd{g, bg_ks(g), x1, bs_ks(x1), x2, x2 < 0 ? 0 : bs_ks(x2), z, pct, early, {o0, o1, o2}};
 }
+constexpr DwbProd dwb_layer(int l) {  // a 256 x 256 layer on the previous layer's output
+  return dwb_prod(BG_L0 + l, BS_H0 + l - 1, -1, false, 100, true, {0, WIDTH, 0, WIDTH, 2 * l, WIDTH, 0, 2 * l + 1});
+}
+// The costs: a product's small blocks are paced by the ring's per-block latency, so its KiB weigh more than those of the 256 x 256 products
+// (profiles/r03_train_bf16_pmc.json: those stream at 5.8 TB/s, layer 4 5.4, the folded product 4.3, the colour head 3.8, layer 0 3.4).
+enum { DWP_L0, DWP_L1, DWP_L2, DWP_L3, DWP_L5, DWP_L6, DWP_L7, DWP_L4, DWP_FOLD, DWP_COL, DWP_N };
+constexpr DwbProd kDwbProds[DWP_N] = {
+    dwb_prod(BG_L0, BS_GP, -1, false, 170, true, {0, WIDTH, 0, POINT_DIM, W_L0, POINT_DIM, 0, B_L0}),  // layer 0: X = gamma_p
+    dwb_layer(1), dwb_layer(2), dwb_layer(3), dwb_layer(5), dwb_layer(6), dwb_layer(7),
+    // layer 4: one pass over dpre4 for both column groups of the [256][316] matrix, X = [h3 | gamma_p]
+    dwb_prod(BG_L0 + 4, BS_H0 + 3, BS_GP, false, 107, true, {0, WIDTH, 0, WIDTH + POINT_DIM, 8, WIDTH + POINT_DIM, 0, 9}),
+    // point_info folded into dir_info (bf16_common.h): ONE product dpre_dir^T [gamma_d | h7] -- columns 0..23 are dir_info's direction
+    // columns, columns 32.. are M = dpre_dir^T h7 (-> k_fold_grads) -- and in the same pass over h7 the sigma head: row 3 of h7^T (dz, dspre)
+    dwb_prod(BG_D, BS_GD, BS_H0 + 7, true, 135, false, {0, HALF, 0, DIR_DIM, W_DIR, WIDTH + DIR_DIM, 0, B_DIR},
+             {0, HALF, 32, WIDTH, DWB_MBUF, WIDTH, 0, -1}, {HALF + 3, 1, 32, WIDTH, W_SIGMA, WIDTH, 0, -1}),
+    // colour head = rows 0..2 of the (dz, dspre) tile against c; row 3 of its column sums = the sigma bias gradient
+    dwb_prod(BG_Z, BS_C, -1, false, 150, false, {0, 3, 0, HALF, W_COLOR, HALF, 0, B_COLOR}, {3, 1, 0, 0, -1, 0, 0, B_SIGMA}),
+};
 
-// every product of a step keeps its own slabs (ONE reduce launch at the end): layer 0, the six grouped 256 x 256 products, layer 4, the
-// folded dpre_dir product with the sigma rows, the colour head
-size_t dw_bf16_slab_floats() {
-  return (size_t)DWB_WGS * 256 * 65 + (size_t)6 * (DWB_WGS / 6) * 256 * 257 + (size_t)DWB_WGS * 256 * 321 + (size_t)DWB_WGS * 160 * 289 + (size_t)DWB_WGS * 32 * 129;
+// The three launch structures, each a list of table rows and the launcher it goes through (DwbPhase below):
+//  * SMALL batches: every product in one multi launch; with an early event the early ones in one and the rest in another;
+//  * LARGE batches: the six 256 x 256 products as a group (42 workgroups each: a sixth of the slab traffic), then the products with small
+//    blocks in one multi launch, where their streams overlap (weight-gradient phase against a launch each: 2,048 rays 0.767 -> 0.707 ms,
+//    4,096 rays 1.375 -> 1.36; layer 4 in a launch of its own: +-0);
+//  * LARGE batches with an early event (it needs layer 0 in front of the event and the folded product and the colour head behind it): a
+//    launch per product around the group -- DWP_L0, kDwbGroup, DWP_L4, <event>, DWP_FOLD, DWP_COL.
+constexpr int kDwbSmall[DWP_N] = {DWP_L0, DWP_L1, DWP_L2, DWP_L3, DWP_L5, DWP_L6, DWP_L7, DWP_L4, DWP_FOLD, DWP_COL};
+constexpr int DWB_SMALL_EARLY = 8;  // the early products of kDwbSmall come first
+constexpr int DWB_NGROUP = 6, DWB_GROUP_WGS = DWB_WGS / DWB_NGROUP;
+constexpr int kDwbGroup[DWB_NGROUP] = {DWP_L1, DWP_L2, DWP_L3, DWP_L5, DWP_L6, DWP_L7};
+constexpr int kDwbLargeRest[4] = {DWP_L4, DWP_L0, DWP_FOLD, DWP_COL};
+
+// the instantiated forms (NIT, HAS_Z); k_dw_bf16_multi's switch lists the same five
+#define DWB_FORMS(F) F(10, false) F(9, true) F(8, false) F(4, false) F(2, false)
+constexpr bool dwb_table_ok() {
+  int nout = 0;
+  for (int i = 0; i < DWP_N; ++i) {
+    const DwbProd& p = kDwbProds[i];
+    bool form = false;
+#define DWB_IS(NIT, Z) form = form || (p.nit() == NIT && p.z == Z);
+    DWB_FORMS(DWB_IS)
+#undef DWB_IS
+    if (!form || (p.x1_ks + p.x2_ks) % 2 || p.x1_ks % 2) return false;  // (the parity of a slot piece = the parity of its X piece)
+    if (p.early != (i < DWB_SMALL_EARLY) || kDwbSmall[i] != i) return false;
+    for (const DwbOut& o : p.out) nout += o.o_count > 0;
+  }
+  const DwbProd& g0 = kDwbProds[kDwbGroup[0]];
+  for (int k : kDwbGroup) {  // a group is one DwBfArgs in front of the event: same shape, no X2, no Z, early
+    const DwbProd& p = kDwbProds[k];
+    if (p.kind() != g0.kind() || p.g_ks != g0.g_ks || p.x2_ks || p.z || !p.early) return false;
+  }
+  return nout <= (int)(sizeof(DwBfReduceBatch::r) / sizeof(DwBfReduceArgs));  // all slab sums of a step fit ONE reduce launch
 }
+static_assert(dwb_table_ok(), "a product of a shape that is not instantiated, an early product behind a late one, or too many outputs");
+
+// Slab space: every product of a step keeps its own slabs (ONE reduce launch at the end).  The worst case is the launch per product: all
+// DWB_WGS workgroups each, DWB_GROUP_WGS for the grouped ones.
+constexpr bool dwb_grouped(int i) {
+  for (int k : kDwbGroup)
+    if (k == i) return true;
+  return false;
+}
+constexpr size_t dwb_slab_floats(const int* prods, int n) {
+  size_t f = 0;
+  for (int i = 0; i < n; ++i) f += (dwb_grouped(prods[i]) ? DWB_GROUP_WGS : DWB_WGS) * kDwbProds[prods[i]].slab_floats();
+  return f;
+}
+constexpr size_t dwb_most_slab_floats(const int* prods, int n) {
+  size_t f = 0;
+  for (int i = 0; i < n; ++i) f = kDwbProds[prods[i]].slab_floats() > f ? kDwbProds[prods[i]].slab_floats() : f;
+  return f;
+}
+constexpr size_t DWB_SLAB_FLOATS = dwb_slab_floats(kDwbSmall, DWP_N);
+static_assert(DWB_SLAB_FLOATS == 54770688, "the slab region is part of the workspace layout");
+// (the large-batch structure without an event: the group, then a multi launch of at most DWB_WGS workgroups; a multi launch checks its own plan too)
+static_assert(dwb_slab_floats(kDwbGroup, DWB_NGROUP) + DWB_WGS * dwb_most_slab_floats(kDwbLargeRest, 4) <= DWB_SLAB_FLOATS, "slab space");
+size_t dw_bf16_slab_floats() { return DWB_SLAB_FLOATS; }
 
 template <int NIT, bool HAS_Z, bool SPLIT>
 static hipError_t dwb_launch_as(const DwBfArgs& a, int wgs, hipStream_t st) {
@@ -347,145 +410,198 @@ static hipError_t dwb_launch_as(const DwBfArgs& a, int wgs, hipStream_t st) {
   hipLaunchKernelGGL((k_dw_bf16<NIT, HAS_Z, SPLIT>), dim3(wgs), dim3(BF_WG), Geo::LDS_BYTES, st, a);
   return hipGetLastError();
 }
-// (a.gdelta / a.xdelta != 0: the two-part form of the split-fp32 train step)
-template <int NIT, bool HAS_Z>
-static hipError_t dwb_launch(const DwBfArgs& a, int wgs, hipStream_t st) {
-  return (a.gdelta || a.xdelta) ? dwb_launch_as<NIT, HAS_Z, true>(a, wgs, st) : dwb_launch_as<NIT, HAS_Z, false>(a, wgs, st);
-}
-
-// One pass over the samples: slabs <- G^T [X1 | X2]  (+ [X1 | X2]^T Z in 32 extra slab rows).  x1_ks + x2_ks in {2,4,8,16,18,20}.
-hipError_t launch_dw_bf16_gemm(const unsigned char* G, int g_ks, const unsigned char* X1, int x1_ks, const unsigned char* X2, int x2_ks,
-                               const unsigned char* Z, int wb_tot, float* slabs, int* nslab, hipStream_t st, DwBfSplit sp) {
-  DwBfArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gdelta = sp.gdelta; a.xdelta = sp.xdelta;
-  a.z_tile0 = Z ? x1_ks / 2 : 0;  // Z multiplies the X2 tiles (the sigma head rides on the product whose second input tensor is h7)
-  a.G[0] = G; a.X1[0] = X1; a.ngemm = 1; a.X2 = X2 ? X2 : X1; a.Z = Z; a.g_ks = g_ks; a.o_tiles = (g_ks + 1) / 2; a.x1_ks = x1_ks; a.wb_tot = wb_tot; a.slabs = slabs;
-  const int wgs = wb_tot < DWB_WGS ? wb_tot : DWB_WGS;
-  *nslab = wgs;
-  const int xks = x1_ks + x2_ks;
-  if (Z) return xks == 18 ? dwb_launch<9, true>(a, wgs, st) : xks == 16 ? dwb_launch<8, true>(a, wgs, st) : hipErrorInvalidValue;
-  switch (xks) {
-    case 20: return dwb_launch<10, false>(a, wgs, st);
-    case 18: return dwb_launch<9, false>(a, wgs, st);
-    case 16: return dwb_launch<8, false>(a, wgs, st);
-    case 8: return dwb_launch<4, false>(a, wgs, st);
-    case 4: return dwb_launch<2, false>(a, wgs, st);
-    case 2: return dwb_launch<1, false>(a, wgs, st);
+// k_dw_bf16 of the form `kind` (a.gdelta / a.xdelta != 0: the two-part form of the split-fp32 train step)
+static hipError_t dwb_launch(int kind, const DwBfArgs& a, int wgs, hipStream_t st) {
+  const bool split = a.gdelta || a.xdelta;
+  switch (kind) {
+#define DWB_CASE(NIT, Z) \
+  case 2 * NIT + (Z ? 1 : 0): return split ? dwb_launch_as<NIT, Z, true>(a, wgs, st) : dwb_launch_as<NIT, Z, false>(a, wgs, st);
+    DWB_FORMS(DWB_CASE)
+#undef DWB_CASE
     default: return hipErrorInvalidValue;
   }
 }
 
-// n (<= 6) products G_k^T X_k of 256 x 256 outputs in one launch; product k's slabs start at slabs + k * (*nslab) * 256 * 257
-hipError_t launch_dw_bf16_group(const unsigned char* const* Gs, const unsigned char* const* Xs, int n, int wb_tot, float* slabs, int* nslab,
-                                hipStream_t st, DwBfSplit sp) {
-  if (n < 1 || n > 6) return hipErrorInvalidValue;
-  DwBfArgs a;
-  memset(&a, 0, sizeof(a));
-  a.gdelta = sp.gdelta; a.xdelta = sp.xdelta;
-  for (int k = 0; k < n; ++k) { a.G[k] = Gs[k]; a.X1[k] = Xs[k]; }
-  a.X2 = Xs[0]; a.ngemm = n; a.g_ks = 16; a.o_tiles = 8; a.x1_ks = 16; a.wb_tot = wb_tot; a.slabs = slabs;
-  int nwg = DWB_WGS / n;
-  if (nwg > wb_tot) nwg = wb_tot;
-  *nslab = nwg;
-  return dwb_launch<8, false>(a, nwg * n, st);
+// All products in one or two multi launches up to this many wave blocks -- where the per-product launches' slabs (219 MB per step whatever
+// the batch) and launch boundaries weigh (a rank's share of a strong-scaling step, the reference's 400-ray batch) -- and the large-batch
+// structures beyond.  NERF_DW_BF16_MULTI=0 / 1 overrides the choice (A/B measurements only).
+constexpr int DW_BF16_MULTI_MAX_WB = 5120;  // 853 rays x (64 + 128); measured: 400 rays -25 %, 512 -18 %, 1024 +-0, 2048 +10 %, 4096 +30 %
+static bool dw_bf16_multi(int wb_tot) {
+  static const int forced = [] { const char* e = getenv("NERF_DW_BF16_MULTI"); return e ? atoi(e) : -1; }();
+  return forced >= 0 ? forced != 0 : wb_tot <= DW_BF16_MULTI_MAX_WB;
 }
 
-// n (<= 12) products of ANY of the shapes above in ONE launch of (at most) DWB_WGS workgroups, dealt out in proportion to the bytes a
-// product reads per wave block (largest remainder, at least one each, never more than wave blocks).  Fills p[i].slabs / p[i].nslab
-// (carved from slab_base in order) and returns the end of the used slab space in *slab_end.
-hipError_t launch_dw_bf16_multi(DwBfProd* p, int n, int wb_tot, float* slab_base, const float* slab_limit, float** slab_end, hipStream_t st, DwBfSplit sp) {
-  if (n < 1 || n > DwBfMulti::MAXP || wb_tot < 1) return hipErrorInvalidValue;
-  DwBfMulti m;
-  memset(&m, 0, sizeof(m));
-  m.n = n;
-  // cost of a product per wave block = its KiB, weighted by how far below the big products' rate its shape streams (small blocks are paced
-  // by the ring's per-block latency: profiles/r03_train_bf16_pmc.json -- 256 x 256 products 5.8 TB/s, layer 4 5.4, the folded product 4.3,
-  // colour head 3.8, layer 0 3.4); the factors in per cent
-  constexpr struct { int l0, col, fold, l4; } costs = {170, 150, 135, 107};
-  int pieces[DwBfMulti::MAXP], total = 0;
-  for (int i = 0; i < n; ++i) {
-    const int kib = p[i].g_ks + p[i].x1_ks + p[i].x2_ks + (p[i].Z ? 2 : 0), xks = p[i].x1_ks + p[i].x2_ks;
-    const int pct = xks == 4 ? costs.l0 : xks == 8 ? costs.col : (xks == 18 && p[i].Z) ? costs.fold : xks == 20 ? costs.l4 : 100;
-    pieces[i] = kib * pct;
-    total += pieces[i];
-  }
-  const int budget = DWB_WGS;
-  int nwg[DwBfMulti::MAXP], used = 0;
-  for (int i = 0; i < n; ++i) {
-    nwg[i] = (int)((long long)budget * pieces[i] / total);
-    if (nwg[i] < 1) nwg[i] = 1;
-    if (nwg[i] > wb_tot) nwg[i] = wb_tot;
-    used += nwg[i];
-  }
-  // hand the remaining workgroups to the products with the most bytes per workgroup (fixed order: deterministic slabs)
-  while (used < budget) {
-    int best = -1;
-    double worst = 0.0;
-    for (int i = 0; i < n; ++i) {
-      const double load = (double)pieces[i] / nwg[i];
-      if (nwg[i] < wb_tot && load > worst) { worst = load; best = i; }
-    }
-    if (best < 0) break;
-    ++nwg[best]; ++used;
-  }
-  while (used > budget) {  // (only when n > budget or the minimum of one each overshoots: not with 12 products)
-    int best = -1;
-    double least = 1e30;
-    for (int i = 0; i < n; ++i) {
-      const double load = (double)pieces[i] / nwg[i];
-      if (nwg[i] > 1 && load < least) { least = load; best = i; }
-    }
-    if (best < 0) break;
-    --nwg[best]; --used;
-  }
-  float* slab = slab_base;
-  int wg0 = 0;
-  for (int i = 0; i < n; ++i) {
-    DwBfArgs& a = m.a[i];
-    const int xks = p[i].x1_ks + p[i].x2_ks, nit = xks / 2;
-    const bool z = p[i].Z != nullptr;
-    if (xks % 2 || !((nit == 10 && !z) || (nit == 9 && z) || (nit == 8 && !z) || (nit == 4 && !z) || (nit == 2 && !z))) return hipErrorInvalidValue;
-    a.G[0] = p[i].G; a.X1[0] = p[i].X1; a.X2 = p[i].X2 ? p[i].X2 : p[i].X1; a.ngemm = 1; a.Z = p[i].Z; a.z_tile0 = z ? p[i].x1_ks / 2 : 0;
-    a.g_ks = p[i].g_ks; a.o_tiles = (p[i].g_ks + 1) / 2; a.x1_ks = p[i].x1_ks; a.wb_tot = wb_tot; a.slabs = slab;
+// One weight-gradient phase being enqueued: the launchers carve each product's slabs from `slab` in launch order and note its slab sums
+// in `rb`, which reduce() sends off in ONE launch.
+struct DwbPhase {
+  const unsigned char *bs, *bg;
+  int wb_tot;
+  float* const* dw;
+  float* mbuf;
+  float* slab;              // the next free slab
+  const float* slab_limit;  // one past the slab space
+  DwBfSplit sp;
+  hipStream_t st;
+  DwBfReduceBatch rb;
+
+  float* dst(int t) const { return t < 0 ? nullptr : t == DWB_MBUF ? mbuf : dw[t]; }
+  // product p joins the argument block `a` (zeroed, then the same-shaped products of a group one after the other), its slabs at `slabs`
+  void add(DwBfArgs& a, const DwbProd& p, float* slabs) const {
+    const int k = a.ngemm++;
+    a.G[k] = bg + (size_t)wb_tot * bg_cum(p.g) * BF_FRAG_BYTES;
+    a.X1[k] = bs + (size_t)wb_tot * bs_cum(p.x1) * BF_FRAG_BYTES;
+    if (k) return;
+    a.X2 = p.x2 < 0 ? a.X1[0] : bs + (size_t)wb_tot * bs_cum(p.x2) * BF_FRAG_BYTES;
+    a.Z = p.z ? bg + (size_t)wb_tot * bg_cum(BG_Z) * BF_FRAG_BYTES : nullptr;
+    a.z_tile0 = p.z_tile0(); a.g_ks = p.g_ks; a.o_tiles = p.o_tiles(); a.x1_ks = p.x1_ks; a.wb_tot = wb_tot; a.slabs = slabs;
     a.gdelta = sp.gdelta; a.xdelta = sp.xdelta;
-    m.kind[i] = 2 * nit + (z ? 1 : 0);
-    m.wg0[i] = wg0;
-    wg0 += nwg[i];
-    p[i].slabs = slab;
-    p[i].nslab = nwg[i];
-    const size_t rows = (size_t)a.o_tiles * 32 + (z ? 32 : 0);
-    slab += (size_t)nwg[i] * rows * (nit * 32 + 1);
   }
-  m.wg0[n] = wg0;
-  if (slab_end) *slab_end = slab;
-  if (slab_limit && slab > slab_limit) return hipErrorOutOfMemory;  // the slabs of this plan would run past the workspace's slab space: nothing is enqueued
-  static std::atomic<unsigned long long> opted{0}, opted_split{0};
-  constexpr int lds_bytes = 144 * 1024;
-  static_assert(DwbGeom<10, false>::LDS_BYTES <= lds_bytes && DwbGeom<9, true>::LDS_BYTES <= lds_bytes && DwbGeom<8, false>::LDS_BYTES <= lds_bytes &&
-                DwbGeom<4, false>::LDS_BYTES <= lds_bytes && DwbGeom<2, false>::LDS_BYTES <= lds_bytes, "LDS of the multi-product launch");
-  static_assert(DwbGeom<10, false, true>::LDS_BYTES <= lds_bytes && DwbGeom<9, true, true>::LDS_BYTES <= lds_bytes && DwbGeom<8, false, true>::LDS_BYTES <= lds_bytes &&
-                DwbGeom<4, false, true>::LDS_BYTES <= 160 * 1024 && DwbGeom<2, false, true>::LDS_BYTES <= 160 * 1024, "LDS of the two-part multi-product launch");
-  if (sp.gdelta || sp.xdelta) {
-    constexpr int lds_split = 160 * 1024;
-    if (hipError_t e = ensure_dynamic_lds(opted_split, {reinterpret_cast<const void*>(&k_dw_bf16_multi<true>)}, lds_split)) return e;
-    hipLaunchKernelGGL(k_dw_bf16_multi<true>, dim3(wg0), dim3(BF_WG), lds_split, st, m);
+  void sums(const DwbProd& p, const float* slabs, int nslab) {
+    for (const DwbOut& o : p.out) {
+      if (o.o_count == 0) continue;
+      DwBfReduceArgs& r = rb.r[rb.n++];
+      r.slabs = slabs; r.nslab = nslab; r.rows = p.rows(); r.ni = p.ni();
+      r.o_first = o.o_first; r.o_count = o.o_count; r.i_first = o.i_first; r.i_count = o.i_count;
+      r.dW = dst(o.dst); r.ldw = o.ldw; r.col0 = o.col0; r.db = dst(o.bias);
+    }
+  }
+  // one pass over the samples for ONE product on all workgroups: slabs <- G^T [X1 | X2]  (+ [X1 | X2]^T Z in 32 extra slab rows)
+  hipError_t each(int prod) {
+    const DwbProd& p = kDwbProds[prod];
+    DwBfArgs a;
+    memset(&a, 0, sizeof(a));
+    add(a, p, slab);
+    const int wgs = wb_tot < DWB_WGS ? wb_tot : DWB_WGS;
+    sums(p, slab, wgs);
+    slab += wgs * p.slab_floats();
+    return dwb_launch(p.kind(), a, wgs, st);
+  }
+  // the products of kDwbGroup in one launch (workgroup b works on product b % 6), one after the other in the slab space
+  hipError_t group() {
+    DwBfArgs a;
+    memset(&a, 0, sizeof(a));
+    const int nwg = wb_tot < DWB_GROUP_WGS ? wb_tot : DWB_GROUP_WGS;
+    for (int k = 0; k < DWB_NGROUP; ++k) {
+      const DwbProd& p = kDwbProds[kDwbGroup[k]];
+      add(a, p, slab);
+      sums(p, slab + k * nwg * p.slab_floats(), nwg);
+    }
+    slab += DWB_NGROUP * nwg * kDwbProds[kDwbGroup[0]].slab_floats();
+    return dwb_launch(kDwbProds[kDwbGroup[0]].kind(), a, nwg * DWB_NGROUP, st);
+  }
+  // n products of any shape in ONE launch of (at most) DWB_WGS workgroups, dealt out in proportion to the products' costs (largest
+  // remainder, at least one each, never more than wave blocks): as many CUs busy as with a launch each, streams of 100+ blocks, a quarter
+  // of the slabs.  Nothing is enqueued when the plan's slabs would run past the slab space.
+  hipError_t multi(const int* prods, int n) {
+    static_assert(DWP_N <= DwBfMulti::MAXP, "products of a multi launch");
+    DwBfMulti m;
+    memset(&m, 0, sizeof(m));
+    m.n = n;
+    int pieces[DwBfMulti::MAXP], total = 0;
+    for (int i = 0; i < n; ++i) {
+      pieces[i] = kDwbProds[prods[i]].kib() * kDwbProds[prods[i]].pct;
+      total += pieces[i];
+    }
+    const int budget = DWB_WGS;
+    int nwg[DwBfMulti::MAXP], used = 0;
+    for (int i = 0; i < n; ++i) {
+      nwg[i] = (int)((long long)budget * pieces[i] / total);
+      if (nwg[i] < 1) nwg[i] = 1;
+      if (nwg[i] > wb_tot) nwg[i] = wb_tot;
+      used += nwg[i];
+    }
+    // hand the remaining workgroups to the products with the most bytes per workgroup (fixed order: deterministic slabs)
+    while (used < budget) {
+      int best = -1;
+      double worst = 0.0;
+      for (int i = 0; i < n; ++i) {
+        const double load = (double)pieces[i] / nwg[i];
+        if (nwg[i] < wb_tot && load > worst) { worst = load; best = i; }
+      }
+      if (best < 0) break;
+      ++nwg[best]; ++used;
+    }
+    while (used > budget) {  // (only when n > budget or the minimum of one each overshoots: not with 12 products)
+      int best = -1;
+      double least = 1e30;
+      for (int i = 0; i < n; ++i) {
+        const double load = (double)pieces[i] / nwg[i];
+        if (nwg[i] > 1 && load < least) { least = load; best = i; }
+      }
+      if (best < 0) break;
+      --nwg[best]; --used;
+    }
+    float* end = slab;
+    for (int i = 0; i < n; ++i) {
+      const DwbProd& p = kDwbProds[prods[i]];
+      add(m.a[i], p, end);
+      m.kind[i] = p.kind();
+      m.wg0[i + 1] = m.wg0[i] + nwg[i];
+      end += nwg[i] * p.slab_floats();
+    }
+    if (end > slab_limit) return hipErrorOutOfMemory;
+    for (int i = 0; i < n; ++i) sums(kDwbProds[prods[i]], m.a[i].slabs, nwg[i]);
+    slab = end;
+    // (bf16 operands: every form fits 144 KiB; two-part operands: the whole LDS, which DwbGeom holds every form to)
+    constexpr int lds_bytes = 144 * 1024, lds_split = 160 * 1024;
+#define DWB_FITS(NIT, Z) static_assert(DwbGeom<NIT, Z>::LDS_BYTES <= lds_bytes && DwbGeom<NIT, Z, true>::LDS_BYTES <= lds_split, "LDS of the multi launch");
+    DWB_FORMS(DWB_FITS)
+#undef DWB_FITS
+    static std::atomic<unsigned long long> opted{0}, opted_split{0};
+    if (sp.gdelta || sp.xdelta) {
+      if (hipError_t e = ensure_dynamic_lds(opted_split, {reinterpret_cast<const void*>(&k_dw_bf16_multi<true>)}, lds_split)) return e;
+      hipLaunchKernelGGL(k_dw_bf16_multi<true>, dim3(m.wg0[n]), dim3(BF_WG), lds_split, st, m);
+      return hipGetLastError();
+    }
+    if (hipError_t e = ensure_dynamic_lds(opted, {reinterpret_cast<const void*>(&k_dw_bf16_multi<false>)}, lds_bytes)) return e;
+    hipLaunchKernelGGL(k_dw_bf16_multi<false>, dim3(m.wg0[n]), dim3(BF_WG), lds_bytes, st, m);
     return hipGetLastError();
   }
-  if (hipError_t e = ensure_dynamic_lds(opted, {reinterpret_cast<const void*>(&k_dw_bf16_multi<false>)}, lds_bytes)) return e;
-  hipLaunchKernelGGL(k_dw_bf16_multi<false>, dim3(wg0), dim3(BF_WG), lds_bytes, st, m);
-  return hipGetLastError();
-}
+  // the slab sums noted so far, in ONE launch
+  hipError_t reduce() {
+    int most = 1;
+    for (int k = 0; k < rb.n; ++k) {
+      const int blocks = (rb.r[k].o_count * (rb.r[k].ni + 1) + 63) / 64;
+      most = blocks > most ? blocks : most;
+    }
+    hipLaunchKernelGGL(k_dw_bf16_reduce_batch, dim3(most, rb.n), dim3(256), 0, st, rb);
+    rb.n = 0;
+    return hipGetLastError();
+  }
+  // point_layer[0..7] are complete: their sums go out now, the rest of the products follow the event
+  hipError_t early_done(hipEvent_t ev) {
+    if (hipError_t e = reduce()) return e;
+    return hipEventRecord(ev, st);
+  }
+};
 
-// slab rows [o_first, o_first + o_count), columns [i_first, i_first + i_count) -> dW[o][col0 + i]; last slab column -> db
-hipError_t launch_dw_bf16_reduce(const float* slabs, int nslab, int rows, int ni, int o_first, int o_count, int i_first, int i_count,
-                                 float* dW, int ldw, int col0, float* db, hipStream_t st) {
-  DwBfReduceArgs r;
-  r.slabs = slabs; r.nslab = nslab; r.rows = rows; r.ni = ni;
-  r.o_first = o_first; r.o_count = o_count; r.i_first = i_first; r.i_count = i_count; r.dW = dW; r.ldw = ldw; r.col0 = col0; r.db = db;
-  const int n = o_count * (ni + 1);
-  hipLaunchKernelGGL(k_dw_bf16_reduce, dim3((n + 63) / 64), dim3(256), 0, st, r);
-  return hipGetLastError();
+#define DWB_TRY(expr) do { if (hipError_t e_ = (expr)) return e_; } while (0)
+hipError_t launch_dw_bf16_phase(const unsigned char* bs, const unsigned char* bg, int wb_tot, float* const* dw, float* mbuf, float* slabs,
+                                size_t slab_floats, const Weights24& w, void* early_event, DwBfSplit sp, hipStream_t st) {
+  if (wb_tot < 1) return hipErrorInvalidValue;
+  DwbPhase ph = {bs, bg, wb_tot, dw, mbuf, slabs, slabs + slab_floats, sp, st, {}};
+  const hipEvent_t ev = static_cast<hipEvent_t>(early_event);
+  if (dw_bf16_multi(wb_tot)) {
+    const int first = ev ? DWB_SMALL_EARLY : DWP_N;
+    DWB_TRY(ph.multi(kDwbSmall, first));
+    if (ev) {
+      DWB_TRY(ph.early_done(ev));
+      DWB_TRY(ph.multi(kDwbSmall + first, DWP_N - first));
+    }
+  } else if (!ev) {
+    DWB_TRY(ph.group());
+    DWB_TRY(ph.multi(kDwbLargeRest, 4));
+  } else {
+    DWB_TRY(ph.each(DWP_L0));
+    DWB_TRY(ph.group());
+    DWB_TRY(ph.each(DWP_L4));
+    DWB_TRY(ph.early_done(ev));
+    DWB_TRY(ph.each(DWP_FOLD));
+    DWB_TRY(ph.each(DWP_COL));
+  }
+  DWB_TRY(ph.reduce());
+  return launch_fold_grads(fold_grad_args(w, dw, mbuf), st);
 }
+#undef DWB_TRY
 
 }  // namespace nerf

@@ -280,6 +280,13 @@ struct FoldGradArgs {
   float* dW_dir;         // [128][280], columns 24.. written
 };
 hipError_t launch_fold_grads(const FoldGradArgs& a, hipStream_t st);
+// (w: the step's weights, dw: its 24 gradient tensors -- dw[B_DIR] final, mbuf: the folded product's sums)
+inline FoldGradArgs fold_grad_args(const Weights24& w, float* const* dw, const float* mbuf) {
+  FoldGradArgs a;
+  a.M = mbuf; a.db_dir = dw[B_DIR]; a.w_dir = w.p[W_DIR]; a.w_pi = w.p[W_PI]; a.b_pi = w.p[B_PI];
+  a.dW_pi = dw[W_PI]; a.db_pi = dw[B_PI]; a.dW_dir = dw[W_DIR];
+  return a;
+}
 
 struct MergeBwdArgs {
   const float* dC_f;       // [B][3]
@@ -332,37 +339,16 @@ hipError_t launch_field_bwd_reg(const FieldBwdArgs& a, bool fine, hipStream_t st
 hipError_t launch_query_grad_bwd(const FieldBwdArgs& a, bool rgb, hipStream_t st);  // the query form of the chain: a.dt = dpoints [M][3] (QGRAD_*)
 hipError_t launch_field_bwd_bf16(const FieldBwdArgs& a, bool fine, hipStream_t st, const BwdFuse* fuse = nullptr);
 hipError_t launch_pack_weights_bf16_bwd(const Weights24& w, const float* fold, unsigned char* img, hipStream_t st);
+// bf16 / split-fp32 weight-gradient phase (dw_bf16.hip): every product of a step over the fragment-layout buffers `bs` (layer inputs) and `bg`
+// (pre-activation gradients) of wb_tot wave blocks, their slab sums into the 24 gradient tensors `dw` and the folded product's M (`mbuf`),
+// then k_fold_grads on the weights `w`.  `slabs`: dw_bf16_slab_floats() floats of partial sums.  early_event (or null) is recorded as soon
+// as the tensors of point_layer[0..7] (dw[0..15]) are final.
 size_t dw_bf16_slab_floats();
 // split-fp32 train step: every operand tensor is a (hi, mid) pair of the same layout -- the mid part of a gradient-type tensor (G, Z) lies
 // gdelta bytes behind its hi part, the mid part of an input tensor xdelta bytes; {0, 0} = plain bf16 operands
 struct DwBfSplit { long long gdelta = 0, xdelta = 0; };
-hipError_t launch_dw_bf16_gemm(const unsigned char* G, int g_ks, const unsigned char* X1, int x1_ks, const unsigned char* X2, int x2_ks,
-                               const unsigned char* Z, int wb_tot, float* slabs, int* nslab, hipStream_t st, DwBfSplit sp = DwBfSplit{});
-hipError_t launch_dw_bf16_group(const unsigned char* const* Gs, const unsigned char* const* Xs, int n, int wb_tot, float* slabs, int* nslab,
-                                hipStream_t st, DwBfSplit sp = DwBfSplit{});
-// one product of a multi-product launch (small batches: dw_bf16.hip): inputs G, X1 (+ X2) (+ Z); slabs / nslab are filled in
-struct DwBfProd {
-  const unsigned char* G; int g_ks;
-  const unsigned char* X1; int x1_ks;
-  const unsigned char* X2; int x2_ks;
-  const unsigned char* Z;
-  float* slabs; int nslab;
-};
-// slab_limit: one past the slab space (checked on the host BEFORE the launch: hipErrorOutOfMemory, nothing enqueued) or null
-hipError_t launch_dw_bf16_multi(DwBfProd* p, int n, int wb_tot, float* slab_base, const float* slab_limit, float** slab_end, hipStream_t st,
-                                DwBfSplit sp = DwBfSplit{});
-hipError_t launch_dw_bf16_reduce(const float* slabs, int nslab, int rows, int ni, int o_first, int o_count, int i_first, int i_count,
-                                 float* dW, int ldw, int col0, float* db, hipStream_t st);
-// dW[o][col0 + i - i_first] = sum over slabs of row o_first + o, column i; db[o] likewise from the last slab column
-struct DwBfReduceArgs {
-  const float* slabs;
-  int nslab, rows, ni;          // slab = [rows][ni + 1]
-  int o_first, o_count, i_first, i_count;   // slab columns [i_first, i_first + i_count) -> dW columns col0 ..
-  float* dW; int ldw, col0;
-  float* db;                    // or null
-};
-struct DwBfReduceBatch { DwBfReduceArgs r[16]; int n; };
-hipError_t launch_dw_bf16_reduce_batch(const DwBfReduceBatch& b, hipStream_t st);  // all slab sums of a step in ONE launch
+hipError_t launch_dw_bf16_phase(const unsigned char* bs, const unsigned char* bg, int wb_tot, float* const* dw, float* mbuf, float* slabs,
+                                size_t slab_floats, const Weights24& w, void* early_event, DwBfSplit sp, hipStream_t st);
 hipError_t launch_dw(const DwBatch& b, long long Mtot, float* slabs, hipStream_t st, int first = 0, int count = -1);  // products [first, first + count) -> their slabs
 hipError_t launch_dw_reduce(const DwBatch& b, hipStream_t st, int first = 0, int count = -1);  // the slabs of items [first, first + count) -> gradients, ONE launch
 size_t dw_item_slab_floats(const DwItem& p);

@@ -2,9 +2,11 @@
 the two segment tables, from which the header derives its named offsets)
 must be the running sums of (tiles x k-steps) in the order the kernels consume them, the streams must be whole 16-fragment
 chunks (or padded up to one), and the training buffers' per-wave-block sizes must add up.  A silent edit of one constant
-would otherwise only show as wrong numbers on the GPU."""
+would otherwise only show as wrong numbers on the GPU.  And the training workspace's layout around the weight-gradient slabs."""
 import os
 import re
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nerf-tiny_amd", "csrc")
@@ -110,3 +112,35 @@ def test_python_decoder_matches_header():
     spec = importlib.util.spec_from_file_location("t_bf16", os.path.join(ROOT, "tests", "test_gpu_bf16.py"))
     src = open(spec.origin).read()
     assert "BS_KS = [4] + [16] * 8 + [8, 2]" in src and "BG_KS = [16] * 8 + [8, 2]" in src
+
+
+def _ws_layouts():
+    import json
+
+    with open(os.path.join(ROOT, "tests", "golden", "bf16_ws_layout.json")) as f:
+        doc = json.load(f)
+    assert doc["recorded_from_commit"]
+    return doc["layouts"]
+
+
+WS_MODES = ("bf16_mlp", "split_mlp")
+WS_SHAPES = [(2, 2, 1), (131, 64, 128), (853, 64, 128), (3, 1024, 1024)]
+
+
+@pytest.mark.parametrize("B,Nc,Nf", WS_SHAPES)
+@pytest.mark.parametrize("mode", WS_MODES)
+def test_training_workspace_layout_is_the_recorded_one(pkg, mode, B, Nc, Nf):
+    """The slab region of the bf16 / split-fp32 weight-gradient phase (csrc/dw_bf16.hip dw_bf16_slab_floats(), computed from the product
+    table) is part of the workspace layout: bG lies in front of it, mbuf and drgb_c behind it, so either moves if its size does.  Held to
+    the values the commit named in tests/golden/bf16_ws_layout.json gave (host-only calls)."""
+    import ctypes as C
+
+    _abi = pkg._abi
+    want = _ws_layouts()[f"{mode}-{B}x{Nc}+{Nf}"]
+    flags = _abi.SAVE_FOR_BACKWARD | {"bf16_mlp": _abi.BF16_MLP, "split_mlp": _abi.SPLIT_MLP}[mode]
+    got = {"ws_bytes": _abi.ws_bytes(B, Nc, Nf, flags)}
+    for name in ("mbuf", "drgb_c", "bG"):
+        off = C.c_size_t(0)
+        _abi.check(_abi.lib().nerf_hip_ws_offset(B, Nc, Nf, flags, name.encode(), C.byref(off)))
+        got[name] = int(off.value)
+    assert got == want

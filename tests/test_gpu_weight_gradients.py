@@ -5,11 +5,12 @@ weight-gradient products are not: after a backward the workspace still holds exa
 the same products evaluated in float64 leave only the kernels' fp32 accumulation order as a difference.  Every one of the 24
 gradient tensors is held to ||dW - ref|| / ||mag|| < BAR, mag being the same formula on absolute values.
 
-The matrix reaches every schedule csrc/api.hip's backward_impl chooses between (expected_path below restates the choice):
+The matrix reaches every schedule csrc/api.hip's backward_impl (fp32) and csrc/dw_bf16.hip's launch_dw_bf16_phase (bf16, split) choose
+between (expected_path below restates the choice):
   fp32         ray duty on / off: the dir_info product writes the per-ray sums itself (dw_ray_duty_ok) or launch_small_grads does
   bf16, split  (a) <= 5120 wave blocks, no early event: one k_dw_bf16_multi launch
                (b) <= 5120, event: two multi launches, early then late
-               (c) >  5120, no event: launch_dw_bf16_group for six products, a multi launch for four
+               (c) >  5120, no event: one k_dw_bf16 launch for the group of six products, a multi launch for four
                (d) >  5120, event: a launch per product
 on both sides of the switch (852 / 853 rays), with ragged last wave blocks in both passes, and at both size limits.  Every case
 with the event also checks its promise (include/nerf_hip.h: tensors 0..15 are final when it fires).
@@ -27,7 +28,7 @@ BAR = 1e-6    # fp32 accumulation over up to 786k rows, relative to the magnitud
 TEETH = 4.0   # one wave block dropped from or doubled in the reference moves the statistic at least this far above BAR
 
 # ---- which schedule a case selects (restated from the library) ---------------------------------------------------------------
-DW_BF16_MULTI_MAX_WB = 5120  # csrc/api.hip DW_BF16_MULTI_MAX_WB
+DW_BF16_MULTI_MAX_WB = 5120  # csrc/dw_bf16.hip DW_BF16_MULTI_MAX_WB
 DW4_DEPTH = 8                # csrc/dw_f32.hip:139
 DW_WGS = 256                 # csrc/kernels.h:227: workgroups of the dir_info product (not one of the grouped seven)
 DIR_MSUBS = 2                # csrc/dw_f32.hip:314-318: nout 128, nin 256 -> 4 waves over 2 blocks
@@ -48,7 +49,7 @@ def expected_path(arith, B, Nc, Nf, event):
     if arith == "fp32":
         return "duty" if dw_ray_duty_ok(B, Nc, Nf) else "noduty"
     wb_tot = W.wave_blocks(B, Nc) + W.wave_blocks(B, Nf)  # csrc/api.hip wave_blocks(), backward_impl()
-    small = wb_tot <= DW_BF16_MULTI_MAX_WB                  # csrc/api.hip dw_bf16_multi(), backward_impl()
+    small = wb_tot <= DW_BF16_MULTI_MAX_WB                  # csrc/dw_bf16.hip dw_bf16_multi(), launch_dw_bf16_phase()
     return ("b" if event else "a") if small else ("d" if event else "c")
 
 

@@ -13,9 +13,12 @@ The cases are the smallest that reach every instantiation of the stream kernels:
     coarse workgroup;
   * 515 rays, 64 + 128: both passes exceed 256 workgroups -- the 8-wave training kernels, separate ray-stage launches, a partial last
     workgroup, no pair kernel;
-  * 130 rays, 31 + 65: partial waves, no fusion, the non-pair 16x16x32 inference form.
-Each in five modes: bf16_mlp inference, bf16_mlp inference with force_tile_kernel (the 32x32x16 form), bf16_mlp train_step, split_mlp
-inference, split_train train_step.  Digested (raw little-endian fp32 bytes, C order): for inference C_coarse, C_fine and the workspace
+  * 130 rays, 31 + 65: partial waves, no fusion, the non-pair 16x16x32 inference form;
+  * 853 rays, 64 + 128: 5128 wave blocks, the smallest batch that selects the large-batch structures of the bf16 / split-fp32
+    weight-gradient phase (csrc/dw_bf16.hip DW_BF16_MULTI_MAX_WB = 5120).
+Each in seven modes: bf16_mlp inference, bf16_mlp inference with force_tile_kernel (the 32x32x16 form), bf16_mlp train_step, split_mlp
+inference, split_train train_step, and the two train steps again with an overlap bucket (parallel.GradBucket.enable_overlap(): the library
+records the early event, which selects the other launch structure of the weight-gradient phase).  Digested (raw little-endian fp32 bytes, C order): for inference C_coarse, C_fine and the workspace
 views sig_c, rgb_c, t_f, sig_f, rgb_f; for a train step C_coarse, C_fine, the loss and all 24 gradients.
 """
 import hashlib
@@ -28,14 +31,17 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 VIEWS = ["sig_c", "rgb_c", "t_f", "sig_f", "rgb_f"]
-CASES = {"r131_64_128": (131, 64, 128, 11), "r515_64_128": (515, 64, 128, 12), "r130_31_65": (130, 31, 65, 9)}  # rays, Nc, Nf, seed
-# mode -> (model attributes, train step?)
+CASES = {"r131_64_128": (131, 64, 128, 11), "r515_64_128": (515, 64, 128, 12), "r130_31_65": (130, 31, 65, 9),
+         "r853_64_128": (853, 64, 128, 13)}  # rays, Nc, Nf, seed
+# mode -> (model attributes, train step?, with an early event?)
 MODES = {
-    "bf16_inference": ({"bf16_mlp": True}, False),
-    "bf16_tile_inference": ({"bf16_mlp": True, "force_tile_kernel": True}, False),
-    "bf16_train_step": ({"bf16_mlp": True}, True),
-    "split_inference": ({"split_mlp": True}, False),
-    "split_train_step": ({"split_train": True}, True),
+    "bf16_inference": ({"bf16_mlp": True}, False, False),
+    "bf16_tile_inference": ({"bf16_mlp": True, "force_tile_kernel": True}, False, False),
+    "bf16_train_step": ({"bf16_mlp": True}, True, False),
+    "split_inference": ({"split_mlp": True}, False, False),
+    "split_train_step": ({"split_train": True}, True, False),
+    "bf16_train_step_event": ({"bf16_mlp": True}, True, True),
+    "split_train_step_event": ({"split_train": True}, True, True),
 }
 INFERENCE_TENSORS = ["C_coarse", "C_fine"] + VIEWS
 N_GRADS = 24
@@ -53,7 +59,7 @@ def _sha(x):
 
 def digests(oracle, pkg, dev):
     """{case: {mode: {tensor: sha256}}} of whatever library the package has loaded."""
-    from nerf_tiny_amd import _abi
+    from nerf_tiny_amd import _abi, parallel
 
     out = {}
     for name, (B, Nc, Nf, seed) in CASES.items():
@@ -61,15 +67,19 @@ def digests(oracle, pkg, dev):
         w = oracle.make_weights(seed, sharp=True)
         shapes = {"sig_c": (B * Nc,), "rgb_c": (B * Nc, 3), "t_f": (B * Nf,), "sig_f": (B * Nf,), "rgb_f": (B * Nf, 3)}
         out[name] = {}
-        for mode, (attrs, train) in MODES.items():
+        for mode, (attrs, train, event) in MODES.items():
             m = pkg.NeRFModel(Nc, Nf, B)
             m.load_state_dict(w)
             m = m.to(dev)
             for k, v in attrs.items():
                 setattr(m, k, v)
             if train:
+                if event:  # the overlap bucket of tests/test_gpu_weight_gradients.py::_step_with_early_copy; p.grad are its views
+                    m.grad_bucket = parallel.GradBucket(m.network.parameters()).enable_overlap()
                 Cc, Cf, loss = m.train_step(row, col, pb, K, C_true)
                 torch.cuda.synchronize()
+                if event:
+                    m.grad_bucket.consume()
                 ps = list(m.network.parameters())
                 assert len(ps) == N_GRADS
                 d = {"C_coarse": _sha(Cc), "C_fine": _sha(Cf), "loss": _sha(loss)}
