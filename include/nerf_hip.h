@@ -56,7 +56,9 @@ extern "C" {
                                      nerf_hip_mesh_vertex_normals; nerf_hip_mesh_measure, nerf_hip_mesh_sample_ws_bytes,
                                      nerf_hip_mesh_sample, nerf_hip_points_nearest_ws_bytes, nerf_hip_points_grid_build,
                                      nerf_hip_points_nearest, nerf_hip_distance_stats; the nerf_hip_mesh_raycast* calls,
-                                     nerf_hip_mesh_face_rays, nerf_hip_mesh_select_faces_*; nerf_hip_tsdf_integrate */
+                                     nerf_hip_mesh_face_rays, nerf_hip_mesh_select_faces_*; nerf_hip_tsdf_integrate;
+                                     nerf_hip_tsdf_integrate_color, nerf_hip_tsdf_sample_color, nerf_hip_mesh_count_masked,
+                                     nerf_hip_mesh_emit_masked */
 
 enum {
   NERF_HIP_OK = 0,
@@ -390,6 +392,32 @@ int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level,
  * with V >= 2^31 cannot be indexed (the caller refuses it after the count).  lo3 / step3 are HOST arrays. */
 int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
                        size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Masked marching cubes: the two calls above with one more input, valid[nx][ny][nz] (uint8,
+ * C order as sigma; non-zero = valid) -- e.g. the lattice points a TSDF fusion observed.
+ *
+ * M. THE MASK RULE.  A cell is LIVE iff all eight of its corners are valid.  Triangles come from live cells only; a cell's table row is
+ *    computed from sigma > level at its eight corners exactly as above, whatever the mask says.  A lattice edge carries a vertex iff its
+ *    ends differ in insideness (as above) AND at least one of the up to four cells that contain the edge is live.  Every sign-changing
+ *    edge of a cell is used by one of that cell's triangles, so no vertex is unreferenced.
+ *    Vertices and faces keep the order above (by the edge's lower endpoint, then axis; by cell, then the table's order).  The masked
+ *    mesh is therefore the unmasked mesh of the same grid with the faces of the cells that are not live removed and the surviving
+ *    vertices and faces renumbered in their order: what nerf_hip_mesh_select_faces_* produce from the unmasked mesh and the keep flags
+ *    "this face's cell is live", bit for bit in verts, normals and faces.
+ *    Normals stay the grid's central differences interpolated along the edge.  They read sigma at invalid points too -- the caller's
+ *    fill value enters them near the mask's edge -- and are bit-identical to the unmasked normals of the same vertices.
+ *
+ * The workspace, its size (nerf_hip_mesh_ws_bytes), the capacities' clamping and every refusal are those of the unmasked calls; a NULL
+ * valid is refused as well.  The mask is read directly: no pre-pass.  An all-valid mask gives the unmasked mesh.
+ * ------------------------------------------------------------------------------------------- */
+int nerf_hip_mesh_count_masked(const float* sigma, const uint8_t* valid, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes,
+                               int64_t* counts, void* stream);
+
+/* Must follow a nerf_hip_mesh_count_masked on the same workspace, grid, mask and level. */
+int nerf_hip_mesh_emit_masked(const float* sigma, const uint8_t* valid, int nx, int ny, int nz, const float* lo3, const float* step3,
+                              float level, const void* ws, size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v,
+                              int64_t max_f, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Narrow-band density grid: the dense grid of nerf_hip_density_grid with the field evaluated only in a band
@@ -865,6 +893,47 @@ int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, 
                             const float* depth, const float* opacity, int n, int H, int W,
                             const float* cam_o /* HOST [n][3] */, const double* Q /* HOST [n][9] */,
                             double trunc, float min_opacity, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Colour fusion: the colours the views show, fused beside the distances, and read back at
+ * arbitrary points.  The new state is a colour volume color[nx][ny][nz][4] (fp32; (R, G, B, Wc) per lattice point, z fastest, 16-byte
+ * aligned), owned and zeroed by the caller like tsdf and weight.  rgb[n][H][W][3] (fp32) is the colour view c shows at pixel (x, y).
+ *
+ * TC. THE COLOUR RULE.  Per voxel and view, in view order, with rule T's quantities: the geometry update is rule T unchanged -- tsdf and
+ *    weight leave nerf_hip_tsdf_integrate_color with the bits nerf_hip_tsdf_integrate gives them.  The view makes a COLOUR OBSERVATION
+ *    of the voxel iff the voxel is in view, the pixel is FOREGROUND, it observes the voxel by rule T's foreground branch (d finite,
+ *    d > 0, sdf >= -trunc), sdf <= trunc (fp64, false on NaN), and the pixel's three colour channels are finite.  So the voxel lies within
+ *    one truncation distance of that view's surface, on either side; carving observations and observations far in front of the surface
+ *    carry no colour, and a pixel whose colour is not finite still makes its geometry observation.  A colour observation updates, in
+ *    fp64 on the fp32 state (C_ch, Wc) and the fp32 pixel colour c_ch, per channel
+ *       C_ch' = fp32(((double(C_ch) * double(Wc)) + double(c_ch)) / (double(Wc) + 1.0)),   then   Wc' = fp32(double(Wc) + 1.0)
+ *    (the three channels use the old Wc).  The state is rounded after every view, so the result does not depend on how the views are
+ *    grouped into launches or calls.  Wc = the number of colour observations; a voxel with Wc == 0 has no colour.
+ *    A voxel that receives no colour observation in a launch neither loads nor stores its colour state.
+ *
+ * Refusals: everything nerf_hip_tsdf_integrate refuses, a NULL or misaligned color and, with n > 0, a NULL rgb.  n == 0 succeeds and
+ * launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+int nerf_hip_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const float* lo3, const float* step3,
+                                  const float* depth, const float* opacity, const float* rgb, int n, int H, int W,
+                                  const float* cam_o /* HOST [n][3] */, const double* Q /* HOST [n][9] */,
+                                  double trunc, float min_opacity, int flags, void* stream);
+
+/* S. THE SAMPLING RULE.  points[M][3] (fp32) -> rgb[M][3] (fp32), valid[M] (uint8, 0 / 1): the colour volume interpolated trilinearly
+ *    over the corners that have a colour.  Per point and axis a, in fp64 on the fp32 inputs:
+ *       g = (x_a - lo_a) / step_a,   i = min(max(floor(g), 0), n_a - 2),   f = min(max(g - i, 0), 1)
+ *    (clamped in fp64 before i becomes an integer: a point outside the box takes the colour of the box's nearest face); along an axis
+ *    with n_a == 1, i = 0, f = 0 and the upper corner is not read.  The corners (i + di, j + dj, k + dk) of the cell are visited in the
+ *    order (di, dj, dk), dk fastest; a corner with Wc > 0 (false on NaN) adds
+ *       w = (wx * wy) * wz   to den   and   w * double(C_ch)   to num_ch,      w_a = f_a at the upper corner, 1.0 - f_a at the lower,
+ *    every product and sum rounded on its own, the sums in that order from 0.0; a corner without a colour adds nothing.
+ *    valid = den > 0 and rgb_ch = fp32(num_ch / den); an invalid point gets rgb = 0, as does a point with a coordinate that is not finite.
+ * One thread per point; the only data-dependent addresses are the eight corners.  Refused: a dimension < 1, nx * ny * nz >= 2^31, M < 0
+ * or >= 2^31, a NULL or misaligned color, a NULL lo3 / step3, a lo that is not finite, a step that is not finite and > 0 along a
+ * dimension of more than one point and, with M > 0, a NULL points / rgb / valid.  M == 0 succeeds and launches nothing.  lo3 / step3
+ * are HOST arrays.  Enqueue-only. */
+int nerf_hip_tsdf_sample_color(const float* color, int nx, int ny, int nz, const float* lo3, const float* step3, const float* points,
+                               int64_t M, float* rgb, uint8_t* valid, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

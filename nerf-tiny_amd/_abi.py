@@ -100,6 +100,12 @@ _PROTOS = {
                                                   _p]),
     "nerf_hip_tsdf_integrate": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_double,
                                           C.c_float, C.c_int, _p]),
+    "nerf_hip_tsdf_integrate_color": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p,
+                                                C.c_double, C.c_float, C.c_int, _p]),
+    "nerf_hip_tsdf_sample_color": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int64, _p, _p, _p]),
+    "nerf_hip_mesh_count_masked": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_mesh_emit_masked": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_float, _p, C.c_size_t, _p, _p, _p, C.c_int64,
+                                            C.c_int64, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

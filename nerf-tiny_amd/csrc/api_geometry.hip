@@ -257,9 +257,16 @@ int nerf_hip_mesh_ws_bytes(int nx, int ny, int nz, size_t* bytes) {
   return NERF_HIP_OK;
 }
 
-int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// nerf_hip_mesh_count and its masked form (valid non-null; masked: a null valid is refused)
+int mesh_count(const float* sigma, const uint8_t* valid, bool masked, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes,
+               int64_t* counts, void* stream) {
   MeshLayout L;
   if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
+  if (masked && !valid) return fail(NERF_HIP_ERR_ARG, "valid is null");
   if (int rc = check_out(counts, "counts", 8)) return rc;
   if (int rc = check_device()) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -268,15 +275,18 @@ int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level,
     return NERF_HIP_OK;
   }
   MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
+  a.valid = valid;
   a.counts = reinterpret_cast<long long*>(counts);
   HIP_TRY(launch_mesh_count(a, st));
   return NERF_HIP_OK;
 }
 
-int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
-                       size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream) {
+// nerf_hip_mesh_emit and its masked form
+int mesh_emit(const float* sigma, const uint8_t* valid, bool masked, int nx, int ny, int nz, const float* lo3, const float* step3, float level,
+              const void* ws, size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream) {
   MeshLayout L;
   if (int rc = check_mesh_call(sigma, nx, ny, nz, level, ws, ws_bytes, &L)) return rc;
+  if (masked && !valid) return fail(NERF_HIP_ERR_ARG, "valid is null");
   if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
   const int dims[3] = {nx, ny, nz};
   for (int c = 0; c < 3; ++c) {
@@ -290,6 +300,7 @@ int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* 
   if (int rc = check_device()) return rc;
   if (nx < 2 || ny < 2 || nz < 2 || (max_v == 0 && max_f == 0)) return NERF_HIP_OK;  // nothing to write
   MeshArgs a = mesh_args(sigma, nx, ny, nz, level, ws, L);
+  a.valid = valid;
   for (int c = 0; c < 3; ++c) {
     a.lo[c] = lo3[c];
     a.step[c] = step3[c];
@@ -301,6 +312,30 @@ int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* 
   a.max_f = max_f;
   HIP_TRY(launch_mesh_emit(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_count(const float* sigma, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, int64_t* counts, void* stream) {
+  return mesh_count(sigma, nullptr, false, nx, ny, nz, level, ws, ws_bytes, counts, stream);
+}
+
+int nerf_hip_mesh_emit(const float* sigma, int nx, int ny, int nz, const float* lo3, const float* step3, float level, const void* ws,
+                       size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v, int64_t max_f, void* stream) {
+  return mesh_emit(sigma, nullptr, false, nx, ny, nz, lo3, step3, level, ws, ws_bytes, verts, normals, faces, max_v, max_f, stream);
+}
+
+int nerf_hip_mesh_count_masked(const float* sigma, const uint8_t* valid, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes,
+                               int64_t* counts, void* stream) {
+  return mesh_count(sigma, valid, true, nx, ny, nz, level, ws, ws_bytes, counts, stream);
+}
+
+int nerf_hip_mesh_emit_masked(const float* sigma, const uint8_t* valid, int nx, int ny, int nz, const float* lo3, const float* step3,
+                              float level, const void* ws, size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t max_v,
+                              int64_t max_f, void* stream) {
+  return mesh_emit(sigma, valid, true, nx, ny, nz, lo3, step3, level, ws, ws_bytes, verts, normals, faces, max_v, max_f, stream);
 }
 
 }  // extern "C"
@@ -1362,9 +1397,14 @@ int nerf_hip_mesh_select_faces_emit(const float* verts, const float* normals, co
 
 static_assert(TSDF_VIEWS == NERF_HIP_TSDF_VIEWS_PER_LAUNCH, "the header states the kernel's views per launch");
 
-int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* lo3, const float* step3, const float* depth,
-                            const float* opacity, int n, int H, int W, const float* cam_o, const double* Q, double trunc, float min_opacity,
-                            int flags, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// nerf_hip_tsdf_integrate and, with with_color, nerf_hip_tsdf_integrate_color (a null color, or a null rgb with n > 0, is then refused)
+int tsdf_integrate(float* tsdf, float* weight, float* color, bool with_color, int nx, int ny, int nz, const float* lo3, const float* step3,
+                   const float* depth, const float* opacity, const float* rgb, int n, int H, int W, const float* cam_o, const double* Q,
+                   double trunc, float min_opacity, int flags, void* stream) {
   if (int rc = check_grid(nx, ny, nz)) return rc;
   if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);
   if (H < 1 || W < 1) return fail(NERF_HIP_ERR_ARG, "H=%d W=%d: an image has at least one pixel", H, W);
@@ -1374,10 +1414,14 @@ int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, 
   if (!isfinite(trunc) || !(trunc > 0.0)) return fail(NERF_HIP_ERR_ARG, "trunc=%g: the truncation distance must be finite and > 0", trunc);
   if (min_opacity != min_opacity) return fail(NERF_HIP_ERR_ARG, "min_opacity is NaN");
   if (!tsdf || !weight || !lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "tsdf / weight / lo3 / step3 is null");
+  if (with_color) {
+    if (int rc = check_out(color, "color", 16)) return rc;
+  }
   if (int rc = check_finite3(lo3, "lo", "the lattice's corner")) return rc;
   if (int rc = check_finite3(step3, "step", "the lattice's step")) return rc;
   if (n == 0) return NERF_HIP_OK;  // (empty arrays may have null pointers)
   if (!depth || !cam_o || !Q) return fail(NERF_HIP_ERR_ARG, "depth / cam_o / Q is null");
+  if (with_color && !rgb) return fail(NERF_HIP_ERR_ARG, "rgb is null");
   for (int c = 0; c < n; ++c) {
     if (int rc = check_finite3(cam_o + (size_t)c * 3, "cam_o", "a camera's position")) return rc;
     for (int e = 0; e < 9; ++e)
@@ -1388,6 +1432,7 @@ int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, 
   memset(&a, 0, sizeof(a));
   a.tsdf = tsdf;
   a.weight = weight;
+  a.color = reinterpret_cast<float4*>(color);
   a.ny = ny;
   a.nz = nz;
   a.npts = nx * ny * nz;
@@ -1406,12 +1451,64 @@ int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, 
     a.nviews = n - v0 < TSDF_VIEWS ? n - v0 : TSDF_VIEWS;
     a.depth = depth + (size_t)v0 * hw;
     a.opacity = opacity ? opacity + (size_t)v0 * hw : nullptr;
+    a.rgb = with_color ? rgb + (size_t)v0 * hw * 3 : nullptr;
     for (int c = 0; c < a.nviews; ++c) {
       for (int e = 0; e < 9; ++e) a.cam[c].Q[e] = Q[(size_t)(v0 + c) * 9 + e];
       for (int e = 0; e < 3; ++e) a.cam[c].o[e] = cam_o[(size_t)(v0 + c) * 3 + e];
     }
     HIP_TRY(launch_tsdf_integrate(a, static_cast<hipStream_t>(stream)));
   }
+  return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* lo3, const float* step3, const float* depth,
+                            const float* opacity, int n, int H, int W, const float* cam_o, const double* Q, double trunc, float min_opacity,
+                            int flags, void* stream) {
+  return tsdf_integrate(tsdf, weight, nullptr, false, nx, ny, nz, lo3, step3, depth, opacity, nullptr, n, H, W, cam_o, Q, trunc, min_opacity,
+                        flags, stream);
+}
+
+int nerf_hip_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const float* lo3, const float* step3,
+                                  const float* depth, const float* opacity, const float* rgb, int n, int H, int W, const float* cam_o,
+                                  const double* Q, double trunc, float min_opacity, int flags, void* stream) {
+  return tsdf_integrate(tsdf, weight, color, true, nx, ny, nz, lo3, step3, depth, opacity, rgb, n, H, W, cam_o, Q, trunc, min_opacity, flags,
+                        stream);
+}
+
+int nerf_hip_tsdf_sample_color(const float* color, int nx, int ny, int nz, const float* lo3, const float* step3, const float* points,
+                               int64_t M, float* rgb, uint8_t* valid, void* stream) {
+  if (int rc = check_grid(nx, ny, nz)) return rc;
+  if (M < 0) return fail(NERF_HIP_ERR_ARG, "M=%lld < 0", (long long)M);
+  if (M >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "M=%lld: a call samples fewer than 2^31 points", (long long)M);
+  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
+  if (int rc = check_out(color, "color", 16)) return rc;
+  if (int rc = check_finite3(lo3, "lo", "the lattice's corner")) return rc;
+  const int dims[3] = {nx, ny, nz};
+  for (int c = 0; c < 3; ++c)
+    if (dims[c] > 1 && !(step3[c] > 0.0f && isfinite(step3[c])))
+      return fail(NERF_HIP_ERR_ARG, "step[%d] = %g: must be positive and finite along a dimension of more than one point", c, (double)step3[c]);
+  if (M == 0) return NERF_HIP_OK;  // (empty arrays may have null pointers)
+  if (!points || !rgb || !valid) return fail(NERF_HIP_ERR_ARG, "points / rgb / valid is null");
+  if (int rc = check_device()) return rc;
+  TsdfSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.points = points;
+  a.color = reinterpret_cast<const float4*>(color);
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  for (int c = 0; c < 3; ++c) {
+    a.lo[c] = lo3[c];
+    a.step[c] = step3[c];
+  }
+  a.rgb = rgb;
+  a.valid = valid;
+  a.M = M;
+  HIP_TRY(launch_tsdf_sample_color(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

@@ -386,13 +386,15 @@ struct GatherArgs {
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_gather_rays(const GatherArgs& a, hipStream_t st);
 
-// ---- marching cubes over a density grid (mesh.hip; nerf_hip_mesh_count / nerf_hip_mesh_emit) ----
+// ---- marching cubes over a density grid (mesh.hip; nerf_hip_mesh_count / nerf_hip_mesh_emit and their _masked forms, DESIGN.md
+// sections 3h and 3h-10) ----
 constexpr int MESH_WG = 256;                   // threads per workgroup
 constexpr int MESH_ROUNDS = 16;                // rounds of MESH_WG consecutive lattice points per workgroup
 constexpr int MESH_PTS = MESH_WG * MESH_ROUNDS;  // lattice points per workgroup (the scan's block)
 
 struct MeshArgs {
   const float* sigma;      // [nx][ny][nz], z fastest
+  const unsigned char* valid;  // [nx][ny][nz] or null: rule M's mask (the MASKED instantiations; null selects the unmasked ones)
   int nx, ny, nz;          // every dimension >= 2, nx * ny * nz < 2^31
   float level;
   float lo[3], step[3];    // emit only
@@ -654,7 +656,9 @@ hipError_t launch_rc_face_rays(const RcFaceRaysArgs& a, hipStream_t st);
 hipError_t launch_sel_count(const SelArgs& a, hipStream_t st);
 hipError_t launch_sel_emit(const SelArgs& a, hipStream_t st);
 
-// ---- TSDF fusion of depth images (tsdf.hip; nerf_hip_tsdf_integrate; rule T of include/nerf_hip.h) ----
+// ---- TSDF fusion of depth images (tsdf.hip; nerf_hip_tsdf_integrate; rule T of include/nerf_hip.h), of the
+// views' colours beside it and the colour volume sampled at points (nerf_hip_tsdf_integrate_color / nerf_hip_tsdf_sample_color, section
+// 3h-10; rules TC and S) ----
 constexpr int TSDF_VIEWS = 32;                 // views per launch (NERF_HIP_TSDF_VIEWS_PER_LAUNCH)
 constexpr int TSDF_WG = 256;
 
@@ -666,6 +670,8 @@ struct TsdfCam {
 
 struct TsdfArgs {
   float *tsdf, *weight;    // [nx][ny][nz], z fastest
+  float4* color;           // [nx][ny][nz] of (R, G, B, Wc), or null: rule TC's state (the COLOR instantiation; null selects the plain one)
+  const float* rgb;        // [nviews][H][W][3]: the FIRST view of this launch onwards (COLOR only)
   int ny, nz;
   int npts;                // nx * ny * nz < 2^31
   float lo[3], step[3];
@@ -681,6 +687,18 @@ struct TsdfArgs {
 static_assert(sizeof(TsdfArgs) <= 4096, "a kernel's arguments may take 4 KB");
 
 hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st);
+
+struct TsdfSampleArgs {
+  const float* points;     // [M][3]
+  const float4* color;     // [nx][ny][nz] of (R, G, B, Wc)
+  int nx, ny, nz;
+  float lo[3], step[3];
+  float* rgb;              // [M][3]
+  unsigned char* valid;    // [M]
+  long long M;
+};
+
+hipError_t launch_tsdf_sample_color(const TsdfSampleArgs& a, hipStream_t st);
 
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)

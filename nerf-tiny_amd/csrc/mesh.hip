@@ -1,4 +1,5 @@
-// mesh.hip -- marching cubes over a density grid (nerf_hip_mesh_count / nerf_hip_mesh_emit):
+// mesh.hip -- marching cubes over a density grid (nerf_hip_mesh_count / nerf_hip_mesh_emit), and the same under a
+// mask of valid lattice points (nerf_hip_mesh_count_masked / nerf_hip_mesh_emit_masked; section 3h-10, rule M of include/nerf_hip.h):
 //   k_mesh_count   per lattice point: the 0-3 vertices it owns (edges to its +x / +y / +z neighbour whose ends differ in insideness)
 //                  and the triangle count of the cell whose lowest corner it is; in-block exclusive vertex offsets, block totals
 //   k_mesh_scan    one workgroup: 64-bit exclusive scans of the block totals (scan.h scan_totals over two channels), and the totals V, F
@@ -8,6 +9,10 @@
 // order is fixed by the scans -- no atomics place anything -- and every store is clamped to the caller's capacities.  The scan is
 // three kernels, never a single-pass look-back: no flag crosses workgroups (or XCDs) inside a launch.  The in-workgroup prefixes
 // (wg_prefix<MESH_WG, 2> over the vertex counts, <MESH_WG, 3> over the triangle counts) and the scan of the totals are scan.h's.
+// MASKED (template <bool MASKED> over count and emit): a cell is live iff its eight corners are valid, triangles come from live cells
+// only and an edge carries a vertex only where one of the up to four cells around it is live.  The mask is read directly, and only
+// where the unmasked rule finds something: 8 bytes for a mixed cell, up to 18 for a sign-changing edge -- no pre-pass, no extra
+// workspace.  Normals read the grid as before, at invalid points too.  The unmasked instantiations never touch the mask.
 // Built with -ffp-contract=off: every product and sum below is rounded on its own, as tests/mc_reference.py restates them.
 #include "scan.h"
 
@@ -65,14 +70,40 @@ __device__ inline Point decode(int p, int ny, int nz) {
   return q;
 }
 
+// rule M: the cell whose lowest corner is (i, j, k) exists and its eight corners are valid
+__device__ inline bool cell_live(const unsigned char* __restrict__ v, int i, int j, int k, int nx, int ny, int nz) {
+  if (i < 0 || j < 0 || k < 0 || i + 1 >= nx || j + 1 >= ny || k + 1 >= nz) return false;
+  const int X = ny * nz, Y = nz, p = (i * ny + j) * nz + k;
+  // (no short circuit: the eight byte loads are independent and go out together)
+  return ((v[p] != 0) & (v[p + 1] != 0) & (v[p + Y] != 0) & (v[p + Y + 1] != 0) & (v[p + X] != 0) & (v[p + X + 1] != 0) & (v[p + X + Y] != 0) &
+          (v[p + X + Y + 1] != 0)) != 0;
+}
+
+// rule M: one of the up to four cells that contain the edge from (i, j, k) to its +ax neighbour is live
+__device__ inline bool edge_live(const unsigned char* __restrict__ v, int i, int j, int k, int ax, int nx, int ny, int nz) {
+  const int u[3] = {ax == 0 ? 0 : 1, ax == 1 ? 0 : 1, ax == 2 ? 0 : 1};  // the cells step back along the two other axes
+  bool live = false;
+  for (int di = 0; di <= u[0]; ++di)
+    for (int dj = 0; dj <= u[1]; ++dj)
+      for (int dk = 0; dk <= u[2]; ++dk) live |= cell_live(v, i - di, j - dj, k - dk, nx, ny, nz);
+  return live;
+}
+
 // bit a: the edge from q to its +a neighbour has a vertex (NaN counts as outside: a comparison with NaN is false)
-__device__ inline unsigned edge_mask(const float* __restrict__ s, const Point& q, int nx, int ny, int nz, float level) {
+template <bool MASKED>
+__device__ inline unsigned edge_mask(const float* __restrict__ s, const unsigned char* __restrict__ valid, const Point& q, int nx, int ny,
+                                     int nz, float level) {
   const int nynz = ny * nz;
   const bool in0 = s[q.p] > level;
   unsigned m = 0;
   if (q.i + 1 < nx && (s[q.p + nynz] > level) != in0) m |= 1u;
   if (q.j + 1 < ny && (s[q.p + nz] > level) != in0) m |= 2u;
   if (q.k + 1 < nz && (s[q.p + 1] > level) != in0) m |= 4u;
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+      if ((m & (1u << ax)) && !edge_live(valid, q.i, q.j, q.k, ax, nx, ny, nz)) m &= ~(1u << ax);
+  }
   return m;
 }
 
@@ -87,6 +118,16 @@ __device__ inline int cube_row(const float* __restrict__ s, const Point& q, int 
   return c;
 }
 
+// triangles of the cell whose lowest corner is q, from its table row c (MASKED: none where the cell is not live)
+template <bool MASKED>
+__device__ inline int cell_faces(const unsigned char* __restrict__ valid, const Point& q, int c, int nx, int ny, int nz) {
+  if (!(c > 0 && c < 255)) return 0;
+  if constexpr (MASKED) {
+    if (!cell_live(valid, q.i, q.j, q.k, nx, ny, nz)) return 0;
+  }
+  return c_mc_ntri.n[c];
+}
+
 __device__ inline float lattice(float lo, int i, float step) { return lo + (float)i * step; }
 
 // d sigma / d x_a at lattice point p (index ia of na >= 2 along a): central inside, one-sided at the grid's faces
@@ -99,6 +140,7 @@ __device__ inline float grad_axis(const float* __restrict__ s, int p, int ia, in
 }  // namespace
 
 // grid = nb workgroups of MESH_WG
+template <bool MASKED>
 __global__ __launch_bounds__(MESH_WG) void k_mesh_count(const MeshArgs a) {
   __shared__ int part[MESH_WG / 64];
   const float* __restrict__ s = a.sigma;
@@ -112,9 +154,9 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_count(const MeshArgs a) {
     Point q{};
     if (pl < N) {
       q = decode((int)pl, a.ny, a.nz);
-      mask = edge_mask(s, q, a.nx, a.ny, a.nz, a.level);
+      mask = edge_mask<MASKED>(s, a.valid, q, a.nx, a.ny, a.nz, a.level);
       const int c = cube_row(s, q, a.nx, a.ny, a.nz, a.level);
-      nf = (c > 0 && c < 255) ? c_mc_ntri.n[c] : 0;
+      nf = cell_faces<MASKED>(a.valid, q, c, a.nx, a.ny, a.nz);
     }
     int tot_v, tot_f;
     const int pre_v = wg_prefix<MESH_WG, 2>(__popc(mask), part, tot_v);
@@ -142,6 +184,7 @@ __global__ __launch_bounds__(1024) void k_mesh_scan(const MeshArgs a, int nb) {
 }
 
 // grid = nb workgroups of MESH_WG
+template <bool MASKED>
 __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
   __shared__ int part[MESH_WG / 64];
   const float* __restrict__ s = a.sigma;
@@ -160,7 +203,7 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
     Point q{};
     if (pl < N) {
       q = decode((int)pl, ny, nz);
-      const unsigned mask = edge_mask(s, q, nx, ny, nz, a.level);
+      const unsigned mask = edge_mask<MASKED>(s, a.valid, q, nx, ny, nz, a.level);
       if (mask) {
         const int idx[3] = {q.i, q.j, q.k};
         float pa[3], ga[3];
@@ -200,7 +243,7 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
         }
       }
       c = cube_row(s, q, nx, ny, nz, a.level);
-      nf = (c > 0 && c < 255) ? c_mc_ntri.n[c] : 0;
+      nf = cell_faces<MASKED>(a.valid, q, c, nx, ny, nz);
     }
     int tot_f;
     const int pre_f = wg_prefix<MESH_WG, 3>(nf, part, tot_f);
@@ -229,13 +272,22 @@ __global__ __launch_bounds__(MESH_WG) void k_mesh_emit(const MeshArgs a) {
 
 hipError_t launch_mesh_count(const MeshArgs& a, hipStream_t st) {
   const int nb = mesh_blocks((long long)a.nx * a.ny * a.nz);
-  LAUNCH(k_mesh_count, dim3(nb), dim3(MESH_WG), 0, st, a);
+  if (a.valid) {
+    LAUNCH(k_mesh_count<true>, dim3(nb), dim3(MESH_WG), 0, st, a);
+  } else {
+    LAUNCH(k_mesh_count<false>, dim3(nb), dim3(MESH_WG), 0, st, a);
+  }
   LAUNCH(k_mesh_scan, dim3(1), dim3(1024), 0, st, a, nb);
   return hipSuccess;
 }
 
 hipError_t launch_mesh_emit(const MeshArgs& a, hipStream_t st) {
-  LAUNCH(k_mesh_emit, dim3(mesh_blocks((long long)a.nx * a.ny * a.nz)), dim3(MESH_WG), 0, st, a);
+  const int nb = mesh_blocks((long long)a.nx * a.ny * a.nz);
+  if (a.valid) {
+    LAUNCH(k_mesh_emit<true>, dim3(nb), dim3(MESH_WG), 0, st, a);
+  } else {
+    LAUNCH(k_mesh_emit<false>, dim3(nb), dim3(MESH_WG), 0, st, a);
+  }
   return hipSuccess;
 }
 

@@ -75,6 +75,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-tsdf-trunc", type=float, default=None, metavar="D",
                     help="truncation distance of --mesh-tsdf in world units (default: 4 lattice steps)")
     ap.add_argument("--mesh-tsdf-every", type=int, default=1, metavar="N", help="--mesh-tsdf fuses every N-th camera of the split (default 1)")
+    ap.add_argument("--mesh-tsdf-color", action="store_true",
+                    help="--mesh-tsdf fuses the colours the rendered views show beside their depth and colours the vertices from that volume; "
+                         "only vertices without a fused colour query the field; the file is <...>_tsdf_fused.ply (default: the field's colours)")
+    ap.add_argument("--mesh-tsdf-unseen", default="solid", choices=["solid", "empty", "skip"],
+                    help="what --mesh-tsdf makes of lattice points no view observed: solid (the mesh closes behind what was seen), empty, or "
+                         "skip -- masked marching cubes, only the surface the cameras saw; the file is <...>_tsdf_skip.ply (default solid)")
     ap.add_argument("--mesh-compare", default=None, metavar="FILE",
                     help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
                          "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
@@ -138,7 +144,8 @@ if __name__ == "__main__":
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,
                              simplify=args.mesh_simplify, smooth=args.mesh_smooth, compare=args.mesh_compare,
                              compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible,
-                             tsdf_from=args.mesh_tsdf, tsdf_trunc=args.mesh_tsdf_trunc, tsdf_every=args.mesh_tsdf_every)
+                             tsdf_from=args.mesh_tsdf, tsdf_trunc=args.mesh_tsdf_trunc, tsdf_every=args.mesh_tsdf_every,
+                             tsdf_color=args.mesh_tsdf_color, tsdf_unseen=args.mesh_tsdf_unseen)
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

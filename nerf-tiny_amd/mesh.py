@@ -5,7 +5,8 @@ edge topology, Taubin smoothing and face-derived vertex normals on the device (c
 evaluation on the device -- measures, area-weighted surface samples, exact nearest points, Chamfer distance and F-scores
 (csrc/mesh_distance.hip) --, rays against a mesh on the device -- closest hits, occlusion, depth images, the
 faces no camera sees (csrc/mesh_raycast.hip) --, TSDF fusion of depth images into a signed distance volume on the
-device (csrc/tsdf.hip) and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
+device (csrc/tsdf.hip), with the views' colours fused beside it and marching cubes under a mask of observed
+points, and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
 build on these."""
 from __future__ import annotations
 
@@ -22,20 +23,26 @@ class Mesh(NamedTuple):
     rgb: object      # [V, 3] fp32 colours, or None
 
 
-def marching_cubes(sigma, level, lo=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), ws=None):
+def marching_cubes(sigma, level, lo=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), ws=None, valid=None):
     """The isosurface sigma == level of a DEVICE grid sigma[nx, ny, nz] (C order, z fastest; e.g. model.density_grid, or the ``sigma``
     of an exported .npz moved to the device).  Lattice point (i, j, k) sits at lo + (i, j, k) * step, each coordinate one fp32 product
     and one fp32 sum (the density grid's rule: pass the .npz's ``lo`` and ``step``).  Inside is sigma > level.  Returns
     (verts [V, 3] fp32, faces [F, 3] int32, normals [V, 3] fp32) on sigma's device; the exact vertex, face and normal rules are in
-    include/nerf_hip.h.  A CPU tensor raises: there is no CPU path."""
+    include/nerf_hip.h.  valid=None: every lattice point counts.  valid = a bool or uint8 DEVICE tensor of sigma's shape: masked
+    marching cubes (rule M of include/nerf_hip.h) -- triangles only from the cells whose eight corners are valid, a vertex only on an
+    edge of such a cell; the result is, bit for bit, filter_faces of the unmasked mesh with the faces of the other cells dropped.  The
+    normals still read sigma at invalid points: fill them with a value of the class you want there.  A CPU tensor raises: there is no
+    CPU path."""
     from . import ops
 
     sigma = torch.as_tensor(sigma)
-    if sigma.device.type != "cuda":
+    if sigma.device.type != "cuda" or (valid is not None and torch.as_tensor(valid).device.type != "cuda"):
         raise RuntimeError("marching_cubes runs only on a ROCm device (MI355X): sigma.to('cuda'); there is no CPU path")
     lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
     step32 = np.asarray(step, dtype=np.float32).reshape(3)
-    return ops.marching_cubes(sigma, lo32.tolist(), step32.tolist(), float(np.float32(level)), ws=ws)
+    if valid is None:
+        return ops.marching_cubes(sigma, lo32.tolist(), step32.tolist(), float(np.float32(level)), ws=ws)
+    return ops.marching_cubes(sigma, lo32.tolist(), step32.tolist(), float(np.float32(level)), ws=ws, valid=torch.as_tensor(valid))
 
 
 class Components(NamedTuple):
@@ -631,12 +638,24 @@ def tsdf_volume(shape, device):
     return torch.zeros(shape, dtype=torch.float32, device=dev), torch.zeros(shape, dtype=torch.float32, device=dev)
 
 
+def tsdf_color_volume(shape, device):
+    """A zeroed colour state C beside tsdf_volume's (T, Wt): fp32 [nx, ny, nz, 4] on ``device`` -- per lattice point the mean colour
+    (R, G, B) of its colour observations and their number Wc -- for tsdf_integrate(rgb=, color=) and tsdf_sample_color."""
+    from .nerf import grid_shape
+
+    shape = grid_shape(shape)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("tsdf_color_volume: the volume lives on a ROCm device (MI355X); there is no CPU path")
+    return torch.zeros(shape + (4,), dtype=torch.float32, device=dev)
+
+
 def tsdf_trunc(step):
     """The default truncation distance of a lattice of fp32 ``step`` [3]: 4 x its largest step (a choice, not a measurement)."""
     return 4.0 * float(np.asarray(step, dtype=np.float32).reshape(3).max())
 
 
-def tsdf_integrate(T, Wt, lo, step, depth, poses_bound17, K_inv, opacity=None, trunc=None, min_opacity=0.5, carve=True):
+def tsdf_integrate(T, Wt, lo, step, depth, poses_bound17, K_inv, opacity=None, trunc=None, min_opacity=0.5, carve=True, rgb=None, color=None):
     """Integrates depth images into the TSDF state (T, Wt) IN PLACE on the DEVICE and returns it.  T, Wt: tsdf_volume's pair over the
     lattice lo + (i, j, k) * step (the density grid's: pass its lo and fp32 step).  depth [n, H, W] fp32: per pixel (row x, column y) of
     camera c the distance to the surface along the UNIT ray the renderer marches along -- render(maps=True)'s D / A, raycast()'s t over
@@ -645,9 +664,17 @@ def tsdf_integrate(T, Wt, lo, step, depth, poses_bound17, K_inv, opacity=None, t
     then marks every lattice point along its ray as empty, without carve it says nothing.  trunc: the truncation distance in world
     units, by default tsdf_trunc(step).  Every lattice point within trunc behind a view's surface, or in front of it, averages
     min(1, (depth - distance to the camera) / trunc) into T and counts 1 into Wt; the exact rule is T of include/nerf_hip.h and the
-    result does not depend on how the views are split over calls.  CPU tensors raise: there is no CPU path."""
+    result does not depend on how the views are split over calls.
+    rgb / color: both None (nothing more happens), or rgb [n, H, W, 3] fp32 -- the colour each view shows at each pixel -- and color,
+    tsdf_color_volume's C over the same lattice: the colours are fused IN PLACE beside the same geometry update (rule TC of
+    include/nerf_hip.h) and (T, Wt, C) is returned.  A view gives a lattice point its pixel's colour only where the point lies within
+    trunc of that view's surface, on either side; carved space and space far in front of the surface get none, nor does a pixel whose
+    colour is not finite.  C[..., :3] is the mean of those colours and C[..., 3] their number.  CPU tensors raise: there is no CPU
+    path."""
     from . import ops
 
+    if (rgb is None) != (color is None):
+        raise ValueError("tsdf_integrate: rgb and color are both given or both None")
     T, Wt = _on_device(T, "tsdf_integrate"), _on_device(Wt, "tsdf_integrate")
     depth = torch.as_tensor(depth)
     if depth.dim() != 3:
@@ -659,9 +686,29 @@ def tsdf_integrate(T, Wt, lo, step, depth, poses_bound17, K_inv, opacity=None, t
     lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
     step32 = np.asarray(step, dtype=np.float32).reshape(3)
     cams = [camera_q(pb[c], K_inv) for c in range(pb.shape[0])]
-    ops.tsdf_integrate(T, Wt, lo32.tolist(), step32.tolist(), depth, opacity, [cam.tolist() for _, cam in cams],
-                       [Q.reshape(-1).tolist() for Q, _ in cams], tsdf_trunc(step32) if trunc is None else float(trunc), min_opacity, carve)
-    return T, Wt
+    args = (T, Wt, lo32.tolist(), step32.tolist(), depth, opacity, [cam.tolist() for _, cam in cams], [Q.reshape(-1).tolist() for Q, _ in cams],
+            tsdf_trunc(step32) if trunc is None else float(trunc), min_opacity, carve)
+    if color is None:
+        ops.tsdf_integrate(*args)
+        return T, Wt
+    color = _on_device(color, "tsdf_integrate")
+    ops.tsdf_integrate(*args, rgb=_on_device(rgb, "tsdf_integrate"), color=color)
+    return T, Wt, color
+
+
+def tsdf_sample_color(C, lo, step, points):
+    """The fused colours at arbitrary points, on the DEVICE: C = tsdf_color_volume's state over the lattice lo + (i, j, k) * step,
+    points [M, 3] -> (rgb [M, 3] fp32, valid [M] bool).  Trilinear interpolation over the corners of the point's cell that have a colour
+    (Wc > 0), renormalised by their weights; valid is False, and rgb 0, where none of the eight has one or a coordinate is not finite.
+    A point outside the lattice takes the colour at the box's nearest face.  The exact rule is S of include/nerf_hip.h.  CPU tensors
+    raise: there is no CPU path."""
+    from . import ops
+
+    C, points = _on_device(C, "tsdf_sample_color"), _on_device(points, "tsdf_sample_color")
+    lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+    step32 = np.asarray(step, dtype=np.float32).reshape(3)
+    rgb, valid = ops.tsdf_sample_color(C, lo32.tolist(), step32.tolist(), points)
+    return rgb, valid != 0
 
 
 def tsdf_grid(T, Wt, unseen="solid"):

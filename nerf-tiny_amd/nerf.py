@@ -662,10 +662,12 @@ class NeRFModel(nn.Module):
         del sigma
         return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible)
 
-    def _mesh_stages(self, verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible):
+    def _mesh_stages(self, verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible, fused=None):
         """Everything of extract_mesh / extract_mesh_tsdf behind marching cubes, in extract_mesh's documented order: the component
         filter, the visibility filter, smoothing, simplification, then the field normals and the colours at the final vertices.
-        verts / faces / nrm: marching cubes' output over the lattice (lo32, hi32, shape)."""
+        verts / faces / nrm: marching cubes' output over the lattice (lo32, hi32, shape).  fused: None, or a colour volume over that
+        lattice (mesh.tsdf_color_volume's C) -- with color, the colours are then mesh.tsdf_sample_color(C) at the final vertices, the
+        field is queried only at the vertices that have no fused colour, and ``self.last_fused_fallback`` is their number."""
         from . import mesh
 
         if min_faces is not None or keep_largest is not None:
@@ -685,11 +687,18 @@ class NeRFModel(nn.Module):
             (verts, faces, nrm, _), _ = mesh.simplify(mesh.Mesh(verts, faces, None if normals == "field" else nrm, None), cell, lo32, dims)
         if normals == "field":
             nrm = field_normals(self.query_grad(verts)[2])
-        rgb = self.query(verts, -nrm)[0] if color else None
+        if color and fused is not None:
+            rgb, ok = mesh.tsdf_sample_color(fused, lo32, grid_step(lo32, hi32, shape), verts)
+            miss = torch.nonzero(~ok).view(-1)  # (one host read of their number)
+            self.last_fused_fallback = int(miss.numel())
+            if miss.numel():
+                rgb[miss] = self.query(verts[miss], -nrm[miss])[0]
+        else:
+            rgb = self.query(verts, -nrm)[0] if color else None
         return mesh.Mesh(verts, faces, nrm, rgb)
 
     @torch.no_grad()
-    def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None):
+    def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None, color=False):
         """TSDF fusion of the model's own rendered depth: every camera of views = (poses_bound [n, 17], K_inv, H, W) is rendered with
         render(maps=True), its expected depth image is integrated into a truncated signed distance volume over the density grid's lattice
         of the box [lo, hi] at res (mesh.tsdf_integrate; rule T of include/nerf_hip.h), and the state (T, Wt) -- two fp32 [nx, ny, nz]
@@ -705,7 +714,11 @@ class NeRFModel(nn.Module):
         depth, not the median: a ray that grazes a silhouette averages foreground and background.
         The views are rendered one at a time (each a render() call of H * W rays: ``bf16_mlp`` / ``split_mlp`` apply as in render) and
         integrated views_per_call at a time (default: the kernel's views per launch), so no more than views_per_call depth and opacity
-        images exist at once; the result does not depend on views_per_call."""
+        images exist at once; the result does not depend on views_per_call.
+        color=False: as above, and nothing more is allocated.  color=True: each view's C_fine of the same render(maps=True) call -- the
+        image the view shows, whichever depth pair is chosen -- is kept as well (at most views_per_call colour images at once) and
+        fused beside the depth (mesh.tsdf_integrate(rgb=, color=); rule TC of include/nerf_hip.h); the return is (T, Wt, C) with C
+        mesh.tsdf_color_volume's fp32 [nx, ny, nz, 4]: the mean colour the views show within trunc of their surface, and the count."""
         import numpy as np
 
         from . import mesh
@@ -726,23 +739,30 @@ class NeRFModel(nn.Module):
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
         step = grid_step(lo32, hi32, shape)
         T, Wt = mesh.tsdf_volume(shape, dev)
+        C = mesh.tsdf_color_volume(shape, dev) if color else None
         n = int(pb.shape[0])
         if n == 0:
-            return T, Wt
+            return (T, Wt, C) if color else (T, Wt)
         row = torch.arange(H, device=dev).repeat_interleave(W)
         col = torch.arange(W, device=dev).repeat(H)
         inf = torch.full((), float("inf"), device=dev)
         D = torch.empty(min(per_call, n), H, W, device=dev)
         A = torch.empty_like(D)
+        RGB = torch.empty(min(per_call, n), H, W, 3, device=dev) if color else None
         for v0 in range(0, n, per_call):
             k = min(per_call, n - v0)
             for c in range(k):
-                M = self.render(row, col, pb[v0 + c].to(dev).expand(H * W, 17), K_inv, maps=True)[2]
+                out = self.render(row, col, pb[v0 + c].to(dev).expand(H * W, 17), K_inv, maps=True)
+                M = out[2]
                 d, a = M[:, col0], M[:, col0 + 1]
                 D[c] = torch.where(a >= min_opacity, d / a, inf).view(H, W)
                 A[c] = a.view(H, W)
-            mesh.tsdf_integrate(T, Wt, lo32, step, D[:k], pb[v0:v0 + k], K_inv, opacity=A[:k], trunc=trunc, min_opacity=min_opacity, carve=carve)
-        return T, Wt
+                if color:
+                    RGB[c] = out[1].view(H, W, 3)
+            kw = dict(rgb=RGB[:k], color=C) if color else {}
+            mesh.tsdf_integrate(T, Wt, lo32, step, D[:k], pb[v0:v0 + k], K_inv, opacity=A[:k], trunc=trunc, min_opacity=min_opacity, carve=carve,
+                                **kw)
+        return (T, Wt, C) if color else (T, Wt)
 
     @torch.no_grad()
     def extract_mesh_tsdf(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, unseen="solid", color=True,
@@ -753,21 +773,35 @@ class NeRFModel(nn.Module):
         threshold enters.  normals="grid": the TSDF lattice's normals (its central differences, pointing outward); "field" and the
         colours query the field at the final vertices as in extract_mesh.  unseen="solid" (default): lattice points no view observed count
         as inside, so the mesh closes behind what the cameras saw; with unseen="empty", or with carve=False, a second sheet appears one
-        truncation distance behind the surface, where the observed band ends (there is no masked marching cubes).  Colours are queried
-        from the field, not fused from the views.  The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt)."""
+        truncation distance behind the surface, where the observed band ends.  unseen="skip": marching cubes runs masked with
+        valid = Wt > 0 (mesh.marching_cubes(valid=); rule M of include/nerf_hip.h) over the grid of "empty": triangles only from cells
+        whose eight corners some view observed -- the surface the cameras saw and nothing else, open where they saw nothing.
+        color=True: colours are queried from the field at the final vertices, seen along the inward normal; color=False: none.
+        color="fused": the views' colours are fused with their depth (fuse_depth(color=True)) and sampled at the final vertices
+        (mesh.tsdf_sample_color); only the vertices without a fused colour -- ``self.last_fused_fallback`` of them -- query the field.
+        The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt), or (T, Wt, C) with color="fused"."""
         import numpy as np
 
         from . import mesh
 
         _check_mesh_stages(normals, simplify, smooth)
+        if unseen not in ("solid", "empty", "skip"):
+            raise ValueError(f"unseen={unseen!r}: 'solid', 'empty' or 'skip'")
+        if not (color is True or color is False or color == "fused"):
+            raise ValueError(f"color={color!r}: True, False or 'fused'")
+        fuse_color = color == "fused"
         shape = grid_shape(res)
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
-        T, Wt = self.fuse_depth(views, lo32, hi32, shape, trunc=trunc, depth=depth, min_opacity=min_opacity, carve=carve,
-                                views_per_call=views_per_call)
-        self.last_tsdf = (T, Wt)
-        verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, unseen), 0.0, lo32, grid_step(lo32, hi32, shape))
-        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible)
+        self.last_tsdf = self.fuse_depth(views, lo32, hi32, shape, trunc=trunc, depth=depth, min_opacity=min_opacity, carve=carve,
+                                         views_per_call=views_per_call, color=fuse_color)
+        T, Wt = self.last_tsdf[:2]
+        if unseen == "skip":
+            verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, "empty"), 0.0, lo32, grid_step(lo32, hi32, shape), valid=Wt > 0)
+        else:
+            verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, unseen), 0.0, lo32, grid_step(lo32, hi32, shape))
+        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, bool(color), normals, min_faces, keep_largest, simplify, smooth, visible,
+                                 fused=self.last_tsdf[2] if fuse_color else None)
 
     @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False):

@@ -157,21 +157,31 @@ def density_band(params, lo, step, shape, level, block=8, ws=None, sigma=None, c
         info["points_evaluated"] += n_pts
 
 
-def marching_cubes(sigma, lo, step, level, ws=None):
+def marching_cubes(sigma, lo, step, level, ws=None, valid=None):
     """Isosurface sigma == level of a device grid sigma[nx, ny, nz] (nerf_hip_mesh_count + nerf_hip_mesh_emit): lo / step three host
     floats (lattice point (i, j, k) at lo + (i, j, k) * step) -> (verts[V, 3] fp32, faces[F, 3] int32, normals[V, 3] fp32) on sigma's
     device.  One count call, one 16-byte read of the counts (this synchronises with the stream), then the emit into buffers sized from
-    them.  ws: a uint8 device buffer of >= _abi.mesh_ws_bytes(nx, ny, nz) bytes (allocated here if None)."""
+    them.  ws: a uint8 device buffer of >= _abi.mesh_ws_bytes(nx, ny, nz) bytes (allocated here if None).  valid: None, or a bool /
+    uint8 device tensor of sigma's shape -- the masked calls (nerf_hip_mesh_count_masked + nerf_hip_mesh_emit_masked; rule M of
+    include/nerf_hip.h): triangles only from cells whose eight corners are valid."""
     if sigma.dim() != 3:
         raise ValueError(f"sigma {tuple(sigma.shape)}: a [nx, ny, nz] grid")
     nx, ny, nz = (int(n) for n in sigma.shape)
     dev = sigma.device
     sigma = sigma.to(torch.float32).contiguous()
+    if valid is not None:
+        if valid.shape != sigma.shape or valid.device != dev or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"valid {tuple(valid.shape)} {valid.dtype} on {valid.device}: a bool or uint8 tensor of sigma's shape {tuple(sigma.shape)} on {dev}")
+        valid = valid.to(torch.uint8).contiguous()
     if ws is None:
         ws = torch.empty(_abi.mesh_ws_bytes(nx, ny, nz), dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     L, st = _abi.lib(), _stream(sigma)
-    _abi.check(L.nerf_hip_mesh_count(sigma.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), ws.numel(), counts.data_ptr(), st))
+    if valid is None:
+        _abi.check(L.nerf_hip_mesh_count(sigma.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), ws.numel(), counts.data_ptr(), st))
+    else:
+        _abi.check(L.nerf_hip_mesh_count_masked(sigma.data_ptr(), valid.data_ptr(), nx, ny, nz, float(level), ws.data_ptr(), ws.numel(),
+                                                counts.data_ptr(), st))
     V, F = (int(n) for n in counts.cpu())
     if V >= 1 << 31 or F >= 1 << 31:
         raise ValueError(f"the mesh has {V} vertices and {F} faces: int32 face indices hold fewer than 2^31 of either "
@@ -181,8 +191,12 @@ def marching_cubes(sigma, lo, step, level, ws=None):
     faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
     if V == 0:
         return verts, faces, normals
-    _abi.check(L.nerf_hip_mesh_emit(sigma.data_ptr(), nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step), float(level), ws.data_ptr(),
-                                    ws.numel(), verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, F, st))
+    tail = (nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step), float(level), ws.data_ptr(), ws.numel(), verts.data_ptr(), normals.data_ptr(),
+            faces.data_ptr(), V, F, st)
+    if valid is None:
+        _abi.check(L.nerf_hip_mesh_emit(sigma.data_ptr(), *tail))
+    else:
+        _abi.check(L.nerf_hip_mesh_emit_masked(sigma.data_ptr(), valid.data_ptr(), *tail))
     return verts, faces, normals
 
 
@@ -560,15 +574,22 @@ def mesh_select_faces(verts, faces, normals, rgb, keep, ws=None):
     return ov, of, on, oc
 
 
-def tsdf_integrate(tsdf, weight, lo, step, depth, opacity, cam_o, Q, trunc, min_opacity=0.5, carve=True):
+def tsdf_integrate(tsdf, weight, lo, step, depth, opacity, cam_o, Q, trunc, min_opacity=0.5, carve=True, rgb=None, color=None):
     """Integrates the depth images depth[n, H, W] (fp32, device; opacity the same or None) of the cameras cam_o (n x 3 host floats) / Q
     (n x 9 host doubles, row-major) into the volumes tsdf / weight [nx, ny, nz] IN PLACE (nerf_hip_tsdf_integrate; rule T of
-    include/nerf_hip.h): contiguous fp32 device tensors on the lattice lo + (i, j, k) * step (three host floats each).  Enqueue only."""
+    include/nerf_hip.h): contiguous fp32 device tensors on the lattice lo + (i, j, k) * step (three host floats each).  rgb / color:
+    both None, or the views' colour images [n, H, W, 3] and the colour volume [nx, ny, nz, 4] -- then nerf_hip_tsdf_integrate_color
+    (rule TC) fuses the colours beside the same geometry update and (tsdf, weight, color) is returned.  Enqueue only."""
     if tsdf.dim() != 3 or tsdf.shape != weight.shape:
         raise ValueError(f"tsdf {tuple(tsdf.shape)} weight {tuple(weight.shape)}: two [nx, ny, nz] volumes")
-    for name, t in (("tsdf", tsdf), ("weight", weight)):
+    if (rgb is None) != (color is None):
+        raise ValueError("rgb and color: both or neither")
+    vols = (("tsdf", tsdf), ("weight", weight)) + ((("color", color),) if color is not None else ())
+    for name, t in vols:
         if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"{name}: a contiguous fp32 device tensor (it is updated in place)")
+    if color is not None and tuple(color.shape) != tuple(tsdf.shape) + (4,):
+        raise ValueError(f"color {tuple(color.shape)}: the volumes' shape {tuple(tsdf.shape)} and 4 channels (R, G, B, Wc)")
     if depth.dim() != 3:
         raise ValueError(f"depth {tuple(depth.shape)}: [n, H, W]")
     dev = tsdf.device
@@ -583,11 +604,37 @@ def tsdf_integrate(tsdf, weight, lo, step, depth, opacity, cam_o, Q, trunc, min_
     if len(cam) != 3 * n or len(q) != 9 * n:
         raise ValueError(f"cam_o / Q: three and nine entries for each of the {n} views")
     nx, ny, nz = (int(x) for x in tsdf.shape)
-    _abi.check(_abi.lib().nerf_hip_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step),
-                                                  depth.data_ptr(), opacity.data_ptr() if opacity is not None else None, n, H, W,
-                                                  _abi.f32_array(cam), (C.c_double * len(q))(*q), float(trunc), float(min_opacity),
-                                                  _abi.TSDF_CARVE if carve else 0, _stream(tsdf)))
-    return tsdf, weight
+    grid = (nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step))
+    op = opacity.data_ptr() if opacity is not None else None
+    tail = (n, H, W, _abi.f32_array(cam), (C.c_double * len(q))(*q), float(trunc), float(min_opacity), _abi.TSDF_CARVE if carve else 0,
+            _stream(tsdf))
+    if color is None:
+        _abi.check(_abi.lib().nerf_hip_tsdf_integrate(tsdf.data_ptr(), weight.data_ptr(), *grid, depth.data_ptr(), op, *tail))
+        return tsdf, weight
+    rgb = rgb.to(dev, torch.float32).contiguous()
+    if tuple(rgb.shape) != (n, H, W, 3):
+        raise ValueError(f"rgb {tuple(rgb.shape)}: a colour per pixel of the depth images, [{n}, {H}, {W}, 3]")
+    _abi.check(_abi.lib().nerf_hip_tsdf_integrate_color(tsdf.data_ptr(), weight.data_ptr(), color.data_ptr(), *grid, depth.data_ptr(), op,
+                                                        rgb.data_ptr(), *tail))
+    return tsdf, weight, color
+
+
+def tsdf_sample_color(color, lo, step, points):
+    """The colour volume color[nx, ny, nz, 4] (fp32 (R, G, B, Wc), device, contiguous) on the lattice lo + (i, j, k) * step sampled at
+    points[M, 3] (nerf_hip_tsdf_sample_color; rule S of include/nerf_hip.h) -> (rgb[M, 3] fp32, valid[M] uint8).  Enqueue only."""
+    if color.dim() != 4 or color.shape[3] != 4 or color.device.type != "cuda" or color.dtype != torch.float32 or not color.is_contiguous():
+        raise ValueError(f"color {tuple(color.shape)} {color.dtype}: a contiguous fp32 [nx, ny, nz, 4] device tensor")
+    dev = color.device
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points {tuple(points.shape)}: [M, 3]")
+    points = points.to(dev, torch.float32).contiguous()
+    M = int(points.shape[0])
+    rgb = torch.empty(M, 3, device=dev)
+    valid = torch.empty(M, dtype=torch.uint8, device=dev)
+    nx, ny, nz = (int(x) for x in color.shape[:3])
+    _abi.check(_abi.lib().nerf_hip_tsdf_sample_color(color.data_ptr(), nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step), points.data_ptr(),
+                                                     M, rgb.data_ptr(), valid.data_ptr(), _stream(color)))
+    return rgb, valid
 
 
 def distance_stats(dist2, unit, thresholds=()):

@@ -551,7 +551,7 @@ class NeRFRunner:
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
                      keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None,
-                     tsdf_from=None, tsdf_trunc=None, tsdf_every=1):
+                     tsdf_from=None, tsdf_trunc=None, tsdf_every=1, tsdf_color=False, tsdf_unseen="solid"):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -578,7 +578,11 @@ class NeRFRunner:
         that split over the same lattice (NeRFModel.extract_mesh_tsdf: truncation distance tsdf_trunc, None = 4 lattice steps; unseen
         space solid, background rays carve).  ``level`` and ``band`` are then ignored -- the ``[MESH] ... [TSDF]`` line says so, with
         the views, the lattice points observed and the truncation distance -- and the file name gets ``_tsdf`` before ``.ply``.  Without
-        it nothing new is computed, printed or written."""
+        it nothing new is computed, printed or written.  tsdf_color=True (with tsdf_from and color): the vertex colours are fused from
+        the same rendered views (NeRFModel.extract_mesh_tsdf(color="fused")); tsdf_unseen: "solid" (default), "empty" or "skip" -- "skip"
+        meshes only what the cameras observed (masked marching cubes).  With either, the ``[TSDF]`` line also counts the lattice points
+        with a fused colour and the vertices that fell back to the field, and the file name gets ``_fused`` and / or ``_skip`` after
+        ``_tsdf``.  Without them the line and the name are unchanged."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -601,15 +605,27 @@ class NeRFRunner:
                 raise ValueError(f"tsdf_from={tsdf_from!r}: None, 'train', 'val' or 'test'")
             if int(tsdf_every) != tsdf_every or int(tsdf_every) < 1:
                 raise ValueError(f"tsdf_every={tsdf_every!r}: an int >= 1")
+            if tsdf_unseen not in ("solid", "empty", "skip"):
+                raise ValueError(f"tsdf_unseen={tsdf_unseen!r}: 'solid', 'empty' or 'skip'")
+            fused = bool(tsdf_color) and bool(color)
+            extended = bool(tsdf_color) or tsdf_unseen != "solid"
+            if extended:
+                kw["unseen"] = tsdf_unseen
             rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[tsdf_from]
             poses = rays.poses[::int(tsdf_every)]
-            m = self.model.extract_mesh_tsdf((poses, self.K_inv, rays.height, rays.width), lo32, hi32, shape, trunc=tsdf_trunc, color=color,
-                                             normals=normals, min_faces=min_faces, keep_largest=keep_largest, simplify=simplify, smooth=smooth,
+            m = self.model.extract_mesh_tsdf((poses, self.K_inv, rays.height, rays.width), lo32, hi32, shape, trunc=tsdf_trunc,
+                                             color="fused" if fused else color, normals=normals, min_faces=min_faces,
+                                             keep_largest=keep_largest, simplify=simplify, smooth=smooth,
                                              **kw)
             Wt = self.model.last_tsdf[1]
             trunc = default_trunc(grid_step(lo32, hi32, shape)) if tsdf_trunc is None else float(tsdf_trunc)
+            more = ""
+            if extended:
+                coloured = int((self.model.last_tsdf[2][..., 3] > 0).sum()) if fused else 0
+                by_field = self.model.last_fused_fallback if fused else (len(m.verts) if color else 0)
+                more = f", {coloured} lattice points with a colour, {by_field} vertices coloured by the field"
             print(f"[MESH] {self.last_iter} [TSDF] {len(poses)} {tsdf_from} views fused, {int((Wt > 0).sum())} / {Wt.numel()} lattice points "
-                  f"observed, trunc {trunc:.6g} (level {level!r} ignored: the surface is the fused depth's)")
+                  f"observed, trunc {trunc:.6g}{more} (level {level!r} ignored: the surface is the fused depth's)")
         else:
             m = self.model.extract_mesh(lo32, hi32, shape, level, color=color, normals=normals, band=band, min_faces=min_faces,
                                         keep_largest=keep_largest, simplify=simplify, smooth=smooth, **kw)
@@ -620,7 +636,8 @@ class NeRFRunner:
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
-            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + ("" if tsdf_from is None else "_tsdf") + ".ply"
+            tsdf_tag = "" if tsdf_from is None else "_tsdf" + ("_fused" if fused else "") + ("_skip" if tsdf_unseen == "skip" else "")
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + tsdf_tag + ".ply"
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
             write_ply(path, out.verts, out.faces, out.normals, out.rgb)
