@@ -58,7 +58,9 @@ extern "C" {
                                      nerf_hip_points_nearest, nerf_hip_distance_stats; the nerf_hip_mesh_raycast* calls,
                                      nerf_hip_mesh_face_rays, nerf_hip_mesh_select_faces_*; nerf_hip_tsdf_integrate;
                                      nerf_hip_tsdf_integrate_color, nerf_hip_tsdf_sample_color, nerf_hip_mesh_count_masked,
-                                     nerf_hip_mesh_emit_masked */
+                                     nerf_hip_mesh_emit_masked; nerf_hip_coarse_composite_maps,
+                                     nerf_hip_coarse_composite_backward_maps, nerf_hip_merge_composite_train,
+                                     nerf_hip_merge_composite_backward */
 
 enum {
   NERF_HIP_OK = 0,
@@ -977,6 +979,37 @@ int nerf_hip_coarse_composite_backward(const float* t_c, const float* sigma_c, c
 int nerf_hip_merge_composite(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f,
                              const float* rgb_c, const float* rgb_f, int B, int Nc, int Nf, float last_delta,
                              float* bundle, float* w, float* C_fine, void* stream);
+
+/* nerf_hip_coarse_composite that also stores each ray's coarse depth and opacity (D_c = sum_i w_i t_c,i, A_c = sum_i w_i) to
+ * columns 0, 1 of maps [B,4] (required; columns 2, 3 untouched): the k_coarse_maps launch of nerf_hip_forward_maps. */
+int nerf_hip_coarse_composite_maps(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                   float delta0, int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f,
+                                   uint32_t* status, float* maps, void* stream);
+
+/* nerf_hip_coarse_composite_backward with the optional upstream gradient of the maps: dmaps [B,4] (columns 0, 1 = d loss/d D_c,
+ * d loss/d A_c are read; may be NULL, then this is nerf_hip_coarse_composite_backward).  ADDS to dsig_c / drgb_c like it. */
+int nerf_hip_coarse_composite_backward_maps(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                            float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
+                                            const float* dmaps, float* dsig_c, float* drgb_c, void* stream);
+
+/* The TRAINING form of nerf_hip_merge_composite, as nerf_hip_forward launches it with NERF_HIP_SAVE_FOR_BACKWARD: the five channel
+ * sorts carry each value's original slot (0..Nc-1 coarse, Nc..Nc+Nf-1 fine), which makes them stable, and
+ * perm [B,5,Nc+Nf] u16 (required) receives, per channel (0 = t, 1..3 = rgb, 4 = sigma), sorted position -> original slot.
+ * The order is torch.sort's: -0 == +0, every NaN last.  joint != 0 (NERF_HIP_CORRECTED): ONE stable sort by depth moves all five
+ * channels; perm then holds that permutation five times.  maps [B,4] (may be NULL): columns 2, 3 receive the fine depth and opacity
+ * D_f = sum_k w_k t_s,k, A_f = sum_k w_k over the sorted channels.  bundle and w may be NULL.  Nc >= 1, Nf >= 1, Nc + Nf <= 2048. */
+int nerf_hip_merge_composite_train(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f,
+                                   const float* rgb_c, const float* rgb_f, int B, int Nc, int Nf, float last_delta,
+                                   float* bundle, float* w, float* C_fine, uint16_t* perm, int joint, float* maps, void* stream);
+
+/* Backward of the merged composite and the channel sorts (autograd through nerf.py:302-321): in the sorted bundle [B,Nc+Nf,5] and
+ * perm [B,5,Nc+Nf] of nerf_hip_merge_composite_train, dC_fine [B,3] and the optional dmaps [B,4] (columns 2, 3 = d loss/d D_f,
+ * d loss/d A_f are read; may be NULL).  WRITES every element of dsig_c [B,Nc], dsig_f [B,Nf], drgb_c [B,Nc,3], drgb_f [B,Nf,3]
+ * (un-sorted through each channel's own permutation) and dt_f [B,Nf] (through the sorted deltas; t_coarse carries no gradient).
+ * perm must hold a permutation of 0..Nc+Nf-1 per channel: a repeated slot leaves another unwritten.  Sizes as the forward's. */
+int nerf_hip_merge_composite_backward(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps,
+                                      int B, int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
+                                      float* drgb_f, float* dt_f, void* stream);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,11 @@ _PROTOS = {
     "nerf_hip_coarse_composite": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "nerf_hip_coarse_composite_backward": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "nerf_hip_merge_composite": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p]),
+    "nerf_hip_coarse_composite_maps": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_coarse_composite_backward_maps": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_merge_composite_train": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_int, _p,
+                                                 _p]),
+    "nerf_hip_merge_composite_backward": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, _p, _p]),
     "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),

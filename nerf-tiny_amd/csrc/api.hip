@@ -915,4 +915,63 @@ int nerf_hip_merge_composite(const float* t_c, const float* t_f, const float* si
   return NERF_HIP_OK;
 }
 
+int nerf_hip_coarse_composite_maps(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far, float delta0,
+                                   int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
+                                   void* stream) {
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  CoarseArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
+  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
+  ca.delta0_mode = 1; ca.delta0 = delta0;
+  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
+  HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream), maps));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_coarse_composite_backward_maps(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                            float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
+                                            const float* dmaps, float* dsig_c, float* drgb_c, void* stream) {
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  CoarseBwdArgs cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c; cb.near_far = near_far;
+  cb.B = B; cb.Nc = Nc; cb.Nf = Nf; cb.delta0_mode = 1; cb.delta0 = delta0;
+  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
+  if (dmaps) HIP_TRY(launch_coarse_bwd_maps(cb, dmaps, static_cast<hipStream_t>(stream)));
+  else HIP_TRY(launch_coarse_bwd(cb, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_merge_composite_train(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f, const float* rgb_c,
+                                   const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
+                                   uint16_t* perm, int joint, float* maps, void* stream) {
+  if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !perm) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  MergeArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
+  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
+  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
+  HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), maps));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_merge_composite_backward(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps, int B, int Nc,
+                                      int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c, float* drgb_f, float* dt_f,
+                                      void* stream) {
+  if (!bundle || !perm || !dC_fine || !dsig_c || !dsig_f || !drgb_c || !drgb_f || !dt_f) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  MergeBwdArgs mb;
+  memset(&mb, 0, sizeof(mb));
+  mb.dC_f = dC_fine; mb.bundle = bundle; mb.perm = perm;
+  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
+  mb.drgb_c = drgb_c; mb.dsig_c = dsig_c; mb.drgb_f = drgb_f; mb.dsig_f = dsig_f; mb.dt_f = dt_f;
+  if (dmaps) HIP_TRY(launch_merge_bwd_maps(mb, dmaps, static_cast<hipStream_t>(stream)));
+  else HIP_TRY(launch_merge_bwd(mb, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
 }  // extern "C"

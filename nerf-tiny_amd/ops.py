@@ -716,3 +716,72 @@ def coarse_composite_backward(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f
                                                              dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(),
                                                              dsig.data_ptr(), drgb.data_ptr(), _stream(t_c)))
     return dsig, drgb
+
+
+def coarse_composite_maps(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
+    """coarse_composite through k_coarse_maps -> w_c, C_coarse, t_f, status(int), maps[B,4] (columns 0, 1 written; 2, 3 left NaN)"""
+    B, Nc = t_c.shape
+    dev = t_c.device
+    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    w_c = torch.empty(B, Nc, device=dev)
+    C_c = torch.empty(B, 3, device=dev)
+    t_f = torch.empty(B, Nf, device=dev)
+    maps = torch.full((B, 4), float("nan"), device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_coarse_composite_maps(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
+                                                         rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), B, Nc, Nf,
+                                                         w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
+                                                         _stream(t_c)))
+    return w_c, C_c, t_f, int(status.item()), maps
+
+
+def coarse_composite_backward_add(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb, dmaps=None, rays=None):
+    """ADDS the coarse stage's gradients of the first `rays` rays (default: all) to dsig[B,Nc], drgb[B,Nc,3] in place; dmaps[B,4]: the
+    optional upstream of the coarse maps (k_coarse_bwd_maps)"""
+    B, Nc = t_c.shape
+    Nf = dt_f.shape[1]
+    rays = B if rays is None else int(rays)
+    if not (1 <= rays <= B and dsig.shape == (B, Nc) and drgb.shape == (B, Nc, 3) and dsig.is_contiguous() and drgb.is_contiguous()):
+        raise ValueError("coarse_composite_backward_add: contiguous dsig [B,Nc] / drgb [B,Nc,3] and 1 <= rays <= B")
+    nf = torch.stack((near, far), dim=1).contiguous().to(t_c.device)
+    _abi.check(_abi.lib().nerf_hip_coarse_composite_backward_maps(
+        t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(), rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
+        dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
+        dsig.data_ptr(), drgb.data_ptr(), _stream(t_c)))
+    return dsig, drgb
+
+
+def merge_composite_train(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last=1e-4, joint=False, maps=False):
+    """the training form of merge_composite (k_merge<true>) -> bundle[B,N,5], w[B,N], C_fine[B,3], perm[B,5,N] int16 (sorted position ->
+    original slot per channel), maps[B,4] (columns 2, 3 written; 0, 1 left NaN) or None"""
+    B, Nc = t_c.shape
+    Nf = t_f.shape[1]
+    dev = t_c.device
+    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
+    w = torch.empty(B, Nc + Nf, device=dev)
+    C_f = torch.empty(B, 3, device=dev)
+    perm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev)
+    M = torch.full((B, 4), float("nan"), device=dev) if maps else None
+    _abi.check(_abi.lib().nerf_hip_merge_composite_train(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
+                                                         sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
+                                                         rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
+                                                         float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), perm.data_ptr(),
+                                                         int(bool(joint)), None if M is None else M.data_ptr(), _stream(t_c)))
+    return bundle, w, C_f, perm, M
+
+
+def merge_composite_backward(bundle, perm, dC_f, Nc, last=1e-4, dmaps=None):
+    """backward of merge_composite_train -> dsig_c[B,Nc], dsig_f[B,Nf], drgb_c[B,Nc,3], drgb_f[B,Nf,3], dt_f[B,Nf]; the outputs start as NaN:
+    the kernel writes every element"""
+    B, N, _ = bundle.shape
+    Nf = N - Nc
+    dev = bundle.device
+    if perm.dtype != torch.int16 or perm.shape != (B, 5, N):
+        raise ValueError("merge_composite_backward: perm is int16 [B,5,N]")
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    dsig_c, dsig_f, drgb_c, drgb_f, dt_f = nan(B, Nc), nan(B, Nf), nan(B, Nc, 3), nan(B, Nf, 3), nan(B, Nf)
+    _abi.check(_abi.lib().nerf_hip_merge_composite_backward(bundle.contiguous().data_ptr(), perm.contiguous().data_ptr(),
+                                                            dC_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
+                                                            B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(), drgb_c.data_ptr(),
+                                                            drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle)))
+    return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
