@@ -60,7 +60,9 @@ extern "C" {
                                      nerf_hip_tsdf_integrate_color, nerf_hip_tsdf_sample_color, nerf_hip_mesh_count_masked,
                                      nerf_hip_mesh_emit_masked; nerf_hip_coarse_composite_maps,
                                      nerf_hip_coarse_composite_backward_maps, nerf_hip_merge_composite_train,
-                                     nerf_hip_merge_composite_backward */
+                                     nerf_hip_merge_composite_backward; nerf_hip_forward_quantiles,
+                                     nerf_hip_coarse_composite_quantiles, nerf_hip_merge_composite_quantiles
+                                     (with NERF_HIP_MAX_QUANTILES) */
 
 enum {
   NERF_HIP_OK = 0,
@@ -166,6 +168,44 @@ int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, con
                           const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
                           int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
                           void* ws, size_t ws_bytes, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Quantile depths: where along the ray the weight sits, beside the maps' mean D / A.
+ *
+ * QD. THE QUANTILE RULE, for one pass of one ray: samples t_0 .. t_{N-1} in the order the composite visits them, with the composite's own
+ *    fp32 weights w_i.  Coarse pass: t_c with w_c.  Fine pass: the SORTED depth channel t_s with the w of C_fine -- without
+ *    NERF_HIP_CORRECTED it inherits quirk Q1 exactly as D_f does (the five channels are sorted independently), with NERF_HIP_CORRECTED it
+ *    is physical.  All arithmetic is fp64 on the fp32 inputs widened exactly; every operation is rounded on its own; every comparison is
+ *    false on NaN.
+ *       W_i   = the inclusive prefix sum of w, formed as the kernels form the cdf: inside each chunk of 64 samples (the last one padded
+ *               with zeros) the Hillis-Steele steps d = 1, 2, 4, .. 32 (v_l += v_{l-d} for l >= d, all l at once), then + carry, the
+ *               carry being element 63 of the chunk before (0 for the first).  This order is part of the rule.
+ *       W     = W_{N-1};   theta = double(q) * W                           for a quantile q (fp32, 0 < q < 1)
+ *       k     = the first i with W_i >= theta;   E = W_{k-1} (0 for k = 0)
+ *       f     = (theta - E) / double(w_k);  f = f > 0 ? f : 0;  f = f < 1 ? f : 1
+ *       t_nxt = t_{k+1} if k + 1 < N, else t_k                             (the last sample is never extrapolated: last_delta may be 1e10)
+ *       Q(q)  = fp32(double(t_k) + f * (double(t_nxt) - double(t_k)))
+ *    If no such k exists (W is NaN, or no W_i reaches theta), or w_k is not > 0 (W = 0: k = 0 with w_0 = 0), Q(q) = t_{N-1}: the pass's
+ *    opacity A already tells the caller that the ray hit nothing.
+ *    Q(q) is the q-quantile of the ray's normalised hit distribution -- the distribution whose mean is D / A --, linearly interpolated
+ *    inside the sample interval.  Q(0.5) is the median depth.  Not differentiable; inference only.
+ *
+ * nerf_hip_forward_quantiles: the arguments of nerf_hip_forward_maps, then
+ *   q       HOST [nq] f32: the quantiles, each strictly inside (0, 1); they travel in the kernels' arguments
+ *   nq      1 .. NERF_HIP_MAX_QUANTILES
+ *   qdepth  [B,2,nq] f32 out, device: row 0 = Q_c(q_j) of the coarse pass, row 1 = Q_f(q_j) of the fine pass
+ * It runs in every inference mode nerf_hip_forward_maps runs in; C_coarse, C_fine, maps, the status word and the workspace are that
+ * call's, bit for bit (k_coarse_qmaps / k_merge_qmaps: the maps kernels with one more loop per ray; small bf16-MLP batches take the
+ * separate launches, as a maps call does).  NERF_HIP_ERR_ARG before any device work: nq < 1 or nq > NERF_HIP_MAX_QUANTILES, a NULL q or
+ * qdepth, a q that is NaN or not strictly inside (0, 1), a NULL maps, NERF_HIP_SAVE_FOR_BACKWARD.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_MAX_QUANTILES 4
+
+int nerf_hip_forward_quantiles(const float* const* weights24, const int64_t* row, const int64_t* col,
+                               const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
+                               int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
+                               void* ws, size_t ws_bytes, int flags, void* stream,
+                               const float* q /* HOST [nq] */, int nq, float* qdepth /* device [B][2][nq]: row 0 coarse, row 1 fine */);
 
 /*
  * nerf_hip_forward_maps for TRAINING (the maps are differentiable through nerf_hip_backward_maps).  The arguments of
@@ -1001,6 +1041,21 @@ int nerf_hip_coarse_composite_backward_maps(const float* t_c, const float* sigma
 int nerf_hip_merge_composite_train(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f,
                                    const float* rgb_c, const float* rgb_f, int B, int Nc, int Nf, float last_delta,
                                    float* bundle, float* w, float* C_fine, uint16_t* perm, int joint, float* maps, void* stream);
+
+/* The stage entries of nerf_hip_forward_quantiles (rule QD above; q / nq / qdepth [B,2,nq] and their refusals as there, maps required).
+ * nerf_hip_coarse_composite_quantiles: the arguments of nerf_hip_coarse_composite_maps, then q, nq, qdepth -- the k_coarse_qmaps launch;
+ * every output it shares with nerf_hip_coarse_composite_maps has that call's bits, and row 0 of qdepth is written (row 1 untouched).  With
+ * delta0 given, Nc = 1 is accepted here (a one-sample ray: Q = t_0).
+ * nerf_hip_merge_composite_quantiles: the arguments of nerf_hip_merge_composite_train, then q, nq, qdepth -- the k_merge_qmaps launch;
+ * shared outputs as that call's, row 1 of qdepth written (row 0 untouched).  perm may be NULL when joint == 0: the values-only sort of
+ * inference (the same bundle, weights, colour and maps). */
+int nerf_hip_coarse_composite_quantiles(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                        float delta0, int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f,
+                                        uint32_t* status, float* maps, void* stream, const float* q, int nq, float* qdepth);
+int nerf_hip_merge_composite_quantiles(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f,
+                                       const float* rgb_c, const float* rgb_f, int B, int Nc, int Nf, float last_delta,
+                                       float* bundle, float* w, float* C_fine, uint16_t* perm, int joint, float* maps, void* stream,
+                                       const float* q, int nq, float* qdepth);
 
 /* Backward of the merged composite and the channel sorts (autograd through nerf.py:302-321): in the sorted bundle [B,Nc+Nf,5] and
  * perm [B,5,Nc+Nf] of nerf_hip_merge_composite_train, dC_fine [B,3] and the optional dmaps [B,4] (columns 2, 3 = d loss/d D_f,

@@ -23,6 +23,7 @@ STATUS_PREP_TIMEOUT = 1 << 1
 SIMPLIFY_TABLE_FULL = 1 << 0
 EDGES_TABLE_FULL = 1 << 0
 TSDF_CARVE = 1 << 0
+MAX_QUANTILES = 4  # NERF_HIP_MAX_QUANTILES: quantiles of one nerf_hip_forward_quantiles call (they travel in the kernels' arguments)
 TSDF_VIEWS_PER_LAUNCH = 32  # NERF_HIP_TSDF_VIEWS_PER_LAUNCH: views whose cameras travel in one launch's kernel arguments
 
 _p = C.c_void_p
@@ -34,6 +35,8 @@ _PROTOS = {
     "nerf_hip_forward": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, C.c_size_t, C.c_int, _p]),
     "nerf_hip_forward_maps": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_size_t, C.c_int,
                                         _p]),
+    "nerf_hip_forward_quantiles": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_size_t, C.c_int,
+                                             _p, _p, C.c_int, _p]),
     "nerf_hip_forward_maps_train": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_size_t,
                                               C.c_int, _p]),
     "nerf_hip_backward": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, C.c_size_t, C.c_int, _p]),
@@ -57,6 +60,10 @@ _PROTOS = {
     "nerf_hip_coarse_composite_backward_maps": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p]),
     "nerf_hip_merge_composite_train": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_int, _p,
                                                  _p]),
+    "nerf_hip_coarse_composite_quantiles": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, C.c_int,
+                                                      _p]),
+    "nerf_hip_merge_composite_quantiles": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_int, _p,
+                                                     _p, _p, C.c_int, _p]),
     "nerf_hip_merge_composite_backward": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, _p, _p]),
     "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),

@@ -250,7 +250,20 @@ struct TrainLoss {
 // else null.  A maps call always takes the separate k_coarse / k_merge launches (never the pair kernel, never the FwdFuse epilogues)
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr);
+                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr);
+// nerf_hip_forward_quantiles and its stage entries: the checks they share, before any device work
+int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) {
+  static_assert(MAX_QUANTILES == NERF_HIP_MAX_QUANTILES, "kernels.h and nerf_hip.h disagree");
+  if (nq < 1 || nq > NERF_HIP_MAX_QUANTILES) return fail(NERF_HIP_ERR_ARG, "nq=%d: 1 .. %d quantiles per call", nq, NERF_HIP_MAX_QUANTILES);
+  if (!q || !qdepth) return fail(NERF_HIP_ERR_ARG, "q or qdepth is null");
+  memset(&qa, 0, sizeof(qa));
+  qa.nq = nq;
+  for (int j = 0; j < nq; ++j) {
+    if (!(q[j] > 0.f && q[j] < 1.f)) return fail(NERF_HIP_ERR_ARG, "q[%d]=%g: a quantile lies strictly inside (0, 1)", j, (double)q[j]);
+    qa.q[j] = q[j];
+  }
+  return NERF_HIP_OK;
+}
 // dmaps: nerf_hip_backward_maps's [B][4] upstream of the maps (its caller has checked it), else null.  A dmaps call always takes the
 // separate k_merge_bwd_maps / k_coarse_bwd_maps launches (never the BwdFuse prologues)
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
@@ -276,6 +289,18 @@ int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, con
                       nullptr, maps);
 }
 
+int nerf_hip_forward_quantiles(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
+                               const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
+                               float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream, const float* q, int nq,
+                               float* qdepth) {
+  if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_quantiles is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
+  if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
+  QuantArgs qa;
+  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
+  return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
+                      nullptr, maps, &qa, qdepth);
+}
+
 int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
                                 const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
                                 float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream) {
@@ -292,7 +317,7 @@ namespace {
 
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps) {
+                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
@@ -426,7 +451,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     ff.mode = 0;
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_COARSE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(launch_coarse(ca, st, maps)); }
+    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(qa ? launch_coarse_quantiles(ca, maps, *qa, qdepth, st) : launch_coarse(ca, st, maps)); }
   }
 
   // fine pass (nerf.py:299), same network (quirk Q10)
@@ -454,7 +479,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(launch_merge(ma, st, maps)); }
+    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(qa ? launch_merge_quantiles(ma, maps, *qa, qdepth, st) : launch_merge(ma, st, maps)); }
   }
   return NERF_HIP_OK;
 }
@@ -956,6 +981,39 @@ int nerf_hip_merge_composite_train(const float* t_c, const float* t_f, const flo
   ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
   ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
   HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), maps));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_coarse_composite_quantiles(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far, float delta0,
+                                        int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
+                                        void* stream, const float* q, int nq, float* qdepth) {
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  QuantArgs qa;
+  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
+  CoarseArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
+  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
+  ca.delta0_mode = 1; ca.delta0 = delta0;
+  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
+  HIP_TRY(launch_coarse_quantiles(ca, maps, qa, qdepth, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_merge_composite_quantiles(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f, const float* rgb_c,
+                                       const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
+                                       uint16_t* perm, int joint, float* maps, void* stream, const float* q, int nq, float* qdepth) {
+  if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  QuantArgs qa;
+  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
+  MergeArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
+  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
+  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
+  HIP_TRY(launch_merge_quantiles(ma, maps, qa, qdepth, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

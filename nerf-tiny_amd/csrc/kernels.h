@@ -199,6 +199,16 @@ hipError_t launch_prep_bf16(const Weights24& w, float* fold, unsigned char* img_
 hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps = nullptr);
 size_t merge_lds_bytes(int P);
 hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps = nullptr);
+// nerf_hip_forward_quantiles: k_coarse_qmaps / k_merge_qmaps -- the maps kernels, which also store each ray's quantile depths (rule QD of
+// include/nerf_hip.h) to qdepth [B][2][nq], row 0 by the coarse kernel, row 1 by the merge kernel.  The quantiles travel as a kernel argument
+// of their own (like the maps pointer: CoarseArgs / MergeArgs ride inside FwdFuse)
+constexpr int MAX_QUANTILES = 4;  // = NERF_HIP_MAX_QUANTILES
+struct QuantArgs {
+  float q[MAX_QUANTILES];
+  int nq;
+};
+hipError_t launch_coarse_quantiles(const CoarseArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
+hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st);
 
 }  // namespace nerf

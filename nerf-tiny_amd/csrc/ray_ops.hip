@@ -4,6 +4,7 @@
 //   k_coarse            sigma -> weights (inclusive transmittance), C_coarse, inverse-CDF resampling
 //   k_merge             merge coarse+fine, five independent channel sorts, composite -> C_fine
 //   k_coarse_maps / k_merge_maps   the same, plus each ray's expected depth and opacity (nerf_hip_forward_maps)
+//   k_coarse_qmaps / k_merge_qmaps the maps kernels, plus each ray's quantile depths (nerf_hip_forward_quantiles, rule QD)
 //   k_ray_loss          sum-of-squares loss and its gradient
 // One 64-lane wave owns one ray: the transmittance cumsum / CDF are wave scans (fp64 accumulator like
 // ATen's CPU cumsum, rounded to fp32 per element), searchsorted is a per-lane binary search in LDS and
@@ -58,6 +59,16 @@ __global__ __launch_bounds__(256) void k_coarse_maps(const CoarseArgs a, float* 
   coarse_ray_stage<true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps);
 }
 
+// k_coarse_qmaps: k_coarse_maps that also stores each live ray's coarse quantile depths (rule QD of include/nerf_hip.h) to row 0 of
+// qdepth [B][2][nq] (nerf_hip_forward_quantiles).  The quantiles and the pointer are kernel arguments of their own, for k_coarse_maps's reason.
+__global__ __launch_bounds__(256) void k_coarse_qmaps(const CoarseArgs a, float* maps, const QuantArgs qa, float* qdepth) {
+  __shared__ float s_w[4][MAXN];
+  __shared__ float s_cdf[4][MAXN];
+  __shared__ float s_t[4][MAXN];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  coarse_ray_stage<true, true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps, &qa, qdepth);
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_merge: nerf.py:302-321.  cat -> sort(dim=1) of a [B,N,5] bundle = five INDEPENDENT ascending channel
 // sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine.
@@ -81,6 +92,16 @@ __global__ __launch_bounds__(64) void k_merge_maps(const MergeArgs a, float* map
   float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
   uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
   merge_ray_stage<WITH_IDX, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps);
+}
+
+// k_merge_qmaps: k_merge_maps that also stores each ray's fine quantile depths (rule QD) to row 1 of qdepth [B][2][nq]
+// (nerf_hip_forward_quantiles).  Both sort paths and the joint mode end in the same merge_ray_composite, as for k_merge_maps.
+template <bool WITH_IDX>
+__global__ __launch_bounds__(64) void k_merge_qmaps(const MergeArgs a, float* maps, const QuantArgs qa, float* qdepth) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
+  uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
+  merge_ray_stage<WITH_IDX, true, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps, &qa, qdepth);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -145,6 +166,21 @@ hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps) {
     hipLaunchKernelGGL(k_merge<false>, dim3(a.B), dim3(64), lds, st, a);
   }
   return hipGetLastError();
+}
+hipError_t launch_coarse_quantiles(const CoarseArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st) {
+  hipLaunchKernelGGL(k_coarse_qmaps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps, qa, qdepth);
+  return hipGetLastError();
+}
+template <bool WITH_IDX>
+hipError_t launch_merge_qmaps(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_qmaps<WITH_IDX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  hipLaunchKernelGGL(k_merge_qmaps<WITH_IDX>, dim3(a.B), dim3(64), lds, st, a, maps, qa, qdepth);
+  return hipGetLastError();
+}
+hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st) {
+  const size_t lds = merge_lds_bytes(a.P);
+  return (a.perm || a.joint) ? launch_merge_qmaps<true>(a, maps, qa, qdepth, lds, st) : launch_merge_qmaps<false>(a, maps, qa, qdepth, lds, st);
 }
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st) {
   hipLaunchKernelGGL(k_ray_loss, dim3(1), dim3(1024), 0, st, Cc, Cf, Ct, B * 3, loss, dCc, dCf);

@@ -37,6 +37,56 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Rule QD (include/nerf_hip.h): the quantile depths of ONE pass of one ray -- the q-quantiles of the hit distribution whose weights are
+// w [N] and whose depths are t [N] (both LDS, in the order the composite visited them), W = the inclusive fp64 scan's last element as the
+// composite loop formed it (wave-uniform).  The loop re-forms that scan chunk by chunk (the same wave_incl_scan + carry: the same W_i),
+// takes per quantile a ballot of W_i >= theta, and the first set lane interpolates inside its sample interval from its own w_k, t_k, its
+// neighbour's E = W_{k-1} (the carry for lane 0) and t_{k+1}; lane 0 stores out [nq] (null: nothing stored).  Every lane reads only w slots
+// that it wrote itself; t is read where the composite loop read it.  No barrier.
+__device__ __forceinline__ void ray_quantile_depths(const float* w, const float* t, int N, double W, int lane, const QuantArgs& qa, float* out) {
+  const float t_last = t[N - 1];
+  float res[MAX_QUANTILES];
+  double theta[MAX_QUANTILES];
+  unsigned todo = 0;
+#pragma unroll
+  for (int j = 0; j < MAX_QUANTILES; ++j) {
+    res[j] = t_last;  // no k, or w_k not > 0: the last sample's depth
+    theta[j] = (double)qa.q[j] * W;
+    if (j < qa.nq) todo |= 1u << j;
+  }
+  double carry = 0.0;
+  for (int base = 0; base < N && todo; base += 64) {
+    const int i = base + lane;
+    const bool v = i < N;
+    const float wi = v ? w[i] : 0.f;
+    const float tk = v ? t[i] : 0.f;
+    const float tn = (v && i + 1 < N) ? t[i + 1] : tk;  // (the last sample is never extrapolated)
+    const double Wi = wave_incl_scan((double)wi, lane) + carry;
+    const double up = __shfl_up(Wi, 1);
+    const double E = lane ? up : carry;  // W_{i-1}
+    carry = __shfl(Wi, 63);
+#pragma unroll
+    for (int j = 0; j < MAX_QUANTILES; ++j) {
+      if (!(todo & (1u << j))) continue;
+      const unsigned long long hit = __ballot(v && Wi >= theta[j]);
+      if (!hit) continue;
+      todo &= ~(1u << j);
+      float r = t_last;
+      if (wi > 0.f) {
+        double f = (theta[j] - E) / (double)wi;
+        f = f > 0.0 ? f : 0.0;  // (false on NaN: 0)
+        f = f < 1.0 ? f : 1.0;
+        r = (float)((double)tk + f * ((double)tn - (double)tk));
+      }
+      res[j] = __shfl(r, __ffsll((long long)hit) - 1);
+    }
+  }
+  if (lane == 0 && out) {
+#pragma unroll
+    for (int j = 0; j < MAX_QUANTILES; ++j)
+      if (j < qa.nq) out[j] = res[j];
+  }
+}
 
 // coarse spacing of ray 0 as the reference takes it (quirk Q6, nerf.py:233): t[0][1] - t[0][0] of numpy.linspace(near, far, Nc)
 __device__ __forceinline__ float ray0_spacing(float n0, float f0, int Nc) {
@@ -50,10 +100,12 @@ __device__ __forceinline__ float ray0_spacing(float n0, float f0, int Nc) {
 // min / max of the cdf (nerf.py:240-241).  The caller orders the LDS writes before coarse_ray_resample's reads.
 // MAPS (nerf_hip_forward_maps): also the ray's coarse depth and opacity D_c = sum_i w_i t_c,i, A_c = sum_i w_i -- fp32 per lane, then wave_sum,
 // as the colour sums -- stored by lane 0 to maps_out[0..1] (null: nothing stored).  Without MAPS the code is the colour-only one.
-template <bool MAPS = false>
+// QD (nerf_hip_forward_quantiles): also hands out W = the last element of the fp64 scan of w (the cdf's, before its rounding to fp32) in
+// W_out, for ray_quantile_depths over the w / tc this function leaves in LDS.
+template <bool MAPS = false, bool QD = false>
 __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const float* rgb, const float* t_c, float near, float far, int Nc, int lane,
                                                    float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out,
-                                                   float* maps_out = nullptr) {
+                                                   float* maps_out = nullptr, double* W_out = nullptr) {
   const float delta_c = (far - near) / (float)Nc;
   double carry = 0.0, carry2 = 0.0;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
@@ -106,6 +158,7 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
       maps_out[1] = asum;
     }
   }
+  if constexpr (QD) *W_out = carry2;
 }
 
 // resample (nerf.py:225-261): u_j = lo + j * ((hi - lo)/(Nf+1)), j = 1..Nf (numpy.linspace(lo, hi, Nf+2)[1:-1] in fp32, nerf.py:243-246),
@@ -300,20 +353,20 @@ __device__ __forceinline__ void merge_channel_job(const MergeArgs& a, const int 
   *reinterpret_cast<uint2*>(idx + 4 * lane) = pk;
 }
 
-template <bool WITH_IDX, bool MAPS = false>
+template <bool WITH_IDX, bool MAPS = false, bool QD = false>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
                                                     float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret = nullptr,
-                                                    float* maps_out = nullptr);
+                                                    float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr);
 
 // nerf.py:302-321 behind the load: val [5][P] (channel 0 = t, 1..3 = rgb, 4 = sigma; slots >= N padded with NaN) and, WITH_IDX, idx [5][P]
 // = the original slot, in LDS -> five independent ascending channel sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`,
 // weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).  MAPS: also the fine depth and
-// opacity to maps_out[0..1] (merge_ray_composite).
+// opacity to maps_out[0..1], QD: also the fine quantile depths to q_out[0..nq-1] (merge_ray_composite).
 struct MergeNoFix { __device__ __forceinline__ void operator()() const {} };
-template <bool WITH_IDX, bool MAPS = false, class Sync, class PostSort = MergeNoFix>
+template <bool WITH_IDX, bool MAPS = false, bool QD = false, class Sync, class PostSort = MergeNoFix>
 __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* idx, int P, int N, float last, int lane, float* w_out, float* bundle_out,
                                                          uint16_t* perm_out, float* C_out, Sync&& sync, PostSort&& post_sort = MergeNoFix{},
-                                                         float* maps_out = nullptr) {
+                                                         float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr) {
   if (P == 256) {  // the usual size (64 + 128 samples): the whole network in registers
     sort256_regs<WITH_IDX>(val, idx, lane, sync);
   } else
@@ -347,17 +400,22 @@ __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* i
     }
   }
   post_sort();  // (the joint-sort mode re-fills channels 1..4 by the depth channel's permutation here)
-  merge_ray_composite<WITH_IDX, MAPS>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out);
+  merge_ray_composite<WITH_IDX, MAPS, QD>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out, qa, q_out);
 }
 
 // the composite over the SORTED channels val [5][P] (and idx): delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine[3]
 // MAPS (nerf_hip_forward_maps): also D_f = sum_i w_i t_s,i over the sorted depth channel t_s (in the reference's mode the channels are sorted
 // independently, quirk Q1: D_f is t composited like a colour channel; in the joint-sort mode the physical expected depth) and A_f = sum_i w_i,
 // fp32 per lane then wave_sum as the colour sums, stored by lane 0 to maps_out[0..1] (null: nothing stored)
-template <bool WITH_IDX, bool MAPS>
+// QD (nerf_hip_forward_quantiles): also the quantile depths of the fine pass (rule QD: the sorted depth channel t_s with these weights) to
+// q_out[0..nq-1].  The loop also forms the fp64 scan of w for its last element W and parks w_i in the ray's own sigma slot val[4 P + i],
+// which the lane has just read and nothing reads afterwards; ray_quantile_depths then takes w from there and t_s from channel 0.
+template <bool WITH_IDX, bool MAPS, bool QD>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
-                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, float* maps_out) {
+                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, float* maps_out,
+                                                    const QuantArgs* qa, float* q_out) {
   double carry = 0.0;
+  double carry_w = 0.0;  // (QD only)
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
   float dsum = 0.f, asum = 0.f;  // (MAPS only)
   for (int base = 0; base < N; base += 64) {
@@ -371,6 +429,11 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
     carry = __shfl(cs, 63);
     const float T = expf(-(float)cs);
     const float wi = v ? T * (1.0f - expf(-s)) : 0.f;
+    if constexpr (QD) {
+      const double cw = wave_incl_scan((double)wi, lane) + carry_w;
+      carry_w = __shfl(cw, 63);
+      if (v) const_cast<float*>(val)[4 * P + i] = wi;
+    }
     if (v) {
       const float r = val[P + i], g = val[2 * P + i], b = val[3 * P + i];
       c0 += wi * r; c1 += wi * g; c2 += wi * b;
@@ -410,6 +473,7 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
       maps_out[1] = asum;
     }
   }
+  if constexpr (QD) ray_quantile_depths(val + 4 * P, val, N, carry_w, lane, *qa, q_out);
 }
 
 // ---- the per-ray stages as their kernels run them (arguments, liveness, stores), for ONE ray by one wave: k_coarse / k_merge (ray_ops.hip)
@@ -417,9 +481,10 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
 
 // k_coarse for ray `ray_raw` (rays behind the batch: computed on a copy of the last ray, nothing stored); w / cdf / tc: Nc floats of LDS each.
 // MAPS (k_coarse_maps): maps [B][4] also gets the ray's (D_c, A_c) in its columns 0, 1
-template <bool MAPS = false, class Sync>
+// QD (k_coarse_qmaps): qdepth [B][2][nq] also gets the ray's coarse quantile depths in its row 0 (rays behind the batch store nothing)
+template <bool MAPS = false, bool QD = false, class Sync>
 __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int ray_raw, const int lane, float* w, float* cdf, float* tc, Sync&& sync,
-                                                 float* maps = nullptr) {
+                                                 float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr) {
   const bool live = ray_raw < a.B;
   const int ray = live ? ray_raw : a.B - 1;
   float near, far;
@@ -439,10 +504,12 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
   }
   const size_t g0 = (size_t)ray * a.Nc;
   float lo, hi;
-  coarse_ray_weights<MAPS>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
+  double W = 0.0;  // (QD only)
+  coarse_ray_weights<MAPS, QD>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
                            (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi,
-                           (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr);
+                           (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr, QD ? &W : nullptr);
   sync();
+  if constexpr (QD) ray_quantile_depths(w, tc, a.Nc, W, lane, *qa, (live && qdepth) ? qdepth + (size_t)ray * 2 * qa->nq : nullptr);
   const bool bad = coarse_ray_resample(w, cdf, tc, lo, hi, delta0, a.Nc, a.Nf, lane, live ? a.t_f + (size_t)ray * a.Nf : nullptr);
   if (live && bad && a.status) atomicOr(a.status, 1u);
   if (live && bad && a.sticky) atomicOr(a.sticky, 1u);
@@ -450,9 +517,10 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
 
 // k_merge for ray `ray` (< B): load the ray's coarse + fine samples into val [5][P] (idx [5][P]: original slots), sort, composite.
 // MAPS (k_merge_maps): maps [B][4] also gets the ray's (D_f, A_f) in its columns 2, 3
-template <bool WITH_IDX, bool MAPS = false, class Sync>
+// QD (k_merge_qmaps): qdepth [B][2][nq] also gets the ray's fine quantile depths in its row 1
+template <bool WITH_IDX, bool MAPS = false, bool QD = false, class Sync>
 __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ray, const int lane, float* val, uint16_t* idx, Sync&& sync,
-                                                float* maps = nullptr) {
+                                                float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr) {
   const int P = a.P, N = a.Nc + a.Nf;
   // load: channel 0 = t, 1..3 = rgb, 4 = sigma
   for (int i = lane; i < P; i += 64) {
@@ -491,9 +559,10 @@ __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ra
       }
     }
   };
-  merge_ray_sort_composite<WITH_IDX, MAPS>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
+  merge_ray_sort_composite<WITH_IDX, MAPS, QD>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
                                            (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix,
-                                           (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr);
+                                           (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr, qa,
+                                           (QD && qdepth) ? qdepth + ((size_t)ray * 2 + 1) * qa->nq : nullptr);
 }
 
 // ---- ray_loss (nerf.py:325-331) in two pieces, bit-compatible with k_ray_loss (ray_ops.hip) ----

@@ -81,6 +81,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-tsdf-unseen", default="solid", choices=["solid", "empty", "skip"],
                     help="what --mesh-tsdf makes of lattice points no view observed: solid (the mesh closes behind what was seen), empty, or "
                          "skip -- masked marching cubes, only the surface the cameras saw; the file is <...>_tsdf_skip.ply (default solid)")
+    ap.add_argument("--mesh-tsdf-depth", default="mean", choices=["mean", "median"],
+                    help="the depth --mesh-tsdf fuses: each ray's expected depth, or its median depth (half of the ray's weight in front), which "
+                         "stays on one surface at silhouettes and behind thin floaters; the file is <...>_tsdf_median.ply (default mean)")
+    ap.add_argument("--mesh-tsdf-max-spread", type=float, default=None, metavar="S",
+                    help="--mesh-tsdf leaves out the pixels whose interquartile depth range exceeds S world units (smeared or bimodal rays) "
+                         "and prints how many (default: keep every pixel)")
     ap.add_argument("--mesh-compare", default=None, metavar="FILE",
                     help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
                          "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
@@ -145,7 +151,8 @@ if __name__ == "__main__":
                              simplify=args.mesh_simplify, smooth=args.mesh_smooth, compare=args.mesh_compare,
                              compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible,
                              tsdf_from=args.mesh_tsdf, tsdf_trunc=args.mesh_tsdf_trunc, tsdf_every=args.mesh_tsdf_every,
-                             tsdf_color=args.mesh_tsdf_color, tsdf_unseen=args.mesh_tsdf_unseen)
+                             tsdf_color=args.mesh_tsdf_color, tsdf_unseen=args.mesh_tsdf_unseen, tsdf_depth_stat=args.mesh_tsdf_depth,
+                             tsdf_max_spread=args.mesh_tsdf_max_spread)
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

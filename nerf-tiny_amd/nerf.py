@@ -82,10 +82,11 @@ def _call_flags(model, need_grad: bool) -> int:
             | (_abi.SPLIT_MLP if split and not bf16 else 0))
 
 
-def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None):
+def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None, quant=None):
     """One nerf_hip_forward call on the model's workspace -> (C_coarse, C_fine, ws, flags).  maps ([B, 4] fp32): nerf_hip_forward_maps
     (inference) / nerf_hip_forward_maps_train (need_grad) instead, which also fill maps with each ray's (D_c, A_c, D_f, A_f) and leave the
-    colours' bits as they are."""
+    colours' bits as they are.  quant = (q, Q) with maps (inference only): nerf_hip_forward_quantiles, which also fills Q ([B, 2, nq] fp32)
+    with the quantile depths of the host floats q (rule QD of include/nerf_hip.h) and leaves colours and maps as they are."""
     B = row.shape[0]
     Nc, Nf = model.num_coarse, model.num_fine
     flags = _call_flags(model, need_grad)
@@ -104,6 +105,11 @@ def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None):
         _abi.check(_abi.lib().nerf_hip_forward(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9,
                                                ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
                                                ws.data_ptr(), ws.numel(), call_flags, stream))
+    elif quant is not None:
+        q, Q = quant
+        _abi.check(_abi.lib().nerf_hip_forward_quantiles(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA,
+                                                         C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags,
+                                                         stream, _abi.f32_array(q), len(q), Q.data_ptr()))
     else:
         fn = _abi.lib().nerf_hip_forward_maps_train if need_grad else _abi.lib().nerf_hip_forward_maps
         _abi.check(fn(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
@@ -379,9 +385,10 @@ class NeRFModel(nn.Module):
             raise ValueError(f"batch of {row.shape[0]} rays, model built for batch_ray={self.batch_ray} (nerf.py:172-176)")
         return self._launch(ps, row, column, poses_bound, K_inv, maps=maps, train_maps=maps)
 
-    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False, train_maps=False):
+    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False, train_maps=False, quantiles=None):
         """maps=True: nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4]) -- with no graph unless `train_maps` is set and grad is
-        enabled for a parameter (then nerf_hip_forward_maps_train under _RenderMapsFn)."""
+        enabled for a parameter (then nerf_hip_forward_maps_train under _RenderMapsFn).  quantiles (a tuple of floats; maps=True, never
+        recorded): nerf_hip_forward_quantiles, -> (C_coarse, C_fine, maps, Q [B, 2, nq])."""
         dev = ps[0].device
         K9 = _abi.f32_array(K_inv.detach().to("cpu", torch.float32).reshape(-1).tolist())
         pb = poses_bound.to(torch.float).to(dev).contiguous()  # cast first like nerf.py:338
@@ -389,16 +396,22 @@ class NeRFModel(nn.Module):
         col_d = column.to(dev, torch.int64).contiguous()
         ray0 = _abi.f32_array(self.ray0_near_far) if self.ray0_near_far is not None else None
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
+        Q = None
         if maps and train_maps and need_grad:
             C_c, C_f, M = _RenderMapsFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)
         elif maps:
             M = torch.empty(row_d.shape[0], 4, dtype=torch.float32, device=dev)
+            if quantiles is not None:
+                Q = torch.empty(row_d.shape[0], 2, len(quantiles), dtype=torch.float32, device=dev)
             with torch.no_grad():
-                C_c, C_f, _, _ = _forward_call(self, False, row_d, col_d, pb, K9, ray0, ps, maps=M)
+                C_c, C_f, _, _ = _forward_call(self, False, row_d, col_d, pb, K9, ray0, ps, maps=M,
+                                               quant=None if quantiles is None else (quantiles, Q))
         else:
             C_c, C_f = _RenderFn.apply(self, need_grad, row_d, col_d, pb, K9, ray0, *ps)
         if self.check_resample and self.resample_fault():
             raise ResampleIndexError("resample index outside [0, Nf-1] (the reference exit(0)s here, nerf.py:251-253)")
+        if Q is not None:
+            return C_c, C_f, M, Q
         return (C_c, C_f, M) if maps else (C_c, C_f)
 
     def train_step(self, row, column, poses_bound, K_inv, C_true):
@@ -698,7 +711,8 @@ class NeRFModel(nn.Module):
         return mesh.Mesh(verts, faces, nrm, rgb)
 
     @torch.no_grad()
-    def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None, color=False):
+    def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None, color=False,
+                   depth_stat="mean", max_spread=None):
         """TSDF fusion of the model's own rendered depth: every camera of views = (poses_bound [n, 17], K_inv, H, W) is rendered with
         render(maps=True), its expected depth image is integrated into a truncated signed distance volume over the density grid's lattice
         of the box [lo, hi] at res (mesh.tsdf_integrate; rule T of include/nerf_hip.h), and the state (T, Wt) -- two fp32 [nx, ny, nz]
@@ -710,8 +724,14 @@ class NeRFModel(nn.Module):
         depth: "coarse" uses (D_c, A_c), "fine" (D_f, A_f), "auto" the fine pair under ``model.corrected`` and the coarse pair otherwise.
         In the default mode the fine pass sorts its five channels independently (quirk Q1), so D_f pairs weights
         with depths they do not belong to -- it is what compositing t like a colour gives --, while D_c is the physical expected depth of
-        the coarse samples; with ``corrected`` the merged samples are sorted once and D_f is physical and sharper.  It is the EXPECTED
-        depth, not the median: a ray that grazes a silhouette averages foreground and background.
+        the coarse samples; with ``corrected`` the merged samples are sorted once and D_f is physical and sharper.
+        depth_stat="mean" (default) fuses this EXPECTED depth: a ray that grazes a silhouette averages foreground and background, and a
+        thin floater in front of a surface drags it forward.  depth_stat="median": the views are rendered with
+        render(maps=True, quantiles=(0.25, 0.5, 0.75)) and the depth is Q(0.5) of the chosen pair (rule QD of include/nerf_hip.h) -- the
+        depth in front of which half of the ray's weight lies, which stays on one of the two surfaces.  max_spread=s (world units, either
+        statistic; None = off): a foreground pixel whose interquartile range Q(0.75) - Q(0.25) exceeds s gets depth NaN and so, by rule T,
+        observes nothing and carves nothing -- rays whose weight is smeared or bimodal are left out instead of averaged in;
+        ``self.last_tsdf_rejected`` counts them (0 without max_spread).  "mean" with max_spread=None makes no quantile call.
         The views are rendered one at a time (each a render() call of H * W rays: ``bf16_mlp`` / ``split_mlp`` apply as in render) and
         integrated views_per_call at a time (default: the kernel's views per launch), so no more than views_per_call depth and opacity
         images exist at once; the result does not depend on views_per_call.
@@ -725,6 +745,13 @@ class NeRFModel(nn.Module):
 
         if depth not in ("auto", "coarse", "fine"):
             raise ValueError(f"depth={depth!r}: 'auto', 'coarse' or 'fine'")
+        if depth_stat not in ("mean", "median"):
+            raise ValueError(f"depth_stat={depth_stat!r}: 'mean' or 'median'")
+        if max_spread is not None and not float(max_spread) >= 0.0:
+            raise ValueError(f"max_spread={max_spread!r}: None or a number >= 0 (world units)")
+        quant = (0.25, 0.5, 0.75) if (depth_stat == "median" or max_spread is not None) else None
+        self.last_tsdf_rejected = 0
+        rejected = None
         col0 = 2 if depth == "fine" or (depth == "auto" and getattr(self, "corrected", False)) else 0
         per_call = _abi.TSDF_VIEWS_PER_LAUNCH if views_per_call is None else int(views_per_call)
         if per_call < 1:
@@ -752,21 +779,29 @@ class NeRFModel(nn.Module):
         for v0 in range(0, n, per_call):
             k = min(per_call, n - v0)
             for c in range(k):
-                out = self.render(row, col, pb[v0 + c].to(dev).expand(H * W, 17), K_inv, maps=True)
+                out = self.render(row, col, pb[v0 + c].to(dev).expand(H * W, 17), K_inv, maps=True, quantiles=quant)
                 M = out[2]
                 d, a = M[:, col0], M[:, col0 + 1]
-                D[c] = torch.where(a >= min_opacity, d / a, inf).view(H, W)
+                if quant is None:
+                    D[c] = torch.where(a >= min_opacity, d / a, inf).view(H, W)
+                else:
+                    dq, rej = tsdf_depth_image(d / a, a, out[3][:, col0 // 2], depth_stat, min_opacity, max_spread)
+                    D[c] = dq.view(H, W)
+                    rejected = rej.sum() if rejected is None else rejected + rej.sum()
                 A[c] = a.view(H, W)
                 if color:
                     RGB[c] = out[1].view(H, W, 3)
             kw = dict(rgb=RGB[:k], color=C) if color else {}
             mesh.tsdf_integrate(T, Wt, lo32, step, D[:k], pb[v0:v0 + k], K_inv, opacity=A[:k], trunc=trunc, min_opacity=min_opacity, carve=carve,
                                 **kw)
+        if rejected is not None:
+            self.last_tsdf_rejected = int(rejected)
         return (T, Wt, C) if color else (T, Wt)
 
     @torch.no_grad()
     def extract_mesh_tsdf(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, unseen="solid", color=True,
-                          normals="grid", min_faces=None, keep_largest=None, simplify=None, smooth=None, visible=None, views_per_call=None):
+                          normals="grid", min_faces=None, keep_largest=None, simplify=None, smooth=None, visible=None, views_per_call=None,
+                          depth_stat="mean", max_spread=None):
         """A triangle mesh of the surface the rendered views agree on: fuse_depth(views, lo, hi, res, ...) -> mesh.tsdf_grid(T, Wt, unseen)
         -> mesh.marching_cubes at level 0 over the same lattice -> the stages of extract_mesh behind marching cubes, with the same keywords
         and order (min_faces / keep_largest, visible, smooth, simplify, then normals and colours at the final vertices).  No density
@@ -779,6 +814,8 @@ class NeRFModel(nn.Module):
         color=True: colours are queried from the field at the final vertices, seen along the inward normal; color=False: none.
         color="fused": the views' colours are fused with their depth (fuse_depth(color=True)) and sampled at the final vertices
         (mesh.tsdf_sample_color); only the vertices without a fused colour -- ``self.last_fused_fallback`` of them -- query the field.
+        depth_stat / max_spread: fuse_depth's (the median depth instead of the mean; pixels whose interquartile depth range exceeds
+        max_spread are left out; ``self.last_tsdf_rejected`` counts them).
         The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt), or (T, Wt, C) with color="fused"."""
         import numpy as np
 
@@ -794,7 +831,7 @@ class NeRFModel(nn.Module):
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
         self.last_tsdf = self.fuse_depth(views, lo32, hi32, shape, trunc=trunc, depth=depth, min_opacity=min_opacity, carve=carve,
-                                         views_per_call=views_per_call, color=fuse_color)
+                                         views_per_call=views_per_call, color=fuse_color, depth_stat=depth_stat, max_spread=max_spread)
         T, Wt = self.last_tsdf[:2]
         if unseen == "skip":
             verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, "empty"), 0.0, lo32, grid_step(lo32, hi32, shape), valid=Wt > 0)
@@ -804,7 +841,8 @@ class NeRFModel(nn.Module):
                                  fused=self.last_tsdf[2] if fuse_color else None)
 
     @torch.no_grad()
-    def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False):
+    def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False,
+               quantiles=None):
         """Inference over a LONG list of rays (a frame, a test set) -- rays [lo, hi) of it -- with the reference's batch semantics and few
         kernel calls: the list is the sequence of batches [g*batch_ray, (g+1)*batch_ray) the reference's display loop feeds to `forward`
         (nerf.py:503-520), every ray gets exactly the bits a per-batch `forward` gives it (`fuse_plan`: consecutive batches whose ray 0
@@ -812,7 +850,12 @@ class NeRFModel(nn.Module):
         (0.71 of the fp32 roof, a fifth of the chip for the bf16 kernels).  The tail batch is rendered too (the reference drops it,
         nerf.py:442), with its own ray 0.  The weights must not change during the call.  Returns (C_coarse, C_fine) [hi - lo, 3].
         maps=True: every call is a nerf_hip_forward_maps call (same colour bits) and the return is (C_coarse, C_fine, maps) with maps
-        [hi - lo, 4] = each ray's (D_c, A_c, D_f, A_f): expected depth and accumulated opacity of the coarse and the fine composite."""
+        [hi - lo, 4] = each ray's (D_c, A_c, D_f, A_f): expected depth and accumulated opacity of the coarse and the fine composite.
+        quantiles (with maps=True; None = the call above): 1 .. 4 floats strictly inside (0, 1), e.g. (0.25, 0.5, 0.75).  Every call is a
+        nerf_hip_forward_quantiles call (same colour and maps bits) and the return is (C_coarse, C_fine, maps, Q) with Q [hi - lo, 2, nq]:
+        row 0 the coarse pass's, row 1 the fine pass's quantile depths (rule QD of include/nerf_hip.h; Q(0.5) is the median depth, where half
+        of the ray's weight lies in front).  Batch semantics and fusing are unchanged."""
+        quantiles = _check_quantiles(quantiles, maps)
         ps = self._params()
         dev = ps[0].device
         n, Bm = row.shape[0], self.batch_ray
@@ -820,8 +863,9 @@ class NeRFModel(nn.Module):
         C_c = torch.empty(max(hi - lo, 0), 3, dtype=torch.float32, device=dev)
         C_f = torch.empty_like(C_c)
         M = torch.empty(max(hi - lo, 0), 4, dtype=torch.float32, device=dev) if maps else None
+        Q = torch.empty(max(hi - lo, 0), 2, len(quantiles), dtype=torch.float32, device=dev) if quantiles is not None else None
         if hi <= lo:
-            return (C_c, C_f, M) if maps else (C_c, C_f)
+            return _render_result(C_c, C_f, M, Q)
         starts = torch.arange(0, n, Bm)
         nf0 = poses_bound[starts.to(poses_bound.device)][:, 15:17].to(torch.float32).cpu().tolist()  # ONE host copy per call
         plan = fuse_plan(nf0, n, Bm, lo, hi, fuse_rays)
@@ -840,16 +884,55 @@ class NeRFModel(nn.Module):
                         # over explicitly, so the real ray's bits do not change
                         k = MIN_CALL_RAYS - (e - s)
                         r_, c_, p_ = (torch.cat((x, x[-1:].expand(k, *x.shape[1:]))) for x in (r_, c_, p_))
-                    out = self._launch(ps, r_, c_, p_, K_inv, maps=maps)
+                    out = self._launch(ps, r_, c_, p_, K_inv, maps=maps, quantiles=quantiles)
                     C_c[s - lo:e - lo] = out[0][: e - s]
                     C_f[s - lo:e - lo] = out[1][: e - s]
                     if maps:
                         M[s - lo:e - lo] = out[2][: e - s]
+                    if Q is not None:
+                        Q[s - lo:e - lo] = out[3][: e - s]
         finally:
             self.ray0_near_far, self._ws_capacity = prev_ray0, prev_cap
         if getattr(self, "bf16_mlp", False):
             self.read_status()  # a frame is not handed out on a poisoned weight image (raises on STATUS_PREP_TIMEOUT; one sync per frame)
-        return (C_c, C_f, M) if maps else (C_c, C_f)
+        return _render_result(C_c, C_f, M, Q)
+
+
+def _render_result(C_c, C_f, M, Q):
+    if Q is not None:
+        return C_c, C_f, M, Q
+    return (C_c, C_f) if M is None else (C_c, C_f, M)
+
+
+def _check_quantiles(quantiles, maps):
+    """render's quantiles keyword -> None or a tuple of 1 .. _abi.MAX_QUANTILES floats strictly inside (0, 1); needs maps=True"""
+    if quantiles is None:
+        return None
+    if not maps:
+        raise ValueError("quantiles needs maps=True: the quantile depths come with the maps call")
+    q = tuple(float(x) for x in quantiles)
+    if not 1 <= len(q) <= _abi.MAX_QUANTILES or not all(0.0 < x < 1.0 for x in q):
+        raise ValueError(f"quantiles={quantiles!r}: 1 .. {_abi.MAX_QUANTILES} numbers strictly inside (0, 1)")
+    return q
+
+
+def tsdf_depth_image(mean, a, Q3, depth_stat="mean", min_opacity=0.5, max_spread=None):
+    """fuse_depth's depth-image rule over flat arrays (torch tensors or numpy arrays of one shape): mean = D / A of the chosen pair, a = its
+    opacity A, Q3 = its quantile depths (Q(0.25), Q(0.5), Q(0.75)) [..., 3] or None (depth_stat="mean" with max_spread=None).
+    -> (depth, rejected): the depth is the mean or the median Q(0.5) where a >= min_opacity (foreground) and +inf elsewhere; with
+    max_spread = s a foreground pixel whose interquartile range Q(0.75) - Q(0.25) > s gets NaN (by rule T it observes nothing and carves
+    nothing); rejected marks those pixels."""
+    if depth_stat not in ("mean", "median"):
+        raise ValueError(f"depth_stat={depth_stat!r}: 'mean' or 'median'")
+    xp = torch if torch.is_tensor(a) else __import__("numpy")
+    fg = a >= min_opacity
+    d = Q3[..., 1] if depth_stat == "median" else mean
+    inf, nan = (xp.full_like(a, v) for v in (float("inf"), float("nan")))
+    d = xp.where(fg, d, inf)
+    if max_spread is None:
+        return d, xp.zeros_like(fg)
+    rejected = fg & ((Q3[..., 2] - Q3[..., 0]) > max_spread)
+    return xp.where(rejected, nan, d), rejected
 
 
 def _check_mesh_stages(normals, simplify, smooth):

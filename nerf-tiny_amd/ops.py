@@ -785,3 +785,48 @@ def merge_composite_backward(bundle, perm, dC_f, Nc, last=1e-4, dmaps=None):
                                                             B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(), drgb_c.data_ptr(),
                                                             drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle)))
     return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
+
+
+def coarse_composite_quantiles(t_c, sigma_c, rgb_c, near, far, delta0, Nf, q, sentinel=float("nan"), rays=None):
+    """coarse_composite_maps through k_coarse_qmaps (nerf_hip_coarse_composite_quantiles) -> w_c, C_coarse, t_f, status(int), maps[B,4],
+    qdepth[B,2,nq]: row 0 = the coarse quantile depths of q (rule QD of include/nerf_hip.h), row 1 left at `sentinel`.  rays: a call of
+    the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
+    B, Nc = t_c.shape
+    rays = B if rays is None else int(rays)
+    if not 1 <= rays <= B:
+        raise ValueError("coarse_composite_quantiles: 1 <= rays <= B")
+    dev = t_c.device
+    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    w_c = torch.empty(B, Nc, device=dev)
+    C_c = torch.empty(B, 3, device=dev)
+    t_f = torch.empty(B, Nf, device=dev)
+    maps = torch.full((B, 4), float("nan"), device=dev)
+    Q = torch.full((B, 2, len(q)), sentinel, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_coarse_composite_quantiles(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
+                                                              rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
+                                                              w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
+                                                              _stream(t_c), _abi.f32_array(q), len(q), Q.data_ptr()))
+    return w_c, C_c, t_f, int(status.item()), maps, Q
+
+
+def merge_composite_quantiles(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, q, last=1e-4, joint=False, perm=True, sentinel=float("nan")):
+    """merge_composite_train(maps=True) through k_merge_qmaps (nerf_hip_merge_composite_quantiles) -> bundle, w, C_fine, perm (None with
+    perm=False: the values-only sort, joint=False only), maps[B,4], qdepth[B,2,nq]: row 1 = the fine quantile depths of q (rule QD), row 0
+    left at `sentinel`"""
+    B, Nc = t_c.shape
+    Nf = t_f.shape[1]
+    dev = t_c.device
+    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
+    w = torch.empty(B, Nc + Nf, device=dev)
+    C_f = torch.empty(B, 3, device=dev)
+    pm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev) if perm else None
+    M = torch.full((B, 4), float("nan"), device=dev)
+    Q = torch.full((B, 2, len(q)), sentinel, device=dev)
+    _abi.check(_abi.lib().nerf_hip_merge_composite_quantiles(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
+                                                             sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
+                                                             rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
+                                                             float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(),
+                                                             None if pm is None else pm.data_ptr(), int(bool(joint)), M.data_ptr(), _stream(t_c),
+                                                             _abi.f32_array(q), len(q), Q.data_ptr()))
+    return bundle, w, C_f, pm, M, Q

@@ -551,7 +551,8 @@ class NeRFRunner:
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
                      keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None,
-                     tsdf_from=None, tsdf_trunc=None, tsdf_every=1, tsdf_color=False, tsdf_unseen="solid"):
+                     tsdf_from=None, tsdf_trunc=None, tsdf_every=1, tsdf_color=False, tsdf_unseen="solid", tsdf_depth_stat="mean",
+                     tsdf_max_spread=None):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -582,7 +583,11 @@ class NeRFRunner:
         the same rendered views (NeRFModel.extract_mesh_tsdf(color="fused")); tsdf_unseen: "solid" (default), "empty" or "skip" -- "skip"
         meshes only what the cameras observed (masked marching cubes).  With either, the ``[TSDF]`` line also counts the lattice points
         with a fused colour and the vertices that fell back to the field, and the file name gets ``_fused`` and / or ``_skip`` after
-        ``_tsdf``.  Without them the line and the name are unchanged."""
+        ``_tsdf``.  Without them the line and the name are unchanged.  tsdf_depth_stat: "mean" (default) or "median" -- the views' median
+        depth Q(0.5) is fused instead of their expected depth (NeRFModel.fuse_depth(depth_stat=): it stays on one surface where a ray
+        grazes a silhouette or passes a thin floater); tsdf_max_spread: None, or a distance s >= 0 in world units -- pixels whose
+        interquartile depth range exceeds s are left out of the fusion (fuse_depth(max_spread=)).  With either, the ``[TSDF]`` line also
+        names the statistic and counts the rejected pixels, and "median" puts ``_median`` right after ``_tsdf`` in the file name."""
         import numpy as np
 
         from .mesh import Mesh, write_ply
@@ -611,6 +616,11 @@ class NeRFRunner:
             extended = bool(tsdf_color) or tsdf_unseen != "solid"
             if extended:
                 kw["unseen"] = tsdf_unseen
+            if tsdf_depth_stat not in ("mean", "median"):
+                raise ValueError(f"tsdf_depth_stat={tsdf_depth_stat!r}: 'mean' or 'median'")
+            quant = tsdf_depth_stat != "mean" or tsdf_max_spread is not None
+            if quant:
+                kw["depth_stat"], kw["max_spread"] = tsdf_depth_stat, tsdf_max_spread
             rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[tsdf_from]
             poses = rays.poses[::int(tsdf_every)]
             m = self.model.extract_mesh_tsdf((poses, self.K_inv, rays.height, rays.width), lo32, hi32, shape, trunc=tsdf_trunc,
@@ -624,6 +634,9 @@ class NeRFRunner:
                 coloured = int((self.model.last_tsdf[2][..., 3] > 0).sum()) if fused else 0
                 by_field = self.model.last_fused_fallback if fused else (len(m.verts) if color else 0)
                 more = f", {coloured} lattice points with a colour, {by_field} vertices coloured by the field"
+            if quant:
+                spread = "" if tsdf_max_spread is None else f" (depth spread > {float(tsdf_max_spread):.6g})"
+                more += f", {tsdf_depth_stat} depth, {self.model.last_tsdf_rejected} pixels rejected{spread}"
             print(f"[MESH] {self.last_iter} [TSDF] {len(poses)} {tsdf_from} views fused, {int((Wt > 0).sum())} / {Wt.numel()} lattice points "
                   f"observed, trunc {trunc:.6g}{more} (level {level!r} ignored: the surface is the fused depth's)")
         else:
@@ -636,7 +649,7 @@ class NeRFRunner:
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
-            tsdf_tag = "" if tsdf_from is None else "_tsdf" + ("_fused" if fused else "") + ("_skip" if tsdf_unseen == "skip" else "")
+            tsdf_tag = "" if tsdf_from is None else "_tsdf" + ("_median" if tsdf_depth_stat == "median" else "") + ("_fused" if fused else "") + ("_skip" if tsdf_unseen == "skip" else "")
             path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_mesh" + tag + tsdf_tag + ".ply"
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
