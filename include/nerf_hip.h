@@ -62,7 +62,10 @@ extern "C" {
                                      nerf_hip_coarse_composite_backward_maps, nerf_hip_merge_composite_train,
                                      nerf_hip_merge_composite_backward; nerf_hip_forward_quantiles,
                                      nerf_hip_coarse_composite_quantiles, nerf_hip_merge_composite_quantiles
-                                     (with NERF_HIP_MAX_QUANTILES) */
+                                     (with NERF_HIP_MAX_QUANTILES); nerf_hip_forward_distortion_train,
+                                     nerf_hip_backward_distortion, nerf_hip_coarse_composite_distortion,
+                                     nerf_hip_merge_composite_distortion, nerf_hip_coarse_composite_backward_distortion,
+                                     nerf_hip_merge_composite_backward_distortion */
 
 enum {
   NERF_HIP_OK = 0,
@@ -218,6 +221,55 @@ int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* ro
                                 const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
                                 int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
                                 void* ws, size_t ws_bytes, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Distortion loss: a trainable measure of how far a ray's weight is spread, the regulariser of
+ * mip-NeRF 360 against floaters.  Beside rule QD, which shows the same spread at inference time.
+ *
+ * DL. THE DISTORTION RULE, for one pass of one ray: samples t_0 .. t_{N-1} in the order the composite visits them (non-decreasing), with
+ *    the composite's own fp32 weights w_i.  Coarse pass: t_c with w_c.  Fine pass: the SORTED depth channel t_s with the w of C_fine --
+ *    without NERF_HIP_CORRECTED it inherits quirk Q1 exactly as D_f and the quantiles do.  All arithmetic is fp64 on the fp32 inputs
+ *    widened exactly.
+ *       m_i = (t_i + t_{i+1}) / 2   for i < N-1        m_{N-1} = t_{N-1}
+ *       d_i = t_{i+1} - t_i         for i < N-1        d_{N-1} = 0       (the last interval is never extrapolated: last_delta may be 1e10)
+ *       r   = 1 / (far - near)      of the ray         (far > near is the caller's guarantee, as everywhere)
+ *       We_i = sum_{j<i} w_j        Se_i = sum_{j<i} w_j m_j             (exclusive prefixes, index order)
+ *       W = sum w                   S = sum w m
+ *       P_i = m_i We_i - Se_i
+ *       R_i = (S - Se_i - w_i m_i) - m_i (W - We_i - w_i)
+ *       L   = r [ 2 sum_i w_i P_i + 1/3 sum_i w_i^2 d_i ]                stored as fp32
+ *    L = r (sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i) because m is non-decreasing; at ties the sign of m_i - m_j is that of
+ *    i - j, which fixes the subgradient.  L is dimensionless (depths in units of the ray's [near, far]).  Its gradients, also fp64:
+ *       dL/dw_i = r [ 2 (P_i + R_i) + 2/3 w_i d_i ]
+ *       a_i     = 2 w_i (We_i - (W - We_i - w_i))                        (= d/dm_i of the double sum)
+ *       dL/dt_k = r [ (k < N-1 ? a_k / 2 - w_k^2 / 3 : a_k) + (k >= 1 ? a_{k-1} / 2 + w_{k-1}^2 / 3 : 0) ]
+ *    With the upstream g = d loss / dL of the ray and pass, the backward adds fp32(double(g) dL/dw_k) to d w_k and fp32(double(g) dL/dt_k)
+ *    to d t_s,k, each as a separate fp32 addition behind the maps terms of nerf_hip_backward_maps.  The depth gradient takes the route of
+ *    the maps' gD_f w_k: through the t channel's own permutation to d t_fine; a coarse origin drops it; NERF_HIP_CORRECTED drops it with
+ *    the rest; t_c carries no gradient, so the coarse pass contributes through d w_c,i alone.
+ *    (The kernels take W and S per lane and then across the wave, and the prefixes by wave scans: fp64 sums whose order differs from the
+ *    index order by rounding in the 16th digit, far below the one fp32 rounding of each result.)
+ *
+ * nerf_hip_forward_distortion_train: the arguments of nerf_hip_forward_maps_train, then
+ *   dist    [B,2] f32 out, device: (L_c, L_f) per ray
+ * NERF_HIP_SAVE_FOR_BACKWARD, maps and dist are required (else NERF_HIP_ERR_ARG before any device work).  Every training mode; C_coarse,
+ * C_fine, maps, the status word and the workspace's saves are nerf_hip_forward_maps_train's, bit for bit (k_coarse_dmaps / k_merge_dmaps:
+ * the training maps kernels with one more accumulation in the composite loop).  The workspace is that call's: nothing per sample is saved.
+ *
+ * nerf_hip_backward_distortion: the arguments of nerf_hip_backward_maps, then
+ *   ddist   [B,2] f32, device, not NULL: g = (d loss / dL_c, d loss / dL_f) per ray
+ * Valid after any training forward on the workspace (near and far come from the ray records every forward keeps).  With ddist = 0 every
+ * gradient equals nerf_hip_backward_maps's.  The per-ray stages run as separate launches (k_merge_bwd_dist / k_coarse_bwd_dist), which
+ * recompute W, S and the prefixes from the weights they recompute anyway.  Null dmaps or ddist -> NERF_HIP_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------------------------- */
+int nerf_hip_forward_distortion_train(const float* const* weights24, const int64_t* row, const int64_t* col,
+                                      const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
+                                      int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
+                                      void* ws, size_t ws_bytes, int flags, void* stream, float* dist /* device [B][2] */);
+int nerf_hip_backward_distortion(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
+                                 const float* ray0_near_far, int B, int Nc, int Nf, float last_delta,
+                                 float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream,
+                                 void* early_event, const float* ddist /* device [B][2] */);
 
 /*
  * Backward of nerf_hip_forward (autograd through nerf.py:286-323, called at nerf.py:473).
@@ -1065,6 +1117,30 @@ int nerf_hip_merge_composite_quantiles(const float* t_c, const float* t_f, const
 int nerf_hip_merge_composite_backward(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps,
                                       int B, int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
                                       float* drgb_f, float* dt_f, void* stream);
+
+/* The stage entries of nerf_hip_forward_distortion_train / nerf_hip_backward_distortion (rule DL above); near_far [B,2] = each ray's
+ * (near, far), dist / ddist [B,2] = (L_c, L_f) / their upstream, all device and required.
+ * nerf_hip_coarse_composite_distortion: the arguments of nerf_hip_coarse_composite_maps, then dist -- the k_coarse_dmaps launch; every
+ * shared output has that call's bits, column 0 of dist is written (column 1 untouched).
+ * nerf_hip_merge_composite_distortion: the arguments of nerf_hip_merge_composite_train (maps required here), then near_far, dist -- the
+ * k_merge_dmaps launch; shared outputs as that call's, column 1 of dist written (column 0 untouched).
+ * nerf_hip_coarse_composite_backward_distortion: the arguments of nerf_hip_coarse_composite_backward_maps, then ddist (column 0 is
+ * read).  ADDS to dsig_c / drgb_c like the call it extends; with ddist = 0 it adds that call's values.
+ * nerf_hip_merge_composite_backward_distortion: the arguments of nerf_hip_merge_composite_backward, then near_far, ddist (column 1 is
+ * read).  WRITES every element like the call it extends; with ddist = 0 its values. */
+int nerf_hip_coarse_composite_distortion(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                         float delta0, int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f,
+                                         uint32_t* status, float* maps, void* stream, float* dist);
+int nerf_hip_merge_composite_distortion(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f,
+                                        const float* rgb_c, const float* rgb_f, int B, int Nc, int Nf, float last_delta,
+                                        float* bundle, float* w, float* C_fine, uint16_t* perm, int joint, float* maps, void* stream,
+                                        const float* near_far, float* dist);
+int nerf_hip_coarse_composite_backward_distortion(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                                  float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
+                                                  const float* dmaps, float* dsig_c, float* drgb_c, void* stream, const float* ddist);
+int nerf_hip_merge_composite_backward_distortion(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps,
+                                                 int B, int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
+                                                 float* drgb_f, float* dt_f, void* stream, const float* near_far, const float* ddist);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,17 @@ _PROTOS = {
     "nerf_hip_merge_composite_quantiles": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_int, _p,
                                                      _p, _p, C.c_int, _p]),
     "nerf_hip_merge_composite_backward": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_forward_distortion_train": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_size_t,
+                                                    C.c_int, _p, _p]),
+    "nerf_hip_backward_distortion": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, C.c_size_t, C.c_int, _p, _p,
+                                               _p]),
+    "nerf_hip_coarse_composite_distortion": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_merge_composite_distortion": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_int, _p,
+                                                      _p, _p, _p]),
+    "nerf_hip_coarse_composite_backward_distortion": (C.c_int, [_p, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p,
+                                                                _p]),
+    "nerf_hip_merge_composite_backward_distortion": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, _p, _p, _p,
+                                                               _p]),
     "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),

@@ -250,7 +250,8 @@ struct TrainLoss {
 // else null.  A maps call always takes the separate k_coarse / k_merge launches (never the pair kernel, never the FwdFuse epilogues)
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr);
+                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr,
+                 float* dist = nullptr);  // dist: the [B][2] output of nerf_hip_forward_distortion_train (with maps, a training call), else null
 // nerf_hip_forward_quantiles and its stage entries: the checks they share, before any device work
 int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) {
   static_assert(MAX_QUANTILES == NERF_HIP_MAX_QUANTILES, "kernels.h and nerf_hip.h disagree");
@@ -268,7 +269,7 @@ int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) 
 // separate k_merge_bwd_maps / k_coarse_bwd_maps launches (never the BwdFuse prologues)
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl, const float* dmaps = nullptr);
+                  const TrainLoss* tl, const float* dmaps = nullptr, const float* ddist = nullptr);  // ddist (with dmaps): nerf_hip_backward_distortion's [B][2]
 }  // namespace
 
 extern "C" {
@@ -311,13 +312,24 @@ int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* ro
                       nullptr, maps);
 }
 
+int nerf_hip_forward_distortion_train(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
+                                      const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta,
+                                      float* C_coarse, float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream,
+                                      float* dist) {
+  if (!(flags & NERF_HIP_SAVE_FOR_BACKWARD))
+    return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_distortion_train is training only (NERF_HIP_SAVE_FOR_BACKWARD not set)");
+  if (!maps || !dist) return fail(NERF_HIP_ERR_ARG, "maps or dist is null");
+  return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
+                      nullptr, maps, nullptr, nullptr, dist);
+}
+
 }  // extern "C"
 
 namespace {
 
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth) {
+                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth, float* dist) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
@@ -451,7 +463,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     ff.mode = 0;
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_COARSE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(qa ? launch_coarse_quantiles(ca, maps, *qa, qdepth, st) : launch_coarse(ca, st, maps)); }
+    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(dist ? launch_coarse_dist(ca, maps, dist, st) : qa ? launch_coarse_quantiles(ca, maps, *qa, qdepth, st) : launch_coarse(ca, st, maps)); }
   }
 
   // fine pass (nerf.py:299), same network (quirk Q10)
@@ -479,7 +491,8 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(qa ? launch_merge_quantiles(ma, maps, *qa, qdepth, st) : launch_merge(ma, st, maps)); }
+    const DistArgs da{at<float>(ws, L.rayf), nullptr, dist, nullptr};  // (dist only)
+    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(dist ? launch_merge_dist(ma, maps, da, st) : qa ? launch_merge_quantiles(ma, maps, *qa, qdepth, st) : launch_merge(ma, st, maps)); }
   }
   return NERF_HIP_OK;
 }
@@ -549,13 +562,21 @@ int nerf_hip_backward_maps(const float* const* weights24, const float* dC_coarse
                        nullptr, dmaps);
 }
 
+int nerf_hip_backward_distortion(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
+                                 const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* const* dweights24, void* ws,
+                                 size_t ws_bytes, int flags, void* stream, void* early_event, const float* ddist) {
+  if (!dmaps || !ddist) return fail(NERF_HIP_ERR_ARG, "dmaps or ddist is null");
+  return backward_impl(weights24, dC_coarse, dC_fine, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes, flags, stream, early_event,
+                       nullptr, dmaps, ddist);
+}
+
 }  // extern "C"
 
 namespace {
 
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl, const float* dmaps) {
+                  const TrainLoss* tl, const float* dmaps, const float* ddist) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (int rc = check_weights(const_cast<const float* const*>(dweights24))) return rc;
@@ -593,7 +614,12 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   const bool fuse_rays = bf16 && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !dmaps;
   BwdFuse bz;
   memset(&bz, 0, sizeof(bz));
-  if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd_maps(mb, dmaps, st)); }
+  if (ddist) {  // (near / far: the ray records the forward left in the workspace)
+    const DistArgs da{at<float>(ws, L.rayf), nullptr, nullptr, ddist};
+    ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc);
+    HIP_TRY(launch_merge_bwd_dist(mb, dmaps, da, st));
+  }
+  else if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd_maps(mb, dmaps, st)); }
   else if (!fuse_rays) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd(mb, st)); }
 
   // 2. fine-pass field backward (dX chain incl. d loss / d t_fine)
@@ -641,6 +667,7 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   if (ray0_near_far) { cb.ray0_override = 1; cb.near0 = ray0_near_far[0]; cb.far0 = ray0_near_far[1]; }
   cb.drgb_c = at<float>(ws, L.drgb_c); cb.dsig_c = at<float>(ws, L.dsig_c);
   if (fuse_rays) { bz.mode = 2; bz.c = cb; }
+  else if (ddist) { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd_dist(cb, dmaps, ddist, st)); }
   else if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd_maps(cb, dmaps, st)); }
   else { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd(cb, st)); }
 
@@ -1014,6 +1041,68 @@ int nerf_hip_merge_composite_quantiles(const float* t_c, const float* t_f, const
   ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
   ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
   HIP_TRY(launch_merge_quantiles(ma, maps, qa, qdepth, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_coarse_composite_distortion(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far, float delta0,
+                                         int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
+                                         void* stream, float* dist) {
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps || !dist) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  CoarseArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
+  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
+  ca.delta0_mode = 1; ca.delta0 = delta0;
+  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
+  HIP_TRY(launch_coarse_dist(ca, maps, dist, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_merge_composite_distortion(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f, const float* rgb_c,
+                                        const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
+                                        uint16_t* perm, int joint, float* maps, void* stream, const float* near_far, float* dist) {
+  if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !perm || !maps || !near_far || !dist)
+    return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  MergeArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
+  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
+  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
+  const DistArgs da{nullptr, near_far, dist, nullptr};
+  HIP_TRY(launch_merge_dist(ma, maps, da, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_coarse_composite_backward_distortion(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
+                                                  float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
+                                                  const float* dmaps, float* dsig_c, float* drgb_c, void* stream, const float* ddist) {
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c || !ddist)
+    return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  CoarseBwdArgs cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c; cb.near_far = near_far;
+  cb.B = B; cb.Nc = Nc; cb.Nf = Nf; cb.delta0_mode = 1; cb.delta0 = delta0;
+  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
+  HIP_TRY(launch_coarse_bwd_dist(cb, dmaps, ddist, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_merge_composite_backward_distortion(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps, int B,
+                                                 int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
+                                                 float* drgb_f, float* dt_f, void* stream, const float* near_far, const float* ddist) {
+  if (!bundle || !perm || !dC_fine || !dsig_c || !dsig_f || !drgb_c || !drgb_f || !dt_f || !near_far || !ddist)
+    return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  MergeBwdArgs mb;
+  memset(&mb, 0, sizeof(mb));
+  mb.dC_f = dC_fine; mb.bundle = bundle; mb.perm = perm;
+  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
+  mb.drgb_c = drgb_c; mb.dsig_c = dsig_c; mb.drgb_f = drgb_f; mb.dsig_f = dsig_f; mb.dt_f = dt_f;
+  const DistArgs da{nullptr, near_far, nullptr, ddist};
+  HIP_TRY(launch_merge_bwd_dist(mb, dmaps, da, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

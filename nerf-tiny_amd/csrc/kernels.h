@@ -209,6 +209,19 @@ struct QuantArgs {
 };
 hipError_t launch_coarse_quantiles(const CoarseArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
 hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
+// nerf_hip_forward_distortion_train / nerf_hip_backward_distortion: k_coarse_dmaps / k_merge_dmaps -- the training maps kernels, which also
+// store each ray's distortion loss (rule DL of include/nerf_hip.h) to dist [B][2], column 0 by the coarse kernel, column 1 by the merge
+// kernel -- and k_merge_bwd_dist / k_coarse_bwd_dist (ray_ops_bwd.hip), the maps backward kernels that also take its upstream ddist [B][2].
+// The merge kernels have no ray records of their own: near / far come from rayf (the workspace's records) or near_far [B][2] (stage entries).
+// A kernel argument of its own, like the maps pointer
+struct DistArgs {
+  const float* rayf;      // [B][RAYF] or null
+  const float* near_far;  // [B][2], used when rayf is null
+  float* dist;            // forward: [B][2]
+  const float* ddist;     // backward: [B][2]
+};
+hipError_t launch_coarse_dist(const CoarseArgs& a, float* maps, float* dist, hipStream_t st);
+hipError_t launch_merge_dist(const MergeArgs& a, float* maps, const DistArgs& da, hipStream_t st);  // a.perm set (a training call)
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st);
 
 }  // namespace nerf
@@ -370,6 +383,9 @@ hipError_t launch_coarse_bwd(const CoarseBwdArgs& a, hipStream_t st);
 // nerf_hip_backward_maps: k_merge_bwd_maps / k_coarse_bwd_maps, which also take each ray's upstream (gD_c, gA_c, gD_f, gA_f) from dmaps [B][4]
 hipError_t launch_merge_bwd_maps(const MergeBwdArgs& a, const float* dmaps, hipStream_t st);
 hipError_t launch_coarse_bwd_maps(const CoarseBwdArgs& a, const float* dmaps, hipStream_t st);
+// nerf_hip_backward_distortion: the maps backward kernels plus rule DL's terms (da.ddist [B][2]: the upstream of L_c, L_f)
+hipError_t launch_merge_bwd_dist(const MergeBwdArgs& a, const float* dmaps, const DistArgs& da, hipStream_t st);
+hipError_t launch_coarse_bwd_dist(const CoarseBwdArgs& a, const float* dmaps, const float* ddist, hipStream_t st);
 
 struct AdamArgs {
   float* param[24];

@@ -5,6 +5,7 @@
 //   k_merge             merge coarse+fine, five independent channel sorts, composite -> C_fine
 //   k_coarse_maps / k_merge_maps   the same, plus each ray's expected depth and opacity (nerf_hip_forward_maps)
 //   k_coarse_qmaps / k_merge_qmaps the maps kernels, plus each ray's quantile depths (nerf_hip_forward_quantiles, rule QD)
+//   k_coarse_dmaps / k_merge_dmaps the training maps kernels, plus each ray's distortion loss (nerf_hip_forward_distortion_train, rule DL)
 //   k_ray_loss          sum-of-squares loss and its gradient
 // One 64-lane wave owns one ray: the transmittance cumsum / CDF are wave scans (fp64 accumulator like
 // ATen's CPU cumsum, rounded to fp32 per element), searchsorted is a per-lane binary search in LDS and
@@ -69,8 +70,18 @@ __global__ __launch_bounds__(256) void k_coarse_qmaps(const CoarseArgs a, float*
   coarse_ray_stage<true, true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps, &qa, qdepth);
 }
 
+// k_coarse_dmaps: k_coarse_maps that also stores each live ray's coarse distortion loss (rule DL of include/nerf_hip.h) to column 0 of
+// dist [B][2] (nerf_hip_forward_distortion_train).  The pointer is a kernel argument of its own, for k_coarse_maps's reason.
+__global__ __launch_bounds__(256) void k_coarse_dmaps(const CoarseArgs a, float* maps, float* dist) {
+  __shared__ float s_w[4][MAXN];
+  __shared__ float s_cdf[4][MAXN];
+  __shared__ float s_t[4][MAXN];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  coarse_ray_stage<true, false, true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps, nullptr, nullptr, dist);
+}
+
 // ---------------------------------------------------------------------------------------------
-// k_merge: nerf.py:302-321.  cat -> sort(dim=1) of a [B,N,5] bundle = five INDEPENDENT ascending channel
+// k_merge: nerf.py:302-321. cat -> sort(dim=1) of a [B,N,5] bundle = five INDEPENDENT ascending channel
 // sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine.
 // One wave (64-thread block) per ray; bitonic sort over P = next_pow2(N) slots per channel in LDS.
 // Ties are broken by original index (a stable sort); indices are kept for the backward pass.
@@ -102,6 +113,15 @@ __global__ __launch_bounds__(64) void k_merge_qmaps(const MergeArgs a, float* ma
   float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
   uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
   merge_ray_stage<WITH_IDX, true, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps, &qa, qdepth);
+}
+
+// k_merge_dmaps: the training k_merge_maps (sorts with slots) that also stores each ray's fine distortion loss (rule DL) to column 1 of
+// da.dist [B][2] (nerf_hip_forward_distortion_train).  Same LDS; both sort paths and the joint mode end in the same merge_ray_composite.
+__global__ __launch_bounds__(64) void k_merge_dmaps(const MergeArgs a, float* maps, const DistArgs da) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
+  uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
+  merge_ray_stage<true, true, false, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps, nullptr, nullptr, &da);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -181,6 +201,17 @@ hipError_t launch_merge_qmaps(const MergeArgs& a, float* maps, const QuantArgs& 
 hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st) {
   const size_t lds = merge_lds_bytes(a.P);
   return (a.perm || a.joint) ? launch_merge_qmaps<true>(a, maps, qa, qdepth, lds, st) : launch_merge_qmaps<false>(a, maps, qa, qdepth, lds, st);
+}
+hipError_t launch_coarse_dist(const CoarseArgs& a, float* maps, float* dist, hipStream_t st) {
+  hipLaunchKernelGGL(k_coarse_dmaps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps, dist);
+  return hipGetLastError();
+}
+hipError_t launch_merge_dist(const MergeArgs& a, float* maps, const DistArgs& da, hipStream_t st) {
+  const size_t lds = merge_lds_bytes(a.P);
+  if (lds > 48 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_dmaps), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  hipLaunchKernelGGL(k_merge_dmaps, dim3(a.B), dim3(64), lds, st, a, maps, da);
+  return hipGetLastError();
 }
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st) {
   hipLaunchKernelGGL(k_ray_loss, dim3(1), dim3(1024), 0, st, Cc, Cf, Ct, B * 3, loss, dCc, dCf);

@@ -5,6 +5,7 @@
 // that run them on SOME waves of a bigger workgroup pass a wave-level fence.  MI355X / gfx950 only; built with -ffp-contract=off.
 #pragma once
 #include "kernels.h"
+#include "ray_dist.h"
 
 namespace nerf {
 
@@ -102,12 +103,16 @@ __device__ __forceinline__ float ray0_spacing(float n0, float f0, int Nc) {
 // as the colour sums -- stored by lane 0 to maps_out[0..1] (null: nothing stored).  Without MAPS the code is the colour-only one.
 // QD (nerf_hip_forward_quantiles): also hands out W = the last element of the fp64 scan of w (the cdf's, before its rounding to fp32) in
 // W_out, for ray_quantile_depths over the w / tc this function leaves in LDS.
-template <bool MAPS = false, bool QD = false>
+// DL (nerf_hip_forward_distortion_train): also the coarse pass's distortion loss L_c (rule DL: t_c with these weights), one fp64 accumulation
+// per sample over two more wave scans (ray_dist.h), stored by lane 0 to dist_out[0] (null: nothing stored).
+template <bool MAPS = false, bool QD = false, bool DL = false>
 __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const float* rgb, const float* t_c, float near, float far, int Nc, int lane,
                                                    float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out,
-                                                   float* maps_out = nullptr, double* W_out = nullptr) {
+                                                   float* maps_out = nullptr, double* W_out = nullptr, float* dist_out = nullptr) {
   const float delta_c = (far - near) / (float)Nc;
   double carry = 0.0, carry2 = 0.0;
+  DistScan dsc;        // (DL only)
+  double dacc = 0.0;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
   float dsum = 0.f, asum = 0.f;  // (MAPS only)
   float lo = INFINITY, hi = -INFINITY;
@@ -124,6 +129,12 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
     double cw = wave_incl_scan((double)wi, lane) + carry2;
     carry2 = __shfl(cw, 63);
     const float cd = (float)cw;
+    if constexpr (DL) {
+      const bool hn = v && i + 1 < Nc;
+      const float ti = v ? t_c[gi] : 0.f;
+      dsc.step(wi, ti, hn ? t_c[gi + 1] : ti, hn, lane, [](double x, int l) { return wave_incl_scan(x, l); });
+      dacc += dsc.summand(wi);
+    }
     if (v) {
       w[i] = wi;
       cdf[i] = cd;
@@ -159,6 +170,10 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
     }
   }
   if constexpr (QD) *W_out = carry2;
+  if constexpr (DL) {
+    const double L = dist_ray_scale(near, far) * wave_sum_f64(dacc);
+    if (lane == 0 && dist_out) dist_out[0] = (float)L;
+  }
 }
 
 // resample (nerf.py:225-261): u_j = lo + j * ((hi - lo)/(Nf+1)), j = 1..Nf (numpy.linspace(lo, hi, Nf+2)[1:-1] in fp32, nerf.py:243-246),
@@ -353,20 +368,23 @@ __device__ __forceinline__ void merge_channel_job(const MergeArgs& a, const int 
   *reinterpret_cast<uint2*>(idx + 4 * lane) = pk;
 }
 
-template <bool WITH_IDX, bool MAPS = false, bool QD = false>
+template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
                                                     float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret = nullptr,
-                                                    float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr);
+                                                    float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr,
+                                                    double dist_r = 0.0, float* dist_out = nullptr);
 
 // nerf.py:302-321 behind the load: val [5][P] (channel 0 = t, 1..3 = rgb, 4 = sigma; slots >= N padded with NaN) and, WITH_IDX, idx [5][P]
 // = the original slot, in LDS -> five independent ascending channel sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`,
 // weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).  MAPS: also the fine depth and
-// opacity to maps_out[0..1], QD: also the fine quantile depths to q_out[0..nq-1] (merge_ray_composite).
+// opacity to maps_out[0..1], QD: also the fine quantile depths to q_out[0..nq-1], DL: also the fine distortion loss to dist_out[0]
+// (merge_ray_composite).
 struct MergeNoFix { __device__ __forceinline__ void operator()() const {} };
-template <bool WITH_IDX, bool MAPS = false, bool QD = false, class Sync, class PostSort = MergeNoFix>
+template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false, class Sync, class PostSort = MergeNoFix>
 __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* idx, int P, int N, float last, int lane, float* w_out, float* bundle_out,
                                                          uint16_t* perm_out, float* C_out, Sync&& sync, PostSort&& post_sort = MergeNoFix{},
-                                                         float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr) {
+                                                         float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr,
+                                                         double dist_r = 0.0, float* dist_out = nullptr) {
   if (P == 256) {  // the usual size (64 + 128 samples): the whole network in registers
     sort256_regs<WITH_IDX>(val, idx, lane, sync);
   } else
@@ -400,7 +418,8 @@ __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* i
     }
   }
   post_sort();  // (the joint-sort mode re-fills channels 1..4 by the depth channel's permutation here)
-  merge_ray_composite<WITH_IDX, MAPS, QD>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out, qa, q_out);
+  merge_ray_composite<WITH_IDX, MAPS, QD, DL>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out, qa, q_out,
+                                              dist_r, dist_out);
 }
 
 // the composite over the SORTED channels val [5][P] (and idx): delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine[3]
@@ -410,12 +429,17 @@ __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* i
 // QD (nerf_hip_forward_quantiles): also the quantile depths of the fine pass (rule QD: the sorted depth channel t_s with these weights) to
 // q_out[0..nq-1].  The loop also forms the fp64 scan of w for its last element W and parks w_i in the ray's own sigma slot val[4 P + i],
 // which the lane has just read and nothing reads afterwards; ray_quantile_depths then takes w from there and t_s from channel 0.
-template <bool WITH_IDX, bool MAPS, bool QD>
+// DL (nerf_hip_forward_distortion_train): also the fine pass's distortion loss L_f (rule DL: the sorted depth channel t_s with these weights,
+// dist_r = the ray's 1 / (far - near)): one fp64 accumulation per sample over two more wave scans (ray_dist.h), stored by lane 0 to
+// dist_out[0] (null: nothing stored).  The last interval's `last` never enters it.
+template <bool WITH_IDX, bool MAPS, bool QD, bool DL>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
                                                     float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, float* maps_out,
-                                                    const QuantArgs* qa, float* q_out) {
+                                                    const QuantArgs* qa, float* q_out, double dist_r, float* dist_out) {
   double carry = 0.0;
   double carry_w = 0.0;  // (QD only)
+  DistScan dsc;          // (DL only)
+  double dacc = 0.0;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
   float dsum = 0.f, asum = 0.f;  // (MAPS only)
   for (int base = 0; base < N; base += 64) {
@@ -433,6 +457,11 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
       const double cw = wave_incl_scan((double)wi, lane) + carry_w;
       carry_w = __shfl(cw, 63);
       if (v) const_cast<float*>(val)[4 * P + i] = wi;
+    }
+    if constexpr (DL) {
+      const bool hn = v && i + 1 < N;
+      dsc.step(wi, ti, hn ? val[i + 1] : ti, hn, lane, [](double x, int l) { return wave_incl_scan(x, l); });
+      dacc += dsc.summand(wi);
     }
     if (v) {
       const float r = val[P + i], g = val[2 * P + i], b = val[3 * P + i];
@@ -474,6 +503,10 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
     }
   }
   if constexpr (QD) ray_quantile_depths(val + 4 * P, val, N, carry_w, lane, *qa, q_out);
+  if constexpr (DL) {
+    const double L = dist_r * wave_sum_f64(dacc);
+    if (lane == 0 && dist_out) dist_out[0] = (float)L;
+  }
 }
 
 // ---- the per-ray stages as their kernels run them (arguments, liveness, stores), for ONE ray by one wave: k_coarse / k_merge (ray_ops.hip)
@@ -482,9 +515,10 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
 // k_coarse for ray `ray_raw` (rays behind the batch: computed on a copy of the last ray, nothing stored); w / cdf / tc: Nc floats of LDS each.
 // MAPS (k_coarse_maps): maps [B][4] also gets the ray's (D_c, A_c) in its columns 0, 1
 // QD (k_coarse_qmaps): qdepth [B][2][nq] also gets the ray's coarse quantile depths in its row 0 (rays behind the batch store nothing)
-template <bool MAPS = false, bool QD = false, class Sync>
+// DL (k_coarse_dmaps): dist [B][2] also gets the ray's coarse distortion loss in its column 0 (rays behind the batch store nothing)
+template <bool MAPS = false, bool QD = false, bool DL = false, class Sync>
 __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int ray_raw, const int lane, float* w, float* cdf, float* tc, Sync&& sync,
-                                                 float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr) {
+                                                 float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr, float* dist = nullptr) {
   const bool live = ray_raw < a.B;
   const int ray = live ? ray_raw : a.B - 1;
   float near, far;
@@ -505,9 +539,10 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
   const size_t g0 = (size_t)ray * a.Nc;
   float lo, hi;
   double W = 0.0;  // (QD only)
-  coarse_ray_weights<MAPS, QD>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
-                           (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi,
-                           (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr, QD ? &W : nullptr);
+  coarse_ray_weights<MAPS, QD, DL>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
+                               (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi,
+                               (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr, QD ? &W : nullptr,
+                               (DL && live && dist) ? dist + (size_t)ray * 2 : nullptr);
   sync();
   if constexpr (QD) ray_quantile_depths(w, tc, a.Nc, W, lane, *qa, (live && qdepth) ? qdepth + (size_t)ray * 2 * qa->nq : nullptr);
   const bool bad = coarse_ray_resample(w, cdf, tc, lo, hi, delta0, a.Nc, a.Nf, lane, live ? a.t_f + (size_t)ray * a.Nf : nullptr);
@@ -518,9 +553,11 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
 // k_merge for ray `ray` (< B): load the ray's coarse + fine samples into val [5][P] (idx [5][P]: original slots), sort, composite.
 // MAPS (k_merge_maps): maps [B][4] also gets the ray's (D_f, A_f) in its columns 2, 3
 // QD (k_merge_qmaps): qdepth [B][2][nq] also gets the ray's fine quantile depths in its row 1
-template <bool WITH_IDX, bool MAPS = false, bool QD = false, class Sync>
+// DL (k_merge_dmaps): da->dist [B][2] also gets the ray's fine distortion loss in its column 1; near / far from da's ray records or near_far
+template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false, class Sync>
 __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ray, const int lane, float* val, uint16_t* idx, Sync&& sync,
-                                                float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr) {
+                                                float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr,
+                                                const DistArgs* da = nullptr) {
   const int P = a.P, N = a.Nc + a.Nf;
   // load: channel 0 = t, 1..3 = rgb, 4 = sigma
   for (int i = lane; i < P; i += 64) {
@@ -559,10 +596,13 @@ __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ra
       }
     }
   };
-  merge_ray_sort_composite<WITH_IDX, MAPS, QD>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
-                                           (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix,
-                                           (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr, qa,
-                                           (QD && qdepth) ? qdepth + ((size_t)ray * 2 + 1) * qa->nq : nullptr);
+  double dist_r = 0.0;  // (DL only)
+  if constexpr (DL) dist_r = dist_ray_scale(dist_near(*da, ray), dist_far(*da, ray));
+  merge_ray_sort_composite<WITH_IDX, MAPS, QD, DL>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
+                                               (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix,
+                                               (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr, qa,
+                                               (QD && qdepth) ? qdepth + ((size_t)ray * 2 + 1) * qa->nq : nullptr, dist_r,
+                                               (DL && da->dist) ? da->dist + (size_t)ray * 2 + 1 : nullptr);
 }
 
 // ---- ray_loss (nerf.py:325-331) in two pieces, bit-compatible with k_ray_loss (ray_ops.hip) ----

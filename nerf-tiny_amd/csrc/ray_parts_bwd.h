@@ -3,6 +3,7 @@
 // caller passes the `sync` that fits its workgroup.  MI355X / gfx950 only; built with -ffp-contract=off.
 #pragma once
 #include "kernels.h"
+#include "ray_dist.h"
 
 namespace nerf {
 
@@ -30,22 +31,30 @@ __device__ __forceinline__ double wave_suffix_scan_d(double v, int lane) {
 // MAPS (nerf_hip_backward_maps): dmaps [B][4] holds each ray's upstream (gD_c, gA_c, gD_f, gA_f); the fine maps add
 // gD_f t_s,k + gA_f to dw_k (pass 1) and gD_f w_k to d t_s,k (pass 3, un-sorted through perm[0] as the delta terms), each as a separate
 // addition behind the colour-only expression.  Without MAPS the code is the colour-only one.
-template <bool MAPS = false, class Sync>
+// DL (with MAPS; nerf_hip_backward_distortion): da->ddist [B][2] column 1 holds the ray's upstream g of L_f (rule DL of
+// include/nerf_hip.h).  Between pass 1 and pass 2 a fix-up pass over the w_k that pass 1 left in LDS (ray_dist.h: the totals W, S, then the
+// prefixes) adds fp32(g dL/dw_k) to dw_k -- one more fp32 addition behind the maps term, dw_k w_k re-formed from the sum -- and parks
+// fp32(g dL/dt_k) in a sixth array, which pass 3 adds to d t_s,k behind the maps term.  sm_f: 6 * (Nc + Nf) floats.
+template <bool MAPS = false, bool DL = false, class Sync>
 __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int ray, const int lane, float* sm_f, Sync&& sync,
-                                              const float* dmaps = nullptr) {
+                                              const float* dmaps = nullptr, const DistArgs* da = nullptr) {
+  static_assert(MAPS || !DL, "the distortion terms extend the maps instantiation");
   const int N = a.Nc + a.Nf;
   float* s_te = sm_f;          // T_k * exp(-s_k)
   float* s_dww = sm_f + N;     // dw_k * w_k
   float* s_dw = sm_f + 2 * N;  // dw_k
   float* s_dd = sm_f + 3 * N;  // d delta_k
   float* s_w = sm_f + 4 * N;   // w_k (MAPS only)
+  float* s_gt = sm_f + 5 * N;  // fp32(g dL/dt_k) (DL only)
   const float* bun = a.bundle + (size_t)ray * N * 5;
   const float dC0 = a.dC_f[(size_t)ray * 3], dC1 = a.dC_f[(size_t)ray * 3 + 1], dC2 = a.dC_f[(size_t)ray * 3 + 2];
   const uint16_t* pm = a.perm + (size_t)ray * 5 * N;
   float gD = 0.f, gA = 0.f;  // (MAPS only)
   if constexpr (MAPS) {
-    gD = dmaps[(size_t)ray * 4 + 2];
-    gA = dmaps[(size_t)ray * 4 + 3];
+    if (!DL || dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
+      gD = dmaps[(size_t)ray * 4 + 2];
+      gA = dmaps[(size_t)ray * 4 + 3];
+    }
   }
 
   // pass 1 (forward): recompute T, w exactly as k_merge did; d rgb_sorted scattered immediately
@@ -83,6 +92,17 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
     }
   }
   sync();
+  if constexpr (DL) {
+    const double r = dist_ray_scale(dist_near(*da, ray), dist_far(*da, ray));
+    dist_grad_terms(s_w, [&](int i) { return bun[(size_t)i * 5]; }, N, r, da->ddist[(size_t)ray * 2 + 1], lane,
+                    [](double x, int l) { return wave_incl_scan_d(x, l); },
+                    [&](int i, float gw, float gt) {  // (lane i % 64 wrote s_dw[i] in pass 1 and reads it in pass 2)
+                      const float dw = s_dw[i] + gw;
+                      s_dw[i] = dw;
+                      s_dww[i] = dw * s_w[i];
+                      s_gt[i] = gt;
+                    });
+  }
   // pass 2 (reverse): ds_k = dw_k T_k e_k - sum_{i>=k} dw_i w_i ; d sigma_k = ds_k delta_k ; d delta_k = ds_k sigma_k
   double rc = 0.0;
   const int nchunks = (N + 63) / 64;
@@ -111,6 +131,7 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
     if (i > 0) g += s_dd[i - 1];
     if (i + 1 < N) g -= s_dd[i];
     if constexpr (MAPS) g += gD * s_w[i];
+    if constexpr (DL) g += s_gt[i];
     const int src = pm[i];
     if (src >= a.Nc) a.dt_f[(size_t)ray * a.Nf + (src - a.Nc)] = g;  // t_coarse carries no gradient
   }
@@ -120,9 +141,13 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
 // backward of resampling + coarse composite for ONE ray by one wave (nerf.py:225-281); w: 5 * Nc floats, ks: Nf u16 of LDS of this wave.
 // MAPS (nerf_hip_backward_maps): the coarse maps add gD_c t_c,i + gA_c (dmaps [B][4] columns 0, 1) to dw_i as a separate addition
 // behind the colour-only sum; t_c carries no gradient.  Without MAPS the code is the colour-only one.
-template <bool MAPS = false, class Sync>
+// DL (with MAPS; nerf_hip_backward_distortion): ddist [B][2] column 0 holds the ray's upstream g of L_c (rule DL).  Before the last loop a
+// pass over the recomputed w (ray_dist.h) leaves fp32(g dL/dw_i) in the cdf slots, which nothing reads any more, and the loop adds it to
+// dw_i as one more fp32 addition behind the maps term; dL/dt_c is dropped (t_c carries no gradient).  Same LDS.
+template <bool MAPS = false, bool DL = false, class Sync>
 __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int ray, const bool live, const int lane, float* w, uint16_t* ks, Sync&& sync,
-                                               const float* dmaps = nullptr) {
+                                               const float* dmaps = nullptr, const float* ddist = nullptr) {
+  static_assert(MAPS || !DL, "the distortion terms extend the maps instantiation");
   const int Nc = a.Nc, Nf = a.Nf;
   float near, far;
   if (a.rayf) {
@@ -223,10 +248,17 @@ __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int
   const float dC0 = a.dC_c[(size_t)ray * 3], dC1 = a.dC_c[(size_t)ray * 3 + 1], dC2 = a.dC_c[(size_t)ray * 3 + 2];
   float gD = 0.f, gA = 0.f;  // (MAPS only)
   if constexpr (MAPS) {
-    gD = dmaps[(size_t)ray * 4];
-    gA = dmaps[(size_t)ray * 4 + 1];
+    if (!DL || dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
+      gD = dmaps[(size_t)ray * 4];
+      gA = dmaps[(size_t)ray * 4 + 1];
+    }
   }
-  // dw_i = suffix_sum(dcdf)_i + dwn_{i-1} + rgb_i . dC_c (+ gD_c t_c,i + gA_c) ; then composite backward
+  if constexpr (DL) {  // (the sync above has ordered the gather loop's reads of cdf before these writes)
+    const float* tr = a.t_c + (size_t)ray * Nc;
+    dist_grad_terms(w, [&](int i) { return tr[i]; }, Nc, dist_ray_scale(near, far), ddist[(size_t)ray * 2], lane,
+                    [](double x, int l) { return wave_incl_scan_d(x, l); }, [&](int i, float gw, float) { cdf[i] = gw; });
+  }
+  // dw_i = suffix_sum(dcdf)_i + dwn_{i-1} + rgb_i . dC_c (+ gD_c t_c,i + gA_c) (+ g dL_c/dw_i) ; then composite backward
   double rc = 0.0, rc2 = 0.0;
   const int nchunks = (Nc + 63) / 64;
   for (int ch = nchunks - 1; ch >= 0; --ch) {
@@ -240,6 +272,7 @@ __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int
       dw = (float)sufc + (i > 0 ? ys[i - 1] : 0.f);
       dw += __builtin_fmaf(a.rgb[gi * 3 + 2], dC2, __builtin_fmaf(a.rgb[gi * 3 + 1], dC1, a.rgb[gi * 3] * dC0));
       if constexpr (MAPS) dw += gD * a.t_c[gi] + gA;
+      if constexpr (DL) dw += cdf[i];  // (written by this lane)
     }
     const double suf = wave_suffix_scan_d(v ? (double)(dw * w[i]) : 0.0, lane) + rc2;
     rc2 = __shfl(suf, 0);

@@ -97,6 +97,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="distance thresholds of --mesh-compare's precision / recall / F-score (up to 8; default: none)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
+    ap.add_argument("--dist-weight", type=float, default=None, metavar="LAMBDA",
+                    help="train with ray_loss + LAMBDA * the distortion loss of the fine pass (mip-NeRF 360's regulariser against floaters, "
+                         "per-ray depths in units of [near, far]; ini key DIST_WEIGHT; default 0)")
     ap.add_argument("--maps", action="store_true",
                     help="display() also renders every frame's expected depth and opacity: <RESULTS_PATH><time>_<iter>_maps.npz (depth, acc, "
                          "near, far) and <i>_depth.png / <i>_acc.png previews beside the frames (rank 0 writes)")
@@ -108,6 +111,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval-views", type=int, nargs="+", default=None, metavar="I",
                     help="view indices of --eval and --eval-every (default: every view)")
     return ap
+
+
+def dist_weight_of(args, conf: ConfigParser) -> float:
+    """NeRFRunner's dist_weight: the command line's --dist-weight, else the ini section's DIST_WEIGHT, else 0"""
+    return args.dist_weight if args.dist_weight is not None else float(conf.get(args.conf, "DIST_WEIGHT", fallback=0.0))
 
 
 if __name__ == "__main__":
@@ -131,6 +139,7 @@ if __name__ == "__main__":
     if args.on_resample_fault or c("ON_RESAMPLE_FAULT"):
         kw["on_resample_fault"] = args.on_resample_fault or c("ON_RESAMPLE_FAULT")
     kw["mask_weight"] = args.mask_weight if args.mask_weight is not None else float(c("MASK_WEIGHT", 0.0))
+    kw["dist_weight"] = dist_weight_of(args, conf)
     if args.eval_every is not None:
         kw["eval_every"], kw["eval_views"] = args.eval_every, args.eval_views
     # data-parallel: started as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 .../main.py ...`

@@ -82,11 +82,12 @@ def _call_flags(model, need_grad: bool) -> int:
             | (_abi.SPLIT_MLP if split and not bf16 else 0))
 
 
-def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None, quant=None):
+def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None, quant=None, dist=None):
     """One nerf_hip_forward call on the model's workspace -> (C_coarse, C_fine, ws, flags).  maps ([B, 4] fp32): nerf_hip_forward_maps
     (inference) / nerf_hip_forward_maps_train (need_grad) instead, which also fill maps with each ray's (D_c, A_c, D_f, A_f) and leave the
     colours' bits as they are.  quant = (q, Q) with maps (inference only): nerf_hip_forward_quantiles, which also fills Q ([B, 2, nq] fp32)
-    with the quantile depths of the host floats q (rule QD of include/nerf_hip.h) and leaves colours and maps as they are."""
+    with the quantile depths of the host floats q (rule QD of include/nerf_hip.h) and leaves colours and maps as they are.  dist ([B, 2]
+    fp32) with maps (need_grad only): nerf_hip_forward_distortion_train, which also fills dist with each ray's (L_c, L_f) (rule DL)."""
     B = row.shape[0]
     Nc, Nf = model.num_coarse, model.num_fine
     flags = _call_flags(model, need_grad)
@@ -110,6 +111,10 @@ def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None, q
         _abi.check(_abi.lib().nerf_hip_forward_quantiles(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA,
                                                          C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags,
                                                          stream, _abi.f32_array(q), len(q), Q.data_ptr()))
+    elif dist is not None:
+        _abi.check(_abi.lib().nerf_hip_forward_distortion_train(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf,
+                                                                LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(),
+                                                                ws.numel(), call_flags, stream, dist.data_ptr()))
     else:
         fn = _abi.lib().nerf_hip_forward_maps_train if need_grad else _abi.lib().nerf_hip_forward_maps
         _abi.check(fn(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
@@ -208,6 +213,33 @@ class _RenderMapsFn(torch.autograd.Function):
         grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_maps(
             wp, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(), ctx.ray0, B, model.num_coarse, model.num_fine, LAST_DELTA, gp,
             ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early)))
+        return (None, None, None, None, None, None, *grads)
+
+
+class _RenderDistFn(torch.autograd.Function):
+    """A training forward with maps and the distortion loss (nerf_hip_forward_distortion_train) -> (C_coarse, C_fine, maps [B, 4],
+    dist [B, 2]); its backward is ONE nerf_hip_backward_distortion call.  An upstream gradient autograd hands over
+    as None counts as zero."""
+
+    @staticmethod
+    def forward(ctx, model, row, col, pb, K9, ray0, *params):
+        ctx.set_materialize_grads(False)
+        M = torch.empty(row.shape[0], 4, dtype=torch.float32, device=row.device)
+        D = torch.empty(row.shape[0], 2, dtype=torch.float32, device=row.device)
+        C_c, C_f, ws, flags = _forward_call(model, True, row, col, pb, K9, ray0, params, maps=M, dist=D)
+        _record(ctx, model, flags, ws, row.shape[0], params, ray0)
+        return C_c, C_f, M, D
+
+    @staticmethod
+    def backward(ctx, dC_c, dC_f, dM, dD):
+        B = ctx.B
+        dev = ctx.params[0].device
+        up = [torch.zeros(B, n, dtype=torch.float32, device=dev) if g is None else g.contiguous().float()
+              for g, n in ((dC_c, 3), (dC_f, 3), (dM, 4), (dD, 2))]
+        model = ctx.model
+        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_distortion(
+            wp, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(), ctx.ray0, B, model.num_coarse, model.num_fine, LAST_DELTA, gp,
+            ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early, up[3].data_ptr())))
         return (None, None, None, None, None, None, *grads)
 
 
@@ -370,25 +402,41 @@ class NeRFModel(nn.Module):
         a = alpha.reshape(-1).to(maps.device, torch.float32)
         return torch.sum(torch.square(maps[:, 1] - a)) + torch.sum(torch.square(maps[:, 3] - a))
 
-    def forward(self, row, column, poses_bound, K_inv, maps=False):
+    def distortion_loss(self, dist, coarse=False):
+        """Not in the reference: the distortion loss of mip-NeRF 360 over a batch, sum_b L_f,b (coarse=True: + sum_b L_c,b) of
+        forward(maps=True, distortion=True)'s dist [B, 2] (rule DL of include/nerf_hip.h) -- a sum, like ray_loss.  Plain torch ops on B
+        elements."""
+        loss = torch.sum(dist[:, 1])
+        return loss + torch.sum(dist[:, 0]) if coarse else loss
+
+    def forward(self, row, column, poses_bound, K_inv, maps=False, distortion=False):
         """nerf.py:333-348.  row/column [B] i64, poses_bound [B,17] (any float dtype), K_inv [3,3];
         CPU or device tensors.  Returns (C_coarse, C_fine) [B,3] fp32 on the model's device.
         maps=True (not in the reference): returns (C_coarse, C_fine, maps) with maps [B, 4] = each ray's (D_c, A_c, D_f, A_f), expected depth
         and accumulated opacity of the coarse and the fine composite (include/nerf_hip.h).  With grad enabled and a parameter that requires
         grad the call records a graph and all three outputs are differentiable with respect to the weights (a mask or depth loss:
-        DESIGN.md section 3l); otherwise it is the inference maps call.  The colours' bits are those of maps=False either way."""
+        DESIGN.md section 3l); otherwise it is the inference maps call.  The colours' bits are those of maps=False either way.
+        distortion=True (with maps=True, training only): returns (C_coarse, C_fine, maps, dist) with dist [B, 2] = each ray's distortion
+        loss (L_c, L_f) of the coarse and the fine pass (rule DL of include/nerf_hip.h), differentiable with the rest (DESIGN.md section
+        3m); colours and maps keep their bits.  ValueError before any device work without maps=True or where no graph would be recorded."""
+        if distortion and not maps:
+            raise ValueError("distortion=True needs maps=True: the distortion loss comes with the training maps call")
+        if distortion and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.network.parameters())):
+            raise ValueError("distortion=True is a training output: grad is disabled or no parameter requires grad, so no graph would be "
+                             "recorded; render(quantiles=) is the inference-time view of the same spread")
         ps = self._params()
         dev = ps[0].device
         if dev.type != "cuda":
             raise RuntimeError("NeRFModel runs only on a ROCm device (MI355X): model.to('cuda'); there is no CPU path")
         if row.shape[0] != self.batch_ray:
             raise ValueError(f"batch of {row.shape[0]} rays, model built for batch_ray={self.batch_ray} (nerf.py:172-176)")
-        return self._launch(ps, row, column, poses_bound, K_inv, maps=maps, train_maps=maps)
+        return self._launch(ps, row, column, poses_bound, K_inv, maps=maps, train_maps=maps, distortion=distortion)
 
-    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False, train_maps=False, quantiles=None):
+    def _launch(self, ps, row, column, poses_bound, K_inv, maps=False, train_maps=False, quantiles=None, distortion=False):
         """maps=True: nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4]) -- with no graph unless `train_maps` is set and grad is
         enabled for a parameter (then nerf_hip_forward_maps_train under _RenderMapsFn).  quantiles (a tuple of floats; maps=True, never
-        recorded): nerf_hip_forward_quantiles, -> (C_coarse, C_fine, maps, Q [B, 2, nq])."""
+        recorded): nerf_hip_forward_quantiles, -> (C_coarse, C_fine, maps, Q [B, 2, nq]).  distortion (forward has checked that a graph is
+        recorded): nerf_hip_forward_distortion_train under _RenderDistFn, -> (C_coarse, C_fine, maps, dist [B, 2])."""
         dev = ps[0].device
         K9 = _abi.f32_array(K_inv.detach().to("cpu", torch.float32).reshape(-1).tolist())
         pb = poses_bound.to(torch.float).to(dev).contiguous()  # cast first like nerf.py:338
@@ -397,7 +445,9 @@ class NeRFModel(nn.Module):
         ray0 = _abi.f32_array(self.ray0_near_far) if self.ray0_near_far is not None else None
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
         Q = None
-        if maps and train_maps and need_grad:
+        if distortion:
+            C_c, C_f, M, Q = _RenderDistFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)  # (the fourth output: dist here, the quantile depths below)
+        elif maps and train_maps and need_grad:
             C_c, C_f, M = _RenderMapsFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)
         elif maps:
             M = torch.empty(row_d.shape[0], 4, dtype=torch.float32, device=dev)

@@ -830,3 +830,81 @@ def merge_composite_quantiles(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, q, last=
                                                              None if pm is None else pm.data_ptr(), int(bool(joint)), M.data_ptr(), _stream(t_c),
                                                              _abi.f32_array(q), len(q), Q.data_ptr()))
     return bundle, w, C_f, pm, M, Q
+
+
+def coarse_composite_distortion(t_c, sigma_c, rgb_c, near, far, delta0, Nf, sentinel=float("nan"), rays=None):
+    """coarse_composite_maps through k_coarse_dmaps (nerf_hip_coarse_composite_distortion) -> w_c, C_coarse, t_f, status(int), maps[B,4],
+    dist[B,2]: column 0 = the coarse distortion loss L_c (rule DL of include/nerf_hip.h), column 1 left at `sentinel`.  rays: a call of
+    the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
+    B, Nc = t_c.shape
+    rays = B if rays is None else int(rays)
+    if not 1 <= rays <= B:
+        raise ValueError("coarse_composite_distortion: 1 <= rays <= B")
+    dev = t_c.device
+    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    w_c = torch.empty(B, Nc, device=dev)
+    C_c = torch.empty(B, 3, device=dev)
+    t_f = torch.empty(B, Nf, device=dev)
+    maps = torch.full((B, 4), float("nan"), device=dev)
+    dist = torch.full((B, 2), sentinel, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_coarse_composite_distortion(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
+                                                               rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
+                                                               w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
+                                                               _stream(t_c), dist.data_ptr()))
+    return w_c, C_c, t_f, int(status.item()), maps, dist
+
+
+def merge_composite_distortion(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, near, far, last=1e-4, joint=False, sentinel=float("nan")):
+    """merge_composite_train(maps=True) through k_merge_dmaps (nerf_hip_merge_composite_distortion) -> bundle, w, C_fine, perm, maps[B,4],
+    dist[B,2]: column 1 = the fine distortion loss L_f (rule DL), column 0 left at `sentinel`"""
+    B, Nc = t_c.shape
+    Nf = t_f.shape[1]
+    dev = t_c.device
+    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
+    w = torch.empty(B, Nc + Nf, device=dev)
+    C_f = torch.empty(B, 3, device=dev)
+    pm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev)
+    M = torch.full((B, 4), float("nan"), device=dev)
+    dist = torch.full((B, 2), sentinel, device=dev)
+    _abi.check(_abi.lib().nerf_hip_merge_composite_distortion(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
+                                                              sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
+                                                              rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
+                                                              float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), pm.data_ptr(),
+                                                              int(bool(joint)), M.data_ptr(), _stream(t_c), nf.data_ptr(), dist.data_ptr()))
+    return bundle, w, C_f, pm, M, dist
+
+
+def coarse_composite_backward_distortion_add(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb, ddist, dmaps=None, rays=None):
+    """coarse_composite_backward_add through k_coarse_bwd_dist (nerf_hip_coarse_composite_backward_distortion): ADDS the coarse stage's
+    gradients, the upstream ddist[B,2] (column 0) of the coarse distortion loss included, to dsig[B,Nc], drgb[B,Nc,3] in place"""
+    B, Nc = t_c.shape
+    Nf = dt_f.shape[1]
+    rays = B if rays is None else int(rays)
+    if not (1 <= rays <= B and dsig.shape == (B, Nc) and drgb.shape == (B, Nc, 3) and dsig.is_contiguous() and drgb.is_contiguous()):
+        raise ValueError("coarse_composite_backward_distortion_add: contiguous dsig [B,Nc] / drgb [B,Nc,3] and 1 <= rays <= B")
+    nf = torch.stack((near, far), dim=1).contiguous().to(t_c.device)
+    _abi.check(_abi.lib().nerf_hip_coarse_composite_backward_distortion(
+        t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(), rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
+        dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
+        dsig.data_ptr(), drgb.data_ptr(), _stream(t_c), ddist.contiguous().data_ptr()))
+    return dsig, drgb
+
+
+def merge_composite_backward_distortion(bundle, perm, dC_f, Nc, near, far, ddist, last=1e-4, dmaps=None):
+    """merge_composite_backward through k_merge_bwd_dist (nerf_hip_merge_composite_backward_distortion), with the upstream ddist[B,2]
+    (column 1) of the fine distortion loss -> dsig_c, dsig_f, drgb_c, drgb_f, dt_f; the outputs start as NaN: the kernel writes every element"""
+    B, N, _ = bundle.shape
+    Nf = N - Nc
+    dev = bundle.device
+    if perm.dtype != torch.int16 or perm.shape != (B, 5, N):
+        raise ValueError("merge_composite_backward_distortion: perm is int16 [B,5,N]")
+    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+    dsig_c, dsig_f, drgb_c, drgb_f, dt_f = nan(B, Nc), nan(B, Nf), nan(B, Nc, 3), nan(B, Nf, 3), nan(B, Nf)
+    _abi.check(_abi.lib().nerf_hip_merge_composite_backward_distortion(
+        bundle.contiguous().data_ptr(), perm.contiguous().data_ptr(), dC_f.contiguous().data_ptr(),
+        None if dmaps is None else dmaps.contiguous().data_ptr(), B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(),
+        drgb_c.data_ptr(), drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle), nf.data_ptr(), ddist.contiguous().data_ptr()))
+    return dsig_c, dsig_f, drgb_c, drgb_f, dt_f

@@ -135,13 +135,15 @@ def consume_buckets_of(params) -> int:
 
 
 def train_step_local(model, bucket: GradBucket, row, col, poses_bound, K_inv, C_true, ray0, world: int, group=None, alpha=None,
-                     mask_weight: float = 0.0):
+                     mask_weight: float = 0.0, dist_weight: float = 0.0):
     """One data-parallel train step on tensors that ARE this rank's slice of the global batch (`NeRFRunner`: the device sampler gathers
     only the slice; `ray0` = (near, far) of the GLOBAL batch's ray 0, host floats -- quirk Q6).  `model.batch_ray` must equal the slice
     size.  Forward + loss + backward with the gradients written straight into `bucket`, then ONE flat SUM all-reduce (in two overlapped
     parts with `bucket.enable_overlap()`), placed where the reference has ``loss.backward(); optimizer.step()`` (nerf.py:473-474).
     Returns this rank's (C_coarse, C_fine, local loss); every rank then holds the full-batch gradient in p.grad (views of `bucket.flat`).
-    mask_weight > 0: the step is train.mask_train_step with the slice's `alpha` (ray_loss + mask_weight * mask_loss through autograd)."""
+    mask_weight > 0: the step is train.mask_train_step with the slice's `alpha` (ray_loss + mask_weight * mask_loss through autograd).
+    dist_weight > 0: the step is train.regularized_train_step (+ dist_weight * distortion_loss; a per-ray sum like the others, so the flat
+    SUM all-reduce holds for it as it stands)."""
     prev_ray0, prev_bucket = model.ray0_near_far, model.grad_bucket
     # `model.check_resample` (mimic nerf.py:251-253: raise where the reference exit(0)s) is a RANK-LOCAL raise; taken before the
     # collective it would leave the other ranks blocked in all_reduce.  The check is therefore made AFTER the all-reduce, its
@@ -152,7 +154,11 @@ def train_step_local(model, bucket: GradBucket, row, col, poses_bound, K_inv, C_
     try:
         if check:
             model.check_resample = False
-        if mask_weight > 0:
+        if dist_weight > 0:
+            from .train import regularized_train_step
+
+            C_c, C_f, loss = regularized_train_step(model, row, col, poses_bound, K_inv, C_true, alpha, mask_weight, dist_weight)
+        elif mask_weight > 0:
             from .train import mask_train_step
 
             C_c, C_f, loss = mask_train_step(model, row, col, poses_bound, K_inv, C_true, alpha, mask_weight)

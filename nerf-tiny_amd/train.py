@@ -114,6 +114,25 @@ def mask_train_step(model, row, col, poses_bound, K_inv, C_true, alpha, weight):
     return C_c.detach(), C_f.detach(), loss.detach()
 
 
+def regularized_train_step(model, row, col, poses_bound, K_inv, C_true, alpha=None, mask_weight=0.0, dist_weight=0.0):
+    """One train step with the optional extra loss terms (not in the reference): ``loss = ray_loss + mask_weight * mask_loss + dist_weight *
+    distortion_loss`` (all sums over the batch), ``loss.backward()``, gradients as in ``mask_train_step``.  dist_weight > 0 takes
+    ``forward(maps=True, distortion=True)`` (nerf_hip_forward_distortion_train / nerf_hip_backward_distortion); with
+    dist_weight == 0 the forward is ``forward(maps=True)`` and nothing new runs.  mask_weight > 0 needs the batch's ``alpha``; a term whose
+    weight is 0 is left out of the sum.  Returns ``(C_coarse, C_fine, loss)`` detached."""
+    if dist_weight > 0:
+        C_c, C_f, M, D = model(row, col, poses_bound, K_inv, maps=True, distortion=True)
+    else:
+        C_c, C_f, M = model(row, col, poses_bound, K_inv, maps=True)
+    loss = model.ray_loss(C_c, C_f, C_true)
+    if mask_weight > 0:
+        loss = loss + mask_weight * model.mask_loss(M, alpha)
+    if dist_weight > 0:
+        loss = loss + dist_weight * model.distortion_loss(D)
+    loss.backward()
+    return C_c.detach(), C_f.detach(), loss.detach()
+
+
 def _writer():
     try:
         from torch.utils.tensorboard import SummaryWriter  # absent offline
@@ -173,7 +192,7 @@ class NeRFRunner:
                  total_iter=100000, batch_ray=400, learning=1e-3, lr_gamma=0.1, lr_milestone=(10, 200), n_coarse=64, n_fine=128,
                  data_type="sync", step=100, decay_end=200000, sched="EXP", continue_=False, *, datasets=None, log_every=None,
                  seed=624, bf16_mlp=False, split_mlp=False, split_train=False, on_resample_fault="raise", distributed=None, overlap_allreduce=None,
-                 eval_every=None, eval_views=None, mask_weight=0.0):
+                 eval_every=None, eval_views=None, mask_weight=0.0, dist_weight=0.0):
         from . import nerf as _nerf
         from . import parallel as par
 
@@ -185,6 +204,10 @@ class NeRFRunner:
         if not mask_weight >= 0.0 or mask_weight == float("inf"):
             raise ValueError(f"mask_weight={mask_weight!r}: a finite weight >= 0")
         self.mask_weight = mask_weight
+        dist_weight = float(dist_weight)
+        if not dist_weight >= 0.0 or dist_weight == float("inf"):  # (refused before anything touches the GPU, like mask_weight)
+            raise ValueError(f"dist_weight={dist_weight!r}: a finite weight >= 0")
+        self.dist_weight = dist_weight
         if mask_weight > 0 and datasets is None and data_type == "llff":  # (refused before anything touches the GPU or a process group)
             raise ValueError(f"MASK_WEIGHT = {mask_weight} needs the per-pixel alpha of the training images; LLFF captures carry none")
 
@@ -368,7 +391,15 @@ class NeRFRunner:
                     # this rank's slice of the batch: forward + loss + backward into the flat bucket, ONE SUM all-reduce (nerf.py:473-474)
                     _, _, loss = par.train_step_local(self.model, self.bucket, row, col, poses_bound, self.K_inv, pix_val, batch[-1],
                                                       self.world, self.group, alpha=batch[5] if masked else None,
-                                                      mask_weight=self.mask_weight)
+                                                      mask_weight=self.mask_weight, dist_weight=self.dist_weight)
+                elif self.dist_weight > 0:
+                    # ... + DIST_WEIGHT * distortion_loss through autograd (forward(maps=True, distortion=True), nerf_hip_backward_distortion)
+                    self.model.grad_bucket = self.bucket
+                    try:
+                        _, _, loss = regularized_train_step(self.model, row, col, poses_bound, self.K_inv, pix_val, batch[5] if masked else None,
+                                                            self.mask_weight, self.dist_weight)
+                    finally:
+                        self.model.grad_bucket = None
                 elif masked:
                     # ray_loss + MASK_WEIGHT * mask_loss through autograd (forward(maps=True), nerf_hip_backward_maps) into the bucket
                     self.model.grad_bucket = self.bucket
