@@ -387,6 +387,10 @@ int nerf_hip_gather_rays(const int64_t* index, const float* pixels, const float*
  * bit-identical to the forward's at the same point and direction.  The model's flags do not apply (no bf16 / split-fp32 variant).
  * Enqueue-only; each call packs its own weight image into `ws` (a query workspace, never a forward's).  Accurate for |p_c| <= 320:
  * the encoding's phase reduction holds its error below 1e-10 rad up to 2^20 rad, and the largest point frequency is 1024 pi.
+ * Beyond that nothing is checked or refused, and the results are not those of sinf / cosf: sin and cos of a phase stay within 2^-23 of
+ * the true values below 2^29 rad (|p_c| < 1.6e5), then the error doubles with every doubling of the phase (4e-5 at 2^39 rad, 4e-2 at
+ * 2^49) while the values stay inside [-1, 1]; from 2^54 rad (|p_c| >= 5.6e12) they leave [-1, 1] and grow without bound (1e2 at 2^55
+ * rad, 1e12 at 2^59; the first +-inf / NaN at 2^70 rad, nothing finite left by 2^90 rad), and so do the outputs.  Callers keep their points inside the domain.
  * ------------------------------------------------------------------------------------------- */
 
 /* Bytes of workspace (256-byte aligned) for the two calls below: packed weight image, fold and, with_rgb != 0, the direction

@@ -212,6 +212,7 @@ __device__ __forceinline__ void sincos_phase(float ph, float& sn, float& cs) {
   const float b = (q & 1) ? ps : pc;
   sn = (q & 2) ? -a : a;
   cs = ((q + 1) & 2) ? -b : b;
+  sn = (ph == 0.f) ? ph : sn;  // sin(-0) = -0 like sinf: the reduction's fma and the last fmaf each add zeros of opposite sign, which gives +0
 }
 
 // gamma_p of this thread's sample -> act[sm][0..63] (cols 60..63 = 0).  Wave wv writes (c,l) pairs 8wv .. 8wv+7.
