@@ -65,7 +65,8 @@ extern "C" {
                                      (with NERF_HIP_MAX_QUANTILES); nerf_hip_forward_distortion_train,
                                      nerf_hip_backward_distortion, nerf_hip_coarse_composite_distortion,
                                      nerf_hip_merge_composite_distortion, nerf_hip_coarse_composite_backward_distortion,
-                                     nerf_hip_merge_composite_backward_distortion */
+                                     nerf_hip_merge_composite_backward_distortion; nerf_hip_mesh_atlas_dims,
+                                     nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1032,6 +1033,67 @@ int nerf_hip_tsdf_integrate_color(float* tsdf, float* weight, float* color, int 
  * are HOST arrays.  Enqueue-only. */
 int nerf_hip_tsdf_sample_color(const float* color, int nx, int ny, int nz, const float* lo3, const float* step3, const float* points,
                                int64_t M, float* rgb, uint8_t* valid, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Texture atlases of indexed meshes: a parameterisation that is a pure function of the
+ * face count, the surface point and viewing direction of every texel (the caller shades them: a field query, a colour volume), and
+ * bilinear lookups by (face, u, v) -- what nerf_hip_mesh_raycast returns.  verts, normals [V][3] fp32, faces [F][3] int32.
+ *
+ * TA. THE ATLAS RULE.  Every face gets the same right-isosceles chart.  n (an int >= 2) is the chart edge in texels, c = n + 5 the cell
+ *    edge, K = ceil(F / 2) the number of cells.  Sx is the smallest integer with Sx * Sx >= K (integer arithmetic), Sy = ceil(K / Sx);
+ *    the atlas is W = Sx * c texels wide and H = Sy * c high, an image [H][W] with row y and column x; F = 0 gives Sx = Sy = W = H = 0.
+ *    Face f lives in cell k = f >> 1 at (cx, cy) = (k % Sx, k / Sx).  Of the cell-local texel (i, j), 0 <= i, j < c (i along x), the
+ *    even (LOWER) face owns i + j <= c - 1 and the odd (UPPER) face i + j >= c; the upper face is addressed through the point
+ *    reflection (i, j) -> (c - 1 - i, c - 1 - j), after which everything below is the lower face's.  A texel whose face index is >= F
+ *    (the last upper half of an odd F, the unused cells of the last row) is UNOWNED: mask 0, point 0, dir 0.
+ *    Chart corners, in cell-local texel coordinates with texel (i, j)'s centre at (i + 0.5, j + 0.5): A = (1.5, 1.5),
+ *    B = (1.5 + n, 1.5), C = (1.5, 1.5 + n) -- on texel centres; an upper face's are c - these.  The UV table: uv[f][corner] =
+ *    (fp32(cx * c + x) / fp32(W), fp32(cy * c + y) / fp32(H)), one fp32 division each (the half-integers are exact in fp32 below
+ *    2^23), y pointing DOWN (a file format with v pointing up stores 1 - y).
+ *    Weights of a lower texel, with a = i - 1, b = j - 1, as integers over 2n:
+ *       SUPPORT  a >= 0, b >= 0, a + b <= n + 1:   (w0, u, v) * 2n = (2n - 2a - 2b, 2a, 2b).  On a + b = n + 1 this extrapolates one
+ *                texel past the hypotenuse (w0 = -1/n), on purpose: with it a bilinear lookup inside the chart returns a colour that is
+ *                linear over the face exactly; clamping there instead is wrong by 0.1 .. 0.25 of the colour range at the hypotenuse.
+ *       GUTTER   every other owned texel: a and b are clamped to [0, n]; then, if a + b > n, the point is projected onto the
+ *                hypotenuse: (u, v) * 2n = (a - b + n, b - a + n); otherwise (u, v) * 2n = (2a, 2b).  w0 * 2n = 2n - u * 2n - v * 2n.
+ *    Each weight is one fp32 division fp32(integer) / fp32(2n).  With the face's corners (A3, B3, C3) = verts[faces[f]] and their
+ *    normals, per axis in fp32, every product and sum rounded on its own:
+ *       p  = w0 * A3 + (u * B3 + v * C3),      nb = w0 * nA + (u * nB + v * nC)
+ *       L  = sqrt((nb_x * nb_x + nb_y * nb_y) + nb_z * nb_z),      dir = -(nb / L) where L is finite and > 0, else (0, 0, 0)
+ *    (the normalisation of the marching-cubes normals).  A texel ON A VERTEX -- two of the three integer weights are 0, the third is
+ *    then 2n: the corner texels and the gutter texels clamped onto them -- takes that vertex's position and normal as they are:
+ *    p = the vertex, dir = -normal (0 where a component of the normal is not finite).  Normalising a unit fp32 vector again can move
+ *    it by an ulp; taken as it is, the corner texel is shaded with exactly the point and direction of the mesh's own vertex colour.
+ *    An owned texel has mask 1 -- unless its face has an index outside [0, V): mask 0, point 0, dir 0.
+ *    Two properties follow (tests/test_mesh_texture_cpu.py holds them): every texel a bilinear lookup inside a face's chart touches with
+ *    non-zero weight is owned by that face, and a colour linear over the face comes back from the lookup exactly.
+ *    Uniform charts: a sliver gets as many texels as a large face; charts sized by area are not built.
+ *
+ * TX. THE LOOKUP RULE.  face[N] int32, uv[N][2] fp64, image[H][W][3] fp32 over the atlas of (F, n) -> rgb[N][3] fp32, valid[N] uint8.
+ *    face < 0, face >= F, or u or v not finite: rgb = background, valid = 0.  Otherwise valid = 1 and, in fp64 with every operation
+ *    rounded on its own:  u = min(max(u, 0), 1),  v = min(max(v, 0), 1 - u);  tx = 1 + u * n,  ty = 1 + v * n  (the point
+ *    A + u (n, 0) + v (0, n) in units of texel centres);  i0 = min(floor(tx), c - 2), fx = tx - i0, and j0, fy alike.  The four texels
+ *    (i0 + di, j0 + dj) of the lower chart -- reflected for an upper face, then moved to the face's cell -- are visited in the order
+ *    (dj, di), di fastest; one with weight w = wx * wy != 0 (wx = fx at di = 1, 1 - fx at di = 0) adds w * double(texel_ch) to a sum
+ *    that starts at 0.0; one with weight 0 is not read.  rgb_ch = fp32(sum).  At a chart corner the result is the corner texel's bits.
+ *
+ * Refused (NERF_HIP_ERR_ARG): n < 2, F < 0 or V < 0, 3 F >= 2^31, W * H >= 2^31 (or W or H alone), row0 < 0, rows < 0,
+ * row0 + rows > H, N < 0 or >= 2^31, a NULL out5, a NULL faces with F > 0, a NULL verts / normals with V > 0 and, where there is
+ * something to write or read, a NULL points / dirs / mask, image / face / uv / background3 / rgb / valid; a uv that is not 8-byte
+ * aligned.  Empty calls succeed and launch nothing.  Enqueue-only; background3 and out5 are HOST arrays.
+ * ------------------------------------------------------------------------------------------- */
+
+/* TA's sizes, on the host: out5 = c, Sx, Sy, W, H. */
+int nerf_hip_mesh_atlas_dims(int64_t F, int n, int* out5);
+
+/* TA: the texels of the atlas rows [row0, row0 + rows), T = rows * W of them in row-major order: points[T][3], dirs[T][3] fp32,
+ * mask[T] uint8. */
+int nerf_hip_mesh_atlas_texels(const float* verts, const float* normals, const int32_t* faces, int64_t V, int64_t F, int n, int row0,
+                               int rows, float* points, float* dirs, uint8_t* mask, void* stream);
+
+/* TX: image is the [H][W][3] atlas of (F, n). */
+int nerf_hip_mesh_texture_sample(const float* image, int64_t F, int n, const int32_t* face, const double* uv, int64_t N,
+                                 const float* background3, float* rgb, uint8_t* valid, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stage entry points (same kernels as nerf_hip_forward; exposed so each row of the hot-path

@@ -129,6 +129,9 @@ _PROTOS = {
     "nerf_hip_mesh_count_masked": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, C.c_size_t, _p, _p]),
     "nerf_hip_mesh_emit_masked": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_float, _p, C.c_size_t, _p, _p, _p, C.c_int64,
                                             C.c_int64, _p]),
+    "nerf_hip_mesh_atlas_dims": (C.c_int, [C.c_int64, C.c_int, _p]),
+    "nerf_hip_mesh_atlas_texels": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p]),
+    "nerf_hip_mesh_texture_sample": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, C.c_int64, _p, _p, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -240,6 +243,13 @@ def mesh_select_faces_ws_bytes(V: int, F: int) -> int:
     n = C.c_size_t(0)
     check(lib().nerf_hip_mesh_select_faces_ws_bytes(int(V), int(F), C.byref(n)))
     return int(n.value)
+
+
+def mesh_atlas_dims(F: int, n: int) -> tuple:
+    """Rule TA's sizes (c, Sx, Sy, W, H) of the atlas of F faces with charts of n texels (nerf_hip_mesh_atlas_dims; host only)."""
+    out = (C.c_int * 5)()
+    check(lib().nerf_hip_mesh_atlas_dims(int(F), int(n), out))
+    return tuple(int(x) for x in out)
 
 
 def points_nearest_ws_bytes(M: int, N: int, dims) -> int:

@@ -1516,6 +1516,105 @@ int nerf_hip_tsdf_sample_color(const float* color, int nx, int ny, int nz, const
 
 namespace {
 
+struct AtlasDims {
+  int c, Sx, Sy, W, H;
+};
+
+// rule TA's sizes of the atlas of F faces with charts of n texels, in integers, and its refusals
+int atlas_dims(int64_t F, int n, AtlasDims* d) {
+  if (n < 2) return fail(NERF_HIP_ERR_ARG, "n=%d: a chart has at least 2 texels along its edge", n);
+  if (F < 0) return fail(NERF_HIP_ERR_ARG, "F=%lld < 0", (long long)F);
+  if (F > ((1ll << 31) - 1) / 3) return fail(NERF_HIP_ERR_ARG, "F=%lld: the 3 F entries of the UV table must stay below 2^31", (long long)F);
+  const long long c = (long long)n + 5, K = (F + 1) / 2;
+  long long Sx = 0;
+  while (Sx * Sx < K) ++Sx;  // (K < 2^29: at most 2^14.5 steps, on the host)
+  const long long Sy = Sx > 0 ? (K + Sx - 1) / Sx : 0;
+  const long long W = Sx * c, H = Sy * c;
+  if (W >= (1ll << 31) || H >= (1ll << 31) || W * H >= (1ll << 31))
+    return fail(NERF_HIP_ERR_ARG, "F=%lld n=%d: the atlas of %lld x %lld texels must stay below 2^31 texels", (long long)F, n, W, H);
+  d->c = (int)c, d->Sx = (int)Sx, d->Sy = (int)Sy, d->W = (int)W, d->H = (int)H;
+  return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_mesh_atlas_dims(int64_t F, int n, int* out5) {
+  if (!out5) return fail(NERF_HIP_ERR_ARG, "out5 is null");
+  AtlasDims d;
+  if (int rc = atlas_dims(F, n, &d)) return rc;
+  out5[0] = d.c, out5[1] = d.Sx, out5[2] = d.Sy, out5[3] = d.W, out5[4] = d.H;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_atlas_texels(const float* verts, const float* normals, const int32_t* faces, int64_t V, int64_t F, int n, int row0,
+                               int rows, float* points, float* dirs, uint8_t* mask, void* stream) {
+  if (int rc = check_mesh_sizes(V, F)) return rc;
+  AtlasDims d;
+  if (int rc = atlas_dims(F, n, &d)) return rc;
+  if (row0 < 0 || rows < 0 || (long long)row0 + rows > d.H)
+    return fail(NERF_HIP_ERR_ARG, "row0=%d rows=%d: a band of the atlas's %d rows", row0, rows, d.H);
+  if (int rc = check_mesh_ptrs(verts, faces, V, F)) return rc;
+  if (V > 0 && !normals) return fail(NERF_HIP_ERR_ARG, "normals is null");
+  const long long T = (long long)rows * d.W;
+  if (T == 0) return NERF_HIP_OK;  // (empty arrays may have null pointers)
+  if (!points || !dirs || !mask) return fail(NERF_HIP_ERR_ARG, "points / dirs / mask is null");
+  if (int rc = check_device()) return rc;
+  AtlasTexelsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.verts = verts;
+  a.normals = normals;
+  a.faces = faces;
+  a.V = (int)V;
+  a.F = (int)F;
+  a.n = n;
+  a.c = d.c;
+  a.Sx = d.Sx;
+  a.W = d.W;
+  a.row0 = row0;
+  a.T = T;
+  a.points = points;
+  a.dirs = dirs;
+  a.mask = mask;
+  HIP_TRY(launch_atlas_texels(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_mesh_texture_sample(const float* image, int64_t F, int n, const int32_t* face, const double* uv, int64_t N,
+                                 const float* background3, float* rgb, uint8_t* valid, void* stream) {
+  AtlasDims d;
+  if (int rc = atlas_dims(F, n, &d)) return rc;
+  if (N < 0) return fail(NERF_HIP_ERR_ARG, "N=%lld < 0", (long long)N);
+  if (N >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "N=%lld: a call makes fewer than 2^31 lookups", (long long)N);
+  if (!background3) return fail(NERF_HIP_ERR_ARG, "background3 is null");
+  if (N == 0) return NERF_HIP_OK;  // (empty arrays may have null pointers)
+  if (F > 0 && !image) return fail(NERF_HIP_ERR_ARG, "image is null");
+  if (!face || !rgb || !valid) return fail(NERF_HIP_ERR_ARG, "face / rgb / valid is null");
+  if (int rc = check_out(uv, "uv", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  TextureSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.image = image;
+  a.F = (int)F;
+  a.n = n;
+  a.c = d.c;
+  a.Sx = d.Sx;
+  a.W = d.W;
+  a.face = face;
+  a.uv = uv;
+  a.N = N;
+  for (int e = 0; e < 3; ++e) a.bg[e] = background3[e];
+  a.rgb = rgb;
+  a.valid = valid;
+  HIP_TRY(launch_texture_sample(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 // Shapes of the image-metrics calls: H, W >= the SSIM window, a view's element count below 2^31.  Sets the tile counts.
 int check_metrics_shape(int n, int H, int W, int* tiles_x, int* tiles) {
   if (n < 0) return fail(NERF_HIP_ERR_ARG, "n=%d < 0", n);

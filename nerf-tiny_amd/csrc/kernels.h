@@ -726,6 +726,35 @@ struct TsdfSampleArgs {
 
 hipError_t launch_tsdf_sample_color(const TsdfSampleArgs& a, hipStream_t st);
 
+// ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
+// 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
+constexpr int TEX_WG = 256;
+
+struct AtlasTexelsArgs {
+  const float *verts, *normals;  // [V][3]
+  const int* faces;        // [F][3]
+  int V, F;
+  int n, c, Sx, W;         // chart edge, cell edge, cells per atlas row, atlas width
+  int row0;                // the band's first atlas row
+  long long T;             // rows * W < 2^31: the band's texels
+  float *points, *dirs;    // [T][3]
+  unsigned char* mask;     // [T]
+};
+
+struct TextureSampleArgs {
+  const float* image;      // [H][W][3]
+  int F, n, c, Sx, W;
+  const int* face;         // [N]
+  const double* uv;        // [N][2]
+  long long N;
+  float bg[3];
+  float* rgb;              // [N][3]
+  unsigned char* valid;    // [N]
+};
+
+hipError_t launch_atlas_texels(const AtlasTexelsArgs& a, hipStream_t st);
+hipError_t launch_texture_sample(const TextureSampleArgs& a, hipStream_t st);
+
 // ---- narrow-band density grid (band.hip + k_field_fwd_reg's SRC_CORNERS / SRC_BLOCKS forms; nerf_hip_band_*) ----
 constexpr int BAND_WG = 256;                   // blocks per workgroup of the per-block kernels (the scan's unit)
 

@@ -87,6 +87,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mesh-tsdf-max-spread", type=float, default=None, metavar="S",
                     help="--mesh-tsdf leaves out the pixels whose interquartile depth range exceeds S world units (smeared or bimodal rays) "
                          "and prints how many (default: keep every pixel)")
+    ap.add_argument("--mesh-texture", type=int, nargs="?", const=2048, default=None, metavar="SIZE",
+                    help="--mesh also bakes a texture atlas of at most SIZE x SIZE texels (default 2048) for the final mesh -- the field queried "
+                         "at every texel along the inward normal, or with --mesh-tsdf-color the fused colours -- and writes "
+                         "<...>_mesh<RES>.obj / .mtl / .png beside the .ply (every face gets the same chart: --mesh-simplify makes the faces "
+                         "more uniform first)")
     ap.add_argument("--mesh-compare", default=None, metavar="FILE",
                     help="--mesh measures the extracted mesh against the ground-truth triangle mesh in FILE (PLY, ASCII or binary "
                          "little-endian) on the device: Chamfer distance, precision / recall / F-score, area and volume, printed and written "
@@ -161,7 +166,7 @@ if __name__ == "__main__":
                              compare_samples=args.mesh_compare_samples, compare_tau=tuple(args.mesh_compare_tau), visible_from=args.mesh_visible,
                              tsdf_from=args.mesh_tsdf, tsdf_trunc=args.mesh_tsdf_trunc, tsdf_every=args.mesh_tsdf_every,
                              tsdf_color=args.mesh_tsdf_color, tsdf_unseen=args.mesh_tsdf_unseen, tsdf_depth_stat=args.mesh_tsdf_depth,
-                             tsdf_max_spread=args.mesh_tsdf_max_spread)
+                             tsdf_max_spread=args.mesh_tsdf_max_spread, texture=args.mesh_texture)
         if m is not None and args.mesh_smooth is not None:  # (new with --mesh-smooth; a run without it prints what it printed before)
             import torch
 

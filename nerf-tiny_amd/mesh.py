@@ -6,7 +6,9 @@ evaluation on the device -- measures, area-weighted surface samples, exact neare
 (csrc/mesh_distance.hip) --, rays against a mesh on the device -- closest hits, occlusion, depth images, the
 faces no camera sees (csrc/mesh_raycast.hip) --, TSDF fusion of depth images into a signed distance volume on the
 device (csrc/tsdf.hip), with the views' colours fused beside it and marching cubes under a mask of observed
-points, and a PLY writer and reader.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
+points, texture atlases -- a per-face parameterisation, the texels' surface points and viewing directions on
+the device, a baker, bilinear lookups by (face, u, v) and the textured mesh seen from a camera (csrc/mesh_texture.hip, DESIGN.md section
+3h-11) --, a PLY writer and reader and an OBJ / MTL / PNG writer.  NeRFModel.extract_mesh / NeRFRunner.extract_mesh
 build on these."""
 from __future__ import annotations
 
@@ -721,8 +723,185 @@ def tsdf_grid(T, Wt, unseen="solid"):
     return torch.where(torch.as_tensor(Wt) > 0, -T, torch.full_like(T, 1.0 if unseen == "solid" else -1.0))
 
 
+class Texture(NamedTuple):
+    image: object    # [H, W, 3] fp32 (device): the baked atlas, row y from the top; 0 where mask is False
+    mask: object     # [H, W] bool: the texels some face owns
+    chart: int       # n: the chart edge in texels
+    faces: int       # F: the face count the atlas was laid out for
+    uv: object       # [F, 3, 2] fp32 (device): per face and corner (x / W, y / H), y pointing down
+
+
+ATLAS_PAD = 5  # a cell is chart + 5 texels wide (rule TA of include/nerf_hip.h)
+
+
+def atlas_dims(F, chart):
+    """The sizes of rule TA's atlas (include/nerf_hip.h) for F faces with charts of ``chart`` texels -> (c, Sx, Sy, W, H) as ints: the
+    cell edge c = chart + 5, the cells per row and column, and the W x H texels.  Two faces share a cell, the cells fill the rows of
+    the smallest square that holds them; F = 0 gives a 0 x 0 atlas.  Integer arithmetic only.  ValueError for chart < 2, F < 0,
+    3 F >= 2^31 or W * H >= 2^31 (what nerf_hip_mesh_atlas_dims refuses)."""
+    import math
+
+    if int(F) != F or int(chart) != chart:
+        raise ValueError(f"F={F!r} chart={chart!r}: two ints")
+    F, n = int(F), int(chart)
+    if n < 2:
+        raise ValueError(f"chart={n}: a chart has at least 2 texels along its edge")
+    if F < 0 or 3 * F >= 2 ** 31:
+        raise ValueError(f"F={F}: 0 <= 3 F < 2^31")
+    c, K = n + ATLAS_PAD, (F + 1) // 2
+    Sx = math.isqrt(K)
+    Sx += Sx * Sx < K
+    Sy = -(-K // Sx) if Sx else 0
+    if Sx * c * Sy * c >= 2 ** 31:
+        raise ValueError(f"F={F} chart={n}: the atlas of {Sx * c} x {Sy * c} texels must stay below 2^31 texels")
+    return c, Sx, Sy, Sx * c, Sy * c
+
+
+def atlas_chart(F, size):
+    """The largest chart n >= 2 whose atlas for F faces is at most ``size`` texels wide (and so at most as high): Sx * (n + 5) <= size.
+    ValueError where even n = 2 does not fit, or F = 0."""
+    Sx = atlas_dims(F, 2)[1]
+    n = int(size) // Sx - ATLAS_PAD if Sx else 0
+    if n < 2:
+        raise ValueError(f"size={size!r}: the atlas of F={int(F)} faces needs at least {Sx * (2 + ATLAS_PAD)} texels along its edge (and F > 0)")
+    atlas_dims(F, n)
+    return n
+
+
+def atlas_uv(F, chart, device):
+    """Rule TA's UV table [F, 3, 2] fp32 on ``device``: per face and corner (x / W, y / H) of the chart's corners A, B, C in the atlas,
+    y pointing down -- the half-integer texel coordinates as fp32, one correctly rounded division each (formed in fp64 from the two
+    fp32 operands, which rounds to the same fp32)."""
+    c, Sx, _, W, H = atlas_dims(F, chart)
+    n = int(chart)
+    f = torch.arange(int(F), device=device)
+    k = f >> 1
+    upper = (f & 1).view(-1, 1).double()
+    local = torch.tensor([[1.5, 1.5], [1.5 + n, 1.5], [1.5, 1.5 + n]], dtype=torch.float64, device=device)  # A, B, C of a lower chart
+    x = local[:, 0].view(1, 3) * (1 - 2 * upper) + upper * c + ((k % max(Sx, 1)) * c).view(-1, 1).double()  # (an upper chart's are c - these)
+    y = local[:, 1].view(1, 3) * (1 - 2 * upper) + upper * c + ((k // max(Sx, 1)) * c).view(-1, 1).double()
+    size = torch.tensor([max(W, 1), max(H, 1)], dtype=torch.float32, device=device).double()
+    return (torch.stack((x, y), dim=2).float().double() / size).float()
+
+
+def atlas_texels(m, chart, row0=0, rows=None):
+    """The surface point and the viewing direction of every texel of the rows [row0, row0 + rows) (default: to the last row) of the
+    Mesh m's atlas with charts of ``chart`` texels, on the DEVICE -> (points [rows, W, 3], dirs [rows, W, 3] fp32, mask [rows, W]
+    bool).  A texel's point is the barycentric blend of its face's corners and its direction the negated, normalised blend of their
+    normals (m.normals is required): what extract_mesh asks the field for at a vertex, at every texel.  mask is False, and both are
+    0, for the texels no face owns and for faces with an index outside [0, V).  The exact rule is TA of include/nerf_hip.h; identical
+    bits from run to run.  A CPU tensor raises: there is no CPU path."""
+    from . import ops
+
+    verts, faces = _on_device(m.verts, "atlas_texels"), torch.as_tensor(m.faces)
+    if m.normals is None:
+        raise ValueError("atlas_texels: the mesh needs vertex normals (the texels' viewing directions)")
+    _, _, _, W, H = atlas_dims(faces.shape[0], chart)
+    rows = H - int(row0) if rows is None else int(rows)
+    if int(row0) < 0 or rows < 0 or int(row0) + rows > H:
+        raise ValueError(f"row0={row0!r} rows={rows!r}: a band of the atlas's {H} rows")
+    p, d, k = ops.mesh_atlas_texels(verts, torch.as_tensor(m.normals), faces, int(chart), int(row0), rows)
+    return p.view(rows, W, 3), d.view(rows, W, 3), k.view(rows, W) != 0
+
+
+def bake_texture(m, chart, shade, rows_per_call=None):
+    """Bakes a texture atlas for the Mesh m on the DEVICE: shade(points [T, 3], dirs [T, 3]) -> rgb [T, 3] is called on the texels of
+    atlas_texels(m, chart), a band of rows_per_call atlas rows at a time (default: about 2^20 texels), so no more than one band's
+    points and directions exist at once; the result does not depend on rows_per_call.  Returns a Texture: the image (0 where no face
+    owns the texel), the mask, the chart, the face count and the UV table.  Every face gets the same chart -- a sliver as many texels as
+    a large face; simplify the mesh first (simplify= of extract_mesh) to make the faces more uniform.  shade sees the unowned
+    texels too (point 0, direction 0); their result is dropped."""
+    verts, faces = _on_device(m.verts, "bake_texture"), torch.as_tensor(m.faces)
+    F = int(faces.shape[0])
+    _, _, _, W, H = atlas_dims(F, chart)
+    per = max(1, (1 << 20) // max(W, 1)) if rows_per_call is None else int(rows_per_call)
+    if per < 1:
+        raise ValueError(f"rows_per_call={rows_per_call!r}: None or an int >= 1")
+    image = torch.zeros(H, W, 3, device=verts.device)
+    mask = torch.zeros(H, W, dtype=torch.bool, device=verts.device)
+    for r0 in range(0, H, per):
+        r = min(per, H - r0)
+        p, d, k = atlas_texels(m, chart, r0, r)
+        rgb = torch.as_tensor(shade(p.view(-1, 3), d.view(-1, 3))).view(r, W, 3)
+        image[r0:r0 + r] = torch.where(k[..., None], rgb, torch.zeros_like(rgb))
+        mask[r0:r0 + r] = k
+    return Texture(image, mask, int(chart), F, atlas_uv(F, chart, verts.device))
+
+
+def sample_texture(tex, face, uv, background=(0.0, 0.0, 0.0)):
+    """The Texture tex looked up at (face [N] int32, uv [N, 2] fp64) -- raycast()'s face and barycentrics: the point is
+    (1 - u - v) A + u B + v C -- on the DEVICE -> (rgb [N, 3] fp32, valid [N] bool): bilinear over the four texels of the face's chart
+    around the point, in fp64, (u, v) clamped into the triangle; ``background`` and valid False for face < 0, face >= tex.faces or a
+    uv that is not finite.  A lookup touches only texels its own face owns, and at a corner returns the corner texel's bits.  The
+    exact rule is TX of include/nerf_hip.h.  CPU tensors raise: there is no CPU path."""
+    from . import ops
+
+    image, face = _on_device(tex.image, "sample_texture"), _on_device(face, "sample_texture")
+    rgb, valid = ops.mesh_texture_sample(image, tex.faces, tex.chart, face.reshape(-1), torch.as_tensor(uv).reshape(-1, 2), background)
+    return rgb, valid != 0
+
+
+def render_texture(handle, tex, poses_bound17, K_inv, H, W, background=(0.0, 0.0, 0.0)):
+    """The textured mesh seen from the cameras poses_bound17 [n, 17] along the renderer's own rays: camera_rays -> raycast(handle) ->
+    sample_texture(tex) -> (rgb [n, H, W, 3] fp32, hit [n, H, W] bool), ``background`` where a pixel's ray meets no face.  handle: a
+    build_raycast of the mesh tex was baked for.  The images feed metrics.image_metrics as they are."""
+    _, face, uv = render_depth(handle, poses_bound17, K_inv, H, W)
+    rgb, valid = sample_texture(tex, face.reshape(-1), uv.reshape(-1, 2), background)
+    return rgb.view(*face.shape, 3), valid.view(face.shape)
+
+
 def _np(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def png_bytes(rgb8):
+    """An 8-bit RGB PNG of rgb8 [H, W, 3] uint8, top row first: one IDAT chunk, filter 0 on every row, the standard library's zlib."""
+    import struct
+    import zlib
+
+    img = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    H, W = img.shape[:2]
+    raw = np.concatenate((np.zeros((H, 1), np.uint8), img.reshape(H, W * 3)), axis=1).tobytes()
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6))
+            + chunk(b"IEND", b""))
+
+
+def write_obj(path, m, tex):
+    """The Mesh m with the Texture tex as a Wavefront OBJ: ``path`` (.obj) with ``v`` / ``vn`` / ``vt`` lines -- 3 F ``vt`` entries, face f's
+    corners at 3 f + 1 .. 3 f + 3, as (x, 1 - y): OBJ's v points up --, ``f a/ta/na`` faces (1-based), ``mtllib`` / ``usemtl``; beside it
+    <stem>.mtl with ``map_Kd <stem>.png`` and <stem>.png, the atlas as 8-bit RGB (clip(rint(x * 255), 0, 255) as in write_ply, top row
+    first; png_bytes).  Floats are written with 9 significant digits, which reads back to the same fp32.  An empty atlas (F = 0) is
+    written as a 1 x 1 black image.  Returns the three paths."""
+    import os
+
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    v = _np(m.verts).astype(np.float32).reshape(-1, 3)
+    f = _np(m.faces).astype(np.int64).reshape(-1, 3)
+    vn = None if m.normals is None else _np(m.normals).astype(np.float32).reshape(-1, 3)
+    uv = _np(tex.uv).astype(np.float32).reshape(-1, 2)
+    if len(uv) != 3 * len(f) or tex.faces != len(f):
+        raise ValueError(f"the texture was laid out for {tex.faces} faces, the mesh has {len(f)}")
+    img = np.clip(np.rint(_np(tex.image).astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+    if img.size == 0:
+        img = np.zeros((1, 1, 3), np.uint8)
+    g = lambda x: np.format_float_positional(x, precision=9, unique=True, trim="0") if np.isfinite(x) else repr(float(x))
+    lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+    lines += [f"v {g(p[0])} {g(p[1])} {g(p[2])}" for p in v]
+    if vn is not None:
+        lines += [f"vn {g(p[0])} {g(p[1])} {g(p[2])}" for p in vn]
+    lines += [f"vt {g(t[0])} {g(np.float32(1.0) - t[1])}" for t in uv]
+    for k, (a, b, c) in enumerate(f + 1):
+        t = 3 * k + 1
+        lines.append(f"f {a}/{t}/{a} {b}/{t + 1}/{b} {c}/{t + 2}/{c}" if vn is not None else f"f {a}/{t} {b}/{t + 1} {c}/{t + 2}")
+    with open(stem + ".obj", "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w") as fh:
+        fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    with open(stem + ".png", "wb") as fh:
+        fh.write(png_bytes(img))
+    return stem + ".obj", stem + ".mtl", stem + ".png"
 
 
 def write_ply(path, verts, faces, normals=None, rgb=None):

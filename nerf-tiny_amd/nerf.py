@@ -677,7 +677,7 @@ class NeRFModel(nn.Module):
 
     @torch.no_grad()
     def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None,
-                     smooth=None, visible=None):
+                     smooth=None, visible=None, texture=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the
         grid's lattice, inside = sigma > level) -> with color, query(verts, dirs=-normals), the colour a ray looking at the surface along
         its inward normal sees.  Returns mesh.Mesh(verts [V, 3], faces [F, 3] int32, normals [V, 3], rgb [V, 3] or None) on the model's
@@ -711,7 +711,11 @@ class NeRFModel(nn.Module):
         cannot drop (mesh.visibility with its default tmin: one shadow ray from each face's centroid to each camera, on the device;
         then mesh.filter_faces).  It runs AFTER the component filter and BEFORE smoothing, simplification and the normal and colour
         queries, so a hidden vertex is never evaluated.  With normals="grid" the kept vertices keep their grid normals.  The result
-        is, bit for bit, the later stages applied to mesh.filter_faces of the earlier stages' mesh."""
+        is, bit for bit, the later stages applied to mesh.filter_faces of the earlier stages' mesh.
+        texture=None: nothing more.  texture=S (an int, with color): a texture atlas of at most S x S texels is baked for the FINAL mesh
+        -- after every stage above, the normals and the colours -- with the chart mesh.atlas_chart(F, S): the field is queried at every
+        texel's surface point along its inward normal (bake_texture below), and the mesh.Texture is kept as ``self.last_texture``;
+        its corner texels are the vertex colours, bit for bit.  The returned Mesh is the one the call without texture returns."""
         import numpy as np
 
         from . import mesh
@@ -723,15 +727,33 @@ class NeRFModel(nn.Module):
         sigma = self.density_grid(lo32, hi32, shape) if band is None else self.density_band(lo32, hi32, shape, level, block=band)[0]
         verts, faces, nrm = mesh.marching_cubes(sigma, level, lo32, grid_step(lo32, hi32, shape))
         del sigma
-        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible)
+        return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible,
+                                 texture=texture)
 
-    def _mesh_stages(self, verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible, fused=None):
+    @torch.no_grad()
+    def bake_texture(self, m, chart, rows_per_call=None):
+        """A mesh.Texture of the Mesh m (with normals) with charts of ``chart`` texels, shaded by the field: mesh.bake_texture with
+        shade = query(points, dirs)[0] -- at every texel the colour a ray looking at the surface along its inward normal sees, the
+        colour extract_mesh gives the vertices; exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say.  The view direction is fixed to
+        the inward normal: view-dependent effects are baked as seen from straight ahead."""
+        from . import mesh
+
+        return mesh.bake_texture(m, chart, lambda p, d: self.query(p, d)[0], rows_per_call)
+
+    def _mesh_stages(self, verts, faces, nrm, lo32, hi32, shape, color, normals, min_faces, keep_largest, simplify, smooth, visible, fused=None,
+                     texture=None):
         """Everything of extract_mesh / extract_mesh_tsdf behind marching cubes, in extract_mesh's documented order: the component
         filter, the visibility filter, smoothing, simplification, then the field normals and the colours at the final vertices.
         verts / faces / nrm: marching cubes' output over the lattice (lo32, hi32, shape).  fused: None, or a colour volume over that
         lattice (mesh.tsdf_color_volume's C) -- with color, the colours are then mesh.tsdf_sample_color(C) at the final vertices, the
-        field is queried only at the vertices that have no fused colour, and ``self.last_fused_fallback`` is their number."""
+        field is queried only at the vertices that have no fused colour, and ``self.last_fused_fallback`` is their number.
+        texture: None, or the bound S on the atlas's edge -- with color, the final mesh is baked with the chart mesh.atlas_chart(F, S)
+        from the source of the vertex colours (the fused volume where it has a colour, the field elsewhere) into
+        ``self.last_texture``."""
         from . import mesh
+
+        if texture is not None and not color:
+            raise ValueError("texture= bakes colours: it needs color")
 
         if min_faces is not None or keep_largest is not None:
             comps = mesh.components(faces, len(verts), verts)
@@ -758,7 +780,16 @@ class NeRFModel(nn.Module):
                 rgb[miss] = self.query(verts[miss], -nrm[miss])[0]
         else:
             rgb = self.query(verts, -nrm)[0] if color else None
-        return mesh.Mesh(verts, faces, nrm, rgb)
+        m = mesh.Mesh(verts, faces, nrm, rgb)
+        if texture is not None:
+            shade = lambda p, d: self.query(p, d)[0]
+            if fused is not None:
+                def shade(p, d):
+                    c, ok = mesh.tsdf_sample_color(fused, lo32, grid_step(lo32, hi32, shape), p)
+                    return torch.where(ok[:, None], c, self.query(p, d)[0])
+            F = int(faces.shape[0])
+            self.last_texture = mesh.bake_texture(m, mesh.atlas_chart(F, int(texture)) if F else 2, shade)  # (no faces: an empty atlas)
+        return m
 
     @torch.no_grad()
     def fuse_depth(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, views_per_call=None, color=False,
@@ -851,7 +882,7 @@ class NeRFModel(nn.Module):
     @torch.no_grad()
     def extract_mesh_tsdf(self, views, lo, hi, res, trunc=None, depth="auto", min_opacity=0.5, carve=True, unseen="solid", color=True,
                           normals="grid", min_faces=None, keep_largest=None, simplify=None, smooth=None, visible=None, views_per_call=None,
-                          depth_stat="mean", max_spread=None):
+                          depth_stat="mean", max_spread=None, texture=None):
         """A triangle mesh of the surface the rendered views agree on: fuse_depth(views, lo, hi, res, ...) -> mesh.tsdf_grid(T, Wt, unseen)
         -> mesh.marching_cubes at level 0 over the same lattice -> the stages of extract_mesh behind marching cubes, with the same keywords
         and order (min_faces / keep_largest, visible, smooth, simplify, then normals and colours at the final vertices).  No density
@@ -866,7 +897,9 @@ class NeRFModel(nn.Module):
         (mesh.tsdf_sample_color); only the vertices without a fused colour -- ``self.last_fused_fallback`` of them -- query the field.
         depth_stat / max_spread: fuse_depth's (the median depth instead of the mean; pixels whose interquartile depth range exceeds
         max_spread are left out; ``self.last_tsdf_rejected`` counts them).
-        The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt), or (T, Wt, C) with color="fused"."""
+        The state of the fusion is kept as ``self.last_tsdf`` = (T, Wt), or (T, Wt, C) with color="fused".
+        texture=S: extract_mesh's -- ``self.last_texture``, baked for the final mesh; with color="fused" a texel takes the fused colour
+        at its point (mesh.tsdf_sample_color) and the field's only where the volume has none, like the vertices."""
         import numpy as np
 
         from . import mesh
@@ -888,7 +921,7 @@ class NeRFModel(nn.Module):
         else:
             verts, faces, nrm = mesh.marching_cubes(mesh.tsdf_grid(T, Wt, unseen), 0.0, lo32, grid_step(lo32, hi32, shape))
         return self._mesh_stages(verts, faces, nrm, lo32, hi32, shape, bool(color), normals, min_faces, keep_largest, simplify, smooth, visible,
-                                 fused=self.last_tsdf[2] if fuse_color else None)
+                                 fused=self.last_tsdf[2] if fuse_color else None, texture=texture)
 
     @torch.no_grad()
     def render(self, row, column, poses_bound, K_inv, lo: int = 0, hi: int | None = None, fuse_rays: int = 16384, maps: bool = False,

@@ -637,6 +637,48 @@ def tsdf_sample_color(color, lo, step, points):
     return rgb, valid
 
 
+def mesh_atlas_texels(verts, normals, faces, n, row0, rows):
+    """The texels of the rows [row0, row0 + rows) of the atlas of faces[F, 3] with charts of n texels (nerf_hip_mesh_atlas_texels; rule
+    TA of include/nerf_hip.h), T = rows * W of them in row-major order -> (points[T, 3], dirs[T, 3] fp32, mask[T] uint8).  verts,
+    normals [V, 3] fp32 on faces' device.  Enqueue only."""
+    verts, faces, V, F = _md_mesh(verts, faces)
+    normals = normals.to(torch.float32).contiguous()
+    if tuple(normals.shape) != (V, 3) or normals.device != faces.device:
+        raise ValueError(f"normals {tuple(normals.shape)} on {normals.device}: [{V}, 3] on {faces.device}")
+    dev = faces.device
+    W = _abi.mesh_atlas_dims(F, n)[3]
+    T = max(int(rows), 0) * W
+    points = torch.empty(T, 3, device=dev)
+    dirs = torch.empty(T, 3, device=dev)
+    mask = torch.empty(T, dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_atlas_texels(verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, F, int(n), int(row0), int(rows),
+                                                     points.data_ptr(), dirs.data_ptr(), mask.data_ptr(), _stream(faces)))
+    return points, dirs, mask
+
+
+def mesh_texture_sample(image, F, n, face, uv, background=(0.0, 0.0, 0.0)):
+    """Bilinear lookups in the atlas image[H, W, 3] (fp32, device, contiguous) of F faces with charts of n texels at face[N] (int32),
+    uv[N, 2] (fp64) (nerf_hip_mesh_texture_sample; rule TX of include/nerf_hip.h) -> (rgb[N, 3] fp32, valid[N] uint8); background
+    (three host floats) where a lookup is not valid.  Enqueue only."""
+    _, _, _, W, H = _abi.mesh_atlas_dims(F, n)
+    if image.device.type != "cuda" or image.dtype != torch.float32 or not image.is_contiguous() or tuple(image.shape) != (H, W, 3):
+        raise ValueError(f"image {tuple(image.shape)} {image.dtype}: a contiguous fp32 [{H}, {W}, 3] device tensor, the atlas of F={F} n={n}")
+    dev = image.device
+    if face.dim() != 1 or tuple(uv.shape) != (face.shape[0], 2):
+        raise ValueError(f"face {tuple(face.shape)} uv {tuple(uv.shape)}: [N] and [N, 2]")
+    face = face.to(dev, torch.int32).contiguous()
+    uv = uv.to(dev, torch.float64).contiguous()
+    N = int(face.shape[0])
+    bg = _abi.f32_array(background)
+    if len(bg) != 3:
+        raise ValueError("background has three entries")
+    rgb = torch.empty(N, 3, device=dev)
+    valid = torch.empty(N, dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().nerf_hip_mesh_texture_sample(image.data_ptr(), int(F), int(n), face.data_ptr(), uv.data_ptr(), N, bg, rgb.data_ptr(),
+                                                       valid.data_ptr(), _stream(image)))
+    return rgb, valid
+
+
 def distance_stats(dist2, unit, thresholds=()):
     """The statistics of squared distances dist2[N] (fp64, device) in units of `unit` (nerf_hip_distance_stats; the definition is in
     include/nerf_hip.h) -> int64[4 + K] ON THE DEVICE: the finite count, the fixed-point sums of d / unit and d2 / unit^2, the clamped,

@@ -583,7 +583,7 @@ class NeRFRunner:
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
                      keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None,
                      tsdf_from=None, tsdf_trunc=None, tsdf_every=1, tsdf_color=False, tsdf_unseen="solid", tsdf_depth_stat="mean",
-                     tsdf_max_spread=None):
+                     tsdf_max_spread=None, texture=None):
         """A triangle mesh of the current model's isosurface sigma == level over a res^3 (or res = (nx, ny, nz)) lattice spanning [lo, hi]
         (NeRFModel.extract_mesh: the density grid's lattice, marching cubes on the device, vertex colours seen along the inward
         normals).  save: writes ``<results_path><start_time>_<last_iter>_mesh<res>.ply`` (binary PLY, mesh.write_ply: positions,
@@ -618,10 +618,15 @@ class NeRFRunner:
         depth Q(0.5) is fused instead of their expected depth (NeRFModel.fuse_depth(depth_stat=): it stays on one surface where a ray
         grazes a silhouette or passes a thin floater); tsdf_max_spread: None, or a distance s >= 0 in world units -- pixels whose
         interquartile depth range exceeds s are left out of the fusion (fuse_depth(max_spread=)).  With either, the ``[TSDF]`` line also
-        names the statistic and counts the rejected pixels, and "median" puts ``_median`` right after ``_tsdf`` in the file name."""
+        names the statistic and counts the rejected pixels, and "median" puts ``_median`` right after ``_tsdf`` in the file name.
+        texture: None, or an int S (with color) -- a texture atlas of at most S x S texels is baked for the final mesh
+        (NeRFModel.extract_mesh(texture=): the field, or with tsdf_color the fused volume, at every texel; kept as
+        ``self.model.last_texture``); one ``[MESH] ... [TEXTURE]`` line gives the atlas's size, the chart, the faces and the share of
+        owned texels, and with save the mesh is also written as ``<...>_mesh<res>.obj`` / ``.mtl`` / ``.png`` beside the ``.ply``
+        (mesh.write_obj).  The returned Mesh and the ``.ply`` are unchanged; without it nothing new is computed, printed or written."""
         import numpy as np
 
-        from .mesh import Mesh, write_ply
+        from .mesh import Mesh, write_obj, write_ply
         from .mesh import tsdf_trunc as default_trunc
         from .nerf import grid_shape, grid_step
 
@@ -636,6 +641,8 @@ class NeRFRunner:
                 raise ValueError(f"visible_from={visible_from!r}: None, 'train', 'val' or 'test'")
             rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[visible_from]
             kw["visible"] = (rays.poses, self.K_inv, rays.height, rays.width)
+        if texture is not None:
+            kw["texture"] = int(texture)
         if tsdf_from is not None:
             if tsdf_from not in ("train", "val", "test"):
                 raise ValueError(f"tsdf_from={tsdf_from!r}: None, 'train', 'val' or 'test'")
@@ -678,6 +685,11 @@ class NeRFRunner:
             print(f"[MESH] {self.last_iter} [VISIBLE] {int(seen.sum())} / {int(seen.numel())} faces seen from the {len(per_cam)} {visible_from} "
                   f"cameras (per camera {min(per_cam, default=0)} .. {max(per_cam, default=0)})")
         out = Mesh(*(None if a is None else a.cpu().numpy() for a in m))
+        if texture is not None:
+            tex = self.model.last_texture
+            th, tw = (int(n) for n in tex.mask.shape)
+            print(f"[MESH] {self.last_iter} [TEXTURE] {tw} x {th}, chart {tex.chart}, {tex.faces} faces, "
+                  f"{int(tex.mask.sum()) / max(th * tw, 1):.3f} of the texels owned")
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
             tsdf_tag = "" if tsdf_from is None else "_tsdf" + ("_median" if tsdf_depth_stat == "median" else "") + ("_fused" if fused else "") + ("_skip" if tsdf_unseen == "skip" else "")
@@ -685,6 +697,8 @@ class NeRFRunner:
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
             write_ply(path, out.verts, out.faces, out.normals, out.rgb)
+            if texture is not None:
+                write_obj(path[:-4] + ".obj", out, tex)
         if compare is not None:
             self.last_mesh_eval = self._compare_mesh(m, compare, compare_samples, compare_tau, save)
         return out
