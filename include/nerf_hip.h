@@ -66,7 +66,8 @@ extern "C" {
                                      nerf_hip_backward_distortion, nerf_hip_coarse_composite_distortion,
                                      nerf_hip_merge_composite_distortion, nerf_hip_coarse_composite_backward_distortion,
                                      nerf_hip_merge_composite_backward_distortion; nerf_hip_mesh_atlas_dims,
-                                     nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample */
+                                     nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample; nerf_hip_normals_ws_bytes,
+                                     nerf_hip_normals_ws_offset, nerf_hip_forward_normals, nerf_hip_normal_composite */
 
 enum {
   NERF_HIP_OK = 0,
@@ -271,6 +272,58 @@ int nerf_hip_backward_distortion(const float* const* weights24, const float* dC_
                                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta,
                                  float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream,
                                  void* early_event, const float* ddist /* device [B][2] */);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Per-ray normal maps: the field's normals composited with the ray's own weights, beside the
+ * maps' D / A and rule QD's quantile depths.
+ *
+ * NM. THE NORMAL RULE, for one pass of one ray: samples t_0 .. t_{N-1} in the order the composite visits them, with the composite's own
+ *    fp32 weights w_i.  Coarse pass: t_c with w_c, N = Nc.  Fine pass: the SORTED depth channel t_s (channel 0 of the sorted bundle) with
+ *    the w of C_fine, N = Nc + Nf -- without NERF_HIP_CORRECTED it inherits quirk Q1 exactly as D_f and the quantiles do, with
+ *    NERF_HIP_CORRECTED it is physical.
+ *       p_i = the world point of the ray at depth t_i as the forward forms it: v = d_cam * t_i, p = ((R0 v0 + R1 v1) + R2 v2) + o, every
+ *             product and sum rounded separately -- the forward's own points, bit for bit
+ *       g_i = what nerf_hip_query_grad(points = p_i, dirs = NULL, dsigma = NULL) stores in dpoints, bit for bit: the exact-fp32 gradient
+ *             of sigma under the train step's convention, whatever NERF_HIP_BF16_MLP / NERF_HIP_SPLIT_MLP say (only the w_i come from
+ *             the mode's own forward)
+ *       n_i = the field normal of g_i, the marching-cubes kernel's rule, in fp32 with every operation rounded:
+ *             len = sqrt((g0 g0 + g1 g1) + g2 g2);  n_i = -g_i / len,  or (0, 0, 0) where len is 0 or not finite
+ *       N_c = fp32( sum_i double(w_i) * double(n_i,c) )    for c = 0 .. 2; a sample whose w_i is 0 or NaN adds nothing (w_i > 0 or
+ *             w_i < 0 is required, and comparisons are false on NaN)
+ *    The sum is fp64, deterministic and free of atomics (per-lane partial sums, then a wave reduction, as the colour sums); its ORDER is not
+ *    part of the rule: a reordering moves an fp64 sum of at most 2,048 terms of magnitude <= |w_i| by less than 2048 * 2^-53 * sum |w_i|.
+ *    N is in the world frame and NOT normalised: |N| <= A, and |N| / A says how far the normals along the ray agree.  Not differentiable;
+ *    inference only.
+ *
+ * nerf_hip_normals_ws_bytes / nerf_hip_normals_ws_offset: the SIDE workspace of nerf_hip_forward_normals for these sizes, and the byte
+ * offset of a named buffer inside it (introspection for tests): "bundle" [B,Nc+Nf,5] and "w_m" [B,Nc+Nf] of the fine pass (24 bytes per
+ * merged sample: the only part that grows with B), then a sigma-only gradient query's workspace ("packed" "fold" "save" "masks" "spre") and
+ * "sigma" "points" [.,3] "grad" [.,3] of ONE chunk of samples.  A chunk is floor(131072 / N) whole rays of the pass (N = Nc or Nc + Nf);
+ * after a call, "points" and "grad" hold the last chunk of the last pass that ran (coarse first, then fine).  The main workspace
+ * (nerf_hip_ws_bytes, nerf_hip_ws_offset) is unchanged by this feature.  Sizes as nerf_hip_ws_bytes checks them.
+ *
+ * nerf_hip_forward_normals: the arguments of nerf_hip_forward_maps, then
+ *   passes     bit 0 = the coarse pass, bit 1 = the fine pass: 1, 2 or 3
+ *   normals    [B,2,3] f32 out, device: row 0 = N of the coarse pass, row 1 = N of the fine pass; a row that is not asked for is untouched
+ *   nws        side workspace of >= nerf_hip_normals_ws_bytes(B,Nc,Nf) bytes, 256-byte aligned
+ * It runs in every inference mode nerf_hip_forward_maps runs in; C_coarse, C_fine, maps, the status word and the main workspace are that
+ * call's, bit for bit (the same launches: the merge kernel also stores its sorted bundle and weights, to nws).  Behind them, per requested
+ * pass and chunk: k_sample_points, the two launches of the gradient query, k_normal_composite; the gradient query's weight image is packed
+ * once per call.  Enqueue-only on the caller's stream.  NERF_HIP_ERR_ARG before any device work: NERF_HIP_SAVE_FOR_BACKWARD, passes
+ * outside 1..3, a NULL maps, normals or nws, nws too small or not 256-byte aligned; and whatever nerf_hip_forward_maps refuses.
+ *
+ * nerf_hip_normal_composite: the stage entry, the k_normal_composite launch on its own.  w [B,N], g [B,N,3] (sigma gradients), device;
+ * out[b * out_stride + c] receives N_c of ray b (out_stride >= 3; nothing else is written).  1 <= N <= 2048.  B = 0 succeeds and launches
+ * nothing.
+ * ------------------------------------------------------------------------------------------- */
+int nerf_hip_normals_ws_bytes(int B, int Nc, int Nf, size_t* bytes);
+int nerf_hip_normals_ws_offset(int B, int Nc, int Nf, const char* name, size_t* offset);
+int nerf_hip_forward_normals(const float* const* weights24, const int64_t* row, const int64_t* col,
+                             const float* poses_bound, const float* K_inv9, const float* ray0_near_far,
+                             int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, float* maps,
+                             void* ws, size_t ws_bytes, int flags, void* stream,
+                             int passes, float* normals /* device [B][2][3] */, void* nws, size_t nws_bytes);
+int nerf_hip_normal_composite(const float* w, const float* g, int B, int N, float* out, int out_stride, void* stream);
 
 /*
  * Backward of nerf_hip_forward (autograd through nerf.py:286-323, called at nerf.py:473).

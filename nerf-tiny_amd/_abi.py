@@ -76,6 +76,11 @@ _PROTOS = {
                                                                 _p]),
     "nerf_hip_merge_composite_backward_distortion": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, _p, _p, _p,
                                                                _p]),
+    "nerf_hip_normals_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "nerf_hip_normals_ws_offset": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t)]),
+    "nerf_hip_forward_normals": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p, _p, _p, _p, C.c_size_t, C.c_int,
+                                           _p, C.c_int, _p, _p, C.c_size_t]),
+    "nerf_hip_normal_composite": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, C.c_int, _p]),
     "nerf_hip_query_ws_bytes": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "nerf_hip_query": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _p, C.c_size_t, _p]),
     "nerf_hip_density_grid": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
@@ -169,6 +174,27 @@ def ws_bytes(B: int, Nc: int, Nf: int, flags: int) -> int:
     n = C.c_size_t(0)
     check(lib().nerf_hip_ws_bytes(B, Nc, Nf, flags, C.byref(n)))
     return int(n.value)
+
+
+def normals_ws_bytes(B: int, Nc: int, Nf: int) -> int:
+    """Bytes of the side workspace of nerf_hip_forward_normals for these sizes."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_normals_ws_bytes(B, Nc, Nf, C.byref(n)))
+    return int(n.value)
+
+
+def normals_ws_view(nws, B, Nc, Nf, name, shape, dtype=None):
+    """A typed view of a named buffer of nerf_hip_forward_normals's side workspace (tests / debugging), as ws_view."""
+    import torch
+
+    off = C.c_size_t(0)
+    check(lib().nerf_hip_normals_ws_offset(B, Nc, Nf, name.encode(), C.byref(off)))
+    dtype = dtype or torch.float32
+    n = 1
+    for d in shape:
+        n *= d
+    nbytes = n * torch.empty((), dtype=dtype).element_size()
+    return nws[off.value: off.value + nbytes].view(dtype).view(*shape)
 
 
 def query_ws_bytes(with_rgb: bool) -> int:

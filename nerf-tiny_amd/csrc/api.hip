@@ -251,7 +251,9 @@ struct TrainLoss {
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
                  int flags, void* stream, TrainLoss* tl, float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr,
-                 float* dist = nullptr);  // dist: the [B][2] output of nerf_hip_forward_distortion_train (with maps, a training call), else null
+                 float* dist = nullptr,  // dist: the [B][2] output of nerf_hip_forward_distortion_train (with maps, a training call), else null
+                 float* side_bundle = nullptr, float* side_w = nullptr);  // nerf_hip_forward_normals (inference): the fine pass's sorted bundle /
+                                                                          // weights go to its side workspace (both set or both null)
 // nerf_hip_forward_quantiles and its stage entries: the checks they share, before any device work
 int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) {
   static_assert(MAX_QUANTILES == NERF_HIP_MAX_QUANTILES, "kernels.h and nerf_hip.h disagree");
@@ -329,7 +331,8 @@ namespace {
 
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth, float* dist) {
+                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth, float* dist, float* side_bundle,
+                 float* side_w) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
@@ -481,6 +484,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   ma.last = last_delta;
   ma.joint = corrected ? 1 : 0;
   if (save) { ma.bundle = at<float>(ws, L.bundle); ma.w = at<float>(ws, L.w_m); ma.perm = at<uint16_t>(ws, L.perm); }
+  else if (side_bundle) { ma.bundle = side_bundle; ma.w = side_w; }  // (the merge kernels store both wherever the pointers are set)
   ma.C_fine = C_fine;
   if (fuse_rays) {
     ff.mode = 2; ff.m = ma;
@@ -497,9 +501,140 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   return NERF_HIP_OK;
 }
 
+// Side workspace of nerf_hip_forward_normals (rule NM): the fine pass's sorted bundle and weights -- the only part that grows with B, 24 bytes
+// per merged sample --, then what a sigma-only gradient query keeps (api_geometry.hip: the packed image WITH the transposed segments, the
+// fold, the compact save / masks / spre of ONE chunk of QGRAD_CHUNK points) and that chunk's sigma, points and gradients.  A chunk is made of
+// whole rays.  Separate from the main workspace: layout() does not change by a byte.
+struct NormalsLayout {
+  size_t bundle, w_m, packed, fold, save, masks, spre, sigma, points, grad, total;
+};
+NormalsLayout normals_layout(int B, int Nc, int Nf) {
+  NormalsLayout L;
+  const size_t b = (size_t)B, N = (size_t)Nc + Nf;
+  const size_t rows = (size_t)QGRAD_CHUNK + DUMP_ROWS;
+  Carve c;
+  L.bundle = c.take(b * N * 5 * 4);
+  L.w_m = c.take(b * N * 4);
+  L.packed = c.take((size_t)PACKED_ALL_F4 * 16);
+  L.fold = c.take((size_t)FOLD_FLOATS * 4);
+  L.save = c.take(rows * QGRAD_GP * 4);
+  L.masks = c.take((size_t)8 * (QGRAD_CHUNK / 64) * 4 * 256 * 2);
+  L.spre = c.take(rows * 4);
+  L.sigma = c.take((size_t)QGRAD_CHUNK * 4);
+  L.points = c.take((size_t)QGRAD_CHUNK * 12);
+  L.grad = c.take((size_t)QGRAD_CHUNK * 12);
+  L.total = c.o;
+  return L;
+}
+
+// One pass of rule NM behind the two composites: t / w = the pass's depths (stride t_stride) and weights, N samples per ray; chunk by chunk of
+// whole rays through the side workspace (stream order: a chunk's points and gradients are consumed before the next chunk overwrites them)
+int normals_pass(const float* rayf, const float* t, int t_stride, const float* w, int B, int N, float* out, FieldArgs& fa, FieldBwdArgs& fb,
+                 float* points, float* grad, hipStream_t st) {
+  static_assert(QGRAD_CHUNK >= 2048, "a chunk holds at least one ray of Nc + Nf <= 2048 samples");
+  const int per = QGRAD_CHUNK / N;  // rays per chunk
+  QuerySrc q;
+  memset(&q, 0, sizeof(q));
+  q.points = points;
+  for (int r0 = 0; r0 < B; r0 += per) {
+    const int nr = (B - r0 < per) ? B - r0 : per;
+    const int n = nr * N;
+    HIP_TRY(launch_sample_points(rayf + (size_t)r0 * RAYF, t + (size_t)r0 * N * t_stride, t_stride, nr, N, points, st));
+    fa.M = n;
+    fa.Mtot = n;
+    HIP_TRY(launch_query_grad_fwd(fa, q, false, st));
+    fb.dt = grad;
+    fb.M = n;
+    fb.Mtot = n;
+    HIP_TRY(launch_query_grad_bwd(fb, false, st));
+    HIP_TRY(launch_normal_composite(w + (size_t)r0 * N, grad, nr, N, out + (size_t)r0 * 6, 6, st));
+  }
+  return NERF_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int nerf_hip_normals_ws_bytes(int B, int Nc, int Nf, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_sizes(B, Nc, Nf)) return rc;
+  *bytes = normals_layout(B, Nc, Nf).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_normals_ws_offset(int B, int Nc, int Nf, const char* name, size_t* offset) {
+  if (!name || !offset) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (int rc = check_sizes(B, Nc, Nf)) return rc;
+  const NormalsLayout L = normals_layout(B, Nc, Nf);
+  struct { const char* n; size_t o; } tab[] = {{"bundle", L.bundle}, {"w_m", L.w_m}, {"packed", L.packed}, {"fold", L.fold}, {"save", L.save},
+                                               {"masks", L.masks}, {"spre", L.spre}, {"sigma", L.sigma}, {"points", L.points}, {"grad", L.grad}};
+  for (auto& e : tab)
+    if (strcmp(e.n, name) == 0) {
+      *offset = e.o;
+      return NERF_HIP_OK;
+    }
+  return fail(NERF_HIP_ERR_ARG, "unknown normals workspace buffer %s", name);
+}
+
+int nerf_hip_forward_normals(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
+                             const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
+                             float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream, int passes, float* normals,
+                             void* nws, size_t nws_bytes) {
+  if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_normals is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
+  if (passes < 1 || passes > 3) return fail(NERF_HIP_ERR_ARG, "passes=%d: bit 0 = coarse, bit 1 = fine, at least one of them", passes);
+  if (!maps || !normals || !nws) return fail(NERF_HIP_ERR_ARG, "maps, normals or nws is null");
+  if (int rc = check_sizes(B, Nc, Nf)) return rc;
+  const NormalsLayout NL = normals_layout(B, Nc, Nf);
+  if (((uintptr_t)nws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "nws must be 256-byte aligned");
+  if (nws_bytes < NL.total) return fail(NERF_HIP_ERR_ARG, "nws %zu < %zu bytes (nerf_hip_normals_ws_bytes)", nws_bytes, NL.total);
+  if (int rc = forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags,
+                            stream, nullptr, maps, nullptr, nullptr, nullptr, at<float>(nws, NL.bundle), at<float>(nws, NL.w_m)))
+    return rc;
+  // the gradients are exact fp32 whatever the flags say: the gradient query's own image and launches, packed once per call
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Weights24 w = as_w24(weights24);
+  const WsLayout L = layout(B, Nc, Nf, flags);
+  HIP_TRY(launch_pack_weights(w, at<float>(nws, NL.fold), at<float4>(nws, NL.packed), NSEG, st));
+  FieldArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.wp = at<float4>(nws, NL.packed);
+  fa.w = w;
+  fa.save = at<float>(nws, NL.save);
+  fa.masks = at<uint16_t>(nws, NL.masks);
+  fa.spre = at<float>(nws, NL.spre);
+  fa.sigma = at<float>(nws, NL.sigma);
+  fa.tiles_tot = QGRAD_CHUNK / 64;
+  fa.MSrows = (long long)QGRAD_CHUNK + DUMP_ROWS;
+  FieldBwdArgs fb;
+  memset(&fb, 0, sizeof(fb));  // G = null, dsig = null: the sigma-only chain with an upstream of ones
+  fb.wp = fa.wp;
+  fb.w = w;
+  fb.save = fa.save;
+  fb.masks = fa.masks;
+  fb.spre = fa.spre;
+  fb.tiles_tot = fa.tiles_tot;
+  fb.MSrows = fa.MSrows;
+  const float* rayf = at<float>(ws, L.rayf);
+  float* points = at<float>(nws, NL.points);
+  float* grad = at<float>(nws, NL.grad);
+  if (passes & 1)
+    if (int rc = normals_pass(rayf, at<float>(ws, L.t_c), 1, at<float>(ws, L.w_c), B, Nc, normals, fa, fb, points, grad, st)) return rc;
+  if (passes & 2)
+    if (int rc = normals_pass(rayf, at<float>(nws, NL.bundle), 5, at<float>(nws, NL.w_m), B, Nc + Nf, normals + 3, fa, fb, points, grad, st)) return rc;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_normal_composite(const float* w, const float* g, int B, int N, float* out, int out_stride, void* stream) {
+  if (B < 0) return fail(NERF_HIP_ERR_ARG, "B=%d < 0", B);
+  if (N < 1 || N > 2048) return fail(NERF_HIP_ERR_ARG, "N=%d outside 1..2048", N);
+  if (out_stride < 3) return fail(NERF_HIP_ERR_ARG, "out_stride=%d < 3", out_stride);
+  if (B == 0) return NERF_HIP_OK;
+  if (!w || !g || !out) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_normal_composite(w, g, B, N, out, out_stride, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
 
 int nerf_hip_profile_begin(int max_launches) {
   if (g_prof.ev) return fail(NERF_HIP_ERR_ARG, "profile already active");

@@ -222,7 +222,12 @@ struct DistArgs {
 };
 hipError_t launch_coarse_dist(const CoarseArgs& a, float* maps, float* dist, hipStream_t st);
 hipError_t launch_merge_dist(const MergeArgs& a, float* maps, const DistArgs& da, hipStream_t st);  // a.perm set (a training call)
-hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st);
+// nerf_hip_forward_normals (ray_normals.hip; rule NM of include/nerf_hip.h): the world points of nrays whole rays of N samples each (rayf and
+// t start at the first of them; t_stride 1 = t_c, 5 = channel 0 of the sorted bundle), and the per-ray composite of the field normals of
+// g [B][N][3] with the weights w [B][N] -> out[b * out_stride + 0..2]
+hipError_t launch_sample_points(const float* rayf, const float* t, int t_stride, int nrays, int N, float* points, hipStream_t st);
+hipError_t launch_normal_composite(const float* w, const float* g, int B, int N, float* out, int out_stride, hipStream_t st);
+hipError_t launch_ray_loss(const float* Cc,const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st);
 
 }  // namespace nerf
 

@@ -108,6 +108,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--maps", action="store_true",
                     help="display() also renders every frame's expected depth and opacity: <RESULTS_PATH><time>_<iter>_maps.npz (depth, acc, "
                          "near, far) and <i>_depth.png / <i>_acc.png previews beside the frames (rank 0 writes)")
+    ap.add_argument("--normal-map", action="store_true",
+                    help="display() also renders every frame's composited field normals (the fine pass; implies --maps): <i>_normal.png "
+                         "beside the frames, 0.5 + 0.5 * the unit normal in the world frame, background mid grey (rank 0 writes)")
     ap.add_argument("--eval", action="store_true",
                     help="after display(): PSNR / SSIM / MSE of the display split (the \"test\" dataset) against its ground truth, printed and "
                          "written to <RESULTS_PATH><time>_<iter>_eval.json (rank 0)")
@@ -151,7 +154,10 @@ if __name__ == "__main__":
     # every rank runs this file; NeRFRunner reads RANK / WORLD_SIZE / LOCAL_RANK from the environment before its first GPU call
     run = P.NeRFRunner(**kw)
     run.trainer("train")
-    run.display(maps=args.maps)
+    if args.normal_map:
+        run.display(maps=True, normals=True)
+    else:
+        run.display(maps=args.maps)
     if args.eval:
         r = run.evaluate("disp", views=args.eval_views, save=True)
         if r is not None:

@@ -950,3 +950,40 @@ def merge_composite_backward_distortion(bundle, perm, dC_f, Nc, near, far, ddist
         None if dmaps is None else dmaps.contiguous().data_ptr(), B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(),
         drgb_c.data_ptr(), drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle), nf.data_ptr(), ddist.contiguous().data_ptr()))
     return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
+
+
+def normal_composite(w, g, out=None, out_stride=3, rays=None, sentinel=float("nan")):
+    """The k_normal_composite launch on its own (nerf_hip_normal_composite, rule NM of include/nerf_hip.h): weights w[B,N] and sigma
+    gradients g[B,N,3] on the device -> out[B, out_stride] whose columns 0..2 are N = sum_i w_i n_i per ray and whose other columns keep
+    `sentinel`.  rays: a call of the first `rays` rays only (default: all) -- the rows behind the call keep `sentinel` too."""
+    B, N = w.shape
+    rays = B if rays is None else int(rays)
+    dev = w.device
+    if out is None:
+        out = torch.full((B, int(out_stride)), sentinel, dtype=torch.float32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_normal_composite(w.contiguous().data_ptr(), g.contiguous().data_ptr(), rays, N, out.data_ptr(),
+                                                    int(out_stride), _stream(w)))
+    return out
+
+
+def forward_normals(params, row, col, poses_bound_f32, K_inv, Nc, Nf, flags=0, passes=2, ray0=None, last=1e-4, ws=None, nws=None,
+                    sentinel=float("nan")):
+    """One nerf_hip_forward_normals call: the maps call plus each ray's composited field normals (rule NM of include/nerf_hip.h).
+    passes: bit 0 = coarse, bit 1 = fine.  -> (C_coarse[B,3], C_fine[B,3], maps[B,4], normals[B,2,3], ws, nws): row 0 / 1 of normals = the
+    coarse / fine pass's N, a row not asked for keeps `sentinel`; ws / nws = the main and the side workspace the call ran on (uint8 device
+    buffers of >= _abi.ws_bytes(B, Nc, Nf, flags) / _abi.normals_ws_bytes(B, Nc, Nf) bytes, allocated here if None).  ray0: the (near, far)
+    of the batch's global ray 0 (two host floats) or None."""
+    B, dev = row.shape[0], row.device
+    if ws is None:
+        ws = torch.zeros(_abi.ws_bytes(B, Nc, Nf, flags), dtype=torch.uint8, device=dev)
+    if nws is None:
+        nws = torch.empty(_abi.normals_ws_bytes(B, Nc, Nf), dtype=torch.uint8, device=dev)
+    C_c = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    C_f = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    maps = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    nrm = torch.full((B, 2, 3), sentinel, dtype=torch.float32, device=dev)
+    _abi.check(_abi.lib().nerf_hip_forward_normals(_abi.ptr_array(params), row.data_ptr(), col.data_ptr(), poses_bound_f32.data_ptr(),
+                                                   _k9(K_inv), None if ray0 is None else _abi.f32_array(ray0), B, Nc, Nf, float(last),
+                                                   C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), int(flags),
+                                                   _stream(row), int(passes), nrm.data_ptr(), nws.data_ptr(), nws.numel()))
+    return C_c, C_f, maps, nrm, ws, nws

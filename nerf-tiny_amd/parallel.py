@@ -254,7 +254,7 @@ def batch_shard_bounds(n: int, batch: int, rank: int, world: int) -> tuple[int, 
 
 
 def render_rows_sharded(model, row, col, poses_bound, K_inv, rank: int, world: int, out: torch.Tensor | None = None,
-                        align_to_batches: bool = True, fuse_rays: int = 16384, maps: bool = False):
+                        align_to_batches: bool = True, fuse_rays: int = 16384, maps: bool = False, normals: bool = False):
     """Inference over a long list of rays (e.g. one frame): this rank renders a contiguous range [lo, hi) in batches of
     model.batch_ray.  No collective.  Returns (lo, hi, C_fine[hi-lo, 3]).
 
@@ -263,17 +263,23 @@ def render_rows_sharded(model, row, col, poses_bound, K_inv, rank: int, world: i
     rays of reference batches that agree in their ray 0's (near, far) and is handed that pair (`nerf.fuse_plan`; `fuse_rays` = the
     longest call, `model.batch_ray` = one call per batch as up to round 2); with `align_to_batches` (default) shards start
     on the batch grid.  The reference silently drops the tail batch (nerf.py:442); here it is rendered, with its own ray 0.
-    maps=True: returns (lo, hi, C_fine, maps[hi-lo, 4]) with NeRFModel.render's per-ray (D_c, A_c, D_f, A_f) (`out` gets C_fine only)."""
+    maps=True: returns (lo, hi, C_fine, maps[hi-lo, 4]) with NeRFModel.render's per-ray (D_c, A_c, D_f, A_f) (`out` gets C_fine only).
+    normals=True (with maps=True): returns (lo, hi, C_fine, maps, N_fine[hi-lo, 3]) with the fine row of NeRFModel.render(normals="fine")."""
+    if normals and not maps:
+        raise ValueError("normals needs maps=True: the normal maps come with the maps call")
     n, Bm = row.shape[0], model.batch_ray
     lo, hi = batch_shard_bounds(n, Bm, rank, world) if align_to_batches else shard_bounds(n, rank, world)
     # NeRFModel.render: the batches of this range that share their ray 0's (near, far) share kernel calls (same bits per ray)
     if hi > lo:
-        r = model.render(row, col, poses_bound, K_inv, lo, hi, fuse_rays=fuse_rays, maps=maps)
+        r = model.render(row, col, poses_bound, K_inv, lo, hi, fuse_rays=fuse_rays, maps=maps, normals="fine" if normals else False)
         C, M = r[1], (r[2] if maps else None)
+        Nf = r[-1][:, 1] if normals else None
     else:
-        C, M = torch.empty(0, 3), torch.empty(0, 4)
+        C, M, Nf = torch.empty(0, 3), torch.empty(0, 4), torch.empty(0, 3)
     if out is not None and hi > lo:
         out[lo:hi] = C
+    if normals:
+        return lo, hi, C, M, Nf
     return (lo, hi, C, M) if maps else (lo, hi, C)
 
 

@@ -738,17 +738,25 @@ class NeRFRunner:
         return r
 
     # nerf.py:503-530
-    def display(self, save=True, maps=False):
+    def display(self, save=True, maps=False, normals=False):
         """Renders every display frame (white where the reference's loop leaves a pixel out) and returns them, [pic, H, W, 3] numpy.
         maps=True: also the fine expected depth and accumulated opacity of every rendered pixel (NeRFModel.render(maps=True): D_f, A_f;
         NaN depth and 0 opacity where the frame stays white), returned as (frames, depth, acc) with depth / acc [pic, H, W] fp32; with save,
         rank 0 also writes ``<results_path><start_time>_<last_iter>_maps.npz`` (``depth``, ``acc``, and every frame's ``near`` / ``far``)
-        and ``<i>_depth.png`` (depth normalised by the frame's near / far) and ``<i>_acc.png`` previews beside the frames."""
+        and ``<i>_depth.png`` (depth normalised by the frame's near / far) and ``<i>_acc.png`` previews beside the frames.
+        normals=True (with maps=True): also the fine pass's composited field normal N_f of every rendered pixel
+        (NeRFModel.render(normals="fine"), rule NM of include/nerf_hip.h; world frame, not normalised, 0 where the frame stays white),
+        returned as (frames, depth, acc, normal) with normal [pic, H, W, 3] fp32; with save, rank 0 also writes ``<i>_normal.png`` beside
+        the frames: 0.5 + 0.5 * nerf.unit_normals(normal, acc), so the background is mid grey."""
+        if normals and not maps:
+            raise ValueError("normals needs maps=True: the normal maps come with the maps call")
         rays = self.disp_rays
         result = torch.full((rays.pic_num, self.height, self.width, 3), 1.0, device=self.device)
         if maps:
             depth = torch.full((rays.pic_num, self.height, self.width), float("nan"), device=self.device)
             acc = torch.zeros((rays.pic_num, self.height, self.width), device=self.device)
+        if normals:
+            nrm = torch.zeros((rays.pic_num, self.height, self.width, 3), device=self.device)
         self.model.eval()
         # the reference's loop (batches of batch_ray rays in pixel order, the tail < batch stays white) through NeRFModel.render: batches
         # whose ray 0 has the same near / far share kernel calls -- same bits per pixel, launches of up to 16,384 rays instead of 400
@@ -765,13 +773,17 @@ class NeRFRunner:
                     if self.distributed:
                         # cfg5: the chunk's reference batches dealt out over the ranks (shards on the batch grid, every call handed its
                         # batches' ray 0: same pixels for any world size), NO collective in the data path; the picture is assembled after
-                        r = par.render_rows_sharded(self.model, row, col, poses_bound, self.K_inv, self.rank, self.world, maps=maps)
+                        r = par.render_rows_sharded(self.model, row, col, poses_bound, self.K_inv, self.rank, self.world, maps=maps, normals=normals)
                         C_fine = par.gather_rows(r[2].to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray)
                         M = par.gather_rows(r[3].to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray) if maps else None
+                        Nf = par.gather_rows(r[4].to(self.device), row.shape[0], self.rank, self.world, self.group, batch=self.batch_ray) if normals else None
                     else:
-                        r = self.model.render(row, col, poses_bound, self.K_inv, maps=maps)
+                        r = self.model.render(row, col, poses_bound, self.K_inv, maps=maps, normals="fine" if normals else False)
                         C_fine, M = r[1], (r[2] if maps else None)
+                        Nf = r[-1][:, 1] if normals else None
                     result[pic, row, col] = C_fine
+                    if normals:
+                        nrm[pic, row, col] = Nf
                     if maps:
                         depth[pic, row, col] = M[:, 2]
                         acc[pic, row, col] = M[:, 3]
@@ -814,4 +826,17 @@ class NeRFRunner:
                     plt.imsave(save_dir + str(i) + "_acc.png", acc[i].clip(0, 1), cmap="gray", vmin=0.0, vmax=1.0)
             except Exception as e:  # pragma: no cover
                 print("display: could not write map previews:", e)
-        return result, depth, acc
+        if not normals:
+            return result, depth, acc
+        nrm = nrm.cpu().numpy()
+        if save and self.rank == 0:
+            import numpy as np
+
+            from .mesh import png_bytes
+            from .nerf import unit_normals
+
+            for i in range(rays.pic_num):
+                img = 0.5 + 0.5 * unit_normals(nrm[i], acc[i])
+                with open(save_dir + str(i) + "_normal.png", "wb") as f:
+                    f.write(png_bytes(np.rint(img.clip(0, 1) * 255.0).astype(np.uint8)))
+        return result, depth, acc, nrm
