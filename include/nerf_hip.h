@@ -67,7 +67,8 @@ extern "C" {
                                      nerf_hip_merge_composite_distortion, nerf_hip_coarse_composite_backward_distortion,
                                      nerf_hip_merge_composite_backward_distortion; nerf_hip_mesh_atlas_dims,
                                      nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample; nerf_hip_normals_ws_bytes,
-                                     nerf_hip_normals_ws_offset, nerf_hip_forward_normals, nerf_hip_normal_composite */
+                                     nerf_hip_normals_ws_offset, nerf_hip_forward_normals, nerf_hip_normal_composite;
+                                     the nerf_hip_volume_* calls (with NERF_HIP_VOLUME_MAX_STEPS) */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1260,6 +1261,138 @@ int nerf_hip_coarse_composite_backward_distortion(const float* t_c, const float*
 int nerf_hip_merge_composite_backward_distortion(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps,
                                                  int B, int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
                                                  float* drgb_f, float* dt_f, void* stream, const float* near_far, const float* ddist);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  SH radiance volumes: the field baked onto a dense lattice -- sigma and a few real
+ * spherical-harmonic colour coefficients per lattice point -- and a ray-marcher with trilinear lookups that renders from it without
+ * the network.  An approximate product of its own: nothing of nerf_hip_forward / nerf_hip_query changes.
+ *
+ * The lattice is nerf_hip_density_grid's: nx, ny, nz >= 2 points (at least one cell per axis), nx * ny * nz < 2^31, point (i, j, k) at
+ * lo + (i, j, k) * step, each coordinate one fp32 product and one fp32 sum, linear index (i * ny + j) * nz + k.  Arrays:
+ *    sigma [nx][ny][nz]            fp32
+ *    coef  [nx][ny][nz][ncoef][3]  fp32, ncoef = (degree + 1)^2 with degree in {0, 1, 2}: a corner is one contiguous 12 ncoef bytes
+ *    occ   [bx][by][bz]            uint8, b_a = ceil((n_a - 1) / B) blocks of B cells per axis
+ * sigma and coef are separate arrays: empty space touches only occ and sigma.  All arithmetic is fp32, every product, sum and division
+ * rounded on its own, evaluated as bracketed; every comparison is false on NaN.
+ *
+ * VA. ACTIVE POINTS.  A lattice point is ACTIVE iff some point of its 3 x 3 x 3 neighbourhood, clipped to the lattice, has sigma > 0:
+ *    exactly the points that are a corner of a cell with a positive corner, i.e. the points whose coefficients a lookup with
+ *    sigma_s > 0 can read.  nerf_hip_volume_active_count / _emit give their number and their linear indices ASCENDING, through a scan
+ *    -- no atomic places anything.  nerf_hip_volume_points writes the world point of each index of a list (any chunk of it) by the
+ *    lattice rule above; an index outside [0, nx ny nz) gives the point (NaN, NaN, NaN).
+ *
+ * VS. SH PROJECTION.  The basis is the 9 real spherical harmonics of degree <= 2 in the order (l, m) ascending, m = -l .. l, without
+ *    the Condon-Shortley sign: for d = (x, y, z)
+ *       Y_0 = C0             Y_1 = C1 y           Y_2 = C1 z                       Y_3 = C1 x          Y_4 = C2 (x y)
+ *       Y_5 = C2 (y z)       Y_6 = C3 ((3 (z z)) - 1)                              Y_7 = C2 (x z)      Y_8 = C4 ((x x) - (y y))
+ *    with C0 .. C4 = fp32(sqrt(1 / 4 pi)), fp32(sqrt(3 / 4 pi)), fp32(sqrt(15 / 4 pi)), fp32(sqrt(5 / 16 pi)), fp32(sqrt(15 / 16 pi))
+ *    = 0.282094806, 0.488602519, 1.09254849, 0.31539157, 0.546274245 (NERF_HIP_VOLUME_SH_C).  The quadrature is the 12 vertices of the
+ *    icosahedron, all weights w = 4 pi / 12: with phi = (1 + sqrt 5) / 2, vertex 4 c + 2 s1 + s2 (c = 0, 1, 2; s1, s2 = 0 for +, 1
+ *    for -) has component c equal to 0, component (c + 1) % 3 equal to +-1 (s1) and component (c + 2) % 3 equal to +-phi (s2), divided
+ *    by sqrt(1 + phi^2) in fp64 and rounded to fp32: NERF_HIP_VOLUME_DIRS below.  They form a spherical 5-design, so the products of
+ *    two basis functions are integrated exactly: sum_k w Y_i(d_k) Y_j(d_k) = delta_ij (1.5e-7 with these fp32 directions).
+ *    The bake: for k = 0 .. 11 IN ORDER, rgb_k = nerf_hip_query(the active points, dirs = d_k), and nerf_hip_volume_sh_accumulate(k)
+ *       coef[p][m][ch] = coef[p][m][ch] + b_km * rgb_k[p][ch]          m < ncoef
+ *    b_km = fp32(w Y_m(d_k)) with Y_m evaluated in fp64 with the unrounded constants at the fp32 direction widened; zero entries are
+ *    +0 (NERF_HIP_VOLUME_SH_B, which nerf_hip_volume_sh_table returns beside the directions).  The caller zeroes coef before k = 0;
+ *    inactive points keep 0.  The first (degree + 1)^2 coefficients do not depend on the degree: a lower-degree bake is the leading
+ *    slab of the degree-2 bake, bit for bit.  An index outside the lattice is skipped.
+ *
+ * VO. BLOCK OCCUPANCY.  Block b of edge B (an int >= 1) covers the cells [b B, min((b + 1) B, n - 1)) per axis; occ[b] = 1 iff some
+ *    lattice point touched by one of its cells -- the points b B .. min((b + 1) B, n - 1) per axis, both ends included -- has
+ *    sigma > 0, else 0.  B >= every n - 1 gives one block.
+ *
+ * VL. LOOKUP at the point x along the direction d.  Per axis a
+ *       g = (x - lo) / step          INSIDE iff 0 <= g and g <= n - 1 (on every axis; false on NaN, so a point that is not finite is outside)
+ *       i = min(max(floor(g), 0), n - 2)          f = g - i
+ *    An outside point has sigma_s = 0 and rgb = 0.  Otherwise, with v[di][dj][dk] the value at corner (i + di, j + dj, k + dk) and
+ *    lerp(a, b, f) = a + (f * (b - a)), the z axis is interpolated first, then y, then x:
+ *       c[di][dj] = lerp(v[di][dj][0], v[di][dj][1], fz),   c[di] = lerp(c[di][0], c[di][1], fy),   value = lerp(c[0], c[1], fx)
+ *    sigma_s is that value of sigma.  The colour: each corner's channel value is s = Y_0(d) coef[corner][0][ch], then
+ *    s = s + (Y_m(d) coef[corner][m][ch]) for m = 1 .. ncoef - 1, with Y_m(d) as in VS in fp32 and d AS GIVEN (not renormalised);
+ *    the eight values are interpolated like sigma and the result is clamped, rgb = fmin(fmax(value, 0), 1) (a NaN becomes 0).
+ *
+ * VR. THE MARCH.  Per ray (o, d), window [tmin, tmax] and step dt > 0.  A ray whose o, d, tmin or tmax is not finite MISSES.  Else
+ *    t_a = tmin, t_b = tmax and per axis, with the box [lo, hi], hi = lo + (n - 1) * step (the last lattice point):
+ *       d == 0:  the ray misses unless lo <= o and o <= hi; nothing else is computed (no 0 * inf)
+ *       else     t1 = (lo - o) / d, t2 = (hi - o) / d, t_a = fmax(t_a, fmin(t1, t2)), t_b = fmin(t_b, fmax(t1, t2))
+ *    (x, y, z in turn).  !(t_a < t_b) is a miss.  K = min(ceil((t_b - t_a) / dt), NERF_HIP_VOLUME_MAX_STEPS), compared in fp32
+ *    before it becomes an integer.  Sample k = 0 .. K - 1 sits at t_k = t_a + ((float(k) + 0.5) * dt), its point is o + (t_k * d) per
+ *    axis, and VL gives (sigma_s, rgb) there along d.  A sample CONTRIBUTES iff sigma_s > 0.  From T = 1, C = D = A = 0:
+ *       alpha = -expm1f(-(sigma_s * dt))        (the accurate library function)
+ *       w = T * alpha,   C_ch = C_ch + (w * rgb_ch),   D = D + (w * t_k),   A = A + w,   T = T - w
+ *    and after the update of a contributing sample the march ends when T < t_stop (t_stop in [0, 1); 0 never ends early).
+ *       rgb_ch = C_ch + ((1 - A) * background_ch),   maps = (D, A),   steps = (contributing samples, evaluated samples)  int32
+ *    d is the renderer's unit d_wrd, so D is on the depth scale of nerf_hip_forward_maps.  A miss gives the background, zero maps and
+ *    zero steps.
+ *    EMPTY BLOCKS.  The marcher may pass over samples that lie in a block with occ = 0 (csrc/volume.hip proves that none of them can
+ *    contribute): rgb, maps and steps[0] do not depend on B, bit for bit; only steps[1], the samples it looked at, does.
+ *
+ * One thread per item everywhere; the march is one ray per lane, no LDS, no atomics.  The data-dependent addresses are the eight
+ * corners and the block byte, each built from indices clamped into their arrays.  All calls are enqueue-only on the caller's stream
+ * and check every argument on the host first (NERF_HIP_ERR_ARG): a dimension < 2, nx * ny * nz >= 2^31, degree outside {0, 1, 2},
+ * block < 1, a lo that is not finite, a step that is not finite and > 0, dt not finite and > 0, t_stop outside [0, 1), a background
+ * that is not finite, k outside [0, 12), a negative count or one >= 2^31, a NULL pointer or one that is not aligned to its element.
+ * A count of 0 succeeds and launches nothing (its per-item pointers may then be NULL).  lo3 / step3 / background3 are HOST arrays.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_VOLUME_MAX_STEPS 65536 /* the cap on K: the march is bounded whatever the inputs; (k + 0.5) stays exact in fp32 */
+#define NERF_HIP_VOLUME_NDIRS 12
+#define NERF_HIP_VOLUME_SH_C {0.282094806f, 0.488602519f, 1.09254849f, 0.31539157f, 0.546274245f}
+#define NERF_HIP_VOLUME_DIRS {                                                                      \
+    0.0f, 0.525731087f, 0.850650787f,    0.0f, 0.525731087f, -0.850650787f,                         \
+    0.0f, -0.525731087f, 0.850650787f,   0.0f, -0.525731087f, -0.850650787f,                        \
+    0.850650787f, 0.0f, 0.525731087f,    -0.850650787f, 0.0f, 0.525731087f,                         \
+    0.850650787f, 0.0f, -0.525731087f,   -0.850650787f, 0.0f, -0.525731087f,                        \
+    0.525731087f, 0.850650787f, 0.0f,    0.525731087f, -0.850650787f, 0.0f,                         \
+    -0.525731087f, 0.850650787f, 0.0f,   -0.525731087f, -0.850650787f, 0.0f}
+#define NERF_HIP_VOLUME_SH_B {                                                                                                    \
+    0.295408964f, 0.268997341f, 0.435246825f, 0.0f, 0.0f, 0.511663318f, 0.386695325f, 0.0f, -0.15811266f,                          \
+    0.295408964f, 0.268997341f, -0.435246825f, 0.0f, 0.0f, -0.511663318f, 0.386695325f, 0.0f, -0.15811266f,                        \
+    0.295408964f, -0.268997341f, 0.435246825f, 0.0f, 0.0f, -0.511663318f, 0.386695325f, 0.0f, -0.15811266f,                        \
+    0.295408964f, -0.268997341f, -0.435246825f, 0.0f, 0.0f, 0.511663318f, 0.386695325f, 0.0f, -0.15811266f,                        \
+    0.295408964f, 0.0f, 0.268997341f, 0.435246825f, 0.0f, 0.0f, -0.0564181209f, 0.511663318f, 0.413944334f,                        \
+    0.295408964f, 0.0f, 0.268997341f, -0.435246825f, 0.0f, 0.0f, -0.0564181209f, -0.511663318f, 0.413944334f,                      \
+    0.295408964f, 0.0f, -0.268997341f, 0.435246825f, 0.0f, 0.0f, -0.0564181209f, -0.511663318f, 0.413944334f,                      \
+    0.295408964f, 0.0f, -0.268997341f, -0.435246825f, 0.0f, 0.0f, -0.0564181209f, 0.511663318f, 0.413944334f,                      \
+    0.295408964f, 0.435246825f, 0.0f, 0.268997341f, 0.511663318f, 0.0f, -0.330277264f, 0.0f, -0.255831659f,                        \
+    0.295408964f, -0.435246825f, 0.0f, 0.268997341f, -0.511663318f, 0.0f, -0.330277264f, 0.0f, -0.255831659f,                      \
+    0.295408964f, 0.435246825f, 0.0f, -0.268997341f, -0.511663318f, 0.0f, -0.330277264f, 0.0f, -0.255831659f,                      \
+    0.295408964f, -0.435246825f, 0.0f, -0.268997341f, 0.511663318f, 0.0f, -0.330277264f, 0.0f, -0.255831659f}
+
+/* dirs36 [12][3] and b108 [12][9]: the two tables above (HOST arrays; either may be NULL).  Host only. */
+int nerf_hip_volume_sh_table(float* dirs36, float* b108);
+
+/* Bytes of workspace (256-byte aligned) of nerf_hip_volume_active_count / _emit: 8 bytes per 2048 lattice points and one count. */
+int nerf_hip_volume_ws_bytes(int nx, int ny, int nz, size_t* bytes);
+
+/* VA: count[0] (int64, device, 8-byte aligned) = the active points of sigma. */
+int nerf_hip_volume_active_count(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, void* stream);
+
+/* VA: index[0 .. min(count, max_n)) = the active points' linear indices, ascending.  Needs no count call before it. */
+int nerf_hip_volume_active_emit(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int32_t* index, int64_t max_n,
+                                void* stream);
+
+/* VA: points[n][3] = the lattice points of index[0 .. n). */
+int nerf_hip_volume_points(const int32_t* index, int64_t n, int nx, int ny, int nz, const float* lo3, const float* step3, float* points,
+                           void* stream);
+
+/* VS: direction k's term added to the coefficients of the points index[0 .. n); rgb[n][3] is nerf_hip_query's at those points along
+ * d_k.  The indices of one call must be distinct (an active list's are): every point is updated by one thread. */
+int nerf_hip_volume_sh_accumulate(float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n, const float* rgb, int k,
+                                  void* stream);
+
+/* VO: occ[bx][by][bz] of sigma for blocks of edge `block`; every byte is written. */
+int nerf_hip_volume_blocks(const float* sigma, int nx, int ny, int nz, int block, uint8_t* occ, void* stream);
+
+/* VL: out_sigma[M], out_rgb[M][3] at points[M][3] along dirs[M][3]. */
+int nerf_hip_volume_sample(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const float* lo3, const float* step3,
+                           const float* points, const float* dirs, int64_t M, float* out_sigma, float* out_rgb, void* stream);
+
+/* VR: origins, dirs [N][3], tmin, tmax [N] (device) -> rgb[N][3], maps[N][2] fp32, steps[N][2] int32.  occ is VO's for `block`. */
+int nerf_hip_volume_render(const float* sigma, const float* coef, const uint8_t* occ, int nx, int ny, int nz, int degree, int block,
+                           const float* lo3, const float* step3, const float* origins, const float* dirs, const float* tmin,
+                           const float* tmax, int64_t N, float dt, float t_stop, const float* background3, float* rgb, float* maps,
+                           int32_t* steps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@ SIMPLIFY_TABLE_FULL = 1 << 0
 EDGES_TABLE_FULL = 1 << 0
 TSDF_CARVE = 1 << 0
 MAX_QUANTILES = 4  # NERF_HIP_MAX_QUANTILES: quantiles of one nerf_hip_forward_quantiles call (they travel in the kernels' arguments)
+VOLUME_MAX_STEPS = 65536  # NERF_HIP_VOLUME_MAX_STEPS: the cap on the samples of one ray of nerf_hip_volume_render
 TSDF_VIEWS_PER_LAUNCH = 32  # NERF_HIP_TSDF_VIEWS_PER_LAUNCH: views whose cameras travel in one launch's kernel arguments
 
 _p = C.c_void_p
@@ -137,6 +138,16 @@ _PROTOS = {
     "nerf_hip_mesh_atlas_dims": (C.c_int, [C.c_int64, C.c_int, _p]),
     "nerf_hip_mesh_atlas_texels": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p]),
     "nerf_hip_mesh_texture_sample": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, C.c_int64, _p, _p, _p, _p]),
+    "nerf_hip_volume_sh_table": (C.c_int, [_p, _p]),
+    "nerf_hip_volume_ws_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "nerf_hip_volume_active_count": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, C.c_size_t, _p, _p]),
+    "nerf_hip_volume_active_emit": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, C.c_size_t, _p, C.c_int64, _p]),
+    "nerf_hip_volume_points": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p]),
+    "nerf_hip_volume_sh_accumulate": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, C.c_int, _p]),
+    "nerf_hip_volume_blocks": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "nerf_hip_volume_sample": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int64, _p, _p, _p]),
+    "nerf_hip_volume_render": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, C.c_int64,
+                                         C.c_float, C.c_float, _p, _p, _p, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -276,6 +287,20 @@ def mesh_atlas_dims(F: int, n: int) -> tuple:
     out = (C.c_int * 5)()
     check(lib().nerf_hip_mesh_atlas_dims(int(F), int(n), out))
     return tuple(int(x) for x in out)
+
+
+def volume_ws_bytes(nx: int, ny: int, nz: int) -> int:
+    """Workspace bytes of nerf_hip_volume_active_count / _emit over an nx x ny x nz lattice."""
+    n = C.c_size_t(0)
+    check(lib().nerf_hip_volume_ws_bytes(int(nx), int(ny), int(nz), C.byref(n)))
+    return int(n.value)
+
+
+def volume_sh_table():
+    """Rule VS's tables (nerf_hip_volume_sh_table; host only) -> (dirs [12][3], b [12][9]) as nested tuples of floats that are exact fp32."""
+    d, b = (C.c_float * 36)(), (C.c_float * 108)()
+    check(lib().nerf_hip_volume_sh_table(d, b))
+    return (tuple(tuple(d[k * 3: k * 3 + 3]) for k in range(12)), tuple(tuple(b[k * 9: k * 9 + 9]) for k in range(12)))
 
 
 def points_nearest_ws_bytes(M: int, N: int, dims) -> int:

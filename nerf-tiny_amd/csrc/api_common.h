@@ -1,5 +1,5 @@
-// api_common.h -- what the two host translation units of the extern "C" surface share (api.hip: render, training, profiling;
-// api_geometry.hip: queries, grids, meshes, metrics): the error text, the workspace carve-up and the argument checks.
+// api_common.h -- what the host translation units of the extern "C" surface share (api.hip: render, training, profiling;
+// api_geometry.hip: queries, grids, meshes, metrics; api_volume.hip: SH radiance volumes): the error text, the workspace carve-up and the argument checks.
 #pragma once
 #include "../../include/nerf_hip.h"
 

@@ -1,0 +1,269 @@
+// api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL
+// and VR): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on the caller's stream.
+// No allocation, no host sync.
+#include <math.h>
+
+#include "api_common.h"
+
+using namespace nerf;
+
+namespace {
+
+static_assert(VOL_MAX_STEPS == NERF_HIP_VOLUME_MAX_STEPS, "the header states the kernel's cap on the steps of a ray");
+
+const float kDirs[NERF_HIP_VOLUME_NDIRS * 3] = NERF_HIP_VOLUME_DIRS;
+const float kShB[NERF_HIP_VOLUME_NDIRS * 9] = NERF_HIP_VOLUME_SH_B;
+
+struct VolLayout {
+  size_t tot, base, count, total;
+};
+VolLayout vol_layout(long long npts) {
+  VolLayout L;
+  Carve c;
+  const size_t nb = (size_t)cc_blocks(npts);
+  L.tot = c.take(nb * 4);
+  L.base = c.take(nb * 4);
+  L.count = c.take(8);
+  L.total = c.o;
+  return L;
+}
+
+// the lattice of a volume: at least one cell per axis, below 2^31 points
+int check_lattice(int nx, int ny, int nz) {
+  if (nx < 2 || ny < 2 || nz < 2) return fail(NERF_HIP_ERR_ARG, "volume %d x %d x %d: every dimension must be at least 2", nx, ny, nz);
+  return check_grid(nx, ny, nz);
+}
+
+int check_degree(int degree) {
+  if (degree < 0 || degree > 2) return fail(NERF_HIP_ERR_ARG, "degree=%d: 0, 1 or 2", degree);
+  return NERF_HIP_OK;
+}
+
+int check_count(const char* name, int64_t n) {
+  if (n < 0) return fail(NERF_HIP_ERR_ARG, "%s=%lld < 0", name, (long long)n);
+  if (n >= (1ll << 31)) return fail(NERF_HIP_ERR_ARG, "%s=%lld: a call takes fewer than 2^31 items", name, (long long)n);
+  return NERF_HIP_OK;
+}
+
+int check_lo_step(const float* lo3, const float* step3) {
+  if (!lo3 || !step3) return fail(NERF_HIP_ERR_ARG, "lo3 / step3 is null");
+  if (int rc = check_finite3(lo3, "lo", "the lattice's corner")) return rc;
+  for (int c = 0; c < 3; ++c)
+    if (!(step3[c] > 0.0f && isfinite(step3[c]))) return fail(NERF_HIP_ERR_ARG, "step[%d]=%g: the lattice's step must be finite and > 0", c, (double)step3[c]);
+  return NERF_HIP_OK;
+}
+
+VolLattice lattice(int nx, int ny, int nz, const float* lo3, const float* step3) {
+  VolLattice g;
+  g.nx = nx;
+  g.ny = ny;
+  g.nz = nz;
+  for (int c = 0; c < 3; ++c) {
+    g.lo[c] = lo3[c];
+    g.step[c] = step3[c];
+  }
+  return g;
+}
+
+// blocks per axis of edge B: ceil((n - 1) / B)
+int blocks_of(int n, int B) { return (int)(((long long)n - 1 + B - 1) / B); }
+
+int active(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, int32_t* index, int64_t max_n, bool emit,
+           void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  const VolLayout L = vol_layout((long long)nx * ny * nz);
+  if (int rc = check_ws(ws, ws_bytes, L.total)) return rc;
+  if (emit) {
+    if (int rc = check_cap("max_n", max_n)) return rc;
+    if (max_n > 0) {
+      if (int rc = check_out(index, "index", 4)) return rc;
+    }
+  } else {
+    if (int rc = check_out(count, "count", 8)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VolActiveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.tot = at<int>(ws, L.tot);
+  a.base = at<int>(ws, L.base);
+  a.count = emit ? at<long long>(ws, L.count) : reinterpret_cast<long long*>(count);
+  a.index = index;
+  a.max_n = max_n;
+  HIP_TRY(launch_volume_active(a, emit, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_hip_volume_sh_table(float* dirs36, float* b108) {
+  if (dirs36) memcpy(dirs36, kDirs, sizeof(kDirs));
+  if (b108) memcpy(b108, kShB, sizeof(kShB));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_ws_bytes(int nx, int ny, int nz, size_t* bytes) {
+  if (!bytes) return fail(NERF_HIP_ERR_ARG, "bytes is null");
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  *bytes = vol_layout((long long)nx * ny * nz).total;
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_active_count(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, void* stream) {
+  return active(sigma, nx, ny, nz, ws, ws_bytes, count, nullptr, 0, false, stream);
+}
+
+int nerf_hip_volume_active_emit(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int32_t* index, int64_t max_n,
+                                void* stream) {
+  return active(sigma, nx, ny, nz, ws, ws_bytes, nullptr, index, max_n, true, stream);
+}
+
+int nerf_hip_volume_points(const int32_t* index, int64_t n, int nx, int ny, int nz, const float* lo3, const float* step3, float* points,
+                           void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(index, "index", 4)) return rc;
+  if (int rc = check_out(points, "points", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolPointsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.index = index;
+  a.n = n;
+  a.g = lattice(nx, ny, nz, lo3, step3);
+  a.points = points;
+  HIP_TRY(launch_volume_points(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_sh_accumulate(float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n, const float* rgb, int k,
+                                  void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (k < 0 || k >= NERF_HIP_VOLUME_NDIRS) return fail(NERF_HIP_ERR_ARG, "k=%d: a quadrature direction, 0 .. %d", k, NERF_HIP_VOLUME_NDIRS - 1);
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(index, "index", 4)) return rc;
+  if (int rc = check_out(rgb, "rgb", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolShArgs a;
+  memset(&a, 0, sizeof(a));
+  a.coef = coef;
+  a.npts = (long long)nx * ny * nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.index = index;
+  a.n = n;
+  a.rgb = rgb;
+  for (int m = 0; m < 9; ++m) a.b[m] = kShB[k * 9 + m];
+  HIP_TRY(launch_volume_sh_accumulate(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_blocks(const float* sigma, int nx, int ny, int nz, int block, uint8_t* occ, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (int rc = check_device()) return rc;
+  VolBlocksArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.B = block;
+  a.bx = blocks_of(nx, block);
+  a.by = blocks_of(ny, block);
+  a.bz = blocks_of(nz, block);
+  a.occ = occ;
+  HIP_TRY(launch_volume_blocks(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_sample(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const float* lo3, const float* step3,
+                           const float* points, const float* dirs, int64_t M, float* out_sigma, float* out_rgb, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("M", M)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (M == 0) return NERF_HIP_OK;
+  if (int rc = check_out(points, "points", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(out_sigma, "out_sigma", 4)) return rc;
+  if (int rc = check_out(out_rgb, "out_rgb", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.g = lattice(nx, ny, nz, lo3, step3);
+  a.points = points;
+  a.dirs = dirs;
+  a.M = M;
+  a.out_sigma = out_sigma;
+  a.out_rgb = out_rgb;
+  HIP_TRY(launch_volume_sample(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_render(const float* sigma, const float* coef, const uint8_t* occ, int nx, int ny, int nz, int degree, int block,
+                           const float* lo3, const float* step3, const float* origins, const float* dirs, const float* tmin,
+                           const float* tmax, int64_t N, float dt, float t_stop, const float* background3, float* rgb, float* maps,
+                           int32_t* steps, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_count("N", N)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (!(dt > 0.0f && isfinite(dt))) return fail(NERF_HIP_ERR_ARG, "dt=%g: the step along the ray must be finite and > 0", (double)dt);
+  if (!(t_stop >= 0.0f && t_stop < 1.0f)) return fail(NERF_HIP_ERR_ARG, "t_stop=%g: the transmittance to stop at lies in [0, 1)", (double)t_stop);
+  if (!background3) return fail(NERF_HIP_ERR_ARG, "background3 is null");
+  if (int rc = check_finite3(background3, "background", "the background colour")) return rc;
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (N == 0) return NERF_HIP_OK;
+  if (int rc = check_out(origins, "origins", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(tmin, "tmin", 4)) return rc;
+  if (int rc = check_out(tmax, "tmax", 4)) return rc;
+  if (int rc = check_out(rgb, "rgb", 4)) return rc;
+  if (int rc = check_out(maps, "maps", 4)) return rc;
+  if (int rc = check_out(steps, "steps", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolRenderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.occ = occ;
+  a.g = lattice(nx, ny, nz, lo3, step3);
+  a.B = block;
+  a.bx = blocks_of(nx, block);
+  a.by = blocks_of(ny, block);
+  a.bz = blocks_of(nz, block);
+  a.origins = origins;
+  a.dirs = dirs;
+  a.tmin = tmin;
+  a.tmax = tmax;
+  a.N = N;
+  a.dt = dt;
+  a.t_stop = t_stop;
+  for (int c = 0; c < 3; ++c) a.bg[c] = background3[c];
+  a.rgb = rgb;
+  a.maps = maps;
+  a.steps = steps;
+  HIP_TRY(launch_volume_render(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+}  // extern "C"

@@ -731,6 +731,78 @@ struct TsdfSampleArgs {
 
 hipError_t launch_tsdf_sample_color(const TsdfSampleArgs& a, hipStream_t st);
 
+// ---- SH radiance volumes (volume.hip; the nerf_hip_volume_* calls; rules VA, VS, VO, VL and VR of
+// include/nerf_hip.h).  The lattice: nx, ny, nz >= 2, npts = nx * ny * nz < 2^31 ----
+constexpr int VOL_WG = 256;                    // the one-thread-per-item kernels
+constexpr int VOL_MARCH_WG = 64;               // k_volume_march: one wave per workgroup, so a workgroup retires with its slowest ray
+constexpr int VOL_MAX_STEPS = 65536;           // NERF_HIP_VOLUME_MAX_STEPS
+
+struct VolLattice {
+  int nx, ny, nz;
+  float lo[3], step[3];
+};
+
+struct VolActiveArgs {
+  const float* sigma;      // [nx][ny][nz]
+  int nx, ny, nz;
+  int *tot, *base;         // [cc_blocks(npts)] (workspace)
+  long long* count;        // [1]: the caller's count, or the workspace's throw-away one (emit)
+  int* index;              // [max_n] (emit)
+  long long max_n;
+};
+
+struct VolPointsArgs {
+  const int* index;        // [n]
+  long long n;
+  VolLattice g;
+  float* points;           // [n][3]
+};
+
+struct VolShArgs {
+  float* coef;             // [npts][ncoef][3]
+  long long npts;
+  int ncoef;
+  const int* index;        // [n]
+  long long n;
+  const float* rgb;        // [n][3]
+  float b[9];              // b_km of this call's direction
+};
+
+struct VolBlocksArgs {
+  const float* sigma;
+  int nx, ny, nz;
+  int B;
+  int bx, by, bz;
+  unsigned char* occ;      // [bx][by][bz], zeroed by the launch sequence
+};
+
+struct VolSampleArgs {
+  const float *sigma, *coef;
+  VolLattice g;
+  const float *points, *dirs;  // [M][3]
+  long long M;
+  float *out_sigma, *out_rgb;  // [M], [M][3]
+};
+
+struct VolRenderArgs {
+  const float *sigma, *coef;
+  const unsigned char* occ;
+  VolLattice g;
+  int B, bx, by, bz;
+  const float *origins, *dirs, *tmin, *tmax;  // [N][3], [N][3], [N], [N]
+  long long N;
+  float dt, t_stop, bg[3];
+  float *rgb, *maps;       // [N][3], [N][2]
+  int* steps;              // [N][2]
+};
+
+hipError_t launch_volume_active(const VolActiveArgs& a, bool emit, hipStream_t st);
+hipError_t launch_volume_points(const VolPointsArgs& a, hipStream_t st);
+hipError_t launch_volume_sh_accumulate(const VolShArgs& a, hipStream_t st);
+hipError_t launch_volume_blocks(const VolBlocksArgs& a, hipStream_t st);
+hipError_t launch_volume_sample(const VolSampleArgs& a, int ncoef, hipStream_t st);
+hipError_t launch_volume_render(const VolRenderArgs& a, int ncoef, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

@@ -40,7 +40,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after display(): write sigma on a RES^3 lattice over --grid-bbox to <RESULTS_PATH><time>_<iter>_sigma<RES>.npz "
                          "(rank 0 only).  With CONTINUE = True and --total-iter at the checkpoint's iteration this exports without training")
     ap.add_argument("--grid-bbox", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
-                    help="box of --density-grid and --mesh: its lowest and highest lattice corner (default -1.5 .. 1.5 on every axis)")
+                    help="box of --density-grid, --mesh and --volume: its lowest and highest lattice corner (default -1.5 .. 1.5 on every axis)")
     ap.add_argument("--mesh", type=int, default=None, metavar="RES",
                     help="after display(): extract the isosurface sigma == --mesh-level on a RES^3 lattice over --grid-bbox (marching cubes on "
                          "the device, vertex colours) to <RESULTS_PATH><time>_<iter>_mesh<RES>.ply (rank 0 only)")
@@ -100,6 +100,17 @@ def build_parser() -> argparse.ArgumentParser:
                     help="surface samples per mesh of --mesh-compare (default 200000)")
     ap.add_argument("--mesh-compare-tau", type=float, nargs="+", default=(), metavar="T",
                     help="distance thresholds of --mesh-compare's precision / recall / F-score (up to 8; default: none)")
+    ap.add_argument("--volume", type=int, default=None, metavar="RES",
+                    help="after display(): bake the field into an SH radiance volume on a RES^3 lattice over --grid-bbox (sigma plus "
+                         "spherical-harmonic colour coefficients per lattice point; renders without the network: volume.py) and write it "
+                         "to <RESULTS_PATH><time>_<iter>_volume<RES>.npz")
+    ap.add_argument("--volume-degree", type=int, default=2, choices=[0, 1, 2],
+                    help="spherical-harmonic degree of --volume: 1, 4 or 9 colour coefficients per channel (default 2)")
+    ap.add_argument("--volume-sigma-min", type=float, default=0.0, metavar="S",
+                    help="--volume sets densities below S to 0 before the bake (default 0: the field's fog is baked too)")
+    ap.add_argument("--volume-preview", nargs="?", const="test", default=None, choices=["train", "val", "test"], metavar="SPLIT",
+                    help="--volume renders SPLIT's views (train, val or test; default test) from the volume to <i>_volume.png beside the "
+                         "frames and prints their PSNR / SSIM against the model's own render of the same views")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--dist-weight", type=float, default=None, metavar="LAMBDA",
@@ -165,6 +176,9 @@ if __name__ == "__main__":
                   f"{r['seconds']:.2f} s]")
     if args.density_grid is not None:
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
+    if args.volume is not None:
+        run.bake_volume(args.volume, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], degree=args.volume_degree, sigma_min=args.volume_sigma_min,
+                        save=True, preview=args.volume_preview)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

@@ -710,6 +710,50 @@ class NeRFModel(nn.Module):
         return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
 
     @torch.no_grad()
+    def bake_volume(self, lo, hi, res, degree=2, sigma_min=0.0, block=8, points_per_call=1 << 22):
+        """The field baked into an SH radiance volume (volume.Volume; rules VA, VS and VO of include/nerf_hip.h) over the lattice of
+        density_grid(lo, hi, res), every n >= 2: sigma is density_grid's, with values below ``sigma_min`` set to 0; the ACTIVE points --
+        those a lookup with a positive sigma can read -- get the (degree + 1)^2 real spherical-harmonic coefficients of their colour,
+        projected through the 12 directions of the icosahedron: per chunk of at most ``points_per_call`` active points and per
+        direction, points -> query -> accumulate; every other point keeps 0.  ``block``: cells per edge of the marcher's occupancy
+        blocks.  Always exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say, and bit-identical for every ``points_per_call``; a
+        lower-degree bake is the leading slab of the degree-2 bake.  sigma_min = 0 keeps everything the field calls dense, its fog
+        included.  Dense storage: 4 + 12 (degree + 1)^2 bytes per lattice point."""
+        import numpy as np
+
+        from . import ops, volume
+
+        ps = self._device_params()
+        dev = ps[0].device
+        shape = grid_shape(res)
+        if min(shape) < 2:
+            raise ValueError(f"res {res!r}: a volume has at least 2 points per axis")
+        if degree not in (0, 1, 2):
+            raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+        if int(points_per_call) != points_per_call or int(points_per_call) < 1:
+            raise ValueError(f"points_per_call={points_per_call!r}: an int >= 1")
+        lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
+        hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
+        step = grid_step(lo32, hi32, shape)
+        sigma = self.density_grid(lo32, hi32, shape)
+        if float(sigma_min) != 0.0:
+            sigma = torch.where(sigma >= float(sigma_min), sigma, torch.zeros_like(sigma))
+        index = ops.volume_active(sigma)
+        ncoef = (int(degree) + 1) ** 2
+        coef = torch.zeros(*shape, ncoef, 3, device=dev)
+        dirs = torch.from_numpy(volume.sh_dirs()).to(dev)
+        ws = self._query_workspace(True, dev)
+        per = int(points_per_call)
+        for p0 in range(0, int(index.shape[0]), per):
+            idx = index[p0:p0 + per]
+            pts = ops.volume_points(idx, shape, lo32.tolist(), step.tolist())
+            for k in range(dirs.shape[0]):
+                rgb, _ = ops.query(ps, pts, dirs[k].expand(pts.shape[0], 3).contiguous(), ws=ws)
+                ops.volume_sh_accumulate(coef, idx, rgb, k)
+        occ = ops.volume_blocks(sigma, block)
+        return volume.Volume(sigma, coef, occ, lo32, step, min(int(block), volume.ONE_BLOCK), int(degree))
+
+    @torch.no_grad()
     def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None,
                      smooth=None, visible=None, texture=None):
         """A triangle mesh of the isosurface sigma == level over the box [lo, hi]: density_grid(lo, hi, res) -> mesh.marching_cubes (the

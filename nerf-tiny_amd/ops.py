@@ -987,3 +987,144 @@ def forward_normals(params, row, col, poses_bound_f32, K_inv, Nc, Nf, flags=0, p
                                                    C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), int(flags),
                                                    _stream(row), int(passes), nrm.data_ptr(), nws.data_ptr(), nws.numel()))
     return C_c, C_f, maps, nrm, ws, nws
+
+
+def _vol_f32(t, what, shape=None):
+    if t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous fp32 device tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} {tuple(t.shape)}: {tuple(shape)}")
+    return t
+
+
+def _vol_index(index, dev):
+    index = index.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    return index, int(index.shape[0])
+
+
+def volume_active(sigma, ws=None):
+    """The ACTIVE lattice points of sigma[nx, ny, nz] (rule VA of include/nerf_hip.h: a positive sigma in the clipped 3 x 3 x 3
+    neighbourhood) -> their linear indices, int32, ascending (nerf_hip_volume_active_count, one 8-byte read of the device count -- this
+    synchronises with the stream --, then nerf_hip_volume_active_emit)."""
+    sigma = _vol_f32(sigma, "sigma")
+    if sigma.dim() != 3:
+        raise ValueError(f"sigma {tuple(sigma.shape)}: [nx, ny, nz]")
+    nx, ny, nz = (int(n) for n in sigma.shape)
+    dev = sigma.device
+    if ws is None:
+        ws = torch.empty(_abi.volume_ws_bytes(nx, ny, nz), dtype=torch.uint8, device=dev)
+    L, st = _abi.lib(), _stream(sigma)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    _abi.check(L.nerf_hip_volume_active_count(sigma.data_ptr(), nx, ny, nz, ws.data_ptr(), ws.numel(), count.data_ptr(), st))
+    n = int(count.cpu())
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    _abi.check(L.nerf_hip_volume_active_emit(sigma.data_ptr(), nx, ny, nz, ws.data_ptr(), ws.numel(), index.data_ptr() if n else None, n, st))
+    return index
+
+
+def volume_points(index, shape, lo, step):
+    """The lattice points lo + (i, j, k) * step of the linear indices index[n] (int32, device) of a lattice of ``shape``
+    (nerf_hip_volume_points) -> points[n, 3] fp32.  Enqueue only."""
+    if index.device.type != "cuda":
+        raise ValueError("index: a device tensor")
+    index, n = _vol_index(index, index.device)
+    nx, ny, nz = (int(x) for x in shape)
+    points = torch.empty(n, 3, device=index.device)
+    _abi.check(_abi.lib().nerf_hip_volume_points(index.data_ptr() if n else None, n, nx, ny, nz, _abi.f32_array(lo), _abi.f32_array(step),
+                                                 points.data_ptr() if n else None, _stream(index)))
+    return points
+
+
+def volume_sh_accumulate(coef, index, rgb, k):
+    """Quadrature direction k's term of rule VS added IN PLACE to the coefficients coef[nx, ny, nz, ncoef, 3] of the points index[n]:
+    rgb[n, 3] is query()'s colour at those points along direction k (nerf_hip_volume_sh_accumulate).  Enqueue only."""
+    coef = _vol_f32(coef, "coef")
+    if coef.dim() != 5 or coef.shape[4] != 3 or int(coef.shape[3]) not in (1, 4, 9):
+        raise ValueError(f"coef {tuple(coef.shape)}: [nx, ny, nz, (degree + 1)^2, 3]")
+    index, n = _vol_index(index, coef.device)
+    rgb = _vol_f32(rgb.to(coef.device, torch.float32).contiguous(), "rgb", (n, 3))
+    nx, ny, nz, nc = (int(x) for x in coef.shape[:4])
+    _abi.check(_abi.lib().nerf_hip_volume_sh_accumulate(coef.data_ptr(), nx, ny, nz, {1: 0, 4: 1, 9: 2}[nc], index.data_ptr() if n else None, n,
+                                                        rgb.data_ptr() if n else None, int(k), _stream(coef)))
+    return coef
+
+
+def volume_block_dims(shape, block):
+    """Blocks per axis of rule VO: ceil((n - 1) / block)."""
+    return tuple((int(n) - 1 + int(block) - 1) // int(block) for n in shape)
+
+
+def volume_blocks(sigma, block):
+    """Rule VO's block occupancy of sigma[nx, ny, nz] for blocks of ``block`` cells per axis (nerf_hip_volume_blocks) ->
+    occ[bx, by, bz] uint8.  Enqueue only."""
+    sigma = _vol_f32(sigma, "sigma")
+    if sigma.dim() != 3:
+        raise ValueError(f"sigma {tuple(sigma.shape)}: [nx, ny, nz]")
+    if int(block) != block or int(block) < 1:
+        raise ValueError(f"block={block!r}: an int >= 1")
+    block = min(int(block), 2**31 - 1)
+    nx, ny, nz = (int(n) for n in sigma.shape)
+    occ = torch.empty(volume_block_dims((max(nx, 2), max(ny, 2), max(nz, 2)), block), dtype=torch.uint8, device=sigma.device)
+    _abi.check(_abi.lib().nerf_hip_volume_blocks(sigma.data_ptr(), nx, ny, nz, block, occ.data_ptr(), _stream(sigma)))
+    return occ
+
+
+def _vol_arrays(sigma, coef):
+    sigma = _vol_f32(sigma, "sigma")
+    if sigma.dim() != 3:
+        raise ValueError(f"sigma {tuple(sigma.shape)}: [nx, ny, nz]")
+    coef = _vol_f32(coef, "coef")
+    if coef.dim() != 5 or tuple(coef.shape[:3]) != tuple(sigma.shape) or coef.shape[4] != 3 or int(coef.shape[3]) not in (1, 4, 9):
+        raise ValueError(f"coef {tuple(coef.shape)}: sigma's shape {tuple(sigma.shape)}, then [(degree + 1)^2, 3]")
+    if coef.device != sigma.device:
+        raise ValueError("sigma and coef live on different devices")
+    return sigma, coef, tuple(int(n) for n in sigma.shape), {1: 0, 4: 1, 9: 2}[int(coef.shape[3])]
+
+
+def volume_sample(sigma, coef, lo, step, points, dirs):
+    """Rule VL: the volume (sigma[nx, ny, nz], coef[nx, ny, nz, ncoef, 3]) on the lattice lo + (i, j, k) * step looked up at points[M, 3]
+    along dirs[M, 3] (nerf_hip_volume_sample) -> (sigma[M], rgb[M, 3]) fp32; a point outside the lattice gives zeros.  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    dev = sigma.device
+    points = points.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    if dirs.shape != points.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and points {tuple(points.shape)} differ")
+    M = int(points.shape[0])
+    out_s = torch.empty(M, device=dev)
+    out_c = torch.empty(M, 3, device=dev)
+    ptr = lambda t: t.data_ptr() if M else None
+    _abi.check(_abi.lib().nerf_hip_volume_sample(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, _abi.f32_array(lo), _abi.f32_array(step),
+                                                 ptr(points), ptr(dirs), M, ptr(out_s), ptr(out_c), _stream(sigma)))
+    return out_s, out_c
+
+
+def volume_render(sigma, coef, occ, block, lo, step, origins, dirs, tmin, tmax, dt, t_stop=0.0, background=(0.0, 0.0, 0.0)):
+    """Rule VR: the rays (origins[N, 3], dirs[N, 3], windows tmin[N] .. tmax[N]) marched through the volume in steps of dt
+    (nerf_hip_volume_render); occ is volume_blocks(sigma, block) -> (rgb[N, 3], maps[N, 2] = (D, A) fp32, steps[N, 2] int32 =
+    (contributing, evaluated)).  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    dev = sigma.device
+    block = min(int(block), 2**31 - 1)
+    if occ.device != dev or occ.dtype != torch.uint8 or not occ.is_contiguous() or (
+            block >= 1 and tuple(occ.shape) != volume_block_dims((nx, ny, nz), block)):
+        raise ValueError(f"occ {tuple(occ.shape)} {occ.dtype}: the contiguous uint8 block occupancy of sigma for block={block}")
+    origins = origins.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    N = int(origins.shape[0])
+    if dirs.shape != origins.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and origins {tuple(origins.shape)} differ")
+    win = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev).expand(N).contiguous() if torch.as_tensor(t).dim() == 0 else \
+        torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous()
+    tmin, tmax = win(tmin), win(tmax)
+    if tmin.shape[0] != N or tmax.shape[0] != N:
+        raise ValueError(f"tmin / tmax: a scalar or one entry per ray ({N})")
+    rgb = torch.empty(N, 3, device=dev)
+    maps = torch.empty(N, 2, device=dev)
+    steps = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if N else None
+    _abi.check(_abi.lib().nerf_hip_volume_render(sigma.data_ptr(), coef.data_ptr(), occ.data_ptr(), nx, ny, nz, degree, block,
+                                                 _abi.f32_array(lo), _abi.f32_array(step), ptr(origins), ptr(dirs), ptr(tmin), ptr(tmax), N,
+                                                 float(dt), float(t_stop), _abi.f32_array(background), ptr(rgb), ptr(maps), ptr(steps),
+                                                 _stream(sigma)))
+    return rgb, maps, steps

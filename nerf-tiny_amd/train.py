@@ -580,6 +580,65 @@ class NeRFRunner:
             np.savez(path, sigma=sigma, lo=lo32, hi=hi32, step=grid_step(lo32, hi32, shape), iter=np.int64(self.last_iter))
         return sigma
 
+    def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None):
+        """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
+        (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
+        ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
+        split is rendered FROM THE VOLUME (volume.render_views: no network) and, with save, written to ``<i>_volume.png`` beside the
+        display frames; the frames are scored against NeRFModel.render of the same views (metrics.image_metrics) and one ``[VOLUME]``
+        line prints the mean PSNR / SSIM.  Under a launcher only rank 0 bakes, renders and writes, without any collective (the comparison
+        frames are rendered whole on rank 0, not through render_view's sharded path); the other ranks return None at once."""
+        import numpy as np
+
+        from . import volume
+        from .mesh import png_bytes
+        from .metrics import image_metrics
+        from .nerf import grid_shape
+
+        if preview is not None and preview not in ("train", "val", "test"):
+            raise ValueError(f"preview={preview!r}: None, 'train', 'val' or 'test'")
+        if self.rank != 0:
+            return None
+        shape = grid_shape(res)
+        self.model.eval()
+        t0 = time.perf_counter()
+        vol = self.model.bake_volume(np.asarray(lo, np.float32), np.asarray(hi, np.float32), shape, degree=degree, sigma_min=sigma_min,
+                                     block=block)
+        torch.cuda.synchronize(self.device)
+        active = int((vol.coef[..., 0, :] != 0).any(dim=-1).sum())
+        print(f"[VOLUME] {self.last_iter} {'x'.join(str(n) for n in shape)} degree {degree}: {active} / {vol.sigma.numel()} lattice points "
+              f"hold colour, {int(vol.occ.sum())} / {vol.occ.numel()} blocks of {vol.block} occupied, "
+              f"{(vol.sigma.numel() * 4 + vol.coef.numel() * 4) / 2**20:.1f} MiB, {time.perf_counter() - t0:.2f} s")
+        if save:
+            tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + ".npz"
+            if os.path.dirname(path):
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+            volume.save(path, vol)
+        if preview is not None:
+            rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[preview]
+            H, W = rays.height, rays.width
+            n = H * W
+            psnr, ssim = [], []
+            for i in range(rays.pic_num):
+                frame = volume.render_views(vol, rays.poses[i:i + 1], self.K_inv, H, W)[0][0]
+                # the model's own frame on THIS rank alone (no collective: the other ranks have returned), as the mesh paths render
+                row, col, _, poses_bound, _ = rays.gather(torch.arange(i * n, (i + 1) * n, device=self.device))
+                with torch.no_grad(), self._evaluation() as mdl:
+                    exact = mdl.render(row, col, poses_bound, self.K_inv)[1].reshape(H, W, 3)
+                m = image_metrics(frame[None], exact[None])
+                psnr.append(float(m["psnr"][0]))
+                ssim.append(float(m["ssim"][0]))
+                if save:
+                    save_dir = self.results_path + self.start_time + "/"
+                    os.makedirs(save_dir, exist_ok=True)
+                    with open(save_dir + str(i) + "_volume.png", "wb") as f:
+                        f.write(png_bytes(np.rint(frame.clamp(0, 1).cpu().numpy() * 255.0).astype(np.uint8)))
+            print(f"[VOLUME] {self.last_iter} {preview} preview vs model.render [PSNR] {np.mean(psnr):.3f} dB [SSIM] {np.mean(ssim):.4f} "
+                  f"[{rays.pic_num} views]")
+            self.last_volume_preview = {"psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim)), "views": rays.pic_num}
+        return vol
+
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,
                      keep_largest=None, simplify=None, smooth=None, compare=None, compare_samples=200_000, compare_tau=(), visible_from=None,
                      tsdf_from=None, tsdf_trunc=None, tsdf_every=1, tsdf_color=False, tsdf_unseen="solid", tsdf_depth_stat="mean",
