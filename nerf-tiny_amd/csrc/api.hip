@@ -246,19 +246,94 @@ struct TrainLoss {
   float *dC_c, *dC_f, *terms, *loss;
   bool fused;
 };
-// maps: the [B][4] output of nerf_hip_forward_maps (inference) / nerf_hip_forward_maps_train (training; its caller has checked the flags),
-// else null.  A maps call always takes the separate k_coarse / k_merge launches (never the pair kernel, never the FwdFuse epilogues)
+// ---- the argument structs of the four per-ray stages: the fields every call fills are written here once.  The stage entries fill them from
+// the caller's pointers (with bounds_given), forward_impl / backward_impl from the workspace layout (with bounds_from_ws) ----
+CoarseArgs coarse_args(const float* t_c, const float* sigma_c, const float* rgb_c, int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f,
+                       uint32_t* status) {
+  CoarseArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c;
+  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
+  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
+  return ca;
+}
+CoarseBwdArgs coarse_bwd_args(const float* t_c, const float* sigma_c, const float* rgb_c, int B, int Nc, int Nf, const float* dC_coarse,
+                              const float* dt_f, float* dsig_c, float* drgb_c) {
+  CoarseBwdArgs cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c;
+  cb.B = B; cb.Nc = Nc; cb.Nf = Nf;
+  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
+  return cb;
+}
+// where a coarse stage, forward or backward (CoarseArgs / CoarseBwdArgs: the same fields), takes each ray's near / far and the spacing of ray
+// 0 (quirk Q6) from: a stage entry gives near_far [B][2] and the spacing itself, ...
+template <class A>
+void bounds_given(A& a, const float* near_far, float delta0) {
+  a.near_far = near_far;
+  a.delta0_mode = 1; a.delta0 = delta0;
+}
+// ... a whole call reads the ray records of its workspace, ray 0's unless the caller names the batch's global ray 0
+template <class A>
+void bounds_from_ws(A& a, void* ws, const WsLayout& L, const float* ray0_near_far) {
+  a.rayf = at<float>(ws, L.rayf);
+  a.delta0_mode = 0;
+  if (ray0_near_far) { a.ray0_override = 1; a.near0 = ray0_near_far[0]; a.far0 = ray0_near_far[1]; }
+}
+CoarseArgs coarse_args_ws(void* ws, const WsLayout& L, const float* ray0_near_far, int B, int Nc, int Nf, float* C_coarse) {
+  CoarseArgs ca = coarse_args(at<float>(ws, L.t_c), at<float>(ws, L.sig_c), at<float>(ws, L.rgb_c), B, Nc, Nf, at<float>(ws, L.w_c), C_coarse,
+                              at<float>(ws, L.t_f), at<uint32_t>(ws, L.status));
+  bounds_from_ws(ca, ws, L, ray0_near_far);
+  ca.sticky = at<uint32_t>(ws, L.status) + STATUS_STICKY_WORD;
+  return ca;
+}
+// (bundle, w and perm stay null: the caller sets the ones it keeps)
+MergeArgs merge_args(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f, const float* rgb_c, const float* rgb_f, int B,
+                     int Nc, int Nf, float last_delta, float* C_fine, bool joint) {
+  MergeArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
+  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
+  ma.C_fine = C_fine; ma.joint = joint ? 1 : 0;
+  return ma;
+}
+MergeBwdArgs merge_bwd_args(const float* bundle, const uint16_t* perm, const float* dC_fine, int B, int Nc, int Nf, float last_delta, float* dsig_c,
+                            float* dsig_f, float* drgb_c, float* drgb_f, float* dt_f) {
+  MergeBwdArgs mb;
+  memset(&mb, 0, sizeof(mb));
+  mb.dC_f = dC_fine; mb.bundle = bundle; mb.perm = perm;
+  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
+  mb.drgb_c = drgb_c; mb.dsig_c = dsig_c; mb.drgb_f = drgb_f; mb.dsig_f = dsig_f; mb.dt_f = dt_f;
+  return mb;
+}
+// the sizes a stage entry accepts (the whole calls have check_sizes).  nc_min: 2 like check_sizes -- except for
+// nerf_hip_coarse_composite_quantiles, which has always accepted Nc = 1 and is tested there (tests/test_gpu_quantile.py: the quantiles of
+// a one-sample ray).  Callers rely on it: the bound stays as it is
+int check_coarse_stage_sizes(int B, int Nc, int Nf, int nc_min = 2) {
+  if (B < 1 || Nc < nc_min || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  return NERF_HIP_OK;
+}
+int check_merge_stage_sizes(int B, int Nc, int Nf) {
+  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
+  return NERF_HIP_OK;
+}
+
+// x: the optional per-ray outputs of the call (kernels.h RayExtras; its caller has checked them and the flags), all null = none.  x.maps:
+// the [B][4] output of nerf_hip_forward_maps (inference) / nerf_hip_forward_maps_train (training); with it x.qa / x.qdepth
+// (nerf_hip_forward_quantiles) or x.dist (nerf_hip_forward_distortion_train, a training call).  A maps call always takes the separate
+// k_coarse_x / k_merge_x launches (never the pair kernel, never the FwdFuse epilogues).
+// side_bundle / side_w: nerf_hip_forward_normals (inference): the fine pass's sorted bundle / weights go to its side workspace (both set or
+// both null)
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr,
-                 float* dist = nullptr,  // dist: the [B][2] output of nerf_hip_forward_distortion_train (with maps, a training call), else null
-                 float* side_bundle = nullptr, float* side_w = nullptr);  // nerf_hip_forward_normals (inference): the fine pass's sorted bundle /
-                                                                          // weights go to its side workspace (both set or both null)
+                 int flags, void* stream, TrainLoss* tl, const RayExtras& x, float* side_bundle, float* side_w);
 // nerf_hip_forward_quantiles and its stage entries: the checks they share, before any device work
-int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) {
+// (x.qdepth: set by the caller; x.qa: filled here)
+int check_quantiles(const float* q, int nq, RayExtras& x) {
   static_assert(MAX_QUANTILES == NERF_HIP_MAX_QUANTILES, "kernels.h and nerf_hip.h disagree");
   if (nq < 1 || nq > NERF_HIP_MAX_QUANTILES) return fail(NERF_HIP_ERR_ARG, "nq=%d: 1 .. %d quantiles per call", nq, NERF_HIP_MAX_QUANTILES);
-  if (!q || !qdepth) return fail(NERF_HIP_ERR_ARG, "q or qdepth is null");
+  if (!q || !x.qdepth) return fail(NERF_HIP_ERR_ARG, "q or qdepth is null");
+  QuantArgs& qa = x.qa;
   memset(&qa, 0, sizeof(qa));
   qa.nq = nq;
   for (int j = 0; j < nq; ++j) {
@@ -267,11 +342,12 @@ int check_quantiles(const float* q, int nq, const float* qdepth, QuantArgs& qa) 
   }
   return NERF_HIP_OK;
 }
-// dmaps: nerf_hip_backward_maps's [B][4] upstream of the maps (its caller has checked it), else null.  A dmaps call always takes the
-// separate k_merge_bwd_maps / k_coarse_bwd_maps launches (never the BwdFuse prologues)
+// x: the upstreams of the optional per-ray outputs (its caller has checked them), all null = none.  x.dmaps: nerf_hip_backward_maps's [B][4]
+// upstream of the maps; with it x.ddist: nerf_hip_backward_distortion's [B][2].  A dmaps call always takes the separate k_merge_bwd_x /
+// k_coarse_bwd_x launches (never the BwdFuse prologues)
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl, const float* dmaps = nullptr, const float* ddist = nullptr);  // ddist (with dmaps): nerf_hip_backward_distortion's [B][2]
+                  const TrainLoss* tl, const RayExtras& x);
 }  // namespace
 
 extern "C" {
@@ -280,7 +356,7 @@ int nerf_hip_forward(const float* const* weights24, const int64_t* row, const in
                      const float* K_inv9, const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse,
                      float* C_fine, void* ws, size_t ws_bytes, int flags, void* stream) {
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
-                      nullptr);
+                      nullptr, RayExtras{}, nullptr, nullptr);
 }
 
 int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
@@ -288,8 +364,10 @@ int nerf_hip_forward_maps(const float* const* weights24, const int64_t* row, con
                           float* C_fine, float* maps, void* ws, size_t ws_bytes, int flags, void* stream) {
   if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_maps is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
   if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
+  RayExtras x{};
+  x.maps = maps;
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
-                      nullptr, maps);
+                      nullptr, x, nullptr, nullptr);
 }
 
 int nerf_hip_forward_quantiles(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
@@ -298,10 +376,11 @@ int nerf_hip_forward_quantiles(const float* const* weights24, const int64_t* row
                                float* qdepth) {
   if (flags & NERF_HIP_SAVE_FOR_BACKWARD) return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_quantiles is inference only (NERF_HIP_SAVE_FOR_BACKWARD set)");
   if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
-  QuantArgs qa;
-  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
+  RayExtras x{};
+  x.maps = maps; x.qdepth = qdepth;
+  if (int rc = check_quantiles(q, nq, x)) return rc;
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
-                      nullptr, maps, &qa, qdepth);
+                      nullptr, x, nullptr, nullptr);
 }
 
 int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
@@ -310,8 +389,10 @@ int nerf_hip_forward_maps_train(const float* const* weights24, const int64_t* ro
   if (!(flags & NERF_HIP_SAVE_FOR_BACKWARD))
     return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_maps_train is training only (NERF_HIP_SAVE_FOR_BACKWARD not set)");
   if (!maps) return fail(NERF_HIP_ERR_ARG, "maps is null");
+  RayExtras x{};
+  x.maps = maps;
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
-                      nullptr, maps);
+                      nullptr, x, nullptr, nullptr);
 }
 
 int nerf_hip_forward_distortion_train(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound,
@@ -321,8 +402,10 @@ int nerf_hip_forward_distortion_train(const float* const* weights24, const int64
   if (!(flags & NERF_HIP_SAVE_FOR_BACKWARD))
     return fail(NERF_HIP_ERR_ARG, "nerf_hip_forward_distortion_train is training only (NERF_HIP_SAVE_FOR_BACKWARD not set)");
   if (!maps || !dist) return fail(NERF_HIP_ERR_ARG, "maps or dist is null");
+  RayExtras x{};
+  x.maps = maps; x.dist = dist;
   return forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags, stream,
-                      nullptr, maps, nullptr, nullptr, dist);
+                      nullptr, x, nullptr, nullptr);
 }
 
 }  // extern "C"
@@ -331,8 +414,7 @@ namespace {
 
 int forward_impl(const float* const* weights24, const int64_t* row, const int64_t* col, const float* poses_bound, const float* K_inv9,
                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* C_coarse, float* C_fine, void* ws, size_t ws_bytes,
-                 int flags, void* stream, TrainLoss* tl, float* maps, const QuantArgs* qa, float* qdepth, float* dist, float* side_bundle,
-                 float* side_w) {
+                 int flags, void* stream, TrainLoss* tl, const RayExtras& x, float* side_bundle, float* side_w) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (!row || !col || !poses_bound || !K_inv9 || !C_coarse || !C_fine || !ws) return fail(NERF_HIP_ERR_ARG, "null argument");
@@ -357,7 +439,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   // (field_fwd_bf16x.hip: k_render_pair_bf16x); with the weight image reused (rendering loops) it is the only launch of the call
   const bool corrected = (flags & NERF_HIP_CORRECTED) != 0;  // joint depth sort (forward); the fused small-batch forms keep the reference's sorts only
   // (a maps call takes the separate launches: the pair kernel forms no depth / opacity; same pixels, test_pair_kernel_equals_separate_launches)
-  const bool pair = bf16x && Nc == 64 && Nf == 128 && pair_bf16(B) && !corrected && !maps;
+  const bool pair = bf16x && Nc == 64 && Nf == 128 && pair_bf16(B) && !corrected && !x.maps;
   if (!(flags & NERF_HIP_WEIGHTS_UNCHANGED) && !one_prep) {
     ProfScope ps(NERF_HIP_K_PACK, st, &pc);
     if (bf16 || split) HIP_TRY(launch_fold_weights(w, at<float>(ws, L.fold), st));  // fp32 W_fold, b_fold for the bf16 / split packers (bf16_common.h)
@@ -444,29 +526,22 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     return NERF_HIP_OK;
   }
   // SMALL bf16 TRAINING batches at the shipped sample counts: k_coarse / k_merge ride as epilogues of the field launches (kernels.h FwdFuse)
-  const bool fuse_rays = bf16 && save && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !maps;
+  const bool fuse_rays = bf16 && save && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !x.maps;
   FwdFuse ff;
   memset(&ff, 0, sizeof(ff));
   const bool tile_kernel = (flags & NERF_HIP_FORCE_TILE_KERNEL) != 0;
   auto field = [&](const FieldArgs& f) { return split ? launch_field_fwd_split(f, save, st) : bf16x ? launch_field_fwd_bf16x(f, st) : bf16 ? launch_field_fwd_bf16(f, save, st, ff.mode ? &ff : nullptr) : tile_kernel ? launch_field_fwd(f, save, st) : launch_field_fwd_reg(f, save, st); };
 
-  CoarseArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.t_c = at<float>(ws, L.t_c); ca.sigma = at<float>(ws, L.sig_c); ca.rgb = at<float>(ws, L.rgb_c);
-  ca.rayf = at<float>(ws, L.rayf);
-  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
-  ca.delta0_mode = 0;
-  if (ray0_near_far) { ca.ray0_override = 1; ca.near0 = ray0_near_far[0]; ca.far0 = ray0_near_far[1]; }
-  ca.w_c = at<float>(ws, L.w_c); ca.C_coarse = C_coarse; ca.t_f = at<float>(ws, L.t_f);
-  ca.status = at<uint32_t>(ws, L.status);
-  ca.sticky = at<uint32_t>(ws, L.status) + STATUS_STICKY_WORD;
+  const CoarseArgs ca = coarse_args_ws(ws, L, ray0_near_far, B, Nc, Nf, C_coarse);
+  RayExtras xs = x;  // (the merge kernel's distortion loss takes near / far from the ray records of this workspace)
+  xs.rayf = at<float>(ws, L.rayf);
   if (fuse_rays) {
     ff.mode = 1; ff.c = ca;
     { ProfScope ps(NERF_HIP_K_FIELD_COARSE, st, &pc); HIP_TRY(field(fa)); }
     ff.mode = 0;
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_COARSE, st, &pc); HIP_TRY(field(fa)); }
-    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(dist ? launch_coarse_dist(ca, maps, dist, st) : qa ? launch_coarse_quantiles(ca, maps, *qa, qdepth, st) : launch_coarse(ca, st, maps)); }
+    { ProfScope ps(NERF_HIP_K_COARSE, st, &pc); HIP_TRY(launch_coarse(ca, st, &xs)); }
   }
 
   // fine pass (nerf.py:299), same network (quirk Q10)
@@ -475,17 +550,10 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
   fa.sigma = at<float>(ws, L.sig_f);
   fa.N = Nf; fa.M = B * Nf;
   if (save) { fa.row0 = B * Nc; fa.tile0 = tiles_c; fa.wb0 = (int)wave_blocks(B, Nc); }
-  MergeArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.t_c = at<float>(ws, L.t_c); ma.t_f = at<float>(ws, L.t_f);
-  ma.sig_c = at<float>(ws, L.sig_c); ma.sig_f = at<float>(ws, L.sig_f);
-  ma.rgb_c = at<float>(ws, L.rgb_c); ma.rgb_f = at<float>(ws, L.rgb_f);
-  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf);
-  ma.last = last_delta;
-  ma.joint = corrected ? 1 : 0;
+  MergeArgs ma = merge_args(at<float>(ws, L.t_c), at<float>(ws, L.t_f), at<float>(ws, L.sig_c), at<float>(ws, L.sig_f), at<float>(ws, L.rgb_c),
+                            at<float>(ws, L.rgb_f), B, Nc, Nf, last_delta, C_fine, corrected);
   if (save) { ma.bundle = at<float>(ws, L.bundle); ma.w = at<float>(ws, L.w_m); ma.perm = at<uint16_t>(ws, L.perm); }
   else if (side_bundle) { ma.bundle = side_bundle; ma.w = side_w; }  // (the merge kernels store both wherever the pointers are set)
-  ma.C_fine = C_fine;
   if (fuse_rays) {
     ff.mode = 2; ff.m = ma;
     if (tl) {  // inside nerf_hip_train_step: ray_loss's per-element work rides in the same epilogue
@@ -495,8 +563,7 @@ int forward_impl(const float* const* weights24, const int64_t* row, const int64_
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
   } else {
     { ProfScope ps(NERF_HIP_K_FIELD_FINE, st, &pc); HIP_TRY(field(fa)); }
-    const DistArgs da{at<float>(ws, L.rayf), nullptr, dist, nullptr};  // (dist only)
-    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(dist ? launch_merge_dist(ma, maps, da, st) : qa ? launch_merge_quantiles(ma, maps, *qa, qdepth, st) : launch_merge(ma, st, maps)); }
+    { ProfScope ps(NERF_HIP_K_MERGE, st, &pc); HIP_TRY(launch_merge(ma, st, &xs)); }
   }
   return NERF_HIP_OK;
 }
@@ -588,8 +655,10 @@ int nerf_hip_forward_normals(const float* const* weights24, const int64_t* row, 
   const NormalsLayout NL = normals_layout(B, Nc, Nf);
   if (((uintptr_t)nws & 255) != 0) return fail(NERF_HIP_ERR_ARG, "nws must be 256-byte aligned");
   if (nws_bytes < NL.total) return fail(NERF_HIP_ERR_ARG, "nws %zu < %zu bytes (nerf_hip_normals_ws_bytes)", nws_bytes, NL.total);
+  RayExtras xm{};
+  xm.maps = maps;
   if (int rc = forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags,
-                            stream, nullptr, maps, nullptr, nullptr, nullptr, at<float>(nws, NL.bundle), at<float>(nws, NL.w_m)))
+                            stream, nullptr, xm, at<float>(nws, NL.bundle), at<float>(nws, NL.w_m)))
     return rc;
   // the gradients are exact fp32 whatever the flags say: the gradient query's own image and launches, packed once per call
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -686,23 +755,27 @@ int nerf_hip_backward_overlap(const float* const* weights24, const float* dC_coa
                               int B, int Nc, int Nf, float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags,
                               void* stream, void* early_event) {
   return backward_impl(weights24, dC_coarse, dC_fine, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes, flags, stream, early_event,
-                       nullptr);
+                       nullptr, RayExtras{});
 }
 
 int nerf_hip_backward_maps(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
                            const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* const* dweights24, void* ws,
                            size_t ws_bytes, int flags, void* stream, void* early_event) {
   if (!dmaps) return fail(NERF_HIP_ERR_ARG, "dmaps is null");
+  RayExtras x{};
+  x.dmaps = dmaps;
   return backward_impl(weights24, dC_coarse, dC_fine, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes, flags, stream, early_event,
-                       nullptr, dmaps);
+                       nullptr, x);
 }
 
 int nerf_hip_backward_distortion(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* dmaps,
                                  const float* ray0_near_far, int B, int Nc, int Nf, float last_delta, float* const* dweights24, void* ws,
                                  size_t ws_bytes, int flags, void* stream, void* early_event, const float* ddist) {
   if (!dmaps || !ddist) return fail(NERF_HIP_ERR_ARG, "dmaps or ddist is null");
+  RayExtras x{};
+  x.dmaps = dmaps; x.ddist = ddist;
   return backward_impl(weights24, dC_coarse, dC_fine, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes, flags, stream, early_event,
-                       nullptr, dmaps, ddist);
+                       nullptr, x);
 }
 
 }  // extern "C"
@@ -711,7 +784,7 @@ namespace {
 
 int backward_impl(const float* const* weights24, const float* dC_coarse, const float* dC_fine, const float* ray0_near_far, int B, int Nc, int Nf,
                   float last_delta, float* const* dweights24, void* ws, size_t ws_bytes, int flags, void* stream, void* early_event,
-                  const TrainLoss* tl, const float* dmaps, const float* ddist) {
+                  const TrainLoss* tl, const RayExtras& x) {
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   if (int rc = check_weights(weights24)) return rc;
   if (int rc = check_weights(const_cast<const float* const*>(dweights24))) return rc;
@@ -737,25 +810,17 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   if (bf16 && prep_bf16_disabled()) { ProfScope ps(NERF_HIP_K_PACK, st, &pc); HIP_TRY(launch_pack_weights_bf16_bwd(w, at<float>(ws, L.fold), at<unsigned char>(ws, L.packed_bf_bwd), st)); }
 
   // 1. merged composite + per-channel sort backward (nerf.py:302-321)
-  MergeBwdArgs mb;
-  memset(&mb, 0, sizeof(mb));
-  mb.dC_f = dC_fine; mb.bundle = at<float>(ws, L.bundle); mb.perm = at<uint16_t>(ws, L.perm);
-  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
-  mb.drgb_c = at<float>(ws, L.drgb_c); mb.dsig_c = at<float>(ws, L.dsig_c);
-  mb.drgb_f = at<float>(ws, L.drgb_f); mb.dsig_f = at<float>(ws, L.dsig_f); mb.dt_f = at<float>(ws, L.dt_f);
+  const MergeBwdArgs mb = merge_bwd_args(at<float>(ws, L.bundle), at<uint16_t>(ws, L.perm), dC_fine, B, Nc, Nf, last_delta, at<float>(ws, L.dsig_c),
+                                         at<float>(ws, L.dsig_f), at<float>(ws, L.drgb_c), at<float>(ws, L.drgb_f), at<float>(ws, L.dt_f));
+  RayExtras xs = x;  // (near / far of the merge backward's distortion terms: the ray records the forward left in the workspace)
+  xs.rayf = at<float>(ws, L.rayf);
   // SMALL bf16 batches: the per-ray backward stages ride as prologues of the chain launches (kernels.h BwdFuse)
   const bool corrected = (flags & NERF_HIP_CORRECTED) != 0;
   // (the workspace holds the same saves after a fused and after a separate forward: either backward form may follow either forward)
-  const bool fuse_rays = bf16 && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !dmaps;
+  const bool fuse_rays = bf16 && Nc == 64 && Nf == 128 && fuse_rays_bf16(B) && !corrected && !x.dmaps;
   BwdFuse bz;
   memset(&bz, 0, sizeof(bz));
-  if (ddist) {  // (near / far: the ray records the forward left in the workspace)
-    const DistArgs da{at<float>(ws, L.rayf), nullptr, nullptr, ddist};
-    ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc);
-    HIP_TRY(launch_merge_bwd_dist(mb, dmaps, da, st));
-  }
-  else if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd_maps(mb, dmaps, st)); }
-  else if (!fuse_rays) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd(mb, st)); }
+  if (!fuse_rays) { ProfScope ps(NERF_HIP_K_BWD_MERGE, st, &pc); HIP_TRY(launch_merge_bwd(mb, st, &xs)); }
 
   // 2. fine-pass field backward (dX chain incl. d loss / d t_fine)
   FieldBwdArgs fb;
@@ -793,18 +858,11 @@ int backward_impl(const float* const* weights24, const float* dC_coarse, const f
   if (corrected) HIP_TRY(hipMemsetAsync(at<float>(ws, L.dt_f), 0, (size_t)B * Nf * sizeof(float), st));
 
   // 3. resampling + coarse composite backward (nerf.py:225-261, 263-281)
-  CoarseBwdArgs cb;
-  memset(&cb, 0, sizeof(cb));
-  cb.dC_c = dC_coarse; cb.dt_f = at<float>(ws, L.dt_f);
-  cb.t_c = at<float>(ws, L.t_c); cb.sigma = at<float>(ws, L.sig_c); cb.rgb = at<float>(ws, L.rgb_c);
-  cb.rayf = at<float>(ws, L.rayf);
-  cb.B = B; cb.Nc = Nc; cb.Nf = Nf;
-  if (ray0_near_far) { cb.ray0_override = 1; cb.near0 = ray0_near_far[0]; cb.far0 = ray0_near_far[1]; }
-  cb.drgb_c = at<float>(ws, L.drgb_c); cb.dsig_c = at<float>(ws, L.dsig_c);
+  CoarseBwdArgs cb = coarse_bwd_args(at<float>(ws, L.t_c), at<float>(ws, L.sig_c), at<float>(ws, L.rgb_c), B, Nc, Nf, dC_coarse, at<float>(ws, L.dt_f),
+                                     at<float>(ws, L.dsig_c), at<float>(ws, L.drgb_c));
+  bounds_from_ws(cb, ws, L, ray0_near_far);
   if (fuse_rays) { bz.mode = 2; bz.c = cb; }
-  else if (ddist) { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd_dist(cb, dmaps, ddist, st)); }
-  else if (dmaps) { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd_maps(cb, dmaps, st)); }
-  else { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd(cb, st)); }
+  else { ProfScope ps(NERF_HIP_K_BWD_COARSE, st, &pc); HIP_TRY(launch_coarse_bwd(cb, st, &xs)); }
 
   // 4. coarse-pass field backward
   fb.t = at<float>(ws, L.t_c); fb.rgb = at<float>(ws, L.rgb_c);
@@ -882,12 +940,12 @@ int nerf_hip_train_step(const float* const* weights24, const int64_t* row, const
   tl.C_true = C_true; tl.dC_c = at<float>(ws, L.dC); tl.dC_f = tl.dC_c + (size_t)B * 3; tl.terms = tl.dC_f + (size_t)B * 3; tl.loss = loss;
   tl.fused = false;
   if (int rc = forward_impl(weights24, row, col, poses_bound, K_inv9, ray0_near_far, B, Nc, Nf, last_delta, C_coarse, C_fine, ws, ws_bytes, flags,
-                            stream, &tl))
+                            stream, &tl, RayExtras{}, nullptr, nullptr))
     return rc;
   if (!tl.fused)  // (fused: d loss / d C and the loss's summands came out of the fine pass's epilogue; its sum is taken in the backward)
     if (int rc = nerf_hip_ray_loss(C_coarse, C_fine, C_true, B, loss, tl.dC_c, tl.dC_f, stream)) return rc;
   return backward_impl(weights24, tl.dC_c, tl.dC_f, ray0_near_far, B, Nc, Nf, last_delta, dweights24, ws, ws_bytes,
-                       flags & ~NERF_HIP_WEIGHTS_UNCHANGED, stream, early_event, &tl);
+                       flags & ~NERF_HIP_WEIGHTS_UNCHANGED, stream, early_event, &tl, RayExtras{});
 }
 
 int nerf_hip_ws_offset(int B, int Nc, int Nf, int flags, const char* name, size_t* offset) {
@@ -895,11 +953,16 @@ int nerf_hip_ws_offset(int B, int Nc, int Nf, int flags, const char* name, size_
   if (int rc = check_sizes(B, Nc, Nf)) return rc;
   const WsLayout L = layout(B, Nc, Nf, flags);
   struct { const char* n; size_t o; } tab[] = {
-      {"status", L.status}, {"dbg", L.dbg}, {"packed", L.packed}, {"packed_bf", L.packed_bf}, {"bsave", L.bsave}, {"bsave2", L.bsave2}, {"bmask", L.bmask}, {"bG", L.bG}, {"bG2", L.bG2}, {"rayf", L.rayf}, {"dvec", L.dvec}, {"t_c", L.t_c}, {"sig_c", L.sig_c},
-      {"rgb_c", L.rgb_c}, {"w_c", L.w_c}, {"t_f", L.t_f}, {"sig_f", L.sig_f}, {"rgb_f", L.rgb_f}, {"perm", L.perm},
-      {"w_m", L.w_m}, {"bundle", L.bundle}, {"save", L.save}, {"masks", L.masks}, {"spre", L.spre}, {"G", L.G}, {"dz", L.dz},
-      {"dspre", L.dspre}, {"mbuf", L.mbuf}, {"fold", L.fold}, {"drgb_c", L.drgb_c}, {"dsig_c", L.dsig_c}, {"drgb_f", L.drgb_f}, {"dsig_f", L.dsig_f},
-      {"dt_f", L.dt_f}, {"slabs", L.slabs}, {"masks", L.masks}, {"sbuf", L.sbuf}, {"gdbuf", L.gdbuf}};
+      // status and diagnostics, weight images and the fold
+      {"status", L.status}, {"dbg", L.dbg}, {"packed", L.packed}, {"packed_bf", L.packed_bf}, {"fold", L.fold},
+      // rays, the two passes' samples, the merged composite
+      {"rayf", L.rayf}, {"dvec", L.dvec}, {"t_c", L.t_c}, {"sig_c", L.sig_c}, {"rgb_c", L.rgb_c}, {"w_c", L.w_c},
+      {"t_f", L.t_f}, {"sig_f", L.sig_f}, {"rgb_f", L.rgb_f}, {"perm", L.perm}, {"w_m", L.w_m}, {"bundle", L.bundle},
+      // what a training forward saves: fp32, then bf16 / split-fp32
+      {"save", L.save}, {"masks", L.masks}, {"spre", L.spre}, {"bsave", L.bsave}, {"bsave2", L.bsave2}, {"bmask", L.bmask},
+      // the backward's gradients and scratch
+      {"G", L.G}, {"dz", L.dz}, {"dspre", L.dspre}, {"bG", L.bG}, {"bG2", L.bG2}, {"slabs", L.slabs}, {"sbuf", L.sbuf}, {"gdbuf", L.gdbuf},
+      {"mbuf", L.mbuf}, {"drgb_c", L.drgb_c}, {"dsig_c", L.dsig_c}, {"drgb_f", L.drgb_f}, {"dsig_f", L.dsig_f}, {"dt_f", L.dt_f}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.o == 0 && strcmp(name, "status") != 0) return fail(NERF_HIP_ERR_ARG, "buffer %s is not part of this layout (flags=%d)", name, flags);
@@ -1026,13 +1089,9 @@ int nerf_hip_field_bf16(const float* const* weights24, const int64_t* row, const
 int nerf_hip_coarse_composite(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far, float delta0,
                               int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, void* stream) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
-  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
-  ca.delta0_mode = 1; ca.delta0 = delta0;
-  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  CoarseArgs ca = coarse_args(t_c, sigma_c, rgb_c, B, Nc, Nf, w_c, C_coarse, t_f, status);
+  bounds_given(ca, near_far, delta0);
   HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
@@ -1078,12 +1137,9 @@ int nerf_hip_coarse_composite_backward(const float* t_c, const float* sigma_c, c
                                        float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
                                        float* dsig_c, float* drgb_c, void* stream) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseBwdArgs cb;
-  memset(&cb, 0, sizeof(cb));
-  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c; cb.near_far = near_far;
-  cb.B = B; cb.Nc = Nc; cb.Nf = Nf; cb.delta0_mode = 1; cb.delta0 = delta0;
-  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  CoarseBwdArgs cb = coarse_bwd_args(t_c, sigma_c, rgb_c, B, Nc, Nf, dC_coarse, dt_f, dsig_c, drgb_c);
+  bounds_given(cb, near_far, delta0);
   HIP_TRY(launch_coarse_bwd(cb, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
@@ -1092,12 +1148,9 @@ int nerf_hip_merge_composite(const float* t_c, const float* t_f, const float* si
                              const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
                              void* stream) {
   if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  MergeArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
-  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
-  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine;
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  MergeArgs ma = merge_args(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, B, Nc, Nf, last_delta, C_fine, false);
+  ma.bundle = bundle; ma.w = w;
   HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
@@ -1106,14 +1159,12 @@ int nerf_hip_coarse_composite_maps(const float* t_c, const float* sigma_c, const
                                    int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
                                    void* stream) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
-  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
-  ca.delta0_mode = 1; ca.delta0 = delta0;
-  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
-  HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream), maps));
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.maps = maps;
+  CoarseArgs ca = coarse_args(t_c, sigma_c, rgb_c, B, Nc, Nf, w_c, C_coarse, t_f, status);
+  bounds_given(ca, near_far, delta0);
+  HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1121,14 +1172,12 @@ int nerf_hip_coarse_composite_backward_maps(const float* t_c, const float* sigma
                                             float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
                                             const float* dmaps, float* dsig_c, float* drgb_c, void* stream) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseBwdArgs cb;
-  memset(&cb, 0, sizeof(cb));
-  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c; cb.near_far = near_far;
-  cb.B = B; cb.Nc = Nc; cb.Nf = Nf; cb.delta0_mode = 1; cb.delta0 = delta0;
-  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
-  if (dmaps) HIP_TRY(launch_coarse_bwd_maps(cb, dmaps, static_cast<hipStream_t>(stream)));
-  else HIP_TRY(launch_coarse_bwd(cb, static_cast<hipStream_t>(stream)));
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.dmaps = dmaps;  // (null: the plain kernel)
+  CoarseBwdArgs cb = coarse_bwd_args(t_c, sigma_c, rgb_c, B, Nc, Nf, dC_coarse, dt_f, dsig_c, drgb_c);
+  bounds_given(cb, near_far, delta0);
+  HIP_TRY(launch_coarse_bwd(cb, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1136,13 +1185,12 @@ int nerf_hip_merge_composite_train(const float* t_c, const float* t_f, const flo
                                    const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
                                    uint16_t* perm, int joint, float* maps, void* stream) {
   if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !perm) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  MergeArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
-  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
-  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
-  HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), maps));
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.maps = maps;  // (null: the plain kernel)
+  MergeArgs ma = merge_args(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, B, Nc, Nf, last_delta, C_fine, joint != 0);
+  ma.bundle = bundle; ma.w = w; ma.perm = perm;
+  HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1150,16 +1198,13 @@ int nerf_hip_coarse_composite_quantiles(const float* t_c, const float* sigma_c, 
                                         int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
                                         void* stream, const float* q, int nq, float* qdepth) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  QuantArgs qa;
-  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
-  CoarseArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
-  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
-  ca.delta0_mode = 1; ca.delta0 = delta0;
-  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
-  HIP_TRY(launch_coarse_quantiles(ca, maps, qa, qdepth, static_cast<hipStream_t>(stream)));
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf, 1)) return rc;
+  RayExtras x{};
+  x.maps = maps; x.qdepth = qdepth;
+  if (int rc = check_quantiles(q, nq, x)) return rc;
+  CoarseArgs ca = coarse_args(t_c, sigma_c, rgb_c, B, Nc, Nf, w_c, C_coarse, t_f, status);
+  bounds_given(ca, near_far, delta0);
+  HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1167,15 +1212,13 @@ int nerf_hip_merge_composite_quantiles(const float* t_c, const float* t_f, const
                                        const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
                                        uint16_t* perm, int joint, float* maps, void* stream, const float* q, int nq, float* qdepth) {
   if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !maps) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  QuantArgs qa;
-  if (int rc = check_quantiles(q, nq, qdepth, qa)) return rc;
-  MergeArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
-  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
-  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
-  HIP_TRY(launch_merge_quantiles(ma, maps, qa, qdepth, static_cast<hipStream_t>(stream)));
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.maps = maps; x.qdepth = qdepth;
+  if (int rc = check_quantiles(q, nq, x)) return rc;
+  MergeArgs ma = merge_args(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, B, Nc, Nf, last_delta, C_fine, joint != 0);
+  ma.bundle = bundle; ma.w = w; ma.perm = perm;
+  HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1183,61 +1226,50 @@ int nerf_hip_coarse_composite_distortion(const float* t_c, const float* sigma_c,
                                          int B, int Nc, int Nf, float* w_c, float* C_coarse, float* t_f, uint32_t* status, float* maps,
                                          void* stream, float* dist) {
   if (!t_c || !sigma_c || !rgb_c || !near_far || !t_f || !maps || !dist) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.t_c = t_c; ca.sigma = sigma_c; ca.rgb = rgb_c; ca.near_far = near_far;
-  ca.B = B; ca.Nc = Nc; ca.Nf = Nf;
-  ca.delta0_mode = 1; ca.delta0 = delta0;
-  ca.w_c = w_c; ca.C_coarse = C_coarse; ca.t_f = t_f; ca.status = status;
-  HIP_TRY(launch_coarse_dist(ca, maps, dist, static_cast<hipStream_t>(stream)));
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.maps = maps; x.dist = dist;
+  CoarseArgs ca = coarse_args(t_c, sigma_c, rgb_c, B, Nc, Nf, w_c, C_coarse, t_f, status);
+  bounds_given(ca, near_far, delta0);
+  HIP_TRY(launch_coarse(ca, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
 int nerf_hip_merge_composite_distortion(const float* t_c, const float* t_f, const float* sigma_c, const float* sigma_f, const float* rgb_c,
                                         const float* rgb_f, int B, int Nc, int Nf, float last_delta, float* bundle, float* w, float* C_fine,
                                         uint16_t* perm, int joint, float* maps, void* stream, const float* near_far, float* dist) {
-  if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !perm || !maps || !near_far || !dist)
-    return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  MergeArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.t_c = t_c; ma.t_f = t_f; ma.sig_c = sigma_c; ma.sig_f = sigma_f; ma.rgb_c = rgb_c; ma.rgb_f = rgb_f;
-  ma.B = B; ma.Nc = Nc; ma.Nf = Nf; ma.P = next_pow2(Nc + Nf); ma.last = last_delta;
-  ma.bundle = bundle; ma.w = w; ma.C_fine = C_fine; ma.perm = perm; ma.joint = joint ? 1 : 0;
-  const DistArgs da{nullptr, near_far, dist, nullptr};
-  HIP_TRY(launch_merge_dist(ma, maps, da, static_cast<hipStream_t>(stream)));
+  if (!t_c || !t_f || !sigma_c || !sigma_f || !rgb_c || !rgb_f || !C_fine || !perm || !maps || !near_far || !dist) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.maps = maps; x.dist = dist; x.near_far = near_far;
+  MergeArgs ma = merge_args(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, B, Nc, Nf, last_delta, C_fine, joint != 0);
+  ma.bundle = bundle; ma.w = w; ma.perm = perm;
+  HIP_TRY(launch_merge(ma, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
 int nerf_hip_coarse_composite_backward_distortion(const float* t_c, const float* sigma_c, const float* rgb_c, const float* near_far,
                                                   float delta0, int B, int Nc, int Nf, const float* dC_coarse, const float* dt_f,
                                                   const float* dmaps, float* dsig_c, float* drgb_c, void* stream, const float* ddist) {
-  if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c || !ddist)
-    return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 2 || Nc > 1024 || Nf < 1 || Nf > 1024) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  CoarseBwdArgs cb;
-  memset(&cb, 0, sizeof(cb));
-  cb.dC_c = dC_coarse; cb.dt_f = dt_f; cb.t_c = t_c; cb.sigma = sigma_c; cb.rgb = rgb_c; cb.near_far = near_far;
-  cb.B = B; cb.Nc = Nc; cb.Nf = Nf; cb.delta0_mode = 1; cb.delta0 = delta0;
-  cb.drgb_c = drgb_c; cb.dsig_c = dsig_c;
-  HIP_TRY(launch_coarse_bwd_dist(cb, dmaps, ddist, static_cast<hipStream_t>(stream)));
+  if (!t_c || !sigma_c || !rgb_c || !near_far || !dC_coarse || !dt_f || !dsig_c || !drgb_c || !ddist) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (int rc = check_coarse_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.dmaps = dmaps; x.ddist = ddist;  // (dmaps null: zeros)
+  CoarseBwdArgs cb = coarse_bwd_args(t_c, sigma_c, rgb_c, B, Nc, Nf, dC_coarse, dt_f, dsig_c, drgb_c);
+  bounds_given(cb, near_far, delta0);
+  HIP_TRY(launch_coarse_bwd(cb, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
 int nerf_hip_merge_composite_backward_distortion(const float* bundle, const uint16_t* perm, const float* dC_fine, const float* dmaps, int B,
                                                  int Nc, int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c,
                                                  float* drgb_f, float* dt_f, void* stream, const float* near_far, const float* ddist) {
-  if (!bundle || !perm || !dC_fine || !dsig_c || !dsig_f || !drgb_c || !drgb_f || !dt_f || !near_far || !ddist)
-    return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  MergeBwdArgs mb;
-  memset(&mb, 0, sizeof(mb));
-  mb.dC_f = dC_fine; mb.bundle = bundle; mb.perm = perm;
-  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
-  mb.drgb_c = drgb_c; mb.dsig_c = dsig_c; mb.drgb_f = drgb_f; mb.dsig_f = dsig_f; mb.dt_f = dt_f;
-  const DistArgs da{nullptr, near_far, nullptr, ddist};
-  HIP_TRY(launch_merge_bwd_dist(mb, dmaps, da, static_cast<hipStream_t>(stream)));
+  if (!bundle || !perm || !dC_fine || !dsig_c || !dsig_f || !drgb_c || !drgb_f || !dt_f || !near_far || !ddist) return fail(NERF_HIP_ERR_ARG, "null argument");
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.dmaps = dmaps; x.ddist = ddist; x.near_far = near_far;  // (dmaps null: zeros)
+  const MergeBwdArgs mb = merge_bwd_args(bundle, perm, dC_fine, B, Nc, Nf, last_delta, dsig_c, dsig_f, drgb_c, drgb_f, dt_f);
+  HIP_TRY(launch_merge_bwd(mb, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 
@@ -1245,14 +1277,11 @@ int nerf_hip_merge_composite_backward(const float* bundle, const uint16_t* perm,
                                       int Nf, float last_delta, float* dsig_c, float* dsig_f, float* drgb_c, float* drgb_f, float* dt_f,
                                       void* stream) {
   if (!bundle || !perm || !dC_fine || !dsig_c || !dsig_f || !drgb_c || !drgb_f || !dt_f) return fail(NERF_HIP_ERR_ARG, "null argument");
-  if (B < 1 || Nc < 1 || Nf < 1 || Nc + Nf > 2048) return fail(NERF_HIP_ERR_ARG, "bad sizes");
-  MergeBwdArgs mb;
-  memset(&mb, 0, sizeof(mb));
-  mb.dC_f = dC_fine; mb.bundle = bundle; mb.perm = perm;
-  mb.B = B; mb.Nc = Nc; mb.Nf = Nf; mb.last = last_delta;
-  mb.drgb_c = drgb_c; mb.dsig_c = dsig_c; mb.drgb_f = drgb_f; mb.dsig_f = dsig_f; mb.dt_f = dt_f;
-  if (dmaps) HIP_TRY(launch_merge_bwd_maps(mb, dmaps, static_cast<hipStream_t>(stream)));
-  else HIP_TRY(launch_merge_bwd(mb, static_cast<hipStream_t>(stream)));
+  if (int rc = check_merge_stage_sizes(B, Nc, Nf)) return rc;
+  RayExtras x{};
+  x.dmaps = dmaps;  // (null: the plain kernel)
+  const MergeBwdArgs mb = merge_bwd_args(bundle, perm, dC_fine, B, Nc, Nf, last_delta, dsig_c, dsig_f, drgb_c, drgb_f, dt_f);
+  HIP_TRY(launch_merge_bwd(mb, static_cast<hipStream_t>(stream), &x));
   return NERF_HIP_OK;
 }
 

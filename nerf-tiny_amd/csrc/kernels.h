@@ -195,33 +195,46 @@ hipError_t launch_rays(const RaysArgs& a, hipStream_t st);
 constexpr int PREP_READY_WORDS = 256;
 hipError_t launch_prep_bf16(const Weights24& w, float* fold, unsigned char* img_fwd, int fwd_form, unsigned char* img_bwd,
                             unsigned* ready, unsigned token, unsigned* sticky, const RaysArgs& rays, hipStream_t st);
-// maps != null (nerf_hip_forward_maps, nerf_hip_forward_maps_train): k_coarse_maps / k_merge_maps, which also store each ray's (D_c, A_c) / (D_f, A_f) to maps [B][4]
-hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps = nullptr);
-size_t merge_lds_bytes(int P);
-hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps = nullptr);
-// nerf_hip_forward_quantiles: k_coarse_qmaps / k_merge_qmaps -- the maps kernels, which also store each ray's quantile depths (rule QD of
-// include/nerf_hip.h) to qdepth [B][2][nq], row 0 by the coarse kernel, row 1 by the merge kernel.  The quantiles travel as a kernel argument
-// of their own (like the maps pointer: CoarseArgs / MergeArgs ride inside FwdFuse)
+// The optional per-ray outputs of one call of the per-ray stages, and in the backward their upstreams: ONE record from the C entry
+// (api.hip) down to the device functions (ray_parts.h, ray_parts_bwd.h).  A null pointer = not asked for; which fields a kernel reads
+// is fixed by the flags of its instantiation (MAPS, QD, DL), never tested at run time.
+// It travels as a kernel argument of its own, not as fields of CoarseArgs / MergeArgs / MergeBwdArgs / CoarseBwdArgs: those structs ride
+// inside FwdFuse / BwdFuse / PairArgs, the arguments of the bf16 training and pair kernels, whose layouts it must not touch.
 constexpr int MAX_QUANTILES = 4;  // = NERF_HIP_MAX_QUANTILES
 struct QuantArgs {
   float q[MAX_QUANTILES];
   int nq;
 };
-hipError_t launch_coarse_quantiles(const CoarseArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
-hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st);
-// nerf_hip_forward_distortion_train / nerf_hip_backward_distortion: k_coarse_dmaps / k_merge_dmaps -- the training maps kernels, which also
-// store each ray's distortion loss (rule DL of include/nerf_hip.h) to dist [B][2], column 0 by the coarse kernel, column 1 by the merge
-// kernel -- and k_merge_bwd_dist / k_coarse_bwd_dist (ray_ops_bwd.hip), the maps backward kernels that also take its upstream ddist [B][2].
-// The merge kernels have no ray records of their own: near / far come from rayf (the workspace's records) or near_far [B][2] (stage entries).
-// A kernel argument of its own, like the maps pointer
-struct DistArgs {
+struct RayExtras {
+  // MAPS (nerf_hip_forward_maps, nerf_hip_forward_maps_train): each ray's (D_c, A_c) by the coarse kernel, (D_f, A_f) by the merge kernel
+  float* maps;            // [B][4]
+  // QD (nerf_hip_forward_quantiles, with maps): each ray's quantile depths (rule QD of include/nerf_hip.h), row 0 by the coarse kernel,
+  // row 1 by the merge kernel.  The quantiles themselves travel here too
+  QuantArgs qa;
+  float* qdepth;          // [B][2][qa.nq]
+  // DL (nerf_hip_forward_distortion_train, with maps): each ray's distortion loss (rule DL), column 0 by the coarse kernel, column 1 by the
+  // merge kernel.  The merge kernels have no ray records of their own: near / far come from rayf (the workspace's records) or near_far
+  // (stage entries)
+  float* dist;            // [B][2]
   const float* rayf;      // [B][RAYF] or null
   const float* near_far;  // [B][2], used when rayf is null
-  float* dist;            // forward: [B][2]
-  const float* ddist;     // backward: [B][2]
+  // backward (nerf_hip_backward_maps, nerf_hip_backward_distortion): the upstreams (gD_c, gA_c, gD_f, gA_f) of the maps and (gL_c, gL_f) of
+  // the distortion losses
+  const float* dmaps;     // [B][4]; DL: or null = zeros (the distortion stage entries may come without it)
+  const float* ddist;     // [B][2]
 };
-hipError_t launch_coarse_dist(const CoarseArgs& a, float* maps, float* dist, hipStream_t st);
-hipError_t launch_merge_dist(const MergeArgs& a, float* maps, const DistArgs& da, hipStream_t st);  // a.perm set (a training call)
+// (launchers of the per-ray stages) the launch of a kernel with `lds` bytes of dynamic LDS: above `limit`, what a launch may ask for as it is, the kernel's attribute is raised first
+template <class... KArgs, class... Args>
+inline hipError_t launch_dyn_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, size_t limit, hipStream_t st, const Args&... args) {
+  if (lds > limit)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
+// x == null or no pointer of it set: k_coarse / k_merge.  Otherwise the instantiation of k_coarse_x / k_merge_x for what x asks for: maps,
+// maps + quantiles (qdepth set) or maps + distortion (dist set; the merge kernel then sorts with slots: a training call, a.perm set)
+hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, const RayExtras* x = nullptr);
+hipError_t launch_merge(const MergeArgs& a, hipStream_t st, const RayExtras* x = nullptr);
 // nerf_hip_forward_normals (ray_normals.hip; rule NM of include/nerf_hip.h): the world points of nrays whole rays of N samples each (rayf and
 // t start at the first of them; t_stride 1 = t_c, 5 = channel 0 of the sorted bundle), and the per-ray composite of the field normals of
 // g [B][N][3] with the weights w [B][N] -> out[b * out_stride + 0..2]
@@ -382,15 +395,10 @@ hipError_t launch_dw_reduce(const DwBatch& b, hipStream_t st, int first = 0, int
 size_t dw_item_slab_floats(const DwItem& p);
 bool dw_ray_duty_ok(const DwItem& p, long long Mtot, int B, int Nc, int Nf);  // may the product of G_dir carry the per-ray sums?
 hipError_t launch_small_grads(const SmallGradArgs& a, float* scratch, hipStream_t st);  // scratch: >= 128 * 128 * 24 floats (the slab buffer, after the reduce)
-size_t merge_bwd_lds_bytes(int N);
-hipError_t launch_merge_bwd(const MergeBwdArgs& a, hipStream_t st);
-hipError_t launch_coarse_bwd(const CoarseBwdArgs& a, hipStream_t st);
-// nerf_hip_backward_maps: k_merge_bwd_maps / k_coarse_bwd_maps, which also take each ray's upstream (gD_c, gA_c, gD_f, gA_f) from dmaps [B][4]
-hipError_t launch_merge_bwd_maps(const MergeBwdArgs& a, const float* dmaps, hipStream_t st);
-hipError_t launch_coarse_bwd_maps(const CoarseBwdArgs& a, const float* dmaps, hipStream_t st);
-// nerf_hip_backward_distortion: the maps backward kernels plus rule DL's terms (da.ddist [B][2]: the upstream of L_c, L_f)
-hipError_t launch_merge_bwd_dist(const MergeBwdArgs& a, const float* dmaps, const DistArgs& da, hipStream_t st);
-hipError_t launch_coarse_bwd_dist(const CoarseBwdArgs& a, const float* dmaps, const float* ddist, hipStream_t st);
+// x == null or no upstream of it set: k_merge_bwd / k_coarse_bwd.  Otherwise k_merge_bwd_x / k_coarse_bwd_x with the maps' upstream
+// (dmaps) or, ddist set, with the distortion losses' upstream too (ray_ops_bwd.hip)
+hipError_t launch_merge_bwd(const MergeBwdArgs& a, hipStream_t st, const RayExtras* x = nullptr);
+hipError_t launch_coarse_bwd(const CoarseBwdArgs& a, hipStream_t st, const RayExtras* x = nullptr);
 
 struct AdamArgs {
   float* param[24];

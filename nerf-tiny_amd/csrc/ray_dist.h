@@ -13,8 +13,10 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 }
 // r of rule DL
 __device__ __forceinline__ double dist_ray_scale(float near, float far) { return 1.0 / ((double)far - (double)near); }
-__device__ __forceinline__ float dist_near(const DistArgs& da, int ray) { return da.rayf ? da.rayf[(size_t)ray * RAYF + RF_NEAR] : da.near_far[2 * ray]; }
-__device__ __forceinline__ float dist_far(const DistArgs& da, int ray) { return da.rayf ? da.rayf[(size_t)ray * RAYF + RF_FAR] : da.near_far[2 * ray + 1]; }
+// ... of ray `ray` for the merge kernels, from the bounds the extras record carries for them (kernels.h RayExtras)
+__device__ __forceinline__ float dist_near(const RayExtras& x, int ray) { return x.rayf ? x.rayf[(size_t)ray * RAYF + RF_NEAR] : x.near_far[2 * ray]; }
+__device__ __forceinline__ float dist_far(const RayExtras& x, int ray) { return x.rayf ? x.rayf[(size_t)ray * RAYF + RF_FAR] : x.near_far[2 * ray + 1]; }
+__device__ __forceinline__ double dist_ray_scale(const RayExtras& x, int ray) { return dist_ray_scale(dist_near(x, ray), dist_far(x, ray)); }
 
 // The prefix form, chunk by chunk: step() takes lane l's sample of the chunk (w_i, t_i, t_{i+1}; has_next = i < N - 1; lanes behind the
 // ray pass w = 0, t = 0) and leaves its m_i, d_i and the exclusive prefixes We_i, Se_i in index order.  Every lane of the wave calls it.

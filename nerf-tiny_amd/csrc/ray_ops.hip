@@ -3,9 +3,9 @@
 //   k_dirs_dvec         the direction-branch vector of queried points (nerf_hip_query)
 //   k_coarse            sigma -> weights (inclusive transmittance), C_coarse, inverse-CDF resampling
 //   k_merge             merge coarse+fine, five independent channel sorts, composite -> C_fine
-//   k_coarse_maps / k_merge_maps   the same, plus each ray's expected depth and opacity (nerf_hip_forward_maps)
-//   k_coarse_qmaps / k_merge_qmaps the maps kernels, plus each ray's quantile depths (nerf_hip_forward_quantiles, rule QD)
-//   k_coarse_dmaps / k_merge_dmaps the training maps kernels, plus each ray's distortion loss (nerf_hip_forward_distortion_train, rule DL)
+//   k_coarse_x / k_merge_x   the same kernel templates over the optional per-ray outputs of ONE extras record (kernels.h RayExtras):
+//                       each ray's expected depth and opacity (nerf_hip_forward_maps), with them its quantile depths (rule QD,
+//                       nerf_hip_forward_quantiles) or its distortion loss (rule DL, nerf_hip_forward_distortion_train)
 //   k_ray_loss          sum-of-squares loss and its gradient
 // One 64-lane wave owns one ray: the transmittance cumsum / CDF are wave scans (fp64 accumulator like
 // ATen's CPU cumsum, rounded to fp32 per element), searchsorted is a per-lane binary search in LDS and
@@ -50,34 +50,18 @@ __global__ __launch_bounds__(256) void k_coarse(const CoarseArgs a) {
   coarse_ray_stage(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); });
 }
 
-// k_coarse_maps: k_coarse that also stores each live ray's coarse depth and opacity to maps [B][4] columns 0, 1 (nerf_hip_forward_maps).  The
-// pointer is a kernel argument of its own, not a CoarseArgs field: CoarseArgs rides inside FwdFuse, the bf16 training kernels' argument.
-__global__ __launch_bounds__(256) void k_coarse_maps(const CoarseArgs a, float* maps) {
+// k_coarse_x: k_coarse with the optional per-ray outputs of the extras record x (kernels.h RayExtras), one instantiation per set asked for:
+//   <true>               each live ray's coarse depth and opacity to x.maps [B][4] columns 0, 1 (nerf_hip_forward_maps)
+//   <true, true>         ... and its coarse quantile depths (rule QD of include/nerf_hip.h) to row 0 of x.qdepth [B][2][nq] (nerf_hip_forward_quantiles)
+//   <true, false, true>  ... and its coarse distortion loss (rule DL) to column 0 of x.dist [B][2] (nerf_hip_forward_distortion_train)
+// The record is a kernel argument of its own, not part of CoarseArgs: CoarseArgs rides inside FwdFuse, the bf16 training kernels' argument.
+template <bool MAPS, bool QD = false, bool DL = false>
+__global__ __launch_bounds__(256) void k_coarse_x(const CoarseArgs a, const RayExtras x) {
   __shared__ float s_w[4][MAXN];
   __shared__ float s_cdf[4][MAXN];
   __shared__ float s_t[4][MAXN];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  coarse_ray_stage<true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps);
-}
-
-// k_coarse_qmaps: k_coarse_maps that also stores each live ray's coarse quantile depths (rule QD of include/nerf_hip.h) to row 0 of
-// qdepth [B][2][nq] (nerf_hip_forward_quantiles).  The quantiles and the pointer are kernel arguments of their own, for k_coarse_maps's reason.
-__global__ __launch_bounds__(256) void k_coarse_qmaps(const CoarseArgs a, float* maps, const QuantArgs qa, float* qdepth) {
-  __shared__ float s_w[4][MAXN];
-  __shared__ float s_cdf[4][MAXN];
-  __shared__ float s_t[4][MAXN];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  coarse_ray_stage<true, true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps, &qa, qdepth);
-}
-
-// k_coarse_dmaps: k_coarse_maps that also stores each live ray's coarse distortion loss (rule DL of include/nerf_hip.h) to column 0 of
-// dist [B][2] (nerf_hip_forward_distortion_train).  The pointer is a kernel argument of its own, for k_coarse_maps's reason.
-__global__ __launch_bounds__(256) void k_coarse_dmaps(const CoarseArgs a, float* maps, float* dist) {
-  __shared__ float s_w[4][MAXN];
-  __shared__ float s_cdf[4][MAXN];
-  __shared__ float s_t[4][MAXN];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  coarse_ray_stage<true, false, true>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, maps, nullptr, nullptr, dist);
+  coarse_ray_stage<MAPS, QD, DL>(a, blockIdx.x * 4 + wv, lane, s_w[wv], s_cdf[wv], s_t[wv], [] { __syncthreads(); }, &x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -95,33 +79,18 @@ __global__ __launch_bounds__(64) void k_merge(const MergeArgs a) {
   merge_ray_stage<WITH_IDX>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); });
 }
 
-// k_merge_maps: k_merge that also stores each ray's fine depth and opacity to maps [B][4] columns 2, 3 (nerf_hip_forward_maps; pointer passed
-// as for k_coarse_maps).  Both sort paths (registers at P = 256, LDS otherwise) end in the same merge_ray_composite.
-template <bool WITH_IDX>
-__global__ __launch_bounds__(64) void k_merge_maps(const MergeArgs a, float* maps) {
+// k_merge_x: k_merge with the optional per-ray outputs of the extras record x (passed as for k_coarse_x).  The same LDS; both sort paths
+// (registers at P = 256, LDS otherwise) and the joint mode end in the same merge_ray_composite.
+//   <WITH_IDX, true>           each ray's fine depth and opacity to x.maps [B][4] columns 2, 3 (nerf_hip_forward_maps, nerf_hip_forward_maps_train)
+//   <WITH_IDX, true, true>     ... and its fine quantile depths (rule QD) to row 1 of x.qdepth [B][2][nq] (nerf_hip_forward_quantiles)
+//   <true, true, false, true>  ... and its fine distortion loss (rule DL) to column 1 of x.dist [B][2]: the training form, which sorts with
+//                              slots (nerf_hip_forward_distortion_train)
+template <bool WITH_IDX, bool MAPS, bool QD = false, bool DL = false>
+__global__ __launch_bounds__(64) void k_merge_x(const MergeArgs a, const RayExtras x) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
   uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
-  merge_ray_stage<WITH_IDX, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps);
-}
-
-// k_merge_qmaps: k_merge_maps that also stores each ray's fine quantile depths (rule QD) to row 1 of qdepth [B][2][nq]
-// (nerf_hip_forward_quantiles).  Both sort paths and the joint mode end in the same merge_ray_composite, as for k_merge_maps.
-template <bool WITH_IDX>
-__global__ __launch_bounds__(64) void k_merge_qmaps(const MergeArgs a, float* maps, const QuantArgs qa, float* qdepth) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
-  uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
-  merge_ray_stage<WITH_IDX, true, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps, &qa, qdepth);
-}
-
-// k_merge_dmaps: the training k_merge_maps (sorts with slots) that also stores each ray's fine distortion loss (rule DL) to column 1 of
-// da.dist [B][2] (nerf_hip_forward_distortion_train).  Same LDS; both sort paths and the joint mode end in the same merge_ray_composite.
-__global__ __launch_bounds__(64) void k_merge_dmaps(const MergeArgs a, float* maps, const DistArgs da) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float* val = reinterpret_cast<float*>(smem_raw);                      // [5][P]
-  uint16_t* idx = reinterpret_cast<uint16_t*>(val + 5 * (size_t)a.P);  // [5][P]
-  merge_ray_stage<true, true, false, true>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, maps, nullptr, nullptr, &da);
+  merge_ray_stage<WITH_IDX, MAPS, QD, DL>(a, blockIdx.x, threadIdx.x, val, idx, [] { __syncthreads(); }, &x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -160,58 +129,25 @@ hipError_t launch_dirs_dvec(const float* dirs, int n, const float* w_dir, const 
   hipLaunchKernelGGL(k_dirs_dvec, dim3(n), dim3(128), 0, st, dirs, w_dir, b_dir, b_fold, dvec);
   return hipGetLastError();
 }
-hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, float* maps) {
-  if (maps) hipLaunchKernelGGL(k_coarse_maps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps);
-  else hipLaunchKernelGGL(k_coarse, dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+hipError_t launch_coarse(const CoarseArgs& a, hipStream_t st, const RayExtras* x) {
+  const dim3 grid((a.B + 3) / 4), block(256);  // one wave per ray; the LDS is static
+  if (!x || !x->maps) hipLaunchKernelGGL(k_coarse, grid, block, 0, st, a);
+  else if (x->dist) hipLaunchKernelGGL((k_coarse_x<true, false, true>), grid, block, 0, st, a, *x);
+  else if (x->qdepth) hipLaunchKernelGGL((k_coarse_x<true, true>), grid, block, 0, st, a, *x);
+  else hipLaunchKernelGGL((k_coarse_x<true>), grid, block, 0, st, a, *x);
   return hipGetLastError();
 }
-size_t merge_lds_bytes(int P) { return (size_t)5 * P * (sizeof(float) + sizeof(uint16_t)); }
-template <bool WITH_IDX>
-hipError_t launch_merge_maps(const MergeArgs& a, float* maps, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_maps<WITH_IDX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  hipLaunchKernelGGL(k_merge_maps<WITH_IDX>, dim3(a.B), dim3(64), lds, st, a, maps);
-  return hipGetLastError();
-}
-hipError_t launch_merge(const MergeArgs& a, hipStream_t st, float* maps) {
+// k_merge / k_merge_x: val [5][P] floats and idx [5][P] u16
+static size_t merge_lds_bytes(int P) { return (size_t)5 * P * (sizeof(float) + sizeof(uint16_t)); }
+constexpr size_t MERGE_LDS_DEFAULT = 48 * 1024;
+hipError_t launch_merge(const MergeArgs& a, hipStream_t st, const RayExtras* x) {
   const size_t lds = merge_lds_bytes(a.P);
-  if (maps) return (a.perm || a.joint) ? launch_merge_maps<true>(a, maps, lds, st) : launch_merge_maps<false>(a, maps, lds, st);
-  if (a.perm || a.joint) {  // (the joint-sort mode needs the depth channel's permutation, stored or not)
-    if (lds > 48 * 1024)
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-    hipLaunchKernelGGL(k_merge<true>, dim3(a.B), dim3(64), lds, st, a);
-  } else {
-    if (lds > 48 * 1024)
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-    hipLaunchKernelGGL(k_merge<false>, dim3(a.B), dim3(64), lds, st, a);
-  }
-  return hipGetLastError();
-}
-hipError_t launch_coarse_quantiles(const CoarseArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st) {
-  hipLaunchKernelGGL(k_coarse_qmaps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps, qa, qdepth);
-  return hipGetLastError();
-}
-template <bool WITH_IDX>
-hipError_t launch_merge_qmaps(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_qmaps<WITH_IDX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  hipLaunchKernelGGL(k_merge_qmaps<WITH_IDX>, dim3(a.B), dim3(64), lds, st, a, maps, qa, qdepth);
-  return hipGetLastError();
-}
-hipError_t launch_merge_quantiles(const MergeArgs& a, float* maps, const QuantArgs& qa, float* qdepth, hipStream_t st) {
-  const size_t lds = merge_lds_bytes(a.P);
-  return (a.perm || a.joint) ? launch_merge_qmaps<true>(a, maps, qa, qdepth, lds, st) : launch_merge_qmaps<false>(a, maps, qa, qdepth, lds, st);
-}
-hipError_t launch_coarse_dist(const CoarseArgs& a, float* maps, float* dist, hipStream_t st) {
-  hipLaunchKernelGGL(k_coarse_dmaps, dim3((a.B + 3) / 4), dim3(256), 0, st, a, maps, dist);
-  return hipGetLastError();
-}
-hipError_t launch_merge_dist(const MergeArgs& a, float* maps, const DistArgs& da, hipStream_t st) {
-  const size_t lds = merge_lds_bytes(a.P);
-  if (lds > 48 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_dmaps), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  hipLaunchKernelGGL(k_merge_dmaps, dim3(a.B), dim3(64), lds, st, a, maps, da);
-  return hipGetLastError();
+  const bool with_idx = a.perm || a.joint;  // (the joint-sort mode needs the depth channel's permutation, stored or not)
+  auto go = [&](auto kernel, const auto&... extras) { return launch_dyn_lds(kernel, dim3(a.B), dim3(64), lds, MERGE_LDS_DEFAULT, st, a, extras...); };
+  if (!x || !x->maps) return with_idx ? go(k_merge<true>) : go(k_merge<false>);
+  if (x->dist) return go(k_merge_x<true, true, false, true>, *x);  // (a training call: a.perm set)
+  if (x->qdepth) return with_idx ? go(k_merge_x<true, true, true>, *x) : go(k_merge_x<false, true, true>, *x);
+  return with_idx ? go(k_merge_x<true, true>, *x) : go(k_merge_x<false, true>, *x);
 }
 hipError_t launch_ray_loss(const float* Cc, const float* Cf, const float* Ct, int B, float* loss, float* dCc, float* dCf, hipStream_t st) {
   hipLaunchKernelGGL(k_ray_loss, dim3(1), dim3(1024), 0, st, Cc, Cf, Ct, B * 3, loss, dCc, dCf);

@@ -1,6 +1,10 @@
 // ray_parts.h -- the per-ray stages of the hot path as device functions of ONE 64-lane wave: coarse weights + C_coarse, inverse-CDF
-// resampling, the five channel sorts and the merged composite.  Used by their stand-alone kernels (k_coarse, k_merge: ray_ops.hip) and by the
-// fused small-batch kernel that renders a pair of rays in one workgroup (field_pair_bf16x.hip) -- one source, the same bits.
+// resampling, the five channel sorts and the merged composite.  Used by their stand-alone kernels (k_coarse, k_merge and their k_coarse_x /
+// k_merge_x forms with optional outputs: ray_ops.hip) and by the fused small-batch kernels (field_fwd_bf16.hip, field_fwd_bf16x.hip) -- one
+// source, the same bits.
+// The optional per-ray outputs (maps, quantile depths, distortion loss) come as ONE record, kernels.h RayExtras, behind the template flags
+// MAPS / QD / DL: a function reads the record's fields of a flag only inside that flag's `if constexpr`, so an instantiation without the flag
+// holds none of that code, and the plain forms (the fused callers', k_coarse's, k_merge's) pass no record at all.
 // None of these functions contains a workgroup barrier: callers whose workgroup is one wave per ray pass __syncthreads() as `sync`, callers
 // that run them on SOME waves of a bigger workgroup pass a wave-level fence.  MI355X / gfx950 only; built with -ffp-contract=off.
 #pragma once
@@ -99,16 +103,18 @@ __device__ __forceinline__ float ray0_spacing(float n0, float f0, int Nc) {
 // get_density (nerf.py:263-272) with delta = (far - near) / Nc (quirk Q5), color_cum (nerf.py:274-281): the ray's Nc coarse samples at
 // sigma[i], rgb[3 i + ch], t_c[i] (global or LDS) -> w, cdf, tc (LDS, this wave's), optionally w_c (global) and C_coarse[3]; lo / hi =
 // min / max of the cdf (nerf.py:240-241).  The caller orders the LDS writes before coarse_ray_resample's reads.
+// Returns W = the last element of the fp64 scan of w (the cdf's, before its rounding to fp32), which ray_quantile_depths takes over the
+// w / tc this function leaves in LDS (QD callers; everyone else drops it).
+// x / ray: the extras record (MAPS / DL only; the plain form passes none) and this ray's row in it, or ray < 0: nothing of it stored (a ray
+// behind the batch).
 // MAPS (nerf_hip_forward_maps): also the ray's coarse depth and opacity D_c = sum_i w_i t_c,i, A_c = sum_i w_i -- fp32 per lane, then wave_sum,
-// as the colour sums -- stored by lane 0 to maps_out[0..1] (null: nothing stored).  Without MAPS the code is the colour-only one.
-// QD (nerf_hip_forward_quantiles): also hands out W = the last element of the fp64 scan of w (the cdf's, before its rounding to fp32) in
-// W_out, for ray_quantile_depths over the w / tc this function leaves in LDS.
+// as the colour sums -- stored by lane 0 to columns 0, 1 of x->maps (null: nothing stored).  Without MAPS the code is the colour-only one.
 // DL (nerf_hip_forward_distortion_train): also the coarse pass's distortion loss L_c (rule DL: t_c with these weights), one fp64 accumulation
-// per sample over two more wave scans (ray_dist.h), stored by lane 0 to dist_out[0] (null: nothing stored).
-template <bool MAPS = false, bool QD = false, bool DL = false>
-__device__ __forceinline__ void coarse_ray_weights(const float* sigma, const float* rgb, const float* t_c, float near, float far, int Nc, int lane,
-                                                   float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out,
-                                                   float* maps_out = nullptr, double* W_out = nullptr, float* dist_out = nullptr) {
+// per sample over two more wave scans (ray_dist.h), stored by lane 0 to column 0 of x->dist (null: nothing stored).
+template <bool MAPS = false, bool DL = false>
+__device__ __forceinline__ double coarse_ray_weights(const float* sigma, const float* rgb, const float* t_c, float near, float far, int Nc, int lane,
+                                                     float* w, float* cdf, float* tc, float* w_c_out, float* C_out, float& lo_out, float& hi_out,
+                                                     const RayExtras* x = nullptr, int ray = -1) {
   const float delta_c = (far - near) / (float)Nc;
   double carry = 0.0, carry2 = 0.0;
   DistScan dsc;        // (DL only)
@@ -164,16 +170,16 @@ __device__ __forceinline__ void coarse_ray_weights(const float* sigma, const flo
   if constexpr (MAPS) {
     dsum = wave_sum(dsum);
     asum = wave_sum(asum);
-    if (lane == 0 && maps_out) {
-      maps_out[0] = dsum;
-      maps_out[1] = asum;
+    if (lane == 0 && ray >= 0 && x->maps) {
+      x->maps[(size_t)ray * 4] = dsum;
+      x->maps[(size_t)ray * 4 + 1] = asum;
     }
   }
-  if constexpr (QD) *W_out = carry2;
   if constexpr (DL) {
     const double L = dist_ray_scale(near, far) * wave_sum_f64(dacc);
-    if (lane == 0 && dist_out) dist_out[0] = (float)L;
+    if (lane == 0 && ray >= 0 && x->dist) x->dist[(size_t)ray * 2] = (float)L;
   }
+  return carry2;
 }
 
 // resample (nerf.py:225-261): u_j = lo + j * ((hi - lo)/(Nf+1)), j = 1..Nf (numpy.linspace(lo, hi, Nf+2)[1:-1] in fp32, nerf.py:243-246),
@@ -371,20 +377,17 @@ __device__ __forceinline__ void merge_channel_job(const MergeArgs& a, const int 
 template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
                                                     float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret = nullptr,
-                                                    float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr,
-                                                    double dist_r = 0.0, float* dist_out = nullptr);
+                                                    const RayExtras* x = nullptr, int ray = 0);
 
 // nerf.py:302-321 behind the load: val [5][P] (channel 0 = t, 1..3 = rgb, 4 = sigma; slots >= N padded with NaN) and, WITH_IDX, idx [5][P]
 // = the original slot, in LDS -> five independent ascending channel sorts (quirk Q1), delta_i = t_{i+1} - t_i with the last = `last`,
-// weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).  MAPS: also the fine depth and
-// opacity to maps_out[0..1], QD: also the fine quantile depths to q_out[0..nq-1], DL: also the fine distortion loss to dist_out[0]
-// (merge_ray_composite).
+// weights, C_fine[3]; optionally w [N], the sorted bundle [N][5] and the permutations perm [5][N] (global).  MAPS / QD / DL: also the fine
+// depth and opacity / quantile depths / distortion loss to row `ray` of the extras record x (merge_ray_composite).
 struct MergeNoFix { __device__ __forceinline__ void operator()() const {} };
 template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false, class Sync, class PostSort = MergeNoFix>
 __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* idx, int P, int N, float last, int lane, float* w_out, float* bundle_out,
                                                          uint16_t* perm_out, float* C_out, Sync&& sync, PostSort&& post_sort = MergeNoFix{},
-                                                         float* maps_out = nullptr, const QuantArgs* qa = nullptr, float* q_out = nullptr,
-                                                         double dist_r = 0.0, float* dist_out = nullptr) {
+                                                         const RayExtras* x = nullptr, int ray = 0) {
   if (P == 256) {  // the usual size (64 + 128 samples): the whole network in registers
     sort256_regs<WITH_IDX>(val, idx, lane, sync);
   } else
@@ -418,24 +421,23 @@ __device__ __forceinline__ void merge_ray_sort_composite(float* val, uint16_t* i
     }
   }
   post_sort();  // (the joint-sort mode re-fills channels 1..4 by the depth channel's permutation here)
-  merge_ray_composite<WITH_IDX, MAPS, QD, DL>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, maps_out, qa, q_out,
-                                              dist_r, dist_out);
+  merge_ray_composite<WITH_IDX, MAPS, QD, DL>(val, idx, P, N, last, lane, w_out, bundle_out, perm_out, C_out, nullptr, x, ray);
 }
 
 // the composite over the SORTED channels val [5][P] (and idx): delta_i = t_{i+1} - t_i with the last = `last`, weights, C_fine[3]
 // MAPS (nerf_hip_forward_maps): also D_f = sum_i w_i t_s,i over the sorted depth channel t_s (in the reference's mode the channels are sorted
 // independently, quirk Q1: D_f is t composited like a colour channel; in the joint-sort mode the physical expected depth) and A_f = sum_i w_i,
-// fp32 per lane then wave_sum as the colour sums, stored by lane 0 to maps_out[0..1] (null: nothing stored)
+// fp32 per lane then wave_sum as the colour sums, stored by lane 0 to columns 2, 3 of row `ray` of x->maps (null: nothing stored)
 // QD (nerf_hip_forward_quantiles): also the quantile depths of the fine pass (rule QD: the sorted depth channel t_s with these weights) to
-// q_out[0..nq-1].  The loop also forms the fp64 scan of w for its last element W and parks w_i in the ray's own sigma slot val[4 P + i],
+// row 1 of x->qdepth [ray].  The loop also forms the fp64 scan of w for its last element W and parks w_i in the ray's own sigma slot val[4 P + i],
 // which the lane has just read and nothing reads afterwards; ray_quantile_depths then takes w from there and t_s from channel 0.
 // DL (nerf_hip_forward_distortion_train): also the fine pass's distortion loss L_f (rule DL: the sorted depth channel t_s with these weights,
-// dist_r = the ray's 1 / (far - near)): one fp64 accumulation per sample over two more wave scans (ray_dist.h), stored by lane 0 to
-// dist_out[0] (null: nothing stored).  The last interval's `last` never enters it.
+// scaled by the ray's 1 / (far - near) from x's ray bounds): one fp64 accumulation per sample over two more wave scans (ray_dist.h), stored
+// by lane 0 to column 1 of x->dist [ray] (null: nothing stored).  The last interval's `last` never enters it.
 template <bool WITH_IDX, bool MAPS, bool QD, bool DL>
 __device__ __forceinline__ void merge_ray_composite(const float* val, const uint16_t* idx, int P, int N, float last, int lane, float* w_out,
-                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, float* maps_out,
-                                                    const QuantArgs* qa, float* q_out, double dist_r, float* dist_out) {
+                                                    float* bundle_out, uint16_t* perm_out, float* C_out, float* c_ret, const RayExtras* x,
+                                                    int ray) {
   double carry = 0.0;
   double carry_w = 0.0;  // (QD only)
   DistScan dsc;          // (DL only)
@@ -497,15 +499,15 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
   if constexpr (MAPS) {
     dsum = wave_sum(dsum);
     asum = wave_sum(asum);
-    if (lane == 0 && maps_out) {
-      maps_out[0] = dsum;
-      maps_out[1] = asum;
+    if (lane == 0 && x->maps) {
+      x->maps[(size_t)ray * 4 + 2] = dsum;
+      x->maps[(size_t)ray * 4 + 3] = asum;
     }
   }
-  if constexpr (QD) ray_quantile_depths(val + 4 * P, val, N, carry_w, lane, *qa, q_out);
+  if constexpr (QD) ray_quantile_depths(val + 4 * P, val, N, carry_w, lane, x->qa, x->qdepth ? x->qdepth + ((size_t)ray * 2 + 1) * x->qa.nq : nullptr);
   if constexpr (DL) {
-    const double L = dist_r * wave_sum_f64(dacc);
-    if (lane == 0 && dist_out) dist_out[0] = (float)L;
+    const double L = dist_ray_scale(*x, ray) * wave_sum_f64(dacc);
+    if (lane == 0 && x->dist) x->dist[(size_t)ray * 2 + 1] = (float)L;
   }
 }
 
@@ -513,12 +515,13 @@ __device__ __forceinline__ void merge_ray_composite(const float* val, const uint
 // and the small-batch epilogues of the bf16 training forward kernels (field_fwd_bf16.hip) are these functions ----
 
 // k_coarse for ray `ray_raw` (rays behind the batch: computed on a copy of the last ray, nothing stored); w / cdf / tc: Nc floats of LDS each.
-// MAPS (k_coarse_maps): maps [B][4] also gets the ray's (D_c, A_c) in its columns 0, 1
-// QD (k_coarse_qmaps): qdepth [B][2][nq] also gets the ray's coarse quantile depths in its row 0 (rays behind the batch store nothing)
-// DL (k_coarse_dmaps): dist [B][2] also gets the ray's coarse distortion loss in its column 0 (rays behind the batch store nothing)
+// x: the extras record of k_coarse_x (with any of the flags; the plain form passes none).  Rays behind the batch store nothing of it either.
+// MAPS: x->maps [B][4] also gets the ray's (D_c, A_c) in its columns 0, 1
+// QD: x->qdepth [B][2][nq] also gets the ray's coarse quantile depths in its row 0
+// DL: x->dist [B][2] also gets the ray's coarse distortion loss in its column 0
 template <bool MAPS = false, bool QD = false, bool DL = false, class Sync>
 __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int ray_raw, const int lane, float* w, float* cdf, float* tc, Sync&& sync,
-                                                 float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr, float* dist = nullptr) {
+                                                 const RayExtras* x = nullptr) {
   const bool live = ray_raw < a.B;
   const int ray = live ? ray_raw : a.B - 1;
   float near, far;
@@ -538,26 +541,24 @@ __device__ __forceinline__ void coarse_ray_stage(const CoarseArgs& a, const int 
   }
   const size_t g0 = (size_t)ray * a.Nc;
   float lo, hi;
-  double W = 0.0;  // (QD only)
-  coarse_ray_weights<MAPS, QD, DL>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
-                               (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi,
-                               (MAPS && live && maps) ? maps + (size_t)ray * 4 : nullptr, QD ? &W : nullptr,
-                               (DL && live && dist) ? dist + (size_t)ray * 2 : nullptr);
+  [[maybe_unused]] const double W =  // (QD only)
+      coarse_ray_weights<MAPS, DL>(a.sigma + g0, a.rgb + g0 * 3, a.t_c + g0, near, far, a.Nc, lane, w, cdf, tc, (live && a.w_c) ? a.w_c + g0 : nullptr,
+                                   (live && a.C_coarse) ? a.C_coarse + (size_t)ray * 3 : nullptr, lo, hi, x, live ? ray : -1);
   sync();
-  if constexpr (QD) ray_quantile_depths(w, tc, a.Nc, W, lane, *qa, (live && qdepth) ? qdepth + (size_t)ray * 2 * qa->nq : nullptr);
+  if constexpr (QD) ray_quantile_depths(w, tc, a.Nc, W, lane, x->qa, (live && x->qdepth) ? x->qdepth + (size_t)ray * 2 * x->qa.nq : nullptr);
   const bool bad = coarse_ray_resample(w, cdf, tc, lo, hi, delta0, a.Nc, a.Nf, lane, live ? a.t_f + (size_t)ray * a.Nf : nullptr);
   if (live && bad && a.status) atomicOr(a.status, 1u);
   if (live && bad && a.sticky) atomicOr(a.sticky, 1u);
 }
 
 // k_merge for ray `ray` (< B): load the ray's coarse + fine samples into val [5][P] (idx [5][P]: original slots), sort, composite.
-// MAPS (k_merge_maps): maps [B][4] also gets the ray's (D_f, A_f) in its columns 2, 3
-// QD (k_merge_qmaps): qdepth [B][2][nq] also gets the ray's fine quantile depths in its row 1
-// DL (k_merge_dmaps): da->dist [B][2] also gets the ray's fine distortion loss in its column 1; near / far from da's ray records or near_far
+// x: the extras record of k_merge_x (with any of the flags; the plain form passes none)
+// MAPS: x->maps [B][4] also gets the ray's (D_f, A_f) in its columns 2, 3
+// QD: x->qdepth [B][2][nq] also gets the ray's fine quantile depths in its row 1
+// DL: x->dist [B][2] also gets the ray's fine distortion loss in its column 1; near / far from x's ray records or near_far
 template <bool WITH_IDX, bool MAPS = false, bool QD = false, bool DL = false, class Sync>
 __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ray, const int lane, float* val, uint16_t* idx, Sync&& sync,
-                                                float* maps = nullptr, const QuantArgs* qa = nullptr, float* qdepth = nullptr,
-                                                const DistArgs* da = nullptr) {
+                                                const RayExtras* x = nullptr) {
   const int P = a.P, N = a.Nc + a.Nf;
   // load: channel 0 = t, 1..3 = rgb, 4 = sigma
   for (int i = lane; i < P; i += 64) {
@@ -596,13 +597,9 @@ __device__ __forceinline__ void merge_ray_stage(const MergeArgs& a, const int ra
       }
     }
   };
-  double dist_r = 0.0;  // (DL only)
-  if constexpr (DL) dist_r = dist_ray_scale(dist_near(*da, ray), dist_far(*da, ray));
   merge_ray_sort_composite<WITH_IDX, MAPS, QD, DL>(val, idx, P, N, a.last, lane, a.w ? a.w + gN : nullptr, a.bundle ? a.bundle + gN * 5 : nullptr,
-                                               (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync, joint_fix,
-                                               (MAPS && maps) ? maps + (size_t)ray * 4 + 2 : nullptr, qa,
-                                               (QD && qdepth) ? qdepth + ((size_t)ray * 2 + 1) * qa->nq : nullptr, dist_r,
-                                               (DL && da->dist) ? da->dist + (size_t)ray * 2 + 1 : nullptr);
+                                                   (WITH_IDX && a.perm) ? a.perm + (size_t)ray * 5 * N : nullptr, a.C_fine + (size_t)ray * 3, sync,
+                                                   joint_fix, x, ray);
 }
 
 // ---- ray_loss (nerf.py:325-331) in two pieces, bit-compatible with k_ray_loss (ray_ops.hip) ----

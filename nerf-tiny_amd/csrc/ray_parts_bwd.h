@@ -1,6 +1,8 @@
-// ray_parts_bwd.h -- backward of the per-ray stages as device functions of ONE 64-lane wave (k_merge_bwd / k_coarse_bwd of ray_ops_bwd.hip are
-// made of them; the bf16 chain kernels call them as prologues for small batches: field_bwd_bf16.hip).  No workgroup barrier inside: the
-// caller passes the `sync` that fits its workgroup.  MI355X / gfx950 only; built with -ffp-contract=off.
+// ray_parts_bwd.h -- backward of the per-ray stages as device functions of ONE 64-lane wave (k_merge_bwd / k_coarse_bwd and their _x forms
+// of ray_ops_bwd.hip are made of them; the bf16 chain kernels call them as prologues for small batches: field_bwd_bf16.hip).  No workgroup
+// barrier inside: the caller passes the `sync` that fits its workgroup.  The upstreams of the optional per-ray outputs come in the extras
+// record (kernels.h RayExtras: dmaps, ddist) behind the flags MAPS / DL; the plain forms pass none.  MI355X / gfx950 only; built with
+// -ffp-contract=off.
 #pragma once
 #include "kernels.h"
 #include "ray_dist.h"
@@ -28,16 +30,16 @@ __device__ __forceinline__ double wave_suffix_scan_d(double v, int lane) {
 // backward of the merged composite + channel sorts for ONE ray by one wave (nerf.py:302-321); sm_f: 4 * (Nc + Nf) floats of LDS of this wave
 // (MAPS: 5 * (Nc + Nf)); `sync` orders this wave's LDS writes before its reads (a one-wave workgroup passes __syncthreads, a wave of a bigger
 // workgroup a wave fence).
-// MAPS (nerf_hip_backward_maps): dmaps [B][4] holds each ray's upstream (gD_c, gA_c, gD_f, gA_f); the fine maps add
+// MAPS (nerf_hip_backward_maps): x->dmaps [B][4] holds each ray's upstream (gD_c, gA_c, gD_f, gA_f); the fine maps add
 // gD_f t_s,k + gA_f to dw_k (pass 1) and gD_f w_k to d t_s,k (pass 3, un-sorted through perm[0] as the delta terms), each as a separate
 // addition behind the colour-only expression.  Without MAPS the code is the colour-only one.
-// DL (with MAPS; nerf_hip_backward_distortion): da->ddist [B][2] column 1 holds the ray's upstream g of L_f (rule DL of
+// DL (with MAPS; nerf_hip_backward_distortion): x->ddist [B][2] column 1 holds the ray's upstream g of L_f (rule DL of
 // include/nerf_hip.h).  Between pass 1 and pass 2 a fix-up pass over the w_k that pass 1 left in LDS (ray_dist.h: the totals W, S, then the
 // prefixes) adds fp32(g dL/dw_k) to dw_k -- one more fp32 addition behind the maps term, dw_k w_k re-formed from the sum -- and parks
 // fp32(g dL/dt_k) in a sixth array, which pass 3 adds to d t_s,k behind the maps term.  sm_f: 6 * (Nc + Nf) floats.
 template <bool MAPS = false, bool DL = false, class Sync>
 __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int ray, const int lane, float* sm_f, Sync&& sync,
-                                              const float* dmaps = nullptr, const DistArgs* da = nullptr) {
+                                              const RayExtras* x = nullptr) {
   static_assert(MAPS || !DL, "the distortion terms extend the maps instantiation");
   const int N = a.Nc + a.Nf;
   float* s_te = sm_f;          // T_k * exp(-s_k)
@@ -51,9 +53,9 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
   const uint16_t* pm = a.perm + (size_t)ray * 5 * N;
   float gD = 0.f, gA = 0.f;  // (MAPS only)
   if constexpr (MAPS) {
-    if (!DL || dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
-      gD = dmaps[(size_t)ray * 4 + 2];
-      gA = dmaps[(size_t)ray * 4 + 3];
+    if (!DL || x->dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
+      gD = x->dmaps[(size_t)ray * 4 + 2];
+      gA = x->dmaps[(size_t)ray * 4 + 3];
     }
   }
 
@@ -93,8 +95,8 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
   }
   sync();
   if constexpr (DL) {
-    const double r = dist_ray_scale(dist_near(*da, ray), dist_far(*da, ray));
-    dist_grad_terms(s_w, [&](int i) { return bun[(size_t)i * 5]; }, N, r, da->ddist[(size_t)ray * 2 + 1], lane,
+    const double r = dist_ray_scale(*x, ray);
+    dist_grad_terms(s_w, [&](int i) { return bun[(size_t)i * 5]; }, N, r, x->ddist[(size_t)ray * 2 + 1], lane,
                     [](double x, int l) { return wave_incl_scan_d(x, l); },
                     [&](int i, float gw, float gt) {  // (lane i % 64 wrote s_dw[i] in pass 1 and reads it in pass 2)
                       const float dw = s_dw[i] + gw;
@@ -139,14 +141,14 @@ __device__ __forceinline__ void merge_bwd_ray(const MergeBwdArgs& a, const int r
 
 
 // backward of resampling + coarse composite for ONE ray by one wave (nerf.py:225-281); w: 5 * Nc floats, ks: Nf u16 of LDS of this wave.
-// MAPS (nerf_hip_backward_maps): the coarse maps add gD_c t_c,i + gA_c (dmaps [B][4] columns 0, 1) to dw_i as a separate addition
+// MAPS (nerf_hip_backward_maps): the coarse maps add gD_c t_c,i + gA_c (x->dmaps [B][4] columns 0, 1) to dw_i as a separate addition
 // behind the colour-only sum; t_c carries no gradient.  Without MAPS the code is the colour-only one.
-// DL (with MAPS; nerf_hip_backward_distortion): ddist [B][2] column 0 holds the ray's upstream g of L_c (rule DL).  Before the last loop a
+// DL (with MAPS; nerf_hip_backward_distortion): x->ddist [B][2] column 0 holds the ray's upstream g of L_c (rule DL).  Before the last loop a
 // pass over the recomputed w (ray_dist.h) leaves fp32(g dL/dw_i) in the cdf slots, which nothing reads any more, and the loop adds it to
 // dw_i as one more fp32 addition behind the maps term; dL/dt_c is dropped (t_c carries no gradient).  Same LDS.
 template <bool MAPS = false, bool DL = false, class Sync>
 __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int ray, const bool live, const int lane, float* w, uint16_t* ks, Sync&& sync,
-                                               const float* dmaps = nullptr, const float* ddist = nullptr) {
+                                               const RayExtras* x = nullptr) {
   static_assert(MAPS || !DL, "the distortion terms extend the maps instantiation");
   const int Nc = a.Nc, Nf = a.Nf;
   float near, far;
@@ -248,14 +250,14 @@ __device__ __forceinline__ void coarse_bwd_ray(const CoarseBwdArgs& a, const int
   const float dC0 = a.dC_c[(size_t)ray * 3], dC1 = a.dC_c[(size_t)ray * 3 + 1], dC2 = a.dC_c[(size_t)ray * 3 + 2];
   float gD = 0.f, gA = 0.f;  // (MAPS only)
   if constexpr (MAPS) {
-    if (!DL || dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
-      gD = dmaps[(size_t)ray * 4];
-      gA = dmaps[(size_t)ray * 4 + 1];
+    if (!DL || x->dmaps) {  // (the distortion stage entry may come without dmaps: zeros)
+      gD = x->dmaps[(size_t)ray * 4];
+      gA = x->dmaps[(size_t)ray * 4 + 1];
     }
   }
   if constexpr (DL) {  // (the sync above has ordered the gather loop's reads of cdf before these writes)
     const float* tr = a.t_c + (size_t)ray * Nc;
-    dist_grad_terms(w, [&](int i) { return tr[i]; }, Nc, dist_ray_scale(near, far), ddist[(size_t)ray * 2], lane,
+    dist_grad_terms(w, [&](int i) { return tr[i]; }, Nc, dist_ray_scale(near, far), x->ddist[(size_t)ray * 2], lane,
                     [](double x, int l) { return wave_incl_scan_d(x, l); }, [&](int i, float gw, float) { cdf[i] = gw; });
   }
   // dw_i = suffix_sum(dcdf)_i + dwn_{i-1} + rgb_i . dC_c (+ gD_c t_c,i + gA_c) (+ g dL_c/dw_i) ; then composite backward

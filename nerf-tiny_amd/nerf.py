@@ -104,29 +104,23 @@ def _forward_call(model, need_grad, row, col, pb, K9, ray0, params, maps=None, q
     C_f = torch.empty(B, 3, dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     wptr = _abi.ptr_array(params)
+    # the entry and its arguments behind the stream, from the outputs asked for; maps (when asked for) sits in front of the workspace
+    lib = _abi.lib()
     if maps is None:
-        _abi.check(_abi.lib().nerf_hip_forward(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9,
-                                               ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), call_flags, stream))
+        fn, tail = lib.nerf_hip_forward, ()
     elif quant is not None:
         q, Q = quant
-        _abi.check(_abi.lib().nerf_hip_forward_quantiles(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA,
-                                                         C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags,
-                                                         stream, _abi.f32_array(q), len(q), Q.data_ptr()))
+        fn, tail = lib.nerf_hip_forward_quantiles, (_abi.f32_array(q), len(q), Q.data_ptr())
     elif norm is not None:
         passes, Nrm = norm
         nws = model._normals_workspace(B, dev)
-        _abi.check(_abi.lib().nerf_hip_forward_normals(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA,
-                                                       C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags,
-                                                       stream, passes, Nrm.data_ptr(), nws.data_ptr(), nws.numel()))
+        fn, tail = lib.nerf_hip_forward_normals, (passes, Nrm.data_ptr(), nws.data_ptr(), nws.numel())
     elif dist is not None:
-        _abi.check(_abi.lib().nerf_hip_forward_distortion_train(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf,
-                                                                LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(), maps.data_ptr(), ws.data_ptr(),
-                                                                ws.numel(), call_flags, stream, dist.data_ptr()))
+        fn, tail = lib.nerf_hip_forward_distortion_train, (dist.data_ptr(),)
     else:
-        fn = _abi.lib().nerf_hip_forward_maps_train if need_grad else _abi.lib().nerf_hip_forward_maps
-        _abi.check(fn(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
-                      maps.data_ptr(), ws.data_ptr(), ws.numel(), call_flags, stream))
+        fn, tail = (lib.nerf_hip_forward_maps_train if need_grad else lib.nerf_hip_forward_maps), ()
+    _abi.check(fn(wptr, row.data_ptr(), col.data_ptr(), pb.data_ptr(), K9, ray0, B, Nc, Nf, LAST_DELTA, C_c.data_ptr(), C_f.data_ptr(),
+                  *(() if maps is None else (maps.data_ptr(),)), ws.data_ptr(), ws.numel(), call_flags, stream, *tail))
     if model._frozen and not need_grad:
         model._packed.add((ws.data_ptr(), flags))
     model._last_ws = ws
@@ -200,55 +194,34 @@ class _RenderFn(torch.autograd.Function):
 
 
 class _RenderMapsFn(torch.autograd.Function):
-    """A training forward with maps (nerf_hip_forward_maps_train) -> (C_coarse, C_fine, maps [B, 4]); its backward is ONE
-    nerf_hip_backward_maps call.  An upstream gradient autograd hands over as None counts as zero."""
+    """A training forward with maps (with_dist False: nerf_hip_forward_maps_train) -> (C_coarse, C_fine, maps [B, 4]), or with maps and the
+    distortion loss (with_dist True: nerf_hip_forward_distortion_train) -> (C_coarse, C_fine, maps, dist [B, 2]).  Its backward is ONE
+    nerf_hip_backward_maps / nerf_hip_backward_distortion call (DESIGN.md sections 3l, 3m).  An upstream gradient autograd hands over as
+    None counts as zero."""
 
     @staticmethod
-    def forward(ctx, model, row, col, pb, K9, ray0, *params):
+    def forward(ctx, model, with_dist, row, col, pb, K9, ray0, *params):
         ctx.set_materialize_grads(False)
         M = torch.empty(row.shape[0], 4, dtype=torch.float32, device=row.device)
-        C_c, C_f, ws, flags = _forward_call(model, True, row, col, pb, K9, ray0, params, maps=M)
-        _record(ctx, model, flags, ws, row.shape[0], params, ray0)
-        return C_c, C_f, M
-
-    @staticmethod
-    def backward(ctx, dC_c, dC_f, dM):
-        B = ctx.B
-        dev = ctx.params[0].device
-        up = [torch.zeros(B, n, dtype=torch.float32, device=dev) if g is None else g.contiguous().float()
-              for g, n in ((dC_c, 3), (dC_f, 3), (dM, 4))]
-        model = ctx.model
-        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_maps(
-            wp, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(), ctx.ray0, B, model.num_coarse, model.num_fine, LAST_DELTA, gp,
-            ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early)))
-        return (None, None, None, None, None, None, *grads)
-
-
-class _RenderDistFn(torch.autograd.Function):
-    """A training forward with maps and the distortion loss (nerf_hip_forward_distortion_train) -> (C_coarse, C_fine, maps [B, 4],
-    dist [B, 2]); its backward is ONE nerf_hip_backward_distortion call.  An upstream gradient autograd hands over
-    as None counts as zero."""
-
-    @staticmethod
-    def forward(ctx, model, row, col, pb, K9, ray0, *params):
-        ctx.set_materialize_grads(False)
-        M = torch.empty(row.shape[0], 4, dtype=torch.float32, device=row.device)
-        D = torch.empty(row.shape[0], 2, dtype=torch.float32, device=row.device)
+        D = torch.empty(row.shape[0], 2, dtype=torch.float32, device=row.device) if with_dist else None
         C_c, C_f, ws, flags = _forward_call(model, True, row, col, pb, K9, ray0, params, maps=M, dist=D)
         _record(ctx, model, flags, ws, row.shape[0], params, ray0)
-        return C_c, C_f, M, D
+        ctx.with_dist = with_dist
+        return (C_c, C_f, M, D) if with_dist else (C_c, C_f, M)
 
     @staticmethod
-    def backward(ctx, dC_c, dC_f, dM, dD):
+    def backward(ctx, dC_c, dC_f, dM, dD=None):
         B = ctx.B
         dev = ctx.params[0].device
+        with_dist = ctx.with_dist
         up = [torch.zeros(B, n, dtype=torch.float32, device=dev) if g is None else g.contiguous().float()
-              for g, n in ((dC_c, 3), (dC_f, 3), (dM, 4), (dD, 2))]
+              for g, n in ((dC_c, 3), (dC_f, 3), (dM, 4)) + (((dD, 2),) if with_dist else ())]
         model = ctx.model
-        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(_abi.lib().nerf_hip_backward_distortion(
+        fn = _abi.lib().nerf_hip_backward_distortion if with_dist else _abi.lib().nerf_hip_backward_maps
+        grads = _backward_call(ctx, lambda wp, gp, stream, early: _abi.check(fn(
             wp, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(), ctx.ray0, B, model.num_coarse, model.num_fine, LAST_DELTA, gp,
-            ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early, up[3].data_ptr())))
-        return (None, None, None, None, None, None, *grads)
+            ctx.ws.data_ptr(), ctx.ws.numel(), ctx.flags, stream, early, *((up[3].data_ptr(),) if with_dist else ()))))
+        return (None, None, None, None, None, None, None, *grads)
 
 
 def field_normals(g):
@@ -460,7 +433,7 @@ class NeRFModel(nn.Module):
         """maps=True: nerf_hip_forward_maps, -> (C_coarse, C_fine, maps [B, 4]) -- with no graph unless `train_maps` is set and grad is
         enabled for a parameter (then nerf_hip_forward_maps_train under _RenderMapsFn).  quantiles (a tuple of floats; maps=True, never
         recorded): nerf_hip_forward_quantiles, -> (C_coarse, C_fine, maps, Q [B, 2, nq]).  distortion (forward has checked that a graph is
-        recorded): nerf_hip_forward_distortion_train under _RenderDistFn, -> (C_coarse, C_fine, maps, dist [B, 2]).  normals (the passes of
+        recorded): nerf_hip_forward_distortion_train under _RenderMapsFn too, -> (C_coarse, C_fine, maps, dist [B, 2]).  normals (the passes of
         rule NM, bit 0 coarse, bit 1 fine; maps=True, never recorded): nerf_hip_forward_normals, with Nrm [B, 2, 3] appended to the return --
         rows not asked for NaN; with quantiles too, a quantile call runs on the same rays first, for Q alone (same colour and maps bits)."""
         dev = ps[0].device
@@ -472,9 +445,9 @@ class NeRFModel(nn.Module):
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in ps)  # grad mode is off inside Function.forward
         Q = None
         if distortion:
-            C_c, C_f, M, Q = _RenderDistFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)  # (the fourth output: dist here, the quantile depths below)
+            C_c, C_f, M, Q = _RenderMapsFn.apply(self, True, row_d, col_d, pb, K9, ray0, *ps)  # (the fourth output: dist here, the quantile depths below)
         elif maps and train_maps and need_grad:
-            C_c, C_f, M = _RenderMapsFn.apply(self, row_d, col_d, pb, K9, ray0, *ps)
+            C_c, C_f, M = _RenderMapsFn.apply(self, False, row_d, col_d, pb, K9, ray0, *ps)
         elif maps:
             M = torch.empty(row_d.shape[0], 4, dtype=torch.float32, device=dev)
             if quantiles is not None:

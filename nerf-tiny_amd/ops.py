@@ -714,242 +714,183 @@ def image_metrics(pred, gt, ws=None):
     return mse, ssim
 
 
-def coarse_composite(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
-    """-> w_c[B,Nc], C_coarse[B,3], t_f[B,Nf], status(int)"""
+# ---- the per-ray stages on their own (the stage entries of include/nerf_hip.h).  Four helpers, one per stage, allocate the outputs, fill
+# the optional ones with their initial values and make the library call; the public functions below say which entry and which optional
+# outputs they stand for.  The optional outputs are those of the library's extras record: maps, quantile depths, distortion loss ----
+_NAN = float("nan")
+
+
+def _near_far(near, far, dev):
+    return torch.stack((near, far), dim=1).contiguous().to(dev)
+
+
+def _ptr(t):
+    return None if t is None else t.contiguous().data_ptr()
+
+
+def _coarse_stage(entry, t_c, sigma_c, rgb_c, near, far, delta0, Nf, rays=None, maps=False, tail=(), who="coarse_composite"):
+    """One forward coarse stage call `entry` of the first `rays` rays (default: all) -> w_c, C_coarse, t_f, status(int), maps[B,4] or None
+    (NaN where the kernel does not write); tail: the entry's arguments behind the stream"""
     B, Nc = t_c.shape
+    rays = B if rays is None else int(rays)
+    if not 1 <= rays <= B:
+        raise ValueError(f"{who}: 1 <= rays <= B")
     dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
+    nf = _near_far(near, far, dev)
     w_c = torch.empty(B, Nc, device=dev)
     C_c = torch.empty(B, 3, device=dev)
     t_f = torch.empty(B, Nf, device=dev)
+    M = torch.full((B, 4), _NAN, device=dev) if maps else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
-                                                    rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), B, Nc, Nf,
-                                                    w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(),
-                                                    _stream(t_c)))
-    return w_c, C_c, t_f, int(status.item())
+    args = [_ptr(t_c), _ptr(sigma_c), _ptr(rgb_c), nf.data_ptr(), float(delta0), rays, Nc, Nf, w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(),
+            status.data_ptr()]
+    _abi.check(getattr(_abi.lib(), entry)(*args, *([M.data_ptr()] if maps else []), _stream(t_c), *tail))
+    return w_c, C_c, t_f, int(status.item()), M
 
 
-def merge_composite(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last=1e-4):
-    """-> bundle[B,N,5], w[B,N], C_fine[B,3]"""
+def _merge_stage(entry, t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last, train=None, tail=()):
+    """One forward merge stage call `entry` -> bundle, w, C_fine, perm, maps.  train: None for the inference entry, else (perm, joint, maps)
+    -- whether the call gets perm[B,5,N] int16 (starting at -1) and maps[B,4] (starting at NaN), which come back as None otherwise"""
     B, Nc = t_c.shape
     Nf = t_f.shape[1]
     dev = t_c.device
     bundle = torch.empty(B, Nc + Nf, 5, device=dev)
     w = torch.empty(B, Nc + Nf, device=dev)
     C_f = torch.empty(B, 3, device=dev)
-    _abi.check(_abi.lib().nerf_hip_merge_composite(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
-                                                   sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
-                                                   rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
-                                                   float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), _stream(t_c)))
-    return bundle, w, C_f
+    pm = M = None
+    mid = []
+    if train is not None:
+        perm, joint, maps = train
+        pm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev) if perm else None
+        M = torch.full((B, 4), _NAN, device=dev) if maps else None
+        mid = [_ptr(pm), int(bool(joint)), _ptr(M)]
+    _abi.check(getattr(_abi.lib(), entry)(_ptr(t_c), _ptr(t_f), _ptr(sigma_c), _ptr(sigma_f), _ptr(rgb_c), _ptr(rgb_f), B, Nc, Nf, float(last),
+                                          bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), *mid, _stream(t_c), *tail))
+    return bundle, w, C_f, pm, M
+
+
+def _coarse_stage_backward(entry, t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb, rays=None, mid=(), tail=(), who=""):
+    """One backward coarse stage call `entry` of the first `rays` rays (default: all), which ADDS to dsig[B,Nc], drgb[B,Nc,3] in place;
+    mid: the entry's arguments between dt_f and dsig (dmaps), tail: those behind the stream (ddist)"""
+    B, Nc = t_c.shape
+    Nf = dt_f.shape[1]
+    rays = B if rays is None else int(rays)
+    if not (1 <= rays <= B and dsig.shape == (B, Nc) and drgb.shape == (B, Nc, 3) and dsig.is_contiguous() and drgb.is_contiguous()):
+        raise ValueError(f"{who}: contiguous dsig [B,Nc] / drgb [B,Nc,3] and 1 <= rays <= B")
+    nf = _near_far(near, far, t_c.device)
+    _abi.check(getattr(_abi.lib(), entry)(_ptr(t_c), _ptr(sigma_c), _ptr(rgb_c), nf.data_ptr(), float(delta0), rays, Nc, Nf, _ptr(dC_c), _ptr(dt_f),
+                                          *mid, dsig.data_ptr(), drgb.data_ptr(), _stream(t_c), *tail))
+    return dsig, drgb
+
+
+def _merge_stage_backward(entry, bundle, perm, dC_f, Nc, last, dmaps, tail=(), who="merge_composite_backward"):
+    """One backward merge stage call `entry` -> dsig_c, dsig_f, drgb_c, drgb_f, dt_f; the outputs start as NaN: the kernel writes every
+    element.  tail: the entry's arguments behind the stream"""
+    B, N, _ = bundle.shape
+    Nf = N - Nc
+    dev = bundle.device
+    if perm.dtype != torch.int16 or perm.shape != (B, 5, N):
+        raise ValueError(f"{who}: perm is int16 [B,5,N]")
+    nan = lambda *s: torch.full(s, _NAN, device=dev)
+    dsig_c, dsig_f, drgb_c, drgb_f, dt_f = nan(B, Nc), nan(B, Nf), nan(B, Nc, 3), nan(B, Nf, 3), nan(B, Nf)
+    _abi.check(getattr(_abi.lib(), entry)(_ptr(bundle), _ptr(perm), _ptr(dC_f), _ptr(dmaps), B, Nc, Nf, float(last), dsig_c.data_ptr(),
+                                          dsig_f.data_ptr(), drgb_c.data_ptr(), drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle), *tail))
+    return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
+
+
+def coarse_composite(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
+    """-> w_c[B,Nc], C_coarse[B,3], t_f[B,Nf], status(int)"""
+    return _coarse_stage("nerf_hip_coarse_composite", t_c, sigma_c, rgb_c, near, far, delta0, Nf)[:4]
+
+
+def merge_composite(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last=1e-4):
+    """-> bundle[B,N,5], w[B,N], C_fine[B,3]"""
+    return _merge_stage("nerf_hip_merge_composite", t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last)[:3]
 
 
 def coarse_composite_backward(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f):
     """-> dsig_c[B,Nc], drgb_c[B,Nc,3] (contributions through C_coarse and the resampled depths)"""
     B, Nc = t_c.shape
-    Nf = dt_f.shape[1]
-    dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    dsig = torch.zeros(B, Nc, device=dev)
-    drgb = torch.zeros(B, Nc, 3, device=dev)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_backward(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
-                                                             rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), B, Nc, Nf,
-                                                             dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(),
-                                                             dsig.data_ptr(), drgb.data_ptr(), _stream(t_c)))
-    return dsig, drgb
+    dsig = torch.zeros(B, Nc, device=t_c.device)
+    drgb = torch.zeros(B, Nc, 3, device=t_c.device)
+    return _coarse_stage_backward("nerf_hip_coarse_composite_backward", t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb,
+                                  who="coarse_composite_backward")
 
 
 def coarse_composite_maps(t_c, sigma_c, rgb_c, near, far, delta0, Nf):
-    """coarse_composite through k_coarse_maps -> w_c, C_coarse, t_f, status(int), maps[B,4] (columns 0, 1 written; 2, 3 left NaN)"""
-    B, Nc = t_c.shape
-    dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    w_c = torch.empty(B, Nc, device=dev)
-    C_c = torch.empty(B, 3, device=dev)
-    t_f = torch.empty(B, Nf, device=dev)
-    maps = torch.full((B, 4), float("nan"), device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_maps(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
-                                                         rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), B, Nc, Nf,
-                                                         w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
-                                                         _stream(t_c)))
-    return w_c, C_c, t_f, int(status.item()), maps
+    """coarse_composite through k_coarse_x<maps> -> w_c, C_coarse, t_f, status(int), maps[B,4] (columns 0, 1 written; 2, 3 left NaN)"""
+    return _coarse_stage("nerf_hip_coarse_composite_maps", t_c, sigma_c, rgb_c, near, far, delta0, Nf, maps=True)
 
 
 def coarse_composite_backward_add(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb, dmaps=None, rays=None):
     """ADDS the coarse stage's gradients of the first `rays` rays (default: all) to dsig[B,Nc], drgb[B,Nc,3] in place; dmaps[B,4]: the
-    optional upstream of the coarse maps (k_coarse_bwd_maps)"""
-    B, Nc = t_c.shape
-    Nf = dt_f.shape[1]
-    rays = B if rays is None else int(rays)
-    if not (1 <= rays <= B and dsig.shape == (B, Nc) and drgb.shape == (B, Nc, 3) and dsig.is_contiguous() and drgb.is_contiguous()):
-        raise ValueError("coarse_composite_backward_add: contiguous dsig [B,Nc] / drgb [B,Nc,3] and 1 <= rays <= B")
-    nf = torch.stack((near, far), dim=1).contiguous().to(t_c.device)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_backward_maps(
-        t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(), rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
-        dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
-        dsig.data_ptr(), drgb.data_ptr(), _stream(t_c)))
-    return dsig, drgb
+    optional upstream of the coarse maps (k_coarse_bwd_x)"""
+    return _coarse_stage_backward("nerf_hip_coarse_composite_backward_maps", t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb,
+                                  rays=rays, mid=(_ptr(dmaps),), who="coarse_composite_backward_add")
 
 
 def merge_composite_train(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last=1e-4, joint=False, maps=False):
     """the training form of merge_composite (k_merge<true>) -> bundle[B,N,5], w[B,N], C_fine[B,3], perm[B,5,N] int16 (sorted position ->
     original slot per channel), maps[B,4] (columns 2, 3 written; 0, 1 left NaN) or None"""
-    B, Nc = t_c.shape
-    Nf = t_f.shape[1]
-    dev = t_c.device
-    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
-    w = torch.empty(B, Nc + Nf, device=dev)
-    C_f = torch.empty(B, 3, device=dev)
-    perm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev)
-    M = torch.full((B, 4), float("nan"), device=dev) if maps else None
-    _abi.check(_abi.lib().nerf_hip_merge_composite_train(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
-                                                         sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
-                                                         rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
-                                                         float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), perm.data_ptr(),
-                                                         int(bool(joint)), None if M is None else M.data_ptr(), _stream(t_c)))
-    return bundle, w, C_f, perm, M
+    return _merge_stage("nerf_hip_merge_composite_train", t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last, train=(True, joint, maps))
 
 
 def merge_composite_backward(bundle, perm, dC_f, Nc, last=1e-4, dmaps=None):
     """backward of merge_composite_train -> dsig_c[B,Nc], dsig_f[B,Nf], drgb_c[B,Nc,3], drgb_f[B,Nf,3], dt_f[B,Nf]; the outputs start as NaN:
     the kernel writes every element"""
-    B, N, _ = bundle.shape
-    Nf = N - Nc
-    dev = bundle.device
-    if perm.dtype != torch.int16 or perm.shape != (B, 5, N):
-        raise ValueError("merge_composite_backward: perm is int16 [B,5,N]")
-    nan = lambda *s: torch.full(s, float("nan"), device=dev)
-    dsig_c, dsig_f, drgb_c, drgb_f, dt_f = nan(B, Nc), nan(B, Nf), nan(B, Nc, 3), nan(B, Nf, 3), nan(B, Nf)
-    _abi.check(_abi.lib().nerf_hip_merge_composite_backward(bundle.contiguous().data_ptr(), perm.contiguous().data_ptr(),
-                                                            dC_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
-                                                            B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(), drgb_c.data_ptr(),
-                                                            drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle)))
-    return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
+    return _merge_stage_backward("nerf_hip_merge_composite_backward", bundle, perm, dC_f, Nc, last, dmaps)
 
 
 def coarse_composite_quantiles(t_c, sigma_c, rgb_c, near, far, delta0, Nf, q, sentinel=float("nan"), rays=None):
-    """coarse_composite_maps through k_coarse_qmaps (nerf_hip_coarse_composite_quantiles) -> w_c, C_coarse, t_f, status(int), maps[B,4],
-    qdepth[B,2,nq]: row 0 = the coarse quantile depths of q (rule QD of include/nerf_hip.h), row 1 left at `sentinel`.  rays: a call of
-    the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
-    B, Nc = t_c.shape
-    rays = B if rays is None else int(rays)
-    if not 1 <= rays <= B:
-        raise ValueError("coarse_composite_quantiles: 1 <= rays <= B")
-    dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    w_c = torch.empty(B, Nc, device=dev)
-    C_c = torch.empty(B, 3, device=dev)
-    t_f = torch.empty(B, Nf, device=dev)
-    maps = torch.full((B, 4), float("nan"), device=dev)
-    Q = torch.full((B, 2, len(q)), sentinel, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_quantiles(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
-                                                              rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
-                                                              w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
-                                                              _stream(t_c), _abi.f32_array(q), len(q), Q.data_ptr()))
-    return w_c, C_c, t_f, int(status.item()), maps, Q
+    """coarse_composite_maps through k_coarse_x<maps, quantiles> (nerf_hip_coarse_composite_quantiles) -> w_c, C_coarse, t_f, status(int),
+    maps[B,4], qdepth[B,2,nq]: row 0 = the coarse quantile depths of q (rule QD of include/nerf_hip.h), row 1 left at `sentinel`.  rays: a
+    call of the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
+    Q = torch.full((t_c.shape[0], 2, len(q)), sentinel, device=t_c.device)
+    return _coarse_stage("nerf_hip_coarse_composite_quantiles", t_c, sigma_c, rgb_c, near, far, delta0, Nf, rays=rays, maps=True,
+                         tail=(_abi.f32_array(q), len(q), Q.data_ptr()), who="coarse_composite_quantiles") + (Q,)
 
 
 def merge_composite_quantiles(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, q, last=1e-4, joint=False, perm=True, sentinel=float("nan")):
-    """merge_composite_train(maps=True) through k_merge_qmaps (nerf_hip_merge_composite_quantiles) -> bundle, w, C_fine, perm (None with
-    perm=False: the values-only sort, joint=False only), maps[B,4], qdepth[B,2,nq]: row 1 = the fine quantile depths of q (rule QD), row 0
-    left at `sentinel`"""
-    B, Nc = t_c.shape
-    Nf = t_f.shape[1]
-    dev = t_c.device
-    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
-    w = torch.empty(B, Nc + Nf, device=dev)
-    C_f = torch.empty(B, 3, device=dev)
-    pm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev) if perm else None
-    M = torch.full((B, 4), float("nan"), device=dev)
-    Q = torch.full((B, 2, len(q)), sentinel, device=dev)
-    _abi.check(_abi.lib().nerf_hip_merge_composite_quantiles(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
-                                                             sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
-                                                             rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
-                                                             float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(),
-                                                             None if pm is None else pm.data_ptr(), int(bool(joint)), M.data_ptr(), _stream(t_c),
-                                                             _abi.f32_array(q), len(q), Q.data_ptr()))
-    return bundle, w, C_f, pm, M, Q
+    """merge_composite_train(maps=True) through k_merge_x<maps, quantiles> (nerf_hip_merge_composite_quantiles) -> bundle, w, C_fine, perm
+    (None with perm=False: the values-only sort, joint=False only), maps[B,4], qdepth[B,2,nq]: row 1 = the fine quantile depths of q (rule
+    QD), row 0 left at `sentinel`"""
+    Q = torch.full((t_c.shape[0], 2, len(q)), sentinel, device=t_c.device)
+    return _merge_stage("nerf_hip_merge_composite_quantiles", t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last, train=(perm, joint, True),
+                        tail=(_abi.f32_array(q), len(q), Q.data_ptr())) + (Q,)
 
 
 def coarse_composite_distortion(t_c, sigma_c, rgb_c, near, far, delta0, Nf, sentinel=float("nan"), rays=None):
-    """coarse_composite_maps through k_coarse_dmaps (nerf_hip_coarse_composite_distortion) -> w_c, C_coarse, t_f, status(int), maps[B,4],
-    dist[B,2]: column 0 = the coarse distortion loss L_c (rule DL of include/nerf_hip.h), column 1 left at `sentinel`.  rays: a call of
-    the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
-    B, Nc = t_c.shape
-    rays = B if rays is None else int(rays)
-    if not 1 <= rays <= B:
-        raise ValueError("coarse_composite_distortion: 1 <= rays <= B")
-    dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    w_c = torch.empty(B, Nc, device=dev)
-    C_c = torch.empty(B, 3, device=dev)
-    t_f = torch.empty(B, Nf, device=dev)
-    maps = torch.full((B, 4), float("nan"), device=dev)
-    dist = torch.full((B, 2), sentinel, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_distortion(t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(),
-                                                               rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
-                                                               w_c.data_ptr(), C_c.data_ptr(), t_f.data_ptr(), status.data_ptr(), maps.data_ptr(),
-                                                               _stream(t_c), dist.data_ptr()))
-    return w_c, C_c, t_f, int(status.item()), maps, dist
+    """coarse_composite_maps through k_coarse_x<maps, distortion> (nerf_hip_coarse_composite_distortion) -> w_c, C_coarse, t_f, status(int),
+    maps[B,4], dist[B,2]: column 0 = the coarse distortion loss L_c (rule DL of include/nerf_hip.h), column 1 left at `sentinel`.  rays: a
+    call of the first `rays` rays only (default: all) -- the outputs keep their B rows, and those behind the call their initial values"""
+    dist = torch.full((t_c.shape[0], 2), sentinel, device=t_c.device)
+    return _coarse_stage("nerf_hip_coarse_composite_distortion", t_c, sigma_c, rgb_c, near, far, delta0, Nf, rays=rays, maps=True,
+                         tail=(dist.data_ptr(),), who="coarse_composite_distortion") + (dist,)
 
 
 def merge_composite_distortion(t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, near, far, last=1e-4, joint=False, sentinel=float("nan")):
-    """merge_composite_train(maps=True) through k_merge_dmaps (nerf_hip_merge_composite_distortion) -> bundle, w, C_fine, perm, maps[B,4],
-    dist[B,2]: column 1 = the fine distortion loss L_f (rule DL), column 0 left at `sentinel`"""
-    B, Nc = t_c.shape
-    Nf = t_f.shape[1]
-    dev = t_c.device
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    bundle = torch.empty(B, Nc + Nf, 5, device=dev)
-    w = torch.empty(B, Nc + Nf, device=dev)
-    C_f = torch.empty(B, 3, device=dev)
-    pm = torch.full((B, 5, Nc + Nf), -1, dtype=torch.int16, device=dev)
-    M = torch.full((B, 4), float("nan"), device=dev)
-    dist = torch.full((B, 2), sentinel, device=dev)
-    _abi.check(_abi.lib().nerf_hip_merge_composite_distortion(t_c.contiguous().data_ptr(), t_f.contiguous().data_ptr(),
-                                                              sigma_c.contiguous().data_ptr(), sigma_f.contiguous().data_ptr(),
-                                                              rgb_c.contiguous().data_ptr(), rgb_f.contiguous().data_ptr(), B, Nc, Nf,
-                                                              float(last), bundle.data_ptr(), w.data_ptr(), C_f.data_ptr(), pm.data_ptr(),
-                                                              int(bool(joint)), M.data_ptr(), _stream(t_c), nf.data_ptr(), dist.data_ptr()))
-    return bundle, w, C_f, pm, M, dist
+    """merge_composite_train(maps=True) through k_merge_x<maps, distortion> (nerf_hip_merge_composite_distortion) -> bundle, w, C_fine, perm,
+    maps[B,4], dist[B,2]: column 1 = the fine distortion loss L_f (rule DL), column 0 left at `sentinel`"""
+    nf = _near_far(near, far, t_c.device)
+    dist = torch.full((t_c.shape[0], 2), sentinel, device=t_c.device)
+    return _merge_stage("nerf_hip_merge_composite_distortion", t_c, t_f, sigma_c, sigma_f, rgb_c, rgb_f, last, train=(True, joint, True),
+                        tail=(nf.data_ptr(), dist.data_ptr())) + (dist,)
 
 
 def coarse_composite_backward_distortion_add(t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb, ddist, dmaps=None, rays=None):
-    """coarse_composite_backward_add through k_coarse_bwd_dist (nerf_hip_coarse_composite_backward_distortion): ADDS the coarse stage's
-    gradients, the upstream ddist[B,2] (column 0) of the coarse distortion loss included, to dsig[B,Nc], drgb[B,Nc,3] in place"""
-    B, Nc = t_c.shape
-    Nf = dt_f.shape[1]
-    rays = B if rays is None else int(rays)
-    if not (1 <= rays <= B and dsig.shape == (B, Nc) and drgb.shape == (B, Nc, 3) and dsig.is_contiguous() and drgb.is_contiguous()):
-        raise ValueError("coarse_composite_backward_distortion_add: contiguous dsig [B,Nc] / drgb [B,Nc,3] and 1 <= rays <= B")
-    nf = torch.stack((near, far), dim=1).contiguous().to(t_c.device)
-    _abi.check(_abi.lib().nerf_hip_coarse_composite_backward_distortion(
-        t_c.contiguous().data_ptr(), sigma_c.contiguous().data_ptr(), rgb_c.contiguous().data_ptr(), nf.data_ptr(), float(delta0), rays, Nc, Nf,
-        dC_c.contiguous().data_ptr(), dt_f.contiguous().data_ptr(), None if dmaps is None else dmaps.contiguous().data_ptr(),
-        dsig.data_ptr(), drgb.data_ptr(), _stream(t_c), ddist.contiguous().data_ptr()))
-    return dsig, drgb
+    """coarse_composite_backward_add through k_coarse_bwd_x<distortion> (nerf_hip_coarse_composite_backward_distortion): ADDS the coarse
+    stage's gradients, the upstream ddist[B,2] (column 0) of the coarse distortion loss included, to dsig[B,Nc], drgb[B,Nc,3] in place"""
+    return _coarse_stage_backward("nerf_hip_coarse_composite_backward_distortion", t_c, sigma_c, rgb_c, near, far, delta0, dC_c, dt_f, dsig, drgb,
+                                  rays=rays, mid=(_ptr(dmaps),), tail=(_ptr(ddist),), who="coarse_composite_backward_distortion_add")
 
 
 def merge_composite_backward_distortion(bundle, perm, dC_f, Nc, near, far, ddist, last=1e-4, dmaps=None):
-    """merge_composite_backward through k_merge_bwd_dist (nerf_hip_merge_composite_backward_distortion), with the upstream ddist[B,2]
-    (column 1) of the fine distortion loss -> dsig_c, dsig_f, drgb_c, drgb_f, dt_f; the outputs start as NaN: the kernel writes every element"""
-    B, N, _ = bundle.shape
-    Nf = N - Nc
-    dev = bundle.device
-    if perm.dtype != torch.int16 or perm.shape != (B, 5, N):
-        raise ValueError("merge_composite_backward_distortion: perm is int16 [B,5,N]")
-    nf = torch.stack((near, far), dim=1).contiguous().to(dev)
-    nan = lambda *s: torch.full(s, float("nan"), device=dev)
-    dsig_c, dsig_f, drgb_c, drgb_f, dt_f = nan(B, Nc), nan(B, Nf), nan(B, Nc, 3), nan(B, Nf, 3), nan(B, Nf)
-    _abi.check(_abi.lib().nerf_hip_merge_composite_backward_distortion(
-        bundle.contiguous().data_ptr(), perm.contiguous().data_ptr(), dC_f.contiguous().data_ptr(),
-        None if dmaps is None else dmaps.contiguous().data_ptr(), B, Nc, Nf, float(last), dsig_c.data_ptr(), dsig_f.data_ptr(),
-        drgb_c.data_ptr(), drgb_f.data_ptr(), dt_f.data_ptr(), _stream(bundle), nf.data_ptr(), ddist.contiguous().data_ptr()))
-    return dsig_c, dsig_f, drgb_c, drgb_f, dt_f
+    """merge_composite_backward through k_merge_bwd_x<distortion> (nerf_hip_merge_composite_backward_distortion), with the upstream
+    ddist[B,2] (column 1) of the fine distortion loss -> dsig_c, dsig_f, drgb_c, drgb_f, dt_f; the outputs start as NaN: the kernel writes
+    every element"""
+    nf = _near_far(near, far, bundle.device)
+    return _merge_stage_backward("nerf_hip_merge_composite_backward_distortion", bundle, perm, dC_f, Nc, last, dmaps,
+                                 tail=(nf.data_ptr(), _ptr(ddist)), who="merge_composite_backward_distortion")
 
 
 def normal_composite(w, g, out=None, out_stride=3, rays=None, sentinel=float("nan")):

@@ -1,8 +1,8 @@
 """Times one training step with and without the distortion loss: forward(maps=True) + ray_loss + backward() against
 forward(maps=True, distortion=True) + ray_loss + 0.01 * distortion_loss + backward(), at 4096 and 400 rays (64 + 128 samples), in exact fp32
 and with the bf16 MLP.  Both steps alternate in one process on one build, HIP events around each, after a warm-up of both; the maps step's
-kernels are untouched by the feature, so the difference is k_coarse_dmaps / k_merge_dmaps against k_coarse_maps / k_merge_maps,
-k_merge_bwd_dist / k_coarse_bwd_dist against their maps forms, and the [B, 2] output and its sum.  Prints one JSON line per case (median ms
+kernels are untouched by the feature, so the difference is the maps + distortion forms of k_coarse_x / k_merge_x and of k_merge_bwd_x /
+k_coarse_bwd_x against their maps forms, and the [B, 2] output and its sum.  Prints one JSON line per case (median ms
 of each step and the ratio).
 Usage: python scripts/distortion_time.py [--reps 30]"""
 import argparse

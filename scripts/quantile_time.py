@@ -2,7 +2,7 @@
 3i-2), for the exact fp32, split-fp32 and bf16-MLP inference kernels: the two versions alternate in one process, HIP events around each
 render, after a warm-up of both.  Two call layouts per precision, as scripts/maps_time.py: the frame's batches fused into 16,384-ray calls
 (render's default) and one call per 400-ray batch (fuse_rays=400).  Both versions take the separate k_coarse / k_merge launches, so the
-difference is the quantile loop of k_coarse_qmaps / k_merge_qmaps and the [n, 2, 3] output.  Prints one JSON line per case (median ms of
+difference is the quantile loop of the maps + quantiles forms of k_coarse_x / k_merge_x and the [n, 2, 3] output.  Prints one JSON line per case (median ms of
 each version and the ratio).
 Usage: python scripts/quantile_time.py [--reps 10]"""
 import argparse

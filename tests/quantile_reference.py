@@ -1,7 +1,7 @@
 """Rule QD of include/nerf_hip.h in numpy: the quantile depths of one pass of a ray, including the order in which the kernels form the
 fp64 prefix sums (per chunk of 64 samples the Hillis-Steele steps 1, 2, 4 .. 32 of wave_incl_scan, then + the carried total).
 
-  prefix_sums(w)        W_i exactly as k_coarse_qmaps / k_merge_qmaps form them           [..., N] fp32 -> [..., N] fp64
+  prefix_sums(w)        W_i exactly as k_coarse_x / k_merge_x (quantile forms) form them  [..., N] fp32 -> [..., N] fp64
   quantile_depths(...)  Q(q_j) per ray                                                    w, t [B, N] fp32, q [nq] -> [B, nq] fp32
   definition(...)       the rule once more, one ray, plain sequential Python floats (tests: exact weights make the scan order irrelevant)
   depth_image(...)      fuse_depth's depth-image rule over arrays (median, spread rejection -> NaN, background -> inf)

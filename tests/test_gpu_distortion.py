@@ -1,5 +1,5 @@
-"""GPU: the distortion loss on the device (rule DL of include/nerf_hip.h) -- k_coarse_dmaps / k_merge_dmaps,
-k_coarse_bwd_dist / k_merge_bwd_dist through their stage entries, nerf_hip_forward_distortion_train / nerf_hip_backward_distortion,
+"""GPU: the distortion loss on the device (rule DL of include/nerf_hip.h) -- the distortion forms of k_coarse_x / k_merge_x,
+k_coarse_bwd_x / k_merge_bwd_x through their stage entries, nerf_hip_forward_distortion_train / nerf_hip_backward_distortion,
 NeRFModel.forward(maps=True, distortion=True) under autograd and the runner's DIST_WEIGHT.
 
   A. stage forward, at every size of tests/ray_stage_reference.py, joint 0 and 1, and on exact ties: the outputs shared with the maps / train

@@ -1,4 +1,4 @@
-"""GPU: the per-ray quantile depths (rule QD of include/nerf_hip.h) -- k_coarse_qmaps / k_merge_qmaps through their stage entries and
+"""GPU: the per-ray quantile depths (rule QD of include/nerf_hip.h) -- the quantile forms of k_coarse_x / k_merge_x through their stage entries and
 through nerf_hip_forward_quantiles, NeRFModel.render(maps=True, quantiles=) and fuse_depth(depth_stat=, max_spread=).
 
   * every output a quantile call shares with the maps call has that call's bits;

@@ -188,7 +188,7 @@ def test_training_sort_permutations(pkg, dev, Nc, Nf, joint):
     _check_sort(pkg, chans, out, joint, Nc)
     bundle, w, C_f, perm, maps = out
     assert bool(torch.isfinite(bundle).all()) and bool(torch.isfinite(w).all()) and bool(torch.isfinite(C_f).all())
-    # without maps: the same bits (k_merge<true> and k_merge_maps<true> end in one composite)
+    # without maps: the same bits (k_merge<true> and k_merge_x<true, maps> end in one composite)
     b1, w1, C1, p1, _ = pkg.ops.merge_composite_train(d["t_c"], t_f, d["sig_c"], d["sig_f"], d["rgb_c"], d["rgb_f"], last=R.LAST, joint=bool(joint))
     assert torch.equal(_bits(b1), _bits(bundle)) and torch.equal(_bits(w1), _bits(w)) and torch.equal(_bits(C1), _bits(C_f)) and torch.equal(p1, perm)
     if not joint:  # the values-only sort of inference (k_merge<false>) gives the same bundle, weights and colour
