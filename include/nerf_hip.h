@@ -68,7 +68,9 @@ extern "C" {
                                      nerf_hip_merge_composite_backward_distortion; nerf_hip_mesh_atlas_dims,
                                      nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample; nerf_hip_normals_ws_bytes,
                                      nerf_hip_normals_ws_offset, nerf_hip_forward_normals, nerf_hip_normal_composite;
-                                     the nerf_hip_volume_* calls (with NERF_HIP_VOLUME_MAX_STEPS) */
+                                     the nerf_hip_volume_* calls (with NERF_HIP_VOLUME_MAX_STEPS);
+                                     nerf_hip_volume_render_backward, nerf_hip_volume_adam_step
+                                     (with NERF_HIP_VOLUME_GRAD_SHIFT) */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1393,6 +1395,60 @@ int nerf_hip_volume_render(const float* sigma, const float* coef, const uint8_t*
                            const float* lo3, const float* step3, const float* origins, const float* dirs, const float* tmin,
                            const float* tmax, int64_t N, float dt, float t_stop, const float* background3, float* rgb, float* maps,
                            int32_t* steps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Fine-tuning a baked volume: the gradient of the march with respect to sigma and the
+ * coefficients, accumulated exactly, and an Adam step over the baked active list.  Nothing of the calls above changes.
+ *
+ * VG. THE GRADIENT OF THE MARCH.  For one ray take i = 1 .. n over the contributing samples of rule VR, in order.  The early end at
+ *    T < t_stop is a constant: no gradient flows through the decision.  Sample i has alpha_i, w_i, T_(i+1) (T after sample i), c_i (the
+ *    clamped colour) and t_i, all the forward's own fp32 values.  Upstream: g_rgb[3] and g_maps = (gD, gA), (0, 0) when NULL.  From
+ *    here on everything is fp64 (the fp32 values widened), evaluated as bracketed:
+ *       gA' = gA - (((g_rgb[0] bg[0]) + (g_rgb[1] bg[1])) + (g_rgb[2] bg[2]))
+ *       v_i = ((((g_rgb[0] c_i[0]) + (g_rgb[1] c_i[1])) + (g_rgb[2] c_i[2])) + (gD t_i)) + gA'
+ *       P_i = P_(i-1) + (w_i v_i)   (P_0 = 0),    S = P_n
+ *       dL/dsigma_s,i = dt (((T_(i+1)) v_i) - (S - P_i))                 (no division: alpha -> 1 is harmless)
+ *       dL/dc_i[ch]   = w_i g_rgb[ch] where the UNCLAMPED colour of rule VL lies in [0, 1], both ends included (what a clamp
+ *                       passes); 0 elsewhere (a NaN included)
+ *    Corner c = (di, dj, dk) of the sample's cell has the weight tw_c = (wx wy) wz with w_a = f_a for d_a = 1 and 1 - f_a for d_a = 0,
+ *    f the fp32 f of rule VL widened.  It receives
+ *       (tw_c) (dL/dsigma_s,i)                   into its sigma word
+ *       ((tw_c) (Y_m(d))) (dL/dc_i[ch])          into its coefficient word (m, ch), Y_m(d) rule VL's fp32 value widened
+ *    Each contribution x is added as llrint(y), y = x 2^40 (NERF_HIP_VOLUME_GRAD_SHIFT) clamped to [-2^62, 2^62] (a NaN adds 0), into
+ *    two int64 arrays with the shapes of sigma and coef: the conversion is never undefined, the sums are integers, and the result
+ *    does not depend on the order in which the contributions arrive -- bit for bit whatever the launch, the batch split, the ray
+ *    order or the block edge.  A contribution that rounds to 0 may be left out.  Misses add nothing; a ray whose upstream values
+ *    (g_rgb, and g_maps when given) are not all finite adds nothing.
+ *    OVERFLOW PRECONDITION.  Between two reads of a word the sum of |x| it receives stays below 2^22 (then |sum| < 2^62 < 2^63).
+ *    Every |tw Y_m| < 1.1 and |dL/dc| <= |g|, so with |g| <= 2 that is about two million full-magnitude contributions to one word.
+ *
+ * VU. THE UPDATE over index[n], the ascending active list (rule VA) of the volume AS BAKED, one thread per (active point, word);
+ *    a point's words are its sigma and its 3 ncoef coefficients, m and v are [n][1 + 3 ncoef] fp32 in that order.  Per word, with acc
+ *    its accumulator, lr = lr_sigma or lr_coef, everything fp64 as bracketed and rounded to fp32 ONCE where fp32() says so:
+ *       g  = (double(acc) 2^-40) grad_scale
+ *       m' = fp32((beta1 m) + ((1 - beta1) g)),    v' = fp32((beta2 v) + ((1 - beta2) (g g)))
+ *       x' = fp32(x - (lr ((m' / c1) / (sqrt(v' / c2) + eps))))         c1 = 1 - beta1^step,  c2 = 1 - beta2^step
+ *    beta^step is formed on the host in fp64 by squaring: p = 1, b = beta, e = step; while e > 0: (e odd: p = p b), b = b b, e = e / 2.
+ *    The accumulator word is zeroed whatever happens: no memset is needed between steps.  An index outside the lattice is skipped.
+ *    FROZEN SUPPORT (the rule's invariant).  A sigma word is updated only while sigma > 0 at entry and is then clamped,
+ *    sigma' = fmax(x', 0); a point that is not > 0 is DEAD: its x, m and v are left alone (its coefficient words are updated like any
+ *    other).  The positive set can therefore only shrink: every corner a contributing sample reads stays inside the baked active
+ *    list, the baked occ stays a valid superset of rule VO's, and accumulators outside the list stay zero.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_VOLUME_GRAD_SHIFT 40
+
+/* VG over the rays of nerf_hip_volume_render (its arguments, no outputs): g_rgb[N][3], g_maps[N][2] or NULL (device, fp32) ->
+ * contributions ADDED IN PLACE to acc_sigma [nx][ny][nz] and acc_coef [nx][ny][nz][ncoef][3] (device, int64, 8-byte aligned).  The
+ * kernel recomputes the march; nothing is taken from a forward call. */
+int nerf_hip_volume_render_backward(const float* sigma, const float* coef, const uint8_t* occ, int nx, int ny, int nz, int degree,
+                                    int block, const float* lo3, const float* step3, const float* origins, const float* dirs,
+                                    const float* tmin, const float* tmax, int64_t N, float dt, float t_stop, const float* background3,
+                                    const float* g_rgb, const float* g_maps, int64_t* acc_sigma, int64_t* acc_coef, void* stream);
+
+/* VU.  step >= 1; grad_scale, the rates, beta1, beta2 in [0, 1) and eps >= 0 finite.  n = 0 succeeds and launches nothing. */
+int nerf_hip_volume_adam_step(float* sigma, float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                              int64_t* acc_sigma, int64_t* acc_coef, float* m, float* v, double grad_scale, int64_t step,
+                              double lr_sigma, double lr_coef, double beta1, double beta2, double eps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ EDGES_TABLE_FULL = 1 << 0
 TSDF_CARVE = 1 << 0
 MAX_QUANTILES = 4  # NERF_HIP_MAX_QUANTILES: quantiles of one nerf_hip_forward_quantiles call (they travel in the kernels' arguments)
 VOLUME_MAX_STEPS = 65536  # NERF_HIP_VOLUME_MAX_STEPS: the cap on the samples of one ray of nerf_hip_volume_render
+VOLUME_GRAD_SHIFT = 40  # NERF_HIP_VOLUME_GRAD_SHIFT: nerf_hip_volume_render_backward's accumulators count units of 2^-40
 TSDF_VIEWS_PER_LAUNCH = 32  # NERF_HIP_TSDF_VIEWS_PER_LAUNCH: views whose cameras travel in one launch's kernel arguments
 
 _p = C.c_void_p
@@ -148,6 +149,10 @@ _PROTOS = {
     "nerf_hip_volume_sample": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int64, _p, _p, _p]),
     "nerf_hip_volume_render": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, C.c_int64,
                                          C.c_float, C.c_float, _p, _p, _p, _p, _p]),
+    "nerf_hip_volume_render_backward": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, C.c_int64,
+                                                  C.c_float, C.c_float, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_volume_adam_step": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p, _p, C.c_double, C.c_int64,
+                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -1,5 +1,5 @@
-// api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL
-// and VR): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on the caller's stream.
+// api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
+// VR, VG and VU): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on the caller's stream.
 // No allocation, no host sync.
 #include <math.h>
 
@@ -67,6 +67,16 @@ VolLattice lattice(int nx, int ny, int nz, const float* lo3, const float* step3)
 
 // blocks per axis of edge B: ceil((n - 1) / B)
 int blocks_of(int n, int B) { return (int)(((long long)n - 1 + B - 1) / B); }
+
+// rule VU's beta^step: by squaring, every product one fp64 rounding in this order
+double pow_by_squaring(double beta, int64_t step) {
+  double p = 1.0, b = beta;
+  for (int64_t e = step; e > 0; e >>= 1) {
+    if (e & 1) p = p * b;
+    b = b * b;
+  }
+  return p;
+}
 
 int active(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, int32_t* index, int64_t max_n, bool emit,
            void* stream) {
@@ -263,6 +273,102 @@ int nerf_hip_volume_render(const float* sigma, const float* coef, const uint8_t*
   a.maps = maps;
   a.steps = steps;
   HIP_TRY(launch_volume_render(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_render_backward(const float* sigma, const float* coef, const uint8_t* occ, int nx, int ny, int nz, int degree,
+                                    int block, const float* lo3, const float* step3, const float* origins, const float* dirs,
+                                    const float* tmin, const float* tmax, int64_t N, float dt, float t_stop, const float* background3,
+                                    const float* g_rgb, const float* g_maps, int64_t* acc_sigma, int64_t* acc_coef, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_count("N", N)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (!(dt > 0.0f && isfinite(dt))) return fail(NERF_HIP_ERR_ARG, "dt=%g: the step along the ray must be finite and > 0", (double)dt);
+  if (!(t_stop >= 0.0f && t_stop < 1.0f)) return fail(NERF_HIP_ERR_ARG, "t_stop=%g: the transmittance to stop at lies in [0, 1)", (double)t_stop);
+  if (!background3) return fail(NERF_HIP_ERR_ARG, "background3 is null");
+  if (int rc = check_finite3(background3, "background", "the background colour")) return rc;
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (int rc = check_out(acc_sigma, "acc_sigma", 8)) return rc;
+  if (int rc = check_out(acc_coef, "acc_coef", 8)) return rc;
+  if (g_maps && ((uintptr_t)g_maps & 3) != 0) return fail(NERF_HIP_ERR_ARG, "g_maps must be 4-byte aligned");
+  if (N == 0) return NERF_HIP_OK;
+  if (int rc = check_out(origins, "origins", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(tmin, "tmin", 4)) return rc;
+  if (int rc = check_out(tmax, "tmax", 4)) return rc;
+  if (int rc = check_out(g_rgb, "g_rgb", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.r.sigma = sigma;
+  a.r.coef = coef;
+  a.r.occ = occ;
+  a.r.g = lattice(nx, ny, nz, lo3, step3);
+  a.r.B = block;
+  a.r.bx = blocks_of(nx, block);
+  a.r.by = blocks_of(ny, block);
+  a.r.bz = blocks_of(nz, block);
+  a.r.origins = origins;
+  a.r.dirs = dirs;
+  a.r.tmin = tmin;
+  a.r.tmax = tmax;
+  a.r.N = N;
+  a.r.dt = dt;
+  a.r.t_stop = t_stop;
+  for (int c = 0; c < 3; ++c) a.r.bg[c] = background3[c];
+  a.g_rgb = g_rgb;
+  a.g_maps = g_maps;
+  a.acc_sigma = reinterpret_cast<long long*>(acc_sigma);
+  a.acc_coef = reinterpret_cast<long long*>(acc_coef);
+  HIP_TRY(launch_volume_render_backward(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_adam_step(float* sigma, float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                              int64_t* acc_sigma, int64_t* acc_coef, float* m, float* v, double grad_scale, int64_t step,
+                              double lr_sigma, double lr_coef, double beta1, double beta2, double eps, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (step < 1) return fail(NERF_HIP_ERR_ARG, "step=%lld: the first update is step 1", (long long)step);
+  if (!isfinite(grad_scale)) return fail(NERF_HIP_ERR_ARG, "grad_scale=%g must be finite", grad_scale);
+  if (!isfinite(lr_sigma) || !isfinite(lr_coef)) return fail(NERF_HIP_ERR_ARG, "lr_sigma=%g lr_coef=%g: the rates must be finite", lr_sigma, lr_coef);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(NERF_HIP_ERR_ARG, "beta1=%g beta2=%g: both lie in [0, 1)", beta1, beta2);
+  if (!(eps >= 0.0 && isfinite(eps))) return fail(NERF_HIP_ERR_ARG, "eps=%g must be finite and >= 0", eps);
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(acc_sigma, "acc_sigma", 8)) return rc;
+  if (int rc = check_out(acc_coef, "acc_coef", 8)) return rc;
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(index, "index", 4)) return rc;
+  if (int rc = check_out(m, "m", 4)) return rc;
+  if (int rc = check_out(v, "v", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolAdamArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.npts = (long long)nx * ny * nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.index = index;
+  a.n = n;
+  a.acc_sigma = reinterpret_cast<long long*>(acc_sigma);
+  a.acc_coef = reinterpret_cast<long long*>(acc_coef);
+  a.m = m;
+  a.v = v;
+  a.grad_scale = grad_scale;
+  a.lr_sigma = lr_sigma;
+  a.lr_coef = lr_coef;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  a.c1 = 1.0 - pow_by_squaring(beta1, step);
+  a.c2 = 1.0 - pow_by_squaring(beta2, step);
+  HIP_TRY(launch_volume_adam_step(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

@@ -811,6 +811,31 @@ hipError_t launch_volume_blocks(const VolBlocksArgs& a, hipStream_t st);
 hipError_t launch_volume_sample(const VolSampleArgs& a, int ncoef, hipStream_t st);
 hipError_t launch_volume_render(const VolRenderArgs& a, int ncoef, hipStream_t st);
 
+// ---- fine-tuning a baked volume (volume_grad.hip; nerf_hip_volume_render_backward, nerf_hip_volume_adam_step, DESIGN.md section
+// 3h-13; rules VG and VU of include/nerf_hip.h) ----
+constexpr int VOL_GRAD_SHIFT = 40;             // NERF_HIP_VOLUME_GRAD_SHIFT
+
+struct VolGradArgs {
+  VolRenderArgs r;         // the forward's arguments; its outputs (rgb, maps, steps) are not used
+  const float *g_rgb, *g_maps;      // [N][3], [N][2] or null
+  long long *acc_sigma, *acc_coef;  // [npts], [npts][ncoef][3]: fixed-point sums, 2^-40 units
+};
+
+struct VolAdamArgs {
+  float *sigma, *coef;     // [npts], [npts][ncoef][3]
+  long long npts;
+  int ncoef;
+  const int* index;        // [n]: the active list of the volume as baked
+  long long n;
+  long long *acc_sigma, *acc_coef;
+  float *m, *v;            // [n][1 + 3 ncoef]
+  double grad_scale, lr_sigma, lr_coef, beta1, beta2, eps;
+  double c1, c2;           // 1 - beta1^step, 1 - beta2^step
+};
+
+hipError_t launch_volume_render_backward(const VolGradArgs& a, int ncoef, hipStream_t st);
+hipError_t launch_volume_adam_step(const VolAdamArgs& a, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

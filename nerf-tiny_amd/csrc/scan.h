@@ -1,5 +1,5 @@
 // scan.h -- the scan and compaction scaffolding of the geometry kernels.  Included by the geometry translation
-// units only -- the mesh_*.hip files, mesh.hip, band.hip, tsdf.hip and volume.hip --, never by a render or training one.
+// units only -- the mesh_*.hip files, mesh.hip, band.hip, tsdf.hip, volume.hip and volume_grad.hip --, never by a render or training one.
 //   lane_prefix / wg_prefix     exclusive prefix of a small per-lane count inside the wave / the workgroup, in item order
 //   wg_prefix_sum               the same for a value of any size (weights, per-cell counts) across a workgroup of CC_WG
 //   Totals / scan_totals        channels of workgroup totals -> exclusive bases and the grand totals, by ONE workgroup of 1024

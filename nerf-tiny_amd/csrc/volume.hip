@@ -8,6 +8,7 @@
 //                         stores of the same value, so the order plays no role and there is no atomic
 //   k_volume_sample<NC>   per point: rule VL
 //   k_volume_march<NC>    per ray: rule VR, one ray per lane
+// The lookup helpers (rule VL's cell, corners and interpolation, rule VS's basis) live in volume_parts.h, shared with volume_grad.hip.
 //
 // THE MARCH.  Everything a ray needs lives in its lane: origin, direction, the nine basis values of its direction (computed once), the
 // running (C, D, A, T) and two counters.  No LDS, no atomics, no barrier; the lanes of a wave are neighbouring pixels, so their
@@ -40,86 +41,11 @@
 // active list) are checked against the lattice before use.
 #include "../../include/nerf_hip.h"
 #include "scan.h"
+#include "volume_parts.h"
 
 namespace nerf {
 
 namespace {
-
-constexpr float VOL_INF = __builtin_huge_valf();
-
-__device__ inline float vol_lerp(float a, float b, float f) { return a + f * (b - a); }
-
-// v[di * 4 + dj * 2 + dk]: z first, then y, then x
-__device__ inline float vol_tri(const float (&v)[8], const float (&f)[3]) {
-  const float c00 = vol_lerp(v[0], v[1], f[2]), c01 = vol_lerp(v[2], v[3], f[2]);
-  const float c10 = vol_lerp(v[4], v[5], f[2]), c11 = vol_lerp(v[6], v[7], f[2]);
-  return vol_lerp(vol_lerp(c00, c01, f[1]), vol_lerp(c10, c11, f[1]), f[0]);
-}
-
-// rule VS's basis at d, in fp32
-__device__ inline void vol_basis(const float (&d)[3], float (&Y)[9]) {
-  constexpr float C[5] = NERF_HIP_VOLUME_SH_C;  // the header's constants: one copy for the rule, the host tables and this kernel
-  constexpr float C0 = C[0], C1 = C[1], C2 = C[2], C3 = C[3], C4 = C[4];
-  const float x = d[0], y = d[1], z = d[2];
-  Y[0] = C0;
-  Y[1] = C1 * y;
-  Y[2] = C1 * z;
-  Y[3] = C1 * x;
-  Y[4] = C2 * (x * y);
-  Y[5] = C2 * (y * z);
-  Y[6] = C3 * ((3.0f * (z * z)) - 1.0f);
-  Y[7] = C2 * (x * z);
-  Y[8] = C4 * ((x * x) - (y * y));
-}
-
-// rule VL's cell of the point x: is it INSIDE?  ci is clamped into [0, n - 2] whatever x is (a NaN gives 0)
-__device__ inline bool vol_cell(const VolLattice& g, const float (&x)[3], int (&ci)[3], float (&f)[3]) {
-  const int dim[3] = {g.nx, g.ny, g.nz};
-  bool in = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float gg = (x[a] - g.lo[a]) / g.step[a];
-    in = in && 0.0f <= gg && gg <= (float)(dim[a] - 1);
-    const float fi = fminf(fmaxf(floorf(gg), 0.0f), (float)(dim[a] - 2));
-    ci[a] = (int)fi;
-    f[a] = gg - fi;
-  }
-  return in;
-}
-
-// the linear indices of the cell's eight corners, di * 4 + dj * 2 + dk
-__device__ inline void vol_corners(const VolLattice& g, const int (&ci)[3], long long (&p)[8]) {
-  const long long sy = g.nz, sx = (long long)g.ny * g.nz;
-  const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) p[c] = base + (c >> 2) * sx + ((c >> 1) & 1) * sy + (c & 1);
-}
-
-__device__ inline float vol_sigma(const float* __restrict__ sigma, const long long (&p)[8], const float (&f)[3]) {
-  float v[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) v[c] = sigma[p[c]];
-  return vol_tri(v, f);
-}
-
-template <int NC>
-__device__ inline void vol_color(const float* __restrict__ coef, const long long (&p)[8], const float (&f)[3], const float (&Y)[9],
-                                 float (&rgb)[3]) {
-  float v[3][8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float* __restrict__ q = coef + p[c] * (NC * 3);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float s = Y[0] * q[ch];
-#pragma unroll
-      for (int m = 1; m < NC; ++m) s = s + Y[m] * q[m * 3 + ch];
-      v[ch][c] = s;
-    }
-  }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) rgb[ch] = fminf(fmaxf(vol_tri(v[ch], f), 0.0f), 1.0f);
-}
 
 // ---- rule VA ----
 

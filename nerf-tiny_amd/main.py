@@ -111,6 +111,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--volume-preview", nargs="?", const="test", default=None, choices=["train", "val", "test"], metavar="SPLIT",
                     help="--volume renders SPLIT's views (train, val or test; default test) from the volume to <i>_volume.png beside the "
                          "frames and prints their PSNR / SSIM against the model's own render of the same views")
+    ap.add_argument("--volume-finetune", type=int, default=0, metavar="ITERS",
+                    help="--volume then fine-tunes the baked sigma and coefficients for ITERS Adam steps against the train split's own "
+                         "pixels with the support frozen (volume.finetune; rank 0) and also writes <...>_volume<RES>_ft<ITERS>.npz; with "
+                         "--volume-preview the PSNR / SSIM against the split's ground-truth images before and after are printed (default 0: "
+                         "the bake alone)")
+    ap.add_argument("--volume-finetune-batch", type=int, default=4096, metavar="N",
+                    help="rays per --volume-finetune step (default 4096)")
+    ap.add_argument("--volume-lr-sigma", type=float, default=None, metavar="X",
+                    help="--volume-finetune's Adam rate of sigma (default: volume.Finetuner's 0.1)")
+    ap.add_argument("--volume-lr-coef", type=float, default=None, metavar="X",
+                    help="--volume-finetune's Adam rate of the SH coefficients (default: volume.Finetuner's 0.01)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--dist-weight", type=float, default=None, metavar="LAMBDA",
@@ -178,7 +189,8 @@ if __name__ == "__main__":
         run.density_grid(args.density_grid, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True)
     if args.volume is not None:
         run.bake_volume(args.volume, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], degree=args.volume_degree, sigma_min=args.volume_sigma_min,
-                        save=True, preview=args.volume_preview)
+                        save=True, preview=args.volume_preview, finetune=args.volume_finetune, finetune_batch=args.volume_finetune_batch,
+                        finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None})
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

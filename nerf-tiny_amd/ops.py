@@ -1069,3 +1069,63 @@ def volume_render(sigma, coef, occ, block, lo, step, origins, dirs, tmin, tmax, 
                                                  float(dt), float(t_stop), _abi.f32_array(background), ptr(rgb), ptr(maps), ptr(steps),
                                                  _stream(sigma)))
     return rgb, maps, steps
+
+
+def _vol_acc(t, what, shape):
+    if t.device.type != "cuda" or t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: a contiguous int64 device tensor of shape {tuple(shape)}")
+    return t
+
+
+def volume_render_backward(sigma, coef, occ, block, lo, step, origins, dirs, tmin, tmax, dt, t_stop, background, g_rgb, g_maps, acc_sigma,
+                           acc_coef):
+    """Rule VG: the gradient of volume_render's march for the upstream g_rgb[N, 3] and g_maps[N, 2] (or None), ADDED IN PLACE to the int64
+    fixed-point accumulators acc_sigma (sigma's shape) and acc_coef (coef's shape), in units of 2^-40
+    (nerf_hip_volume_render_backward).  The kernel recomputes the march.  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    dev = sigma.device
+    block = min(int(block), 2**31 - 1)
+    if occ.device != dev or occ.dtype != torch.uint8 or not occ.is_contiguous() or (
+            block >= 1 and tuple(occ.shape) != volume_block_dims((nx, ny, nz), block)):
+        raise ValueError(f"occ {tuple(occ.shape)} {occ.dtype}: the contiguous uint8 block occupancy of sigma for block={block}")
+    acc_sigma = _vol_acc(acc_sigma, "acc_sigma", sigma.shape)
+    acc_coef = _vol_acc(acc_coef, "acc_coef", coef.shape)
+    origins = origins.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    N = int(origins.shape[0])
+    if dirs.shape != origins.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and origins {tuple(origins.shape)} differ")
+    win = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev).expand(N).contiguous() if torch.as_tensor(t).dim() == 0 else \
+        torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous()
+    tmin, tmax = win(tmin), win(tmax)
+    if tmin.shape[0] != N or tmax.shape[0] != N:
+        raise ValueError(f"tmin / tmax: a scalar or one entry per ray ({N})")
+    g_rgb = _vol_f32(g_rgb.detach().to(dev, torch.float32).contiguous(), "g_rgb", (N, 3))
+    if g_maps is not None:
+        g_maps = _vol_f32(g_maps.detach().to(dev, torch.float32).contiguous(), "g_maps", (N, 2))
+    ptr = lambda t: t.data_ptr() if N else None
+    _abi.check(_abi.lib().nerf_hip_volume_render_backward(sigma.data_ptr(), coef.data_ptr(), occ.data_ptr(), nx, ny, nz, degree, block,
+                                                          _abi.f32_array(lo), _abi.f32_array(step), ptr(origins), ptr(dirs), ptr(tmin),
+                                                          ptr(tmax), N, float(dt), float(t_stop), _abi.f32_array(background), ptr(g_rgb),
+                                                          ptr(g_maps) if g_maps is not None else None, acc_sigma.data_ptr(),
+                                                          acc_coef.data_ptr(), _stream(sigma)))
+
+
+def volume_adam_step(sigma, coef, index, acc_sigma, acc_coef, m, v, grad_scale, step, lr_sigma, lr_coef, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Rule VU: one Adam step IN PLACE over the words of the points index[n] (int32, device: the ascending active list of the volume as
+    baked) from the fixed-point accumulators, which are zeroed; m, v [n, 1 + 3 ncoef] fp32 are the moments (nerf_hip_volume_adam_step).
+    A sigma that is not > 0 stays as it is, with its moments.  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    dev = sigma.device
+    if not torch.is_tensor(index) or index.device.type != "cuda":
+        raise ValueError("index: a device tensor")
+    index, n = _vol_index(index, dev)
+    acc_sigma = _vol_acc(acc_sigma, "acc_sigma", sigma.shape)
+    acc_coef = _vol_acc(acc_coef, "acc_coef", coef.shape)
+    words = 1 + 3 * int(coef.shape[3])
+    m = _vol_f32(m, "m", (n, words))
+    v = _vol_f32(v, "v", (n, words))
+    ptr = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_adam_step(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, ptr(index), n, acc_sigma.data_ptr(),
+                                                    acc_coef.data_ptr(), ptr(m), ptr(v), float(grad_scale), int(step), float(lr_sigma),
+                                                    float(lr_coef), float(beta1), float(beta2), float(eps), _stream(sigma)))

@@ -580,14 +580,20 @@ class NeRFRunner:
             np.savez(path, sigma=sigma, lo=lo32, hi=hi32, step=grid_step(lo32, hi32, shape), iter=np.int64(self.last_iter))
         return sigma
 
-    def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None):
+    def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
+                    finetune_batch=4096, finetune_lr=None):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
         split is rendered FROM THE VOLUME (volume.render_views: no network) and, with save, written to ``<i>_volume.png`` beside the
         display frames; the frames are scored against NeRFModel.render of the same views (metrics.image_metrics) and one ``[VOLUME]``
         line prints the mean PSNR / SSIM.  Under a launcher only rank 0 bakes, renders and writes, without any collective (the comparison
-        frames are rendered whole on rank 0, not through render_view's sharded path); the other ranks return None at once."""
+        frames are rendered whole on rank 0, not through render_view's sharded path); the other ranks return None at once.
+        finetune > 0: the baked volume is then fine-tuned for that many Adam steps of finetune_batch rays against the TRAIN split's own
+        pixels with the support frozen (volume.finetune; finetune_lr: None, (lr_sigma, lr_coef) or Finetuner's keywords), on rank 0 as
+        the bake; the fine-tuned volume is returned and, with save, also written to ``..._volume<res>_ft<finetune>.npz``; one more
+        ``[VOLUME] ... finetune`` line prints the first and the last batch loss and, with preview, the split's PSNR / SSIM against its
+        GROUND-TRUTH images before and after.  finetune = 0 computes, prints and writes nothing new."""
         import numpy as np
 
         from . import volume
@@ -597,6 +603,8 @@ class NeRFRunner:
 
         if preview is not None and preview not in ("train", "val", "test"):
             raise ValueError(f"preview={preview!r}: None, 'train', 'val' or 'test'")
+        if int(finetune) != finetune or finetune < 0:
+            raise ValueError(f"finetune={finetune!r}: a number of steps >= 0")
         if self.rank != 0:
             return None
         shape = grid_shape(res)
@@ -637,6 +645,33 @@ class NeRFRunner:
             print(f"[VOLUME] {self.last_iter} {preview} preview vs model.render [PSNR] {np.mean(psnr):.3f} dB [SSIM] {np.mean(ssim):.4f} "
                   f"[{rays.pic_num} views]")
             self.last_volume_preview = {"psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim)), "views": rays.pic_num}
+        if finetune:
+            def against_truth(v):
+                rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[preview]
+                H, W = rays.height, rays.width
+                truth = rays.pixels.view(rays.pic_num, H, W, 3)
+                ms = [image_metrics(volume.render_views(v, rays.poses[i:i + 1], self.K_inv, H, W)[0], truth[i:i + 1]) for i in range(rays.pic_num)]
+                return float(np.mean([float(m["psnr"][0]) for m in ms])), float(np.mean([float(m["ssim"][0]) for m in ms]))
+
+            lrs = {} if finetune_lr is None else (dict(finetune_lr) if isinstance(finetune_lr, dict) else
+                                                  dict(zip(("lr_sigma", "lr_coef"), finetune_lr)))
+            before = against_truth(vol) if preview is not None else None
+            t0 = time.perf_counter()
+            vol, losses = volume.finetune(vol, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), **lrs)
+            losses = losses.cpu().numpy()
+            seconds = time.perf_counter() - t0
+            self.last_volume_finetune = {"iters": int(finetune), "first_loss": float(losses[0]), "last_loss": float(losses[-1]), "seconds": seconds}
+            scores = ""
+            if preview is not None:
+                after = against_truth(vol)
+                scores = (f", {preview} views vs ground truth [PSNR] {before[0]:.3f} -> {after[0]:.3f} dB [SSIM] {before[1]:.4f} -> "
+                          f"{after[1]:.4f}")
+                self.last_volume_finetune.update(psnr_before=before[0], psnr_after=after[0], ssim_before=before[1], ssim_after=after[1])
+            print(f"[VOLUME] {self.last_iter} finetune {int(finetune)} steps of {int(finetune_batch)} train rays: batch loss {losses[0]:.3e} -> "
+                  f"{losses[-1]:.3e}{scores}, {seconds:.2f} s")
+            if save:
+                tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
+                volume.save(self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + "_ft" + str(int(finetune)) + ".npz", vol)
         return vol
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,

@@ -7,6 +7,11 @@ looks it up at points, ``save`` / ``load`` keep it as a plain ``.npz``.  The exa
 include/nerf_hip.h.  An APPROXIMATE product of its own: a uniform-step estimator over interpolated values, not the renderer's coarse
 + fine composite; ``NeRFModel.render`` is untouched by it.
 
+FINE-TUNING (rules VG and VU).  The bake only projects the field onto the lattice; ``render_backward`` is the
+gradient of the march with respect to sigma and the coefficients, accumulated exactly in int64 fixed point (``grad_buffers``,
+``gradients``), ``render_train`` is ``render`` with that gradient under torch.autograd, and ``Finetuner`` / ``finetune`` optimise the
+baked values against ground-truth pixels with the support frozen: the active list of the volume as baked never grows.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -97,6 +102,123 @@ def render_views(vol, poses_bound17, K_inv, H, W, dt=None, t_stop=1e-3, backgrou
     far = pb[:, 16].repeat_interleave(H * W)
     rgb, maps, steps = render(vol, o, d, near, far, dt=dt, t_stop=t_stop, background=background)
     return rgb.view(n, H, W, 3), maps.view(n, H, W, 2), steps.view(n, H, W, 2)
+
+
+class VolumeGrad(NamedTuple):
+    acc_sigma: torch.Tensor   # [nx, ny, nz] int64: sums of llrint(x 2^40)
+    acc_coef: torch.Tensor    # [nx, ny, nz, (degree + 1)^2, 3] int64
+
+
+def grad_buffers(vol):
+    """Zeroed accumulators of rule VG for ``vol``: 8 bytes per parameter."""
+    _on_device(vol.sigma, "volume.grad_buffers")
+    return VolumeGrad(torch.zeros(vol.sigma.shape, dtype=torch.int64, device=vol.sigma.device),
+                      torch.zeros(vol.coef.shape, dtype=torch.int64, device=vol.sigma.device))
+
+
+def render_backward(vol, grad, origins, dirs, tmin, tmax, g_rgb, g_maps=None, dt=None, t_stop=1e-3, background=(0.0, 0.0, 0.0)):
+    """Rule VG: the gradient of ``render``'s (rgb, maps) of these rays, for the upstream g_rgb [N, 3] and g_maps [N, 2] (None: zeros),
+    with respect to vol.sigma and vol.coef, ACCUMULATED into ``grad`` (grad_buffers).  The sums are integers: the accumulators hold the
+    same bits whatever the ray order, the batch split or vol.block.  Misses and rays with an upstream value that is not finite add
+    nothing.  The early end at t_stop is a constant of the gradient.  -> grad"""
+    _on_device(vol.sigma, "volume.render_backward")
+    dt = default_dt(vol) if dt is None else float(dt)
+    ops.volume_render_backward(vol.sigma.detach(), vol.coef.detach(), vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(),
+                               _on_device(origins, "volume.render_backward"), torch.as_tensor(dirs), tmin, tmax, dt, t_stop, background,
+                               _on_device(g_rgb, "volume.render_backward"), None if g_maps is None else torch.as_tensor(g_maps),
+                               grad.acc_sigma, grad.acc_coef)
+    return grad
+
+
+def gradients(grad, scale=1.0):
+    """The accumulators read as fp32: (d_sigma [nx, ny, nz], d_coef [nx, ny, nz, ncoef, 3]) = fp32((double(acc) 2^-40) scale)."""
+    f = lambda a: ((a.to(torch.float64) * 2.0 ** -_abi.VOLUME_GRAD_SHIFT) * float(scale)).to(torch.float32)
+    return f(grad.acc_sigma), f(grad.acc_coef)
+
+
+class _RenderTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sigma, coef, vol, origins, dirs, tmin, tmax, dt, t_stop, background):
+        rgb, maps, steps = ops.volume_render(sigma.detach(), coef.detach(), vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(), origins, dirs,
+                                             tmin, tmax, dt, t_stop, background)
+        ctx.vol = vol._replace(sigma=sigma.detach(), coef=coef.detach())
+        ctx.args = (origins, dirs, tmin, tmax, dt, t_stop, background)
+        ctx.mark_non_differentiable(steps)
+        return rgb, maps, steps
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_maps, _g_steps):
+        origins, dirs, tmin, tmax, dt, t_stop, background = ctx.args
+        if g_rgb is None:
+            g_rgb = torch.zeros(origins.reshape(-1, 3).shape[0], 3, device=ctx.vol.sigma.device)
+        grad = render_backward(ctx.vol, grad_buffers(ctx.vol), origins, dirs, tmin, tmax, g_rgb, g_maps, dt=dt, t_stop=t_stop,
+                               background=background)
+        d_sigma, d_coef = gradients(grad)
+        return (d_sigma if ctx.needs_input_grad[0] else None, d_coef if ctx.needs_input_grad[1] else None) + (None,) * 8
+
+
+def render_train(vol, origins, dirs, tmin, tmax, dt=None, t_stop=1e-3, background=(0.0, 0.0, 0.0)):
+    """``render`` under torch.autograd: the same (rgb, maps, steps), bit for bit, with rgb and maps carrying gradients to vol.sigma and
+    vol.coef where those require them (render_backward into fresh grad_buffers, then gradients).  vol.occ must be blocks(vol.sigma,
+    vol.block) of the CURRENT sigma, or a superset of it."""
+    _on_device(vol.sigma, "volume.render_train")
+    dt = default_dt(vol) if dt is None else float(dt)
+    return _RenderTrain.apply(vol.sigma, vol.coef, vol, _on_device(origins, "volume.render_train"), torch.as_tensor(dirs), tmin, tmax, dt,
+                              float(t_stop), tuple(float(b) for b in background))
+
+
+class Finetuner:
+    """Adam on a baked volume's sigma and coefficients against target pixels, the support frozen (rule VU): it works on its own copies
+    (the input volume keeps its bits) and holds the active list of the volume as baked, the moments [n, 1 + 3 ncoef], the int64
+    accumulators and the step count.  A sigma that reaches 0 stays 0, so the baked occupancy stays valid throughout.  The default rates
+    are starting values from a CPU prototype on a hand-made volume, not a measurement on a scene."""
+
+    def __init__(self, vol, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8):
+        _on_device(vol.sigma, "volume.Finetuner")
+        self.vol = vol._replace(sigma=vol.sigma.detach().clone(), coef=vol.coef.detach().clone())
+        self.index = active(vol.sigma)
+        words = 1 + 3 * int(vol.coef.shape[3])
+        self.m = torch.zeros(int(self.index.shape[0]), words, device=vol.sigma.device)
+        self.v = torch.zeros_like(self.m)
+        self.grad = grad_buffers(self.vol)
+        self.lr_sigma, self.lr_coef, self.betas, self.eps = float(lr_sigma), float(lr_coef), (float(betas[0]), float(betas[1])), float(eps)
+        self.steps = 0
+
+    def step(self, origins, dirs, tmin, tmax, target, background=(0.0, 0.0, 0.0), dt=None, t_stop=1e-3):
+        """One update on the rays' mean squared colour error against target [N, 3]: forward, g_rgb = 2 (rgb - target) with
+        grad_scale = 1 / (3 N), backward, rule VU -> the batch's MSE before the update, a device scalar (no host sync)."""
+        dev = self.vol.sigma.device
+        rgb, _, _ = render(self.vol, origins, dirs, tmin, tmax, dt=dt, t_stop=t_stop, background=background)
+        diff = rgb - torch.as_tensor(target).to(dev, torch.float32).reshape(-1, 3)
+        n = max(int(rgb.shape[0]), 1)
+        render_backward(self.vol, self.grad, origins, dirs, tmin, tmax, 2.0 * diff, None, dt=dt, t_stop=t_stop, background=background)
+        self.steps += 1
+        ops.volume_adam_step(self.vol.sigma, self.vol.coef, self.index, self.grad.acc_sigma, self.grad.acc_coef, self.m, self.v,
+                             1.0 / (3.0 * n), self.steps, self.lr_sigma, self.lr_coef, self.betas[0], self.betas[1], self.eps)
+        return (diff * diff).mean() if rgb.numel() else torch.zeros((), device=dev)
+
+    def volume(self):
+        """The current state as a Volume, its occupancy rebuilt by ``blocks`` (the arrays are the tuner's own, not copies)."""
+        return self.vol._replace(occ=blocks(self.vol.sigma, self.vol.block))
+
+
+def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.0, 0.0), **lrs):
+    """``iters`` Finetuner steps on batches of ``batch`` pixels drawn (with replacement) from the data.DeviceRays ``rays``: the origin is
+    the pose's translation, the direction ops.rays' unit d_wrd (as mesh.camera_rays forms it), the window the pose's near / far, the
+    target the pixel's colour.  lrs: Finetuner's keywords.  -> (the fine-tuned Volume, the batch losses [iters] on the device)."""
+    dev = _on_device(vol.sigma, "volume.finetune").device
+    tuner = Finetuner(vol, **lrs)
+    gen = torch.Generator(device=dev)
+    if seed is not None:
+        gen.manual_seed(int(seed))
+    losses = []
+    for _ in range(int(iters)):
+        idx = torch.randint(int(rays.num_pix), (int(batch),), device=dev, generator=gen)
+        row, col, pix, pb, _ = rays.gather(idx)
+        _, d_wrd, _ = ops.rays(row, col, pb, torch.as_tensor(K_inv), 2)
+        o = pb[:, :15].reshape(-1, 3, 5)[:, :, 3].contiguous()
+        losses.append(tuner.step(o, d_wrd, pb[:, 15].contiguous(), pb[:, 16].contiguous(), pix, background=background))
+    return tuner.volume(), (torch.stack(losses) if losses else torch.zeros(0, device=dev))
 
 
 def save(path, vol):
