@@ -70,7 +70,8 @@ extern "C" {
                                      nerf_hip_normals_ws_offset, nerf_hip_forward_normals, nerf_hip_normal_composite;
                                      the nerf_hip_volume_* calls (with NERF_HIP_VOLUME_MAX_STEPS);
                                      nerf_hip_volume_render_backward, nerf_hip_volume_adam_step
-                                     (with NERF_HIP_VOLUME_GRAD_SHIFT) */
+                                     (with NERF_HIP_VOLUME_GRAD_SHIFT); nerf_hip_volume_member_mask,
+                                     nerf_hip_volume_tv_backward, nerf_hip_volume_upsample, nerf_hip_volume_prune */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1449,6 +1450,68 @@ int nerf_hip_volume_render_backward(const float* sigma, const float* coef, const
 int nerf_hip_volume_adam_step(float* sigma, float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
                               int64_t* acc_sigma, int64_t* acc_coef, float* m, float* v, double grad_scale, int64_t step,
                               double lr_sigma, double lr_coef, double beta1, double beta2, double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Coarse-to-fine fine-tuning: a total-variation prior over a level's active list, added to
+ * rule VG's accumulators; the x2 refinement of the lattice; pruning.  Nothing of the calls above changes.  A refined or pruned volume
+ * is fine-tuned with a NEW active list and new moments, so rule VU's frozen-support invariant holds level by level.
+ *
+ * VM. MEMBER MASK.  member[nx][ny][nz] uint8: 1 at the lattice points of index[n], 0 elsewhere.  Every byte is written; an index outside
+ *    the lattice is skipped.  The mask is the membership test of the active list AS BAKED FOR THIS LEVEL, not a test of the current
+ *    sigma: the positive set shrinks while training (rule VU), the list does not.
+ *
+ * VT. TOTAL VARIATION OVER THE MEMBERS, added to rule VG's accumulators.  A WORD is sigma or one coefficient (m, ch).  Everything is
+ *    fp64 on the fp32 values widened, evaluated as bracketed.  For a member p, a word x and an axis a, with e_a the axis' unit step:
+ *       d_a(p) = x(p + e_a) - x(p)    if p + e_a lies inside the lattice AND is a member,    else 0
+ *       tau(p) = sqrt((((d_x d_x) + (d_y d_y)) + (d_z d_z)) + eps)
+ *       Q_a(p) = llrint(y),  y = (w (d_a(p) / tau(p))) 2^40 clamped to [-2^62, 2^62]    (a NaN gives 0; rule VG's fixed point)
+ *    with w = w_sigma for the sigma word and w_coef for a coefficient word.  The accumulator word of p receives -Q_a(p) and the one of
+ *    p + e_a receives +Q_a(p), as INTEGER adds: the gradient of w sum_(p member) tau(p), one word's terms summed.  A difference whose
+ *    far end is outside the lattice or not a member is the CONSTANT 0, so
+ *       - a point that is not a member receives nothing: rule VU's "accumulators outside the list stay zero" survives;
+ *       - the loss is a function of the members' values alone;
+ *       - the integers one call adds to the words of one type (sigma, or one (m, ch)) sum to exactly 0 over the lattice.
+ *    One thread per (entry of index[n], word) GATHERS: its own three Q_a(q), and Q_a(q - e_a) for every axis on which q - e_a lies inside
+ *    the lattice and is a member (that point's tau is recomputed); then one plain read-modify-write of its own accumulator word.  No
+ *    atomic, no LDS, no dependence on the launch order.  The indices of one call must be distinct (an active list's are); index[n]
+ *    may be any chunk of the level's list, member is the mask of the WHOLE list; an entry that is outside the lattice or not a member is
+ *    skipped.  A dead sigma word (sigma not > 0) receives its terms like any other; rule VU ignores and zeroes them.
+ *    OVERFLOW PRECONDITION.  |d_a / tau| <= 1, so a word receives at most six terms of magnitude <= w <= 2^16 per call: within rule VG's.
+ *
+ * VX. x2 REFINEMENT.  The new lattice has 2 n - 1 points per axis over the same box: lo' = lo, step' = step * 0.5f (exact).  Per axis
+ *       U(v)[2 i]     = v[i]                                  (taken as it is: no arithmetic, the bits are kept)
+ *       U(v)[2 i + 1] = v[i] + (0.5f * (v[i + 1] - v[i]))     (rule VL's lerp at f = 0.5, fp32)
+ *    applied along z first, then y, then x, to sigma and to every coefficient word.  One thread per (new point, word) gathers the at
+ *    most eight coarse values and interpolates only along the axes whose new index is odd: bit for bit the three separable passes.
+ *    sigma' >= 0 wherever sigma >= 0; rule VA's active set of sigma' is the refined support and contains every coarse active point's
+ *    image.  A fine point between a coarse active point and an inactive one can lie outside it and still hold half a coefficient: no
+ *    contributing sample reads it, and rule VP at threshold 0 clears it.  (2 nx - 1)(2 ny - 1)(2 nz - 1) >= 2^31 is refused.
+ *
+ * VP. PRUNE, in place, two stream-ordered kernels.  First, pointwise,
+ *       sigma'(p) = sigma(p)  if sigma(p) > threshold (false on NaN),    +0 otherwise
+ *    then every coefficient word of a point that is not active (rule VA) in sigma' becomes +0; the others keep their bits.
+ *    threshold is finite and >= 0; threshold = 0 clears only stale coefficients (and a NaN or negative sigma).
+ *
+ * All four are enqueue-only and check every argument on the host first (NERF_HIP_ERR_ARG), as the calls above: the lattice, the degree,
+ * a negative count or one >= 2^31, eps not finite or not > 0, a weight that is not finite, < 0 or > 2^16, a threshold that is not
+ * finite or < 0, a NULL pointer or one that is not aligned to its element.  n = 0, or both weights 0, succeeds and launches no kernel
+ * of rule VT.  Data-dependent addresses are built only from indices already compared with the size of their array.
+ * ------------------------------------------------------------------------------------------- */
+
+/* VM: member[nx][ny][nz] (device, uint8) of index[0 .. n). */
+int nerf_hip_volume_member_mask(const int32_t* index, int64_t n, int nx, int ny, int nz, uint8_t* member, void* stream);
+
+/* VT over index[0 .. n) with the mask of the whole list: the terms are ADDED IN PLACE to rule VG's accumulators. */
+int nerf_hip_volume_tv_backward(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                                const uint8_t* member, double w_sigma, double w_coef, double eps, int64_t* acc_sigma, int64_t* acc_coef,
+                                void* stream);
+
+/* VX: sigma2 [2 nx - 1][2 ny - 1][2 nz - 1], coef2 [..][ncoef][3] (device; they do not overlap the inputs). */
+int nerf_hip_volume_upsample(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, float* sigma2, float* coef2,
+                             void* stream);
+
+/* VP, in place. */
+int nerf_hip_volume_prune(float* sigma, float* coef, int nx, int ny, int nz, int degree, float threshold, void* stream);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,11 @@ _PROTOS = {
                                                   C.c_float, C.c_float, _p, _p, _p, _p, _p, _p]),
     "nerf_hip_volume_adam_step": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p, _p, C.c_double, C.c_int64,
                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
+    "nerf_hip_volume_member_mask": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "nerf_hip_volume_tv_backward": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, C.c_double, C.c_double,
+                                              C.c_double, _p, _p, _p]),
+    "nerf_hip_volume_upsample": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_prune": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

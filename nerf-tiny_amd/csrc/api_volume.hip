@@ -1,6 +1,6 @@
 // api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
-// VR, VG and VU): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on the caller's stream.
-// No allocation, no host sync.
+// VR, VG, VU, VM, VT, VX and VP): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
+// the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
 #include "api_common.h"
@@ -369,6 +369,106 @@ int nerf_hip_volume_adam_step(float* sigma, float* coef, int nx, int ny, int nz,
   a.c1 = 1.0 - pow_by_squaring(beta1, step);
   a.c2 = 1.0 - pow_by_squaring(beta2, step);
   HIP_TRY(launch_volume_adam_step(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_member_mask(const int32_t* index, int64_t n, int nx, int ny, int nz, uint8_t* member, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (int rc = check_out(member, "member", 1)) return rc;
+  if (n > 0) {
+    if (int rc = check_out(index, "index", 4)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VolMemberArgs a;
+  memset(&a, 0, sizeof(a));
+  a.index = index;
+  a.n = n;
+  a.npts = (long long)nx * ny * nz;
+  a.member = member;
+  HIP_TRY(launch_volume_member_mask(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_tv_backward(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                                const uint8_t* member, double w_sigma, double w_coef, double eps, int64_t* acc_sigma, int64_t* acc_coef,
+                                void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (!(eps > 0.0 && isfinite(eps))) return fail(NERF_HIP_ERR_ARG, "eps=%g must be finite and > 0", eps);
+  if (!(w_sigma >= 0.0 && w_sigma <= 65536.0) || !(w_coef >= 0.0 && w_coef <= 65536.0))
+    return fail(NERF_HIP_ERR_ARG, "w_sigma=%g w_coef=%g: the weights lie in [0, 2^16]", w_sigma, w_coef);
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(member, "member", 1)) return rc;
+  if (int rc = check_out(acc_sigma, "acc_sigma", 8)) return rc;
+  if (int rc = check_out(acc_coef, "acc_coef", 8)) return rc;
+  if (n == 0 || (w_sigma == 0.0 && w_coef == 0.0)) return NERF_HIP_OK;
+  if (int rc = check_out(index, "index", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolTvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.index = index;
+  a.n = n;
+  a.member = member;
+  a.w_sigma = w_sigma;
+  a.w_coef = w_coef;
+  a.eps = eps;
+  a.acc_sigma = reinterpret_cast<long long*>(acc_sigma);
+  a.acc_coef = reinterpret_cast<long long*>(acc_coef);
+  HIP_TRY(launch_volume_tv_backward(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_upsample(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, float* sigma2, float* coef2,
+                             void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if ((2ll * nx - 1) * (2ll * ny - 1) >= (1ll << 31) || (2ll * nx - 1) * (2ll * ny - 1) * (2ll * nz - 1) >= (1ll << 31))
+    return fail(NERF_HIP_ERR_ARG, "volume %d x %d x %d: the refined lattice must stay below 2^31 points", nx, ny, nz);
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(sigma2, "sigma2", 4)) return rc;
+  if (int rc = check_out(coef2, "coef2", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolUpsampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.sigma2 = sigma2;
+  a.coef2 = coef2;
+  HIP_TRY(launch_volume_upsample(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_prune(float* sigma, float* coef, int nx, int ny, int nz, int degree, float threshold, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (!(threshold >= 0.0f && isfinite(threshold))) return fail(NERF_HIP_ERR_ARG, "threshold=%g must be finite and >= 0", (double)threshold);
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolPruneArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.threshold = threshold;
+  HIP_TRY(launch_volume_prune(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

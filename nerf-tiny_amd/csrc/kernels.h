@@ -836,6 +836,41 @@ struct VolAdamArgs {
 hipError_t launch_volume_render_backward(const VolGradArgs& a, int ncoef, hipStream_t st);
 hipError_t launch_volume_adam_step(const VolAdamArgs& a, hipStream_t st);
 
+// ---- coarse-to-fine fine-tuning (volume_refine.hip; nerf_hip_volume_member_mask, _tv_backward, _upsample, _prune, DESIGN.md section
+// 3h-14; rules VM, VT, VX and VP of include/nerf_hip.h) ----
+struct VolMemberArgs {
+  const int* index;        // [n]
+  long long n, npts;
+  unsigned char* member;   // [npts]
+};
+
+struct VolTvArgs {
+  const float *sigma, *coef;        // [npts], [npts][ncoef][3]
+  int nx, ny, nz, ncoef;
+  const int* index;                 // [n]: distinct
+  long long n;
+  const unsigned char* member;      // [npts]: rule VM's mask of the level's whole list
+  double w_sigma, w_coef, eps;
+  long long *acc_sigma, *acc_coef;  // rule VG's accumulators
+};
+
+struct VolUpsampleArgs {
+  const float *sigma, *coef;  // the coarse lattice nx x ny x nz
+  int nx, ny, nz, ncoef;
+  float *sigma2, *coef2;      // the lattice (2 nx - 1) x (2 ny - 1) x (2 nz - 1)
+};
+
+struct VolPruneArgs {
+  float *sigma, *coef;
+  int nx, ny, nz, ncoef;
+  float threshold;
+};
+
+hipError_t launch_volume_member_mask(const VolMemberArgs& a, hipStream_t st);
+hipError_t launch_volume_tv_backward(const VolTvArgs& a, hipStream_t st);
+hipError_t launch_volume_upsample(const VolUpsampleArgs& a, hipStream_t st);
+hipError_t launch_volume_prune(const VolPruneArgs& a, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

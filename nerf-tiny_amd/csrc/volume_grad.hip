@@ -137,13 +137,6 @@ __device__ inline double vol_v(const VolHit& h, const float (&g)[3], double gD, 
   return ((((double)g[0] * (double)h.c[0] + (double)g[1] * (double)h.c[1]) + (double)g[2] * (double)h.c[2]) + gD * (double)h.tk) + gA1;
 }
 
-// rule VG's fixed point: llrint(x 2^40) of the product clamped to +-2^62; a NaN adds 0
-__device__ inline long long vol_fix(double x) {
-  double y = x * (double)(1ll << VOL_GRAD_SHIFT);
-  y = fmin(fmax(y, -(double)(1ll << 62)), (double)(1ll << 62));
-  return x == x ? llrint(y) : 0ll;
-}
-
 // a value of lane src (wave-uniform) in every lane
 __device__ inline float lane_value(float x, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src)); }
 __device__ inline double lane_value(double x, int src) {

@@ -1,5 +1,5 @@
 // volume_parts.h -- the device helpers the SH radiance volume kernels share (volume.hip: the lookups and the march; volume_grad.hip:
-// the march's backward pass; DESIGN.md sections 3h-12 and 3h-13): rule VL's cell, corners and interpolation and rule VS's basis, in the
+// the march's backward pass; volume_refine.hip: the TV prior; DESIGN.md sections 3h-12 to 3h-14): rule VL's cell, corners and interpolation and rule VS's basis, in the
 // fp32 order the rules of include/nerf_hip.h fix.  No kernel and no launch lives here.  Everything has internal linkage: every includer
 // gets its own copy.
 #pragma once
@@ -84,6 +84,13 @@ __device__ inline void vol_color(const float* __restrict__ coef, const long long
   }
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) rgb[ch] = fminf(fmaxf(vol_tri(v[ch], f), 0.0f), 1.0f);
+}
+
+// rule VG's fixed point: llrint(x 2^40) of the product clamped to +-2^62; a NaN adds 0
+__device__ inline long long vol_fix(double x) {
+  double y = x * (double)(1ll << VOL_GRAD_SHIFT);
+  y = fmin(fmax(y, -(double)(1ll << 62)), (double)(1ll << 62));
+  return x == x ? llrint(y) : 0ll;
 }
 
 }  // namespace

@@ -122,6 +122,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--volume-finetune's Adam rate of sigma (default: volume.Finetuner's 0.1)")
     ap.add_argument("--volume-lr-coef", type=float, default=None, metavar="X",
                     help="--volume-finetune's Adam rate of the SH coefficients (default: volume.Finetuner's 0.01)")
+    ap.add_argument("--volume-tv-sigma", type=float, default=0.0, metavar="X",
+                    help="--volume-finetune adds X * the mean total variation of sigma over the active lattice points to its loss "
+                         "(default 0: no prior)")
+    ap.add_argument("--volume-tv-coef", type=float, default=0.0, metavar="X",
+                    help="--volume-finetune adds X * the mean total variation of the SH coefficients (summed over the words) to its loss "
+                         "(default 0)")
+    ap.add_argument("--volume-upsample-at", type=int, nargs="+", default=(), metavar="I",
+                    help="--volume-finetune doubles the lattice (2 n - 1 points per axis, trilinear) after step I (strictly increasing, each in "
+                         "(0, ITERS)) and goes on with a fresh optimiser; k of them write <...>_volume<RES>_ft<ITERS>_up<k>.npz")
+    ap.add_argument("--volume-prune", type=float, default=None, metavar="X",
+                    help="before each --volume-upsample-at doubling, densities at or below X become 0 and the coefficients nothing reads "
+                         "any more are cleared (default: no pruning)")
     ap.add_argument("--mask-weight", type=float, default=None, metavar="LAMBDA",
                     help="train with ray_loss + LAMBDA * the alpha-mask loss on the opacity maps (needs RGBA images; ini key MASK_WEIGHT; default 0)")
     ap.add_argument("--dist-weight", type=float, default=None, metavar="LAMBDA",
@@ -190,7 +202,9 @@ if __name__ == "__main__":
     if args.volume is not None:
         run.bake_volume(args.volume, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], degree=args.volume_degree, sigma_min=args.volume_sigma_min,
                         save=True, preview=args.volume_preview, finetune=args.volume_finetune, finetune_batch=args.volume_finetune_batch,
-                        finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None})
+                        finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None},
+                        finetune_tv=(args.volume_tv_sigma, args.volume_tv_coef) if (args.volume_tv_sigma or args.volume_tv_coef) else None,
+                        finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

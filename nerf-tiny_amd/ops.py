@@ -1129,3 +1129,55 @@ def volume_adam_step(sigma, coef, index, acc_sigma, acc_coef, m, v, grad_scale, 
     _abi.check(_abi.lib().nerf_hip_volume_adam_step(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, ptr(index), n, acc_sigma.data_ptr(),
                                                     acc_coef.data_ptr(), ptr(m), ptr(v), float(grad_scale), int(step), float(lr_sigma),
                                                     float(lr_coef), float(beta1), float(beta2), float(eps), _stream(sigma)))
+
+
+def volume_member_mask(index, shape):
+    """Rule VM: member[nx, ny, nz] uint8, 1 at the lattice points of index[n] (int32, device) and 0 elsewhere
+    (nerf_hip_volume_member_mask).  Enqueue only."""
+    if not torch.is_tensor(index) or index.device.type != "cuda":
+        raise ValueError("index: a device tensor")
+    index, n = _vol_index(index, index.device)
+    nx, ny, nz = (int(x) for x in shape)
+    member = torch.empty(nx, ny, nz, dtype=torch.uint8, device=index.device)
+    _abi.check(_abi.lib().nerf_hip_volume_member_mask(index.data_ptr() if n else None, n, nx, ny, nz, member.data_ptr(), _stream(index)))
+    return member
+
+
+def volume_tv_backward(sigma, coef, index, member, w_sigma, w_coef, eps, acc_sigma, acc_coef):
+    """Rule VT: the gradient of w_sigma sum_p tau_sigma(p) + w_coef sum_p sum_words tau(p) over the members, ADDED IN PLACE to rule VG's
+    int64 accumulators for the words of the points index[n] (int32, device, distinct: the level's active list or a chunk of it); member
+    is volume_member_mask of the WHOLE list (nerf_hip_volume_tv_backward).  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    dev = sigma.device
+    if not torch.is_tensor(index) or index.device.type != "cuda":
+        raise ValueError("index: a device tensor")
+    index, n = _vol_index(index, dev)
+    if member.device != dev or member.dtype != torch.uint8 or not member.is_contiguous() or tuple(member.shape) != (nx, ny, nz):
+        raise ValueError(f"member {tuple(member.shape)} {member.dtype}: the contiguous uint8 mask of sigma's shape {(nx, ny, nz)}")
+    acc_sigma = _vol_acc(acc_sigma, "acc_sigma", sigma.shape)
+    acc_coef = _vol_acc(acc_coef, "acc_coef", coef.shape)
+    _abi.check(_abi.lib().nerf_hip_volume_tv_backward(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, index.data_ptr() if n else None, n,
+                                                      member.data_ptr(), float(w_sigma), float(w_coef), float(eps), acc_sigma.data_ptr(),
+                                                      acc_coef.data_ptr(), _stream(sigma)))
+
+
+def volume_upsample(sigma, coef):
+    """Rule VX: the volume on the lattice of 2 n - 1 points per axis (nerf_hip_volume_upsample) -> (sigma2, coef2), new tensors.
+    Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    shape2 = (2 * nx - 1, 2 * ny - 1, 2 * nz - 1)
+    if shape2[0] * shape2[1] * shape2[2] >= 2**31:
+        raise ValueError(f"volume {(nx, ny, nz)}: the refined lattice {shape2} must stay below 2^31 points")
+    sigma2 = torch.empty(shape2, device=sigma.device)
+    coef2 = torch.empty(shape2 + tuple(coef.shape[3:]), device=sigma.device)
+    _abi.check(_abi.lib().nerf_hip_volume_upsample(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, sigma2.data_ptr(), coef2.data_ptr(),
+                                                   _stream(sigma)))
+    return sigma2, coef2
+
+
+def volume_prune(sigma, coef, threshold):
+    """Rule VP IN PLACE: sigma not > threshold becomes +0, then the coefficients of the points that are not active (rule VA) in the
+    result become +0 (nerf_hip_volume_prune).  Enqueue only."""
+    sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
+    _abi.check(_abi.lib().nerf_hip_volume_prune(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, float(threshold), _stream(sigma)))
+    return sigma, coef

@@ -581,7 +581,7 @@ class NeRFRunner:
         return sigma
 
     def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
-                    finetune_batch=4096, finetune_lr=None):
+                    finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
@@ -593,7 +593,11 @@ class NeRFRunner:
         pixels with the support frozen (volume.finetune; finetune_lr: None, (lr_sigma, lr_coef) or Finetuner's keywords), on rank 0 as
         the bake; the fine-tuned volume is returned and, with save, also written to ``..._volume<res>_ft<finetune>.npz``; one more
         ``[VOLUME] ... finetune`` line prints the first and the last batch loss and, with preview, the split's PSNR / SSIM against its
-        GROUND-TRUTH images before and after.  finetune = 0 computes, prints and writes nothing new."""
+        GROUND-TRUTH images before and after.  finetune = 0 computes, prints and writes nothing new.
+        COARSE TO FINE (volume.finetune): finetune_tv = None or (tv_sigma, tv_coef), the total-variation weights; finetune_upsample =
+        the step counts after which the lattice is doubled (k of them give a (2^k (res - 1) + 1)^3 volume, written as
+        ``..._ft<finetune>_up<k>.npz``); finetune_prune = None, or the density at or below which a point is cleared before each
+        doubling.  The finetune line then names the final lattice and the TV weights; without these arguments nothing changes."""
         import numpy as np
 
         from . import volume
@@ -605,9 +609,17 @@ class NeRFRunner:
             raise ValueError(f"preview={preview!r}: None, 'train', 'val' or 'test'")
         if int(finetune) != finetune or finetune < 0:
             raise ValueError(f"finetune={finetune!r}: a number of steps >= 0")
+        shape = grid_shape(res)
+        tv = (0.0, 0.0) if finetune_tv is None else tuple(float(w) for w in finetune_tv)
+        if len(tv) != 2:
+            raise ValueError(f"finetune_tv={finetune_tv!r}: None or (tv_sigma, tv_coef)")
+        if not finetune and (tuple(finetune_upsample) or finetune_prune is not None or any(tv)):
+            raise ValueError("finetune_tv / finetune_upsample / finetune_prune need finetune > 0")
+        if finetune:
+            volume._check_tv(tv[0], tv[1], 1e-9)
+            ups, _ = volume.check_schedule(shape, finetune, finetune_upsample, finetune_prune)
         if self.rank != 0:
             return None
-        shape = grid_shape(res)
         self.model.eval()
         t0 = time.perf_counter()
         vol = self.model.bake_volume(np.asarray(lo, np.float32), np.asarray(hi, np.float32), shape, degree=degree, sigma_min=sigma_min,
@@ -657,21 +669,34 @@ class NeRFRunner:
                                                   dict(zip(("lr_sigma", "lr_coef"), finetune_lr)))
             before = against_truth(vol) if preview is not None else None
             t0 = time.perf_counter()
-            vol, losses = volume.finetune(vol, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), **lrs)
+            if any(tv):
+                lrs.update(tv_sigma=tv[0], tv_coef=tv[1])
+            vol, losses = volume.finetune(vol, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), upsample_at=ups,
+                                          prune=finetune_prune, **lrs)
             losses = losses.cpu().numpy()
             seconds = time.perf_counter() - t0
-            self.last_volume_finetune = {"iters": int(finetune), "first_loss": float(losses[0]), "last_loss": float(losses[-1]), "seconds": seconds}
+            self.last_volume_finetune = {"iters": int(finetune), "first_loss": float(losses[0]), "last_loss": float(losses[-1]), "seconds": seconds,
+                                         "shape": tuple(int(n) for n in vol.sigma.shape)}
             scores = ""
             if preview is not None:
                 after = against_truth(vol)
                 scores = (f", {preview} views vs ground truth [PSNR] {before[0]:.3f} -> {after[0]:.3f} dB [SSIM] {before[1]:.4f} -> "
                           f"{after[1]:.4f}")
                 self.last_volume_finetune.update(psnr_before=before[0], psnr_after=after[0], ssim_before=before[1], ssim_after=after[1])
-            print(f"[VOLUME] {self.last_iter} finetune {int(finetune)} steps of {int(finetune_batch)} train rays: batch loss {losses[0]:.3e} -> "
-                  f"{losses[-1]:.3e}{scores}, {seconds:.2f} s")
+            extra = ""
+            if ups:
+                extra += f", {len(ups)} upsample{'s' if len(ups) > 1 else ''} to {'x'.join(str(int(n)) for n in vol.sigma.shape)}"
+                if finetune_prune is not None:
+                    extra += f" pruned at {float(finetune_prune):g}"
+            if any(tv):
+                extra += f", TV sigma {tv[0]:g} coef {tv[1]:g}"
+            print(f"[VOLUME] {self.last_iter} finetune {int(finetune)} steps of {int(finetune_batch)} train rays{extra}: batch loss "
+                  f"{losses[0]:.3e} -> {losses[-1]:.3e}{scores}, {seconds:.2f} s")
             if save:
                 tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
-                volume.save(self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + "_ft" + str(int(finetune)) + ".npz", vol)
+                up = f"_up{len(ups)}" if ups else ""
+                volume.save(self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + "_ft" + str(int(finetune)) + up +
+                            ".npz", vol)
         return vol
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,

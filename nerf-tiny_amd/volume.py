@@ -12,6 +12,11 @@ gradient of the march with respect to sigma and the coefficients, accumulated ex
 ``gradients``), ``render_train`` is ``render`` with that gradient under torch.autograd, and ``Finetuner`` / ``finetune`` optimise the
 baked values against ground-truth pixels with the support frozen: the active list of the volume as baked never grows.
 
+COARSE TO FINE (rules VM, VT, VX and VP).  ``upsample`` doubles the lattice (2 n - 1 points per axis over the
+same box), ``prune`` clears thin density and the coefficients nothing can read any more, ``member_mask`` / ``tv_backward`` add the
+gradient of a total-variation prior over a level's active list to the same accumulators.  ``Finetuner(tv_sigma=, tv_coef=)`` applies
+the prior every step and ``finetune(upsample_at=, prune=)`` trains level by level, each level with a fresh active list and fresh moments.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -167,14 +172,62 @@ def render_train(vol, origins, dirs, tmin, tmax, dt=None, t_stop=1e-3, backgroun
                               float(t_stop), tuple(float(b) for b in background))
 
 
+def member_mask(vol, index):
+    """Rule VM: member[nx, ny, nz] uint8, 1 at the lattice points of ``index`` (an active list of ``vol``'s lattice), 0 elsewhere."""
+    _on_device(vol.sigma, "volume.member_mask")
+    return ops.volume_member_mask(_on_device(index, "volume.member_mask"), vol.sigma.shape)
+
+
+def tv_backward(vol, grad, index, member, w_sigma, w_coef, eps=1e-9):
+    """Rule VT: the gradient of w_sigma sum_p tau_sigma(p) + w_coef sum_p sum_words tau(p), p over the members, with respect to
+    vol.sigma and vol.coef, ACCUMULATED into ``grad`` (grad_buffers) for the words of the points ``index`` (distinct; the level's list
+    or a chunk of it -- ``member`` is member_mask of the whole list).  tau(p) = sqrt(sum_a d_a(p)^2 + eps) over the forward differences
+    to members.  Points outside the mask receive nothing; the integers added to one word type sum to 0.  -> grad"""
+    _on_device(vol.sigma, "volume.tv_backward")
+    ops.volume_tv_backward(vol.sigma.detach(), vol.coef.detach(), _on_device(index, "volume.tv_backward"), member, w_sigma, w_coef, eps,
+                           grad.acc_sigma, grad.acc_coef)
+    return grad
+
+
+def upsampled_shape(shape):
+    return tuple(2 * int(n) - 1 for n in shape)
+
+
+def upsample(vol):
+    """Rule VX: a new Volume on the lattice of 2 n - 1 points per axis over the same box (the step halved exactly), every value
+    the trilinear mean of rule VL at f = 0.5 or the coarse value itself.  The block edge is kept; the occupancy is rebuilt by
+    ``blocks``.  The input keeps its bits."""
+    _on_device(vol.sigma, "volume.upsample")
+    sigma2, coef2 = ops.volume_upsample(vol.sigma.detach(), vol.coef.detach())
+    step2 = (np.asarray(vol.step, np.float32) * np.float32(0.5)).astype(np.float32)
+    return Volume(sigma2, coef2, blocks(sigma2, vol.block), np.asarray(vol.lo, np.float32).copy(), step2, vol.block, vol.degree)
+
+
+def prune(vol, sigma_min):
+    """Rule VP on copies: sigma not > sigma_min (finite, >= 0) becomes 0, and the coefficients of every point that is then not active
+    (rule VA) become 0 -> a new Volume with its occupancy rebuilt.  sigma_min = 0 clears only stale coefficients.  The input keeps
+    its bits."""
+    _on_device(vol.sigma, "volume.prune")
+    sigma, coef = ops.volume_prune(vol.sigma.detach().clone(), vol.coef.detach().clone(), sigma_min)
+    return vol._replace(sigma=sigma, coef=coef, occ=blocks(sigma, vol.block))
+
+
+_prune = prune  # finetune's keyword ``prune`` hides the function
+
+
 class Finetuner:
     """Adam on a baked volume's sigma and coefficients against target pixels, the support frozen (rule VU): it works on its own copies
     (the input volume keeps its bits) and holds the active list of the volume as baked, the moments [n, 1 + 3 ncoef], the int64
     accumulators and the step count.  A sigma that reaches 0 stays 0, so the baked occupancy stays valid throughout.  The default rates
-    are starting values from a CPU prototype on a hand-made volume, not a measurement on a scene."""
+    are starting values from a CPU prototype on a hand-made volume, not a measurement on a scene.
 
-    def __init__(self, vol, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8):
+    tv_sigma / tv_coef > 0 add a total-variation prior over the active list (rule VT): the loss becomes
+    MSE + tv_sigma mean_p tau_sigma(p) + tv_coef mean_p sum_words tau(p), the means over the n members.  With both 0 no mask is
+    allocated and no kernel is launched: the tuner is the plain one, bit for bit."""
+
+    def __init__(self, vol, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8, tv_sigma=0.0, tv_coef=0.0, tv_eps=1e-9):
         _on_device(vol.sigma, "volume.Finetuner")
+        _check_tv(tv_sigma, tv_coef, tv_eps)
         self.vol = vol._replace(sigma=vol.sigma.detach().clone(), coef=vol.coef.detach().clone())
         self.index = active(vol.sigma)
         words = 1 + 3 * int(vol.coef.shape[3])
@@ -183,15 +236,21 @@ class Finetuner:
         self.grad = grad_buffers(self.vol)
         self.lr_sigma, self.lr_coef, self.betas, self.eps = float(lr_sigma), float(lr_coef), (float(betas[0]), float(betas[1])), float(eps)
         self.steps = 0
+        self.tv_sigma, self.tv_coef, self.tv_eps = float(tv_sigma), float(tv_coef), float(tv_eps)
+        self.member = member_mask(self.vol, self.index) if (self.tv_sigma > 0.0 or self.tv_coef > 0.0) else None
 
     def step(self, origins, dirs, tmin, tmax, target, background=(0.0, 0.0, 0.0), dt=None, t_stop=1e-3):
         """One update on the rays' mean squared colour error against target [N, 3]: forward, g_rgb = 2 (rgb - target) with
-        grad_scale = 1 / (3 N), backward, rule VU -> the batch's MSE before the update, a device scalar (no host sync)."""
+        grad_scale = 1 / (3 N), backward, the TV prior's gradient when it is on (w = tv / n * 3 N: rule VU multiplies the whole
+        accumulator by grad_scale), rule VU -> the batch's MSE before the update, a device scalar (no host sync)."""
         dev = self.vol.sigma.device
         rgb, _, _ = render(self.vol, origins, dirs, tmin, tmax, dt=dt, t_stop=t_stop, background=background)
         diff = rgb - torch.as_tensor(target).to(dev, torch.float32).reshape(-1, 3)
         n = max(int(rgb.shape[0]), 1)
         render_backward(self.vol, self.grad, origins, dirs, tmin, tmax, 2.0 * diff, None, dt=dt, t_stop=t_stop, background=background)
+        if self.member is not None and int(self.index.shape[0]) > 0:
+            k = 3.0 * n / int(self.index.shape[0])
+            tv_backward(self.vol, self.grad, self.index, self.member, self.tv_sigma * k, self.tv_coef * k, self.tv_eps)
         self.steps += 1
         ops.volume_adam_step(self.vol.sigma, self.vol.coef, self.index, self.grad.acc_sigma, self.grad.acc_coef, self.m, self.v,
                              1.0 / (3.0 * n), self.steps, self.lr_sigma, self.lr_coef, self.betas[0], self.betas[1], self.eps)
@@ -201,18 +260,71 @@ class Finetuner:
         """The current state as a Volume, its occupancy rebuilt by ``blocks`` (the arrays are the tuner's own, not copies)."""
         return self.vol._replace(occ=blocks(self.vol.sigma, self.vol.block))
 
+    def refined(self, prune=None):
+        """The next level of a coarse-to-fine schedule: this tuner's volume, pruned (rule VP at ``prune``) unless that is None, refined
+        (rule VX) -> a FRESH Finetuner on it with the same rates and TV weights: a new active list, zero moments, the step count at 0.
+        This tuner's moments, accumulators and mask are released first; it takes no further step."""
+        level = self.volume()
+        self.m = self.v = self.grad = self.member = None
+        if prune is not None:
+            level = _prune(level, prune)
+        return Finetuner(upsample(level), lr_sigma=self.lr_sigma, lr_coef=self.lr_coef, betas=self.betas, eps=self.eps,
+                         tv_sigma=self.tv_sigma, tv_coef=self.tv_coef, tv_eps=self.tv_eps)
 
-def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.0, 0.0), **lrs):
+
+def _check_tv(tv_sigma, tv_coef, tv_eps):
+    for name, w in (("tv_sigma", tv_sigma), ("tv_coef", tv_coef)):
+        if not (np.isfinite(float(w)) and float(w) >= 0.0):
+            raise ValueError(f"{name}={w!r}: a finite weight >= 0")
+    if not (np.isfinite(float(tv_eps)) and float(tv_eps) > 0.0):
+        raise ValueError(f"tv_eps={tv_eps!r}: finite and > 0")
+
+
+def check_schedule(shape, iters, upsample_at=(), prune=None):
+    """Validates a coarse-to-fine schedule for a lattice of ``shape`` (ValueError) -> (the sorted step counts as a tuple, the final
+    lattice's shape): strictly increasing ints in (0, iters), every level's lattice below 2^31 points, prune None or finite and >= 0."""
+    iters = int(iters)
+    ups = []
+    for u in upsample_at:
+        if isinstance(u, bool) or int(u) != u:
+            raise ValueError(f"upsample_at={tuple(upsample_at)!r}: step counts are ints")
+        ups.append(int(u))
+    for i, u in enumerate(ups):
+        if not (0 < u < iters):
+            raise ValueError(f"upsample_at={tuple(ups)!r}: every step count lies in (0, iters={iters})")
+        if i and not ups[i - 1] < u:
+            raise ValueError(f"upsample_at={tuple(ups)!r}: strictly increasing")
+    if prune is not None and not (np.isfinite(float(prune)) and float(prune) >= 0.0):
+        raise ValueError(f"prune={prune!r}: None, or a finite density >= 0")
+    shape = tuple(int(n) for n in shape)
+    for _ in ups:
+        shape = upsampled_shape(shape)
+        if shape[0] * shape[1] * shape[2] >= 2**31:
+            raise ValueError(f"upsample_at={tuple(ups)!r}: the lattice {shape} of the last level must stay below 2^31 points")
+    return tuple(ups), shape
+
+
+def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.0, 0.0), upsample_at=(), prune=None, **lrs):
     """``iters`` Finetuner steps on batches of ``batch`` pixels drawn (with replacement) from the data.DeviceRays ``rays``: the origin is
     the pose's translation, the direction ops.rays' unit d_wrd (as mesh.camera_rays forms it), the window the pose's near / far, the
-    target the pixel's colour.  lrs: Finetuner's keywords.  -> (the fine-tuned Volume, the batch losses [iters] on the device)."""
+    target the pixel's colour.  lrs: Finetuner's keywords (the rates and the TV weights).
+
+    COARSE TO FINE.  ``upsample_at``: strictly increasing step counts in (0, iters); after that many steps the tuner's volume is pruned
+    (``prune``: None, or rule VP's threshold) and refined (``upsample``), the old tuner's buffers are released and a FRESH Finetuner
+    takes over (Finetuner.refined): a new active list, zero moments, the bias correction restarting at step 1, the same rates and TV weights; the march's
+    default dt follows the halved step.  The whole schedule is validated before the first step (ValueError).
+    -> (the fine-tuned Volume, the batch losses [iters] on the device, all levels concatenated)."""
     dev = _on_device(vol.sigma, "volume.finetune").device
+    ups, _ = check_schedule(vol.sigma.shape, iters, upsample_at, prune)
+    _check_tv(lrs.get("tv_sigma", 0.0), lrs.get("tv_coef", 0.0), lrs.get("tv_eps", 1e-9))
     tuner = Finetuner(vol, **lrs)
     gen = torch.Generator(device=dev)
     if seed is not None:
         gen.manual_seed(int(seed))
     losses = []
-    for _ in range(int(iters)):
+    for it in range(int(iters)):
+        if it in ups:
+            tuner = tuner.refined(prune)
         idx = torch.randint(int(rays.num_pix), (int(batch),), device=dev, generator=gen)
         row, col, pix, pb, _ = rays.gather(idx)
         _, d_wrd, _ = ops.rays(row, col, pb, torch.as_tensor(K_inv), 2)
