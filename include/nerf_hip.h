@@ -71,7 +71,8 @@ extern "C" {
                                      the nerf_hip_volume_* calls (with NERF_HIP_VOLUME_MAX_STEPS);
                                      nerf_hip_volume_render_backward, nerf_hip_volume_adam_step
                                      (with NERF_HIP_VOLUME_GRAD_SHIFT); nerf_hip_volume_member_mask,
-                                     nerf_hip_volume_tv_backward, nerf_hip_volume_upsample, nerf_hip_volume_prune */
+                                     nerf_hip_volume_tv_backward, nerf_hip_volume_upsample, nerf_hip_volume_prune;
+                                     the nerf_hip_volume_compact_* calls */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1512,6 +1513,64 @@ int nerf_hip_volume_upsample(const float* sigma, const float* coef, int nx, int 
 
 /* VP, in place. */
 int nerf_hip_volume_prune(float* sigma, float* coef, int nx, int ny, int nz, int degree, float threshold, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Compact volumes: the deployment form of a volume.  Only the rows of the ACTIVE lattice
+ * points (rule VA) are stored, behind an int32 slot lattice; the coefficients are fp32 or fp16.  Nothing of the calls above changes.
+ *
+ * VC. THE COMPACT FORM of a dense volume (sigma, coef) on the lattice nx x ny x nz whose ascending active list (rule VA) is index[n],
+ *    ncoef = (degree + 1)^2:
+ *       slot[nx][ny][nz]  int32: r at the lattice point index[r], -1 everywhere else -- a slot is the point's rank in rule VA's list;
+ *       sigma_rows[n]     fp32:  sigma_rows[r] = sigma[index[r]], bit for bit;
+ *       coef_rows[n][S]   half = 0: fp32, S = 3 ncoef, the dense row's words in the dense order (m-major, channel fastest);
+ *                         half = 1: fp16, S = 3 ncoef rounded up to a multiple of 4 (4 / 12 / 28 for degree 0 / 1 / 2); every half is
+ *                         the round-to-nearest-even fp16 of the fp32 word (a finite value past 65504 becomes +-inf, a NaN stays a
+ *                         NaN), the pad halves are +0; every row starts on an 8-byte boundary and is read in 8-byte words;
+ *       occ, lo, step, block, degree as in the dense form; occ is rule VO's occupancy of the dense sigma.
+ *    PACK gathers the rows of index[n] from dense arrays (one thread per row word; an index outside the lattice gives a +0 row); with
+ *    index = NULL the rows are the lattice's points in order (n = nx ny nz): the conversion of fp32 rows to fp16 rows.  UNPACK
+ *    scatters rows to the points index[n] of dense arrays THE CALLER HAS ZEROED, fp16 widened (exact); an index outside the lattice
+ *    is skipped.  SLOTS fills the lattice with -1 and stores r at index[r] (distinct indices; one outside the lattice is skipped).
+ *
+ *    VC-L. LOOKUP: rule VL with each corner's values taken through its slot.  A corner with slot < 0 or slot >= n has sigma +0 and
+ *    an all-zero coefficient row -- a slot outside [0, n) is never turned into an address; any other corner has sigma_rows[slot] and
+ *    the row coef_rows[slot], an fp16 row widened to fp32 word by word.  Everything after that is rule VL's fp32 arithmetic in rule
+ *    VL's order (a zero row goes through the same products and sums).
+ *    VC-R. MARCH: rule VR over VC-L, the passing over of empty blocks included.
+ *
+ *    EQUIVALENCE (proved in csrc/volume_compact.hip).  With U the dense volume that holds a compact volume's rows at the points whose
+ *    slot lies in [0, n) and +0 elsewhere, VC-L equals VL on U and VC-R equals VR on U, bit for bit.  For ANY dense volume V -- garbage
+ *    at its inactive points included: negative sigma, -0, NaN, non-zero coefficients -- rgb, maps and both columns of steps of VC-R on
+ *    the fp32 pack of V equal rule VR on V bit for bit, and those of the fp16 pack equal rule VR on V with every coefficient replaced
+ *    by fp32(fp16(.)).
+ *
+ * All five are enqueue-only and check every argument on the host first (NERF_HIP_ERR_ARG) as the calls above do, and in addition
+ * half outside {0, 1}, n outside [0, nx ny nz], and fp16 coef_rows that are not 8-byte aligned.  n = 0 is legal: the row pointers may
+ * then be NULL, every corner is inactive, sample gives zeros and render the background with zero maps.
+ * ------------------------------------------------------------------------------------------- */
+
+/* VC's slot[nx][ny][nz] (device, int32) of the active list index[0 .. n). */
+int nerf_hip_volume_compact_slots(const int32_t* index, int64_t n, int nx, int ny, int nz, int32_t* slot, void* stream);
+
+/* VC's PACK: dense (sigma, coef) -> sigma_rows[n], coef_rows[n][S] (device).  index may be NULL (the identity; then n = nx ny nz);
+ * sigma and sigma_rows may both be NULL to convert the coefficients only. */
+int nerf_hip_volume_compact_pack(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                                 int half, float* sigma_rows, void* coef_rows, void* stream);
+
+/* VC's UNPACK into dense arrays the caller has zeroed.  coef_rows and coef may both be NULL to scatter sigma only. */
+int nerf_hip_volume_compact_unpack(const float* sigma_rows, const void* coef_rows, int half, const int32_t* index, int64_t n, int nx, int ny,
+                                   int nz, int degree, float* sigma, float* coef, void* stream);
+
+/* VC-L at points[M][3] along dirs[M][3] -> out_sigma[M], out_rgb[M][3] (device, fp32), as nerf_hip_volume_sample. */
+int nerf_hip_volume_compact_sample(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n, int half, int nx, int ny,
+                                   int nz, int degree, const float* lo3, const float* step3, const float* points, const float* dirs,
+                                   int64_t M, float* out_sigma, float* out_rgb, void* stream);
+
+/* VC-R over N rays -> rgb[N][3], maps[N][2], steps[N][2], as nerf_hip_volume_render. */
+int nerf_hip_volume_compact_render(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n, int half,
+                                   const uint8_t* occ, int nx, int ny, int nz, int degree, int block, const float* lo3, const float* step3,
+                                   const float* origins, const float* dirs, const float* tmin, const float* tmax, int64_t N, float dt,
+                                   float t_stop, const float* background3, float* rgb, float* maps, int32_t* steps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,13 @@ _PROTOS = {
                                               C.c_double, _p, _p, _p]),
     "nerf_hip_volume_upsample": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
     "nerf_hip_volume_prune": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p]),
+    "nerf_hip_volume_compact_slots": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "nerf_hip_volume_compact_pack": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_compact_unpack": (C.c_int, [_p, _p, C.c_int, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_compact_sample": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int64,
+                                                 _p, _p, _p]),
+    "nerf_hip_volume_compact_render": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p,
+                                                 _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

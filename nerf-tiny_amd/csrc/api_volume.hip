@@ -1,5 +1,5 @@
 // api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
-// VR, VG, VU, VM, VT, VX and VP): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
+// VR, VG, VU, VM, VT, VX, VP and VC): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
 // the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -76,6 +76,40 @@ double pow_by_squaring(double beta, int64_t step) {
     b = b * b;
   }
   return p;
+}
+
+// ---- rule VC's arguments ----
+
+int check_half(int half) {
+  if (half != 0 && half != 1) return fail(NERF_HIP_ERR_ARG, "half=%d: 0 (fp32 rows) or 1 (fp16 rows)", half);
+  return NERF_HIP_OK;
+}
+
+// the rows of a compact volume: at most one per lattice point
+int check_rows(int64_t n, int nx, int ny, int nz) {
+  if (n < 0 || n > (int64_t)nx * ny * nz) return fail(NERF_HIP_ERR_ARG, "n=%lld: the rows of a %d x %d x %d lattice number 0 .. %lld", (long long)n, nx, ny, nz, (long long)nx * ny * nz);
+  return NERF_HIP_OK;
+}
+
+// the arrays a lookup reads; without rows (n = 0) only the slot lattice is there
+int check_compact(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n, int half, int nx, int ny, int nz) {
+  if (int rc = check_half(half)) return rc;
+  if (int rc = check_rows(n, nx, ny, nz)) return rc;
+  if (int rc = check_out(slot, "slot", 4)) return rc;
+  if (n > 0) {
+    if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+    if (int rc = check_out(coef_rows, "coef_rows", half ? 8 : 4)) return rc;
+  }
+  return NERF_HIP_OK;
+}
+
+VolCompact compact(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n) {
+  VolCompact c;
+  c.slot = slot;
+  c.sigma_rows = sigma_rows;
+  c.coef_rows = coef_rows;
+  c.n = n;
+  return c;
 }
 
 int active(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, int32_t* index, int64_t max_n, bool emit,
@@ -469,6 +503,164 @@ int nerf_hip_volume_prune(float* sigma, float* coef, int nx, int ny, int nz, int
   a.ncoef = (degree + 1) * (degree + 1);
   a.threshold = threshold;
   HIP_TRY(launch_volume_prune(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_slots(const int32_t* index, int64_t n, int nx, int ny, int nz, int32_t* slot, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_rows(n, nx, ny, nz)) return rc;
+  if (int rc = check_out(slot, "slot", 4)) return rc;
+  if (n > 0) {
+    if (int rc = check_out(index, "index", 4)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VolSlotsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.index = index;
+  a.n = n;
+  a.npts = (long long)nx * ny * nz;
+  a.slot = slot;
+  HIP_TRY(launch_volume_compact_slots(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_pack(const float* sigma, const float* coef, int nx, int ny, int nz, int degree, const int32_t* index, int64_t n,
+                                 int half, float* sigma_rows, void* coef_rows, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_half(half)) return rc;
+  if (int rc = check_rows(n, nx, ny, nz)) return rc;
+  if (n == 0) return NERF_HIP_OK;
+  if (!index && n != (int64_t)nx * ny * nz) return fail(NERF_HIP_ERR_ARG, "n=%lld: without an index the rows are the lattice's %lld points", (long long)n, (long long)nx * ny * nz);
+  if ((sigma == nullptr) != (sigma_rows == nullptr)) return fail(NERF_HIP_ERR_ARG, "sigma and sigma_rows: both, or both null");
+  if (sigma) {
+    if (int rc = check_out(sigma, "sigma", 4)) return rc;
+    if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+  }
+  if (int rc = check_out(coef, "coef", 4)) return rc;
+  if (int rc = check_out(coef_rows, "coef_rows", half ? 8 : 4)) return rc;
+  if (index) {
+    if (int rc = check_out(index, "index", 4)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VolPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = const_cast<float*>(sigma);
+  a.coef = const_cast<float*>(coef);
+  a.npts = (long long)nx * ny * nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.index = index;
+  a.n = n;
+  a.sigma_rows = sigma_rows;
+  a.coef_rows = coef_rows;
+  HIP_TRY(launch_volume_compact_pack(a, half != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_unpack(const float* sigma_rows, const void* coef_rows, int half, const int32_t* index, int64_t n, int nx, int ny,
+                                   int nz, int degree, float* sigma, float* coef, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_half(half)) return rc;
+  if (int rc = check_rows(n, nx, ny, nz)) return rc;
+  if ((coef == nullptr) != (coef_rows == nullptr) && n > 0) return fail(NERF_HIP_ERR_ARG, "coef and coef_rows: both, or both null");
+  if (int rc = check_out(sigma, "sigma", 4)) return rc;
+  if (coef) {
+    if (int rc = check_out(coef, "coef", 4)) return rc;
+  }
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+  if (coef) {
+    if (int rc = check_out(coef_rows, "coef_rows", half ? 8 : 4)) return rc;
+  }
+  if (int rc = check_out(index, "index", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma = sigma;
+  a.coef = coef;
+  a.npts = (long long)nx * ny * nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.index = index;
+  a.n = n;
+  a.sigma_rows = const_cast<float*>(sigma_rows);
+  a.coef_rows = const_cast<void*>(coef_rows);
+  HIP_TRY(launch_volume_compact_unpack(a, half != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_sample(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n, int half, int nx, int ny,
+                                   int nz, int degree, const float* lo3, const float* step3, const float* points, const float* dirs,
+                                   int64_t M, float* out_sigma, float* out_rgb, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("M", M)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (int rc = check_compact(slot, sigma_rows, coef_rows, n, half, nx, ny, nz)) return rc;
+  if (M == 0) return NERF_HIP_OK;
+  if (int rc = check_out(points, "points", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(out_sigma, "out_sigma", 4)) return rc;
+  if (int rc = check_out(out_rgb, "out_rgb", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolCompactSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = compact(slot, sigma_rows, coef_rows, n);
+  a.g = lattice(nx, ny, nz, lo3, step3);
+  a.points = points;
+  a.dirs = dirs;
+  a.M = M;
+  a.out_sigma = out_sigma;
+  a.out_rgb = out_rgb;
+  HIP_TRY(launch_volume_compact_sample(a, (degree + 1) * (degree + 1), half != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_render(const int32_t* slot, const float* sigma_rows, const void* coef_rows, int64_t n, int half,
+                                   const uint8_t* occ, int nx, int ny, int nz, int degree, int block, const float* lo3, const float* step3,
+                                   const float* origins, const float* dirs, const float* tmin, const float* tmax, int64_t N, float dt,
+                                   float t_stop, const float* background3, float* rgb, float* maps, int32_t* steps, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_count("N", N)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (!(dt > 0.0f && isfinite(dt))) return fail(NERF_HIP_ERR_ARG, "dt=%g: the step along the ray must be finite and > 0", (double)dt);
+  if (!(t_stop >= 0.0f && t_stop < 1.0f)) return fail(NERF_HIP_ERR_ARG, "t_stop=%g: the transmittance to stop at lies in [0, 1)", (double)t_stop);
+  if (!background3) return fail(NERF_HIP_ERR_ARG, "background3 is null");
+  if (int rc = check_finite3(background3, "background", "the background colour")) return rc;
+  if (int rc = check_compact(slot, sigma_rows, coef_rows, n, half, nx, ny, nz)) return rc;
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (N == 0) return NERF_HIP_OK;
+  if (int rc = check_out(origins, "origins", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(tmin, "tmin", 4)) return rc;
+  if (int rc = check_out(tmax, "tmax", 4)) return rc;
+  if (int rc = check_out(rgb, "rgb", 4)) return rc;
+  if (int rc = check_out(maps, "maps", 4)) return rc;
+  if (int rc = check_out(steps, "steps", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolCompactRenderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = compact(slot, sigma_rows, coef_rows, n);
+  a.r.occ = occ;
+  a.r.g = lattice(nx, ny, nz, lo3, step3);
+  a.r.B = block;
+  a.r.bx = blocks_of(nx, block);
+  a.r.by = blocks_of(ny, block);
+  a.r.bz = blocks_of(nz, block);
+  a.r.origins = origins;
+  a.r.dirs = dirs;
+  a.r.tmin = tmin;
+  a.r.tmax = tmax;
+  a.r.N = N;
+  a.r.dt = dt;
+  a.r.t_stop = t_stop;
+  for (int c = 0; c < 3; ++c) a.r.bg[c] = background3[c];
+  a.r.rgb = rgb;
+  a.r.maps = maps;
+  a.r.steps = steps;
+  HIP_TRY(launch_volume_compact_render(a, (degree + 1) * (degree + 1), half != 0, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

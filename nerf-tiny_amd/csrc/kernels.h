@@ -871,6 +871,54 @@ hipError_t launch_volume_tv_backward(const VolTvArgs& a, hipStream_t st);
 hipError_t launch_volume_upsample(const VolUpsampleArgs& a, hipStream_t st);
 hipError_t launch_volume_prune(const VolPruneArgs& a, hipStream_t st);
 
+// ---- compact volumes (volume_compact.hip; the nerf_hip_volume_compact_* calls; rule VC of
+// include/nerf_hip.h): the rows of the active points behind an int32 slot lattice, fp32 or fp16 coefficients ----
+// halves of an fp16 coefficient row: 3 ncoef rounded up to a multiple of 4 (4 / 12 / 28), so a row is whole 8-byte words
+constexpr int vol_half_stride(int ncoef) { return (3 * ncoef + 3) & ~3; }
+
+struct VolCompact {
+  const int* slot;          // [nx][ny][nz]: the row of the point, or anything outside [0, n) where there is none
+  const float* sigma_rows;  // [n]
+  const void* coef_rows;    // [n][3 ncoef] fp32, or [n][vol_half_stride(ncoef)] fp16 (8-byte aligned)
+  long long n;
+};
+
+struct VolSlotsArgs {
+  const int* index;        // [n]
+  long long n, npts;
+  int* slot;               // [npts], filled with -1 by the launch sequence
+};
+
+// pack gathers dense -> rows, unpack scatters rows -> dense (zeroed by the caller); a null sigma pair / coef pair is left out
+struct VolPackArgs {
+  float *sigma, *coef;     // [npts], [npts][ncoef][3] (pack reads them, unpack writes them)
+  long long npts;
+  int ncoef;
+  const int* index;        // [n], or null: row r is point r
+  long long n;
+  float* sigma_rows;       // [n]
+  void* coef_rows;         // [n][stride]
+};
+
+struct VolCompactSampleArgs {
+  VolCompact c;
+  VolLattice g;
+  const float *points, *dirs;  // [M][3]
+  long long M;
+  float *out_sigma, *out_rgb;  // [M], [M][3]
+};
+
+struct VolCompactRenderArgs {
+  VolCompact c;
+  VolRenderArgs r;         // the dense march's arguments; its sigma and coef are not used
+};
+
+hipError_t launch_volume_compact_slots(const VolSlotsArgs& a, hipStream_t st);
+hipError_t launch_volume_compact_pack(const VolPackArgs& a, bool half, hipStream_t st);
+hipError_t launch_volume_compact_unpack(const VolPackArgs& a, bool half, hipStream_t st);
+hipError_t launch_volume_compact_sample(const VolCompactSampleArgs& a, int ncoef, bool half, hipStream_t st);
+hipError_t launch_volume_compact_render(const VolCompactRenderArgs& a, int ncoef, bool half, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

@@ -1,5 +1,5 @@
 // volume_parts.h -- the device helpers the SH radiance volume kernels share (volume.hip: the lookups and the march; volume_grad.hip:
-// the march's backward pass; volume_refine.hip: the TV prior; DESIGN.md sections 3h-12 to 3h-14): rule VL's cell, corners and interpolation and rule VS's basis, in the
+// the march's backward pass; volume_refine.hip: the TV prior; volume_compact.hip: the same lookups through a slot lattice; DESIGN.md sections 3h-12 to 3h-15): rule VL's cell, corners and interpolation and rule VS's basis, in the
 // fp32 order the rules of include/nerf_hip.h fix.  No kernel and no launch lives here.  Everything has internal linkage: every includer
 // gets its own copy.
 #pragma once
@@ -91,6 +91,76 @@ __device__ inline long long vol_fix(double x) {
   double y = x * (double)(1ll << VOL_GRAD_SHIFT);
   y = fmin(fmax(y, -(double)(1ll << 62)), (double)(1ll << 62));
   return x == x ? llrint(y) : 0ll;
+}
+
+// ---- rule VC-L: rule VL's corners taken through the slot lattice (volume_compact.hip) ----
+
+typedef _Float16 volc_half4 __attribute__((ext_vector_type(4)));  // one 8-byte word of an fp16 row
+
+// the corners' rows: the slot where it lies in [0, n), -1 otherwise -- only a checked slot ever becomes an address
+__device__ inline void volc_rows(const VolCompact& c, const long long (&p)[8], int (&r)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int s = c.slot[p[k]];
+    r[k] = (s >= 0 && (long long)s < c.n) ? s : -1;
+  }
+}
+
+// an inactive corner has sigma +0
+__device__ inline float volc_sigma(const float* __restrict__ sigma_rows, const int (&r)[8], const float (&f)[3]) {
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = r[k] >= 0 ? sigma_rows[r[k]] : 0.0f;
+  return vol_tri(v, f);
+}
+
+// row r's 3 NC words as fp32 (an fp16 row widened word by word: exact), all +0 for r < 0; the address is formed in 64 bits
+template <int NC>
+__device__ inline void volc_row(const float* __restrict__ rows, int r, float (&q)[NC * 3]) {
+#pragma unroll
+  for (int i = 0; i < NC * 3; ++i) q[i] = 0.0f;
+  if (r >= 0) {
+    const float* __restrict__ w = rows + (long long)r * (NC * 3);
+#pragma unroll
+    for (int i = 0; i < NC * 3; ++i) q[i] = w[i];
+  }
+}
+
+template <int NC>
+__device__ inline void volc_row(const _Float16* __restrict__ rows, int r, float (&q)[NC * 3]) {
+  constexpr int S = vol_half_stride(NC);
+#pragma unroll
+  for (int i = 0; i < NC * 3; ++i) q[i] = 0.0f;
+  if (r >= 0) {
+    const volc_half4* __restrict__ w = reinterpret_cast<const volc_half4*>(rows + (long long)r * S);
+#pragma unroll
+    for (int i = 0; i < S / 4; ++i) {
+      const volc_half4 h = w[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i * 4 + j < NC * 3) q[i * 4 + j] = (float)h[j];
+    }
+  }
+}
+
+// vol_color over rows: the same bracketed sums
+template <int NC, class T>
+__device__ inline void volc_color(const T* __restrict__ rows, const int (&r)[8], const float (&f)[3], const float (&Y)[9], float (&rgb)[3]) {
+  float v[3][8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    float q[NC * 3];
+    volc_row<NC>(rows, r[c], q);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float s = Y[0] * q[ch];
+#pragma unroll
+      for (int m = 1; m < NC; ++m) s = s + Y[m] * q[m * 3 + ch];
+      v[ch][c] = s;
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) rgb[ch] = fminf(fmaxf(vol_tri(v[ch], f), 0.0f), 1.0f);
 }
 
 }  // namespace

@@ -111,6 +111,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--volume-preview", nargs="?", const="test", default=None, choices=["train", "val", "test"], metavar="SPLIT",
                     help="--volume renders SPLIT's views (train, val or test; default test) from the volume to <i>_volume.png beside the "
                          "frames and prints their PSNR / SSIM against the model's own render of the same views")
+    ap.add_argument("--volume-compact", default=None, choices=["fp32", "fp16"],
+                    help="--volume writes the compact form: only the rows of the active lattice points behind an int32 slot lattice, the "
+                         "coefficients fp32 or fp16 (volume.CompactVolume; the march gives the dense form's bits, fp16 those of the rounded "
+                         "coefficients), to <...>_volume<RES>_c32.npz / _c16.npz; the dense coefficient array is never allocated unless "
+                         "--volume-finetune is given (default: the dense form)")
     ap.add_argument("--volume-finetune", type=int, default=0, metavar="ITERS",
                     help="--volume then fine-tunes the baked sigma and coefficients for ITERS Adam steps against the train split's own "
                          "pixels with the support frozen (volume.finetune; rank 0) and also writes <...>_volume<RES>_ft<ITERS>.npz; with "
@@ -204,7 +209,7 @@ if __name__ == "__main__":
                         save=True, preview=args.volume_preview, finetune=args.volume_finetune, finetune_batch=args.volume_finetune_batch,
                         finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None},
                         finetune_tv=(args.volume_tv_sigma, args.volume_tv_coef) if (args.volume_tv_sigma or args.volume_tv_coef) else None,
-                        finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune)
+                        finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune, compact=args.volume_compact)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

@@ -683,7 +683,7 @@ class NeRFModel(nn.Module):
         return ops.density_band(ps, lo32.tolist(), step.tolist(), shape, level, block, ws=ws)
 
     @torch.no_grad()
-    def bake_volume(self, lo, hi, res, degree=2, sigma_min=0.0, block=8, points_per_call=1 << 22):
+    def bake_volume(self, lo, hi, res, degree=2, sigma_min=0.0, block=8, points_per_call=1 << 22, compact=None):
         """The field baked into an SH radiance volume (volume.Volume; rules VA, VS and VO of include/nerf_hip.h) over the lattice of
         density_grid(lo, hi, res), every n >= 2: sigma is density_grid's, with values below ``sigma_min`` set to 0; the ACTIVE points --
         those a lookup with a positive sigma can read -- get the (degree + 1)^2 real spherical-harmonic coefficients of their colour,
@@ -691,7 +691,10 @@ class NeRFModel(nn.Module):
         direction, points -> query -> accumulate; every other point keeps 0.  ``block``: cells per edge of the marcher's occupancy
         blocks.  Always exact fp32 whatever ``bf16_mlp`` / ``split_mlp`` say, and bit-identical for every ``points_per_call``; a
         lower-degree bake is the leading slab of the degree-2 bake.  sigma_min = 0 keeps everything the field calls dense, its fog
-        included.  Dense storage: 4 + 12 (degree + 1)^2 bytes per lattice point."""
+        included.  Dense storage: 4 + 12 (degree + 1)^2 bytes per lattice point.
+        compact = "fp32" / "fp16": a volume.CompactVolume (rule VC) instead -- the SH terms are accumulated straight into the rows of
+        the active points (the same accumulate call on the rows seen as a small lattice of their own) and, for "fp16", converted at
+        the end; the dense coefficient array is never allocated.  Bit for bit volume.pack(bake_volume(...), compact)."""
         import numpy as np
 
         from . import ops, volume
@@ -705,6 +708,8 @@ class NeRFModel(nn.Module):
             raise ValueError(f"degree={degree!r}: 0, 1 or 2")
         if int(points_per_call) != points_per_call or int(points_per_call) < 1:
             raise ValueError(f"points_per_call={points_per_call!r}: an int >= 1")
+        if compact not in (None, "fp32", "fp16"):
+            raise ValueError(f"compact={compact!r}: None, 'fp32' or 'fp16'")
         lo32 = np.asarray(lo, dtype=np.float32).reshape(3)
         hi32 = np.asarray(hi, dtype=np.float32).reshape(3)
         step = grid_step(lo32, hi32, shape)
@@ -713,18 +718,33 @@ class NeRFModel(nn.Module):
             sigma = torch.where(sigma >= float(sigma_min), sigma, torch.zeros_like(sigma))
         index = ops.volume_active(sigma)
         ncoef = (int(degree) + 1) ** 2
-        coef = torch.zeros(*shape, ncoef, 3, device=dev)
+        n = int(index.shape[0])
+        if compact is None:
+            coef = torch.zeros(*shape, ncoef, 3, device=dev)
+        else:
+            # the rows as a lattice of their own for the accumulate and convert calls, which want two points per axis: (n4 / 4, 2, 2),
+            # n4 = n rounded up to a multiple of 4 and at least 8 -- at most 7 rows more than n, and the calls' bounds are the allocation's
+            n4 = max(8, (n + 3) // 4 * 4)
+            coef = torch.zeros(n4 // 4, 2, 2, ncoef, 3, device=dev)
         dirs = torch.from_numpy(volume.sh_dirs()).to(dev)
         ws = self._query_workspace(True, dev)
         per = int(points_per_call)
-        for p0 in range(0, int(index.shape[0]), per):
+        for p0 in range(0, n, per):
             idx = index[p0:p0 + per]
             pts = ops.volume_points(idx, shape, lo32.tolist(), step.tolist())
+            rows = idx if compact is None else torch.arange(p0, p0 + int(idx.shape[0]), dtype=torch.int32, device=dev)
             for k in range(dirs.shape[0]):
                 rgb, _ = ops.query(ps, pts, dirs[k].expand(pts.shape[0], 3).contiguous(), ws=ws)
-                ops.volume_sh_accumulate(coef, idx, rgb, k)
+                ops.volume_sh_accumulate(coef, rows, rgb, k)
         occ = ops.volume_blocks(sigma, block)
-        return volume.Volume(sigma, coef, occ, lo32, step, min(int(block), volume.ONE_BLOCK), int(degree))
+        if compact is None:
+            return volume.Volume(sigma, coef, occ, lo32, step, min(int(block), volume.ONE_BLOCK), int(degree))
+        slot = ops.volume_compact_slots(index, shape)
+        sigma_rows = sigma.reshape(-1)[index.long()]
+        if compact == "fp16":
+            _, coef = ops.volume_compact_pack(None, coef, None, True)
+        coef_rows = coef.reshape(n4, -1)[:n]
+        return volume.CompactVolume(slot, sigma_rows, coef_rows, occ, lo32, step, min(int(block), volume.ONE_BLOCK), int(degree), tuple(shape))
 
     @torch.no_grad()
     def extract_mesh(self, lo, hi, res, level, color=True, normals="grid", band=None, min_faces=None, keep_largest=None, simplify=None,

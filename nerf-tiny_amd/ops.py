@@ -1181,3 +1181,136 @@ def volume_prune(sigma, coef, threshold):
     sigma, coef, (nx, ny, nz), degree = _vol_arrays(sigma, coef)
     _abi.check(_abi.lib().nerf_hip_volume_prune(sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree, float(threshold), _stream(sigma)))
     return sigma, coef
+
+
+def volume_row_width(degree, half):
+    """Rule VC: the words of a stored coefficient row -- 3 (degree + 1)^2 fp32 words, or that many halves rounded up to a multiple of 4."""
+    w = 3 * (int(degree) + 1) ** 2
+    return (w + 3) & ~3 if half else w
+
+
+def _vol_compact(slot, sigma_rows, coef_rows, degree):
+    """The arrays of a compact volume, checked -> ((nx, ny, nz), n, half)."""
+    if slot.device.type != "cuda" or slot.dtype != torch.int32 or not slot.is_contiguous() or slot.dim() != 3:
+        raise ValueError(f"slot {tuple(slot.shape)} {slot.dtype}: a contiguous int32 device tensor [nx, ny, nz]")
+    if degree not in (0, 1, 2):
+        raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+    sigma_rows = _vol_f32(sigma_rows, "sigma rows")
+    n = int(sigma_rows.shape[0])
+    if coef_rows.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"coefficient rows {coef_rows.dtype}: fp32 or fp16")
+    half = coef_rows.dtype == torch.float16
+    if (coef_rows.device != slot.device or sigma_rows.device != slot.device or not coef_rows.is_contiguous() or sigma_rows.dim() != 1
+            or tuple(coef_rows.shape) != (n, volume_row_width(degree, half))):
+        raise ValueError(f"rows {tuple(sigma_rows.shape)} / {tuple(coef_rows.shape)}: [n] and [n, {volume_row_width(degree, half)}] on the slots' device")
+    return tuple(int(x) for x in slot.shape), n, int(half)
+
+
+def volume_compact_slots(index, shape):
+    """Rule VC's slot lattice of the active list index[n] (int32, ascending, device) of a lattice of ``shape``
+    (nerf_hip_volume_compact_slots) -> slot[nx, ny, nz] int32: the row of the point, -1 where there is none.  Enqueue only."""
+    if index.device.type != "cuda":
+        raise ValueError("index: a device tensor")
+    index, n = _vol_index(index, index.device)
+    nx, ny, nz = (int(x) for x in shape)
+    slot = torch.empty(nx, ny, nz, dtype=torch.int32, device=index.device)
+    _abi.check(_abi.lib().nerf_hip_volume_compact_slots(index.data_ptr() if n else None, n, nx, ny, nz, slot.data_ptr(), _stream(index)))
+    return slot
+
+
+def volume_compact_pack(sigma, coef, index, half):
+    """Rule VC's PACK (nerf_hip_volume_compact_pack): the rows of the points index[n] of the dense coef[nx, ny, nz, ncoef, 3] and, unless
+    ``sigma`` is None, sigma[nx, ny, nz] -> (sigma_rows [n] fp32 or None, coef_rows [n, S] fp32 or, with ``half``, fp16 with the pad
+    halves +0).  index = None: every lattice point in order -- the conversion of fp32 rows seen as a lattice to fp16.  Enqueue only."""
+    coef = _vol_f32(coef, "coef")
+    if coef.dim() != 5 or coef.shape[4] != 3 or int(coef.shape[3]) not in (1, 4, 9):
+        raise ValueError(f"coef {tuple(coef.shape)}: [nx, ny, nz, (degree + 1)^2, 3]")
+    nx, ny, nz, nc = (int(x) for x in coef.shape[:4])
+    degree = {1: 0, 4: 1, 9: 2}[nc]
+    dev = coef.device
+    if sigma is not None:
+        sigma = _vol_f32(sigma, "sigma", (nx, ny, nz))
+    if index is None:
+        n = nx * ny * nz
+    else:
+        index, n = _vol_index(index, dev)
+    sigma_rows = None if sigma is None else torch.empty(n, device=dev)
+    coef_rows = torch.empty(n, volume_row_width(degree, half), dtype=torch.float16 if half else torch.float32, device=dev)
+    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_pack(None if sigma is None else sigma.data_ptr(), coef.data_ptr(), nx, ny, nz, degree,
+                                                       ptr(index), n, int(bool(half)), None if sigma is None else ptr(sigma_rows),
+                                                       ptr(coef_rows), _stream(coef)))
+    return sigma_rows, coef_rows
+
+
+def volume_compact_unpack(sigma_rows, coef_rows, index, shape, degree):
+    """Rule VC's UNPACK (nerf_hip_volume_compact_unpack): the rows scattered to the points index[n] of zeroed dense arrays, fp16 widened
+    -> (sigma [nx, ny, nz], coef [nx, ny, nz, ncoef, 3]) fp32; coef_rows = None: (sigma, None).  Enqueue only."""
+    sigma_rows = _vol_f32(sigma_rows, "sigma rows")
+    dev = sigma_rows.device
+    index, n = _vol_index(index, dev)
+    nx, ny, nz = (int(x) for x in shape)
+    nc = (int(degree) + 1) ** 2
+    half = coef_rows is not None and coef_rows.dtype == torch.float16
+    if sigma_rows.dim() != 1 or int(sigma_rows.shape[0]) != n:
+        raise ValueError(f"sigma rows {tuple(sigma_rows.shape)}: one per index ({n})")
+    if coef_rows is not None and (coef_rows.device != dev or coef_rows.dtype not in (torch.float32, torch.float16) or not coef_rows.is_contiguous()
+                                  or tuple(coef_rows.shape) != (n, volume_row_width(degree, half))):
+        raise ValueError(f"coefficient rows {tuple(coef_rows.shape)} {coef_rows.dtype}: contiguous fp32 / fp16 [{n}, {volume_row_width(degree, half)}]")
+    sigma = torch.zeros(nx, ny, nz, device=dev)
+    coef = None if coef_rows is None else torch.zeros(nx, ny, nz, nc, 3, device=dev)
+    ptr = lambda t: t.data_ptr() if (t is not None and n) else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_unpack(ptr(sigma_rows), ptr(coef_rows), int(half), ptr(index), n, nx, ny, nz, int(degree),
+                                                         sigma.data_ptr(), None if coef is None else coef.data_ptr(), _stream(sigma_rows)))
+    return sigma, coef
+
+
+def volume_compact_sample(slot, sigma_rows, coef_rows, degree, lo, step, points, dirs):
+    """Rule VC-L: volume_sample over the compact form (nerf_hip_volume_compact_sample) -> (sigma[M], rgb[M, 3]) fp32.  Enqueue only."""
+    (nx, ny, nz), n, half = _vol_compact(slot, sigma_rows, coef_rows, degree)
+    dev = slot.device
+    points = points.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    if dirs.shape != points.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and points {tuple(points.shape)} differ")
+    M = int(points.shape[0])
+    out_s = torch.empty(M, device=dev)
+    out_c = torch.empty(M, 3, device=dev)
+    ptr = lambda t: t.data_ptr() if M else None
+    row = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_sample(slot.data_ptr(), row(sigma_rows), row(coef_rows), n, half, nx, ny, nz, int(degree),
+                                                         _abi.f32_array(lo), _abi.f32_array(step), ptr(points), ptr(dirs), M, ptr(out_s),
+                                                         ptr(out_c), _stream(slot)))
+    return out_s, out_c
+
+
+def volume_compact_render(slot, sigma_rows, coef_rows, degree, occ, block, lo, step, origins, dirs, tmin, tmax, dt, t_stop=0.0,
+                          background=(0.0, 0.0, 0.0)):
+    """Rule VC-R: volume_render over the compact form (nerf_hip_volume_compact_render) -> (rgb[N, 3], maps[N, 2] fp32, steps[N, 2]
+    int32).  Enqueue only."""
+    (nx, ny, nz), n, half = _vol_compact(slot, sigma_rows, coef_rows, degree)
+    dev = slot.device
+    block = min(int(block), 2**31 - 1)
+    if occ.device != dev or occ.dtype != torch.uint8 or not occ.is_contiguous() or (
+            block >= 1 and tuple(occ.shape) != volume_block_dims((nx, ny, nz), block)):
+        raise ValueError(f"occ {tuple(occ.shape)} {occ.dtype}: the contiguous uint8 block occupancy of sigma for block={block}")
+    origins = origins.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    N = int(origins.shape[0])
+    if dirs.shape != origins.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and origins {tuple(origins.shape)} differ")
+    win = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev).expand(N).contiguous() if torch.as_tensor(t).dim() == 0 else \
+        torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous()
+    tmin, tmax = win(tmin), win(tmax)
+    if tmin.shape[0] != N or tmax.shape[0] != N:
+        raise ValueError(f"tmin / tmax: a scalar or one entry per ray ({N})")
+    rgb = torch.empty(N, 3, device=dev)
+    maps = torch.empty(N, 2, device=dev)
+    steps = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if N else None
+    row = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_render(slot.data_ptr(), row(sigma_rows), row(coef_rows), n, half, occ.data_ptr(), nx, ny, nz,
+                                                         int(degree), block, _abi.f32_array(lo), _abi.f32_array(step), ptr(origins),
+                                                         ptr(dirs), ptr(tmin), ptr(tmax), N, float(dt), float(t_stop),
+                                                         _abi.f32_array(background), ptr(rgb), ptr(maps), ptr(steps), _stream(slot)))
+    return rgb, maps, steps

@@ -581,7 +581,7 @@ class NeRFRunner:
         return sigma
 
     def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
-                    finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None):
+                    finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None, compact=None):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
@@ -597,7 +597,12 @@ class NeRFRunner:
         COARSE TO FINE (volume.finetune): finetune_tv = None or (tv_sigma, tv_coef), the total-variation weights; finetune_upsample =
         the step counts after which the lattice is doubled (k of them give a (2^k (res - 1) + 1)^3 volume, written as
         ``..._ft<finetune>_up<k>.npz``); finetune_prune = None, or the density at or below which a point is cleared before each
-        doubling.  The finetune line then names the final lattice and the TV weights; without these arguments nothing changes."""
+        doubling.  The finetune line then names the final lattice and the TV weights; without these arguments nothing changes.
+        COMPACT (volume.CompactVolume, rule VC): compact = "fp32" / "fp16" bakes straight into the rows of the active points
+        (NeRFModel.bake_volume(compact=)), returns that form, names the file ``..._volume<res>_c32.npz`` / ``_c16.npz``, renders the
+        preview from the compact form, and the first ``[VOLUME]`` line gains the compact and the dense byte counts.  With finetune > 0
+        the bake and the fine-tuning stay dense and each volume is packed before it is written, previewed or returned.  compact = None
+        computes, prints and writes nothing new."""
         import numpy as np
 
         from . import volume
@@ -609,6 +614,9 @@ class NeRFRunner:
             raise ValueError(f"preview={preview!r}: None, 'train', 'val' or 'test'")
         if int(finetune) != finetune or finetune < 0:
             raise ValueError(f"finetune={finetune!r}: a number of steps >= 0")
+        if compact not in (None, "fp32", "fp16"):
+            raise ValueError(f"compact={compact!r}: None, 'fp32' or 'fp16'")
+        ctag = "" if compact is None else {"fp32": "_c32", "fp16": "_c16"}[compact]
         shape = grid_shape(res)
         tv = (0.0, 0.0) if finetune_tv is None else tuple(float(w) for w in finetune_tv)
         if len(tv) != 2:
@@ -623,15 +631,25 @@ class NeRFRunner:
         self.model.eval()
         t0 = time.perf_counter()
         vol = self.model.bake_volume(np.asarray(lo, np.float32), np.asarray(hi, np.float32), shape, degree=degree, sigma_min=sigma_min,
-                                     block=block)
+                                     block=block, compact=None if finetune else compact)
+        if compact is not None and finetune:
+            vol, dense = volume.pack(vol, compact), vol      # written and previewed compact; fine-tuned dense
         torch.cuda.synchronize(self.device)
-        active = int((vol.coef[..., 0, :] != 0).any(dim=-1).sum())
-        print(f"[VOLUME] {self.last_iter} {'x'.join(str(n) for n in shape)} degree {degree}: {active} / {vol.sigma.numel()} lattice points "
-              f"hold colour, {int(vol.occ.sum())} / {vol.occ.numel()} blocks of {vol.block} occupied, "
-              f"{(vol.sigma.numel() * 4 + vol.coef.numel() * 4) / 2**20:.1f} MiB, {time.perf_counter() - t0:.2f} s")
+        if compact is None:
+            active = int((vol.coef[..., 0, :] != 0).any(dim=-1).sum())
+            print(f"[VOLUME] {self.last_iter} {'x'.join(str(n) for n in shape)} degree {degree}: {active} / {vol.sigma.numel()} lattice points "
+                  f"hold colour, {int(vol.occ.sum())} / {vol.occ.numel()} blocks of {vol.block} occupied, "
+                  f"{(vol.sigma.numel() * 4 + vol.coef.numel() * 4) / 2**20:.1f} MiB, {time.perf_counter() - t0:.2f} s")
+        else:
+            npts = int(np.prod(shape))
+            active = int((vol.coef[:, :3] != 0).any(dim=-1).sum())
+            print(f"[VOLUME] {self.last_iter} {'x'.join(str(n) for n in shape)} degree {degree}: {active} / {npts} lattice points "
+                  f"hold colour, {int(vol.occ.sum())} / {vol.occ.numel()} blocks of {vol.block} occupied, {int(vol.sigma.shape[0])} rows, "
+                  f"compact {compact} {volume.nbytes(vol)} bytes (dense {npts * (4 + 12 * (int(degree) + 1) ** 2) + vol.occ.numel()} bytes), "
+                  f"{time.perf_counter() - t0:.2f} s")
         if save:
             tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
-            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + ".npz"
+            path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + ctag + ".npz"
             if os.path.dirname(path):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
             volume.save(path, vol)
@@ -671,12 +689,16 @@ class NeRFRunner:
             t0 = time.perf_counter()
             if any(tv):
                 lrs.update(tv_sigma=tv[0], tv_coef=tv[1])
-            vol, losses = volume.finetune(vol, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), upsample_at=ups,
+            vol, losses = volume.finetune(vol if compact is None else dense, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), upsample_at=ups,
                                           prune=finetune_prune, **lrs)
             losses = losses.cpu().numpy()
             seconds = time.perf_counter() - t0
+            final_shape = tuple(int(n) for n in vol.sigma.shape)
+            if compact is not None:
+                dense = None
+                vol = volume.pack(vol, compact)
             self.last_volume_finetune = {"iters": int(finetune), "first_loss": float(losses[0]), "last_loss": float(losses[-1]), "seconds": seconds,
-                                         "shape": tuple(int(n) for n in vol.sigma.shape)}
+                                         "shape": final_shape}
             scores = ""
             if preview is not None:
                 after = against_truth(vol)
@@ -685,7 +707,7 @@ class NeRFRunner:
                 self.last_volume_finetune.update(psnr_before=before[0], psnr_after=after[0], ssim_before=before[1], ssim_after=after[1])
             extra = ""
             if ups:
-                extra += f", {len(ups)} upsample{'s' if len(ups) > 1 else ''} to {'x'.join(str(int(n)) for n in vol.sigma.shape)}"
+                extra += f", {len(ups)} upsample{'s' if len(ups) > 1 else ''} to {'x'.join(str(n) for n in final_shape)}"
                 if finetune_prune is not None:
                     extra += f" pruned at {float(finetune_prune):g}"
             if any(tv):
@@ -696,7 +718,7 @@ class NeRFRunner:
                 tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
                 up = f"_up{len(ups)}" if ups else ""
                 volume.save(self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + "_ft" + str(int(finetune)) + up +
-                            ".npz", vol)
+                            ctag + ".npz", vol)
         return vol
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,

@@ -17,6 +17,12 @@ same box), ``prune`` clears thin density and the coefficients nothing can read a
 gradient of a total-variation prior over a level's active list to the same accumulators.  ``Finetuner(tv_sigma=, tv_coef=)`` applies
 the prior every step and ``finetune(upsample_at=, prune=)`` trains level by level, each level with a fresh active list and fresh moments.
 
+COMPACT VOLUMES (rule VC).  ``pack`` turns a Volume into a CompactVolume -- the rows of the active lattice
+points behind an int32 slot lattice, the coefficients fp32 or fp16 --, ``unpack`` goes back, ``nbytes`` counts either form.
+``sample``, ``render``, ``render_views``, ``default_dt``, ``with_block``, ``save`` and ``load`` take both forms; the compact march equals
+the dense one bit for bit (fp16: the dense march of the rounded coefficients).  ``NeRFModel.bake_volume(compact=)`` bakes straight into
+rows.  The training calls take the dense form only (TypeError): ``unpack`` is the way back to ``Finetuner``.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -41,11 +47,81 @@ class Volume(NamedTuple):
     degree: int            # 0, 1 or 2
 
 
+class CompactVolume(NamedTuple):
+    slot: torch.Tensor     # [nx, ny, nz] int32: the row of the lattice point, -1 where it has none (rule VC)
+    sigma: torch.Tensor    # [n] fp32: the active points' sigma, in the order of rule VA's list
+    coef: torch.Tensor     # [n, 3 (degree + 1)^2] fp32, or [n, that rounded up to a multiple of 4] fp16 with +0 pad halves
+    occ: torch.Tensor      # [bx, by, bz] uint8: blocks(the dense sigma, block)
+    lo: np.ndarray         # [3] fp32
+    step: np.ndarray       # [3] fp32
+    block: int
+    degree: int
+    shape: tuple           # (nx, ny, nz)
+
+
+_DTYPES = {"fp32": False, "fp16": True}
+
+
 def _on_device(t, what):
     t = torch.as_tensor(t)
     if t.device.type != "cuda":
         raise RuntimeError(f"{what} runs only on a ROCm device (MI355X): move the input to 'cuda'; there is no CPU path")
     return t
+
+
+def _dense_only(vol, what):
+    if isinstance(vol, CompactVolume):
+        raise TypeError(f"{what} works on the dense volume.Volume: a CompactVolume is the deployment form -- volume.unpack(cvol) gives the "
+                        "dense volume back")
+    return vol
+
+
+def _anchor(vol):
+    """the tensor that says where a volume of either form lives"""
+    return vol.slot if isinstance(vol, CompactVolume) else vol.sigma
+
+
+def pack(vol, dtype="fp32"):
+    """Rule VC: the dense ``vol`` as a CompactVolume -- active(vol.sigma) -> the slot lattice -> the rows, gathered on the device;
+    dtype "fp32" keeps the coefficients' bits, "fp16" rounds them to nearest even (past 65504: +-inf).  occ and block are taken over.
+    What the inactive points of ``vol`` hold is dropped: no lookup with a positive sigma can read it."""
+    _dense_only(vol, "volume.pack")
+    if dtype not in _DTYPES:
+        raise ValueError(f"dtype={dtype!r}: 'fp32' or 'fp16'")
+    _on_device(vol.sigma, "volume.pack")
+    index = active(vol.sigma)
+    shape = tuple(int(n) for n in vol.sigma.shape)
+    slot = ops.volume_compact_slots(index, shape)
+    sigma_rows, coef_rows = ops.volume_compact_pack(vol.sigma.detach(), vol.coef.detach(), index, _DTYPES[dtype])
+    return CompactVolume(slot, sigma_rows, coef_rows, vol.occ, np.asarray(vol.lo, np.float32), np.asarray(vol.step, np.float32), vol.block,
+                         vol.degree, shape)
+
+
+def _row_points(cvol):
+    """index[n] int32: the lattice point that holds row r (-1: none), from the slots that lie in [0, n)"""
+    flat = cvol.slot.reshape(-1)
+    n = int(cvol.sigma.shape[0])
+    where = torch.nonzero((flat >= 0) & (flat < n)).reshape(-1)
+    index = torch.full((n,), -1, dtype=torch.int32, device=flat.device)
+    index[flat[where].long()] = where.to(torch.int32)
+    return index
+
+
+def unpack(cvol):
+    """Rule VC: the dense Volume that holds the rows at their lattice points and +0 everywhere else (fp16 widened: exact).  For a
+    packed volume the points with a slot, in lattice order, are the active list.  sample / render of the result equal sample / render
+    of ``cvol`` bit for bit."""
+    if not isinstance(cvol, CompactVolume):
+        raise TypeError("volume.unpack takes a CompactVolume")
+    _on_device(cvol.slot, "volume.unpack")
+    sigma, coef = ops.volume_compact_unpack(cvol.sigma, cvol.coef, _row_points(cvol), cvol.shape, cvol.degree)
+    return Volume(sigma, coef, cvol.occ, np.asarray(cvol.lo, np.float32), np.asarray(cvol.step, np.float32), cvol.block, cvol.degree)
+
+
+def nbytes(vol):
+    """The bytes of the volume's arrays (dense: sigma, coef, occ; compact: slot, the rows, occ)."""
+    ts = (vol.slot, vol.sigma, vol.coef, vol.occ) if isinstance(vol, CompactVolume) else (vol.sigma, vol.coef, vol.occ)
+    return sum(int(t.numel()) * t.element_size() for t in ts)
 
 
 def sh_dirs():
@@ -66,14 +142,23 @@ def active(sigma):
 
 
 def with_block(vol, block):
-    """vol with its occupancy rebuilt for another block edge (the arrays are shared)."""
+    """vol with its occupancy rebuilt for another block edge (the arrays are shared).  A CompactVolume rebuilds it from a temporary
+    dense sigma of 4 bytes per lattice point."""
+    if isinstance(vol, CompactVolume):
+        _on_device(vol.slot, "volume.with_block")
+        sigma, _ = ops.volume_compact_unpack(vol.sigma, None, _row_points(vol), vol.shape, vol.degree)
+        return vol._replace(occ=blocks(sigma, block), block=min(int(block), ONE_BLOCK))
     return vol._replace(occ=blocks(vol.sigma, block), block=min(int(block), ONE_BLOCK))
 
 
 def sample(vol, points, dirs):
     """Rule VL: (sigma [M], rgb [M, 3]) of the volume at points [M, 3] along dirs [M, 3] (used as given, not renormalised): trilinear
-    sigma, and the trilinear mean of the corners' SH colours clamped to [0, 1]; zeros outside the lattice."""
-    _on_device(vol.sigma, "volume.sample")
+    sigma, and the trilinear mean of the corners' SH colours clamped to [0, 1]; zeros outside the lattice.  A CompactVolume is looked
+    up through its slots (rule VC-L): the same bits as sample(unpack(vol), ...)."""
+    _on_device(_anchor(vol), "volume.sample")
+    if isinstance(vol, CompactVolume):
+        return ops.volume_compact_sample(vol.slot, vol.sigma, vol.coef, vol.degree, vol.lo.tolist(), vol.step.tolist(),
+                                         _on_device(points, "volume.sample"), torch.as_tensor(dirs))
     return ops.volume_sample(vol.sigma, vol.coef, vol.lo.tolist(), vol.step.tolist(), _on_device(points, "volume.sample"), torch.as_tensor(dirs))
 
 
@@ -86,9 +171,13 @@ def render(vol, origins, dirs, tmin, tmax, dt=None, t_stop=1e-3, background=(0.0
     """Rule VR: rays (origins [N, 3], unit dirs [N, 3]) marched through the volume inside the window [tmin, tmax] (scalars or [N]) in
     steps of dt (default: half the smallest lattice step), ending a ray once its transmittance falls below t_stop (0: never)
     -> (rgb [N, 3], maps [N, 2] = (D, A) on render(maps=True)'s scale, steps [N, 2] int32 = (contributing, evaluated samples)).  Rays
-    that miss the lattice get the background, zero maps and zero steps.  rgb, maps and steps[:, 0] do not depend on vol.block."""
-    _on_device(vol.sigma, "volume.render")
+    that miss the lattice get the background, zero maps and zero steps.  rgb, maps and steps[:, 0] do not depend on vol.block.  A
+    CompactVolume is marched through its slots (rule VC-R): the same bits as render(unpack(vol), ...)."""
+    _on_device(_anchor(vol), "volume.render")
     dt = default_dt(vol) if dt is None else float(dt)
+    if isinstance(vol, CompactVolume):
+        return ops.volume_compact_render(vol.slot, vol.sigma, vol.coef, vol.degree, vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(),
+                                         _on_device(origins, "volume.render"), torch.as_tensor(dirs), tmin, tmax, dt, t_stop, background)
     return ops.volume_render(vol.sigma, vol.coef, vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(), _on_device(origins, "volume.render"),
                              torch.as_tensor(dirs), tmin, tmax, dt, t_stop, background)
 
@@ -99,7 +188,7 @@ def render_views(vol, poses_bound17, K_inv, H, W, dt=None, t_stop=1e-3, backgrou
     metrics.image_metrics as they are."""
     from . import mesh
 
-    dev = _on_device(vol.sigma, "volume.render_views").device
+    dev = _on_device(_anchor(vol), "volume.render_views").device
     pb = torch.as_tensor(poses_bound17).to(dev, torch.float32).reshape(-1, 17)
     n, H, W = int(pb.shape[0]), int(H), int(W)
     o, d = mesh.camera_rays(pb, K_inv, H, W, device=dev)
@@ -116,6 +205,7 @@ class VolumeGrad(NamedTuple):
 
 def grad_buffers(vol):
     """Zeroed accumulators of rule VG for ``vol``: 8 bytes per parameter."""
+    _dense_only(vol, "volume.grad_buffers")
     _on_device(vol.sigma, "volume.grad_buffers")
     return VolumeGrad(torch.zeros(vol.sigma.shape, dtype=torch.int64, device=vol.sigma.device),
                       torch.zeros(vol.coef.shape, dtype=torch.int64, device=vol.sigma.device))
@@ -126,6 +216,7 @@ def render_backward(vol, grad, origins, dirs, tmin, tmax, g_rgb, g_maps=None, dt
     with respect to vol.sigma and vol.coef, ACCUMULATED into ``grad`` (grad_buffers).  The sums are integers: the accumulators hold the
     same bits whatever the ray order, the batch split or vol.block.  Misses and rays with an upstream value that is not finite add
     nothing.  The early end at t_stop is a constant of the gradient.  -> grad"""
+    _dense_only(vol, "volume.render_backward")
     _on_device(vol.sigma, "volume.render_backward")
     dt = default_dt(vol) if dt is None else float(dt)
     ops.volume_render_backward(vol.sigma.detach(), vol.coef.detach(), vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(),
@@ -166,6 +257,7 @@ def render_train(vol, origins, dirs, tmin, tmax, dt=None, t_stop=1e-3, backgroun
     """``render`` under torch.autograd: the same (rgb, maps, steps), bit for bit, with rgb and maps carrying gradients to vol.sigma and
     vol.coef where those require them (render_backward into fresh grad_buffers, then gradients).  vol.occ must be blocks(vol.sigma,
     vol.block) of the CURRENT sigma, or a superset of it."""
+    _dense_only(vol, "volume.render_train")
     _on_device(vol.sigma, "volume.render_train")
     dt = default_dt(vol) if dt is None else float(dt)
     return _RenderTrain.apply(vol.sigma, vol.coef, vol, _on_device(origins, "volume.render_train"), torch.as_tensor(dirs), tmin, tmax, dt,
@@ -183,6 +275,7 @@ def tv_backward(vol, grad, index, member, w_sigma, w_coef, eps=1e-9):
     vol.sigma and vol.coef, ACCUMULATED into ``grad`` (grad_buffers) for the words of the points ``index`` (distinct; the level's list
     or a chunk of it -- ``member`` is member_mask of the whole list).  tau(p) = sqrt(sum_a d_a(p)^2 + eps) over the forward differences
     to members.  Points outside the mask receive nothing; the integers added to one word type sum to 0.  -> grad"""
+    _dense_only(vol, "volume.tv_backward")
     _on_device(vol.sigma, "volume.tv_backward")
     ops.volume_tv_backward(vol.sigma.detach(), vol.coef.detach(), _on_device(index, "volume.tv_backward"), member, w_sigma, w_coef, eps,
                            grad.acc_sigma, grad.acc_coef)
@@ -197,6 +290,7 @@ def upsample(vol):
     """Rule VX: a new Volume on the lattice of 2 n - 1 points per axis over the same box (the step halved exactly), every value
     the trilinear mean of rule VL at f = 0.5 or the coarse value itself.  The block edge is kept; the occupancy is rebuilt by
     ``blocks``.  The input keeps its bits."""
+    _dense_only(vol, "volume.upsample")
     _on_device(vol.sigma, "volume.upsample")
     sigma2, coef2 = ops.volume_upsample(vol.sigma.detach(), vol.coef.detach())
     step2 = (np.asarray(vol.step, np.float32) * np.float32(0.5)).astype(np.float32)
@@ -207,6 +301,7 @@ def prune(vol, sigma_min):
     """Rule VP on copies: sigma not > sigma_min (finite, >= 0) becomes 0, and the coefficients of every point that is then not active
     (rule VA) become 0 -> a new Volume with its occupancy rebuilt.  sigma_min = 0 clears only stale coefficients.  The input keeps
     its bits."""
+    _dense_only(vol, "volume.prune")
     _on_device(vol.sigma, "volume.prune")
     sigma, coef = ops.volume_prune(vol.sigma.detach().clone(), vol.coef.detach().clone(), sigma_min)
     return vol._replace(sigma=sigma, coef=coef, occ=blocks(sigma, vol.block))
@@ -226,6 +321,7 @@ class Finetuner:
     allocated and no kernel is launched: the tuner is the plain one, bit for bit."""
 
     def __init__(self, vol, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8, tv_sigma=0.0, tv_coef=0.0, tv_eps=1e-9):
+        _dense_only(vol, "volume.Finetuner")
         _on_device(vol.sigma, "volume.Finetuner")
         _check_tv(tv_sigma, tv_coef, tv_eps)
         self.vol = vol._replace(sigma=vol.sigma.detach().clone(), coef=vol.coef.detach().clone())
@@ -314,6 +410,7 @@ def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.
     takes over (Finetuner.refined): a new active list, zero moments, the bias correction restarting at step 1, the same rates and TV weights; the march's
     default dt follows the halved step.  The whole schedule is validated before the first step (ValueError).
     -> (the fine-tuned Volume, the batch losses [iters] on the device, all levels concatenated)."""
+    _dense_only(vol, "volume.finetune")
     dev = _on_device(vol.sigma, "volume.finetune").device
     ups, _ = check_schedule(vol.sigma.shape, iters, upsample_at, prune)
     _check_tv(lrs.get("tv_sigma", 0.0), lrs.get("tv_coef", 0.0), lrs.get("tv_eps", 1e-9))
@@ -334,7 +431,14 @@ def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.
 
 
 def save(path, vol):
-    """The volume as a plain ``.npz`` (numpy.savez: sigma, coef, occ, lo, step, block, degree)."""
+    """The volume as a plain ``.npz`` (numpy.savez: sigma, coef, occ, lo, step, block, degree).  A CompactVolume is written with the
+    keys slot, sigma_rows, coef_rows (fp32 or fp16), occ, lo, step, block, degree: the key ``slot`` tells the forms apart."""
+    if isinstance(vol, CompactVolume):
+        with open(path, "wb") as f:
+            np.savez(f, slot=vol.slot.cpu().numpy(), sigma_rows=vol.sigma.detach().cpu().numpy(), coef_rows=vol.coef.detach().cpu().numpy(),
+                     occ=vol.occ.cpu().numpy(), lo=np.asarray(vol.lo, np.float32), step=np.asarray(vol.step, np.float32),
+                     block=np.int64(vol.block), degree=np.int64(vol.degree))
+        return
     with open(path, "wb") as f:
         np.savez(f, sigma=vol.sigma.detach().cpu().numpy(), coef=vol.coef.detach().cpu().numpy(), occ=vol.occ.detach().cpu().numpy(),
                  lo=np.asarray(vol.lo, np.float32), step=np.asarray(vol.step, np.float32), block=np.int64(vol.block),
@@ -342,11 +446,15 @@ def save(path, vol):
 
 
 def load(path, device="cuda"):
-    """save()'s file -> a Volume on ``device`` with the saved bits."""
+    """save()'s file -> the form it holds, a Volume or (a file with the key ``slot``) a CompactVolume, on ``device`` with the saved bits."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("volume.load puts the volume on a ROCm device (MI355X): there is no CPU path")
     with np.load(path) as z:
         t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])).to(dev)
+        if "slot" in z.files:
+            slot = t("slot")
+            return CompactVolume(slot, t("sigma_rows"), t("coef_rows"), t("occ"), z["lo"].astype(np.float32).reshape(3),
+                                 z["step"].astype(np.float32).reshape(3), int(z["block"]), int(z["degree"]), tuple(int(n) for n in slot.shape))
         return Volume(t("sigma"), t("coef"), t("occ"), z["lo"].astype(np.float32).reshape(3), z["step"].astype(np.float32).reshape(3),
                       int(z["block"]), int(z["degree"]))
