@@ -1572,6 +1572,64 @@ int nerf_hip_volume_compact_render(const int32_t* slot, const float* sigma_rows,
                                    const float* origins, const float* dirs, const float* tmin, const float* tmax, int64_t N, float dt,
                                    float t_stop, const float* background3, float* rgb, float* maps, int32_t* steps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Fine-tuning a compact volume: rules VG, VU and VT over the rows of a compact volume
+ * whose coefficients are fp32 (half = 0).  The accumulators and the moments are kept PER ROW:
+ *       acc_sigma_rows[n], acc_coef_rows[n][3 ncoef]   int64, 8-byte aligned, rule VG's fixed point (units of 2^-40);
+ *       m, v [n][1 + 3 ncoef]                          fp32, a row's sigma word first, then its coefficient words.
+ * Nothing of the calls above changes; the dense training calls keep taking the dense form only.
+ *
+ * VCG. THE GRADIENT OF THE COMPACT MARCH: rule VG over rule VC-R's march.  The contributing samples, alpha_i, w_i, T_(i+1), c_i, the
+ *    unclamped colour and t_i are rule VC-R's own fp32 values; the fp64 brackets, the shift, the clamp to [-2^62, 2^62], misses and
+ *    upstream values that are not finite adding nothing, and the overflow precondition are rule VG's, verbatim.  A corner of a
+ *    contributing sample's cell whose slot r lies in [0, n) adds its contributions into the words of row r; a corner whose slot lies
+ *    outside [0, n) receives nothing, and its slot is never turned into an address.
+ *
+ * VCU. THE UPDATE OVER ROWS: rule VU with the rows as the list, one thread per (row, word) -- no index list.  The word (r, 0) is
+ *    sigma_rows[r], the word (r, 1 + j) is coef_rows[r][j]; the brackets, beta^step by squaring on the host, the FROZEN SUPPORT (a row
+ *    whose sigma is not > 0 at entry is dead: its sigma word and that word's m and v are left alone) and the accumulator word being
+ *    zeroed whatever happens are rule VU's.
+ *
+ * VCT. TOTAL VARIATION OVER ROWS: rule VT with the slot lattice as the membership test -- a lattice point is a member iff its slot lies
+ *    in [0, n).  point[n] (int32) is the lattice point of each row; a row r whose point is -1, outside the lattice, not a member, or a
+ *    member whose slot is not r is skipped (a point list that disagrees with the slots adds nothing for that row).
+ *    One thread per (row, word) gathers its own three Q_a(q) and the up to three Q_a(q - e_a), a neighbour's value read
+ *    through that neighbour's slot (compared with n first), then does one plain read-modify-write of its own accumulator word.
+ *
+ * EQUIVALENCE (proved in csrc/volume_compact_grad.hip).  Let the slots in [0, n) be distinct, U be the dense volume that holds the
+ *    rows at the points with such a slot and +0 elsewhere, and index[r] the point whose slot is r.  After the same calls on zeroed
+ *    accumulators, acc_*_rows[r] equals the dense accumulator word at index[r] bit for bit -- VCG against rule VG on U, VCT against
+ *    rule VT on U with rule VM's mask of index -- and VCU leaves sigma_rows, coef_rows, m and v equal to rule VU's on U over index at
+ *    those points.  If the compact volume is rule VC's PACK of ANY dense volume V (garbage at its inactive points included), rule VG
+ *    on V adds nothing outside the active list and agrees with VCG inside it.  The sums are integers: the accumulators hold the same
+ *    bits for the same call twice, for permuted rays, for a split batch and for every block edge.
+ *
+ * All three are enqueue-only and check every argument on the host first (NERF_HIP_ERR_ARG) as the calls above do: the lattice, the
+ * degree, n outside [0, nx ny nz] (VCU: < 0 or >= 2^31), a NULL pointer or one that is not aligned to its element (the accumulators: 8
+ * bytes), and the scalars as rules VG, VU and VT state them.  n = 0 succeeds and launches nothing (the row pointers may then be NULL),
+ * as does N = 0 for VCG and both weights 0 for VCT.  Data-dependent addresses are built only from values already compared with the
+ * size of their array.
+ * ------------------------------------------------------------------------------------------- */
+
+/* VCG over the rays of nerf_hip_volume_compact_render (its arguments without half -- the rows are fp32 -- and without outputs):
+ * g_rgb[N][3], g_maps[N][2] or NULL (device, fp32) -> contributions ADDED IN PLACE to acc_sigma_rows[n] and acc_coef_rows[n][3 ncoef]. */
+int nerf_hip_volume_compact_render_backward(const int32_t* slot, const float* sigma_rows, const float* coef_rows, int64_t n,
+                                            const uint8_t* occ, int nx, int ny, int nz, int degree, int block, const float* lo3,
+                                            const float* step3, const float* origins, const float* dirs, const float* tmin,
+                                            const float* tmax, int64_t N, float dt, float t_stop, const float* background3,
+                                            const float* g_rgb, const float* g_maps, int64_t* acc_sigma_rows, int64_t* acc_coef_rows,
+                                            void* stream);
+
+/* VCU.  The scalars are nerf_hip_volume_adam_step's. */
+int nerf_hip_volume_compact_adam_step(float* sigma_rows, float* coef_rows, int64_t n, int degree, int64_t* acc_sigma_rows,
+                                      int64_t* acc_coef_rows, float* m, float* v, double grad_scale, int64_t step, double lr_sigma,
+                                      double lr_coef, double beta1, double beta2, double eps, void* stream);
+
+/* VCT: the terms are ADDED IN PLACE to the rows' accumulators.  The weights lie in [0, 2^16], eps is finite and > 0. */
+int nerf_hip_volume_compact_tv_backward(const int32_t* slot, const float* sigma_rows, const float* coef_rows, const int32_t* point,
+                                        int64_t n, int nx, int ny, int nz, int degree, double w_sigma, double w_coef, double eps,
+                                        int64_t* acc_sigma_rows, int64_t* acc_coef_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,12 @@ _PROTOS = {
                                                  _p, _p, _p]),
     "nerf_hip_volume_compact_render": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p,
                                                  _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p]),
+    "nerf_hip_volume_compact_render_backward": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p,
+                                                          _p, _p, _p, C.c_int64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _p]),
+    "nerf_hip_volume_compact_adam_step": (C.c_int, [_p, _p, C.c_int64, C.c_int, _p, _p, _p, _p, C.c_double, C.c_int64, C.c_double, C.c_double,
+                                                    C.c_double, C.c_double, C.c_double, _p]),
+    "nerf_hip_volume_compact_tv_backward": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                      C.c_double, _p, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -1,5 +1,5 @@
 // api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
-// VR, VG, VU, VM, VT, VX, VP and VC): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
+// VR, VG, VU, VM, VT, VX, VP, VC, VCG, VCU and VCT): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
 // the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -110,6 +110,17 @@ VolCompact compact(const int32_t* slot, const float* sigma_rows, const void* coe
   c.coef_rows = coef_rows;
   c.n = n;
   return c;
+}
+
+// the per-row accumulators of rules VCG, VCU and VCT: without rows (n = 0) they may be null, never misaligned
+int check_row_accumulators(const int64_t* acc_sigma_rows, const int64_t* acc_coef_rows, int64_t n) {
+  if (n > 0 || acc_sigma_rows) {
+    if (int rc = check_out(acc_sigma_rows, "acc_sigma_rows", 8)) return rc;
+  }
+  if (n > 0 || acc_coef_rows) {
+    if (int rc = check_out(acc_coef_rows, "acc_coef_rows", 8)) return rc;
+  }
+  return NERF_HIP_OK;
 }
 
 int active(const float* sigma, int nx, int ny, int nz, void* ws, size_t ws_bytes, int64_t* count, int32_t* index, int64_t max_n, bool emit,
@@ -661,6 +672,126 @@ int nerf_hip_volume_compact_render(const int32_t* slot, const float* sigma_rows,
   a.r.maps = maps;
   a.r.steps = steps;
   HIP_TRY(launch_volume_compact_render(a, (degree + 1) * (degree + 1), half != 0, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_render_backward(const int32_t* slot, const float* sigma_rows, const float* coef_rows, int64_t n,
+                                            const uint8_t* occ, int nx, int ny, int nz, int degree, int block, const float* lo3,
+                                            const float* step3, const float* origins, const float* dirs, const float* tmin,
+                                            const float* tmax, int64_t N, float dt, float t_stop, const float* background3,
+                                            const float* g_rgb, const float* g_maps, int64_t* acc_sigma_rows, int64_t* acc_coef_rows,
+                                            void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_count("N", N)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (!(dt > 0.0f && isfinite(dt))) return fail(NERF_HIP_ERR_ARG, "dt=%g: the step along the ray must be finite and > 0", (double)dt);
+  if (!(t_stop >= 0.0f && t_stop < 1.0f)) return fail(NERF_HIP_ERR_ARG, "t_stop=%g: the transmittance to stop at lies in [0, 1)", (double)t_stop);
+  if (!background3) return fail(NERF_HIP_ERR_ARG, "background3 is null");
+  if (int rc = check_finite3(background3, "background", "the background colour")) return rc;
+  if (int rc = check_compact(slot, sigma_rows, coef_rows, n, 0, nx, ny, nz)) return rc;
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (int rc = check_row_accumulators(acc_sigma_rows, acc_coef_rows, n)) return rc;
+  if (g_maps && ((uintptr_t)g_maps & 3) != 0) return fail(NERF_HIP_ERR_ARG, "g_maps must be 4-byte aligned");
+  if (N == 0 || n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(origins, "origins", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(tmin, "tmin", 4)) return rc;
+  if (int rc = check_out(tmax, "tmax", 4)) return rc;
+  if (int rc = check_out(g_rgb, "g_rgb", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolCompactGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = compact(slot, sigma_rows, coef_rows, n);
+  a.r.occ = occ;
+  a.r.g = lattice(nx, ny, nz, lo3, step3);
+  a.r.B = block;
+  a.r.bx = blocks_of(nx, block);
+  a.r.by = blocks_of(ny, block);
+  a.r.bz = blocks_of(nz, block);
+  a.r.origins = origins;
+  a.r.dirs = dirs;
+  a.r.tmin = tmin;
+  a.r.tmax = tmax;
+  a.r.N = N;
+  a.r.dt = dt;
+  a.r.t_stop = t_stop;
+  for (int c = 0; c < 3; ++c) a.r.bg[c] = background3[c];
+  a.g_rgb = g_rgb;
+  a.g_maps = g_maps;
+  a.acc_sigma_rows = reinterpret_cast<long long*>(acc_sigma_rows);
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  HIP_TRY(launch_volume_compact_render_backward(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_adam_step(float* sigma_rows, float* coef_rows, int64_t n, int degree, int64_t* acc_sigma_rows,
+                                      int64_t* acc_coef_rows, float* m, float* v, double grad_scale, int64_t step, double lr_sigma,
+                                      double lr_coef, double beta1, double beta2, double eps, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (step < 1) return fail(NERF_HIP_ERR_ARG, "step=%lld: the first update is step 1", (long long)step);
+  if (!isfinite(grad_scale)) return fail(NERF_HIP_ERR_ARG, "grad_scale=%g must be finite", grad_scale);
+  if (!isfinite(lr_sigma) || !isfinite(lr_coef)) return fail(NERF_HIP_ERR_ARG, "lr_sigma=%g lr_coef=%g: the rates must be finite", lr_sigma, lr_coef);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(NERF_HIP_ERR_ARG, "beta1=%g beta2=%g: both lie in [0, 1)", beta1, beta2);
+  if (!(eps >= 0.0 && isfinite(eps))) return fail(NERF_HIP_ERR_ARG, "eps=%g must be finite and >= 0", eps);
+  if (int rc = check_row_accumulators(acc_sigma_rows, acc_coef_rows, n)) return rc;
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+  if (int rc = check_out(coef_rows, "coef_rows", 4)) return rc;
+  if (int rc = check_out(m, "m", 4)) return rc;
+  if (int rc = check_out(v, "v", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolCompactAdamArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma_rows = sigma_rows;
+  a.coef_rows = coef_rows;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.n = n;
+  a.acc_sigma_rows = reinterpret_cast<long long*>(acc_sigma_rows);
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  a.m = m;
+  a.v = v;
+  a.grad_scale = grad_scale;
+  a.lr_sigma = lr_sigma;
+  a.lr_coef = lr_coef;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  a.c1 = 1.0 - pow_by_squaring(beta1, step);
+  a.c2 = 1.0 - pow_by_squaring(beta2, step);
+  HIP_TRY(launch_volume_compact_adam_step(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_tv_backward(const int32_t* slot, const float* sigma_rows, const float* coef_rows, const int32_t* point,
+                                        int64_t n, int nx, int ny, int nz, int degree, double w_sigma, double w_coef, double eps,
+                                        int64_t* acc_sigma_rows, int64_t* acc_coef_rows, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (int rc = check_degree(degree)) return rc;
+  if (!(eps > 0.0 && isfinite(eps))) return fail(NERF_HIP_ERR_ARG, "eps=%g must be finite and > 0", eps);
+  if (!(w_sigma >= 0.0 && w_sigma <= 65536.0) || !(w_coef >= 0.0 && w_coef <= 65536.0))
+    return fail(NERF_HIP_ERR_ARG, "w_sigma=%g w_coef=%g: the weights lie in [0, 2^16]", w_sigma, w_coef);
+  if (int rc = check_compact(slot, sigma_rows, coef_rows, n, 0, nx, ny, nz)) return rc;
+  if (int rc = check_row_accumulators(acc_sigma_rows, acc_coef_rows, n)) return rc;
+  if (n == 0 || (w_sigma == 0.0 && w_coef == 0.0)) return NERF_HIP_OK;
+  if (int rc = check_out(point, "point", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolCompactTvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = compact(slot, sigma_rows, coef_rows, n);
+  a.point = point;
+  a.nx = nx;
+  a.ny = ny;
+  a.nz = nz;
+  a.ncoef = (degree + 1) * (degree + 1);
+  a.w_sigma = w_sigma;
+  a.w_coef = w_coef;
+  a.eps = eps;
+  a.acc_sigma_rows = reinterpret_cast<long long*>(acc_sigma_rows);
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  HIP_TRY(launch_volume_compact_tv_backward(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

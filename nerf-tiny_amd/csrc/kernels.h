@@ -919,6 +919,38 @@ hipError_t launch_volume_compact_unpack(const VolPackArgs& a, bool half, hipStre
 hipError_t launch_volume_compact_sample(const VolCompactSampleArgs& a, int ncoef, bool half, hipStream_t st);
 hipError_t launch_volume_compact_render(const VolCompactRenderArgs& a, int ncoef, bool half, hipStream_t st);
 
+// ---- fine-tuning a compact volume (volume_compact_grad.hip; nerf_hip_volume_compact_render_backward, _adam_step, _tv_backward,
+// DESIGN.md section 3h-16; rules VCG, VCU and VCT of include/nerf_hip.h): rules VG, VU and VT over fp32 rows, the accumulators and the
+// moments one per row ----
+struct VolCompactGradArgs {
+  VolCompact c;            // fp32 rows
+  VolRenderArgs r;         // the dense march's arguments; its sigma, coef and outputs are not used
+  const float *g_rgb, *g_maps;                // [N][3], [N][2] or null
+  long long *acc_sigma_rows, *acc_coef_rows;  // [n], [n][3 ncoef]: fixed-point sums, 2^-40 units
+};
+
+struct VolCompactAdamArgs {
+  float *sigma_rows, *coef_rows;  // [n], [n][3 ncoef]
+  int ncoef;
+  long long n;
+  long long *acc_sigma_rows, *acc_coef_rows;
+  float *m, *v;            // [n][1 + 3 ncoef]
+  double grad_scale, lr_sigma, lr_coef, beta1, beta2, eps;
+  double c1, c2;           // 1 - beta1^step, 1 - beta2^step
+};
+
+struct VolCompactTvArgs {
+  VolCompact c;            // fp32 rows; a point is a member iff its slot lies in [0, n)
+  const int* point;        // [n]: the lattice point of each row, -1: none
+  int nx, ny, nz, ncoef;
+  double w_sigma, w_coef, eps;
+  long long *acc_sigma_rows, *acc_coef_rows;
+};
+
+hipError_t launch_volume_compact_render_backward(const VolCompactGradArgs& a, int ncoef, hipStream_t st);
+hipError_t launch_volume_compact_adam_step(const VolCompactAdamArgs& a, hipStream_t st);
+hipError_t launch_volume_compact_tv_backward(const VolCompactTvArgs& a, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

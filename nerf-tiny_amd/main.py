@@ -121,6 +121,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "pixels with the support frozen (volume.finetune; rank 0) and also writes <...>_volume<RES>_ft<ITERS>.npz; with "
                          "--volume-preview the PSNR / SSIM against the split's ground-truth images before and after are printed (default 0: "
                          "the bake alone)")
+    ap.add_argument("--volume-finetune-compact", action="store_true",
+                    help="--volume-finetune trains the compact form itself (needs --volume-compact): the bake goes straight into fp32 rows, "
+                         "the accumulators and the Adam moments are kept per row (volume.finetune_compact), and the dense coefficient array "
+                         "is never allocated; the files hold the same arrays as without it (default: fine-tune the dense form)")
     ap.add_argument("--volume-finetune-batch", type=int, default=4096, metavar="N",
                     help="rays per --volume-finetune step (default 4096)")
     ap.add_argument("--volume-lr-sigma", type=float, default=None, metavar="X",
@@ -169,6 +173,8 @@ if __name__ == "__main__":
     import nerf_tiny_amd as P
 
     args = build_parser().parse_args()
+    if args.volume_finetune_compact and (args.volume_compact is None or args.volume_finetune <= 0):
+        raise ValueError("--volume-finetune-compact needs --volume-compact and --volume-finetune ITERS > 0")  # before any training
     conf = ConfigParser()
     conf.read(os.path.join(args.conf_dir, args.conf + ".ini"))
     c = lambda k, d=None: conf.get(args.conf, k, fallback=d)
@@ -209,7 +215,8 @@ if __name__ == "__main__":
                         save=True, preview=args.volume_preview, finetune=args.volume_finetune, finetune_batch=args.volume_finetune_batch,
                         finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None},
                         finetune_tv=(args.volume_tv_sigma, args.volume_tv_coef) if (args.volume_tv_sigma or args.volume_tv_coef) else None,
-                        finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune, compact=args.volume_compact)
+                        finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune, compact=args.volume_compact,
+                        finetune_compact=args.volume_finetune_compact)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

@@ -1314,3 +1314,84 @@ def volume_compact_render(slot, sigma_rows, coef_rows, degree, occ, block, lo, s
                                                          ptr(dirs), ptr(tmin), ptr(tmax), N, float(dt), float(t_stop),
                                                          _abi.f32_array(background), ptr(rgb), ptr(maps), ptr(steps), _stream(slot)))
     return rgb, maps, steps
+
+
+def _vol_compact_train(slot, sigma_rows, coef_rows, degree, acc_sigma_rows, acc_coef_rows):
+    """The arrays of a compact volume under training: fp32 rows and one int64 accumulator word per row word -> ((nx, ny, nz), n)."""
+    shape, n, half = _vol_compact(slot, sigma_rows, coef_rows, degree)
+    if half:
+        raise ValueError("coefficient rows torch.float16: a compact volume is trained on fp32 rows")
+    _vol_acc(acc_sigma_rows, "acc_sigma rows", (n,))
+    _vol_acc(acc_coef_rows, "acc_coef rows", (n, volume_row_width(degree, False)))
+    if acc_sigma_rows.device != slot.device or acc_coef_rows.device != slot.device:
+        raise ValueError("the accumulators and the slots live on different devices")
+    return shape, n
+
+
+def volume_compact_render_backward(slot, sigma_rows, coef_rows, degree, occ, block, lo, step, origins, dirs, tmin, tmax, dt, t_stop,
+                                   background, g_rgb, g_maps, acc_sigma_rows, acc_coef_rows):
+    """Rule VCG: volume_render_backward over the compact form with fp32 rows, ADDED IN PLACE to the per-row int64 accumulators
+    acc_sigma_rows [n] and acc_coef_rows [n, 3 ncoef] (nerf_hip_volume_compact_render_backward).  Enqueue only."""
+    (nx, ny, nz), n = _vol_compact_train(slot, sigma_rows, coef_rows, degree, acc_sigma_rows, acc_coef_rows)
+    dev = slot.device
+    block = min(int(block), 2**31 - 1)
+    if occ.device != dev or occ.dtype != torch.uint8 or not occ.is_contiguous() or (
+            block >= 1 and tuple(occ.shape) != volume_block_dims((nx, ny, nz), block)):
+        raise ValueError(f"occ {tuple(occ.shape)} {occ.dtype}: the contiguous uint8 block occupancy of sigma for block={block}")
+    origins = origins.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    N = int(origins.shape[0])
+    if dirs.shape != origins.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and origins {tuple(origins.shape)} differ")
+    win = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev).expand(N).contiguous() if torch.as_tensor(t).dim() == 0 else \
+        torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous()
+    tmin, tmax = win(tmin), win(tmax)
+    if tmin.shape[0] != N or tmax.shape[0] != N:
+        raise ValueError(f"tmin / tmax: a scalar or one entry per ray ({N})")
+    g_rgb = _vol_f32(g_rgb.detach().to(dev, torch.float32).contiguous(), "g_rgb", (N, 3))
+    if g_maps is not None:
+        g_maps = _vol_f32(g_maps.detach().to(dev, torch.float32).contiguous(), "g_maps", (N, 2))
+    ptr = lambda t: t.data_ptr() if N else None
+    row = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_render_backward(
+        slot.data_ptr(), row(sigma_rows), row(coef_rows), n, occ.data_ptr(), nx, ny, nz, int(degree), block, _abi.f32_array(lo),
+        _abi.f32_array(step), ptr(origins), ptr(dirs), ptr(tmin), ptr(tmax), N, float(dt), float(t_stop), _abi.f32_array(background), ptr(g_rgb),
+        ptr(g_maps) if g_maps is not None else None, row(acc_sigma_rows), row(acc_coef_rows), _stream(slot)))
+
+
+def volume_compact_adam_step(sigma_rows, coef_rows, degree, acc_sigma_rows, acc_coef_rows, m, v, grad_scale, step, lr_sigma, lr_coef,
+                             beta1=0.9, beta2=0.999, eps=1e-8):
+    """Rule VCU: one Adam step IN PLACE over the words of the fp32 rows from their fixed-point accumulators, which are zeroed; m, v
+    [n, 1 + 3 ncoef] fp32 are the moments (nerf_hip_volume_compact_adam_step).  A row whose sigma is not > 0 keeps it, with its
+    moments.  Enqueue only."""
+    if degree not in (0, 1, 2):
+        raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+    sigma_rows = _vol_f32(sigma_rows, "sigma rows")
+    if sigma_rows.dim() != 1:
+        raise ValueError(f"sigma rows {tuple(sigma_rows.shape)}: [n]")
+    n, width = int(sigma_rows.shape[0]), volume_row_width(degree, False)
+    coef_rows = _vol_f32(coef_rows, "coefficient rows", (n, width))
+    _vol_acc(acc_sigma_rows, "acc_sigma rows", (n,))
+    _vol_acc(acc_coef_rows, "acc_coef rows", (n, width))
+    m = _vol_f32(m, "m", (n, 1 + width))
+    v = _vol_f32(v, "v", (n, 1 + width))
+    ptr = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_adam_step(ptr(sigma_rows), ptr(coef_rows), n, int(degree), ptr(acc_sigma_rows),
+                                                            ptr(acc_coef_rows), ptr(m), ptr(v), float(grad_scale), int(step), float(lr_sigma),
+                                                            float(lr_coef), float(beta1), float(beta2), float(eps), _stream(sigma_rows)))
+
+
+def volume_compact_tv_backward(slot, sigma_rows, coef_rows, degree, point, w_sigma, w_coef, eps, acc_sigma_rows, acc_coef_rows):
+    """Rule VCT: volume_tv_backward over the compact form with fp32 rows -- the members are the points whose slot lies in [0, n), point[n]
+    (int32, device) is the lattice point of each row --, ADDED IN PLACE to the per-row accumulators
+    (nerf_hip_volume_compact_tv_backward).  Enqueue only."""
+    (nx, ny, nz), n = _vol_compact_train(slot, sigma_rows, coef_rows, degree, acc_sigma_rows, acc_coef_rows)
+    if not torch.is_tensor(point) or point.device.type != "cuda":
+        raise ValueError("point: a device tensor")
+    point, npoint = _vol_index(point, slot.device)
+    if npoint != n:
+        raise ValueError(f"point {npoint}: one lattice point per row ({n})")
+    row = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_tv_backward(slot.data_ptr(), row(sigma_rows), row(coef_rows), row(point), n, nx, ny, nz,
+                                                              int(degree), float(w_sigma), float(w_coef), float(eps), row(acc_sigma_rows),
+                                                              row(acc_coef_rows), _stream(slot)))

@@ -581,7 +581,8 @@ class NeRFRunner:
         return sigma
 
     def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
-                    finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None, compact=None):
+                    finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None, compact=None,
+                    finetune_compact=False):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
@@ -602,7 +603,11 @@ class NeRFRunner:
         (NeRFModel.bake_volume(compact=)), returns that form, names the file ``..._volume<res>_c32.npz`` / ``_c16.npz``, renders the
         preview from the compact form, and the first ``[VOLUME]`` line gains the compact and the dense byte counts.  With finetune > 0
         the bake and the fine-tuning stay dense and each volume is packed before it is written, previewed or returned.  compact = None
-        computes, prints and writes nothing new."""
+        computes, prints and writes nothing new.
+        finetune_compact = True (needs compact and finetune > 0: ValueError) trains the compact form itself: the bake goes straight into
+        fp32 rows, the dense coefficient array is never allocated, the fine-tuning is volume.finetune_compact, and each volume is
+        converted to ``compact``'s element type when it is written, previewed or returned.  The files hold the same arrays and carry
+        the same names; the finetune line gains the word ``compact``."""
         import numpy as np
 
         from . import volume
@@ -616,6 +621,8 @@ class NeRFRunner:
             raise ValueError(f"finetune={finetune!r}: a number of steps >= 0")
         if compact not in (None, "fp32", "fp16"):
             raise ValueError(f"compact={compact!r}: None, 'fp32' or 'fp16'")
+        if finetune_compact and (compact is None or not finetune):
+            raise ValueError("finetune_compact trains the compact form: it needs compact = 'fp32' / 'fp16' and finetune > 0")
         ctag = "" if compact is None else {"fp32": "_c32", "fp16": "_c16"}[compact]
         shape = grid_shape(res)
         tv = (0.0, 0.0) if finetune_tv is None else tuple(float(w) for w in finetune_tv)
@@ -631,8 +638,10 @@ class NeRFRunner:
         self.model.eval()
         t0 = time.perf_counter()
         vol = self.model.bake_volume(np.asarray(lo, np.float32), np.asarray(hi, np.float32), shape, degree=degree, sigma_min=sigma_min,
-                                     block=block, compact=None if finetune else compact)
-        if compact is not None and finetune:
+                                     block=block, compact="fp32" if finetune_compact else (None if finetune else compact))
+        if finetune_compact:
+            vol, rows32 = volume.convert(vol, compact), vol  # written and previewed as asked for; fine-tuned on fp32 rows
+        elif compact is not None and finetune:
             vol, dense = volume.pack(vol, compact), vol      # written and previewed compact; fine-tuned dense
         torch.cuda.synchronize(self.device)
         if compact is None:
@@ -689,12 +698,20 @@ class NeRFRunner:
             t0 = time.perf_counter()
             if any(tv):
                 lrs.update(tv_sigma=tv[0], tv_coef=tv[1])
-            vol, losses = volume.finetune(vol if compact is None else dense, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), upsample_at=ups,
-                                          prune=finetune_prune, **lrs)
+            if finetune_compact:
+                vol = None                                   # the converted copy of the bake is not kept through the training
+                vol, losses = volume.finetune_compact(rows32, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch),
+                                                      upsample_at=ups, prune=finetune_prune, **lrs)
+                rows32 = None
+            else:
+                vol, losses = volume.finetune(vol if compact is None else dense, self.train_rays, self.K_inv, int(finetune), batch=int(finetune_batch), upsample_at=ups,
+                                              prune=finetune_prune, **lrs)
             losses = losses.cpu().numpy()
             seconds = time.perf_counter() - t0
-            final_shape = tuple(int(n) for n in vol.sigma.shape)
-            if compact is not None:
+            final_shape = tuple(int(n) for n in (vol.shape if finetune_compact else vol.sigma.shape))
+            if finetune_compact:
+                vol = volume.convert(vol, compact)
+            elif compact is not None:
                 dense = None
                 vol = volume.pack(vol, compact)
             self.last_volume_finetune = {"iters": int(finetune), "first_loss": float(losses[0]), "last_loss": float(losses[-1]), "seconds": seconds,
@@ -712,7 +729,7 @@ class NeRFRunner:
                     extra += f" pruned at {float(finetune_prune):g}"
             if any(tv):
                 extra += f", TV sigma {tv[0]:g} coef {tv[1]:g}"
-            print(f"[VOLUME] {self.last_iter} finetune {int(finetune)} steps of {int(finetune_batch)} train rays{extra}: batch loss "
+            print(f"[VOLUME] {self.last_iter} finetune{' compact' if finetune_compact else ''} {int(finetune)} steps of {int(finetune_batch)} train rays{extra}: batch loss "
                   f"{losses[0]:.3e} -> {losses[-1]:.3e}{scores}, {seconds:.2f} s")
             if save:
                 tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)

@@ -23,6 +23,11 @@ points behind an int32 slot lattice, the coefficients fp32 or fp16 --, ``unpack`
 the dense one bit for bit (fp16: the dense march of the rounded coefficients).  ``NeRFModel.bake_volume(compact=)`` bakes straight into
 rows.  The training calls take the dense form only (TypeError): ``unpack`` is the way back to ``Finetuner``.
 
+COMPACT TRAINING (rules VCG, VCU and VCT).  Calls of their own train the compact form in place:
+``compact_grad_buffers`` / ``compact_render_backward`` / ``compact_tv_backward`` keep one int64 accumulator word per ROW word,
+``CompactFinetuner`` / ``finetune_compact`` are ``Finetuner`` / ``finetune`` over fp32 rows with per-row moments.  Every result equals
+the dense call's on ``unpack(cvol)``, gathered at the rows, bit for bit; only a refinement goes through a transient dense level.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -414,7 +419,12 @@ def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.
     dev = _on_device(vol.sigma, "volume.finetune").device
     ups, _ = check_schedule(vol.sigma.shape, iters, upsample_at, prune)
     _check_tv(lrs.get("tv_sigma", 0.0), lrs.get("tv_coef", 0.0), lrs.get("tv_eps", 1e-9))
-    tuner = Finetuner(vol, **lrs)
+    tuner, losses = _finetune_loop(Finetuner(vol, **lrs), rays, K_inv, iters, batch, seed, background, ups, prune, dev)
+    return tuner.volume(), losses
+
+
+def _finetune_loop(tuner, rays, K_inv, iters, batch, seed, background, ups, prune, dev):
+    """finetune's steps for a tuner of either form -> (the last level's tuner, the batch losses [iters])"""
     gen = torch.Generator(device=dev)
     if seed is not None:
         gen.manual_seed(int(seed))
@@ -427,7 +437,169 @@ def finetune(vol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.
         _, d_wrd, _ = ops.rays(row, col, pb, torch.as_tensor(K_inv), 2)
         o = pb[:, :15].reshape(-1, 3, 5)[:, :, 3].contiguous()
         losses.append(tuner.step(o, d_wrd, pb[:, 15].contiguous(), pb[:, 16].contiguous(), pix, background=background))
-    return tuner.volume(), (torch.stack(losses) if losses else torch.zeros(0, device=dev))
+    return tuner, (torch.stack(losses) if losses else torch.zeros(0, device=dev))
+
+
+class CompactGrad(NamedTuple):
+    acc_sigma: torch.Tensor   # [n] int64: sums of llrint(x 2^40), one per row
+    acc_coef: torch.Tensor    # [n, 3 (degree + 1)^2] int64
+
+
+def _compact_only(cvol, what):
+    if not isinstance(cvol, CompactVolume):
+        raise TypeError(f"{what} works on a volume.CompactVolume: volume.pack(vol) gives one; the dense volume.Volume has training "
+                        "calls of its own (Finetuner, render_backward, tv_backward, finetune)")
+    return cvol
+
+
+def _fp32_rows(cvol, what):
+    if cvol.coef.dtype != torch.float32:
+        raise ValueError(f"{what}: a compact volume is trained on fp32 rows -- CompactFinetuner widens fp16 rows itself")
+
+
+def convert(cvol, dtype):
+    """cvol with its coefficient rows in ``dtype``: fp32 -> fp16 rounds with pack's own call on the rows seen as a small lattice
+    ((n4 / 4, 2, 2), as NeRFModel.bake_volume converts them), fp16 -> fp32 widens (exact); the other arrays are shared.  Rounding
+    holds a zeroed fp32 copy of the rows (the padded lattice) beside the input and the fp16 result until it returns: 12 ncoef bytes
+    per row more, as the compact bake's own conversion."""
+    half = _DTYPES[dtype]
+    if (cvol.coef.dtype == torch.float16) == half:
+        return cvol
+    n, words = int(cvol.sigma.shape[0]), 3 * (cvol.degree + 1) ** 2
+    if not half:
+        return cvol._replace(coef=cvol.coef[:, :words].to(torch.float32).contiguous())
+    n4 = max(8, (n + 3) // 4 * 4)
+    lattice = torch.zeros(n4 // 4, 2, 2, (cvol.degree + 1) ** 2, 3, device=cvol.coef.device)
+    lattice.reshape(n4, -1)[:n] = cvol.coef
+    return cvol._replace(coef=ops.volume_compact_pack(None, lattice, None, True)[1][:n])
+
+
+def row_points(cvol):
+    """index[n] int32: the lattice point that holds row r (-1: none), from the slots that lie in [0, n).  For a packed volume this is
+    rule VA's active list."""
+    _compact_only(cvol, "volume.row_points")
+    _on_device(cvol.slot, "volume.row_points")
+    return _row_points(cvol)
+
+
+def compact_grad_buffers(cvol):
+    """Zeroed accumulators of rule VCG for ``cvol``, one int64 word per row word: 8 bytes per stored parameter."""
+    _compact_only(cvol, "volume.compact_grad_buffers")
+    dev = _on_device(cvol.slot, "volume.compact_grad_buffers").device
+    n = int(cvol.sigma.shape[0])
+    return CompactGrad(torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, 3 * (cvol.degree + 1) ** 2, dtype=torch.int64, device=dev))
+
+
+def compact_render_backward(cvol, grad, origins, dirs, tmin, tmax, g_rgb, g_maps=None, dt=None, t_stop=1e-3, background=(0.0, 0.0, 0.0)):
+    """Rule VCG: ``render_backward`` over a CompactVolume with fp32 rows, ACCUMULATED into ``grad`` (compact_grad_buffers): row r
+    receives, bit for bit, what render_backward on unpack(cvol) adds at the row's lattice point; a corner without a row receives
+    nothing.  The same bits whatever the ray order, the batch split or cvol.block.  -> grad"""
+    _compact_only(cvol, "volume.compact_render_backward")
+    _on_device(cvol.slot, "volume.compact_render_backward")
+    _fp32_rows(cvol, "volume.compact_render_backward")
+    dt = default_dt(cvol) if dt is None else float(dt)
+    ops.volume_compact_render_backward(cvol.slot, cvol.sigma.detach(), cvol.coef.detach(), cvol.degree, cvol.occ, cvol.block, cvol.lo.tolist(),
+                                       cvol.step.tolist(), _on_device(origins, "volume.compact_render_backward"), torch.as_tensor(dirs), tmin,
+                                       tmax, dt, t_stop, background, _on_device(g_rgb, "volume.compact_render_backward"),
+                                       None if g_maps is None else torch.as_tensor(g_maps), grad.acc_sigma, grad.acc_coef)
+    return grad
+
+
+def compact_tv_backward(cvol, grad, w_sigma, w_coef, eps=1e-9):
+    """Rule VCT: ``tv_backward`` over a CompactVolume with fp32 rows, the members being the points with a row, ACCUMULATED into
+    ``grad`` (compact_grad_buffers): bit for bit tv_backward on unpack(cvol) with member_mask(row_points(cvol)), gathered at the
+    rows.  NOT enqueue-only: every call rebuilds the row -> point list from the slot lattice (row_points: passes over the whole
+    lattice and one host sync).  A caller that repeats it uses CompactFinetuner, which keeps the list, or
+    ops.volume_compact_tv_backward with row_points(cvol) cached.  -> grad"""
+    _compact_only(cvol, "volume.compact_tv_backward")
+    _on_device(cvol.slot, "volume.compact_tv_backward")
+    _fp32_rows(cvol, "volume.compact_tv_backward")
+    ops.volume_compact_tv_backward(cvol.slot, cvol.sigma.detach(), cvol.coef.detach(), cvol.degree, _row_points(cvol), w_sigma, w_coef, eps,
+                                   grad.acc_sigma, grad.acc_coef)
+    return grad
+
+
+class CompactFinetuner:
+    """``Finetuner`` on the compact form (rules VCG, VCU and VCT): Adam on the ROWS of a CompactVolume, the
+    accumulators and the moments one per row -- 112 + 224 + 224 + 4 bytes per row at degree 2 beside the slot lattice, instead of a
+    dense working copy, dense int64 accumulators and a member mask.  It works on its own copies of the rows (fp16 rows are widened,
+    exactly; training is in fp32) and shares the slot lattice, which never changes.  Every step equals Finetuner(unpack(cvol))'s bit
+    for bit: the same losses, and the same values at the rows."""
+
+    def __init__(self, cvol, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8, tv_sigma=0.0, tv_coef=0.0, tv_eps=1e-9):
+        _compact_only(cvol, "volume.CompactFinetuner")
+        _on_device(cvol.slot, "volume.CompactFinetuner")
+        _check_tv(tv_sigma, tv_coef, tv_eps)
+        words = 3 * (cvol.degree + 1) ** 2
+        self.cvol = cvol._replace(sigma=cvol.sigma.detach().clone(), coef=cvol.coef.detach()[:, :words].to(torch.float32, copy=True).contiguous())
+        self.point = _row_points(cvol)
+        n = int(cvol.sigma.shape[0])
+        self.m = torch.zeros(n, 1 + words, device=cvol.slot.device)
+        self.v = torch.zeros_like(self.m)
+        self.grad = compact_grad_buffers(self.cvol)
+        self.lr_sigma, self.lr_coef, self.betas, self.eps = float(lr_sigma), float(lr_coef), (float(betas[0]), float(betas[1])), float(eps)
+        self.steps = 0
+        self.tv_sigma, self.tv_coef, self.tv_eps = float(tv_sigma), float(tv_coef), float(tv_eps)
+
+    def step(self, origins, dirs, tmin, tmax, target, background=(0.0, 0.0, 0.0), dt=None, t_stop=1e-3):
+        """Finetuner.step on the rows: the same scaling (grad_scale = 1 / (3 N), the TV weights times 3 N / n) -> the batch's MSE
+        before the update, a device scalar (no host sync)."""
+        c, dev = self.cvol, self.cvol.slot.device
+        rgb, _, _ = render(c, origins, dirs, tmin, tmax, dt=dt, t_stop=t_stop, background=background)
+        diff = rgb - torch.as_tensor(target).to(dev, torch.float32).reshape(-1, 3)
+        n = max(int(rgb.shape[0]), 1)
+        rows = int(c.sigma.shape[0])
+        compact_render_backward(c, self.grad, origins, dirs, tmin, tmax, 2.0 * diff, None, dt=dt, t_stop=t_stop, background=background)
+        if (self.tv_sigma > 0.0 or self.tv_coef > 0.0) and rows > 0:
+            k = 3.0 * n / rows
+            ops.volume_compact_tv_backward(c.slot, c.sigma, c.coef, c.degree, self.point, self.tv_sigma * k, self.tv_coef * k, self.tv_eps,
+                                           self.grad.acc_sigma, self.grad.acc_coef)
+        self.steps += 1
+        ops.volume_compact_adam_step(c.sigma, c.coef, c.degree, self.grad.acc_sigma, self.grad.acc_coef, self.m, self.v, 1.0 / (3.0 * n),
+                                     self.steps, self.lr_sigma, self.lr_coef, self.betas[0], self.betas[1], self.eps)
+        return (diff * diff).mean() if rgb.numel() else torch.zeros((), device=dev)
+
+    def volume(self, dtype="fp32"):
+        """The current state REPACKED as a CompactVolume with ``dtype`` coefficients: a temporary dense sigma (4 bytes per lattice
+        point) from the rows -> active -> new slots -> the kept rows gathered -> blocks.  Rows that rule VA no longer keeps -- a sigma
+        that reached 0 took its neighbourhood's last positive value with it -- are dropped, so the result equals
+        pack(Finetuner(unpack(cvol)) ... .volume(), dtype) bit for bit in slot, sigma, coef and occ."""
+        if dtype not in _DTYPES:
+            raise ValueError(f"dtype={dtype!r}: 'fp32' or 'fp16'")
+        c = self.cvol
+        n = int(c.sigma.shape[0])
+        sigma, _ = ops.volume_compact_unpack(c.sigma, None, self.point, c.shape, c.degree)
+        index = active(sigma)
+        old = c.slot.reshape(-1)[index.long()].long()
+        kept = (old >= 0) & (old < n)  # a point of the new list without a row holds +0, as it does in unpack(cvol)
+        old = old.clamp(0, max(n - 1, 0))  # (without rows sigma is all +0 and the new list is empty)
+        zero = torch.zeros((), device=sigma.device)
+        sigma_rows, coef_rows = torch.where(kept, c.sigma[old], zero), torch.where(kept[:, None], c.coef[old], zero)
+        out = c._replace(slot=ops.volume_compact_slots(index, c.shape), sigma=sigma_rows, coef=coef_rows, occ=blocks(sigma, c.block))
+        return convert(out, dtype)
+
+    def refined(self, prune=None):
+        """Finetuner.refined through a TRANSIENT DENSE LEVEL: this tuner's volume unpacked, pruned (rule VP at ``prune``) unless that is
+        None, refined (rule VX), packed -> a FRESH CompactFinetuner on it with the same rates and TV weights.  The dense coarse and fine
+        levels live until the pack: compact upsample / prune kernels do not exist.  This tuner's buffers are released first."""
+        level = unpack(self.volume())
+        self.m = self.v = self.grad = self.point = self.cvol = None
+        if prune is not None:
+            level = _prune(level, prune)
+        return CompactFinetuner(pack(upsample(level)), lr_sigma=self.lr_sigma, lr_coef=self.lr_coef, betas=self.betas, eps=self.eps,
+                                tv_sigma=self.tv_sigma, tv_coef=self.tv_coef, tv_eps=self.tv_eps)
+
+
+def finetune_compact(cvol, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.0, 0.0), upsample_at=(), prune=None, **lrs):
+    """``finetune`` with a CompactFinetuner: the same validation, the same batches for the same seed, the same schedule (each
+    refinement through CompactFinetuner.refined's transient dense level) -> (the fine-tuned CompactVolume with fp32 rows, the batch
+    losses [iters] on the device).  Bit for bit pack(finetune(unpack(cvol), ...)[0]) and its losses when ``prune`` is given."""
+    _compact_only(cvol, "volume.finetune_compact")
+    dev = _on_device(cvol.slot, "volume.finetune_compact").device
+    ups, _ = check_schedule(cvol.shape, iters, upsample_at, prune)
+    _check_tv(lrs.get("tv_sigma", 0.0), lrs.get("tv_coef", 0.0), lrs.get("tv_eps", 1e-9))
+    tuner, losses = _finetune_loop(CompactFinetuner(cvol, **lrs), rays, K_inv, iters, batch, seed, background, ups, prune, dev)
+    return tuner.volume(), losses
 
 
 def save(path, vol):
