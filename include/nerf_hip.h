@@ -72,7 +72,8 @@ extern "C" {
                                      nerf_hip_volume_render_backward, nerf_hip_volume_adam_step
                                      (with NERF_HIP_VOLUME_GRAD_SHIFT); nerf_hip_volume_member_mask,
                                      nerf_hip_volume_tv_backward, nerf_hip_volume_upsample, nerf_hip_volume_prune;
-                                     the nerf_hip_volume_compact_* calls */
+                                     the nerf_hip_volume_compact_* calls; nerf_hip_volume_compact_importance and the
+                                     nerf_hip_volume_vq_* calls (with NERF_HIP_VOLUME_VQ_SHIFT, NERF_HIP_VOLUME_VQ_MAX_CODES) */
 
 enum {
   NERF_HIP_OK = 0,
@@ -1629,6 +1630,74 @@ int nerf_hip_volume_compact_adam_step(float* sigma_rows, float* coef_rows, int64
 int nerf_hip_volume_compact_tv_backward(const int32_t* slot, const float* sigma_rows, const float* coef_rows, const int32_t* point,
                                         int64_t n, int nx, int ny, int nz, int degree, double w_sigma, double w_coef, double eps,
                                         int64_t* acc_sigma_rows, int64_t* acc_coef_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Vector-quantised compact volumes: a per-row importance from training rays, a k-means
+ * codebook over the coefficient rows, and the decode of (class, code) back to rule VC's fp16 rows.  Nothing of the calls above
+ * changes; the marchers keep reading rows -- the quantised form is a FILE form, decoded once after loading.
+ *
+ * VI. IMPORTANCE.  Rule VC-R's march, unchanged: the slab test, the samples t_k = t_a + (k + 0.5) dt, the passing over of empty
+ *    blocks with its verification, alpha = -expm1f(-(sigma_s dt)), w = T alpha, T = T - w, the end once T < t_stop.  No coefficient
+ *    row is read (the call takes none).  At each contributing sample, with (f_x, f_y, f_z) the cell's fp32 fractions and w the
+ *    sample's fp32 weight (BEFORE T is updated), every corner c = di 4 + dj 2 + dk whose slot r lies in [0, n) receives
+ *       imp_rows[r] += llrint( clamp( (((wx wy) wz) (double)w) 2^40, +-2^62 ) )
+ *    where wx = f_x if di else 1 - f_x (likewise wy, wz), formed in fp64 from the fp32 fractions exactly as rule VG forms its corner
+ *    terms; the units (NERF_HIP_VOLUME_GRAD_SHIFT) and the clamp are rule VG's.  The additions are int64 atomics: the sums hold the
+ *    same bits whatever the order of the rays, the split of a batch or the block edge.  A corner whose slot lies outside [0, n)
+ *    receives nothing and its slot is never turned into an address.  imp_rows belongs to the caller and is ADDED to.  steps[N][2]
+ *    equals nerf_hip_volume_compact_render's bit for bit.  A row's sum stays below 2^62 for fewer than 2^22 contributing samples
+ *    per row and call sequence at full weight; the caller's precondition, as rule VG's.
+ *
+ * VQ-A. ASSIGN.  rows[m][W] and codebook[K][W] are fp32, W = 3 ncoef, 1 <= K <= NERF_HIP_VOLUME_VQ_MAX_CODES.  For row q and code j
+ *       d_j = (..((t_0 t_0) + t_1 t_1) + ..) + t_(W-1) t_(W-1),      t_w = q_w - c_jw
+ *    in fp32, every difference, product and sum rounded on its own, in the order w = 0 .. W - 1.  assign[r] is the result of scanning
+ *    j = 0 .. K - 1 with  "if (d_j < best) best = d_j, code = j"  from best = +inf, code = 0: the lowest index wins a tie, a NaN d_j
+ *    never wins, and code 0 is the answer when nothing wins.  dist[r] (optional) is the final best (+inf when nothing won).
+ *
+ * VQ-U. UPDATE.  weight[m] is int64 with 0 <= weight[r] <= imax (rule VI's sums of the coded rows and their maximum);
+ *    u_r = (double)weight[r] / (double)imax, and u_r = 1 when weight is NULL or imax = 0.  ACCUMULATE adds, for every row r whose
+ *    assign[r] = j lies in [0, K) (any other value is skipped and never becomes an address),
+ *       sum[j][w] += llrint( clamp( (u_r (double)q_rw) 2^20, +-2^62 ) )   (a NaN product adds 0),      cnt[j] += llrint(u_r 2^20)
+ *    with int64 atomics (NERF_HIP_VOLUME_VQ_SHIFT = 20): the sums do not depend on the order of the rows.  THE BOUND: with
+ *    |q_rw| <= 2^10, u_r <= 1 and m < 2^31 a sum stays below 2^10 2^20 2^31 = 2^61 < 2^62 and a count below 2^51; rows with a larger or
+ *    non-finite word are the caller's to keep out (volume.vq_classes keeps them verbatim).  UPDATE then sets, per code and word,
+ *       c_jw = (float)((double)sum[j][w] / (double)cnt[j])     where cnt[j] > 0;
+ *    a code with cnt[j] <= 0 keeps its words.  The caller zeroes sum and cnt between iterations.
+ *
+ * VQ-D. DECODE.  cls[n] (uint8: 0 pruned, 1 coded, 2 kept), rank[n] (int32: the row's rank among the rows of its class, in row order),
+ *    code[n_coded] (uint16), kept[n_kept][S] and codebook[K][S] (fp16, S = rule VC's fp16 stride, pads +0) -> coef_rows[n][S] fp16:
+ *    a coded row r copies the S halves of codebook[code[rank[r]]], a kept row those of kept[rank[r]], a pruned row is +0 -- as is any
+ *    row whose class is none of the three, whose rank lies outside its class, or whose code is >= K.  One thread per 8-byte word.
+ *
+ * All five are enqueue-only and check every argument on the host first (NERF_HIP_ERR_ARG) as the calls above do: the lattice, the
+ * degree, a count < 0 or >= 2^31, K outside [1, 65536] (decode: [0, 65536], and > 0 with coded rows), imax < 0,
+ * n_coded + n_kept > n, a NULL pointer or one that is not aligned to its element (int64: 8; fp16 rows: 8).  N = 0, m = 0 and n = 0
+ * succeed and launch nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_VOLUME_VQ_SHIFT 20
+#define NERF_HIP_VOLUME_VQ_MAX_CODES 65536
+
+/* VI over the rays of nerf_hip_volume_compact_render (its arguments without coef_rows, half, degree, background and the float
+ * outputs): contributions ADDED IN PLACE to imp_rows[n] (device, int64, units of 2^-40); steps[N][2] as render's. */
+int nerf_hip_volume_compact_importance(const int32_t* slot, const float* sigma_rows, int64_t n, const uint8_t* occ, int nx, int ny, int nz,
+                                       int block, const float* lo3, const float* step3, const float* origins, const float* dirs,
+                                       const float* tmin, const float* tmax, int64_t N, float dt, float t_stop, int64_t* imp_rows,
+                                       int32_t* steps, void* stream);
+
+/* VQ-A: assign[m] (device, int32) and, unless NULL, dist[m] (fp32). */
+int nerf_hip_volume_vq_assign(const float* rows, int64_t m, const float* codebook, int64_t K, int degree, int32_t* assign, float* dist,
+                              void* stream);
+
+/* VQ-U's ACCUMULATE into sum[K][W] and cnt[K] (device, int64, zeroed by the caller); weight may be NULL. */
+int nerf_hip_volume_vq_accumulate(const float* rows, int64_t m, int degree, const int64_t* weight, int64_t imax, const int32_t* assign,
+                                  int64_t K, int64_t* sum, int64_t* cnt, void* stream);
+
+/* VQ-U's UPDATE of codebook[K][W] in place. */
+int nerf_hip_volume_vq_update(float* codebook, int64_t K, int degree, const int64_t* sum, const int64_t* cnt, void* stream);
+
+/* VQ-D -> coef_rows[n][S] (device, fp16, 8-byte aligned). */
+int nerf_hip_volume_vq_decode(const uint8_t* cls, const int32_t* rank, int64_t n, const uint16_t* code, int64_t n_coded, const void* kept,
+                              int64_t n_kept, const void* codebook, int64_t K, int degree, void* coef_rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,12 @@ _PROTOS = {
                                                     C.c_double, C.c_double, C.c_double, _p]),
     "nerf_hip_volume_compact_tv_backward": (C.c_int, [_p, _p, _p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                                       C.c_double, _p, _p, _p]),
+    "nerf_hip_volume_compact_importance": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p,
+                                                     C.c_int64, C.c_float, C.c_float, _p, _p, _p]),
+    "nerf_hip_volume_vq_assign": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_vq_accumulate": (C.c_int, [_p, C.c_int64, C.c_int, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
+    "nerf_hip_volume_vq_update": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_vq_decode": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

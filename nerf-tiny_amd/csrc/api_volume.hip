@@ -1,5 +1,5 @@
 // api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
-// VR, VG, VU, VM, VT, VX, VP, VC, VCG, VCU and VCT): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
+// VR, VG, VU, VM, VT, VX, VP, VC, VCG, VCU, VCT, VI, VQ-A, VQ-U and VQ-D): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
 // the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -120,6 +120,13 @@ int check_row_accumulators(const int64_t* acc_sigma_rows, const int64_t* acc_coe
   if (n > 0 || acc_coef_rows) {
     if (int rc = check_out(acc_coef_rows, "acc_coef_rows", 8)) return rc;
   }
+  return NERF_HIP_OK;
+}
+
+// rule VQ's codebook: 1 .. 65536 codes (a code is a uint16)
+static_assert(VQ_SHIFT == NERF_HIP_VOLUME_VQ_SHIFT && VQ_MAX_CODES == NERF_HIP_VOLUME_VQ_MAX_CODES, "the header states rule VQ's constants");
+int check_codes(int64_t K) {
+  if (K < 1 || K > VQ_MAX_CODES) return fail(NERF_HIP_ERR_ARG, "K=%lld: a codebook has 1 .. %d codes", (long long)K, VQ_MAX_CODES);
   return NERF_HIP_OK;
 }
 
@@ -792,6 +799,159 @@ int nerf_hip_volume_compact_tv_backward(const int32_t* slot, const float* sigma_
   a.acc_sigma_rows = reinterpret_cast<long long*>(acc_sigma_rows);
   a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
   HIP_TRY(launch_volume_compact_tv_backward(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_compact_importance(const int32_t* slot, const float* sigma_rows, int64_t n, const uint8_t* occ, int nx, int ny, int nz,
+                                       int block, const float* lo3, const float* step3, const float* origins, const float* dirs,
+                                       const float* tmin, const float* tmax, int64_t N, float dt, float t_stop, int64_t* imp_rows,
+                                       int32_t* steps, void* stream) {
+  if (int rc = check_lattice(nx, ny, nz)) return rc;
+  if (block < 1) return fail(NERF_HIP_ERR_ARG, "block=%d: a block has at least one cell per axis", block);
+  if (int rc = check_count("N", N)) return rc;
+  if (int rc = check_lo_step(lo3, step3)) return rc;
+  if (!(dt > 0.0f && isfinite(dt))) return fail(NERF_HIP_ERR_ARG, "dt=%g: the step along the ray must be finite and > 0", (double)dt);
+  if (!(t_stop >= 0.0f && t_stop < 1.0f)) return fail(NERF_HIP_ERR_ARG, "t_stop=%g: the transmittance to stop at lies in [0, 1)", (double)t_stop);
+  if (int rc = check_rows(n, nx, ny, nz)) return rc;
+  if (int rc = check_out(slot, "slot", 4)) return rc;
+  if (n > 0) {
+    if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+  }
+  if (n > 0 || imp_rows) {
+    if (int rc = check_out(imp_rows, "imp_rows", 8)) return rc;
+  }
+  if (int rc = check_out(occ, "occ", 1)) return rc;
+  if (N == 0) return NERF_HIP_OK;
+  if (int rc = check_out(origins, "origins", 4)) return rc;
+  if (int rc = check_out(dirs, "dirs", 4)) return rc;
+  if (int rc = check_out(tmin, "tmin", 4)) return rc;
+  if (int rc = check_out(tmax, "tmax", 4)) return rc;
+  if (int rc = check_out(steps, "steps", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VolImportanceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = compact(slot, sigma_rows, nullptr, n);
+  a.r.occ = occ;
+  a.r.g = lattice(nx, ny, nz, lo3, step3);
+  a.r.B = block;
+  a.r.bx = blocks_of(nx, block);
+  a.r.by = blocks_of(ny, block);
+  a.r.bz = blocks_of(nz, block);
+  a.r.origins = origins;
+  a.r.dirs = dirs;
+  a.r.tmin = tmin;
+  a.r.tmax = tmax;
+  a.r.N = N;
+  a.r.dt = dt;
+  a.r.t_stop = t_stop;
+  a.r.steps = steps;
+  a.imp_rows = reinterpret_cast<long long*>(imp_rows);
+  HIP_TRY(launch_volume_compact_importance(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_assign(const float* rows, int64_t m, const float* codebook, int64_t K, int degree, int32_t* assign, float* dist,
+                              void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("m", m)) return rc;
+  if (int rc = check_codes(K)) return rc;
+  if (dist && ((uintptr_t)dist & 3) != 0) return fail(NERF_HIP_ERR_ARG, "dist must be 4-byte aligned");
+  if (m == 0) return NERF_HIP_OK;
+  if (int rc = check_out(rows, "rows", 4)) return rc;
+  if (int rc = check_out(codebook, "codebook", 4)) return rc;
+  if (int rc = check_out(assign, "assign", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VqAssignArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.m = m;
+  a.codebook = codebook;
+  a.K = K;
+  a.assign = assign;
+  a.dist = dist;
+  HIP_TRY(launch_volume_vq_assign(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_accumulate(const float* rows, int64_t m, int degree, const int64_t* weight, int64_t imax, const int32_t* assign,
+                                  int64_t K, int64_t* sum, int64_t* cnt, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("m", m)) return rc;
+  if (int rc = check_codes(K)) return rc;
+  if (imax < 0) return fail(NERF_HIP_ERR_ARG, "imax=%lld < 0", (long long)imax);
+  if (weight && ((uintptr_t)weight & 7) != 0) return fail(NERF_HIP_ERR_ARG, "weight must be 8-byte aligned");
+  if (int rc = check_out(sum, "sum", 8)) return rc;
+  if (int rc = check_out(cnt, "cnt", 8)) return rc;
+  if (m == 0) return NERF_HIP_OK;
+  if (int rc = check_out(rows, "rows", 4)) return rc;
+  if (int rc = check_out(assign, "assign", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VqAccumulateArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.m = m;
+  a.words = 3 * (degree + 1) * (degree + 1);
+  a.weight = reinterpret_cast<const long long*>(weight);
+  a.imax = imax;
+  a.assign = assign;
+  a.K = K;
+  a.sum = reinterpret_cast<long long*>(sum);
+  a.cnt = reinterpret_cast<long long*>(cnt);
+  HIP_TRY(launch_volume_vq_accumulate(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_update(float* codebook, int64_t K, int degree, const int64_t* sum, const int64_t* cnt, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_codes(K)) return rc;
+  if (int rc = check_out(codebook, "codebook", 4)) return rc;
+  if (int rc = check_out(sum, "sum", 8)) return rc;
+  if (int rc = check_out(cnt, "cnt", 8)) return rc;
+  if (int rc = check_device()) return rc;
+  VqUpdateArgs a;
+  memset(&a, 0, sizeof(a));
+  a.codebook = codebook;
+  a.K = K;
+  a.words = 3 * (degree + 1) * (degree + 1);
+  a.sum = reinterpret_cast<const long long*>(sum);
+  a.cnt = reinterpret_cast<const long long*>(cnt);
+  HIP_TRY(launch_volume_vq_update(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_decode(const uint8_t* cls, const int32_t* rank, int64_t n, const uint16_t* code, int64_t n_coded, const void* kept,
+                              int64_t n_kept, const void* codebook, int64_t K, int degree, void* coef_rows, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (n_coded < 0 || n_kept < 0 || n_coded + n_kept > n) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld n_kept=%lld: classes of the %lld rows", (long long)n_coded, (long long)n_kept, (long long)n);
+  if (K < 0 || K > VQ_MAX_CODES) return fail(NERF_HIP_ERR_ARG, "K=%lld: 0 .. %d codes", (long long)K, VQ_MAX_CODES);
+  if (n_coded > 0 && K == 0) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld rows and no codebook", (long long)n_coded);
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(cls, "cls", 1)) return rc;
+  if (int rc = check_out(rank, "rank", 4)) return rc;
+  if (int rc = check_out(coef_rows, "coef_rows", 8)) return rc;
+  if (n_coded > 0) {
+    if (int rc = check_out(code, "code", 2)) return rc;
+    if (int rc = check_out(codebook, "codebook", 8)) return rc;
+  }
+  if (n_kept > 0) {
+    if (int rc = check_out(kept, "kept", 8)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VqDecodeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cls = cls;
+  a.rank = rank;
+  a.n = n;
+  a.code = code;
+  a.n_coded = n_coded;
+  a.kept = static_cast<const unsigned long long*>(kept);
+  a.n_kept = n_kept;
+  a.codebook = static_cast<const unsigned long long*>(codebook);
+  a.K = n_coded > 0 ? K : 0;
+  a.stride = vol_half_stride((degree + 1) * (degree + 1));
+  a.out = static_cast<unsigned long long*>(coef_rows);
+  HIP_TRY(launch_volume_vq_decode(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

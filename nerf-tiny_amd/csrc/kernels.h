@@ -951,6 +951,66 @@ hipError_t launch_volume_compact_render_backward(const VolCompactGradArgs& a, in
 hipError_t launch_volume_compact_adam_step(const VolCompactAdamArgs& a, hipStream_t st);
 hipError_t launch_volume_compact_tv_backward(const VolCompactTvArgs& a, hipStream_t st);
 
+// ---- vector-quantised compact volumes (volume_vq.hip; nerf_hip_volume_compact_importance and the nerf_hip_volume_vq_* calls,
+// DESIGN.md section 3h-17; rules VI, VQ-A, VQ-U and VQ-D of include/nerf_hip.h) ----
+constexpr int VQ_WG = 256;                     // k_volume_vq_assign: one row per lane
+constexpr int VQ_TILE = 128;                   // codes per LDS tile: 128 x 28 x 4 = 14 KiB at degree 2
+constexpr int VQ_SHIFT = 20;                   // NERF_HIP_VOLUME_VQ_SHIFT
+constexpr int VQ_MAX_CODES = 65536;            // NERF_HIP_VOLUME_VQ_MAX_CODES: a code is a uint16
+
+struct VolImportanceArgs {
+  VolCompact c;            // coef_rows is not read
+  VolRenderArgs r;         // the dense march's arguments; of its outputs only steps is written
+  long long* imp_rows;     // [n]: fixed-point sums, 2^-40 units
+};
+
+struct VqAssignArgs {
+  const float* rows;       // [m][3 ncoef]
+  long long m;
+  const float* codebook;   // [K][3 ncoef]
+  long long K;
+  int* assign;             // [m]
+  float* dist;             // [m] or null
+};
+
+struct VqAccumulateArgs {
+  const float* rows;       // [m][words]
+  long long m;
+  int words;               // 3 ncoef
+  const long long* weight; // [m] or null: u = 1
+  long long imax;          // <= 0: u = 1
+  const int* assign;       // [m]
+  long long K;
+  long long *sum, *cnt;    // [K][words], [K]: fixed-point sums, 2^-20 units
+};
+
+struct VqUpdateArgs {
+  float* codebook;         // [K][words]
+  long long K;
+  int words;
+  const long long *sum, *cnt;
+};
+
+struct VqDecodeArgs {
+  const unsigned char* cls;          // [n]: 0 pruned, 1 coded, 2 kept
+  const int* rank;                   // [n]: the row's rank within its class
+  long long n;
+  const unsigned short* code;        // [n_coded]
+  long long n_coded;
+  const unsigned long long* kept;    // [n_kept][stride / 4]: fp16 rows as 8-byte words
+  long long n_kept;
+  const unsigned long long* codebook;  // [K][stride / 4]
+  long long K;
+  int stride;                        // vol_half_stride(ncoef)
+  unsigned long long* out;           // [n][stride / 4]
+};
+
+hipError_t launch_volume_compact_importance(const VolImportanceArgs& a, hipStream_t st);
+hipError_t launch_volume_vq_assign(const VqAssignArgs& a, int ncoef, hipStream_t st);
+hipError_t launch_volume_vq_accumulate(const VqAccumulateArgs& a, hipStream_t st);
+hipError_t launch_volume_vq_update(const VqUpdateArgs& a, hipStream_t st);
+hipError_t launch_volume_vq_decode(const VqDecodeArgs& a, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

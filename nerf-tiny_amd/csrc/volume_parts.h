@@ -1,5 +1,5 @@
 // volume_parts.h -- the device helpers the SH radiance volume kernels share (volume.hip: the lookups and the march; volume_grad.hip:
-// the march's backward pass; volume_refine.hip: the TV prior; volume_compact.hip and volume_compact_grad.hip: the same lookups through a slot lattice; DESIGN.md sections 3h-12 to 3h-16): rule VL's cell, corners and interpolation and rule VS's basis, in the
+// the march's backward pass; volume_refine.hip: the TV prior; volume_compact.hip and volume_compact_grad.hip: the same lookups through a slot lattice; volume_vq.hip: the importance march; DESIGN.md sections 3h-12 to 3h-17): rule VL's cell, corners and interpolation and rule VS's basis, in the
 // fp32 order the rules of include/nerf_hip.h fix.  No kernel and no launch lives here.  Everything has internal linkage: every includer
 // gets its own copy.
 #pragma once

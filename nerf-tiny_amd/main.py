@@ -116,6 +116,16 @@ def build_parser() -> argparse.ArgumentParser:
                          "coefficients fp32 or fp16 (volume.CompactVolume; the march gives the dense form's bits, fp16 those of the rounded "
                          "coefficients), to <...>_volume<RES>_c32.npz / _c16.npz; the dense coefficient array is never allocated unless "
                          "--volume-finetune is given (default: the dense form)")
+    ap.add_argument("--volume-vq", type=int, default=None, metavar="K",
+                    help="--volume-compact also writes the vector-quantised FILE form (volume.quantize): every row is scored by the "
+                         "rendering weight the train views give it, the rows are replaced by an index into a K-code k-means codebook "
+                         "(1 .. 65536), to <the compact file's stem>_vq<K>.npz; volume.dequantize turns the file back into the compact "
+                         "form, device memory is not reduced (default: none)")
+    ap.add_argument("--volume-vq-iters", type=int, default=10, metavar="N", help="k-means iterations of --volume-vq (default 10)")
+    ap.add_argument("--volume-vq-prune", type=float, default=None, metavar="SHARE",
+                    help="--volume-vq drops the least important rows that together hold at most SHARE of the importance (default: none)")
+    ap.add_argument("--volume-vq-keep", type=float, default=0.0, metavar="SHARE",
+                    help="--volume-vq keeps verbatim the most important rows that together hold at most SHARE of the importance (default 0)")
     ap.add_argument("--volume-finetune", type=int, default=0, metavar="ITERS",
                     help="--volume then fine-tunes the baked sigma and coefficients for ITERS Adam steps against the train split's own "
                          "pixels with the support frozen (volume.finetune; rank 0) and also writes <...>_volume<RES>_ft<ITERS>.npz; with "
@@ -173,6 +183,8 @@ if __name__ == "__main__":
     import nerf_tiny_amd as P
 
     args = build_parser().parse_args()
+    if args.volume_vq is not None and args.volume_compact is None:
+        raise ValueError("--volume-vq needs --volume-compact")  # before any training
     if args.volume_finetune_compact and (args.volume_compact is None or args.volume_finetune <= 0):
         raise ValueError("--volume-finetune-compact needs --volume-compact and --volume-finetune ITERS > 0")  # before any training
     conf = ConfigParser()
@@ -216,7 +228,8 @@ if __name__ == "__main__":
                         finetune_lr={k: x for k, x in (("lr_sigma", args.volume_lr_sigma), ("lr_coef", args.volume_lr_coef)) if x is not None},
                         finetune_tv=(args.volume_tv_sigma, args.volume_tv_coef) if (args.volume_tv_sigma or args.volume_tv_coef) else None,
                         finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune, compact=args.volume_compact,
-                        finetune_compact=args.volume_finetune_compact)
+                        finetune_compact=args.volume_finetune_compact, vq=args.volume_vq, vq_iters=args.volume_vq_iters,
+                        vq_prune=args.volume_vq_prune, vq_keep=args.volume_vq_keep)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

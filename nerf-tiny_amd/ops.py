@@ -1395,3 +1395,134 @@ def volume_compact_tv_backward(slot, sigma_rows, coef_rows, degree, point, w_sig
     _abi.check(_abi.lib().nerf_hip_volume_compact_tv_backward(slot.data_ptr(), row(sigma_rows), row(coef_rows), row(point), n, nx, ny, nz,
                                                               int(degree), float(w_sigma), float(w_coef), float(eps), row(acc_sigma_rows),
                                                               row(acc_coef_rows), _stream(slot)))
+
+
+VQ_MAX_CODES = 65536   # NERF_HIP_VOLUME_VQ_MAX_CODES: a code is a uint16
+VQ_SHIFT = 20          # NERF_HIP_VOLUME_VQ_SHIFT
+
+
+def volume_compact_importance(slot, sigma_rows, occ, block, lo, step, origins, dirs, tmin, tmax, dt, t_stop, imp_rows):
+    """Rule VI: volume_compact_render's march without a colour; every contributing sample's weight, split by the trilinear corner terms,
+    ADDED IN PLACE to the int64 fixed-point words imp_rows [n] (units of 2^-40) of the corners that have a row
+    (nerf_hip_volume_compact_importance) -> steps[N, 2] int32, volume_compact_render's own.  Enqueue only."""
+    if slot.device.type != "cuda" or slot.dtype != torch.int32 or not slot.is_contiguous() or slot.dim() != 3:
+        raise ValueError(f"slot {tuple(slot.shape)} {slot.dtype}: a contiguous int32 device tensor [nx, ny, nz]")
+    dev = slot.device
+    sigma_rows = _vol_f32(sigma_rows, "sigma rows")
+    if sigma_rows.dim() != 1 or sigma_rows.device != dev:
+        raise ValueError(f"sigma rows {tuple(sigma_rows.shape)}: [n] on the slots' device")
+    n = int(sigma_rows.shape[0])
+    _vol_acc(imp_rows, "imp rows", (n,))
+    if imp_rows.device != dev:
+        raise ValueError("the importance words and the slots live on different devices")
+    nx, ny, nz = (int(x) for x in slot.shape)
+    block = min(int(block), 2**31 - 1)
+    if occ.device != dev or occ.dtype != torch.uint8 or not occ.is_contiguous() or (
+            block >= 1 and tuple(occ.shape) != volume_block_dims((nx, ny, nz), block)):
+        raise ValueError(f"occ {tuple(occ.shape)} {occ.dtype}: the contiguous uint8 block occupancy of sigma for block={block}")
+    origins = origins.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    dirs = dirs.to(dev, torch.float32).reshape(-1, 3).contiguous()
+    N = int(origins.shape[0])
+    if dirs.shape != origins.shape:
+        raise ValueError(f"dirs {tuple(dirs.shape)} and origins {tuple(origins.shape)} differ")
+    win = lambda t: torch.as_tensor(t, dtype=torch.float32).to(dev).expand(N).contiguous() if torch.as_tensor(t).dim() == 0 else \
+        torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous()
+    tmin, tmax = win(tmin), win(tmax)
+    if tmin.shape[0] != N or tmax.shape[0] != N:
+        raise ValueError(f"tmin / tmax: a scalar or one entry per ray ({N})")
+    steps = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if N else None
+    row = lambda t: t.data_ptr() if n else None
+    _abi.check(_abi.lib().nerf_hip_volume_compact_importance(slot.data_ptr(), row(sigma_rows), n, occ.data_ptr(), nx, ny, nz, block,
+                                                             _abi.f32_array(lo), _abi.f32_array(step), ptr(origins), ptr(dirs), ptr(tmin),
+                                                             ptr(tmax), N, float(dt), float(t_stop), row(imp_rows), ptr(steps),
+                                                             _stream(slot)))
+    return steps
+
+
+def _vq_rows(rows, what="rows"):
+    """fp32 rows [m, W], W in (3, 12, 27) -> (m, degree)"""
+    rows = _vol_f32(rows, what)
+    if rows.dim() != 2 or int(rows.shape[1]) not in (3, 12, 27):
+        raise ValueError(f"{what} {tuple(rows.shape)}: [m, 3 (degree + 1)^2]")
+    return int(rows.shape[0]), {3: 0, 12: 1, 27: 2}[int(rows.shape[1])]
+
+
+def _vq_codebook(codebook, degree, dev):
+    K, d2 = _vq_rows(codebook, "codebook")
+    if d2 != degree or codebook.device != dev:
+        raise ValueError(f"codebook {tuple(codebook.shape)}: [K, {3 * (degree + 1) ** 2}] on the rows' device")
+    if not 1 <= K <= VQ_MAX_CODES:
+        raise ValueError(f"K={K}: a codebook has 1 .. {VQ_MAX_CODES} codes")
+    return K
+
+
+def volume_vq_assign(rows, codebook, with_dist=False):
+    """Rule VQ-A: the nearest code of every fp32 row [m, W] in the fp32 codebook [K, W] under the fp32 running-sum distance, the lowest
+    index on a tie (nerf_hip_volume_vq_assign) -> assign [m] int32, or (assign, dist [m] fp32).  Enqueue only."""
+    m, degree = _vq_rows(rows)
+    K = _vq_codebook(codebook, degree, rows.device)
+    assign = torch.empty(m, dtype=torch.int32, device=rows.device)
+    dist = torch.empty(m, device=rows.device) if with_dist else None
+    ptr = lambda t: t.data_ptr() if (t is not None and m) else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_assign(ptr(rows), m, codebook.data_ptr(), K, degree, ptr(assign), ptr(dist), _stream(rows)))
+    return (assign, dist) if with_dist else assign
+
+
+def volume_vq_accumulate(rows, weight, imax, assign, K, sums=None, counts=None):
+    """Rule VQ-U's ACCUMULATE: the weighted fixed-point sums of the rows of every code, ADDED to sums [K, W] and counts [K] (int64,
+    units of 2^-20; zeroed buffers are made when None).  weight [m] int64 in [0, imax] or None (u = 1)
+    (nerf_hip_volume_vq_accumulate) -> (sums, counts).  Enqueue only."""
+    m, degree = _vq_rows(rows)
+    dev, W = rows.device, int(rows.shape[1])
+    K = int(K)
+    if not 1 <= K <= VQ_MAX_CODES:
+        raise ValueError(f"K={K}: a codebook has 1 .. {VQ_MAX_CODES} codes")
+    if weight is not None:
+        _vol_acc(weight, "weight", (m,))
+    if assign.device != dev or assign.dtype != torch.int32 or not assign.is_contiguous() or tuple(assign.shape) != (m,):
+        raise ValueError(f"assign: a contiguous int32 device tensor [{m}]")
+    sums = torch.zeros(K, W, dtype=torch.int64, device=dev) if sums is None else _vol_acc(sums, "sums", (K, W))
+    counts = torch.zeros(K, dtype=torch.int64, device=dev) if counts is None else _vol_acc(counts, "counts", (K,))
+    ptr = lambda t: t.data_ptr() if (t is not None and m) else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_accumulate(ptr(rows), m, degree, ptr(weight), int(imax), ptr(assign), K, sums.data_ptr(),
+                                                        counts.data_ptr(), _stream(rows)))
+    return sums, counts
+
+
+def volume_vq_update(codebook, sums, counts):
+    """Rule VQ-U's UPDATE, IN PLACE: every word of a code with a positive count becomes (float)(sum / count); an empty code keeps its
+    words (nerf_hip_volume_vq_update).  Enqueue only."""
+    K, degree = _vq_rows(codebook, "codebook")
+    K = _vq_codebook(codebook, degree, codebook.device)
+    _vol_acc(sums, "sums", (K, int(codebook.shape[1])))
+    _vol_acc(counts, "counts", (K,))
+    _abi.check(_abi.lib().nerf_hip_volume_vq_update(codebook.data_ptr(), K, degree, sums.data_ptr(), counts.data_ptr(), _stream(codebook)))
+    return codebook
+
+
+def volume_vq_decode(cls, rank, code, kept, codebook, degree):
+    """Rule VQ-D: cls [n] uint8 (0 pruned, 1 coded, 2 kept), rank [n] int32 (the rank within the class), code [n_coded] uint16, kept
+    [n_kept, S] and codebook [K, S] fp16 -> the fp16 rows [n, S] of rule VC (nerf_hip_volume_vq_decode).  Enqueue only."""
+    if degree not in (0, 1, 2):
+        raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+    S = volume_row_width(degree, True)
+    dev = cls.device
+    if dev.type != "cuda" or cls.dtype != torch.uint8 or cls.dim() != 1 or not cls.is_contiguous():
+        raise ValueError("cls: a contiguous uint8 device tensor [n]")
+    n = int(cls.shape[0])
+    if rank.device != dev or rank.dtype != torch.int32 or tuple(rank.shape) != (n,) or not rank.is_contiguous():
+        raise ValueError(f"rank: a contiguous int32 device tensor [{n}]")
+    if code.device != dev or code.dtype != torch.uint16 or code.dim() != 1 or not code.is_contiguous():
+        raise ValueError("code: a contiguous uint16 device tensor [n_coded]")
+    for t, what in ((kept, "kept"), (codebook, "codebook")):
+        if t.device != dev or t.dtype != torch.float16 or t.dim() != 2 or int(t.shape[1]) != S or not t.is_contiguous():
+            raise ValueError(f"{what} {tuple(t.shape)} {t.dtype}: a contiguous fp16 device tensor [., {S}]")
+    n_coded, n_kept, K = int(code.shape[0]), int(kept.shape[0]), int(codebook.shape[0])
+    if K > VQ_MAX_CODES:
+        raise ValueError(f"K={K}: a codebook has at most {VQ_MAX_CODES} codes")
+    out = torch.empty(n, S, dtype=torch.float16, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_decode(ptr(cls), ptr(rank), n, ptr(code), n_coded, ptr(kept), n_kept, ptr(codebook), K, int(degree),
+                                                    ptr(out), _stream(cls)))
+    return out

@@ -582,7 +582,7 @@ class NeRFRunner:
 
     def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
                     finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None, compact=None,
-                    finetune_compact=False):
+                    finetune_compact=False, vq=None, vq_iters=10, vq_prune=None, vq_keep=0.0):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
@@ -607,7 +607,15 @@ class NeRFRunner:
         finetune_compact = True (needs compact and finetune > 0: ValueError) trains the compact form itself: the bake goes straight into
         fp32 rows, the dense coefficient array is never allocated, the fine-tuning is volume.finetune_compact, and each volume is
         converted to ``compact``'s element type when it is written, previewed or returned.  The files hold the same arrays and carry
-        the same names; the finetune line gains the word ``compact``."""
+        the same names; the finetune line gains the word ``compact``.
+        VECTOR QUANTISATION (volume.quantize): vq = K (needs compact: ValueError) scores every row of the
+        volume that is returned -- after any fine-tuning -- by the rendering weight the TRAIN split's views give it
+        (volume.importance_views), quantises it with a K-code codebook (vq_iters k-means iterations, vq_prune / vq_keep the
+        importance shares that are dropped / kept verbatim) and, with save, writes the VQVolume beside the compact file as
+        ``<the compact file's stem>_vq<K>.npz``.  One ``[VOLUME] ... vq`` line prints the class counts and the byte counts; with
+        preview the split is also rendered from the DEQUANTIZED volume and both PSNR / SSIM pairs against the ground-truth images are
+        printed.  The return value stays the compact volume; self.last_volume_vq holds the numbers and the path.  vq = None computes,
+        prints and writes nothing new."""
         import numpy as np
 
         from . import volume
@@ -623,6 +631,12 @@ class NeRFRunner:
             raise ValueError(f"compact={compact!r}: None, 'fp32' or 'fp16'")
         if finetune_compact and (compact is None or not finetune):
             raise ValueError("finetune_compact trains the compact form: it needs compact = 'fp32' / 'fp16' and finetune > 0")
+        if vq is not None:
+            if compact is None:
+                raise ValueError("vq quantises the compact form: it needs compact = 'fp32' / 'fp16'")
+            from .volume import _check_k, _share
+            vq, vq_iters = _check_k(vq, vq_iters)
+            _share(vq_keep, "vq_keep"), (None if vq_prune is None else _share(vq_prune, "vq_prune"))
         ctag = "" if compact is None else {"fp32": "_c32", "fp16": "_c16"}[compact]
         shape = grid_shape(res)
         tv = (0.0, 0.0) if finetune_tv is None else tuple(float(w) for w in finetune_tv)
@@ -736,6 +750,40 @@ class NeRFRunner:
                 up = f"_up{len(ups)}" if ups else ""
                 volume.save(self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + "_ft" + str(int(finetune)) + up +
                             ctag + ".npz", vol)
+        if vq is not None:
+            t0 = time.perf_counter()
+            tr = self.train_rays
+            imp, _ = volume.importance_views(vol, tr.poses[:tr.pic_num], self.K_inv, tr.height, tr.width, views_per_call=4)
+            vqv = volume.quantize(vol, imp, K=vq, iters=vq_iters, prune_share=vq_prune, keep_share=vq_keep)
+            counts = [int((vqv.cls == k).sum()) for k in (0, 1, 2)]
+            seconds = time.perf_counter() - t0
+            self.last_volume_vq = {"K": int(vqv.codebook.shape[0]), "pruned": counts[0], "coded": counts[1], "kept": counts[2],
+                                   "nbytes": volume.nbytes(vqv), "compact_nbytes": volume.nbytes(vol), "seconds": seconds, "path": None}
+            scores = ""
+            if preview is not None:
+                rays = {"train": self.train_rays, "val": self.val_rays, "test": self.disp_rays}[preview]
+                H, W = rays.height, rays.width
+                truth = rays.pixels.view(rays.pic_num, H, W, 3)
+
+                def truth_scores(v):
+                    ms = [image_metrics(volume.render_views(v, rays.poses[i:i + 1], self.K_inv, H, W)[0], truth[i:i + 1]) for i in range(rays.pic_num)]
+                    return float(np.mean([float(m["psnr"][0]) for m in ms])), float(np.mean([float(m["ssim"][0]) for m in ms]))
+
+                was, now = truth_scores(vol), truth_scores(volume.dequantize(vqv))
+                scores = (f", {preview} views vs ground truth [PSNR] compact {was[0]:.3f} dB dequantized {now[0]:.3f} dB [SSIM] compact "
+                          f"{was[1]:.4f} dequantized {now[1]:.4f}")
+                self.last_volume_vq.update(psnr_compact=was[0], psnr_vq=now[0], ssim_compact=was[1], ssim_vq=now[1])
+            print(f"[VOLUME] {self.last_iter} vq {self.last_volume_vq['K']} codes, {vq_iters} iterations over {tr.pic_num} train views: "
+                  f"{counts[0]} rows pruned, {counts[1]} coded, {counts[2]} kept, {volume.nbytes(vqv)} bytes (compact {volume.nbytes(vol)} bytes)"
+                  f"{scores}, {seconds:.2f} s")
+            if save:
+                tag = str(shape[0]) if len(set(shape)) == 1 else "x".join(str(n) for n in shape)
+                ft = ("_ft" + str(int(finetune)) + (f"_up{len(ups)}" if ups else "")) if finetune else ""
+                path = self.results_path + self.start_time + "_" + str(self.last_iter) + "_volume" + tag + ft + ctag + f"_vq{vq}.npz"
+                if os.path.dirname(path):
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                volume.save(path, vqv)
+                self.last_volume_vq["path"] = path
         return vol
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,

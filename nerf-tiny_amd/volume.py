@@ -28,6 +28,13 @@ COMPACT TRAINING (rules VCG, VCU and VCT).  Calls of th
 ``CompactFinetuner`` / ``finetune_compact`` are ``Finetuner`` / ``finetune`` over fp32 rows with per-row moments.  Every result equals
 the dense call's on ``unpack(cvol)``, gathered at the rows, bit for bit; only a refinement goes through a transient dense level.
 
+VECTOR QUANTISATION (rules VI, VQ-A, VQ-U and VQ-D).  ``importance`` / ``importance_views`` score every row by
+the rendering weight the training rays give it, ``vq_classes`` sorts the rows into pruned / coded / kept with exact integer
+thresholds, ``kmeans`` clusters the coded rows on the device (reproducibly: fixed fp32 order, int64 sums), ``quantize`` puts the three
+together into a VQVolume and ``dequantize`` decodes that back to a CompactVolume with fp16 rows.  The VQVolume is what ``save`` makes
+SMALL (a bit mask, fp32 sigma, one class byte and at most one uint16 code per row, a codebook); on the device it is decoded before
+anything reads it -- sample, render and the training calls refuse it (TypeError) -- so device memory is NOT reduced by it.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -74,7 +81,16 @@ def _on_device(t, what):
     return t
 
 
+def _no_vq(vol, what):
+    """a VQVolume is a file form: nothing marches, samples or trains it"""
+    if isinstance(vol, VQVolume):
+        raise TypeError(f"{what} does not read a VQVolume: it is the small FILE form -- volume.dequantize(vq) gives the CompactVolume "
+                        "(fp16 rows) that is sampled, rendered and trained")
+    return vol
+
+
 def _dense_only(vol, what):
+    _no_vq(vol, what)
     if isinstance(vol, CompactVolume):
         raise TypeError(f"{what} works on the dense volume.Volume: a CompactVolume is the deployment form -- volume.unpack(cvol) gives the "
                         "dense volume back")
@@ -124,7 +140,10 @@ def unpack(cvol):
 
 
 def nbytes(vol):
-    """The bytes of the volume's arrays (dense: sigma, coef, occ; compact: slot, the rows, occ)."""
+    """The bytes of the volume's arrays (dense: sigma, coef, occ; compact: slot, the rows, occ; VQ: point, sigma, cls, code, kept,
+    codebook -- its file is smaller still: save writes a bit mask of the lattice in place of point)."""
+    if isinstance(vol, VQVolume):
+        return sum(int(t.numel()) * t.element_size() for t in (vol.point, vol.sigma, vol.cls, vol.code, vol.kept, vol.codebook))
     ts = (vol.slot, vol.sigma, vol.coef, vol.occ) if isinstance(vol, CompactVolume) else (vol.sigma, vol.coef, vol.occ)
     return sum(int(t.numel()) * t.element_size() for t in ts)
 
@@ -149,6 +168,7 @@ def active(sigma):
 def with_block(vol, block):
     """vol with its occupancy rebuilt for another block edge (the arrays are shared).  A CompactVolume rebuilds it from a temporary
     dense sigma of 4 bytes per lattice point."""
+    _no_vq(vol, "volume.with_block")
     if isinstance(vol, CompactVolume):
         _on_device(vol.slot, "volume.with_block")
         sigma, _ = ops.volume_compact_unpack(vol.sigma, None, _row_points(vol), vol.shape, vol.degree)
@@ -160,7 +180,7 @@ def sample(vol, points, dirs):
     """Rule VL: (sigma [M], rgb [M, 3]) of the volume at points [M, 3] along dirs [M, 3] (used as given, not renormalised): trilinear
     sigma, and the trilinear mean of the corners' SH colours clamped to [0, 1]; zeros outside the lattice.  A CompactVolume is looked
     up through its slots (rule VC-L): the same bits as sample(unpack(vol), ...)."""
-    _on_device(_anchor(vol), "volume.sample")
+    _on_device(_anchor(_no_vq(vol, "volume.sample")), "volume.sample")
     if isinstance(vol, CompactVolume):
         return ops.volume_compact_sample(vol.slot, vol.sigma, vol.coef, vol.degree, vol.lo.tolist(), vol.step.tolist(),
                                          _on_device(points, "volume.sample"), torch.as_tensor(dirs))
@@ -178,7 +198,7 @@ def render(vol, origins, dirs, tmin, tmax, dt=None, t_stop=1e-3, background=(0.0
     -> (rgb [N, 3], maps [N, 2] = (D, A) on render(maps=True)'s scale, steps [N, 2] int32 = (contributing, evaluated samples)).  Rays
     that miss the lattice get the background, zero maps and zero steps.  rgb, maps and steps[:, 0] do not depend on vol.block.  A
     CompactVolume is marched through its slots (rule VC-R): the same bits as render(unpack(vol), ...)."""
-    _on_device(_anchor(vol), "volume.render")
+    _on_device(_anchor(_no_vq(vol, "volume.render")), "volume.render")
     dt = default_dt(vol) if dt is None else float(dt)
     if isinstance(vol, CompactVolume):
         return ops.volume_compact_render(vol.slot, vol.sigma, vol.coef, vol.degree, vol.occ, vol.block, vol.lo.tolist(), vol.step.tolist(),
@@ -193,7 +213,7 @@ def render_views(vol, poses_bound17, K_inv, H, W, dt=None, t_stop=1e-3, backgrou
     metrics.image_metrics as they are."""
     from . import mesh
 
-    dev = _on_device(_anchor(vol), "volume.render_views").device
+    dev = _on_device(_anchor(_no_vq(vol, "volume.render_views")), "volume.render_views").device
     pb = torch.as_tensor(poses_bound17).to(dev, torch.float32).reshape(-1, 17)
     n, H, W = int(pb.shape[0]), int(H), int(W)
     o, d = mesh.camera_rays(pb, K_inv, H, W, device=dev)
@@ -446,6 +466,7 @@ class CompactGrad(NamedTuple):
 
 
 def _compact_only(cvol, what):
+    _no_vq(cvol, what)
     if not isinstance(cvol, CompactVolume):
         raise TypeError(f"{what} works on a volume.CompactVolume: volume.pack(vol) gives one; the dense volume.Volume has training "
                         "calls of its own (Finetuner, render_backward, tv_backward, finetune)")
@@ -604,7 +625,11 @@ def finetune_compact(cvol, rays, K_inv, iters, batch=4096, seed=None, background
 
 def save(path, vol):
     """The volume as a plain ``.npz`` (numpy.savez: sigma, coef, occ, lo, step, block, degree).  A CompactVolume is written with the
-    keys slot, sigma_rows, coef_rows (fp32 or fp16), occ, lo, step, block, degree: the key ``slot`` tells the forms apart."""
+    keys slot, sigma_rows, coef_rows (fp32 or fp16), occ, lo, step, block, degree: the key ``slot`` tells the forms apart.  A VQVolume
+    is written with the keys mask (numpy.packbits of the lattice: 1 where a point has a row), sigma_rows, cls, code, kept, codebook,
+    lo, step, block, degree, shape: the key ``codebook`` tells it from the other two."""
+    if isinstance(vol, VQVolume):
+        return _save_vq(path, vol)
     if isinstance(vol, CompactVolume):
         with open(path, "wb") as f:
             np.savez(f, slot=vol.slot.cpu().numpy(), sigma_rows=vol.sigma.detach().cpu().numpy(), coef_rows=vol.coef.detach().cpu().numpy(),
@@ -618,15 +643,243 @@ def save(path, vol):
 
 
 def load(path, device="cuda"):
-    """save()'s file -> the form it holds, a Volume or (a file with the key ``slot``) a CompactVolume, on ``device`` with the saved bits."""
+    """save()'s file -> the form it holds, a Volume, (a file with the key ``slot``) a CompactVolume or (the key ``codebook``) a
+    VQVolume, on ``device`` with the saved bits."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("volume.load puts the volume on a ROCm device (MI355X): there is no CPU path")
     with np.load(path) as z:
         t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])).to(dev)
+        if "codebook" in z.files:
+            return _load_vq(z, dev)
         if "slot" in z.files:
             slot = t("slot")
             return CompactVolume(slot, t("sigma_rows"), t("coef_rows"), t("occ"), z["lo"].astype(np.float32).reshape(3),
                                  z["step"].astype(np.float32).reshape(3), int(z["block"]), int(z["degree"]), tuple(int(n) for n in slot.shape))
         return Volume(t("sigma"), t("coef"), t("occ"), z["lo"].astype(np.float32).reshape(3), z["step"].astype(np.float32).reshape(3),
                       int(z["block"]), int(z["degree"]))
+
+
+# ---- vector-quantised volumes (DESIGN.md section 3h-17; rules VI, VQ-A, VQ-U and VQ-D of include/nerf_hip.h) ----
+
+VQ_MAX_CODES = ops.VQ_MAX_CODES
+VQ_MAX_WORD = 1024.0  # rule VQ-U's bound on a coded word: a row with a larger or non-finite word is kept verbatim
+
+
+class VQVolume(NamedTuple):
+    point: torch.Tensor     # [n] int32: the lattice point of each row, ascending (rule VA's list of the volume it came from)
+    sigma: torch.Tensor     # [n] fp32: the rows' sigma; a pruned row holds +0
+    cls: torch.Tensor       # [n] uint8: 0 pruned, 1 coded, 2 kept
+    code: torch.Tensor      # [n_coded] uint16: the coded rows' codes, in row order
+    kept: torch.Tensor      # [n_kept, S] fp16: the kept rows verbatim (rule VC's fp16 rows), in row order
+    codebook: torch.Tensor  # [K', S] fp16
+    lo: np.ndarray          # [3] fp32
+    step: np.ndarray        # [3] fp32
+    block: int
+    degree: int
+    shape: tuple            # (nx, ny, nz)
+
+
+def _vq_cvol(cvol, what):
+    if not isinstance(cvol, CompactVolume):
+        raise TypeError(f"{what} works on a volume.CompactVolume (volume.pack(vol) gives one; volume.dequantize(vq) turns a VQVolume "
+                        f"back into one), not on {type(cvol).__name__}")
+    _on_device(cvol.slot, what)
+    return cvol
+
+
+def importance(cvol, origins, dirs, tmin, tmax, acc=None, dt=None, t_stop=1e-3):
+    """Rule VI: the rendering weight every ROW of ``cvol`` receives from these rays -- render's march (the same samples, the same
+    w = T alpha, the same end at t_stop), each contributing sample's w split over the cell's corners by the trilinear terms and added
+    to the corners' rows in int64 fixed point (units of 2^-40, as the gradient accumulators).  Either row dtype: no coefficient is
+    read.  ``acc`` [n] int64 is ADDED to (a zeroed one is made when None), so batches and views accumulate; the sums hold the same
+    bits whatever the ray order, the batch split or cvol.block.  -> (acc, steps [N, 2] = render's own steps)"""
+    _vq_cvol(cvol, "volume.importance")
+    n = int(cvol.sigma.shape[0])
+    if acc is None:
+        acc = torch.zeros(n, dtype=torch.int64, device=cvol.slot.device)
+    dt = default_dt(cvol) if dt is None else float(dt)
+    steps = ops.volume_compact_importance(cvol.slot, cvol.sigma.detach(), cvol.occ, cvol.block, cvol.lo.tolist(), cvol.step.tolist(),
+                                          _on_device(origins, "volume.importance"), torch.as_tensor(dirs), tmin, tmax, dt, t_stop, acc)
+    return acc, steps
+
+
+def importance_views(cvol, poses_bound17, K_inv, H, W, acc=None, views_per_call=None, dt=None, t_stop=1e-3):
+    """``importance`` over the cameras poses_bound17 [n, 17] along render_views' own rays (mesh.camera_rays; each camera's window its
+    near / far), ``views_per_call`` cameras per call (None: all at once) -> (acc, steps [n, H, W, 2])."""
+    from . import mesh
+
+    dev = _vq_cvol(cvol, "volume.importance_views").slot.device
+    pb = torch.as_tensor(poses_bound17).to(dev, torch.float32).reshape(-1, 17)
+    n, H, W = int(pb.shape[0]), int(H), int(W)
+    per = n if views_per_call is None else int(views_per_call)
+    if n and per < 1:
+        raise ValueError(f"views_per_call={views_per_call!r}: an int >= 1")
+    if acc is None:
+        acc = torch.zeros(int(cvol.sigma.shape[0]), dtype=torch.int64, device=dev)
+    steps = []
+    for v0 in range(0, n, max(per, 1)):
+        part = pb[v0:v0 + per]
+        o, d = mesh.camera_rays(part, K_inv, H, W, device=dev)
+        near, far = part[:, 15].repeat_interleave(H * W), part[:, 16].repeat_interleave(H * W)
+        steps.append(importance(cvol, o, d, near, far, acc=acc, dt=dt, t_stop=t_stop)[1])
+    steps = torch.cat(steps) if steps else torch.zeros(0, 2, dtype=torch.int32, device=dev)
+    return acc, steps.view(n, H, W, 2)
+
+
+def _share(share, what):
+    from fractions import Fraction
+
+    f = Fraction(share)
+    if not 0 <= f <= 1:
+        raise ValueError(f"{what}={share!r}: a share lies in [0, 1]")
+    return f
+
+
+def vq_classes(imp, prune_share=None, keep_share=0.0, rows=None):
+    """The class of every row from its importance imp [n] (int64, >= 0) -> cls [n] uint8: 0 pruned, 1 coded, 2 kept.  EXACT: the rows
+    are ordered by (imp ascending, row ascending) -- a stable sort --, the running sums are int64 and the thresholds integers,
+    floor(Fraction(share) * total):
+      * pruned: the rows from the bottom of the order whose running sum is <= floor(prune_share * total); prune_share = None prunes
+        nothing, not even a row of importance 0 (prune_share = 0 prunes exactly those at the bottom);
+      * kept: the rows from the top of the order whose running sum FROM THE TOP is <= floor(keep_share * total);
+      * a row that is both is pruned; every other row is coded;
+      * with ``rows`` [n, W] (fp32 or fp16): a row with a non-finite word or one of magnitude above 1024 is kept whatever its
+        importance -- rule VQ-U's overflow bound needs the coded words within 2^10.
+    One host read (the total).  The one call of this family that also takes CPU tensors: there is no kernel in it."""
+    imp = torch.as_tensor(imp)  # exact integer plumbing: it runs wherever imp lives
+    if imp.dtype != torch.int64 or imp.dim() != 1:
+        raise ValueError(f"imp {tuple(imp.shape)} {imp.dtype}: int64 [n]")
+    n, dev = int(imp.shape[0]), imp.device
+    prune = None if prune_share is None else _share(prune_share, "prune_share")
+    keep = _share(keep_share, "keep_share")
+    cls = torch.ones(n, dtype=torch.uint8, device=dev)
+    if n:
+        if int(imp.min()) < 0:
+            raise ValueError("imp: an importance is a sum of weights, >= 0")
+        srt, order = torch.sort(imp, stable=True)
+        cs = torch.cumsum(srt, 0)
+        total = int(cs[-1])
+        from_top = (total - cs) + srt
+        kept = from_top <= int(keep * total)
+        cls[order[kept]] = 2
+        if prune is not None:
+            cls[order[cs <= int(prune * total)]] = 0
+    if rows is not None:
+        if tuple(rows.shape[:1]) != (n,) or rows.device != dev:
+            raise ValueError(f"rows {tuple(rows.shape)}: one per importance ({n}) on its device")
+        r32 = rows.to(torch.float32)
+        cls[~(torch.isfinite(r32) & (r32.abs() <= VQ_MAX_WORD)).all(dim=1)] = 2
+    return cls
+
+
+def _check_k(K, iters=0):
+    if int(K) != K or not 1 <= int(K) <= VQ_MAX_CODES:
+        raise ValueError(f"K={K!r}: a codebook has 1 .. {VQ_MAX_CODES} codes (a code is a uint16)")
+    if int(iters) != iters or int(iters) < 0:
+        raise ValueError(f"iters={iters!r}: an int >= 0")
+    return int(K), int(iters)
+
+
+def kmeans(rows, weight, K, iters):
+    """Weighted k-means over the fp32 rows [m, W] (rules VQ-A and VQ-U) -> (codebook [K', W] fp32, assign [m] int32), K' = min(K, m).
+    INIT: codebook[j] is the row at position (j m) // K' of the order (weight descending, row ascending) -- with K' = m every row is
+    its own code.  ONE ITERATION: assign, zero the sums, accumulate, update; after ``iters`` of them one more assign gives the codes.
+    weight [m] int64 >= 0 or None (every row counts 1).  Every step is exact or a fixed order of fp32 roundings, the sums are int64:
+    the result has one value, whatever the order the device works in.  One host read (the largest weight)."""
+    rows = _on_device(rows, "volume.kmeans")
+    K, iters = _check_k(K, iters)
+    m, dev = int(rows.shape[0]), rows.device
+    if weight is not None:
+        if weight.dtype != torch.int64 or tuple(weight.shape) != (m,) or weight.device != dev:
+            raise ValueError(f"weight: int64 [{m}] on the rows' device")
+        if m and int(weight.min()) < 0:
+            raise ValueError("weight: an importance is a sum of weights, >= 0")
+    if m == 0:
+        return rows.new_zeros((0,) + tuple(rows.shape[1:])), torch.zeros(0, dtype=torch.int32, device=dev)
+    Kp = min(K, m)
+    order = torch.arange(m, device=dev) if weight is None else torch.sort(weight, descending=True, stable=True)[1]
+    codebook = rows[order[(torch.arange(Kp, device=dev) * m) // Kp]].contiguous().clone()
+    imax = 0 if weight is None else int(weight.max())
+    weight = None if weight is None else weight.contiguous()
+    sums = counts = None
+    for _ in range(iters):
+        assign = ops.volume_vq_assign(rows, codebook)
+        if sums is not None:
+            sums.zero_(), counts.zero_()
+        sums, counts = ops.volume_vq_accumulate(rows, weight, imax, assign, Kp, sums, counts)
+        ops.volume_vq_update(codebook, sums, counts)
+    return codebook, ops.volume_vq_assign(rows, codebook)
+
+
+def _rows_to_half(rows32, degree):
+    """fp32 rows [k, 3 ncoef] -> rule VC's fp16 rows [k, S] (+0 pads), rounded by pack's own call as ``convert`` rounds"""
+    k = int(rows32.shape[0])
+    k4 = max(8, (k + 3) // 4 * 4)
+    lattice = torch.zeros(k4 // 4, 2, 2, (degree + 1) ** 2, 3, device=rows32.device)
+    lattice.reshape(k4, -1)[:k] = rows32
+    return ops.volume_compact_pack(None, lattice, None, True)[1][:k].contiguous()
+
+
+def quantize(cvol, imp, K=4096, iters=10, prune_share=None, keep_share=0.0):
+    """``cvol`` as a VQVolume (VQRF's three steps): vq_classes(imp, prune_share, keep_share, rows) sorts the rows into pruned, coded and
+    kept; the coded rows (fp16 rows widened first, exactly) are clustered by kmeans(.., weight = their importance, K, iters); the
+    codebook and the kept rows are rounded to fp16 ONCE, with convert's rule.  A pruned row keeps its place in the list with sigma +0
+    -- sigma stays fp32 and no other sigma moves, so the support and rule VA's list are those of ``cvol``.  The rows of ``cvol`` must
+    be in the order of their lattice points (pack and the compact bake make them so)."""
+    _vq_cvol(cvol, "volume.quantize")
+    K, iters = _check_k(K, iters)
+    n, words, dev = int(cvol.sigma.shape[0]), 3 * (cvol.degree + 1) ** 2, cvol.slot.device
+    imp = _on_device(imp, "volume.quantize")
+    if imp.dtype != torch.int64 or tuple(imp.shape) != (n,):
+        raise ValueError(f"imp {tuple(imp.shape)} {imp.dtype}: int64, one per row ({n})")
+    point = _row_points(cvol)
+    if n and (int(point[0]) < 0 or (n > 1 and not bool((point[1:] > point[:-1]).all()))):
+        raise ValueError("volume.quantize: the rows are not in the order of their lattice points (or a row has no point)")
+    rows32 = cvol.coef.detach()[:, :words].to(torch.float32).contiguous()
+    cls = vq_classes(imp, prune_share, keep_share, rows=rows32)
+    coded = cls == 1
+    codebook, assign = kmeans(rows32[coded].contiguous(), imp[coded].contiguous(), K, iters)
+    zero = torch.zeros((), device=dev)
+    return VQVolume(point, torch.where(cls == 0, zero, cvol.sigma.detach()), cls, assign.to(torch.uint16),
+                    _rows_to_half(rows32[cls == 2], cvol.degree), _rows_to_half(codebook, cvol.degree),
+                    np.asarray(cvol.lo, np.float32), np.asarray(cvol.step, np.float32), cvol.block, cvol.degree, tuple(cvol.shape))
+
+
+def dequantize(vq):
+    """Rule VQ-D: the VQVolume as a CompactVolume with fp16 rows -- the slots from ``point`` (volume_compact_slots), every row from
+    its class (a coded row copies its code's words, a kept row its own, a pruned row is +0 with sigma +0), occ rebuilt from the
+    decoded sigma as with_block does.  The device-side form is rule VC's again: the quantised form makes the FILE small, not the
+    memory the marcher reads."""
+    if not isinstance(vq, VQVolume):
+        raise TypeError("volume.dequantize takes a VQVolume")
+    _on_device(vq.point, "volume.dequantize")
+    cls = vq.cls
+    coded, kept = cls == 1, cls == 2
+    rank = torch.where(coded, torch.cumsum(coded, 0) - 1, torch.where(kept, torch.cumsum(kept, 0) - 1, 0)).to(torch.int32)
+    rows = ops.volume_vq_decode(cls.contiguous(), rank.contiguous(), vq.code, vq.kept, vq.codebook, vq.degree)
+    slot = ops.volume_compact_slots(vq.point, vq.shape)
+    sigma, _ = ops.volume_compact_unpack(vq.sigma, None, vq.point, vq.shape, vq.degree)
+    return CompactVolume(slot, vq.sigma, rows, blocks(sigma, vq.block), np.asarray(vq.lo, np.float32), np.asarray(vq.step, np.float32),
+                         vq.block, vq.degree, tuple(vq.shape))
+
+
+def _save_vq(path, vq):
+    """point is stored as a numpy.packbits mask of the lattice (1 bit per lattice point instead of 4 bytes per row or per point)"""
+    npts = int(np.prod(vq.shape))
+    mask = np.zeros(npts, bool)
+    mask[vq.point.cpu().numpy().astype(np.int64)] = True
+    with open(path, "wb") as f:
+        np.savez(f, mask=np.packbits(mask), sigma_rows=vq.sigma.detach().cpu().numpy(), cls=vq.cls.cpu().numpy(), code=vq.code.cpu().numpy(),
+                 kept=vq.kept.cpu().numpy(), codebook=vq.codebook.cpu().numpy(), lo=np.asarray(vq.lo, np.float32),
+                 step=np.asarray(vq.step, np.float32), block=np.int64(vq.block), degree=np.int64(vq.degree),
+                 shape=np.asarray(vq.shape, np.int64))
+
+
+def _load_vq(z, dev):
+    t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k])).to(dev)
+    shape = tuple(int(x) for x in z["shape"])
+    mask = np.unpackbits(z["mask"], count=int(np.prod(shape))).astype(bool)
+    point = torch.from_numpy(np.flatnonzero(mask).astype(np.int32)).to(dev)
+    return VQVolume(point, t("sigma_rows"), t("cls"), t("code"), t("kept"), t("codebook"), z["lo"].astype(np.float32).reshape(3),
+                    z["step"].astype(np.float32).reshape(3), int(z["block"]), int(z["degree"]), shape)
