@@ -1699,6 +1699,79 @@ int nerf_hip_volume_vq_update(float* codebook, int64_t K, int degree, const int6
 int nerf_hip_volume_vq_decode(const uint8_t* cls, const int32_t* rank, int64_t n, const uint16_t* code, int64_t n_coded, const void* kept,
                               int64_t n_kept, const void* codebook, int64_t K, int degree, void* coef_rows, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ABI 7 additions.  Fine-tuning a vector-quantised volume: VQRF's fourth step -- the codebook, the kept rows
+ * and sigma trained jointly against the training rays with the assignments FROZEN.  Nothing of the calls above changes: the march
+ * and its gradient stay rules VC-R and VCG over fp32 rows; what is new is the way from the trainable state to those rows (VQ-X), the
+ * way from the rows' accumulators to the codes' (VQ-G) and an update over three kinds of parameter (VQ-V).  Throughout W = 3 ncoef and
+ *       sigma_rows[n]            fp32, trained;
+ *       kept32[n_kept][W]        fp32 masters of the kept rows, trained;
+ *       codebook32[K][W]         fp32 masters of the codebook, trained;
+ *       cls[n], rank[n], code[n_coded]   frozen, as in rule VQ-D.
+ *
+ * VQ-X. EXPAND: rule VQ-D in fp32 and without pads.  coef_rows[n][W] fp32: a coded row r receives the W words of
+ *    codebook32[code[rank[r]]], a kept row those of kept32[rank[r]], a pruned row +0 -- as does any row whose class is none of the
+ *    three, whose rank lies outside its class, or whose code is >= K.  No index becomes an address before it has been compared with
+ *    the size of its array.  One thread per (row, word).  These rows are what nerf_hip_volume_compact_render and
+ *    nerf_hip_volume_compact_render_backward read.  A row that receives +0 still has a slot, so rule VCG adds to its accumulator words
+ *    whenever it is a corner of a contributing cell, and nothing below consumes them: with acc_coef_rows not NULL, EXPAND also sets the
+ *    W accumulator words of every row that receives +0 to 0 (the words of the other rows are not touched).
+ *
+ * VQ-G. REDUCE: from the rows' accumulators to the codes'.  The coded rows are given GROUPED BY CODE: member[n_coded] (int32 row
+ *    numbers) and offset[K + 1] (int32, ascending, offset[0] = 0, offset[K] = n_coded): the members of code j are
+ *    member[offset[j] .. offset[j + 1]).  The caller builds both once -- the codes are frozen.  Then, for every code j and word w,
+ *       acc_code[j][w] += sum over the members r of code j of acc_coef_rows[r][w]
+ *    in plain int64 adds (two's complement: the sum of the members' words, whatever the order), and every word that was read is set
+ *    to 0.  The result does not depend on the order of the members within a code, on the launch shape or on where a large code is
+ *    split.  A member outside [0, n) is skipped and never becomes an address.  The members must be distinct (a row has one code); a
+ *    row listed twice is read and cleared by two threads in no order.  offset is DEVICE memory: the host cannot see it and refuses
+ *    only what it can (below); the kernel clamps -- code j covers [a_j, b_j) with a_j = min(max(offset[j], 0), n_coded) and
+ *    b_j = min(max(offset[j + 1], a_j), n_coded), so whatever offset holds no address leaves member[0 .. n_coded).
+ *    OVERFLOW PRECONDITION, as rule VG's: between two updates the sum, over the members of one code, of the |x| their words (m, ch)
+ *    received stays below 2^22; then |acc_code| < 2^62 < 2^63.  WHY IT HOLDS FOR ANY GROUPING.  One ray, one word (m, ch): sample i
+ *    sends ((tw_c Y_m) (w_i g_ch)) to corner c (rule VG).  A cell's corner terms tw_c are >= 0 and sum to 1; the weights w_i are >= 0
+ *    and sum to the ray's opacity, at most 1 (rule VR: w = T alpha, T = T - w from T = 1); |tw Y_m| < 1.1 (rule VG).  So the |x| one
+ *    ray sends to ALL rows together, for one word, sum to less than 1.1 |g_ch|.  With |g_rgb| <= 2 -- the gradient 2 (rgb - target) of
+ *    a squared error between colours in [0, 1] -- a batch of at most 2^20 rays sends less than 2.2 2^20 < 2^22 to all rows, hence to
+ *    the members of any one code, and to any one row (rule VG's own precondition).  The rounding of each contribution to a multiple of
+ *    2^-40 adds at most 2^-41 per contribution: with fewer than 2^31 contributions, below 2^-10.
+ *
+ * VQ-V. UPDATE: rule VU's word bracket, verbatim -- g = (double(acc) 2^-40) grad_scale, m' and v' each rounded to fp32 once,
+ *    x' = fp32(x - (lr ((m' / c1) / (sqrt(v' / c2) + eps)))), beta^step by squaring on the host, the accumulator word zeroed whatever
+ *    happens -- over three groups of words in one launch, one thread per word:
+ *       (a) the sigma word of every row r: x = sigma_rows[r], acc = acc_sigma_rows[r], lr = lr_sigma, with rule VCU's FROZEN SUPPORT (a
+ *           row whose sigma is not > 0 at entry is dead: x, m and v are left alone; otherwise sigma' = fmax(x', 0));
+ *       (b) the W words of every kept row k: x = kept32[k][w], acc = acc_coef_rows[kept_row[k]][w], lr = lr_coef; kept_row[n_kept]
+ *           (int32) is the row of kept row k; a kept_row outside [0, n) never becomes an address and its words are left alone;
+ *       (c) the K W words of the codebook: x = codebook32[j][w], acc = acc_code[j][w], lr = lr_coef.
+ *    m, v [n + n_kept W + K W] fp32 hold the moments in that order: 8 bytes of moments per coded row, where rule VCU holds 8 (1 + W).
+ *    The accumulator words of a pruned row's coefficients belong to none of the groups: rule VQ-X clears them.
+ *
+ * ONE STEP is: rule VC-R's render of the rows, rule VCG with 2 (rgb - target), VQ-G, VQ-V with grad_scale = 1 / (3 N), VQ-X.  With
+ * every code holding one row, or every row kept, it equals rule VCU's step on the same rows bit for bit.
+ *
+ * All three are enqueue-only and check every argument on the host first (NERF_HIP_ERR_ARG) as the calls above do: the degree, a
+ * count < 0 or >= 2^31, K outside [0, 65536] (and > 0 with coded rows), n_coded + n_kept > n, the scalars as rule VU states them, a
+ * NULL pointer or one that is not aligned to its element (int64: 8).  Zero counts succeed and launch nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define NERF_HIP_VOLUME_VQ_REDUCE_CHUNK 256
+
+/* VQ-X -> coef_rows[n][3 ncoef] (device, fp32); acc_coef_rows[n][3 ncoef] (int64) or NULL. */
+int nerf_hip_volume_vq_expand(const uint8_t* cls, const int32_t* rank, int64_t n, const uint16_t* code, int64_t n_coded, const float* kept32,
+                              int64_t n_kept, const float* codebook32, int64_t K, int degree, float* coef_rows, int64_t* acc_coef_rows,
+                              void* stream);
+
+/* VQ-G: acc_coef_rows[n][3 ncoef] -> ADDED to acc_code[K][3 ncoef] (device, int64), the words read are zeroed.  The members are walked
+ * in chunks of NERF_HIP_VOLUME_VQ_REDUCE_CHUNK consecutive entries of member[], one workgroup each. */
+int nerf_hip_volume_vq_grad_reduce(int64_t* acc_coef_rows, int64_t n, int degree, const int32_t* offset, const int32_t* member,
+                                   int64_t n_coded, int64_t K, int64_t* acc_code, void* stream);
+
+/* VQ-V.  The scalars are nerf_hip_volume_adam_step's. */
+int nerf_hip_volume_vq_adam_step(float* sigma_rows, int64_t n, float* kept32, const int32_t* kept_row, int64_t n_kept, float* codebook32,
+                                 int64_t K, int degree, int64_t* acc_sigma_rows, int64_t* acc_coef_rows, int64_t* acc_code, float* m,
+                                 float* v, double grad_scale, int64_t step, double lr_sigma, double lr_coef, double beta1, double beta2,
+                                 double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

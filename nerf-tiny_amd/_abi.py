@@ -177,6 +177,10 @@ _PROTOS = {
     "nerf_hip_volume_vq_accumulate": (C.c_int, [_p, C.c_int64, C.c_int, _p, C.c_int64, _p, C.c_int64, _p, _p, _p]),
     "nerf_hip_volume_vq_update": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, _p]),
     "nerf_hip_volume_vq_decode": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p]),
+    "nerf_hip_volume_vq_expand": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p, _p]),
+    "nerf_hip_volume_vq_grad_reduce": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, C.c_int64, C.c_int64, _p, _p]),
+    "nerf_hip_volume_vq_adam_step": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, C.c_int, _p, _p, _p, _p, _p, C.c_double,
+                                               C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p]),
 }
 EXPORTS = tuple(_PROTOS)
 

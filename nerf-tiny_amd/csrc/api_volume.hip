@@ -1,5 +1,5 @@
 // api_volume.hip -- the SH radiance volume part of the extern "C" surface of libnerf_hip.so (include/nerf_hip.h: rules VA, VS, VO, VL,
-// VR, VG, VU, VM, VT, VX, VP, VC, VCG, VCU, VCT, VI, VQ-A, VQ-U and VQ-D): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
+// VR, VG, VU, VM, VT, VX, VP, VC, VCG, VCU, VCT, VI, VQ-A, VQ-U, VQ-D, VQ-X, VQ-G and VQ-V): host code only, as api_geometry.hip -- argument checks, workspace carve-up and kernel sequencing on
 // the caller's stream.  No allocation, no host sync.
 #include <math.h>
 
@@ -952,6 +952,136 @@ int nerf_hip_volume_vq_decode(const uint8_t* cls, const int32_t* rank, int64_t n
   a.stride = vol_half_stride((degree + 1) * (degree + 1));
   a.out = static_cast<unsigned long long*>(coef_rows);
   HIP_TRY(launch_volume_vq_decode(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+static_assert(VQT_CHUNK == NERF_HIP_VOLUME_VQ_REDUCE_CHUNK, "the header states rule VQ-G's chunk");
+
+int nerf_hip_volume_vq_expand(const uint8_t* cls, const int32_t* rank, int64_t n, const uint16_t* code, int64_t n_coded, const float* kept32,
+                              int64_t n_kept, const float* codebook32, int64_t K, int degree, float* coef_rows, int64_t* acc_coef_rows,
+                              void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (n_coded < 0 || n_kept < 0 || n_coded + n_kept > n) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld n_kept=%lld: classes of the %lld rows", (long long)n_coded, (long long)n_kept, (long long)n);
+  if (K < 0 || K > VQ_MAX_CODES) return fail(NERF_HIP_ERR_ARG, "K=%lld: 0 .. %d codes", (long long)K, VQ_MAX_CODES);
+  if (n_coded > 0 && K == 0) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld rows and no codebook", (long long)n_coded);
+  if (acc_coef_rows && ((uintptr_t)acc_coef_rows & 7) != 0) return fail(NERF_HIP_ERR_ARG, "acc_coef_rows must be 8-byte aligned");
+  if (n == 0) return NERF_HIP_OK;
+  if (int rc = check_out(cls, "cls", 1)) return rc;
+  if (int rc = check_out(rank, "rank", 4)) return rc;
+  if (int rc = check_out(coef_rows, "coef_rows", 4)) return rc;
+  if (n_coded > 0) {
+    if (int rc = check_out(code, "code", 2)) return rc;
+    if (int rc = check_out(codebook32, "codebook32", 4)) return rc;
+  }
+  if (n_kept > 0) {
+    if (int rc = check_out(kept32, "kept32", 4)) return rc;
+  }
+  if (int rc = check_device()) return rc;
+  VqExpandArgs a;
+  memset(&a, 0, sizeof(a));
+  a.cls = cls;
+  a.rank = rank;
+  a.n = n;
+  a.code = code;
+  a.n_coded = n_coded;
+  a.kept32 = kept32;
+  a.n_kept = n_kept;
+  a.codebook32 = codebook32;
+  a.K = n_coded > 0 ? K : 0;
+  a.words = 3 * (degree + 1) * (degree + 1);
+  a.out = coef_rows;
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  HIP_TRY(launch_volume_vq_expand(a, static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_grad_reduce(int64_t* acc_coef_rows, int64_t n, int degree, const int32_t* offset, const int32_t* member,
+                                   int64_t n_coded, int64_t K, int64_t* acc_code, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (n_coded < 0 || n_coded > n) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld: the coded rows of %lld rows", (long long)n_coded, (long long)n);
+  if (K < 0 || K > VQ_MAX_CODES) return fail(NERF_HIP_ERR_ARG, "K=%lld: 0 .. %d codes", (long long)K, VQ_MAX_CODES);
+  if (n_coded > 0 && K == 0) return fail(NERF_HIP_ERR_ARG, "n_coded=%lld rows and no codebook", (long long)n_coded);
+  if (acc_coef_rows && ((uintptr_t)acc_coef_rows & 7) != 0) return fail(NERF_HIP_ERR_ARG, "acc_coef_rows must be 8-byte aligned");
+  if (acc_code && ((uintptr_t)acc_code & 7) != 0) return fail(NERF_HIP_ERR_ARG, "acc_code must be 8-byte aligned");
+  if (n_coded == 0) return NERF_HIP_OK;
+  if (int rc = check_out(acc_coef_rows, "acc_coef_rows", 8)) return rc;
+  if (int rc = check_out(acc_code, "acc_code", 8)) return rc;
+  if (int rc = check_out(offset, "offset", 4)) return rc;
+  if (int rc = check_out(member, "member", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VqReduceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  a.n = n;
+  a.offset = offset;
+  a.member = member;
+  a.n_coded = n_coded;
+  a.K = K;
+  a.acc_code = reinterpret_cast<long long*>(acc_code);
+  HIP_TRY(launch_volume_vq_grad_reduce(a, (degree + 1) * (degree + 1), static_cast<hipStream_t>(stream)));
+  return NERF_HIP_OK;
+}
+
+int nerf_hip_volume_vq_adam_step(float* sigma_rows, int64_t n, float* kept32, const int32_t* kept_row, int64_t n_kept, float* codebook32,
+                                 int64_t K, int degree, int64_t* acc_sigma_rows, int64_t* acc_coef_rows, int64_t* acc_code, float* m,
+                                 float* v, double grad_scale, int64_t step, double lr_sigma, double lr_coef, double beta1, double beta2,
+                                 double eps, void* stream) {
+  if (int rc = check_degree(degree)) return rc;
+  if (int rc = check_count("n", n)) return rc;
+  if (n_kept < 0 || n_kept > n) return fail(NERF_HIP_ERR_ARG, "n_kept=%lld: the kept rows of %lld rows", (long long)n_kept, (long long)n);
+  if (K < 0 || K > VQ_MAX_CODES) return fail(NERF_HIP_ERR_ARG, "K=%lld: 0 .. %d codes", (long long)K, VQ_MAX_CODES);
+  if (step < 1) return fail(NERF_HIP_ERR_ARG, "step=%lld: the first update is step 1", (long long)step);
+  if (!isfinite(grad_scale)) return fail(NERF_HIP_ERR_ARG, "grad_scale=%g must be finite", grad_scale);
+  if (!isfinite(lr_sigma) || !isfinite(lr_coef)) return fail(NERF_HIP_ERR_ARG, "lr_sigma=%g lr_coef=%g: the rates must be finite", lr_sigma, lr_coef);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(NERF_HIP_ERR_ARG, "beta1=%g beta2=%g: both lie in [0, 1)", beta1, beta2);
+  if (!(eps >= 0.0 && isfinite(eps))) return fail(NERF_HIP_ERR_ARG, "eps=%g must be finite and >= 0", eps);
+  if (n > 0 || acc_sigma_rows) {
+    if (int rc = check_out(acc_sigma_rows, "acc_sigma_rows", 8)) return rc;
+  }
+  if (acc_coef_rows && ((uintptr_t)acc_coef_rows & 7) != 0) return fail(NERF_HIP_ERR_ARG, "acc_coef_rows must be 8-byte aligned");
+  if (acc_code && ((uintptr_t)acc_code & 7) != 0) return fail(NERF_HIP_ERR_ARG, "acc_code must be 8-byte aligned");
+  if (n == 0 && K == 0) return NERF_HIP_OK;
+  if (n > 0) {
+    if (int rc = check_out(sigma_rows, "sigma_rows", 4)) return rc;
+  }
+  if (n_kept > 0) {
+    if (int rc = check_out(kept32, "kept32", 4)) return rc;
+    if (int rc = check_out(kept_row, "kept_row", 4)) return rc;
+    if (int rc = check_out(acc_coef_rows, "acc_coef_rows", 8)) return rc;
+  }
+  if (K > 0) {
+    if (int rc = check_out(codebook32, "codebook32", 4)) return rc;
+    if (int rc = check_out(acc_code, "acc_code", 8)) return rc;
+  }
+  if (int rc = check_out(m, "m", 4)) return rc;
+  if (int rc = check_out(v, "v", 4)) return rc;
+  if (int rc = check_device()) return rc;
+  VqAdamArgs a;
+  memset(&a, 0, sizeof(a));
+  a.sigma_rows = sigma_rows;
+  a.n = n;
+  a.kept32 = kept32;
+  a.kept_row = kept_row;
+  a.n_kept = n_kept;
+  a.codebook32 = codebook32;
+  a.K = K;
+  a.words = 3 * (degree + 1) * (degree + 1);
+  a.acc_sigma_rows = reinterpret_cast<long long*>(acc_sigma_rows);
+  a.acc_coef_rows = reinterpret_cast<long long*>(acc_coef_rows);
+  a.acc_code = reinterpret_cast<long long*>(acc_code);
+  a.m = m;
+  a.v = v;
+  a.grad_scale = grad_scale;
+  a.lr_sigma = lr_sigma;
+  a.lr_coef = lr_coef;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  a.c1 = 1.0 - pow_by_squaring(beta1, step);
+  a.c2 = 1.0 - pow_by_squaring(beta2, step);
+  HIP_TRY(launch_volume_vq_adam_step(a, static_cast<hipStream_t>(stream)));
   return NERF_HIP_OK;
 }
 

@@ -1011,6 +1011,54 @@ hipError_t launch_volume_vq_accumulate(const VqAccumulateArgs& a, hipStream_t st
 hipError_t launch_volume_vq_update(const VqUpdateArgs& a, hipStream_t st);
 hipError_t launch_volume_vq_decode(const VqDecodeArgs& a, hipStream_t st);
 
+// ---- fine-tuning a vector-quantised volume (volume_vq_train.hip; nerf_hip_volume_vq_expand, _grad_reduce, _adam_step, DESIGN.md
+// section 3h-18; rules VQ-X, VQ-G and VQ-V of include/nerf_hip.h) ----
+constexpr int VQT_WG = 256;                    // k_volume_vq_reduce: floor(256 / W) member lanes of W words each
+constexpr int VQT_CHUNK = 256;                 // NERF_HIP_VOLUME_VQ_REDUCE_CHUNK: consecutive entries of member[] per workgroup
+
+struct VqExpandArgs {
+  const unsigned char* cls;          // [n]
+  const int* rank;                   // [n]
+  long long n;
+  const unsigned short* code;        // [n_coded]
+  long long n_coded;
+  const float* kept32;               // [n_kept][words]
+  long long n_kept;
+  const float* codebook32;           // [K][words]
+  long long K;
+  int words;                         // 3 ncoef
+  float* out;                        // [n][words]
+  long long* acc_coef_rows;          // [n][words] or null: zeroed where a row receives +0
+};
+
+struct VqReduceArgs {
+  long long* acc_coef_rows;          // [n][3 ncoef]: read and zeroed at the members
+  long long n;
+  const int* offset;                 // [K + 1]: clamped by the kernel
+  const int* member;                 // [n_coded]: rows, grouped by code
+  long long n_coded, K;
+  long long* acc_code;               // [K][3 ncoef]
+};
+
+struct VqAdamArgs {
+  float* sigma_rows;                 // [n]
+  long long n;
+  float* kept32;                     // [n_kept][words]
+  const int* kept_row;               // [n_kept]
+  long long n_kept;
+  float* codebook32;                 // [K][words]
+  long long K;
+  int words;
+  long long *acc_sigma_rows, *acc_coef_rows, *acc_code;
+  float *m, *v;                      // [n + n_kept words + K words]
+  double grad_scale, lr_sigma, lr_coef, beta1, beta2, eps;
+  double c1, c2;                     // 1 - beta1^step, 1 - beta2^step
+};
+
+hipError_t launch_volume_vq_expand(const VqExpandArgs& a, hipStream_t st);
+hipError_t launch_volume_vq_grad_reduce(const VqReduceArgs& a, int ncoef, hipStream_t st);
+hipError_t launch_volume_vq_adam_step(const VqAdamArgs& a, hipStream_t st);
+
 // ---- texture atlases of indexed meshes (mesh_texture.hip; nerf_hip_mesh_atlas_texels, nerf_hip_mesh_texture_sample, DESIGN.md section
 // 3h-11; rules TA and TX of include/nerf_hip.h).  The atlas of (F, n): cells of c = n + 5 texels, Sx per row, W = Sx * c wide ----
 constexpr int TEX_WG = 256;

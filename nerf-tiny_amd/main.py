@@ -126,6 +126,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--volume-vq drops the least important rows that together hold at most SHARE of the importance (default: none)")
     ap.add_argument("--volume-vq-keep", type=float, default=0.0, metavar="SHARE",
                     help="--volume-vq keeps verbatim the most important rows that together hold at most SHARE of the importance (default 0)")
+    ap.add_argument("--volume-vq-finetune", type=int, default=0, metavar="ITERS",
+                    help="--volume-vq then fine-tunes the quantised form for ITERS Adam steps against the train split's own pixels -- the "
+                         "codebook, the kept rows and sigma, the codes frozen (volume.finetune_vq) -- and also writes "
+                         "<...>_vq<K>_ft<ITERS>.npz, a file of the same size (default 0: the quantisation alone)")
+    ap.add_argument("--volume-vq-finetune-batch", type=int, default=4096, metavar="N",
+                    help="rays per --volume-vq-finetune step, at most 2^20 (default 4096)")
+    ap.add_argument("--volume-vq-lr-sigma", type=float, default=None, metavar="X",
+                    help="--volume-vq-finetune's Adam rate of sigma (default: volume.VQFinetuner's 0.1)")
+    ap.add_argument("--volume-vq-lr-coef", type=float, default=None, metavar="X",
+                    help="--volume-vq-finetune's Adam rate of the codebook and the kept rows (default: volume.VQFinetuner's 0.01)")
     ap.add_argument("--volume-finetune", type=int, default=0, metavar="ITERS",
                     help="--volume then fine-tunes the baked sigma and coefficients for ITERS Adam steps against the train split's own "
                          "pixels with the support frozen (volume.finetune; rank 0) and also writes <...>_volume<RES>_ft<ITERS>.npz; with "
@@ -185,6 +195,8 @@ if __name__ == "__main__":
     args = build_parser().parse_args()
     if args.volume_vq is not None and args.volume_compact is None:
         raise ValueError("--volume-vq needs --volume-compact")  # before any training
+    if args.volume_vq_finetune and args.volume_vq is None:
+        raise ValueError("--volume-vq-finetune needs --volume-vq")  # before any training
     if args.volume_finetune_compact and (args.volume_compact is None or args.volume_finetune <= 0):
         raise ValueError("--volume-finetune-compact needs --volume-compact and --volume-finetune ITERS > 0")  # before any training
     conf = ConfigParser()
@@ -229,7 +241,9 @@ if __name__ == "__main__":
                         finetune_tv=(args.volume_tv_sigma, args.volume_tv_coef) if (args.volume_tv_sigma or args.volume_tv_coef) else None,
                         finetune_upsample=tuple(args.volume_upsample_at), finetune_prune=args.volume_prune, compact=args.volume_compact,
                         finetune_compact=args.volume_finetune_compact, vq=args.volume_vq, vq_iters=args.volume_vq_iters,
-                        vq_prune=args.volume_vq_prune, vq_keep=args.volume_vq_keep)
+                        vq_prune=args.volume_vq_prune, vq_keep=args.volume_vq_keep, vq_finetune=args.volume_vq_finetune,
+                        vq_finetune_batch=args.volume_vq_finetune_batch, vq_lr_sigma=args.volume_vq_lr_sigma,
+                        vq_lr_coef=args.volume_vq_lr_coef)
     if args.mesh is not None:
         m = run.extract_mesh(args.mesh, args.mesh_level, lo=args.grid_bbox[:3], hi=args.grid_bbox[3:], save=True, normals=args.mesh_normals,
                              band=args.mesh_band, min_faces=args.mesh_min_faces, keep_largest=args.mesh_keep_largest,

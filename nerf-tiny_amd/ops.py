@@ -1526,3 +1526,107 @@ def volume_vq_decode(cls, rank, code, kept, codebook, degree):
     _abi.check(_abi.lib().nerf_hip_volume_vq_decode(ptr(cls), ptr(rank), n, ptr(code), n_coded, ptr(kept), n_kept, ptr(codebook), K, int(degree),
                                                     ptr(out), _stream(cls)))
     return out
+
+
+VQ_REDUCE_CHUNK = 256  # NERF_HIP_VOLUME_VQ_REDUCE_CHUNK: entries of member[] per workgroup of volume_vq_grad_reduce
+VQ_MAX_RAYS = 2**20    # rule VQ-G's overflow precondition: rays per update
+
+
+def _vq_classes(cls, rank, code):
+    """cls [n] uint8, rank [n] int32, code [n_coded] uint16, contiguous on one device -> (n, n_coded)"""
+    dev = cls.device
+    if dev.type != "cuda" or cls.dtype != torch.uint8 or cls.dim() != 1 or not cls.is_contiguous():
+        raise ValueError("cls: a contiguous uint8 device tensor [n]")
+    n = int(cls.shape[0])
+    if rank.device != dev or rank.dtype != torch.int32 or tuple(rank.shape) != (n,) or not rank.is_contiguous():
+        raise ValueError(f"rank: a contiguous int32 device tensor [{n}]")
+    if code.device != dev or code.dtype != torch.uint16 or code.dim() != 1 or not code.is_contiguous():
+        raise ValueError("code: a contiguous uint16 device tensor [n_coded]")
+    return n, int(code.shape[0])
+
+
+def _vq_masters(kept32, codebook32, degree, dev):
+    """the fp32 masters [n_kept, W] and [K, W] -> (n_kept, K)"""
+    W = volume_row_width(degree, False)
+    for t, what in ((kept32, "kept32"), (codebook32, "codebook32")):
+        _vol_f32(t, what)
+        if t.device != dev or t.dim() != 2 or int(t.shape[1]) != W:
+            raise ValueError(f"{what} {tuple(t.shape)}: [., {W}] on the rows' device")
+    K = int(codebook32.shape[0])
+    if K > VQ_MAX_CODES:
+        raise ValueError(f"K={K}: a codebook has at most {VQ_MAX_CODES} codes")
+    return int(kept32.shape[0]), K
+
+
+def volume_vq_expand(cls, rank, code, kept32, codebook32, degree, out=None, acc_coef_rows=None):
+    """Rule VQ-X: rule VQ-D in fp32 and without pads -- the fp32 rows [n, 3 ncoef] of the classes (cls, rank, code) from the fp32
+    masters kept32 [n_kept, W] and codebook32 [K, W]; whatever does not check out gives +0.  ``out``: the rows to overwrite (made when
+    None).  ``acc_coef_rows`` [n, W] int64 or None: the accumulator words of every row that receives +0 are zeroed
+    (nerf_hip_volume_vq_expand).  Enqueue only.  -> out"""
+    if degree not in (0, 1, 2):
+        raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+    n, n_coded = _vq_classes(cls, rank, code)
+    dev, W = cls.device, volume_row_width(degree, False)
+    n_kept, K = _vq_masters(kept32, codebook32, degree, dev)
+    out = torch.empty(n, W, device=dev) if out is None else _vol_f32(out, "coefficient rows", (n, W))
+    if acc_coef_rows is not None:
+        _vol_acc(acc_coef_rows, "acc_coef rows", (n, W))
+    ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_expand(ptr(cls), ptr(rank), n, ptr(code), n_coded, ptr(kept32), n_kept, ptr(codebook32), K,
+                                                    int(degree), ptr(out), ptr(acc_coef_rows), _stream(cls)))
+    return out
+
+
+def volume_vq_grad_reduce(acc_coef_rows, offset, member, acc_code):
+    """Rule VQ-G: the rows' int64 accumulator words acc_coef_rows [n, W] summed into their codes' acc_code [K, W] (ADDED IN PLACE) and
+    zeroed; the coded rows are given grouped by code, member [n_coded] int32 with offset [K + 1] int32 (device).  Integer adds: the same
+    bits whatever the order of the members or the launch (nerf_hip_volume_vq_grad_reduce).  Enqueue only.  -> acc_code"""
+    if acc_coef_rows.dim() != 2 or int(acc_coef_rows.shape[1]) not in (3, 12, 27):
+        raise ValueError(f"acc_coef rows {tuple(acc_coef_rows.shape)}: [n, 3 (degree + 1)^2]")
+    n, W = (int(x) for x in acc_coef_rows.shape)
+    _vol_acc(acc_coef_rows, "acc_coef rows", (n, W))
+    dev = acc_coef_rows.device
+    if acc_code.dim() != 2:
+        raise ValueError(f"acc_code {tuple(acc_code.shape)}: [K, {W}]")
+    K = int(acc_code.shape[0])
+    _vol_acc(acc_code, "acc_code", (K, W))
+    if K > VQ_MAX_CODES:
+        raise ValueError(f"K={K}: a codebook has at most {VQ_MAX_CODES} codes")
+    for t, what, shape in ((offset, "offset", (K + 1,)), (member, "member", None)):
+        if t.device != dev or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or (shape and tuple(t.shape) != shape):
+            raise ValueError(f"{what}: a contiguous int32 tensor {list(shape) if shape else '[n_coded]'} on the accumulators' device")
+    n_coded = int(member.shape[0])
+    if acc_code.device != dev:
+        raise ValueError("acc_code and the rows' accumulators live on different devices")
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_grad_reduce(ptr(acc_coef_rows), n, {3: 0, 12: 1, 27: 2}[W], ptr(offset), ptr(member), n_coded, K,
+                                                         ptr(acc_code), _stream(acc_coef_rows)))
+    return acc_code
+
+
+def volume_vq_adam_step(sigma_rows, kept32, kept_row, codebook32, degree, acc_sigma_rows, acc_coef_rows, acc_code, m, v, grad_scale, step,
+                        lr_sigma, lr_coef, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Rule VQ-V: one Adam step IN PLACE over the sigma word of every row (frozen support, lr_sigma), the words of the kept rows'
+    masters kept32 [n_kept, W] (their accumulators are those of the rows kept_row [n_kept] int32) and the words of codebook32 [K, W]
+    (accumulators acc_code [K, W]); every accumulator word read is zeroed; m, v [n + n_kept W + K W] fp32 hold the moments in that
+    order (nerf_hip_volume_vq_adam_step).  Enqueue only."""
+    if degree not in (0, 1, 2):
+        raise ValueError(f"degree={degree!r}: 0, 1 or 2")
+    sigma_rows = _vol_f32(sigma_rows, "sigma rows")
+    if sigma_rows.dim() != 1:
+        raise ValueError(f"sigma rows {tuple(sigma_rows.shape)}: [n]")
+    n, W, dev = int(sigma_rows.shape[0]), volume_row_width(degree, False), sigma_rows.device
+    n_kept, K = _vq_masters(kept32, codebook32, degree, dev)
+    if kept_row.device != dev or kept_row.dtype != torch.int32 or tuple(kept_row.shape) != (n_kept,) or not kept_row.is_contiguous():
+        raise ValueError(f"kept_row: a contiguous int32 device tensor [{n_kept}]")
+    _vol_acc(acc_sigma_rows, "acc_sigma rows", (n,))
+    _vol_acc(acc_coef_rows, "acc_coef rows", (n, W))
+    _vol_acc(acc_code, "acc_code", (K, W))
+    words = n + (n_kept + K) * W
+    m = _vol_f32(m, "m", (words,))
+    v = _vol_f32(v, "v", (words,))
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    _abi.check(_abi.lib().nerf_hip_volume_vq_adam_step(ptr(sigma_rows), n, ptr(kept32), ptr(kept_row), n_kept, ptr(codebook32), K, int(degree),
+                                                       ptr(acc_sigma_rows), ptr(acc_coef_rows), ptr(acc_code), ptr(m), ptr(v),
+                                                       float(grad_scale), int(step), float(lr_sigma), float(lr_coef), float(beta1),
+                                                       float(beta2), float(eps), _stream(sigma_rows)))

@@ -582,7 +582,8 @@ class NeRFRunner:
 
     def bake_volume(self, res, lo=(-1.5,) * 3, hi=(1.5,) * 3, degree=2, sigma_min=0.0, block=8, save=True, preview=None, finetune=0,
                     finetune_batch=4096, finetune_lr=None, finetune_tv=None, finetune_upsample=(), finetune_prune=None, compact=None,
-                    finetune_compact=False, vq=None, vq_iters=10, vq_prune=None, vq_keep=0.0):
+                    finetune_compact=False, vq=None, vq_iters=10, vq_prune=None, vq_keep=0.0, vq_finetune=0, vq_finetune_batch=4096,
+                    vq_lr_sigma=None, vq_lr_coef=None):
         """The current model baked into an SH radiance volume on a res^3 (or res = (nx, ny, nz)) lattice over the box [lo, hi]
         (NeRFModel.bake_volume: exact fp32; volume.py) -> the volume.Volume.  save: writes it with volume.save to
         ``<results_path><start_time>_<last_iter>_volume<res>.npz``.  preview: None, or "train" / "val" / "test" -- every view of that
@@ -615,7 +616,13 @@ class NeRFRunner:
         ``<the compact file's stem>_vq<K>.npz``.  One ``[VOLUME] ... vq`` line prints the class counts and the byte counts; with
         preview the split is also rendered from the DEQUANTIZED volume and both PSNR / SSIM pairs against the ground-truth images are
         printed.  The return value stays the compact volume; self.last_volume_vq holds the numbers and the path.  vq = None computes,
-        prints and writes nothing new."""
+        prints and writes nothing new.
+        VQ FINE-TUNING (volume.finetune_vq): vq_finetune = ITERS > 0 (needs vq: ValueError) then trains the
+        VQVolume's codebook, kept rows and sigma for ITERS Adam steps of vq_finetune_batch rays (at most 2^20) against the TRAIN
+        split's own pixels, the codes frozen (vq_lr_sigma / vq_lr_coef: None, or VQFinetuner's rates), and, with save, writes the tuned
+        VQVolume beside the untuned file as ``<...>_vq<K>_ft<ITERS>.npz``.  The vq line and self.last_volume_vq gain the first and the
+        last batch loss (first_loss, last_loss, finetune_iters, finetune_seconds, finetune_path) and, with preview, the tuned PSNR /
+        SSIM (psnr_vq_ft, ssim_vq_ft).  vq_finetune = 0 computes, prints and writes nothing new."""
         import numpy as np
 
         from . import volume
@@ -637,6 +644,12 @@ class NeRFRunner:
             from .volume import _check_k, _share
             vq, vq_iters = _check_k(vq, vq_iters)
             _share(vq_keep, "vq_keep"), (None if vq_prune is None else _share(vq_prune, "vq_prune"))
+        if isinstance(vq_finetune, bool) or int(vq_finetune) != vq_finetune or vq_finetune < 0:
+            raise ValueError(f"vq_finetune={vq_finetune!r}: a number of steps >= 0")
+        if vq_finetune and vq is None:
+            raise ValueError("vq_finetune trains the quantised form: it needs vq = K")
+        if vq_finetune and not 1 <= int(vq_finetune_batch) <= volume.VQ_MAX_RAYS:
+            raise ValueError(f"vq_finetune_batch={vq_finetune_batch!r}: 1 .. 2^20 rays per step")
         ctag = "" if compact is None else {"fp32": "_c32", "fp16": "_c16"}[compact]
         shape = grid_shape(res)
         tv = (0.0, 0.0) if finetune_tv is None else tuple(float(w) for w in finetune_tv)
@@ -773,6 +786,20 @@ class NeRFRunner:
                 scores = (f", {preview} views vs ground truth [PSNR] compact {was[0]:.3f} dB dequantized {now[0]:.3f} dB [SSIM] compact "
                           f"{was[1]:.4f} dequantized {now[1]:.4f}")
                 self.last_volume_vq.update(psnr_compact=was[0], psnr_vq=now[0], ssim_compact=was[1], ssim_vq=now[1])
+            tuned = None
+            if vq_finetune:
+                t1 = time.perf_counter()
+                vq_lrs = {k: float(x) for k, x in (("lr_sigma", vq_lr_sigma), ("lr_coef", vq_lr_coef)) if x is not None}
+                tuned, vq_losses = volume.finetune_vq(vqv, tr, self.K_inv, int(vq_finetune), batch=int(vq_finetune_batch), **vq_lrs)
+                vq_losses = vq_losses.cpu().numpy()
+                self.last_volume_vq.update(finetune_iters=int(vq_finetune), first_loss=float(vq_losses[0]), last_loss=float(vq_losses[-1]),
+                                           finetune_seconds=time.perf_counter() - t1, finetune_path=None)
+                scores += (f", vq finetune {int(vq_finetune)} steps of {int(vq_finetune_batch)} train rays: batch loss {vq_losses[0]:.3e} -> "
+                           f"{vq_losses[-1]:.3e}")
+                if preview is not None:
+                    ft = truth_scores(volume.dequantize(tuned))
+                    scores += f" [PSNR] tuned {ft[0]:.3f} dB [SSIM] tuned {ft[1]:.4f}"
+                    self.last_volume_vq.update(psnr_vq_ft=ft[0], ssim_vq_ft=ft[1])
             print(f"[VOLUME] {self.last_iter} vq {self.last_volume_vq['K']} codes, {vq_iters} iterations over {tr.pic_num} train views: "
                   f"{counts[0]} rows pruned, {counts[1]} coded, {counts[2]} kept, {volume.nbytes(vqv)} bytes (compact {volume.nbytes(vol)} bytes)"
                   f"{scores}, {seconds:.2f} s")
@@ -784,6 +811,9 @@ class NeRFRunner:
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                 volume.save(path, vqv)
                 self.last_volume_vq["path"] = path
+                if tuned is not None:
+                    volume.save(path[:-4] + f"_ft{int(vq_finetune)}.npz", tuned)
+                    self.last_volume_vq["finetune_path"] = path[:-4] + f"_ft{int(vq_finetune)}.npz"
         return vol
 
     def extract_mesh(self, res, level, lo=(-1.5,) * 3, hi=(1.5,) * 3, color=True, save=True, normals="grid", band=None, min_faces=None,

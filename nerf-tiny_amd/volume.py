@@ -35,6 +35,11 @@ together into a VQVolume and ``dequantize`` decodes that back to a CompactVolume
 SMALL (a bit mask, fp32 sigma, one class byte and at most one uint16 code per row, a codebook); on the device it is decoded before
 anything reads it -- sample, render and the training calls refuse it (TypeError) -- so device memory is NOT reduced by it.
 
+VQ FINE-TUNING (rules VQ-X, VQ-G and VQ-V).  ``VQFinetuner`` / ``finetune_vq`` are VQRF's fourth step: the
+codebook, the kept rows and sigma of a VQVolume trained jointly against rays with the assignments frozen.  The march and its gradient
+are the compact ones over fp32 rows expanded from the masters; the rows' int64 accumulators are summed per code, exactly, and one Adam
+launch updates the three kinds of parameter.  ``VQFinetuner.volume()`` is a VQVolume again: the file stays as small as it was.
+
 Everything runs on the device; a CPU tensor raises: there is no CPU path.
 """
 from __future__ import annotations
@@ -85,7 +90,8 @@ def _no_vq(vol, what):
     """a VQVolume is a file form: nothing marches, samples or trains it"""
     if isinstance(vol, VQVolume):
         raise TypeError(f"{what} does not read a VQVolume: it is the small FILE form -- volume.dequantize(vq) gives the CompactVolume "
-                        "(fp16 rows) that is sampled, rendered and trained")
+                        "(fp16 rows) that is sampled, rendered and trained; volume.VQFinetuner / finetune_vq train the quantised form "
+                        "itself (the codebook, the kept rows and sigma)")
     return vol
 
 
@@ -862,6 +868,107 @@ def dequantize(vq):
     sigma, _ = ops.volume_compact_unpack(vq.sigma, None, vq.point, vq.shape, vq.degree)
     return CompactVolume(slot, vq.sigma, rows, blocks(sigma, vq.block), np.asarray(vq.lo, np.float32), np.asarray(vq.step, np.float32),
                          vq.block, vq.degree, tuple(vq.shape))
+
+
+# ---- fine-tuning the quantised form (rules VQ-X, VQ-G and VQ-V of include/nerf_hip.h) ----
+
+VQ_MAX_RAYS = ops.VQ_MAX_RAYS  # rule VQ-G's overflow precondition: the rays of one update
+
+
+def _vq_rank(cls):
+    """rank [n] int32: a row's rank among the rows of its class, in row order (0 for a pruned row), as dequantize forms it"""
+    coded, kept = cls == 1, cls == 2
+    return torch.where(coded, torch.cumsum(coded, 0) - 1, torch.where(kept, torch.cumsum(kept, 0) - 1, 0)).to(torch.int32).contiguous()
+
+
+def vq_members(cls, code, K):
+    """The coded rows GROUPED BY CODE, as rule VQ-G reads them -> (offset [K + 1] int32, member [n_coded] int32): a stable sort of the
+    codes, so the members of a code are in row order; offset is the exclusive prefix sum of the codes' counts.  A code >= K sorts
+    past offset[K] and belongs to no group.  Exact integer plumbing, as vq_classes: it runs wherever cls lives."""
+    rows = torch.nonzero(cls == 1).reshape(-1)
+    c = code.to(torch.int64)
+    if tuple(c.shape) != tuple(rows.shape):
+        raise ValueError(f"code {tuple(code.shape)}: one per coded row ({int(rows.shape[0])})")
+    order = torch.sort(c, stable=True)[1]
+    counts = torch.bincount(c, minlength=int(K))[:int(K)]
+    offset = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int32)
+    return offset.contiguous(), rows[order].to(torch.int32).contiguous()
+
+
+class VQFinetuner:
+    """VQRF's fourth step (rules VQ-X, VQ-G and VQ-V): Adam on the CODEBOOK, the KEPT ROWS and SIGMA of a
+    VQVolume against rays, the classes and the codes frozen.  It holds fp32 masters widened from the fp16 codebook and kept rows
+    (exact), a working CompactVolume with fp32 rows expanded from them (the slots from ``point``, occ from sigma, as dequantize builds
+    them) that the compact march and its gradient read, the per-row accumulators, one int64 accumulator row per code, the member lists
+    (built once: the codes are frozen) and the moments -- per coded row 8 bytes of moments (its sigma) where CompactFinetuner holds
+    8 (1 + W).  With every code holding one row, or every row kept, each step equals CompactFinetuner(dequantize(vq))'s bit for bit.
+    No TV prior: VQRF uses none here."""
+
+    def __init__(self, vq, lr_sigma=0.1, lr_coef=0.01, betas=(0.9, 0.999), eps=1e-8):
+        if not isinstance(vq, VQVolume):
+            raise TypeError("volume.VQFinetuner takes a VQVolume (volume.quantize gives one; CompactFinetuner trains a CompactVolume)")
+        dev = _on_device(vq.point, "volume.VQFinetuner").device
+        words = 3 * (vq.degree + 1) ** 2
+        self.vq = vq
+        self.cls, self.code, self.rank = vq.cls.contiguous(), vq.code.contiguous(), _vq_rank(vq.cls)
+        self.kept32 = vq.kept[:, :words].to(torch.float32).contiguous()
+        self.codebook32 = vq.codebook[:, :words].to(torch.float32).contiguous()
+        n, n_kept, K = int(vq.sigma.shape[0]), int(self.kept32.shape[0]), int(self.codebook32.shape[0])
+        sigma_rows = vq.sigma.detach().clone()
+        rows = ops.volume_vq_expand(self.cls, self.rank, self.code, self.kept32, self.codebook32, vq.degree)
+        sigma, _ = ops.volume_compact_unpack(sigma_rows, None, vq.point, vq.shape, vq.degree)
+        self.cvol = CompactVolume(ops.volume_compact_slots(vq.point, vq.shape), sigma_rows, rows, blocks(sigma, vq.block),
+                                  np.asarray(vq.lo, np.float32), np.asarray(vq.step, np.float32), vq.block, vq.degree, tuple(vq.shape))
+        self.kept_row = torch.nonzero(self.cls == 2).reshape(-1).to(torch.int32).contiguous()
+        self.offset, self.member = vq_members(self.cls, self.code, K)
+        self.grad = compact_grad_buffers(self.cvol)
+        self.acc_code = torch.zeros(K, words, dtype=torch.int64, device=dev)
+        self.m = torch.zeros(n + (n_kept + K) * words, device=dev)
+        self.v = torch.zeros_like(self.m)
+        self.lr_sigma, self.lr_coef, self.betas, self.eps = float(lr_sigma), float(lr_coef), (float(betas[0]), float(betas[1])), float(eps)
+        self.steps = 0
+
+    def step(self, origins, dirs, tmin, tmax, target, background=(0.0, 0.0, 0.0), dt=None, t_stop=1e-3):
+        """render the working rows -> the gradient of the batch's MSE into the rows' accumulators (rule VCG with 2 diff) -> the coded
+        rows' words summed per code (VQ-G) -> one Adam launch over sigma, the kept rows and the codebook with grad_scale = 1 / (3 N)
+        (VQ-V) -> the working rows rebuilt from the masters (VQ-X).  At most 2^20 rays (rule VQ-G's overflow precondition: ValueError);
+        pixels and background are colours in [0, 1].  -> the batch's MSE before the update, a device scalar (no host sync)."""
+        c, dev = self.cvol, self.cvol.slot.device
+        if int(torch.as_tensor(origins).numel()) // 3 > VQ_MAX_RAYS:
+            raise ValueError(f"volume.VQFinetuner.step: {int(torch.as_tensor(origins).numel()) // 3} rays -- one update takes at most 2^20 "
+                             "(the int64 sums of a code's gradient are proved not to overflow up to there)")
+        rgb, _, _ = render(c, origins, dirs, tmin, tmax, dt=dt, t_stop=t_stop, background=background)
+        diff = rgb - torch.as_tensor(target).to(dev, torch.float32).reshape(-1, 3)
+        n = max(int(rgb.shape[0]), 1)
+        compact_render_backward(c, self.grad, origins, dirs, tmin, tmax, 2.0 * diff, None, dt=dt, t_stop=t_stop, background=background)
+        ops.volume_vq_grad_reduce(self.grad.acc_coef, self.offset, self.member, self.acc_code)
+        self.steps += 1
+        ops.volume_vq_adam_step(c.sigma, self.kept32, self.kept_row, self.codebook32, c.degree, self.grad.acc_sigma, self.grad.acc_coef,
+                                self.acc_code, self.m, self.v, 1.0 / (3.0 * n), self.steps, self.lr_sigma, self.lr_coef, self.betas[0],
+                                self.betas[1], self.eps)
+        ops.volume_vq_expand(self.cls, self.rank, self.code, self.kept32, self.codebook32, c.degree, out=c.coef, acc_coef_rows=self.grad.acc_coef)
+        return (diff * diff).mean() if rgb.numel() else torch.zeros((), device=dev)
+
+    def volume(self):
+        """The current state as a VQVolume: the same point, cls and code, the current sigma (a copy), the codebook and the kept rows
+        rounded to fp16 ONCE with quantize's rule.  A row whose sigma reached 0 keeps its class; the file format does not change."""
+        vq = self.vq
+        return vq._replace(sigma=self.cvol.sigma.detach().clone(), kept=_rows_to_half(self.kept32, vq.degree),
+                           codebook=_rows_to_half(self.codebook32, vq.degree))
+
+
+def finetune_vq(vq, rays, K_inv, iters, batch=4096, seed=None, background=(0.0, 0.0, 0.0), **lrs):
+    """``finetune_compact`` with a VQFinetuner: the same batches for the same seed (finetune's own loop), no schedule -- a VQ volume is
+    not refined -- -> (the fine-tuned VQVolume, the batch losses [iters] on the device).  lrs: VQFinetuner's keywords."""
+    if not isinstance(vq, VQVolume):
+        raise TypeError("volume.finetune_vq takes a VQVolume (volume.quantize gives one)")
+    dev = _on_device(vq.point, "volume.finetune_vq").device
+    if int(iters) != iters or int(iters) < 0:
+        raise ValueError(f"iters={iters!r}: a number of steps >= 0")
+    if int(batch) > VQ_MAX_RAYS:
+        raise ValueError(f"batch={batch!r}: one update takes at most 2^20 rays")
+    tuner, losses = _finetune_loop(VQFinetuner(vq, **lrs), rays, K_inv, iters, batch, seed, background, (), None, dev)
+    return tuner.volume(), losses
 
 
 def _save_vq(path, vq):
